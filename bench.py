@@ -11,7 +11,11 @@ records.  Inputs are already in HBM when the timed region starts.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  `--dry-run-gloo` exercises only the sharding + gather
+Prints ONE JSON line on rank 0: the headline (metric, value, unit, ms_per_step, dtype, config).
+`--full` adds what takes instrumentation or runs of its own: per-kernel event timers and rooflines,
+stage times, the isolated passes, the CPU baseline and the extra legs (fp32 MFMA, front end,
+outlier / trained-like weights, configs[3]).  `--dump-outputs DIR` writes the ids and id counts of
+the last timed step as DIR/*.npy (float64).  `--dry-run-gloo` exercises only the sharding + gather
 plumbing on CPU (world_size-2 gloo test in tests/test_distributed.py).
 """
 from __future__ import annotations
@@ -19,6 +23,7 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import shutil
 import sys
 import tempfile
 import time
@@ -281,7 +286,14 @@ def main() -> None:
     ap.add_argument("--report-maps", action="store_true", help="add the libamdhip64 files this process has mapped to the line")
     ap.add_argument("--rehearse-nccl", action="store_true",
                     help="single rank: create the RCCL communicator and run the N > 1 collectives anyway")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: kernel event timers and rooflines, stage times, "
+                         "isolated passes, CPU baseline and the extra legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's ids and id counts as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.dry_run_gloo:
         dry_run_gloo(args)
         return
@@ -341,9 +353,9 @@ def main() -> None:
         eng.set_option("gemm_variant", args.gemm_variant)
     if args.bf16:
         eng.set_option("bf16", 1)
-    # per-launch HIP event pairs on every 4th encoder pass of the timed region (an event pair per launch on every
-    # pass costs ~1 % of the pipeline period)
-    eng.set_option("kernel_timers", 4 if args.kernel_timers is None else args.kernel_timers)
+    # --full: per-launch HIP event pairs on every 4th encoder pass of the timed region (an event pair per launch on every
+    # pass costs ~1 % of the pipeline period); the headline alone runs without them
+    eng.set_option("kernel_timers", (4 if args.full else 0) if args.kernel_timers is None else args.kernel_timers)
     eng.set_option("stop_at_eot", 0)  # full-length decode: 30 positions, 27 argmax steps
     B = args.batch
     lo, hi = shard_range(rank, world, world * B)
@@ -460,7 +472,7 @@ def main() -> None:
     gathered.update(collectives=0, records=0, crc=0, digest=0)  # count the timed region only
     fence()
     t0 = time.perf_counter()
-    ids, n, rec = run_steps(args.steps, accumulate)
+    ids, n, rec = run_steps(args.steps, accumulate if args.full else None)
     fence()
     elapsed = time.perf_counter() - t0
     timed = dict(gathered)
@@ -468,11 +480,20 @@ def main() -> None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the ids ([clip][32], zero after the count) and the
+        # id counts of this rank's batch; at N > 1 also the gathered records of that step ([global clip][32 ids + count])
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "ids.npy"), np.asarray(ids, np.float64))
+        np.save(os.path.join(args.dump_outputs, "n_ids.npy"), np.asarray(n, np.float64))
+        if world > 1:
+            last = rec.reshape(world, -1, B, ID_STRIDE + 1)[:, -1].reshape(world * B, ID_STRIDE + 1)
+            np.save(os.path.join(args.dump_outputs, "records.npy"), last.astype(np.float64))
 
     # the same pipeline with every ENCODER contraction on the fp32 MFMA instruction (reported beside
     # the headline, outside the timed region, so the effect of the plane kernels is visible)
     fp32_leg = None
-    if pipelined and args.gemm_variant is None and args.attn_variant is None and not args.no_fp32_leg and not args.bf16:
+    if args.full and pipelined and args.gemm_variant is None and args.attn_variant is None and not args.no_fp32_leg and not args.bf16:
         eng.set_option("gemm_variant", 0)
         eng.set_option("attn_variant", 0)
         run_steps(3)
@@ -506,7 +527,7 @@ def main() -> None:
     # second number of SURVEY 8(d): the same pipeline fed with device-resident PCM, i.e. with the log-mel
     # front end (whisper.cpp:109-216) inside every step; PCM ~ N(0, 0.1^2) clipped to [-1, 1]
     with_frontend = None
-    if pipelined and not args.no_fp32_leg and not args.bf16:
+    if args.full and pipelined and not args.no_fp32_leg and not args.bf16:
         pcm_host = np.clip(np.random.default_rng([MEL_SEED, 7]).normal(0.0, 0.1, size=(B, eng.pcm_len)), -1, 1).astype(np.float32)
         d_pcm = eng.device_array(pcm_host)
         eng.device_synchronize()
@@ -541,7 +562,7 @@ def main() -> None:
                          "input": "PCM [32][480000] resident in HBM, N(0, 0.1^2) clipped"}
         d_pcm.free()
 
-    legs_ok = pipelined and world == 1 and not args.no_fp32_leg and not args.bf16 and args.arch == "tiny" \
+    legs_ok = args.full and pipelined and world == 1 and not args.no_fp32_leg and not args.bf16 and args.arch == "tiny" \
         and args.gemm_variant is None and args.attn_variant is None
 
     # What trained-like weight statistics cost: the same workload on weights whose layer-0 value projection has one
@@ -630,7 +651,7 @@ def main() -> None:
         return c3_leg
 
     iso = None
-    if pipelined:
+    if args.full and pipelined:
         # outside the timed region: two synchronous passes, so the per-kernel figures are also
         # reported without the encoder and the decoders sharing the chip
         iso_stats = {}
@@ -725,6 +746,9 @@ def main() -> None:
                                   "fp32 accumulate (measured error at or below the fp32-MFMA kernel's, tests/test_gpu_kernels.py; "
                                   "bf16 x3 split and fp32 MFMA forms selectable); residual streams, softmax, LayerNorm fp32; decoder "
                                   "cross-attention on the encoder output's planes with the K / V projections absorbed (no KV cache)"},
+        }
+        # --full: what the headline does not need (event timers, isolated passes, stage events, legs, CPU baseline)
+        full = {
             "roofline": ({**roof, "isolated": {k: iso_det[dom][k] for k in ("achieved", "frac", "avg_launch_us")},
                           "note": "achieved/avg_launch_us: HIP events inside the timed (pipelined) region, where decoder "
                                   "chains share the chip; isolated: the same launches in two synchronous passes after it — "
@@ -760,6 +784,8 @@ def main() -> None:
             "stage_ms_per_step": stage,
             "host_enqueue_ms_per_step": round(1e3 * host["submit_s"] / max(1, host["submits"]), 3) if pipelined else None,
         }
+        if args.full:
+            out.update(full)
         out["collectives"] = timed["collectives"]
         if args.report_maps:
             with open("/proc/self/maps") as f:
@@ -768,7 +794,7 @@ def main() -> None:
             out["gathered_records"] = timed["records"]
             out["ids_crc"] = timed["crc"]
             out["ids_digest"] = timed["digest"]
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             info = eng.vocab_info()
             prompt = [info["sot"], 50259 + eng.get_option("language"), info["transcribe"], info["not"]]
             cb = cpu_baseline(prefix, mel_host, prompt, info["eot"])
@@ -783,6 +809,7 @@ def main() -> None:
             out["configs3_bf16_base"] = run_c3_leg()
         print(json.dumps(out))
     eng.close()
+    shutil.rmtree(tmp, ignore_errors=True)
     if world > 1 or FORCE_COLLECTIVES:
         dist.barrier()
         dist.destroy_process_group()

@@ -483,7 +483,7 @@ def test_bench_rccl_branch_executes_on_one_rank(tmp_path):
     barrier, all_reduce of the elapsed time) executed on ONE rank in a fresh child process, so that the driver's
     8-GPU run is not the first time it runs.  Ids must equal those of the same run without collectives."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29541", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "9", "--warmup", "1",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "9", "--warmup", "1", "--full",
             "--no-cpu-baseline", "--no-fp32-leg", "--emit-ids"]
     r1 = subprocess.run(base + ["--rehearse-nccl"], capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert r1.returncode == 0, r1.stderr[-3000:]
@@ -495,6 +495,26 @@ def test_bench_rccl_branch_executes_on_one_rank(tmp_path):
     assert a["n_gpus"] == 1 and a["steps"] == 9 and a["value"] > 0 and a["unit"] == "audio-sec/s"
     assert a["gathered_records"] == 32 * 9 and a["ids_crc"] == b["ids_crc"]
     assert "roofline" in a and "config" in a
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline only and, with --dump-outputs, writes the ids and id counts of its last
+    timed step: every clip decoded to full length (4 prompt ids + 27 argmax steps), ids inside the vocabulary."""
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    a = json.loads(r.stdout.strip().splitlines()[-1])
+    assert a["steps"] == 3 and a["warmup"] == 1 and a["value"] > 0 and a["ms_per_step"] > 0
+    assert a["unit"] == "audio-sec/s" and a["higher_is_better"] is True and a["dtype"].startswith("f32")
+    assert abs(a["value"] - 32 * 30.0 / (a["ms_per_step"] * 1e-3)) < 1e-2 * a["value"]
+    for key in ("roofline", "cpu_baseline", "encoder_fp32_mfma", "with_frontend", "configs3_bf16_base"):
+        assert key not in a
+    ids, n = np.load(out / "ids.npy"), np.load(out / "n_ids.npy")
+    assert ids.dtype == np.float64 and ids.shape == (32, 32) and n.dtype == np.float64 and n.shape == (32,)
+    assert (n == 31).all() and (ids[:, :31] >= 0).all() and (ids < 51865).all() and (ids[:, 31] == 0).all()
+    assert (ids == np.round(ids)).all()
 
 
 def test_bench_two_ranks_share_the_gpu_and_the_gather_cadence(tmp_path):

@@ -6,11 +6,11 @@ run() { # label, env..., args...
 }
 for i in 1 2; do
   for r in 8 6 5 4 3; do
-    run "reserve=$r" WT_ENC_CU_RESERVE=$r python bench.py --gpus 1 --steps 80 --no-cpu-baseline --no-fp32-leg 2>/dev/null
+    run "reserve=$r" WT_ENC_CU_RESERVE=$r python bench.py --full --gpus 1 --steps 80 --no-cpu-baseline --no-fp32-leg 2>/dev/null
   done
 done
 for i in 1 2; do
   for c in 0 1 2 3 4 6 8; do
-    run "abs_chunks=$c" python bench.py --gpus 1 --steps 80 --abs-chunks $c --no-cpu-baseline --no-fp32-leg 2>/dev/null
+    run "abs_chunks=$c" python bench.py --full --gpus 1 --steps 80 --abs-chunks $c --no-cpu-baseline --no-fp32-leg 2>/dev/null
   done
 done

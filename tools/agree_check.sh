@@ -2,7 +2,7 @@
 set -o pipefail
 root=$PWD; out=$root/gpurun_out; tag=${1:-r04_agree}
 cd /tmp && export TMPDIR=/tmp && cd $root
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag} -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-leg > $out/${tag}_bench.json 2> $out/${tag}_bench.err || { tail -5 $out/${tag}_bench.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag} -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-leg > $out/${tag}_bench.json 2> $out/${tag}_bench.err || { tail -5 $out/${tag}_bench.err; exit 1; }
 python3 - <<PY
 import csv, glob, json
 d = json.loads(open("$out/${tag}_bench.json").read().strip().splitlines()[-1])

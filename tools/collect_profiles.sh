@@ -14,8 +14,8 @@ root=$PWD
 out=$root/gpurun_out
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $root
-BENCH="bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-fp32-leg $extra"
-SERIAL="bench.py --steps 2 --warmup 1 --no-pipeline --no-cpu-baseline --no-fp32-leg $extra"
+BENCH="bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-fp32-leg $extra"
+SERIAL="bench.py --full --steps 2 --warmup 1 --no-pipeline --no-cpu-baseline --no-fp32-leg $extra"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_stats -- python3 $BENCH > $out/${tag}_prof_bench.json 2> $out/${tag}_prof_bench.err || exit 1
 cp $out/prof_${tag}_stats/*/*_kernel_stats.csv $out/${tag}_bench_default_kernel_stats.csv
 python3 tools/prof_summary.py $out/prof_${tag}_stats 39 > $out/${tag}_kernel_summary.txt

@@ -41,7 +41,7 @@ print(json.dumps({
     "fabric_read_bytes_per_launch": rd,
     "fabric_write_bytes_per_launch": wr,
     "traffic_bytes_per_launch": rd + wr,
-    "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --steps 2 --warmup 1 "
+    "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --full --steps 2 --warmup 1 "
               "--no-pipeline --no-cpu-baseline`; bytes = 2*1024*FETCH_SIZE + 1024*WRITE_SIZE (gfx950 FETCH_SIZE counts half "
               "of a wide coalesced read, MI355X_MICROARCH.md HBM section; calibrated on layernorm_rows). The counters sit on "
               "the L2's fabric side, so Infinity-Cache hits are included: L2-miss traffic, an upper bound on HBM traffic.",
