@@ -135,7 +135,9 @@ struct EncDec : public Engine {
   // Pads/truncates the CALLER's vector to 480000 samples like the reference (whisper.cpp:753).
   std::string transcribe(std::vector<float>& samples) final;
   std::string transcribe(const char* waveFile) final;
-  wt_engine* handle() const { return handle_; }  // for the batch entry points of wt_capi.h
+  // for the batch entry points and options of wt_capi.h: wt_engine_set_option(handle(), "beam_size", 5) makes both
+  // transcribe() overloads decode with beam search
+  wt_engine* handle() const { return handle_; }
 
  private:
   wt_engine* handle_ = nullptr;

@@ -94,6 +94,14 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * pipelined batches of equal size <= 32 share one decoder chain; change only with nothing in flight), "dec_group" (2 =
  * default, 3 or 4: that many consecutive batches per chain, rows = group x batch <= 128; three or four want 3 x group + 4
  * or more batches in flight and pay off on long jobs only: +1 % at four),
+ * Decoding: "beam_size" (1 = default: the reference's greedy argmax, unchanged; 2..8 = beam search with that many
+ * hypotheses per clip on every synchronous entry point: per step each live hypothesis offers its top beam_size + 1 tokens
+ * by log-softmax over the full vocabulary, the candidates are taken by sum of log-probabilities, an EOT candidate
+ * finishes its hypothesis, a clip is done with beam_size finished ones, and the result is the finished hypothesis with
+ * the best sum / generated ids (EOT included), DESIGN.md section 11.  Deliberate scope cuts, WT_ERR_UNSUPPORTED with
+ * beam_size > 1: the pipelined wt_pipeline_submit* calls, the bf16 storage mode, cross_absorb = 0 (and weights or a
+ * gemm_variant without the absorbed form), stop_at_eot = 0, the forced-ids debug tap and the logits tap of
+ * wt_encdec_debug_batch),
  * "last_batches" (N = the next N pipelined submits are the last of a job: they are decoded one chain per batch, the very
  * last on the encoder's stream, so the pipeline drains sooner; counts down to 0 by itself, may be set with batches in
  * flight), "force_fallback" (test hook: bit mask of contractions sent to the full-range kernels, nothing in flight).
@@ -173,6 +181,12 @@ int wt_encdec_debug_batch(wt_engine* h, const float* mel, int batch, int64_t* id
                           float* enc_out, float* logits, int logits_steps_cap);
 
 int wt_last_timings(const wt_engine* h, wt_timings* out);
+
+/* Beam search (option "beam_size" > 1): for every clip of the last synchronous beam call, the chosen hypothesis's sum of
+ * natural-log probabilities and its number of generated ids, EOT included (at most cap entries written).  Returns the
+ * clip count, or -WT_ERR_INVALID_ARG when the last synchronous decode was not a beam search (negative, so that it cannot
+ * be taken for a count of one clip). */
+int wt_last_beam_scores(const wt_engine* h, float* sum_logprob, int32_t* n_generated, int cap);
 
 /* Per-kernel-class device time of the encoder phase of the last batch call: HIP event pairs
  * recorded on the engine's stream around every launch of the class.  flops / bytes are the

@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Beam-search costs on one MI355X, synthetic tiny weights:
+  * single-clip transcribe latency (wt_transcribe_pcm) at beam_size 1 and K;
+  * audio-sec/s of wt_encdec_tokens_batch_dev at beam_size K with 25 and 64 clips (and greedy beside it).
+Every GPU step runs in a child process of its own under a time limit; the parent only collects the JSON lines.
+
+  python tools/beam_bench.py [--beam 5] [--iters 10] [--only CASE]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def child(case: str, beam: int, iters: int, tmp: str) -> dict:
+    sys.path.insert(0, ROOT)
+    import __graft_entry__ as ge
+    pkg = ge.load_package()
+    prefix, vocab = ge._assets(tmp, "tiny", 0)
+    eng = pkg.Engine(prefix, vocab, True)
+    eng.set_option("beam_size", beam)
+    rng = np.random.default_rng(1234)
+    if case == "latency":
+        pcm = (0.1 * rng.standard_normal(eng.pcm_len)).astype(np.float32)
+        for _ in range(3):
+            eng.transcribe(pcm)
+        t = []
+        for _ in range(iters):
+            t0 = time.perf_counter()
+            eng.transcribe(pcm)
+            t.append(time.perf_counter() - t0)
+        out = {"case": "transcribe_latency_ms", "beam_size": beam, "median": 1e3 * float(np.median(t)),
+               "min": 1e3 * float(np.min(t))}
+    else:
+        batch = int(case)
+        mel = rng.uniform(-1.0, 1.5, size=(batch,) + eng.mel_shape).astype(np.float32)
+        d = ctypes_dev(pkg, eng, mel)
+        for _ in range(3):
+            eng.encdec_tokens_batch_dev(d, batch)
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            eng.encdec_tokens_batch_dev(d, batch)
+        dt = (time.perf_counter() - t0) / iters
+        tm = eng.timings()
+        out = {"case": "encdec_tokens_batch_dev", "beam_size": beam, "batch": batch, "ms_per_call": 1e3 * dt,
+               "audio_sec_per_s": batch * 30.0 / dt, "decoder_ms": tm.decoder_ms}
+    eng.close()
+    return out
+
+
+def ctypes_dev(pkg, eng, a):
+    import ctypes
+    p = ctypes.c_void_p()
+    L = pkg.lib()
+    assert L.wt_device_alloc(eng.handle, ctypes.c_size_t(a.nbytes), ctypes.byref(p)) == 0
+    assert L.wt_device_upload(eng.handle, p, 0, a.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(a.nbytes)) == 0
+    return p.value
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--beam", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--timeout", type=int, default=300, help="seconds per child")
+    ap.add_argument("--only", default=None, help="latency, 25 or 64")
+    ap.add_argument("--child", nargs=3, metavar=("CASE", "BEAM", "TMP"), help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        print(json.dumps(child(a.child[0], int(a.child[1]), a.iters, a.child[2])))
+        return 0
+    runs = [("latency", 1), ("latency", a.beam), ("25", 1), ("25", a.beam), ("64", 1), ("64", a.beam)]
+    if a.only:
+        runs = [r for r in runs if r[0] == a.only]
+    results = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for case, beam in runs:
+            cmd = [sys.executable, os.path.abspath(__file__), "--iters", str(a.iters), "--child", case, str(beam), tmp]
+            try:
+                p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
+            except subprocess.TimeoutExpired:
+                print(json.dumps({"case": case, "beam_size": beam, "error": "timeout"}))
+                return 124
+            if p.returncode != 0:
+                print(json.dumps({"case": case, "beam_size": beam, "error": p.returncode, "stderr": p.stderr[-2000:]}))
+                return 1  # nothing more on the GPU after a failed step
+            line = p.stdout.strip().splitlines()[-1]
+            print(line, flush=True)
+            results.append(json.loads(line))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -42,7 +42,7 @@ CAPI_SYMBOLS = [
     "wt_logmel_batch", "wt_logmel_batch_dev", "wt_encdec_tokens_batch",
     "wt_encdec_tokens_batch_dev", "wt_transcribe_tokens_batch_dev", "wt_pipeline_submit_dev", "wt_pipeline_submit_pcm_dev", "wt_pipeline_collect",
     "wt_encdec_debug_batch",
-    "wt_last_timings", "wt_last_kernel_stats", "wt_decode_text", "wt_language_id", "wt_lang_code", "wt_wav_read_legacy",
+    "wt_last_timings", "wt_last_beam_scores", "wt_last_kernel_stats", "wt_decode_text", "wt_language_id", "wt_lang_code", "wt_wav_read_legacy",
     "wt_vocab_info", "wt_filters", "wt_write_synthetic_weights", "wt_write_synthetic_vocab",
     "wt_vocab_open", "wt_vocab_close", "wt_vocab_get_info", "wt_vocab_get_filters", "wt_vocab_size", "wt_vocab_token",
     "wt_vocab_decode", "wt_log_mel_spectrogram", "wt_convert_tflite", "wt_shutdown",
@@ -118,6 +118,7 @@ def lib() -> ctypes.CDLL:
         L.wt_pipeline_collect.argtypes = [c_void_p, ip64, ip32]
         L.wt_encdec_debug_batch.argtypes = [c_void_p, fp, c_int, ip64, ip32, fp, fp, c_int]
         L.wt_last_timings.argtypes = [c_void_p, POINTER(Timings)]
+        L.wt_last_beam_scores.argtypes = [c_void_p, fp, ip32, c_int]
         L.wt_last_kernel_stats.argtypes = [c_void_p, POINTER(KernelStat), c_int]
         L.wt_decode_text.argtypes = [c_void_p, ip64, c_int, c_int, c_char_p, c_size_t, POINTER(c_size_t)]
         L.wt_language_id.argtypes = [c_char_p]
@@ -433,6 +434,17 @@ class Engine:
         t = Timings()
         self._check(lib().wt_last_timings(self._h, byref(t)))
         return t
+
+    def last_beam_scores(self):
+        """Beam search: (sum of log-probabilities float32 [B], generated ids incl. EOT int32 [B]) of the chosen hypothesis
+        of every clip of the last synchronous beam call."""
+        n = lib().wt_last_beam_scores(self._h, None, None, 0)
+        if n < 0:
+            raise WtError(-n, "the last synchronous decode was not a beam search")
+        sums = np.zeros(n, np.float32)
+        lens = np.zeros(n, np.int32)
+        lib().wt_last_beam_scores(self._h, _fp(sums), lens.ctypes.data_as(POINTER(c_int32)), n)
+        return sums, lens
 
     def kernel_stats(self) -> dict:
         arr = (KernelStat * 8)()

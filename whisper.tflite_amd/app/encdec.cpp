@@ -22,12 +22,13 @@ void usage(const char* argv0) {
             << "  --input         Path to the 16 kHz mono WAV        REQUIRED\n"
             << "  --lang          language code of the prompt (default de, as the reference hard-codes)\n"
             << "  --english       English-only vocabulary ids (multilingual = false; the reference hard-codes true)\n"
-            << "  --long          transcribe every 30 s window of the file, not only the first\n";
+            << "  --long          transcribe every 30 s window of the file, not only the first\n"
+            << "  --beam N        beam search with N hypotheses, 2..8 (default: greedy, as the reference)\n";
 }
 }  // namespace
 
 int main(int argc, char* argv[]) {
-  std::string model_prefix, vocab, input, lang;
+  std::string model_prefix, vocab, input, lang, beam;
   bool long_audio = false, english = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], v;
@@ -57,6 +58,7 @@ int main(int argc, char* argv[]) {
     else if (a == "--vocab") vocab = v;
     else if (a == "--input") input = v;
     else if (a == "--lang") lang = v;
+    else if (a == "--beam") beam = v;
     else {
       std::cerr << "The following argument was not expected: " << a << "\n";
       usage(argv[0]);
@@ -83,6 +85,14 @@ int main(int argc, char* argv[]) {
     const int id = language_id(lang);
     if (wt_engine_set_option(encdec.handle(), "language", id) != WT_OK) {
       std::cerr << "--lang: unknown language code " << lang << "\n";
+      return 105;
+    }
+  }
+  if (!beam.empty()) {
+    char* end = nullptr;
+    const long n = std::strtol(beam.c_str(), &end, 10);
+    if (end == beam.c_str() || *end || wt_engine_set_option(encdec.handle(), "beam_size", n) != WT_OK) {
+      std::cerr << "--beam: expected a beam size in [1, 8], got " << beam << "\n";
       return 105;
     }
   }

@@ -237,6 +237,9 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
   } else if (k == "kernel_timers") {
     if (value < 0 || value > 1024) return fail(h, WT_ERR_INVALID_ARG, "kernel_timers must be in [0, 1024]");
     e.kernel_timers = value;
+  } else if (k == "beam_size") {
+    if (value < 1 || value > wt::kBeamMax) return fail(h, WT_ERR_INVALID_ARG, "beam_size must be in [1, 8] (1 = greedy)");
+    e.beam_size = value;
   } else if (k == "bf16") {
     // bf16 storage mode (BASELINE configs[3]); the first switch reads the weight file again for the bf16 copies
     try {
@@ -277,6 +280,7 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "last_batches") *value = e.last_batches;
   else if (k == "cross_absorb_active") *value = e.absorb_active() ? 1 : 0;  // read-only
   else if (k == "bf16") *value = e.bf16;
+  else if (k == "beam_size") *value = e.beam_size;
   else if (k == "kernel_timers") *value = e.kernel_timers;
   else if (k == "fc2_ksplit") *value = e.fc2_ksplit;
   else if (k == "attn_variant") *value = e.attn_variant;
@@ -367,6 +371,20 @@ int wt_encdec_tokens_batch_dev(wt_engine* h, const float* d_mel, int batch, int6
       e.decode(batch, ids, n_ids, nullptr, 0);
       return;
     }
+    if (e.beam_size > 1) {  // beam search is synchronous: consecutive calls of up to 64 clips, their scores joined
+      std::vector<float> sums;
+      std::vector<int> lens;
+      for (int b0 = 0; b0 < batch; b0 += 64) {
+        const int nb = std::min(64, batch - b0);
+        e.encode(d_mel + size_t(b0) * e.mel_elems(), nb);
+        e.decode(nb, ids + size_t(b0) * WT_MAX_IDS, n_ids + b0, nullptr, 0);
+        sums.insert(sums.end(), e.beam_sum.begin(), e.beam_sum.end());
+        lens.insert(lens.end(), e.beam_len.begin(), e.beam_len.end());
+      }
+      e.beam_sum = sums;
+      e.beam_len = lens;
+      return;
+    }
     // larger batches run as pipelined sub-batches of 32 clips: the encoder of a later
     // sub-batch overlaps the decoders of the earlier ones
     const int n_sub = (batch + 31) / 32;
@@ -433,6 +451,7 @@ int wt_encdec_debug_batch(wt_engine* h, const float* mel, int batch, int64_t* id
   return guarded(h, [&] {
     wt::Engine& e = *h->impl;
     e.require_idle();
+    e.check_beam_call(logits != nullptr);  // (before the encoder pass)
     float* d_mel = e.staging_mel(batch);
     hipchk(hipMemcpyAsync(d_mel, mel, size_t(batch) * e.mel_elems() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D mel");
     e.encode(d_mel, batch);
@@ -456,6 +475,18 @@ int wt_last_timings(const wt_engine* h, wt_timings* out) {
   out->batch = t.batch;
   out->decoder_steps = t.decoder_steps;
   return WT_OK;
+}
+
+int wt_last_beam_scores(const wt_engine* h, float* sum_logprob, int32_t* n_generated, int cap) {
+  if (!h || cap < 0 || (cap > 0 && (!sum_logprob || !n_generated))) return -WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.beam_scores_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.beam_sum.size());
+  for (int i = 0; i < n && i < cap; ++i) {
+    sum_logprob[i] = e.beam_sum[i];
+    n_generated[i] = e.beam_len[i];
+  }
+  return n;
 }
 
 int wt_last_kernel_stats(const wt_engine* h, wt_kernel_stat* out, int cap) {

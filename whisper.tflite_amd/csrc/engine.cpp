@@ -863,6 +863,9 @@ void Engine::release() noexcept {
     if (sl.d_flag) (void)hipFree(sl.d_flag);
     sl.h_ids = nullptr, sl.h_n = nullptr, sl.h_flag = nullptr, sl.d_flag = nullptr;
   }
+  for (void* p : {static_cast<void*>(bw_.h_prompt), static_cast<void*>(bw_.h_sum), static_cast<void*>(bw_.h_len)})
+    if (p) (void)hipHostFree(p);
+  bw_ = BeamWorkspace();  // (its device buffers are in allocations_)
   if (ev_switch_) (void)hipEventDestroy(ev_switch_);
   if (trace_base_) (void)hipEventDestroy(trace_base_);
   ev_switch_ = nullptr, trace_base_ = nullptr;
@@ -1182,6 +1185,7 @@ void Engine::require_idle() const {
 
 void Engine::encode(const float* d_mel, int batch) {
   require_idle();
+  check_beam_call(false);
   select_stream(false);
   encode_enqueue(d_mel, batch);
 }
@@ -1613,6 +1617,12 @@ void Engine::set_bf16(bool on) {
 void Engine::decode(int batch, int64_t* ids, int32_t* n_ids, float* logits_host,
                     int logits_steps_cap) {
   require_idle();
+  check_beam_call(logits_host != nullptr);
+  if (beam_size > 1) {
+    decode_beam(batch, last_enc_slot_, ids, n_ids);
+    return;
+  }
+  beam_scores_valid = false;
   decode_enqueue(batch, last_enc_slot_, logits_host, logits_steps_cap);
   decode_collect(last_enc_slot_, ids, n_ids);
 }
@@ -1667,6 +1677,7 @@ void Engine::submit_decoder(int batch, int s) {
 }
 
 void Engine::submit(const float* d_mel, int batch) {
+  if (beam_size > 1) throw Error(kErrUnsupported, "beam search runs on the synchronous entry points only, not in the pipeline");
   if (int(inflight_.size()) >= kSlots) throw Error(1, "pipeline is full (24 batches in flight): collect() first");
   if (batch > 64) throw Error(1, "decoder batches are limited to 64 clips per call");
   select_stream(true);
@@ -1676,6 +1687,7 @@ void Engine::submit(const float* d_mel, int batch) {
 }
 
 void Engine::submit_pcm(const float* d_pcm, int batch) {
+  if (beam_size > 1) throw Error(kErrUnsupported, "beam search runs on the synchronous entry points only, not in the pipeline");
   if (int(inflight_.size()) >= kSlots) throw Error(1, "pipeline is full (24 batches in flight): collect() first");
   if (batch > 64) throw Error(1, "decoder batches are limited to 64 clips per call");
   select_stream(true);
@@ -2100,6 +2112,249 @@ void Engine::decode_collect(int slot_idx, int64_t* ids, int32_t* n_ids) {
     timings_.logmel_ms = 0;
     if (hipEventElapsedTime(&ms, ev_[0], ev_[1]) == hipSuccess) timings_.logmel_ms = ms;
   }
+}
+
+}  // namespace wt
+
+// -------------------------------------------------------- beam search ---
+
+namespace wt {
+
+void Engine::check_beam_call(bool logits_tap) const {
+  if (beam_size <= 1) return;
+  auto no = [](const char* why) { throw Error(kErrUnsupported, std::string("beam search: ") + why); };
+  if (bf16) no("not in the bf16 storage mode");
+  if (!cross_absorb) no("needs the absorbed cross-attention (cross_absorb = 1)");
+  if (!absorb_active()) no("the absorbed cross-attention is not available with these weights or this gemm_variant");
+  if (!stop_at_eot) no("needs stop_at_eot = 1");
+  if (!forced_ids.empty()) no("not with forced ids");
+  if (logits_tap) no("no logits tap");
+  if (dims_.n_vocab > kBeamChunk * kBeamMaxChunks) no("vocabularies of at most 65536 entries");
+}
+
+void Engine::ensure_beam_workspace() {
+  if (bw_.h_len) return;  // (allocated last)
+  const wtw::Dims& c = dims_;
+  const size_t R = kDecRowsMax, d = c.n_text_state, V = c.n_vocab, C = kBeamClipsMax, S = kBeamMax;
+  auto alloc = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, std::max<size_t>(bytes, 4)));
+    allocations_.push_back(p);
+    HIPCHK(hipMemset(p, 0, std::max<size_t>(bytes, 4)));
+    return p;
+  };
+  for (int i = 0; i < 2; ++i) {
+    bw_.kv[i] = static_cast<float*>(alloc(size_t(c.n_text_layer) * 2 * R * self_cap_ * d * sizeof(float)));
+    bw_.ids[i] = static_cast<long long*>(alloc(R * 32 * sizeof(long long)));
+  }
+  bw_.logits = static_cast<float*>(alloc(R * V * sizeof(float)));
+  bw_.best = static_cast<unsigned long long*>(alloc(R * ((V + 31) / 32) * sizeof(unsigned long long)));
+  bw_.part = static_cast<BeamPart*>(alloc(R * beam_chunks(int(V)) * sizeof(BeamPart)));
+  bw_.parent = static_cast<int*>(alloc(R * sizeof(int)));
+  bw_.token = static_cast<long long*>(alloc(R * sizeof(long long)));
+  bw_.live_sum = static_cast<float*>(alloc(C * S * sizeof(float)));
+  bw_.fin_sum = static_cast<float*>(alloc(C * S * sizeof(float)));
+  bw_.fin_len = static_cast<int*>(alloc(C * S * sizeof(int)));
+  bw_.fin_tok = static_cast<int*>(alloc(C * S * 32 * sizeof(int)));
+  bw_.n_fin = static_cast<int*>(alloc(C * sizeof(int)));
+  bw_.done = static_cast<int*>(alloc(C * sizeof(int)));
+  bw_.out_ids = static_cast<long long*>(alloc(C * 32 * sizeof(long long)));
+  bw_.out_n = static_cast<int*>(alloc(C * sizeof(int)));
+  bw_.out_sum = static_cast<float*>(alloc(C * sizeof(float)));
+  bw_.out_len = static_cast<int*>(alloc(C * sizeof(int)));
+  void* p = nullptr;
+  HIPCHK(hipHostMalloc(&p, C * 32 * sizeof(long long), 0));
+  bw_.h_prompt = static_cast<long long*>(p);
+  HIPCHK(hipHostMalloc(&p, C * sizeof(float), 0));
+  bw_.h_sum = static_cast<float*>(p);
+  HIPCHK(hipHostMalloc(&p, C * sizeof(int), 0));
+  bw_.h_len = static_cast<int*>(p);
+}
+
+// Beam search.  A chain decodes nc <= 128 / K clips: the prompt passes over nc rows as greedy runs
+// them, then per step the K live hypotheses of every clip as K * nc rows, row = k * nc + c — one position per pass, so
+// every per-row kernel sees K * nc independent sequences, and the absorbed cross-attention sees nc clips with K query
+// rows each (its position loop).  Between the logits GEMM and the next pass: top-k, select, reorder (k_beam.hip).
+// Chains of one call run one after the other on the slot's decoder stream, each reading the encoder planes at its clip
+// offset.  Like greedy's, a chain's launch sequence is fixed for its key and replayed from a hipGraph.
+void Engine::decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids) {
+  const int K = int(beam_size);
+  beam_scores_valid = false;
+  if (batch < 1 || batch > kBeamClipsMax) throw Error(kErrInvalidArg, "decoder batches are limited to 64 clips per call");
+  Slot& slot = slots_[slot_idx];
+  if (!slot.absorbed) throw Error(kErrUnsupported, "beam search: the encoder pass did not prepare the absorbed cross-attention");
+  ensure_beam_workspace();
+  const wtw::Dims& c = dims_;
+  const int d = c.n_text_state, T = c.n_audio_ctx, H = c.n_text_head, V = c.n_vocab, L = c.n_text_layer;
+  const std::vector<long long> prompt = this->prompt();
+  const int n_prompt = int(prompt.size()), stride = 32;
+  for (long long id : prompt) {
+    if (id < 0 || id >= V) throw Error(1, "prompt token id outside the model's vocabulary");
+  }
+  const int max_pos = int(std::min<long>(std::max<long>(max_tokens, n_prompt), 31));
+  const int n_steps = max_pos - n_prompt + 1;  // the positions at which greedy takes an argmax
+  const int per_chain = kDecRowsMax / K;
+  slot.dec = slot_idx % n_dec_streams_;
+  slot.pair_leader = -1;
+  DecWorkspace& dw = dws_[slot.dec];
+  hipStream_t const st = dec_stream_at(slot.dec);
+  for (int b = 0; b < kBeamClipsMax; ++b) {
+    for (int i = 0; i < stride; ++i) bw_.h_prompt[size_t(b) * stride + i] = i < n_prompt ? prompt[i] : 0;
+  }
+  HIPCHK(hipStreamWaitEvent(st, slot.enc_done, 0));
+  HIPCHK(hipEventRecord(slot.dec_begin, st));
+  const bool split = fc2_ksplit == 2 && (4 * d) % 256 == 0;
+  const int nq_max = cross_absorbed_max_nq(H);
+  float* const x = dw.xd;
+
+  auto enqueue_chain = [&](int c0, int nc) {
+    const int rows = K * nc;
+    int n_abs = abs_chunks > 0 ? int(abs_chunks) : std::min(16, std::max(1, (256 + nc - 1) / nc));
+    n_abs = std::min(n_abs, (T + 31) / 32);
+    HIPCHK(hipMemcpyAsync(bw_.ids[0], bw_.h_prompt, size_t(nc) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(bw_.n_fin + c0, 0, size_t(nc) * sizeof(int), st));
+    HIPCHK(hipMemsetAsync(bw_.done + c0, 0, size_t(nc) * sizeof(int), st));
+    // one decoder pass: np positions from pos0 of `seqs` sequences (rows p * seqs + s, caches of seqs rows); the
+    // cross-attention sees the nc clips with np * seqs / nc query rows each (row = q * nc + clip)
+    auto pass = [&](int pos0, int np, int seqs, const long long* idsb, float* kv, bool logits) {
+      const int M = np * seqs, nq_all = M / nc;
+      const size_t self_slab = size_t(seqs) * self_cap_ * d;
+      for (int l = 0; l < L; ++l) {
+        const DecBlockWeights& w = dec_blocks_[l];
+        DecGemmArgs q;  // LN + fused q|k|v projection (+ token/positional embedding at layer 0)
+        q.Wt = w.wqkv.w; q.w_scale = w.wqkv.scale; q.N = 3 * d; q.K = d; q.B = seqs; q.M = M;
+        q.xin = x; q.ln_g = w.attn_ln_g; q.ln_b = w.attn_ln_b;
+        if (l > 0 && split) {
+          q.xin = dw.xb; q.xpart = dw.xpart; q.xout = x;
+        }
+        if (l == 0) {
+          q.ids = idsb; q.ids_stride = stride; q.pos = pos0; q.tok_emb = tok_emb; q.pos_emb = dec_pos;
+          q.n_vocab = V; q.xout = x;
+        }
+        q.bias = w.bqkv; q.Y = dw.qkvd; q.ldy = 3 * d;
+        launch_dec_gemm(q, kProLn, kDecBias, st);
+        launch_self_attention(dw.qkvd, kv + (size_t(l) * 2 + 0) * self_slab, kv + (size_t(l) * 2 + 1) * self_slab, self_cap_,
+                              pos0, np, dw.attd, seqs, H, st);
+        DecGemmArgs o;  // x += attn . Wo^T + bo
+        o.Wt = w.wo.w; o.w_scale = w.wo.scale; o.N = d; o.K = d; o.B = seqs; o.M = M; o.X = dw.attd; o.ldx = d;
+        o.bias = w.bo; o.R = x; o.Y = x; o.ldy = d;
+        launch_dec_gemm(o, kProNone, kDecResid, st);
+        DecGemmArgs qa;  // LN + absorbed query projection
+        qa.Wt = w.wq_abs.w; qa.w_scale = w.wq_abs.scale; qa.N = H * d; qa.K = d; qa.B = seqs; qa.M = M;
+        qa.xin = x; qa.ln_g = w.cross_ln_g; qa.ln_b = w.cross_ln_b; qa.bias = w.bq_abs; qa.Y = dw.qp; qa.ldy = H * d;
+        launch_dec_gemm(qa, kProLn, kDecBias, st);
+        for (int p0 = 0; p0 < nq_all; p0 += nq_max) {
+          CrossAbsorbedArgs ca;
+          ca.qp = dw.qp; ca.e = slot.e_planes + size_t(c0) * T * d; ca.e_plane = long(ws_.batch) * T * d;
+          ca.e_scale = sc_cross_kv_.a;
+          ca.ws = dw.abs_ws; ca.batch = nc; ca.heads = H; ca.d_model = d; ca.T = T; ca.chunks = n_abs;
+          ca.nq = std::min(nq_max, nq_all - p0); ca.p0 = p0;
+          launch_cross_absorbed(ca, st);
+        }
+        launch_cross_absorbed_combine(dw.abs_ws, w.cross_wv_t, w.cross_bv, dw.cabs, M, H, n_abs, d, st);
+        DecGemmArgs co;  // x += o . Wco^T + bco
+        co.Wt = w.cross_wo.w; co.w_scale = w.cross_wo.scale; co.N = d; co.K = d; co.B = seqs; co.M = M;
+        co.X = dw.cabs; co.ldx = d; co.bias = w.cross_bo; co.R = x; co.Y = x; co.ldy = d;
+        launch_dec_gemm(co, kProNone, kDecResid, st);
+        DecGemmArgs f1;  // LN + fc1 + GELU
+        f1.Wt = w.w1.w; f1.w_scale = w.w1.scale; f1.N = 4 * d; f1.K = d; f1.B = seqs; f1.M = M;
+        f1.xin = x; f1.ln_g = w.mlp_ln_g; f1.ln_b = w.mlp_ln_b;
+        f1.bias = w.b1; f1.Y = dw.hd; f1.ldy = 4 * d;
+        launch_dec_gemm(f1, kProLn, kDecBiasGelu, st);
+        DecGemmArgs f2;  // x += h . W2^T + b2
+        f2.Wt = w.w2.w; f2.w_scale = w.w2.scale; f2.N = d; f2.K = 4 * d; f2.B = seqs; f2.M = M; f2.X = dw.hd; f2.ldx = 4 * d;
+        f2.bias = w.b2; f2.R = x; f2.Y = x; f2.ldy = d;
+        if (split) {
+          f2.Y = dw.xb; f2.ksplit = 2; f2.part = dw.xpart;
+        }
+        launch_dec_gemm(f2, kProNone, kDecResid, st);
+      }
+      if (logits) {  // the last position's rows: final LayerNorm + logits, written out for the top-k pass
+        const size_t off = size_t(np - 1) * seqs * d;
+        DecGemmArgs lg;
+        lg.Wt = tok_emb_tiled.w; lg.w_scale = tok_emb_tiled.scale; lg.N = V; lg.K = d; lg.B = seqs;
+        lg.xin = (split ? dw.xb : x) + off; lg.xpart = split ? dw.xpart + off : nullptr; lg.ln_g = dec_ln_g; lg.ln_b = dec_ln_b;
+        lg.Y = bw_.logits; lg.ldy = V; lg.best = bw_.best;
+        launch_dec_gemm(lg, kProLn, kDecLogits, st);
+      }
+    };
+    const int np_max = std::max(1, std::min(4, kDecRowsMax / nc));
+    for (int pos0 = 0, np = 1; pos0 < n_prompt; pos0 += np) {
+      np = std::min(np_max, n_prompt - pos0);
+      pass(pos0, np, nc, bw_.ids[0], bw_.kv[0], pos0 + np == n_prompt);
+    }
+    int cur = 0;
+    for (int t = 0; t < n_steps; ++t) {
+      const int pos = n_prompt - 1 + t, live_rows = t == 0 ? nc : rows;
+      const bool more = t + 1 < n_steps;
+      launch_beam_topk(bw_.logits, V, V, live_rows, K + 1, bw_.part, st);
+      BeamStepArgs sa;
+      sa.part = bw_.part; sa.n_chunks = beam_chunks(V); sa.ids = bw_.ids[cur];
+      sa.clips = nc; sa.K = K; sa.n_live = t == 0 ? 1 : K; sa.pos = pos; sa.n_prompt = n_prompt; sa.V = V; sa.c0 = c0;
+      sa.eot = vocab_.token_eot;
+      sa.live_sum = bw_.live_sum; sa.fin_tok = bw_.fin_tok; sa.fin_sum = bw_.fin_sum; sa.fin_len = bw_.fin_len;
+      sa.n_fin = bw_.n_fin; sa.done = bw_.done; sa.parent = bw_.parent; sa.token = bw_.token;
+      launch_beam_select(sa, st);
+      BeamReorderArgs ra;  // (after the last step only the id rows: finalize reads the live hypotheses from them)
+      ra.kv_src = bw_.kv[cur]; ra.kv_dst = bw_.kv[cur ^ 1]; ra.src_rows = live_rows; ra.dst_rows = rows; ra.cap = self_cap_;
+      ra.d = d; ra.slabs = more ? 2 * L : 0; ra.pos = pos; ra.V = V;
+      ra.ids_src = bw_.ids[cur]; ra.ids_dst = bw_.ids[cur ^ 1]; ra.parent = bw_.parent; ra.token = bw_.token;
+      launch_beam_reorder(ra, st);
+      cur ^= 1;
+      if (more) pass(pos + 1, 1, rows, bw_.ids[cur], bw_.kv[cur], true);
+    }
+    BeamFinalArgs fa;
+    fa.ids = bw_.ids[cur]; fa.clips = nc; fa.K = K; fa.c0 = c0; fa.pos = max_pos - 1; fa.n_prompt = n_prompt;
+    fa.live_sum = bw_.live_sum; fa.fin_tok = bw_.fin_tok; fa.fin_sum = bw_.fin_sum; fa.fin_len = bw_.fin_len;
+    fa.n_fin = bw_.n_fin; fa.done = bw_.done;
+    fa.out_ids = bw_.out_ids; fa.out_n = bw_.out_n; fa.out_sum = bw_.out_sum; fa.out_len = bw_.out_len;
+    launch_beam_finalize(fa, st);
+  };
+
+  for (int c0 = 0; c0 < batch; c0 += per_chain) {
+    const int nc = std::min(per_chain, batch - c0);
+    // (greedy's keys have 14 entries and start with the slot; a beam key starts with -beam_size)
+    const std::vector<long long> key{-K, slot_idx, c0, nc, max_pos, n_prompt, abs_chunks, fc2_ksplit, slot.dec};
+    auto it = use_graphs ? graphs_.find(key) : graphs_.end();
+    if (it != graphs_.end()) {
+      HIPCHK(hipGraphLaunch(it->second.exec, st));
+      continue;
+    }
+    enqueue_chain(c0, nc);  // eager the first time (the kernels' one-time set-up), then captured for the next calls
+    if (use_graphs) {
+      hipGraph_t graph = nullptr;
+      hipGraphExec_t ge = nullptr;
+      try {
+        HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        try {
+          enqueue_chain(c0, nc);
+        } catch (...) {
+          (void)hipStreamEndCapture(st, &graph);
+          if (graph) (void)hipGraphDestroy(graph);
+          throw;
+        }
+        HIPCHK(hipStreamEndCapture(st, &graph));
+        const hipError_t ie = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (ie != hipSuccess) throw Error(kErrDevice, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
+        graphs_[key] = GraphEntry{ge, n_steps};
+      } catch (const std::exception& e) {
+        (void)hipGetLastError();
+        use_graphs = 0;
+        std::fprintf(stderr, "[wt] beam-search hipGraph capture failed (%s): continuing with eager launches\n", e.what());
+      }
+    }
+  }
+  HIPCHK(hipMemcpyAsync(slot.h_ids, bw_.out_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(slot.h_n, bw_.out_n, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(bw_.h_sum, bw_.out_sum, size_t(batch) * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(bw_.h_len, bw_.out_len, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord(slot.dec_done, st));
+  slot.steps = n_steps;
+  decode_collect(slot_idx, ids, n_ids);  // waits; the encoder's non-finite flag, timings
+  beam_sum.assign(bw_.h_sum, bw_.h_sum + batch);
+  beam_len.assign(bw_.h_len, bw_.h_len + batch);
+  beam_scores_valid = true;
 }
 
 }  // namespace wt

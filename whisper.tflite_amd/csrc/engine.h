@@ -15,6 +15,8 @@
 
 namespace wt {
 
+struct BeamPart;  // kernels.h
+
 struct Timings {
   float logmel_ms = 0, encoder_ms = 0, cross_kv_ms = 0, decoder_ms = 0, total_ms = 0;
   int batch = 0, decoder_steps = 0;
@@ -121,7 +123,19 @@ class Engine {
   // ... and chosen for a call: every pipelined batch (throughput: half the decoder's stream bytes, no cross-KV GEMM);
   // synchronous calls only from 32 clips on — below that the cached form's 7 launches per decoder layer beat the absorbed
   // form's 9 (single clip 7.2 against 9.0 ms, 16 clips 11.1 against 12.1 ms, 32 clips 15.2 against 15.0 ms)
-  bool absorb_for(int batch) const { return absorb_active() && (pipelined_call_ || batch >= 32); }
+  // (beam search: always, whatever the batch size; its K query rows per clip ride the absorbed form's position loop)
+  bool absorb_for(int batch) const { return absorb_active() && (pipelined_call_ || batch >= 32 || beam_size > 1); }
+  // 1 = greedy (the reference's argmax loop); 2..8 = beam search with that many hypotheses per clip on the synchronous
+  // entry points (decode_beam).  Scope: stop_at_eot = 1, the absorbed cross-attention, fp32-accurate
+  // storage; no pipeline, no forced ids, no logits tap (check_beam_call).
+  long beam_size = 1;
+  // throws kErrUnsupported when beam_size > 1 and the call or the options fall outside beam search's scope
+  void check_beam_call(bool logits_tap) const;
+  // per clip of the last synchronous beam call: the chosen hypothesis's sum of log-probabilities and generated ids
+  // (EOT included); valid = the last synchronous decode was a beam search
+  std::vector<float> beam_sum;
+  std::vector<int> beam_len;
+  bool beam_scores_valid = false;
   long gemm_variant = -1;  // -1 = plane GEMM (per-contraction fall-back to 13/16); 0 = fp32 MFMA, 13 / 16 = three bf16 planes
   // 1 = bf16 STORAGE mode (BASELINE configs[3]): bf16 weights, activations and both KV caches, fp32 accumulation,
   // fp32 residual stream; k_gemm_bf16.hip and the BF variants of the attention / decoder kernels.  Set through
@@ -223,6 +237,24 @@ class Engine {
   std::vector<int> pending_;  // consecutive slots submitted, encoder enqueued, decoder waiting for the rest of their group
   void flush_pending();
   void decode_collect(int slot, int64_t* ids, int32_t* n_ids);
+  // beam search over the slot encode() just filled: consecutive chains of <= 128 / beam_size clips on one decoder stream
+  void decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids);
+  struct BeamWorkspace {  // allocated on the first beam call, sized for 128 rows and 64 clips whatever the batch
+    float* kv[2] = {nullptr, nullptr};          // self-attention caches [layer][k|v][row][cap][d], double-buffered
+    long long* ids[2] = {nullptr, nullptr};     // id rows [128][32], double-buffered with them
+    float* logits = nullptr;                    // [128][n_vocab]
+    unsigned long long* best = nullptr;         // the logits GEMM's argmax records (unused here, written anyway)
+    BeamPart* part = nullptr;                   // [128][chunks]
+    int* parent = nullptr;
+    long long* token = nullptr;
+    float *live_sum = nullptr, *fin_sum = nullptr, *out_sum = nullptr;
+    int *fin_tok = nullptr, *fin_len = nullptr, *n_fin = nullptr, *done = nullptr, *out_n = nullptr, *out_len = nullptr;
+    long long* out_ids = nullptr;
+    long long* h_prompt = nullptr;  // pinned [64][32]: the prompt rows a chain starts from
+    float* h_sum = nullptr;         // pinned [64]
+    int* h_len = nullptr;           // pinned [64]
+  } bw_;
+  void ensure_beam_workspace();
 
   int enc_cus_masked_ = 0;  // CUs the pipelined encoder stream may use
  public:

@@ -306,6 +306,60 @@ void launch_select_token(const unsigned long long* best, int n_tiles, long long*
                          int pos, int* n_ids, int* finished, long long eot, int stop_at_eot, int batch,
                          hipStream_t s, bool keep_ids = false);
 
+// ----------------------------------------------------------- beam search ---
+// k_beam.hip (option beam_size 2..8).  Rows of a step are laid out row = k * clips + c (hypothesis slot k of clip c);
+// the id rows are [row][32] int64 and the self-attention caches [layer][k|v][row][cap][d] as in launch_self_attention.
+constexpr int kBeamMax = 8;          // largest beam_size
+constexpr int kBeamChunk = 4096;     // vocabulary entries per top-k block: fixed, so a row's sums have one order
+constexpr int kBeamMaxChunks = 16;   // n_vocab <= 65536
+constexpr int kBeamClipsMax = 64;    // clips of one synchronous call (the per-clip state is indexed by clip)
+struct BeamPart {                    // one (row, chunk): max logit, sum of exp(logit - max), top K+1 keys
+  float m, s;                        // key = order-preserving bits of the logit << 32 | id (0 = none)
+  unsigned long long key[kBeamMax + 1];
+};
+int beam_chunks(int n_vocab);
+// logits [rows][ldl] -> part [rows][beam_chunks(V)], kk = K + 1 keys per chunk
+void launch_beam_topk(const float* logits, int ldl, int V, int rows, int kk, BeamPart* part, hipStream_t s);
+// per-clip state [kBeamClipsMax][kBeamMax] (fin_tok [clip][slot][32] generated ids), indexed by c0 + clip
+struct BeamStepArgs {
+  const BeamPart* part = nullptr;
+  int n_chunks = 0;
+  const long long* ids = nullptr;  // id rows of the live hypotheses (step 0: the prompt rows, one per clip)
+  int clips = 0, K = 0, n_live = 0, pos = 0, n_prompt = 0, V = 0, c0 = 0;  // pos: the position the logits belong to
+  long long eot = 0;
+  float* live_sum = nullptr;
+  int* fin_tok = nullptr;
+  float* fin_sum = nullptr;
+  int *fin_len = nullptr, *n_fin = nullptr, *done = nullptr;
+  int* parent = nullptr;       // [K * clips]: the row each new row continues
+  long long* token = nullptr;  // [K * clips]: its id at pos + 1
+};
+void launch_beam_select(const BeamStepArgs& a, hipStream_t s);
+struct BeamReorderArgs {
+  const float* kv_src = nullptr;  // [slabs][src_rows][cap][d]
+  float* kv_dst = nullptr;        // [slabs][dst_rows][cap][d]
+  int src_rows = 0, dst_rows = 0, cap = 0, d = 0, slabs = 0, pos = 0, V = 0;  // slabs = 0: the id rows only
+  const long long* ids_src = nullptr;
+  long long* ids_dst = nullptr;
+  const int* parent = nullptr;
+  const long long* token = nullptr;
+};
+void launch_beam_reorder(const BeamReorderArgs& a, hipStream_t s);
+struct BeamFinalArgs {
+  const long long* ids = nullptr;  // id rows after the last step's reorder
+  int clips = 0, K = 0, c0 = 0, pos = 0, n_prompt = 0;
+  const float* live_sum = nullptr;
+  int* fin_tok = nullptr;
+  float* fin_sum = nullptr;
+  int *fin_len = nullptr, *n_fin = nullptr;
+  const int* done = nullptr;
+  long long* out_ids = nullptr;  // [kBeamClipsMax][32]
+  int* out_n = nullptr;
+  float* out_sum = nullptr;
+  int* out_len = nullptr;
+};
+void launch_beam_finalize(const BeamFinalArgs& a, hipStream_t s);
+
 // ---- load-time re-layouts of decoder weights (host) ----
 // bf16 storage mode: W [N][K] fp32 -> ONE bf16 plane (round to nearest even) in the same fragment order,
 // [ceil(N/32)][K/16][64 lanes][8]
