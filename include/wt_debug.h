@@ -110,6 +110,28 @@ int wt_dbg_self_attention_bf16(wt_engine* h, int batch, int heads, int cap, int 
 int wt_dbg_cross_attention_bf16(wt_engine* h, int batch, int heads, int T, int chunks, int nq, const float* x,
                                 const float* ln_g, const float* ln_b, const float* wq, const float* bq, const float* kc,
                                 const float* vc, float* out);
+/* beam search (k_beam.hip).  Rows are laid out row = k * clips + c; the per-clip state is the
+ * engine's: live_sum / fin_sum / fin_len [64][8], fin_tok [64][8][32], n_fin / done [64], indexed by c0 + clip, all
+ * in / out.  A shape the launcher refuses is WT_ERR_INVALID_ARG. */
+/* beam_topk_partial: logits [rows][ldl] -> per (row, 4096-entry chunk) the maximum m [rows][chunks], the sum of
+ * exp(z - m) s [rows][chunks] and the top kk keys [rows][chunks][kk] (order bits of the logit << 32 | id; 0 = none) */
+int wt_dbg_beam_topk(wt_engine* h, int rows, int V, int ldl, int kk, const float* logits, float* m, float* s,
+                     uint64_t* keys);
+/* one step of decode_beam: beam_topk_partial over logits [n_live * clips][V], beam_select, then beam_reorder of the
+ * id rows only (ids [n_live * clips][32] -> ids_next [K * clips][32]); parent [K * clips], token [K * clips] */
+int wt_dbg_beam_step(wt_engine* h, int K, int clips, int c0, int n_live, int pos, int n_prompt, int V, int64_t eot,
+                     const float* logits, const int64_t* ids, float* live_sum, int32_t* fin_tok, float* fin_sum,
+                     int32_t* fin_len, int32_t* n_fin, int32_t* done, int32_t* parent, int64_t* token, int64_t* ids_next);
+/* beam_reorder: kv_src [slabs][src_rows][cap][d]; kv_dst [slabs * dst_rows + 1][cap][d] in / out (the last row is a
+ * guard that the kernel must not write); ids_src [src_rows][32]; ids_dst [128][32] in / out; parent [dst_rows],
+ * token [dst_rows] */
+int wt_dbg_beam_reorder(wt_engine* h, int src_rows, int dst_rows, int cap, int d, int slabs, int pos, int V,
+                        const float* kv_src, float* kv_dst, const int64_t* ids_src, int64_t* ids_dst,
+                        const int32_t* parent, const int64_t* token);
+/* beam_finalize over ids [K * clips][32]; out_ids [64][32], out_n / out_sum / out_len [64] in / out */
+int wt_dbg_beam_finalize(wt_engine* h, int K, int clips, int c0, int pos, int n_prompt, const int64_t* ids,
+                         const float* live_sum, int32_t* fin_tok, float* fin_sum, int32_t* fin_len, int32_t* n_fin,
+                         const int32_t* done, int64_t* out_ids, int32_t* out_n, float* out_sum, int32_t* out_len);
 #ifdef __cplusplus
 }
 #endif

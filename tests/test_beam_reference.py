@@ -88,3 +88,63 @@ def test_eot_from_a_later_slot_and_the_length_normalisation():
     # the list: [4, EOT] (from the walk), then the best live hypothesis [5, 5]; both have two generated ids
     expect = [1, 4, EOT] if fin_eot >= live0 else [1, 5, 5]
     assert r["ids"] == expect and r["n_gen"] == 2
+
+
+def test_ranked_prefix_is_the_full_order_prefix():
+    rng = np.random.default_rng(7)
+    for V in (6, 50, 4097):
+        lp = rng.integers(-4, 4, V).astype(np.float64)  # many exact ties
+        lp[rng.integers(0, V, 3)] = -math.inf
+        full = beam_ref.ranked(lp)
+        for n in (1, 3, 9, V):
+            assert list(beam_ref.ranked(lp, n)) == list(full[:n])
+
+
+def test_signed_zeros_are_one_logit():
+    # ids 3 (-0) and 2 (+0) are equal logits: the larger id first, whichever zero it holds
+    z = np.array([-3.0, -1.0, 0.0, -0.0, -2.0, -2.5], np.float32)
+    assert list(beam_ref.ranked(lp(z))[:2]) == [3, 2]
+    fn = table({1: z, 2: z})
+    r = beam_ref.beam_search(fn, [1], 2, 1, EOT)
+    assert r["ids"] == [1, 3]
+    assert r["gaps"]["logit"][0] == 0.0
+    z2 = z.copy()
+    z2[[2, 3]] = z[[3, 2]]  # the signs swapped: the same order
+    assert list(beam_ref.ranked(lp(z2))) == list(beam_ref.ranked(lp(z)))
+
+
+def test_minus_inf_entries_and_a_masked_chunk():
+    # a row whose first 4096 entries (one whole top-k chunk of the kernels) are -inf: they take no probability and rank
+    # last; the decision gaps stay numbers
+    V = 8192 + 5
+    z = np.full(V, -20.0, np.float32)
+    z[:4096] = -np.inf
+    z[[5000, 6000, 7000, 8196]] = [1.0, 2.0, 2.0, 0.5]
+    want = lp(z[4096:])
+    got = lp(z)
+    assert np.all(np.isneginf(got[:4096])) and np.array_equal(got[4096:], want)
+    fn = table({1: z, 2: z, 3: z})
+    r = beam_ref.beam_search(fn, [1], 3, 3, EOT)
+    assert r["ids"] == [1, 7000, 7000, 7000]
+    assert all(not math.isnan(g) for k in beam_ref.GAP_KINDS for g in r["gaps"][k])
+    # few finite entries: the -inf ones fill the ranks after them, larger id first
+    z = np.full(12, -np.inf, np.float32)
+    z[[4, 9]] = [0.0, 1.0]
+    assert list(beam_ref.ranked(lp(z))[:4]) == [9, 4, 11, 10]
+
+
+def test_gap_kinds_and_dropped_eot():
+    # ids 5 and 4 tie at the top, ids 3 and 2 at ranks K+1 / K+2; the two live slots share a sum, so at step 1 slot 0's
+    # rank 1 and slot 1's rank 0 tie where the walk ends
+    z = [-1.0, -1.0, 0.0, 0.0, 1.0, 1.0]
+    r = beam_ref.beam_search(table({1: z, 2: z, 3: z}), [1], 2, 2, EOT)
+    assert r["gaps"]["logit"][0] == 0.0 and r["gaps"]["logit"][1] > 0.0
+    assert r["gaps"]["cut"][0] == 0.0 and r["gaps"]["score"] == [0.0]
+    assert r["ids"] == [1, 5, 5] and r["gaps"]["final"] == [0.0]  # two lists of equal sum and length: the first wins
+    # EOT first in every row: step 0 finishes one, step 1 offers it from both slots with one list place left
+    z1 = [3.0, 2.0, 2.0, 0.0, 0.0, 0.0]
+    z2 = [5.0, 0.0, 0.0, 0.0, 0.0, 0.0]
+    r = beam_ref.beam_search(table({1: z1, 2: z2}), [1], 2, 2, EOT)
+    assert r["done_early"] and r["eot_slots"] == [0, 0] and r["eot_dropped"] == 1
+    # [1, EOT] (sum lp1[0] over 1) against [2, EOT] (lp1[2] + lp2[0] over 2): the final ranking
+    assert len(r["gaps"]["final"]) == 1

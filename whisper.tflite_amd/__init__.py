@@ -52,6 +52,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_cross_attention", "wt_dbg_self_attention", "wt_dbg_interference", "wt_dbg_concurrency",
     "wt_dbg_gemm_planes", "wt_dbg_set_plane_gemm_mode", "wt_dbg_set_forced_ids", "wt_dbg_dec_gemm_bf16", "wt_dbg_dec_ln_gemm_bf16",
     "wt_dbg_self_attention_bf16", "wt_dbg_cross_attention_bf16", "wt_dbg_encoder_attention_planes", "wt_dbg_gemm_bf16", "wt_dbg_gemm_bf16_ln", "wt_dbg_encoder_attention_bf16",
+    "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
 ]
 
 
@@ -170,6 +171,14 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_self_attention.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp]
         L.wt_dbg_self_attention_bf16.argtypes = L.wt_dbg_self_attention.argtypes
         L.wt_dbg_cross_attention_bf16.argtypes = L.wt_dbg_cross_attention.argtypes
+        u64p = POINTER(c_uint64)
+        L.wt_dbg_beam_topk.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, u64p]
+        L.wt_dbg_beam_step.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, fp, ip64, fp, ip32,
+                                       fp, ip32, ip32, ip32, ip32, ip64, ip64]
+        L.wt_dbg_beam_reorder.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, fp, fp, ip64, ip64, ip32,
+                                          ip64]
+        L.wt_dbg_beam_finalize.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, ip64, fp, ip32, fp, ip32, ip32, ip32,
+                                           ip64, ip32, fp, ip32]
         _lib = L
     return _lib
 
@@ -180,6 +189,18 @@ def _f32(a) -> np.ndarray:
 
 def _fp(a: np.ndarray):
     return a.ctypes.data_as(POINTER(c_float)) if a is not None else None
+
+
+def _ip32(a: np.ndarray):
+    if a.dtype != np.int32 or not a.flags.c_contiguous:
+        raise ValueError("expected a contiguous int32 array")
+    return a.ctypes.data_as(POINTER(c_int32))
+
+
+def _ip64(a: np.ndarray):
+    if a.dtype != np.int64 or not a.flags.c_contiguous:
+        raise ValueError("expected a contiguous int64 array")
+    return a.ctypes.data_as(POINTER(c_int64))
 
 
 def write_synthetic_weights(path: str, arch: str = "tiny", seed: int = 0) -> None:
@@ -665,6 +686,71 @@ class Engine:
         fn = lib().wt_dbg_self_attention_bf16 if bf16 else lib().wt_dbg_self_attention
         self._check(fn(self._h, B, d // 64, cap, pos, npos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
         return out, kcache, vcache
+
+    # beam search (k_beam.hip).  The per-clip state is a dict of the engine's arrays (beam_state()), updated in place.
+    @staticmethod
+    def beam_state(fill=0):
+        """live_sum / fin_sum / fin_len [64][8], fin_tok [64][8][32], n_fin / done [64]; every entry = fill."""
+        C, S = 64, 8
+        return {"live_sum": np.full((C, S), fill, np.float32), "fin_tok": np.full((C, S, 32), fill, np.int32),
+                "fin_sum": np.full((C, S), fill, np.float32), "fin_len": np.full((C, S), fill, np.int32),
+                "n_fin": np.full(C, fill, np.int32), "done": np.full(C, fill, np.int32)}
+
+    @staticmethod
+    def _beam_state_ptrs(st):
+        want = Engine.beam_state()
+        for k, a in want.items():
+            if st[k].dtype != a.dtype or st[k].shape != a.shape or not st[k].flags.c_contiguous:
+                raise ValueError(f"beam state {k}: expected a contiguous {a.dtype} array of shape {a.shape}")
+        return (_fp(st["live_sum"]), _ip32(st["fin_tok"]), _fp(st["fin_sum"]), _ip32(st["fin_len"]), _ip32(st["n_fin"]),
+                _ip32(st["done"]))
+
+    def dbg_beam_topk(self, logits, V, kk):
+        """logits [rows][ldl] -> (m [rows][chunks], s [rows][chunks], keys uint64 [rows][chunks][kk])."""
+        logits = _f32(logits)
+        rows, ldl = logits.shape
+        chunks = (V + 4095) // 4096
+        m = np.zeros((rows, chunks), np.float32)
+        s = np.zeros((rows, chunks), np.float32)
+        keys = np.zeros((rows, chunks, kk), np.uint64)
+        self._check(lib().wt_dbg_beam_topk(self._h, rows, V, ldl, kk, _fp(logits), _fp(m), _fp(s),
+                                           keys.ctypes.data_as(POINTER(c_uint64))))
+        return m, s, keys
+
+    def dbg_beam_step(self, K, clips, c0, n_live, pos, n_prompt, eot, logits, ids, state):
+        """One step over logits [n_live * clips][V] and id rows [n_live * clips][32]; state updated in place.
+        Returns (parent [K * clips], token [K * clips], ids_next [K * clips][32])."""
+        logits = _f32(logits)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        V = logits.shape[1]
+        parent = np.zeros(K * clips, np.int32)
+        token = np.zeros(K * clips, np.int64)
+        ids_next = np.zeros((K * clips, 32), np.int64)
+        self._check(lib().wt_dbg_beam_step(self._h, K, clips, c0, n_live, pos, n_prompt, V, eot, _fp(logits), _ip64(ids),
+                                           *self._beam_state_ptrs(state), _ip32(parent), _ip64(token), _ip64(ids_next)))
+        return parent, token, ids_next
+
+    def dbg_beam_reorder(self, src_rows, dst_rows, cap, d, slabs, pos, V, kv_src, kv_dst, ids_src, ids_dst, parent, token):
+        """kv_dst [slabs * dst_rows + 1][cap][d] and ids_dst [128][32]: returned updated (copies)."""
+        kv_src = _f32(kv_src) if slabs > 0 else None
+        kv_dst = _f32(kv_dst).copy() if slabs > 0 else None
+        ids_src = np.ascontiguousarray(ids_src, dtype=np.int64)
+        ids_dst = np.array(ids_dst, dtype=np.int64, order="C")
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        token = np.ascontiguousarray(token, dtype=np.int64)
+        self._check(lib().wt_dbg_beam_reorder(self._h, src_rows, dst_rows, cap, d, slabs, pos, V, _fp(kv_src), _fp(kv_dst),
+                                              _ip64(ids_src), _ip64(ids_dst), _ip32(parent), _ip64(token)))
+        return kv_dst, ids_dst
+
+    def dbg_beam_finalize(self, K, clips, c0, pos, n_prompt, ids, state, out=None):
+        """ids [K * clips][32]; state updated in place; out = dict(ids [64][32], n, sum, len [64]) in / out."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        if out is None:
+            out = {"ids": np.zeros((64, 32), np.int64), "n": np.zeros(64, np.int32), "sum": np.zeros(64, np.float32),
+                   "len": np.zeros(64, np.int32)}
+        self._check(lib().wt_dbg_beam_finalize(self._h, K, clips, c0, pos, n_prompt, _ip64(ids), *self._beam_state_ptrs(state),
+                                               _ip64(out["ids"]), _ip32(out["n"]), _fp(out["sum"]), _ip32(out["len"])))
+        return out
 
 
 class DeviceArray:

@@ -1501,3 +1501,152 @@ int wt_dbg_self_attention_bf16(wt_engine* h, int batch, int heads, int cap, int 
 }
 
 }  // extern "C"
+
+namespace {
+// device copy of a host array of n elements of T (n = 0 or host = nullptr: uninitialised, at least one element)
+template <class T>
+struct DevArr {
+  T* p = nullptr;
+  size_t n = 0;
+  explicit DevArr(size_t n_, const T* host = nullptr) : n(n_) {
+    hipchk(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)), "hipMalloc");
+    if (host && n) hipchk(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice), "H2D");
+  }
+  ~DevArr() { (void)hipFree(p); }
+  void to_host(T* host) const {
+    if (host && n) hipchk(hipMemcpy(host, p, n * sizeof(T), hipMemcpyDeviceToHost), "D2H");
+  }
+};
+
+// the engine's per-clip beam state (ensure_beam_workspace), host in / host out
+struct DevBeamState {
+  static constexpr size_t C = wt::kBeamClipsMax, S = wt::kBeamMax;
+  DevArr<float> live_sum, fin_sum;
+  DevArr<int> fin_tok, fin_len, n_fin, done;
+  DevBeamState(const float* ls, const int32_t* ft, const float* fs, const int32_t* fl, const int32_t* nf, const int32_t* dn)
+      : live_sum(C * S, ls), fin_sum(C * S, fs), fin_tok(C * S * 32, ft), fin_len(C * S, fl), n_fin(C, nf), done(C, dn) {}
+};
+}  // namespace
+
+extern "C" {
+
+int wt_dbg_beam_topk(wt_engine* h, int rows, int V, int ldl, int kk, const float* logits, float* m, float* s,
+                     uint64_t* keys) {
+  if (!h || !logits || !m || !s || !keys || rows < 1 || V < 1 || ldl < V || kk < 1) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    const int chunks = wt::beam_chunks(V);
+    DevArr<float> dz(size_t(rows) * ldl, logits);
+    DevArr<wt::BeamPart> dp(size_t(rows) * chunks);
+    hipchk(hipMemset(dp.p, 0, dp.n * sizeof(wt::BeamPart)), "memset");
+    wt::launch_beam_topk(dz.p, ldl, V, rows, kk, dp.p, h->impl->stream());
+    h->impl->sync();
+    std::vector<wt::BeamPart> part(dp.n);
+    dp.to_host(part.data());
+    for (size_t i = 0; i < part.size(); ++i) {
+      m[i] = part[i].m;
+      s[i] = part[i].s;
+      for (int r = 0; r < kk; ++r) keys[i * kk + r] = part[i].key[r];
+    }
+  });
+}
+
+int wt_dbg_beam_step(wt_engine* h, int K, int clips, int c0, int n_live, int pos, int n_prompt, int V, int64_t eot,
+                     const float* logits, const int64_t* ids, float* live_sum, int32_t* fin_tok, float* fin_sum,
+                     int32_t* fin_len, int32_t* n_fin, int32_t* done, int32_t* parent, int64_t* token, int64_t* ids_next) {
+  if (!h || !logits || !ids || !live_sum || !fin_tok || !fin_sum || !fin_len || !n_fin || !done || !parent || !token ||
+      !ids_next || K < 1 || clips < 1 || n_live < 1 || V < 1 || size_t(K) * clips > 128 || size_t(n_live) * clips > 128) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    hipStream_t st = h->impl->stream();
+    const int src_rows = n_live * clips, dst_rows = K * clips;
+    DevArr<float> dz(size_t(src_rows) * V, logits);
+    DevArr<wt::BeamPart> dp(size_t(src_rows) * wt::beam_chunks(V));
+    DevArr<long long> dids(size_t(src_rows) * 32, reinterpret_cast<const long long*>(ids)), dnext(size_t(dst_rows) * 32);
+    DevArr<int> dparent(dst_rows);
+    DevArr<long long> dtoken(dst_rows);
+    DevBeamState bs(live_sum, fin_tok, fin_sum, fin_len, n_fin, done);
+    wt::launch_beam_topk(dz.p, V, V, src_rows, K + 1, dp.p, st);
+    wt::BeamStepArgs sa;
+    sa.part = dp.p; sa.n_chunks = wt::beam_chunks(V); sa.ids = dids.p;
+    sa.clips = clips; sa.K = K; sa.n_live = n_live; sa.pos = pos; sa.n_prompt = n_prompt; sa.V = V; sa.c0 = c0;
+    sa.eot = eot;
+    sa.live_sum = bs.live_sum.p; sa.fin_tok = bs.fin_tok.p; sa.fin_sum = bs.fin_sum.p; sa.fin_len = bs.fin_len.p;
+    sa.n_fin = bs.n_fin.p; sa.done = bs.done.p; sa.parent = dparent.p; sa.token = dtoken.p;
+    wt::launch_beam_select(sa, st);
+    wt::BeamReorderArgs ra;  // the id rows only, as after decode_beam's last step
+    ra.src_rows = src_rows; ra.dst_rows = dst_rows; ra.cap = 32; ra.d = 4; ra.slabs = 0; ra.pos = pos; ra.V = V;
+    ra.ids_src = dids.p; ra.ids_dst = dnext.p; ra.parent = dparent.p; ra.token = dtoken.p;
+    wt::launch_beam_reorder(ra, st);
+    h->impl->sync();
+    bs.live_sum.to_host(live_sum);
+    bs.fin_tok.to_host(fin_tok);
+    bs.fin_sum.to_host(fin_sum);
+    bs.fin_len.to_host(fin_len);
+    bs.n_fin.to_host(n_fin);
+    bs.done.to_host(done);
+    dparent.to_host(parent);
+    dtoken.to_host(reinterpret_cast<long long*>(token));
+    dnext.to_host(reinterpret_cast<long long*>(ids_next));
+  });
+}
+
+int wt_dbg_beam_reorder(wt_engine* h, int src_rows, int dst_rows, int cap, int d, int slabs, int pos, int V,
+                        const float* kv_src, float* kv_dst, const int64_t* ids_src, int64_t* ids_dst,
+                        const int32_t* parent, const int64_t* token) {
+  if (!h || !ids_src || !ids_dst || !parent || !token || src_rows < 1 || dst_rows < 1 || cap < 1 || d < 1 || slabs < 0 ||
+      src_rows > 128 || dst_rows > 128 || (slabs > 0 && (!kv_src || !kv_dst))) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const size_t row = size_t(cap) * d;
+    DevArr<float> dsrc(slabs > 0 ? size_t(slabs) * src_rows * row : 0, kv_src);
+    DevArr<float> ddst(slabs > 0 ? (size_t(slabs) * dst_rows + 1) * row : 0, kv_dst);
+    DevArr<long long> dids_src(size_t(src_rows) * 32, reinterpret_cast<const long long*>(ids_src));
+    DevArr<long long> dids_dst(size_t(128) * 32, reinterpret_cast<const long long*>(ids_dst));
+    DevArr<int> dparent(dst_rows, parent);
+    DevArr<long long> dtoken(dst_rows, reinterpret_cast<const long long*>(token));
+    wt::BeamReorderArgs ra;
+    ra.kv_src = slabs > 0 ? dsrc.p : nullptr; ra.kv_dst = slabs > 0 ? ddst.p : nullptr;
+    ra.src_rows = src_rows; ra.dst_rows = dst_rows; ra.cap = cap; ra.d = d; ra.slabs = slabs; ra.pos = pos; ra.V = V;
+    ra.ids_src = dids_src.p; ra.ids_dst = dids_dst.p; ra.parent = dparent.p; ra.token = dtoken.p;
+    wt::launch_beam_reorder(ra, h->impl->stream());
+    h->impl->sync();
+    if (slabs > 0) ddst.to_host(kv_dst);
+    dids_dst.to_host(reinterpret_cast<long long*>(ids_dst));
+  });
+}
+
+int wt_dbg_beam_finalize(wt_engine* h, int K, int clips, int c0, int pos, int n_prompt, const int64_t* ids,
+                         const float* live_sum, int32_t* fin_tok, float* fin_sum, int32_t* fin_len, int32_t* n_fin,
+                         const int32_t* done, int64_t* out_ids, int32_t* out_n, float* out_sum, int32_t* out_len) {
+  if (!h || !ids || !live_sum || !fin_tok || !fin_sum || !fin_len || !n_fin || !done || !out_ids || !out_n || !out_sum ||
+      !out_len || K < 1 || clips < 1 || size_t(K) * clips > 128) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    constexpr size_t C = wt::kBeamClipsMax;
+    DevArr<long long> dids(size_t(K) * clips * 32, reinterpret_cast<const long long*>(ids));
+    DevBeamState bs(live_sum, fin_tok, fin_sum, fin_len, n_fin, done);
+    DevArr<long long> dout(C * 32, reinterpret_cast<const long long*>(out_ids));
+    DevArr<int> dn(C, out_n), dlen(C, out_len);
+    DevArr<float> dsum(C, out_sum);
+    wt::BeamFinalArgs fa;
+    fa.ids = dids.p; fa.clips = clips; fa.K = K; fa.c0 = c0; fa.pos = pos; fa.n_prompt = n_prompt;
+    fa.live_sum = bs.live_sum.p; fa.fin_tok = bs.fin_tok.p; fa.fin_sum = bs.fin_sum.p; fa.fin_len = bs.fin_len.p;
+    fa.n_fin = bs.n_fin.p; fa.done = bs.done.p;
+    fa.out_ids = dout.p; fa.out_n = dn.p; fa.out_sum = dsum.p; fa.out_len = dlen.p;
+    wt::launch_beam_finalize(fa, h->impl->stream());
+    h->impl->sync();
+    bs.fin_tok.to_host(fin_tok);
+    bs.fin_sum.to_host(fin_sum);
+    bs.fin_len.to_host(fin_len);
+    bs.n_fin.to_host(n_fin);
+    dout.to_host(reinterpret_cast<long long*>(out_ids));
+    dn.to_host(out_n);
+    dsum.to_host(out_sum);
+    dlen.to_host(out_len);
+  });
+}
+
+}  // extern "C"

@@ -20,10 +20,11 @@ constexpr int kTopThreads = 256, kTopPer = kBeamChunk / kTopThreads;  // 16 entr
 constexpr int kKK = kBeamMax + 1;                                     // candidates per hypothesis, at most
 
 // float -> unsigned with the same order (larger float, larger key); the low 32 bits of a key hold the id, so the
-// maximum key is the larger logit and, on equal logits, the larger id: the reference argmax's last-index rule
+// maximum key is the larger logit and, on equal logits, the larger id: the reference argmax's last-index rule.  -0 and
+// +0 are one logit, so they share the key of +0 (every other value keeps its bits)
 __device__ __forceinline__ unsigned ord_of(float f) {
   const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return (u & 0x80000000u) ? (u == 0x80000000u ? 0x80000000u : ~u) : (u | 0x80000000u);
 }
 __device__ __forceinline__ float float_of(unsigned o) {
   return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(kTopThreads) void beam_topk_partial(const float* __
   BeamPart* const out = part + ((long)row * gridDim.x + chunk);
   if (tid == 0) {
     out->m = m;
-    out->s = ((red[0] + red[1]) + red[2]) + red[3];
+    out->s = m == -INFINITY ? 0.0f : ((red[0] + red[1]) + red[2]) + red[3];  // (a masked chunk: exp(-inf - -inf) is NaN)
   }
   // top kk keys: round r takes the largest key below the previous round's winner (keys are distinct: the id is in them)
   unsigned long long prev = ~0ull;
