@@ -132,6 +132,28 @@ int wt_dbg_beam_reorder(wt_engine* h, int src_rows, int dst_rows, int cap, int d
 int wt_dbg_beam_finalize(wt_engine* h, int K, int clips, int c0, int pos, int n_prompt, const int64_t* ids,
                          const float* live_sum, int32_t* fin_tok, float* fin_sum, int32_t* fin_len, int32_t* n_fin,
                          const int32_t* done, int64_t* out_ids, int32_t* out_n, float* out_sum, int32_t* out_len);
+/* the tail of a greedy decoder step kernel by kernel (k_decoder.hip, select_token in k_misc.hip); bf16 != 0 selects
+ * the BF = true instantiation.  fc2 as the engine runs it with fc2_ksplit = 2 (M <= 128 rows = M / B positions x B
+ * clips, K % 256 == 0): Y = R + bias + X[:, :K/2] . W[:, :K/2]^T and part = X[:, K/2:] . W[:, K/2:]^T, out of place;
+ * R, Y, part [M][N] in / out (R must come back unwritten) */
+int wt_dbg_dec_gemm_ksplit(wt_engine* h, int bf16, int M, int B, int N, int K, const float* X, const float* W,
+                           const float* bias, float* R, float* Y, float* part);
+/* LayerNorm prologue + GEMM over every row source: x = xin (LNMODE 0), xin + xpart (3), or, with ids [B][ids_stride],
+ * row p * B + b = tok_emb[ids[b][pos + p]] + pos_emb[pos + p] for M = positions x B rows (2).  Y [M][N] =
+ * act(LayerNorm(x) . W^T + bias); xout [M + 1][K] in / out: modes 2 and 3 store x there (block 0), the last row is a
+ * guard the kernel must not write.  K in {128, 384, 512}. */
+int wt_dbg_dec_ln_gemm_rows(wt_engine* h, int bf16, int M, int B, int N, int K, const float* xin, const float* xpart,
+                            const int64_t* ids, int ids_stride, int pos, const float* tok_emb, const float* pos_emb,
+                            int n_vocab, int n_pos, const float* ln_g, const float* ln_b, const float* W, const float* bias,
+                            int gelu, float* Y, float* xout);
+/* the final LayerNorm of xin (xpart == NULL) or xin + xpart, logits against E [V][K] and the per-tile argmax records
+ * (dec_logits_persistent with `blocks` resident blocks, 0 = the default 512); logits [M + 1][V] (may be NULL) and
+ * records [M + 1][ceil(V / 32)] in / out, the last row of each a guard the kernel must not write */
+int wt_dbg_dec_logits(wt_engine* h, int bf16, int M, int V, int K, const float* xin, const float* xpart, const float* ln_g,
+                      const float* ln_b, const float* E, int blocks, float* logits, uint64_t* records);
+/* select_token over records [B][n_tiles]; ids [B][stride], n_ids [B], finished [B] in / out */
+int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* records, int64_t* ids, int stride, int pos,
+                        int32_t* n_ids, int32_t* finished, int64_t eot, int stop_at_eot, int keep_ids);
 #ifdef __cplusplus
 }
 #endif

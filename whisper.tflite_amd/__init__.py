@@ -53,6 +53,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_gemm_planes", "wt_dbg_set_plane_gemm_mode", "wt_dbg_set_forced_ids", "wt_dbg_dec_gemm_bf16", "wt_dbg_dec_ln_gemm_bf16",
     "wt_dbg_self_attention_bf16", "wt_dbg_cross_attention_bf16", "wt_dbg_encoder_attention_planes", "wt_dbg_gemm_bf16", "wt_dbg_gemm_bf16_ln", "wt_dbg_encoder_attention_bf16",
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
+    "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
 ]
 
 
@@ -179,6 +180,12 @@ def lib() -> ctypes.CDLL:
                                           ip64]
         L.wt_dbg_beam_finalize.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, ip64, fp, ip32, fp, ip32, ip32, ip32,
                                            ip64, ip32, fp, ip32]
+        L.wt_dbg_dec_gemm_ksplit.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp, fp, fp]
+        L.wt_dbg_dec_ln_gemm_rows.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, ip64, c_int, c_int, fp, fp,
+                                              c_int, c_int, fp, fp, fp, fp, c_int, fp, fp]
+        L.wt_dbg_dec_logits.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp, fp, c_int, fp, u64p]
+        L.wt_dbg_select_token.argtypes = [c_void_p, c_int, c_int, u64p, ip64, c_int, c_int, ip32, ip32, c_int64, c_int,
+                                          c_int]
         _lib = L
     return _lib
 
@@ -751,6 +758,77 @@ class Engine:
         self._check(lib().wt_dbg_beam_finalize(self._h, K, clips, c0, pos, n_prompt, _ip64(ids), *self._beam_state_ptrs(state),
                                                _ip64(out["ids"]), _ip32(out["n"]), _fp(out["sum"]), _ip32(out["len"])))
         return out
+
+    # the tail of a greedy decoder step (k_decoder.hip, select_token), kernel by kernel
+    def dbg_dec_gemm_ksplit(self, X, W, bias, R, B=None, bf16=False):
+        """fc2 as the engine runs it with fc2_ksplit = 2 over X [M][K] (M / B positions x B clips): returns (Y, part,
+        R as read back) with Y = R + bias + X[:, :K/2] . W[:, :K/2]^T and part = X[:, K/2:] . W[:, K/2:]^T; Y and part
+        start as NaN."""
+        X, W, bias = _f32(X), _f32(W), _f32(bias)
+        R = np.array(R, np.float32, order="C")
+        M, K = X.shape
+        N = W.shape[0]
+        Y = np.full((M, N), np.nan, np.float32)
+        part = np.full((M, N), np.nan, np.float32)
+        self._check(lib().wt_dbg_dec_gemm_ksplit(self._h, int(bf16), M, B or M, N, K, _fp(X), _fp(W), _fp(bias), _fp(R),
+                                                 _fp(Y), _fp(part)))
+        return Y, part, R
+
+    def dbg_dec_ln_gemm_rows(self, W, bias, ln_g, ln_b, xin=None, xpart=None, ids=None, pos=0, tok_emb=None, pos_emb=None,
+                             B=None, M=None, gelu=False, bf16=False, xout=None):
+        """LayerNorm prologue + GEMM over a row source: xin [M][K] (LNMODE 0), xin + xpart (3), or embedding rows from
+        ids [B][stride] for M = positions x B rows (2).  xout [M + 1][K] (zeros when not given) is in / out, its last row
+        a guard.  Returns (Y [M][N], xout)."""
+        W, bias, ln_g, ln_b = _f32(W), _f32(bias), _f32(ln_g), _f32(ln_b)
+        N, K = W.shape
+        xin = _f32(xin) if xin is not None else None
+        xpart = _f32(xpart) if xpart is not None else None
+        ids_a = np.ascontiguousarray(ids, dtype=np.int64) if ids is not None else None
+        tok_emb = _f32(tok_emb) if tok_emb is not None else None
+        pos_emb = _f32(pos_emb) if pos_emb is not None else None
+        if ids_a is not None:
+            B, stride = ids_a.shape
+            M = M or B
+        else:
+            M, stride = xin.shape[0], 0
+            B = B or M
+        xout = np.array(xout, np.float32, order="C") if xout is not None else np.zeros((M + 1, K), np.float32)
+        assert xout.shape == (M + 1, K)
+        Y = np.zeros((M, N), np.float32)
+        self._check(lib().wt_dbg_dec_ln_gemm_rows(
+            self._h, int(bf16), M, B, N, K, _fp(xin), _fp(xpart), _ip64(ids_a) if ids_a is not None else None, stride, pos,
+            _fp(tok_emb), _fp(pos_emb), tok_emb.shape[0] if tok_emb is not None else 0,
+            pos_emb.shape[0] if pos_emb is not None else 0, _fp(ln_g), _fp(ln_b), _fp(W), _fp(bias), int(gelu), _fp(Y),
+            _fp(xout)))
+        return Y, xout
+
+    def dbg_dec_logits(self, xin, ln_g, ln_b, E, xpart=None, blocks=0, bf16=False, want_logits=True,
+                       logits_guard=1.0e30, records_guard=0xA5A5A5A5A5A5A5A5):
+        """Final LayerNorm of xin [M][K] (+ xpart), logits against E [V][K] and the per-tile argmax records on `blocks`
+        resident blocks (0 = 512).  Returns (logits [M + 1][V] or None, records uint64 [M + 1][ceil(V / 32)]); both
+        start filled with the guard values, and their last rows must keep them."""
+        xin, ln_g, ln_b, E = _f32(xin), _f32(ln_g), _f32(ln_b), _f32(E)
+        xpart = _f32(xpart) if xpart is not None else None
+        M, K = xin.shape
+        V = E.shape[0]
+        logits = np.full((M + 1, V), logits_guard, np.float32) if want_logits else None
+        records = np.full((M + 1, (V + 31) // 32), records_guard, np.uint64)
+        self._check(lib().wt_dbg_dec_logits(self._h, int(bf16), M, V, K, _fp(xin), _fp(xpart), _fp(ln_g), _fp(ln_b), _fp(E),
+                                            blocks, _fp(logits), records.ctypes.data_as(POINTER(c_uint64))))
+        return logits, records
+
+    def dbg_select_token(self, records, ids, pos, n_ids, finished, eot, stop_at_eot=True, keep_ids=False):
+        """select_token over records uint64 [B][n_tiles]; ids int64 [B][stride], n_ids / finished int32 [B] are copied
+        and returned updated: (ids, n_ids, finished)."""
+        records = np.ascontiguousarray(records, dtype=np.uint64)
+        B, n_tiles = records.shape
+        ids = np.array(ids, np.int64, order="C")
+        n_ids = np.array(n_ids, np.int32, order="C")
+        finished = np.array(finished, np.int32, order="C")
+        self._check(lib().wt_dbg_select_token(self._h, B, n_tiles, records.ctypes.data_as(POINTER(c_uint64)), _ip64(ids),
+                                              ids.shape[1], pos, _ip32(n_ids), _ip32(finished), int(eot), int(stop_at_eot),
+                                              int(keep_ids)))
+        return ids, n_ids, finished
 
 
 class DeviceArray:

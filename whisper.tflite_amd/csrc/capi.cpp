@@ -1649,4 +1649,111 @@ int wt_dbg_beam_finalize(wt_engine* h, int K, int clips, int c0, int pos, int n_
   });
 }
 
+// ------------------------------------------- the greedy step's tail, kernel by kernel ---
+int wt_dbg_dec_gemm_ksplit(wt_engine* h, int bf16, int M, int B, int N, int K, const float* X, const float* W,
+                           const float* bias, float* R, float* Y, float* part) {
+  if (!h || !X || !W || !bias || !R || !Y || !part || B < 1 || M < B || M > 128 || M % B != 0 || N < 1 || K < 1) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const bool bf = bf16 != 0;
+    const DevTiled dW(W, N, K, bf);
+    const size_t mn = size_t(M) * N;
+    DevArr<float> dX(size_t(M) * K, X), dB(N, bias), dR(mn, R), dY(mn, Y), dP(mn, part);
+    wt::DecGemmArgs g;  // the engine's fc2 with fc2_ksplit = 2: out of place, second K-half into `part`
+    g.bf16 = bf;
+    g.Wt = dW.w(); g.w_scale = dW.scale; g.N = N; g.K = K; g.B = B; g.M = M; g.X = dX.p; g.ldx = K;
+    g.bias = dB.p; g.R = dR.p; g.Y = dY.p; g.ldy = N; g.ksplit = 2; g.part = dP.p;
+    wt::launch_dec_gemm(g, wt::kProNone, wt::kDecResid, h->impl->stream());
+    h->impl->sync();
+    dR.to_host(R);
+    dY.to_host(Y);
+    dP.to_host(part);
+  });
+}
+
+int wt_dbg_dec_ln_gemm_rows(wt_engine* h, int bf16, int M, int B, int N, int K, const float* xin, const float* xpart,
+                            const int64_t* ids, int ids_stride, int pos, const float* tok_emb, const float* pos_emb,
+                            int n_vocab, int n_pos, const float* ln_g, const float* ln_b, const float* W, const float* bias,
+                            int gelu, float* Y, float* xout) {
+  if (!h || !ln_g || !ln_b || !W || !bias || !Y || !xout || B < 1 || M < B || M > 128 || M % B != 0 || N < 1 ||
+      (K != 128 && K != 384 && K != 512) || (ids ? (xin || xpart) : !xin)) {
+    return WT_ERR_INVALID_ARG;
+  }
+  const int np = M / B;
+  if (ids && (!tok_emb || !pos_emb || n_vocab < 1 || pos < 0 || pos + np > ids_stride || pos + np > n_pos)) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const bool bf = bf16 != 0;
+    const DevTiled dW(W, N, K, bf);
+    const size_t mk = size_t(M) * K;
+    DevArr<float> dxin(xin ? mk : 0, xin), dxp(xpart ? mk : 0, xpart);
+    DevArr<long long> dids(ids ? size_t(B) * ids_stride : 0, reinterpret_cast<const long long*>(ids));
+    DevArr<float> dtok(ids ? size_t(n_vocab) * K : 0, tok_emb), dpos(ids ? size_t(n_pos) * K : 0, pos_emb);
+    DevArr<float> dg(K, ln_g), db(K, ln_b), dB(N, bias), dY(size_t(M) * N);
+    DevArr<float> dxo(mk + K, xout);  // [M + 1][K]: the last row is a guard the kernel must not write
+    wt::DecGemmArgs g;
+    g.bf16 = bf;
+    g.Wt = dW.w(); g.w_scale = dW.scale; g.N = N; g.K = K; g.B = B; g.M = M;
+    g.ln_g = dg.p; g.ln_b = db.p; g.xout = dxo.p;
+    if (ids) {  // LNMODE 2: row p * B + b = tok_emb[ids[b][pos + p]] + pos_emb[pos + p]
+      g.ids = dids.p; g.ids_stride = ids_stride; g.pos = pos; g.tok_emb = dtok.p; g.pos_emb = dpos.p; g.n_vocab = n_vocab;
+    } else {    // LNMODE 0 (xin) or 3 (xin + xpart)
+      g.xin = dxin.p; g.xpart = xpart ? dxp.p : nullptr;
+    }
+    g.bias = dB.p; g.Y = dY.p; g.ldy = N;
+    wt::launch_dec_gemm(g, wt::kProLn, gelu ? wt::kDecBiasGelu : wt::kDecBias, h->impl->stream());
+    h->impl->sync();
+    dY.to_host(Y);
+    dxo.to_host(xout);
+  });
+}
+
+int wt_dbg_dec_logits(wt_engine* h, int bf16, int M, int V, int K, const float* xin, const float* xpart, const float* ln_g,
+                      const float* ln_b, const float* E, int blocks, float* logits, uint64_t* records) {
+  if (!h || !xin || !ln_g || !ln_b || !E || !records || M < 1 || M > 128 || V < 1 || blocks < 0 ||
+      (K != 128 && K != 384 && K != 512)) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const bool bf = bf16 != 0;
+    const int n_tiles = (V + 31) / 32;
+    const DevTiled dE(E, V, K, bf);
+    const size_t mk = size_t(M) * K;
+    DevArr<float> dxin(mk, xin), dxp(xpart ? mk : 0, xpart), dg(K, ln_g), db(K, ln_b);
+    // [M + 1][V] and [M + 1][n_tiles]: the last row of each is a guard the kernel must not write
+    DevArr<float> dY(logits ? (size_t(M) + 1) * V : 0, logits);
+    DevArr<unsigned long long> dBest((size_t(M) + 1) * n_tiles, reinterpret_cast<const unsigned long long*>(records));
+    wt::DecGemmArgs g;  // the engine's final LayerNorm + logits + argmax records
+    g.bf16 = bf;
+    g.logits_blocks = blocks;
+    g.Wt = dE.w(); g.w_scale = dE.scale; g.N = V; g.K = K; g.B = M; g.M = M;
+    g.xin = dxin.p; g.xpart = xpart ? dxp.p : nullptr; g.ln_g = dg.p; g.ln_b = db.p;
+    g.Y = logits ? dY.p : nullptr; g.ldy = V; g.best = dBest.p;
+    wt::launch_dec_gemm(g, wt::kProLn, wt::kDecLogits, h->impl->stream());
+    h->impl->sync();
+    if (logits) dY.to_host(logits);
+    dBest.to_host(reinterpret_cast<unsigned long long*>(records));
+  });
+}
+
+int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* records, int64_t* ids, int stride, int pos,
+                        int32_t* n_ids, int32_t* finished, int64_t eot, int stop_at_eot, int keep_ids) {
+  if (!h || !records || !ids || !n_ids || !finished || B < 1 || n_tiles < 1 || pos < 0 || pos + 1 >= stride) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    DevArr<unsigned long long> dRec(size_t(B) * n_tiles, reinterpret_cast<const unsigned long long*>(records));
+    DevArr<long long> dids(size_t(B) * stride, reinterpret_cast<const long long*>(ids));
+    DevArr<int> dn(B, n_ids), dfin(B, finished);
+    wt::launch_select_token(dRec.p, n_tiles, dids.p, stride, pos, dn.p, dfin.p, eot, stop_at_eot, B, h->impl->stream(),
+                            keep_ids != 0);
+    h->impl->sync();
+    dids.to_host(reinterpret_cast<long long*>(ids));
+    dn.to_host(n_ids);
+    dfin.to_host(finished);
+  });
+}
+
 }  // extern "C"
