@@ -82,6 +82,23 @@ int wt_dbg_cross_absorbed(wt_engine* h, int batch, int heads, int T, int chunks,
 /* the same with E as ONE bf16 plane (bf16 storage mode): queries and probabilities rounded to bf16 in the kernel */
 int wt_dbg_cross_absorbed_bf16(wt_engine* h, int batch, int heads, int T, int chunks, int nq, const float* qp, const float* E,
                                const float* wv, const float* bv, float* out, int iters, float* avg_us);
+/* the absorbed cross-attention as a decoder chain runs it (Engine::decode's position loop, then cross_absorbed_combine):
+ * bf16 != 0 selects the one-plane form.  n_src (1..4) encoder batches of `split` clips each, the last one shorter:
+ * E_src[i] [clips of group i][T][d] on the host, every source a device allocation of its own with room for `batch`
+ * clips at ONE plane stride and ONE e_scale (from the maximum over all sources); the clips a group does not have hold
+ * NaN, so a wrong source or clip offset shows.  n_src == 1 needs split == batch.  qp [nq * batch][heads * d], wv [d][d],
+ * bv [d].  out [nq * batch + 1][d] and ws [nq * batch + 1][heads][chunks][d + 4] (the raw workspace: c[d], m, l, pad per
+ * record) are in / out, the last row of each a guard the kernels must not write.
+ * mode 0: positions in steps of cross_absorbed_max_nq(heads), then combine; 1: ONE attention launch over positions
+ * p0_only .. p0_only + nq_only - 1, then combine; 2: combine alone over the given ws (E_src, qp unused).
+ * A shape the launcher refuses is WT_ERR_INVALID_ARG, before anything is launched. */
+int wt_dbg_cross_absorbed_chain(wt_engine* h, int bf16, int batch, int heads, int T, int chunks, int nq, int split, int n_src,
+                                const float* const* E_src, const float* qp, const float* wv, const float* bv, int mode,
+                                int p0_only, int nq_only, float* out, float* ws);
+/* the host fold of the absorbed query projection (absorbed_query_matrix, engine.cpp): wq, wk [d][d] row-major, bq [d],
+ * d = 64 * heads -> A [heads * d][d] (A_h = c0 Wk_h^T Wq_h), av [heads * d] (a_h = c0 Wk_h^T bq_h),
+ * c0 = 1/8 log2 e.  Needs no engine and no GPU. */
+int wt_dbg_absorbed_query_matrix(int heads, int d, const float* wq, const float* bq, const float* wk, float* A, float* av);
 int wt_dbg_self_attention(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
                           float* kcache, float* vcache, float* out);
 /* bf16 storage mode kernels (option "bf16"): operands are rounded to bf16 on the host, contracted by

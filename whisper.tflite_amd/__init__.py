@@ -54,6 +54,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_self_attention_bf16", "wt_dbg_cross_attention_bf16", "wt_dbg_encoder_attention_planes", "wt_dbg_gemm_bf16", "wt_dbg_gemm_bf16_ln", "wt_dbg_encoder_attention_bf16",
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
+    "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix",
 ]
 
 
@@ -147,6 +148,9 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_encoder_attention_planes.argtypes = [c_void_p, c_int, c_int, c_int, fp, c_int, fp, POINTER(c_float)]
         L.wt_dbg_cross_absorbed.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp, fp, c_int, POINTER(c_float)]
         L.wt_dbg_cross_absorbed_bf16.argtypes = L.wt_dbg_cross_absorbed.argtypes
+        L.wt_dbg_cross_absorbed_chain.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(fp),
+                                                  fp, fp, fp, c_int, c_int, c_int, fp, fp]
+        L.wt_dbg_absorbed_query_matrix.argtypes = [c_int, c_int, fp, fp, fp, fp, fp]
         L.wt_dbg_gemm_planes_ln.argtypes = [c_void_p, c_int, c_int, fp, fp, fp, fp, fp, c_int, c_int, fp, fp, c_int, fp, fp, fp,
                                             POINTER(c_int)]
         L.wt_dbg_gemm_bf16.argtypes = [c_void_p, c_int, c_int, c_int, fp, fp, fp, fp, fp, c_int, c_int, c_int, c_int, fp,
@@ -220,6 +224,20 @@ def write_synthetic_vocab(path: str, n_tokens: int = 50257) -> None:
     rc = lib().wt_write_synthetic_vocab(path.encode(), n_tokens)
     if rc != WT_OK:
         raise WtError(rc, lib().wt_last_error(None).decode())
+
+
+def absorbed_query_matrix(wq, bq, wk):
+    """The host fold of the absorbed cross-attention's query projection (no engine, no GPU): wq, wk [d][d], bq [d] ->
+    A [heads * d][d] = c0 Wk_h^T Wq_h stacked over the heads and a [heads * d] = c0 Wk_h^T bq_h, c0 = 1/8 log2 e."""
+    wq, bq, wk = _f32(wq), _f32(bq), _f32(wk)
+    d = wq.shape[0]
+    heads = d // 64
+    A = np.zeros((heads * d, d), np.float32)
+    av = np.zeros(heads * d, np.float32)
+    rc = lib().wt_dbg_absorbed_query_matrix(heads, d, _fp(wq), _fp(bq), _fp(wk), _fp(A), _fp(av))
+    if rc != WT_OK:
+        raise WtError(rc, "absorbed_query_matrix: bad shape")
+    return A, av
 
 
 def language_id(code: str) -> int:
@@ -560,6 +578,28 @@ class Engine:
         fn = lib().wt_dbg_cross_absorbed_bf16 if bf16 else lib().wt_dbg_cross_absorbed
         self._check(fn(self._h, batch, heads, T, chunks, nq, _fp(qp), _fp(E), _fp(wv), _fp(bv), _fp(out), iters, byref(us)))
         return (out, us.value) if iters > 0 else out
+
+    def dbg_cross_absorbed_chain(self, qp, E_src, wv, bv, batch, heads, T, chunks, nq, split=None, bf16=False, only=None,
+                                 combine_only=False, ws=None, out=None, ws_fill=-7.0, out_fill=-9.0):
+        """The absorbed cross-attention as a decoder chain runs it: E_src is a list of 1..4 arrays [clips of the group][T][d]
+        (clip b reads E_src[b // split][b % split]), qp [nq * batch][heads * d].  only = (p0, nq) restricts the attention
+        to that ONE launch; combine_only skips it (ws then holds hand-made records).  Returns (out [nq * batch + 1][d],
+        ws [nq * batch + 1][heads][chunks][d + 4]); both start from the given arrays or the fills, and their last rows
+        are guards the kernels must leave alone."""
+        d, rows = heads * 64, nq * batch
+        wv, bv = _f32(wv), _f32(bv)
+        srcs = [_f32(e) for e in (E_src or [])]
+        qp = _f32(qp) if qp is not None else None
+        ws = np.array(ws, np.float32, order="C") if ws is not None else np.full((rows + 1, heads, chunks, d + 4), ws_fill, np.float32)
+        out = np.array(out, np.float32, order="C") if out is not None else np.full((rows + 1, d), out_fill, np.float32)
+        assert ws.shape == (rows + 1, heads, chunks, d + 4) and out.shape == (rows + 1, d)
+        ptrs = (POINTER(c_float) * max(1, len(srcs)))(*[_fp(e) for e in srcs])
+        mode = 2 if combine_only else (1 if only is not None else 0)
+        p0, n1 = only if only is not None else (0, 0)
+        self._check(lib().wt_dbg_cross_absorbed_chain(
+            self._h, int(bf16), batch, heads, T, chunks, nq, batch if split is None else split, len(srcs), ptrs, _fp(qp),
+            _fp(wv), _fp(bv), mode, p0, n1, _fp(out), _fp(ws)))
+        return out, ws
 
     def dbg_encoder_attention_planes(self, qkv, batch, T, heads, iters=0):
         qkv = _f32(qkv)

@@ -1756,4 +1756,87 @@ int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* record
   });
 }
 
+int wt_dbg_cross_absorbed_chain(wt_engine* h, int bf16, int batch, int heads, int T, int chunks, int nq, int split, int n_src,
+                                const float* const* E_src, const float* qp, const float* wv, const float* bv, int mode,
+                                int p0_only, int nq_only, float* out, float* ws) {
+  if (!h || !wv || !bv || !out || !ws || batch < 1 || heads < 1 || heads > 8 || T < 1 || nq < 1 || chunks < 1 || chunks > 16 ||
+      size_t(nq) * batch > 128 || mode < 0 || mode > 2) {
+    return WT_ERR_INVALID_ARG;
+  }
+  if (mode != 2) {
+    if (!qp || !E_src || n_src < 1 || n_src > 4 || split < 1 || split > batch || (n_src == 1 && split != batch)) return WT_ERR_INVALID_ARG;
+    for (int i = 0; i < n_src; ++i)
+      if (!E_src[i]) return WT_ERR_INVALID_ARG;
+    // a single launch must stay inside the nq positions ws and qp were sized for
+    if (mode == 1 && (p0_only < 0 || nq_only < 1 || p0_only + nq_only > nq)) return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const bool bf = bf16 != 0;
+    const size_t d = size_t(heads) * 64, rows = size_t(nq) * batch, clip = size_t(T) * d;
+    const std::vector<float> wvt = wt::cross_q_layout(wv, int(d));
+    DevArr<float> dwv(wvt.size(), wvt.data()), dbv(d, bv), dq(mode != 2 ? rows * heads * d : 0, qp);
+    // [rows + 1][...]: the last row of each is a guard the kernels must not write
+    DevArr<float> dws((rows + 1) * heads * chunks * (d + 4), ws), dout((rows + 1) * d, out);
+    hipStream_t st = h->impl->stream();
+    // Every source is an allocation of its own with room for `batch` clips at ONE plane stride; the clips a group does
+    // not have hold NaN halfs, so a wrong source or clip offset reads poison instead of some other clip's bytes.
+    const size_t plane = size_t(batch) * clip + 64;
+    std::vector<std::unique_ptr<DevArr<unsigned short>>> src;
+    float se = 1.0f;
+    if (mode != 2) {
+      const auto clips_of = [&](int i) { return std::max(0, std::min(split, batch - i * split)); };
+      float mx = 0.0f;
+      for (int i = 0; i < n_src; ++i) mx = std::max(mx, max_abs(E_src[i], size_t(clips_of(i)) * clip));
+      se = bf ? 1.0f : wt::f16_scale_for(mx);  // one scale for all sources, as the engine's sc_cross_kv_
+      for (int i = 0; i < n_src; ++i) {
+        const size_t n = size_t(clips_of(i)) * clip;
+        std::vector<unsigned short> host((bf ? 1 : 2) * plane, bf ? 0x7FC0 : 0x7E00);
+        for (size_t k = 0; k < n; ++k) {
+          if (bf) {
+            host[k] = DevBf16::rne(E_src[i][k]);
+          } else {
+            const float v = E_src[i][k] * se;
+            const _Float16 hi = static_cast<_Float16>(v), lo = static_cast<_Float16>(v - static_cast<float>(hi));
+            std::memcpy(&host[k], &hi, 2);
+            std::memcpy(&host[plane + k], &lo, 2);
+          }
+        }
+        src.push_back(std::make_unique<DevArr<unsigned short>>(host.size(), host.data()));
+      }
+      const int nq_max = wt::cross_absorbed_max_nq(heads);
+      const auto launch = [&](int p0, int n) {
+        wt::CrossAbsorbedArgs a;
+        a.qp = dq.p; a.e = src[0]->p; a.e_plane = long(plane); a.e_scale = se; a.ws = dws.p; a.bf16 = bf;
+        if (n_src > 1) {
+          a.split = split;
+          a.e2 = src[1]->p;
+          if (n_src > 2) a.e3 = src[2]->p;
+          if (n_src > 3) a.e4 = src[3]->p;
+        }
+        a.batch = batch; a.heads = heads; a.d_model = int(d); a.T = T; a.chunks = chunks; a.nq = n; a.p0 = p0;
+        wt::launch_cross_absorbed(a, st);
+      };
+      if (mode == 1) {
+        launch(p0_only, nq_only);
+      } else {
+        for (int p0 = 0; p0 < nq; p0 += nq_max) launch(p0, std::min(nq_max, nq - p0));  // Engine::decode's loop
+      }
+    }
+    wt::launch_cross_absorbed_combine(dws.p, dwv.p, dbv.p, dout.p, int(rows), heads, chunks, int(d), st);
+    h->impl->sync();
+    dout.to_host(out);
+    dws.to_host(ws);
+  });
+}
+
+int wt_dbg_absorbed_query_matrix(int heads, int d, const float* wq, const float* bq, const float* wk, float* A, float* av) {
+  if (heads < 1 || d != heads * 64 || !wq || !bq || !wk || !A || !av) return WT_ERR_INVALID_ARG;
+  return guarded(nullptr, [&] {
+    std::vector<float> Am, am;
+    wt::absorbed_query_matrix(wq, bq, wk, heads, d, &Am, &am);
+    std::memcpy(A, Am.data(), Am.size() * sizeof(float));
+    std::memcpy(av, am.data(), am.size() * sizeof(float));
+  });
+}
+
 }  // extern "C"

@@ -215,8 +215,8 @@ void check_wtw_file(const std::string& path) {
 // The fused query matrix of the absorbed cross-attention, folded once, in double: A_h = c0 Wk_h^T Wq_h stacked over the
 // heads ([heads * d][d]: row (h, c) gives column c of head h's d-wide query) and a_h = c0 Wk_h^T bq_h, with
 // c0 = d_head^-1/2 log2 e (the kernel's softmax is an exp2).
-static void absorbed_query_matrix(const float* wq, const float* bq, const float* wk, int heads, int d, std::vector<float>* A,
-                                  std::vector<float>* av) {
+void absorbed_query_matrix(const float* wq, const float* bq, const float* wk, int heads, int d, std::vector<float>* A,
+                           std::vector<float>* av) {
   const double c0 = 0.125 * 1.44269504088896340736;
   A->assign(size_t(heads) * d * d, 0.0f);
   av->assign(size_t(heads) * d, 0.0f);

@@ -323,10 +323,12 @@ __global__ __launch_bounds__(320) void cross_absorbed_attention(CrossAbsDev a) {
     // accumulator register r of this lane: key 4 lq + r of its sub-tile, query column qc
     const int kbase = key_lo + t * 32 + 4 * lq;
     if (kbase + 32 > key_hi) {  // the chunk's last tile: keys past its end do not exist
+      // -inf, not a large finite value: the mask is applied BEFORE the multiplication by s_inv, which is as small as
+      // 2^-109 / e_scale for tiny queries (-1e30 s_inv then stayed near 0 and the masked keys kept weight ~1)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        if (kbase + r >= key_hi) s0[r] = -1e30f;
-        if (kbase + 16 + r >= key_hi) s1[r] = -1e30f;
+        if (kbase + r >= key_hi) s0[r] = -__builtin_inff();
+        if (kbase + 16 + r >= key_hi) s1[r] = -__builtin_inff();
       }
     }
     // -- online softmax per query column (a column lives on lanes qc, qc + 16, qc + 32, qc + 48), deferred maximum

@@ -370,5 +370,9 @@ std::vector<unsigned short> tile_weights_bf16(const float* W, int N, int K);
 std::vector<unsigned short> tile_weights_f16(const float* W, int N, int K, float* scale);
 // Wq [d][d] -> [head][d / 4][64 outputs][4 k] for cross_attention_step's in-kernel query projection
 std::vector<float> cross_q_layout(const float* Wq, int d);
+// The absorbed cross-attention's fused query matrix (engine.cpp): A [heads * d][d], A_h = c0 Wk_h^T Wq_h, and
+// av [heads * d], a_h = c0 Wk_h^T bq_h, c0 = d_head^-1/2 log2 e; wq, wk [d][d] row-major, bq [d].  Host only.
+void absorbed_query_matrix(const float* wq, const float* bq, const float* wk, int heads, int d, std::vector<float>* A,
+                           std::vector<float>* av);
 
 }  // namespace wt
