@@ -116,6 +116,8 @@ struct Monolith : public Engine {
   Monolith& operator=(const Monolith&) = delete;
   std::string transcribe(std::vector<float>& samples) final;
   std::string transcribe(const char* waveFile) final;
+  // an addition: as EncDec::detect_language
+  std::pair<int, float> detect_language(std::vector<float>& samples);
   wt_engine* handle() const { return handle_; }
 
  private:
@@ -135,6 +137,10 @@ struct EncDec : public Engine {
   // Pads/truncates the CALLER's vector to 480000 samples like the reference (whisper.cpp:753).
   std::string transcribe(std::vector<float>& samples) final;
   std::string transcribe(const char* waveFile) final;
+  // An addition to the reference's interface: the spoken language of the first 30 s of `samples` (not modified) as
+  // {index into language_meta / lang_code, its probability among the language tokens}; encoder + one decoder position,
+  // nothing is transcribed.  Throws std::runtime_error for an English-only engine or on a device error.
+  std::pair<int, float> detect_language(std::vector<float>& samples);
   // for the batch entry points and options of wt_capi.h: wt_engine_set_option(handle(), "beam_size", 5) makes both
   // transcribe() overloads decode with beam search
   wt_engine* handle() const { return handle_; }

@@ -75,7 +75,10 @@ const char* wt_last_error(const wt_engine* h);
 int wt_engine_dims(const wt_engine* h, wt_dims* out);
 
 /* Options (reference hard-codes them): "language" (prompt language id, whisper.cpp:327,
- * default language_id("de") = 2), "max_tokens" (max decoder positions, whisper.cpp:364,
+ * default language_id("de") = 2; WT_LANGUAGE_AUTO = -1: every greedy decode — synchronous, long-audio and pipelined —
+ * detects the language of each clip on the device from the logits at the sot position and puts its token at ids[b][1],
+ * DESIGN.md section 12; WT_ERR_UNSUPPORTED on a Monolith engine and without language tokens, and at the call together
+ * with beam_size > 1, a caller prompt or the forced-ids tap), "max_tokens" (max decoder positions, whisper.cpp:364,
  * default 30), "stop_at_eot" (whisper.cpp:397-399, default 1), "verbose" (default 0),
  * "cross_chunks" (key chunks per (clip, head) in the decoder cross attention: 1, 2, 4, 8, or 0 = by batch size, the default).
  * Kernel selection (results stay within the fp32 error budget for every value): "gemm_variant"
@@ -181,6 +184,23 @@ int wt_encdec_debug_batch(wt_engine* h, const float* mel, int batch, int64_t* id
                           float* enc_out, float* logits, int logits_steps_cap);
 
 int wt_last_timings(const wt_engine* h, wt_timings* out);
+
+/* Spoken-language detection: softmax over the language tokens of the logits at the sot position. */
+#define WT_LANGUAGE_AUTO (-1)
+/* number of language tokens of this engine's vocabulary (99 for 51865), or -WT_ERR_UNSUPPORTED (an English-only engine,
+ * or a vocabulary that ends before the language tokens) */
+int wt_language_count(const wt_engine* h);
+/* encoder + one decoder position + language head, nothing else decoded (beam_size and a caller prompt do not matter):
+ * lang [B] (index into wt_lang_code), probs [B][wt_language_count()] or NULL */
+int wt_detect_language_batch(wt_engine* h, const float* mel, int batch, int32_t* lang, float* probs);
+int wt_detect_language_batch_dev(wt_engine* h, const float* d_mel, int batch, int32_t* lang, float* probs);
+/* the same for one clip of PCM, padded or truncated to 30 s as wt_transcribe_pcm: *lang and its probability (prob may be NULL) */
+int wt_detect_language_pcm(wt_engine* h, const float* pcm, size_t n_samples, int32_t* lang, float* prob);
+/* after a synchronous decode with "language" = WT_LANGUAGE_AUTO (a batch call of up to 64 clips, wt_transcribe_pcm /
+ * _file, or wt_transcribe_long_pcm: one entry per window): per clip the language used and its probability (at most cap
+ * entries written).  Returns the clip count, or -WT_ERR_INVALID_ARG when the last synchronous decode did not detect
+ * (as wt_last_beam_scores).  Pipelined batches carry the language in their ids: ids[b][1] - 50259. */
+int wt_last_languages(const wt_engine* h, int32_t* lang, float* prob, int cap);
 
 /* Beam search (option "beam_size" > 1): for every clip of the last synchronous beam call, the chosen hypothesis's sum of
  * natural-log probabilities and its number of generated ids, EOT included (at most cap entries written).  Returns the

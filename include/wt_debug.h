@@ -171,6 +171,13 @@ int wt_dbg_dec_logits(wt_engine* h, int bf16, int M, int V, int K, const float* 
 /* select_token over records [B][n_tiles]; ids [B][stride], n_ids [B], finished [B] in / out */
 int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* records, int64_t* ids, int stride, int pos,
                         int32_t* n_ids, int32_t* finished, int64_t eot, int stop_at_eot, int keep_ids);
+/* language_head (k_misc.hip) over host rows x [rows][d] (+ xpart [rows][d] or NULL), the final LayerNorm's ln_g, ln_b [d]
+ * and an embedding table tok_emb [n_vocab][d] (n_vocab <= 4096) whose rows lang_lo .. lang_lo + n_lang - 1 are the
+ * language rows: probs [rows][n_lang], lang [rows], lang_prob [rows]; ids [rows][ids_stride] in / out (may be NULL):
+ * ids[b][1] = lang_lo + lang[b].  forced_lang >= 0: lang, lang_prob and the id report that language, not the argmax. */
+int wt_dbg_language_head(wt_engine* h, int rows, int d, int n_vocab, int lang_lo, int n_lang, int forced_lang, const float* x,
+                         const float* xpart, const float* ln_g, const float* ln_b, const float* tok_emb, float* probs,
+                         int32_t* lang, float* lang_prob, int64_t* ids, int ids_stride);
 #ifdef __cplusplus
 }
 #endif

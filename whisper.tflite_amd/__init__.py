@@ -30,6 +30,7 @@ LIB_PATH = os.environ.get("WT_LIB_PATH") or os.path.join(_HERE, "lib", "libwhisp
 WT_OK = 0
 WT_MAX_IDS = 32
 WT_PIPELINE_DEPTH = 24  # include/wt_capi.h
+WT_LANGUAGE_AUTO = -1  # option "language": detected per clip
 CHUNK_SAMPLES = 480000
 STATUS_NAMES = {0: "WT_OK", 1: "WT_ERR_INVALID_ARG", 2: "WT_ERR_IO", 3: "WT_ERR_FORMAT",
                 4: "WT_ERR_UNSUPPORTED", 5: "WT_ERR_DEVICE", 6: "WT_ERR_BUFFER"}
@@ -42,6 +43,7 @@ CAPI_SYMBOLS = [
     "wt_logmel_batch", "wt_logmel_batch_dev", "wt_encdec_tokens_batch",
     "wt_encdec_tokens_batch_dev", "wt_transcribe_tokens_batch_dev", "wt_pipeline_submit_dev", "wt_pipeline_submit_pcm_dev", "wt_pipeline_collect",
     "wt_encdec_debug_batch",
+    "wt_language_count", "wt_detect_language_batch", "wt_detect_language_batch_dev", "wt_detect_language_pcm", "wt_last_languages",
     "wt_last_timings", "wt_last_beam_scores", "wt_last_kernel_stats", "wt_decode_text", "wt_language_id", "wt_lang_code", "wt_wav_read_legacy",
     "wt_vocab_info", "wt_filters", "wt_write_synthetic_weights", "wt_write_synthetic_vocab",
     "wt_vocab_open", "wt_vocab_close", "wt_vocab_get_info", "wt_vocab_get_filters", "wt_vocab_size", "wt_vocab_token",
@@ -54,7 +56,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_self_attention_bf16", "wt_dbg_cross_attention_bf16", "wt_dbg_encoder_attention_planes", "wt_dbg_gemm_bf16", "wt_dbg_gemm_bf16_ln", "wt_dbg_encoder_attention_bf16",
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
-    "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix",
+    "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head",
 ]
 
 
@@ -190,6 +192,13 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_dec_logits.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp, fp, c_int, fp, u64p]
         L.wt_dbg_select_token.argtypes = [c_void_p, c_int, c_int, u64p, ip64, c_int, c_int, ip32, ip32, c_int64, c_int,
                                           c_int]
+        L.wt_language_count.argtypes = [c_void_p]
+        L.wt_detect_language_batch.argtypes = [c_void_p, fp, c_int, ip32, fp]
+        L.wt_detect_language_batch_dev.argtypes = [c_void_p, c_void_p, c_int, ip32, fp]
+        L.wt_detect_language_pcm.argtypes = [c_void_p, fp, c_size_t, ip32, fp]
+        L.wt_last_languages.argtypes = [c_void_p, ip32, fp, c_int]
+        L.wt_dbg_language_head.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp, fp, fp, ip32, fp,
+                                           ip64, c_int]
         _lib = L
     return _lib
 
@@ -491,6 +500,48 @@ class Engine:
         lens = np.zeros(n, np.int32)
         lib().wt_last_beam_scores(self._h, _fp(sums), lens.ctypes.data_as(POINTER(c_int32)), n)
         return sums, lens
+
+    # -- spoken-language detection ---------------------------
+    def language_count(self) -> int:
+        """Language tokens of this engine's vocabulary (99 for 51865 entries); WtError when it has none."""
+        n = lib().wt_language_count(self._h)
+        if n < 0:
+            raise WtError(-n, "this engine's vocabulary has no language tokens")
+        return n
+
+    def detect_language(self, mel):
+        """Encoder + one decoder position + language head: (lang int32 [B], probs float32 [B][language_count()])."""
+        mel = _f32(mel).reshape((-1,) + self.mel_shape)
+        B = mel.shape[0]
+        n_lang = max(lib().wt_language_count(self._h), 1)
+        lang = np.zeros(B, np.int32)
+        probs = np.zeros((B, n_lang), np.float32)
+        self._check(lib().wt_detect_language_batch(self._h, _fp(mel), B, _ip32(lang), _fp(probs)))
+        return lang, probs
+
+    def detect_language_dev(self, d_mel_ptr: int, batch: int):
+        n_lang = max(lib().wt_language_count(self._h), 1)
+        lang = np.zeros(batch, np.int32)
+        probs = np.zeros((batch, n_lang), np.float32)
+        self._check(lib().wt_detect_language_batch_dev(self._h, c_void_p(d_mel_ptr), batch, _ip32(lang), _fp(probs)))
+        return lang, probs
+
+    def detect_language_pcm(self, samples):
+        """One clip of PCM (padded or truncated to one window): (lang, probability)."""
+        pcm = _f32(samples).reshape(-1)
+        lang, prob = c_int32(0), c_float(0)
+        self._check(lib().wt_detect_language_pcm(self._h, _fp(pcm), pcm.size, byref(lang), byref(prob)))
+        return lang.value, prob.value
+
+    def last_languages(self):
+        """After a synchronous decode with language = -1: (lang int32 [B], probability float32 [B]) per clip."""
+        n = lib().wt_last_languages(self._h, None, None, 0)
+        if n < 0:
+            raise WtError(-n, "the last synchronous decode did not detect the language")
+        lang = np.zeros(n, np.int32)
+        prob = np.zeros(n, np.float32)
+        lib().wt_last_languages(self._h, _ip32(lang), _fp(prob), n)
+        return lang, prob
 
     def kernel_stats(self) -> dict:
         arr = (KernelStat * 8)()
@@ -856,6 +907,22 @@ class Engine:
         self._check(lib().wt_dbg_dec_logits(self._h, int(bf16), M, V, K, _fp(xin), _fp(xpart), _fp(ln_g), _fp(ln_b), _fp(E),
                                             blocks, _fp(logits), records.ctypes.data_as(POINTER(c_uint64))))
         return logits, records
+
+    def dbg_language_head(self, x, ln_g, ln_b, tok_emb, lang_lo, n_lang, xpart=None, ids=None, forced_lang=-1):
+        """language_head over rows x [rows][d] (+ xpart) against tok_emb [n_vocab][d], language rows lang_lo .. lang_lo +
+        n_lang - 1.  Returns (probs [rows][n_lang], lang [rows], lang_prob [rows], ids copy or None)."""
+        x, ln_g, ln_b, tok_emb = _f32(x), _f32(ln_g), _f32(ln_b), _f32(tok_emb)
+        xpart = _f32(xpart) if xpart is not None else None
+        rows, d = x.shape
+        probs = np.full((rows, n_lang), np.nan, np.float32)
+        lang = np.full(rows, -1, np.int32)
+        prob = np.full(rows, np.nan, np.float32)
+        ids = np.array(ids, np.int64, order="C") if ids is not None else None
+        self._check(lib().wt_dbg_language_head(
+            self._h, rows, d, tok_emb.shape[0], lang_lo, n_lang, forced_lang, _fp(x), _fp(xpart), _fp(ln_g), _fp(ln_b),
+            _fp(tok_emb), _fp(probs), _ip32(lang), _fp(prob), _ip64(ids) if ids is not None else None,
+            ids.shape[1] if ids is not None else 0))
+        return probs, lang, prob, ids
 
     def dbg_select_token(self, records, ids, pos, n_ids, finished, eot, stop_at_eot=True, keep_ids=False):
         """select_token over records uint64 [B][n_tiles]; ids int64 [B][stride], n_ids / finished int32 [B] are copied

@@ -1,6 +1,7 @@
 // encdec — same command line as the reference's app/encdec.cpp:30-36:
 //   encdec --model-prefix P --vocab V --input WAV
-// prints the transcript followed by '\n' as the last line of stdout.  The reference pulls
+// prints the transcript followed by '\n' as the last line of stdout (with --lang auto, a line
+// "language: <code> (p=...)" per 30 s window before it).  The reference pulls
 // in the 11 kLoC CLI11 header for three required options; a minimal parser keeps the same
 // flags (and --flag=value spelling) and exit status on a usage error.
 #include <cstdlib>
@@ -20,7 +21,8 @@ void usage(const char* argv0) {
             << "  --model-prefix  Model prefix (loads <prefix>.wtw)   REQUIRED\n"
             << "  --vocab         Path to vocabulary                 REQUIRED\n"
             << "  --input         Path to the 16 kHz mono WAV        REQUIRED\n"
-            << "  --lang          language code of the prompt (default de, as the reference hard-codes)\n"
+            << "  --lang          language code of the prompt (default de, as the reference hard-codes), or auto:\n"
+            << "                  detected per 30 s window, printed as \"language: <code> (p=...)\" before the transcript\n"
             << "  --english       English-only vocabulary ids (multilingual = false; the reference hard-codes true)\n"
             << "  --long          transcribe every 30 s window of the file, not only the first\n"
             << "  --beam N        beam search with N hypotheses, 2..8 (default: greedy, as the reference)\n";
@@ -82,8 +84,13 @@ int main(int argc, char* argv[]) {
   }
   EncDec& encdec = *engine;
   if (!lang.empty()) {
-    const int id = language_id(lang);
-    if (wt_engine_set_option(encdec.handle(), "language", id) != WT_OK) {
+    const int id = lang == "auto" ? WT_LANGUAGE_AUTO : language_id(lang);
+    const int rc = wt_engine_set_option(encdec.handle(), "language", id);
+    if (rc == WT_ERR_UNSUPPORTED) {
+      std::cerr << "--lang auto: " << wt_last_error(encdec.handle()) << "\n";
+      return 105;
+    }
+    if (rc != WT_OK) {
       std::cerr << "--lang: unknown language code " << lang << "\n";
       return 105;
     }
@@ -112,6 +119,16 @@ int main(int argc, char* argv[]) {
     // look like an empty transcript
     const char* err = wt_last_error(encdec.handle());
     if (err && *err) return 2;
+  }
+  if (lang == "auto") {  // the languages the decode just used, one per window
+    std::vector<int32_t> l(1);
+    std::vector<float> p(1);
+    const int n = wt_last_languages(encdec.handle(), l.data(), p.data(), 0);
+    if (n > 0) {
+      l.resize(size_t(n)), p.resize(size_t(n));
+      wt_last_languages(encdec.handle(), l.data(), p.data(), n);
+      for (int i = 0; i < n; ++i) std::cout << "language: " << lang_code(size_t(l[i])) << " (p=" << p[i] << ")\n";
+    }
   }
   std::cout << text << "\n";
   return 0;

@@ -187,8 +187,11 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
   wt::Engine& e = *h->impl;
   const std::string k(key);
   if (k == "language") {
-    if (value < 0 || value >= wt::language_count()) return fail(h, WT_ERR_INVALID_ARG, "language id out of range");
-    e.language = value;
+    try {  // WT_LANGUAGE_AUTO (-1): detected per clip; unsupported on a Monolith engine or without language tokens
+      e.set_language(value);
+    } catch (const wt::Error& err) {
+      return fail(h, err.code, err.what());
+    }
   } else if (k == "max_tokens") {
     if (value < 4 || value > 31) return fail(h, WT_ERR_INVALID_ARG, "max_tokens must be in [4, 31]");
     e.max_tokens = value;
@@ -451,6 +454,7 @@ int wt_encdec_debug_batch(wt_engine* h, const float* mel, int batch, int64_t* id
   return guarded(h, [&] {
     wt::Engine& e = *h->impl;
     e.require_idle();
+    e.check_language_call();
     e.check_beam_call(logits != nullptr);  // (before the encoder pass)
     float* d_mel = e.staging_mel(batch);
     hipchk(hipMemcpyAsync(d_mel, mel, size_t(batch) * e.mel_elems() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D mel");
@@ -485,6 +489,73 @@ int wt_last_beam_scores(const wt_engine* h, float* sum_logprob, int32_t* n_gener
   for (int i = 0; i < n && i < cap; ++i) {
     sum_logprob[i] = e.beam_sum[i];
     n_generated[i] = e.beam_len[i];
+  }
+  return n;
+}
+
+// ------------------------------------------------- language detection ---
+
+int wt_language_count(const wt_engine* h) {
+  if (!h) return -WT_ERR_INVALID_ARG;
+  const int n = h->impl->lang_tokens();
+  return n > 0 ? n : -WT_ERR_UNSUPPORTED;
+}
+
+int wt_detect_language_batch_dev(wt_engine* h, const float* d_mel, int batch, int32_t* lang, float* probs) {
+  if (!h || !d_mel || !lang || batch < 1) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::Engine& e = *h->impl;
+    e.require_idle();
+    const int n_lang = e.lang_tokens();
+    if (n_lang < 1) throw wt::Error(WT_ERR_UNSUPPORTED, "language detection: this engine's vocabulary has no language tokens");
+    for (int b0 = 0; b0 < batch; b0 += 64) {  // one encoder pass + one decoder position per 64 clips
+      const int nb = std::min(64, batch - b0);
+      e.encode(d_mel + size_t(b0) * e.mel_elems(), nb);
+      e.detect_language(nb, lang + b0, probs ? probs + size_t(b0) * n_lang : nullptr, nullptr);
+    }
+  });
+}
+
+int wt_detect_language_batch(wt_engine* h, const float* mel, int batch, int32_t* lang, float* probs) {
+  if (!h || !mel || !lang || batch < 1) return WT_ERR_INVALID_ARG;
+  float* d_mel = nullptr;
+  const int rc = guarded(h, [&] {
+    wt::Engine& e = *h->impl;
+    e.require_idle();
+    if (e.lang_tokens() < 1) throw wt::Error(WT_ERR_UNSUPPORTED, "language detection: this engine's vocabulary has no language tokens");
+    d_mel = e.staging_mel(batch);
+    hipchk(hipMemcpyAsync(d_mel, mel, size_t(batch) * e.mel_elems() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D mel");
+  });
+  if (rc != WT_OK) return rc;
+  return wt_detect_language_batch_dev(h, d_mel, batch, lang, probs);  // (its decoder pass waits for the copy's stream)
+}
+
+int wt_detect_language_pcm(wt_engine* h, const float* pcm, size_t n_samples, int32_t* lang, float* prob) {
+  if (!h || (!pcm && n_samples) || !lang) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::Engine& e = *h->impl;
+    e.require_idle();
+    if (e.lang_tokens() < 1) throw wt::Error(WT_ERR_UNSUPPORTED, "language detection: this engine's vocabulary has no language tokens");
+    std::vector<float> clip(e.pcm_elems(), 0.0f);  // one 30 s window, as wt_transcribe_pcm
+    std::memcpy(clip.data(), pcm, std::min(n_samples, clip.size()) * sizeof(float));
+    float* d_pcm = e.staging_pcm(1);
+    float* d_mel = e.staging_mel(1);
+    hipchk(hipMemcpyAsync(d_pcm, clip.data(), clip.size() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D pcm");
+    e.logmel(d_pcm, 1, d_mel);
+    e.encode(d_mel, 1);
+    e.detect_language(1, lang, nullptr, prob);
+    e.sync();
+  });
+}
+
+int wt_last_languages(const wt_engine* h, int32_t* lang, float* prob, int cap) {
+  if (!h || cap < 0 || (cap > 0 && (!lang || !prob))) return -WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_lang_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last_lang.size());
+  for (int i = 0; i < n && i < cap; ++i) {
+    lang[i] = e.last_lang[i];
+    prob[i] = e.last_lang_prob[i];
   }
   return n;
 }
@@ -545,6 +616,8 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
     e.require_idle();
     const size_t win = e.pcm_elems();
     const size_t n_win = std::max<size_t>(1, (n_samples + win - 1) / win);
+    std::vector<int> langs;  // automatic language: every window's, joined over the batches
+    std::vector<float> lang_probs;
     for (size_t w0 = 0; w0 < n_win; w0 += 32) {
       const int B = int(std::min<size_t>(32, n_win - w0));
       std::vector<float> clips(size_t(B) * win, 0.0f);
@@ -561,12 +634,17 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
       std::vector<int32_t> n(B);
       e.decode(B, ids.data(), n.data(), nullptr, 0);
       e.sync();  // clips[] is read by the H2D copy on the encoder stream
+      if (e.last_lang_valid) {
+        langs.insert(langs.end(), e.last_lang.begin(), e.last_lang.end());
+        lang_probs.insert(lang_probs.end(), e.last_lang_prob.begin(), e.last_lang_prob.end());
+      }
       for (int b = 0; b < B; ++b) {
         if (w0 + b) text += '\n';
         bool missing = false;
         text += wt::decode_tokens(e.vocab(), &ids[size_t(b) * WT_MAX_IDS], n[b], false, &missing);
       }
     }
+    if (e.last_lang_valid) e.last_lang = langs, e.last_lang_prob = lang_probs;
   });
   if (rc != WT_OK) {
     if (len) *len = 0;
@@ -1753,6 +1831,34 @@ int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* record
     dids.to_host(reinterpret_cast<long long*>(ids));
     dn.to_host(n_ids);
     dfin.to_host(finished);
+  });
+}
+
+int wt_dbg_language_head(wt_engine* h, int rows, int d, int n_vocab, int lang_lo, int n_lang, int forced_lang, const float* x,
+                         const float* xpart, const float* ln_g, const float* ln_b, const float* tok_emb, float* probs,
+                         int32_t* lang, float* lang_prob, int64_t* ids, int ids_stride) {
+  if (!h || !x || !ln_g || !ln_b || !tok_emb || !probs || !lang || !lang_prob || rows < 1 || rows > 128 || d < 1 ||
+      d > wt::kLangMaxD || n_vocab < 1 || n_vocab > 4096 || lang_lo < 0 || n_lang < 1 || n_lang > wt::kLangMax ||
+      lang_lo + n_lang > n_vocab || forced_lang >= n_lang || (ids && ids_stride < 2)) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const size_t rd = size_t(rows) * d;
+    DevArr<float> dx(rd, x), dxp(xpart ? rd : 0, xpart), dg(d, ln_g), db(d, ln_b), demb(size_t(n_vocab) * d, tok_emb);
+    DevArr<float> dprobs(size_t(rows) * n_lang), dprob(rows);
+    DevArr<int> dlang(rows);
+    DevArr<long long> dids(ids ? size_t(rows) * ids_stride : 0, reinterpret_cast<const long long*>(ids));
+    wt::LanguageHeadArgs a;
+    a.x = dx.p; a.xpart = xpart ? dxp.p : nullptr; a.ln_g = dg.p; a.ln_b = db.p; a.tok_emb = demb.p;
+    a.rows = rows; a.d = d; a.n_vocab = n_vocab; a.lang_lo = lang_lo; a.n_lang = n_lang;
+    a.probs = dprobs.p; a.lang = dlang.p; a.lang_prob = dprob.p; a.forced_lang = forced_lang;
+    if (ids) a.ids = dids.p, a.ids_stride = ids_stride, a.id_pos = 1;
+    wt::launch_language_head(a, h->impl->stream());
+    h->impl->sync();
+    dprobs.to_host(probs);
+    dprob.to_host(lang_prob);
+    dlang.to_host(lang);
+    if (ids) dids.to_host(reinterpret_cast<long long*>(ids));
   });
 }
 

@@ -866,6 +866,10 @@ void Engine::release() noexcept {
   for (void* p : {static_cast<void*>(bw_.h_prompt), static_cast<void*>(bw_.h_sum), static_cast<void*>(bw_.h_len)})
     if (p) (void)hipHostFree(p);
   bw_ = BeamWorkspace();  // (its device buffers are in allocations_)
+  for (void* p : {static_cast<void*>(h_lang_probs_), static_cast<void*>(h_lang_prob_), static_cast<void*>(h_lang_)})
+    if (p) (void)hipHostFree(p);
+  h_lang_probs_ = nullptr, h_lang_prob_ = nullptr, h_lang_ = nullptr;
+  for (LangWorkspace& lw : lw_) lw = LangWorkspace();
   if (ev_switch_) (void)hipEventDestroy(ev_switch_);
   if (trace_base_) (void)hipEventDestroy(trace_base_);
   ev_switch_ = nullptr, trace_base_ = nullptr;
@@ -1617,7 +1621,9 @@ void Engine::set_bf16(bool on) {
 void Engine::decode(int batch, int64_t* ids, int32_t* n_ids, float* logits_host,
                     int logits_steps_cap) {
   require_idle();
+  check_language_call();
   check_beam_call(logits_host != nullptr);
+  last_lang_valid = false;
   if (beam_size > 1) {
     decode_beam(batch, last_enc_slot_, ids, n_ids);
     return;
@@ -1625,6 +1631,79 @@ void Engine::decode(int batch, int64_t* ids, int32_t* n_ids, float* logits_host,
   beam_scores_valid = false;
   decode_enqueue(batch, last_enc_slot_, logits_host, logits_steps_cap);
   decode_collect(last_enc_slot_, ids, n_ids);
+  if (language < 0) {  // the chain's language_head results came back with the ids (pinned copies, decode_enqueue)
+    last_lang.assign(h_lang_, h_lang_ + batch);
+    last_lang_prob.assign(h_lang_prob_, h_lang_prob_ + batch);
+    last_lang_valid = true;
+  }
+}
+
+// -------------------------------------------------- language detection ---
+
+int Engine::lang_tokens() const {
+  if (!multilingual_ || vocab_.token_translate > dims_.n_vocab) return 0;
+  return int(std::max<long>(0, std::min<long>(std::min(language_count(), kLangMax), vocab_.token_translate - kLangLo)));
+}
+
+void Engine::check_language_call() const {
+  if (language >= 0) return;
+  auto no = [](const char* why) { throw Error(kErrUnsupported, std::string("automatic language: ") + why); };
+  if (lang_tokens() < 1) no("this engine's vocabulary has no language tokens");
+  if (monolith_) no("the Monolith engine forces <|en|>");
+  if (beam_size > 1) no("not with beam search (beam_size > 1)");
+  if (!prompt_override.empty()) no("not with a caller prompt (wt_engine_set_prompt)");
+  if (!forced_ids.empty()) no("not with forced ids");
+}
+
+void Engine::set_language(long value) {
+  if (value < -1 || value >= language_count()) throw Error(kErrInvalidArg, "language id out of range (-1 = automatic)");
+  if (value < 0) {
+    if (monolith_) throw Error(kErrUnsupported, "automatic language: the Monolith engine forces <|en|>");
+    if (lang_tokens() < 1) throw Error(kErrUnsupported, "automatic language: this engine's vocabulary has no language tokens");
+  }
+  language = value;
+}
+
+void Engine::ensure_lang_workspace() {
+  if (h_lang_) return;  // (allocated last)
+  auto alloc = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    allocations_.push_back(p);
+    HIPCHK(hipMemset(p, 0, bytes));
+    return p;
+  };
+  for (LangWorkspace& lw : lw_) {
+    lw.probs = static_cast<float*>(alloc(size_t(kDecRowsMax) * kLangMax * sizeof(float)));
+    lw.prob = static_cast<float*>(alloc(kDecRowsMax * sizeof(float)));
+    lw.lang = static_cast<int*>(alloc(kDecRowsMax * sizeof(int)));
+  }
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h_lang_probs_), size_t(kDecRowsMax) * kLangMax * sizeof(float), hipHostMallocDefault));
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h_lang_prob_), kDecRowsMax * sizeof(float), hipHostMallocDefault));
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h_lang_), kDecRowsMax * sizeof(int), hipHostMallocDefault));
+}
+
+void Engine::detect_language(int batch, int32_t* lang, float* probs, float* prob) {
+  require_idle();
+  const int n_lang = lang_tokens();
+  if (n_lang < 1) throw Error(kErrUnsupported, "language detection: this engine's vocabulary has no language tokens");
+  if (batch < 1 || batch > 64) throw Error(kErrInvalidArg, "language detection takes 1 to 64 clips per call");
+  detect_only_ = true;
+  try {
+    decode_enqueue(batch, last_enc_slot_, nullptr, 0);
+  } catch (...) {
+    detect_only_ = false;
+    throw;
+  }
+  detect_only_ = false;
+  std::vector<int64_t> ids(size_t(batch) * 32);
+  std::vector<int32_t> n(batch);
+  decode_collect(last_enc_slot_, ids.data(), n.data());
+  for (int b = 0; b < batch; ++b) {
+    if (lang) lang[b] = h_lang_[b];
+    if (prob) prob[b] = h_lang_prob_[b];
+    if (probs) std::memcpy(probs + size_t(b) * n_lang, h_lang_probs_ + size_t(b) * n_lang, size_t(n_lang) * sizeof(float));
+  }
 }
 
 void Engine::flush_pending() {
@@ -1678,6 +1757,8 @@ void Engine::submit_decoder(int batch, int s) {
 
 void Engine::submit(const float* d_mel, int batch) {
   if (beam_size > 1) throw Error(kErrUnsupported, "beam search runs on the synchronous entry points only, not in the pipeline");
+  check_language_call();
+  last_lang_valid = false;
   if (int(inflight_.size()) >= kSlots) throw Error(1, "pipeline is full (24 batches in flight): collect() first");
   if (batch > 64) throw Error(1, "decoder batches are limited to 64 clips per call");
   select_stream(true);
@@ -1688,6 +1769,8 @@ void Engine::submit(const float* d_mel, int batch) {
 
 void Engine::submit_pcm(const float* d_pcm, int batch) {
   if (beam_size > 1) throw Error(kErrUnsupported, "beam search runs on the synchronous entry points only, not in the pipeline");
+  check_language_call();
+  last_lang_valid = false;
   if (int(inflight_.size()) >= kSlots) throw Error(1, "pipeline is full (24 batches in flight): collect() first");
   if (batch > 64) throw Error(1, "decoder batches are limited to 64 clips per call");
   select_stream(true);
@@ -1715,7 +1798,8 @@ std::vector<long long> Engine::prompt() const {
   // (export/generate.py:24-30): English-only checkpoints [sot, notimestamps] — the head of kGoldenGeneratedIDs,
   // whisper.h:27-32 — multilingual ones [sot, language, transcribe, notimestamps].
   if (monolith_ && !multilingual_) return {vocab_.token_sot, vocab_.token_not};
-  return {vocab_.token_sot, 50259 + language, vocab_.token_transcribe, vocab_.token_not};
+  // (language = -1: position 1 is a placeholder that language_head overwrites on the device, decode_enqueue)
+  return {vocab_.token_sot, kLangLo + std::max<long>(language, 0), vocab_.token_transcribe, vocab_.token_not};
 }
 
 void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int logits_steps_cap, int group, bool pipelined,
@@ -1744,17 +1828,27 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
   int* const h_n_ = slot.h_n;
   const wtw::Dims& c = dims_;
   const int d = c.n_text_state, T = c.n_audio_ctx, H = c.n_text_head, V = c.n_vocab;
-  const std::vector<long long> prompt = this->prompt();
+  // Language mode of the chain: 0 = the prompt names the language; 1 = language -1: position 0 goes through the layers
+  // alone, language_head writes ids[b][1] on the device, and the rest of the prompt follows in the usual grouping;
+  // 2 = detection alone (detect_language): that first pass over [sot] and the head, nothing else
+  const int lang_mode = detect_only_ ? 2 : (language < 0 ? 1 : 0);
+  const int n_lang = lang_mode ? lang_tokens() : 0;
+  if (lang_mode) {
+    if (n_lang < 1) throw Error(kErrUnsupported, "language detection: this engine's vocabulary has no language tokens");
+    ensure_lang_workspace();  // (before any capture: nothing may be allocated inside one)
+  }
+  const std::vector<long long> prompt = lang_mode == 2 ? std::vector<long long>{vocab_.token_sot} : this->prompt();
   const int n_prompt = int(prompt.size()), stride = 32;
   for (long long id : prompt) {
     if (id < 0 || id >= V) throw Error(1, "prompt token id outside the model's vocabulary");
   }
-  const int max_pos = int(std::min<long>(std::max<long>(max_tokens, n_prompt), 31));
-  const bool forced = !forced_ids.empty();
+  const int max_pos = lang_mode == 2 ? 1 : int(std::min<long>(std::max<long>(max_tokens, n_prompt), 31));
+  const bool forced = !forced_ids.empty() && lang_mode != 2;
   if (forced && forced_ids.size() != size_t(batch) * stride) {
     throw Error(kErrInvalidArg, "forced ids are set for another number of clips than this decode has");
   }
   for (long long id : forced_ids) {
+    if (!forced) break;
     if (id < 0 || id >= V) throw Error(kErrInvalidArg, "forced token id outside the model's vocabulary");
   }
   for (int b = 0; b < batch; ++b) {
@@ -1832,6 +1926,7 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
     const int prompt_end = std::min(n_prompt, max_pos);
     for (int pos0 = 0, np = 1; pos0 < max_pos; pos0 += np) {
       np = pos0 < prompt_end ? std::min(np_max, prompt_end - pos0) : 1;
+      if (lang_mode && pos0 == 0) np = 1;  // the language is read off position 0 before position 1 can be embedded
       const int M = np * batch, last = pos0 + np - 1;
       for (int l = 0; l < c.n_text_layer; ++l) {
         const DecBlockWeights& w = bf ? dec_blocks_bf_[l] : dec_blocks_[l];
@@ -1918,7 +2013,24 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
         }
         DT(7, launch_dec_gemm(f2, kProNone, kDecResid, stream_));
       }
-      if (last >= n_prompt - 1) {
+      if (lang_mode && pos0 == 0) {
+        // position 0's residual rows -> language probabilities and ids[b][1]; no logits GEMM at this position
+        LangWorkspace& lw = lw_[dec_of(si)];
+        LanguageHeadArgs la;
+        la.x = split ? dw.xb : x; la.xpart = split ? dw.xpart : nullptr; la.ln_g = dec_ln_g; la.ln_b = dec_ln_b;
+        la.tok_emb = tok_emb; la.rows = batch; la.d = d; la.n_vocab = V; la.lang_lo = int(kLangLo); la.n_lang = n_lang;
+        la.probs = lw.probs; la.lang = lw.lang; la.lang_prob = lw.prob;
+        if (lang_mode == 1) la.ids = dw.ids, la.ids_stride = stride, la.id_pos = 1;
+        DT(10, launch_language_head(la, stream_));
+        if (!pipelined) {  // a synchronous call reads them after decode_collect (pipelined callers read ids[b][1])
+          HIPCHK(hipMemcpyAsync(h_lang_, lw.lang, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, stream_));
+          HIPCHK(hipMemcpyAsync(h_lang_prob_, lw.prob, size_t(batch) * sizeof(float), hipMemcpyDeviceToHost, stream_));
+          if (lang_mode == 2) {
+            HIPCHK(hipMemcpyAsync(h_lang_probs_, lw.probs, size_t(batch) * n_lang * sizeof(float), hipMemcpyDeviceToHost, stream_));
+          }
+        }
+      }
+      if (last >= n_prompt - 1 && lang_mode != 2) {
         // logits against the tied embedding + greedy argmax (whisper.cpp:379-399); only the
         // last position's rows exist here, the reference computes and drops the others
         const size_t off = size_t(np - 1) * batch * d;
@@ -1952,7 +2064,7 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
   // kernels' one-time attribute set-up) and then captures one hipGraph per slot; later calls
   // replay the slot's graph: one host call instead of ~1100. The logits tap stays eager.
   auto key_of = [&](int si) {
-    return std::vector<long long>{si, batch, max_pos, n_prompt, chunks, long(stop_at_eot), fc2_ksplit, bf16, absorbed ? 1 : 0, n_abs, group, stream_override, forced ? 1 : 0, pipelined ? 1 : 0};
+    return std::vector<long long>{si, batch, max_pos, n_prompt, chunks, long(stop_at_eot), fc2_ksplit, bf16, absorbed ? 1 : 0, n_abs, group, stream_override, forced ? 1 : 0, pipelined ? 1 : 0, lang_mode};
   };
   // the cached form's graphs are captured for EVERY slot at once (below) and hold each slot's cache pointer: all of
   // them must exist before the capture (need_cross_kv allocates; nothing may be allocated inside a capture)

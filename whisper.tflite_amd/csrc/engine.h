@@ -90,7 +90,7 @@ class Engine {
   hipStream_t decoder_stream(int i) const { return dstream_[i % n_dec_streams_]; }
 
   // options (reference hard-codes them, see wt_capi.h)
-  long language = 2;  // language_id("de")
+  long language = 2;  // language_id("de"); -1 = detected per clip on the device (language_head)
   long max_tokens = 30;
   long stop_at_eot = 1;
   long verbose = 0;
@@ -136,6 +136,22 @@ class Engine {
   std::vector<float> beam_sum;
   std::vector<int> beam_len;
   bool beam_scores_valid = false;
+  // Spoken-language detection.  The language tokens are ids [kLangLo, kLangLo + lang_tokens()): lang_tokens() =
+  // min(language_count(), token_translate - kLangLo), or 0 when the engine has none (English-only, or a vocabulary
+  // that ends before them).  language = -1 makes every greedy decode detect per clip (decode_enqueue); scope:
+  // no beam search, no caller prompt, no forced ids, no Monolith engine (check_language_call).
+  static constexpr long kLangLo = 50259;
+  int lang_tokens() const;
+  // option "language": -1 .. language_count() - 1; -1 is kErrUnsupported on a Monolith engine or without language tokens
+  void set_language(long value);
+  void check_language_call() const;  // throws kErrUnsupported when language = -1 and the options fall outside that scope
+  // encoder output of the last encode() -> one decoder pass over position 0 of [sot] + language_head, nothing else
+  // decoded: lang [batch], probs [batch][lang_tokens()] (or nullptr), prob [batch] (or nullptr).  batch <= 64.
+  void detect_language(int batch, int32_t* lang, float* probs, float* prob);
+  // per clip of the last synchronous decode with language = -1: the language used and its probability
+  std::vector<int> last_lang;
+  std::vector<float> last_lang_prob;
+  bool last_lang_valid = false;
   long gemm_variant = -1;  // -1 = plane GEMM (per-contraction fall-back to 13/16); 0 = fp32 MFMA, 13 / 16 = three bf16 planes
   // 1 = bf16 STORAGE mode (BASELINE configs[3]): bf16 weights, activations and both KV caches, fp32 accumulation,
   // fp32 residual stream; k_gemm_bf16.hip and the BF variants of the attention / decoder kernels.  Set through
@@ -390,6 +406,16 @@ class Engine {
     long long* ids = nullptr;
     int *n_ids = nullptr, *finished = nullptr;
   } dws_[kDecStreams + 1];  // one per decoder stream, + one for a chain on the encoder stream (kEncAsDec)
+  // language_head outputs, one set per decoder workspace (128 rows whatever the batch), and the pinned copies a
+  // synchronous call reads; allocated by the first detecting call
+  struct LangWorkspace {
+    float *probs = nullptr, *prob = nullptr;  // [128][kLangMax], [128]
+    int* lang = nullptr;                      // [128]
+  } lw_[kDecStreams + 1];
+  float *h_lang_probs_ = nullptr, *h_lang_prob_ = nullptr;
+  int* h_lang_ = nullptr;
+  void ensure_lang_workspace();
+  bool detect_only_ = false;  // set by detect_language() around its decode_enqueue
   struct Workspace {
     int batch = 0;
     float *melT = nullptr, *h1p = nullptr, *x = nullptr, *ln = nullptr, *qkv = nullptr,

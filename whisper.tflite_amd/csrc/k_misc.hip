@@ -337,7 +337,98 @@ __global__ __launch_bounds__(256) void select_token(const unsigned long long* __
   }
 }
 
+// Block sum in one fixed order: lanes by butterfly, then the four wavefront partials left to right.  Every thread
+// gets the same value; red[] may be reused after the call.
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  __syncthreads();  // the previous use of red[] is over
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// Spoken-language head, one block per clip: final LayerNorm of the clip's position-0 residual row (x, or x + xpart
+// after a K-split fc2), the n_lang logits against embedding rows lang_lo .. lang_lo + n_lang - 1, softmax over those
+// logits alone, and the argmax with the project's tie rule (larger logit, then larger id).  Wavefronts take
+// embedding rows, lanes stride over d, every reduction is a fixed butterfly: a clip's result depends on its own row
+// only, not on the grid or its place in it.  forced_lang >= 0: lang / lang_prob / the id report that language
+// instead of the argmax (probs unchanged).  ids != nullptr: ids[b][id_pos] = lang_lo + lang.
+// Contract: finite row, d <= kLangMaxD, 1 <= n_lang <= kLangMax, the embedding rows inside the table (launcher).
+__global__ __launch_bounds__(256) void language_head(const float* __restrict__ x, const float* __restrict__ xpart,
+                                                     const float* __restrict__ g, const float* __restrict__ bta,
+                                                     const float* __restrict__ tok_emb, int d, int lang_lo, int n_lang,
+                                                     float* __restrict__ probs, int* __restrict__ lang,
+                                                     float* __restrict__ lang_prob, long long* ids, int ids_stride,
+                                                     int id_pos, int forced_lang) {
+  __shared__ float ys[kLangMaxD];
+  __shared__ float zs[kLangMax];
+  __shared__ float red[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* row = x + (long)b * d;
+  const float* prow = xpart ? xpart + (long)b * d : nullptr;
+  float s = 0.0f;
+  for (int i = tid; i < d; i += 256) {
+    const float v = prow ? row[i] + prow[i] : row[i];
+    ys[i] = v;
+    s += v;
+  }
+  const float mean = block_sum_256(s, red) / (float)d;
+  float q = 0.0f;
+  for (int i = tid; i < d; i += 256) {
+    const float t = ys[i] - mean;
+    q += t * t;
+  }
+  const float rstd = rsqrtf(block_sum_256(q, red) / (float)d + 1e-5f);
+  for (int i = tid; i < d; i += 256) ys[i] = (ys[i] - mean) * rstd * g[i] + bta[i];
+  __syncthreads();
+  for (int r = wave; r < n_lang; r += 4) {
+    const float* e = tok_emb + (long)(lang_lo + r) * d;
+    float acc = 0.0f;
+    for (int i = lane; i < d; i += 64) acc = fmaf(ys[i], e[i], acc);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane == 0) zs[r] = acc;
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  // softmax and argmax over zs[0 .. n_lang) by the first wavefront: lane l owns entries l and l + 64
+  float bz = -INFINITY;
+  int bi = -1;
+  for (int r = lane; r < n_lang; r += 64) {
+    if (zs[r] >= bz) bz = zs[r], bi = r;  // ascending r: an equal logit at a larger id wins
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float oz = __shfl_xor(bz, off, 64);
+    const int oi = __shfl_xor(bi, off, 64);
+    if (oz > bz || (oz == bz && oi > bi)) bz = oz, bi = oi;
+  }
+  float sum = 0.0f;
+  for (int r = lane; r < n_lang; r += 64) sum += expf(zs[r] - bz);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
+  const float inv = 1.0f / sum;
+  for (int r = lane; r < n_lang; r += 64) probs[(long)b * n_lang + r] = expf(zs[r] - bz) * inv;
+  if (lane != 0) return;
+  if (forced_lang >= 0) bi = forced_lang < n_lang ? forced_lang : n_lang - 1;
+  bi = bi < 0 ? 0 : bi;  // (a non-finite row breaks the contract; the index stays inside the range all the same)
+  lang[b] = bi;
+  lang_prob[b] = expf(zs[bi] - bz) * inv;
+  if (ids) ids[(long)b * ids_stride + id_pos] = (long long)lang_lo + bi;
+}
+
 }  // namespace
+
+void launch_language_head(const LanguageHeadArgs& a, hipStream_t s) {
+  if (a.rows < 1 || a.d < 1 || a.d > kLangMaxD || a.n_lang < 1 || a.n_lang > kLangMax || a.lang_lo < 0 ||
+      long(a.lang_lo) + a.n_lang > long(a.n_vocab) || !a.x || !a.ln_g || !a.ln_b || !a.tok_emb || !a.probs || !a.lang ||
+      !a.lang_prob || a.forced_lang >= a.n_lang || (a.ids && (a.id_pos < 0 || a.id_pos >= a.ids_stride))) {
+    throw Error(kErrInvalidArg, "language_head: bad shape or language range");
+  }
+  hipLaunchKernelGGL(language_head, dim3(a.rows), dim3(256), 0, s, a.x, a.xpart, a.ln_g, a.ln_b, a.tok_emb, a.d, a.lang_lo,
+                     a.n_lang, a.probs, a.lang, a.lang_prob, a.ids, a.ids_stride, a.id_pos, a.forced_lang < 0 ? -1 : a.forced_lang);
+}
 
 void launch_layernorm(const float* x, float* y, const float* g, const float* b, int M, int d,
                       hipStream_t s, int* nonfinite) {

@@ -306,6 +306,25 @@ void launch_select_token(const unsigned long long* best, int n_tiles, long long*
                          int pos, int* n_ids, int* finished, long long eot, int stop_at_eot, int batch,
                          hipStream_t s, bool keep_ids = false);
 
+// Spoken-language head (k_misc.hip, option "language" = -1 and wt_detect_language_*): per clip the final LayerNorm of
+// its position-0 residual row (x [rows][d], + xpart when a K-split fc2 left two halves), the logits against the fp32
+// embedding rows lang_lo .. lang_lo + n_lang - 1, softmax over those alone and the argmax (larger logit, then larger
+// id).  probs [rows][n_lang], lang / lang_prob [rows]; ids != nullptr: ids[b][id_pos] = lang_lo + lang[b].
+// forced_lang >= 0 (test tap): lang, lang_prob and the id report that language instead of the argmax.
+constexpr int kLangMax = 128;    // language tokens (Whisper has 99 or 100)
+constexpr int kLangMaxD = 1280;  // d_model of the largest Whisper
+struct LanguageHeadArgs {
+  const float *x = nullptr, *xpart = nullptr, *ln_g = nullptr, *ln_b = nullptr;
+  const float* tok_emb = nullptr;  // [n_vocab][d]
+  int rows = 0, d = 0, n_vocab = 0, lang_lo = 0, n_lang = 0;
+  float* probs = nullptr;
+  int* lang = nullptr;
+  float* lang_prob = nullptr;
+  long long* ids = nullptr;
+  int ids_stride = 0, id_pos = 1, forced_lang = -1;
+};
+void launch_language_head(const LanguageHeadArgs& a, hipStream_t s);
+
 // ----------------------------------------------------------- beam search ---
 // k_beam.hip (option beam_size 2..8).  Rows of a step are laid out row = k * clips + c (hypothesis slot k of clip c);
 // the id rows are [row][32] int64 and the self-attention caches [layer][k|v][row][cap][d] as in launch_self_attention.

@@ -69,6 +69,19 @@ EncDec::~EncDec() { wt_engine_destroy(handle_); }
 std::string EncDec::transcribe(std::vector<float>& samples) { return transcribe_samples(handle_, samples); }
 std::string EncDec::transcribe(const char* waveFile) { return transcribe_wav(handle_, waveFile); }
 
+namespace {
+std::pair<int, float> detect_samples(wt_engine* h, const std::vector<float>& samples) {
+  int32_t lang = 0;
+  float prob = 0.0f;
+  if (wt_detect_language_pcm(h, samples.data(), samples.size(), &lang, &prob) != WT_OK) {
+    throw std::runtime_error(std::string("detect_language: ") + wt_last_error(h));
+  }
+  return {int(lang), prob};
+}
+}  // namespace
+std::pair<int, float> EncDec::detect_language(std::vector<float>& samples) { return detect_samples(handle_, samples); }
+std::pair<int, float> Monolith::detect_language(std::vector<float>& samples) { return detect_samples(handle_, samples); }
+
 Monolith::Monolith(const std::string& model_prefix, const std::string& vocab_path, bool multilingual)
     : handle_(open_engine(WT_ENGINE_MONOLITH, model_prefix, vocab_path, multilingual)) {}
 Monolith::~Monolith() { wt_engine_destroy(handle_); }
