@@ -79,7 +79,9 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * detects the language of each clip on the device from the logits at the sot position and puts its token at ids[b][1],
  * DESIGN.md section 12; WT_ERR_UNSUPPORTED on a Monolith engine and without language tokens, and at the call together
  * with beam_size > 1, a caller prompt or the forced-ids tap), "max_tokens" (max decoder positions, whisper.cpp:364,
- * default 30), "stop_at_eot" (whisper.cpp:397-399, default 1), "verbose" (default 0),
+ * default 30), "max_positions" (0 = default: off, the max_tokens path with its 31 positions; 32 .. n_text_ctx = full-length
+ * greedy decoding on the wt_*_tokens_full_batch* and the text entry points, see below and DESIGN.md section 13),
+ * "stop_at_eot" (whisper.cpp:397-399, default 1), "verbose" (default 0),
  * "cross_chunks" (key chunks per (clip, head) in the decoder cross attention: 1, 2, 4, 8, or 0 = by batch size, the default).
  * Kernel selection (results stay within the fp32 error budget for every value): "gemm_variant"
  * (-1 = default: every encoder GEMM on the plane kernel, operands as two fp16 planes with power-of-two scales
@@ -163,6 +165,20 @@ int wt_encdec_tokens_batch_dev(wt_engine* h, const float* d_mel, int batch, int6
 /* PCM -> ids in one call (front end + encoder + decoder), device-resident input. */
 int wt_transcribe_tokens_batch_dev(wt_engine* h, const float* d_pcm, int batch, int64_t* ids,
                                    int32_t* n_ids);
+
+/* Full-length greedy decoding (option "max_positions" = P in [32, n_text_ctx]): positions 0 .. P - 1
+ * are fed, so a row holds at most P + 1 ids (prompt + generated, zero-padded); ids [B][ids_stride] with ids_stride >=
+ * P + 1 (else WT_ERR_BUFFER), B <= 64.  The decoder chain runs in segments of 32 positions and ends after the segment in
+ * which the last clip emitted EOT; wt_timings.decoder_steps reports the steps run.  wt_transcribe_pcm / _file /
+ * _long_pcm honour the option.  With max_positions = 0 these calls are WT_ERR_INVALID_ARG.  While the option is set, the
+ * calls with rows of WT_MAX_IDS ids (wt_encdec_tokens_batch*, wt_transcribe_tokens_batch_dev, wt_encdec_debug_batch) and
+ * wt_pipeline_submit* are WT_ERR_UNSUPPORTED, and so is a full-length call with beam_size > 1, the bf16 storage mode,
+ * language = WT_LANGUAGE_AUTO or the forced-ids tap; the engine stays usable after each. */
+int wt_encdec_tokens_full_batch(wt_engine* h, const float* mel, int batch, int64_t* ids, int ids_stride, int32_t* n_ids);
+int wt_encdec_tokens_full_batch_dev(wt_engine* h, const float* d_mel, int batch, int64_t* ids, int ids_stride,
+                                    int32_t* n_ids);
+int wt_transcribe_tokens_full_batch_dev(wt_engine* h, const float* d_pcm, int batch, int64_t* ids, int ids_stride,
+                                        int32_t* n_ids);
 
 /* Pipelined form of the same path: submit enqueues encoder (one HIP stream) and decoder (one
  * of three further streams, in rotation) for one device-resident batch and returns at once;

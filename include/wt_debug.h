@@ -101,6 +101,11 @@ int wt_dbg_cross_absorbed_chain(wt_engine* h, int bf16, int batch, int heads, in
 int wt_dbg_absorbed_query_matrix(int heads, int d, const float* wq, const float* bq, const float* wk, float* A, float* av);
 int wt_dbg_self_attention(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
                           float* kcache, float* vcache, float* out);
+/* self_attention_long (k_attention.hip, option "max_positions"): ONE new position `pos` against caches [B][cap][d],
+ * cap <= 448; qkv [B][3d], out [B][d]; the caches come back with row pos appended and nothing else changed.  pos < 0,
+ * pos >= cap, cap > 448 and a batch or head count below 1 are WT_ERR_INVALID_ARG, before anything is launched. */
+int wt_dbg_self_attention_long(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
+                               float* vcache, float* out);
 /* bf16 storage mode kernels (option "bf16"): operands are rounded to bf16 on the host, contracted by
  * gemm_bf16_planes / encoder_attention_planes<true>; bf16_out = 1 returns the kernel's bf16 output widened to fp32 */
 int wt_dbg_gemm_bf16(wt_engine* h, int M, int N, int K, const float* A, const float* W, const float* bias,

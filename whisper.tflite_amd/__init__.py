@@ -43,6 +43,7 @@ CAPI_SYMBOLS = [
     "wt_logmel_batch", "wt_logmel_batch_dev", "wt_encdec_tokens_batch",
     "wt_encdec_tokens_batch_dev", "wt_transcribe_tokens_batch_dev", "wt_pipeline_submit_dev", "wt_pipeline_submit_pcm_dev", "wt_pipeline_collect",
     "wt_encdec_debug_batch",
+    "wt_encdec_tokens_full_batch", "wt_encdec_tokens_full_batch_dev", "wt_transcribe_tokens_full_batch_dev",
     "wt_language_count", "wt_detect_language_batch", "wt_detect_language_batch_dev", "wt_detect_language_pcm", "wt_last_languages",
     "wt_last_timings", "wt_last_beam_scores", "wt_last_kernel_stats", "wt_decode_text", "wt_language_id", "wt_lang_code", "wt_wav_read_legacy",
     "wt_vocab_info", "wt_filters", "wt_write_synthetic_weights", "wt_write_synthetic_vocab",
@@ -56,7 +57,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_self_attention_bf16", "wt_dbg_cross_attention_bf16", "wt_dbg_encoder_attention_planes", "wt_dbg_gemm_bf16", "wt_dbg_gemm_bf16_ln", "wt_dbg_encoder_attention_bf16",
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
-    "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head",
+    "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_self_attention_long",
 ]
 
 
@@ -199,6 +200,10 @@ def lib() -> ctypes.CDLL:
         L.wt_last_languages.argtypes = [c_void_p, ip32, fp, c_int]
         L.wt_dbg_language_head.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp, fp, fp, ip32, fp,
                                            ip64, c_int]
+        L.wt_encdec_tokens_full_batch.argtypes = [c_void_p, fp, c_int, ip64, c_int, ip32]
+        L.wt_encdec_tokens_full_batch_dev.argtypes = [c_void_p, c_void_p, c_int, ip64, c_int, ip32]
+        L.wt_transcribe_tokens_full_batch_dev.argtypes = [c_void_p, c_void_p, c_int, ip64, c_int, ip32]
+        L.wt_dbg_self_attention_long.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp]
         _lib = L
     return _lib
 
@@ -450,6 +455,29 @@ class Engine:
         self._check(lib().wt_transcribe_tokens_batch_dev(
             self._h, c_void_p(d_pcm_ptr), batch, ids.ctypes.data_as(POINTER(c_int64)),
             n.ctypes.data_as(POINTER(c_int32))))
+        return ids, n
+
+    # -- full-length greedy decoding (option max_positions) ------
+    def _full_rows(self, batch, ids_stride):
+        stride = self.get_option("max_positions") + 1 if ids_stride is None else int(ids_stride)
+        return np.zeros((batch, max(stride, 1)), np.int64), np.zeros(batch, np.int32), stride
+
+    def encdec_tokens_full(self, mel, ids_stride=None):
+        """mel [B][n_mels][frames] -> (ids int64 [B][max_positions + 1], n_ids int32 [B]); ids_stride overrides the row
+        length handed to the library."""
+        mel = _f32(mel).reshape((-1,) + self.mel_shape)
+        ids, n, stride = self._full_rows(mel.shape[0], ids_stride)
+        self._check(lib().wt_encdec_tokens_full_batch(self._h, _fp(mel), mel.shape[0], _ip64(ids), stride, _ip32(n)))
+        return ids, n
+
+    def encdec_tokens_full_dev(self, d_mel_ptr: int, batch: int, ids_stride=None):
+        ids, n, stride = self._full_rows(batch, ids_stride)
+        self._check(lib().wt_encdec_tokens_full_batch_dev(self._h, c_void_p(d_mel_ptr), batch, _ip64(ids), stride, _ip32(n)))
+        return ids, n
+
+    def transcribe_tokens_full_dev(self, d_pcm_ptr: int, batch: int, ids_stride=None):
+        ids, n, stride = self._full_rows(batch, ids_stride)
+        self._check(lib().wt_transcribe_tokens_full_batch_dev(self._h, c_void_p(d_pcm_ptr), batch, _ip64(ids), stride, _ip32(n)))
         return ids, n
 
     def pipeline_submit_dev(self, d_mel_ptr: int, batch: int) -> None:
@@ -783,6 +811,15 @@ class Engine:
         out = np.zeros((npos * B, d), np.float32)
         fn = lib().wt_dbg_self_attention_bf16 if bf16 else lib().wt_dbg_self_attention
         self._check(fn(self._h, B, d // 64, cap, pos, npos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
+        return out, kcache, vcache
+
+    def dbg_self_attention_long(self, qkv, kcache, vcache, pos):
+        """self_attention_long: one new position against caches [B][cap][d] (cap <= 448); returns (out [B][d], kcache,
+        vcache) with row pos appended."""
+        qkv, kcache, vcache = _f32(qkv), _f32(kcache).copy(), _f32(vcache).copy()
+        B, cap, d = kcache.shape
+        out = np.zeros((B, d), np.float32)
+        self._check(lib().wt_dbg_self_attention_long(self._h, B, d // 64, cap, pos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
         return out, kcache, vcache
 
     # beam search (k_beam.hip).  The per-clip state is a dict of the engine's arrays (beam_state()), updated in place.

@@ -25,12 +25,14 @@ void usage(const char* argv0) {
             << "                  detected per 30 s window, printed as \"language: <code> (p=...)\" before the transcript\n"
             << "  --english       English-only vocabulary ids (multilingual = false; the reference hard-codes true)\n"
             << "  --long          transcribe every 30 s window of the file, not only the first\n"
-            << "  --beam N        beam search with N hypotheses, 2..8 (default: greedy, as the reference)\n";
+            << "  --beam N        beam search with N hypotheses, 2..8 (default: greedy, as the reference)\n"
+            << "  --max-positions N  full-length greedy decoding over N positions, 32 .. n_text_ctx (default: the\n"
+            << "                  reference's 31 positions)\n";
 }
 }  // namespace
 
 int main(int argc, char* argv[]) {
-  std::string model_prefix, vocab, input, lang, beam;
+  std::string model_prefix, vocab, input, lang, beam, max_positions;
   bool long_audio = false, english = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], v;
@@ -61,6 +63,7 @@ int main(int argc, char* argv[]) {
     else if (a == "--input") input = v;
     else if (a == "--lang") lang = v;
     else if (a == "--beam") beam = v;
+    else if (a == "--max-positions") max_positions = v;
     else {
       std::cerr << "The following argument was not expected: " << a << "\n";
       usage(argv[0]);
@@ -100,6 +103,14 @@ int main(int argc, char* argv[]) {
     const long n = std::strtol(beam.c_str(), &end, 10);
     if (end == beam.c_str() || *end || wt_engine_set_option(encdec.handle(), "beam_size", n) != WT_OK) {
       std::cerr << "--beam: expected a beam size in [1, 8], got " << beam << "\n";
+      return 105;
+    }
+  }
+  if (!max_positions.empty()) {
+    char* end = nullptr;
+    const long n = std::strtol(max_positions.c_str(), &end, 10);
+    if (end == max_positions.c_str() || *end || wt_engine_set_option(encdec.handle(), "max_positions", n) != WT_OK) {
+      std::cerr << "--max-positions: expected 0 or a position count in [32, n_text_ctx], got " << max_positions << "\n";
       return 105;
     }
   }

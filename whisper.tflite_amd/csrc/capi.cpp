@@ -73,6 +73,15 @@ int copy_text(const std::string& s, char* out, size_t cap, size_t* len) {
 void hipchk(hipError_t e, const char* what) {
   if (e != hipSuccess) throw wt::Error(WT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
+
+// the token calls with rows of WT_MAX_IDS ids cannot return a full-length decode
+void refuse_fixed_rows(const wt::Engine& e) {
+  if (e.max_positions > 0) {
+    throw wt::Error(WT_ERR_UNSUPPORTED, "max_positions is set: rows of WT_MAX_IDS ids cannot hold the result, use the "
+                                        "wt_*_tokens_full_batch* entry points (or set max_positions to 0)");
+  }
+}
+
 }  // namespace
 
 namespace {
@@ -195,6 +204,12 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
   } else if (k == "max_tokens") {
     if (value < 4 || value > 31) return fail(h, WT_ERR_INVALID_ARG, "max_tokens must be in [4, 31]");
     e.max_tokens = value;
+  } else if (k == "max_positions") {
+    // full-length greedy decoding: 0 = off, else the positions fed per clip
+    if (value != 0 && (value < 32 || value > e.full_cap())) {
+      return fail(h, WT_ERR_INVALID_ARG, "max_positions must be 0 (off) or in [32, n_text_ctx] (at most 448)");
+    }
+    e.max_positions = value;
   } else if (k == "stop_at_eot") {
     e.stop_at_eot = value != 0;
   } else if (k == "verbose") {
@@ -271,6 +286,7 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   const std::string k(key);
   if (k == "language") *value = e.language;
   else if (k == "max_tokens") *value = e.max_tokens;
+  else if (k == "max_positions") *value = e.max_positions;
   else if (k == "stop_at_eot") *value = e.stop_at_eot;
   else if (k == "verbose") *value = e.verbose;
   else if (k == "cross_chunks") *value = e.cross_chunks;
@@ -369,6 +385,7 @@ int wt_encdec_tokens_batch_dev(wt_engine* h, const float* d_mel, int batch, int6
   return guarded(h, [&] {
     wt::Engine& e = *h->impl;
     e.require_idle();
+    refuse_fixed_rows(e);
     if (batch <= 64) {  // one encoder pass + one decode (the decoder kernels take up to 64 clips per pass)
       e.encode(d_mel, batch);
       e.decode(batch, ids, n_ids, nullptr, 0);
@@ -428,6 +445,7 @@ int wt_encdec_tokens_batch(wt_engine* h, const float* mel, int batch, int64_t* i
   const int rc = guarded(h, [&] {
     wt::Engine& e = *h->impl;
     e.require_idle();
+    refuse_fixed_rows(e);
     d_mel = e.staging_mel(batch);
     hipchk(hipMemcpyAsync(d_mel, mel, size_t(batch) * e.mel_elems() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D mel");
   });
@@ -441,10 +459,52 @@ int wt_transcribe_tokens_batch_dev(wt_engine* h, const float* d_pcm, int batch, 
   return guarded(h, [&] {
     wt::Engine& e = *h->impl;
     e.require_idle();
+    refuse_fixed_rows(e);
     float* d_mel = e.staging_mel(batch);
     e.logmel(d_pcm, batch, d_mel);
     e.encode(d_mel, batch);
     e.decode(batch, ids, n_ids, nullptr, 0);
+  });
+}
+
+// full-length greedy decoding (option max_positions = P): ids rows of ids_stride >= P + 1
+int wt_encdec_tokens_full_batch_dev(wt_engine* h, const float* d_mel, int batch, int64_t* ids, int ids_stride,
+                                    int32_t* n_ids) {
+  if (!h || !d_mel || !ids || !n_ids) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::Engine& e = *h->impl;
+    e.require_idle();
+    e.check_full_args(batch, ids_stride);  // before anything is enqueued
+    e.encode_full(d_mel, batch);
+    e.decode_full(batch, ids, ids_stride, n_ids);
+  });
+}
+
+int wt_encdec_tokens_full_batch(wt_engine* h, const float* mel, int batch, int64_t* ids, int ids_stride, int32_t* n_ids) {
+  if (!h || !mel || !ids || !n_ids) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::Engine& e = *h->impl;
+    e.require_idle();
+    e.check_full_args(batch, ids_stride);  // before anything is enqueued
+    float* d_mel = e.staging_mel(batch);
+    hipchk(hipMemcpyAsync(d_mel, mel, size_t(batch) * e.mel_elems() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D mel");
+    e.encode_full(d_mel, batch);
+    e.decode_full(batch, ids, ids_stride, n_ids);
+    e.sync();  // mel is read by the H2D copy on the encoder stream
+  });
+}
+
+int wt_transcribe_tokens_full_batch_dev(wt_engine* h, const float* d_pcm, int batch, int64_t* ids, int ids_stride,
+                                        int32_t* n_ids) {
+  if (!h || !d_pcm || !ids || !n_ids) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::Engine& e = *h->impl;
+    e.require_idle();
+    e.check_full_args(batch, ids_stride);  // before anything is enqueued
+    float* d_mel = e.staging_mel(batch);
+    e.logmel(d_pcm, batch, d_mel);
+    e.encode_full(d_mel, batch);
+    e.decode_full(batch, ids, ids_stride, n_ids);
   });
 }
 
@@ -454,6 +514,7 @@ int wt_encdec_debug_batch(wt_engine* h, const float* mel, int batch, int64_t* id
   return guarded(h, [&] {
     wt::Engine& e = *h->impl;
     e.require_idle();
+    refuse_fixed_rows(e);
     e.check_language_call();
     e.check_beam_call(logits != nullptr);  // (before the encoder pass)
     float* d_mel = e.staging_mel(batch);
@@ -590,13 +651,19 @@ int wt_transcribe_pcm(wt_engine* h, const float* pcm, size_t n_samples, char* ou
     float* d_mel = e.staging_mel(1);
     hipchk(hipMemcpyAsync(d_pcm, clip.data(), clip.size() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D pcm");
     e.logmel(d_pcm, 1, d_mel);
-    e.encode(d_mel, 1);
-    int64_t ids[WT_MAX_IDS];
+    const bool full = e.max_positions > 0;  // full-length decoding: rows of max_positions + 1 ids
+    std::vector<int64_t> ids(full ? size_t(e.max_positions) + 1 : size_t(WT_MAX_IDS));
     int32_t n = 0;
-    e.decode(1, ids, &n, nullptr, 0);
+    if (full) {
+      e.encode_full(d_mel, 1);
+      e.decode_full(1, ids.data(), int(ids.size()), &n);
+    } else {
+      e.encode(d_mel, 1);
+      e.decode(1, ids.data(), &n, nullptr, 0);
+    }
     bool missing = false;
     // omit_special_tokens = false, as EncDec::transcribe passes (whisper.cpp:766-767)
-    text = wt::decode_tokens(e.vocab(), ids, n, false, &missing);
+    text = wt::decode_tokens(e.vocab(), ids.data(), n, false, &missing);
     if (missing && e.verbose) std::fprintf(stderr, "[wt] token id without a vocab entry skipped\n");
   });
   if (rc != WT_OK) {
@@ -629,10 +696,17 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
       float* d_mel = e.staging_mel(B);
       hipchk(hipMemcpyAsync(d_pcm, clips.data(), clips.size() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D pcm");
       e.logmel(d_pcm, B, d_mel);
-      e.encode(d_mel, B);
-      std::vector<int64_t> ids(size_t(B) * WT_MAX_IDS);
+      const bool full = e.max_positions > 0;
+      const size_t row = full ? size_t(e.max_positions) + 1 : size_t(WT_MAX_IDS);
+      std::vector<int64_t> ids(size_t(B) * row);
       std::vector<int32_t> n(B);
-      e.decode(B, ids.data(), n.data(), nullptr, 0);
+      if (full) {
+        e.encode_full(d_mel, B);
+        e.decode_full(B, ids.data(), int(row), n.data());
+      } else {
+        e.encode(d_mel, B);
+        e.decode(B, ids.data(), n.data(), nullptr, 0);
+      }
       e.sync();  // clips[] is read by the H2D copy on the encoder stream
       if (e.last_lang_valid) {
         langs.insert(langs.end(), e.last_lang.begin(), e.last_lang.end());
@@ -641,7 +715,7 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
       for (int b = 0; b < B; ++b) {
         if (w0 + b) text += '\n';
         bool missing = false;
-        text += wt::decode_tokens(e.vocab(), &ids[size_t(b) * WT_MAX_IDS], n[b], false, &missing);
+        text += wt::decode_tokens(e.vocab(), &ids[size_t(b) * row], n[b], false, &missing);
       }
     }
     if (e.last_lang_valid) e.last_lang = langs, e.last_lang_prob = lang_probs;
@@ -1576,6 +1650,21 @@ int wt_dbg_self_attention(wt_engine* h, int batch, int heads, int cap, int pos, 
 int wt_dbg_self_attention_bf16(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
                                float* kcache, float* vcache, float* out) {
   return dbg_self_attention_impl(h, batch, heads, cap, pos, npos, qkv, kcache, vcache, out, true);
+}
+int wt_dbg_self_attention_long(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
+                               float* vcache, float* out) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::check_self_attention_long(cap, pos, batch, heads);  // the launcher's own refusals, before anything is allocated
+    if (!qkv || !kcache || !vcache || !out) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_self_attention_long: NULL array");
+    const size_t d = size_t(heads) * 64, nc = size_t(batch) * cap * d;
+    DevBuf dq(qkv, size_t(batch) * 3 * d), dk(kcache, nc), dv(vcache, nc), dout(size_t(batch) * d);
+    wt::launch_self_attention_long(dq.p, dk.p, dv.p, cap, pos, dout.p, batch, heads, h->impl->stream());
+    h->impl->sync();
+    dout.to_host(out, size_t(batch) * d);
+    dk.to_host(kcache, nc);
+    dv.to_host(vcache, nc);
+  });
 }
 
 }  // extern "C"

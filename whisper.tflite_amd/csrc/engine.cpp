@@ -866,6 +866,9 @@ void Engine::release() noexcept {
   for (void* p : {static_cast<void*>(bw_.h_prompt), static_cast<void*>(bw_.h_sum), static_cast<void*>(bw_.h_len)})
     if (p) (void)hipHostFree(p);
   bw_ = BeamWorkspace();  // (its device buffers are in allocations_)
+  for (void* p : {static_cast<void*>(fw_.h_ids), static_cast<void*>(fw_.h_n), static_cast<void*>(fw_.h_fin)})
+    if (p) (void)hipHostFree(p);
+  fw_ = FullWorkspace();
   for (void* p : {static_cast<void*>(h_lang_probs_), static_cast<void*>(h_lang_prob_), static_cast<void*>(h_lang_)})
     if (p) (void)hipHostFree(p);
   h_lang_probs_ = nullptr, h_lang_prob_ = nullptr, h_lang_ = nullptr;
@@ -1756,6 +1759,7 @@ void Engine::submit_decoder(int batch, int s) {
 }
 
 void Engine::submit(const float* d_mel, int batch) {
+  if (max_positions > 0) throw Error(kErrUnsupported, "full-length decoding (max_positions) runs on the synchronous entry points only, not in the pipeline");
   if (beam_size > 1) throw Error(kErrUnsupported, "beam search runs on the synchronous entry points only, not in the pipeline");
   check_language_call();
   last_lang_valid = false;
@@ -1768,6 +1772,7 @@ void Engine::submit(const float* d_mel, int batch) {
 }
 
 void Engine::submit_pcm(const float* d_pcm, int batch) {
+  if (max_positions > 0) throw Error(kErrUnsupported, "full-length decoding (max_positions) runs on the synchronous entry points only, not in the pipeline");
   if (beam_size > 1) throw Error(kErrUnsupported, "beam search runs on the synchronous entry points only, not in the pipeline");
   check_language_call();
   last_lang_valid = false;
@@ -2168,6 +2173,18 @@ void Engine::debug_concurrency(const float* d_mel, int batch, int n_dec, int n_e
 }
 
 void Engine::decode_collect(int slot_idx, int64_t* ids, int32_t* n_ids) {
+  finish_slot(slot_idx);
+  const Slot& slot = slots_[slot_idx];
+  const int batch = slot.batch, stride = 32;
+  for (int b = 0; b < batch; ++b) {
+    n_ids[b] = slot.h_n[b];
+    for (int i = 0; i < stride; ++i)
+      ids[size_t(b) * stride + i] = i < slot.h_n[b] ? slot.h_ids[size_t(b) * stride + i] : 0;
+  }
+}
+
+// waits for the slot's decoder chain; the encoder's non-finite flag, kernel statistics and timings of the batch
+void Engine::finish_slot(int slot_idx) {
   Slot& slot = slots_[slot_idx];
   HIPCHK(hipEventSynchronize(slot.dec_done));
   HIPCHK(hipGetLastError());
@@ -2177,14 +2194,9 @@ void Engine::decode_collect(int slot_idx, int64_t* ids, int32_t* n_ids) {
                    "(|activation| > 65504 or |weight| > 1023) or the input holds NaN/Inf; gemm_variant 16 and "
                    "attn_variant 1 (bf16 three-plane split) have the full fp32 range");
   }
-  const int batch = slot.batch, stride = 32;
+  const int batch = slot.batch;
   // (a batch decoded by its pair leader's chain has its ids in its OWN buffers; the leader only times the chain)
   const Slot& src = slot.pair_leader >= 0 ? slots_[slot.pair_leader] : slot;
-  for (int b = 0; b < batch; ++b) {
-    n_ids[b] = slot.h_n[b];
-    for (int i = 0; i < stride; ++i)
-      ids[size_t(b) * stride + i] = i < slot.h_n[b] ? slot.h_ids[size_t(b) * stride + i] : 0;
-  }
   resolve_kernel_stats(slot_idx);
   float ms = 0;
   timings_.batch = batch;
@@ -2467,6 +2479,287 @@ void Engine::decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids) 
   beam_sum.assign(bw_.h_sum, bw_.h_sum + batch);
   beam_len.assign(bw_.h_len, bw_.h_len + batch);
   beam_scores_valid = true;
+}
+
+// ------------------------------------------------ full-length decoding ---
+
+void Engine::check_full_args(int batch, int ids_stride) const {
+  if (max_positions <= 0) throw Error(kErrInvalidArg, "the full-length entry points need the option max_positions (32 .. n_text_ctx)");
+  check_full_call();
+  if (batch < 1 || batch > 64) throw Error(kErrInvalidArg, "decoder batches are limited to 64 clips per call");
+  if (ids_stride < max_positions + 1) throw Error(kErrBuffer, "ids_stride is smaller than max_positions + 1");
+}
+
+void Engine::check_full_call() const {
+  if (max_positions <= 0) return;
+  auto no = [](const char* why) { throw Error(kErrUnsupported, std::string("full-length decoding (max_positions): ") + why); };
+  if (beam_size > 1) no("greedy only, not with beam search (beam_size > 1)");
+  if (bf16) no("not in the bf16 storage mode");
+  if (language < 0) no("not with automatic language detection (language = -1)");
+  if (!forced_ids.empty()) no("not with forced ids");
+}
+
+// A full-length call is synchronous and finds the engine idle, so it may choose its pipeline slot: always slot 0, and
+// one set of segment graphs serves every call (a greedy call rotates over the slots and captures all of them at once).
+// The rotation of the other calls goes on where it was.
+void Engine::encode_full(const float* d_mel, int batch) {
+  require_idle();
+  check_full_call();
+  const int next = enc_slot_;
+  enc_slot_ = 0;
+  try {
+    encode(d_mel, batch);
+  } catch (...) {
+    enc_slot_ = next;
+    throw;
+  }
+  enc_slot_ = next;
+}
+
+// The self-attention cache is sized by the largest batch a full-length call has had: layers x 2 x clips x cap x d
+// floats (tiny: 5.5 MB per clip, 352 MB at 64 clips; large-v3's 32 layers of d = 1280: 147 MB per clip).  A larger
+// batch frees it, and with it the segment graphs that hold its address.  Rows written by an earlier call, at whatever
+// batch stride, are never read: the kernels read cache rows <= pos only, all written by the running chain.
+void Engine::ensure_full_workspace(int batch) {
+  const wtw::Dims& c = dims_;
+  const size_t C = 64, cap = size_t(full_cap()), d = c.n_text_state;
+  auto alloc = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    allocations_.push_back(p);
+    HIPCHK(hipMemset(p, 0, bytes));
+    return p;
+  };
+  if (batch > fw_.kv_clips) {
+    if (fw_.kv) {
+      HIPCHK(hipStreamSynchronize(stream_));
+      for (auto& ds : dstream_) HIPCHK(hipStreamSynchronize(ds));
+      // every full-length segment graph, whatever its batch, holds the old cache's base address in its kernel
+      // arguments: all of them go with it (greedy's and beam's graphs never see this cache and stay)
+      for (auto it = graphs_.begin(); it != graphs_.end();) {
+        if (it->first[0] == kFullKey) {
+          (void)hipGraphExecDestroy(it->second.exec);
+          it = graphs_.erase(it);
+        } else {
+          ++it;
+        }
+      }
+      allocations_.erase(std::remove(allocations_.begin(), allocations_.end(), static_cast<void*>(fw_.kv)), allocations_.end());
+      (void)hipFree(fw_.kv);
+      fw_.kv = nullptr, fw_.kv_clips = 0;
+    }
+    fw_.kv = static_cast<float*>(alloc(size_t(c.n_text_layer) * 2 * size_t(batch) * cap * d * sizeof(float)));
+    fw_.kv_clips = batch;
+  }
+  if (fw_.h_fin) return;  // (allocated last)
+  fw_.ids = static_cast<long long*>(alloc(C * (cap + 1) * sizeof(long long)));
+  void* p = nullptr;
+  HIPCHK(hipHostMalloc(&p, C * (cap + 1) * sizeof(long long), 0));
+  fw_.h_ids = static_cast<long long*>(p);
+  HIPCHK(hipHostMalloc(&p, C * sizeof(int), 0));
+  fw_.h_n = static_cast<int*>(p);
+  HIPCHK(hipHostMalloc(&p, C * sizeof(int), 0));
+  fw_.h_fin = static_cast<int*>(p);
+}
+
+// Full-length greedy decoding: decode_enqueue's passes — the prompt grouped by np_max, then one
+// pass per position — continued to P = max_positions, over a self-attention cache of full_cap() rows and id rows of
+// stride full_cap() + 1.  Positions 0 .. 31 run self_attention_step on that cache, later ones self_attention_long; the
+// cross-attention form is the one the slot's encoder pass prepared.  The chain is enqueued in segments of 32 positions;
+// a segment's launch sequence is fixed for its key and replayed from a hipGraph of the calling slot.  After each
+// segment the finished flags come back, and the chain ends once every clip has emitted EOT (stop_at_eot = 1).
+void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids) {
+  require_idle();
+  check_full_args(batch, ids_stride);
+  const int P = int(max_positions), slot_idx = last_enc_slot_;
+  last_lang_valid = false;
+  beam_scores_valid = false;
+  ensure_batch(batch);
+  ensure_full_workspace(batch);  // (before any capture: nothing may be allocated inside one)
+  Slot& slot = slots_[slot_idx];
+  const wtw::Dims& c = dims_;
+  const int d = c.n_text_state, T = c.n_audio_ctx, H = c.n_text_head, V = c.n_vocab, L = c.n_text_layer;
+  const int cap = full_cap(), stride = cap + 1;
+  const std::vector<long long> prompt = this->prompt();
+  const int n_prompt = int(prompt.size());
+  for (long long id : prompt) {
+    if (id < 0 || id >= V) throw Error(kErrInvalidArg, "prompt token id outside the model's vocabulary");
+  }
+  slot.dec = slot_idx % n_dec_streams_;
+  slot.pair_leader = -1;
+  DecWorkspace& dw = dws_[slot.dec];
+  hipStream_t const st = dec_stream_at(slot.dec);
+  for (int b = 0; b < batch; ++b) {
+    for (int i = 0; i < stride; ++i) fw_.h_ids[size_t(b) * stride + i] = i < n_prompt ? prompt[i] : 0;
+    fw_.h_n[b] = n_prompt;
+  }
+  int chunks = int(cross_chunks);  // as decode_enqueue chooses them for a synchronous call of this size
+  if (chunks == 0) {
+    chunks = 1;
+    while (chunks < 8 && batch * H * chunks < 192) chunks *= 2;
+  }
+  const bool absorbed = slot.absorbed;
+  int n_abs = abs_chunks > 0 ? int(abs_chunks) : std::min(16, std::max(1, (256 + batch - 1) / batch));
+  n_abs = std::min(n_abs, (T + 31) / 32);
+  const bool split = fc2_ksplit == 2 && (4 * d) % 256 == 0;
+  const size_t kv_slab = size_t(batch) * T * d, self_slab = size_t(batch) * cap * d;
+  float* const x = dw.xd;
+  const int np_max = std::max(1, std::min(4, kDecRowsMax / batch));
+  const int prompt_end = std::min(n_prompt, P);
+
+  HIPCHK(hipStreamWaitEvent(st, slot.enc_done, 0));
+  HIPCHK(hipEventRecord(slot.dec_begin, st));
+  HIPCHK(hipMemcpyAsync(fw_.ids, fw_.h_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dw.n_ids, fw_.h_n, size_t(batch) * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(dw.finished, 0, size_t(batch) * sizeof(int), st));
+
+  // the passes whose first position lies in [lo, hi); returns the argmax steps among them
+  auto enqueue_segment = [&](int lo, int hi) {
+    int seg_steps = 0;
+    for (int pos0 = 0, np = 1; pos0 < hi; pos0 += np) {
+      np = pos0 < prompt_end ? std::min(np_max, prompt_end - pos0) : 1;
+      if (pos0 < lo) continue;
+      const int M = np * batch, last = pos0 + np - 1;
+      for (int l = 0; l < L; ++l) {
+        const DecBlockWeights& w = dec_blocks_[l];
+        DecGemmArgs q;  // LN + fused q|k|v projection (+ token/positional embedding at layer 0)
+        q.Wt = w.wqkv.w; q.w_scale = w.wqkv.scale; q.N = 3 * d; q.K = d; q.B = batch; q.M = M;
+        q.xin = x; q.ln_g = w.attn_ln_g; q.ln_b = w.attn_ln_b;
+        if (l > 0 && split) {
+          q.xin = dw.xb; q.xpart = dw.xpart; q.xout = x;
+        }
+        if (l == 0) {
+          q.ids = fw_.ids; q.ids_stride = stride; q.pos = pos0; q.tok_emb = tok_emb; q.pos_emb = dec_pos;
+          q.n_vocab = V; q.xout = x;
+        }
+        q.bias = w.bqkv; q.Y = dw.qkvd; q.ldy = 3 * d;
+        launch_dec_gemm(q, kProLn, kDecBias, st);
+        float* const kc = fw_.kv + (size_t(l) * 2 + 0) * self_slab;
+        float* const vc = fw_.kv + (size_t(l) * 2 + 1) * self_slab;
+        if (pos0 + np <= 32) {
+          launch_self_attention(dw.qkvd, kc, vc, cap, pos0, np, dw.attd, batch, H, st);
+        } else {  // (np == 1: the prompt has at most 8 ids)
+          launch_self_attention_long(dw.qkvd, kc, vc, cap, pos0, dw.attd, batch, H, st);
+        }
+        DecGemmArgs o;  // x += attn . Wo^T + bo
+        o.Wt = w.wo.w; o.w_scale = w.wo.scale; o.N = d; o.K = d; o.B = batch; o.M = M; o.X = dw.attd; o.ldx = d;
+        o.bias = w.bo; o.R = x; o.Y = x; o.ldy = d;
+        launch_dec_gemm(o, kProNone, kDecResid, st);
+        if (absorbed) {
+          DecGemmArgs qa;  // LN + absorbed query projection
+          qa.Wt = w.wq_abs.w; qa.w_scale = w.wq_abs.scale; qa.N = H * d; qa.K = d; qa.B = batch; qa.M = M;
+          qa.xin = x; qa.ln_g = w.cross_ln_g; qa.ln_b = w.cross_ln_b; qa.bias = w.bq_abs; qa.Y = dw.qp; qa.ldy = H * d;
+          launch_dec_gemm(qa, kProLn, kDecBias, st);
+          const int nq_max = cross_absorbed_max_nq(H);
+          for (int p0 = 0; p0 < np; p0 += nq_max) {
+            CrossAbsorbedArgs ca;
+            ca.qp = dw.qp; ca.e = slot.e_planes; ca.e_plane = long(ws_.batch) * T * d; ca.e_scale = sc_cross_kv_.a;
+            ca.ws = dw.abs_ws; ca.batch = batch; ca.heads = H; ca.d_model = d; ca.T = T; ca.chunks = n_abs;
+            ca.nq = std::min(nq_max, np - p0); ca.p0 = p0;
+            launch_cross_absorbed(ca, st);
+          }
+          launch_cross_absorbed_combine(dw.abs_ws, w.cross_wv_t, w.cross_bv, dw.cabs, M, H, n_abs, d, st);
+          DecGemmArgs co;  // x += o . Wco^T + bco
+          co.Wt = w.cross_wo.w; co.w_scale = w.cross_wo.scale; co.N = d; co.K = d; co.B = batch; co.M = M;
+          co.X = dw.cabs; co.ldx = d; co.bias = w.cross_bo; co.R = x; co.Y = x; co.ldy = d;
+          launch_dec_gemm(co, kProNone, kDecResid, st);
+        } else {
+          CrossAttnArgs ca;  // LN + query projection + attention over the cached encoder keys, per key chunk
+          ca.x = x; ca.ln_g = w.cross_ln_g; ca.ln_b = w.cross_ln_b; ca.wq_t = w.cross_wq_t; ca.bq = w.cross_bq;
+          ca.kc = slot.cross_kv + (size_t(l) * 2 + 0) * kv_slab; ca.vc = slot.cross_kv + (size_t(l) * 2 + 1) * kv_slab;
+          ca.ws = dw.cross_ws; ca.batch = batch; ca.heads = H; ca.T = T; ca.chunks = chunks; ca.nq = np;
+          launch_cross_attention(ca, st);
+          DecGemmArgs co;  // x += combine(chunks) . Wco^T + bco
+          co.Wt = w.cross_wo.w; co.w_scale = w.cross_wo.scale; co.N = d; co.K = d; co.B = batch; co.M = M;
+          co.cross_ws = dw.cross_ws; co.heads = H; co.chunks = chunks;
+          co.bias = w.cross_bo; co.R = x; co.Y = x; co.ldy = d;
+          launch_dec_gemm(co, kProCombine, kDecResid, st);
+        }
+        DecGemmArgs f1;  // LN + fc1 + GELU
+        f1.Wt = w.w1.w; f1.w_scale = w.w1.scale; f1.N = 4 * d; f1.K = d; f1.B = batch; f1.M = M;
+        f1.xin = x; f1.ln_g = w.mlp_ln_g; f1.ln_b = w.mlp_ln_b;
+        f1.bias = w.b1; f1.Y = dw.hd; f1.ldy = 4 * d;
+        launch_dec_gemm(f1, kProLn, kDecBiasGelu, st);
+        DecGemmArgs f2;  // x += h . W2^T + b2
+        f2.Wt = w.w2.w; f2.w_scale = w.w2.scale; f2.N = d; f2.K = 4 * d; f2.B = batch; f2.M = M; f2.X = dw.hd; f2.ldx = 4 * d;
+        f2.bias = w.b2; f2.R = x; f2.Y = x; f2.ldy = d;
+        if (split) {
+          f2.Y = dw.xb; f2.ksplit = 2; f2.part = dw.xpart;
+        }
+        launch_dec_gemm(f2, kProNone, kDecResid, st);
+      }
+      if (last >= n_prompt - 1) {  // final LayerNorm + logits + argmax records of the last position's rows, then the token
+        const size_t off = size_t(np - 1) * batch * d;
+        DecGemmArgs lg;
+        lg.Wt = tok_emb_tiled.w; lg.w_scale = tok_emb_tiled.scale; lg.N = V; lg.K = d; lg.B = batch;
+        lg.xin = (split ? dw.xb : x) + off; lg.xpart = split ? dw.xpart + off : nullptr; lg.ln_g = dec_ln_g; lg.ln_b = dec_ln_b;
+        lg.Y = nullptr; lg.ldy = V; lg.best = dw.best;
+        launch_dec_gemm(lg, kProLn, kDecLogits, st);
+        launch_select_token(dw.best, (V + 31) / 32, fw_.ids, stride, last, dw.n_ids, dw.finished, vocab_.token_eot,
+                            int(stop_at_eot), batch, st);
+        ++seg_steps;
+      }
+    }
+    return seg_steps;
+  };
+
+  int steps = 0;
+  for (int lo = 0; lo < P; lo += 32) {
+    const int hi = std::min(P, lo + 32);
+    // (greedy's keys start with the slot, a beam key with -beam_size; a full-length key starts with kFullKey)
+    const std::vector<long long> key{kFullKey, slot_idx, batch, lo, P, n_prompt, chunks, long(stop_at_eot), fc2_ksplit,
+                                     absorbed ? 1 : 0, n_abs, slot.dec};
+    auto it = use_graphs ? graphs_.find(key) : graphs_.end();
+    if (it != graphs_.end()) {
+      HIPCHK(hipGraphLaunch(it->second.exec, st));
+      steps += it->second.steps;
+    } else {
+      const int seg_steps = enqueue_segment(lo, hi);  // eager the first time, then captured for the next calls
+      steps += seg_steps;
+      if (use_graphs) {
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t ge = nullptr;
+        try {
+          HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+          try {
+            enqueue_segment(lo, hi);
+          } catch (...) {
+            (void)hipStreamEndCapture(st, &graph);
+            if (graph) (void)hipGraphDestroy(graph);
+            throw;
+          }
+          HIPCHK(hipStreamEndCapture(st, &graph));
+          const hipError_t ie = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
+          (void)hipGraphDestroy(graph);
+          if (ie != hipSuccess) throw Error(kErrDevice, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
+          graphs_[key] = GraphEntry{ge, seg_steps};
+        } catch (const std::exception& e) {
+          (void)hipGetLastError();
+          use_graphs = 0;
+          std::fprintf(stderr, "[wt] full-length hipGraph capture failed (%s): continuing with eager launches\n", e.what());
+        }
+      }
+    }
+    if (hi == P) break;
+    if (stop_at_eot) {  // every clip finished: the remaining segments would change nothing
+      HIPCHK(hipMemcpyAsync(fw_.h_fin, dw.finished, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      bool all = true;
+      for (int b = 0; b < batch; ++b) all = all && fw_.h_fin[b] != 0;
+      if (all) break;
+    }
+  }
+  HIPCHK(hipMemcpyAsync(fw_.h_ids, fw_.ids, size_t(batch) * stride * sizeof(long long), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(fw_.h_n, dw.n_ids, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord(slot.dec_done, st));
+  slot.steps = steps;
+  finish_slot(slot_idx);  // waits; the encoder's non-finite flag, timings
+  for (int b = 0; b < batch; ++b) {
+    n_ids[b] = fw_.h_n[b];
+    for (int i = 0; i < ids_stride; ++i) {
+      ids[size_t(b) * ids_stride + i] = i < fw_.h_n[b] && i < stride ? fw_.h_ids[size_t(b) * stride + i] : 0;
+    }
+  }
 }
 
 }  // namespace wt

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <map>
 #include <stdexcept>
@@ -152,6 +153,20 @@ class Engine {
   std::vector<int> last_lang;
   std::vector<float> last_lang_prob;
   bool last_lang_valid = false;
+  // Full-length greedy decoding (decode_full).  0 = off: the max_tokens path above, 31 positions.
+  // P in [32, full_cap()]: the oracle's max_positions — positions 0 .. P - 1 are fed, a row holds at most P + 1 ids —
+  // on the synchronous full-length entry points and the text entry points.  Scope: greedy, fp32-accurate storage, a
+  // prompt language; no pipeline, no forced ids, no logits tap (check_full_call).
+  long max_positions = 0;
+  int full_cap() const { return std::min(dims_.n_text_ctx, 448); }  // (448: kSelfLongCap, kernels.h)
+  // arguments of a full-length token call: kErrInvalidArg without the option or for a batch outside [1, 64],
+  // check_full_call(), kErrBuffer for ids_stride < max_positions + 1
+  void check_full_args(int batch, int ids_stride) const;
+  void check_full_call() const;  // throws kErrUnsupported when max_positions is set and the options fall outside that scope
+  // encoder output of the last encode() -> ids [batch][ids_stride] (prompt + generated, zero-padded), n_ids [batch];
+  // ids_stride >= max_positions + 1, batch <= 64.  Synchronises.
+  void decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids);
+  void encode_full(const float* d_mel, int batch);  // encode() into slot 0: the slot every full-length call uses
   long gemm_variant = -1;  // -1 = plane GEMM (per-contraction fall-back to 13/16); 0 = fp32 MFMA, 13 / 16 = three bf16 planes
   // 1 = bf16 STORAGE mode (BASELINE configs[3]): bf16 weights, activations and both KV caches, fp32 accumulation,
   // fp32 residual stream; k_gemm_bf16.hip and the BF variants of the attention / decoder kernels.  Set through
@@ -253,6 +268,7 @@ class Engine {
   std::vector<int> pending_;  // consecutive slots submitted, encoder enqueued, decoder waiting for the rest of their group
   void flush_pending();
   void decode_collect(int slot, int64_t* ids, int32_t* n_ids);
+  void finish_slot(int slot);  // decode_collect without the id rows: wait, non-finite flag, statistics, timings
   // beam search over the slot encode() just filled: consecutive chains of <= 128 / beam_size clips on one decoder stream
   void decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids);
   struct BeamWorkspace {  // allocated on the first beam call, sized for 128 rows and 64 clips whatever the batch
@@ -271,6 +287,15 @@ class Engine {
     int* h_len = nullptr;           // pinned [64]
   } bw_;
   void ensure_beam_workspace();
+  struct FullWorkspace {  // allocated on the first full-length call
+    float* kv = nullptr;            // self-attention caches [layer][k|v][clip][full_cap()][d] for kv_clips clips
+    int kv_clips = 0;               // the largest batch of a full-length call so far
+    long long* ids = nullptr;       // id rows [64][full_cap() + 1]
+    long long* h_ids = nullptr;     // pinned mirror of the id rows
+    int *h_n = nullptr, *h_fin = nullptr;  // pinned [64]: id counts, finished flags after a segment
+  } fw_;
+  void ensure_full_workspace(int batch);
+  static constexpr long long kFullKey = -1000;  // first entry of a full-length segment's graph key
 
   int enc_cus_masked_ = 0;  // CUs the pipelined encoder stream may use
  public:

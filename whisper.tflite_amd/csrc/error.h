@@ -13,6 +13,6 @@ struct Error : std::runtime_error {
 };
 
 // status codes used below the ABI (mirror enum wt_status)
-constexpr int kErrInvalidArg = 1, kErrIo = 2, kErrFormat = 3, kErrUnsupported = 4, kErrDevice = 5;
+constexpr int kErrInvalidArg = 1, kErrIo = 2, kErrFormat = 3, kErrUnsupported = 4, kErrDevice = 5, kErrBuffer = 6;
 
 }  // namespace wt

@@ -548,6 +548,107 @@ __global__ void self_attention_step(const float* __restrict__ qkv, void* __restr
   }
 }
 
+// -------------------------------- decoder self attention over a long cache ---
+// Full-length decoding (option max_positions): ONE new position `pos` per launch, cache [b][cap][d] with cap up to
+// kSelfLongCap.  One block of 256 threads per (clip, head), in the form of cross_attention_step's key sweep: 16 lanes
+// own a key row (16-byte loads), four rows in flight per lane, so a round trip to memory covers 64 keys; each 16-lane
+// group runs an online softmax over its keys g, g + 16, g + 32, ... in ascending order and the 16 group partials are
+// merged through LDS in group order — the order of every sum depends on `pos` alone, never on the clip, the batch or
+// the grid.  The first wavefront appends the new k and v to cache row `pos`; the group that owns key `pos` takes them
+// from LDS (the row is not read back), and a key index >= pos is redirected to row max(pos - 1, 0) before the load, so
+// nothing reads cache rows > pos (row pos itself only at pos = 0, where the redirect lands on it and the value is dropped).  Scores in log2 units, p = exp2(s - m).  qkv / out rows: row = b (one position).
+__global__ __launch_bounds__(256) void self_attention_long(const float* __restrict__ qkv, float* __restrict__ kcache,
+                                                           float* __restrict__ vcache, int cap, int pos,
+                                                           float* __restrict__ out, int heads) {
+  constexpr int NG = 16, U = 4;  // key rows per load round, rounds in flight
+  __shared__ __attribute__((aligned(16))) float qs[64];
+  __shared__ __attribute__((aligned(16))) float kn[64];
+  __shared__ __attribute__((aligned(16))) float vn[64];
+  __shared__ __attribute__((aligned(16))) float go[NG * 64];
+  __shared__ float gm[NG], gl[NG];
+  const int b = blockIdx.x / heads, h = blockIdx.x % heads;
+  const int tid = threadIdx.x, grp = tid >> 4, gl16 = tid & 15;
+  const int d = heads * 64;
+  float* kc = kcache + ((long)b * cap) * d + h * 64;
+  float* vc = vcache + ((long)b * cap) * d + h * 64;
+  const int n = pos + 1;                      // causal: keys 0 .. pos
+  const int last_old = pos > 0 ? pos - 1 : 0;  // where the loads of keys >= pos go instead (their values are dropped)
+  const float* kb = kc + gl16 * 4;
+  const float* vb = vc + gl16 * 4;
+  f32x4 kv[U], vv[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {  // the first 64 keys are requested before the new row is staged
+    const int k = grp + NG * u;
+    const int kk = k < pos ? k : last_old;
+    kv[u] = *reinterpret_cast<const f32x4*>(kb + (long)kk * d);
+    vv[u] = *reinterpret_cast<const f32x4*>(vb + (long)kk * d);
+  }
+  constexpr float kScale = 0.125f * 1.44269504088896340736f;
+  if (tid < 64) {
+    const float* row = qkv + (long)b * 3 * d + h * 64 + tid;
+    const float knew = row[d], vnew = row[2 * d];
+    qs[tid] = row[0] * kScale;
+    kn[tid] = knew;
+    vn[tid] = vnew;
+    kc[(long)pos * d + tid] = knew;
+    vc[(long)pos * d + tid] = vnew;
+  }
+  __syncthreads();
+  const f32x4 q4 = *reinterpret_cast<const f32x4*>(&qs[gl16 * 4]);
+  const f32x4 kn4 = *reinterpret_cast<const f32x4*>(&kn[gl16 * 4]);
+  const f32x4 vn4 = *reinterpret_cast<const f32x4*>(&vn[gl16 * 4]);
+  float m = -1e30f, l = 0.0f;
+  f32x4 o = {0.0f, 0.0f, 0.0f, 0.0f};
+  for (int k0 = grp; k0 < n; k0 += NG * U) {
+    if (k0 != grp) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int k = k0 + NG * u;
+        const int kk = k < pos ? k : last_old;
+        kv[u] = *reinterpret_cast<const f32x4*>(kb + (long)kk * d);
+        vv[u] = *reinterpret_cast<const f32x4*>(vb + (long)kk * d);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int k = k0 + NG * u;
+      const f32x4 kf = k == pos ? kn4 : kv[u];
+      const f32x4 vf = k == pos ? vn4 : vv[u];
+      float s = (kf[0] * q4[0] + kf[1] * q4[1]) + (kf[2] * q4[2] + kf[3] * q4[3]);
+      s += __shfl_xor(s, 8, 64);
+      s += __shfl_xor(s, 4, 64);
+      s += __shfl_xor(s, 2, 64);
+      s += __shfl_xor(s, 1, 64);
+      if (k >= n) s = -1e30f;
+      const float mn = fmaxf(m, s);
+      const float a = exp2f(m - mn), pr = k >= n ? 0.0f : exp2f(s - mn);
+      l = l * a + pr;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = o[j] * a + pr * vf[j];
+      m = mn;
+    }
+  }
+  *reinterpret_cast<f32x4*>(&go[grp * 64 + gl16 * 4]) = o;
+  if (gl16 == 0) {
+    gm[grp] = m;
+    gl[grp] = l;
+  }
+  __syncthreads();
+  if (tid < 64) {  // groups without a key (pos < 15) carry m = -1e30, l = 0: weight exp2(-1e30 - mx) = 0
+    float mx = gm[0];
+#pragma unroll
+    for (int g = 1; g < NG; ++g) mx = fmaxf(mx, gm[g]);
+    float acc = 0.0f, lsum = 0.0f;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const float w = exp2f(gm[g] - mx);
+      acc += w * go[g * 64 + tid];
+      lsum += w * gl[g];
+    }
+    out[(long)b * d + h * 64 + tid] = acc / lsum;
+  }
+}
+
 // ------------------------------------------------ decoder cross attention ---
 // One block per (clip, head, key chunk), NQ query rows (NQ = 1 for a generated position; the prompt positions of
 // the first pass share one sweep of the cache).  The block first makes its own queries — q = LayerNorm(x[row]) .
@@ -791,6 +892,18 @@ void launch_self_attention(const float* qkv, void* kcache, void* vcache, int cap
     hipLaunchKernelGGL(self_attention_step<false>, dim3(batch * heads), dim3(64), 0, s, qkv, kcache, vcache, cap, pos0,
                        npos, batch, out, heads);
   }
+}
+
+void check_self_attention_long(int cap, int pos, int batch, int heads) {
+  if (batch < 1 || heads < 1) throw Error(kErrInvalidArg, "decoder self-attention (long cache): no clips or no heads");
+  if (cap < 1 || cap > kSelfLongCap) throw Error(kErrInvalidArg, "decoder self-attention (long cache): cache rows outside [1, 448]");
+  if (pos < 0 || pos >= cap) throw Error(kErrInvalidArg, "decoder self-attention (long cache): position outside the cache");
+}
+
+void launch_self_attention_long(const float* qkv, float* kcache, float* vcache, int cap, int pos, float* out, int batch,
+                                int heads, hipStream_t s) {
+  check_self_attention_long(cap, pos, batch, heads);
+  hipLaunchKernelGGL(self_attention_long, dim3(batch * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out, heads);
 }
 
 template <int NQ, bool BF>

@@ -260,6 +260,14 @@ void launch_mel_normalize(float* logmel, const unsigned* clip_max, int batch, in
 // bf16: the cache holds bf16 elements (bf16 storage mode).
 void launch_self_attention(const float* qkv, void* kcache, void* vcache, int cap, int pos0, int npos, float* out,
                            int batch, int heads, hipStream_t s, bool bf16 = false);
+// Full-length decoding (option max_positions): ONE new position `pos` (any in [0, cap); the engine uses it from 32 on)
+// against a cache [B][cap][d], cap <= kSelfLongCap, fp32.  Appends the position's k and v (qkv rows b, [.][3d]) at cache
+// row pos and attends its q causally over rows 0 .. pos; out rows b.  Rows > pos are neither read nor written.
+// Throws kErrInvalidArg for pos < 0, pos >= cap, cap > kSelfLongCap, batch < 1 or heads < 1 (check_self_attention_long).
+constexpr int kSelfLongCap = 448;  // n_text_ctx of every Whisper
+void check_self_attention_long(int cap, int pos, int batch, int heads);
+void launch_self_attention_long(const float* qkv, float* kcache, float* vcache, int cap, int pos, float* out, int batch,
+                                int heads, hipStream_t s);
 // Cross attention of nq (1..4) query rows per clip over T cached keys, the query projection included:
 // q = LayerNorm(x[row]) . Wq^T + bq with x the residual stream [nq * B][d], rows p * B + b.  wq_t = Wq in the
 // layout of cross_q_layout(); kc, vc [B][heads][T][64]; partial results per key chunk in ws
