@@ -141,6 +141,14 @@ struct EncDec : public Engine {
   // {index into language_meta / lang_code, its probability among the language tokens}; encoder + one decoder position,
   // nothing is transcribed.  Throws std::runtime_error for an English-only engine or on a device error.
   std::pair<int, float> detect_language(std::vector<float>& samples);
+  // An addition: the time-stamped segments of the last transcribe() with the options "timestamps" = 1 and
+  // "max_positions" set (wt_capi.h, wt_last_segments); empty when that call ran without timestamps.
+  struct Segment {
+    int clip = 0, t0_ms = 0, t1_ms = 0;
+    bool open = false;  // the text ran to the end of the window without a closing timestamp
+    std::string text;
+  };
+  std::vector<Segment> segments() const;
   // for the batch entry points and options of wt_capi.h: wt_engine_set_option(handle(), "beam_size", 5) makes both
   // transcribe() overloads decode with beam search
   wt_engine* handle() const { return handle_; }

@@ -81,6 +81,9 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * with beam_size > 1, a caller prompt or the forced-ids tap), "max_tokens" (max decoder positions, whisper.cpp:364,
  * default 30), "max_positions" (0 = default: off, the max_tokens path with its 31 positions; 32 .. n_text_ctx = full-length
  * greedy decoding on the wt_*_tokens_full_batch* and the text entry points, see below and DESIGN.md section 13),
+ * "timestamps" (0 = default: off; 1 = full-length greedy decoding behind Whisper's timestamp rules, see wt_last_segments
+ * below and DESIGN.md section 14; WT_ERR_UNSUPPORTED when the model's vocabulary has no timestamp ids), "max_initial_timestamp"
+ * (latest first timestamp in ticks of 20 ms, default 50 = 1.0 s, -1 = no limit, at most 1500),
  * "stop_at_eot" (whisper.cpp:397-399, default 1), "verbose" (default 0),
  * "cross_chunks" (key chunks per (clip, head) in the decoder cross attention: 1, 2, 4, 8, or 0 = by batch size, the default).
  * Kernel selection (results stay within the fp32 error budget for every value): "gemm_variant"
@@ -224,6 +227,30 @@ int wt_last_languages(const wt_engine* h, int32_t* lang, float* prob, int cap);
  * be taken for a count of one clip). */
 int wt_last_beam_scores(const wt_engine* h, float* sum_logprob, int32_t* n_generated, int cap);
 
+/* Timestamp decoding (option "timestamps" = 1 together with "max_positions").  The default prompt
+ * then ends before <|notimestamps|> ([sot, language, transcribe]; a Monolith engine on an English vocabulary [sot]; a
+ * caller prompt is used as given), and every step of a full-length greedy decode is filtered on the device by Whisper's
+ * timestamp rules: timestamps come in pairs, never decrease, the first id is a timestamp of at most
+ * "max_initial_timestamp" ticks, and a timestamp is chosen when the timestamps' summed probability exceeds every text
+ * token's.  The ids come back as from any full-length call, timestamp ids (token_beg + tick, 20 ms per tick) among them;
+ * the text entry points print those as the vocabulary's own token strings.  With the option set, a decode call is
+ * WT_ERR_UNSUPPORTED without "max_positions" and wherever "max_positions" refuses one (the calls with rows of WT_MAX_IDS
+ * ids, the pipeline, beam_size > 1, the bf16 storage mode, language = WT_LANGUAGE_AUTO, the forced-ids tap); the engine
+ * stays usable after each.
+ * A segment is the text between an opening and a closing timestamp: ids[id_begin .. id_begin + id_count) of the clip's
+ * row, spoken from t0_ms to t1_ms.  Two consecutive timestamps close one segment and open the next; text left unclosed
+ * at the end of the row (EOT or the position cap) closes at the window end, 30 000 ms, with open = 1; an opening
+ * timestamp without text yields no segment. */
+typedef struct wt_segment {
+  int32_t clip, t0_ms, t1_ms, id_begin, id_count, open;
+} wt_segment;
+/* the segments of every clip of the last synchronous timestamp decode, in clip order (at most cap written).  After
+ * wt_transcribe_long_pcm: clip = the window's index, and 30 000 ms x that index is added to both times.  Returns the
+ * segment count, or -WT_ERR_INVALID_ARG when the last synchronous decode ran without timestamps (as wt_last_beam_scores). */
+int wt_last_segments(const wt_engine* h, wt_segment* out, int cap);
+/* the text of segment `index` of that list: its ids decoded as wt_decode_text does with omit_special_tokens = 0 */
+int wt_last_segment_text(const wt_engine* h, int index, char* out, size_t cap, size_t* len);
+
 /* Per-kernel-class device time of the encoder phase of the last batch call: HIP event pairs
  * recorded on the engine's stream around every launch of the class.  flops / bytes are the
  * ALGORITHMIC work of those launches (2*M*N*K per GEMM with the true K, 4*B*H*T*T*64 per
@@ -269,6 +296,9 @@ int wt_vocab_size(const wt_vocab* v);
 int wt_vocab_token(const wt_vocab* v, int id, char* out, size_t cap, size_t* len);
 int wt_vocab_decode(const wt_vocab* v, const int64_t* ids, int n, int omit_special_tokens, char* out,
                     size_t cap, size_t* len);
+/* the segments (see wt_last_segments; clip = 0) of one id row of n ids whose first sample_begin are the prompt; no GPU.
+ * Returns the segment count (at most cap written), or -WT_ERR_INVALID_ARG. */
+int wt_vocab_segments(const wt_vocab* v, const int64_t* ids, int n, int sample_begin, wt_segment* out, int cap);
 
 /* ---- the log-mel front end as a free function ---------------------------------------------
  * Replaces whisper::log_mel_spectrogram (whisper.h:123, whisper.cpp:109-216) for callers that hold a

@@ -106,6 +106,15 @@ int wt_dbg_self_attention(wt_engine* h, int batch, int heads, int cap, int pos, 
  * pos >= cap, cap > 448 and a batch or head count below 1 are WT_ERR_INVALID_ARG, before anything is launched. */
 int wt_dbg_self_attention_long(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
                                float* vcache, float* out);
+/* ts_partial + ts_select (k_timestamps.hip, option "timestamps"): one step of Whisper's timestamp
+ * rules per row.  logits [B][V]; row b of ids [B][ids_stride] holds n_ids[b] ids, the first sample_begin of them the
+ * prompt, and the step decides the id that follows them: token[b].  L [B] (optional) = rule 5's logsumexp of the allowed
+ * timestamp logits, M [B] (optional) = the best allowed logit below beg; NaN where no such id is allowed.  The carried
+ * state is derived from the id row on the device (ts_state_init).  Needs 0 <= eot < beg < V <= 262144, B <= 64 and
+ * 1 <= sample_begin <= n_ids[b] <= ids_stride, else WT_ERR_INVALID_ARG before anything is launched. */
+int wt_dbg_timestamp_select(wt_engine* h, int B, int V, const float* logits, const int64_t* ids, int ids_stride,
+                            const int32_t* n_ids, int sample_begin, int eot, int beg, int max_initial_timestamp,
+                            int64_t* token, double* L, float* M);
 /* bf16 storage mode kernels (option "bf16"): operands are rounded to bf16 on the host, contracted by
  * gemm_bf16_planes / encoder_attention_planes<true>; bf16_out = 1 returns the kernel's bf16 output widened to fp32 */
 int wt_dbg_gemm_bf16(wt_engine* h, int M, int N, int K, const float* A, const float* W, const float* bias,

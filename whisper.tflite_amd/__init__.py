@@ -44,6 +44,7 @@ CAPI_SYMBOLS = [
     "wt_encdec_tokens_batch_dev", "wt_transcribe_tokens_batch_dev", "wt_pipeline_submit_dev", "wt_pipeline_submit_pcm_dev", "wt_pipeline_collect",
     "wt_encdec_debug_batch",
     "wt_encdec_tokens_full_batch", "wt_encdec_tokens_full_batch_dev", "wt_transcribe_tokens_full_batch_dev",
+    "wt_last_segments", "wt_last_segment_text", "wt_vocab_segments",
     "wt_language_count", "wt_detect_language_batch", "wt_detect_language_batch_dev", "wt_detect_language_pcm", "wt_last_languages",
     "wt_last_timings", "wt_last_beam_scores", "wt_last_kernel_stats", "wt_decode_text", "wt_language_id", "wt_lang_code", "wt_wav_read_legacy",
     "wt_vocab_info", "wt_filters", "wt_write_synthetic_weights", "wt_write_synthetic_vocab",
@@ -58,6 +59,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_self_attention_long",
+    "wt_dbg_timestamp_select",
 ]
 
 
@@ -204,6 +206,11 @@ def lib() -> ctypes.CDLL:
         L.wt_encdec_tokens_full_batch_dev.argtypes = [c_void_p, c_void_p, c_int, ip64, c_int, ip32]
         L.wt_transcribe_tokens_full_batch_dev.argtypes = [c_void_p, c_void_p, c_int, ip64, c_int, ip32]
         L.wt_dbg_self_attention_long.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp]
+        L.wt_last_segments.argtypes = [c_void_p, c_void_p, c_int]
+        L.wt_last_segment_text.argtypes = [c_void_p, c_int, c_char_p, c_size_t, POINTER(c_size_t)]
+        L.wt_vocab_segments.argtypes = [c_void_p, ip64, c_int, c_int, c_void_p, c_int]
+        L.wt_dbg_timestamp_select.argtypes = [c_void_p, c_int, c_int, fp, ip64, c_int, ip32, c_int, c_int, c_int, c_int,
+                                              ip64, POINTER(ctypes.c_double), fp]
         _lib = L
     return _lib
 
@@ -272,6 +279,21 @@ def wav_read_legacy(path: str) -> np.ndarray:
     return out
 
 
+# one time-stamped segment (wt_segment): the text ids row[id_begin : id_begin + id_count] of clip
+# `clip`, spoken from t0_ms to t1_ms; open = the text ran to the end of the row without a closing timestamp
+SEGMENT_DTYPE = np.dtype([(k, np.int32) for k in ("clip", "t0_ms", "t1_ms", "id_begin", "id_count", "open")])
+
+
+def _segments(call):
+    n = call(None, 0)
+    if n < 0:
+        raise WtError(-n, "no timestamp segments: the last synchronous decode ran without timestamps, or bad arguments")
+    out = np.zeros(n, SEGMENT_DTYPE)
+    if n:
+        call(out.ctypes.data_as(c_void_p), n)
+    return out
+
+
 class Vocab:
     """Host-side mirror of the reference's ``Vocab`` + ``Filters`` as ``Reader::read`` fills them
     (whisper.h:44-101, :236-248) and of ``decode`` (whisper.h:252-257).  Needs no GPU."""
@@ -328,6 +350,13 @@ class Vocab:
         if rc != WT_OK:
             raise WtError(rc, lib().wt_last_error(None).decode())
         return buf.raw[: n.value]
+
+    def segments(self, ids, sample_begin: int = 0) -> np.ndarray:
+        """The timestamp segments of one id row whose first sample_begin ids are the prompt (SEGMENT_DTYPE records, clip
+        = 0): text between an opening and a closing timestamp id; unclosed text ends at 30 000 ms with open = 1."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        return _segments(lambda out, cap: lib().wt_vocab_segments(self._v, ids.ctypes.data_as(POINTER(c_int64)), ids.size,
+                                                                  int(sample_begin), out, cap))
 
 
 def log_mel_spectrogram(samples, filters, device_id: int = 0) -> np.ndarray:
@@ -528,6 +557,21 @@ class Engine:
         lens = np.zeros(n, np.int32)
         lib().wt_last_beam_scores(self._h, _fp(sums), lens.ctypes.data_as(POINTER(c_int32)), n)
         return sums, lens
+
+    # -- timestamp decoding (options timestamps + max_positions) ----
+    def last_segments(self, with_text: bool = False):
+        """SEGMENT_DTYPE records of every clip of the last synchronous timestamp decode (after transcribe_long: clip = the
+        window's index, times in the file); with_text: (records, [bytes of each segment's text])."""
+        segs = _segments(lambda out, cap: lib().wt_last_segments(self._h, out, cap))
+        if not with_text:
+            return segs
+        texts = []
+        for i in range(segs.size):
+            buf = ctypes.create_string_buffer(1 << 16)
+            n = c_size_t(0)
+            self._check(lib().wt_last_segment_text(self._h, i, buf, len(buf), byref(n)))
+            texts.append(buf.raw[: n.value])
+        return segs, texts
 
     # -- spoken-language detection (DESIGN.md section 12) ---------------------------
     def language_count(self) -> int:
@@ -812,6 +856,21 @@ class Engine:
         fn = lib().wt_dbg_self_attention_bf16 if bf16 else lib().wt_dbg_self_attention
         self._check(fn(self._h, B, d // 64, cap, pos, npos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
         return out, kcache, vcache
+
+    def dbg_timestamp_select(self, logits, ids, n_ids, sample_begin, eot, beg, max_initial_timestamp=50):
+        """One step of the timestamp rules (k_timestamps.hip) per row: logits [B][V], ids [B][stride] with n_ids [B]
+        ids each, the first sample_begin the prompt -> (token int64 [B], L float64 [B], M float32 [B]); L / M are NaN
+        where no timestamp / no id below beg is allowed."""
+        logits = _f32(logits)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        n_ids = np.ascontiguousarray(n_ids, dtype=np.int32)
+        B, V = logits.shape
+        assert ids.shape[0] == B and n_ids.shape == (B,)
+        tok, L, M = np.zeros(B, np.int64), np.zeros(B, np.float64), np.zeros(B, np.float32)
+        self._check(lib().wt_dbg_timestamp_select(self._h, B, V, _fp(logits), _ip64(ids), ids.shape[1], _ip32(n_ids),
+                                                  int(sample_begin), int(eot), int(beg), int(max_initial_timestamp),
+                                                  _ip64(tok), L.ctypes.data_as(POINTER(ctypes.c_double)), _fp(M)))
+        return tok, L, M
 
     def dbg_self_attention_long(self, qkv, kcache, vcache, pos):
         """self_attention_long: one new position against caches [B][cap][d] (cap <= 448); returns (out [B][d], kcache,

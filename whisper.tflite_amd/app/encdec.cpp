@@ -4,6 +4,7 @@
 // "language: <code> (p=...)" per 30 s window before it).  The reference pulls
 // in the 11 kLoC CLI11 header for three required options; a minimal parser keeps the same
 // flags (and --flag=value spelling) and exit status on a usage error.
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -27,13 +28,15 @@ void usage(const char* argv0) {
             << "  --long          transcribe every 30 s window of the file, not only the first\n"
             << "  --beam N        beam search with N hypotheses, 2..8 (default: greedy, as the reference)\n"
             << "  --max-positions N  full-length greedy decoding over N positions, 32 .. n_text_ctx (default: the\n"
-            << "                  reference's 31 positions)\n";
+            << "                  reference's 31 positions)\n"
+            << "  --timestamps    with --max-positions: decode with timestamps and print one line per segment,\n"
+            << "                  [mm:ss.mmm --> mm:ss.mmm] text\n";
 }
 }  // namespace
 
 int main(int argc, char* argv[]) {
   std::string model_prefix, vocab, input, lang, beam, max_positions;
-  bool long_audio = false, english = false;
+  bool long_audio = false, english = false, timestamps = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], v;
     if (a == "-h" || a == "--help") {
@@ -46,6 +49,10 @@ int main(int argc, char* argv[]) {
     }
     if (a == "--english") {
       english = true;
+      continue;
+    }
+    if (a == "--timestamps") {
+      timestamps = true;
       continue;
     }
     const size_t eq = a.find('=');
@@ -114,6 +121,16 @@ int main(int argc, char* argv[]) {
       return 105;
     }
   }
+  if (timestamps) {
+    if (max_positions.empty()) {
+      std::cerr << "--timestamps requires --max-positions\n";
+      return 105;
+    }
+    if (wt_engine_set_option(encdec.handle(), "timestamps", 1) != WT_OK) {
+      std::cerr << "--timestamps: " << wt_last_error(encdec.handle()) << "\n";
+      return 105;
+    }
+  }
   std::string text;
   if (long_audio) {
     std::vector<float> pcm = wav_read_legacy(input.c_str());
@@ -140,6 +157,17 @@ int main(int argc, char* argv[]) {
       wt_last_languages(encdec.handle(), l.data(), p.data(), n);
       for (int i = 0; i < n; ++i) std::cout << "language: " << lang_code(size_t(l[i])) << " (p=" << p[i] << ")\n";
     }
+  }
+  if (timestamps) {
+    auto stamp = [](int ms) {
+      char b[32];
+      std::snprintf(b, sizeof b, "%02d:%02d.%03d", ms / 60000, ms / 1000 % 60, ms % 1000);
+      return std::string(b);
+    };
+    for (const EncDec::Segment& s : encdec.segments()) {
+      std::cout << "[" << stamp(s.t0_ms) << " --> " << stamp(s.t1_ms) << "] " << s.text << "\n";
+    }
+    return 0;
   }
   std::cout << text << "\n";
   return 0;

@@ -76,6 +76,7 @@ void hipchk(hipError_t e, const char* what) {
 
 // the token calls with rows of WT_MAX_IDS ids cannot return a full-length decode
 void refuse_fixed_rows(const wt::Engine& e) {
+  e.check_timestamp_call();
   if (e.max_positions > 0) {
     throw wt::Error(WT_ERR_UNSUPPORTED, "max_positions is set: rows of WT_MAX_IDS ids cannot hold the result, use the "
                                         "wt_*_tokens_full_batch* entry points (or set max_positions to 0)");
@@ -210,6 +211,16 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
       return fail(h, WT_ERR_INVALID_ARG, "max_positions must be 0 (off) or in [32, n_text_ctx] (at most 448)");
     }
     e.max_positions = value;
+  } else if (k == "timestamps") {
+    // timestamp decoding: full-length greedy decoding behind Whisper's timestamp rules
+    if (value != 0 && value != 1) return fail(h, WT_ERR_INVALID_ARG, "timestamps must be 0 or 1");
+    if (value == 1 && !e.has_timestamp_tokens()) {
+      return fail(h, WT_ERR_UNSUPPORTED, "timestamps: the model's vocabulary has no timestamp ids (n_vocab <= token_beg + 1)");
+    }
+    e.timestamps = value;
+  } else if (k == "max_initial_timestamp") {
+    if (value < -1 || value > 1500) return fail(h, WT_ERR_INVALID_ARG, "max_initial_timestamp must be in [-1, 1500] (ticks of 20 ms, -1 = no limit)");
+    e.max_initial_timestamp = value;
   } else if (k == "stop_at_eot") {
     e.stop_at_eot = value != 0;
   } else if (k == "verbose") {
@@ -287,6 +298,8 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   if (k == "language") *value = e.language;
   else if (k == "max_tokens") *value = e.max_tokens;
   else if (k == "max_positions") *value = e.max_positions;
+  else if (k == "timestamps") *value = e.timestamps;
+  else if (k == "max_initial_timestamp") *value = e.max_initial_timestamp;
   else if (k == "stop_at_eot") *value = e.stop_at_eot;
   else if (k == "verbose") *value = e.verbose;
   else if (k == "cross_chunks") *value = e.cross_chunks;
@@ -554,6 +567,29 @@ int wt_last_beam_scores(const wt_engine* h, float* sum_logprob, int32_t* n_gener
   return n;
 }
 
+static int copy_segments(const std::vector<wt::Segment>& v, wt_segment* out, int cap) {
+  static_assert(sizeof(wt_segment) == sizeof(wt::Segment), "wt_segment mirrors wt::Segment");
+  for (int i = 0; i < int(v.size()) && i < cap; ++i) std::memcpy(&out[i], &v[i], sizeof(wt_segment));
+  return int(v.size());
+}
+
+int wt_last_segments(const wt_engine* h, wt_segment* out, int cap) {
+  if (!h || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_segments_valid) return -WT_ERR_INVALID_ARG;
+  return copy_segments(e.last_segments, out, cap);
+}
+
+int wt_last_segment_text(const wt_engine* h, int index, char* out, size_t cap, size_t* len) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_segments_valid || index < 0 || size_t(index) >= e.last_segment_text.size()) {
+    if (len) *len = 0;
+    return WT_ERR_INVALID_ARG;
+  }
+  return copy_text(e.last_segment_text[size_t(index)], out, cap, len);
+}
+
 // ------------------------------------------------- language detection ---
 
 int wt_language_count(const wt_engine* h) {
@@ -644,6 +680,7 @@ int wt_transcribe_pcm(wt_engine* h, const float* pcm, size_t n_samples, char* ou
   const int rc = guarded(h, [&] {
     wt::Engine& e = *h->impl;
     e.require_idle();
+    e.check_timestamp_call();  // before anything is enqueued
     // pad with zeros or truncate to one 30 s window (whisper.cpp:753)
     std::vector<float> clip(e.pcm_elems(), 0.0f);
     std::memcpy(clip.data(), pcm, std::min(n_samples, clip.size()) * sizeof(float));
@@ -681,10 +718,13 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
   const int rc = guarded(h, [&] {
     wt::Engine& e = *h->impl;
     e.require_idle();
+    e.check_timestamp_call();  // before anything is enqueued
     const size_t win = e.pcm_elems();
     const size_t n_win = std::max<size_t>(1, (n_samples + win - 1) / win);
     std::vector<int> langs;  // automatic language: every window's, joined over the batches
     std::vector<float> lang_probs;
+    std::vector<wt::Segment> segments;  // option timestamps: every window's, clip = window index, times in the file
+    std::vector<std::string> segment_text;
     for (size_t w0 = 0; w0 < n_win; w0 += 32) {
       const int B = int(std::min<size_t>(32, n_win - w0));
       std::vector<float> clips(size_t(B) * win, 0.0f);
@@ -712,6 +752,14 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
         langs.insert(langs.end(), e.last_lang.begin(), e.last_lang.end());
         lang_probs.insert(lang_probs.end(), e.last_lang_prob.begin(), e.last_lang_prob.end());
       }
+      if (e.last_segments_valid) {
+        for (wt::Segment sg : e.last_segments) {
+          sg.clip += int(w0);
+          sg.t0_ms += wt::kWindowMs * sg.clip, sg.t1_ms += wt::kWindowMs * sg.clip;
+          segments.push_back(sg);
+        }
+        segment_text.insert(segment_text.end(), e.last_segment_text.begin(), e.last_segment_text.end());
+      }
       for (int b = 0; b < B; ++b) {
         if (w0 + b) text += '\n';
         bool missing = false;
@@ -719,6 +767,7 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
       }
     }
     if (e.last_lang_valid) e.last_lang = langs, e.last_lang_prob = lang_probs;
+    if (e.last_segments_valid) e.last_segments = segments, e.last_segment_text = segment_text;
   });
   if (rc != WT_OK) {
     if (len) *len = 0;
@@ -850,6 +899,13 @@ int wt_vocab_decode(const wt_vocab* v, const int64_t* ids, int n, int omit_speci
     return fail(nullptr, WT_ERR_INVALID_ARG, "token id without a vocab entry");
   }
   return copy_text(s, out, cap, len);
+}
+
+int wt_vocab_segments(const wt_vocab* v, const int64_t* ids, int n, int sample_begin, wt_segment* out, int cap) {
+  if (!v || n < 0 || (!ids && n) || sample_begin < 0 || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
+  std::vector<wt::Segment> segs;
+  wt::parse_segments(v->vocab, ids, n, sample_begin, 0, &segs);
+  return copy_segments(segs, out, cap);
 }
 
 // ------------------------------------------- log-mel as a free function ---
@@ -1920,6 +1976,55 @@ int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* record
     dids.to_host(reinterpret_cast<long long*>(ids));
     dn.to_host(n_ids);
     dfin.to_host(finished);
+  });
+}
+
+int wt_dbg_timestamp_select(wt_engine* h, int B, int V, const float* logits, const int64_t* ids, int ids_stride,
+                            const int32_t* n_ids, int sample_begin, int eot, int beg, int max_initial_timestamp,
+                            int64_t* token, double* L, float* M) {
+  if (!h || !logits || !ids || !n_ids || !token || B < 1 || B > 64 || V < 2 || ids_stride < 1 || sample_begin < 0) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    // every row decides the step behind ITS n_ids[b] ids; the kernels take one step count per launch, so runs of
+    // consecutive rows with equal n_ids are launched together (a run's launch sees only its own rows: same grid-independent arithmetic)
+    const int ldl = (V + 3) & ~3;
+    for (int b = 0; b < B; ++b) {
+      if (n_ids[b] < sample_begin || n_ids[b] > ids_stride) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_timestamp_select: n_ids outside [sample_begin, ids_stride]");
+    }
+    std::vector<float> padded(size_t(B) * ldl, 0.0f);
+    for (int b = 0; b < B; ++b) std::memcpy(&padded[size_t(b) * ldl], logits + size_t(b) * V, size_t(V) * sizeof(float));
+    // id rows with one more column: the kernel writes the token at ids[b][n_ids[b]]
+    const int stride = ids_stride + 1;
+    std::vector<long long> rows(size_t(B) * stride, 0);
+    for (int b = 0; b < B; ++b)
+      for (int i = 0; i < n_ids[b]; ++i) rows[size_t(b) * stride + i] = ids[size_t(b) * ids_stride + i];
+    DevArr<float> dlog(padded.size(), padded.data());
+    DevArr<long long> dids(rows.size(), rows.data());
+    DevArr<int> dn(B, n_ids), dfin(B);
+    DevArr<wt::TsPart> dpart(size_t(B) * wt::ts_chunks(V));
+    DevArr<wt::TsState> dstate(B);
+    DevArr<double> dL(B);
+    DevArr<float> dM(B);
+    hipchk(hipMemsetAsync(dfin.p, 0, size_t(B) * sizeof(int), h->impl->stream()), "memset");
+    wt::launch_ts_state_init(dids.p, stride, dn.p, 0, sample_begin, V, beg, dstate.p, B, h->impl->stream());
+    for (int b0 = 0, b1 = 0; b0 < B; b0 = b1 + 1) {
+      b1 = b0;  // the run of consecutive rows with n_ids[b0]
+      while (b1 + 1 < B && n_ids[b1 + 1] == n_ids[b0]) ++b1;
+      wt::TsSelectArgs t;
+      t.logits = dlog.p + size_t(b0) * ldl; t.ldl = ldl; t.V = V; t.batch = b1 - b0 + 1;
+      t.eot = eot; t.beg = beg; t.max_initial = max_initial_timestamp;
+      t.n_gen = n_ids[b0] - sample_begin; t.part = dpart.p + size_t(b0) * wt::ts_chunks(V); t.state = dstate.p + b0;
+      t.ids = dids.p + size_t(b0) * stride; t.ids_stride = stride; t.pos = n_ids[b0] - 1; t.stop_at_eot = 1;
+      t.n_ids = dn.p + b0; t.finished = dfin.p + b0;
+      t.dbg_L = dL.p + b0; t.dbg_M = dM.p + b0;
+      wt::launch_ts_select(t, h->impl->stream());
+    }
+    h->impl->sync();
+    dids.to_host(rows.data());
+    for (int b = 0; b < B; ++b) token[b] = rows[size_t(b) * stride + n_ids[b]];
+    if (L) dL.to_host(L);
+    if (M) dM.to_host(M);
   });
 }
 

@@ -1624,9 +1624,11 @@ void Engine::set_bf16(bool on) {
 void Engine::decode(int batch, int64_t* ids, int32_t* n_ids, float* logits_host,
                     int logits_steps_cap) {
   require_idle();
+  check_timestamp_call();
   check_language_call();
   check_beam_call(logits_host != nullptr);
   last_lang_valid = false;
+  last_segments_valid = false;
   if (beam_size > 1) {
     decode_beam(batch, last_enc_slot_, ids, n_ids);
     return;
@@ -1759,6 +1761,7 @@ void Engine::submit_decoder(int batch, int s) {
 }
 
 void Engine::submit(const float* d_mel, int batch) {
+  check_timestamp_call();
   if (max_positions > 0) throw Error(kErrUnsupported, "full-length decoding (max_positions) runs on the synchronous entry points only, not in the pipeline");
   if (beam_size > 1) throw Error(kErrUnsupported, "beam search runs on the synchronous entry points only, not in the pipeline");
   check_language_call();
@@ -1772,6 +1775,7 @@ void Engine::submit(const float* d_mel, int batch) {
 }
 
 void Engine::submit_pcm(const float* d_pcm, int batch) {
+  check_timestamp_call();
   if (max_positions > 0) throw Error(kErrUnsupported, "full-length decoding (max_positions) runs on the synchronous entry points only, not in the pipeline");
   if (beam_size > 1) throw Error(kErrUnsupported, "beam search runs on the synchronous entry points only, not in the pipeline");
   check_language_call();
@@ -1802,7 +1806,12 @@ std::vector<long long> Engine::prompt() const {
   // Monolith: the forced decoder ids HF generate() applies inside the reference's single graph
   // (export/generate.py:24-30): English-only checkpoints [sot, notimestamps] — the head of kGoldenGeneratedIDs,
   // whisper.h:27-32 — multilingual ones [sot, language, transcribe, notimestamps].
-  if (monolith_ && !multilingual_) return {vocab_.token_sot, vocab_.token_not};
+  // option timestamps: the same prompts without their last id, <|notimestamps|>
+  if (monolith_ && !multilingual_) {
+    if (timestamps) return {vocab_.token_sot};
+    return {vocab_.token_sot, vocab_.token_not};
+  }
+  if (timestamps) return {vocab_.token_sot, kLangLo + std::max<long>(language, 0), vocab_.token_transcribe};
   // (language = -1: position 1 is a placeholder that language_head overwrites on the device, decode_enqueue)
   return {vocab_.token_sot, kLangLo + std::max<long>(language, 0), vocab_.token_transcribe, vocab_.token_not};
 }
@@ -2483,7 +2492,16 @@ void Engine::decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids) 
 
 // ------------------------------------------------ full-length decoding ---
 
+// option timestamps outside full-length decoding: every decode call is refused (with max_positions set, the refusals
+// of check_full_call and of the other entry points apply as they are)
+void Engine::check_timestamp_call() const {
+  if (timestamps && max_positions <= 0) {
+    throw Error(kErrUnsupported, "timestamps: full-length greedy decoding only, set the option max_positions (32 .. n_text_ctx)");
+  }
+}
+
 void Engine::check_full_args(int batch, int ids_stride) const {
+  check_timestamp_call();
   if (max_positions <= 0) throw Error(kErrInvalidArg, "the full-length entry points need the option max_positions (32 .. n_text_ctx)");
   check_full_call();
   if (batch < 1 || batch > 64) throw Error(kErrInvalidArg, "decoder batches are limited to 64 clips per call");
@@ -2497,6 +2515,7 @@ void Engine::check_full_call() const {
   if (bf16) no("not in the bf16 storage mode");
   if (language < 0) no("not with automatic language detection (language = -1)");
   if (!forced_ids.empty()) no("not with forced ids");
+  if (timestamps && !has_timestamp_tokens()) no("timestamps: the model's vocabulary has no timestamp ids");
 }
 
 // A full-length call is synchronous and finds the engine idle, so it may choose its pipeline slot: always slot 0, and
@@ -2551,6 +2570,13 @@ void Engine::ensure_full_workspace(int batch) {
     fw_.kv = static_cast<float*>(alloc(size_t(c.n_text_layer) * 2 * size_t(batch) * cap * d * sizeof(float)));
     fw_.kv_clips = batch;
   }
+  if (timestamps && !fw_.ts_state) {  // (allocated last of the three)
+    const size_t ldl = (size_t(c.n_vocab) + 3) & ~size_t(3);
+    fw_.ts_logits = static_cast<float*>(alloc(C * ldl * sizeof(float)));
+    fw_.ts_ldl = int(ldl);
+    fw_.ts_part = static_cast<TsPart*>(alloc(C * size_t(ts_chunks(c.n_vocab)) * sizeof(TsPart)));
+    fw_.ts_state = static_cast<TsState*>(alloc(C * sizeof(TsState)));
+  }
   if (fw_.h_fin) return;  // (allocated last)
   fw_.ids = static_cast<long long*>(alloc(C * (cap + 1) * sizeof(long long)));
   void* p = nullptr;
@@ -2574,6 +2600,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   const int P = int(max_positions), slot_idx = last_enc_slot_;
   last_lang_valid = false;
   beam_scores_valid = false;
+  last_segments_valid = false;
+  const bool ts = timestamps != 0;
   ensure_batch(batch);
   ensure_full_workspace(batch);  // (before any capture: nothing may be allocated inside one)
   Slot& slot = slots_[slot_idx];
@@ -2612,6 +2640,9 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   HIPCHK(hipMemcpyAsync(fw_.ids, fw_.h_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(dw.n_ids, fw_.h_n, size_t(batch) * sizeof(int), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(dw.finished, 0, size_t(batch) * sizeof(int), st));
+  if (ts) {  // the carried state of the timestamp rules: nothing generated yet
+    launch_ts_state_init(fw_.ids, stride, nullptr, n_prompt, n_prompt, V, vocab_.token_beg, fw_.ts_state, batch, st);
+  }
 
   // the passes whose first position lies in [lo, hi); returns the argmax steps among them
   auto enqueue_segment = [&](int lo, int hi) {
@@ -2694,9 +2725,20 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
         lg.Wt = tok_emb_tiled.w; lg.w_scale = tok_emb_tiled.scale; lg.N = V; lg.K = d; lg.B = batch;
         lg.xin = (split ? dw.xb : x) + off; lg.xpart = split ? dw.xpart + off : nullptr; lg.ln_g = dec_ln_g; lg.ln_b = dec_ln_b;
         lg.Y = nullptr; lg.ldy = V; lg.best = dw.best;
+        if (ts) lg.Y = fw_.ts_logits, lg.ldy = fw_.ts_ldl;  // the timestamp rules read the whole row
         launch_dec_gemm(lg, kProLn, kDecLogits, st);
-        launch_select_token(dw.best, (V + 31) / 32, fw_.ids, stride, last, dw.n_ids, dw.finished, vocab_.token_eot,
-                            int(stop_at_eot), batch, st);
+        if (ts) {
+          TsSelectArgs t;
+          t.logits = fw_.ts_logits; t.ldl = fw_.ts_ldl; t.V = V; t.batch = batch;
+          t.eot = vocab_.token_eot; t.beg = vocab_.token_beg; t.max_initial = int(max_initial_timestamp);
+          t.n_gen = last + 1 - n_prompt; t.part = fw_.ts_part; t.state = fw_.ts_state;
+          t.ids = fw_.ids; t.ids_stride = stride; t.pos = last; t.stop_at_eot = int(stop_at_eot);
+          t.n_ids = dw.n_ids; t.finished = dw.finished;
+          launch_ts_select(t, st);
+        } else {
+          launch_select_token(dw.best, (V + 31) / 32, fw_.ids, stride, last, dw.n_ids, dw.finished, vocab_.token_eot,
+                              int(stop_at_eot), batch, st);
+        }
         ++seg_steps;
       }
     }
@@ -2708,7 +2750,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     const int hi = std::min(P, lo + 32);
     // (greedy's keys start with the slot, a beam key with -beam_size; a full-length key starts with kFullKey)
     const std::vector<long long> key{kFullKey, slot_idx, batch, lo, P, n_prompt, chunks, long(stop_at_eot), fc2_ksplit,
-                                     absorbed ? 1 : 0, n_abs, slot.dec};
+                                     absorbed ? 1 : 0, n_abs, slot.dec, ts ? 1 : 0, ts ? max_initial_timestamp : 0};
     auto it = use_graphs ? graphs_.find(key) : graphs_.end();
     if (it != graphs_.end()) {
       HIPCHK(hipGraphLaunch(it->second.exec, st));
@@ -2759,6 +2801,20 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     for (int i = 0; i < ids_stride; ++i) {
       ids[size_t(b) * ids_stride + i] = i < fw_.h_n[b] && i < stride ? fw_.h_ids[size_t(b) * stride + i] : 0;
     }
+  }
+  if (ts) {
+    last_segments.clear();
+    last_segment_text.clear();
+    for (int b = 0; b < batch; ++b) {
+      const int64_t* const row = reinterpret_cast<const int64_t*>(fw_.h_ids + size_t(b) * stride);
+      const size_t first = last_segments.size();
+      parse_segments(vocab_, row, std::min(fw_.h_n[b], stride), n_prompt, b, &last_segments);
+      for (size_t i = first; i < last_segments.size(); ++i) {
+        bool missing = false;
+        last_segment_text.push_back(decode_tokens(vocab_, row + last_segments[i].id_begin, last_segments[i].id_count, false, &missing));
+      }
+    }
+    last_segments_valid = true;
   }
 }
 

@@ -16,6 +16,9 @@
 
 namespace wt {
 
+struct TsPart;   // kernels.h
+struct TsState;
+
 struct BeamPart;  // kernels.h
 
 struct Timings {
@@ -167,6 +170,20 @@ class Engine {
   // ids_stride >= max_positions + 1, batch <= 64.  Synchronises.
   void decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids);
   void encode_full(const float* d_mel, int batch);  // encode() into slot 0: the slot every full-length call uses
+  // Timestamp decoding.  1: the default prompt ends before <|notimestamps|> and decode_full applies
+  // Whisper's timestamp rules on the device (k_timestamps.hip) in place of select_token.  Full-length greedy decoding
+  // only: with the option set every decode call outside that scope is kErrUnsupported (check_timestamp_call; with
+  // max_positions set, check_full_call and the refusals of the other entry points cover the rest).
+  long timestamps = 0;
+  long max_initial_timestamp = 50;  // ticks of 20 ms allowed for the first timestamp (Whisper's 1.0 s); -1 = no limit
+  // the model's logits reach past <|0.00|>: ids token_beg .. n_vocab - 1 are the timestamps
+  bool has_timestamp_tokens() const { return dims_.n_vocab > vocab_.token_beg + 1 && vocab_.token_eot >= 0 && vocab_.token_eot < vocab_.token_beg; }
+  void check_timestamp_call() const;
+  // segments of every clip of the last synchronous timestamp decode (clip = index in the call; wt_transcribe_long_pcm
+  // renumbers them per window); valid = the last synchronous decode ran with timestamps
+  std::vector<Segment> last_segments;
+  std::vector<std::string> last_segment_text;  // the decoded text ids of each
+  bool last_segments_valid = false;
   long gemm_variant = -1;  // -1 = plane GEMM (per-contraction fall-back to 13/16); 0 = fp32 MFMA, 13 / 16 = three bf16 planes
   // 1 = bf16 STORAGE mode (BASELINE configs[3]): bf16 weights, activations and both KV caches, fp32 accumulation,
   // fp32 residual stream; k_gemm_bf16.hip and the BF variants of the attention / decoder kernels.  Set through
@@ -293,6 +310,12 @@ class Engine {
     long long* ids = nullptr;       // id rows [64][full_cap() + 1]
     long long* h_ids = nullptr;     // pinned mirror of the id rows
     int *h_n = nullptr, *h_fin = nullptr;  // pinned [64]: id counts, finished flags after a segment
+    // option timestamps (allocated on the first such call): the logits of a step [64][ts_ldl], rows 16-byte aligned,
+    // the per-chunk records [64][ts_chunks(n_vocab)] and the carried state [64]
+    float* ts_logits = nullptr;
+    int ts_ldl = 0;
+    TsPart* ts_part = nullptr;
+    TsState* ts_state = nullptr;
   } fw_;
   void ensure_full_workspace(int batch);
   static constexpr long long kFullKey = -1000;  // first entry of a full-length segment's graph key

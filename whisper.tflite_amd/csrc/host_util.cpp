@@ -324,4 +324,21 @@ std::string remove_extra_spaces(const std::string& in) {
   return out;
 }
 
+void parse_segments(const VocabData& vocab, const int64_t* ids, int n, int sample_begin, int clip, std::vector<Segment>* out) {
+  int t_open = 0, begin = -1, count = 0;
+  for (int i = std::max(sample_begin, 0); i < n; ++i) {
+    const int64_t id = ids[i];
+    if (id == vocab.token_eot) break;
+    if (id >= vocab.token_beg) {
+      const int ms = int(std::min<int64_t>(id - vocab.token_beg, 1500)) * 20;
+      if (count > 0) out->push_back(Segment{clip, t_open, ms, begin, count, 0});
+      t_open = ms, begin = -1, count = 0;
+    } else {
+      if (count == 0) begin = i;
+      ++count;
+    }
+  }
+  if (count > 0) out->push_back(Segment{clip, t_open, kWindowMs, begin, count, 1});
+}
+
 }  // namespace wt

@@ -64,6 +64,17 @@ std::string decode_tokens(const VocabData& vocab, const int64_t* ids, int n,
                           bool omit_special_tokens, bool* missing);
 std::string remove_extra_spaces(const std::string& in);
 
+// Timestamp segments of one id row: the text ids between an opening and a closing timestamp
+// (ids >= token_beg, 20 ms per tick).  ids[sample_begin .. n) are read up to the first EOT.  A timestamp behind text
+// closes the segment and opens the next; one behind a timestamp opens anew; text left unclosed at the end of the row
+// closes at the window end (30 000 ms) with open = 1; text without an opening timestamp starts at 0.  Every id below
+// token_beg other than EOT counts as text.  Appends to *out.
+struct Segment {
+  int32_t clip, t0_ms, t1_ms, id_begin, id_count, open;  // ids[id_begin .. id_begin + id_count): the text, timestamps excluded
+};
+constexpr int kWindowMs = 30000;
+void parse_segments(const VocabData& vocab, const int64_t* ids, int n, int sample_begin, int clip, std::vector<Segment>* out);
+
 int language_count();
 int language_id(const std::string& code);  // == language_count() when absent
 const std::string& lang_code(size_t id);

@@ -387,6 +387,42 @@ struct BeamFinalArgs {
 };
 void launch_beam_finalize(const BeamFinalArgs& a, hipStream_t s);
 
+// ------------------------------------------------------------ timestamps ---
+// k_timestamps.hip (option timestamps): Whisper's timestamp rules on a row of logits, then the greedy
+// step of select_token.  With g the ids a clip has generated, tick(id) = id - beg, last_ts = g[-1] >= beg,
+// pen_ts = |g| < 2 or g[-2] >= beg:  (1) eot < id < beg is masked;  (2) last_ts and pen_ts: id >= beg masked; last_ts and
+// not pen_ts: id < eot masked;  (3) ticks below the last timestamp's (+ 1 unless last_ts and not pen_ts) masked;
+// (4) |g| = 0: id < beg masked, and ticks above max_initial when that is >= 0;  (5) logsumexp of the allowed timestamps
+// above the best allowed text logit: id < beg masked;  (6) argmax, larger id on equal logits.
+constexpr int kTsChunk = 4096;     // vocabulary entries per ts_partial block: fixed, so a row's sums have one order
+constexpr int kTsMaxChunks = 64;   // n_vocab <= 262144
+struct TsState {                   // carried per clip from step to step
+  int tick;                        // tick of the last timestamp generated, -1: none yet
+  int last_is_ts, prev_is_ts;      // g[-1], g[-2] are timestamps (0 where they do not exist)
+};
+struct TsPart {                    // one (clip, chunk); key = order-preserving bits of the logit << 32 | id, 0 = none
+  unsigned long long key_text, key_ts;  // best allowed id below beg, best allowed timestamp
+  float m, s;                           // max of the allowed timestamps' logits, sum of exp(logit - m)
+};
+int ts_chunks(int n_vocab);
+// state[b] from the ids [sample_begin, n) of row b, n = n_ids[b] (or n_fixed for every row when n_ids is nullptr)
+void launch_ts_state_init(const long long* ids, int ids_stride, const int* n_ids, int n_fixed, int sample_begin, int V,
+                          int beg, TsState* state, int batch, hipStream_t s);
+struct TsSelectArgs {
+  const float* logits = nullptr;  // [batch][ldl], ldl % 4 == 0, 16-byte aligned: the logits of position pos
+  int ldl = 0, V = 0, batch = 0;
+  int eot = 0, beg = 0, max_initial = -1;  // 0 <= eot < beg < V
+  int n_gen = 0;                  // ids generated before this step: pos + 1 - sample_begin
+  TsPart* part = nullptr;         // [batch][ts_chunks(V)]
+  TsState* state = nullptr;       // [batch], read and advanced
+  long long* ids = nullptr;       // ids[b][pos + 1] = the token
+  int ids_stride = 0, pos = 0, stop_at_eot = 1;
+  int *n_ids = nullptr, *finished = nullptr;  // as launch_select_token
+  double* dbg_L = nullptr;        // optional [batch]: rule 5's logsumexp and best text logit, NaN where none is allowed
+  float* dbg_M = nullptr;
+};
+void launch_ts_select(const TsSelectArgs& a, hipStream_t s);  // ts_partial + ts_select; throws kErrInvalidArg
+
 // ---- load-time re-layouts of decoder weights (host) ----
 // bf16 storage mode: W [N][K] fp32 -> ONE bf16 plane (round to nearest even) in the same fragment order,
 // [ceil(N/32)][K/16][64 lanes][8]

@@ -80,6 +80,24 @@ std::pair<int, float> detect_samples(wt_engine* h, const std::vector<float>& sam
 }
 }  // namespace
 std::pair<int, float> EncDec::detect_language(std::vector<float>& samples) { return detect_samples(handle_, samples); }
+
+std::vector<EncDec::Segment> EncDec::segments() const {
+  std::vector<Segment> out;
+  const int n = wt_last_segments(handle_, nullptr, 0);
+  if (n <= 0) return out;
+  std::vector<wt_segment> raw(static_cast<size_t>(n));
+  wt_last_segments(handle_, raw.data(), n);
+  for (int i = 0; i < n; ++i) {
+    Segment s;
+    s.clip = raw[i].clip, s.t0_ms = raw[i].t0_ms, s.t1_ms = raw[i].t1_ms, s.open = raw[i].open != 0;
+    size_t len = 0;
+    wt_last_segment_text(handle_, i, nullptr, 0, &len);
+    std::vector<char> buf(len + 1);
+    if (wt_last_segment_text(handle_, i, buf.data(), buf.size(), &len) == WT_OK) s.text.assign(buf.data(), len);
+    out.push_back(s);
+  }
+  return out;
+}
 std::pair<int, float> Monolith::detect_language(std::vector<float>& samples) { return detect_samples(handle_, samples); }
 
 Monolith::Monolith(const std::string& model_prefix, const std::string& vocab_path, bool multilingual)
