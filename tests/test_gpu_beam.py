@@ -166,6 +166,19 @@ def test_parity_eot_rich_micro(pkg, orc, eot_rich):
     model.close()
 
 
+def test_parity_fc2_ksplit_1(pkg, orc, eot_rich):
+    """The chains share one decoder pass: beam search with fc2 unsplit (fc2_ksplit = 1, x handed from layer to layer and
+    to the logits GEMM whole instead of as two halves), 8 clips at beam_size 2, held to the same reference."""
+    prefix, vocab = eot_rich
+    model = orc.Model(prefix + ".wtw")
+    eng = pkg.Engine(prefix, vocab, True)
+    eng.set_option("fc2_ksplit", 1)
+    assert eng.get_option("fc2_ksplit") == 1
+    check_parity(eng, model, mels(8, eng.mel_shape), 2, 30, {})
+    eng.close()
+    model.close()
+
+
 def test_parity_tiny(pkg, orc, tiny_rich):
     prefix, vocab = tiny_rich
     model = orc.Model(prefix + ".wtw")

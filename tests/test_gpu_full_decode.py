@@ -127,6 +127,22 @@ def test_eot_rich_ids_and_counts_equal_the_oracle(rich_eng, rich_mel, rich_ref, 
     assert max(len(w) for w in want) == positions + 1  # a clip runs to the cap
 
 
+def test_fc2_ksplit_1_ids_and_counts_equal_the_oracle(pkg, rich, rich_mel, rich_ref):
+    """The chains share one decoder pass: full-length decoding with fc2 unsplit (fc2_ksplit = 1, x handed from layer to
+    layer and to the logits GEMM whole instead of as two halves), 2 clips at P = 40: one ends early, one runs to the cap
+    (positions past 32, the second segment)."""
+    eng = pkg.Engine(rich[0], rich[1], True)
+    eng.set_option("fc2_ksplit", 1)
+    eng.set_option("max_positions", 40)
+    ids, n = eng.encdec_tokens_full(np.ascontiguousarray(rich_mel[[0, 1]]))
+    check_padding(ids, n)
+    want = [rich_ref[40][b][0] for b in (0, 1)]
+    assert [int(x) for x in n] == [len(w) for w in want]
+    assert rows_of(ids, n) == want
+    assert len(want[0]) < 32 and len(want[1]) == 41
+    eng.close()
+
+
 def test_segment_stop(rich_eng, rich_mel, rich_ref):
     """A chain whose clips all finished inside the first 32 positions ends there; a mixed one runs on."""
     eng = rich_eng

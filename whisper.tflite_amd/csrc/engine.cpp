@@ -1816,6 +1816,180 @@ std::vector<long long> Engine::prompt() const {
   return {vocab_.token_sot, kLangLo + std::max<long>(language, 0), vocab_.token_transcribe, vocab_.token_not};
 }
 
+// ------------------------------------------------------ the decoder pass ---
+
+namespace {
+// begin-capture, enqueue(), end-capture, instantiate: the executable graph of what enqueue() put on the stream.
+// Throws what enqueue() throws, or kErrDevice; nothing stays captured or allocated then.
+template <class F>
+hipGraphExec_t capture_graph(hipStream_t s, F&& enqueue) {
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t ge = nullptr;
+  HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  try {
+    enqueue();
+  } catch (...) {
+    (void)hipStreamEndCapture(s, &graph);
+    if (graph) (void)hipGraphDestroy(graph);
+    throw;
+  }
+  HIPCHK(hipStreamEndCapture(s, &graph));
+  const hipError_t ie = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(graph);
+  if (ie != hipSuccess) throw Error(kErrDevice, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
+  return ge;
+}
+
+// WT_DEC_KERNEL_TIMERS=1 (diagnostics, eager launches only): an event pair around a decoder launch of class `cls`
+// (finish_slot's kNames); without timers the launch alone
+template <class F>
+void timed(DecTimers* t, int cls, F&& launch) {
+  if (!t) return launch();
+  while (t->ev.size() < t->used + 2) {
+    hipEvent_t e;
+    HIPCHK(hipEventCreate(&e));
+    t->ev.push_back(e);
+  }
+  HIPCHK(hipEventRecord(t->ev[t->used], t->stream));
+  launch();
+  HIPCHK(hipEventRecord(t->ev[t->used + 1], t->stream));
+  t->cls.push_back(cls);
+  t->used += 2;
+}
+}  // namespace
+
+int Engine::cross_chunks_for(int batch) const {
+  int chunks = int(cross_chunks);  // 1, 2, 4 or 8 (wt_engine_set_option), 0 = by batch size
+  if (chunks == 0) {
+    chunks = 1;
+    while (chunks < 8 && batch * dims_.n_text_head * chunks < 192) chunks *= 2;
+  }
+  return chunks;
+}
+
+// key chunks of the absorbed form: clips x chunks ~ `blocks` blocks, a chunk a whole number of 32-key tiles
+// (option abs_chunks; 0 = 256 / clips: one block per CU when the decoder has the chip; pipelined 128 / clips — fewer,
+// longer blocks: a block costs ~9 us before its first tile, and the decoders share the CUs the encoder leaves)
+// (bf16 storage mode: half the bytes per key row, so half as many blocks again: 122.5 k against 120.5 k on configs[3])
+int Engine::abs_chunks_for(int clips, int blocks) const {
+  const int n_abs = abs_chunks > 0 ? int(abs_chunks) : std::min(16, std::max(1, (blocks + clips - 1) / clips));
+  return std::min(n_abs, (dims_.n_audio_ctx + 31) / 32);
+}
+
+void Engine::check_prompt_ids(const std::vector<long long>& prompt, int code) const {
+  for (long long id : prompt) {
+    if (id < 0 || id >= dims_.n_vocab) throw Error(code, "prompt token id outside the model's vocabulary");
+  }
+}
+
+// One decoder pass: every layer over the M = np * B rows of positions pos0 .. pos0 + np - 1 (row = p * B + sequence)
+// and, when p.best is set, the final LayerNorm + logits GEMM of the last position's rows.  This is the launch sequence
+// of every decode chain; greedy, beam search and full-length decoding differ in what they put into the DecPass only.
+void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
+  const wtw::Dims& c = dims_;
+  const int d = c.n_text_state, T = c.n_audio_ctx, H = c.n_text_head, V = c.n_vocab;
+  const DecWorkspace& dw = *p.dw;
+  DecTimers* const tm = p.timers;
+  const int B = p.B, M = p.np * B;
+  const bool bf = p.bf, split = p.split;  // bf16 storage mode: bf16 weights and caches (element size 2 in the cache offsets)
+  const size_t kv_slab = size_t(p.clips) * T * d;  // one (layer, k|v) slab of the cross cache
+  const size_t self_slab = size_t(B) * p.self_cap * d;
+  auto cache_at = [&](float* base, size_t elems) -> void* {
+    return bf ? static_cast<void*>(reinterpret_cast<unsigned short*>(base) + elems) : static_cast<void*>(base + elems);
+  };
+  float* const x = dw.xd;  // residual stream [rows][d], updated in place by the residual GEMMs
+  for (int l = 0; l < c.n_text_layer; ++l) {
+    const DecBlockWeights& w = bf ? dec_blocks_bf_[l] : dec_blocks_[l];
+    DecGemmArgs q;  // LN + fused q|k|v projection (+ token/positional embedding at layer 0)
+    q.bf16 = bf;
+    q.Wt = w.wqkv.w; q.w_scale = w.wqkv.scale; q.N = 3 * d; q.K = d; q.B = B; q.M = M;
+    q.xin = x; q.ln_g = w.attn_ln_g; q.ln_b = w.attn_ln_b;
+    if (l > 0 && split) {  // the previous layer's fc2 left x in two halves: sum them, block 0 completes x
+      q.xin = dw.xb; q.xpart = dw.xpart; q.xout = x;
+    }
+    if (l == 0) {
+      q.ids = p.ids; q.ids_stride = p.ids_stride; q.pos = p.pos0; q.tok_emb = tok_emb; q.pos_emb = dec_pos;
+      q.n_vocab = V; q.xout = x;
+    }
+    q.bias = w.bqkv; q.Y = dw.qkvd; q.ldy = 3 * d;
+    timed(tm, 0, [&] { launch_dec_gemm(q, kProLn, kDecBias, st); });
+    void* const kc = cache_at(p.self_kv, (size_t(l) * 2 + 0) * self_slab);
+    void* const vc = cache_at(p.self_kv, (size_t(l) * 2 + 1) * self_slab);
+    timed(tm, 1, [&] {
+      if (p.self_long) {  // one position past 32, fp32 cache (full-length decoding)
+        launch_self_attention_long(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0, dw.attd, B, H, st);
+      } else {
+        launch_self_attention(dw.qkvd, kc, vc, p.self_cap, p.pos0, p.np, dw.attd, B, H, st, bf);
+      }
+    });
+    DecGemmArgs o;  // x += attn . Wo^T + bo
+    o.bf16 = bf;
+    o.Wt = w.wo.w; o.w_scale = w.wo.scale; o.N = d; o.K = d; o.B = B; o.M = M; o.X = dw.attd; o.ldx = d;
+    o.bias = w.bo; o.R = x; o.Y = x; o.ldy = d;
+    timed(tm, 2, [&] { launch_dec_gemm(o, kProNone, kDecResid, st); });
+
+    DecGemmArgs co;  // x += (cross-attention context) . Wco^T + bco
+    co.bf16 = bf;
+    co.Wt = w.cross_wo.w; co.w_scale = w.cross_wo.scale; co.N = d; co.K = d; co.B = B; co.M = M;
+    co.bias = w.cross_bo; co.R = x; co.Y = x; co.ldy = d;
+    if (p.absorbed) {
+      // Cross attention against the encoder output itself (k_cross_absorbed.hip): LN + absorbed query projection
+      // q'_h = c0 Wk_h^T (Wq_h LN(x) + bq_h) for all heads in one GEMM, the matrix-core sweep of E per key chunk
+      // (the M / clips query rows of a clip in groups of 16 / heads query columns), the chunk combine with the heads'
+      // value projections, and the ordinary out-projection.
+      DecGemmArgs qa;
+      qa.bf16 = bf; qa.Wt = w.wq_abs.w; qa.w_scale = w.wq_abs.scale; qa.N = H * d; qa.K = d; qa.B = B; qa.M = M;
+      qa.xin = x; qa.ln_g = w.cross_ln_g; qa.ln_b = w.cross_ln_b; qa.bias = w.bq_abs; qa.Y = dw.qp; qa.ldy = H * d;
+      timed(tm, 3, [&] { launch_dec_gemm(qa, kProLn, kDecBias, st); });
+      const int nq_max = cross_absorbed_max_nq(H), nq_all = M / p.clips;
+      for (int p0 = 0; p0 < nq_all; p0 += nq_max) {
+        CrossAbsorbedArgs ca;
+        ca.qp = dw.qp; ca.e = p.e; ca.e_plane = long(ws_.batch) * T * d; ca.e_scale = sc_cross_kv_.a;
+        ca.bf16 = bf; ca.split = p.e_split; ca.e2 = p.e2; ca.e3 = p.e3; ca.e4 = p.e4;
+        ca.ws = dw.abs_ws; ca.batch = p.clips; ca.heads = H; ca.d_model = d; ca.T = T; ca.chunks = p.n_abs;
+        ca.nq = std::min(nq_max, nq_all - p0); ca.p0 = p0;
+        timed(tm, 4, [&] { launch_cross_absorbed(ca, st); });
+      }
+      timed(tm, 8, [&] { launch_cross_absorbed_combine(dw.abs_ws, w.cross_wv_t, w.cross_bv, dw.cabs, M, H, p.n_abs, d, st); });
+      co.X = dw.cabs; co.ldx = d;
+    } else {
+      CrossAttnArgs ca;  // LN + query projection + attention over the cached encoder keys, per key chunk
+      ca.x = x; ca.ln_g = w.cross_ln_g; ca.ln_b = w.cross_ln_b; ca.wq_t = w.cross_wq_t; ca.bq = w.cross_bq;
+      ca.kc = cache_at(p.cross_kv, (size_t(l) * 2 + 0) * kv_slab); ca.vc = cache_at(p.cross_kv, (size_t(l) * 2 + 1) * kv_slab);
+      ca.bf16 = bf; ca.ws = dw.cross_ws; ca.batch = p.clips; ca.heads = H; ca.T = T; ca.chunks = p.chunks; ca.nq = p.np;
+      timed(tm, 4, [&] { launch_cross_attention(ca, st); });
+      co.cross_ws = dw.cross_ws; co.heads = H; co.chunks = p.chunks;  // the out-projection's prologue combines the chunks
+    }
+    timed(tm, 5, [&] { launch_dec_gemm(co, p.absorbed ? kProNone : kProCombine, kDecResid, st); });
+
+    DecGemmArgs f1;  // LN + fc1 + GELU
+    f1.bf16 = bf;
+    f1.Wt = w.w1.w; f1.w_scale = w.w1.scale; f1.N = 4 * d; f1.K = d; f1.B = B; f1.M = M;
+    f1.xin = x; f1.ln_g = w.mlp_ln_g; f1.ln_b = w.mlp_ln_b;
+    f1.bias = w.b1; f1.Y = dw.hd; f1.ldy = 4 * d;
+    timed(tm, 6, [&] { launch_dec_gemm(f1, kProLn, kDecBiasGelu, st); });
+    DecGemmArgs f2;  // x += h . W2^T + b2
+    f2.bf16 = bf;
+    f2.Wt = w.w2.w; f2.w_scale = w.w2.scale; f2.N = d; f2.K = 4 * d; f2.B = B; f2.M = M; f2.X = dw.hd; f2.ldx = 4 * d;
+    f2.bias = w.b2; f2.R = x; f2.Y = x; f2.ldy = d;
+    if (split) {  // x stays in two halves for the next kProLn consumer: the next layer's qkv, the logits GEMM, language_head
+      f2.Y = dw.xb; f2.ksplit = 2; f2.part = dw.xpart;
+    }
+    timed(tm, 7, [&] { launch_dec_gemm(f2, kProNone, kDecResid, st); });
+  }
+  if (!p.best) return;
+  // logits against the tied embedding + argmax records (whisper.cpp:379-399); only the last position's rows exist
+  // here, the reference computes and drops the others
+  const size_t off = size_t(p.np - 1) * B * d;
+  const TiledW& emb = bf ? tok_emb_tiled_bf_ : tok_emb_tiled;
+  DecGemmArgs lg;  // final LayerNorm (of x, or of the two halves a K-split fc2 left) + logits + argmax records
+  lg.bf16 = bf; lg.logits_blocks = p.logits_blocks;
+  lg.Wt = emb.w; lg.w_scale = emb.scale; lg.N = V; lg.K = d; lg.B = B;
+  lg.xin = (split ? dw.xb : x) + off; lg.xpart = split ? dw.xpart + off : nullptr; lg.ln_g = dec_ln_g; lg.ln_b = dec_ln_b;
+  lg.Y = p.Y; lg.ldy = p.ldy; lg.best = p.best;
+  timed(tm, 9, [&] { launch_dec_gemm(lg, kProLn, kDecLogits, st); });
+}
+
 void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int logits_steps_cap, int group, bool pipelined,
                             int stream_override) {
   const bool paired = group > 1;
@@ -1833,7 +2007,6 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
   auto dec_of = [&](int si) { return stream_override >= 0 ? stream_override : (si / group) % n_dec_streams_; };
   slot.dec = dec_of(slot_idx);
   slot.pair_leader = -1;
-  DecWorkspace& dw = dws_[slot.dec];
   hipStream_t const stream_ = dec_stream_at(slot.dec);  // everything below runs on this decoder stream
   HIPCHK(hipStreamWaitEvent(stream_, slot.enc_done, 0));
   for (int j = 1; j < group; ++j) HIPCHK(hipStreamWaitEvent(stream_, slots_[(slot_idx + j) % kSlots].enc_done, 0));
@@ -1841,7 +2014,7 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
   long long* const h_ids_ = slot.h_ids;
   int* const h_n_ = slot.h_n;
   const wtw::Dims& c = dims_;
-  const int d = c.n_text_state, T = c.n_audio_ctx, H = c.n_text_head, V = c.n_vocab;
+  const int d = c.n_text_state, V = c.n_vocab;
   // Language mode of the chain: 0 = the prompt names the language; 1 = language -1: position 0 goes through the layers
   // alone, language_head writes ids[b][1] on the device, and the rest of the prompt follows in the usual grouping;
   // 2 = detection alone (detect_language): that first pass over [sot] and the head, nothing else
@@ -1853,9 +2026,7 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
   }
   const std::vector<long long> prompt = lang_mode == 2 ? std::vector<long long>{vocab_.token_sot} : this->prompt();
   const int n_prompt = int(prompt.size()), stride = 32;
-  for (long long id : prompt) {
-    if (id < 0 || id >= V) throw Error(1, "prompt token id outside the model's vocabulary");
-  }
+  check_prompt_ids(prompt, 1);
   const int max_pos = lang_mode == 2 ? 1 : int(std::min<long>(std::max<long>(max_tokens, n_prompt), 31));
   const bool forced = !forced_ids.empty() && lang_mode != 2;
   if (forced && forced_ids.size() != size_t(batch) * stride) {
@@ -1871,45 +2042,12 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
     }
     h_n_[b] = n_prompt;
   }
-  int chunks = int(cross_chunks);  // 1, 2, 4 or 8 (wt_engine_set_option), 0 = by batch size
-  if (chunks == 0) {
-    chunks = 1;
-    while (chunks < 8 && batch * H * chunks < 192) chunks *= 2;
-  }
-  // key chunks of the absorbed form: clips x chunks ~ 256 blocks, a chunk a whole number of 32-key tiles
+  const int chunks = cross_chunks_for(batch);
   const bool absorbed = slot.absorbed;  // the form this slot's encoder pass prepared (the same for every slot of a graph set)
-  // (option abs_chunks; 0 = 256 / clips: one block per CU when the decoder has the chip; pipelined 128 / clips — fewer,
-  // longer blocks: a block costs ~9 us before its first tile, and the decoders share the CUs the encoder leaves)
-  // (bf16 storage mode: half the bytes per key row, so half as many blocks again: 122.5 k against 120.5 k on configs[3])
-  const int abs_blocks = pipelined ? (bf16 ? 64 : 128) : 256;
-  int n_abs = abs_chunks > 0 ? int(abs_chunks) : std::min(16, std::max(1, (abs_blocks + batch - 1) / batch));
-  n_abs = std::min(n_abs, (T + 31) / 32);
+  const int n_abs = abs_chunks_for(batch, pipelined ? (bf16 ? 64 : 128) : 256);
   int steps = 0;
-  // WT_DEC_KERNEL_TIMERS=1 (diagnostics, eager launches only): event pairs around every decoder launch
   static const bool dec_timers = getenv("WT_DEC_KERNEL_TIMERS") != nullptr;
-  std::vector<hipEvent_t>& dt_ev = slot.dt_events;
-  std::vector<int>& dt_cls = slot.dt_cls;
-  size_t dt_used = 0;
-  bool dt_on = false;
-#define DT(CLS, CALL)                                                         \
-  do {                                                                        \
-    if (dt_on) {                                                              \
-      while (dt_ev.size() < dt_used + 2) {                                    \
-        hipEvent_t e_;                                                        \
-        HIPCHK(hipEventCreate(&e_));                                          \
-        dt_ev.push_back(e_);                                                  \
-      }                                                                       \
-      HIPCHK(hipEventRecord(dt_ev[dt_used], stream_));                        \
-      CALL;                                                                   \
-      HIPCHK(hipEventRecord(dt_ev[dt_used + 1], stream_));                    \
-      dt_cls.push_back(CLS);                                                  \
-      dt_used += 2;                                                           \
-    } else {                                                                  \
-      CALL;                                                                   \
-    }                                                                         \
-  } while (0)
-  (void)dw;
-  auto enqueue_all = [&](int si) {
+  auto enqueue_all = [&](int si, DecTimers* tm) {
     Slot& slot = slots_[si];
     const Slot* const member[4] = {&slot, &slots_[(si + 1) % kSlots], &slots_[(si + 2) % kSlots], &slots_[(si + 3) % kSlots]};  // the group's batches
     DecWorkspace& dw = dws_[dec_of(si)];
@@ -1917,20 +2055,21 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
     long long* const h_ids_ = slot.h_ids;
     int* const h_n_ = slot.h_n;
     steps = 0;
-    HIPCHK(hipMemcpyAsync(dw.ids, h_ids_, size_t(batch) * stride * sizeof(long long),
-                          hipMemcpyHostToDevice, stream_));
+    HIPCHK(hipMemcpyAsync(dw.ids, h_ids_, size_t(batch) * stride * sizeof(long long), hipMemcpyHostToDevice, stream_));
     HIPCHK(hipMemcpyAsync(dw.n_ids, h_n_, size_t(batch) * sizeof(int), hipMemcpyHostToDevice, stream_));
     HIPCHK(hipMemsetAsync(dw.finished, 0, size_t(batch) * sizeof(int), stream_));
 
-    const bool bf = bf16 != 0;  // bf16 storage mode: bf16 weights and caches (element size 2 in the cache offsets)
-    const size_t kv_slab = size_t(batch) * T * d;  // one (layer, k|v) slab of the cross cache
-    const size_t self_slab = size_t(batch) * self_cap_ * d;
-    auto cache_at = [&](float* base, size_t elems) -> void* {
-      return bf ? static_cast<void*>(reinterpret_cast<unsigned short*>(base) + elems) : static_cast<void*>(base + elems);
-    };
-    float* const x = dw.xd;  // residual stream [rows][d], updated in place by the residual GEMMs
-    // fc2 (K = 4 d) runs over twice the blocks when its K splits evenly over 2 x 8 waves x 16
-    const bool split = fc2_ksplit == 2 && (4 * d) % 256 == 0;
+    DecPass p;  // what stays the same over the chain's passes
+    p.B = p.clips = batch; p.ids = dw.ids; p.ids_stride = stride; p.self_kv = dw.self_kv; p.self_cap = self_cap_;
+    p.absorbed = absorbed; p.n_abs = n_abs; p.chunks = chunks; p.e = slot.e_planes; p.cross_kv = slot.cross_kv;
+    if (paired) {
+      p.e_split = per;
+      p.e2 = member[1]->e_planes;
+      if (group > 2) p.e3 = member[2]->e_planes;
+      if (group > 3) p.e4 = member[3]->e_planes;
+    }
+    p.bf = bf16 != 0; p.split = fc2_split(); p.dw = &dw; p.timers = tm;
+    p.ldy = V; p.logits_blocks = pipelined ? 256 : 0;
     // Passes.  The prompt positions of every clip go through the layers TOGETHER when they fit one pass (rows =
     // positions x clips <= 128, at most 4 positions: causal self-attention inside the pass, one sweep of the
     // cross-KV cache for all of them); the reference feeds the same prefix to its graph at once, whisper.cpp:367-375.
@@ -1941,101 +2080,19 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
     for (int pos0 = 0, np = 1; pos0 < max_pos; pos0 += np) {
       np = pos0 < prompt_end ? std::min(np_max, prompt_end - pos0) : 1;
       if (lang_mode && pos0 == 0) np = 1;  // the language is read off position 0 before position 1 can be embedded
-      const int M = np * batch, last = pos0 + np - 1;
-      for (int l = 0; l < c.n_text_layer; ++l) {
-        const DecBlockWeights& w = bf ? dec_blocks_bf_[l] : dec_blocks_[l];
-        DecGemmArgs q;  // LN + fused q|k|v projection (+ token/positional embedding at layer 0)
-        q.bf16 = bf;
-        q.Wt = w.wqkv.w; q.w_scale = w.wqkv.scale; q.N = 3 * d; q.K = d; q.B = batch; q.M = M;
-        q.xin = x; q.ln_g = w.attn_ln_g; q.ln_b = w.attn_ln_b;
-        if (l > 0 && split) {  // the previous layer's fc2 left x in two halves: sum them, block 0 completes x
-          q.xin = dw.xb; q.xpart = dw.xpart; q.xout = x;
-        }
-        if (l == 0) {
-          q.ids = dw.ids; q.ids_stride = stride; q.pos = pos0; q.tok_emb = tok_emb; q.pos_emb = dec_pos;
-          q.n_vocab = V; q.xout = x;
-        }
-        q.bias = w.bqkv; q.Y = dw.qkvd; q.ldy = 3 * d;
-        DT(0, launch_dec_gemm(q, kProLn, kDecBias, stream_));
-        DT(1, launch_self_attention(dw.qkvd, cache_at(dw.self_kv, (size_t(l) * 2 + 0) * self_slab),
-                                    cache_at(dw.self_kv, (size_t(l) * 2 + 1) * self_slab), self_cap_, pos0, np, dw.attd,
-                                    batch, H, stream_, bf));
-        DecGemmArgs o;  // x += attn . Wo^T + bo
-        o.bf16 = bf;
-        o.Wt = w.wo.w; o.w_scale = w.wo.scale; o.N = d; o.K = d; o.B = batch; o.M = M; o.X = dw.attd; o.ldx = d;
-        o.bias = w.bo; o.R = x; o.Y = x; o.ldy = d;
-        DT(2, launch_dec_gemm(o, kProNone, kDecResid, stream_));
-
-        if (absorbed) {
-          // Cross attention against the encoder output itself (k_cross_absorbed.hip): LN + absorbed query projection
-          // q'_h = c0 Wk_h^T (Wq_h LN(x) + bq_h) for all heads in one GEMM, the matrix-core sweep of E per key chunk
-          // (positions in groups of 16 / heads query columns), the chunk combine with the heads' value projections,
-          // and the ordinary out-projection.
-          DecGemmArgs qa;
-          qa.Wt = w.wq_abs.w; qa.w_scale = w.wq_abs.scale; qa.N = H * d; qa.K = d; qa.B = batch; qa.M = M;
-          qa.bf16 = bf;
-          qa.xin = x; qa.ln_g = w.cross_ln_g; qa.ln_b = w.cross_ln_b; qa.bias = w.bq_abs; qa.Y = dw.qp; qa.ldy = H * d;
-          DT(3, launch_dec_gemm(qa, kProLn, kDecBias, stream_));
-          const int nq_max = cross_absorbed_max_nq(H);
-          for (int p0 = 0; p0 < np; p0 += nq_max) {
-            CrossAbsorbedArgs ca;
-            ca.qp = dw.qp; ca.e = slot.e_planes; ca.e_plane = long(ws_.batch) * T * d; ca.e_scale = sc_cross_kv_.a;
-            ca.bf16 = bf;
-            if (paired) {
-              ca.split = per;
-              ca.e2 = member[1]->e_planes;
-              if (group > 2) ca.e3 = member[2]->e_planes;
-              if (group > 3) ca.e4 = member[3]->e_planes;
-            }
-            ca.ws = dw.abs_ws; ca.batch = batch; ca.heads = H; ca.d_model = d; ca.T = T; ca.chunks = n_abs;
-            ca.nq = std::min(nq_max, np - p0); ca.p0 = p0;
-            DT(4, launch_cross_absorbed(ca, stream_));
-          }
-          DT(8, launch_cross_absorbed_combine(dw.abs_ws, w.cross_wv_t, w.cross_bv, dw.cabs, M, H, n_abs, d, stream_));
-          DecGemmArgs co;  // x += o . Wco^T + bco
-          co.bf16 = bf;
-          co.Wt = w.cross_wo.w; co.w_scale = w.cross_wo.scale; co.N = d; co.K = d; co.B = batch; co.M = M;
-          co.X = dw.cabs; co.ldx = d; co.bias = w.cross_bo; co.R = x; co.Y = x; co.ldy = d;
-          DT(5, launch_dec_gemm(co, kProNone, kDecResid, stream_));
-        } else {
-        CrossAttnArgs ca;  // LN + query projection + attention over the cached encoder keys, per key chunk
-        ca.x = x; ca.ln_g = w.cross_ln_g; ca.ln_b = w.cross_ln_b; ca.wq_t = w.cross_wq_t; ca.bq = w.cross_bq;
-        ca.kc = cache_at(slot.cross_kv, (size_t(l) * 2 + 0) * kv_slab); ca.vc = cache_at(slot.cross_kv, (size_t(l) * 2 + 1) * kv_slab);
-        ca.bf16 = bf;
-        ca.ws = dw.cross_ws; ca.batch = batch; ca.heads = H; ca.T = T; ca.chunks = chunks; ca.nq = np;
-        DT(4, launch_cross_attention(ca, stream_));
-        DecGemmArgs co;  // x += combine(chunks) . Wco^T + bco
-        co.bf16 = bf;
-        co.Wt = w.cross_wo.w; co.w_scale = w.cross_wo.scale; co.N = d; co.K = d; co.B = batch; co.M = M;
-        co.cross_ws = dw.cross_ws; co.heads = H; co.chunks = chunks;
-        co.bias = w.cross_bo; co.R = x; co.Y = x; co.ldy = d;
-        DT(5, launch_dec_gemm(co, kProCombine, kDecResid, stream_));
-        }
-
-        DecGemmArgs f1;  // LN + fc1 + GELU
-        f1.bf16 = bf;
-        f1.Wt = w.w1.w; f1.w_scale = w.w1.scale; f1.N = 4 * d; f1.K = d; f1.B = batch; f1.M = M;
-        f1.xin = x; f1.ln_g = w.mlp_ln_g; f1.ln_b = w.mlp_ln_b;
-        f1.bias = w.b1; f1.Y = dw.hd; f1.ldy = 4 * d;
-        DT(6, launch_dec_gemm(f1, kProLn, kDecBiasGelu, stream_));
-        DecGemmArgs f2;  // x += h . W2^T + b2
-        f2.bf16 = bf;
-        f2.Wt = w.w2.w; f2.w_scale = w.w2.scale; f2.N = d; f2.K = 4 * d; f2.B = batch; f2.M = M; f2.X = dw.hd; f2.ldx = 4 * d;
-        f2.bias = w.b2; f2.R = x; f2.Y = x; f2.ldy = d;
-        if (split) {
-          f2.Y = dw.xb; f2.ksplit = 2; f2.part = dw.xpart;
-        }
-        DT(7, launch_dec_gemm(f2, kProNone, kDecResid, stream_));
-      }
+      const int last = pos0 + np - 1;
+      const bool logits = last >= n_prompt - 1 && lang_mode != 2;  // then greedy argmax (whisper.cpp:379-399)
+      p.pos0 = pos0; p.np = np; p.best = logits ? dw.best : nullptr; p.Y = logits_host ? dw.logits : nullptr;
+      decoder_pass(p, stream_);
       if (lang_mode && pos0 == 0) {
         // position 0's residual rows -> language probabilities and ids[b][1]; no logits GEMM at this position
         LangWorkspace& lw = lw_[dec_of(si)];
         LanguageHeadArgs la;
-        la.x = split ? dw.xb : x; la.xpart = split ? dw.xpart : nullptr; la.ln_g = dec_ln_g; la.ln_b = dec_ln_b;
+        la.x = p.split ? dw.xb : dw.xd; la.xpart = p.split ? dw.xpart : nullptr; la.ln_g = dec_ln_g; la.ln_b = dec_ln_b;
         la.tok_emb = tok_emb; la.rows = batch; la.d = d; la.n_vocab = V; la.lang_lo = int(kLangLo); la.n_lang = n_lang;
         la.probs = lw.probs; la.lang = lw.lang; la.lang_prob = lw.prob;
         if (lang_mode == 1) la.ids = dw.ids, la.ids_stride = stride, la.id_pos = 1;
-        DT(10, launch_language_head(la, stream_));
+        timed(tm, 10, [&] { launch_language_head(la, stream_); });
         if (!pipelined) {  // a synchronous call reads them after decode_collect (pipelined callers read ids[b][1])
           HIPCHK(hipMemcpyAsync(h_lang_, lw.lang, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, stream_));
           HIPCHK(hipMemcpyAsync(h_lang_prob_, lw.prob, size_t(batch) * sizeof(float), hipMemcpyDeviceToHost, stream_));
@@ -2044,24 +2101,14 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
           }
         }
       }
-      if (last >= n_prompt - 1 && lang_mode != 2) {
-        // logits against the tied embedding + greedy argmax (whisper.cpp:379-399); only the
-        // last position's rows exist here, the reference computes and drops the others
-        const size_t off = size_t(np - 1) * batch * d;
-        DecGemmArgs lg;  // final LayerNorm (of x, or of the two halves a K-split fc2 left) + logits + argmax records
-        lg.bf16 = bf;
-        lg.logits_blocks = pipelined ? 256 : 0;
-        lg.Wt = (bf ? tok_emb_tiled_bf_ : tok_emb_tiled).w; lg.w_scale = (bf ? tok_emb_tiled_bf_ : tok_emb_tiled).scale; lg.N = V; lg.K = d; lg.B = batch;
-        lg.xin = (split ? dw.xb : x) + off; lg.xpart = split ? dw.xpart + off : nullptr; lg.ln_g = dec_ln_g; lg.ln_b = dec_ln_b;
-        lg.Y = logits_host ? dw.logits : nullptr; lg.ldy = V; lg.best = dw.best;
-        DT(9, launch_dec_gemm(lg, kProLn, kDecLogits, stream_));
+      if (logits) {
         if (logits_host && steps < logits_steps_cap) {
           HIPCHK(hipMemcpy2DAsync(logits_host + size_t(steps) * V, size_t(logits_steps_cap) * V * sizeof(float),
                                   dw.logits, size_t(V) * sizeof(float), size_t(V) * sizeof(float), batch,
                                   hipMemcpyDeviceToHost, stream_));
         }
-        DT(10, launch_select_token(dw.best, (V + 31) / 32, dw.ids, stride, last, dw.n_ids, dw.finished,
-                            vocab_.token_eot, int(stop_at_eot), batch, stream_, forced));
+        timed(tm, 10, [&] { launch_select_token(dw.best, (V + 31) / 32, dw.ids, stride, last, dw.n_ids, dw.finished,
+                                                vocab_.token_eot, int(stop_at_eot), batch, stream_, forced); });
         ++steps;
       }
     }
@@ -2096,10 +2143,9 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
   if (exec) {
     HIPCHK(hipGraphLaunch(exec, stream_));
   } else {
-    dt_on = dec_timers && !logits_host;
-    dt_cls.clear();
-    enqueue_all(slot_idx);
-    dt_on = false;
+    DecTimers timers{slot.dt_events, slot.dt_cls, stream_};
+    slot.dt_cls.clear();
+    enqueue_all(slot_idx, dec_timers && !logits_host ? &timers : nullptr);
     const int eager_steps = steps;
     // the eager work of THIS batch is queued: its completion event and step count are set before anything that can
     // fail, so that submit() / collect() stay consistent whatever happens to the captures below
@@ -2116,22 +2162,8 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
       std::map<std::vector<long long>, GraphEntry> fresh;
       try {
         for (int si = 0; si < kSlots; ++si) {
-          hipStream_t cs = dec_stream_at(dec_of(si));
-          hipGraph_t graph = nullptr;
-          hipGraphExec_t ge = nullptr;
-          HIPCHK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-          try {
-            enqueue_all(si);
-          } catch (...) {
-            (void)hipStreamEndCapture(cs, &graph);
-            if (graph) (void)hipGraphDestroy(graph);
-            throw;
-          }
-          HIPCHK(hipStreamEndCapture(cs, &graph));
-          const hipError_t ie = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
-          (void)hipGraphDestroy(graph);
-          if (ie != hipSuccess) throw Error(kErrDevice, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
-          fresh[key_of(si)] = GraphEntry{ge, steps};
+          hipGraphExec_t const ge = capture_graph(dec_stream_at(dec_of(si)), [&] { enqueue_all(si, nullptr); });
+          fresh[key_of(si)] = GraphEntry{ge, steps};  // (steps: as enqueue_all has just counted them)
         }
         for (auto& g : fresh) graphs_[g.first] = g.second;  // all slots or none
       } catch (const std::exception& e) {
@@ -2152,8 +2184,6 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
     sb.pair_leader = slot_idx, sb.steps = steps, sb.dec = slot.dec;
   }
 }
-
-#undef DT
 
 void Engine::debug_concurrency(const float* d_mel, int batch, int n_dec, int n_enc, float* dec_ms,
                                float* enc_ms) {
@@ -2318,12 +2348,10 @@ void Engine::decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids) 
   if (!slot.absorbed) throw Error(kErrUnsupported, "beam search: the encoder pass did not prepare the absorbed cross-attention");
   ensure_beam_workspace();
   const wtw::Dims& c = dims_;
-  const int d = c.n_text_state, T = c.n_audio_ctx, H = c.n_text_head, V = c.n_vocab, L = c.n_text_layer;
+  const int d = c.n_text_state, T = c.n_audio_ctx, V = c.n_vocab, L = c.n_text_layer;
   const std::vector<long long> prompt = this->prompt();
   const int n_prompt = int(prompt.size()), stride = 32;
-  for (long long id : prompt) {
-    if (id < 0 || id >= V) throw Error(1, "prompt token id outside the model's vocabulary");
-  }
+  check_prompt_ids(prompt, 1);
   const int max_pos = int(std::min<long>(std::max<long>(max_tokens, n_prompt), 31));
   const int n_steps = max_pos - n_prompt + 1;  // the positions at which greedy takes an argmax
   const int per_chain = kDecRowsMax / K;
@@ -2336,80 +2364,21 @@ void Engine::decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids) 
   }
   HIPCHK(hipStreamWaitEvent(st, slot.enc_done, 0));
   HIPCHK(hipEventRecord(slot.dec_begin, st));
-  const bool split = fc2_ksplit == 2 && (4 * d) % 256 == 0;
-  const int nq_max = cross_absorbed_max_nq(H);
-  float* const x = dw.xd;
 
   auto enqueue_chain = [&](int c0, int nc) {
     const int rows = K * nc;
-    int n_abs = abs_chunks > 0 ? int(abs_chunks) : std::min(16, std::max(1, (256 + nc - 1) / nc));
-    n_abs = std::min(n_abs, (T + 31) / 32);
     HIPCHK(hipMemcpyAsync(bw_.ids[0], bw_.h_prompt, size_t(nc) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(bw_.n_fin + c0, 0, size_t(nc) * sizeof(int), st));
     HIPCHK(hipMemsetAsync(bw_.done + c0, 0, size_t(nc) * sizeof(int), st));
+    DecPass p;
+    p.clips = nc; p.ids_stride = stride; p.self_cap = self_cap_; p.absorbed = true; p.n_abs = abs_chunks_for(nc, 256);
+    p.e = slot.e_planes + size_t(c0) * T * d; p.split = fc2_split(); p.dw = &dw; p.Y = bw_.logits; p.ldy = V;
     // one decoder pass: np positions from pos0 of `seqs` sequences (rows p * seqs + s, caches of seqs rows); the
-    // cross-attention sees the nc clips with np * seqs / nc query rows each (row = q * nc + clip)
+    // cross-attention sees the nc clips with np * seqs / nc query rows each (row = q * nc + clip).  logits: the last
+    // position's rows, written out for the top-k pass
     auto pass = [&](int pos0, int np, int seqs, const long long* idsb, float* kv, bool logits) {
-      const int M = np * seqs, nq_all = M / nc;
-      const size_t self_slab = size_t(seqs) * self_cap_ * d;
-      for (int l = 0; l < L; ++l) {
-        const DecBlockWeights& w = dec_blocks_[l];
-        DecGemmArgs q;  // LN + fused q|k|v projection (+ token/positional embedding at layer 0)
-        q.Wt = w.wqkv.w; q.w_scale = w.wqkv.scale; q.N = 3 * d; q.K = d; q.B = seqs; q.M = M;
-        q.xin = x; q.ln_g = w.attn_ln_g; q.ln_b = w.attn_ln_b;
-        if (l > 0 && split) {
-          q.xin = dw.xb; q.xpart = dw.xpart; q.xout = x;
-        }
-        if (l == 0) {
-          q.ids = idsb; q.ids_stride = stride; q.pos = pos0; q.tok_emb = tok_emb; q.pos_emb = dec_pos;
-          q.n_vocab = V; q.xout = x;
-        }
-        q.bias = w.bqkv; q.Y = dw.qkvd; q.ldy = 3 * d;
-        launch_dec_gemm(q, kProLn, kDecBias, st);
-        launch_self_attention(dw.qkvd, kv + (size_t(l) * 2 + 0) * self_slab, kv + (size_t(l) * 2 + 1) * self_slab, self_cap_,
-                              pos0, np, dw.attd, seqs, H, st);
-        DecGemmArgs o;  // x += attn . Wo^T + bo
-        o.Wt = w.wo.w; o.w_scale = w.wo.scale; o.N = d; o.K = d; o.B = seqs; o.M = M; o.X = dw.attd; o.ldx = d;
-        o.bias = w.bo; o.R = x; o.Y = x; o.ldy = d;
-        launch_dec_gemm(o, kProNone, kDecResid, st);
-        DecGemmArgs qa;  // LN + absorbed query projection
-        qa.Wt = w.wq_abs.w; qa.w_scale = w.wq_abs.scale; qa.N = H * d; qa.K = d; qa.B = seqs; qa.M = M;
-        qa.xin = x; qa.ln_g = w.cross_ln_g; qa.ln_b = w.cross_ln_b; qa.bias = w.bq_abs; qa.Y = dw.qp; qa.ldy = H * d;
-        launch_dec_gemm(qa, kProLn, kDecBias, st);
-        for (int p0 = 0; p0 < nq_all; p0 += nq_max) {
-          CrossAbsorbedArgs ca;
-          ca.qp = dw.qp; ca.e = slot.e_planes + size_t(c0) * T * d; ca.e_plane = long(ws_.batch) * T * d;
-          ca.e_scale = sc_cross_kv_.a;
-          ca.ws = dw.abs_ws; ca.batch = nc; ca.heads = H; ca.d_model = d; ca.T = T; ca.chunks = n_abs;
-          ca.nq = std::min(nq_max, nq_all - p0); ca.p0 = p0;
-          launch_cross_absorbed(ca, st);
-        }
-        launch_cross_absorbed_combine(dw.abs_ws, w.cross_wv_t, w.cross_bv, dw.cabs, M, H, n_abs, d, st);
-        DecGemmArgs co;  // x += o . Wco^T + bco
-        co.Wt = w.cross_wo.w; co.w_scale = w.cross_wo.scale; co.N = d; co.K = d; co.B = seqs; co.M = M;
-        co.X = dw.cabs; co.ldx = d; co.bias = w.cross_bo; co.R = x; co.Y = x; co.ldy = d;
-        launch_dec_gemm(co, kProNone, kDecResid, st);
-        DecGemmArgs f1;  // LN + fc1 + GELU
-        f1.Wt = w.w1.w; f1.w_scale = w.w1.scale; f1.N = 4 * d; f1.K = d; f1.B = seqs; f1.M = M;
-        f1.xin = x; f1.ln_g = w.mlp_ln_g; f1.ln_b = w.mlp_ln_b;
-        f1.bias = w.b1; f1.Y = dw.hd; f1.ldy = 4 * d;
-        launch_dec_gemm(f1, kProLn, kDecBiasGelu, st);
-        DecGemmArgs f2;  // x += h . W2^T + b2
-        f2.Wt = w.w2.w; f2.w_scale = w.w2.scale; f2.N = d; f2.K = 4 * d; f2.B = seqs; f2.M = M; f2.X = dw.hd; f2.ldx = 4 * d;
-        f2.bias = w.b2; f2.R = x; f2.Y = x; f2.ldy = d;
-        if (split) {
-          f2.Y = dw.xb; f2.ksplit = 2; f2.part = dw.xpart;
-        }
-        launch_dec_gemm(f2, kProNone, kDecResid, st);
-      }
-      if (logits) {  // the last position's rows: final LayerNorm + logits, written out for the top-k pass
-        const size_t off = size_t(np - 1) * seqs * d;
-        DecGemmArgs lg;
-        lg.Wt = tok_emb_tiled.w; lg.w_scale = tok_emb_tiled.scale; lg.N = V; lg.K = d; lg.B = seqs;
-        lg.xin = (split ? dw.xb : x) + off; lg.xpart = split ? dw.xpart + off : nullptr; lg.ln_g = dec_ln_g; lg.ln_b = dec_ln_b;
-        lg.Y = bw_.logits; lg.ldy = V; lg.best = bw_.best;
-        launch_dec_gemm(lg, kProLn, kDecLogits, st);
-      }
+      p.pos0 = pos0; p.np = np; p.B = seqs; p.ids = idsb; p.self_kv = kv; p.best = logits ? bw_.best : nullptr;
+      decoder_pass(p, st);
     };
     const int np_max = std::max(1, std::min(4, kDecRowsMax / nc));
     for (int pos0 = 0, np = 1; pos0 < n_prompt; pos0 += np) {
@@ -2455,22 +2424,8 @@ void Engine::decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids) 
     }
     enqueue_chain(c0, nc);  // eager the first time (the kernels' one-time set-up), then captured for the next calls
     if (use_graphs) {
-      hipGraph_t graph = nullptr;
-      hipGraphExec_t ge = nullptr;
       try {
-        HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        try {
-          enqueue_chain(c0, nc);
-        } catch (...) {
-          (void)hipStreamEndCapture(st, &graph);
-          if (graph) (void)hipGraphDestroy(graph);
-          throw;
-        }
-        HIPCHK(hipStreamEndCapture(st, &graph));
-        const hipError_t ie = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess) throw Error(kErrDevice, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
-        graphs_[key] = GraphEntry{ge, n_steps};
+        graphs_.emplace(key, GraphEntry{capture_graph(st, [&] { enqueue_chain(c0, nc); }), n_steps});
       } catch (const std::exception& e) {
         (void)hipGetLastError();
         use_graphs = 0;
@@ -2605,14 +2560,10 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   ensure_batch(batch);
   ensure_full_workspace(batch);  // (before any capture: nothing may be allocated inside one)
   Slot& slot = slots_[slot_idx];
-  const wtw::Dims& c = dims_;
-  const int d = c.n_text_state, T = c.n_audio_ctx, H = c.n_text_head, V = c.n_vocab, L = c.n_text_layer;
-  const int cap = full_cap(), stride = cap + 1;
+  const int V = dims_.n_vocab, cap = full_cap(), stride = cap + 1;
   const std::vector<long long> prompt = this->prompt();
   const int n_prompt = int(prompt.size());
-  for (long long id : prompt) {
-    if (id < 0 || id >= V) throw Error(kErrInvalidArg, "prompt token id outside the model's vocabulary");
-  }
+  check_prompt_ids(prompt, kErrInvalidArg);
   slot.dec = slot_idx % n_dec_streams_;
   slot.pair_leader = -1;
   DecWorkspace& dw = dws_[slot.dec];
@@ -2621,17 +2572,9 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     for (int i = 0; i < stride; ++i) fw_.h_ids[size_t(b) * stride + i] = i < n_prompt ? prompt[i] : 0;
     fw_.h_n[b] = n_prompt;
   }
-  int chunks = int(cross_chunks);  // as decode_enqueue chooses them for a synchronous call of this size
-  if (chunks == 0) {
-    chunks = 1;
-    while (chunks < 8 && batch * H * chunks < 192) chunks *= 2;
-  }
+  const int chunks = cross_chunks_for(batch);  // as decode_enqueue chooses them for a synchronous call of this size
   const bool absorbed = slot.absorbed;
-  int n_abs = abs_chunks > 0 ? int(abs_chunks) : std::min(16, std::max(1, (256 + batch - 1) / batch));
-  n_abs = std::min(n_abs, (T + 31) / 32);
-  const bool split = fc2_ksplit == 2 && (4 * d) % 256 == 0;
-  const size_t kv_slab = size_t(batch) * T * d, self_slab = size_t(batch) * cap * d;
-  float* const x = dw.xd;
+  const int n_abs = abs_chunks_for(batch, 256);
   const int np_max = std::max(1, std::min(4, kDecRowsMax / batch));
   const int prompt_end = std::min(n_prompt, P);
 
@@ -2644,89 +2587,23 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     launch_ts_state_init(fw_.ids, stride, nullptr, n_prompt, n_prompt, V, vocab_.token_beg, fw_.ts_state, batch, st);
   }
 
+  DecPass p;
+  p.B = p.clips = batch; p.ids = fw_.ids; p.ids_stride = stride; p.self_kv = fw_.kv; p.self_cap = cap;
+  p.absorbed = absorbed; p.n_abs = n_abs; p.chunks = chunks; p.e = slot.e_planes; p.cross_kv = slot.cross_kv;
+  p.split = fc2_split(); p.dw = &dw; p.ldy = V;
+  if (ts) p.Y = fw_.ts_logits, p.ldy = fw_.ts_ldl;  // the timestamp rules read the whole row
   // the passes whose first position lies in [lo, hi); returns the argmax steps among them
   auto enqueue_segment = [&](int lo, int hi) {
     int seg_steps = 0;
     for (int pos0 = 0, np = 1; pos0 < hi; pos0 += np) {
       np = pos0 < prompt_end ? std::min(np_max, prompt_end - pos0) : 1;
       if (pos0 < lo) continue;
-      const int M = np * batch, last = pos0 + np - 1;
-      for (int l = 0; l < L; ++l) {
-        const DecBlockWeights& w = dec_blocks_[l];
-        DecGemmArgs q;  // LN + fused q|k|v projection (+ token/positional embedding at layer 0)
-        q.Wt = w.wqkv.w; q.w_scale = w.wqkv.scale; q.N = 3 * d; q.K = d; q.B = batch; q.M = M;
-        q.xin = x; q.ln_g = w.attn_ln_g; q.ln_b = w.attn_ln_b;
-        if (l > 0 && split) {
-          q.xin = dw.xb; q.xpart = dw.xpart; q.xout = x;
-        }
-        if (l == 0) {
-          q.ids = fw_.ids; q.ids_stride = stride; q.pos = pos0; q.tok_emb = tok_emb; q.pos_emb = dec_pos;
-          q.n_vocab = V; q.xout = x;
-        }
-        q.bias = w.bqkv; q.Y = dw.qkvd; q.ldy = 3 * d;
-        launch_dec_gemm(q, kProLn, kDecBias, st);
-        float* const kc = fw_.kv + (size_t(l) * 2 + 0) * self_slab;
-        float* const vc = fw_.kv + (size_t(l) * 2 + 1) * self_slab;
-        if (pos0 + np <= 32) {
-          launch_self_attention(dw.qkvd, kc, vc, cap, pos0, np, dw.attd, batch, H, st);
-        } else {  // (np == 1: the prompt has at most 8 ids)
-          launch_self_attention_long(dw.qkvd, kc, vc, cap, pos0, dw.attd, batch, H, st);
-        }
-        DecGemmArgs o;  // x += attn . Wo^T + bo
-        o.Wt = w.wo.w; o.w_scale = w.wo.scale; o.N = d; o.K = d; o.B = batch; o.M = M; o.X = dw.attd; o.ldx = d;
-        o.bias = w.bo; o.R = x; o.Y = x; o.ldy = d;
-        launch_dec_gemm(o, kProNone, kDecResid, st);
-        if (absorbed) {
-          DecGemmArgs qa;  // LN + absorbed query projection
-          qa.Wt = w.wq_abs.w; qa.w_scale = w.wq_abs.scale; qa.N = H * d; qa.K = d; qa.B = batch; qa.M = M;
-          qa.xin = x; qa.ln_g = w.cross_ln_g; qa.ln_b = w.cross_ln_b; qa.bias = w.bq_abs; qa.Y = dw.qp; qa.ldy = H * d;
-          launch_dec_gemm(qa, kProLn, kDecBias, st);
-          const int nq_max = cross_absorbed_max_nq(H);
-          for (int p0 = 0; p0 < np; p0 += nq_max) {
-            CrossAbsorbedArgs ca;
-            ca.qp = dw.qp; ca.e = slot.e_planes; ca.e_plane = long(ws_.batch) * T * d; ca.e_scale = sc_cross_kv_.a;
-            ca.ws = dw.abs_ws; ca.batch = batch; ca.heads = H; ca.d_model = d; ca.T = T; ca.chunks = n_abs;
-            ca.nq = std::min(nq_max, np - p0); ca.p0 = p0;
-            launch_cross_absorbed(ca, st);
-          }
-          launch_cross_absorbed_combine(dw.abs_ws, w.cross_wv_t, w.cross_bv, dw.cabs, M, H, n_abs, d, st);
-          DecGemmArgs co;  // x += o . Wco^T + bco
-          co.Wt = w.cross_wo.w; co.w_scale = w.cross_wo.scale; co.N = d; co.K = d; co.B = batch; co.M = M;
-          co.X = dw.cabs; co.ldx = d; co.bias = w.cross_bo; co.R = x; co.Y = x; co.ldy = d;
-          launch_dec_gemm(co, kProNone, kDecResid, st);
-        } else {
-          CrossAttnArgs ca;  // LN + query projection + attention over the cached encoder keys, per key chunk
-          ca.x = x; ca.ln_g = w.cross_ln_g; ca.ln_b = w.cross_ln_b; ca.wq_t = w.cross_wq_t; ca.bq = w.cross_bq;
-          ca.kc = slot.cross_kv + (size_t(l) * 2 + 0) * kv_slab; ca.vc = slot.cross_kv + (size_t(l) * 2 + 1) * kv_slab;
-          ca.ws = dw.cross_ws; ca.batch = batch; ca.heads = H; ca.T = T; ca.chunks = chunks; ca.nq = np;
-          launch_cross_attention(ca, st);
-          DecGemmArgs co;  // x += combine(chunks) . Wco^T + bco
-          co.Wt = w.cross_wo.w; co.w_scale = w.cross_wo.scale; co.N = d; co.K = d; co.B = batch; co.M = M;
-          co.cross_ws = dw.cross_ws; co.heads = H; co.chunks = chunks;
-          co.bias = w.cross_bo; co.R = x; co.Y = x; co.ldy = d;
-          launch_dec_gemm(co, kProCombine, kDecResid, st);
-        }
-        DecGemmArgs f1;  // LN + fc1 + GELU
-        f1.Wt = w.w1.w; f1.w_scale = w.w1.scale; f1.N = 4 * d; f1.K = d; f1.B = batch; f1.M = M;
-        f1.xin = x; f1.ln_g = w.mlp_ln_g; f1.ln_b = w.mlp_ln_b;
-        f1.bias = w.b1; f1.Y = dw.hd; f1.ldy = 4 * d;
-        launch_dec_gemm(f1, kProLn, kDecBiasGelu, st);
-        DecGemmArgs f2;  // x += h . W2^T + b2
-        f2.Wt = w.w2.w; f2.w_scale = w.w2.scale; f2.N = d; f2.K = 4 * d; f2.B = batch; f2.M = M; f2.X = dw.hd; f2.ldx = 4 * d;
-        f2.bias = w.b2; f2.R = x; f2.Y = x; f2.ldy = d;
-        if (split) {
-          f2.Y = dw.xb; f2.ksplit = 2; f2.part = dw.xpart;
-        }
-        launch_dec_gemm(f2, kProNone, kDecResid, st);
-      }
-      if (last >= n_prompt - 1) {  // final LayerNorm + logits + argmax records of the last position's rows, then the token
-        const size_t off = size_t(np - 1) * batch * d;
-        DecGemmArgs lg;
-        lg.Wt = tok_emb_tiled.w; lg.w_scale = tok_emb_tiled.scale; lg.N = V; lg.K = d; lg.B = batch;
-        lg.xin = (split ? dw.xb : x) + off; lg.xpart = split ? dw.xpart + off : nullptr; lg.ln_g = dec_ln_g; lg.ln_b = dec_ln_b;
-        lg.Y = nullptr; lg.ldy = V; lg.best = dw.best;
-        if (ts) lg.Y = fw_.ts_logits, lg.ldy = fw_.ts_ldl;  // the timestamp rules read the whole row
-        launch_dec_gemm(lg, kProLn, kDecLogits, st);
+      const int last = pos0 + np - 1;
+      const bool logits = last >= n_prompt - 1;  // then the token of the last position's rows
+      p.pos0 = pos0; p.np = np; p.best = logits ? dw.best : nullptr;
+      p.self_long = pos0 + np > 32;  // (np == 1 there: the prompt has at most 8 ids)
+      decoder_pass(p, st);
+      if (logits) {
         if (ts) {
           TsSelectArgs t;
           t.logits = fw_.ts_logits; t.ldl = fw_.ts_ldl; t.V = V; t.batch = batch;
@@ -2759,22 +2636,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       const int seg_steps = enqueue_segment(lo, hi);  // eager the first time, then captured for the next calls
       steps += seg_steps;
       if (use_graphs) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t ge = nullptr;
         try {
-          HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-          try {
-            enqueue_segment(lo, hi);
-          } catch (...) {
-            (void)hipStreamEndCapture(st, &graph);
-            if (graph) (void)hipGraphDestroy(graph);
-            throw;
-          }
-          HIPCHK(hipStreamEndCapture(st, &graph));
-          const hipError_t ie = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
-          (void)hipGraphDestroy(graph);
-          if (ie != hipSuccess) throw Error(kErrDevice, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
-          graphs_[key] = GraphEntry{ge, seg_steps};
+          graphs_.emplace(key, GraphEntry{capture_graph(st, [&] { enqueue_segment(lo, hi); }), seg_steps});
         } catch (const std::exception& e) {
           (void)hipGetLastError();
           use_graphs = 0;

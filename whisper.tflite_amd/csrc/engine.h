@@ -21,6 +21,14 @@ struct TsState;
 
 struct BeamPart;  // kernels.h
 
+// WT_DEC_KERNEL_TIMERS diagnostics: the event pairs and launch classes of a slot's eager decoder launches
+struct DecTimers {
+  std::vector<hipEvent_t>& ev;
+  std::vector<int>& cls;
+  hipStream_t stream;
+  size_t used = 0;
+};
+
 struct Timings {
   float logmel_ms = 0, encoder_ms = 0, cross_kv_ms = 0, decoder_ms = 0, total_ms = 0;
   int batch = 0, decoder_steps = 0;
@@ -454,6 +462,32 @@ class Engine {
     long long* ids = nullptr;
     int *n_ids = nullptr, *finished = nullptr;
   } dws_[kDecStreams + 1];  // one per decoder stream, + one for a chain on the encoder stream (kEncAsDec)
+  // What a decode chain may vary in a decoder pass (decoder_pass: the one launch sequence of the decoder layers)
+  struct DecPass {
+    int pos0 = 0, np = 1;  // positions pos0 .. pos0 + np - 1
+    int B = 0;             // rows per position (sequences): M = np * B rows, row = p * B + sequence
+    const long long* ids = nullptr;  // id rows [B][ids_stride]
+    float* self_kv = nullptr;        // self-attention caches [layer][k|v][B][self_cap][d] (bf16 elements when bf)
+    int ids_stride = 32, self_cap = 32;
+    bool self_long = false;  // self_attention_long (np = 1, any position below self_cap) instead of self_attention
+    int clips = 0;           // clips the cross-attention sees: B, or fewer with M / clips query rows each (beam search)
+    bool absorbed = false;   // cross-attention form: absorbed (e .. e4, e_split, n_abs) or cached (cross_kv, chunks)
+    const unsigned short *e = nullptr, *e2 = nullptr, *e3 = nullptr, *e4 = nullptr;  // as in CrossAbsorbedArgs
+    int e_split = 0, n_abs = 1, chunks = 1;
+    float* cross_kv = nullptr;
+    bool bf = false, split = false;  // bf16 storage mode; fc2 K-split (x is handed on as xb + xpart)
+    const DecWorkspace* dw = nullptr;
+    // best set: the final LayerNorm + logits GEMM of the last position's rows follows the layers (Y null: records only)
+    unsigned long long* best = nullptr;
+    float* Y = nullptr;
+    int ldy = 0, logits_blocks = 0;
+    DecTimers* timers = nullptr;  // per-launch event pairs: greedy's eager launches under WT_DEC_KERNEL_TIMERS
+  };
+  void decoder_pass(const DecPass& p, hipStream_t st);
+  int cross_chunks_for(int batch) const;              // key chunks of the cached cross-attention (option cross_chunks)
+  int abs_chunks_for(int clips, int blocks) const;    // key chunks of the absorbed one for ~`blocks` blocks (option abs_chunks)
+  bool fc2_split() const { return fc2_ksplit == 2 && (4 * dims_.n_text_state) % 256 == 0; }
+  void check_prompt_ids(const std::vector<long long>& prompt, int code) const;  // throws Error(code, ..) outside the vocabulary
   // language_head outputs, one set per decoder workspace (128 rows whatever the batch), and the pinned copies a
   // synchronous call reads; allocated by the first detecting call
   struct LangWorkspace {
