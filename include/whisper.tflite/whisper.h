@@ -104,6 +104,14 @@ struct Engine {  // reference whisper.h:159-163
   virtual ~Engine() = default;
 };
 
+// An addition: the confidence of one 30 s window of the last transcribe() with the options "scores" = 1 and
+// "max_positions" set (wt_capi.h, wt_last_scores).
+struct ClipScore {
+  float sum_logprob = 0.0f, avg_logprob = 0.0f, no_speech_prob = 0.0f;
+  int n_generated = 0;
+  bool skipped = false;  // option "skip_silence" blanked the window
+};
+
 // reference whisper.h:165-179, whisper.cpp:667-738: one .tflite graph with HuggingFace generate() inside.
 // Here the same HIP encoder / decoder kernels run from "<prefix>.wtw" with the prompt that graph forces
 // ([sot, notimestamps] for an English-only model, [sot, <|en|>, transcribe, notimestamps] for a
@@ -118,6 +126,7 @@ struct Monolith : public Engine {
   std::string transcribe(const char* waveFile) final;
   // an addition: as EncDec::detect_language
   std::pair<int, float> detect_language(std::vector<float>& samples);
+  std::vector<ClipScore> scores() const;  // an addition: as EncDec::scores
   wt_engine* handle() const { return handle_; }
 
  private:
@@ -147,8 +156,11 @@ struct EncDec : public Engine {
     int clip = 0, t0_ms = 0, t1_ms = 0;
     bool open = false;  // the text ran to the end of the window without a closing timestamp
     std::string text;
+    float avg_logprob = 0.0f;  // mean token log-probability of the text ids (option "scores"; 0 without it)
   };
   std::vector<Segment> segments() const;
+  // one per window of the last transcribe(); empty when that call ran without the option "scores"
+  std::vector<ClipScore> scores() const;
   // for the batch entry points and options of wt_capi.h: wt_engine_set_option(handle(), "beam_size", 5) makes both
   // transcribe() overloads decode with beam search
   wt_engine* handle() const { return handle_; }

@@ -84,6 +84,11 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * "timestamps" (0 = default: off; 1 = full-length greedy decoding behind Whisper's timestamp rules, see wt_last_segments
  * below and DESIGN.md section 14; WT_ERR_UNSUPPORTED when the model's vocabulary has no timestamp ids), "max_initial_timestamp"
  * (latest first timestamp in ticks of 20 ms, default 50 = 1.0 s, -1 = no limit, at most 1500),
+ * "scores" (0 = default: off; 1 = full-length greedy decoding also returns token log-probabilities, avg_logprob and
+ * no_speech_prob, see wt_last_scores below and DESIGN.md section 15; WT_ERR_UNSUPPORTED when the model's vocabulary has
+ * no <|nospeech|> id), "skip_silence" (0 = default; 1 = a clip with no_speech_prob > "no_speech_threshold" / 1000
+ * (default 600) and not avg_logprob > "logprob_threshold" / 1000 (default -1000) yields empty text and no segments; needs
+ * "scores" = 1 at the call),
  * "stop_at_eot" (whisper.cpp:397-399, default 1), "verbose" (default 0),
  * "cross_chunks" (key chunks per (clip, head) in the decoder cross attention: 1, 2, 4, 8, or 0 = by batch size, the default).
  * Kernel selection (results stay within the fp32 error budget for every value): "gemm_variant"
@@ -250,6 +255,27 @@ typedef struct wt_segment {
 int wt_last_segments(const wt_engine* h, wt_segment* out, int cap);
 /* the text of segment `index` of that list: its ids decoded as wt_decode_text does with omit_special_tokens = 0 */
 int wt_last_segment_text(const wt_engine* h, int index, char* out, size_t cap, size_t* len);
+
+/* Decode confidence (option "scores" = 1 together with "max_positions", with or without "timestamps"; DESIGN.md section
+ * 15).  Formed on the device inside the decoder chain.  The log-probability of a generated id is its fp32 logit minus the
+ * float64 logsumexp of the logits of the ids that step chose from: the whole vocabulary, or with "timestamps" what the
+ * timestamp rules left.  sum_logprob sums it over the n_generated ids of the clip, the EOT that ended it included;
+ * avg_logprob = sum_logprob / n_generated; no_speech_prob is the softmax probability of <|nospeech|> (50361, multilingual
+ * 50362) at position 0, behind sot alone, over the whole vocabulary.  skipped = 1: option "skip_silence" blanked the clip
+ * in the text entry points and in wt_last_segments; the id-returning calls return its ids as decoded.  With the option
+ * set, a decode call is WT_ERR_UNSUPPORTED without "max_positions" and wherever "max_positions" refuses one; the engine
+ * stays usable after each. */
+typedef struct wt_clip_score { float sum_logprob, avg_logprob, no_speech_prob; int32_t n_generated, skipped; } wt_clip_score;
+/* every clip of the last synchronous decode with "scores" = 1 (after wt_transcribe_long_pcm: one per window);
+ * returns the clip count, or -WT_ERR_INVALID_ARG when that decode ran without scores (as wt_last_beam_scores) */
+int wt_last_scores(const wt_engine* h, wt_clip_score* out, int cap);
+/* log-probabilities aligned with the id rows: out[b][i] belongs to ids[b][i]; 0 for prompt ids and padding (at most
+ * cap_clips rows of `stride` floats written, columns past the decode's own row length zero).  Returns the clip count or
+ * -WT_ERR_INVALID_ARG as above. */
+int wt_last_token_logprobs(const wt_engine* h, float* out, int stride, int cap_clips);
+/* mean token log-probability over the text ids of each segment of wt_last_segments, same order (at most cap written).
+ * Returns the segment count, or -WT_ERR_INVALID_ARG unless the last synchronous decode ran with scores and timestamps. */
+int wt_last_segment_scores(const wt_engine* h, float* avg_logprob, int cap);
 
 /* Per-kernel-class device time of the encoder phase of the last batch call: HIP event pairs
  * recorded on the engine's stream around every launch of the class.  flops / bytes are the

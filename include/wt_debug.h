@@ -115,6 +115,16 @@ int wt_dbg_self_attention_long(wt_engine* h, int batch, int heads, int cap, int 
 int wt_dbg_timestamp_select(wt_engine* h, int B, int V, const float* logits, const int64_t* ids, int ids_stride,
                             const int32_t* n_ids, int sample_begin, int eot, int beg, int max_initial_timestamp,
                             int64_t* token, double* L, float* M);
+/* score_partial + score_finish (k_scores.hip, option "scores") alone: the log-probability of the id
+ * each row chose at one step.  logits [B][V]; row b of ids [B][ids_stride] holds n_ids[b] ids, the LAST of them the id
+ * the step chose (any id in [0, V)), the first sample_begin the prompt.  timestamps = 0: every id is allowed; 1: the set
+ * the timestamp rules leave behind the n_ids[b] - 1 earlier ids (state by ts_state_init, eot / beg / max_initial_timestamp
+ * as wt_dbg_timestamp_select), rule 5 decided as ts_select decides it.  live [B]: 1 = the clip was live at the step.
+ * sum [B] / count [B] in / out: the carried per-clip sum and count, advanced where live.  lp [B]; den [B] (optional) = the
+ * float64 logsumexp of the allowed set.  B <= 64, n_ids[b] in [max(sample_begin, 0) + 1, ids_stride]. */
+int wt_dbg_token_scores(wt_engine* h, int B, int V, const float* logits, const int64_t* ids, int ids_stride,
+                        const int32_t* n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
+                        const int32_t* live, float* lp, double* sum, int32_t* count, double* den);
 /* bf16 storage mode kernels (option "bf16"): operands are rounded to bf16 on the host, contracted by
  * gemm_bf16_planes / encoder_attention_planes<true>; bf16_out = 1 returns the kernel's bf16 output widened to fp32 */
 int wt_dbg_gemm_bf16(wt_engine* h, int M, int N, int K, const float* A, const float* W, const float* bias,

@@ -45,6 +45,7 @@ CAPI_SYMBOLS = [
     "wt_encdec_debug_batch",
     "wt_encdec_tokens_full_batch", "wt_encdec_tokens_full_batch_dev", "wt_transcribe_tokens_full_batch_dev",
     "wt_last_segments", "wt_last_segment_text", "wt_vocab_segments",
+    "wt_last_scores", "wt_last_token_logprobs", "wt_last_segment_scores",
     "wt_language_count", "wt_detect_language_batch", "wt_detect_language_batch_dev", "wt_detect_language_pcm", "wt_last_languages",
     "wt_last_timings", "wt_last_beam_scores", "wt_last_kernel_stats", "wt_decode_text", "wt_language_id", "wt_lang_code", "wt_wav_read_legacy",
     "wt_vocab_info", "wt_filters", "wt_write_synthetic_weights", "wt_write_synthetic_vocab",
@@ -59,7 +60,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_self_attention_long",
-    "wt_dbg_timestamp_select",
+    "wt_dbg_timestamp_select", "wt_dbg_token_scores",
 ]
 
 
@@ -211,6 +212,11 @@ def lib() -> ctypes.CDLL:
         L.wt_vocab_segments.argtypes = [c_void_p, ip64, c_int, c_int, c_void_p, c_int]
         L.wt_dbg_timestamp_select.argtypes = [c_void_p, c_int, c_int, fp, ip64, c_int, ip32, c_int, c_int, c_int, c_int,
                                               ip64, POINTER(ctypes.c_double), fp]
+        L.wt_last_scores.argtypes = [c_void_p, c_void_p, c_int]
+        L.wt_last_token_logprobs.argtypes = [c_void_p, fp, c_int, c_int]
+        L.wt_last_segment_scores.argtypes = [c_void_p, fp, c_int]
+        L.wt_dbg_token_scores.argtypes = [c_void_p, c_int, c_int, fp, ip64, c_int, ip32, c_int, c_int, c_int, c_int, c_int,
+                                          ip32, fp, POINTER(ctypes.c_double), ip32, POINTER(ctypes.c_double)]
         _lib = L
     return _lib
 
@@ -282,6 +288,11 @@ def wav_read_legacy(path: str) -> np.ndarray:
 # one time-stamped segment (wt_segment): the text ids row[id_begin : id_begin + id_count] of clip
 # `clip`, spoken from t0_ms to t1_ms; open = the text ran to the end of the row without a closing timestamp
 SEGMENT_DTYPE = np.dtype([(k, np.int32) for k in ("clip", "t0_ms", "t1_ms", "id_begin", "id_count", "open")])
+
+
+# one clip of a decode with option scores (wt_clip_score)
+SCORE_DTYPE = np.dtype([("sum_logprob", np.float32), ("avg_logprob", np.float32), ("no_speech_prob", np.float32),
+                        ("n_generated", np.int32), ("skipped", np.int32)])
 
 
 def _segments(call):
@@ -559,19 +570,50 @@ class Engine:
         return sums, lens
 
     # -- timestamp decoding (options timestamps + max_positions) ----
-    def last_segments(self, with_text: bool = False):
+    def last_segments(self, with_text: bool = False, with_scores: bool = False):
         """SEGMENT_DTYPE records of every clip of the last synchronous timestamp decode (after transcribe_long: clip = the
-        window's index, times in the file); with_text: (records, [bytes of each segment's text])."""
+        window's index, times in the file); with_text: (records, [bytes of each segment's text]); with_scores (option
+        scores): the mean token log-probability of each segment's text ids, float32, follows as the last element."""
         segs = _segments(lambda out, cap: lib().wt_last_segments(self._h, out, cap))
-        if not with_text:
-            return segs
-        texts = []
-        for i in range(segs.size):
-            buf = ctypes.create_string_buffer(1 << 16)
-            n = c_size_t(0)
-            self._check(lib().wt_last_segment_text(self._h, i, buf, len(buf), byref(n)))
-            texts.append(buf.raw[: n.value])
-        return segs, texts
+        out = [segs]
+        if with_text:
+            texts = []
+            for i in range(segs.size):
+                buf = ctypes.create_string_buffer(1 << 16)
+                n = c_size_t(0)
+                self._check(lib().wt_last_segment_text(self._h, i, buf, len(buf), byref(n)))
+                texts.append(buf.raw[: n.value])
+            out.append(texts)
+        if with_scores:
+            n = lib().wt_last_segment_scores(self._h, None, 0)
+            if n < 0:
+                raise WtError(-n, "no segment scores: the last synchronous decode ran without scores or without timestamps")
+            sc = np.zeros(n, np.float32)
+            lib().wt_last_segment_scores(self._h, _fp(sc), n)
+            out.append(sc)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    # -- decode confidence (options scores + max_positions, DESIGN.md section 15) ----
+    def last_scores(self) -> np.ndarray:
+        """SCORE_DTYPE records of every clip of the last synchronous decode with scores = 1 (after transcribe_long: one per
+        window): sum_logprob, avg_logprob, no_speech_prob, n_generated, skipped."""
+        n = lib().wt_last_scores(self._h, None, 0)
+        if n < 0:
+            raise WtError(-n, "no scores: the last synchronous decode ran without the option scores")
+        out = np.zeros(n, SCORE_DTYPE)
+        if n:
+            lib().wt_last_scores(self._h, out.ctypes.data_as(c_void_p), n)
+        return out
+
+    def last_token_logprobs(self, stride: int) -> np.ndarray:
+        """float32 [clips][stride] aligned with the id rows of that decode: 0 for prompt ids and padding."""
+        n = lib().wt_last_token_logprobs(self._h, None, 0, 0)
+        if n < 0:
+            raise WtError(-n, "no scores: the last synchronous decode ran without the option scores")
+        out = np.zeros((n, int(stride)), np.float32)
+        if out.size:
+            lib().wt_last_token_logprobs(self._h, _fp(out), int(stride), n)
+        return out
 
     # -- spoken-language detection (DESIGN.md section 12) ---------------------------
     def language_count(self) -> int:
@@ -871,6 +913,27 @@ class Engine:
                                                   int(sample_begin), int(eot), int(beg), int(max_initial_timestamp),
                                                   _ip64(tok), L.ctypes.data_as(POINTER(ctypes.c_double)), _fp(M)))
         return tok, L, M
+
+    def dbg_token_scores(self, logits, ids, n_ids, sample_begin, live=None, sums=None, counts=None, timestamps=False, eot=0,
+                         beg=1, max_initial_timestamp=50):
+        """The score kernels (k_scores.hip) alone, one step per row: logits [B][V]; row b of ids [B][stride] holds n_ids[b]
+        ids, the last of them the id the step chose; live [B] (default all), carried sums float64 [B] and counts int32 [B]
+        (default 0).  Returns (lp float32 [B], sums, counts, den float64 [B] = the logsumexp of the allowed set)."""
+        logits = _f32(logits)
+        ids = np.ascontiguousarray(ids, np.int64)
+        n_ids = np.ascontiguousarray(n_ids, np.int32)
+        B, V = logits.shape
+        live = np.ones(B, np.int32) if live is None else np.ascontiguousarray(live, np.int32)
+        sums = np.zeros(B, np.float64) if sums is None else np.array(sums, np.float64)
+        counts = np.zeros(B, np.int32) if counts is None else np.array(counts, np.int32)
+        lp = np.zeros(B, np.float32)
+        den = np.zeros(B, np.float64)
+        dp = POINTER(ctypes.c_double)
+        self._check(lib().wt_dbg_token_scores(self._h, B, V, _fp(logits), _ip64(ids), ids.shape[1], _ip32(n_ids),
+                                              int(sample_begin), int(bool(timestamps)), int(eot), int(beg),
+                                              int(max_initial_timestamp), _ip32(live), _fp(lp), sums.ctypes.data_as(dp),
+                                              _ip32(counts), den.ctypes.data_as(dp)))
+        return lp, sums, counts, den
 
     def dbg_self_attention_long(self, qkv, kcache, vcache, pos):
         """self_attention_long: one new position against caches [B][cap][d] (cap <= 448); returns (out [B][d], kcache,

@@ -30,13 +30,16 @@ void usage(const char* argv0) {
             << "  --max-positions N  full-length greedy decoding over N positions, 32 .. n_text_ctx (default: the\n"
             << "                  reference's 31 positions)\n"
             << "  --timestamps    with --max-positions: decode with timestamps and print one line per segment,\n"
-            << "                  [mm:ss.mmm --> mm:ss.mmm] text\n";
+            << "                  [mm:ss.mmm --> mm:ss.mmm] text\n"
+            << "  --scores        with --max-positions: print avg_logprob and no_speech_prob of every 30 s window (with\n"
+            << "                  --timestamps also each segment's mean log-probability on its line)\n"
+            << "  --skip-silence  with --scores: windows Whisper's no-speech rule calls silent yield no text\n";
 }
 }  // namespace
 
 int main(int argc, char* argv[]) {
   std::string model_prefix, vocab, input, lang, beam, max_positions;
-  bool long_audio = false, english = false, timestamps = false;
+  bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], v;
     if (a == "-h" || a == "--help") {
@@ -53,6 +56,14 @@ int main(int argc, char* argv[]) {
     }
     if (a == "--timestamps") {
       timestamps = true;
+      continue;
+    }
+    if (a == "--scores") {
+      scores = true;
+      continue;
+    }
+    if (a == "--skip-silence") {
+      skip_silence = true;
       continue;
     }
     const size_t eq = a.find('=');
@@ -131,6 +142,26 @@ int main(int argc, char* argv[]) {
       return 105;
     }
   }
+  if (scores) {
+    if (max_positions.empty()) {
+      std::cerr << "--scores requires --max-positions\n";
+      return 105;
+    }
+    if (wt_engine_set_option(encdec.handle(), "scores", 1) != WT_OK) {
+      std::cerr << "--scores: " << wt_last_error(encdec.handle()) << "\n";
+      return 105;
+    }
+  }
+  if (skip_silence) {
+    if (!scores) {
+      std::cerr << "--skip-silence requires --scores\n";
+      return 105;
+    }
+    if (wt_engine_set_option(encdec.handle(), "skip_silence", 1) != WT_OK) {
+      std::cerr << "--skip-silence: " << wt_last_error(encdec.handle()) << "\n";
+      return 105;
+    }
+  }
   std::string text;
   if (long_audio) {
     std::vector<float> pcm = wav_read_legacy(input.c_str());
@@ -158,6 +189,13 @@ int main(int argc, char* argv[]) {
       for (int i = 0; i < n; ++i) std::cout << "language: " << lang_code(size_t(l[i])) << " (p=" << p[i] << ")\n";
     }
   }
+  if (scores) {  // one line per window
+    int w = 0;
+    for (const ClipScore& c : encdec.scores()) {
+      std::cout << "window " << w++ << ": avg_logprob=" << c.avg_logprob << " no_speech_prob=" << c.no_speech_prob
+                << (c.skipped ? " (skipped)" : "") << "\n";
+    }
+  }
   if (timestamps) {
     auto stamp = [](int ms) {
       char b[32];
@@ -165,7 +203,9 @@ int main(int argc, char* argv[]) {
       return std::string(b);
     };
     for (const EncDec::Segment& s : encdec.segments()) {
-      std::cout << "[" << stamp(s.t0_ms) << " --> " << stamp(s.t1_ms) << "] " << s.text << "\n";
+      std::cout << "[" << stamp(s.t0_ms) << " --> " << stamp(s.t1_ms) << "] " << s.text;
+      if (scores) std::cout << " (avg_logprob=" << s.avg_logprob << ")";
+      std::cout << "\n";
     }
     return 0;
   }

@@ -218,6 +218,22 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
       return fail(h, WT_ERR_UNSUPPORTED, "timestamps: the model's vocabulary has no timestamp ids (n_vocab <= token_beg + 1)");
     }
     e.timestamps = value;
+  } else if (k == "scores") {
+    // decode confidence: token log-probabilities, avg_logprob and no_speech_prob of a full-length decode
+    if (value != 0 && value != 1) return fail(h, WT_ERR_INVALID_ARG, "scores must be 0 or 1");
+    if (value == 1 && !e.has_no_speech_token()) {
+      return fail(h, WT_ERR_UNSUPPORTED, "scores: the model's vocabulary has no <|nospeech|> id (token_solm >= n_vocab)");
+    }
+    e.scores = value;
+  } else if (k == "skip_silence") {
+    if (value != 0 && value != 1) return fail(h, WT_ERR_INVALID_ARG, "skip_silence must be 0 or 1");
+    e.skip_silence = value;
+  } else if (k == "no_speech_threshold") {
+    if (value < 0 || value > 1000) return fail(h, WT_ERR_INVALID_ARG, "no_speech_threshold must be in [0, 1000] (thousandths)");
+    e.no_speech_threshold = value;
+  } else if (k == "logprob_threshold") {
+    if (value > 0 || value < -1000000) return fail(h, WT_ERR_INVALID_ARG, "logprob_threshold must be in [-1000000, 0] (thousandths)");
+    e.logprob_threshold = value;
   } else if (k == "max_initial_timestamp") {
     if (value < -1 || value > 1500) return fail(h, WT_ERR_INVALID_ARG, "max_initial_timestamp must be in [-1, 1500] (ticks of 20 ms, -1 = no limit)");
     e.max_initial_timestamp = value;
@@ -300,6 +316,10 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "max_positions") *value = e.max_positions;
   else if (k == "timestamps") *value = e.timestamps;
   else if (k == "max_initial_timestamp") *value = e.max_initial_timestamp;
+  else if (k == "scores") *value = e.scores;
+  else if (k == "skip_silence") *value = e.skip_silence;
+  else if (k == "no_speech_threshold") *value = e.no_speech_threshold;
+  else if (k == "logprob_threshold") *value = e.logprob_threshold;
   else if (k == "stop_at_eot") *value = e.stop_at_eot;
   else if (k == "verbose") *value = e.verbose;
   else if (k == "cross_chunks") *value = e.cross_chunks;
@@ -590,6 +610,36 @@ int wt_last_segment_text(const wt_engine* h, int index, char* out, size_t cap, s
   return copy_text(e.last_segment_text[size_t(index)], out, cap, len);
 }
 
+int wt_last_scores(const wt_engine* h, wt_clip_score* out, int cap) {
+  static_assert(sizeof(wt_clip_score) == sizeof(wt::ClipScore), "wt_clip_score mirrors wt::ClipScore");
+  if (!h || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_scores_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last_scores.size());
+  for (int i = 0; i < n && i < cap; ++i) std::memcpy(&out[i], &e.last_scores[size_t(i)], sizeof(wt_clip_score));
+  return n;
+}
+
+int wt_last_token_logprobs(const wt_engine* h, float* out, int stride, int cap_clips) {
+  if (!h || cap_clips < 0 || stride < 0 || (cap_clips > 0 && stride > 0 && !out)) return -WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_scores_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last_scores.size()), own = e.last_lp_stride;
+  for (int b = 0; b < n && b < cap_clips; ++b) {
+    for (int i = 0; i < stride; ++i) out[size_t(b) * stride + i] = i < own ? e.last_token_logprob[size_t(b) * own + i] : 0.0f;
+  }
+  return n;
+}
+
+int wt_last_segment_scores(const wt_engine* h, float* avg_logprob, int cap) {
+  if (!h || cap < 0 || (cap > 0 && !avg_logprob)) return -WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_scores_valid || !e.last_segments_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last_segment_score.size());
+  for (int i = 0; i < n && i < cap; ++i) avg_logprob[i] = e.last_segment_score[size_t(i)];
+  return n;
+}
+
 // ------------------------------------------------- language detection ---
 
 int wt_language_count(const wt_engine* h) {
@@ -701,6 +751,8 @@ int wt_transcribe_pcm(wt_engine* h, const float* pcm, size_t n_samples, char* ou
     bool missing = false;
     // omit_special_tokens = false, as EncDec::transcribe passes (whisper.cpp:766-767)
     text = wt::decode_tokens(e.vocab(), ids.data(), n, false, &missing);
+    // option skip_silence: a silent window (only a call that itself ran with scores has them)
+    if (full && e.scores && e.last_scores_valid && !e.last_scores.empty() && e.last_scores[0].skipped) text.clear();
     if (missing && e.verbose) std::fprintf(stderr, "[wt] token id without a vocab entry skipped\n");
   });
   if (rc != WT_OK) {
@@ -725,6 +777,8 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
     std::vector<float> lang_probs;
     std::vector<wt::Segment> segments;  // option timestamps: every window's, clip = window index, times in the file
     std::vector<std::string> segment_text;
+    std::vector<wt::ClipScore> scores;  // option scores: every window's
+    std::vector<float> token_logprob, segment_score;
     for (size_t w0 = 0; w0 < n_win; w0 += 32) {
       const int B = int(std::min<size_t>(32, n_win - w0));
       std::vector<float> clips(size_t(B) * win, 0.0f);
@@ -760,12 +814,20 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
         }
         segment_text.insert(segment_text.end(), e.last_segment_text.begin(), e.last_segment_text.end());
       }
+      const bool scored = full && e.scores && e.last_scores_valid && e.last_scores.size() == size_t(B);  // THIS batch ran with scores
+      if (scored) {
+        scores.insert(scores.end(), e.last_scores.begin(), e.last_scores.end());
+        token_logprob.insert(token_logprob.end(), e.last_token_logprob.begin(), e.last_token_logprob.end());
+        segment_score.insert(segment_score.end(), e.last_segment_score.begin(), e.last_segment_score.end());
+      }
       for (int b = 0; b < B; ++b) {
         if (w0 + b) text += '\n';
+        if (scored && e.last_scores[size_t(b)].skipped) continue;  // option skip_silence: an empty line
         bool missing = false;
         text += wt::decode_tokens(e.vocab(), &ids[size_t(b) * row], n[b], false, &missing);
       }
     }
+    if (e.last_scores_valid) e.last_scores = scores, e.last_token_logprob = token_logprob, e.last_segment_score = segment_score;
     if (e.last_lang_valid) e.last_lang = langs, e.last_lang_prob = lang_probs;
     if (e.last_segments_valid) e.last_segments = segments, e.last_segment_text = segment_text;
   });
@@ -2025,6 +2087,62 @@ int wt_dbg_timestamp_select(wt_engine* h, int B, int V, const float* logits, con
     for (int b = 0; b < B; ++b) token[b] = rows[size_t(b) * stride + n_ids[b]];
     if (L) dL.to_host(L);
     if (M) dM.to_host(M);
+  });
+}
+
+int wt_dbg_token_scores(wt_engine* h, int B, int V, const float* logits, const int64_t* ids, int ids_stride,
+                        const int32_t* n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
+                        const int32_t* live, float* lp, double* sum, int32_t* count, double* den) {
+  if (!h || !logits || !ids || !n_ids || !live || !lp || !sum || !count || B < 1 || B > 64 || V < 2 || ids_stride < 1 ||
+      sample_begin < 0) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const int ldl = (V + 3) & ~3;
+    for (int b = 0; b < B; ++b) {
+      if (n_ids[b] < sample_begin + 1 || n_ids[b] > ids_stride) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_token_scores: n_ids outside [sample_begin + 1, ids_stride]");
+    }
+    std::vector<float> padded(size_t(B) * ldl, 0.0f);
+    for (int b = 0; b < B; ++b) std::memcpy(&padded[size_t(b) * ldl], logits + size_t(b) * V, size_t(V) * sizeof(float));
+    // device rows are the caller's behind one more leading column, so that the chosen id (the last of the row) sits at
+    // pos + 1 with pos = n_ids[b] - 1 >= 0 even when it is the only id
+    const int stride = ids_stride + 1, sb = sample_begin + 1;
+    std::vector<long long> rows(size_t(B) * stride, 0);
+    std::vector<int> n_before(B), n_after(B);
+    for (int b = 0; b < B; ++b) {
+      for (int i = 0; i < n_ids[b]; ++i) rows[size_t(b) * stride + 1 + i] = ids[size_t(b) * ids_stride + i];
+      n_before[b] = n_ids[b];                  // the device row's ids before the chosen one
+      n_after[b] = live[b] ? n_ids[b] + 1 : 0;  // what the selection kernel leaves where the clip was live: pos + 2
+    }
+    DevArr<float> dlog(padded.size(), padded.data()), dlp(size_t(B) * stride);
+    DevArr<long long> dids(rows.size(), rows.data());
+    DevArr<int> dn0(B, n_before.data()), dn1(B, n_after.data()), dcount(B, count);
+    DevArr<double> dsum(B, sum), dden(B);
+    DevArr<wt::ScorePart> dpart(size_t(B) * wt::ts_chunks(V));
+    DevArr<wt::TsState> dstate(B);
+    hipStream_t st = h->impl->stream();
+    hipchk(hipMemsetAsync(dlp.p, 0, size_t(B) * stride * sizeof(float), st), "memset");
+    if (timestamps) wt::launch_ts_state_init(dids.p, stride, dn0.p, 0, sb, V, beg, dstate.p, B, st);
+    for (int b0 = 0, b1 = 0; b0 < B; b0 = b1 + 1) {  // runs of consecutive rows with equal n_ids: one step count per launch
+      b1 = b0;
+      while (b1 + 1 < B && n_ids[b1 + 1] == n_ids[b0]) ++b1;
+      wt::ScoreArgs a;
+      a.logits = dlog.p + size_t(b0) * ldl; a.ldl = ldl; a.V = V; a.batch = b1 - b0 + 1;
+      a.state = timestamps ? dstate.p + b0 : nullptr; a.eot = eot; a.beg = beg; a.max_initial = max_initial_timestamp;
+      a.n_gen = n_ids[b0] - 1 - sample_begin; a.part = dpart.p + size_t(b0) * wt::ts_chunks(V);
+      a.ids = dids.p + size_t(b0) * stride; a.ids_stride = stride; a.pos = n_ids[b0] - 1; a.n_ids = dn1.p + b0;
+      a.token_logprob = dlp.p + size_t(b0) * stride; a.lp_stride = stride; a.sum = dsum.p + b0; a.count = dcount.p + b0;
+      a.dbg_den = dden.p + b0;
+      wt::launch_score_partial(a, st);
+      wt::launch_score_finish(a, st);
+    }
+    h->impl->sync();
+    std::vector<float> hlp(size_t(B) * stride);
+    dlp.to_host(hlp.data());
+    for (int b = 0; b < B; ++b) lp[b] = hlp[size_t(b) * stride + n_ids[b]];
+    dsum.to_host(sum);
+    dcount.to_host(count);
+    if (den) dden.to_host(den);
   });
 }
 

@@ -866,7 +866,9 @@ void Engine::release() noexcept {
   for (void* p : {static_cast<void*>(bw_.h_prompt), static_cast<void*>(bw_.h_sum), static_cast<void*>(bw_.h_len)})
     if (p) (void)hipHostFree(p);
   bw_ = BeamWorkspace();  // (its device buffers are in allocations_)
-  for (void* p : {static_cast<void*>(fw_.h_ids), static_cast<void*>(fw_.h_n), static_cast<void*>(fw_.h_fin)})
+  for (void* p : {static_cast<void*>(fw_.h_ids), static_cast<void*>(fw_.h_n), static_cast<void*>(fw_.h_fin),
+                  static_cast<void*>(fw_.h_lp), static_cast<void*>(fw_.h_nosp), static_cast<void*>(fw_.h_sum),
+                  static_cast<void*>(fw_.h_count)})
     if (p) (void)hipHostFree(p);
   fw_ = FullWorkspace();
   for (void* p : {static_cast<void*>(h_lang_probs_), static_cast<void*>(h_lang_prob_), static_cast<void*>(h_lang_)})
@@ -1629,6 +1631,7 @@ void Engine::decode(int batch, int64_t* ids, int32_t* n_ids, float* logits_host,
   check_beam_call(logits_host != nullptr);
   last_lang_valid = false;
   last_segments_valid = false;
+  clear_last_scores();
   if (beam_size > 1) {
     decode_beam(batch, last_enc_slot_, ids, n_ids);
     return;
@@ -1766,6 +1769,7 @@ void Engine::submit(const float* d_mel, int batch) {
   if (beam_size > 1) throw Error(kErrUnsupported, "beam search runs on the synchronous entry points only, not in the pipeline");
   check_language_call();
   last_lang_valid = false;
+  clear_last_scores();  // (the getters report the last decode, and this one has no scores)
   if (int(inflight_.size()) >= kSlots) throw Error(1, "pipeline is full (24 batches in flight): collect() first");
   if (batch > 64) throw Error(1, "decoder batches are limited to 64 clips per call");
   select_stream(true);
@@ -1780,6 +1784,7 @@ void Engine::submit_pcm(const float* d_pcm, int batch) {
   if (beam_size > 1) throw Error(kErrUnsupported, "beam search runs on the synchronous entry points only, not in the pipeline");
   check_language_call();
   last_lang_valid = false;
+  clear_last_scores();  // (the getters report the last decode, and this one has no scores)
   if (int(inflight_.size()) >= kSlots) throw Error(1, "pipeline is full (24 batches in flight): collect() first");
   if (batch > 64) throw Error(1, "decoder batches are limited to 64 clips per call");
   select_stream(true);
@@ -2447,12 +2452,25 @@ void Engine::decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids) 
 
 // ------------------------------------------------ full-length decoding ---
 
+void Engine::clear_last_scores() {
+  last_scores_valid = false;
+  last_scores.clear();
+  last_token_logprob.clear();
+  last_segment_score.clear();
+  last_lp_stride = 0;
+}
+
 // option timestamps outside full-length decoding: every decode call is refused (with max_positions set, the refusals
 // of check_full_call and of the other entry points apply as they are)
+// (options scores and skip_silence live in the same scope and are refused here with it)
 void Engine::check_timestamp_call() const {
   if (timestamps && max_positions <= 0) {
     throw Error(kErrUnsupported, "timestamps: full-length greedy decoding only, set the option max_positions (32 .. n_text_ctx)");
   }
+  if (scores && max_positions <= 0) {
+    throw Error(kErrUnsupported, "scores: full-length greedy decoding only, set the option max_positions (32 .. n_text_ctx)");
+  }
+  if (skip_silence && !scores) throw Error(kErrUnsupported, "skip_silence: needs the option scores = 1");
 }
 
 void Engine::check_full_args(int batch, int ids_stride) const {
@@ -2471,6 +2489,7 @@ void Engine::check_full_call() const {
   if (language < 0) no("not with automatic language detection (language = -1)");
   if (!forced_ids.empty()) no("not with forced ids");
   if (timestamps && !has_timestamp_tokens()) no("timestamps: the model's vocabulary has no timestamp ids");
+  if (scores && !has_no_speech_token()) no("scores: the model's vocabulary has no <|nospeech|> id");
 }
 
 // A full-length call is synchronous and finds the engine idle, so it may choose its pipeline slot: always slot 0, and
@@ -2525,12 +2544,30 @@ void Engine::ensure_full_workspace(int batch) {
     fw_.kv = static_cast<float*>(alloc(size_t(c.n_text_layer) * 2 * size_t(batch) * cap * d * sizeof(float)));
     fw_.kv_clips = batch;
   }
-  if (timestamps && !fw_.ts_state) {  // (allocated last of the three)
+  if ((timestamps || scores) && !fw_.ts_logits) {  // the logits of a step: the timestamp rules and the scores read whole rows
     const size_t ldl = (size_t(c.n_vocab) + 3) & ~size_t(3);
-    fw_.ts_logits = static_cast<float*>(alloc(C * ldl * sizeof(float)));
     fw_.ts_ldl = int(ldl);
+    fw_.ts_logits = static_cast<float*>(alloc(C * ldl * sizeof(float)));
+  }
+  if (timestamps && !fw_.ts_state) {  // (allocated last of the two)
     fw_.ts_part = static_cast<TsPart*>(alloc(C * size_t(ts_chunks(c.n_vocab)) * sizeof(TsPart)));
     fw_.ts_state = static_cast<TsState*>(alloc(C * sizeof(TsState)));
+  }
+  if (scores) {  // (every buffer is its own sentinel: a failed allocation leaves the earlier ones in place for the next call)
+    auto pinned = [&](size_t bytes) -> void* {
+      void* q = nullptr;
+      HIPCHK(hipHostMalloc(&q, bytes, 0));
+      return q;
+    };
+    if (!fw_.sc_part) fw_.sc_part = static_cast<ScorePart*>(alloc(C * size_t(ts_chunks(c.n_vocab)) * sizeof(ScorePart)));
+    if (!fw_.sc_lp) fw_.sc_lp = static_cast<float*>(alloc(C * (cap + 1) * sizeof(float)));
+    if (!fw_.sc_nosp) fw_.sc_nosp = static_cast<float*>(alloc(C * sizeof(float)));
+    if (!fw_.sc_sum) fw_.sc_sum = static_cast<double*>(alloc(C * sizeof(double)));
+    if (!fw_.sc_count) fw_.sc_count = static_cast<int*>(alloc(C * sizeof(int)));
+    if (!fw_.h_lp) fw_.h_lp = static_cast<float*>(pinned(C * (cap + 1) * sizeof(float)));
+    if (!fw_.h_nosp) fw_.h_nosp = static_cast<float*>(pinned(C * sizeof(float)));
+    if (!fw_.h_sum) fw_.h_sum = static_cast<double*>(pinned(C * sizeof(double)));
+    if (!fw_.h_count) fw_.h_count = static_cast<int*>(pinned(C * sizeof(int)));
   }
   if (fw_.h_fin) return;  // (allocated last)
   fw_.ids = static_cast<long long*>(alloc(C * (cap + 1) * sizeof(long long)));
@@ -2556,7 +2593,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   last_lang_valid = false;
   beam_scores_valid = false;
   last_segments_valid = false;
-  const bool ts = timestamps != 0;
+  clear_last_scores();
+  const bool ts = timestamps != 0, sc = scores != 0;
   ensure_batch(batch);
   ensure_full_workspace(batch);  // (before any capture: nothing may be allocated inside one)
   Slot& slot = slots_[slot_idx];
@@ -2586,24 +2624,44 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   if (ts) {  // the carried state of the timestamp rules: nothing generated yet
     launch_ts_state_init(fw_.ids, stride, nullptr, n_prompt, n_prompt, V, vocab_.token_beg, fw_.ts_state, batch, st);
   }
+  if (sc) {  // the carried sums and counts of the scores: nothing generated yet
+    HIPCHK(hipMemsetAsync(fw_.sc_sum, 0, size_t(batch) * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(fw_.sc_count, 0, size_t(batch) * sizeof(int), st));
+  }
 
   DecPass p;
   p.B = p.clips = batch; p.ids = fw_.ids; p.ids_stride = stride; p.self_kv = fw_.kv; p.self_cap = cap;
   p.absorbed = absorbed; p.n_abs = n_abs; p.chunks = chunks; p.e = slot.e_planes; p.cross_kv = slot.cross_kv;
   p.split = fc2_split(); p.dw = &dw; p.ldy = V;
-  if (ts) p.Y = fw_.ts_logits, p.ldy = fw_.ts_ldl;  // the timestamp rules read the whole row
+  if (ts || sc) p.Y = fw_.ts_logits, p.ldy = fw_.ts_ldl;  // the timestamp rules and the scores read the whole row
+  ScoreArgs sa;
+  if (sc) {
+    sa.logits = fw_.ts_logits; sa.ldl = fw_.ts_ldl; sa.V = V; sa.batch = batch; sa.part = fw_.sc_part;
+    sa.eot = vocab_.token_eot; sa.beg = vocab_.token_beg; sa.max_initial = int(max_initial_timestamp);
+    sa.ids = fw_.ids; sa.ids_stride = stride; sa.n_ids = dw.n_ids; sa.token_logprob = fw_.sc_lp; sa.lp_stride = stride;
+    sa.sum = fw_.sc_sum; sa.count = fw_.sc_count;
+  }
   // the passes whose first position lies in [lo, hi); returns the argmax steps among them
   auto enqueue_segment = [&](int lo, int hi) {
     int seg_steps = 0;
     for (int pos0 = 0, np = 1; pos0 < hi; pos0 += np) {
       np = pos0 < prompt_end ? std::min(np_max, prompt_end - pos0) : 1;
+      if (sc && pos0 == 0) np = 1;  // the row behind sot alone, with logits: the no-speech probability
       if (pos0 < lo) continue;
       const int last = pos0 + np - 1;
       const bool logits = last >= n_prompt - 1;  // then the token of the last position's rows
-      p.pos0 = pos0; p.np = np; p.best = logits ? dw.best : nullptr;
+      p.pos0 = pos0; p.np = np; p.best = logits || (sc && pos0 == 0) ? dw.best : nullptr;
       p.self_long = pos0 + np > 32;  // (np == 1 there: the prompt has at most 8 ids)
       decoder_pass(p, st);
+      if (sc && pos0 == 0) {
+        sa.state = nullptr;
+        launch_no_speech_prob(sa, vocab_.token_solm, fw_.sc_nosp, st);
+      }
       if (logits) {
+        if (sc) {  // the partial sums of the allowed set, from the state BEFORE ts_select advances it
+          sa.state = ts ? fw_.ts_state : nullptr; sa.n_gen = last + 1 - n_prompt; sa.pos = last;
+          launch_score_partial(sa, st);
+        }
         if (ts) {
           TsSelectArgs t;
           t.logits = fw_.ts_logits; t.ldl = fw_.ts_ldl; t.V = V; t.batch = batch;
@@ -2616,6 +2674,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
           launch_select_token(dw.best, (V + 31) / 32, fw_.ids, stride, last, dw.n_ids, dw.finished, vocab_.token_eot,
                               int(stop_at_eot), batch, st);
         }
+        if (sc) launch_score_finish(sa, st);
         ++seg_steps;
       }
     }
@@ -2627,7 +2686,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     const int hi = std::min(P, lo + 32);
     // (greedy's keys start with the slot, a beam key with -beam_size; a full-length key starts with kFullKey)
     const std::vector<long long> key{kFullKey, slot_idx, batch, lo, P, n_prompt, chunks, long(stop_at_eot), fc2_ksplit,
-                                     absorbed ? 1 : 0, n_abs, slot.dec, ts ? 1 : 0, ts ? max_initial_timestamp : 0};
+                                     absorbed ? 1 : 0, n_abs, slot.dec, ts ? 1 : 0, ts ? max_initial_timestamp : 0, sc ? 1 : 0};
     auto it = use_graphs ? graphs_.find(key) : graphs_.end();
     if (it != graphs_.end()) {
       HIPCHK(hipGraphLaunch(it->second.exec, st));
@@ -2656,9 +2715,37 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   }
   HIPCHK(hipMemcpyAsync(fw_.h_ids, fw_.ids, size_t(batch) * stride * sizeof(long long), hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(fw_.h_n, dw.n_ids, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (sc) {  // the scores come down with the ids: no further synchronisation point
+    HIPCHK(hipMemcpyAsync(fw_.h_lp, fw_.sc_lp, size_t(batch) * stride * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(fw_.h_sum, fw_.sc_sum, size_t(batch) * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(fw_.h_count, fw_.sc_count, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(fw_.h_nosp, fw_.sc_nosp, size_t(batch) * sizeof(float), hipMemcpyDeviceToHost, st));
+  }
   HIPCHK(hipEventRecord(slot.dec_done, st));
   slot.steps = steps;
   finish_slot(slot_idx);  // waits; the encoder's non-finite flag, timings
+  if (sc) {
+    last_scores.assign(size_t(batch), ClipScore{});
+    last_lp_stride = stride;
+    last_token_logprob.assign(size_t(batch) * stride, 0.0f);
+    for (int b = 0; b < batch; ++b) {
+      ClipScore& s = last_scores[size_t(b)];
+      // every clip generates at least one id (max_positions > the prompt): a count of 0 is a device-side error
+      if (fw_.h_count[b] < 1) throw Error(kErrDevice, "scores: a clip came back with no generated id counted");
+      s.n_generated = fw_.h_count[b];
+      s.sum_logprob = float(fw_.h_sum[b]);
+      s.avg_logprob = float(fw_.h_sum[b] / double(s.n_generated));
+      s.no_speech_prob = fw_.h_nosp[b];
+      // Whisper's rule: silence unless the text itself is confident
+      s.skipped = skip_silence && double(s.no_speech_prob) > double(no_speech_threshold) / 1000.0 &&
+                  !(double(s.avg_logprob) > double(logprob_threshold) / 1000.0);
+      for (int i = n_prompt; i < std::min(fw_.h_n[b], stride); ++i) {
+        last_token_logprob[size_t(b) * stride + i] = fw_.h_lp[size_t(b) * stride + i];
+      }
+    }
+    last_segment_score.clear();
+    last_scores_valid = true;
+  }
   for (int b = 0; b < batch; ++b) {
     n_ids[b] = fw_.h_n[b];
     for (int i = 0; i < ids_stride; ++i) {
@@ -2669,12 +2756,18 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     last_segments.clear();
     last_segment_text.clear();
     for (int b = 0; b < batch; ++b) {
+      if (sc && last_scores[size_t(b)].skipped) continue;  // a silent clip has no segments
       const int64_t* const row = reinterpret_cast<const int64_t*>(fw_.h_ids + size_t(b) * stride);
       const size_t first = last_segments.size();
       parse_segments(vocab_, row, std::min(fw_.h_n[b], stride), n_prompt, b, &last_segments);
       for (size_t i = first; i < last_segments.size(); ++i) {
         bool missing = false;
         last_segment_text.push_back(decode_tokens(vocab_, row + last_segments[i].id_begin, last_segments[i].id_count, false, &missing));
+        if (sc) {  // the mean log-probability of the segment's text ids
+          double sum = 0.0;
+          for (int k = 0; k < last_segments[i].id_count; ++k) sum += double(fw_.h_lp[size_t(b) * stride + last_segments[i].id_begin + k]);
+          last_segment_score.push_back(float(sum / double(std::max(last_segments[i].id_count, 1))));
+        }
       }
     }
     last_segments_valid = true;

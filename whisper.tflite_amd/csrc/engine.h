@@ -20,6 +20,13 @@ struct TsPart;   // kernels.h
 struct TsState;
 
 struct BeamPart;  // kernels.h
+struct ScorePart;
+
+// option scores: one clip of the last full-length decode (wt_clip_score mirrors it)
+struct ClipScore {
+  float sum_logprob, avg_logprob, no_speech_prob;
+  int32_t n_generated, skipped;
+};
 
 // WT_DEC_KERNEL_TIMERS diagnostics: the event pairs and launch classes of a slot's eager decoder launches
 struct DecTimers {
@@ -192,6 +199,24 @@ class Engine {
   std::vector<Segment> last_segments;
   std::vector<std::string> last_segment_text;  // the decoded text ids of each
   bool last_segments_valid = false;
+  // Decode confidence.  scores = 1: decode_full also forms, on the device inside the chain
+  // (k_scores.hip), the log-probability of every generated id under the set it was chosen from, their sum and count per
+  // clip, and the no-speech probability of the position-0 row.  Full-length greedy decoding only, with or without
+  // timestamps; refused like timestamps outside that scope (check_timestamp_call).  skip_silence = 1 (needs scores):
+  // a clip with no_speech_prob > no_speech_threshold / 1000 and not avg_logprob > logprob_threshold / 1000 (Whisper's
+  // rule) yields empty text and no segments; its id row is returned as decoded.
+  long scores = 0, skip_silence = 0;
+  long no_speech_threshold = 600, logprob_threshold = -1000;  // thousandths
+  // <|nospeech|> is the id the vocabulary calls token_solm (50361, multilingual 50362); the option needs it below n_vocab
+  bool has_no_speech_token() const { return vocab_.token_solm >= 0 && vocab_.token_solm < dims_.n_vocab; }
+  // per clip of the last synchronous decode with scores (wt_transcribe_long_pcm: per window); token log-probabilities
+  // [clips][last_lp_stride] aligned with the id rows (0 for prompt ids and padding); the mean over each segment's text ids
+  std::vector<ClipScore> last_scores;
+  std::vector<float> last_token_logprob;
+  int last_lp_stride = 0;
+  std::vector<float> last_segment_score;
+  bool last_scores_valid = false;
+  void clear_last_scores();  // every decode that forms no scores calls it: the getters never report an earlier call
   long gemm_variant = -1;  // -1 = plane GEMM (per-contraction fall-back to 13/16); 0 = fp32 MFMA, 13 / 16 = three bf16 planes
   // 1 = bf16 STORAGE mode (BASELINE configs[3]): bf16 weights, activations and both KV caches, fp32 accumulation,
   // fp32 residual stream; k_gemm_bf16.hip and the BF variants of the attention / decoder kernels.  Set through
@@ -324,6 +349,13 @@ class Engine {
     int ts_ldl = 0;
     TsPart* ts_part = nullptr;
     TsState* ts_state = nullptr;
+    // option scores (allocated on the first such call; it shares ts_logits): the per-chunk records [64][chunks], the
+    // token log-probabilities [64][full_cap() + 1], the carried sums and counts [64], the no-speech probabilities [64],
+    // and their pinned mirrors
+    ScorePart* sc_part = nullptr;
+    float *sc_lp = nullptr, *sc_nosp = nullptr, *h_lp = nullptr, *h_nosp = nullptr;
+    double *sc_sum = nullptr, *h_sum = nullptr;
+    int *sc_count = nullptr, *h_count = nullptr;
   } fw_;
   void ensure_full_workspace(int batch);
   static constexpr long long kFullKey = -1000;  // first entry of a full-length segment's graph key

@@ -14,6 +14,7 @@
 
 #include "error.h"
 #include "kernels.h"
+#include "ts_rules.h"
 
 namespace wt {
 namespace {
@@ -46,28 +47,6 @@ __device__ __forceinline__ float wave_sum_f(float v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
-}
-
-struct Allowed {
-  int t_lo, t_hi, s_lo, s_hi;  // inclusive id intervals; lo > hi: empty
-};
-
-// rules 1 .. 4 for a clip that has generated n_gen ids
-__device__ __forceinline__ Allowed allowed_of(const TsState st, int n_gen, int V, int eot, int beg, int mit) {
-  const bool last_ts = n_gen >= 1 && st.last_is_ts != 0;
-  const bool pen_ts = n_gen < 2 || st.prev_is_ts != 0;
-  Allowed a;
-  a.t_lo = 0, a.t_hi = eot;      // rule 1: (eot, beg) is never allowed
-  a.s_lo = beg, a.s_hi = V - 1;
-  if (last_ts && pen_ts) a.s_lo = V;   // rule 2: a pair is complete, text (or EOT) follows
-  if (last_ts && !pen_ts) a.t_lo = eot;  //         a segment was closed: its pair (or EOT) follows
-  const int tick = min(max(st.tick, -1), V - 1 - beg);  // (the state is data: bounded)
-  if (tick >= 0) a.s_lo = max(a.s_lo, beg + tick + (last_ts && !pen_ts ? 0 : 1));  // rule 3
-  if (n_gen == 0) {                                                                 // rule 4
-    a.t_lo = 1, a.t_hi = 0;
-    if (mit >= 0) a.s_hi = min(a.s_hi, beg + mit);
-  }
-  return a;
 }
 
 // grid (chunks, clips): thread t holds the 4 consecutive entries chunk * 4096 + j * 1024 + 4 t .. + 3, j = 0 .. 3

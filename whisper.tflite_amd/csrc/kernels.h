@@ -423,6 +423,37 @@ struct TsSelectArgs {
 };
 void launch_ts_select(const TsSelectArgs& a, hipStream_t s);  // ts_partial + ts_select; throws kErrInvalidArg
 
+// ---------------------------------------------------------------- scores ---
+// k_scores.hip (option scores): the log-probability of the id a greedy step chose,
+// lp = z[tok] - logsumexp(z[i] : i allowed at that step), and a clip's no-speech probability.  The allowed set is the
+// whole vocabulary (state == nullptr) or the one the timestamp rules left: rules 1 .. 4 from the clip's TsState BEFORE
+// the step's ts_select advanced it, then rule 5 decided as ts_select decides it.
+struct ScorePart {                 // one (clip, chunk of kTsChunk entries)
+  float mt, st;                    // max of the allowed text logits, sum of exp(logit - mt)
+  float ms, ss;                    // the same of the allowed timestamps
+  int has_t, has_s;                // the clip's intervals are non-empty (equal in all its chunks)
+};
+struct ScoreArgs {
+  const float* logits = nullptr;   // [batch][ldl], ldl % 4 == 0, 16-byte aligned: the logits of position pos
+  int ldl = 0, V = 0, batch = 0;
+  const TsState* state = nullptr;  // [batch] or nullptr = plain mode; with it eot, beg, max_initial, n_gen as TsSelectArgs
+  int eot = 0, beg = 0, max_initial = -1, n_gen = 0;
+  ScorePart* part = nullptr;       // [batch][ts_chunks(V)]
+  // launch_score_finish only:
+  const long long* ids = nullptr;  // ids[b][pos + 1] = the id the selection kernel wrote
+  int ids_stride = 0, pos = 0;
+  const int* n_ids = nullptr;      // after the selection kernel: n_ids[b] == pos + 2 where the clip was live
+  float* token_logprob = nullptr;  // [batch][lp_stride]: token_logprob[b][pos + 1] = lp
+  int lp_stride = 0;
+  double* sum = nullptr;           // [batch] carried: += lp where the clip was live
+  int* count = nullptr;            // [batch] carried: += 1 there
+  double* dbg_den = nullptr;       // optional [batch]: the float64 logsumexp of the allowed set
+};
+void launch_score_partial(const ScoreArgs& a, hipStream_t s);  // throws kErrInvalidArg, as launch_ts_select
+void launch_score_finish(const ScoreArgs& a, hipStream_t s);   // reads the records launch_score_partial wrote
+// prob[b] = exp(z[b][nosp] - logsumexp(z[b][0 .. V - 1])): score_partial over the whole row + a finish kernel
+void launch_no_speech_prob(const ScoreArgs& a, int nosp, float* prob, hipStream_t s);
+
 // ---- load-time re-layouts of decoder weights (host) ----
 // bf16 storage mode: W [N][K] fp32 -> ONE bf16 plane (round to nearest even) in the same fragment order,
 // [ceil(N/32)][K/16][64 lanes][8]

@@ -81,12 +81,33 @@ std::pair<int, float> detect_samples(wt_engine* h, const std::vector<float>& sam
 }  // namespace
 std::pair<int, float> EncDec::detect_language(std::vector<float>& samples) { return detect_samples(handle_, samples); }
 
+namespace {
+std::vector<ClipScore> clip_scores(const wt_engine* h) {
+  std::vector<ClipScore> out;
+  const int n = wt_last_scores(h, nullptr, 0);
+  if (n <= 0) return out;
+  std::vector<wt_clip_score> raw(static_cast<size_t>(n));
+  wt_last_scores(h, raw.data(), n);
+  for (const wt_clip_score& r : raw) {
+    ClipScore s;
+    s.sum_logprob = r.sum_logprob, s.avg_logprob = r.avg_logprob, s.no_speech_prob = r.no_speech_prob;
+    s.n_generated = r.n_generated, s.skipped = r.skipped != 0;
+    out.push_back(s);
+  }
+  return out;
+}
+}  // namespace
+std::vector<ClipScore> EncDec::scores() const { return clip_scores(handle_); }
+std::vector<ClipScore> Monolith::scores() const { return clip_scores(handle_); }
+
 std::vector<EncDec::Segment> EncDec::segments() const {
   std::vector<Segment> out;
   const int n = wt_last_segments(handle_, nullptr, 0);
   if (n <= 0) return out;
   std::vector<wt_segment> raw(static_cast<size_t>(n));
   wt_last_segments(handle_, raw.data(), n);
+  std::vector<float> score(static_cast<size_t>(n), 0.0f);
+  (void)wt_last_segment_scores(handle_, score.data(), n);  // (fails, and leaves zeros, without the option "scores")
   for (int i = 0; i < n; ++i) {
     Segment s;
     s.clip = raw[i].clip, s.t0_ms = raw[i].t0_ms, s.t1_ms = raw[i].t1_ms, s.open = raw[i].open != 0;
@@ -94,6 +115,7 @@ std::vector<EncDec::Segment> EncDec::segments() const {
     wt_last_segment_text(handle_, i, nullptr, 0, &len);
     std::vector<char> buf(len + 1);
     if (wt_last_segment_text(handle_, i, buf.data(), buf.size(), &len) == WT_OK) s.text.assign(buf.data(), len);
+    s.avg_logprob = score[static_cast<size_t>(i)];
     out.push_back(s);
   }
   return out;
