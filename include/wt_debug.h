@@ -202,6 +202,36 @@ int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* record
 int wt_dbg_language_head(wt_engine* h, int rows, int d, int n_vocab, int lang_lo, int n_lang, int forced_lang, const float* x,
                          const float* xpart, const float* ln_g, const float* ln_b, const float* tok_emb, float* probs,
                          int32_t* lang, float* lang_prob, int64_t* ids, int ids_stride);
+/* The log-mel front end, kernel by kernel (Engine::logmel, k_misc.hip; DESIGN "front end, kernel by kernel").
+ * wt_dbg_frontend_dims: {frames T0, samples per clip, pcm_stride (samples + the zero tail), pw_ld, mel_n, mel_k, dft_n,
+ * dft_k} of the engine's front end. */
+int wt_dbg_frontend_dims(wt_engine* h, int32_t out[8]);
+/* Runs Engine::logmel (the same function the product calls, no restatement) over pcm [batch][samples] with the given
+ * valid_frames (-1 = all) and returns every stage; any output but mel may be NULL:
+ * mel [batch][n_mels][T0] the result; planes [batch][pcm_stride] the PCM planes as (hi + lo) / scale, hi / lo
+ * [batch][pcm_stride] their raw fp16 bits; pw [batch * T0][pw_ld] the power spectrum; melacc [batch * T0][mel_n];
+ * raw [batch][n_mels][T0] the log-mel before mel_normalize; words [batch][4] the clip's partial-maximum words as the
+ * kernel left them (0 = never written), maxima [batch][4] the floats they stand for (-inf for 0); basis [dft_n][dft_k]
+ * the fp32 windowed DFT basis and mel_matrix [mel_n][mel_k] the engine built its device tables from. */
+int wt_dbg_frontend_stages(wt_engine* h, int batch, const float* pcm, int valid_frames, float* mel, float* planes,
+                           uint16_t* hi, uint16_t* lo, float* pw, float* melacc, float* raw, uint32_t* words, float* maxima,
+                           float* basis, float* mel_matrix);
+/* log_clipmax alone: melacc [B * T][ld] -> raw [B][n_mel][T] and the partial maxima over frames < t_valid (< 0: T) as
+ * words / maxima [B][4] (either may be NULL), the words cleared first as the engine clears them.  Needs n_mel <= ld. */
+int wt_dbg_log_clipmax(wt_engine* h, int B, int T, int n_mel, int ld, int t_valid, const float* melacc, float* raw,
+                       uint32_t* words, float* maxima);
+/* mel_normalize alone: logmel [B][n_mel][T] in / out against the partial-maximum words [B][4] */
+int wt_dbg_mel_normalize(wt_engine* h, int B, int T, int n_mel, const uint32_t* words, float* logmel);
+/* the hand-over of the log-mel to the encoder: mel [B][C][T] -> out [B][T + 2][ld], in / out (rows 0 and T + 1 and the
+ * columns >= C belong to the caller and must come back as given).  planes 0: mel_transpose, out is fp32 and ld must be
+ * C; 1: mel_transpose_planes<false>, out is the fp16 hi buffer followed by the lo buffer, values times scale; 2:
+ * mel_transpose_planes<true>, out is one bf16 buffer (scale unused). */
+int wt_dbg_mel_transpose(wt_engine* h, int planes, int B, int C, int T, int ld, float scale, const float* mel, void* out);
+/* pcm_to_planes alone: pcm [batch][n] -> planes, in / out: hi [batch * out_stride + guard] then lo (same size) as fp16
+ * bits; clip b is written at b * out_stride, everything else belongs to the caller.  n % 4 == 0, out_stride % 8 == 0,
+ * out_stride >= n, (batch * out_stride + guard) % 4 == 0. */
+int wt_dbg_pcm_to_planes(wt_engine* h, int batch, int n, int out_stride, int guard, float scale, float limit, const float* pcm,
+                         uint16_t* planes);
 #ifdef __cplusplus
 }
 #endif

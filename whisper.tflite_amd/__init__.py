@@ -61,6 +61,8 @@ DEBUG_SYMBOLS = [
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_self_attention_long",
     "wt_dbg_timestamp_select", "wt_dbg_token_scores",
+    "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
+    "wt_dbg_pcm_to_planes",
 ]
 
 
@@ -217,6 +219,13 @@ def lib() -> ctypes.CDLL:
         L.wt_last_segment_scores.argtypes = [c_void_p, fp, c_int]
         L.wt_dbg_token_scores.argtypes = [c_void_p, c_int, c_int, fp, ip64, c_int, ip32, c_int, c_int, c_int, c_int, c_int,
                                           ip32, fp, POINTER(ctypes.c_double), ip32, POINTER(ctypes.c_double)]
+        u16p, u32p = POINTER(ctypes.c_uint16), POINTER(ctypes.c_uint32)
+        L.wt_dbg_frontend_dims.argtypes = [c_void_p, ip32]
+        L.wt_dbg_frontend_stages.argtypes = [c_void_p, c_int, fp, c_int, fp, fp, u16p, u16p, fp, fp, fp, u32p, fp, fp, fp]
+        L.wt_dbg_log_clipmax.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, u32p, fp]
+        L.wt_dbg_mel_normalize.argtypes = [c_void_p, c_int, c_int, c_int, u32p, fp]
+        L.wt_dbg_mel_transpose.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, fp, c_void_p]
+        L.wt_dbg_pcm_to_planes.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, fp, u16p]
         _lib = L
     return _lib
 
@@ -1095,6 +1104,92 @@ class Engine:
                                               ids.shape[1], pos, _ip32(n_ids), _ip32(finished), int(eot), int(stop_at_eot),
                                               int(keep_ids)))
         return ids, n_ids, finished
+
+
+    # --- the log-mel front end, kernel by kernel (include/wt_debug.h) ---
+
+    def dbg_frontend_dims(self) -> dict:
+        d = np.zeros(8, np.int32)
+        self._check(lib().wt_dbg_frontend_dims(self._h, _ip32(d)))
+        return dict(zip(("frames", "samples", "pcm_stride", "pw_ld", "mel_n", "mel_k", "dft_n", "dft_k"), map(int, d)))
+
+    def dbg_frontend_stages(self, pcm, valid_frames=-1) -> dict:
+        """Engine::logmel over pcm [batch][samples], every stage: mel, planes ((hi + lo) / scale), hi / lo (float16 views
+        of the raw planes), pw, melacc, raw (the log-mel before mel_normalize), words / maxima [batch][4], basis,
+        mel_matrix."""
+        pcm = _f32(pcm)
+        d = self.dbg_frontend_dims()
+        B, T0 = pcm.shape[0], d["frames"]
+        assert pcm.shape == (B, d["samples"])
+        n_mel = self.mel_shape[0]
+        r = {
+            "mel": np.empty((B, n_mel, T0), np.float32), "planes": np.empty((B, d["pcm_stride"]), np.float32),
+            "hi": np.empty((B, d["pcm_stride"]), np.uint16), "lo": np.empty((B, d["pcm_stride"]), np.uint16),
+            "pw": np.empty((B * T0, d["pw_ld"]), np.float32), "melacc": np.empty((B * T0, d["mel_n"]), np.float32),
+            "raw": np.empty((B, n_mel, T0), np.float32), "words": np.empty((B, 4), np.uint32),
+            "maxima": np.empty((B, 4), np.float32), "basis": np.empty((d["dft_n"], d["dft_k"]), np.float32),
+            "mel_matrix": np.empty((d["mel_n"], d["mel_k"]), np.float32),
+        }
+        u16, u32 = POINTER(ctypes.c_uint16), POINTER(ctypes.c_uint32)
+        self._check(lib().wt_dbg_frontend_stages(
+            self._h, B, _fp(pcm), valid_frames, _fp(r["mel"]), _fp(r["planes"]), r["hi"].ctypes.data_as(u16),
+            r["lo"].ctypes.data_as(u16), _fp(r["pw"]), _fp(r["melacc"]), _fp(r["raw"]), r["words"].ctypes.data_as(u32),
+            _fp(r["maxima"]), _fp(r["basis"]), _fp(r["mel_matrix"])))
+        r["hi"], r["lo"] = r["hi"].view(np.float16), r["lo"].view(np.float16)
+        return r
+
+    def dbg_log_clipmax(self, melacc, n_mel, t_valid=-1):
+        """log_clipmax over melacc [B][T][ld]: (raw [B][n_mel][T], words uint32 [B][4], maxima float32 [B][4])."""
+        melacc = _f32(melacc)
+        B, T, ld = melacc.shape
+        raw = np.full((B, max(n_mel, 0), T), np.nan, np.float32)
+        words, maxima = np.zeros((B, 4), np.uint32), np.zeros((B, 4), np.float32)
+        self._check(lib().wt_dbg_log_clipmax(self._h, B, T, n_mel, ld, t_valid, _fp(melacc), _fp(raw),
+                                             words.ctypes.data_as(POINTER(ctypes.c_uint32)), _fp(maxima)))
+        return raw, words, maxima
+
+    @staticmethod
+    def clip_max_words(maxima) -> np.ndarray:
+        """floats -> the order-preserving words log_clipmax keeps its partial maxima in; -inf -> 0 (never written)."""
+        m = np.ascontiguousarray(maxima, dtype=np.float32)
+        u = m.view(np.uint32)
+        w = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+        return np.where(np.isneginf(m), np.uint32(0), w).astype(np.uint32)
+
+    def dbg_mel_normalize(self, raw, words):
+        """mel_normalize over raw [B][n_mel][T] against words uint32 [B][4]; returns the normalised copy."""
+        out = np.array(raw, np.float32, order="C")
+        B, n_mel, T = out.shape
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        assert words.shape == (B, 4)
+        self._check(lib().wt_dbg_mel_normalize(self._h, B, T, n_mel, words.ctypes.data_as(POINTER(ctypes.c_uint32)), _fp(out)))
+        return out
+
+    def dbg_mel_transpose(self, mel, out, planes=0, scale=1.0):
+        """mel [B][C][T] -> a copy of `out` with the kernel's rows written.  planes 0: out float32 [B][T + 2][C]; 1: out
+        float16 [2][B][T + 2][ld] (hi, lo); 2: out uint16 [B][T + 2][ld] (bf16 bits)."""
+        mel = _f32(mel)
+        B, C, T = mel.shape
+        out = np.array(out, order="C")
+        want = {0: np.float32, 1: np.float16, 2: np.uint16}[planes]
+        lead = (2, B, T + 2) if planes == 1 else (B, T + 2)
+        if out.dtype != want or out.shape[:-1] != lead:
+            raise ValueError("out has the wrong type or shape")
+        self._check(lib().wt_dbg_mel_transpose(self._h, planes, B, C, T, out.shape[-1], scale, _fp(mel),
+                                               out.ctypes.data_as(c_void_p)))
+        return out
+
+    def dbg_pcm_to_planes(self, pcm, planes, out_stride, scale, limit):
+        """pcm [batch][n] -> a copy of planes float16 [2][batch * out_stride + guard] with the clips written."""
+        pcm = _f32(pcm)
+        batch, n = pcm.shape
+        planes = np.array(planes, np.float16, order="C")
+        if planes.ndim != 2 or planes.shape[0] != 2:
+            raise ValueError("planes must be [2][batch * out_stride + guard]")
+        guard = planes.shape[1] - batch * out_stride
+        self._check(lib().wt_dbg_pcm_to_planes(self._h, batch, n, out_stride, guard, scale, limit, _fp(pcm),
+                                               planes.ctypes.data_as(POINTER(ctypes.c_uint16))))
+        return planes
 
 
 class DeviceArray:

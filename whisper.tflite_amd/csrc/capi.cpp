@@ -10,6 +10,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include <cmath>
+#include <limits>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -2254,6 +2255,144 @@ int wt_dbg_absorbed_query_matrix(int heads, int d, const float* wq, const float*
     wt::absorbed_query_matrix(wq, bq, wk, heads, d, &Am, &am);
     std::memcpy(A, Am.data(), Am.size() * sizeof(float));
     std::memcpy(av, am.data(), am.size() * sizeof(float));
+  });
+}
+
+// --- the log-mel front end, kernel by kernel (tests/test_gpu_frontend_kernels.py) ---
+
+}  // extern "C"
+
+namespace {
+// a partial-maximum word of log_clipmax (order-preserving bits of a float; 0 = no block wrote it) -> the float
+float clip_max_word_value(unsigned o) {
+  if (o == 0u) return -std::numeric_limits<float>::infinity();
+  const unsigned u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+// device words [(b * kClipMaxWays + w) * kClipMaxStride] -> words [B][kClipMaxWays] (+ their values)
+void clip_max_to_host(const unsigned* d_words, int B, uint32_t* words, float* maxima) {
+  std::vector<unsigned> host(size_t(B) * wt::kClipMaxWays * wt::kClipMaxStride);
+  hipchk(hipMemcpy(host.data(), d_words, host.size() * sizeof(unsigned), hipMemcpyDeviceToHost), "D2H clip_max");
+  for (size_t i = 0; i < size_t(B) * wt::kClipMaxWays; ++i) {
+    if (words) words[i] = host[i * wt::kClipMaxStride];
+    if (maxima) maxima[i] = clip_max_word_value(host[i * wt::kClipMaxStride]);
+  }
+}
+float half_bits_to_float(unsigned short b) {
+  _Float16 x;
+  std::memcpy(&x, &b, 2);
+  return static_cast<float>(x);
+}
+}  // namespace
+
+extern "C" {
+
+int wt_dbg_frontend_dims(wt_engine* h, int32_t out[8]) {
+  if (!h || !out) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    const wt::Engine& e = *h->impl;
+    const wt::Engine::FrontendView v = e.frontend_view();
+    if (v.dft_n == 0) throw wt::Error(WT_ERR_FORMAT, "vocab file carries no 80x201 mel filter bank");
+    const int32_t d[8] = {e.mel_frames(), int32_t(e.pcm_elems()), int32_t(v.pcm_stride), v.pw_ld, v.mel_n, v.mel_k, v.dft_n, v.dft_k};
+    std::memcpy(out, d, sizeof(d));
+  });
+}
+
+int wt_dbg_frontend_stages(wt_engine* h, int batch, const float* pcm, int valid_frames, float* mel, float* planes,
+                           uint16_t* hi, uint16_t* lo, float* pw, float* melacc, float* raw, uint32_t* words, float* maxima,
+                           float* basis, float* mel_matrix) {
+  if (!h || !pcm || !mel || batch < 1 || valid_frames < -1 || valid_frames > h->impl->mel_frames()) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::Engine& e = *h->impl;
+    e.require_idle();
+    const size_t nb = size_t(batch), T0 = size_t(e.mel_frames());
+    float* d_pcm = e.staging_pcm(batch);
+    float* d_mel = e.staging_mel(batch);
+    DevBuf d_raw(nb * e.mel_elems());
+    hipchk(hipMemcpyAsync(d_pcm, pcm, nb * e.pcm_elems() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D pcm");
+    e.logmel(d_pcm, batch, d_mel, valid_frames, d_raw.p);
+    e.sync();
+    const wt::Engine::FrontendView v = e.frontend_view();
+    hipchk(hipMemcpy(mel, d_mel, nb * e.mel_elems() * sizeof(float), hipMemcpyDeviceToHost), "D2H mel");
+    if (raw) d_raw.to_host(raw, nb * e.mel_elems());
+    if (planes || hi || lo) {
+      const size_t n = nb * size_t(v.pcm_stride);
+      std::vector<unsigned short> hh(n), hl(n);
+      hipchk(hipMemcpy(hh.data(), v.pcm_planes, n * 2, hipMemcpyDeviceToHost), "D2H pcm hi");
+      hipchk(hipMemcpy(hl.data(), v.pcm_planes + v.pcm_plane, n * 2, hipMemcpyDeviceToHost), "D2H pcm lo");
+      if (hi) std::memcpy(hi, hh.data(), n * 2);
+      if (lo) std::memcpy(lo, hl.data(), n * 2);
+      for (size_t i = 0; planes && i < n; ++i) planes[i] = (half_bits_to_float(hh[i]) + half_bits_to_float(hl[i])) / v.pcm_scale;
+    }
+    if (pw) hipchk(hipMemcpy(pw, v.pw, nb * T0 * size_t(v.pw_ld) * sizeof(float), hipMemcpyDeviceToHost), "D2H pw");
+    if (melacc) hipchk(hipMemcpy(melacc, v.melacc, nb * T0 * size_t(v.mel_n) * sizeof(float), hipMemcpyDeviceToHost), "D2H melacc");
+    if (words || maxima) clip_max_to_host(v.clip_max, batch, words, maxima);
+    if (basis) std::memcpy(basis, v.basis, size_t(v.dft_n) * v.dft_k * sizeof(float));
+    if (mel_matrix) std::memcpy(mel_matrix, v.mel_matrix, size_t(v.mel_n) * v.mel_k * sizeof(float));
+  });
+}
+
+int wt_dbg_log_clipmax(wt_engine* h, int B, int T, int n_mel, int ld, int t_valid, const float* melacc, float* raw,
+                       uint32_t* words, float* maxima) {
+  if (!h || !melacc || !raw || B < 1 || T < 1 || n_mel < 1 || ld < 1) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    DevArr<float> din(size_t(B) * T * ld, melacc), dout(size_t(B) * n_mel * T);
+    DevArr<unsigned> dmax(size_t(B) * wt::kClipMaxWays * wt::kClipMaxStride);
+    hipchk(hipMemset(dmax.p, 0, dmax.n * sizeof(unsigned)), "memset");  // as Engine::logmel clears them
+    wt::launch_log_clipmax(din.p, ld, dout.p, dmax.p, B, n_mel, T, h->impl->stream(), t_valid);
+    h->impl->sync();
+    dout.to_host(raw);
+    clip_max_to_host(dmax.p, B, words, maxima);
+  });
+}
+
+int wt_dbg_mel_normalize(wt_engine* h, int B, int T, int n_mel, const uint32_t* words, float* logmel) {
+  if (!h || !words || !logmel || B < 1 || T < 1 || n_mel < 1) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    DevArr<float> dx(size_t(B) * n_mel * T, logmel);
+    std::vector<unsigned> host(size_t(B) * wt::kClipMaxWays * wt::kClipMaxStride, 0u);
+    for (size_t i = 0; i < size_t(B) * wt::kClipMaxWays; ++i) host[i * wt::kClipMaxStride] = words[i];
+    DevArr<unsigned> dmax(host.size(), host.data());
+    wt::launch_mel_normalize(dx.p, dmax.p, B, n_mel, T, h->impl->stream());
+    h->impl->sync();
+    dx.to_host(logmel);
+  });
+}
+
+int wt_dbg_mel_transpose(wt_engine* h, int planes, int B, int C, int T, int ld, float scale, const float* mel, void* out) {
+  if (!h || !mel || !out || planes < 0 || planes > 2 || B < 1 || C < 1 || T < 1 || ld < 1 || (planes == 0 && ld != C)) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const size_t n = size_t(B) * (size_t(T) + 2) * ld;
+    DevArr<float> din(size_t(B) * C * T, mel);
+    if (planes == 0) {
+      DevArr<float> dout(n, static_cast<const float*>(out));
+      wt::launch_mel_transpose(din.p, dout.p, B, C, T, h->impl->stream());
+      h->impl->sync();
+      dout.to_host(static_cast<float*>(out));
+    } else {
+      DevArr<unsigned short> dout(planes == 1 ? 2 * n : n, static_cast<const unsigned short*>(out));
+      wt::launch_mel_transpose_planes(din.p, dout.p, planes == 1 ? long(n) : 0, planes == 1 ? scale : 1.0f, B, C, T, ld,
+                                      h->impl->stream(), planes == 2);
+      h->impl->sync();
+      dout.to_host(static_cast<unsigned short*>(out));
+    }
+  });
+}
+
+int wt_dbg_pcm_to_planes(wt_engine* h, int batch, int n, int out_stride, int guard, float scale, float limit, const float* pcm,
+                         uint16_t* planes) {
+  if (!h || !pcm || !planes || batch < 1 || n < 1 || out_stride < 1 || guard < 0) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    const size_t plane = size_t(batch) * out_stride + guard;
+    DevArr<float> din(size_t(batch) * n, pcm);
+    DevArr<unsigned short> dout(2 * plane, planes);
+    wt::launch_pcm_to_planes(din.p, dout.p, long(plane), scale, limit, batch, long(n), long(out_stride), h->impl->stream());
+    h->impl->sync();
+    dout.to_host(planes);
   });
 }
 

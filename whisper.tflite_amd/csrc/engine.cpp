@@ -705,6 +705,7 @@ void Engine::build_frontend_tables() {
   }
   dft_w_scale_ = f16_scale_for(bmax);
   dft_basis_p_ = upload_planes(basis.data(), dft_n, dft_k, dft_k, dft_w_scale_);
+  dft_basis_host_ = std::move(basis);
   dft_zero_bias_ = upload(std::vector<float>(size_t(dft_n), 0.0f));
   pw_ld_ = dft_n / 2;  // 256 powers per frame row (201 used)
   mel_k = int(round_up(n_bins, 32));  // 224 (the mel GEMM reads rows of pw_ld_ = 256 powers)
@@ -713,6 +714,7 @@ void Engine::build_frontend_tables() {
   for (int j = 0; j < dims_.n_mels; ++j)
     for (int k = 0; k < n_bins; ++k) mw[size_t(j) * mel_k + k] = filters_.data[size_t(j) * n_bins + k];
   mel_w = upload(mw);
+  mel_w_host_ = std::move(mw);
   have_logmel_ = true;
 }
 
@@ -1058,7 +1060,26 @@ float* Engine::staging_pcm(int batch) {
 
 // ---------------------------------------------------------- front end ---
 
-void Engine::logmel(const float* d_pcm, int batch, float* d_mel, int valid_frames) {
+Engine::FrontendView Engine::frontend_view() const {
+  FrontendView v;
+  v.pcm_planes = ws_.pcm_planes;
+  v.pcm_plane = pcm_plane_;
+  v.pcm_stride = long(pcm_elems()) + 512;
+  v.pcm_scale = f16_scale_for(kPcmBound);
+  v.pw = ws_.pw;
+  v.melacc = ws_.melacc;
+  v.clip_max = ws_.clip_max;
+  v.pw_ld = pw_ld_;
+  v.mel_n = mel_n;
+  v.mel_k = mel_k;
+  v.dft_n = dft_n;
+  v.dft_k = dft_k;
+  v.basis = dft_basis_host_.data();
+  v.mel_matrix = mel_w_host_.data();
+  return v;
+}
+
+void Engine::logmel(const float* d_pcm, int batch, float* d_mel, int valid_frames, float* d_raw) {
   if (!have_logmel_) throw Error(3, "vocab file carries no 80x201 mel filter bank");
   ensure_batch(batch);
   const size_t T0 = mel_frames(), n_samples = pcm_elems(), pad = n_samples + 512;
@@ -1116,6 +1137,7 @@ void Engine::logmel(const float* d_pcm, int batch, float* d_mel, int valid_frame
   launch_gemm(m, 0, stream_);
   HIPCHK(hipMemsetAsync(ws_.clip_max, 0, sizeof(unsigned) * batch * kClipMaxStride * kClipMaxWays, stream_));
   launch_log_clipmax(ws_.melacc, mel_n, d_mel, ws_.clip_max, batch, dims_.n_mels, int(T0), stream_, valid_frames);
+  if (d_raw) HIPCHK(hipMemcpyAsync(d_raw, d_mel, size_t(batch) * mel_elems() * sizeof(float), hipMemcpyDeviceToDevice, stream_));
   launch_mel_normalize(d_mel, ws_.clip_max, batch, dims_.n_mels, int(T0), stream_);
   HIPCHK(hipEventRecord(ev_[1], stream_));
   timings_.logmel_ms = -1.0f;  // resolved lazily in decode()/sync by the C ABI

@@ -240,7 +240,23 @@ class Engine {
 
   // d_pcm [B][pcm_elems] -> d_mel [B][n_mels][frames]; device pointers, async on stream().  valid_frames >= 0:
   // the normalisation maximum runs over frames [0, valid_frames) only (a clip shorter than the window)
-  void logmel(const float* d_pcm, int batch, float* d_mel, int valid_frames = -1);
+  // d_raw (test tap, wt_dbg_frontend_stages): device [B][n_mels][frames] that receives the log-mel as log_clipmax left
+  // it, copied out before mel_normalize works on d_mel in place; the launches are the same with and without it
+  void logmel(const float* d_pcm, int batch, float* d_mel, int valid_frames = -1, float* d_raw = nullptr);
+  // what logmel() left in the front end's workspace and the tables it contracts against (test tap); device pointers are
+  // valid after a logmel() call, until the batch capacity grows
+  struct FrontendView {
+    const unsigned short* pcm_planes = nullptr;  // hi [clip][pcm_stride], lo at + pcm_plane
+    long pcm_plane = 0, pcm_stride = 0;
+    float pcm_scale = 1.0f;
+    const float* pw = nullptr;         // [B * frames][pw_ld]
+    const float* melacc = nullptr;     // [B * frames][mel_n]
+    const unsigned* clip_max = nullptr;  // [(b * kClipMaxWays + w) * kClipMaxStride]
+    int pw_ld = 0, mel_n = 0, mel_k = 0, dft_n = 0, dft_k = 0;
+    const float* basis = nullptr;      // host, [dft_n][dft_k] fp32 (what the basis planes were split from)
+    const float* mel_matrix = nullptr;  // host, [mel_n][mel_k]
+  };
+  FrontendView frontend_view() const;
   // d_mel -> encoder output (internal) -> cross KV cache of the next pipeline slot; async on
   // the encoder stream
   void encode(const float* d_mel, int batch);
@@ -483,6 +499,7 @@ class Engine {
   long pcm_plane_ = 0;               // elements between the hi and the lo plane of the PCM workspace
   static constexpr float kPcmBound = 32.0f;  // PCM is clamped to +-32 for the fp16 planes (audio lives in +-1)
   const float* mel_w = nullptr;      // [mel_n][mel_k]
+  std::vector<float> dft_basis_host_, mel_w_host_;  // the fp32 tables the device copies were made from (frontend_view)
   int dft_n = 0, dft_k = 0, mel_n = 0, mel_k = 0;
 
   struct DecWorkspace {  // one per decoder stream

@@ -262,7 +262,10 @@ __global__ __launch_bounds__(256) void log_clipmax(const float* __restrict__ mel
       v = fmaf(l2, 0.30102999566f, l2 * -1.4320989e-8f);  // log10(2) = float(0.30102999566) - 1.4320989e-8
       if (e <= 1e-10f) v = -10.0f;  // the floor itself is exact: silence normalises to exactly -1.5, as in the reference
       const unsigned o = ordered_bits(v);
-      if (t < t_valid) lmax = o > lmax ? o : lmax;  // the reference's maximum runs over n_len frames only
+      // the reference's maximum runs over n_len frames only, and its `>` never takes a NaN (whisper.cpp:198-203): the
+      // frames a NaN sample poisoned stay NaN, the rest of the clip is floored as if they were absent.  Unguarded, a NaN
+      // with a clear sign bit orders above every finite value here and mel_normalize would clamp nothing
+      if (t < t_valid && v == v) lmax = o > lmax ? o : lmax;
     }
     tile[ty + 8 * i][tx] = v;
   }
@@ -481,7 +484,8 @@ void launch_f32_to_planes(const float* x, unsigned short* yp, long plane, long M
 
 void launch_pcm_to_planes(const float* pcm, unsigned short* yp, long plane, float scale, float limit, int batch, long n,
                           long out_stride, hipStream_t s) {
-  if (batch < 1 || n < 4 || n % 4 != 0 || out_stride % 8 != 0 || out_stride < n || !(scale > 0.0f) || !(limit > 0.0f)) {
+  if (batch < 1 || n < 4 || n % 4 != 0 || out_stride % 8 != 0 || out_stride < n || plane % 4 != 0 || !(scale > 0.0f) ||
+      !(limit > 0.0f)) {
     throw Error(kErrInvalidArg, "pcm_to_planes: bad shape");
   }
   const long total4 = (long)batch * (n / 4);
@@ -492,6 +496,9 @@ void launch_pcm_to_planes(const float* pcm, unsigned short* yp, long plane, floa
 
 void launch_mel_transpose_planes(const float* mel, unsigned short* out, long plane, float scale, int batch, int n_mels,
                                  int T, int ld, hipStream_t s, bool bf16) {
+  if (batch < 1 || batch > 65535 || n_mels < 1 || T < 1 || ld < n_mels || plane < 0 || (!bf16 && !(scale > 0.0f))) {
+    throw Error(kErrInvalidArg, "mel_transpose_planes: bad shape");
+  }
   const dim3 grid((T + 31) / 32, (n_mels + 31) / 32, batch);
   if (bf16) {
     hipLaunchKernelGGL(mel_transpose_planes<true>, grid, dim3(256), 0, s, mel, reinterpret_cast<_Float16*>(out), plane, scale,
@@ -512,18 +519,21 @@ void launch_chain_probe(float* p, int blocks, hipStream_t stream) {
 
 void launch_mel_transpose(const float* mel, float* melT, int batch, int n_mels, int T,
                           hipStream_t s) {
+  if (batch < 1 || batch > 65535 || n_mels < 1 || T < 1) throw Error(kErrInvalidArg, "mel_transpose: bad shape");
   hipLaunchKernelGGL(mel_transpose, dim3((T + 31) / 32, (n_mels + 31) / 32, batch), dim3(256), 0, s,
                      mel, melT, n_mels, T);
 }
 
 void launch_log_clipmax(const float* melacc, int ld, float* logmel, unsigned* clip_max, int batch,
                         int n_mel, int T, hipStream_t s, int t_valid) {
+  if (batch < 1 || batch > 65535 || n_mel < 1 || T < 1 || ld < n_mel) throw Error(kErrInvalidArg, "log_clipmax: bad shape");
   hipLaunchKernelGGL(log_clipmax, dim3((T + 31) / 32, (n_mel + 31) / 32, batch), dim3(256), 0, s,
                      melacc, ld, logmel, clip_max, n_mel, T, t_valid < 0 ? T : t_valid);
 }
 
 void launch_mel_normalize(float* logmel, const unsigned* clip_max, int batch, int n_mel, int T,
                           hipStream_t s) {
+  if (batch < 1 || batch > 65535 || n_mel < 1 || T < 1) throw Error(kErrInvalidArg, "mel_normalize: bad shape");
   hipLaunchKernelGGL(mel_normalize, dim3(64, batch), dim3(256), 0, s, logmel, clip_max,
                      (long)n_mel * T);
 }
