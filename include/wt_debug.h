@@ -232,6 +232,38 @@ int wt_dbg_mel_transpose(wt_engine* h, int planes, int B, int C, int T, int ld, 
  * out_stride >= n, (batch * out_stride + guard) % 4 == 0. */
 int wt_dbg_pcm_to_planes(wt_engine* h, int batch, int n, int out_stride, int guard, float scale, float limit, const float* pcm,
                          uint16_t* planes);
+/* The encoder GEMMs under the operand and output addressing Engine::encode_enqueue / encode_enqueue_bf16 give them
+ * (conv1 over overlapping rows into a padded buffer, conv2 with stride 2, the q|k|v planes, the cross-KV scatter).  The
+ * tap fills the launcher's argument struct from its parameters and calls the launcher; it restates no addressing.
+ * kind 0: launch_gemm with the engine's gemm_variant option; 1: launch_gemm_planes; 2: launch_gemm_bf16_planes.
+ * A [a_len] is ONE flat fp32 buffer, converted elementwise for the kind (1: two fp16 planes at one power-of-two scale from
+ * the buffer's maximum, 2: one bf16 plane) and uploaded with 64 zero elements behind it; row m of the operand starts at
+ * (m / a_rpb) * a_bs + (m % a_rpb) * lda and is K long.  W [N][K], bias [N], pos [pos_period][N] (kEpiPos) are laid out
+ * per kind as wt_dbg_gemm / wt_dbg_gemm_planes / wt_dbg_gemm_bf16 do.
+ * out is a flat buffer of c_len elements, in / out: uploaded as given, written by the kernel at base + c_off with c_rpb,
+ * c_bs, ldc (kEpiKvLayout: the cache [N / kv_dmodel][kv_batch][kv_heads][c_rpb][64] at base + c_off), downloaded whole,
+ * so that every cell the launch does not address comes back as given.  out_format 0: float [c_len] (kEpiResidual: R
+ * is the output itself, in place); 1 (kind 1): fp16 bits [2][c_len], hi then lo, column n times out_scale[n / seg]
+ * (seg = 0: one segment); 2 (kind 2): bf16 bits [c_len].
+ * WT_ERR_INVALID_ARG before anything is launched: an a_len shorter than the last addressed row's end, an output the
+ * buffer does not hold, an offset or (kind 0) a stride the 16-byte accesses cannot take, and whatever the launcher
+ * itself refuses (c_rpb < 32, pos_period < 32 with kEpiPos, strides that are no multiple of 8 for kinds 1 and 2,
+ * seg % 8 or more than three segments, kEpiKvLayout as fp32 from kind 2, an epilogue it has no kernel for). */
+int wt_dbg_gemm_addressed(wt_engine* h, int kind, int epi, int M, int N, int K, const float* A, long a_len, int a_rpb,
+                          long a_bs, int lda, const float* W, const float* bias, const float* pos, int pos_period,
+                          int out_format, void* out, long c_len, long c_off, int c_rpb, long c_bs, int ldc,
+                          const float* out_scale, int seg, int kv_batch, int kv_heads, int kv_dmodel, int n_cu);
+/* launch_layernorm_planes: x [M][d], g, b [d] -> planes in / out: fp16 bits [2][M * d + guard] (hi, then lo; y * scale)
+ * or, bf16 != 0, bf16 bits [M * d + guard]; y32 [M * d + guard] in / out (may be NULL: the kernel writes no fp32 copy);
+ * *nonfinite (may be NULL: no flag is passed) is cleared first and comes back 1 when a row's mean or variance was not
+ * finite.  The guard elements belong to the caller; guard % 4 == 0.  A d the launcher has no kernel for is its
+ * WT_ERR_FORMAT. */
+int wt_dbg_layernorm_planes(wt_engine* h, int M, int d, const float* x, const float* g, const float* b, float scale, int bf16,
+                            int guard, uint16_t* planes, float* y32, int32_t* nonfinite);
+/* launch_f32_to_planes: x [M][ld] -> planes in / out, fp16 bits [2][M * ld + guard] of x * scales[n / seg] (seg = 0: one
+ * segment, scales[0]); scales always holds three values.  guard % 4 == 0. */
+int wt_dbg_f32_to_planes(wt_engine* h, int M, int ld, const float* x, const float* scales, int seg, int guard,
+                         uint16_t* planes);
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_timestamp_select", "wt_dbg_token_scores",
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
     "wt_dbg_pcm_to_planes",
+    "wt_dbg_gemm_addressed", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes",
 ]
 
 
@@ -226,6 +227,11 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_mel_normalize.argtypes = [c_void_p, c_int, c_int, c_int, u32p, fp]
         L.wt_dbg_mel_transpose.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, fp, c_void_p]
         L.wt_dbg_pcm_to_planes.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, fp, u16p]
+        L.wt_dbg_gemm_addressed.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, c_long, c_int, c_long, c_int, fp, fp,
+                                            fp, c_int, c_int, c_void_p, c_long, c_long, c_int, c_long, c_int, fp, c_int, c_int,
+                                            c_int, c_int, c_int]
+        L.wt_dbg_layernorm_planes.argtypes = [c_void_p, c_int, c_int, fp, fp, fp, c_float, c_int, c_int, u16p, fp, ip32]
+        L.wt_dbg_f32_to_planes.argtypes = [c_void_p, c_int, c_int, fp, fp, c_int, c_int, u16p]
         _lib = L
     return _lib
 
@@ -1188,6 +1194,71 @@ class Engine:
             raise ValueError("planes must be [2][batch * out_stride + guard]")
         guard = planes.shape[1] - batch * out_stride
         self._check(lib().wt_dbg_pcm_to_planes(self._h, batch, n, out_stride, guard, scale, limit, _fp(pcm),
+                                               planes.ctypes.data_as(POINTER(ctypes.c_uint16))))
+        return planes
+
+    def dbg_gemm_addressed(self, kind, epi, M, N, K, A, a_rpb, a_bs, lda, W, out, c_off, c_rpb, c_bs, ldc, bias=None, pos=None,
+                           pos_period=None, out_scale=None, seg=0, kv=(0, 0, 0), n_cu=0, a_len=None, copy=True):
+        """An encoder GEMM under the engine's operand / output addressing (wt_dbg_gemm_addressed).  A is one flat float32
+        buffer, W [N][K]; `out` is the flat in / out buffer and its type selects the format: float32 [c_len], float16
+        [2][c_len] (hi, lo planes; kind 1) or uint16 [c_len] (bf16 bits; kind 2).  Returns the buffer after the launch (a
+        copy of `out`, or `out` itself, written in place, with copy=False).  kv = (kv_batch, kv_heads, kv_dmodel)."""
+        A, W = _f32(A).reshape(-1), _f32(W)
+        if W.shape != (N, K):
+            raise ValueError("W must be [N][K]")
+        out = np.array(out, order="C") if copy else out
+        if not out.flags.c_contiguous:
+            raise ValueError("out must be contiguous")
+        if out.dtype == np.float32 and out.ndim == 1:
+            fmt, c_len = 0, out.shape[0]
+        elif out.dtype == np.float16 and out.ndim == 2 and out.shape[0] == 2:
+            fmt, c_len = 1, out.shape[1]
+        elif out.dtype == np.uint16 and out.ndim == 1:
+            fmt, c_len = 2, out.shape[0]
+        else:
+            raise ValueError("out must be float32 [c_len], float16 [2][c_len] or uint16 [c_len]")
+        bias = _f32(bias) if bias is not None else None
+        pos = _f32(pos) if pos is not None else None
+        if pos_period is None:
+            pos_period = pos.shape[0] if pos is not None else 0
+        scales = _f32(out_scale if out_scale is not None else [1.0, 1.0, 1.0])
+        if scales.shape != (3,):
+            raise ValueError("out_scale holds three values")
+        self._check(lib().wt_dbg_gemm_addressed(
+            self._h, kind, epi, M, N, K, _fp(A), A.shape[0] if a_len is None else a_len, a_rpb, a_bs, lda, _fp(W), _fp(bias),
+            _fp(pos), pos_period, fmt, out.ctypes.data_as(c_void_p), c_len, c_off, c_rpb, c_bs, ldc, _fp(scales), seg,
+            kv[0], kv[1], kv[2], int(n_cu)))
+        return out
+
+    def dbg_layernorm_planes(self, x, g, b, scale, planes, y32=None, bf16=False, want_flag=True):
+        """launch_layernorm_planes over x [M][d].  planes: float16 [2][M * d + guard] (hi, lo) or, bf16, uint16
+        [M * d + guard]; y32: float32 [M * d + guard] or None (the kernel then writes no fp32 copy).  Returns copies
+        (planes, y32, flag) with the kernel's cells written; flag is None with want_flag=False."""
+        x = _f32(x)
+        M, d = x.shape
+        planes = np.array(planes, np.uint16 if bf16 else np.float16, order="C")
+        if planes.shape[:-1] != (() if bf16 else (2,)):
+            raise ValueError("planes must be [2][M * d + guard] float16, or [M * d + guard] uint16 with bf16")
+        guard = planes.shape[-1] - M * d
+        if y32 is not None:
+            y32 = np.array(y32, np.float32, order="C")
+            if y32.shape != (M * d + guard,):
+                raise ValueError("y32 must be [M * d + guard]")
+        flag = np.full(1, -1, np.int32)
+        self._check(lib().wt_dbg_layernorm_planes(self._h, M, d, _fp(x), _fp(_f32(g)), _fp(_f32(b)), scale, int(bf16), guard,
+                                                  planes.ctypes.data_as(POINTER(ctypes.c_uint16)), _fp(y32),
+                                                  _ip32(flag) if want_flag else None))
+        return planes, y32, (int(flag[0]) if want_flag else None)
+
+    def dbg_f32_to_planes(self, x, scales, seg, planes):
+        """launch_f32_to_planes over x [M][ld] -> a copy of planes float16 [2][M * ld + guard] with the rows written."""
+        x = _f32(x)
+        M, ld = x.shape
+        scales = _f32(scales)
+        planes = np.array(planes, np.float16, order="C")
+        if planes.ndim != 2 or planes.shape[0] != 2 or scales.shape != (3,):
+            raise ValueError("planes must be [2][M * ld + guard], scales [3]")
+        self._check(lib().wt_dbg_f32_to_planes(self._h, M, ld, _fp(x), _fp(scales), seg, planes.shape[1] - M * ld,
                                                planes.ctypes.data_as(POINTER(ctypes.c_uint16))))
         return planes
 

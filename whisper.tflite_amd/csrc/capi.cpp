@@ -2340,7 +2340,7 @@ int wt_dbg_log_clipmax(wt_engine* h, int B, int T, int n_mel, int ld, int t_vali
   return guarded(h, [&] {
     DevArr<float> din(size_t(B) * T * ld, melacc), dout(size_t(B) * n_mel * T);
     DevArr<unsigned> dmax(size_t(B) * wt::kClipMaxWays * wt::kClipMaxStride);
-    hipchk(hipMemset(dmax.p, 0, dmax.n * sizeof(unsigned)), "memset");  // as Engine::logmel clears them
+    hipchk(hipMemsetAsync(dmax.p, 0, dmax.n * sizeof(unsigned), h->impl->stream()), "memset");  // as Engine::logmel clears them, on the launch's stream
     wt::launch_log_clipmax(din.p, ld, dout.p, dmax.p, B, n_mel, T, h->impl->stream(), t_valid);
     h->impl->sync();
     dout.to_host(raw);
@@ -2391,6 +2391,131 @@ int wt_dbg_pcm_to_planes(wt_engine* h, int batch, int n, int out_stride, int gua
     DevArr<float> din(size_t(batch) * n, pcm);
     DevArr<unsigned short> dout(2 * plane, planes);
     wt::launch_pcm_to_planes(din.p, dout.p, long(plane), scale, limit, batch, long(n), long(out_stride), h->impl->stream());
+    h->impl->sync();
+    dout.to_host(planes);
+  });
+}
+
+}  // extern "C"
+
+namespace {
+// one past the last element that rows 0 .. M - 1 of `width` elements reach when row m starts at
+// (m / rpb) * bs + (m % rpb) * ld: the last row, or the last row of the last whole group of rpb rows
+long rows_extent(int M, int rpb, long bs, long ld, long width) {
+  const long last = long((M - 1) / rpb) * bs + long((M - 1) % rpb) * ld;
+  const long whole = M >= rpb ? long(M / rpb - 1) * bs + long(rpb - 1) * ld : 0;
+  return std::max(last, whole) + width;
+}
+}  // namespace
+
+extern "C" {
+
+int wt_dbg_gemm_addressed(wt_engine* h, int kind, int epi, int M, int N, int K, const float* A, long a_len, int a_rpb,
+                          long a_bs, int lda, const float* W, const float* bias, const float* pos, int pos_period,
+                          int out_format, void* out, long c_len, long c_off, int c_rpb, long c_bs, int ldc,
+                          const float* out_scale, int seg, int kv_batch, int kv_heads, int kv_dmodel, int n_cu) {
+  if (!h || !A || !W || !out || kind < 0 || kind > 2 || M < 1 || N < 1 || K < 1 || a_rpb < 1 || a_bs < 0 || lda < 0 ||
+      c_rpb < 1 || c_bs < 0 || ldc < 0 || c_off < 0 || c_len < 1 || n_cu < 0 || seg < 0 || ((epi & wt::kEpiBias) && !bias) ||
+      ((epi & wt::kEpiPos) && (!pos || pos_period < 1)) || (out_format != 0 && out_format != kind) ||
+      (out_format == 1 && !out_scale)) {
+    return WT_ERR_INVALID_ARG;
+  }
+  // nothing is launched over operands or an output the buffers do not hold, or at an address the 16-byte accesses of
+  // the kernels cannot take; what the launchers check themselves (rows per clip, multiples of 8, segments) is left to them
+  if (a_len < rows_extent(M, a_rpb, a_bs, lda, K)) return WT_ERR_INVALID_ARG;
+  const bool kv = (epi & wt::kEpiKvLayout) != 0;
+  if (kv) {
+    if (kv_batch < 1 || kv_heads < 1 || kv_dmodel != 64 * kv_heads || N % kv_dmodel != 0 || long(kv_batch) * c_rpb < M ||
+        c_off + long(N / kv_dmodel) * kv_batch * kv_heads * c_rpb * 64 > c_len) {
+      return WT_ERR_INVALID_ARG;
+    }
+  } else if (c_off + rows_extent(M, c_rpb, c_bs, ldc, N) > c_len) {
+    return WT_ERR_INVALID_ARG;
+  }
+  const int align = out_format == 0 ? 4 : 8;
+  if (c_off % align != 0 || (out_format == 1 && c_len % 8 != 0) ||
+      (kind == 0 && (lda % 4 != 0 || a_bs % 4 != 0 || ldc % 4 != 0 || c_bs % 4 != 0))) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    DevBuf dB(bias, N), dP(pos, pos ? size_t(pos_period) * N : 0);
+    hipStream_t st = h->impl->stream();
+    if (kind == 0) {
+      DevArr<float> dA(size_t(a_len) + 64), dC(size_t(c_len), static_cast<const float*>(out));
+      // (cleared on the launch's own stream: it does not wait for the null stream, and hipMemset may return early)
+      hipchk(hipMemsetAsync(dA.p + a_len, 0, 64 * sizeof(float), st), "memset");
+      hipchk(hipMemcpy(dA.p, A, size_t(a_len) * sizeof(float), hipMemcpyHostToDevice), "H2D");
+      DevBuf dW(W, size_t(N) * K);
+      wt::GemmArgs g;
+      g.A = dA.p; g.a_rpb = a_rpb; g.a_bs = a_bs; g.lda = lda; g.W = dW.p; g.bias = dB.p;
+      g.C = dC.p + c_off; g.R = g.C; g.c_rpb = c_rpb; g.c_bs = c_bs; g.ldc = ldc;
+      g.pos = dP.p; g.pos_period = pos_period > 0 ? pos_period : 1;
+      g.kv_batch = kv_batch; g.kv_heads = kv_heads; g.kv_dmodel = kv_dmodel;
+      g.M = M; g.N = N; g.K = K; g.variant = int(h->impl->gemm_variant);
+      wt::launch_gemm(g, epi, st);
+      h->impl->sync();
+      dC.to_host(static_cast<float*>(out));
+      return;
+    }
+    wt::PlaneGemmArgs g;
+    g.a_rpb = a_rpb; g.a_bs = a_bs; g.lda = lda; g.bias = dB.p;
+    g.c_rpb = c_rpb; g.c_bs = c_bs; g.ldc = ldc; g.pos = dP.p; g.pos_period = pos_period > 0 ? pos_period : 1;
+    g.kv_batch = kv_batch; g.kv_heads = kv_heads; g.kv_dmodel = kv_dmodel;
+    g.M = M; g.N = N; g.K = K; g.n_cu = n_cu;
+    DevArr<float> dC(out_format == 0 ? size_t(c_len) : 0, static_cast<const float*>(out));
+    DevArr<unsigned short> dO(out_format == 1 ? 2 * size_t(c_len) : out_format == 2 ? size_t(c_len) : 0,
+                              static_cast<const unsigned short*>(out));
+    if (out_format == 0) {
+      g.C = dC.p + c_off; g.R = g.C;
+    } else {
+      g.P = dO.p + c_off; g.p_plane = c_len; g.seg = seg;
+      if (out_format == 1) g.out_scale[0] = out_scale[0], g.out_scale[1] = out_scale[1], g.out_scale[2] = out_scale[2];
+    }
+    if (kind == 1) {
+      const float sa = wt::f16_scale_for(max_abs(A, size_t(a_len))), sw = wt::f16_scale_for(max_abs(W, size_t(N) * K));
+      const DevPlanes dA(A, size_t(a_len), sa);
+      const DevWeightPlanes dW(W, N, K, sw);
+      g.A = dA.ptr(); g.a_plane = dA.plane; g.W = dW.ptr(); g.a_scale = sa; g.w_scale = sw;
+      wt::launch_gemm_planes(g, epi, st);
+      h->impl->sync();
+    } else {
+      const DevBf16 dA(A, size_t(a_len)), dW(W, size_t(N) * K);
+      g.A = dA.ptr(); g.W = dW.ptr();
+      wt::launch_gemm_bf16_planes(g, epi, st);
+      h->impl->sync();
+    }
+    if (out_format == 0) dC.to_host(static_cast<float*>(out)); else dO.to_host(static_cast<unsigned short*>(out));
+  });
+}
+
+int wt_dbg_layernorm_planes(wt_engine* h, int M, int d, const float* x, const float* g, const float* b, float scale, int bf16,
+                            int guard, uint16_t* planes, float* y32, int32_t* nonfinite) {
+  if (!h || !x || !g || !b || !planes || M < 1 || d < 1 || guard < 0 || guard % 4 != 0 || !(scale > 0.0f)) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    const size_t plane = size_t(M) * d + guard;
+    DevArr<float> dx(size_t(M) * d, x), dg(size_t(d), g), db(size_t(d), b), dy(y32 ? plane : 0, y32);
+    DevArr<unsigned short> dout(bf16 ? plane : 2 * plane, planes);
+    DevArr<int> dflag(1);
+    // cleared on the launch's own stream, as the engine clears its flag: that stream does not wait for the null stream, on
+    // which a hipMemset may still be pending when the kernel sets the word
+    hipchk(hipMemsetAsync(dflag.p, 0, sizeof(int), h->impl->stream()), "memset");
+    wt::launch_layernorm_planes(dx.p, dout.p, bf16 ? 0 : long(plane), scale, y32 ? dy.p : nullptr, dg.p, db.p, M, d,
+                                h->impl->stream(), nonfinite ? dflag.p : nullptr, bf16 != 0);
+    h->impl->sync();
+    dout.to_host(planes);
+    dy.to_host(y32);
+    if (nonfinite) dflag.to_host(nonfinite);
+  });
+}
+
+int wt_dbg_f32_to_planes(wt_engine* h, int M, int ld, const float* x, const float* scales, int seg, int guard,
+                         uint16_t* planes) {
+  if (!h || !x || !scales || !planes || M < 0 || ld < 1 || seg < 0 || guard < 0 || guard % 4 != 0) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    const size_t plane = size_t(M) * ld + guard;
+    DevArr<float> dx(size_t(M) * ld, x);
+    DevArr<unsigned short> dout(2 * plane, planes);
+    wt::launch_f32_to_planes(dx.p, dout.p, long(plane), M, ld, scales, seg, h->impl->stream());
     h->impl->sync();
     dout.to_host(planes);
   });

@@ -424,6 +424,7 @@ bool launch_gemm_bf16_planes(const PlaneGemmArgs& a, int epi, hipStream_t s) {
   }
   switch (epi | (bf_out ? 256 : 0)) {
     case kEpiBias: launch_bf16_planes<kEpiBias, false>(g, s); break;
+    case kEpiBias | kEpiGelu: launch_bf16_planes<kEpiBias | kEpiGelu, false>(g, s); break;  // fp32 copy of a GELU output (kernel-level taps)
     case kEpiBias | kEpiResidual: launch_bf16_planes<kEpiBias | kEpiResidual, false>(g, s); break;
     case kEpiBias | kEpiGelu | kEpiPos: launch_bf16_planes<kEpiBias | kEpiGelu | kEpiPos, false>(g, s); break;
     case kEpiBias | 256: launch_bf16_planes<kEpiBias, true>(g, s); break;

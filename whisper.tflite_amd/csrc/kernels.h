@@ -206,11 +206,10 @@ void launch_layernorm_planes(const float* x, unsigned short* yp, long plane, flo
 
 // fp32 rows [M][ld] (contiguous) -> planes of x * scales[n / seg] (seg = 0: one segment), hi at yp, lo at yp + plane:
 // the operand hand-over between a contraction on the fp32-storage fall-back kernels and one on the plane kernels
-// probe kernel of Engine::create_streams: one wavefront busy for `microseconds` (k_misc.hip)
-void launch_spin(int microseconds, hipStream_t s);
-
 void launch_f32_to_planes(const float* x, unsigned short* yp, long plane, long M, int ld, const float* scales, int seg,
                           hipStream_t s);
+// probe kernel of Engine::create_streams: one wavefront busy for `microseconds` (k_misc.hip)
+void launch_spin(int microseconds, hipStream_t s);
 // PCM [batch][n] fp32 -> fp16 planes of clamp(x, -limit, limit) * scale, [batch][out_stride] (columns >= n untouched:
 // the caller zeroes them once — the reference's zero fill past the last sample, whisper.cpp:149-153): hi at yp, lo at
 // yp + plane.  n % 4 == 0, out_stride % 8 == 0.
@@ -235,9 +234,9 @@ void launch_encoder_attention_bf16(const unsigned short* qkv, unsigned short* ou
                                    hipStream_t stream);
 
 // ------------------------------------------------------------- front end ---
-// mel [B][n_mels][T] -> melT [B][T + 2][n_mels] rows 1..T (rows 0 and T+1 stay zero).
 // one dependent link of a launch-latency chain (test tap): blocks x 64 threads, p[block] += 1
 void launch_chain_probe(float* p, int blocks, hipStream_t stream);
+// mel [B][n_mels][T] -> melT [B][T + 2][n_mels] rows 1..T (rows 0 and T+1 stay zero).
 void launch_mel_transpose(const float* mel, float* melT, int batch, int n_mels, int T,
                           hipStream_t s);
 // mel [B][n_mels][T] -> fp16 planes of melT * scale, [B][T + 2][ld] rows 1..T, columns [0, n_mels) (the rest and
