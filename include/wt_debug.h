@@ -264,6 +264,21 @@ int wt_dbg_layernorm_planes(wt_engine* h, int M, int d, const float* x, const fl
  * segment, scales[0]); scales always holds three values.  guard % 4 == 0. */
 int wt_dbg_f32_to_planes(wt_engine* h, int M, int ld, const float* x, const float* scales, int seg, int guard,
                          uint16_t* planes);
+/* The encoder attention launchers at a given shape, with given operand scales and with rows that belong to no clip
+ * behind the last one.  The tap fills the launcher's arguments and calls the launcher; it restates no addressing.
+ * kind 0: launch_encoder_attention with `variant` 0 (encoder_attention_f32) or 1 (encoder_attention_split<4, 3>), given
+ * here and not through the attn_variant option; 1: launch_encoder_attention_planes; 2: launch_encoder_attention_bf16.
+ * qkv [batch * T + guard_rows][3 * 64 * heads] fp32, uploaded whole: as it is (kind 0), multiplied by d_head^-1/2 log2(e)
+ * scales[0] | scales[1] | scales[2] and split into two fp16 planes as wt_dbg_encoder_attention_planes does (kind 1), or
+ * rounded to bf16 (kind 2).  scales = {q, k, v, out}, powers of two, read by kind 1 only (may be NULL otherwise).
+ * out [batch * T + guard_rows][64 * heads] is in / out, uploaded as given and downloaded whole, so that every cell the
+ * launch does not write comes back as given: float (kind 0), fp16 bits [2][rows * 64 * heads], hi then lo, of the
+ * result times scales[3] (kind 1), bf16 bits (kind 2).
+ * WT_ERR_INVALID_ARG before anything is launched: a null pointer, guard_rows < 0, a negative count, a scale that is no
+ * power of two, a kind or variant the launchers do not have, and whatever the launcher refuses (batch, T or heads below
+ * 1); out is then not written. */
+int wt_dbg_encoder_attention_at(wt_engine* h, int kind, int variant, int batch, int T, int heads, int guard_rows,
+                                const float* qkv, const float scales[4], void* out);
 #ifdef __cplusplus
 }
 #endif

@@ -63,7 +63,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_timestamp_select", "wt_dbg_token_scores",
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
     "wt_dbg_pcm_to_planes",
-    "wt_dbg_gemm_addressed", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes",
+    "wt_dbg_gemm_addressed", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes", "wt_dbg_encoder_attention_at",
 ]
 
 
@@ -232,6 +232,7 @@ def lib() -> ctypes.CDLL:
                                             c_int, c_int, c_int]
         L.wt_dbg_layernorm_planes.argtypes = [c_void_p, c_int, c_int, fp, fp, fp, c_float, c_int, c_int, u16p, fp, ip32]
         L.wt_dbg_f32_to_planes.argtypes = [c_void_p, c_int, c_int, fp, fp, c_int, c_int, u16p]
+        L.wt_dbg_encoder_attention_at.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, fp, c_void_p]
         _lib = L
     return _lib
 
@@ -1261,6 +1262,38 @@ class Engine:
         self._check(lib().wt_dbg_f32_to_planes(self._h, M, ld, _fp(x), _fp(scales), seg, planes.shape[1] - M * ld,
                                                planes.ctypes.data_as(POINTER(ctypes.c_uint16))))
         return planes
+
+    def dbg_encoder_attention_at(self, kind, qkv, batch, T, heads, out, variant=0, scales=None, guard_rows=None, copy=True):
+        """An encoder attention launcher (wt_dbg_encoder_attention_at): kind 0 = launch_encoder_attention with `variant`
+        0 or 1, 1 = launch_encoder_attention_planes with scales = (q, k, v, out), 2 = launch_encoder_attention_bf16.
+        qkv [batch * T + guard_rows][3 * 64 * heads]; guard_rows defaults to the rows qkv has behind batch * T.  `out` is the
+        in / out buffer of rows = batch * T + guard_rows rows: float32 [rows][64 * heads] (kind 0), float16 [2][rows][64 *
+        heads] (hi, lo planes; kind 1) or uint16 [rows][64 * heads] (bf16 bits; kind 2).  Returns (raw, values): the buffer
+        after the launch (a copy of `out`, or `out` itself, written in place, with copy=False) and what it holds as
+        float32 [rows][64 * heads]: (hi + lo) / scales[3] for kind 1, the widened bf16 for kind 2."""
+        qkv = _f32(qkv)
+        d = 64 * heads
+        if guard_rows is None:
+            guard_rows = qkv.shape[0] - batch * T
+        rows = batch * T + guard_rows
+        out = np.array(out, order="C") if copy else out
+        want = {0: np.float32, 1: np.float16, 2: np.uint16}.get(kind, out.dtype)
+        if out.dtype != want or not out.flags.c_contiguous:
+            raise ValueError("out must be contiguous float32 (kind 0), float16 (kind 1) or uint16 (kind 2)")
+        if qkv.size < max(rows, 0) * 3 * d or out.size < (2 if kind == 1 else 1) * max(rows, 0) * d:
+            raise ValueError("qkv or out is shorter than batch * T + guard_rows rows")
+        sc = _f32(scales) if scales is not None else None
+        if sc is not None and sc.shape != (4,):
+            raise ValueError("scales holds four values: q, k, v, out")
+        self._check(lib().wt_dbg_encoder_attention_at(self._h, kind, variant, batch, T, heads, guard_rows, _fp(qkv), _fp(sc),
+                                                      out.ctypes.data_as(c_void_p)))
+        if kind == 1:
+            values = (out[0].astype(np.float32) + out[1].astype(np.float32)) / np.float32(sc[3])
+        elif kind == 2:
+            values = (out.astype(np.uint32) << 16).view(np.float32)
+        else:
+            values = out
+        return out, values.reshape(rows, d)
 
 
 class DeviceArray:

@@ -2521,4 +2521,48 @@ int wt_dbg_f32_to_planes(wt_engine* h, int M, int ld, const float* x, const floa
   });
 }
 
+int wt_dbg_encoder_attention_at(wt_engine* h, int kind, int variant, int batch, int T, int heads, int guard_rows,
+                                const float* qkv, const float scales[4], void* out) {
+  if (!h || !qkv || !out || kind < 0 || kind > 2 || guard_rows < 0 || batch < 0 || T < 0 || heads < 0 || (kind == 1 && !scales)) {
+    return WT_ERR_INVALID_ARG;
+  }
+  if (kind == 1) {
+    for (int i = 0; i < 4; ++i) {
+      int e = 0;
+      if (!(scales[i] > 0.0f) || !std::isfinite(scales[i]) || std::frexp(scales[i], &e) != 0.5f) return WT_ERR_INVALID_ARG;
+    }
+  }
+  // batch, T or heads of zero, and a variant it does not have, are the launcher's to refuse: it throws before it launches,
+  // and nothing is downloaded behind a throw
+  return guarded(h, [&] {
+    const size_t d = size_t(heads) * 64, rows = size_t(batch) * T + guard_rows, n_in = rows * 3 * d, n_out = rows * d;
+    hipStream_t st = h->impl->stream();
+    if (kind == 0) {
+      const DevArr<float> dQ(n_in, qkv), dO(n_out, static_cast<const float*>(out));
+      wt::launch_encoder_attention(dQ.p, dO.p, batch, T, heads, variant, st);
+      h->impl->sync();
+      dO.to_host(static_cast<float*>(out));
+    } else if (kind == 1) {
+      constexpr float kQ = 0.125f * 1.44269504088896340736f;
+      // planes as the qkv GEMM's epilogue writes them: q * kQ * q_scale | k * k_scale | v * v_scale
+      std::vector<float> scaled(n_in);
+      for (size_t r = 0; r < rows; ++r)
+        for (size_t c = 0; c < 3 * d; ++c)
+          scaled[r * 3 * d + c] = qkv[r * 3 * d + c] * (c < d ? kQ * scales[0] : c < 2 * d ? scales[1] : scales[2]);
+      const DevPlanes dQ(scaled.data(), n_in, 1.0f);
+      const DevArr<unsigned short> dO(2 * n_out, static_cast<const unsigned short*>(out));
+      wt::launch_encoder_attention_planes(dQ.ptr(), dQ.plane, dO.p, long(n_out), batch, T, heads, scales[0], scales[1],
+                                          scales[2], scales[3], st);
+      h->impl->sync();
+      dO.to_host(static_cast<unsigned short*>(out));
+    } else {
+      const DevBf16 dQ(qkv, n_in);
+      const DevArr<unsigned short> dO(n_out, static_cast<const unsigned short*>(out));
+      wt::launch_encoder_attention_bf16(dQ.ptr(), dO.p, batch, T, heads, st);
+      h->impl->sync();
+      dO.to_host(static_cast<unsigned short*>(out));
+    }
+  });
+}
+
 }  // extern "C"

@@ -867,6 +867,7 @@ __global__ __launch_bounds__(256) void cross_attention_step(const float* __restr
 
 void launch_encoder_attention(const float* qkv, float* out, int batch, int T, int heads, int variant,
                               hipStream_t s, float q_scale, float k_scale, float v_scale) {
+  if (batch < 1 || T < 1 || heads < 1) throw Error(kErrInvalidArg, "encoder attention: bad shape");
   const int q_blocks = (T + AQ - 1) / AQ;
   const dim3 grid(batch * heads * q_blocks);
   (void)q_scale; (void)k_scale; (void)v_scale;

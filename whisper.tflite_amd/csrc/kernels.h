@@ -218,9 +218,11 @@ void launch_pcm_to_planes(const float* pcm, unsigned short* yp, long plane, floa
 
 // ------------------------------------------------------ encoder attention ---
 // qkv [B*T][3*d] (q | k | v, heads of 64 inside each third) -> out [B*T][d].
-// Non-causal softmax(q k^T / 8) v per (clip, head), flash-style; `variant`: 0 fp32 MFMA, 1/2 three bf16
-// planes (128 / 256 queries per block), 3 bf16 operands, 4 two fp16 planes.
-// q_scale, k_scale, v_scale: f16_scale_for() of the operands' bounds (variant 4 only)
+// Non-causal softmax(q k^T / 8) v per (clip, head), flash-style, on fp32 storage: the forms a layer falls back to
+// when its operands leave the plane kernel's range.  `variant`: 0 = encoder_attention_f32 (fp32 MFMA), 1 =
+// encoder_attention_split<4, 3> (three bf16 planes, six products, 128 queries per block); any other variant and
+// batch, T or heads below 1 are kErrInvalidArg, before anything is launched.  q_scale, k_scale and v_scale are
+// unused: both forms take the operands at their own magnitude.
 void launch_encoder_attention(const float* qkv, float* out, int batch, int T, int heads, int variant,
                               hipStream_t stream, float q_scale = 1.0f, float k_scale = 1.0f, float v_scale = 1.0f);
 // The same attention on pre-split operands (k_attention_planes.hip): qkv as fp16 planes [B*T][3d] (hi at qkv, lo at
