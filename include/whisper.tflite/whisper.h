@@ -104,6 +104,15 @@ struct Engine {  // reference whisper.h:159-163
   virtual ~Engine() = default;
 };
 
+// An addition: how one 30 s window of the last transcribe() was decoded under the options "temperature" /
+// "temperature_fallback" with "max_positions" set (wt_capi.h, wt_last_decode_info).
+struct ClipDecode {
+  float temperature = 0.0f;     // the temperature the kept result was decoded at
+  int attempts = 0;             // decodes the window took
+  bool needs_fallback = false;  // the kept result still met the fall-back condition: the schedule was exhausted
+  float compression_ratio = 0.0f;
+};
+
 // An addition: the confidence of one 30 s window of the last transcribe() with the options "scores" = 1 and
 // "max_positions" set (wt_capi.h, wt_last_scores).
 struct ClipScore {
@@ -127,6 +136,7 @@ struct Monolith : public Engine {
   // an addition: as EncDec::detect_language
   std::pair<int, float> detect_language(std::vector<float>& samples);
   std::vector<ClipScore> scores() const;  // an addition: as EncDec::scores
+  std::vector<ClipDecode> decode_info() const;  // an addition: as EncDec::decode_info
   wt_engine* handle() const { return handle_; }
 
  private:
@@ -161,6 +171,8 @@ struct EncDec : public Engine {
   std::vector<Segment> segments() const;
   // one per window of the last transcribe(); empty when that call ran without the option "scores"
   std::vector<ClipScore> scores() const;
+  // one per window of the last transcribe(); empty when that call neither sampled nor ran the temperature fall-back
+  std::vector<ClipDecode> decode_info() const;
   // for the batch entry points and options of wt_capi.h: wt_engine_set_option(handle(), "beam_size", 5) makes both
   // transcribe() overloads decode with beam search
   wt_engine* handle() const { return handle_; }

@@ -89,6 +89,13 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * no <|nospeech|> id), "skip_silence" (0 = default; 1 = a clip with no_speech_prob > "no_speech_threshold" / 1000
  * (default 600) and not avg_logprob > "logprob_threshold" / 1000 (default -1000) yields empty text and no segments; needs
  * "scores" = 1 at the call),
+ * "temperature" (thousandths, 0 = default: greedy, up to 1000; full-length decoding samples every id from
+ * softmax(logits / T) over the ids the step may choose, on the device, see wt_last_decode_info below and DESIGN.md
+ * section 19), "seed" (default 0: the 64-bit key of the sampler's Philox4x32-10 stream; a decode is a function of the
+ * audio, the options and the seed), "temperature_fallback" (0 = default; 1 = Whisper's temperature fall-back: a clip is
+ * decoded again at "temperature" + "temperature_increment" (default 200), ... up to 1000 while its compression ratio
+ * exceeds "compression_ratio_threshold" / 1000 (default 2400, 0 = off) or its avg_logprob lies below
+ * "logprob_threshold" / 1000, unless it is silence by "no_speech_threshold"; needs "scores" = 1 at the call),
  * "stop_at_eot" (whisper.cpp:397-399, default 1), "verbose" (default 0),
  * "cross_chunks" (key chunks per (clip, head) in the decoder cross attention: 1, 2, 4, 8, or 0 = by batch size, the default).
  * Kernel selection (results stay within the fp32 error budget for every value): "gemm_variant"
@@ -276,6 +283,24 @@ int wt_last_token_logprobs(const wt_engine* h, float* out, int stride, int cap_c
 /* mean token log-probability over the text ids of each segment of wt_last_segments, same order (at most cap written).
  * Returns the segment count, or -WT_ERR_INVALID_ARG unless the last synchronous decode ran with scores and timestamps. */
 int wt_last_segment_scores(const wt_engine* h, float* avg_logprob, int cap);
+
+/* Temperature sampling and fall-back (options "temperature", "seed", "temperature_fallback" together with
+ * "max_positions", with or without "timestamps" and "scores").  The token of a step is the argmax
+ * over the allowed ids of logit / T + Gumbel noise (Philox4x32-10 under the key "seed" and the counter (id / 4, position,
+ * clip index, attempt)), which is a sample from softmax(logits / T); the timestamp rules and the scores work on the
+ * untempered logits.  T = 0 is the greedy step.  With fall-back a clip's result is that of the first temperature of
+ * the schedule after which it needs no further attempt, or of the last.  temperature_milli: the temperature the kept
+ * result was decoded at; attempts: decodes the clip took; needs_fallback: 1 when the kept result still met the
+ * fall-back condition (the schedule was exhausted); compression_ratio: bytes of the clip's text (its generated ids below
+ * EOT, decoded as wt_decode_text does with omit_special_tokens = 1) over bytes of zlib's compress() of it, 0 for empty
+ * text and where zlib (libz.so.1, loaded at first use) is not available — a nonzero "compression_ratio_threshold" is
+ * then WT_ERR_UNSUPPORTED at a fall-back call.  With sampling or fall-back set, a decode call is WT_ERR_UNSUPPORTED
+ * without "max_positions" and wherever "max_positions" refuses one; the engine stays usable after each. */
+typedef struct wt_clip_decode { int32_t temperature_milli, attempts, needs_fallback; float compression_ratio; } wt_clip_decode;
+/* every clip of the last synchronous decode that sampled or ran fall-back (after wt_transcribe_long_pcm: one per window,
+ * whose clip index in the counter is its index in the file); returns the clip count, or -WT_ERR_INVALID_ARG when that
+ * decode did neither (as wt_last_scores) */
+int wt_last_decode_info(const wt_engine* h, wt_clip_decode* out, int cap);
 
 /* Per-kernel-class device time of the encoder phase of the last batch call: HIP event pairs
  * recorded on the engine's stream around every launch of the class.  flops / bytes are the

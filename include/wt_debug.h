@@ -115,6 +115,19 @@ int wt_dbg_self_attention_long(wt_engine* h, int batch, int heads, int cap, int 
 int wt_dbg_timestamp_select(wt_engine* h, int B, int V, const float* logits, const int64_t* ids, int ids_stride,
                             const int32_t* n_ids, int sample_begin, int eot, int beg, int max_initial_timestamp,
                             int64_t* token, double* L, float* M);
+/* sample_partial + sample_select (k_sample.hip, option "temperature"): one sampling step per row.
+ * logits, ids, n_ids, sample_begin, eot, beg, max_initial_timestamp, token, L and M as wt_dbg_timestamp_select;
+ * timestamps = 0: the allowed set is the whole vocabulary (beg and max_initial_timestamp unused, L is NaN, M the row's
+ * maximum).  temperature [B]: 0 = greedy (no random number is drawn), else the token is the argmax of
+ * z / T + Gumbel noise from Philox4x32-10 under the key (seed & 0xffffffff, seed >> 32) and the counter
+ * (id >> 2, position, clip_base + b, attempt); the position is `pos`, or n_ids[b] - 1 where pos < 0.
+ * key [B] (optional) = the winning key as the kernel formed it.  Needs 0 <= eot < V (timestamps: eot < beg < V),
+ * V <= 262144, B <= 64, temperature >= 0 and 1 <= sample_begin <= n_ids[b] <= ids_stride, else WT_ERR_INVALID_ARG
+ * before anything is launched. */
+int wt_dbg_sample_select(wt_engine* h, int B, int V, const float* logits, const int64_t* ids, int ids_stride,
+                         const int32_t* n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
+                         const float* temperature, uint64_t seed, int attempt, int clip_base, int pos, int64_t* token,
+                         double* L, float* M, float* key);
 /* score_partial + score_finish (k_scores.hip, option "scores") alone: the log-probability of the id
  * each row chose at one step.  logits [B][V]; row b of ids [B][ids_stride] holds n_ids[b] ids, the LAST of them the id
  * the step chose (any id in [0, V)), the first sample_begin the prompt.  timestamps = 0: every id is allowed; 1: the set

@@ -45,7 +45,7 @@ CAPI_SYMBOLS = [
     "wt_encdec_debug_batch",
     "wt_encdec_tokens_full_batch", "wt_encdec_tokens_full_batch_dev", "wt_transcribe_tokens_full_batch_dev",
     "wt_last_segments", "wt_last_segment_text", "wt_vocab_segments",
-    "wt_last_scores", "wt_last_token_logprobs", "wt_last_segment_scores",
+    "wt_last_scores", "wt_last_token_logprobs", "wt_last_segment_scores", "wt_last_decode_info",
     "wt_language_count", "wt_detect_language_batch", "wt_detect_language_batch_dev", "wt_detect_language_pcm", "wt_last_languages",
     "wt_last_timings", "wt_last_beam_scores", "wt_last_kernel_stats", "wt_decode_text", "wt_language_id", "wt_lang_code", "wt_wav_read_legacy",
     "wt_vocab_info", "wt_filters", "wt_write_synthetic_weights", "wt_write_synthetic_vocab",
@@ -60,7 +60,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_self_attention_long",
-    "wt_dbg_timestamp_select", "wt_dbg_token_scores",
+    "wt_dbg_timestamp_select", "wt_dbg_token_scores", "wt_dbg_sample_select",
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
     "wt_dbg_pcm_to_planes",
     "wt_dbg_gemm_addressed", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes", "wt_dbg_encoder_attention_at",
@@ -215,7 +215,10 @@ def lib() -> ctypes.CDLL:
         L.wt_vocab_segments.argtypes = [c_void_p, ip64, c_int, c_int, c_void_p, c_int]
         L.wt_dbg_timestamp_select.argtypes = [c_void_p, c_int, c_int, fp, ip64, c_int, ip32, c_int, c_int, c_int, c_int,
                                               ip64, POINTER(ctypes.c_double), fp]
+        L.wt_dbg_sample_select.argtypes = [c_void_p, c_int, c_int, fp, ip64, c_int, ip32, c_int, c_int, c_int, c_int, c_int,
+                                           fp, ctypes.c_uint64, c_int, c_int, c_int, ip64, POINTER(ctypes.c_double), fp, fp]
         L.wt_last_scores.argtypes = [c_void_p, c_void_p, c_int]
+        L.wt_last_decode_info.argtypes = [c_void_p, c_void_p, c_int]
         L.wt_last_token_logprobs.argtypes = [c_void_p, fp, c_int, c_int]
         L.wt_last_segment_scores.argtypes = [c_void_p, fp, c_int]
         L.wt_dbg_token_scores.argtypes = [c_void_p, c_int, c_int, fp, ip64, c_int, ip32, c_int, c_int, c_int, c_int, c_int,
@@ -309,6 +312,9 @@ SEGMENT_DTYPE = np.dtype([(k, np.int32) for k in ("clip", "t0_ms", "t1_ms", "id_
 # one clip of a decode with option scores (wt_clip_score)
 SCORE_DTYPE = np.dtype([("sum_logprob", np.float32), ("avg_logprob", np.float32), ("no_speech_prob", np.float32),
                         ("n_generated", np.int32), ("skipped", np.int32)])
+# one clip of a decode that sampled or ran fall-back (wt_clip_decode)
+DECODE_DTYPE = np.dtype([("temperature_milli", np.int32), ("attempts", np.int32), ("needs_fallback", np.int32),
+                         ("compression_ratio", np.float32)])
 
 
 def _segments(call):
@@ -621,6 +627,18 @@ class Engine:
             lib().wt_last_scores(self._h, out.ctypes.data_as(c_void_p), n)
         return out
 
+    def last_decode_info(self) -> np.ndarray:
+        """DECODE_DTYPE records of every clip of the last synchronous decode that sampled or ran fall-back (options
+        temperature, temperature_fallback): temperature_milli, attempts, needs_fallback,
+        compression_ratio."""
+        n = lib().wt_last_decode_info(self._h, None, 0)
+        if n < 0:
+            raise WtError(-n, "no decode info: the last synchronous decode neither sampled nor ran fall-back")
+        out = np.zeros(n, DECODE_DTYPE)
+        if n:
+            lib().wt_last_decode_info(self._h, out.ctypes.data_as(c_void_p), n)
+        return out
+
     def last_token_logprobs(self, stride: int) -> np.ndarray:
         """float32 [clips][stride] aligned with the id rows of that decode: 0 for prompt ids and padding."""
         n = lib().wt_last_token_logprobs(self._h, None, 0, 0)
@@ -929,6 +947,26 @@ class Engine:
                                                   int(sample_begin), int(eot), int(beg), int(max_initial_timestamp),
                                                   _ip64(tok), L.ctypes.data_as(POINTER(ctypes.c_double)), _fp(M)))
         return tok, L, M
+
+    def dbg_sample_select(self, logits, ids, n_ids, sample_begin, temperature, seed=0, attempt=0, clip_base=0, pos=-1,
+                          timestamps=False, eot=0, beg=1, max_initial_timestamp=50):
+        """One sampling step (k_sample.hip) per row: arguments as dbg_timestamp_select, plus temperature float32 [B]
+        (0 = greedy), the Philox seed, attempt and clip_base, and the position word of the counter (pos < 0: the row's
+        n_ids - 1).  timestamps=False: the whole vocabulary is allowed.  Returns (token int64 [B], L float64 [B],
+        M float32 [B], key float32 [B] = the winning key z / T + g)."""
+        logits = _f32(logits)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        n_ids = np.ascontiguousarray(n_ids, dtype=np.int32)
+        B, V = logits.shape
+        temperature = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, np.float32), (B,)))
+        assert ids.shape[0] == B and n_ids.shape == (B,)
+        tok, L, M, key = np.zeros(B, np.int64), np.zeros(B, np.float64), np.zeros(B, np.float32), np.zeros(B, np.float32)
+        self._check(lib().wt_dbg_sample_select(self._h, B, V, _fp(logits), _ip64(ids), ids.shape[1], _ip32(n_ids),
+                                               int(sample_begin), int(bool(timestamps)), int(eot), int(beg),
+                                               int(max_initial_timestamp), _fp(temperature), int(seed), int(attempt),
+                                               int(clip_base), int(pos), _ip64(tok),
+                                               L.ctypes.data_as(POINTER(ctypes.c_double)), _fp(M), _fp(key)))
+        return tok, L, M, key
 
     def dbg_token_scores(self, logits, ids, n_ids, sample_begin, live=None, sums=None, counts=None, timestamps=False, eot=0,
                          beg=1, max_initial_timestamp=50):

@@ -33,13 +33,18 @@ void usage(const char* argv0) {
             << "                  [mm:ss.mmm --> mm:ss.mmm] text\n"
             << "  --scores        with --max-positions: print avg_logprob and no_speech_prob of every 30 s window (with\n"
             << "                  --timestamps also each segment's mean log-probability on its line)\n"
-            << "  --skip-silence  with --scores: windows Whisper's no-speech rule calls silent yield no text\n";
+            << "  --skip-silence  with --scores: windows Whisper's no-speech rule calls silent yield no text\n"
+            << "  --temperature T with --max-positions: sample every id at temperature T in [0, 1] (default 0: greedy)\n"
+            << "  --seed N        the sampler's 64-bit seed (default 0): same audio, options and seed, same text\n"
+            << "  --fallback      with --scores: Whisper's temperature fall-back, T, T + 0.2, ... 1.0 per window, and one\n"
+            << "                  line per window with the temperature kept, the attempts and the compression ratio\n"
+            << "  --compression-ratio-threshold X  with --fallback: decode again above this ratio (default 2.4, 0 = off)\n";
 }
 }  // namespace
 
 int main(int argc, char* argv[]) {
-  std::string model_prefix, vocab, input, lang, beam, max_positions;
-  bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false;
+  std::string model_prefix, vocab, input, lang, beam, max_positions, temperature, seed, cr_threshold;
+  bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], v;
     if (a == "-h" || a == "--help") {
@@ -66,6 +71,10 @@ int main(int argc, char* argv[]) {
       skip_silence = true;
       continue;
     }
+    if (a == "--fallback") {
+      fallback = true;
+      continue;
+    }
     const size_t eq = a.find('=');
     if (eq != std::string::npos) {
       v = a.substr(eq + 1);
@@ -82,6 +91,9 @@ int main(int argc, char* argv[]) {
     else if (a == "--lang") lang = v;
     else if (a == "--beam") beam = v;
     else if (a == "--max-positions") max_positions = v;
+    else if (a == "--temperature") temperature = v;
+    else if (a == "--seed") seed = v;
+    else if (a == "--compression-ratio-threshold") cr_threshold = v;
     else {
       std::cerr << "The following argument was not expected: " << a << "\n";
       usage(argv[0]);
@@ -162,6 +174,40 @@ int main(int argc, char* argv[]) {
       return 105;
     }
   }
+  if (!temperature.empty() || fallback || !seed.empty() || !cr_threshold.empty()) {
+    if (max_positions.empty()) {
+      std::cerr << "--temperature, --seed, --fallback and --compression-ratio-threshold require --max-positions\n";
+      return 105;
+    }
+    if (fallback && !scores) {
+      std::cerr << "--fallback requires --scores\n";
+      return 105;
+    }
+    auto thousandths = [&](const std::string& text, const char* flag, const char* key) {  // "0.6" -> 600
+      char* end = nullptr;
+      const double x = std::strtod(text.c_str(), &end);
+      if (end == text.c_str() || *end || !(x >= 0.0 && x <= 1000.0) ||
+          wt_engine_set_option(encdec.handle(), key, long(x * 1000.0 + 0.5)) != WT_OK) {
+        std::cerr << flag << ": " << (end == text.c_str() || *end ? "expected a number" : wt_last_error(encdec.handle())) << ", got " << text << "\n";
+        return false;
+      }
+      return true;
+    };
+    if (!temperature.empty() && !thousandths(temperature, "--temperature", "temperature")) return 105;
+    if (!cr_threshold.empty() && !thousandths(cr_threshold, "--compression-ratio-threshold", "compression_ratio_threshold")) return 105;
+    if (!seed.empty()) {
+      char* end = nullptr;
+      const unsigned long long n = std::strtoull(seed.c_str(), &end, 10);
+      if (end == seed.c_str() || *end || wt_engine_set_option(encdec.handle(), "seed", long(n)) != WT_OK) {
+        std::cerr << "--seed: expected an unsigned 64-bit number, got " << seed << "\n";
+        return 105;
+      }
+    }
+    if (fallback && wt_engine_set_option(encdec.handle(), "temperature_fallback", 1) != WT_OK) {
+      std::cerr << "--fallback: " << wt_last_error(encdec.handle()) << "\n";
+      return 105;
+    }
+  }
   std::string text;
   if (long_audio) {
     std::vector<float> pcm = wav_read_legacy(input.c_str());
@@ -194,6 +240,13 @@ int main(int argc, char* argv[]) {
     for (const ClipScore& c : encdec.scores()) {
       std::cout << "window " << w++ << ": avg_logprob=" << c.avg_logprob << " no_speech_prob=" << c.no_speech_prob
                 << (c.skipped ? " (skipped)" : "") << "\n";
+    }
+  }
+  {  // sampling or fall-back: one line per window
+    int w = 0;
+    for (const ClipDecode& d : encdec.decode_info()) {
+      std::cout << "window " << w++ << ": temperature=" << d.temperature << " attempts=" << d.attempts
+                << " compression_ratio=" << d.compression_ratio << (d.needs_fallback ? " (schedule exhausted)" : "") << "\n";
     }
   }
   if (timestamps) {

@@ -235,6 +235,21 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
   } else if (k == "logprob_threshold") {
     if (value > 0 || value < -1000000) return fail(h, WT_ERR_INVALID_ARG, "logprob_threshold must be in [-1000000, 0] (thousandths)");
     e.logprob_threshold = value;
+  } else if (k == "temperature") {
+    // temperature sampling, thousandths: 0 = greedy
+    if (value < 0 || value > 1000) return fail(h, WT_ERR_INVALID_ARG, "temperature must be in [0, 1000] (thousandths)");
+    e.temperature = value;
+  } else if (k == "temperature_fallback") {
+    if (value != 0 && value != 1) return fail(h, WT_ERR_INVALID_ARG, "temperature_fallback must be 0 or 1");
+    e.temperature_fallback = value;
+  } else if (k == "temperature_increment") {
+    if (value < 1 || value > 1000) return fail(h, WT_ERR_INVALID_ARG, "temperature_increment must be in [1, 1000] (thousandths)");
+    e.temperature_increment = value;
+  } else if (k == "compression_ratio_threshold") {
+    if (value < 0 || value > 1000000) return fail(h, WT_ERR_INVALID_ARG, "compression_ratio_threshold must be in [0, 1000000] (thousandths, 0 = off)");
+    e.compression_ratio_threshold = value;
+  } else if (k == "seed") {
+    e.seed = value;  // all 64 bits are the Philox key
   } else if (k == "max_initial_timestamp") {
     if (value < -1 || value > 1500) return fail(h, WT_ERR_INVALID_ARG, "max_initial_timestamp must be in [-1, 1500] (ticks of 20 ms, -1 = no limit)");
     e.max_initial_timestamp = value;
@@ -321,6 +336,11 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "skip_silence") *value = e.skip_silence;
   else if (k == "no_speech_threshold") *value = e.no_speech_threshold;
   else if (k == "logprob_threshold") *value = e.logprob_threshold;
+  else if (k == "temperature") *value = e.temperature;
+  else if (k == "temperature_fallback") *value = e.temperature_fallback;
+  else if (k == "temperature_increment") *value = e.temperature_increment;
+  else if (k == "compression_ratio_threshold") *value = e.compression_ratio_threshold;
+  else if (k == "seed") *value = e.seed;
   else if (k == "stop_at_eot") *value = e.stop_at_eot;
   else if (k == "verbose") *value = e.verbose;
   else if (k == "cross_chunks") *value = e.cross_chunks;
@@ -621,6 +641,16 @@ int wt_last_scores(const wt_engine* h, wt_clip_score* out, int cap) {
   return n;
 }
 
+int wt_last_decode_info(const wt_engine* h, wt_clip_decode* out, int cap) {
+  static_assert(sizeof(wt_clip_decode) == sizeof(wt::Engine::ClipDecode), "wt_clip_decode mirrors wt::Engine::ClipDecode");
+  if (!h || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_decode_info_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last_decode_info.size());
+  for (int i = 0; i < n && i < cap; ++i) std::memcpy(&out[i], &e.last_decode_info[size_t(i)], sizeof(wt_clip_decode));
+  return n;
+}
+
 int wt_last_token_logprobs(const wt_engine* h, float* out, int stride, int cap_clips) {
   if (!h || cap_clips < 0 || stride < 0 || (cap_clips > 0 && stride > 0 && !out)) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
@@ -780,6 +810,11 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
     std::vector<std::string> segment_text;
     std::vector<wt::ClipScore> scores;  // option scores: every window's
     std::vector<float> token_logprob, segment_score;
+    std::vector<wt::Engine::ClipDecode> decode_info;  // sampling / fall-back: every window's
+    struct ClipBase {  // a window's Philox clip index is its index in the file, however the windows are batched
+      wt::Engine& e;
+      ~ClipBase() { e.clip_base = 0; }
+    } clip_base{e};
     for (size_t w0 = 0; w0 < n_win; w0 += 32) {
       const int B = int(std::min<size_t>(32, n_win - w0));
       std::vector<float> clips(size_t(B) * win, 0.0f);
@@ -797,12 +832,14 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
       std::vector<int32_t> n(B);
       if (full) {
         e.encode_full(d_mel, B);
+        e.clip_base = long(w0);
         e.decode_full(B, ids.data(), int(row), n.data());
       } else {
         e.encode(d_mel, B);
         e.decode(B, ids.data(), n.data(), nullptr, 0);
       }
       e.sync();  // clips[] is read by the H2D copy on the encoder stream
+      if (e.last_decode_info_valid) decode_info.insert(decode_info.end(), e.last_decode_info.begin(), e.last_decode_info.end());
       if (e.last_lang_valid) {
         langs.insert(langs.end(), e.last_lang.begin(), e.last_lang.end());
         lang_probs.insert(lang_probs.end(), e.last_lang_prob.begin(), e.last_lang_prob.end());
@@ -829,6 +866,7 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
       }
     }
     if (e.last_scores_valid) e.last_scores = scores, e.last_token_logprob = token_logprob, e.last_segment_score = segment_score;
+    if (e.last_decode_info_valid) e.last_decode_info = decode_info;
     if (e.last_lang_valid) e.last_lang = langs, e.last_lang_prob = lang_probs;
     if (e.last_segments_valid) e.last_segments = segments, e.last_segment_text = segment_text;
   });
@@ -2088,6 +2126,64 @@ int wt_dbg_timestamp_select(wt_engine* h, int B, int V, const float* logits, con
     for (int b = 0; b < B; ++b) token[b] = rows[size_t(b) * stride + n_ids[b]];
     if (L) dL.to_host(L);
     if (M) dM.to_host(M);
+  });
+}
+
+int wt_dbg_sample_select(wt_engine* h, int B, int V, const float* logits, const int64_t* ids, int ids_stride,
+                         const int32_t* n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
+                         const float* temperature, uint64_t seed, int attempt, int clip_base, int pos, int64_t* token,
+                         double* L, float* M, float* key) {
+  if (!h || !logits || !ids || !n_ids || !token || !temperature || B < 1 || B > wt::kSampleClipsMax || V < 2 ||
+      ids_stride < 1 || sample_begin < 1 || attempt < 0 || clip_base < 0) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    // as wt_dbg_timestamp_select: runs of consecutive rows with equal n_ids are launched together
+    const int ldl = (V + 3) & ~3;
+    wt::SampleParams prm{};
+    prm.seed_lo = unsigned(seed & 0xffffffffull), prm.seed_hi = unsigned(seed >> 32);
+    prm.attempt = unsigned(attempt), prm.clip_base = unsigned(clip_base);
+    for (int b = 0; b < B; ++b) {
+      if (n_ids[b] < sample_begin || n_ids[b] > ids_stride) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_sample_select: n_ids outside [sample_begin, ids_stride]");
+      if (!(temperature[b] >= 0.0f) || std::isinf(temperature[b])) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_sample_select: a temperature is negative or not finite");
+      prm.inv_t[b] = temperature[b] > 0.0f ? 1.0f / temperature[b] : 0.0f;
+    }
+    std::vector<float> padded(size_t(B) * ldl, 0.0f);
+    for (int b = 0; b < B; ++b) std::memcpy(&padded[size_t(b) * ldl], logits + size_t(b) * V, size_t(V) * sizeof(float));
+    const int stride = ids_stride + 1;  // the kernel writes the token at ids[b][n_ids[b]]
+    std::vector<long long> rows(size_t(B) * stride, 0);
+    for (int b = 0; b < B; ++b)
+      for (int i = 0; i < n_ids[b]; ++i) rows[size_t(b) * stride + i] = ids[size_t(b) * ids_stride + i];
+    DevArr<float> dlog(padded.size(), padded.data());
+    DevArr<long long> dids(rows.size(), rows.data());
+    DevArr<int> dn(B, n_ids), dfin(B);
+    DevArr<wt::SamplePart> dpart(size_t(B) * wt::ts_chunks(V));
+    DevArr<wt::TsState> dstate(B);
+    DevArr<wt::SampleParams> dprm(1, &prm);
+    DevArr<double> dL(B);
+    DevArr<float> dM(B), dK(B);
+    hipchk(hipMemsetAsync(dfin.p, 0, size_t(B) * sizeof(int), h->impl->stream()), "memset");
+    if (timestamps) wt::launch_ts_state_init(dids.p, stride, dn.p, 0, sample_begin, V, beg, dstate.p, B, h->impl->stream());
+    for (int b0 = 0, b1 = 0; b0 < B; b0 = b1 + 1) {
+      b1 = b0;
+      while (b1 + 1 < B && n_ids[b1 + 1] == n_ids[b0]) ++b1;
+      wt::SampleArgs t;
+      t.logits = dlog.p + size_t(b0) * ldl; t.ldl = ldl; t.V = V; t.batch = b1 - b0 + 1;
+      t.eot = eot; t.beg = beg; t.max_initial = max_initial_timestamp;
+      t.n_gen = n_ids[b0] - sample_begin; t.part = dpart.p + size_t(b0) * wt::ts_chunks(V);
+      t.state = timestamps ? dstate.p + b0 : nullptr;
+      t.params = dprm.p; t.row0 = b0; t.rng_pos = pos;
+      t.ids = dids.p + size_t(b0) * stride; t.ids_stride = stride; t.pos = n_ids[b0] - 1; t.stop_at_eot = 1;
+      t.n_ids = dn.p + b0; t.finished = dfin.p + b0;
+      t.dbg_L = dL.p + b0; t.dbg_M = dM.p + b0; t.dbg_key = dK.p + b0;
+      wt::launch_sample_select(t, h->impl->stream());
+    }
+    h->impl->sync();
+    dids.to_host(rows.data());
+    for (int b = 0; b < B; ++b) token[b] = rows[size_t(b) * stride + n_ids[b]];
+    if (L) dL.to_host(L);
+    if (M) dM.to_host(M);
+    if (key) dK.to_host(key);
   });
 }
 

@@ -3,6 +3,7 @@
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
+#include <dlfcn.h>
 #include <unistd.h>
 
 #include <chrono>
@@ -870,7 +871,7 @@ void Engine::release() noexcept {
   bw_ = BeamWorkspace();  // (its device buffers are in allocations_)
   for (void* p : {static_cast<void*>(fw_.h_ids), static_cast<void*>(fw_.h_n), static_cast<void*>(fw_.h_fin),
                   static_cast<void*>(fw_.h_lp), static_cast<void*>(fw_.h_nosp), static_cast<void*>(fw_.h_sum),
-                  static_cast<void*>(fw_.h_count)})
+                  static_cast<void*>(fw_.h_count), static_cast<void*>(fw_.h_prm)})
     if (p) (void)hipHostFree(p);
   fw_ = FullWorkspace();
   for (void* p : {static_cast<void*>(h_lang_probs_), static_cast<void*>(h_lang_prob_), static_cast<void*>(h_lang_)})
@@ -2480,6 +2481,8 @@ void Engine::clear_last_scores() {
   last_token_logprob.clear();
   last_segment_score.clear();
   last_lp_stride = 0;
+  last_decode_info_valid = false;  // (nor a sampled one)
+  last_decode_info.clear();
 }
 
 // option timestamps outside full-length decoding: every decode call is refused (with max_positions set, the refusals
@@ -2493,6 +2496,46 @@ void Engine::check_timestamp_call() const {
     throw Error(kErrUnsupported, "scores: full-length greedy decoding only, set the option max_positions (32 .. n_text_ctx)");
   }
   if (skip_silence && !scores) throw Error(kErrUnsupported, "skip_silence: needs the option scores = 1");
+  if (sampling() && max_positions <= 0) {
+    throw Error(kErrUnsupported, "temperature: full-length decoding only, set the option max_positions (32 .. n_text_ctx)");
+  }
+  if (temperature_fallback && !scores) throw Error(kErrUnsupported, "temperature_fallback: needs the option scores = 1");
+  if (temperature_fallback && compression_ratio_threshold != 0 && !zlib_available()) {
+    throw Error(kErrUnsupported, "compression_ratio_threshold: libz.so.1 could not be loaded; set the threshold to 0 (off)");
+  }
+}
+
+// zlib through dlopen: no header and no link-time dependency a machine may lack
+namespace {
+struct Zlib {
+  unsigned long (*bound)(unsigned long) = nullptr;
+  int (*compress)(unsigned char*, unsigned long*, const unsigned char*, unsigned long) = nullptr;
+  Zlib() {
+    void* const lib = dlopen("libz.so.1", RTLD_NOW | RTLD_LOCAL);
+    if (!lib) return;
+    bound = reinterpret_cast<decltype(bound)>(dlsym(lib, "compressBound"));
+    compress = reinterpret_cast<decltype(compress)>(dlsym(lib, "compress"));
+    if (!bound || !compress) bound = nullptr, compress = nullptr;
+  }
+};
+const Zlib& zlib() {
+  static const Zlib z;  // loaded at first use
+  return z;
+}
+}  // namespace
+
+bool Engine::zlib_available() { return zlib().compress != nullptr; }
+
+double Engine::compression_ratio(const std::string& text) {
+  if (text.empty()) return 0.0;
+  const Zlib& z = zlib();
+  if (!z.compress) throw Error(kErrUnsupported, "compression ratio: libz.so.1 could not be loaded");
+  unsigned long n = z.bound(static_cast<unsigned long>(text.size()));
+  std::vector<unsigned char> out(n);
+  if (z.compress(out.data(), &n, reinterpret_cast<const unsigned char*>(text.data()), static_cast<unsigned long>(text.size())) != 0 || n == 0) {
+    throw Error(kErrDevice, "compression ratio: zlib's compress() failed");
+  }
+  return double(text.size()) / double(n);
 }
 
 void Engine::check_full_args(int batch, int ids_stride) const {
@@ -2566,7 +2609,7 @@ void Engine::ensure_full_workspace(int batch) {
     fw_.kv = static_cast<float*>(alloc(size_t(c.n_text_layer) * 2 * size_t(batch) * cap * d * sizeof(float)));
     fw_.kv_clips = batch;
   }
-  if ((timestamps || scores) && !fw_.ts_logits) {  // the logits of a step: the timestamp rules and the scores read whole rows
+  if ((timestamps || scores || sampling()) && !fw_.ts_logits) {  // the logits of a step: the timestamp rules and the scores read whole rows
     const size_t ldl = (size_t(c.n_vocab) + 3) & ~size_t(3);
     fw_.ts_ldl = int(ldl);
     fw_.ts_logits = static_cast<float*>(alloc(C * ldl * sizeof(float)));
@@ -2590,6 +2633,15 @@ void Engine::ensure_full_workspace(int batch) {
     if (!fw_.h_nosp) fw_.h_nosp = static_cast<float*>(pinned(C * sizeof(float)));
     if (!fw_.h_sum) fw_.h_sum = static_cast<double*>(pinned(C * sizeof(double)));
     if (!fw_.h_count) fw_.h_count = static_cast<int*>(pinned(C * sizeof(int)));
+  }
+  if (sampling()) {
+    if (!fw_.sm_part) fw_.sm_part = static_cast<SamplePart*>(alloc(C * size_t(ts_chunks(c.n_vocab)) * sizeof(SamplePart)));
+    if (!fw_.sm_prm) fw_.sm_prm = static_cast<SampleParams*>(alloc(sizeof(SampleParams)));
+    if (!fw_.h_prm) {
+      void* q = nullptr;
+      HIPCHK(hipHostMalloc(&q, sizeof(SampleParams), 0));
+      fw_.h_prm = static_cast<SampleParams*>(q);
+    }
   }
   if (fw_.h_fin) return;  // (allocated last)
   fw_.ids = static_cast<long long*>(alloc(C * (cap + 1) * sizeof(long long)));
@@ -2615,8 +2667,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   last_lang_valid = false;
   beam_scores_valid = false;
   last_segments_valid = false;
-  clear_last_scores();
-  const bool ts = timestamps != 0, sc = scores != 0;
+  clear_last_scores();  // (the decode info with them)
+  const bool ts = timestamps != 0, sc = scores != 0, smp = sampling();
   ensure_batch(batch);
   ensure_full_workspace(batch);  // (before any capture: nothing may be allocated inside one)
   Slot& slot = slots_[slot_idx];
@@ -2628,34 +2680,17 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   slot.pair_leader = -1;
   DecWorkspace& dw = dws_[slot.dec];
   hipStream_t const st = dec_stream_at(slot.dec);
-  for (int b = 0; b < batch; ++b) {
-    for (int i = 0; i < stride; ++i) fw_.h_ids[size_t(b) * stride + i] = i < n_prompt ? prompt[i] : 0;
-    fw_.h_n[b] = n_prompt;
-  }
   const int chunks = cross_chunks_for(batch);  // as decode_enqueue chooses them for a synchronous call of this size
   const bool absorbed = slot.absorbed;
   const int n_abs = abs_chunks_for(batch, 256);
   const int np_max = std::max(1, std::min(4, kDecRowsMax / batch));
   const int prompt_end = std::min(n_prompt, P);
 
-  HIPCHK(hipStreamWaitEvent(st, slot.enc_done, 0));
-  HIPCHK(hipEventRecord(slot.dec_begin, st));
-  HIPCHK(hipMemcpyAsync(fw_.ids, fw_.h_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dw.n_ids, fw_.h_n, size_t(batch) * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(dw.finished, 0, size_t(batch) * sizeof(int), st));
-  if (ts) {  // the carried state of the timestamp rules: nothing generated yet
-    launch_ts_state_init(fw_.ids, stride, nullptr, n_prompt, n_prompt, V, vocab_.token_beg, fw_.ts_state, batch, st);
-  }
-  if (sc) {  // the carried sums and counts of the scores: nothing generated yet
-    HIPCHK(hipMemsetAsync(fw_.sc_sum, 0, size_t(batch) * sizeof(double), st));
-    HIPCHK(hipMemsetAsync(fw_.sc_count, 0, size_t(batch) * sizeof(int), st));
-  }
-
   DecPass p;
   p.B = p.clips = batch; p.ids = fw_.ids; p.ids_stride = stride; p.self_kv = fw_.kv; p.self_cap = cap;
   p.absorbed = absorbed; p.n_abs = n_abs; p.chunks = chunks; p.e = slot.e_planes; p.cross_kv = slot.cross_kv;
   p.split = fc2_split(); p.dw = &dw; p.ldy = V;
-  if (ts || sc) p.Y = fw_.ts_logits, p.ldy = fw_.ts_ldl;  // the timestamp rules and the scores read the whole row
+  if (ts || sc || smp) p.Y = fw_.ts_logits, p.ldy = fw_.ts_ldl;  // the timestamp rules, the scores and the sampler read the whole row
   ScoreArgs sa;
   if (sc) {
     sa.logits = fw_.ts_logits; sa.ldl = fw_.ts_ldl; sa.V = V; sa.batch = batch; sa.part = fw_.sc_part;
@@ -2680,11 +2715,19 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
         launch_no_speech_prob(sa, vocab_.token_solm, fw_.sc_nosp, st);
       }
       if (logits) {
-        if (sc) {  // the partial sums of the allowed set, from the state BEFORE ts_select advances it
+        if (sc) {  // the partial sums of the allowed set, from the state BEFORE the selection advances it
           sa.state = ts ? fw_.ts_state : nullptr; sa.n_gen = last + 1 - n_prompt; sa.pos = last;
           launch_score_partial(sa, st);
         }
-        if (ts) {
+        if (smp) {  // a sample at the temperature the parameter block holds (0: the greedy step), in both modes
+          SampleArgs t;
+          t.logits = fw_.ts_logits; t.ldl = fw_.ts_ldl; t.V = V; t.batch = batch;
+          t.eot = vocab_.token_eot; t.beg = vocab_.token_beg; t.max_initial = int(max_initial_timestamp);
+          t.n_gen = last + 1 - n_prompt; t.params = fw_.sm_prm; t.part = fw_.sm_part; t.state = ts ? fw_.ts_state : nullptr;
+          t.ids = fw_.ids; t.ids_stride = stride; t.pos = last; t.stop_at_eot = int(stop_at_eot);
+          t.n_ids = dw.n_ids; t.finished = dw.finished;
+          launch_sample_select(t, st);
+        } else if (ts) {
           TsSelectArgs t;
           t.logits = fw_.ts_logits; t.ldl = fw_.ts_ldl; t.V = V; t.batch = batch;
           t.eot = vocab_.token_eot; t.beg = vocab_.token_beg; t.max_initial = int(max_initial_timestamp);
@@ -2703,49 +2746,147 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     return seg_steps;
   };
 
+  // One decoder chain over the slot's encoder output; the results come back in the pinned mirrors fw_.h_*.
+  // frozen (sampling only): clips that start with finished = 1 — accepted by an earlier attempt — so that the chain
+  // ends when the others end; their device rows are overwritten and their counts stay at zero.
   int steps = 0;
-  for (int lo = 0; lo < P; lo += 32) {
-    const int hi = std::min(P, lo + 32);
-    // (greedy's keys start with the slot, a beam key with -beam_size; a full-length key starts with kFullKey)
-    const std::vector<long long> key{kFullKey, slot_idx, batch, lo, P, n_prompt, chunks, long(stop_at_eot), fc2_ksplit,
-                                     absorbed ? 1 : 0, n_abs, slot.dec, ts ? 1 : 0, ts ? max_initial_timestamp : 0, sc ? 1 : 0};
-    auto it = use_graphs ? graphs_.find(key) : graphs_.end();
-    if (it != graphs_.end()) {
-      HIPCHK(hipGraphLaunch(it->second.exec, st));
-      steps += it->second.steps;
+  auto run_chain = [&](const std::vector<int>* frozen, bool first) {
+    for (int b = 0; b < batch; ++b) {
+      for (int i = 0; i < stride; ++i) fw_.h_ids[size_t(b) * stride + i] = i < n_prompt ? prompt[i] : 0;
+      fw_.h_n[b] = n_prompt;
+    }
+    HIPCHK(hipStreamWaitEvent(st, slot.enc_done, 0));
+    if (first) HIPCHK(hipEventRecord(slot.dec_begin, st));
+    HIPCHK(hipMemcpyAsync(fw_.ids, fw_.h_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dw.n_ids, fw_.h_n, size_t(batch) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (frozen) {
+      for (int b = 0; b < batch; ++b) fw_.h_fin[b] = (*frozen)[size_t(b)];
+      HIPCHK(hipMemcpyAsync(dw.finished, fw_.h_fin, size_t(batch) * sizeof(int), hipMemcpyHostToDevice, st));
     } else {
-      const int seg_steps = enqueue_segment(lo, hi);  // eager the first time, then captured for the next calls
-      steps += seg_steps;
-      if (use_graphs) {
-        try {
-          graphs_.emplace(key, GraphEntry{capture_graph(st, [&] { enqueue_segment(lo, hi); }), seg_steps});
-        } catch (const std::exception& e) {
-          (void)hipGetLastError();
-          use_graphs = 0;
-          std::fprintf(stderr, "[wt] full-length hipGraph capture failed (%s): continuing with eager launches\n", e.what());
+      HIPCHK(hipMemsetAsync(dw.finished, 0, size_t(batch) * sizeof(int), st));
+    }
+    if (smp) HIPCHK(hipMemcpyAsync(fw_.sm_prm, fw_.h_prm, sizeof(SampleParams), hipMemcpyHostToDevice, st));
+    if (ts) {  // the carried state of the timestamp rules: nothing generated yet
+      launch_ts_state_init(fw_.ids, stride, nullptr, n_prompt, n_prompt, V, vocab_.token_beg, fw_.ts_state, batch, st);
+    }
+    if (sc) {  // the carried sums and counts of the scores: nothing generated yet
+      HIPCHK(hipMemsetAsync(fw_.sc_sum, 0, size_t(batch) * sizeof(double), st));
+      HIPCHK(hipMemsetAsync(fw_.sc_count, 0, size_t(batch) * sizeof(int), st));
+    }
+    for (int lo = 0; lo < P; lo += 32) {
+      const int hi = std::min(P, lo + 32);
+      // (greedy's keys start with the slot, a beam key with -beam_size; a full-length key starts with kFullKey)
+      // (the sampling kernels are one entry; temperature, seed and attempt are data, never part of the key)
+      const std::vector<long long> key{kFullKey, slot_idx, batch, lo, P, n_prompt, chunks, long(stop_at_eot), fc2_ksplit,
+                                       absorbed ? 1 : 0, n_abs, slot.dec, ts ? 1 : 0, ts ? max_initial_timestamp : 0, sc ? 1 : 0,
+                                       smp ? 1 : 0};
+      auto it = use_graphs ? graphs_.find(key) : graphs_.end();
+      if (it != graphs_.end()) {
+        HIPCHK(hipGraphLaunch(it->second.exec, st));
+        steps += it->second.steps;
+      } else {
+        const int seg_steps = enqueue_segment(lo, hi);  // eager the first time, then captured for the next calls
+        steps += seg_steps;
+        if (use_graphs) {
+          try {
+            graphs_.emplace(key, GraphEntry{capture_graph(st, [&] { enqueue_segment(lo, hi); }), seg_steps});
+          } catch (const std::exception& e) {
+            (void)hipGetLastError();
+            use_graphs = 0;
+            std::fprintf(stderr, "[wt] full-length hipGraph capture failed (%s): continuing with eager launches\n", e.what());
+          }
         }
       }
+      if (hi == P) break;
+      if (stop_at_eot) {  // every clip finished: the remaining segments would change nothing
+        HIPCHK(hipMemcpyAsync(fw_.h_fin, dw.finished, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        bool all = true;
+        for (int b = 0; b < batch; ++b) all = all && fw_.h_fin[b] != 0;
+        if (all) break;
+      }
     }
-    if (hi == P) break;
-    if (stop_at_eot) {  // every clip finished: the remaining segments would change nothing
-      HIPCHK(hipMemcpyAsync(fw_.h_fin, dw.finished, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      bool all = true;
-      for (int b = 0; b < batch; ++b) all = all && fw_.h_fin[b] != 0;
-      if (all) break;
+    HIPCHK(hipMemcpyAsync(fw_.h_ids, fw_.ids, size_t(batch) * stride * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(fw_.h_n, dw.n_ids, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (sc) {  // the scores come down with the ids: no further synchronisation point
+      HIPCHK(hipMemcpyAsync(fw_.h_lp, fw_.sc_lp, size_t(batch) * stride * sizeof(float), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(fw_.h_sum, fw_.sc_sum, size_t(batch) * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(fw_.h_count, fw_.sc_count, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(fw_.h_nosp, fw_.sc_nosp, size_t(batch) * sizeof(float), hipMemcpyDeviceToHost, st));
     }
+    HIPCHK(hipEventRecord(slot.dec_done, st));
+    slot.steps = steps;  // (summed over the attempts)
+    finish_slot(slot_idx);  // waits; the encoder's non-finite flag, timings
+  };
+
+  if (!smp) {
+    run_chain(nullptr, true);
+  } else {
+    // Whisper's decode_with_fallback: the schedule's temperatures in turn, every attempt over the clips that still
+    // need one; the host keeps what a clip was accepted with and puts the merged result back into the mirrors
+    std::vector<long> temps{temperature};
+    if (temperature_fallback) {
+      for (long t = temperature + temperature_increment; t <= 1000; t += temperature_increment) temps.push_back(t);
+    }
+    std::vector<int> frozen(size_t(batch), 0);
+    std::vector<long long> m_ids(size_t(batch) * stride, 0);
+    std::vector<int> m_n(size_t(batch), 0), m_count(size_t(batch), 0);
+    std::vector<float> m_lp(sc ? size_t(batch) * stride : 0, 0.0f), m_nosp(size_t(batch), 0.0f);
+    std::vector<double> m_sum(size_t(batch), 0.0);
+    last_decode_info.assign(size_t(batch), ClipDecode{0, 0, 0, 0.0f});
+    for (size_t attempt = 0; attempt < temps.size(); ++attempt) {
+      SampleParams& prm = *fw_.h_prm;
+      const unsigned long long sd = static_cast<unsigned long long>(seed);
+      prm.seed_lo = unsigned(sd & 0xffffffffull), prm.seed_hi = unsigned(sd >> 32);
+      prm.attempt = unsigned(attempt), prm.clip_base = unsigned(clip_base);
+      const float T = float(temps[attempt]) / 1000.0f;
+      for (int b = 0; b < kSampleClipsMax; ++b) prm.inv_t[b] = temps[attempt] > 0 ? 1.0f / T : 0.0f;
+      run_chain(attempt == 0 ? nullptr : &frozen, attempt == 0);
+      bool again = false;
+      for (int b = 0; b < batch; ++b) {
+        if (frozen[size_t(b)]) continue;
+        std::copy(fw_.h_ids + size_t(b) * stride, fw_.h_ids + size_t(b + 1) * stride, m_ids.begin() + size_t(b) * stride);
+        m_n[size_t(b)] = fw_.h_n[b];
+        ClipDecode& info = last_decode_info[size_t(b)];
+        info.temperature_milli = int32_t(temps[attempt]);
+        info.attempts = int32_t(attempt) + 1;
+        info.needs_fallback = 0;
+        const int n_row = std::min(fw_.h_n[b], stride);
+        std::vector<int64_t> gen;  // the generated ids below eot: the clip's text
+        for (int i = n_prompt; i < n_row; ++i) {
+          if (fw_.h_ids[size_t(b) * stride + i] < vocab_.token_eot) gen.push_back(fw_.h_ids[size_t(b) * stride + i]);
+        }
+        const double ratio = zlib_available() ? compression_ratio(decode_tokens(vocab_, gen.data(), int(gen.size()), true, nullptr)) : 0.0;
+        info.compression_ratio = float(ratio);
+        if (sc) {
+          // every live clip generates at least one id (max_positions > the prompt): a count of 0 is a device-side error
+          if (fw_.h_count[b] < 1) throw Error(kErrDevice, "scores: a clip came back with no generated id counted");
+          std::copy(fw_.h_lp + size_t(b) * stride, fw_.h_lp + size_t(b + 1) * stride, m_lp.begin() + size_t(b) * stride);
+          m_sum[size_t(b)] = fw_.h_sum[b], m_count[size_t(b)] = fw_.h_count[b], m_nosp[size_t(b)] = fw_.h_nosp[b];
+        }
+        if (temperature_fallback) {  // (needs scores: check_timestamp_call)
+          const double avg = double(float(fw_.h_sum[b] / double(fw_.h_count[b])));
+          const double lp_thr = double(logprob_threshold) / 1000.0;
+          bool need = avg < lp_thr;
+          if (compression_ratio_threshold != 0 && ratio > double(compression_ratio_threshold) / 1000.0) need = true;
+          if (double(fw_.h_nosp[b]) > double(no_speech_threshold) / 1000.0 && avg < lp_thr) need = false;  // silence
+          info.needs_fallback = need ? 1 : 0;
+        }
+        if (info.needs_fallback && attempt + 1 < temps.size()) again = true;
+        else frozen[size_t(b)] = 1;  // accepted, or the schedule is exhausted: the last result is kept
+      }
+      if (!again) break;
+    }
+    std::copy(m_ids.begin(), m_ids.end(), fw_.h_ids);
+    std::copy(m_n.begin(), m_n.end(), fw_.h_n);
+    if (sc) {
+      std::copy(m_lp.begin(), m_lp.end(), fw_.h_lp);
+      std::copy(m_sum.begin(), m_sum.end(), fw_.h_sum);
+      std::copy(m_count.begin(), m_count.end(), fw_.h_count);
+      std::copy(m_nosp.begin(), m_nosp.end(), fw_.h_nosp);
+    }
+    last_decode_info_valid = true;
   }
-  HIPCHK(hipMemcpyAsync(fw_.h_ids, fw_.ids, size_t(batch) * stride * sizeof(long long), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(fw_.h_n, dw.n_ids, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
-  if (sc) {  // the scores come down with the ids: no further synchronisation point
-    HIPCHK(hipMemcpyAsync(fw_.h_lp, fw_.sc_lp, size_t(batch) * stride * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(fw_.h_sum, fw_.sc_sum, size_t(batch) * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(fw_.h_count, fw_.sc_count, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(fw_.h_nosp, fw_.sc_nosp, size_t(batch) * sizeof(float), hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(hipEventRecord(slot.dec_done, st));
-  slot.steps = steps;
-  finish_slot(slot_idx);  // waits; the encoder's non-finite flag, timings
   if (sc) {
     last_scores.assign(size_t(batch), ClipScore{});
     last_lp_stride = stride;

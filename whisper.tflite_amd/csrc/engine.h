@@ -21,6 +21,8 @@ struct TsState;
 
 struct BeamPart;  // kernels.h
 struct ScorePart;
+struct SamplePart;
+struct SampleParams;
 
 // option scores: one clip of the last full-length decode (wt_clip_score mirrors it)
 struct ClipScore {
@@ -217,6 +219,29 @@ class Engine {
   std::vector<float> last_segment_score;
   bool last_scores_valid = false;
   void clear_last_scores();  // every decode that forms no scores calls it: the getters never report an earlier call
+  // Temperature sampling and fall-back.  temperature (thousandths) > 0 or temperature_fallback = 1:
+  // decode_full selects with sample_partial + sample_select (k_sample.hip) in place of select_token / ts_select; the
+  // parameters of an attempt (1 / T per clip, seed, attempt, clip_base) reach the kernels through a block in device
+  // memory, so the segment graphs serve every attempt.  temperature_fallback = 1 (needs scores): Whisper's
+  // decode_with_fallback over the schedule temperature, + temperature_increment, ... <= 1000; a clip is decoded again
+  // while compression_ratio > compression_ratio_threshold / 1000 (0 = off) or avg_logprob < logprob_threshold / 1000,
+  // unless it is silence (no_speech_prob > no_speech_threshold / 1000 and avg_logprob < logprob_threshold / 1000).
+  // Scope and refusals: those of max_positions (check_timestamp_call, check_full_call).
+  long temperature = 0, temperature_fallback = 0, temperature_increment = 200, compression_ratio_threshold = 2400;
+  long seed = 0;
+  long clip_base = 0;  // index of the call's first clip in the Philox counter (wt_transcribe_long_pcm: the window index)
+  bool sampling() const { return temperature > 0 || temperature_fallback != 0; }
+  struct ClipDecode {  // (wt_clip_decode)
+    int32_t temperature_milli, attempts, needs_fallback;
+    float compression_ratio;
+  };
+  // per clip of the last synchronous decode that sampled or ran fall-back; cleared by every decode that did neither
+  std::vector<ClipDecode> last_decode_info;
+  bool last_decode_info_valid = false;
+  // bytes of text / bytes of zlib's compress() of it at the default level, 0 for empty text; zlib is loaded at first
+  // use (libz.so.1): kErrUnsupported when it cannot be
+  static bool zlib_available();
+  static double compression_ratio(const std::string& text);
   long gemm_variant = -1;  // -1 = plane GEMM (per-contraction fall-back to 13/16); 0 = fp32 MFMA, 13 / 16 = three bf16 planes
   // 1 = bf16 STORAGE mode (BASELINE configs[3]): bf16 weights, activations and both KV caches, fp32 accumulation,
   // fp32 residual stream; k_gemm_bf16.hip and the BF variants of the attention / decoder kernels.  Set through
@@ -372,6 +397,10 @@ class Engine {
     float *sc_lp = nullptr, *sc_nosp = nullptr, *h_lp = nullptr, *h_nosp = nullptr;
     double *sc_sum = nullptr, *h_sum = nullptr;
     int *sc_count = nullptr, *h_count = nullptr;
+    // sampling (allocated on the first such call; it shares ts_logits): the per-chunk records [64][chunks], the
+    // parameter block and its pinned mirror
+    SamplePart* sm_part = nullptr;
+    SampleParams *sm_prm = nullptr, *h_prm = nullptr;
   } fw_;
   void ensure_full_workspace(int batch);
   static constexpr long long kFullKey = -1000;  // first entry of a full-length segment's graph key

@@ -424,6 +424,40 @@ struct TsSelectArgs {
 };
 void launch_ts_select(const TsSelectArgs& a, hipStream_t s);  // ts_partial + ts_select; throws kErrInvalidArg
 
+// -------------------------------------------------------------- sampling ---
+// k_sample.hip (option temperature): the selection step at a temperature.  The token is the argmax
+// over the allowed ids of k_i = z_i * inv_t + g_i (ties: the larger id), g_i = -log(-log u_i), u_i from Philox4x32-10
+// under the counter (i >> 2, rng_pos, clip_base + row0 + b, attempt) and the key (seed_lo, seed_hi); inv_t = 0: k_i =
+// z_i, the step of select_token / ts_select.  The allowed set is the whole vocabulary (state == nullptr) or what the
+// timestamp rules leave, rule 5 decided on the untempered logits exactly as ts_select decides it.
+constexpr int kSampleClipsMax = 64;  // clips of one synchronous call
+struct SampleParams {                // device memory, written ahead of a chain: nothing here is a kernel argument
+  unsigned seed_lo, seed_hi, attempt, clip_base;
+  float inv_t[kSampleClipsMax];      // 1 / T per clip, 0 = greedy
+};
+struct SamplePart {                  // one (clip, chunk); keys as TsPart's
+  unsigned long long pkey_text, pkey_ts;  // best perturbed key over the allowed ids below beg / the allowed timestamps
+  unsigned long long key_text, key_ts;    // ts_partial's record: the same bits
+  float m, s;
+};
+struct SampleArgs {
+  const float* logits = nullptr;  // as TsSelectArgs
+  int ldl = 0, V = 0, batch = 0;
+  int eot = 0, beg = 0, max_initial = -1, n_gen = 0;
+  const SampleParams* params = nullptr;
+  int row0 = 0;                   // clip b of this launch is clip row0 + b of the parameter block
+  int rng_pos = -1;               // the counter's position word; -1 = pos
+  SamplePart* part = nullptr;     // [batch][ts_chunks(V)]
+  TsState* state = nullptr;       // [batch], read and advanced; nullptr = plain mode
+  long long* ids = nullptr;
+  int ids_stride = 0, pos = 0, stop_at_eot = 1;
+  int *n_ids = nullptr, *finished = nullptr;
+  double* dbg_L = nullptr;        // optional [batch], as TsSelectArgs
+  float* dbg_M = nullptr;
+  float* dbg_key = nullptr;       // optional [batch]: the winning key k
+};
+void launch_sample_select(const SampleArgs& a, hipStream_t s);  // sample_partial + sample_select; throws kErrInvalidArg
+
 // ---------------------------------------------------------------- scores ---
 // k_scores.hip (option scores): the log-probability of the id a greedy step chose,
 // lp = z[tok] - logsumexp(z[i] : i allowed at that step), and a clip's no-speech probability.  The allowed set is the

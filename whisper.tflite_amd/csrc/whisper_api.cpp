@@ -100,6 +100,25 @@ std::vector<ClipScore> clip_scores(const wt_engine* h) {
 std::vector<ClipScore> EncDec::scores() const { return clip_scores(handle_); }
 std::vector<ClipScore> Monolith::scores() const { return clip_scores(handle_); }
 
+namespace {
+std::vector<ClipDecode> clip_decodes(const wt_engine* h) {
+  std::vector<ClipDecode> out;
+  const int n = wt_last_decode_info(h, nullptr, 0);
+  if (n <= 0) return out;
+  std::vector<wt_clip_decode> raw(static_cast<size_t>(n));
+  wt_last_decode_info(h, raw.data(), n);
+  for (const wt_clip_decode& r : raw) {
+    ClipDecode d;
+    d.temperature = float(r.temperature_milli) / 1000.0f, d.attempts = r.attempts;
+    d.needs_fallback = r.needs_fallback != 0, d.compression_ratio = r.compression_ratio;
+    out.push_back(d);
+  }
+  return out;
+}
+}  // namespace
+std::vector<ClipDecode> EncDec::decode_info() const { return clip_decodes(handle_); }
+std::vector<ClipDecode> Monolith::decode_info() const { return clip_decodes(handle_); }
+
 std::vector<EncDec::Segment> EncDec::segments() const {
   std::vector<Segment> out;
   const int n = wt_last_segments(handle_, nullptr, 0);
