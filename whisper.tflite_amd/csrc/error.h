@@ -1,6 +1,6 @@
 // Failure type shared by the engine and the kernel launchers: carries the wt_status code the C ABI
 // reports (include/wt_capi.h).  Nothing below the C ABI calls abort()/exit(): a shape the kernels do
-// not support is an Error, which capi.cpp's guarded() turns into a status code + wt_last_error().
+// not support is an Error, which guarded() (capi_internal.h) turns into a status code + wt_last_error().
 #pragma once
 #include <stdexcept>
 #include <string>
