@@ -138,6 +138,21 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value);
  * (whisper.cpp:327-339) with n (1..8) caller ids; n = 0 restores the default.  Needed for
  * test-sized vocabularies that do not contain the multilingual special ids. */
 int wt_engine_set_prompt(wt_engine* h, const int64_t* ids, int n);
+/* A context in front of the prompt: Whisper's initial_prompt / condition_on_previous_text.  With
+ * n (1..4096) ids set, every full-length decode ("max_positions") feeds [<|startofprev|>] + the LAST n_text_ctx / 2 - 1
+ * of them + the prompt (the default one, the "timestamps" one, or wt_engine_set_prompt's), the same for every clip of the
+ * call; generated ids, the timestamp rules and the scores all start behind the whole of it, and no_speech_prob is read at
+ * sot's position.  n = 0 clears the context; the read-only option "context_ids" tells how many ids are kept.  An id outside
+ * the vocabulary or n > 4096 is WT_ERR_INVALID_ARG, a vocabulary without <|startofprev|> (token_prev >= n_vocab) or a
+ * Monolith engine WT_ERR_UNSUPPORTED.  It works with and without "timestamps", "scores", "temperature" and
+ * "temperature_fallback".  With a context set a decode call is WT_ERR_UNSUPPORTED without "max_positions" and wherever
+ * "max_positions" refuses one (the calls with rows of WT_MAX_IDS ids, the pipeline, beam_size > 1, the bf16 storage mode,
+ * language = WT_LANGUAGE_AUTO, the forced-ids tap), and WT_ERR_INVALID_ARG when the fed prompt leaves no position to
+ * generate (its length >= "max_positions"); the engine stays usable after each.  Such calls run their launches eagerly:
+ * no decoder graph is captured for them ("graphs_cached", read-only, does not grow with the context lengths seen).
+ * Option "prompt_group": 0 = the prompt passes take 128 / batch positions each (default), 1 = one position each; it
+ * changes nothing without a context. */
+int wt_engine_set_context(wt_engine* h, const int64_t* ids, int n);
 
 /* ---- single-clip entry points (the reference's two virtuals) ----------------------------
  * Replace Engine::transcribe(std::vector<float>&) (whisper.h:160, whisper.cpp:752-769; JNI
@@ -302,6 +317,28 @@ typedef struct wt_clip_decode { int32_t temperature_milli, attempts, needs_fallb
  * decode did neither (as wt_last_scores) */
 int wt_last_decode_info(const wt_engine* h, wt_clip_decode* out, int cap);
 
+/* Seeking long-audio transcription (option "seek" = 1 together with "timestamps" = 1 and "max_positions", else a decode
+ * call is WT_ERR_UNSUPPORTED).  wt_transcribe_long_pcm then decodes one window at a time as Whisper's
+ * transcribe() does: window w is pcm[seek : seek + 480000) zero-padded, decoded as one clip (all decode options apply; its
+ * clip index in the sampling counter is w) behind the context, cut into segments by wt_vocab_seek_step, and the next
+ * window starts advance_samples later: at the last closed timestamp, or at the window's end.  The kept ids (those of the
+ * kept segments, timestamps included) are the window's line of text and are appended to the context of the next window;
+ * "condition_on_previous_text" = 0 (default 1), or a window whose kept result was decoded above temperature 0.5, empties
+ * the context instead.  A window "skip_silence" blanked keeps nothing and advances by the whole window.  The caller's
+ * wt_engine_set_context ids seed the first window and are the engine's context again after the call.  The log-mel of a
+ * window is the front end's on that slice of PCM, as for any clip.
+ * After such a call wt_last_segments holds the kept segments (clip = w, times in the file: seek / 16 ms + tick x 20 ms,
+ * ids[id_begin .. id_begin + id_count) of the window's id row, the segment's timestamps included), wt_last_scores,
+ * wt_last_token_logprobs and wt_last_decode_info one entry per window, wt_last_segment_scores the mean over each
+ * segment's ids below EOT, and wt_last_windows one record per window. */
+typedef struct wt_window {
+  int64_t seek_sample;
+  int32_t advance_samples, n_context, n_prompt, n_kept_ids, skipped, temperature_milli;
+} wt_window;
+/* returns the window count (at most cap written), or -WT_ERR_INVALID_ARG when the last synchronous decode was not a
+ * seeking one */
+int wt_last_windows(const wt_engine* h, wt_window* out, int cap);
+
 /* Per-kernel-class device time of the encoder phase of the last batch call: HIP event pairs
  * recorded on the engine's stream around every launch of the class.  flops / bytes are the
  * ALGORITHMIC work of those launches (2*M*N*K per GEMM with the true K, 4*B*H*T*T*64 per
@@ -350,6 +387,18 @@ int wt_vocab_decode(const wt_vocab* v, const int64_t* ids, int n, int omit_speci
 /* the segments (see wt_last_segments; clip = 0) of one id row of n ids whose first sample_begin are the prompt; no GPU.
  * Returns the segment count (at most cap written), or -WT_ERR_INVALID_ARG. */
 int wt_vocab_segments(const wt_vocab* v, const int64_t* ids, int n, int sample_begin, wt_segment* out, int cap);
+/* Whisper's seek rule on the n ids g a window generated before its first EOT; no GPU.  ts(i) = g[i] >= token_beg,
+ * tick(id) = id - token_beg clamped to [0, win_ticks]; seg_ticks (<= win_ticks) = the ticks of audio the window holds.
+ * With pairs of consecutive timestamps the row is cut at the second of each pair, and at n when it ends in a single
+ * timestamp; every slice is a segment from the tick of its first id to the tick of its last, *advance_ticks = the tick of
+ * the id before the last cut (seg_ticks when the row ends in a single timestamp), and ids behind the last cut belong to
+ * no segment.  Without a pair the whole row is one segment from 0 to the last timestamp's tick, or to seg_ticks with
+ * open = 1 when there is none or it is tick 0, and *advance_ticks = seg_ticks.  A segment with no id below EOT or with
+ * t0 == t1 is dropped; an advance of 0 becomes seg_ticks.  Segments: clip = 0, times = tick x 20 ms, g[id_begin ..
+ * id_begin + id_count) the slice, timestamps included.  Returns the segment count (at most cap written), or
+ * -WT_ERR_INVALID_ARG. */
+int wt_vocab_seek_step(const wt_vocab* v, const int64_t* g, int n, int win_ticks, int seg_ticks, wt_segment* out, int cap,
+                       int32_t* advance_ticks);
 
 /* ---- the log-mel front end as a free function ---------------------------------------------
  * Replaces whisper::log_mel_spectrogram (whisper.h:123, whisper.cpp:109-216) for callers that hold a

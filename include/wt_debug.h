@@ -106,6 +106,12 @@ int wt_dbg_self_attention(wt_engine* h, int batch, int heads, int cap, int pos, 
  * pos >= cap, cap > 448 and a batch or head count below 1 are WT_ERR_INVALID_ARG, before anything is launched. */
 int wt_dbg_self_attention_long(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
                                float* vcache, float* out);
+/* self_attention_prefill (k_attention.hip, wt_engine_set_context): npos >= 1 new positions pos .. pos + npos - 1 against
+ * caches [B][cap][d], cap <= 448; qkv [npos * B][3d] and out [npos * B][d], rows p * B + b; the caches come back with rows
+ * pos .. pos + npos - 1 appended and nothing else changed.  pos < 0, npos < 1, pos + npos > cap, cap > 448,
+ * npos * batch > 128 and a batch or head count below 1 are WT_ERR_INVALID_ARG, before anything is launched. */
+int wt_dbg_self_attention_prefill(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
+                                  float* kcache, float* vcache, float* out);
 /* ts_partial + ts_select (k_timestamps.hip, option "timestamps"): one step of Whisper's timestamp
  * rules per row.  logits [B][V]; row b of ids [B][ids_stride] holds n_ids[b] ids, the first sample_begin of them the
  * prompt, and the step decides the id that follows them: token[b].  L [B] (optional) = rule 5's logsumexp of the allowed

@@ -39,12 +39,12 @@ STATUS_NAMES = {0: "WT_OK", 1: "WT_ERR_INVALID_ARG", 2: "WT_ERR_IO", 3: "WT_ERR_
 CAPI_SYMBOLS = [
     "wt_device_alloc", "wt_device_free", "wt_device_upload", "wt_device_download", "wt_device_synchronize",
     "wt_engine_create", "wt_engine_destroy", "wt_last_error", "wt_engine_dims",
-    "wt_engine_set_option", "wt_engine_get_option", "wt_engine_set_prompt", "wt_transcribe_pcm", "wt_transcribe_long_pcm", "wt_transcribe_file",
+    "wt_engine_set_option", "wt_engine_get_option", "wt_engine_set_prompt", "wt_engine_set_context", "wt_transcribe_pcm", "wt_transcribe_long_pcm", "wt_transcribe_file",
     "wt_logmel_batch", "wt_logmel_batch_dev", "wt_encdec_tokens_batch",
     "wt_encdec_tokens_batch_dev", "wt_transcribe_tokens_batch_dev", "wt_pipeline_submit_dev", "wt_pipeline_submit_pcm_dev", "wt_pipeline_collect",
     "wt_encdec_debug_batch",
     "wt_encdec_tokens_full_batch", "wt_encdec_tokens_full_batch_dev", "wt_transcribe_tokens_full_batch_dev",
-    "wt_last_segments", "wt_last_segment_text", "wt_vocab_segments",
+    "wt_last_segments", "wt_last_segment_text", "wt_vocab_segments", "wt_vocab_seek_step", "wt_last_windows",
     "wt_last_scores", "wt_last_token_logprobs", "wt_last_segment_scores", "wt_last_decode_info",
     "wt_language_count", "wt_detect_language_batch", "wt_detect_language_batch_dev", "wt_detect_language_pcm", "wt_last_languages",
     "wt_last_timings", "wt_last_beam_scores", "wt_last_kernel_stats", "wt_decode_text", "wt_language_id", "wt_lang_code", "wt_wav_read_legacy",
@@ -60,6 +60,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_self_attention_long",
+    "wt_dbg_self_attention_prefill",
     "wt_dbg_timestamp_select", "wt_dbg_token_scores", "wt_dbg_sample_select",
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
     "wt_dbg_pcm_to_planes",
@@ -117,6 +118,7 @@ def lib() -> ctypes.CDLL:
         L.wt_engine_set_option.argtypes = [c_void_p, c_char_p, c_long]
         L.wt_engine_get_option.argtypes = [c_void_p, c_char_p, POINTER(c_long)]
         L.wt_engine_set_prompt.argtypes = [c_void_p, ip64, c_int]
+        L.wt_engine_set_context.argtypes = [c_void_p, ip64, c_int]
         L.wt_transcribe_pcm.argtypes = [c_void_p, fp, c_size_t, c_char_p, c_size_t, POINTER(c_size_t)]
         L.wt_transcribe_long_pcm.argtypes = [c_void_p, fp, c_size_t, c_char_p, c_size_t, POINTER(c_size_t)]
         L.wt_transcribe_file.argtypes = [c_void_p, c_char_p, c_char_p, c_size_t, POINTER(c_size_t)]
@@ -210,7 +212,10 @@ def lib() -> ctypes.CDLL:
         L.wt_encdec_tokens_full_batch_dev.argtypes = [c_void_p, c_void_p, c_int, ip64, c_int, ip32]
         L.wt_transcribe_tokens_full_batch_dev.argtypes = [c_void_p, c_void_p, c_int, ip64, c_int, ip32]
         L.wt_dbg_self_attention_long.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp]
+        L.wt_dbg_self_attention_prefill.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp]
         L.wt_last_segments.argtypes = [c_void_p, c_void_p, c_int]
+        L.wt_last_windows.argtypes = [c_void_p, c_void_p, c_int]
+        L.wt_vocab_seek_step.argtypes = [c_void_p, ip64, c_int, c_int, c_int, c_void_p, c_int, POINTER(c_int32)]
         L.wt_last_segment_text.argtypes = [c_void_p, c_int, c_char_p, c_size_t, POINTER(c_size_t)]
         L.wt_vocab_segments.argtypes = [c_void_p, ip64, c_int, c_int, c_void_p, c_int]
         L.wt_dbg_timestamp_select.argtypes = [c_void_p, c_int, c_int, fp, ip64, c_int, ip32, c_int, c_int, c_int, c_int,
@@ -317,6 +322,14 @@ DECODE_DTYPE = np.dtype([("temperature_milli", np.int32), ("attempts", np.int32)
                          ("compression_ratio", np.float32)])
 
 
+# one window of a seeking transcribe_long (wt_window): where it started in the file, how far the
+# next one lies, the context and prompt ids it was decoded behind, the ids kept from it, whether skip_silence blanked it
+# and the temperature its kept result was decoded at
+WINDOW_DTYPE = np.dtype([("seek_sample", np.int64), ("advance_samples", np.int32), ("n_context", np.int32),
+                         ("n_prompt", np.int32), ("n_kept_ids", np.int32), ("skipped", np.int32),
+                         ("temperature_milli", np.int32)], align=True)
+
+
 def _segments(call):
     n = call(None, 0)
     if n < 0:
@@ -391,6 +404,16 @@ class Vocab:
         return _segments(lambda out, cap: lib().wt_vocab_segments(self._v, ids.ctypes.data_as(POINTER(c_int64)), ids.size,
                                                                   int(sample_begin), out, cap))
 
+    def seek_step(self, g, win_ticks: int, seg_ticks: int):
+        """Whisper's seek rule (wt_vocab_seek_step) on the ids g a window generated before its first
+        EOT: (SEGMENT_DTYPE records with clip = 0, times = tick x 20 ms and g[id_begin : id_begin + id_count] the slice,
+        timestamps included; advance in ticks)."""
+        g = np.ascontiguousarray(g, dtype=np.int64).reshape(-1)
+        adv = c_int32(0)
+        segs = _segments(lambda out, cap: lib().wt_vocab_seek_step(self._v, g.ctypes.data_as(POINTER(c_int64)), g.size,
+                                                                   int(win_ticks), int(seg_ticks), out, cap, byref(adv)))
+        return segs, adv.value
+
 
 def log_mel_spectrogram(samples, filters, device_id: int = 0) -> np.ndarray:
     """Mirror of the free function ``whisper::log_mel_spectrogram`` (whisper.h:123): [n_mel][n_samples // 160]."""
@@ -458,6 +481,12 @@ class Engine:
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
         self._check(lib().wt_engine_set_prompt(self._h, ids.ctypes.data_as(POINTER(c_int64)), ids.size))
 
+    def set_context(self, ids) -> None:
+        """Ids fed in front of the prompt behind <|startofprev|> by every full-length decode (Whisper's initial_prompt;
+        the engine keeps the last n_text_ctx / 2 - 1, option context_ids); an empty list clears the context."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        self._check(lib().wt_engine_set_context(self._h, ids.ctypes.data_as(POINTER(c_int64)), ids.size))
+
     # -- shapes ----------------------------------------------------------------------
     @property
     def mel_shape(self):
@@ -480,7 +509,8 @@ class Engine:
         return buf.raw[: n.value].decode("utf-8", errors="replace")
 
     def transcribe_long(self, samples) -> str:
-        """Long audio: consecutive 30 s windows, batched; per-window texts joined with '\\n'."""
+        """Long audio: consecutive 30 s windows, batched; per-window texts joined with '\\n'.  Option seek = 1: one window
+        at a time, each starting at the last closed timestamp of the one before."""
         pcm = _f32(samples).reshape(-1)
         buf = ctypes.create_string_buffer(1 << 20)
         n = c_size_t(0)
@@ -614,6 +644,17 @@ class Engine:
             lib().wt_last_segment_scores(self._h, _fp(sc), n)
             out.append(sc)
         return out[0] if len(out) == 1 else tuple(out)
+
+    def last_windows(self) -> np.ndarray:
+        """WINDOW_DTYPE records, one per window, of the last synchronous decode when that was a transcribe_long with
+        seek = 1."""
+        n = lib().wt_last_windows(self._h, None, 0)
+        if n < 0:
+            raise WtError(-n, "no windows: the last synchronous decode was not a seeking transcribe_long")
+        out = np.zeros(n, WINDOW_DTYPE)
+        if n:
+            lib().wt_last_windows(self._h, out.ctypes.data_as(c_void_p), n)
+        return out
 
     # -- decode confidence (options scores + max_positions, DESIGN.md section 15) ----
     def last_scores(self) -> np.ndarray:
@@ -996,6 +1037,16 @@ class Engine:
         B, cap, d = kcache.shape
         out = np.zeros((B, d), np.float32)
         self._check(lib().wt_dbg_self_attention_long(self._h, B, d // 64, cap, pos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
+        return out, kcache, vcache
+
+    def dbg_self_attention_prefill(self, qkv, kcache, vcache, pos, npos):
+        """self_attention_prefill: npos new positions pos .. pos + npos - 1 against caches [B][cap][d] (cap <= 448,
+        npos * B <= 128), qkv [npos * B][3d] with rows p * B + b; returns (out [npos * B][d], kcache, vcache) with those
+        rows appended."""
+        qkv, kcache, vcache = _f32(qkv), _f32(kcache).copy(), _f32(vcache).copy()
+        B, cap, d = kcache.shape
+        out = np.zeros((npos * B, d), np.float32)
+        self._check(lib().wt_dbg_self_attention_prefill(self._h, B, d // 64, cap, pos, npos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
         return out, kcache, vcache
 
     # beam search (k_beam.hip).  The per-clip state is a dict of the engine's arrays (beam_state()), updated in place.

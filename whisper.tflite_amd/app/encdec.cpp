@@ -4,6 +4,8 @@
 // "language: <code> (p=...)" per 30 s window before it).  The reference pulls
 // in the 11 kLoC CLI11 header for three required options; a minimal parser keeps the same
 // flags (and --flag=value spelling) and exit status on a usage error.
+#include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,13 +40,18 @@ void usage(const char* argv0) {
             << "  --seed N        the sampler's 64-bit seed (default 0): same audio, options and seed, same text\n"
             << "  --fallback      with --scores: Whisper's temperature fall-back, T, T + 0.2, ... 1.0 per window, and one\n"
             << "                  line per window with the temperature kept, the attempts and the compression ratio\n"
-            << "  --compression-ratio-threshold X  with --fallback: decode again above this ratio (default 2.4, 0 = off)\n";
+            << "  --compression-ratio-threshold X  with --fallback: decode again above this ratio (default 2.4, 0 = off)\n"
+            << "  --seek          with --long --timestamps: every window starts at the last closed timestamp of the one\n"
+            << "                  before and is decoded behind the text kept so far (Whisper's transcribe loop)\n"
+            << "  --no-condition  with --seek: do not feed the previous windows' text to the next (condition_on_previous_text = 0)\n"
+            << "  --context-ids 1,2,3  with --max-positions: token ids fed in front of the prompt (Whisper's initial_prompt)\n";
 }
 }  // namespace
 
 int main(int argc, char* argv[]) {
-  std::string model_prefix, vocab, input, lang, beam, max_positions, temperature, seed, cr_threshold;
-  bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false;
+  std::string model_prefix, vocab, input, lang, beam, max_positions, temperature, seed, cr_threshold, context_ids;
+  bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
+       no_condition = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], v;
     if (a == "-h" || a == "--help") {
@@ -75,6 +82,14 @@ int main(int argc, char* argv[]) {
       fallback = true;
       continue;
     }
+    if (a == "--seek") {
+      seek = true;
+      continue;
+    }
+    if (a == "--no-condition") {
+      no_condition = true;
+      continue;
+    }
     const size_t eq = a.find('=');
     if (eq != std::string::npos) {
       v = a.substr(eq + 1);
@@ -94,6 +109,7 @@ int main(int argc, char* argv[]) {
     else if (a == "--temperature") temperature = v;
     else if (a == "--seed") seed = v;
     else if (a == "--compression-ratio-threshold") cr_threshold = v;
+    else if (a == "--context-ids") context_ids = v;
     else {
       std::cerr << "The following argument was not expected: " << a << "\n";
       usage(argv[0]);
@@ -205,6 +221,52 @@ int main(int argc, char* argv[]) {
     }
     if (fallback && wt_engine_set_option(encdec.handle(), "temperature_fallback", 1) != WT_OK) {
       std::cerr << "--fallback: " << wt_last_error(encdec.handle()) << "\n";
+      return 105;
+    }
+  }
+  if (!context_ids.empty()) {
+    if (max_positions.empty()) {
+      std::cerr << "--context-ids requires --max-positions\n";
+      return 105;
+    }
+    std::vector<int64_t> ids;
+    const char* p = context_ids.c_str();
+    bool ok = true;
+    while (ok) {
+      char* end = nullptr;
+      const long long id = std::strtoll(p, &end, 10);
+      ok = end != p && id >= 0;
+      if (!ok) break;
+      ids.push_back(id);
+      if (!*end) break;
+      ok = *end == ',';
+      p = end + 1;
+    }
+    if (!ok) {
+      std::cerr << "--context-ids: expected token ids separated by commas, got " << context_ids << "\n";
+      return 105;
+    }
+    if (ids.size() > 4096) {
+      std::cerr << "--context-ids: at most 4096 ids, got " << ids.size() << "\n";
+      return 105;
+    }
+    if (wt_engine_set_context(encdec.handle(), ids.data(), int(ids.size())) != WT_OK) {
+      std::cerr << "--context-ids: " << wt_last_error(encdec.handle()) << "\n";
+      return 105;
+    }
+  }
+  if (seek || no_condition) {
+    if (no_condition && !seek) {
+      std::cerr << "--no-condition requires --seek\n";
+      return 105;
+    }
+    if (!long_audio || !timestamps) {
+      std::cerr << "--seek requires --long --timestamps\n";
+      return 105;
+    }
+    if (wt_engine_set_option(encdec.handle(), "seek", 1) != WT_OK ||
+        wt_engine_set_option(encdec.handle(), "condition_on_previous_text", no_condition ? 0 : 1) != WT_OK) {
+      std::cerr << "--seek: " << wt_last_error(encdec.handle()) << "\n";
       return 105;
     }
   }

@@ -16,6 +16,7 @@
 
 #include "capi_internal.h"
 #include "kernels.h"
+#include "longform.h"
 #include "tflite_extract.h"
 #include "weights_gen.h"
 
@@ -221,6 +222,17 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
   } else if (k == "max_initial_timestamp") {
     if (value < -1 || value > 1500) return fail(h, WT_ERR_INVALID_ARG, "max_initial_timestamp must be in [-1, 1500] (ticks of 20 ms, -1 = no limit)");
     e.max_initial_timestamp = value;
+  } else if (k == "prompt_group") {
+    // prompt passes behind a context: 0 = as many positions as a pass takes, 1 = one position each
+    if (value != 0 && value != 1) return fail(h, WT_ERR_INVALID_ARG, "prompt_group must be 0 (grouped) or 1 (one position per pass)");
+    e.prompt_group = value;
+  } else if (k == "seek") {
+    // seeking long-audio transcription: wt_transcribe_long_pcm follows the timestamps
+    if (value != 0 && value != 1) return fail(h, WT_ERR_INVALID_ARG, "seek must be 0 or 1");
+    e.seek = value;
+  } else if (k == "condition_on_previous_text") {
+    if (value != 0 && value != 1) return fail(h, WT_ERR_INVALID_ARG, "condition_on_previous_text must be 0 or 1");
+    e.condition_on_previous_text = value;
   } else if (k == "stop_at_eot") {
     e.stop_at_eot = value != 0;
   } else if (k == "verbose") {
@@ -291,6 +303,16 @@ int wt_engine_set_prompt(wt_engine* h, const int64_t* ids, int n) {
   return WT_OK;
 }
 
+int wt_engine_set_context(wt_engine* h, const int64_t* ids, int n) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  try {
+    h->impl->set_context(ids, n);
+  } catch (const wt::Error& err) {
+    return fail(h, err.code, err.what());
+  }
+  return WT_OK;
+}
+
 int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   if (!h || !key || !value) return WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
@@ -309,6 +331,11 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "temperature_increment") *value = e.temperature_increment;
   else if (k == "compression_ratio_threshold") *value = e.compression_ratio_threshold;
   else if (k == "seed") *value = e.seed;
+  else if (k == "prompt_group") *value = e.prompt_group;
+  else if (k == "seek") *value = e.seek;
+  else if (k == "condition_on_previous_text") *value = e.condition_on_previous_text;
+  else if (k == "context_ids") *value = long(e.context_ids.size());  // read-only: ids kept by wt_engine_set_context
+  else if (k == "graphs_cached") *value = e.graphs_cached();          // read-only: captured decoder graphs held
   else if (k == "stop_at_eot") *value = e.stop_at_eot;
   else if (k == "verbose") *value = e.verbose;
   else if (k == "cross_chunks") *value = e.cross_chunks;
@@ -619,6 +646,16 @@ int wt_last_decode_info(const wt_engine* h, wt_clip_decode* out, int cap) {
   return n;
 }
 
+int wt_last_windows(const wt_engine* h, wt_window* out, int cap) {
+  static_assert(sizeof(wt_window) == sizeof(wt::Engine::Window), "wt_window mirrors wt::Engine::Window");
+  if (!h || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_windows_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last_windows.size());
+  for (int i = 0; i < n && i < cap; ++i) std::memcpy(&out[i], &e.last_windows[size_t(i)], sizeof(wt_window));
+  return n;
+}
+
 int wt_last_token_logprobs(const wt_engine* h, float* out, int stride, int cap_clips) {
   if (!h || cap_clips < 0 || stride < 0 || (cap_clips > 0 && stride > 0 && !out)) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
@@ -770,6 +807,10 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
     wt::Engine& e = *h->impl;
     e.require_idle();
     e.check_timestamp_call();  // before anything is enqueued
+    if (e.seek) {  // one window at a time, each starting at the last closed timestamp of the one before (longform.cpp)
+      wt::transcribe_seek(e, pcm, n_samples, &text);
+      return;
+    }
     const size_t win = e.pcm_elems();
     const size_t n_win = std::max<size_t>(1, (n_samples + win - 1) / win);
     std::vector<int> langs;  // automatic language: every window's, joined over the batches
@@ -974,6 +1015,17 @@ int wt_vocab_segments(const wt_vocab* v, const int64_t* ids, int n, int sample_b
   if (!v || n < 0 || (!ids && n) || sample_begin < 0 || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
   std::vector<wt::Segment> segs;
   wt::parse_segments(v->vocab, ids, n, sample_begin, 0, &segs);
+  return copy_segments(segs, out, cap);
+}
+
+int wt_vocab_seek_step(const wt_vocab* v, const int64_t* g, int n, int win_ticks, int seg_ticks, wt_segment* out, int cap,
+                       int32_t* advance_ticks) {
+  if (!v || n < 0 || (!g && n) || win_ticks < 1 || seg_ticks < 0 || seg_ticks > win_ticks || cap < 0 || (cap > 0 && !out) ||
+      !advance_ticks) {
+    return -WT_ERR_INVALID_ARG;
+  }
+  std::vector<wt::Segment> segs;
+  *advance_ticks = wt::seek_step(v->vocab, g, n, win_ticks, seg_ticks, &segs);
   return copy_segments(segs, out, cap);
 }
 

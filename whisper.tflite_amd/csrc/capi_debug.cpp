@@ -711,6 +711,21 @@ int wt_dbg_self_attention_long(wt_engine* h, int batch, int heads, int cap, int 
     dv.to_host(vcache, nc);
   });
 }
+int wt_dbg_self_attention_prefill(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
+                                  float* kcache, float* vcache, float* out) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::check_self_attention_prefill(cap, pos, npos, batch, heads);  // the launcher's own refusals, before anything is allocated
+    if (!qkv || !kcache || !vcache || !out) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_self_attention_prefill: NULL array");
+    const size_t d = size_t(heads) * 64, rows = size_t(npos) * batch, nc = size_t(batch) * cap * d;
+    DevArr<float> dq(rows * 3 * d, qkv), dk(nc, kcache), dv(nc, vcache), dout(rows * d);
+    wt::launch_self_attention_prefill(dq.p, dk.p, dv.p, cap, pos, npos, dout.p, batch, heads, h->impl->stream());
+    h->impl->sync();
+    dout.to_host(out, rows * d);
+    dk.to_host(kcache, nc);
+    dv.to_host(vcache, nc);
+  });
+}
 
 }  // extern "C"
 

@@ -1654,6 +1654,7 @@ void Engine::decode(int batch, int64_t* ids, int32_t* n_ids, float* logits_host,
   check_beam_call(logits_host != nullptr);
   last_lang_valid = false;
   last_segments_valid = false;
+  last_windows_valid = false;
   clear_last_scores();
   if (beam_size > 1) {
     decode_beam(batch, last_enc_slot_, ids, n_ids);
@@ -1844,6 +1845,34 @@ std::vector<long long> Engine::prompt() const {
   return {vocab_.token_sot, kLangLo + std::max<long>(language, 0), vocab_.token_transcribe, vocab_.token_not};
 }
 
+std::vector<long long> Engine::fed_prompt() const {
+  std::vector<long long> out;
+  if (!context_ids.empty()) {  // Whisper's initial_prompt / condition_on_previous_text: <|startofprev|> + the previous ids
+    out.push_back(vocab_.token_prev);
+    out.insert(out.end(), context_ids.begin(), context_ids.end());
+  }
+  const std::vector<long long> tail = prompt();
+  out.insert(out.end(), tail.begin(), tail.end());
+  return out;
+}
+
+void Engine::set_context(const int64_t* ids, int n) {
+  if (n < 0 || n > kContextIdsMax || (n > 0 && !ids)) throw Error(kErrInvalidArg, "context: 0 .. 4096 ids");
+  if (n == 0) {
+    context_ids.clear();
+    return;
+  }
+  if (monolith_) throw Error(kErrUnsupported, "context: not on a Monolith engine (the reference's single graph takes no prompt)");
+  if (!has_prev_token()) {
+    throw Error(kErrUnsupported, "context: the model's vocabulary has no <|startofprev|> id (token_prev >= n_vocab)");
+  }
+  for (int i = 0; i < n; ++i) {
+    if (ids[i] < 0 || ids[i] >= dims_.n_vocab) throw Error(kErrInvalidArg, "context token id outside the model's vocabulary");
+  }
+  const int keep = std::min(n, context_keep());  // the LAST n_text_ctx / 2 - 1 ids, as Whisper's decoder keeps them
+  context_ids.assign(ids + (n - keep), ids + n);
+}
+
 // ------------------------------------------------------ the decoder pass ---
 
 namespace {
@@ -1944,7 +1973,9 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
     void* const kc = cache_at(p.self_kv, (size_t(l) * 2 + 0) * self_slab);
     void* const vc = cache_at(p.self_kv, (size_t(l) * 2 + 1) * self_slab);
     timed(tm, 1, [&] {
-      if (p.self_long) {  // one position past 32, fp32 cache (full-length decoding)
+      if (p.self_prefill) {  // np positions of a prompt behind a context, fp32 cache
+        launch_self_attention_prefill(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0, p.np, dw.attd, B, H, st);
+      } else if (p.self_long) {  // one position past 32, fp32 cache (full-length decoding)
         launch_self_attention_long(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0, dw.attd, B, H, st);
       } else {
         launch_self_attention(dw.qkvd, kc, vc, p.self_cap, p.pos0, p.np, dw.attd, B, H, st, bf);
@@ -1984,8 +2015,12 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
       CrossAttnArgs ca;  // LN + query projection + attention over the cached encoder keys, per key chunk
       ca.x = x; ca.ln_g = w.cross_ln_g; ca.ln_b = w.cross_ln_b; ca.wq_t = w.cross_wq_t; ca.bq = w.cross_bq;
       ca.kc = cache_at(p.cross_kv, (size_t(l) * 2 + 0) * kv_slab); ca.vc = cache_at(p.cross_kv, (size_t(l) * 2 + 1) * kv_slab);
-      ca.bf16 = bf; ca.ws = dw.cross_ws; ca.batch = p.clips; ca.heads = H; ca.T = T; ca.chunks = p.chunks; ca.nq = p.np;
-      timed(tm, 4, [&] { launch_cross_attention(ca, st); });
+      ca.bf16 = bf; ca.batch = p.clips; ca.heads = H; ca.T = T; ca.chunks = p.chunks;
+      // four query rows per launch (cross_attention_step's NQ); only a prompt behind a context has more positions
+      for (int p0 = 0; p0 < p.np; p0 += 4) {
+        ca.x = x + size_t(p0) * B * d; ca.ws = dw.cross_ws + size_t(p0) * B * H * p.chunks * 68; ca.nq = std::min(4, p.np - p0);
+        timed(tm, 4, [&] { launch_cross_attention(ca, st); });
+      }
       co.cross_ws = dw.cross_ws; co.heads = H; co.chunks = p.chunks;  // the out-projection's prologue combines the chunks
     }
     timed(tm, 5, [&] { launch_dec_gemm(co, p.absorbed ? kProNone : kProCombine, kDecResid, st); });
@@ -2499,6 +2534,12 @@ void Engine::check_timestamp_call() const {
   if (sampling() && max_positions <= 0) {
     throw Error(kErrUnsupported, "temperature: full-length decoding only, set the option max_positions (32 .. n_text_ctx)");
   }
+  if (seek && (!timestamps || max_positions <= 0)) {
+    throw Error(kErrUnsupported, "seek: needs the options timestamps = 1 and max_positions (32 .. n_text_ctx)");
+  }
+  if (!context_ids.empty() && max_positions <= 0) {
+    throw Error(kErrUnsupported, "context: full-length decoding only, set the option max_positions (32 .. n_text_ctx) or clear the context");
+  }
   if (temperature_fallback && !scores) throw Error(kErrUnsupported, "temperature_fallback: needs the option scores = 1");
   if (temperature_fallback && compression_ratio_threshold != 0 && !zlib_available()) {
     throw Error(kErrUnsupported, "compression_ratio_threshold: libz.so.1 could not be loaded; set the threshold to 0 (off)");
@@ -2555,6 +2596,9 @@ void Engine::check_full_call() const {
   if (!forced_ids.empty()) no("not with forced ids");
   if (timestamps && !has_timestamp_tokens()) no("timestamps: the model's vocabulary has no timestamp ids");
   if (scores && !has_no_speech_token()) no("scores: the model's vocabulary has no <|nospeech|> id");
+  if (!context_ids.empty() && long(fed_prompt().size()) >= max_positions) {
+    throw Error(kErrInvalidArg, "context: the prompt behind it leaves no position to generate (prompt ids >= max_positions)");
+  }
 }
 
 // A full-length call is synchronous and finds the engine idle, so it may choose its pipeline slot: always slot 0, and
@@ -2667,14 +2711,18 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   last_lang_valid = false;
   beam_scores_valid = false;
   last_segments_valid = false;
+  last_windows_valid = false;
   clear_last_scores();  // (the decode info with them)
   const bool ts = timestamps != 0, sc = scores != 0, smp = sampling();
   ensure_batch(batch);
   ensure_full_workspace(batch);  // (before any capture: nothing may be allocated inside one)
   Slot& slot = slots_[slot_idx];
   const int V = dims_.n_vocab, cap = full_cap(), stride = cap + 1;
-  const std::vector<long long> prompt = this->prompt();
+  // with a context (set_context): [prev] + context + prompt(), every count below starts behind all of it
+  const bool ctx = !context_ids.empty();
+  const std::vector<long long> prompt = fed_prompt();
   const int n_prompt = int(prompt.size());
+  const int sot_idx = ctx ? 1 + int(context_ids.size()) : 0;  // Whisper's sot_index: the no-speech logits are read there
   check_prompt_ids(prompt, kErrInvalidArg);
   slot.dec = slot_idx % n_dec_streams_;
   slot.pair_leader = -1;
@@ -2683,8 +2731,12 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   const int chunks = cross_chunks_for(batch);  // as decode_enqueue chooses them for a synchronous call of this size
   const bool absorbed = slot.absorbed;
   const int n_abs = abs_chunks_for(batch, 256);
-  const int np_max = std::max(1, std::min(4, kDecRowsMax / batch));
+  // prompt positions per pass: four without a context (self_attention_step's launch), as many rows as a pass takes
+  // with one (self_attention_prefill); option prompt_group = 1: one position per pass, the A/B handle
+  const int np_max = ctx ? (prompt_group == 1 ? 1 : std::max(1, kDecRowsMax / batch)) : std::max(1, std::min(4, kDecRowsMax / batch));
   const int prompt_end = std::min(n_prompt, P);
+  // a context's length is part of every launch: such calls run eagerly
+  auto graphs = [&] { return use_graphs && !ctx; };
 
   DecPass p;
   p.B = p.clips = batch; p.ids = fw_.ids; p.ids_stride = stride; p.self_kv = fw_.kv; p.self_cap = cap;
@@ -2703,14 +2755,16 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     int seg_steps = 0;
     for (int pos0 = 0, np = 1; pos0 < hi; pos0 += np) {
       np = pos0 < prompt_end ? std::min(np_max, prompt_end - pos0) : 1;
-      if (sc && pos0 == 0) np = 1;  // the row behind sot alone, with logits: the no-speech probability
+      if (sc && pos0 <= sot_idx) np = std::min(np, sot_idx - pos0 + 1);  // a pass ends at sot, with logits: the no-speech probability
       if (pos0 < lo) continue;
       const int last = pos0 + np - 1;
       const bool logits = last >= n_prompt - 1;  // then the token of the last position's rows
-      p.pos0 = pos0; p.np = np; p.best = logits || (sc && pos0 == 0) ? dw.best : nullptr;
-      p.self_long = pos0 + np > 32;  // (np == 1 there: the prompt has at most 8 ids)
+      const bool nosp = sc && last == sot_idx;
+      p.pos0 = pos0; p.np = np; p.best = logits || nosp ? dw.best : nullptr;
+      p.self_prefill = ctx && pos0 < prompt_end;  // the prompt behind a context, whatever np is
+      p.self_long = !p.self_prefill && pos0 + np > 32;  // (np == 1 there: a prompt without a context has at most 8 ids)
       decoder_pass(p, st);
-      if (sc && pos0 == 0) {
+      if (nosp) {
         sa.state = nullptr;
         launch_no_speech_prob(sa, vocab_.token_solm, fw_.sc_nosp, st);
       }
@@ -2780,14 +2834,14 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       const std::vector<long long> key{kFullKey, slot_idx, batch, lo, P, n_prompt, chunks, long(stop_at_eot), fc2_ksplit,
                                        absorbed ? 1 : 0, n_abs, slot.dec, ts ? 1 : 0, ts ? max_initial_timestamp : 0, sc ? 1 : 0,
                                        smp ? 1 : 0};
-      auto it = use_graphs ? graphs_.find(key) : graphs_.end();
+      auto it = graphs() ? graphs_.find(key) : graphs_.end();
       if (it != graphs_.end()) {
         HIPCHK(hipGraphLaunch(it->second.exec, st));
         steps += it->second.steps;
       } else {
         const int seg_steps = enqueue_segment(lo, hi);  // eager the first time, then captured for the next calls
         steps += seg_steps;
-        if (use_graphs) {
+        if (graphs()) {
           try {
             graphs_.emplace(key, GraphEntry{capture_graph(st, [&] { enqueue_segment(lo, hi); }), seg_steps});
           } catch (const std::exception& e) {

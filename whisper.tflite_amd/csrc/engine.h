@@ -258,6 +258,34 @@ class Engine {
   std::vector<long long> forced_ids;
   // ids the decoder starts from (prompt_override, or the reference's rule for the engine type)
   std::vector<long long> prompt() const;
+  // A context in front of the prompt: Whisper's initial_prompt / condition_on_previous_text.  The
+  // engine keeps the LAST context_keep() = n_text_ctx / 2 - 1 ids of what set_context is given (n = 0 clears; more than
+  // kContextIdsMax ids or one outside the vocabulary: kErrInvalidArg; a vocabulary without <|startofprev|> or a Monolith
+  // engine: kErrUnsupported) and decode_full feeds fed_prompt() = [prev] + context + prompt(): every count of the decode
+  // — sample_begin, n_gen, the timestamp-rule state, the scores — starts behind all of it, and the no-speech
+  // probability is read behind sot, wherever that is.  The prompt passes then take kDecRowsMax / batch positions each on
+  // self_attention_prefill (prompt_group = 1: one position each), and the call runs eagerly: a context's length is a
+  // launch constant of every pass, so its segments are not captured and graphs_cached() does not grow with the lengths seen.
+  // Scope: wherever max_positions decoding is; every other decode call with a context set is kErrUnsupported
+  // (check_timestamp_call, check_full_call), a prompt that leaves no position to generate kErrInvalidArg.
+  static constexpr int kContextIdsMax = 4096;
+  std::vector<long long> context_ids;
+  int context_keep() const { return std::max(0, dims_.n_text_ctx / 2 - 1); }
+  bool has_prev_token() const { return !monolith_ && vocab_.token_prev >= 0 && vocab_.token_prev < dims_.n_vocab; }
+  void set_context(const int64_t* ids, int n);
+  std::vector<long long> fed_prompt() const;
+  long prompt_group = 0;
+  int graphs_cached() const { return int(graphs_.size()); }
+  // Seeking long-audio transcription (wt_transcribe_long_pcm with seek = 1, longform.cpp): needs timestamps and
+  // max_positions; condition_on_previous_text is read only then
+  long seek = 0, condition_on_previous_text = 1;
+  struct Window {  // (wt_window)
+    int64_t seek_sample;
+    int32_t advance_samples, n_context, n_prompt, n_kept_ids, skipped, temperature_milli;
+  };
+  // one record per window of the last synchronous decode when that was a seeking one
+  std::vector<Window> last_windows;
+  bool last_windows_valid = false;
 
   int mel_frames() const { return 2 * dims_.n_audio_ctx; }
   size_t mel_elems() const { return size_t(dims_.n_mels) * mel_frames(); }
@@ -548,6 +576,7 @@ class Engine {
     float* self_kv = nullptr;        // self-attention caches [layer][k|v][B][self_cap][d] (bf16 elements when bf)
     int ids_stride = 32, self_cap = 32;
     bool self_long = false;  // self_attention_long (np = 1, any position below self_cap) instead of self_attention
+    bool self_prefill = false;  // self_attention_prefill (np >= 1: a prompt behind a context) instead of either
     int clips = 0;           // clips the cross-attention sees: B, or fewer with M / clips query rows each (beam search)
     bool absorbed = false;   // cross-attention form: absorbed (e .. e4, e_split, n_abs) or cached (cross_kv, chunks)
     const unsigned short *e = nullptr, *e2 = nullptr, *e3 = nullptr, *e4 = nullptr;  // as in CrossAbsorbedArgs

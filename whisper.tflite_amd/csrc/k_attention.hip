@@ -649,6 +649,106 @@ __global__ __launch_bounds__(256) void self_attention_long(const float* __restri
   }
 }
 
+// ------------------------------------- decoder self attention over a prompt ---
+// A prompt behind a context (wt_engine_set_context): np >= 1 new positions pos0 .. pos0 + np - 1 per launch, cache
+// [b][cap][d] with cap up to kSelfLongCap, fp32.  One block of 256 threads per (clip, head, group of kPrefillQ = 16
+// query positions): a 16-lane group owns one query (4 of the 64 dimensions per lane) and runs an online softmax over
+// the keys 0 .. pos0 + p in ascending order, so the order of every sum depends on the key index alone — never on the
+// clip, the batch or the grid.  The keys reach the groups in tiles of kPrefillTile = 32 rows staged in LDS (16 KB for
+// K and V; the next tile's loads are in flight while the current one is scored): rows < pos0 come from the cache,
+// rows >= pos0 from qkv, rows past the block's last key are not loaded at all.  Nothing reads a cache row >= pos0, and
+// a block appends exactly the k and v rows of its own queries, so each new row is written once and blocks cannot
+// race on it.  Scores in log2 units, p = exp2(s - m).  qkv / out rows: row(p) = p * B + b.
+constexpr int kPrefillQ = 16, kPrefillTile = 32;
+__global__ __launch_bounds__(256) void self_attention_prefill(const float* __restrict__ qkv, float* __restrict__ kcache,
+                                                              float* __restrict__ vcache, int cap, int pos0, int np,
+                                                              int B, float* __restrict__ out, int heads) {
+  constexpr int TK = kPrefillTile;
+  __shared__ __attribute__((aligned(16))) float Ks[TK][64];
+  __shared__ __attribute__((aligned(16))) float Vs[TK][64];
+  const int qblocks = (np + kPrefillQ - 1) / kPrefillQ;
+  const int qb = blockIdx.x % qblocks, bh = blockIdx.x / qblocks;
+  const int b = bh / heads, h = bh % heads;
+  const int tid = threadIdx.x, grp = tid >> 4, gl16 = tid & 15;
+  const int d = heads * 64;
+  float* kc = kcache + ((long)b * cap) * d + h * 64;
+  float* vc = vcache + ((long)b * cap) * d + h * 64;
+  const int p_first = qb * kPrefillQ;
+  const int p_last = min(np, p_first + kPrefillQ) - 1;  // the block's last query
+  const int kend = pos0 + p_last + 1;                   // keys 0 .. kend - 1 are all this block may see
+  // staging: thread t carries 16 bytes of rows t / 16 and t / 16 + 16 of a tile
+  f32x4 kr[2], vr[2];
+  auto fetch = [&](int k0) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int k = k0 + grp + 16 * u;
+      kr[u] = vr[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      if (k < pos0) {
+        kr[u] = *reinterpret_cast<const f32x4*>(kc + (long)k * d + gl16 * 4);
+        vr[u] = *reinterpret_cast<const f32x4*>(vc + (long)k * d + gl16 * 4);
+      } else if (k < kend) {
+        const float* row = qkv + ((long)(k - pos0) * B + b) * 3 * d + h * 64 + gl16 * 4;
+        kr[u] = *reinterpret_cast<const f32x4*>(row + d);
+        vr[u] = *reinterpret_cast<const f32x4*>(row + 2 * d);
+      }
+    }
+  };
+  fetch(0);
+  constexpr float kScale = 0.125f * 1.44269504088896340736f;
+  const int p = p_first + grp;
+  const bool live = p <= p_last;
+  const int n = live ? pos0 + p + 1 : 0;  // causal: keys 0 .. pos0 + p
+  f32x4 q4 = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (live) {  // the query, and the append of this position's k and v (each row by the one group that owns it)
+    const float* row = qkv + ((long)p * B + b) * 3 * d + h * 64 + gl16 * 4;
+    q4 = *reinterpret_cast<const f32x4*>(row);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q4[j] *= kScale;
+    *reinterpret_cast<f32x4*>(kc + (long)(pos0 + p) * d + gl16 * 4) = *reinterpret_cast<const f32x4*>(row + d);
+    *reinterpret_cast<f32x4*>(vc + (long)(pos0 + p) * d + gl16 * 4) = *reinterpret_cast<const f32x4*>(row + 2 * d);
+  }
+  float m = -1e30f, l = 0.0f;
+  f32x4 o = {0.0f, 0.0f, 0.0f, 0.0f};
+  for (int k0 = 0; k0 < kend; k0 += TK) {
+    __syncthreads();  // the previous tile has been scored by every group
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      *reinterpret_cast<f32x4*>(&Ks[grp + 16 * u][gl16 * 4]) = kr[u];
+      *reinterpret_cast<f32x4*>(&Vs[grp + 16 * u][gl16 * 4]) = vr[u];
+    }
+    __syncthreads();
+    if (k0 + TK < kend) fetch(k0 + TK);
+    const int jn = min(TK, kend - k0);  // (scored in fours: a row in [kend, k0 + TK) holds zeros and is masked, k >= n)
+    for (int j0 = 0; j0 < jn; j0 += 4) {
+#pragma unroll
+     for (int j = j0; j < j0 + 4; ++j) {
+      const int k = k0 + j;
+      const f32x4 kf = *reinterpret_cast<const f32x4*>(&Ks[j][gl16 * 4]);
+      const f32x4 vf = *reinterpret_cast<const f32x4*>(&Vs[j][gl16 * 4]);
+      float s = (kf[0] * q4[0] + kf[1] * q4[1]) + (kf[2] * q4[2] + kf[3] * q4[3]);
+      s += __shfl_xor(s, 8, 64);
+      s += __shfl_xor(s, 4, 64);
+      s += __shfl_xor(s, 2, 64);
+      s += __shfl_xor(s, 1, 64);
+      if (k >= n) s = -1e30f;
+      const float mn = fmaxf(m, s);
+      const float a = exp2f(m - mn), pr = k >= n ? 0.0f : exp2f(s - mn);
+      l = l * a + pr;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[c] = o[c] * a + pr * vf[c];
+      m = mn;
+     }
+    }
+  }
+  if (live) {
+    const float inv = 1.0f / l;
+    f32x4 r;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) r[c] = o[c] * inv;
+    *reinterpret_cast<f32x4*>(out + ((long)p * B + b) * d + h * 64 + gl16 * 4) = r;
+  }
+}
+
 // ------------------------------------------------ decoder cross attention ---
 // One block per (clip, head, key chunk), NQ query rows (NQ = 1 for a generated position; the prompt positions of
 // the first pass share one sweep of the cache).  The block first makes its own queries — q = LayerNorm(x[row]) .
@@ -905,6 +1005,21 @@ void launch_self_attention_long(const float* qkv, float* kcache, float* vcache, 
                                 int heads, hipStream_t s) {
   check_self_attention_long(cap, pos, batch, heads);
   hipLaunchKernelGGL(self_attention_long, dim3(batch * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out, heads);
+}
+
+void check_self_attention_prefill(int cap, int pos0, int np, int batch, int heads) {
+  if (batch < 1 || heads < 1) throw Error(kErrInvalidArg, "decoder self-attention (prefill): no clips or no heads");
+  if (cap < 1 || cap > kSelfLongCap) throw Error(kErrInvalidArg, "decoder self-attention (prefill): cache rows outside [1, 448]");
+  if (pos0 < 0 || np < 1 || pos0 > cap - np) throw Error(kErrInvalidArg, "decoder self-attention (prefill): positions outside the cache");
+  if (np > kSelfPrefillRows / batch) throw Error(kErrInvalidArg, "decoder self-attention (prefill): more than 128 rows");
+}
+
+void launch_self_attention_prefill(const float* qkv, float* kcache, float* vcache, int cap, int pos0, int np, float* out,
+                                   int batch, int heads, hipStream_t s) {
+  check_self_attention_prefill(cap, pos0, np, batch, heads);
+  const int qblocks = (np + kPrefillQ - 1) / kPrefillQ;
+  hipLaunchKernelGGL(self_attention_prefill, dim3(batch * heads * qblocks), dim3(256), 0, s, qkv, kcache, vcache, cap, pos0,
+                     np, batch, out, heads);
 }
 
 template <int NQ, bool BF>

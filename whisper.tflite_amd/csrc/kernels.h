@@ -269,6 +269,16 @@ constexpr int kSelfLongCap = 448;  // n_text_ctx of every Whisper
 void check_self_attention_long(int cap, int pos, int batch, int heads);
 void launch_self_attention_long(const float* qkv, float* kcache, float* vcache, int cap, int pos, float* out, int batch,
                                 int heads, hipStream_t s);
+// A prompt behind a context (wt_engine_set_context): np >= 1 new positions pos0 .. pos0 + np - 1 against a cache
+// [B][cap][d], cap <= kSelfLongCap, fp32.  Appends their k and v (qkv rows p * B + b, [.][3d]) at cache rows pos0 + p,
+// each row written once, and attends each q causally over rows 0 .. pos0 + p: rows < pos0 from the cache, the others from
+// qkv; out rows p * B + b.  Cache rows >= pos0 are never read, rows >= pos0 + np neither read nor written.
+// Throws kErrInvalidArg for pos0 < 0, np < 1, pos0 + np > cap, cap > kSelfLongCap, np * batch > kSelfPrefillRows, batch < 1
+// or heads < 1 (check_self_attention_prefill).
+constexpr int kSelfPrefillRows = 128;  // rows of one decoder pass (Engine::kDecRowsMax)
+void check_self_attention_prefill(int cap, int pos0, int np, int batch, int heads);
+void launch_self_attention_prefill(const float* qkv, float* kcache, float* vcache, int cap, int pos0, int np, float* out,
+                                   int batch, int heads, hipStream_t s);
 // Cross attention of nq (1..4) query rows per clip over T cached keys, the query projection included:
 // q = LayerNorm(x[row]) . Wq^T + bq with x the residual stream [nq * B][d], rows p * B + b.  wq_t = Wq in the
 // layout of cross_q_layout(); kc, vc [B][heads][T][64]; partial results per key chunk in ws
