@@ -400,6 +400,62 @@ int wt_vocab_segments(const wt_vocab* v, const int64_t* ids, int n, int sample_b
 int wt_vocab_seek_step(const wt_vocab* v, const int64_t* g, int n, int win_ticks, int seg_ticks, wt_segment* out, int cap,
                        int32_t* advance_ticks);
 
+/* ---- word-level timestamps -------------------------------------------
+ * Option "word_timestamps" = 1 (default 0; needs "timestamps" = 1, "max_positions" and the absorbed cross-attention the
+ * default weights and gemm_variant give: otherwise every decode call is WT_ERR_UNSUPPORTED and the engine stays usable).  After the decode, and after the temperature fall-back, every clip's row prompt + <|notimestamps|>
+ * + text + EOT is fed through the decoder once more, teacher-forced; the cross-attention weights of the alignment heads
+ * over the clip's valid frames are normalised per frame over the positions, median-filtered (7 wide, reflect padding),
+ * averaged over the heads and dynamic-time-warped against the ids on the device (Whisper's find_alignment), and the path
+ * is cut into words by wt_vocab_split_words and wt_vocab_merge_punctuation.  text = the ids below EOT of the clip's
+ * segments; at most n_text_ctx - prompt - 2 of them are aligned, the rest form no words.  A clip that came in as PCM
+ * (wt_transcribe_pcm, _file, _long_pcm) is aligned over the frames of its own samples, floor(samples / 320), at least 1;
+ * any other clip over all n_audio_ctx frames.  Not reproduced from Whisper: the duration heuristics of
+ * add_word_timestamps, moving the seek position to the last word, other punctuation sets.
+ * Alignment heads: n (layer, head) pairs, at most 128; n = 0 restores the default, every head of the upper half of the
+ * decoder layers.  WT_ERR_INVALID_ARG for a pair outside the model, a duplicate or n > 128.  The read-only option
+ * "alignment_heads" gives the count in effect. */
+int wt_engine_set_alignment_heads(wt_engine* h, const int32_t* layer_head /* [n][2] */, int n);
+/* One word: ids[id_begin .. id_begin + id_count) of clip `clip`'s id row (a word that spans a timestamp id counts it),
+ * spoken from t0_ms to t1_ms (20 ms steps), inside segment `segment` of wt_last_segments (that of its first id);
+ * probability = the mean over its ids of exp(token log-probability) of the decode itself (wt_last_token_logprobs), 0
+ * when the decode ran without "scores".  After wt_transcribe_long_pcm clip is the window index and the times are the
+ * file's: 30 000 ms per window, or with "seek" = 1 the window's seek_sample / 16 ms, the text being the ids below EOT of
+ * the segments wt_vocab_seek_step kept of the window. */
+typedef struct wt_word {
+  int32_t clip, segment, t0_ms, t1_ms, id_begin, id_count;
+  float probability;
+} wt_word;
+/* the words of the last synchronous decode, in clip order: returns their count (at most cap written), or
+ * -WT_ERR_INVALID_ARG when that decode ran without "word_timestamps" */
+int wt_last_words(const wt_engine* h, wt_word* out, int cap);
+/* the ids below EOT of word `index`, decoded */
+int wt_last_word_text(const wt_engine* h, int index, char* out, size_t cap, size_t* len);
+
+/* ---- word-level timestamps: the host half (no GPU needed) -----------
+ * Whisper's split_to_word_tokens on a row of n ids (a clip's text ids, then EOT): word_len_out gets the id counts of
+ * the words, in order; they add up to n.  First the ids are grouped into complete UTF-8 sequences over the vocabulary's
+ * bytes: a group is closed when it decodes without U+FFFD, or when the whole row has U+FFFD at the place of the group's
+ * first one (ill-formed bytes are replaced as Python's decode(errors="replace") replaces them).  unicode_only != 0
+ * (zh, ja, th, lo, my, yue): these groups are the words.  Otherwise a group starts a word when it is the first, its first
+ * id is >= EOT, its bytes begin with a space or, stripped of ASCII white space, are one ASCII punctuation character;
+ * any other group joins the word before it.  Returns the word count (at most cap written), or -WT_ERR_INVALID_ARG. */
+int wt_vocab_split_words(const wt_vocab* v, const int64_t* ids, int n, int unicode_only, int32_t* word_len_out, int cap);
+/* Whisper's merge_punctuations with its default marks on the words word_len[0 .. n_words) of a row of n ids (counts
+ * that add up to n).  From the back, a word that begins with a space and is otherwise one of  " ' “ ¿ ( [ { -  is put in
+ * front of the word behind it; then, from the front, a word that is exactly one of  " ' . 。 , ， ! ！ ? ？ : ： ” ) ] } 、
+ * is put behind the word before it unless that one ends in a space.  merged_len_out gets the id counts of the merged
+ * words, in order (they add up to n: a merged word is the id run of its parts).  Returns the merged word count (at most
+ * cap written), or -WT_ERR_INVALID_ARG. */
+int wt_vocab_merge_punctuation(const wt_vocab* v, const int64_t* ids, int n, const int32_t* word_len, int n_words,
+                               int32_t* merged_len_out, int cap);
+/* Dynamic time warping as Whisper's find_alignment runs it, in fp32, over cost [N][F]: D[0][0] = 0, the rest of row 0 and
+ * column 0 +inf, D[i][j] = cost[i - 1][j - 1] + min(c0, c1, c2) with c0 = D[i - 1][j - 1], c1 = D[i - 1][j], c2 = D[i][j - 1];
+ * the step taken is c0's when c0 < c1 and c0 < c2, else c1's when c1 < c0 and c1 < c2, else c2's, and the path runs back
+ * from (N, F).  jump [N] gets the first frame of the path in each row; path_out (may be NULL) the (row, frame) pairs from
+ * (0, 0) to (N - 1, F - 1), at most path_cap pairs.  1 <= N <= 447, 1 <= F <= 1500.  Returns the number of path cells, or
+ * -WT_ERR_INVALID_ARG. */
+int wt_dtw_path(const float* cost, int N, int F, int32_t* jump, int32_t* path_out, int path_cap);
+
 /* ---- the log-mel front end as a free function ---------------------------------------------
  * Replaces whisper::log_mel_spectrogram (whisper.h:123, whisper.cpp:109-216) for callers that hold a
  * Filters table but no engine: the same gfx950 kernels the engine uses, on `device_id`, through a

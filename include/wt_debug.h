@@ -298,6 +298,47 @@ int wt_dbg_f32_to_planes(wt_engine* h, int M, int ld, const float* x, const floa
  * 1); out is then not written. */
 int wt_dbg_encoder_attention_at(wt_engine* h, int kind, int variant, int batch, int T, int heads, int guard_rows,
                                 const float* qkv, const float scales[4], void* out);
+/* launch_align_scores (word-level timestamps): the attention weights of n_heads heads of one layer
+ * for the np positions of one decoder pass.  qp [np * batch][H * 64 H] absorbed queries (row = p * batch + b), E [batch][T]
+ * [64 H] the encoder output, split into fp16 planes on the host as wt_dbg_cross_absorbed does; head [n_heads] the heads'
+ * indices in the layer, slot [n_heads] their places in W's head axis, F [batch] the clips' valid frames.
+ * W [batch][heads_total][L_max][ld] is in / out, uploaded as given and downloaded whole: the kernel writes the frames
+ * < T of the rows pos0 .. pos0 + np - 1 of the listed slots (softmax over t < F[b], zero behind) and nothing else.
+ * The tap fills the launcher's arguments and calls the launcher.  WT_ERR_INVALID_ARG before anything is launched: a null
+ * pointer, batch > 64, n_heads > 8, and whatever the launcher refuses: no heads, a head >= H or a slot >= heads_total,
+ * an F[b] outside [1, T], np * batch > 128, pos0 + np > L_max, T % 4 != 0 or T > 1500, ld < T or ld % 4 != 0, an H
+ * other than 2, 6 or 8, a head or a slot listed twice, a mode other than 0 (one wavefront sweeps all frames of its
+ * columns, softmax in the same kernel) or 1 (blocks per 128 frames, then align_softmax_rows). */
+int wt_dbg_align_scores(wt_engine* h, int batch, int H, int T, int np, int pos0, const float* qp, const float* E, int n_heads,
+                        const int32_t* head, const int32_t* slot, int heads_total, const int32_t* F, int L_max, int ld, float* W,
+                        int mode);
+/* launch_align_matrix (word-level timestamps): W [clips][heads][L_max][ld] attention weights ->
+ * C [clips][N_max][ld] in / out and stats [clips][heads][2][ld] in / out (mean, then 1 / std; may be NULL), both
+ * uploaded as given and downloaded whole, so that every cell the kernels do not write comes back as given.  L [clips] is
+ * the clips' fed positions, F [clips] their valid frames; cost row r of a clip is W's row n_a + r and a clip has
+ * L[b] - n_a - 1 of them.  The tap fills the launcher's arguments and calls the launcher; it restates no addressing.
+ * WT_ERR_INVALID_ARG before anything is launched: a null pointer, an L[b] outside [n_a + 2, L_max], an F[b] outside
+ * [1, ld], an N_max below a clip's row count, and whatever the launcher refuses (heads > 128, N_max > 447, ld > 1500). */
+int wt_dbg_align_matrix(wt_engine* h, int clips, int heads, int L_max, int ld, int n_a, int N_max, const float* W,
+                        const int32_t* L, const int32_t* F, float* C, float* stats);
+/* launch_align_dtw: C [clips][N_max][ld], N [clips] rows and F [clips] frames of each clip -> jump [clips][N_max] in / out
+ * (the kernel writes a clip's whole row: first frames, then zeros) and, when not NULL, trace [clips][N_max][ld] in / out,
+ * the trace codes of the cells.  WT_ERR_INVALID_ARG before anything is launched: a null pointer, an N[b] outside
+ * [0, N_max], an F[b] outside [1, ld], and what the launcher refuses (N_max > 447, ld > 1500). */
+int wt_dbg_align_dtw(wt_engine* h, int clips, int N_max, int ld, const float* C, const int32_t* N, const int32_t* F,
+                     int32_t* jump, uint8_t* trace);
+/* Measurement and test handles of the alignment pass (word_timestamps): keep = 1 keeps what the pass forms per clip for
+ * wt_dbg_last_alignment (it then synchronises and copies per clip); mode = the form of align_scores, 0 or 1 (default 1);
+ * sub = the most clips per sub-group of the pass, 0 = as many as the weight workspace's bound allows (default).  A
+ * negative argument leaves that setting as it is.  WT_ERR_INVALID_ARG for a value outside these. */
+int wt_dbg_set_alignment(wt_engine* h, int keep, int mode, int sub);
+/* What the alignment pass of the last decode with word_timestamps = 1, behind wt_dbg_set_alignment(h, 1, ..), formed for clip
+ * `clip`: dims = {n_a, L, N, F, heads, T} (prompt ids, ids fed, cost rows, valid frames, alignment heads, n_audio_ctx);
+ * row [L] the ids fed, W [heads][L][T] the attention weights, C [N][T] the cost (frames >= F are not the engine's),
+ * jump [N] the first frame of every cost row.  After a seeking wt_transcribe_long_pcm `clip` is the window; a window
+ * without words has L = 0.  Every output pointer may be NULL.  WT_ERR_INVALID_ARG when that decode kept nothing or has no
+ * such clip. */
+int wt_dbg_last_alignment(const wt_engine* h, int clip, int32_t dims[6], int64_t* row, float* W, float* C, int32_t* jump);
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,8 @@ CAPI_SYMBOLS = [
     "wt_encdec_debug_batch",
     "wt_encdec_tokens_full_batch", "wt_encdec_tokens_full_batch_dev", "wt_transcribe_tokens_full_batch_dev",
     "wt_last_segments", "wt_last_segment_text", "wt_vocab_segments", "wt_vocab_seek_step", "wt_last_windows",
+    "wt_vocab_split_words", "wt_vocab_merge_punctuation", "wt_dtw_path",
+    "wt_engine_set_alignment_heads", "wt_last_words", "wt_last_word_text",
     "wt_last_scores", "wt_last_token_logprobs", "wt_last_segment_scores", "wt_last_decode_info",
     "wt_language_count", "wt_detect_language_batch", "wt_detect_language_batch_dev", "wt_detect_language_pcm", "wt_last_languages",
     "wt_last_timings", "wt_last_beam_scores", "wt_last_kernel_stats", "wt_decode_text", "wt_language_id", "wt_lang_code", "wt_wav_read_legacy",
@@ -65,6 +67,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
     "wt_dbg_pcm_to_planes",
     "wt_dbg_gemm_addressed", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes", "wt_dbg_encoder_attention_at",
+    "wt_dbg_align_scores", "wt_dbg_align_matrix", "wt_dbg_align_dtw", "wt_dbg_last_alignment", "wt_dbg_set_alignment",
 ]
 
 
@@ -241,6 +244,18 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_layernorm_planes.argtypes = [c_void_p, c_int, c_int, fp, fp, fp, c_float, c_int, c_int, u16p, fp, ip32]
         L.wt_dbg_f32_to_planes.argtypes = [c_void_p, c_int, c_int, fp, fp, c_int, c_int, u16p]
         L.wt_dbg_encoder_attention_at.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, fp, c_void_p]
+        L.wt_vocab_split_words.argtypes = [c_void_p, ip64, c_int, c_int, ip32, c_int]
+        L.wt_vocab_merge_punctuation.argtypes = [c_void_p, ip64, c_int, ip32, c_int, ip32, c_int]
+        L.wt_dtw_path.argtypes = [fp, c_int, c_int, ip32, ip32, c_int]
+        L.wt_engine_set_alignment_heads.argtypes = [c_void_p, ip32, c_int]
+        L.wt_last_words.argtypes = [c_void_p, c_void_p, c_int]
+        L.wt_last_word_text.argtypes = [c_void_p, c_int, c_char_p, c_size_t, POINTER(c_size_t)]
+        L.wt_dbg_last_alignment.argtypes = [c_void_p, c_int, ip32, ip64, fp, fp, ip32]
+        L.wt_dbg_align_scores.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, c_int, ip32, ip32, c_int, ip32,
+                                          c_int, c_int, fp, c_int]
+        L.wt_dbg_set_alignment.argtypes = [c_void_p, c_int, c_int, c_int]
+        L.wt_dbg_align_matrix.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, ip32, ip32, fp, fp]
+        L.wt_dbg_align_dtw.argtypes = [c_void_p, c_int, c_int, c_int, fp, ip32, ip32, ip32, POINTER(ctypes.c_uint8)]
         _lib = L
     return _lib
 
@@ -330,6 +345,11 @@ WINDOW_DTYPE = np.dtype([("seek_sample", np.int64), ("advance_samples", np.int32
                          ("temperature_milli", np.int32)], align=True)
 
 
+# one word of a decode with option word_timestamps (wt_word)
+WORD_DTYPE = np.dtype([("clip", np.int32), ("segment", np.int32), ("t0_ms", np.int32), ("t1_ms", np.int32),
+                       ("id_begin", np.int32), ("id_count", np.int32), ("probability", np.float32)])
+
+
 def _segments(call):
     n = call(None, 0)
     if n < 0:
@@ -413,6 +433,41 @@ class Vocab:
         segs = _segments(lambda out, cap: lib().wt_vocab_seek_step(self._v, g.ctypes.data_as(POINTER(c_int64)), g.size,
                                                                    int(win_ticks), int(seg_ticks), out, cap, byref(adv)))
         return segs, adv.value
+
+    def split_words(self, ids, unicode_only: bool = False) -> np.ndarray:
+        """Whisper's split_to_word_tokens (wt_vocab_split_words, DESIGN.md section 21) on a row of ids, usually a clip's
+        text ids and then EOT: the id counts of its words, int32; they add up to len(ids).  unicode_only: the split of the
+        languages written without spaces, one word per complete UTF-8 sequence."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        out = np.zeros(max(ids.size, 1), np.int32)
+        n = lib().wt_vocab_split_words(self._v, _ip64(ids), ids.size, int(bool(unicode_only)), _ip32(out), out.size)
+        if n < 0:
+            raise WtError(-n, "split_words: bad arguments")
+        return out[:n].copy()
+
+    def merge_punctuation(self, ids, word_len) -> np.ndarray:
+        """Whisper's merge_punctuations with its default marks (wt_vocab_merge_punctuation) on the words word_len of a
+        row of ids: the id counts of the merged words, int32."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        word_len = np.ascontiguousarray(word_len, dtype=np.int32).reshape(-1)
+        out = np.zeros(max(word_len.size, 1), np.int32)
+        n = lib().wt_vocab_merge_punctuation(self._v, _ip64(ids), ids.size, _ip32(word_len), word_len.size, _ip32(out),
+                                             out.size)
+        if n < 0:
+            raise WtError(-n, "merge_punctuation: the word counts must be positive and add up to the id count")
+        return out[:n].copy()
+
+
+def dtw_path(cost):
+    """Whisper's dynamic time warping in fp32 on the host (wt_dtw_path): cost [N][F] -> (jump int32
+    [N], the first frame of the path in each row; path int32 [cells][2], the (row, frame) pairs from (0, 0) on)."""
+    cost = _f32(cost)
+    N, F = cost.shape
+    jump, path = np.zeros(N, np.int32), np.zeros((N + F, 2), np.int32)
+    n = lib().wt_dtw_path(_fp(cost), N, F, _ip32(jump), _ip32(path), N + F)
+    if n < 0:
+        raise WtError(-n, "dtw_path: 1 <= N <= 447 and 1 <= F <= 1500")
+    return jump, path[:n].copy()
 
 
 def log_mel_spectrogram(samples, filters, device_id: int = 0) -> np.ndarray:
@@ -988,6 +1043,94 @@ class Engine:
                                                   int(sample_begin), int(eot), int(beg), int(max_initial_timestamp),
                                                   _ip64(tok), L.ctypes.data_as(POINTER(ctypes.c_double)), _fp(M)))
         return tok, L, M
+
+    def set_alignment_heads(self, pairs=()) -> None:
+        """The (layer, head) pairs whose cross-attention the word timestamps are read from (wt_engine_set_alignment_heads,
+        DESIGN.md section 21); none: the default, every head of the upper half of the decoder layers."""
+        a = np.ascontiguousarray(np.asarray(list(pairs), np.int32).reshape(-1, 2))
+        self._check(lib().wt_engine_set_alignment_heads(self._h, _ip32(a) if a.size else None, a.shape[0]))
+
+    def last_words(self, with_text: bool = False):
+        """The words of the last synchronous decode with option word_timestamps (WORD_DTYPE records, in clip order); with
+        with_text also the list of their decoded bytes."""
+        n = lib().wt_last_words(self._h, None, 0)
+        if n < 0:
+            raise WtError(-n, "no words: the last synchronous decode ran without word_timestamps")
+        out = np.zeros(n, WORD_DTYPE)
+        if n:
+            lib().wt_last_words(self._h, out.ctypes.data_as(c_void_p), n)
+        if not with_text:
+            return out
+        texts = []
+        for i in range(n):
+            buf = ctypes.create_string_buffer(1 << 12)
+            ln = c_size_t(0)
+            self._check(lib().wt_last_word_text(self._h, i, buf, len(buf), byref(ln)))
+            texts.append(buf.raw[: ln.value])
+        return out, texts
+
+    def dbg_set_alignment(self, keep=-1, mode=-1, sub=-1) -> None:
+        """Handles of the alignment pass (wt_dbg_set_alignment): keep what it forms for dbg_last_alignment, the form of
+        align_scores (0 / 1), the most clips per sub-group (0 = by the workspace bound); -1 leaves a setting alone."""
+        self._check(lib().wt_dbg_set_alignment(self._h, int(keep), int(mode), int(sub)))
+
+    def dbg_last_alignment(self, clip: int) -> dict:
+        """What the alignment pass of the last decode with word_timestamps = 1 behind dbg_set_alignment(keep=1) formed for one clip:
+        row [L], W [heads][L][T], C [N][T], jump [N] and the counts n_a, L, N, F, heads, T."""
+        dims = np.zeros(6, np.int32)
+        self._check(lib().wt_dbg_last_alignment(self._h, int(clip), _ip32(dims), None, None, None, None))
+        n_a, L, N, F, heads, T = (int(v) for v in dims)
+        row, W = np.zeros(L, np.int64), np.zeros((heads, L, T), np.float32)
+        C, jump = np.zeros((N, T), np.float32), np.zeros(N, np.int32)
+        self._check(lib().wt_dbg_last_alignment(self._h, int(clip), _ip32(dims), _ip64(row), _fp(W), _fp(C), _ip32(jump)))
+        return dict(n_a=n_a, L=L, N=N, F=F, heads=heads, T=T, row=row, W=W, C=C, jump=jump)
+
+    def dbg_align_scores(self, qp, E, head, slot, F, W, pos0=0, mode=1):
+        """align_scores (k_align.hip): qp [np][batch][H * d] absorbed queries of one pass, E [batch]
+        [T][d] encoder output, head / slot the layer's alignment heads and their places in W's head axis, F [batch]
+        valid frames; W [batch][heads_total][L_max][ld] is the output buffer as given (in / out).  Returns the buffer
+        with W[b][slot][pos0 + p][t < T] = softmax over t < F[b] of q'_head(p, b) . e_t written into it.  mode: 0 = the
+        fused kernel, 1 = frame chunks and the row softmax kernel."""
+        qp, E, W = _f32(qp), _f32(E), _f32(W).copy()
+        n_pos, batch, hd = qp.shape
+        T, d = E.shape[1], E.shape[2]
+        head, slot = np.ascontiguousarray(head, dtype=np.int32), np.ascontiguousarray(slot, dtype=np.int32)
+        F = np.ascontiguousarray(F, dtype=np.int32)
+        assert E.shape[0] == batch and hd == (d // 64) * d and W.shape[0] == batch and W.ndim == 4
+        assert head.shape == slot.shape and F.shape == (batch,)
+        self._check(lib().wt_dbg_align_scores(self._h, batch, d // 64, T, n_pos, int(pos0), _fp(qp), _fp(E), head.size,
+                                              _ip32(head), _ip32(slot), W.shape[1], _ip32(F), W.shape[2], W.shape[3],
+                                              _fp(W), int(mode)))
+        return W
+
+    def dbg_align_matrix(self, W, L, F, n_a, N_max=None, C=None, stats=None):
+        """The two stage kernels of the alignment (k_align.hip): W [clips][heads][L_max][ld]
+        attention weights, L [clips] fed positions and F [clips] valid frames -> (C [clips][N_max][ld], the cost of the
+        rows n_a .. L[b] - 2; stats [clips][heads][2][ld], mean and 1 / std).  C and stats are in / out: cells the kernels
+        do not write keep what the given arrays hold (zeros when None)."""
+        W = _f32(W)
+        clips, heads, L_max, ld = W.shape
+        L, F = np.ascontiguousarray(L, dtype=np.int32), np.ascontiguousarray(F, dtype=np.int32)
+        N_max = int(L.max()) - n_a - 1 if N_max is None else int(N_max)
+        C = np.zeros((clips, max(N_max, 0), ld), np.float32) if C is None else _f32(C).copy()
+        stats = np.zeros((clips, heads, 2, ld), np.float32) if stats is None else _f32(stats).copy()
+        assert L.shape == (clips,) and F.shape == (clips,) and C.shape == (clips, N_max, ld) and stats.shape == (clips, heads, 2, ld)
+        self._check(lib().wt_dbg_align_matrix(self._h, clips, heads, L_max, ld, int(n_a), N_max, _fp(W), _ip32(L), _ip32(F),
+                                              _fp(C), _fp(stats)))
+        return C, stats
+
+    def dbg_align_dtw(self, C, N, F, jump=None, trace=None):
+        """align_dtw (k_align.hip): C [clips][N_max][ld], N [clips] rows and F [clips] frames per clip -> (jump int32
+        [clips][N_max], trace uint8 [clips][N_max][ld]); both in / out as dbg_align_matrix's."""
+        C = _f32(C)
+        clips, N_max, ld = C.shape
+        N, F = np.ascontiguousarray(N, dtype=np.int32), np.ascontiguousarray(F, dtype=np.int32)
+        jump = np.zeros((clips, N_max), np.int32) if jump is None else np.ascontiguousarray(jump, dtype=np.int32).copy()
+        trace = np.zeros((clips, N_max, ld), np.uint8) if trace is None else np.ascontiguousarray(trace, dtype=np.uint8).copy()
+        assert N.shape == (clips,) and F.shape == (clips,) and jump.shape == (clips, N_max) and trace.shape == C.shape
+        self._check(lib().wt_dbg_align_dtw(self._h, clips, N_max, ld, _fp(C), _ip32(N), _ip32(F), _ip32(jump),
+                                           trace.ctypes.data_as(POINTER(ctypes.c_uint8))))
+        return jump, trace
 
     def dbg_sample_select(self, logits, ids, n_ids, sample_begin, temperature, seed=0, attempt=0, clip_base=0, pos=-1,
                           timestamps=False, eot=0, beg=1, max_initial_timestamp=50):

@@ -44,12 +44,17 @@ void usage(const char* argv0) {
             << "  --seek          with --long --timestamps: every window starts at the last closed timestamp of the one\n"
             << "                  before and is decoded behind the text kept so far (Whisper's transcribe loop)\n"
             << "  --no-condition  with --seek: do not feed the previous windows' text to the next (condition_on_previous_text = 0)\n"
-            << "  --context-ids 1,2,3  with --max-positions: token ids fed in front of the prompt (Whisper's initial_prompt)\n";
+            << "  --context-ids 1,2,3  with --max-positions: token ids fed in front of the prompt (Whisper's initial_prompt)\n"
+            << "  --word-timestamps  with --timestamps: align every word to the audio and print, behind the segment lines,\n"
+            << "                  one line per word: t0 t1 text (seconds)\n"
+            << "  --alignment-heads 2:2,3:0,...  with --word-timestamps: the layer:head pairs to align on (default: every\n"
+            << "                  head of the upper half of the decoder layers)\n";
 }
 }  // namespace
 
 int main(int argc, char* argv[]) {
-  std::string model_prefix, vocab, input, lang, beam, max_positions, temperature, seed, cr_threshold, context_ids;
+  std::string model_prefix, vocab, input, lang, beam, max_positions, temperature, seed, cr_threshold, context_ids, alignment_heads;
+  bool word_timestamps = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
        no_condition = false;
   for (int i = 1; i < argc; ++i) {
@@ -72,6 +77,10 @@ int main(int argc, char* argv[]) {
     }
     if (a == "--scores") {
       scores = true;
+      continue;
+    }
+    if (a == "--word-timestamps") {
+      word_timestamps = true;
       continue;
     }
     if (a == "--skip-silence") {
@@ -110,6 +119,7 @@ int main(int argc, char* argv[]) {
     else if (a == "--seed") seed = v;
     else if (a == "--compression-ratio-threshold") cr_threshold = v;
     else if (a == "--context-ids") context_ids = v;
+    else if (a == "--alignment-heads") alignment_heads = v;
     else {
       std::cerr << "The following argument was not expected: " << a << "\n";
       usage(argv[0]);
@@ -270,6 +280,34 @@ int main(int argc, char* argv[]) {
       return 105;
     }
   }
+  if (word_timestamps || !alignment_heads.empty()) {
+    if (!word_timestamps || !timestamps) {
+      std::cerr << (word_timestamps ? "--word-timestamps requires --timestamps\n" : "--alignment-heads requires --word-timestamps\n");
+      return 105;
+    }
+    std::vector<int32_t> pairs;  // layer:head,layer:head,...
+    for (size_t at = 0; at < alignment_heads.size();) {
+      char* end = nullptr;
+      const long l = std::strtol(alignment_heads.c_str() + at, &end, 10);
+      if (end == alignment_heads.c_str() + at || *end != ':') {
+        pairs.clear(), pairs.push_back(-1), pairs.push_back(-1);
+        break;
+      }
+      const char* const hs = end + 1;
+      const long hd = std::strtol(hs, &end, 10);
+      if (end == hs || (*end && *end != ',')) {
+        pairs.clear(), pairs.push_back(-1), pairs.push_back(-1);
+        break;
+      }
+      pairs.push_back(int32_t(l)), pairs.push_back(int32_t(hd));
+      at = size_t(end - alignment_heads.c_str()) + (*end ? 1 : 0);
+    }
+    if (wt_engine_set_alignment_heads(encdec.handle(), pairs.data(), int(pairs.size() / 2)) != WT_OK ||
+        wt_engine_set_option(encdec.handle(), "word_timestamps", 1) != WT_OK) {
+      std::cerr << "--word-timestamps: " << wt_last_error(encdec.handle()) << "\n";
+      return 105;
+    }
+  }
   std::string text;
   if (long_audio) {
     std::vector<float> pcm = wav_read_legacy(input.c_str());
@@ -321,6 +359,21 @@ int main(int argc, char* argv[]) {
       std::cout << "[" << stamp(s.t0_ms) << " --> " << stamp(s.t1_ms) << "] " << s.text;
       if (scores) std::cout << " (avg_logprob=" << s.avg_logprob << ")";
       std::cout << "\n";
+    }
+    if (word_timestamps) {  // behind the segment lines, one line per word: t0 t1 text
+      const int n = wt_last_words(encdec.handle(), nullptr, 0);
+      std::vector<wt_word> words(size_t(std::max(n, 0)));
+      if (n > 0) wt_last_words(encdec.handle(), words.data(), n);
+      for (int i = 0; i < n; ++i) {
+        size_t len = 0;
+        wt_last_word_text(encdec.handle(), i, nullptr, 0, &len);  // the length first: a word is as long as its ids make it
+        std::string word(len + 1, '\0');
+        wt_last_word_text(encdec.handle(), i, &word[0], word.size(), &len);
+        word.resize(len);
+        char line[64];
+        std::snprintf(line, sizeof line, "%.2f %.2f ", words[size_t(i)].t0_ms / 1000.0, words[size_t(i)].t1_ms / 1000.0);
+        std::cout << line << word << "\n";
+      }
     }
     return 0;
   }

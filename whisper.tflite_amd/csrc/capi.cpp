@@ -19,6 +19,7 @@
 #include "longform.h"
 #include "tflite_extract.h"
 #include "weights_gen.h"
+#include "words.h"
 
 namespace {
 thread_local std::string g_create_error;
@@ -233,6 +234,10 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
   } else if (k == "condition_on_previous_text") {
     if (value != 0 && value != 1) return fail(h, WT_ERR_INVALID_ARG, "condition_on_previous_text must be 0 or 1");
     e.condition_on_previous_text = value;
+  } else if (k == "word_timestamps") {
+    // word-level timestamps: the alignment pass behind a timestamp decode
+    if (value != 0 && value != 1) return fail(h, WT_ERR_INVALID_ARG, "word_timestamps must be 0 or 1");
+    e.word_timestamps = value;
   } else if (k == "stop_at_eot") {
     e.stop_at_eot = value != 0;
   } else if (k == "verbose") {
@@ -313,6 +318,16 @@ int wt_engine_set_context(wt_engine* h, const int64_t* ids, int n) {
   return WT_OK;
 }
 
+int wt_engine_set_alignment_heads(wt_engine* h, const int32_t* layer_head, int n) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  try {
+    h->impl->set_alignment_heads(layer_head, n);
+  } catch (const wt::Error& err) {
+    return fail(h, err.code, err.what());
+  }
+  return WT_OK;
+}
+
 int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   if (!h || !key || !value) return WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
@@ -334,6 +349,8 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "prompt_group") *value = e.prompt_group;
   else if (k == "seek") *value = e.seek;
   else if (k == "condition_on_previous_text") *value = e.condition_on_previous_text;
+  else if (k == "word_timestamps") *value = e.word_timestamps;
+  else if (k == "alignment_heads") *value = long(e.alignment_heads_in_effect().size());  // read-only: the count in effect
   else if (k == "context_ids") *value = long(e.context_ids.size());  // read-only: ids kept by wt_engine_set_context
   else if (k == "graphs_cached") *value = e.graphs_cached();          // read-only: captured decoder graphs held
   else if (k == "stop_at_eot") *value = e.stop_at_eot;
@@ -626,6 +643,25 @@ int wt_last_segment_text(const wt_engine* h, int index, char* out, size_t cap, s
   return copy_text(e.last_segment_text[size_t(index)], out, cap, len);
 }
 
+int wt_last_words(const wt_engine* h, wt_word* out, int cap) {
+  static_assert(sizeof(wt_word) == sizeof(wt::Engine::Word), "wt_word mirrors wt::Engine::Word");
+  if (!h || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_words_valid) return -WT_ERR_INVALID_ARG;
+  for (int i = 0; i < int(e.last_words.size()) && i < cap; ++i) std::memcpy(&out[i], &e.last_words[size_t(i)], sizeof(wt_word));
+  return int(e.last_words.size());
+}
+
+int wt_last_word_text(const wt_engine* h, int index, char* out, size_t cap, size_t* len) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_words_valid || index < 0 || size_t(index) >= e.last_word_text.size()) {
+    if (len) *len = 0;
+    return WT_ERR_INVALID_ARG;
+  }
+  return copy_text(e.last_word_text[size_t(index)], out, cap, len);
+}
+
 int wt_last_scores(const wt_engine* h, wt_clip_score* out, int cap) {
   static_assert(sizeof(wt_clip_score) == sizeof(wt::ClipScore), "wt_clip_score mirrors wt::ClipScore");
   if (!h || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
@@ -779,7 +815,8 @@ int wt_transcribe_pcm(wt_engine* h, const float* pcm, size_t n_samples, char* ou
     int32_t n = 0;
     if (full) {
       e.encode_full(d_mel, 1);
-      e.decode_full(1, ids.data(), int(ids.size()), &n);
+      const std::vector<long long> valid{(long long)std::min(n_samples, clip.size())};  // word timestamps: the window's own frames
+      e.decode_full(1, ids.data(), int(ids.size()), &n, &valid);
     } else {
       e.encode(d_mel, 1);
       e.decode(1, ids.data(), &n, nullptr, 0);
@@ -820,6 +857,8 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
     std::vector<wt::ClipScore> scores;  // option scores: every window's
     std::vector<float> token_logprob, segment_score;
     std::vector<wt::Engine::ClipDecode> decode_info;  // sampling / fall-back: every window's
+    std::vector<wt::Engine::Word> words;  // option word_timestamps: every window's, clip = window index, times in the file
+    std::vector<std::string> word_text;
     struct ClipBase {  // a window's Philox clip index is its index in the file, however the windows are batched
       wt::Engine& e;
       ~ClipBase() { e.clip_base = 0; }
@@ -842,7 +881,12 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
       if (full) {
         e.encode_full(d_mel, B);
         e.clip_base = long(w0);
-        e.decode_full(B, ids.data(), int(row), n.data());
+        std::vector<long long> valid;
+        for (int b = 0; b < B; ++b) {
+          const size_t off = (w0 + b) * win;
+          valid.push_back(off < n_samples ? (long long)std::min(win, n_samples - off) : 0);
+        }
+        e.decode_full(B, ids.data(), int(row), n.data(), &valid);
       } else {
         e.encode(d_mel, B);
         e.decode(B, ids.data(), n.data(), nullptr, 0);
@@ -852,6 +896,15 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
       if (e.last_lang_valid) {
         langs.insert(langs.end(), e.last_lang.begin(), e.last_lang.end());
         lang_probs.insert(lang_probs.end(), e.last_lang_prob.begin(), e.last_lang_prob.end());
+      }
+      if (e.last_words_valid) {  // (before the segments are renumbered: a word's segment index counts in the whole file)
+        for (wt::Engine::Word wd : e.last_words) {
+          wd.clip += int(w0);
+          wd.segment += int(segments.size());
+          wd.t0_ms += wt::kWindowMs * wd.clip, wd.t1_ms += wt::kWindowMs * wd.clip;
+          words.push_back(wd);
+        }
+        word_text.insert(word_text.end(), e.last_word_text.begin(), e.last_word_text.end());
       }
       if (e.last_segments_valid) {
         for (wt::Segment sg : e.last_segments) {
@@ -878,6 +931,7 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
     if (e.last_decode_info_valid) e.last_decode_info = decode_info;
     if (e.last_lang_valid) e.last_lang = langs, e.last_lang_prob = lang_probs;
     if (e.last_segments_valid) e.last_segments = segments, e.last_segment_text = segment_text;
+    if (e.last_words_valid) e.last_words = words, e.last_word_text = word_text;
   });
   if (rc != WT_OK) {
     if (len) *len = 0;
@@ -1027,6 +1081,40 @@ int wt_vocab_seek_step(const wt_vocab* v, const int64_t* g, int n, int win_ticks
   std::vector<wt::Segment> segs;
   *advance_ticks = wt::seek_step(v->vocab, g, n, win_ticks, seg_ticks, &segs);
   return copy_segments(segs, out, cap);
+}
+
+static int copy_counts(const std::vector<int>& counts, int32_t* out, int cap) {
+  for (int i = 0; i < int(counts.size()) && i < cap; ++i) out[i] = counts[size_t(i)];
+  return int(counts.size());
+}
+
+int wt_vocab_split_words(const wt_vocab* v, const int64_t* ids, int n, int unicode_only, int32_t* word_len_out, int cap) {
+  if (!v || n < 0 || (!ids && n) || cap < 0 || (cap > 0 && !word_len_out)) return -WT_ERR_INVALID_ARG;
+  return copy_counts(wt::split_words(v->vocab, ids, n, unicode_only != 0), word_len_out, cap);
+}
+
+int wt_vocab_merge_punctuation(const wt_vocab* v, const int64_t* ids, int n, const int32_t* word_len, int n_words,
+                               int32_t* merged_len_out, int cap) {
+  if (!v || n < 0 || (!ids && n) || n_words < 0 || (!word_len && n_words) || cap < 0 || (cap > 0 && !merged_len_out)) {
+    return -WT_ERR_INVALID_ARG;
+  }
+  long total = 0;
+  for (int k = 0; k < n_words; ++k) {
+    if (word_len[k] < 1) return -WT_ERR_INVALID_ARG;
+    total += word_len[k];
+  }
+  if (total != n) return -WT_ERR_INVALID_ARG;
+  return copy_counts(wt::merge_punctuation(v->vocab, ids, n, word_len, n_words), merged_len_out, cap);
+}
+
+int wt_dtw_path(const float* cost, int N, int F, int32_t* jump, int32_t* path_out, int path_cap) {
+  if (!cost || !jump || N < 1 || N > 447 || F < 1 || F > 1500 || path_cap < 0 || (path_cap > 0 && !path_out)) {
+    return -WT_ERR_INVALID_ARG;
+  }
+  std::vector<int32_t> path;
+  const int cells = wt::dtw_path(cost, N, F, F, jump, path_out ? &path : nullptr, nullptr);
+  if (path_out) std::memcpy(path_out, path.data(), size_t(std::min(cells, path_cap)) * 2 * sizeof(int32_t));
+  return cells;
 }
 
 // ------------------------------------------- log-mel as a free function ---

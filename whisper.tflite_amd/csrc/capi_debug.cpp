@@ -1499,4 +1499,91 @@ int wt_dbg_encoder_attention_at(wt_engine* h, int kind, int variant, int batch, 
   });
 }
 
+int wt_dbg_align_scores(wt_engine* h, int batch, int H, int T, int np, int pos0, const float* qp, const float* E, int n_heads,
+                        const int32_t* head, const int32_t* slot, int heads_total, const int32_t* F, int L_max, int ld, float* W,
+                        int mode) {
+  if (!h || !qp || !E || !head || !slot || !F || !W || batch < 1 || batch > wt::kAlignClipsMax || H < 1 || T < 1 || np < 1 ||
+      n_heads < 0 || n_heads > wt::kAlignLayerHeadsMax || heads_total < 1 || L_max < 1 || ld < 1) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const size_t d = size_t(H) * 64, ne = size_t(batch) * T * d;
+    const float se = wt::f16_scale_for(max_abs(E, ne));
+    const DevArr<unsigned short> dE(to_f16_planes(E, ne, se, 64));
+    DevArr<float> dq(size_t(np) * batch * H * d, qp), dW(size_t(batch) * heads_total * L_max * ld, W);
+    wt::AlignScoresArgs a;
+    a.qp = dq.p; a.e = dE.p; a.e_plane = long(ne + 64); a.e_scale = se;
+    a.batch = batch; a.H = H; a.d_model = int(d); a.T = T; a.np = np; a.pos0 = pos0; a.n_heads = n_heads;
+    for (int i = 0; i < n_heads; ++i) a.head[i] = head[i], a.slot[i] = slot[i];
+    for (int b = 0; b < batch; ++b) a.F[b] = F[b];
+    a.W = dW.p; a.heads_total = heads_total; a.L_max = L_max; a.ldw = ld; a.mode = mode;
+    wt::launch_align_scores(a, h->impl->stream());
+    h->impl->sync();
+    dW.to_host(W);
+  });
+}
+
+int wt_dbg_align_matrix(wt_engine* h, int clips, int heads, int L_max, int ld, int n_a, int N_max, const float* W,
+                        const int32_t* L, const int32_t* F, float* C, float* stats) {
+  if (!h || !W || !L || !F || !C || clips < 1 || heads < 1 || L_max < 1 || ld < 1 || n_a < 0 || N_max < 1) return WT_ERR_INVALID_ARG;
+  for (int b = 0; b < clips; ++b) {
+    if (L[b] < n_a + 2 || L[b] > L_max || F[b] < 1 || F[b] > ld || L[b] - n_a - 1 > N_max) return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const size_t bh = size_t(clips) * heads;
+    DevArr<float> dW(bh * L_max * ld, W), dC(size_t(clips) * N_max * ld, C), dS(bh * 2 * ld, stats);
+    DevArr<int> dL(clips, L), dF(clips, F);
+    wt::AlignMatrixArgs a;
+    a.W = dW.p; a.clips = clips; a.heads = heads; a.L_max = L_max; a.ldw = ld;
+    a.L = dL.p; a.F = dF.p; a.n_a = n_a; a.stats = dS.p; a.C = dC.p; a.N_max = N_max; a.ldc = ld;
+    wt::launch_align_matrix(a, h->impl->stream());
+    h->impl->sync();
+    dC.to_host(C);
+    dS.to_host(stats);
+  });
+}
+
+int wt_dbg_align_dtw(wt_engine* h, int clips, int N_max, int ld, const float* C, const int32_t* N, const int32_t* F,
+                     int32_t* jump, uint8_t* trace) {
+  if (!h || !C || !N || !F || !jump || clips < 1 || N_max < 1 || ld < 1) return WT_ERR_INVALID_ARG;
+  for (int b = 0; b < clips; ++b) {
+    if (N[b] < 0 || N[b] > N_max || F[b] < 1 || F[b] > ld) return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const size_t cells = size_t(clips) * N_max * ld;
+    DevArr<float> dC(cells, C);
+    DevArr<unsigned char> dT(cells, trace);
+    DevArr<int> dN(clips, N), dF(clips, F), dJ(size_t(clips) * N_max, jump);
+    wt::AlignDtwArgs a;
+    a.C = dC.p; a.clips = clips; a.N_max = N_max; a.ldc = ld; a.N = dN.p; a.F = dF.p; a.trace = dT.p; a.jump = dJ.p;
+    wt::launch_align_dtw(a, h->impl->stream());
+    h->impl->sync();
+    dJ.to_host(jump);
+    dT.to_host(trace);
+  });
+}
+
+int wt_dbg_set_alignment(wt_engine* h, int keep, int mode, int sub) {
+  if (!h || keep > 1 || mode > 1 || sub > wt::kAlignClipsMax) return WT_ERR_INVALID_ARG;
+  wt::Engine& e = *h->impl;
+  if (keep >= 0) e.keep_alignment = keep;
+  if (mode >= 0) e.align_mode = mode;
+  if (sub >= 0) e.align_sub = sub;
+  return WT_OK;
+}
+
+int wt_dbg_last_alignment(const wt_engine* h, int clip, int32_t dims[6], int64_t* row, float* W, float* C, int32_t* jump) {
+  if (!h || clip < 0 || size_t(clip) >= h->impl->last_alignment.size()) return WT_ERR_INVALID_ARG;
+  const wt::Engine::ClipAlignment& a = h->impl->last_alignment[size_t(clip)];
+  if (dims) {
+    const int32_t v[6] = {a.n_a, a.L, a.N, a.F, a.heads, a.T};
+    std::memcpy(dims, v, sizeof(v));
+  }
+  if (row) std::copy(a.row.begin(), a.row.end(), row);
+  if (W) std::copy(a.W.begin(), a.W.end(), W);
+  if (C) std::copy(a.C.begin(), a.C.end(), C);
+  if (jump) std::copy(a.jump.begin(), a.jump.end(), jump);
+  return WT_OK;
+}
+
 }  // extern "C"

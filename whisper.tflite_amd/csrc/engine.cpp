@@ -15,6 +15,7 @@
 #include <stdexcept>
 
 #include "kernels.h"
+#include "words.h"
 
 namespace wt {
 
@@ -874,6 +875,9 @@ void Engine::release() noexcept {
                   static_cast<void*>(fw_.h_count), static_cast<void*>(fw_.h_prm)})
     if (p) (void)hipHostFree(p);
   fw_ = FullWorkspace();
+  for (void* p : {static_cast<void*>(aw_.h_jump), static_cast<void*>(aw_.h_lfn)})
+    if (p) (void)hipHostFree(p);
+  aw_ = AlignWorkspace();  // (its device buffers are in allocations_)
   for (void* p : {static_cast<void*>(h_lang_probs_), static_cast<void*>(h_lang_prob_), static_cast<void*>(h_lang_)})
     if (p) (void)hipHostFree(p);
   h_lang_probs_ = nullptr, h_lang_prob_ = nullptr, h_lang_ = nullptr;
@@ -2000,6 +2004,17 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
       qa.bf16 = bf; qa.Wt = w.wq_abs.w; qa.w_scale = w.wq_abs.scale; qa.N = H * d; qa.K = d; qa.B = B; qa.M = M;
       qa.xin = x; qa.ln_g = w.cross_ln_g; qa.ln_b = w.cross_ln_b; qa.bias = w.bq_abs; qa.Y = dw.qp; qa.ldy = H * d;
       timed(tm, 3, [&] { launch_dec_gemm(qa, kProLn, kDecBias, st); });
+      if (p.align && !p.align->layer[size_t(l)].empty()) {  // word timestamps: keep this layer's alignment heads' weights
+        const AlignSink& sk = *p.align;
+        AlignScoresArgs as;
+        as.qp = dw.qp; as.e = p.e; as.e_plane = long(ws_.batch) * T * d; as.e_scale = sc_cross_kv_.a;
+        as.batch = p.clips; as.H = H; as.d_model = d; as.T = T; as.np = p.np; as.pos0 = p.pos0;
+        as.n_heads = int(sk.layer[size_t(l)].size());
+        for (int i = 0; i < as.n_heads; ++i) as.head[i] = sk.layer[size_t(l)][size_t(i)].first, as.slot[i] = sk.layer[size_t(l)][size_t(i)].second;
+        for (int b = 0; b < p.clips; ++b) as.F[b] = sk.F[b];
+        as.W = sk.W; as.heads_total = sk.heads_total; as.L_max = sk.L_max; as.ldw = sk.ldw; as.mode = int(align_mode);
+        launch_align_scores(as, st);
+      }
       const int nq_max = cross_absorbed_max_nq(H), nq_all = M / p.clips;
       for (int p0 = 0; p0 < nq_all; p0 += nq_max) {
         CrossAbsorbedArgs ca;
@@ -2540,10 +2555,48 @@ void Engine::check_timestamp_call() const {
   if (!context_ids.empty() && max_positions <= 0) {
     throw Error(kErrUnsupported, "context: full-length decoding only, set the option max_positions (32 .. n_text_ctx) or clear the context");
   }
+  check_word_call();
   if (temperature_fallback && !scores) throw Error(kErrUnsupported, "temperature_fallback: needs the option scores = 1");
   if (temperature_fallback && compression_ratio_threshold != 0 && !zlib_available()) {
     throw Error(kErrUnsupported, "compression_ratio_threshold: libz.so.1 could not be loaded; set the threshold to 0 (off)");
   }
+}
+
+void Engine::check_word_call() const {
+  if (!word_timestamps) return;
+  auto no = [](const char* why) { throw Error(kErrUnsupported, std::string("word_timestamps: ") + why); };
+  if (!timestamps || max_positions <= 0) no("needs the options timestamps = 1 and max_positions (32 .. n_text_ctx)");
+  if (!cross_absorb) no("needs the absorbed cross-attention (cross_absorb = 1)");
+  if (!absorb_active()) no("the absorbed cross-attention is not available with these weights or this gemm_variant");
+  if (vocab_.token_not < 0 || vocab_.token_not >= dims_.n_vocab) no("the model's vocabulary has no <|notimestamps|> id");
+  if (dims_.n_audio_ctx % 4 != 0 || dims_.n_audio_ctx > kAlignFramesMax) no("n_audio_ctx must be a multiple of 4, at most 1500");
+  if (alignment_heads.empty() && (dims_.n_text_layer - dims_.n_text_layer / 2) * dims_.n_text_head > kAlignHeadsMax) {
+    no("the default of every head of the upper layers is more than 128 heads: set them with wt_engine_set_alignment_heads");
+  }
+}
+
+void Engine::set_alignment_heads(const int32_t* layer_head, int n) {
+  if (n < 0 || n > kAlignHeadsMax || (n > 0 && !layer_head)) throw Error(kErrInvalidArg, "alignment heads: 0 (the default) to 128 (layer, head) pairs");
+  std::vector<std::pair<int, int>> v;
+  for (int i = 0; i < n; ++i) {
+    const std::pair<int, int> lh{layer_head[2 * i], layer_head[2 * i + 1]};
+    if (lh.first < 0 || lh.first >= dims_.n_text_layer || lh.second < 0 || lh.second >= dims_.n_text_head) {
+      throw Error(kErrInvalidArg, "alignment heads: a (layer, head) pair outside the model");
+    }
+    if (std::find(v.begin(), v.end(), lh) != v.end()) throw Error(kErrInvalidArg, "alignment heads: a pair is listed twice");
+    v.push_back(lh);
+  }
+  alignment_heads = v;
+}
+
+std::vector<std::pair<int, int>> Engine::alignment_heads_in_effect() const {
+  std::vector<std::pair<int, int>> v = alignment_heads;
+  if (v.empty()) {
+    for (int l = dims_.n_text_layer / 2; l < dims_.n_text_layer; ++l)
+      for (int h = 0; h < dims_.n_text_head; ++h) v.emplace_back(l, h);
+  }
+  std::sort(v.begin(), v.end());
+  return v;
 }
 
 // zlib through dlopen: no header and no link-time dependency a machine may lack
@@ -2704,7 +2757,7 @@ void Engine::ensure_full_workspace(int batch) {
 // cross-attention form is the one the slot's encoder pass prepared.  The chain is enqueued in segments of 32 positions;
 // a segment's launch sequence is fixed for its key and replayed from a hipGraph of the calling slot.  After each
 // segment the finished flags come back, and the chain ends once every clip has emitted EOT (stop_at_eot = 1).
-void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids) {
+void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids, const std::vector<long long>* valid_samples) {
   require_idle();
   check_full_args(batch, ids_stride);
   const int P = int(max_positions), slot_idx = last_enc_slot_;
@@ -2712,6 +2765,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   beam_scores_valid = false;
   last_segments_valid = false;
   last_windows_valid = false;
+  last_words_valid = false;
+  last_alignment.clear();
   clear_last_scores();  // (the decode info with them)
   const bool ts = timestamps != 0, sc = scores != 0, smp = sampling();
   ensure_batch(batch);
@@ -2989,6 +3044,200 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     }
     last_segments_valid = true;
   }
+  if (word_timestamps && !defer_word_alignment) {
+    align_words(batch, last_segments, valid_samples ? *valid_samples : std::vector<long long>());
+  }
+}
+
+// Word-level timestamps: the alignment pass over the kept results of a timestamp decode.  Clips go
+// through in sub-groups whose weight workspace [clips][heads][L][T] stays below kAlignWeightBytes; a sub-group's rows are
+// fed in passes of kDecRowsMax / clips positions on self_attention_prefill and the absorbed cross-attention, eagerly (the
+// row lengths are launch constants, as a context's are), without logits.  The self-attention cache and the id rows are
+// the decode's own: its results are on the host by now.
+void Engine::align_words(int batch, const std::vector<Segment>& segs, const std::vector<long long>& valid_samples) {
+  Slot& slot = slots_[last_enc_slot_];
+  static_assert(kAlignClipsMax >= 64, "a full-length call has up to 64 clips");
+  const wtw::Dims& c = dims_;
+  const int T = c.n_audio_ctx, d = c.n_text_state, cap = full_cap(), stride = cap + 1;
+  const std::vector<long long> A = prompt();
+  const int n_a = int(A.size());
+  const std::vector<std::pair<int, int>> heads = alignment_heads_in_effect();
+  const int n_heads = int(heads.size());
+  const int text_cap = cap - n_a - 2;
+  if (text_cap < 1) throw Error(kErrInvalidArg, "word_timestamps: the prompt leaves no position for text");
+  const bool scored = scores != 0 && last_scores_valid;
+  const std::string lang = language >= 0 && language < language_count() ? lang_code(size_t(language)) : std::string("en");
+  const bool unicode_only = lang == "zh" || lang == "ja" || lang == "th" || lang == "lo" || lang == "my" || lang == "yue";
+
+  // ---- the rows: per clip the text ids of its segments (below EOT, timestamps removed) and where they sit in its id row
+  struct Clip {
+    std::vector<long long> text;
+    std::vector<int> at, seg;  // index in the id row, index in last_segments
+    int L = 0, N = 0, F = 0;
+  };
+  std::vector<Clip> clips(static_cast<size_t>(batch));
+  for (size_t i = 0; i < segs.size(); ++i) {
+    const Segment& sg = segs[i];
+    if (sg.clip < 0 || sg.clip >= batch || sg.id_begin < 0 || sg.id_begin + sg.id_count > stride) {
+      throw Error(kErrInvalidArg, "word_timestamps: a segment outside the call's id rows");
+    }
+    Clip& cl = clips[size_t(sg.clip)];
+    for (int k = 0; k < sg.id_count; ++k) {
+      const long long id = fw_.h_ids[size_t(sg.clip) * stride + sg.id_begin + k];
+      if (id >= vocab_.token_eot || int(cl.text.size()) >= text_cap) continue;
+      cl.text.push_back(id), cl.at.push_back(sg.id_begin + k), cl.seg.push_back(int(i));
+    }
+  }
+  int L_max = 0;
+  for (int b = 0; b < batch; ++b) {
+    Clip& cl = clips[size_t(b)];
+    cl.N = int(cl.text.size()) + 1;
+    cl.L = n_a + 1 + int(cl.text.size()) + 1;
+    const long long vs = size_t(b) < valid_samples.size() ? valid_samples[size_t(b)] : (long long)T * 320;
+    cl.F = int(std::min<long long>(T, std::max<long long>(1, vs / 320)));
+    L_max = std::max(L_max, cl.L);
+  }
+  const int N_max = L_max - n_a - 1;
+  for (int b = 0; b < batch; ++b) {  // rows padded with EOT: causality keeps the padding out of a clip's own positions
+    const Clip& cl = clips[size_t(b)];
+    long long* row = fw_.h_ids + size_t(b) * stride;
+    for (int i = 0; i < stride; ++i) row[i] = vocab_.token_eot;
+    std::copy(A.begin(), A.end(), row);
+    row[n_a] = vocab_.token_not;
+    std::copy(cl.text.begin(), cl.text.end(), row + n_a + 1);
+  }
+
+  // ---- workspaces (outside any capture; this pass captures nothing)
+  const size_t per_clip = size_t(n_heads) * L_max * T;
+  int sub = int(std::max<size_t>(1, std::min<size_t>(size_t(batch), kAlignWeightBytes / (per_clip * sizeof(float)))));
+  if (align_sub > 0) sub = int(std::min<long>(sub, align_sub));
+  auto grow = [&](auto*& ptr, size_t& have, size_t want) {
+    if (want <= have) return;
+    if (ptr) {
+      HIPCHK(hipStreamSynchronize(dec_stream_at(slot.dec)));
+      allocations_.erase(std::remove(allocations_.begin(), allocations_.end(), static_cast<void*>(ptr)), allocations_.end());
+      (void)hipFree(ptr);
+      ptr = nullptr, have = 0;
+    }
+    void* q = nullptr;
+    HIPCHK(hipMalloc(&q, want * sizeof(*ptr)));
+    allocations_.push_back(q);
+    ptr = static_cast<std::remove_reference_t<decltype(ptr)>>(q), have = want;
+  };
+  grow(aw_.W, aw_.w_elems, size_t(sub) * per_clip);
+  grow(aw_.stats, aw_.s_elems, size_t(sub) * n_heads * 2 * T);
+  {
+    const size_t want = size_t(batch) * N_max * T, had = aw_.c_elems;
+    grow(aw_.C, aw_.c_elems, want);
+    size_t t_have = had;
+    grow(aw_.trace, t_have, want);
+  }
+  if (!aw_.h_lfn) {  // (committed together, the last pointer is the sentinel: a failure half way leaves nothing behind)
+    void *j = nullptr, *l = nullptr, *hj = nullptr, *hl = nullptr;
+    const bool ok = hipMalloc(&j, size_t(64) * kAlignRowsMax * sizeof(int)) == hipSuccess &&
+                    hipMalloc(&l, size_t(3) * 64 * sizeof(int)) == hipSuccess &&
+                    hipHostMalloc(&hj, size_t(64) * kAlignRowsMax * sizeof(int), 0) == hipSuccess &&
+                    hipHostMalloc(&hl, size_t(3) * 64 * sizeof(int), 0) == hipSuccess;
+    if (!ok) {
+      (void)hipFree(j), (void)hipFree(l), (void)hipHostFree(hj), (void)hipHostFree(hl);
+      (void)hipGetLastError();
+      throw Error(kErrDevice, "word_timestamps: out of memory for the alignment workspace");
+    }
+    allocations_.push_back(j), allocations_.push_back(l);
+    aw_.jump = static_cast<int*>(j), aw_.lfn = static_cast<int*>(l);
+    aw_.h_jump = static_cast<int*>(hj), aw_.h_lfn = static_cast<int*>(hl);
+  }
+
+  DecWorkspace& dw = dws_[slot.dec];
+  hipStream_t const st = dec_stream_at(slot.dec);
+  for (int b = 0; b < batch; ++b) aw_.h_lfn[b] = clips[size_t(b)].L, aw_.h_lfn[64 + b] = clips[size_t(b)].F, aw_.h_lfn[128 + b] = clips[size_t(b)].N;
+  HIPCHK(hipMemcpyAsync(aw_.lfn, aw_.h_lfn, size_t(3) * 64 * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(fw_.ids, fw_.h_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
+  if (!slot.absorbed) {  // the decode ran the cached form: the planes the absorbed form reads, from the fp32 encoder output
+    launch_f32_to_planes(ws_.enc_out, slot.e_planes, long(ws_.batch) * T * d, long(batch) * T, d, &sc_cross_kv_.a, 0, st);
+  }
+  AlignSink sink;
+  sink.heads_total = n_heads; sink.L_max = L_max; sink.ldw = T; sink.W = aw_.W;
+  sink.layer.resize(size_t(c.n_text_layer));
+  for (int a = 0; a < n_heads; ++a) sink.layer[size_t(heads[size_t(a)].first)].emplace_back(heads[size_t(a)].second, a);
+  const size_t keep0 = last_alignment.size();  // (the seeking loop appends window after window)
+  if (keep_alignment) last_alignment.resize(keep0 + size_t(batch));
+  for (int c0 = 0; c0 < batch; c0 += sub) {
+    const int nb = std::min(sub, batch - c0);
+    for (int b = 0; b < nb; ++b) sink.F[b] = clips[size_t(c0 + b)].F;
+    DecPass p;
+    p.B = p.clips = nb; p.ids = fw_.ids + size_t(c0) * stride; p.ids_stride = stride; p.self_kv = fw_.kv; p.self_cap = cap;
+    p.absorbed = true; p.n_abs = abs_chunks_for(nb, 256); p.e = slot.e_planes + size_t(c0) * T * d;
+    p.split = fc2_split(); p.dw = &dw; p.self_prefill = true; p.align = &sink; p.best = nullptr;
+    const int group = std::max(1, kDecRowsMax / nb);
+    for (int pos0 = 0; pos0 < L_max; pos0 += group) {
+      p.pos0 = pos0; p.np = std::min(group, L_max - pos0);
+      decoder_pass(p, st);
+    }
+    AlignMatrixArgs am;
+    am.W = aw_.W; am.clips = nb; am.heads = n_heads; am.L_max = L_max; am.ldw = T; am.L = aw_.lfn + c0; am.F = aw_.lfn + 64 + c0;
+    am.n_a = n_a; am.stats = aw_.stats; am.C = aw_.C + size_t(c0) * N_max * T; am.N_max = N_max; am.ldc = T;
+    launch_align_matrix(am, st);
+    if (keep_alignment) {
+      HIPCHK(hipStreamSynchronize(st));
+      for (int b = 0; b < nb; ++b) {
+        ClipAlignment& ka = last_alignment[keep0 + size_t(c0 + b)];
+        const Clip& cl = clips[size_t(c0 + b)];
+        ka.n_a = n_a, ka.L = cl.L, ka.N = cl.N, ka.F = cl.F, ka.heads = n_heads, ka.T = T;
+        ka.row.assign(fw_.h_ids + size_t(c0 + b) * stride, fw_.h_ids + size_t(c0 + b) * stride + cl.L);
+        ka.W.resize(size_t(n_heads) * cl.L * T);
+        for (int a = 0; a < n_heads; ++a) {
+          HIPCHK(hipMemcpy(ka.W.data() + size_t(a) * cl.L * T, aw_.W + (size_t(b) * n_heads + a) * L_max * T, size_t(cl.L) * T * sizeof(float), hipMemcpyDeviceToHost));
+        }
+        ka.C.resize(size_t(cl.N) * T);
+        HIPCHK(hipMemcpy(ka.C.data(), aw_.C + size_t(c0 + b) * N_max * T, ka.C.size() * sizeof(float), hipMemcpyDeviceToHost));
+      }
+    }
+  }
+  AlignDtwArgs ad;
+  ad.C = aw_.C; ad.clips = batch; ad.N_max = N_max; ad.ldc = T; ad.N = aw_.lfn + 128; ad.F = aw_.lfn + 64; ad.trace = aw_.trace; ad.jump = aw_.jump;
+  launch_align_dtw(ad, st);
+  HIPCHK(hipMemcpyAsync(aw_.h_jump, aw_.jump, size_t(batch) * N_max * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+
+  // ---- words on the host
+  last_words.clear();
+  last_word_text.clear();
+  for (int b = 0; b < batch; ++b) {
+    const Clip& cl = clips[size_t(b)];
+    const int* jump = aw_.h_jump + size_t(b) * N_max;
+    if (keep_alignment) last_alignment[keep0 + size_t(b)].jump.assign(jump, jump + cl.N);
+    const int n_text = int(cl.text.size());
+    if (n_text == 0) continue;  // no segments (nothing decoded, or skip_silence blanked the clip): no words
+    std::vector<int64_t> ids(cl.text.begin(), cl.text.end());
+    ids.push_back(vocab_.token_eot);
+    std::vector<int> words = split_words(vocab_, ids.data(), n_text + 1, unicode_only);
+    // the final EOT served as the last end time; ids that share its word (none: a special id starts a word) stay
+    int covered = 0;
+    std::vector<int> kept;
+    for (int len : words) {
+      if (covered + len > n_text) len = n_text - covered;
+      if (len > 0) kept.push_back(len);
+      covered += len;
+    }
+    const std::vector<int> merged = merge_punctuation(vocab_, ids.data(), n_text, kept.data(), int(kept.size()));
+    int s0 = 0;
+    for (int len : merged) {
+      Word w{};
+      w.clip = b; w.segment = cl.seg[size_t(s0)];
+      w.t0_ms = jump[s0] * 20; w.t1_ms = jump[s0 + len] * 20;
+      w.id_begin = cl.at[size_t(s0)]; w.id_count = cl.at[size_t(s0 + len - 1)] - cl.at[size_t(s0)] + 1;
+      if (scored) {
+        double sum = 0.0;
+        for (int k = 0; k < len; ++k) sum += std::exp(double(last_token_logprob[size_t(b) * last_lp_stride + cl.at[size_t(s0 + k)]]));
+        w.probability = float(sum / double(len));
+      }
+      last_words.push_back(w);
+      last_word_text.push_back(decode_tokens(vocab_, ids.data() + s0, len, true, nullptr));
+      s0 += len;
+    }
+  }
+  last_words_valid = true;
 }
 
 }  // namespace wt

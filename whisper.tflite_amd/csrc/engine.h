@@ -8,6 +8,7 @@
 #include <map>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "error.h"
@@ -185,7 +186,8 @@ class Engine {
   void check_full_call() const;  // throws kErrUnsupported when max_positions is set and the options fall outside that scope
   // encoder output of the last encode() -> ids [batch][ids_stride] (prompt + generated, zero-padded), n_ids [batch];
   // ids_stride >= max_positions + 1, batch <= 64.  Synchronises.
-  void decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids);
+  // valid_samples (word timestamps): the samples each clip holds before its zero padding; nullptr = full-length clips
+  void decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids, const std::vector<long long>* valid_samples = nullptr);
   void encode_full(const float* d_mel, int batch);  // encode() into slot 0: the slot every full-length call uses
   // Timestamp decoding.  1: the default prompt ends before <|notimestamps|> and decode_full applies
   // Whisper's timestamp rules on the device (k_timestamps.hip) in place of select_token.  Full-length greedy decoding
@@ -279,6 +281,43 @@ class Engine {
   // Seeking long-audio transcription (wt_transcribe_long_pcm with seek = 1, longform.cpp): needs timestamps and
   // max_positions; condition_on_previous_text is read only then
   long seek = 0, condition_on_previous_text = 1;
+  // Word-level timestamps.  word_timestamps = 1 (needs timestamps = 1, max_positions and the absorbed
+  // cross-attention: check_word_call): after the decode, and after the fall-back loop, decode_full feeds every clip's
+  // row prompt() + [<|notimestamps|>] + text + [eot] through the decoder once more, teacher-forced, keeps the
+  // cross-attention weights of the alignment heads (align_scores), turns them into a cost matrix and a DTW path on the
+  // device (k_align.hip) and cuts the path into words on the host (words.cpp).
+  long word_timestamps = 0;
+  // measurement and test handles (wt_dbg_set_alignment): keep what the pass formed per clip; the form of align_scores (0
+  // fused softmax, 1 frame chunks + row kernel); clips per sub-group (0 = as many as kAlignWeightBytes allows)
+  long keep_alignment = 0, align_mode = 1, align_sub = 0;
+  std::vector<std::pair<int, int>> alignment_heads;  // (layer, head) pairs set by the caller; empty = Whisper's default
+  // n = 0 restores the default: every head of the layers n_text_layer / 2 .. n_text_layer - 1.  kErrInvalidArg for a pair
+  // outside the model, a duplicate or more than kAlignHeadsMax pairs.
+  void set_alignment_heads(const int32_t* layer_head, int n);
+  std::vector<std::pair<int, int>> alignment_heads_in_effect() const;  // sorted by (layer, head)
+  void check_word_call() const;  // throws kErrUnsupported when word_timestamps is set outside its scope
+  // The alignment pass over the id rows the last decode_full left on the host: segs = the segments whose ids below EOT
+  // are the clips' text (clip = index in that call, id_begin an index into the clip's id row), valid_samples = the
+  // samples of every clip (empty: full length).  Fills last_words (segment = index into segs) and, with keep_alignment,
+  // appends to last_alignment.  decode_full calls it with its own segments unless defer_word_alignment is set: the
+  // seeking loop sets that and aligns each window over the segments seek_step kept.
+  void align_words(int batch, const std::vector<Segment>& segs, const std::vector<long long>& valid_samples);
+  bool defer_word_alignment = false;
+  struct Word {  // (wt_word)
+    int32_t clip, segment, t0_ms, t1_ms, id_begin, id_count;
+    float probability;
+  };
+  std::vector<Word> last_words;
+  std::vector<std::string> last_word_text;
+  bool last_words_valid = false;
+  struct ClipAlignment {  // keep_alignment: what the alignment pass formed for one clip
+    std::vector<long long> row;  // the L ids fed
+    int n_a = 0, L = 0, N = 0, F = 0, heads = 0, T = 0;
+    std::vector<float> W, C;     // [heads][L][T], [N][T]
+    std::vector<int> jump;       // [N]
+  };
+  std::vector<ClipAlignment> last_alignment;
+
   struct Window {  // (wt_window)
     int64_t seek_sample;
     int32_t advance_samples, n_context, n_prompt, n_kept_ids, skipped, temperature_milli;
@@ -431,6 +470,14 @@ class Engine {
     SampleParams *sm_prm = nullptr, *h_prm = nullptr;
   } fw_;
   void ensure_full_workspace(int batch);
+  struct AlignWorkspace {  // allocated by the first call with word_timestamps, outside any capture
+    float *W = nullptr, *stats = nullptr, *C = nullptr;
+    size_t w_elems = 0, c_elems = 0, s_elems = 0;
+    unsigned char* trace = nullptr;
+    int *jump = nullptr, *lfn = nullptr;  // [64][kAlignRowsMax]; L | F | N [3][64]
+    int *h_jump = nullptr, *h_lfn = nullptr;  // pinned mirrors
+  } aw_;
+  static constexpr size_t kAlignWeightBytes = size_t(256) << 20;  // bound of the weight workspace: clips go through in sub-groups
   static constexpr long long kFullKey = -1000;  // first entry of a full-length segment's graph key
 
   int enc_cus_masked_ = 0;  // CUs the pipelined encoder stream may use
@@ -569,7 +616,14 @@ class Engine {
     int *n_ids = nullptr, *finished = nullptr;
   } dws_[kDecStreams + 1];  // one per decoder stream, + one for a chain on the encoder stream (kEncAsDec)
   // What a decode chain may vary in a decoder pass (decoder_pass: the one launch sequence of the decoder layers)
+  struct AlignSink {  // where a teacher-forced pass leaves the attention weights of the alignment heads
+    float* W = nullptr;  // [B][heads_total][L_max][ldw]
+    int heads_total = 0, L_max = 0, ldw = 0;
+    int F[64] = {};                                            // valid frames of the pass's clips (kAlignClipsMax)
+    std::vector<std::vector<std::pair<int, int>>> layer;       // per decoder layer: (head, slot in W's head axis)
+  };
   struct DecPass {
+    const AlignSink* align = nullptr;  // set: align_scores runs on dw.qp right after the qa GEMM of a layer that owns heads
     int pos0 = 0, np = 1;  // positions pos0 .. pos0 + np - 1
     int B = 0;             // rows per position (sequences): M = np * B rows, row = p * B + sequence
     const long long* ids = nullptr;  // id rows [B][ids_stride]

@@ -499,6 +499,60 @@ void launch_score_finish(const ScoreArgs& a, hipStream_t s);   // reads the reco
 // prob[b] = exp(z[b][nosp] - logsumexp(z[b][0 .. V - 1])): score_partial over the whole row + a finish kernel
 void launch_no_speech_prob(const ScoreArgs& a, int nosp, float* prob, hipStream_t s);
 
+// ------------------------------------------------------------- alignment ---
+// k_align.hip (word-level timestamps): from the cross-attention weights W of a teacher-forced pass
+// to the frame at which every text id begins.  Per-clip sizes are read from device memory; a size outside its array's
+// bounds is clamped to them by the kernels.
+constexpr int kAlignHeadsMax = 128;    // alignment heads of one call
+constexpr int kAlignRowsMax = 447;     // cost rows of a clip: <|notimestamps|> and its text ids
+constexpr int kAlignFramesMax = 1500;  // encoder frames of a clip
+constexpr int kAlignClipsMax = 64;     // clips of one launch
+constexpr int kAlignLayerHeadsMax = 8; // alignment heads of one layer (d_model <= 512)
+constexpr int kAlignChunkTiles = 8;    // mode 1: 16-frame tiles per block of align_scores (128 frames)
+struct AlignScoresArgs {
+  const float* qp = nullptr;       // [np * batch][H * d_model] absorbed queries of one pass of a layer, row = p * batch + b
+  const unsigned short* e = nullptr;  // E as fp16 planes [batch][T][d_model]: hi at e, lo at e + e_plane, times e_scale
+  long e_plane = 0;
+  float e_scale = 1.0f;
+  int batch = 0, H = 0, d_model = 0, T = 0;  // T % 4 == 0
+  int np = 0, pos0 = 0;            // the pass holds the fed positions pos0 .. pos0 + np - 1; np * batch <= 128
+  int n_heads = 0;                 // alignment heads of this layer
+  int head[kAlignLayerHeadsMax] = {}, slot[kAlignLayerHeadsMax] = {};  // their index in the layer and in W's head axis
+  int F[kAlignClipsMax] = {};      // valid frames of every clip, 1 .. T
+  float* W = nullptr;              // [batch][heads_total][L_max][ldw]: rows pos0 .. pos0 + np - 1 of the n_heads slots are
+  int heads_total = 0, L_max = 0, ldw = 0;  // written whole, frames < T; ldw % 4 == 0, 16-byte aligned
+  // 0: one wavefront sweeps all frames of its 16 columns, softmax in the same kernel; 1: blocks per chunk of
+  // kAlignChunkTiles tiles store the scores, align_softmax_rows normalises them (one more launch)
+  int mode = 1;
+};
+// W = softmax over t < F[b] of q' . e_t on the matrix cores, zero at F[b] <= t < T.  Head list and frame counts are
+// launch constants; a head or a slot listed twice is refused.  Throws kErrInvalidArg before anything is launched.
+void launch_align_scores(const AlignScoresArgs& a, hipStream_t s);
+struct AlignMatrixArgs {
+  const float* W = nullptr;   // [clips][heads][L_max][ldw]: softmax over the frames t < F[b], per head and fed position
+  int clips = 0, heads = 0, L_max = 0, ldw = 0;
+  const int* L = nullptr;     // device [clips]: fed positions of the clip, the rows its statistics run over
+  const int* F = nullptr;     // device [clips]: valid frames
+  int n_a = 0;                // cost row r is W's row n_a + r; a clip has N[b] = L[b] - n_a - 1 of them
+  float* stats = nullptr;     // [clips][heads][2][ldw]: mean, then 1 / std (population; 0 for a column of equal values)
+  float* C = nullptr;         // [clips][N_max][ldc]: rows < N[b], frames < F[b] are written, nothing else
+  int N_max = 0, ldc = 0;
+};
+// align_column_stats, then align_filter_mean: C = -mean over the heads (ascending) of median7(Z) with reflect padding
+// (no filter when F[b] <= 3), Z = (W - mean) / std.  Throws kErrInvalidArg.
+void launch_align_matrix(const AlignMatrixArgs& a, hipStream_t s);
+struct AlignDtwArgs {
+  const float* C = nullptr;        // [clips][N_max][ldc]
+  int clips = 0, N_max = 0, ldc = 0;
+  const int* N = nullptr;          // device [clips]: rows of the clip (0: nothing to align)
+  const int* F = nullptr;          // device [clips]: frames
+  unsigned char* trace = nullptr;  // [clips][N_max][ldc] workspace: the trace codes of the cells
+  int* jump = nullptr;             // [clips][N_max]: first frame of the path in each row < N[b], 0 behind them
+};
+// wt::dtw_path (words.h) per clip, bit for bit: one block per clip over the anti-diagonals, then the back-trace.
+// N_max <= kAlignRowsMax, ldc <= kAlignFramesMax, else kErrInvalidArg.
+void launch_align_dtw(const AlignDtwArgs& a, hipStream_t s);
+
 // ---- load-time re-layouts of decoder weights (host) ----
 // bf16 storage mode: W [N][K] fp32 -> ONE bf16 plane (round to nearest even) in the same fragment order,
 // [ceil(N/32)][K/16][64 lanes][8]

@@ -49,6 +49,7 @@ void transcribe_seek(Engine& e, const float* pcm, size_t n_samples, std::string*
   if (!e.timestamps || e.max_positions <= 0) {
     throw Error(kErrUnsupported, "seek: needs the options timestamps = 1 and max_positions (32 .. n_text_ctx)");
   }
+  e.check_word_call();
   if (e.condition_on_previous_text && !e.has_prev_token()) {
     throw Error(kErrUnsupported, "seek: condition_on_previous_text needs a vocabulary with <|startofprev|> and an EncDec engine");
   }
@@ -58,7 +59,7 @@ void transcribe_seek(Engine& e, const float* pcm, size_t n_samples, std::string*
   struct Restore {  // the caller's context and clip index come back however the loop ends
     Engine& e;
     std::vector<long long> context;
-    ~Restore() { e.context_ids = context, e.clip_base = 0; }
+    ~Restore() { e.context_ids = context, e.clip_base = 0, e.defer_word_alignment = false; }
   } restore{e, e.context_ids};
   std::vector<int64_t> ctx(e.context_ids.begin(), e.context_ids.end());
   std::vector<Segment> segments;
@@ -67,6 +68,10 @@ void transcribe_seek(Engine& e, const float* pcm, size_t n_samples, std::string*
   std::vector<float> token_logprob, segment_score;
   std::vector<Engine::ClipDecode> decode_info;
   std::vector<Engine::Window> windows;
+  std::vector<Engine::Word> words;  // option word_timestamps: every window's, aligned over the segments seek_step kept
+  std::vector<std::string> word_text;
+  std::vector<Engine::ClipAlignment> kept_alignment;
+  e.defer_word_alignment = true;  // decode_full leaves the id row; the pass runs below, once the kept segments are known
   const size_t row = size_t(e.max_positions) + 1;
   std::vector<int64_t> ids(row);
   std::vector<float> clip(win);
@@ -115,6 +120,19 @@ void transcribe_seek(Engine& e, const float* pcm, size_t n_samples, std::string*
     if (!skipped) {
       std::vector<Segment> segs;
       advance = seek_step(vocab, g, n_gen, win_ticks, seg_ticks, &segs);
+      if (e.word_timestamps) {  // the window's words: clip = window, times in the file, segment = index in the whole call
+        std::vector<Segment> in_row = segs;
+        for (Segment& sg : in_row) sg.clip = 0, sg.id_begin += n_prompt;
+        e.last_alignment.clear();
+        e.align_words(1, in_row, std::vector<long long>{(long long)have});
+        for (Engine::Word wd : e.last_words) {
+          wd.clip = w;
+          wd.segment += int(segments.size());
+          wd.t0_ms += int32_t(seek / 16), wd.t1_ms += int32_t(seek / 16);
+          words.push_back(wd);
+        }
+        word_text.insert(word_text.end(), e.last_word_text.begin(), e.last_word_text.end());
+      }
       for (Segment sg : segs) {
         kept.insert(kept.end(), g + sg.id_begin, g + sg.id_begin + sg.id_count);
         sg.clip = w;
@@ -137,6 +155,9 @@ void transcribe_seek(Engine& e, const float* pcm, size_t n_samples, std::string*
     ctx.insert(ctx.end(), kept.begin(), kept.end());
     if (!skipped && (!e.condition_on_previous_text || rec.temperature_milli > 500)) ctx.clear();
     if (ctx.size() > size_t(Engine::kContextIdsMax)) ctx.erase(ctx.begin(), ctx.end() - Engine::kContextIdsMax);
+    if (e.word_timestamps && e.keep_alignment) {  // one record per window, empty for a window without words
+      kept_alignment.push_back(!skipped && !e.last_alignment.empty() ? e.last_alignment.back() : Engine::ClipAlignment());
+    }
     rec.advance_samples = advance * 320;
     rec.n_kept_ids = int32_t(kept.size());
     windows.push_back(rec);
@@ -150,6 +171,10 @@ void transcribe_seek(Engine& e, const float* pcm, size_t n_samples, std::string*
   }
   if (sampled) e.last_decode_info = decode_info, e.last_decode_info_valid = true;
   e.last_windows = windows, e.last_windows_valid = true;
+  if (e.word_timestamps) {
+    e.last_words = words, e.last_word_text = word_text, e.last_words_valid = true;
+    e.last_alignment = kept_alignment;
+  }
 }
 
 }  // namespace wt
