@@ -109,13 +109,13 @@ std::vector<float> cross_q_layout(const float* Wq, int d) {
   return out;
 }
 
-Engine::PlaneW Engine::upload_planes(const float* W, int N, int K, int Kpad, float scale) {
+const unsigned short* Engine::upload_planes(const float* W, int N, int K, int Kpad, float scale) {
   const std::vector<unsigned short> planes = split_weight_planes(W, N, K, Kpad, scale);
   void* p = nullptr;
   HIPCHK(hipMalloc(&p, planes.size() * sizeof(unsigned short) + 256));
   allocations_.push_back(p);
   HIPCHK(hipMemcpy(p, planes.data(), planes.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-  return PlaneW{static_cast<const unsigned short*>(p)};
+  return static_cast<const unsigned short*>(p);
 }
 
 TiledW Engine::upload_tiled(const float* W, int N, int K) {
@@ -204,6 +204,57 @@ struct WtwFile {
     return it->second.first;
   }
 };
+
+// A convolution weight [co][ci][3] in the implicit GEMM's order [co][kk * n_ci + ci]: the three taps of output frame t
+// are three consecutive rows of the time-major padded input
+std::vector<float> conv_gemm_order(const float* w, int n_co, int n_ci) {
+  std::vector<float> r(size_t(n_co) * 3 * n_ci);
+  for (int co = 0; co < n_co; ++co)
+    for (int ci = 0; ci < n_ci; ++ci)
+      for (int kk = 0; kk < 3; ++kk) r[size_t(co) * 3 * n_ci + kk * n_ci + ci] = w[(size_t(co) * n_ci + ci) * 3 + kk];
+  return r;
+}
+
+// query | key | value of the self-attention `p` as one matrix [3d][d]
+std::vector<float> fused_qkv_weight(const WtwFile& f, const std::string& p, int d) {
+  const size_t dd = size_t(d) * d;
+  std::vector<float> w(3 * dd);
+  std::memcpy(w.data(), f.get(p + ".query.weight", dd), dd * 4);
+  std::memcpy(w.data() + dd, f.get(p + ".key.weight", dd), dd * 4);
+  std::memcpy(w.data() + 2 * dd, f.get(p + ".value.weight", dd), dd * 4);
+  return w;
+}
+
+// all decoder layers' cross K/V projections act on the same encoder output: one matrix [layer][k|v][d][d]
+std::vector<float> cross_kv_weight(const WtwFile& f, const wtw::Dims& c) {
+  const size_t dd = size_t(c.n_text_state) * c.n_text_state;
+  std::vector<float> w(size_t(c.n_text_layer) * 2 * dd);
+  for (int l = 0; l < c.n_text_layer; ++l) {
+    const std::string blk = "decoder.blocks." + std::to_string(l);
+    std::memcpy(w.data() + (size_t(l) * 2 + 0) * dd, f.get(blk + ".cross_attn.key.weight", dd), dd * 4);
+    std::memcpy(w.data() + (size_t(l) * 2 + 1) * dd, f.get(blk + ".cross_attn.value.weight", dd), dd * 4);
+  }
+  return w;
+}
+
+// Which tensors of the file make up which encoder contraction: fn(record, W, N, K) for each of them, W [N][K] fp32 on
+// the host as the GEMMs contract with it.  upload_weights and ensure_bf16_weights fill the records' forms through it.
+template <class Fn>
+void fill_enc_linears(const WtwFile& f, const wtw::Dims& c, EncLinear& conv1, EncLinear& conv2, std::vector<EncLayer>& layers,
+                      EncLinear& cross_kv, Fn&& fn) {
+  const int d = c.n_audio_state, nm = c.n_mels;
+  const size_t dd = size_t(d) * d;
+  fn(conv1, conv_gemm_order(f.get("encoder.conv1.weight", size_t(d) * nm * 3), d, nm).data(), d, 3 * nm);
+  fn(conv2, conv_gemm_order(f.get("encoder.conv2.weight", dd * 3), d, d).data(), d, 3 * d);
+  for (size_t l = 0; l < layers.size(); ++l) {
+    const std::string blk = "encoder.blocks." + std::to_string(l);
+    fn(layers[l].qkv, fused_qkv_weight(f, blk + ".attn", d).data(), 3 * d, d);
+    fn(layers[l].out, f.get(blk + ".attn.out.weight", dd), d, d);
+    fn(layers[l].fc1, f.get(blk + ".mlp.0.weight", 4 * dd), 4 * d, d);
+    fn(layers[l].fc2, f.get(blk + ".mlp.2.weight", 4 * dd), d, 4 * d);
+  }
+  fn(cross_kv, cross_kv_weight(f, c).data(), c.n_text_layer * 2 * d, d);
+}
 }  // namespace
 
 void check_wtw_file(const std::string& path) {
@@ -272,59 +323,28 @@ void Engine::upload_weights(const std::string& path) {
   };
 
   const int d = c.n_audio_state, nm = c.n_mels;
-  // conv1 [d][n_mels][3] -> [d][kpad], k = kk * n_mels + ci  (implicit-GEMM order: the three
-  // taps of output frame t are three consecutive rows of the time-major padded input)
-  conv1_kpad = int(round_up(size_t(3) * nm, 32));
-  {
-    const float* w = H("encoder.conv1.weight", size_t(d) * nm * 3);
-    std::vector<float> r(size_t(d) * conv1_kpad, 0.0f);
-    for (int co = 0; co < d; ++co)
-      for (int ci = 0; ci < nm; ++ci)
-        for (int kk = 0; kk < 3; ++kk)
-          r[size_t(co) * conv1_kpad + kk * nm + ci] = w[(size_t(co) * nm + ci) * 3 + kk];
-    conv1_w = upload(r);
-    conv1_b = up("encoder.conv1.bias", d);
-  }
-  {
-    const float* w = H("encoder.conv2.weight", size_t(d) * d * 3);
-    std::vector<float> r(size_t(d) * 3 * d);
-    for (int co = 0; co < d; ++co)
-      for (int ci = 0; ci < d; ++ci)
-        for (int kk = 0; kk < 3; ++kk)
-          r[size_t(co) * 3 * d + kk * d + ci] = w[(size_t(co) * d + ci) * 3 + kk];
-    conv2_w = upload(r);
-    conv2_b = up("encoder.conv2.bias", d);
-  }
-  enc_pos = up("encoder.positional_embedding", size_t(c.n_audio_ctx) * d);
-
-  auto fused_qkv = [&](const std::string& p, std::vector<float>* w, std::vector<float>* b) {
-    const size_t dd = size_t(d) * d;
-    w->assign(3 * dd, 0.0f);
-    b->assign(3 * size_t(d), 0.0f);
-    std::memcpy(w->data(), H(p + ".query.weight", dd), dd * 4);
-    std::memcpy(w->data() + dd, H(p + ".key.weight", dd), dd * 4);
-    std::memcpy(w->data() + 2 * dd, H(p + ".value.weight", dd), dd * 4);
-    std::memcpy(b->data(), H(p + ".query.bias", d), size_t(d) * 4);
-    std::memcpy(b->data() + 2 * size_t(d), H(p + ".value.bias", d), size_t(d) * 4);  // key has no bias
+  // The encoder's vectors.  Its matrices follow the scales below: one of their forms is made with them (fill_enc_linears).
+  auto fused_qkv_bias = [&](const std::string& p) {
+    std::vector<float> b(3 * size_t(d), 0.0f);  // key has no bias
+    std::memcpy(b.data(), H(p + ".query.bias", d), size_t(d) * 4);
+    std::memcpy(b.data() + 2 * size_t(d), H(p + ".value.bias", d), size_t(d) * 4);
+    return b;
   };
-  enc_blocks_.resize(c.n_audio_layer);
+  conv1_.bias = up("encoder.conv1.bias", d);
+  conv2_.bias = up("encoder.conv2.bias", d);
+  enc_pos = up("encoder.positional_embedding", size_t(c.n_audio_ctx) * d);
+  enc_layers_.assign(c.n_audio_layer, EncLayer{});
   for (int l = 0; l < c.n_audio_layer; ++l) {
     const std::string blk = "encoder.blocks." + std::to_string(l);
-    BlockWeights& bw = enc_blocks_[l];
-    bw.attn_ln_g = up(blk + ".attn_ln.weight", d);
-    bw.attn_ln_b = up(blk + ".attn_ln.bias", d);
-    std::vector<float> wqkv, bqkv;
-    fused_qkv(blk + ".attn", &wqkv, &bqkv);
-    bw.attn.wqkv = upload(wqkv);
-    bw.attn.bqkv = upload(bqkv);
-    bw.attn.wo = up(blk + ".attn.out.weight", size_t(d) * d);
-    bw.attn.bo = up(blk + ".attn.out.bias", d);
-    bw.mlp_ln_g = up(blk + ".mlp_ln.weight", d);
-    bw.mlp_ln_b = up(blk + ".mlp_ln.bias", d);
-    bw.w1 = up(blk + ".mlp.0.weight", size_t(4) * d * d);
-    bw.b1 = up(blk + ".mlp.0.bias", size_t(4) * d);
-    bw.w2 = up(blk + ".mlp.2.weight", size_t(4) * d * d);
-    bw.b2 = up(blk + ".mlp.2.bias", d);
+    EncLayer& el = enc_layers_[l];
+    el.attn_ln_g = up(blk + ".attn_ln.weight", d);
+    el.attn_ln_b = up(blk + ".attn_ln.bias", d);
+    el.qkv.bias = upload(fused_qkv_bias(blk + ".attn"));
+    el.out.bias = up(blk + ".attn.out.bias", d);
+    el.mlp_ln_g = up(blk + ".mlp_ln.weight", d);
+    el.mlp_ln_b = up(blk + ".mlp_ln.bias", d);
+    el.fc1.bias = up(blk + ".mlp.0.bias", size_t(4) * d);
+    el.fc2.bias = up(blk + ".mlp.2.bias", d);
   }
   enc_ln_post_g = up("encoder.ln_post.weight", d);
   enc_ln_post_b = up("encoder.ln_post.bias", d);
@@ -334,16 +354,14 @@ void Engine::upload_weights(const std::string& path) {
   dec_pos = up("decoder.positional_embedding", size_t(c.n_text_ctx) * d);
   dec_blocks_.resize(c.n_text_layer);
   const size_t dd = size_t(d) * d;
-  std::vector<float> ckv_w(size_t(c.n_text_layer) * 2 * dd), ckv_b(size_t(c.n_text_layer) * 2 * d, 0.0f);
+  std::vector<float> ckv_b(size_t(c.n_text_layer) * 2 * d, 0.0f);
   for (int l = 0; l < c.n_text_layer; ++l) {
     const std::string blk = "decoder.blocks." + std::to_string(l);
     DecBlockWeights& bw = dec_blocks_[l];
     bw.attn_ln_g = up(blk + ".attn_ln.weight", d);
     bw.attn_ln_b = up(blk + ".attn_ln.bias", d);
-    std::vector<float> wqkv, bqkv;
-    fused_qkv(blk + ".attn", &wqkv, &bqkv);
-    bw.wqkv = upload_tiled(wqkv.data(), 3 * d, d);  // decoder Linears: fp16 planes in MFMA-fragment order
-    bw.bqkv = upload(bqkv);
+    bw.wqkv = upload_tiled(fused_qkv_weight(file, blk + ".attn", d).data(), 3 * d, d);  // decoder Linears: fp16 planes in MFMA-fragment order
+    bw.bqkv = upload(fused_qkv_bias(blk + ".attn"));
     bw.wo = upload_tiled(H(blk + ".attn.out.weight", dd), d, d);
     bw.bo = up(blk + ".attn.out.bias", d);
     bw.cross_ln_g = up(blk + ".cross_attn_ln.weight", d);
@@ -367,9 +385,7 @@ void Engine::upload_weights(const std::string& path) {
       bw.cross_wv_t = upload(cross_q_layout(wv, d));
       bw.cross_bv = upload(std::vector<float>(bv, bv + d));
     }
-    // all layers' cross K/V projections act on the same encoder output: one GEMM
-    std::memcpy(ckv_w.data() + (size_t(l) * 2 + 0) * dd, H(blk + ".cross_attn.key.weight", dd), dd * 4);
-    std::memcpy(ckv_w.data() + (size_t(l) * 2 + 1) * dd, H(blk + ".cross_attn.value.weight", dd), dd * 4);
+    // all layers' cross K/V projections act on the same encoder output: one GEMM (cross_kv_weight; the key has no bias)
     std::memcpy(ckv_b.data() + (size_t(l) * 2 + 1) * d, H(blk + ".cross_attn.value.bias", d), size_t(d) * 4);
     bw.mlp_ln_g = up(blk + ".mlp_ln.weight", d);
     bw.mlp_ln_b = up(blk + ".mlp_ln.bias", d);
@@ -378,8 +394,7 @@ void Engine::upload_weights(const std::string& path) {
     bw.w2 = upload_tiled(H(blk + ".mlp.2.weight", 4 * dd), d, 4 * d);
     bw.b2 = up(blk + ".mlp.2.bias", d);
   }
-  cross_kv_w = upload(ckv_w);
-  cross_kv_b = upload(ckv_b);
+  cross_kv_.bias = upload(ckv_b);
   dec_ln_g = up("decoder.ln.weight", d);
   dec_ln_b = up("decoder.ln.bias", d);
   // ---- operand bounds -> fp16 plane scales (engine.h, GemmScale) ----
@@ -456,22 +471,21 @@ void Engine::upload_weights(const std::string& path) {
     // which has the same absolute values
     const Op mel_op{std::vector<float>(1, kMelBound), 1.0f};
     const float* c1w = H("encoder.conv1.weight", size_t(d) * nm * 3);
-    sc_conv1_ = scale_of(mel_op, c1w, size_t(d) * nm * 3);
+    conv1_.sc = scale_of(mel_op, c1w, size_t(d) * nm * 3);
     const Op h1 = gelu_op(linear_op(c1w, H("encoder.conv1.bias", d), d, nm * 3, mel_op));
     const float* c2w = H("encoder.conv2.weight", size_t(d) * d * 3);
-    sc_conv2_ = scale_of(h1, c2w, size_t(d) * d * 3);
-    sc_layers_.assign(c.n_audio_layer, EncLayerScales{});
+    conv2_.sc = scale_of(h1, c2w, size_t(d) * d * 3);
     const size_t dd2 = size_t(d) * d;
     for (int l = 0; l < c.n_audio_layer; ++l) {
       const std::string blk = "encoder.blocks." + std::to_string(l);
-      EncLayerScales& sl = sc_layers_[l];
+      EncLayer& sl = enc_layers_[l];
       const Op ln1 = ln_op(blk + ".attn_ln.weight", blk + ".attn_ln.bias");
       const float* wq = H(blk + ".attn.query.weight", dd2);
       const float* wk = H(blk + ".attn.key.weight", dd2);
       const float* wv = H(blk + ".attn.value.weight", dd2);
       const float wmax = std::max(maxabs(wq, dd2), std::max(maxabs(wk, dd2), maxabs(wv, dd2)));
-      sl.qkv = GemmScale{f16_scale_for(vmax(ln1.bound)), f16_scale_for(wmax), slack_ok(ln1)};
-      if (!sl.qkv.f16_ok) ++n_f16_fallbacks_;
+      sl.qkv.sc = GemmScale{f16_scale_for(vmax(ln1.bound)), f16_scale_for(wmax), slack_ok(ln1)};
+      if (!sl.qkv.sc.f16_ok) ++n_f16_fallbacks_;
       const Op qo = linear_op(wq, H(blk + ".attn.query.bias", d), d, d, ln1);
       const Op ko = linear_op(wk, nullptr, d, d, ln1);
       const Op vo = linear_op(wv, H(blk + ".attn.value.bias", d), d, d, ln1);
@@ -480,56 +494,40 @@ void Engine::upload_weights(const std::string& path) {
       sl.v = f16_scale_for(vmax(vo.bound));
       sl.attn_f16_ok = slack_ok(qo) && slack_ok(ko) && slack_ok(vo);
       if (!sl.attn_f16_ok) ++n_f16_fallbacks_;
-      sl.out = scale_of(vo, H(blk + ".attn.out.weight", dd2), dd2);  // a convex combination of V rows
+      sl.out.sc = scale_of(vo, H(blk + ".attn.out.weight", dd2), dd2);  // a convex combination of V rows
       const Op ln2 = ln_op(blk + ".mlp_ln.weight", blk + ".mlp_ln.bias");
       const float* w1 = H(blk + ".mlp.0.weight", 4 * dd2);
-      sl.fc1 = scale_of(ln2, w1, 4 * dd2);
+      sl.fc1.sc = scale_of(ln2, w1, 4 * dd2);
       const Op hb = gelu_op(linear_op(w1, H(blk + ".mlp.0.bias", size_t(4) * d), 4 * d, d, ln2));
-      sl.fc2 = scale_of(hb, H(blk + ".mlp.2.weight", 4 * dd2), 4 * dd2);
+      sl.fc2.sc = scale_of(hb, H(blk + ".mlp.2.weight", 4 * dd2), 4 * dd2);
     }
     const Op lnp = ln_op("encoder.ln_post.weight", "encoder.ln_post.bias");
-    sc_cross_kv_ = GemmScale{f16_scale_for(vmax(lnp.bound)), f16_scale_for(maxabs(ckv_w.data(), ckv_w.size())), slack_ok(lnp)};
-    if (!sc_cross_kv_.f16_ok) ++n_f16_fallbacks_;
+    const std::vector<float> ckv_w = cross_kv_weight(file, c);
+    cross_kv_.sc = GemmScale{f16_scale_for(vmax(lnp.bound)), f16_scale_for(maxabs(ckv_w.data(), ckv_w.size())), slack_ok(lnp)};
+    if (!cross_kv_.sc.f16_ok) ++n_f16_fallbacks_;
     load_ok_.clear();
     for (bool* f : ok_flags()) load_ok_.push_back(*f);
   }
-  // ---- encoder weights as fp16 planes (k_gemm_planes.hip): split once, here ----
-  {
-    conv1_kpad_p_ = int(round_up(size_t(3) * nm, 32));
-    std::vector<float> r(size_t(d) * 3 * nm);
-    const float* w = H("encoder.conv1.weight", size_t(d) * nm * 3);
-    for (int co = 0; co < d; ++co)
-      for (int ci = 0; ci < nm; ++ci)
-        for (int kk = 0; kk < 3; ++kk) r[size_t(co) * 3 * nm + kk * nm + ci] = w[(size_t(co) * nm + ci) * 3 + kk];
-    conv1_p_ = upload_planes(r.data(), d, 3 * nm, conv1_kpad_p_, sc_conv1_.w);
-    std::vector<float> r2(size_t(d) * 3 * d);
-    const float* w2 = H("encoder.conv2.weight", size_t(d) * d * 3);
-    for (int co = 0; co < d; ++co)
-      for (int ci = 0; ci < d; ++ci)
-        for (int kk = 0; kk < 3; ++kk) r2[size_t(co) * 3 * d + kk * d + ci] = w2[(size_t(co) * d + ci) * 3 + kk];
-    conv2_p_ = upload_planes(r2.data(), d, 3 * d, 3 * d, sc_conv2_.w);
-    enc_planes_.resize(c.n_audio_layer);
-    const size_t dd3 = size_t(d) * d;
-    for (int l = 0; l < c.n_audio_layer; ++l) {
-      const std::string blk = "encoder.blocks." + std::to_string(l);
-      std::vector<float> wqkv, bqkv;
-      fused_qkv(blk + ".attn", &wqkv, &bqkv);
-      enc_planes_[l].qkv = upload_planes(wqkv.data(), 3 * d, d, d, sc_layers_[l].qkv.w);
-      enc_planes_[l].out = upload_planes(H(blk + ".attn.out.weight", dd3), d, d, d, sc_layers_[l].out.w);
-      enc_planes_[l].fc1 = upload_planes(H(blk + ".mlp.0.weight", 4 * dd3), 4 * d, d, d, sc_layers_[l].fc1.w);
-      enc_planes_[l].fc2 = upload_planes(H(blk + ".mlp.2.weight", 4 * dd3), d, 4 * d, 4 * d, sc_layers_[l].fc2.w);
-    }
-    cross_kv_p_ = upload_planes(ckv_w.data(), c.n_text_layer * 2 * d, d, d, sc_cross_kv_.w);
-  }
-
+  // ---- the encoder's matrices: fp32 for the fall-back kernels (k_gemm.hip) and the two fp16 planes of W * sc.w for the
+  // plane GEMM (k_gemm_planes.hip), split once, here ----
+  fill_enc_linears(file, c, conv1_, conv2_, enc_layers_, cross_kv_, [&](EncLinear& L, const float* W, int N, int K) {
+    L.N = N; L.k = K;
+    L.k32 = L.kp = int(round_up(size_t(K), 32));
+    L.kbf = int(round_up(size_t(K), 64));
+    std::vector<float> w32(size_t(N) * L.k32, 0.0f);
+    for (int n = 0; n < N; ++n) std::memcpy(w32.data() + size_t(n) * L.k32, W + size_t(n) * K, size_t(K) * 4);
+    L.w32 = upload(w32);
+    L.wp = upload_planes(W, N, K, L.kp, L.sc.w);
+  });
 }
 
+// The f16_ok / attn_f16_ok verdicts of the records in launch order: the bit numbering of force_fallback
 std::vector<bool*> Engine::ok_flags() {
-  std::vector<bool*> f{&sc_conv1_.f16_ok, &sc_conv2_.f16_ok};
-  for (EncLayerScales& sl : sc_layers_) {
-    for (bool* p : {&sl.qkv.f16_ok, &sl.attn_f16_ok, &sl.out.f16_ok, &sl.fc1.f16_ok, &sl.fc2.f16_ok}) f.push_back(p);
+  std::vector<bool*> f{&conv1_.sc.f16_ok, &conv2_.sc.f16_ok};
+  for (EncLayer& el : enc_layers_) {
+    for (bool* p : {&el.qkv.sc.f16_ok, &el.attn_f16_ok, &el.out.sc.f16_ok, &el.fc1.sc.f16_ok, &el.fc2.sc.f16_ok}) f.push_back(p);
   }
-  f.push_back(&sc_cross_kv_.f16_ok);
+  f.push_back(&cross_kv_.sc.f16_ok);
   return f;
 }
 
@@ -554,7 +552,7 @@ void Engine::ensure_bf16_weights() {
   if (dims_.n_audio_state == 0) throw Error(kErrUnsupported, "front-end-only engine: no model weights loaded");
   const WtwFile file(weights_path_);
   const wtw::Dims& c = dims_;
-  const int d = c.n_audio_state, nm = c.n_mels;
+  const int d = c.n_audio_state;
   auto H = [&](const std::string& n, size_t expect) -> const float* { return file.get(n, expect); };
   auto up16 = [&](const std::vector<unsigned short>& v) -> const unsigned short* {
     void* p = nullptr;
@@ -564,44 +562,14 @@ void Engine::ensure_bf16_weights() {
     return static_cast<const unsigned short*>(p);
   };
   const size_t dd = size_t(d) * d;
-  {
-    bf_.conv1_kpad = int(round_up(size_t(3) * nm, 64));
-    std::vector<float> r(size_t(d) * 3 * nm);
-    const float* w = H("encoder.conv1.weight", size_t(d) * nm * 3);
-    for (int co = 0; co < d; ++co)
-      for (int ci = 0; ci < nm; ++ci)
-        for (int kk = 0; kk < 3; ++kk) r[size_t(co) * 3 * nm + kk * nm + ci] = w[(size_t(co) * nm + ci) * 3 + kk];
-    bf_.conv1 = up16(round_weights_bf16(r.data(), d, 3 * nm, bf_.conv1_kpad));
-    std::vector<float> r2(size_t(d) * 3 * d);
-    const float* w2 = H("encoder.conv2.weight", size_t(d) * d * 3);
-    for (int co = 0; co < d; ++co)
-      for (int ci = 0; ci < d; ++ci)
-        for (int kk = 0; kk < 3; ++kk) r2[size_t(co) * 3 * d + kk * d + ci] = w2[(size_t(co) * d + ci) * 3 + kk];
-    bf_.conv2 = up16(round_weights_bf16(r2.data(), d, 3 * d, 3 * d));
-  }
-  auto fused_qkv = [&](const std::string& p) {
-    std::vector<float> w(3 * dd);
-    std::memcpy(w.data(), H(p + ".query.weight", dd), dd * 4);
-    std::memcpy(w.data() + dd, H(p + ".key.weight", dd), dd * 4);
-    std::memcpy(w.data() + 2 * dd, H(p + ".value.weight", dd), dd * 4);
-    return w;
-  };
-  bf_.layers.resize(c.n_audio_layer);
-  for (int l = 0; l < c.n_audio_layer; ++l) {
-    const std::string blk = "encoder.blocks." + std::to_string(l);
-    bf_.layers[l].qkv = up16(round_weights_bf16(fused_qkv(blk + ".attn").data(), 3 * d, d, d));
-    bf_.layers[l].out = up16(round_weights_bf16(H(blk + ".attn.out.weight", dd), d, d, d));
-    bf_.layers[l].fc1 = up16(round_weights_bf16(H(blk + ".mlp.0.weight", 4 * dd), 4 * d, d, d));
-    bf_.layers[l].fc2 = up16(round_weights_bf16(H(blk + ".mlp.2.weight", 4 * dd), d, 4 * d, 4 * d));
-  }
-  std::vector<float> ckv_w(size_t(c.n_text_layer) * 2 * dd);
+  fill_enc_linears(file, c, conv1_, conv2_, enc_layers_, cross_kv_, [&](EncLinear& L, const float* W, int N, int K) {
+    L.wbf = up16(round_weights_bf16(W, N, K, L.kbf));
+  });
   dec_blocks_bf_ = dec_blocks_;  // fp32 vectors shared; the tiled matrices are replaced below
   for (int l = 0; l < c.n_text_layer; ++l) {
     const std::string blk = "decoder.blocks." + std::to_string(l);
-    std::memcpy(ckv_w.data() + (size_t(l) * 2 + 0) * dd, H(blk + ".cross_attn.key.weight", dd), dd * 4);
-    std::memcpy(ckv_w.data() + (size_t(l) * 2 + 1) * dd, H(blk + ".cross_attn.value.weight", dd), dd * 4);
     DecBlockWeights& bw = dec_blocks_bf_[l];
-    bw.wqkv = TiledW{up16(tile_weights_bf16(fused_qkv(blk + ".attn").data(), 3 * d, d)), 1.0f};
+    bw.wqkv = TiledW{up16(tile_weights_bf16(fused_qkv_weight(file, blk + ".attn", d).data(), 3 * d, d)), 1.0f};
     bw.wo = TiledW{up16(tile_weights_bf16(H(blk + ".attn.out.weight", dd), d, d)), 1.0f};
     bw.cross_wo = TiledW{up16(tile_weights_bf16(H(blk + ".cross_attn.out.weight", dd), d, d)), 1.0f};
     bw.w1 = TiledW{up16(tile_weights_bf16(H(blk + ".mlp.0.weight", 4 * dd), 4 * d, d)), 1.0f};
@@ -611,7 +579,6 @@ void Engine::ensure_bf16_weights() {
                           H(blk + ".cross_attn.key.weight", dd), c.n_text_head, d, &A, &av);
     bw.wq_abs = TiledW{up16(tile_weights_bf16(A.data(), c.n_text_head * d, d)), 1.0f};
   }
-  bf_.cross_kv = up16(round_weights_bf16(ckv_w.data(), c.n_text_layer * 2 * d, d, d));
   tok_emb_tiled_bf_ = TiledW{up16(tile_weights_bf16(H("decoder.token_embedding.weight", size_t(c.n_vocab) * d), c.n_vocab, d)), 1.0f};
   bf16_ready_ = true;
 }
@@ -1117,7 +1084,7 @@ void Engine::logmel(const float* d_pcm, int batch, float* d_mel, int valid_frame
   g.a_rpb = int(T0);
   g.a_bs = long(pad);
   g.lda = 160;  // hop: frame i starts at sample 160 * i
-  g.W = dft_basis_p_.w;
+  g.W = dft_basis_p_;
   g.bias = dft_zero_bias_;
   g.C = ws_.pw;
   g.M = int(M);
@@ -1226,17 +1193,41 @@ void Engine::encode(const float* d_mel, int batch) {
   encode_enqueue(d_mel, batch);
 }
 
+namespace {
+// One encoder contraction as encode_enqueue describes it, once, for whichever kernel runs it.  `g` holds the addressing
+// (M, lda, a_rpb, a_bs, c_rpb, c_bs, ldc, pos, kv_*, R), the A operand as planes (A, a_plane) and the LayerNorm-fusion
+// request (ln_*); its weight side (W, bias, N, K, scales) comes from the record, its output from the fields below.
+struct EncGemm {
+  PlaneGemmArgs g;
+  const EncLinear* w = nullptr;
+  int epi = 0;
+  const float* A32 = nullptr;  // the A operand as fp32
+  // The output in both forms: the consumer decides (to_planes).  The residual stream and the fp32 cross-KV cache have C32 only.
+  float* C32 = nullptr;
+  unsigned short* P = nullptr;
+  long p_plane = 0;
+  const float* out_scale = nullptr;  // of P: one scale, or three with `seg` columns each; null = 1
+  int seg = 0;
+  bool to_planes = false;
+  // the hand-over behind a fall-back kernel in front of a plane consumer, where it is not "the rows [M][ldc] at C32 ->
+  // ws_.cvt": the padded rows of conv1's output
+  const float* cvt_src = nullptr;
+  unsigned short* cvt_dst = nullptr;
+  long cvt_plane = 0, cvt_rows = 0;
+};
+struct PlaneOperand {  // where a plane consumer finds its A operand
+  const unsigned short* p;
+  long plane;
+};
+}  // namespace
+
 void Engine::encode_enqueue(const float* d_mel, int batch) {
   if (dims_.n_audio_state == 0) throw Error(kErrUnsupported, "front-end-only engine: no model weights loaded");
   ensure_batch(batch);
-  TimerDisarm disarm_on_exit;  // (covers the bf16 pass too: it is called from here)
+  TimerDisarm disarm_on_exit;
   // per-launch event pairs (bench.py's live roofline figures) on every kernel_timers-th encoder pass: an event pair
   // costs the stream a few microseconds per launch, which 41 launches per pass make visible in the pipeline period
   kt_on_ = kernel_timers > 0 && (enc_count_++ % kernel_timers) == 0;
-  if (bf16) {
-    encode_enqueue_bf16(d_mel, batch);
-    return;
-  }
   // The encoder graph.  Every contraction chooses its kernel BY ITSELF: the plane kernels
   // (k_gemm_planes.hip, k_attention_planes.hip: operands as two fp16 planes, made by the kernel that produces them)
   // unless the load-time slack check flagged that contraction's operand (GemmScale::f16_ok, upload_weights) or an
@@ -1244,9 +1235,13 @@ void Engine::encode_enqueue(const float* d_mel, int batch) {
   // operand range).  A tensor has exactly one consumer, so its format follows the consumer: a plane kernel that feeds a
   // flagged contraction writes fp32 (C instead of P), LayerNorm has both forms, and where a fall-back kernel feeds a
   // plane kernel its fp32 output is split by launch_f32_to_planes into the scratch planes ws_.cvt.  The residual
-  // stream x stays fp32 throughout.
+  // stream x stays fp32 throughout.  That rule is enc_gemm below; every contraction is described once and handed to it.
+  // bf16 storage mode (option "bf16") is the same graph with every contraction "on planes": each operand is ONE bf16
+  // matrix (k_gemm_bf16.hip, encoder_attention_planes<true>), so every plane offset is 0 and every scale 1; x and the
+  // API's enc_out stay fp32, the cross-KV cache of the slot is written as bf16 (half the bytes, same layout).
   const wtw::Dims& c = dims_;
   const int T0 = mel_frames(), T = c.n_audio_ctx, d = c.n_audio_state, M = batch * T, nm = c.n_mels;
+  const bool bf = bf16 != 0;
   const long Bw = ws_.batch;  // plane strides follow the workspace, not the call
   const int cus = (stream_ == stream_masked_ && stream_masked_) ? enc_cus_masked_ : n_cu_;  // CUs of this stream
   Slot& slot = slots_[enc_slot_];
@@ -1266,365 +1261,199 @@ void Engine::encode_enqueue(const float* d_mel, int batch) {
   unsigned short* const qkvp = reinterpret_cast<unsigned short*>(ws_.qkv);
   unsigned short* const attp = reinterpret_cast<unsigned short*>(ws_.att);
   unsigned short* const hidp = reinterpret_cast<unsigned short*>(ws_.hid);
-  const long melT_plane = Bw * (T0 + 2) * nm + 128, h1p_plane = Bw * (T0 + 2) * d + 128;
-  const long ln_plane = Bw * T * d, qkv_plane = Bw * T * 3 * d, hid_plane = Bw * T * 4 * d, cvt_plane = Bw * T * 4 * d;
-  const long e_plane = Bw * T * d;
+  auto plane = [&](long elems) { return bf ? 0 : elems; };  // elements between the hi and the lo plane of a tensor
+  const long melT_plane = plane(Bw * (T0 + 2) * nm + 128), h1p_plane = plane(Bw * (T0 + 2) * d + 128);
+  const long ln_plane = plane(Bw * T * d), qkv_plane = plane(Bw * T * 3 * d), hid_plane = plane(Bw * T * 4 * d);
+  const long cvt_plane = plane(Bw * T * 4 * d), e_plane = plane(Bw * T * d);
   const bool absorb = absorb_for(batch);
   const int alt = alt_gemm_variant();
+  auto on_planes = [&](const EncLinear& w) { return bf || gemm_on_planes(w.sc); };
+  auto a_scale = [&](const EncLinear& w) { return bf ? 1.0f : w.sc.a; };  // the scale of the A planes made for `w`
+  // a transpose or LayerNorm into planes counts 2 x its fp32 bytes; into one bf16 plane 1.5 x (bench.py's roofline table)
+  const double planes_io = bf ? 1.5 : 2.0;
 
-  auto plane_gemm = [&](PlaneGemmArgs& g, const GemmScale& sc, int epi, double flops) {
-    g.n_cu = cus; g.a_scale = sc.a; g.w_scale = sc.w;
-    kt_begin(kKcGemm, flops, 0);
-    const bool ln_fused = launch_gemm_planes(g, epi, stream_);
+  auto hand_over = [&](const float* src, unsigned short* dst, long dst_plane, long rows, int ld, const float* scales, int seg) {
+    kt_begin(kKcConvert, 0, 2.0 * rows * ld * 4);
+    launch_f32_to_planes(src, dst, dst_plane, rows, ld, scales, seg, stream_);
     kt_end();
-    return ln_fused;
+    return PlaneOperand{dst, dst_plane};
   };
   // The LayerNorm that follows a GEMM whose output is the residual stream x (conv2, out-projection, fc2) is made by
-  // that GEMM's epilogue when its 384-column tile owns whole rows and both sides run on planes; ln_done then tells the
+  // that GEMM's epilogue when its tile owns whole rows and both sides run on planes; ln_done then tells the
   // consumer's side not to launch the LayerNorm kernel.
   bool ln_done = false;
   static const bool no_ln_fuse = getenv("WT_NO_LN_FUSE") != nullptr;  // measurement knob: separate LayerNorm launches
-  auto fuse_ln = [&](PlaneGemmArgs& g, const float* gain, const float* shift, float scale) {
-    if (no_ln_fuse) return;
-    g.ln_g = gain; g.ln_b = shift; g.ln_P = lnp; g.ln_plane = ln_plane; g.ln_scale = scale;
+  auto fuse_ln = [&](EncGemm& e, const float* gain, const float* shift, const EncLinear& consumer) {
+    if (no_ln_fuse || !on_planes(consumer)) return;
+    e.g.ln_g = gain; e.g.ln_b = shift; e.g.ln_P = lnp; e.g.ln_plane = ln_plane; e.g.ln_scale = a_scale(consumer);
   };
-  auto alt_gemm = [&](GemmArgs& g, const GemmScale& sc, int epi, double flops) {
-    g.variant = alt; g.a_scale = sc.a; g.w_scale = sc.w;
-    kt_begin(kKcGemmAlt, flops, 0);
-    launch_gemm(g, epi, stream_);
-    kt_end();
-  };
-  auto to_planes = [&](const float* src, unsigned short* dst, long plane, long rows, int ld, const float* scales, int seg) {
-    kt_begin(kKcConvert, 0, 2.0 * rows * ld * 4);
-    launch_f32_to_planes(src, dst, plane, rows, ld, scales, seg, stream_);
-    kt_end();
-  };
-
-  const bool c1p = gemm_on_planes(sc_conv1_), c2p = gemm_on_planes(sc_conv2_);
-  kt_begin(kKcTranspose, 0, 2.0 * batch * nm * T0 * 4);
-  if (c1p) {
-    launch_mel_transpose_planes(d_mel, ws_.melTp, melT_plane, sc_conv1_.a, batch, nm, T0, nm, stream_);
-  } else {
-    launch_mel_transpose(d_mel, ws_.melT, batch, nm, T0, stream_);
-  }
-  kt_end();
-  // conv1 + GELU: rows (clip, t) read melT rows t..t+2 (input t-1..t+1); row t lands at padded row t + 1 of h1
-  if (c1p) {
-    PlaneGemmArgs g;
-    g.A = ws_.melTp; g.a_plane = melT_plane; g.a_rpb = T0; g.a_bs = long(T0 + 2) * nm; g.lda = nm;
-    g.W = conv1_p_.w; g.bias = conv1_b;
-    if (c2p) {
-      g.P = ws_.h1pp + d; g.p_plane = h1p_plane; g.out_scale[0] = sc_conv2_.a;
-    } else {
-      g.C = ws_.h1p + d;
+  // Runs a contraction on the kernel its record and the mode select and leaves the result in the consumer's format;
+  // returns where a plane consumer finds it.
+  auto enc_gemm = [&](const EncGemm& e) {
+    const EncLinear& w = *e.w;
+    const double flops = 2.0 * e.g.M * w.N * double(w.k);
+    if (on_planes(w)) {
+      PlaneGemmArgs g = e.g;
+      g.W = bf ? w.wbf : w.wp; g.bias = w.bias; g.N = w.N; g.K = bf ? w.kbf : w.kp;
+      if (e.to_planes) {
+        g.P = e.P; g.p_plane = e.p_plane; g.seg = e.seg;
+        for (int i = 0; e.out_scale && i < (e.seg ? 3 : 1); ++i) g.out_scale[i] = e.out_scale[i];
+      } else {
+        g.C = e.C32;
+      }
+      if (!bf) g.n_cu = cus, g.a_scale = w.sc.a, g.w_scale = w.sc.w;
+      kt_begin(kKcGemm, flops, 0);
+      ln_done = bf ? launch_gemm_bf16_planes(g, e.epi, stream_) : launch_gemm_planes(g, e.epi, stream_);
+      kt_end();
+      return PlaneOperand{g.P, g.p_plane};
     }
-    g.c_rpb = T0; g.c_bs = long(T0 + 2) * d; g.ldc = d;
-    g.M = batch * T0; g.N = d; g.K = conv1_kpad_p_;
-    plane_gemm(g, sc_conv1_, kEpiBias | kEpiGelu, 2.0 * g.M * g.N * (3.0 * nm));
-  } else {
     GemmArgs g;
-    g.A = ws_.melT; g.a_rpb = T0; g.a_bs = long(T0 + 2) * nm; g.lda = nm;
-    g.W = conv1_w; g.bias = conv1_b;
-    g.C = ws_.h1p + d; g.c_rpb = T0; g.c_bs = long(T0 + 2) * d; g.ldc = d;
-    g.M = batch * T0; g.N = d; g.K = conv1_kpad;
-    alt_gemm(g, sc_conv1_, kEpiBias | kEpiGelu, 2.0 * g.M * g.N * (3.0 * nm));
-    // the pad rows of h1p are zero and stay zero as planes
-    if (c2p) to_planes(ws_.h1p, ws_.h1pp, h1p_plane, long(batch) * (T0 + 2), d, &sc_conv2_.a, 0);
-  }
-  // conv2 (stride 2) + GELU + positional embedding: output t reads padded rows 2t..2t+2
-  if (c2p) {
-    PlaneGemmArgs g;
-    g.A = ws_.h1pp; g.a_plane = h1p_plane; g.a_rpb = T; g.a_bs = long(T0 + 2) * d; g.lda = 2 * d;
-    g.W = conv2_p_.w; g.bias = conv2_b; g.pos = enc_pos; g.pos_period = T;
-    g.C = ws_.x; g.ldc = d; g.M = M; g.N = d; g.K = 3 * d;
-    if (gemm_on_planes(sc_layers_[0].qkv)) fuse_ln(g, enc_blocks_[0].attn_ln_g, enc_blocks_[0].attn_ln_b, sc_layers_[0].qkv.a);
-    ln_done = plane_gemm(g, sc_conv2_, kEpiBias | kEpiGelu | kEpiPos, 2.0 * g.M * g.N * g.K);
-  } else {
-    GemmArgs g;
-    g.A = ws_.h1p; g.a_rpb = T; g.a_bs = long(T0 + 2) * d; g.lda = 2 * d;
-    g.W = conv2_w; g.bias = conv2_b; g.pos = enc_pos; g.pos_period = T;
-    g.C = ws_.x; g.ldc = d; g.M = M; g.N = d; g.K = 3 * d;
-    alt_gemm(g, sc_conv2_, kEpiBias | kEpiGelu | kEpiPos, 2.0 * g.M * g.N * g.K);
-  }
-  constexpr float kQScale = 0.125f * 1.44269504088896340736f;  // d_head^-1/2 * log2(e): softmax as exp2
-  auto layernorm_for = [&](bool planes, float scale, const float* g, const float* b) {
+    g.A = e.A32; g.W = w.w32; g.C = e.C32; g.bias = w.bias; g.R = e.g.R; g.pos = e.g.pos;
+    g.M = e.g.M; g.N = w.N; g.K = w.k32;
+    g.a_rpb = e.g.a_rpb; g.a_bs = e.g.a_bs; g.lda = e.g.lda; g.c_rpb = e.g.c_rpb; g.c_bs = e.g.c_bs; g.ldc = e.g.ldc;
+    g.pos_period = e.g.pos_period; g.kv_batch = e.g.kv_batch; g.kv_heads = e.g.kv_heads; g.kv_dmodel = e.g.kv_dmodel;
+    g.variant = alt; g.a_scale = w.sc.a; g.w_scale = w.sc.w;
+    kt_begin(kKcGemmAlt, flops, 0);
+    launch_gemm(g, e.epi, stream_);
+    kt_end();
+    if (!e.to_planes) return PlaneOperand{nullptr, 0};
+    if (e.cvt_src) return hand_over(e.cvt_src, e.cvt_dst, e.cvt_plane, e.cvt_rows, e.g.ldc, e.out_scale, e.seg);
+    return hand_over(e.C32, ws_.cvt, cvt_plane, e.g.M, e.g.ldc, e.out_scale, e.seg);
+  };
+  auto layernorm_for = [&](const EncLinear& consumer, const float* g, const float* b) {
     if (ln_done) {  // the producing GEMM's epilogue has written these planes
       ln_done = false;
       return;
     }
-    kt_begin(kKcLayerNorm, 0, 2.0 * M * d * 4);
-    if (planes) {
-      launch_layernorm_planes(ws_.x, lnp, ln_plane, scale, nullptr, g, b, M, d, stream_);
+    kt_begin(kKcLayerNorm, 0, planes_io * M * d * 4);
+    if (on_planes(consumer)) {
+      launch_layernorm_planes(ws_.x, lnp, ln_plane, a_scale(consumer), nullptr, g, b, M, d, stream_, nullptr, bf);
     } else {
       launch_layernorm(ws_.x, ws_.ln, g, b, M, d, stream_);
     }
     kt_end();
   };
-  for (int l = 0; l < c.n_audio_layer; ++l) {
-    const BlockWeights& w = enc_blocks_[l];
-    const EncLayerPlanes& wp = enc_planes_[l];
-    const EncLayerScales& sc = sc_layers_[l];
-    const bool qp = gemm_on_planes(sc.qkv), op = gemm_on_planes(sc.out), f1p = gemm_on_planes(sc.fc1), f2p = gemm_on_planes(sc.fc2);
-    // the plane attention writes planes, so its consumer (the out-projection) must take them
-    const bool ap = gemm_variant < 0 && attn_variant == 4 && sc.attn_f16_ok && op;
-    const int attn_alt = attn_variant == 4 ? 1 : int(attn_variant);  // fall-back form: three bf16 planes
 
-    layernorm_for(qp, sc.qkv.a, w.attn_ln_g, w.attn_ln_b);
-    const float qkv_scales[3] = {kQScale * sc.q, sc.k, sc.v};
-    const unsigned short* qkv_src = qkvp;  // the plane attention's operand
-    long qkv_src_plane = qkv_plane;
-    if (qp) {
-      PlaneGemmArgs q;  // q | k | v: the attention kernel's operand planes, or fp32 for the fall-back attention
-      q.A = lnp; q.a_plane = ln_plane; q.lda = d; q.W = wp.qkv.w; q.bias = w.attn.bqkv;
-      if (ap) {
-        q.P = qkvp; q.p_plane = qkv_plane; q.seg = d;
-        q.out_scale[0] = qkv_scales[0]; q.out_scale[1] = qkv_scales[1]; q.out_scale[2] = qkv_scales[2];
-      } else {
-        q.C = ws_.qkv;
-      }
-      q.ldc = 3 * d; q.M = M; q.N = 3 * d; q.K = d;
-      plane_gemm(q, sc.qkv, kEpiBias, 2.0 * q.M * q.N * q.K);
-    } else {
-      GemmArgs q;
-      q.A = ws_.ln; q.lda = d; q.W = w.attn.wqkv; q.bias = w.attn.bqkv; q.C = ws_.qkv; q.ldc = 3 * d;
-      q.M = M; q.N = 3 * d; q.K = d;
-      alt_gemm(q, sc.qkv, kEpiBias, 2.0 * q.M * q.N * q.K);
-      if (ap) {
-        to_planes(ws_.qkv, ws_.cvt, cvt_plane, M, 3 * d, qkv_scales, d);
-        qkv_src = ws_.cvt; qkv_src_plane = cvt_plane;
-      }
-    }
-    const unsigned short* att_src = attp;  // the plane out-projection's operand
-    long att_src_plane = ln_plane;
+  kt_begin(kKcTranspose, 0, planes_io * batch * nm * T0 * 4);
+  if (on_planes(conv1_)) {
+    launch_mel_transpose_planes(d_mel, ws_.melTp, melT_plane, a_scale(conv1_), batch, nm, T0, nm, stream_, bf);
+  } else {
+    launch_mel_transpose(d_mel, ws_.melT, batch, nm, T0, stream_);
+  }
+  kt_end();
+  const float s_conv2 = a_scale(conv2_);
+  {
+    EncGemm e;  // conv1 + GELU: rows (clip, t) read melT rows t..t+2 (input t-1..t+1); row t lands at padded row t + 1 of h1
+    e.w = &conv1_; e.epi = kEpiBias | kEpiGelu;
+    e.A32 = ws_.melT; e.g.A = ws_.melTp; e.g.a_plane = melT_plane;
+    e.g.M = batch * T0; e.g.a_rpb = T0; e.g.a_bs = long(T0 + 2) * nm; e.g.lda = nm;
+    e.g.c_rpb = T0; e.g.c_bs = long(T0 + 2) * d; e.g.ldc = d;
+    e.to_planes = on_planes(conv2_); e.C32 = ws_.h1p + d; e.P = ws_.h1pp + d; e.p_plane = h1p_plane; e.out_scale = &s_conv2;
+    // (the pad rows of h1p are zero and stay zero as planes)
+    e.cvt_src = ws_.h1p; e.cvt_dst = ws_.h1pp; e.cvt_plane = h1p_plane; e.cvt_rows = long(batch) * (T0 + 2);
+    enc_gemm(e);
+  }
+  {
+    EncGemm e;  // conv2 (stride 2) + GELU + positional embedding: output t reads padded rows 2t..2t+2
+    e.w = &conv2_; e.epi = kEpiBias | kEpiGelu | kEpiPos;
+    e.A32 = ws_.h1p; e.g.A = ws_.h1pp; e.g.a_plane = h1p_plane;
+    e.g.M = M; e.g.a_rpb = T; e.g.a_bs = long(T0 + 2) * d; e.g.lda = 2 * d; e.g.ldc = d;
+    e.g.pos = enc_pos; e.g.pos_period = T;
+    e.C32 = ws_.x;
+    fuse_ln(e, enc_layers_[0].attn_ln_g, enc_layers_[0].attn_ln_b, enc_layers_[0].qkv);
+    enc_gemm(e);
+  }
+  constexpr float kQScale = 0.125f * 1.44269504088896340736f;  // d_head^-1/2 * log2(e): softmax as exp2
+  for (int l = 0; l < c.n_audio_layer; ++l) {
+    const EncLayer& L = enc_layers_[l];
+    const bool op = on_planes(L.out);
+    // the plane attention writes planes, so its consumer (the out-projection) must take them
+    const bool ap = bf || (gemm_variant < 0 && attn_variant == 4 && L.attn_f16_ok && op);
+    const int attn_alt = attn_variant == 4 ? 1 : int(attn_variant);  // fall-back form: three bf16 planes
+    const float qkv_scales[3] = {kQScale * L.q, L.k, L.v}, s_out = a_scale(L.out), s_fc2 = a_scale(L.fc2);
+
+    layernorm_for(L.qkv, L.attn_ln_g, L.attn_ln_b);
+    EncGemm q;  // q | k | v: the attention kernel's operand planes, or fp32 for the fall-back attention
+    q.w = &L.qkv; q.epi = kEpiBias;
+    q.A32 = ws_.ln; q.g.A = lnp; q.g.a_plane = ln_plane; q.g.M = M; q.g.lda = d; q.g.ldc = 3 * d;
+    q.to_planes = ap; q.C32 = ws_.qkv; q.P = qkvp; q.p_plane = qkv_plane;
+    if (!bf) q.out_scale = qkv_scales, q.seg = d;  // (the bf16 attention takes q unscaled)
+    const PlaneOperand qkv_src = enc_gemm(q);
+    PlaneOperand att_src{attp, ln_plane};  // the plane out-projection's operand
+    const double attn_flops = 4.0 * batch * c.n_audio_head * double(T) * T * 64;
     if (ap) {
-      kt_begin(kKcEncAttn, 4.0 * batch * c.n_audio_head * double(T) * T * 64, 0);
-      launch_encoder_attention_planes(qkv_src, qkv_src_plane, attp, ln_plane, batch, T, c.n_audio_head, sc.q, sc.k, sc.v,
-                                      sc.out.a, stream_);
+      kt_begin(kKcEncAttn, attn_flops, 0);
+      if (bf) {
+        launch_encoder_attention_bf16(qkv_src.p, attp, batch, T, c.n_audio_head, stream_);
+      } else {
+        launch_encoder_attention_planes(qkv_src.p, qkv_src.plane, attp, ln_plane, batch, T, c.n_audio_head, L.q, L.k, L.v,
+                                        L.out.sc.a, stream_);
+      }
       kt_end();
     } else {
-      kt_begin(kKcEncAttnAlt, 4.0 * batch * c.n_audio_head * double(T) * T * 64, 0);
+      kt_begin(kKcEncAttnAlt, attn_flops, 0);
       launch_encoder_attention(ws_.qkv, ws_.att, batch, T, c.n_audio_head, attn_alt, stream_);
       kt_end();
-      if (op) {
-        to_planes(ws_.att, ws_.cvt, cvt_plane, M, d, &sc.out.a, 0);
-        att_src = ws_.cvt; att_src_plane = cvt_plane;
+      if (op) att_src = hand_over(ws_.att, ws_.cvt, cvt_plane, M, d, &s_out, 0);
+    }
+    EncGemm o;
+    o.w = &L.out; o.epi = kEpiBias | kEpiResidual;
+    o.A32 = ws_.att; o.g.A = att_src.p; o.g.a_plane = att_src.plane; o.g.M = M; o.g.lda = d; o.g.ldc = d;
+    o.C32 = ws_.x; o.g.R = ws_.x;
+    fuse_ln(o, L.mlp_ln_g, L.mlp_ln_b, L.fc1);
+    enc_gemm(o);
+    layernorm_for(L.fc1, L.mlp_ln_g, L.mlp_ln_b);
+    EncGemm f1;
+    f1.w = &L.fc1; f1.epi = kEpiBias | kEpiGelu;
+    f1.A32 = ws_.ln; f1.g.A = lnp; f1.g.a_plane = ln_plane; f1.g.M = M; f1.g.lda = d; f1.g.ldc = 4 * d;
+    f1.to_planes = on_planes(L.fc2); f1.C32 = ws_.hid; f1.P = hidp; f1.p_plane = hid_plane; f1.out_scale = &s_fc2;
+    const PlaneOperand hid_src = enc_gemm(f1);
+    EncGemm f2;
+    f2.w = &L.fc2; f2.epi = kEpiBias | kEpiResidual;
+    f2.A32 = ws_.hid; f2.g.A = hid_src.p; f2.g.a_plane = hid_src.plane; f2.g.M = M; f2.g.lda = 4 * d; f2.g.ldc = d;
+    f2.C32 = ws_.x; f2.g.R = ws_.x;
+    if (l + 1 < c.n_audio_layer) {
+      fuse_ln(f2, enc_layers_[l + 1].attn_ln_g, enc_layers_[l + 1].attn_ln_b, enc_layers_[l + 1].qkv);
+    } else {  // the encoder's final LayerNorm: also the API's fp32 enc_out and the non-finite flag
+      fuse_ln(f2, enc_ln_post_g, enc_ln_post_b, cross_kv_);
+      if (f2.g.ln_P) {
+        f2.g.ln_y32 = ws_.enc_out; f2.g.nonfinite = slot.d_flag;
+        // absorbed cross-attention: these planes ARE what the decoder streams (no cross-KV projection)
+        if (absorb) f2.g.ln_P = slot.e_planes, f2.g.ln_plane = e_plane;
       }
     }
-    if (op) {
-      PlaneGemmArgs o;
-      o.A = att_src; o.a_plane = att_src_plane; o.lda = d; o.W = wp.out.w; o.bias = w.attn.bo;
-      o.C = ws_.x; o.R = ws_.x; o.ldc = d; o.M = M; o.N = d; o.K = d;
-      if (f1p) fuse_ln(o, w.mlp_ln_g, w.mlp_ln_b, sc.fc1.a);
-      ln_done = plane_gemm(o, sc.out, kEpiBias | kEpiResidual, 2.0 * o.M * o.N * o.K);
-    } else {
-      GemmArgs o;
-      o.A = ws_.att; o.lda = d; o.W = w.attn.wo; o.bias = w.attn.bo; o.C = ws_.x; o.R = ws_.x; o.ldc = d;
-      o.M = M; o.N = d; o.K = d;
-      alt_gemm(o, sc.out, kEpiBias | kEpiResidual, 2.0 * o.M * o.N * o.K);
-    }
-    layernorm_for(f1p, sc.fc1.a, w.mlp_ln_g, w.mlp_ln_b);
-    const unsigned short* hid_src = hidp;  // the plane fc2's operand
-    long hid_src_plane = hid_plane;
-    if (f1p) {
-      PlaneGemmArgs f1;
-      f1.A = lnp; f1.a_plane = ln_plane; f1.lda = d; f1.W = wp.fc1.w; f1.bias = w.b1;
-      if (f2p) {
-        f1.P = hidp; f1.p_plane = hid_plane; f1.out_scale[0] = sc.fc2.a;
-      } else {
-        f1.C = ws_.hid;
-      }
-      f1.ldc = 4 * d; f1.M = M; f1.N = 4 * d; f1.K = d;
-      plane_gemm(f1, sc.fc1, kEpiBias | kEpiGelu, 2.0 * f1.M * f1.N * f1.K);
-    } else {
-      GemmArgs f1;
-      f1.A = ws_.ln; f1.lda = d; f1.W = w.w1; f1.bias = w.b1; f1.C = ws_.hid; f1.ldc = 4 * d;
-      f1.M = M; f1.N = 4 * d; f1.K = d;
-      alt_gemm(f1, sc.fc1, kEpiBias | kEpiGelu, 2.0 * f1.M * f1.N * f1.K);
-      if (f2p) {
-        to_planes(ws_.hid, ws_.cvt, cvt_plane, M, 4 * d, &sc.fc2.a, 0);
-        hid_src = ws_.cvt; hid_src_plane = cvt_plane;
-      }
-    }
-    if (f2p) {
-      PlaneGemmArgs f2;
-      f2.A = hid_src; f2.a_plane = hid_src_plane; f2.lda = 4 * d; f2.W = wp.fc2.w; f2.bias = w.b2;
-      f2.C = ws_.x; f2.R = ws_.x; f2.ldc = d; f2.M = M; f2.N = d; f2.K = 4 * d;
-      if (l + 1 < c.n_audio_layer) {
-        if (gemm_on_planes(sc_layers_[l + 1].qkv)) fuse_ln(f2, enc_blocks_[l + 1].attn_ln_g, enc_blocks_[l + 1].attn_ln_b, sc_layers_[l + 1].qkv.a);
-      } else if (gemm_on_planes(sc_cross_kv_)) {  // the encoder's final LayerNorm: also the API's fp32 enc_out and the non-finite flag
-        fuse_ln(f2, enc_ln_post_g, enc_ln_post_b, sc_cross_kv_.a);
-        f2.ln_y32 = ws_.enc_out; f2.nonfinite = slot.d_flag;
-        if (absorb && f2.ln_P) {  // absorbed cross-attention: these planes ARE what the decoder streams (no cross-KV projection)
-          f2.ln_P = slot.e_planes; f2.ln_plane = e_plane;
-        }
-        if (!f2.ln_P) f2.ln_y32 = nullptr, f2.nonfinite = nullptr;
-      }
-      ln_done = plane_gemm(f2, sc.fc2, kEpiBias | kEpiResidual, 2.0 * f2.M * f2.N * f2.K);
-    } else {
-      GemmArgs f2;
-      f2.A = ws_.hid; f2.lda = 4 * d; f2.W = w.w2; f2.bias = w.b2; f2.C = ws_.x; f2.R = ws_.x; f2.ldc = d;
-      f2.M = M; f2.N = d; f2.K = 4 * d;
-      alt_gemm(f2, sc.fc2, kEpiBias | kEpiResidual, 2.0 * f2.M * f2.N * f2.K);
-    }
+    enc_gemm(f2);
   }
-  const bool kp = gemm_on_planes(sc_cross_kv_);
-  if (ln_done) {
-    ln_done = false;
-  } else {
-    kt_begin(kKcLayerNorm, 0, 2.0 * M * d * 4);
+  const bool kp = on_planes(cross_kv_), post_fused = ln_done;
+  ln_done = false;
+  // bf16 storage mode keeps two habits of its own here, both inputs of bench.py's roofline table: it makes the ln_post
+  // record even when the LayerNorm was fused, with the flag copy inside its event pair, ...
+  if (bf || !post_fused) kt_begin(kKcLayerNorm, 0, (bf ? 2.5 : 2.0) * M * d * 4);  // ... and counts 2.5 x the fp32 bytes
+  if (!post_fused) {
     if (kp) {
-      launch_layernorm_planes(ws_.x, absorb ? slot.e_planes : lnp, absorb ? e_plane : ln_plane, sc_cross_kv_.a, ws_.enc_out,
-                              enc_ln_post_g, enc_ln_post_b, M, d, stream_, slot.d_flag);
+      launch_layernorm_planes(ws_.x, absorb ? slot.e_planes : lnp, absorb ? e_plane : ln_plane, a_scale(cross_kv_), ws_.enc_out,
+                              enc_ln_post_g, enc_ln_post_b, M, d, stream_, slot.d_flag, bf);
     } else {
       launch_layernorm(ws_.x, ws_.enc_out, enc_ln_post_g, enc_ln_post_b, M, d, stream_, slot.d_flag);
     }
-    kt_end();
+    if (!bf) kt_end();
   }
   HIPCHK(hipMemcpyAsync(slot.h_flag, slot.d_flag, sizeof(int), hipMemcpyDeviceToHost, stream_));
+  if (bf) kt_end();
   HIPCHK(hipEventRecord(slot.enc_mid, stream_));
   // cross-attention K/V of every decoder layer, projected once per clip into the persistent cache
   // [layer][k|v][clip][head][t][64] (the reference recomputes them inside every decoder Invoke(), whisper.cpp:375) —
   // unless the decoder runs the absorbed form, which needs the planes of the encoder output and nothing else
   slot.absorbed = absorb;
-  if (absorb) {
-  } else if (kp) {
-    PlaneGemmArgs g;
-    need_cross_kv(slot);
-    g.A = lnp; g.a_plane = ln_plane; g.lda = d; g.W = cross_kv_p_.w; g.bias = cross_kv_b;
-    g.C = slot.cross_kv; g.M = M; g.N = c.n_text_layer * 2 * d; g.K = d;
-    g.c_rpb = T; g.kv_batch = batch; g.kv_heads = c.n_text_head; g.kv_dmodel = d;
-    plane_gemm(g, sc_cross_kv_, kEpiBias | kEpiKvLayout, 2.0 * g.M * g.N * g.K);
-  } else {
-    GemmArgs g;
-    need_cross_kv(slot);
-    g.A = ws_.enc_out; g.lda = d; g.W = cross_kv_w; g.bias = cross_kv_b; g.C = slot.cross_kv;
-    g.M = M; g.N = c.n_text_layer * 2 * d; g.K = d;
-    g.c_rpb = T; g.kv_batch = batch; g.kv_heads = c.n_text_head; g.kv_dmodel = d;
-    alt_gemm(g, sc_cross_kv_, kEpiBias | kEpiKvLayout, 2.0 * g.M * g.N * g.K);
-  }
-  HIPCHK(hipEventRecord(slot.enc_done, stream_));
-  slot.used = true;
-  last_enc_slot_ = enc_slot_;
-  enc_slot_ = (enc_slot_ + 1) % kSlots;
-}
-
-// bf16 storage mode (option "bf16"): the same graph with every contraction operand stored as ONE bf16 matrix
-// (k_gemm_bf16.hip, encoder_attention_planes<true>); the residual stream x and the API's enc_out stay fp32, the
-// cross-KV cache of the slot is written as bf16 (half the bytes of the default mode, same layout).
-void Engine::encode_enqueue_bf16(const float* d_mel, int batch) {
-  const wtw::Dims& c = dims_;
-  const int T0 = mel_frames(), T = c.n_audio_ctx, d = c.n_audio_state, M = batch * T, nm = c.n_mels;
-  Slot& slot = slots_[enc_slot_];
-  if (slot.used) HIPCHK(hipStreamWaitEvent(stream_, slot.dec_done, 0));
-  slot.kt_cls.clear();
-  slot.kt_flops.clear();
-  slot.kt_bytes.clear();
-  slot.batch = batch;
-  HIPCHK(hipMemsetAsync(slot.d_flag, 0, sizeof(int), stream_));
-  HIPCHK(hipEventRecord(slot.enc_begin, stream_));
-  unsigned short* const lnp = reinterpret_cast<unsigned short*>(ws_.ln);
-  unsigned short* const qkvp = reinterpret_cast<unsigned short*>(ws_.qkv);
-  unsigned short* const attp = reinterpret_cast<unsigned short*>(ws_.att);
-  unsigned short* const hidp = reinterpret_cast<unsigned short*>(ws_.hid);
-
-  kt_begin(kKcTranspose, 0, 1.5 * batch * nm * T0 * 4);
-  launch_mel_transpose_planes(d_mel, ws_.melTp, 0, 1.0f, batch, nm, T0, nm, stream_, true);
-  kt_end();
-  {
-    PlaneGemmArgs g;  // conv1 + GELU: rows (clip, t) read melT rows t..t+2 (input t-1..t+1)
-    g.A = ws_.melTp; g.a_rpb = T0; g.a_bs = long(T0 + 2) * nm; g.lda = nm;
-    g.W = bf_.conv1; g.bias = conv1_b;
-    g.P = ws_.h1pp + d;  // row t lands at padded row t + 1
-    g.c_rpb = T0; g.c_bs = long(T0 + 2) * d; g.ldc = d;
-    g.M = batch * T0; g.N = d; g.K = bf_.conv1_kpad;
-    kt_begin(kKcGemm, 2.0 * g.M * g.N * (3.0 * nm), 0);
-    launch_gemm_bf16_planes(g, kEpiBias | kEpiGelu, stream_);
-    kt_end();
-  }
-  bool have_ln = false;  // the LayerNorm plane of the coming layer is already in lnp (written by a GEMM epilogue)
-  {
-    PlaneGemmArgs g;  // conv2 (stride 2) + GELU + positional embedding
-    g.A = ws_.h1pp; g.a_rpb = T; g.a_bs = long(T0 + 2) * d; g.lda = 2 * d;
-    g.W = bf_.conv2; g.bias = conv2_b; g.pos = enc_pos; g.pos_period = T;
-    g.C = ws_.x; g.ldc = d;
-    g.M = M; g.N = d; g.K = 3 * d;
-    // (round 4) the LayerNorm in front of a layer's qkv / fc1 GEMM and ln_post are written by the epilogue of the GEMM
-    // that finishes the residual rows (k_gemm_bf16.hip, whole-row tiles): no separate launch re-reads the stream
-    if (c.n_audio_layer > 0) g.ln_g = enc_blocks_[0].attn_ln_g, g.ln_b = enc_blocks_[0].attn_ln_b, g.ln_P = lnp;
-    kt_begin(kKcGemm, 2.0 * g.M * g.N * g.K, 0);
-    have_ln = launch_gemm_bf16_planes(g, kEpiBias | kEpiGelu | kEpiPos, stream_);
-    kt_end();
-  }
-  const bool absorb = absorb_for(batch);  // the decoder streams the encoder output itself (one bf16 plane per slot): no cross-KV GEMM
-  bool have_post = false;
-  for (int l = 0; l < c.n_audio_layer; ++l) {
-    const BlockWeights& w = enc_blocks_[l];
-    const Bf16Encoder::Layer& wb = bf_.layers[l];
-    if (!have_ln) {
-      kt_begin(kKcLayerNorm, 0, 1.5 * M * d * 4);
-      launch_layernorm_planes(ws_.x, lnp, 0, 1.0f, nullptr, w.attn_ln_g, w.attn_ln_b, M, d, stream_, nullptr, true);
-      kt_end();
-    }
-    PlaneGemmArgs q;
-    q.A = lnp; q.lda = d; q.W = wb.qkv; q.bias = w.attn.bqkv;
-    q.P = qkvp; q.ldc = 3 * d; q.M = M; q.N = 3 * d; q.K = d;
-    kt_begin(kKcGemm, 2.0 * q.M * q.N * q.K, 0);
-    launch_gemm_bf16_planes(q, kEpiBias, stream_);
-    kt_end();
-    kt_begin(kKcEncAttn, 4.0 * batch * c.n_audio_head * double(T) * T * 64, 0);
-    launch_encoder_attention_bf16(qkvp, attp, batch, T, c.n_audio_head, stream_);
-    kt_end();
-    PlaneGemmArgs o;
-    o.A = attp; o.lda = d; o.W = wb.out; o.bias = w.attn.bo;
-    o.C = ws_.x; o.R = ws_.x; o.ldc = d; o.M = M; o.N = d; o.K = d;
-    o.ln_g = w.mlp_ln_g; o.ln_b = w.mlp_ln_b; o.ln_P = lnp;
-    kt_begin(kKcGemm, 2.0 * o.M * o.N * o.K, 0);
-    const bool have_mlp_ln = launch_gemm_bf16_planes(o, kEpiBias | kEpiResidual, stream_);
-    kt_end();
-    if (!have_mlp_ln) {
-      kt_begin(kKcLayerNorm, 0, 1.5 * M * d * 4);
-      launch_layernorm_planes(ws_.x, lnp, 0, 1.0f, nullptr, w.mlp_ln_g, w.mlp_ln_b, M, d, stream_, nullptr, true);
-      kt_end();
-    }
-    PlaneGemmArgs f1;
-    f1.A = lnp; f1.lda = d; f1.W = wb.fc1; f1.bias = w.b1;
-    f1.P = hidp; f1.ldc = 4 * d; f1.M = M; f1.N = 4 * d; f1.K = d;
-    kt_begin(kKcGemm, 2.0 * f1.M * f1.N * f1.K, 0);
-    launch_gemm_bf16_planes(f1, kEpiBias | kEpiGelu, stream_);
-    kt_end();
-    PlaneGemmArgs f2;
-    f2.A = hidp; f2.lda = 4 * d; f2.W = wb.fc2; f2.bias = w.b2;
-    f2.C = ws_.x; f2.R = ws_.x; f2.ldc = d; f2.M = M; f2.N = d; f2.K = 4 * d;
-    const bool last = l + 1 == c.n_audio_layer;
-    if (!last) {
-      f2.ln_g = enc_blocks_[l + 1].attn_ln_g; f2.ln_b = enc_blocks_[l + 1].attn_ln_b; f2.ln_P = lnp;
-    } else {  // ln_post: the bf16 plane (the decoder's stream in the absorbed form), the fp32 enc_out and the non-finite flag
-      f2.ln_g = enc_ln_post_g; f2.ln_b = enc_ln_post_b; f2.ln_P = absorb ? slot.e_planes : lnp;
-      f2.ln_y32 = ws_.enc_out; f2.nonfinite = slot.d_flag;
-    }
-    kt_begin(kKcGemm, 2.0 * f2.M * f2.N * f2.K, 0);
-    const bool fused = launch_gemm_bf16_planes(f2, kEpiBias | kEpiResidual, stream_);
-    kt_end();
-    (last ? have_post : have_ln) = fused;
-  }
-  kt_begin(kKcLayerNorm, 0, 2.5 * M * d * 4);
-  if (!have_post) {
-    launch_layernorm_planes(ws_.x, absorb ? slot.e_planes : lnp, 0, 1.0f, ws_.enc_out, enc_ln_post_g, enc_ln_post_b, M, d, stream_,
-                            slot.d_flag, true);
-  }
-  HIPCHK(hipMemcpyAsync(slot.h_flag, slot.d_flag, sizeof(int), hipMemcpyDeviceToHost, stream_));
-  kt_end();
-  HIPCHK(hipEventRecord(slot.enc_mid, stream_));
-  slot.absorbed = absorb;
   if (!absorb) {
-    PlaneGemmArgs g;  // cross-attention K/V of every decoder layer into the slot's cache, as bf16
     need_cross_kv(slot);
-    g.A = lnp; g.lda = d; g.W = bf_.cross_kv; g.bias = cross_kv_b;
-    g.P = reinterpret_cast<unsigned short*>(slot.cross_kv); g.M = M; g.N = c.n_text_layer * 2 * d; g.K = d;
-    g.c_rpb = T; g.kv_batch = batch; g.kv_heads = c.n_text_head; g.kv_dmodel = d;
-    kt_begin(kKcGemm, 2.0 * g.M * g.N * g.K, 0);
-    launch_gemm_bf16_planes(g, kEpiBias | kEpiKvLayout, stream_);
-    kt_end();
+    EncGemm e;
+    e.w = &cross_kv_; e.epi = kEpiBias | kEpiKvLayout;
+    e.A32 = ws_.enc_out; e.g.A = lnp; e.g.a_plane = ln_plane; e.g.M = M; e.g.lda = d;
+    e.g.c_rpb = T; e.g.kv_batch = batch; e.g.kv_heads = c.n_text_head; e.g.kv_dmodel = d;
+    // its consumer, the cached cross-attention, reads fp32, or in bf16 storage mode bf16 in the same layout
+    e.to_planes = bf; e.C32 = slot.cross_kv; e.P = reinterpret_cast<unsigned short*>(slot.cross_kv);
+    enc_gemm(e);
   }
   HIPCHK(hipEventRecord(slot.enc_done, stream_));
   slot.used = true;
@@ -2007,7 +1836,7 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
       if (p.align && !p.align->layer[size_t(l)].empty()) {  // word timestamps: keep this layer's alignment heads' weights
         const AlignSink& sk = *p.align;
         AlignScoresArgs as;
-        as.qp = dw.qp; as.e = p.e; as.e_plane = long(ws_.batch) * T * d; as.e_scale = sc_cross_kv_.a;
+        as.qp = dw.qp; as.e = p.e; as.e_plane = long(ws_.batch) * T * d; as.e_scale = cross_kv_.sc.a;
         as.batch = p.clips; as.H = H; as.d_model = d; as.T = T; as.np = p.np; as.pos0 = p.pos0;
         as.n_heads = int(sk.layer[size_t(l)].size());
         for (int i = 0; i < as.n_heads; ++i) as.head[i] = sk.layer[size_t(l)][size_t(i)].first, as.slot[i] = sk.layer[size_t(l)][size_t(i)].second;
@@ -2018,7 +1847,7 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
       const int nq_max = cross_absorbed_max_nq(H), nq_all = M / p.clips;
       for (int p0 = 0; p0 < nq_all; p0 += nq_max) {
         CrossAbsorbedArgs ca;
-        ca.qp = dw.qp; ca.e = p.e; ca.e_plane = long(ws_.batch) * T * d; ca.e_scale = sc_cross_kv_.a;
+        ca.qp = dw.qp; ca.e = p.e; ca.e_plane = long(ws_.batch) * T * d; ca.e_scale = cross_kv_.sc.a;
         ca.bf16 = bf; ca.split = p.e_split; ca.e2 = p.e2; ca.e3 = p.e3; ca.e4 = p.e4;
         ca.ws = dw.abs_ws; ca.batch = p.clips; ca.heads = H; ca.d_model = d; ca.T = T; ca.chunks = p.n_abs;
         ca.nq = std::min(nq_max, nq_all - p0); ca.p0 = p0;
@@ -3154,7 +2983,7 @@ void Engine::align_words(int batch, const std::vector<Segment>& segs, const std:
   HIPCHK(hipMemcpyAsync(aw_.lfn, aw_.h_lfn, size_t(3) * 64 * sizeof(int), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(fw_.ids, fw_.h_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
   if (!slot.absorbed) {  // the decode ran the cached form: the planes the absorbed form reads, from the fp32 encoder output
-    launch_f32_to_planes(ws_.enc_out, slot.e_planes, long(ws_.batch) * T * d, long(batch) * T, d, &sc_cross_kv_.a, 0, st);
+    launch_f32_to_planes(ws_.enc_out, slot.e_planes, long(ws_.batch) * T * d, long(batch) * T, d, &cross_kv_.sc.a, 0, st);
   }
   AlignSink sink;
   sink.heads_total = n_heads; sink.L_max = L_max; sink.ldw = T; sink.W = aw_.W;

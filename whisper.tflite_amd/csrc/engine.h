@@ -58,14 +58,30 @@ struct KernelStat {
 // kKcConvert: the fp32 -> planes hand-over between the two kinds
 enum KernelClass { kKcGemm = 0, kKcEncAttn, kKcLayerNorm, kKcTranspose, kKcGemmAlt, kKcEncAttnAlt, kKcConvert, kKcCount };
 
-struct AttnWeights {
-  const float *wqkv = nullptr, *bqkv = nullptr;  // fused [3d][d] (self attention)
-  const float *wo = nullptr, *bo = nullptr;
+// Operand scales of the two-plane fp16 encoder kernels (powers of two, f16_scale_for): derived at load
+// time from weight-only upper bounds of every contraction operand (LayerNorm output <= |g| sqrt(d-1) + |b|,
+// Linear output <= sum |W| * input bound + |bias|, GELU(x) <= max(x, 0.17), attention output <= V bound),
+// so no operand can overflow fp16 for an input mel inside Engine::kMelBound
+struct GemmScale {
+  float a = 1.0f, w = 64.0f;
+  bool f16_ok = true;  // false: the operand's bound is too far above its typical magnitude (upload_weights)
 };
-struct BlockWeights {  // encoder layer: fp32 row-major [N][K]
-  const float *attn_ln_g, *attn_ln_b;
-  AttnWeights attn;
-  const float *mlp_ln_g, *mlp_ln_b, *w1, *b1, *w2, *b2;
+// The weight side of one encoder contraction, in every form a kernel takes it (Engine::encode_enqueue picks one per launch)
+struct EncLinear {
+  const float* w32 = nullptr;           // [N][k32] fp32 row-major: the fp32-storage fall-back kernels (k_gemm.hip)
+  const unsigned short* wp = nullptr;   // both fp16 planes, blocked (split_weight_planes), scaled by sc.w: the plane GEMM
+  const unsigned short* wbf = nullptr;  // [N][kbf] bf16: bf16 storage mode; null until ensure_bf16_weights
+  const float* bias = nullptr;
+  // k: the contraction's own length; k32 / kp / kbf: what each form pads it to, zero filled (its k-tile: 32, 32 and
+  // 64).  Only conv1's k = 3 n_mels is no multiple of them already.
+  int N = 0, k = 0, k32 = 0, kp = 0, kbf = 0;
+  GemmScale sc;
+};
+struct EncLayer {
+  const float *attn_ln_g = nullptr, *attn_ln_b = nullptr, *mlp_ln_g = nullptr, *mlp_ln_b = nullptr;
+  EncLinear qkv, out, fc1, fc2;      // qkv: query | key | value fused, [3d][d] (the key has no bias)
+  float q = 1.0f, k = 1.0f, v = 1.0f;  // operand scales of the plane attention
+  bool attn_f16_ok = true;
 };
 // decoder Linear weights: two fp16 planes in MFMA-fragment order (kernels.h tile_weights_f16) + their scale
 struct TiledW {
@@ -141,7 +157,7 @@ class Engine {
   long last_batches = 0;  // the next N submits are the last of a job: decoded one chain per batch (latency form); counts down
   // absorbed cross-attention in effect: the default mode needs E as fp16 planes (no fall-back on that operand); bf16
   // storage mode streams E as one bf16 plane
-  bool absorb_active() const { return cross_absorb != 0 && (bf16 != 0 || (gemm_variant < 0 && sc_cross_kv_.f16_ok)); }
+  bool absorb_active() const { return cross_absorb != 0 && (bf16 != 0 || (gemm_variant < 0 && cross_kv_.sc.f16_ok)); }
   // ... and chosen for a call: every pipelined batch (throughput: half the decoder's stream bytes, no cross-KV GEMM);
   // synchronous calls only from 32 clips on — below that the cached form's 7 launches per decoder layer beat the absorbed
   // form's 9 (single clip 7.2 against 9.0 ms, 16 clips 11.1 against 12.1 ms, 32 clips 15.2 against 15.0 ms)
@@ -402,15 +418,6 @@ class Engine {
   void ensure_bf16_weights();
   std::string weights_path_;
   bool bf16_ready_ = false;
-  struct Bf16Encoder {  // bf16 [N][Kpad] matrices of the encoder (k_gemm_bf16.hip)
-    const unsigned short *conv1 = nullptr, *conv2 = nullptr, *cross_kv = nullptr;
-    int conv1_kpad = 0;
-    struct Layer {
-      const unsigned short *qkv = nullptr, *out = nullptr, *fc1 = nullptr, *fc2 = nullptr;
-    };
-    std::vector<Layer> layers;
-  } bf_;
-  void encode_enqueue_bf16(const float* d_mel, int batch);
   const float* dev(const std::string& name) const;
   float* upload(const std::vector<float>& host);
   TiledW upload_tiled(const float* W, int N, int K);
@@ -491,6 +498,8 @@ class Engine {
   hipEvent_t ev_switch_ = nullptr;
   void select_stream(bool pipelined);
   void pick_decoder_streams();  // decoder streams that do not share a hardware queue with the encoder stream
+  // The encoder's one launch sequence, for the plane kernels, their per-contraction fall-back and bf16 storage mode
+  // alike: every contraction is described once and takes its kernel from its EncLinear record and the mode.
   // default encoder GEMM: the k16 split kernel in its two-plane fp16 form, at 2 blocks per CU when decoders
   // share the chip (pipelined), at 3 blocks per CU otherwise
   void encode_enqueue(const float* d_mel, int batch);
@@ -542,61 +551,36 @@ class Engine {
   std::map<std::string, const float*> tensors_;  // raw tensors by .wtw name
 
   // derived, re-laid-out weights
-  const float *conv1_w = nullptr, *conv1_b = nullptr, *conv2_w = nullptr, *conv2_b = nullptr;
-  int conv1_kpad = 0;
-  // encoder weights as fp16 planes for the plane GEMM (hi plane, then lo plane at + N * K), scaled by GemmScale::w
-  struct PlaneW {
-    const unsigned short* w = nullptr;  // both fp16 planes, blocked (split_weight_planes)
-  };
-  PlaneW conv1_p_, conv2_p_, cross_kv_p_;
-  struct EncLayerPlanes {
-    PlaneW qkv, out, fc1, fc2;
-  };
-  std::vector<EncLayerPlanes> enc_planes_;
-  PlaneW upload_planes(const float* W, int N, int K, int Kpad, float scale);
-  int conv1_kpad_p_ = 0;  // conv1's K padded to the plane GEMM's k-tile
+  // The encoder's contractions, one record each: conv1 and conv2 as implicit GEMMs ([co][kk * ci], fill_enc_linears),
+  // the layers' four, and the cross K/V projections of all decoder layers as one matrix [L*2*d][d]
+  EncLinear conv1_, conv2_, cross_kv_;
+  std::vector<EncLayer> enc_layers_;
+  const unsigned short* upload_planes(const float* W, int N, int K, int Kpad, float scale);
   const float* enc_pos = nullptr;
-  std::vector<BlockWeights> enc_blocks_;
   std::vector<DecBlockWeights> dec_blocks_;
   std::vector<DecBlockWeights> dec_blocks_bf_;  // bf16 storage mode: TiledW members are single bf16 planes
   TiledW tok_emb_tiled_bf_;
-  // Operand scales of the two-plane fp16 encoder kernels (powers of two, f16_scale_for): derived at load
-  // time from weight-only upper bounds of every contraction operand (LayerNorm output <= |g| sqrt(d-1) + |b|,
-  // Linear output <= sum |W| * input bound + |bias|, GELU(x) <= max(x, 0.17), attention output <= V bound),
-  // so no operand can overflow fp16 for an input mel inside kMelBound
-  struct GemmScale {
-    float a = 1.0f, w = 64.0f;
-    bool f16_ok = true;  // false: the operand's bound is too far above its typical magnitude (upload_weights)
-  };
   // Per contraction: the plane kernels unless the load-time slack check gave that contraction the full-range form
   // (GemmScale::f16_ok) or an explicit gemm_variant / attn_variant selects the fp32-storage kernels for all of them
   bool gemm_on_planes(const GemmScale& sc) const { return gemm_variant < 0 && sc.f16_ok; }
-  struct EncLayerScales {
-    GemmScale qkv, out, fc1, fc2;
-    float q = 1.0f, k = 1.0f, v = 1.0f;
-    bool attn_f16_ok = true;
-  };
   static constexpr float kMelBound = 8.0f;
   static constexpr float kF16Slack = 4096.0f;  // largest bound / typical ratio the two-plane fp16 form is used for
   int n_f16_fallbacks_ = 0;
   float f16_min_slack_bits_ = 0.0f;  // smallest log2(kF16Slack * typical / bound) over the checked operands (load time)
   long force_fallback_ = 0;
   std::vector<bool> load_ok_;  // the slack check's own verdicts, in contraction order (set_force_fallback)
-  std::vector<bool*> ok_flags();  // the f16_ok / attn_f16_ok members in contraction order
+  std::vector<bool*> ok_flags();  // the records' f16_ok / attn_f16_ok in that order: a walk in launch order
   // the fp32-storage GEMM a contraction falls back to: the forced variant, else three bf16 planes (13; 16 = the same
   // at two blocks per CU beside the decoders of the pipeline)
   int alt_gemm_variant() const {
     if (gemm_variant >= 0) return int(gemm_variant);
     return (stream_ == stream_masked_ && stream_masked_) ? 16 : 13;
   }
-  GemmScale sc_conv1_, sc_conv2_, sc_cross_kv_;
-  std::vector<EncLayerScales> sc_layers_;
   const float *enc_ln_post_g = nullptr, *enc_ln_post_b = nullptr;
-  const float *cross_kv_w = nullptr, *cross_kv_b = nullptr;  // [L*2*d][d], [L*2*d]
   const float *tok_emb = nullptr, *dec_pos = nullptr, *dec_ln_g = nullptr, *dec_ln_b = nullptr;
   TiledW tok_emb_tiled;  // logits GEMM against the tied embedding
   // front end
-  PlaneW dft_basis_p_;               // [dft_n][dft_k] windowed basis, rows (2 k, 2 k + 1) = (re, im) of bin k, as fp16 planes
+  const unsigned short* dft_basis_p_ = nullptr;  // [dft_n][dft_k] windowed basis, rows (2 k, 2 k + 1) = (re, im) of bin k, as fp16 planes
   const float* dft_zero_bias_ = nullptr;
   float dft_w_scale_ = 1.0f;
   int pw_ld_ = 0;                    // row stride of the power spectrum (dft_n / 2)
