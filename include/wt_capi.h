@@ -154,6 +154,20 @@ int wt_engine_set_prompt(wt_engine* h, const int64_t* ids, int n);
  * changes nothing without a context. */
 int wt_engine_set_context(wt_engine* h, const int64_t* ids, int n);
 
+/* Per-clip contexts: clip b of every following full-length call is decoded behind ids[offsets[b] .. offsets[b + 1])
+ * (an empty range: that clip's fed prompt is the prompt alone).  n_clips 1..64; each clip keeps the last
+ * n_text_ctx / 2 - 1 ids, as wt_engine_set_context.  n_clips = 0 clears.  Setting either kind of context clears the other.
+ * The call is one ragged decoder chain: a clip's ids, scores and samples are those of a call of
+ * its own behind wt_engine_set_context with its ids.  The read-only option "context_clips" tells n_clips.  An id outside
+ * the vocabulary, offsets that decrease, more than 4096 ids for a clip or n_clips > 64 is WT_ERR_INVALID_ARG, a vocabulary
+ * without <|startofprev|> or a Monolith engine WT_ERR_UNSUPPORTED as soon as some clip's range is not empty.  With contexts set a full-length call whose batch
+ * differs from n_clips, or in which some clip's fed prompt is >= "max_positions", is WT_ERR_INVALID_ARG; "word_timestamps"
+ * = 1 is WT_ERR_UNSUPPORTED (the alignment pass takes one prompt length per call), and so is every call that
+ * "max_positions" or a wt_engine_set_context context refuses; the engine stays usable after each.  Such calls run
+ * eagerly and capture no graph.  It works with and without "timestamps", "scores", "skip_silence", "temperature" and
+ * "temperature_fallback". */
+int wt_engine_set_contexts(wt_engine* h, const int64_t* ids, const int32_t* offsets, int n_clips);
+
 /* ---- single-clip entry points (the reference's two virtuals) ----------------------------
  * Replace Engine::transcribe(std::vector<float>&) (whisper.h:160, whisper.cpp:752-769; JNI
  * transcribeBuffer, bindings/java/whisper.tflite.cpp:45-58) and
@@ -338,6 +352,26 @@ typedef struct wt_window {
 /* returns the window count (at most cap written), or -WT_ERR_INVALID_ARG when the last synchronous decode was not a
  * seeking one */
 int wt_last_windows(const wt_engine* h, wt_window* out, int cap);
+
+/* Seeking transcription of n_files (1..64) recordings side by side (options as for wt_transcribe_long_pcm with "seek" = 1;
+ * the option "seek" itself is not read).  Every round decodes the next window of every file still running as ONE batch
+ * behind per-clip contexts (wt_engine_set_contexts), then every file takes the step of the seeking loop on its own clip;
+ * a file that has reached its end leaves the batch.  A file's result is by definition what wt_transcribe_long_pcm with
+ * "seek" = 1 gives for that file alone: window w of a file has clip index w in the sampling counter, the caller's
+ * wt_engine_set_context ids seed every file's first window, and both kinds of context are the caller's again after the
+ * call.  wt_last_windows then lists the windows file by file and wt_last_window_files is parallel to it;
+ * wt_last_segments has clip = index into that list and times in the file; wt_last_scores, wt_last_token_logprobs,
+ * wt_last_segment_scores and wt_last_decode_info have one entry per window in the same order; wt_last_file_text returns
+ * a file's lines joined by '\n'.  WT_ERR_UNSUPPORTED: "word_timestamps" = 1, more than 64 files, "condition_on_previous_text"
+ * = 1 on a vocabulary without <|startofprev|> (as wt_transcribe_long_pcm), and whatever full-length decoding refuses (the bf16 storage mode, the pipeline, beam_size > 1,
+ * language = WT_LANGUAGE_AUTO). */
+int wt_transcribe_long_batch(wt_engine* h, const float* const* pcm, const size_t* n_samples, int n_files);
+/* text of file `file` of the last wt_transcribe_long_batch (as wt_last_text: *len = its length, WT_ERR_BUFFER when cap
+ * is too small); WT_ERR_INVALID_ARG when the last synchronous decode was another call or for a file outside it */
+int wt_last_file_text(const wt_engine* h, int file, char* out, size_t cap, size_t* len);
+/* parallel to wt_last_windows: the file of every window; returns the window count (at most cap written), or
+ * -WT_ERR_INVALID_ARG when the last synchronous decode was not wt_transcribe_long_batch */
+int wt_last_window_files(const wt_engine* h, int32_t* file, int cap);
 
 /* Per-kernel-class device time of the encoder phase of the last batch call: HIP event pairs
  * recorded on the engine's stream around every launch of the class.  flops / bytes are the

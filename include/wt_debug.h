@@ -112,6 +112,22 @@ int wt_dbg_self_attention_long(wt_engine* h, int batch, int heads, int cap, int 
  * npos * batch > 128 and a batch or head count below 1 are WT_ERR_INVALID_ARG, before anything is launched. */
 int wt_dbg_self_attention_prefill(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
                                   float* kcache, float* vcache, float* out);
+/* The ragged forms of the two (wt_engine_set_contexts): the same arguments plus start [B] and P.  pos
+ * counts slots and clip b is at Whisper position pos - start[b]; a position outside [0, P) is void: its `out` rows come
+ * back zero and its caches untouched, every other clip's rows carry the bits of the unragged tap at the shifted
+ * position.  The refusals are the unragged ones, except that the long form's slot may lie past the cache (below 896);
+ * P outside [1, cap] and a NULL start are refused too. */
+int wt_dbg_self_attention_long_ragged(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
+                                      float* vcache, float* out, const int32_t* start, int P);
+int wt_dbg_self_attention_prefill_ragged(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
+                                         float* kcache, float* vcache, float* out, const int32_t* start, int P);
+/* wt_dbg_dec_ln_gemm's embedding rows under a slot count: row b = tok_emb[ids[b]] + pos_emb[clamp(pos - pos_start[b], 0,
+ * n_pos - 1)]; pos_start = NULL is wt_dbg_dec_ln_gemm with ids. */
+int wt_dbg_dec_ln_gemm_ragged(wt_engine* h, int B, int N, int K, const int64_t* ids, int pos, const int32_t* pos_start,
+                              const float* tok_emb, const float* pos_emb, int n_vocab, int n_pos, const float* ln_g,
+                              const float* ln_b, const float* W, const float* bias, int gelu, float* Y, float* xout);
+/* ragged_cap (k_misc.hip): finished[b] = 1 where pos - start[b] == P - 1, unchanged elsewhere; batch 1..64 */
+int wt_dbg_ragged_cap(wt_engine* h, int batch, int pos, int P, const int32_t* start, int32_t* finished);
 /* ts_partial + ts_select (k_timestamps.hip, option "timestamps"): one step of Whisper's timestamp
  * rules per row.  logits [B][V]; row b of ids [B][ids_stride] holds n_ids[b] ids, the first sample_begin of them the
  * prompt, and the step decides the id that follows them: token[b].  L [B] (optional) = rule 5's logsumexp of the allowed

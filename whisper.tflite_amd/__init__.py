@@ -39,12 +39,13 @@ STATUS_NAMES = {0: "WT_OK", 1: "WT_ERR_INVALID_ARG", 2: "WT_ERR_IO", 3: "WT_ERR_
 CAPI_SYMBOLS = [
     "wt_device_alloc", "wt_device_free", "wt_device_upload", "wt_device_download", "wt_device_synchronize",
     "wt_engine_create", "wt_engine_destroy", "wt_last_error", "wt_engine_dims",
-    "wt_engine_set_option", "wt_engine_get_option", "wt_engine_set_prompt", "wt_engine_set_context", "wt_transcribe_pcm", "wt_transcribe_long_pcm", "wt_transcribe_file",
+    "wt_engine_set_option", "wt_engine_get_option", "wt_engine_set_prompt", "wt_engine_set_context", "wt_engine_set_contexts", "wt_transcribe_pcm", "wt_transcribe_long_pcm", "wt_transcribe_file",
     "wt_logmel_batch", "wt_logmel_batch_dev", "wt_encdec_tokens_batch",
     "wt_encdec_tokens_batch_dev", "wt_transcribe_tokens_batch_dev", "wt_pipeline_submit_dev", "wt_pipeline_submit_pcm_dev", "wt_pipeline_collect",
     "wt_encdec_debug_batch",
     "wt_encdec_tokens_full_batch", "wt_encdec_tokens_full_batch_dev", "wt_transcribe_tokens_full_batch_dev",
     "wt_last_segments", "wt_last_segment_text", "wt_vocab_segments", "wt_vocab_seek_step", "wt_last_windows",
+    "wt_transcribe_long_batch", "wt_last_file_text", "wt_last_window_files",
     "wt_vocab_split_words", "wt_vocab_merge_punctuation", "wt_dtw_path",
     "wt_engine_set_alignment_heads", "wt_last_words", "wt_last_word_text",
     "wt_last_scores", "wt_last_token_logprobs", "wt_last_segment_scores", "wt_last_decode_info",
@@ -63,6 +64,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_self_attention_long",
     "wt_dbg_self_attention_prefill",
+    "wt_dbg_self_attention_long_ragged", "wt_dbg_self_attention_prefill_ragged", "wt_dbg_dec_ln_gemm_ragged", "wt_dbg_ragged_cap",
     "wt_dbg_timestamp_select", "wt_dbg_token_scores", "wt_dbg_sample_select",
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
     "wt_dbg_pcm_to_planes",
@@ -122,6 +124,10 @@ def lib() -> ctypes.CDLL:
         L.wt_engine_get_option.argtypes = [c_void_p, c_char_p, POINTER(c_long)]
         L.wt_engine_set_prompt.argtypes = [c_void_p, ip64, c_int]
         L.wt_engine_set_context.argtypes = [c_void_p, ip64, c_int]
+        L.wt_engine_set_contexts.argtypes = [c_void_p, ip64, ip32, c_int]
+        L.wt_transcribe_long_batch.argtypes = [c_void_p, POINTER(fp), POINTER(c_size_t), c_int]
+        L.wt_last_file_text.argtypes = [c_void_p, c_int, c_char_p, c_size_t, POINTER(c_size_t)]
+        L.wt_last_window_files.argtypes = [c_void_p, ip32, c_int]
         L.wt_transcribe_pcm.argtypes = [c_void_p, fp, c_size_t, c_char_p, c_size_t, POINTER(c_size_t)]
         L.wt_transcribe_long_pcm.argtypes = [c_void_p, fp, c_size_t, c_char_p, c_size_t, POINTER(c_size_t)]
         L.wt_transcribe_file.argtypes = [c_void_p, c_char_p, c_char_p, c_size_t, POINTER(c_size_t)]
@@ -216,6 +222,11 @@ def lib() -> ctypes.CDLL:
         L.wt_transcribe_tokens_full_batch_dev.argtypes = [c_void_p, c_void_p, c_int, ip64, c_int, ip32]
         L.wt_dbg_self_attention_long.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp]
         L.wt_dbg_self_attention_prefill.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp]
+        L.wt_dbg_self_attention_long_ragged.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp, ip32, c_int]
+        L.wt_dbg_self_attention_prefill_ragged.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp, ip32, c_int]
+        L.wt_dbg_dec_ln_gemm_ragged.argtypes = [c_void_p, c_int, c_int, c_int, ip64, c_int, ip32, fp, fp,
+                                                c_int, c_int, fp, fp, fp, fp, c_int, fp, fp]
+        L.wt_dbg_ragged_cap.argtypes = [c_void_p, c_int, c_int, c_int, ip32, ip32]
         L.wt_last_segments.argtypes = [c_void_p, c_void_p, c_int]
         L.wt_last_windows.argtypes = [c_void_p, c_void_p, c_int]
         L.wt_vocab_seek_step.argtypes = [c_void_p, ip64, c_int, c_int, c_int, c_void_p, c_int, POINTER(c_int32)]
@@ -542,6 +553,18 @@ class Engine:
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
         self._check(lib().wt_engine_set_context(self._h, ids.ctypes.data_as(POINTER(c_int64)), ids.size))
 
+    def set_contexts(self, contexts) -> None:
+        """Per-clip contexts: clip b of every following full-length call is decoded behind contexts[b] (an empty list:
+        the prompt alone); the call's batch must equal len(contexts).  One ragged decoder chain.
+        An empty list clears; setting either kind of context clears the other (option context_clips)."""
+        rows = [np.ascontiguousarray(c, dtype=np.int64).reshape(-1) for c in contexts]
+        offsets = np.zeros(len(rows) + 1, np.int32)
+        offsets[1:] = np.cumsum([r.size for r in rows])
+        flat = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+        flat = np.ascontiguousarray(flat, dtype=np.int64)
+        self._check(lib().wt_engine_set_contexts(self._h, flat.ctypes.data_as(POINTER(c_int64)),
+                                                 offsets.ctypes.data_as(POINTER(c_int32)), len(rows)))
+
     # -- shapes ----------------------------------------------------------------------
     @property
     def mel_shape(self):
@@ -571,6 +594,33 @@ class Engine:
         n = c_size_t(0)
         self._check(lib().wt_transcribe_long_pcm(self._h, _fp(pcm), pcm.size, buf, len(buf), byref(n)))
         return buf.raw[: n.value].decode("utf-8", errors="replace")
+
+    def transcribe_long_batch(self, samples_list) -> list:
+        """Seeking transcription of several recordings side by side: one window of every file per decoder chain (options
+        as for transcribe_long with seek = 1).  Returns the per-file texts, each what transcribe_long
+        gives for that file alone; last_windows() lists the windows file by file, last_window_files() is parallel to it."""
+        pcms = [_f32(s).reshape(-1) for s in samples_list]
+        n = len(pcms)
+        ptrs = (POINTER(c_float) * max(n, 1))(*[_fp(p) if p.size else None for p in pcms])
+        sizes = (c_size_t * max(n, 1))(*[p.size for p in pcms])
+        self._check(lib().wt_transcribe_long_batch(self._h, ptrs, sizes, n))
+        texts = []
+        for f in range(n):
+            ln = c_size_t(0)
+            buf = ctypes.create_string_buffer(1 << 20)
+            self._check(lib().wt_last_file_text(self._h, f, buf, len(buf), byref(ln)))
+            texts.append(buf.raw[: ln.value].decode("utf-8", errors="replace"))
+        return texts
+
+    def last_window_files(self) -> np.ndarray:
+        """int32 [windows]: the file of every record of last_windows() after transcribe_long_batch."""
+        n = lib().wt_last_window_files(self._h, None, 0)
+        if n < 0:
+            raise WtError(-n, "no window files: the last synchronous decode was not a transcribe_long_batch")
+        out = np.zeros(n, np.int32)
+        if n:
+            lib().wt_last_window_files(self._h, out.ctypes.data_as(POINTER(c_int32)), n)
+        return out
 
     # -- batch entry points ----------------------------------------------------------
     def logmel_batch(self, pcm) -> np.ndarray:
@@ -1191,6 +1241,49 @@ class Engine:
         out = np.zeros((npos * B, d), np.float32)
         self._check(lib().wt_dbg_self_attention_prefill(self._h, B, d // 64, cap, pos, npos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
         return out, kcache, vcache
+
+    def dbg_self_attention_long_ragged(self, qkv, kcache, vcache, pos, start, P):
+        """self_attention_long under a slot count: clip b at position pos - start[b], void outside [0, P)."""
+        qkv, kcache, vcache = _f32(qkv), _f32(kcache).copy(), _f32(vcache).copy()
+        start = np.ascontiguousarray(start, np.int32)
+        B, cap, d = kcache.shape
+        assert start.shape == (B,)
+        out = np.full((B, d), np.nan, np.float32)
+        self._check(lib().wt_dbg_self_attention_long_ragged(self._h, B, d // 64, cap, pos, _fp(qkv), _fp(kcache), _fp(vcache),
+                                                            _fp(out), _ip32(start), P))
+        return out, kcache, vcache
+
+    def dbg_self_attention_prefill_ragged(self, qkv, kcache, vcache, pos, npos, start, P):
+        """self_attention_prefill under a slot count: query p of clip b at position pos + p - start[b], void outside [0, P)."""
+        qkv, kcache, vcache = _f32(qkv), _f32(kcache).copy(), _f32(vcache).copy()
+        start = np.ascontiguousarray(start, np.int32)
+        B, cap, d = kcache.shape
+        assert start.shape == (B,)
+        out = np.full((npos * B, d), np.nan, np.float32)
+        self._check(lib().wt_dbg_self_attention_prefill_ragged(self._h, B, d // 64, cap, pos, npos, _fp(qkv), _fp(kcache),
+                                                               _fp(vcache), _fp(out), _ip32(start), P))
+        return out, kcache, vcache
+
+    def dbg_dec_ln_gemm_ragged(self, W, bias, ln_g, ln_b, ids, pos, pos_start, tok_emb, pos_emb, gelu=False):
+        """dbg_dec_ln_gemm's embedding rows with the positional row pos - pos_start[b] (clamped); pos_start None: as it is."""
+        W, bias, ln_g, ln_b, tok_emb, pos_emb = _f32(W), _f32(bias), _f32(ln_g), _f32(ln_b), _f32(tok_emb), _f32(pos_emb)
+        N, K = W.shape
+        ids_a = np.ascontiguousarray(ids, dtype=np.int64)
+        B = ids_a.shape[0]
+        st = np.ascontiguousarray(pos_start, np.int32) if pos_start is not None else None
+        Y = np.zeros((B, N), np.float32)
+        xout = np.zeros((B, K), np.float32)
+        self._check(lib().wt_dbg_dec_ln_gemm_ragged(
+            self._h, B, N, K, _ip64(ids_a), pos, _ip32(st) if st is not None else None, _fp(tok_emb), _fp(pos_emb),
+            tok_emb.shape[0], pos_emb.shape[0], _fp(ln_g), _fp(ln_b), _fp(W), _fp(bias), int(gelu), _fp(Y), _fp(xout)))
+        return Y, xout
+
+    def dbg_ragged_cap(self, pos, P, start, finished):
+        """ragged_cap: returns finished with finished[b] = 1 where pos - start[b] == P - 1."""
+        start = np.ascontiguousarray(start, np.int32)
+        fin = np.array(finished, np.int32)
+        self._check(lib().wt_dbg_ragged_cap(self._h, start.size, pos, P, _ip32(start), _ip32(fin)))
+        return fin
 
     # beam search (k_beam.hip).  The per-clip state is a dict of the engine's arrays (beam_state()), updated in place.
     @staticmethod

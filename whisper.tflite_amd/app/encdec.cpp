@@ -44,6 +44,8 @@ void usage(const char* argv0) {
             << "  --seek          with --long --timestamps: every window starts at the last closed timestamp of the one\n"
             << "                  before and is decoded behind the text kept so far (Whisper's transcribe loop)\n"
             << "  --no-condition  with --seek: do not feed the previous windows' text to the next (condition_on_previous_text = 0)\n"
+            << "  --inputs a.wav,b.wav  with --long --timestamps --seek: the recordings side by side, one window of every file\n"
+            << "                  per decoder chain; prints every file's text under a \"== <path>\" line\n"
             << "  --context-ids 1,2,3  with --max-positions: token ids fed in front of the prompt (Whisper's initial_prompt)\n"
             << "  --word-timestamps  with --timestamps: align every word to the audio and print, behind the segment lines,\n"
             << "                  one line per word: t0 t1 text (seconds)\n"
@@ -53,7 +55,7 @@ void usage(const char* argv0) {
 }  // namespace
 
 int main(int argc, char* argv[]) {
-  std::string model_prefix, vocab, input, lang, beam, max_positions, temperature, seed, cr_threshold, context_ids, alignment_heads;
+  std::string model_prefix, vocab, input, inputs, lang, beam, max_positions, temperature, seed, cr_threshold, context_ids, alignment_heads;
   bool word_timestamps = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
        no_condition = false;
@@ -112,6 +114,7 @@ int main(int argc, char* argv[]) {
     if (a == "--model-prefix") model_prefix = v;
     else if (a == "--vocab") vocab = v;
     else if (a == "--input") input = v;
+    else if (a == "--inputs") inputs = v;
     else if (a == "--lang") lang = v;
     else if (a == "--beam") beam = v;
     else if (a == "--max-positions") max_positions = v;
@@ -126,7 +129,11 @@ int main(int argc, char* argv[]) {
       return 109;
     }
   }
-  if (model_prefix.empty() || vocab.empty() || input.empty()) {
+  if (!inputs.empty() && !(long_audio && timestamps && seek)) {
+    std::cerr << "--inputs requires --long --timestamps --seek\n";
+    return 105;
+  }
+  if (model_prefix.empty() || vocab.empty() || (input.empty() && inputs.empty())) {
     std::cerr << (model_prefix.empty() ? "--model-prefix" : vocab.empty() ? "--vocab" : "--input")
               << " is required\n";
     usage(argv[0]);
@@ -307,6 +314,35 @@ int main(int argc, char* argv[]) {
       std::cerr << "--word-timestamps: " << wt_last_error(encdec.handle()) << "\n";
       return 105;
     }
+  }
+  if (!inputs.empty()) {  // several recordings side by side: every file's text under a "== <path>" line
+    std::vector<std::string> paths;
+    for (size_t at = 0; at <= inputs.size();) {
+      const size_t comma = std::min(inputs.find(',', at), inputs.size());
+      if (comma > at) paths.push_back(inputs.substr(at, comma - at));
+      at = comma + 1;
+    }
+    std::vector<std::vector<float>> pcms;
+    std::vector<const float*> ptrs;
+    std::vector<size_t> sizes;
+    for (const std::string& path : paths) pcms.push_back(wav_read_legacy(path.c_str()));
+    for (const std::vector<float>& x : pcms) ptrs.push_back(x.data()), sizes.push_back(x.size());
+    if (wt_transcribe_long_batch(encdec.handle(), ptrs.data(), sizes.data(), int(paths.size())) != WT_OK) {
+      std::cerr << "transcribe failed: " << wt_last_error(encdec.handle()) << "\n";
+      return 1;
+    }
+    for (size_t f = 0; f < paths.size(); ++f) {
+      size_t len = 0;
+      wt_last_file_text(encdec.handle(), int(f), nullptr, 0, &len);  // the length first
+      std::string text(len + 1, '\0');
+      if (wt_last_file_text(encdec.handle(), int(f), &text[0], text.size(), &len) != WT_OK) {
+        std::cerr << "transcribe failed: " << wt_last_error(encdec.handle()) << "\n";
+        return 1;
+      }
+      text.resize(len);
+      std::cout << "== " << paths[f] << "\n" << text << "\n";
+    }
+    return 0;
   }
   std::string text;
   if (long_audio) {

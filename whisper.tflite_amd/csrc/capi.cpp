@@ -318,6 +318,16 @@ int wt_engine_set_context(wt_engine* h, const int64_t* ids, int n) {
   return WT_OK;
 }
 
+int wt_engine_set_contexts(wt_engine* h, const int64_t* ids, const int32_t* offsets, int n_clips) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  try {
+    h->impl->set_contexts(ids, offsets, n_clips);
+  } catch (const wt::Error& err) {
+    return fail(h, err.code, err.what());
+  }
+  return WT_OK;
+}
+
 int wt_engine_set_alignment_heads(wt_engine* h, const int32_t* layer_head, int n) {
   if (!h) return WT_ERR_INVALID_ARG;
   try {
@@ -352,6 +362,7 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "word_timestamps") *value = e.word_timestamps;
   else if (k == "alignment_heads") *value = long(e.alignment_heads_in_effect().size());  // read-only: the count in effect
   else if (k == "context_ids") *value = long(e.context_ids.size());  // read-only: ids kept by wt_engine_set_context
+  else if (k == "context_clips") *value = long(e.clip_contexts.size());  // read-only: clips given to wt_engine_set_contexts
   else if (k == "graphs_cached") *value = e.graphs_cached();          // read-only: captured decoder graphs held
   else if (k == "stop_at_eot") *value = e.stop_at_eot;
   else if (k == "verbose") *value = e.verbose;
@@ -692,6 +703,15 @@ int wt_last_windows(const wt_engine* h, wt_window* out, int cap) {
   return n;
 }
 
+int wt_last_window_files(const wt_engine* h, int32_t* file, int cap) {
+  if (!h || cap < 0 || (cap > 0 && !file)) return -WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_windows_valid || e.last_window_files.size() != e.last_windows.size()) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last_window_files.size());
+  for (int i = 0; i < n && i < cap; ++i) file[i] = e.last_window_files[size_t(i)];
+  return n;
+}
+
 int wt_last_token_logprobs(const wt_engine* h, float* out, int stride, int cap_clips) {
   if (!h || cap_clips < 0 || stride < 0 || (cap_clips > 0 && stride > 0 && !out)) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
@@ -834,6 +854,24 @@ int wt_transcribe_pcm(wt_engine* h, const float* pcm, size_t n_samples, char* ou
     return rc;
   }
   return copy_text(text, out, cap, len);
+}
+
+int wt_transcribe_long_batch(wt_engine* h, const float* const* pcm, const size_t* n_samples, int n_files) {
+  if (!h || !pcm || !n_samples) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::Engine& e = *h->impl;
+    e.require_idle();
+    e.check_timestamp_call();  // before anything is enqueued
+    e.check_full_call();
+    wt::transcribe_seek_batch(e, pcm, n_samples, n_files);
+  });
+}
+
+int wt_last_file_text(const wt_engine* h, int file, char* out, size_t cap, size_t* len) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_windows_valid || file < 0 || size_t(file) >= e.last_file_text.size()) return WT_ERR_INVALID_ARG;
+  return copy_text(e.last_file_text[size_t(file)], out, cap, len);
 }
 
 int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, char* out, size_t cap,

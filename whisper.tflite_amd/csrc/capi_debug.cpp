@@ -523,8 +523,11 @@ int wt_dbg_dec_gemm_bf16(wt_engine* h, int mode, int B, int N, int K, const floa
 
 static int dbg_dec_ln_gemm_impl(wt_engine* h, int B, int N, int K, const float* xin, const int64_t* ids, int pos,
                                 const float* tok_emb, const float* pos_emb, int n_vocab, int n_pos, const float* ln_g,
-                                const float* ln_b, const float* W, const float* bias, int gelu, float* Y, float* xout, bool bf) {
-  if (!h || B < 1 || B > 64 || (K != 128 && K != 384 && K != 512) || (!xin && !ids) || pos < 0 || (ids && pos >= n_pos)) return WT_ERR_INVALID_ARG;
+                                const float* ln_b, const float* W, const float* bias, int gelu, float* Y, float* xout, bool bf,
+                                const int32_t* pos_start = nullptr) {
+  // (pos_start: pos counts slots and may lie past the table; the kernel clamps the row it reads)
+  if (!h || B < 1 || B > 64 || (K != 128 && K != 384 && K != 512) || (!xin && !ids) || pos < 0 ||
+      (ids && pos >= (pos_start ? 4096 : n_pos)) || (pos_start && (!ids || n_pos < 1))) return WT_ERR_INVALID_ARG;
   return guarded(h, [&] {
     const DevTiled dW(W, N, K, bf);
     DevArr<float> dxin(xin ? size_t(B) * K : 0, xin);
@@ -543,6 +546,8 @@ static int dbg_dec_ln_gemm_impl(wt_engine* h, int B, int N, int K, const float* 
       g.ids = dids.p; g.ids_stride = pos + 1; g.pos = pos;
       g.tok_emb = dtok.p; g.pos_emb = dpos.p; g.n_vocab = n_vocab;
     }
+    const DevArr<int> dstart(pos_start ? size_t(B) : 0, pos_start);
+    if (pos_start) g.pos_start = dstart.p, g.n_ctx = n_pos;
     g.bias = dB.p; g.Y = dY.p; g.ldy = N;
     wt::launch_dec_gemm(g, wt::kProLn, gelu ? wt::kDecBiasGelu : wt::kDecBias, h->impl->stream());
     h->impl->sync();
@@ -562,6 +567,13 @@ int wt_dbg_dec_ln_gemm_bf16(wt_engine* h, int B, int N, int K, const float* xin,
                             const float* ln_g, const float* ln_b, const float* W, const float* bias,
                             int gelu, float* Y, float* xout) {
   return dbg_dec_ln_gemm_impl(h, B, N, K, xin, ids, pos, tok_emb, pos_emb, n_vocab, n_pos, ln_g, ln_b, W, bias, gelu, Y, xout, true);
+}
+
+int wt_dbg_dec_ln_gemm_ragged(wt_engine* h, int B, int N, int K, const int64_t* ids, int pos, const int32_t* pos_start,
+                              const float* tok_emb, const float* pos_emb, int n_vocab, int n_pos,
+                              const float* ln_g, const float* ln_b, const float* W, const float* bias,
+                              int gelu, float* Y, float* xout) {
+  return dbg_dec_ln_gemm_impl(h, B, N, K, nullptr, ids, pos, tok_emb, pos_emb, n_vocab, n_pos, ln_g, ln_b, W, bias, gelu, Y, xout, false, pos_start);
 }
 
 int wt_dbg_layernorm(wt_engine* h, int M, int d, const float* x, const float* g, const float* b, float* y) {
@@ -724,6 +736,48 @@ int wt_dbg_self_attention_prefill(wt_engine* h, int batch, int heads, int cap, i
     dout.to_host(out, rows * d);
     dk.to_host(kcache, nc);
     dv.to_host(vcache, nc);
+  });
+}
+int wt_dbg_self_attention_long_ragged(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
+                                      float* vcache, float* out, const int32_t* start, int P) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::check_self_attention_long_ragged(cap, pos, P, batch, heads);  // the launcher's own refusals, before anything is allocated
+    if (!qkv || !kcache || !vcache || !out || !start) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_self_attention_long_ragged: NULL array");
+    const size_t d = size_t(heads) * 64, nc = size_t(batch) * cap * d;
+    DevArr<float> dq(size_t(batch) * 3 * d, qkv), dk(nc, kcache), dv(nc, vcache), dout(size_t(batch) * d);
+    const DevArr<int> ds(size_t(batch), start);
+    wt::launch_self_attention_long_ragged(dq.p, dk.p, dv.p, cap, pos, ds.p, P, dout.p, batch, heads, h->impl->stream());
+    h->impl->sync();
+    dout.to_host(out, size_t(batch) * d);
+    dk.to_host(kcache, nc);
+    dv.to_host(vcache, nc);
+  });
+}
+int wt_dbg_self_attention_prefill_ragged(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
+                                         float* kcache, float* vcache, float* out, const int32_t* start, int P) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::check_self_attention_prefill_ragged(cap, pos, npos, P, batch, heads);  // the launcher's own refusals, before anything is allocated
+    if (!qkv || !kcache || !vcache || !out || !start) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_self_attention_prefill_ragged: NULL array");
+    const size_t d = size_t(heads) * 64, rows = size_t(npos) * batch, nc = size_t(batch) * cap * d;
+    DevArr<float> dq(rows * 3 * d, qkv), dk(nc, kcache), dv(nc, vcache), dout(rows * d);
+    const DevArr<int> ds(size_t(batch), start);
+    wt::launch_self_attention_prefill_ragged(dq.p, dk.p, dv.p, cap, pos, npos, ds.p, P, dout.p, batch, heads, h->impl->stream());
+    h->impl->sync();
+    dout.to_host(out, rows * d);
+    dk.to_host(kcache, nc);
+    dv.to_host(vcache, nc);
+  });
+}
+int wt_dbg_ragged_cap(wt_engine* h, int batch, int pos, int P, const int32_t* start, int32_t* finished) {
+  if (!h || batch < 1 || batch > 64 || !start || !finished) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    const DevArr<int> ds(size_t(batch), start);
+    DevArr<int> df(size_t(batch), finished);
+    wt::launch_ragged_cap(ds.p, pos, P, df.p, batch, h->impl->stream());
+    h->impl->sync();
+    df.to_host(finished, size_t(batch));
   });
 }
 

@@ -842,6 +842,9 @@ void Engine::release() noexcept {
                   static_cast<void*>(fw_.h_count), static_cast<void*>(fw_.h_prm)})
     if (p) (void)hipHostFree(p);
   fw_ = FullWorkspace();
+  for (void* p : {static_cast<void*>(rw_.h_ids), static_cast<void*>(rw_.h_lp), static_cast<void*>(rw_.h_start)})
+    if (p) (void)hipHostFree(p);
+  rw_ = RaggedWorkspace();
   for (void* p : {static_cast<void*>(aw_.h_jump), static_cast<void*>(aw_.h_lfn)})
     if (p) (void)hipHostFree(p);
   aw_ = AlignWorkspace();  // (its device buffers are in allocations_)
@@ -1488,6 +1491,7 @@ void Engine::decode(int batch, int64_t* ids, int32_t* n_ids, float* logits_host,
   last_lang_valid = false;
   last_segments_valid = false;
   last_windows_valid = false;
+  last_window_files.clear(), last_file_text.clear();
   clear_last_scores();
   if (beam_size > 1) {
     decode_beam(batch, last_enc_slot_, ids, n_ids);
@@ -1704,6 +1708,50 @@ void Engine::set_context(const int64_t* ids, int n) {
   }
   const int keep = std::min(n, context_keep());  // the LAST n_text_ctx / 2 - 1 ids, as Whisper's decoder keeps them
   context_ids.assign(ids + (n - keep), ids + n);
+  clip_contexts.clear();  // one kind of context at a time
+}
+
+void Engine::set_contexts(const int64_t* ids, const int32_t* offsets, int n_clips) {
+  if (n_clips < 0 || n_clips > 64 || (n_clips > 0 && !offsets)) throw Error(kErrInvalidArg, "contexts: 0 .. 64 clips");
+  if (n_clips == 0) {
+    clip_contexts.clear();
+    return;
+  }
+  if (offsets[0] < 0) throw Error(kErrInvalidArg, "contexts: offsets must start at 0 or above and never decrease");
+  for (int b = 0; b < n_clips; ++b) {
+    if (offsets[b + 1] < offsets[b] || offsets[b + 1] - offsets[b] > kContextIdsMax) {
+      throw Error(kErrInvalidArg, "contexts: offsets must never decrease, at most 4096 ids per clip");
+    }
+  }
+  if (offsets[n_clips] > offsets[0] && !ids) throw Error(kErrInvalidArg, "contexts: NULL ids");
+  if (offsets[n_clips] > offsets[0]) {  // some clip has a context (empty ones all round need no <|startofprev|>)
+    if (monolith_) throw Error(kErrUnsupported, "contexts: not on a Monolith engine (the reference's single graph takes no prompt)");
+    if (!has_prev_token()) {
+      throw Error(kErrUnsupported, "contexts: the model's vocabulary has no <|startofprev|> id (token_prev >= n_vocab)");
+    }
+  }
+  for (int32_t i = offsets[0]; i < offsets[n_clips]; ++i) {
+    if (ids[i] < 0 || ids[i] >= dims_.n_vocab) throw Error(kErrInvalidArg, "context token id outside the model's vocabulary");
+  }
+  std::vector<std::vector<long long>> v(static_cast<size_t>(n_clips));
+  for (int b = 0; b < n_clips; ++b) {
+    const int n = offsets[b + 1] - offsets[b], keep = std::min(n, context_keep());
+    v[size_t(b)].assign(ids + offsets[b] + (n - keep), ids + offsets[b + 1]);
+  }
+  clip_contexts = v;
+  context_ids.clear();
+}
+
+std::vector<long long> Engine::fed_prompt_of(int clip) const {
+  std::vector<long long> out;
+  const std::vector<long long>& c = clip_contexts[size_t(clip)];
+  if (!c.empty()) {
+    out.push_back(vocab_.token_prev);
+    out.insert(out.end(), c.begin(), c.end());
+  }
+  const std::vector<long long> tail = prompt();
+  out.insert(out.end(), tail.begin(), tail.end());
+  return out;
 }
 
 // ------------------------------------------------------ the decoder pass ---
@@ -1800,13 +1848,20 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
     if (l == 0) {
       q.ids = p.ids; q.ids_stride = p.ids_stride; q.pos = p.pos0; q.tok_emb = tok_emb; q.pos_emb = dec_pos;
       q.n_vocab = V; q.xout = x;
+      q.pos_start = p.pos_start; q.n_ctx = c.n_text_ctx;
     }
     q.bias = w.bqkv; q.Y = dw.qkvd; q.ldy = 3 * d;
     timed(tm, 0, [&] { launch_dec_gemm(q, kProLn, kDecBias, st); });
     void* const kc = cache_at(p.self_kv, (size_t(l) * 2 + 0) * self_slab);
     void* const vc = cache_at(p.self_kv, (size_t(l) * 2 + 1) * self_slab);
     timed(tm, 1, [&] {
-      if (p.self_prefill) {  // np positions of a prompt behind a context, fp32 cache
+      if (p.pos_start && p.self_prefill) {  // the ragged chain: prompt slots, then one generated slot per pass
+        launch_self_attention_prefill_ragged(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0, p.np,
+                                             p.pos_start, p.pos_limit, dw.attd, B, H, st);
+      } else if (p.pos_start) {
+        launch_self_attention_long_ragged(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0,
+                                          p.pos_start, p.pos_limit, dw.attd, B, H, st);
+      } else if (p.self_prefill) {  // np positions of a prompt behind a context, fp32 cache
         launch_self_attention_prefill(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0, p.np, dw.attd, B, H, st);
       } else if (p.self_long) {  // one position past 32, fp32 cache (full-length decoding)
         launch_self_attention_long(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0, dw.attd, B, H, st);
@@ -2384,6 +2439,12 @@ void Engine::check_timestamp_call() const {
   if (!context_ids.empty() && max_positions <= 0) {
     throw Error(kErrUnsupported, "context: full-length decoding only, set the option max_positions (32 .. n_text_ctx) or clear the context");
   }
+  if (!clip_contexts.empty() && max_positions <= 0) {
+    throw Error(kErrUnsupported, "contexts: full-length decoding only, set the option max_positions (32 .. n_text_ctx) or clear the contexts");
+  }
+  if (!clip_contexts.empty() && word_timestamps) {
+    throw Error(kErrUnsupported, "contexts: not with word_timestamps (the alignment pass takes one prompt length per call)");
+  }
   check_word_call();
   if (temperature_fallback && !scores) throw Error(kErrUnsupported, "temperature_fallback: needs the option scores = 1");
   if (temperature_fallback && compression_ratio_threshold != 0 && !zlib_available()) {
@@ -2467,6 +2528,9 @@ void Engine::check_full_args(int batch, int ids_stride) const {
   check_full_call();
   if (batch < 1 || batch > 64) throw Error(kErrInvalidArg, "decoder batches are limited to 64 clips per call");
   if (ids_stride < max_positions + 1) throw Error(kErrBuffer, "ids_stride is smaller than max_positions + 1");
+  if (!clip_contexts.empty() && size_t(batch) != clip_contexts.size()) {
+    throw Error(kErrInvalidArg, "contexts: the call's batch differs from the number of clips wt_engine_set_contexts was given");
+  }
 }
 
 void Engine::check_full_call() const {
@@ -2480,6 +2544,11 @@ void Engine::check_full_call() const {
   if (scores && !has_no_speech_token()) no("scores: the model's vocabulary has no <|nospeech|> id");
   if (!context_ids.empty() && long(fed_prompt().size()) >= max_positions) {
     throw Error(kErrInvalidArg, "context: the prompt behind it leaves no position to generate (prompt ids >= max_positions)");
+  }
+  for (size_t b = 0; b < clip_contexts.size(); ++b) {
+    if (long(fed_prompt_of(int(b)).size()) >= max_positions) {
+      throw Error(kErrInvalidArg, "contexts: a clip's prompt leaves no position to generate (prompt ids >= max_positions)");
+    }
   }
 }
 
@@ -2580,6 +2649,30 @@ void Engine::ensure_full_workspace(int batch) {
   fw_.h_fin = static_cast<int*>(p);
 }
 
+void Engine::ensure_ragged_workspace() {
+  const size_t C = 64, S = size_t(ragged_stride());
+  auto alloc = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    allocations_.push_back(p);
+    HIPCHK(hipMemset(p, 0, bytes));
+    return p;
+  };
+  auto pinned = [&](size_t bytes) -> void* {
+    void* q = nullptr;
+    HIPCHK(hipHostMalloc(&q, bytes, 0));
+    return q;
+  };
+  if (!rw_.ids) rw_.ids = static_cast<long long*>(alloc(C * S * sizeof(long long)));
+  if (!rw_.h_ids) rw_.h_ids = static_cast<long long*>(pinned(C * S * sizeof(long long)));
+  if (!rw_.start) rw_.start = static_cast<int*>(alloc(C * sizeof(int)));
+  if (!rw_.h_start) rw_.h_start = static_cast<int*>(pinned(C * sizeof(int)));
+  if (scores) {
+    if (!rw_.lp) rw_.lp = static_cast<float*>(alloc(C * S * sizeof(float)));
+    if (!rw_.h_lp) rw_.h_lp = static_cast<float*>(pinned(C * S * sizeof(float)));
+  }
+}
+
 // Full-length greedy decoding: decode_enqueue's passes — the prompt grouped by np_max, then one
 // pass per position — continued to P = max_positions, over a self-attention cache of full_cap() rows and id rows of
 // stride full_cap() + 1.  Positions 0 .. 31 run self_attention_step on that cache, later ones self_attention_long; the
@@ -2594,19 +2687,43 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   beam_scores_valid = false;
   last_segments_valid = false;
   last_windows_valid = false;
+  last_window_files.clear(), last_file_text.clear();
   last_words_valid = false;
   last_alignment.clear();
   clear_last_scores();  // (the decode info with them)
   const bool ts = timestamps != 0, sc = scores != 0, smp = sampling();
   ensure_batch(batch);
   ensure_full_workspace(batch);  // (before any capture: nothing may be allocated inside one)
+  // per-clip contexts (set_contexts): the chain runs in slots, the fed prompts right-aligned so that
+  // every clip's prompt ends at slot n_prompt - 1; `stride`, `n_prompt`, `sot_idx` and the chain's length are in slots,
+  // and the rows come back to the caller's layout when the chain has ended (run_chain)
+  const bool rag = !clip_contexts.empty();
+  if (rag) ensure_ragged_workspace();
   Slot& slot = slots_[slot_idx];
-  const int V = dims_.n_vocab, cap = full_cap(), stride = cap + 1;
+  const int V = dims_.n_vocab, cap = full_cap(), out_stride = cap + 1, stride = rag ? ragged_stride() : out_stride;
   // with a context (set_context): [prev] + context + prompt(), every count below starts behind all of it
-  const bool ctx = !context_ids.empty();
+  const bool ctx = !context_ids.empty() || rag;
   const std::vector<long long> prompt = fed_prompt();
-  const int n_prompt = int(prompt.size());
-  const int sot_idx = ctx ? 1 + int(context_ids.size()) : 0;  // Whisper's sot_index: the no-speech logits are read there
+  std::vector<std::vector<long long>> prompts;  // ragged: the clips' fed prompts
+  int n_prompt = int(prompt.size()), n_min = n_prompt;
+  if (rag) {
+    n_prompt = 0, n_min = 1 << 30;
+    for (int b = 0; b < batch; ++b) {
+      prompts.push_back(fed_prompt_of(b));
+      check_prompt_ids(prompts.back(), kErrInvalidArg);
+      n_prompt = std::max(n_prompt, int(prompts.back().size()));
+      n_min = std::min(n_min, int(prompts.back().size()));
+    }
+    for (int b = 0; b < batch; ++b) rw_.h_start[b] = n_prompt - int(prompts[size_t(b)].size());
+  }
+  auto np_of = [&](int b) { return rag ? int(prompts[size_t(b)].size()) : n_prompt; };  // clip b's fed prompt, in Whisper terms
+  // Whisper's sot_index: the no-speech logits are read there
+  const int sot_idx = rag ? n_prompt - int(this->prompt().size()) : !context_ids.empty() ? 1 + int(context_ids.size()) : 0;
+  const int PS = rag ? n_prompt - n_min + P : P;  // the chain's length: the clip behind the shortest prompt reaches its cap last
+  long long* const d_ids = rag ? rw_.ids : fw_.ids;
+  long long* const h_ids = rag ? rw_.h_ids : fw_.h_ids;
+  float* const d_lp = rag ? rw_.lp : fw_.sc_lp;
+  float* const h_lp = rag ? rw_.h_lp : fw_.h_lp;
   check_prompt_ids(prompt, kErrInvalidArg);
   slot.dec = slot_idx % n_dec_streams_;
   slot.pair_leader = -1;
@@ -2618,12 +2735,13 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   // prompt positions per pass: four without a context (self_attention_step's launch), as many rows as a pass takes
   // with one (self_attention_prefill); option prompt_group = 1: one position per pass, the A/B handle
   const int np_max = ctx ? (prompt_group == 1 ? 1 : std::max(1, kDecRowsMax / batch)) : std::max(1, std::min(4, kDecRowsMax / batch));
-  const int prompt_end = std::min(n_prompt, P);
+  const int prompt_end = std::min(n_prompt, PS);
   // a context's length is part of every launch: such calls run eagerly
   auto graphs = [&] { return use_graphs && !ctx; };
 
   DecPass p;
-  p.B = p.clips = batch; p.ids = fw_.ids; p.ids_stride = stride; p.self_kv = fw_.kv; p.self_cap = cap;
+  p.B = p.clips = batch; p.ids = d_ids; p.ids_stride = stride; p.self_kv = fw_.kv; p.self_cap = cap;
+  if (rag) p.pos_start = rw_.start, p.pos_limit = P;
   p.absorbed = absorbed; p.n_abs = n_abs; p.chunks = chunks; p.e = slot.e_planes; p.cross_kv = slot.cross_kv;
   p.split = fc2_split(); p.dw = &dw; p.ldy = V;
   if (ts || sc || smp) p.Y = fw_.ts_logits, p.ldy = fw_.ts_ldl;  // the timestamp rules, the scores and the sampler read the whole row
@@ -2631,7 +2749,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   if (sc) {
     sa.logits = fw_.ts_logits; sa.ldl = fw_.ts_ldl; sa.V = V; sa.batch = batch; sa.part = fw_.sc_part;
     sa.eot = vocab_.token_eot; sa.beg = vocab_.token_beg; sa.max_initial = int(max_initial_timestamp);
-    sa.ids = fw_.ids; sa.ids_stride = stride; sa.n_ids = dw.n_ids; sa.token_logprob = fw_.sc_lp; sa.lp_stride = stride;
+    sa.ids = d_ids; sa.ids_stride = stride; sa.n_ids = dw.n_ids; sa.token_logprob = d_lp; sa.lp_stride = stride;
     sa.sum = fw_.sc_sum; sa.count = fw_.sc_count;
   }
   // the passes whose first position lies in [lo, hi); returns the argmax steps among them
@@ -2646,7 +2764,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       const bool nosp = sc && last == sot_idx;
       p.pos0 = pos0; p.np = np; p.best = logits || nosp ? dw.best : nullptr;
       p.self_prefill = ctx && pos0 < prompt_end;  // the prompt behind a context, whatever np is
-      p.self_long = !p.self_prefill && pos0 + np > 32;  // (np == 1 there: a prompt without a context has at most 8 ids)
+      // (np == 1 there: a prompt without a context has at most 8 ids; the ragged chain has no step form)
+      p.self_long = !p.self_prefill && (rag || pos0 + np > 32);
       decoder_pass(p, st);
       if (nosp) {
         sa.state = nullptr;
@@ -2662,7 +2781,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
           t.logits = fw_.ts_logits; t.ldl = fw_.ts_ldl; t.V = V; t.batch = batch;
           t.eot = vocab_.token_eot; t.beg = vocab_.token_beg; t.max_initial = int(max_initial_timestamp);
           t.n_gen = last + 1 - n_prompt; t.params = fw_.sm_prm; t.part = fw_.sm_part; t.state = ts ? fw_.ts_state : nullptr;
-          t.ids = fw_.ids; t.ids_stride = stride; t.pos = last; t.stop_at_eot = int(stop_at_eot);
+          t.ids = d_ids; t.ids_stride = stride; t.pos = last; t.stop_at_eot = int(stop_at_eot);
           t.n_ids = dw.n_ids; t.finished = dw.finished;
           launch_sample_select(t, st);
         } else if (ts) {
@@ -2670,14 +2789,15 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
           t.logits = fw_.ts_logits; t.ldl = fw_.ts_ldl; t.V = V; t.batch = batch;
           t.eot = vocab_.token_eot; t.beg = vocab_.token_beg; t.max_initial = int(max_initial_timestamp);
           t.n_gen = last + 1 - n_prompt; t.part = fw_.ts_part; t.state = fw_.ts_state;
-          t.ids = fw_.ids; t.ids_stride = stride; t.pos = last; t.stop_at_eot = int(stop_at_eot);
+          t.ids = d_ids; t.ids_stride = stride; t.pos = last; t.stop_at_eot = int(stop_at_eot);
           t.n_ids = dw.n_ids; t.finished = dw.finished;
           launch_ts_select(t, st);
         } else {
-          launch_select_token(dw.best, (V + 31) / 32, fw_.ids, stride, last, dw.n_ids, dw.finished, vocab_.token_eot,
+          launch_select_token(dw.best, (V + 31) / 32, d_ids, stride, last, dw.n_ids, dw.finished, vocab_.token_eot,
                               int(stop_at_eot), batch, st);
         }
         if (sc) launch_score_finish(sa, st);
+        if (rag) launch_ragged_cap(rw_.start, last, P, dw.finished, batch, st);  // a clip that has fed its position P - 1 stops counting
         ++seg_steps;
       }
     }
@@ -2690,12 +2810,20 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   int steps = 0;
   auto run_chain = [&](const std::vector<int>* frozen, bool first) {
     for (int b = 0; b < batch; ++b) {
-      for (int i = 0; i < stride; ++i) fw_.h_ids[size_t(b) * stride + i] = i < n_prompt ? prompt[i] : 0;
+      for (int i = 0; i < stride; ++i) {
+        if (rag) {  // right-aligned: slots in front of the clip's prompt hold id 0 and are void
+          const int k = i - rw_.h_start[b];
+          h_ids[size_t(b) * stride + i] = k >= 0 && i < n_prompt ? prompts[size_t(b)][size_t(k)] : 0;
+        } else {
+          h_ids[size_t(b) * stride + i] = i < n_prompt ? prompt[i] : 0;
+        }
+      }
       fw_.h_n[b] = n_prompt;
     }
     HIPCHK(hipStreamWaitEvent(st, slot.enc_done, 0));
     if (first) HIPCHK(hipEventRecord(slot.dec_begin, st));
-    HIPCHK(hipMemcpyAsync(fw_.ids, fw_.h_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_ids, h_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
+    if (rag) HIPCHK(hipMemcpyAsync(rw_.start, rw_.h_start, size_t(batch) * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(dw.n_ids, fw_.h_n, size_t(batch) * sizeof(int), hipMemcpyHostToDevice, st));
     if (frozen) {
       for (int b = 0; b < batch; ++b) fw_.h_fin[b] = (*frozen)[size_t(b)];
@@ -2705,14 +2833,14 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     }
     if (smp) HIPCHK(hipMemcpyAsync(fw_.sm_prm, fw_.h_prm, sizeof(SampleParams), hipMemcpyHostToDevice, st));
     if (ts) {  // the carried state of the timestamp rules: nothing generated yet
-      launch_ts_state_init(fw_.ids, stride, nullptr, n_prompt, n_prompt, V, vocab_.token_beg, fw_.ts_state, batch, st);
+      launch_ts_state_init(d_ids, stride, nullptr, n_prompt, n_prompt, V, vocab_.token_beg, fw_.ts_state, batch, st);
     }
     if (sc) {  // the carried sums and counts of the scores: nothing generated yet
       HIPCHK(hipMemsetAsync(fw_.sc_sum, 0, size_t(batch) * sizeof(double), st));
       HIPCHK(hipMemsetAsync(fw_.sc_count, 0, size_t(batch) * sizeof(int), st));
     }
-    for (int lo = 0; lo < P; lo += 32) {
-      const int hi = std::min(P, lo + 32);
+    for (int lo = 0; lo < PS; lo += 32) {
+      const int hi = std::min(PS, lo + 32);
       // (greedy's keys start with the slot, a beam key with -beam_size; a full-length key starts with kFullKey)
       // (the sampling kernels are one entry; temperature, seed and attempt are data, never part of the key)
       const std::vector<long long> key{kFullKey, slot_idx, batch, lo, P, n_prompt, chunks, long(stop_at_eot), fc2_ksplit,
@@ -2735,8 +2863,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
           }
         }
       }
-      if (hi == P) break;
-      if (stop_at_eot) {  // every clip finished: the remaining segments would change nothing
+      if (hi == PS) break;
+      if (stop_at_eot || rag) {  // every clip finished (ragged: or capped): the remaining segments would change nothing
         HIPCHK(hipMemcpyAsync(fw_.h_fin, dw.finished, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         bool all = true;
@@ -2744,10 +2872,10 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
         if (all) break;
       }
     }
-    HIPCHK(hipMemcpyAsync(fw_.h_ids, fw_.ids, size_t(batch) * stride * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_ids, d_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(fw_.h_n, dw.n_ids, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
     if (sc) {  // the scores come down with the ids: no further synchronisation point
-      HIPCHK(hipMemcpyAsync(fw_.h_lp, fw_.sc_lp, size_t(batch) * stride * sizeof(float), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(h_lp, d_lp, size_t(batch) * stride * sizeof(float), hipMemcpyDeviceToHost, st));
       HIPCHK(hipMemcpyAsync(fw_.h_sum, fw_.sc_sum, size_t(batch) * sizeof(double), hipMemcpyDeviceToHost, st));
       HIPCHK(hipMemcpyAsync(fw_.h_count, fw_.sc_count, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
       HIPCHK(hipMemcpyAsync(fw_.h_nosp, fw_.sc_nosp, size_t(batch) * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -2755,6 +2883,20 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     HIPCHK(hipEventRecord(slot.dec_done, st));
     slot.steps = steps;  // (summed over the attempts)
     finish_slot(slot_idx);  // waits; the encoder's non-finite flag, timings
+    if (rag) {  // back to the caller's layout: row b starts at its own prompt, counts in Whisper terms
+      for (int b = 0; b < batch; ++b) {
+        const int s0 = rw_.h_start[b];
+        long long* const r = h_ids + size_t(b) * stride;
+        std::copy(r + s0, r + stride, r);
+        std::fill(r + (stride - s0), r + stride, 0ll);
+        if (sc) {
+          float* const q = h_lp + size_t(b) * stride;
+          std::copy(q + s0, q + stride, q);
+          std::fill(q + (stride - s0), q + stride, 0.0f);
+        }
+        fw_.h_n[b] -= s0;
+      }
+    }
   };
 
   if (!smp) {
@@ -2778,12 +2920,17 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       prm.seed_lo = unsigned(sd & 0xffffffffull), prm.seed_hi = unsigned(sd >> 32);
       prm.attempt = unsigned(attempt), prm.clip_base = unsigned(clip_base);
       const float T = float(temps[attempt]) / 1000.0f;
-      for (int b = 0; b < kSampleClipsMax; ++b) prm.inv_t[b] = temps[attempt] > 0 ? 1.0f / T : 0.0f;
+      for (int b = 0; b < kSampleClipsMax; ++b) {
+        prm.inv_t[b] = temps[attempt] > 0 ? 1.0f / T : 0.0f;
+        // ragged: the counter takes the clip's own Whisper position, and the clip index the caller gave it
+        prm.pos_off[b] = rag && b < batch ? rw_.h_start[b] : 0;
+        prm.clip_off[b] = rag && size_t(b) < clip_index_off.size() ? clip_index_off[size_t(b)] : 0;
+      }
       run_chain(attempt == 0 ? nullptr : &frozen, attempt == 0);
       bool again = false;
       for (int b = 0; b < batch; ++b) {
         if (frozen[size_t(b)]) continue;
-        std::copy(fw_.h_ids + size_t(b) * stride, fw_.h_ids + size_t(b + 1) * stride, m_ids.begin() + size_t(b) * stride);
+        std::copy(h_ids + size_t(b) * stride, h_ids + size_t(b + 1) * stride, m_ids.begin() + size_t(b) * stride);
         m_n[size_t(b)] = fw_.h_n[b];
         ClipDecode& info = last_decode_info[size_t(b)];
         info.temperature_milli = int32_t(temps[attempt]);
@@ -2791,15 +2938,15 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
         info.needs_fallback = 0;
         const int n_row = std::min(fw_.h_n[b], stride);
         std::vector<int64_t> gen;  // the generated ids below eot: the clip's text
-        for (int i = n_prompt; i < n_row; ++i) {
-          if (fw_.h_ids[size_t(b) * stride + i] < vocab_.token_eot) gen.push_back(fw_.h_ids[size_t(b) * stride + i]);
+        for (int i = np_of(b); i < n_row; ++i) {
+          if (h_ids[size_t(b) * stride + i] < vocab_.token_eot) gen.push_back(h_ids[size_t(b) * stride + i]);
         }
         const double ratio = zlib_available() ? compression_ratio(decode_tokens(vocab_, gen.data(), int(gen.size()), true, nullptr)) : 0.0;
         info.compression_ratio = float(ratio);
         if (sc) {
           // every live clip generates at least one id (max_positions > the prompt): a count of 0 is a device-side error
           if (fw_.h_count[b] < 1) throw Error(kErrDevice, "scores: a clip came back with no generated id counted");
-          std::copy(fw_.h_lp + size_t(b) * stride, fw_.h_lp + size_t(b + 1) * stride, m_lp.begin() + size_t(b) * stride);
+          std::copy(h_lp + size_t(b) * stride, h_lp + size_t(b + 1) * stride, m_lp.begin() + size_t(b) * stride);
           m_sum[size_t(b)] = fw_.h_sum[b], m_count[size_t(b)] = fw_.h_count[b], m_nosp[size_t(b)] = fw_.h_nosp[b];
         }
         if (temperature_fallback) {  // (needs scores: check_timestamp_call)
@@ -2815,10 +2962,10 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       }
       if (!again) break;
     }
-    std::copy(m_ids.begin(), m_ids.end(), fw_.h_ids);
+    std::copy(m_ids.begin(), m_ids.end(), h_ids);
     std::copy(m_n.begin(), m_n.end(), fw_.h_n);
     if (sc) {
-      std::copy(m_lp.begin(), m_lp.end(), fw_.h_lp);
+      std::copy(m_lp.begin(), m_lp.end(), h_lp);
       std::copy(m_sum.begin(), m_sum.end(), fw_.h_sum);
       std::copy(m_count.begin(), m_count.end(), fw_.h_count);
       std::copy(m_nosp.begin(), m_nosp.end(), fw_.h_nosp);
@@ -2827,8 +2974,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   }
   if (sc) {
     last_scores.assign(size_t(batch), ClipScore{});
-    last_lp_stride = stride;
-    last_token_logprob.assign(size_t(batch) * stride, 0.0f);
+    last_lp_stride = out_stride;
+    last_token_logprob.assign(size_t(batch) * out_stride, 0.0f);
     for (int b = 0; b < batch; ++b) {
       ClipScore& s = last_scores[size_t(b)];
       // every clip generates at least one id (max_positions > the prompt): a count of 0 is a device-side error
@@ -2840,8 +2987,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       // Whisper's rule: silence unless the text itself is confident
       s.skipped = skip_silence && double(s.no_speech_prob) > double(no_speech_threshold) / 1000.0 &&
                   !(double(s.avg_logprob) > double(logprob_threshold) / 1000.0);
-      for (int i = n_prompt; i < std::min(fw_.h_n[b], stride); ++i) {
-        last_token_logprob[size_t(b) * stride + i] = fw_.h_lp[size_t(b) * stride + i];
+      for (int i = np_of(b); i < std::min(fw_.h_n[b], out_stride); ++i) {
+        last_token_logprob[size_t(b) * out_stride + i] = h_lp[size_t(b) * stride + i];
       }
     }
     last_segment_score.clear();
@@ -2850,7 +2997,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   for (int b = 0; b < batch; ++b) {
     n_ids[b] = fw_.h_n[b];
     for (int i = 0; i < ids_stride; ++i) {
-      ids[size_t(b) * ids_stride + i] = i < fw_.h_n[b] && i < stride ? fw_.h_ids[size_t(b) * stride + i] : 0;
+      ids[size_t(b) * ids_stride + i] = i < fw_.h_n[b] && i < stride ? h_ids[size_t(b) * stride + i] : 0;
     }
   }
   if (ts) {
@@ -2858,15 +3005,15 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     last_segment_text.clear();
     for (int b = 0; b < batch; ++b) {
       if (sc && last_scores[size_t(b)].skipped) continue;  // a silent clip has no segments
-      const int64_t* const row = reinterpret_cast<const int64_t*>(fw_.h_ids + size_t(b) * stride);
+      const int64_t* const row = reinterpret_cast<const int64_t*>(h_ids + size_t(b) * stride);
       const size_t first = last_segments.size();
-      parse_segments(vocab_, row, std::min(fw_.h_n[b], stride), n_prompt, b, &last_segments);
+      parse_segments(vocab_, row, std::min(fw_.h_n[b], stride), np_of(b), b, &last_segments);
       for (size_t i = first; i < last_segments.size(); ++i) {
         bool missing = false;
         last_segment_text.push_back(decode_tokens(vocab_, row + last_segments[i].id_begin, last_segments[i].id_count, false, &missing));
         if (sc) {  // the mean log-probability of the segment's text ids
           double sum = 0.0;
-          for (int k = 0; k < last_segments[i].id_count; ++k) sum += double(fw_.h_lp[size_t(b) * stride + last_segments[i].id_begin + k]);
+          for (int k = 0; k < last_segments[i].id_count; ++k) sum += double(h_lp[size_t(b) * stride + last_segments[i].id_begin + k]);
           last_segment_score.push_back(float(sum / double(std::max(last_segments[i].id_count, 1))));
         }
       }

@@ -293,6 +293,18 @@ class Engine {
   void set_context(const int64_t* ids, int n);
   std::vector<long long> fed_prompt() const;
   long prompt_group = 0;
+  // Per-clip contexts: clip b of every following full-length call is decoded behind
+  // clip_contexts[b] (each cut to its last context_keep() ids; an empty one: that clip's fed prompt is prompt() alone).
+  // The call's batch must equal their number.  Such a call is one RAGGED chain: the clips' fed prompts are right-aligned
+  // in slots, clip b at Whisper position slot - start_b, so every clip starts generating at the same slot and only the
+  // embedding, the self-attention and the sampler's counter see the per-clip position.  Runs eagerly, as a context does.
+  // n_clips = 0 clears; setting either kind of context clears the other.  Refusals: set_context's, more than 64 clips
+  // (kErrInvalidArg), word_timestamps (kErrUnsupported).
+  std::vector<std::vector<long long>> clip_contexts;
+  // the sampler's clip word of clip b is clip_base + b + clip_index_off[b] (empty: zeros); the batched seeking loop sets it
+  std::vector<int> clip_index_off;
+  void set_contexts(const int64_t* ids, const int32_t* offsets, int n_clips);
+  std::vector<long long> fed_prompt_of(int clip) const;  // [prev] + clip_contexts[clip] + prompt(), or prompt() alone
   int graphs_cached() const { return int(graphs_.size()); }
   // Seeking long-audio transcription (wt_transcribe_long_pcm with seek = 1, longform.cpp): needs timestamps and
   // max_positions; condition_on_previous_text is read only then
@@ -341,6 +353,10 @@ class Engine {
   // one record per window of the last synchronous decode when that was a seeking one
   std::vector<Window> last_windows;
   bool last_windows_valid = false;
+  // wt_transcribe_long_batch: the file of every entry of last_windows, and every file's text (its windows' lines joined
+  // by '\n'); both empty after any other call
+  std::vector<int32_t> last_window_files;
+  std::vector<std::string> last_file_text;
 
   int mel_frames() const { return 2 * dims_.n_audio_ctx; }
   size_t mel_elems() const { return size_t(dims_.n_mels) * mel_frames(); }
@@ -477,6 +493,14 @@ class Engine {
     SampleParams *sm_prm = nullptr, *h_prm = nullptr;
   } fw_;
   void ensure_full_workspace(int batch);
+  struct RaggedWorkspace {  // allocated by the first ragged call: the slot-space rows [64][ragged_stride()] and the starts [64]
+    long long *ids = nullptr, *h_ids = nullptr;
+    float *lp = nullptr, *h_lp = nullptr;  // option scores
+    int *start = nullptr, *h_start = nullptr;
+  } rw_;
+  // a ragged chain runs at most N - min n_b + P < 2 full_cap() slots, and a selection writes the id of the slot behind it
+  int ragged_stride() const { return 2 * full_cap() + 2; }
+  void ensure_ragged_workspace();
   struct AlignWorkspace {  // allocated by the first call with word_timestamps, outside any capture
     float *W = nullptr, *stats = nullptr, *C = nullptr;
     size_t w_elems = 0, c_elems = 0, s_elems = 0;
@@ -615,6 +639,10 @@ class Engine {
     int ids_stride = 32, self_cap = 32;
     bool self_long = false;  // self_attention_long (np = 1, any position below self_cap) instead of self_attention
     bool self_prefill = false;  // self_attention_prefill (np >= 1: a prompt behind a context) instead of either
+    // ragged chain: pos0 counts slots, sequence b is at Whisper position slot - pos_start[b] (device [B]) and may feed
+    // positions [0, pos_limit); the embedding and the ragged self-attention kernels take both (self_prefill or the long form)
+    const int* pos_start = nullptr;
+    int pos_limit = 0;
     int clips = 0;           // clips the cross-attention sees: B, or fewer with M / clips query rows each (beam search)
     bool absorbed = false;   // cross-attention form: absorbed (e .. e4, e_split, n_abs) or cached (cross_kv, chunks)
     const unsigned short *e = nullptr, *e2 = nullptr, *e3 = nullptr, *e4 = nullptr;  // as in CrossAbsorbedArgs

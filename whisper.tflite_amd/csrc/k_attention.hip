@@ -557,10 +557,24 @@ __global__ void self_attention_step(const float* __restrict__ qkv, void* __restr
 // the grid.  The first wavefront appends the new k and v to cache row `pos`; the group that owns key `pos` takes them
 // from LDS (the row is not read back), and a key index >= pos is redirected to row max(pos - 1, 0) before the load, so
 // nothing reads cache rows > pos (row pos itself only at pos = 0, where the redirect lands on it and the value is dropped).  Scores in log2 units, p = exp2(s - m).  qkv / out rows: row = b (one position).
+// RAGGED: `pos` counts slots and clip b is at Whisper position pos - start[b]; everything below
+// runs at that position, so a clip's sums are the unragged kernel's there.  A clip whose position lies outside
+// [0, min(P, cap)) is void: its blocks write zeros to `out` and touch no cache row.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void self_attention_long(const float* __restrict__ qkv, float* __restrict__ kcache,
                                                            float* __restrict__ vcache, int cap, int pos,
-                                                           float* __restrict__ out, int heads) {
+                                                           float* __restrict__ out, int heads,
+                                                           const int* __restrict__ start, int P) {
   constexpr int NG = 16, U = 4;  // key rows per load round, rounds in flight
+  if (RAGGED) {
+    const int bb = blockIdx.x / heads;
+    const int st = min(max(start[bb], -(1 << 20)), 1 << 20);  // (no overflow whatever the array holds)
+    pos -= st;
+    if (pos < 0 || pos >= min(P, cap)) {  // uniform over the block
+      if (threadIdx.x < 64) out[(long)bb * heads * 64 + (blockIdx.x % heads) * 64 + threadIdx.x] = 0.0f;
+      return;
+    }
+  }
   __shared__ __attribute__((aligned(16))) float qs[64];
   __shared__ __attribute__((aligned(16))) float kn[64];
   __shared__ __attribute__((aligned(16))) float vn[64];
@@ -660,9 +674,15 @@ __global__ __launch_bounds__(256) void self_attention_long(const float* __restri
 // a block appends exactly the k and v rows of its own queries, so each new row is written once and blocks cannot
 // race on it.  Scores in log2 units, p = exp2(s - m).  qkv / out rows: row(p) = p * B + b.
 constexpr int kPrefillQ = 16, kPrefillTile = 32;
+// RAGGED: `pos0` counts slots and clip b's query p is at Whisper position pos0 - start[b] + p.  A
+// query outside [0, min(P, cap)) is void: zeros in `out`, nothing appended; the others run as above at their own
+// positions, with keys from qkv for positions >= max(pos0 - start[b], 0) — qkv row = position - (pos0 - start[b]) —
+// and from the cache below that.  A block without a live query reads nothing.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void self_attention_prefill(const float* __restrict__ qkv, float* __restrict__ kcache,
                                                               float* __restrict__ vcache, int cap, int pos0, int np,
-                                                              int B, float* __restrict__ out, int heads) {
+                                                              int B, float* __restrict__ out, int heads,
+                                                              const int* __restrict__ start, int P) {
   constexpr int TK = kPrefillTile;
   __shared__ __attribute__((aligned(16))) float Ks[TK][64];
   __shared__ __attribute__((aligned(16))) float Vs[TK][64];
@@ -675,7 +695,18 @@ __global__ __launch_bounds__(256) void self_attention_prefill(const float* __res
   float* vc = vcache + ((long)b * cap) * d + h * 64;
   const int p_first = qb * kPrefillQ;
   const int p_last = min(np, p_first + kPrefillQ) - 1;  // the block's last query
-  const int kend = pos0 + p_last + 1;                   // keys 0 .. kend - 1 are all this block may see
+  int lim = 0;                                          // RAGGED: positions [0, lim) are live
+  if (RAGGED) {
+    pos0 -= min(max(start[b], -(1 << 20)), 1 << 20);  // the clip's position at p = 0; negative in front of its prompt
+    lim = min(P, cap);
+    if (pos0 + p_last < 0 || pos0 + p_first >= lim) {  // no live query (uniform over the block)
+      const int pv = p_first + (threadIdx.x >> 4);
+      if (pv <= p_last) *reinterpret_cast<f32x4*>(out + ((long)pv * B + b) * heads * 64 + h * 64 + (threadIdx.x & 15) * 4) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      return;
+    }
+  }
+  // keys 0 .. kend - 1 are all this block may see (RAGGED: some query is live, so 0 < kend <= lim)
+  const int kend = RAGGED ? min(pos0 + p_last + 1, lim) : pos0 + p_last + 1;
   // staging: thread t carries 16 bytes of rows t / 16 and t / 16 + 16 of a tile
   f32x4 kr[2], vr[2];
   auto fetch = [&](int k0) {
@@ -696,7 +727,7 @@ __global__ __launch_bounds__(256) void self_attention_prefill(const float* __res
   fetch(0);
   constexpr float kScale = 0.125f * 1.44269504088896340736f;
   const int p = p_first + grp;
-  const bool live = p <= p_last;
+  const bool live = p <= p_last && (!RAGGED || (pos0 + p >= 0 && pos0 + p < lim));
   const int n = live ? pos0 + p + 1 : 0;  // causal: keys 0 .. pos0 + p
   f32x4 q4 = {0.0f, 0.0f, 0.0f, 0.0f};
   if (live) {  // the query, and the append of this position's k and v (each row by the one group that owns it)
@@ -746,6 +777,8 @@ __global__ __launch_bounds__(256) void self_attention_prefill(const float* __res
 #pragma unroll
     for (int c = 0; c < 4; ++c) r[c] = o[c] * inv;
     *reinterpret_cast<f32x4*>(out + ((long)p * B + b) * d + h * 64 + gl16 * 4) = r;
+  } else if (RAGGED && p <= p_last) {  // a void query next to live ones
+    *reinterpret_cast<f32x4*>(out + ((long)p * B + b) * d + h * 64 + gl16 * 4) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   }
 }
 
@@ -1004,7 +1037,8 @@ void check_self_attention_long(int cap, int pos, int batch, int heads) {
 void launch_self_attention_long(const float* qkv, float* kcache, float* vcache, int cap, int pos, float* out, int batch,
                                 int heads, hipStream_t s) {
   check_self_attention_long(cap, pos, batch, heads);
-  hipLaunchKernelGGL(self_attention_long, dim3(batch * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out, heads);
+  hipLaunchKernelGGL(self_attention_long<false>, dim3(batch * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out, heads,
+                     static_cast<const int*>(nullptr), 0);
 }
 
 void check_self_attention_prefill(int cap, int pos0, int np, int batch, int heads) {
@@ -1018,8 +1052,38 @@ void launch_self_attention_prefill(const float* qkv, float* kcache, float* vcach
                                    int batch, int heads, hipStream_t s) {
   check_self_attention_prefill(cap, pos0, np, batch, heads);
   const int qblocks = (np + kPrefillQ - 1) / kPrefillQ;
-  hipLaunchKernelGGL(self_attention_prefill, dim3(batch * heads * qblocks), dim3(256), 0, s, qkv, kcache, vcache, cap, pos0,
-                     np, batch, out, heads);
+  hipLaunchKernelGGL(self_attention_prefill<false>, dim3(batch * heads * qblocks), dim3(256), 0, s, qkv, kcache, vcache, cap,
+                     pos0, np, batch, out, heads, static_cast<const int*>(nullptr), 0);
+}
+
+// The ragged forms: the unragged refusals, except that a slot may lie past the cache (a clip behind a long prompt is
+// capped while one behind a short prompt goes on: at most 2 x kSelfLongCap slots), plus the limit and the array.
+void check_self_attention_long_ragged(int cap, int pos, int P, int batch, int heads) {
+  check_self_attention_long(cap, pos < cap ? pos : 0, batch, heads);
+  if (pos >= 2 * kSelfLongCap) throw Error(kErrInvalidArg, "decoder self-attention (long cache, ragged): slot outside [0, 896)");
+  if (P < 1 || P > cap) throw Error(kErrInvalidArg, "decoder self-attention (long cache, ragged): position limit outside [1, cap]");
+}
+
+void launch_self_attention_long_ragged(const float* qkv, float* kcache, float* vcache, int cap, int pos, const int* start,
+                                       int P, float* out, int batch, int heads, hipStream_t s) {
+  check_self_attention_long_ragged(cap, pos, P, batch, heads);
+  if (!start) throw Error(kErrInvalidArg, "decoder self-attention (long cache, ragged): no start array");
+  hipLaunchKernelGGL(self_attention_long<true>, dim3(batch * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out, heads,
+                     start, P);
+}
+
+void check_self_attention_prefill_ragged(int cap, int pos0, int np, int P, int batch, int heads) {
+  check_self_attention_prefill(cap, pos0, np, batch, heads);
+  if (P < 1 || P > cap) throw Error(kErrInvalidArg, "decoder self-attention (prefill, ragged): position limit outside [1, cap]");
+}
+
+void launch_self_attention_prefill_ragged(const float* qkv, float* kcache, float* vcache, int cap, int pos0, int np,
+                                          const int* start, int P, float* out, int batch, int heads, hipStream_t s) {
+  check_self_attention_prefill_ragged(cap, pos0, np, P, batch, heads);
+  if (!start) throw Error(kErrInvalidArg, "decoder self-attention (prefill, ragged): no start array");
+  const int qblocks = (np + kPrefillQ - 1) / kPrefillQ;
+  hipLaunchKernelGGL(self_attention_prefill<true>, dim3(batch * heads * qblocks), dim3(256), 0, s, qkv, kcache, vcache, cap,
+                     pos0, np, batch, out, heads, start, P);
 }
 
 template <int NQ, bool BF>

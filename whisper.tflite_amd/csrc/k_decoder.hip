@@ -72,11 +72,15 @@ struct DecGemmDev {
   float* part;
   const float* xpart;
   int lnp_off;  // float offset of the LayerNorm gain / shift staging area in LDS
+  const int* pos_start;  // ragged chain: slot of clip b's position 0, or null
+  int n_ctx;             // rows of pos_emb: the clamp of a ragged row's position
 };
 
 // Row sources of the residual stream.  LNMODE 0: x = xin;  2: x = tok_emb[id] + pos_emb (row = p * B + b reads
 // ids[b][pos + p] and positional row pos + p);  3: x = xin + xpart (the second K-half of the previous residual
 // GEMM is still pending in xpart).
+// pos_start (LNMODE 2, optional): `pos` counts slots and clip b's positional row is pos + p - pos_start[b], clamped into
+// the table for the rows in front of a clip's position 0 and behind its cap (void rows: nothing reads what they make).
 struct RowSrc {
   const float* xin;
   const float* xpart;
@@ -85,6 +89,8 @@ struct RowSrc {
   const float* tok_emb;
   const float* pos_emb;
   int n_vocab;
+  const int* pos_start;
+  int n_ctx;
 };
 
 // 8 lanes own one row (16-byte columns sub, sub + 8, ...); the NF4 loads of the row are
@@ -103,7 +109,12 @@ __device__ __forceinline__ void load_row(f32x4 (&v)[NF4], const RowSrc& r, int r
 #pragma unroll
   for (int j = 0; j < NF4; ++j) v[j] = *reinterpret_cast<const f32x4*>(src + (sub + 8 * j) * 4);
   if (LNMODE == 2) {
-    const float* pe = r.pos_emb + (long)(r.pos + p) * K;
+    int pr = r.pos + p;
+    if (r.pos_start) {  // (uniform over the launch)
+      const int st = min(max(r.pos_start[row - p * r.B], -(1 << 20)), 1 << 20);
+      pr = min(max(pr - st, 0), r.n_ctx - 1);
+    }
+    const float* pe = r.pos_emb + (long)pr * K;
 #pragma unroll
     for (int j = 0; j < NF4; ++j) v[j] += *reinterpret_cast<const f32x4*>(pe + (sub + 8 * j) * 4);
   }
@@ -200,7 +211,7 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm(DecGemmDev g) {
       static_assert(PRO != kProLn || WAVES == 4, "the LayerNorm prologue maps 4 waves x 8 rows");
       const bool writer = (LNMODE == 2 || LNMODE == 3) && blockIdx.x == 0 && g.xout != nullptr;
       const int r8 = lane >> 3, sub = lane & 7;
-      const RowSrc src{g.xin, g.xpart, g.ids, g.ids_stride, g.pos, g.B, g.tok_emb, g.pos_emb, g.n_vocab};
+      const RowSrc src{g.xin, g.xpart, g.ids, g.ids_stride, g.pos, g.B, g.tok_emb, g.pos_emb, g.n_vocab, g.pos_start, g.n_ctx};
       constexpr int NV = NF4 > 0 ? NF4 : 1;
       if (g0 > 0) __syncthreads();  // the previous group's partials (aliasing xs) have been consumed
 #pragma unroll 1
@@ -466,7 +477,7 @@ __global__ __launch_bounds__(256, 2) void dec_logits_persistent(DecGemmDev g) {
     // 8 lanes per row, a wavefront normalises 8 rows: the 32 rows of the tile in one pass (as dec_finalize_ln did)
     constexpr int NF4 = 2 * KS;
     const int r8 = lane >> 3, sub = lane & 7, lrow = wid * 8 + r8, row = m0 + lrow;
-    const RowSrc src{g.xin, g.xpart, nullptr, 0, 0, g.B, nullptr, nullptr, 0};
+    const RowSrc src{g.xin, g.xpart, nullptr, 0, 0, g.B, nullptr, nullptr, 0, nullptr, 0};
     f32x4 v[NF4], gg[NF4], bb[NF4];
 #pragma unroll
     for (int j = 0; j < NF4; ++j) {
@@ -750,14 +761,15 @@ void launch_dec_gemm(const DecGemmArgs& a, int pro, int epi, hipStream_t s) {
   DecGemmDev g{a.Wt,      1.0f / a.w_scale, a.N,  a.K,       M,         a.B,     a.X,     a.ldx,   a.xin,  a.xout,
                a.ln_g,    a.ln_b,    a.ids,      a.ids_stride, a.pos,   a.tok_emb, a.pos_emb, a.n_vocab,
                a.cross_ws, a.heads,  a.chunks,   a.bias,    gelu,      a.R,     a.Y,     a.ldy,   a.best,
-               a.best_stride > 0 ? a.best_stride : (a.N + 31) / 32, ksplit, a.part,  a.xpart, 0};
+               a.best_stride > 0 ? a.best_stride : (a.N + 31) / 32, ksplit, a.part,  a.xpart, 0,
+               a.pos_start, a.n_ctx};
   // host-side shape contract: operands must match what the kernel indexes
   const bool resid = epi == kDecResid;  // N = d_model: 8 wavefronts split K
   const int waves = resid ? 8 : 4;
   const int kblock = a.K / ksplit;
   if (!a.Wt || a.B < 1 || M < a.B || M > 128 || M % a.B != 0 || a.K > 4096 || a.K % 16 != 0 || !(a.w_scale > 0.0f) ||
       ksplit > 2 || kblock % (16 * waves) != 0 ||
-      (pro == kProCombine && a.K != a.heads * 64) || (resid && (!a.R || !a.Y))) {
+      (pro == kProCombine && a.K != a.heads * 64) || (resid && (!a.R || !a.Y)) || (a.pos_start && a.n_ctx < 1)) {
     throw Error(kErrInvalidArg, "decoder GEMM shape outside the kernel contract");
   }
   if (ksplit != 1 && !(pro == kProNone && epi == kDecResid && a.part && a.R != a.Y)) {
@@ -785,7 +797,7 @@ static void launch_finalize_mode(const RowSrc& src, const float* g, const float*
 
 void launch_dec_finalize_ln(const float* xin, const float* g, const float* b, float* y, int B, int K,
                             hipStream_t s, const float* xpart) {
-  const RowSrc src{xin, xpart, nullptr, 0, 0, B, nullptr, nullptr, 0};
+  const RowSrc src{xin, xpart, nullptr, 0, 0, B, nullptr, nullptr, 0, nullptr, 0};
   if (xpart) {
     launch_finalize_mode<3>(src, g, b, y, B, K, s);
   } else {

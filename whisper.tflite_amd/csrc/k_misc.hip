@@ -340,6 +340,15 @@ __global__ __launch_bounds__(256) void select_token(const unsigned long long* __
   }
 }
 
+// The ragged chain's position cap: after the selection of slot `pos`, clip b — at Whisper position
+// pos - start[b] — has fed its last position when that is P - 1; from then on its count stands still, as behind EOT.
+__global__ void ragged_cap(const int* __restrict__ start, int pos, int P, int* finished, int batch) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= batch) return;
+  const int st = min(max(start[b], -(1 << 20)), 1 << 20);
+  if (pos - st == P - 1) finished[b] = 1;
+}
+
 // Block sum in one fixed order: lanes by butterfly, then the four wavefront partials left to right.  Every thread
 // gets the same value; red[] may be reused after the call.
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
@@ -536,6 +545,11 @@ void launch_mel_normalize(float* logmel, const unsigned* clip_max, int batch, in
   if (batch < 1 || batch > 65535 || n_mel < 1 || T < 1) throw Error(kErrInvalidArg, "mel_normalize: bad shape");
   hipLaunchKernelGGL(mel_normalize, dim3(64, batch), dim3(256), 0, s, logmel, clip_max,
                      (long)n_mel * T);
+}
+
+void launch_ragged_cap(const int* start, int pos, int P, int* finished, int batch, hipStream_t s) {
+  if (!start || !finished || batch < 1 || pos < 0 || P < 1) throw Error(kErrInvalidArg, "ragged_cap: needs start, finished, batch >= 1, pos >= 0 and P >= 1");
+  hipLaunchKernelGGL(ragged_cap, dim3((batch + 63) / 64), dim3(64), 0, s, start, pos, P, finished, batch);
 }
 
 void launch_select_token(const unsigned long long* best, int n_tiles, long long* ids, int ids_stride,

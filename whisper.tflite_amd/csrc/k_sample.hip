@@ -84,7 +84,9 @@ __global__ __launch_bounds__(kThreads) void sample_partial(const float* __restri
     a.t_lo = 0, a.t_hi = V - 1, a.s_lo = V, a.s_hi = V - 1;
   }
   const float inv_t = prm->inv_t[row0 + row];  // 0: greedy
-  const unsigned k0 = prm->seed_lo, k1 = prm->seed_hi, attempt = prm->attempt, clip = prm->clip_base + (unsigned)(row0 + row);
+  const unsigned k0 = prm->seed_lo, k1 = prm->seed_hi, attempt = prm->attempt;
+  const unsigned clip = prm->clip_base + (unsigned)(row0 + row) + (unsigned)prm->clip_off[row0 + row];
+  rng_pos -= prm->pos_off[row0 + row];
   const float* z = logits + (long)row * ldl;  // ldl % 4 == 0 and a 16-byte base: every quad below is aligned
   float v[4 * kQuads];
   unsigned long long kt = 0ull, ks = 0ull, pt = 0ull, ps = 0ull;

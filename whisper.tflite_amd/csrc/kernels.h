@@ -171,6 +171,10 @@ struct DecGemmArgs {
   const float* tok_emb = nullptr;
   const float* pos_emb = nullptr;  // the whole table [n_text_ctx][K]
   int n_vocab = 0;
+  // ragged chain (optional, device [B]): `pos` counts slots, clip b's positional row is pos + p - pos_start[b] clamped
+  // into [0, n_ctx); null = the rows above
+  const int* pos_start = nullptr;
+  int n_ctx = 0;  // rows of pos_emb (needed with pos_start)
   const float* cross_ws = nullptr;
   int heads = 0, chunks = 0;
   const float* bias = nullptr;
@@ -279,6 +283,16 @@ constexpr int kSelfPrefillRows = 128;  // rows of one decoder pass (Engine::kDec
 void check_self_attention_prefill(int cap, int pos0, int np, int batch, int heads);
 void launch_self_attention_prefill(const float* qkv, float* kcache, float* vcache, int cap, int pos0, int np, float* out,
                                    int batch, int heads, hipStream_t s);
+// The ragged forms of the two: pos / pos0 count SLOTS, clip b is at Whisper position slot - start[b]
+// (start: device [B]) and runs there exactly as above; a position outside [0, min(P, cap)) is void — zeros in `out`, no
+// cache row read or written.  The refusals are those above, except that self_attention_long's slot may lie past the
+// cache (below 2 x kSelfLongCap); P outside [1, cap] and a null `start` are refused too.
+void check_self_attention_long_ragged(int cap, int pos, int P, int batch, int heads);
+void launch_self_attention_long_ragged(const float* qkv, float* kcache, float* vcache, int cap, int pos, const int* start,
+                                       int P, float* out, int batch, int heads, hipStream_t s);
+void check_self_attention_prefill_ragged(int cap, int pos0, int np, int P, int batch, int heads);
+void launch_self_attention_prefill_ragged(const float* qkv, float* kcache, float* vcache, int cap, int pos0, int np,
+                                          const int* start, int P, float* out, int batch, int heads, hipStream_t s);
 // Cross attention of nq (1..4) query rows per clip over T cached keys, the query projection included:
 // q = LayerNorm(x[row]) . Wq^T + bq with x the residual stream [nq * B][d], rows p * B + b.  wq_t = Wq in the
 // layout of cross_q_layout(); kc, vc [B][heads][T][64]; partial results per key chunk in ws
@@ -324,6 +338,8 @@ void launch_cross_absorbed_combine(const float* ws, const float* wv_t, const flo
 void launch_select_token(const unsigned long long* best, int n_tiles, long long* ids, int ids_stride,
                          int pos, int* n_ids, int* finished, long long eot, int stop_at_eot, int batch,
                          hipStream_t s, bool keep_ids = false);
+// ragged chain: finished[b] = 1 where pos - start[b] == P - 1 (device arrays [batch]); runs after the selection of slot pos
+void launch_ragged_cap(const int* start, int pos, int P, int* finished, int batch, hipStream_t s);
 
 // Spoken-language head (k_misc.hip, option "language" = -1 and wt_detect_language_*): per clip the final LayerNorm of
 // its position-0 residual row (x [rows][d], + xpart when a K-split fc2 left two halves), the logits against the fp32
@@ -444,6 +460,10 @@ constexpr int kSampleClipsMax = 64;  // clips of one synchronous call
 struct SampleParams {                // device memory, written ahead of a chain: nothing here is a kernel argument
   unsigned seed_lo, seed_hi, attempt, clip_base;
   float inv_t[kSampleClipsMax];      // 1 / T per clip, 0 = greedy
+  // the ragged chain: the counter's position word is rng_pos - pos_off[clip] (the clip's own Whisper
+  // position under a slot count) and its clip word clip_base + clip + clip_off[clip]; zeros give the words above
+  int pos_off[kSampleClipsMax];
+  int clip_off[kSampleClipsMax];
 };
 struct SamplePart {                  // one (clip, chunk); keys as TsPart's
   unsigned long long pkey_text, pkey_ts;  // best perturbed key over the allowed ids below beg / the allowed timestamps

@@ -29,4 +29,13 @@ int seek_step(const VocabData& vocab, const int64_t* g, int n, int win_ticks, in
 // engine's last_* results (segments, scores, decode info, windows) one entry per window and its context as it was.
 void transcribe_seek(Engine& e, const float* pcm, size_t n_samples, std::string* text);
 
+// wt_transcribe_long_batch: the same loop over n_files recordings side by side.  A round cuts the next
+// window of every file still running, and the windows go through the front end, the encoder and ONE ragged decoder chain
+// (Engine::set_contexts: every file's own context); then every file takes transcribe_seek's step with its clip's
+// result and a file that has reached its end leaves the batch.  A file's result is transcribe_seek's for that file
+// alone.  Leaves last_* one entry per window, the windows listed file by file (last_window_files parallel to
+// last_windows, Segment::clip an index into that list), last_file_text one text per file, and both kinds of context
+// as they were.
+void transcribe_seek_batch(Engine& e, const float* const* pcm, const size_t* n_samples, int n_files);
+
 }  // namespace wt
