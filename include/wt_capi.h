@@ -122,6 +122,17 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * beam_size > 1: the pipelined wt_pipeline_submit* calls, the bf16 storage mode, cross_absorb = 0 (and weights or a
  * gemm_variant without the absorbed form), stop_at_eot = 0, the forced-ids debug tap and the logits tap of
  * wt_encdec_debug_batch),
+ * "full_beam" (0 = default: a full-length call, "max_positions" set, with beam_size > 1 is WT_ERR_UNSUPPORTED; 1 = such a
+ * call runs full-length beam search, DESIGN.md section 23: the walk, the finished list, the fill at the cap and the ranker
+ * are beam_size's, but every live hypothesis first applies the step's allowed set to its OWN generated ids — the whole
+ * vocabulary, or with "timestamps" what the timestamp rules leave — and a token's log-probability is its logit minus
+ * the logsumexp over that set; a hypothesis offers its top beam_size + 1 allowed ids, fewer where fewer are allowed, a
+ * clip then has fewer live hypotheses, and it is done with beam_size finished ones or none live.  It works with and
+ * without "timestamps", "scores" and "skip_silence" on every full-length entry point, wt_transcribe_pcm / _file and
+ * wt_transcribe_long_pcm with fixed windows included; with "scores" the sums, counts and token log-probabilities are the
+ * chosen hypothesis's, and wt_last_beam_scores is valid too.  WT_ERR_UNSUPPORTED with full_beam = 1 and beam_size > 1:
+ * what beam_size and "max_positions" refuse, "temperature" > 0 and "temperature_fallback", either kind of context,
+ * "seek", "word_timestamps" and wt_transcribe_long_batch; the engine stays usable after each),
  * "last_batches" (N = the next N pipelined submits are the last of a job: they are decoded one chain per batch, the very
  * last on the encoder's stream, so the pipeline drains sooner; counts down to 0 by itself, may be set with batches in
  * flight), "force_fallback" (test hook: bit mask of contractions sent to the full-range kernels, nothing in flight).
@@ -216,8 +227,9 @@ int wt_transcribe_tokens_batch_dev(wt_engine* h, const float* d_pcm, int batch, 
  * which the last clip emitted EOT; wt_timings.decoder_steps reports the steps run.  wt_transcribe_pcm / _file /
  * _long_pcm honour the option.  With max_positions = 0 these calls are WT_ERR_INVALID_ARG.  While the option is set, the
  * calls with rows of WT_MAX_IDS ids (wt_encdec_tokens_batch*, wt_transcribe_tokens_batch_dev, wt_encdec_debug_batch) and
- * wt_pipeline_submit* are WT_ERR_UNSUPPORTED, and so is a full-length call with beam_size > 1, the bf16 storage mode,
- * language = WT_LANGUAGE_AUTO or the forced-ids tap; the engine stays usable after each. */
+ * wt_pipeline_submit* are WT_ERR_UNSUPPORTED, and so is a full-length call with beam_size > 1 (unless "full_beam" = 1:
+ * full-length beam search), the bf16 storage mode, language = WT_LANGUAGE_AUTO or the forced-ids tap; the engine stays
+ * usable after each. */
 int wt_encdec_tokens_full_batch(wt_engine* h, const float* mel, int batch, int64_t* ids, int ids_stride, int32_t* n_ids);
 int wt_encdec_tokens_full_batch_dev(wt_engine* h, const float* d_mel, int batch, int64_t* ids, int ids_stride,
                                     int32_t* n_ids);

@@ -121,6 +121,13 @@ int wt_dbg_self_attention_long_ragged(wt_engine* h, int batch, int heads, int ca
                                       float* vcache, float* out, const int32_t* start, int P);
 int wt_dbg_self_attention_prefill_ragged(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
                                          float* kcache, float* vcache, float* out, const int32_t* start, int P);
+/* The gathered form of self_attention_long (full-length beam search): the arguments of
+ * wt_dbg_self_attention_long — `rows` in the place of the batch, at most 128 — plus anc [rows][cap] bytes.  Row r reads
+ * key k < pos from cache row min(anc[r][k], rows - 1) and appends key pos to its own row; entries at k >= pos are not
+ * read.  With anc[r][k] = r the output and the caches carry the bits of wt_dbg_self_attention_long.  The refusals are
+ * that tap's; rows > 128 and a NULL table are refused too. */
+int wt_dbg_self_attention_long_gather(wt_engine* h, int rows, int heads, int cap, int pos, const float* qkv, float* kcache,
+                                      float* vcache, float* out, const uint8_t* anc);
 /* wt_dbg_dec_ln_gemm's embedding rows under a slot count: row b = tok_emb[ids[b]] + pos_emb[clamp(pos - pos_start[b], 0,
  * n_pos - 1)]; pos_start = NULL is wt_dbg_dec_ln_gemm with ids. */
 int wt_dbg_dec_ln_gemm_ragged(wt_engine* h, int B, int N, int K, const int64_t* ids, int pos, const int32_t* pos_start,
@@ -208,6 +215,41 @@ int wt_dbg_beam_reorder(wt_engine* h, int src_rows, int dst_rows, int cap, int d
 int wt_dbg_beam_finalize(wt_engine* h, int K, int clips, int c0, int pos, int n_prompt, const int64_t* ids,
                          const float* live_sum, int32_t* fin_tok, float* fin_sum, int32_t* fin_len, int32_t* n_fin,
                          const int32_t* done, int64_t* out_ids, int32_t* out_n, float* out_sum, int32_t* out_len);
+/* full-length beam search (k_beam_full.hip).  Rows are laid out row = k * clips + c; step
+ * t = pos + 1 - n_prompt has `clips` live rows at t = 0 and K * clips afterwards.  The per-clip state is the engine's,
+ * indexed by c0 + clip, all in / out.  A shape the launchers refuse is WT_ERR_INVALID_ARG. */
+typedef struct wt_dbg_beam_full_args {
+  int32_t K, clips, c0, pos, n_prompt, V, ldl, stride, cap, eot, beg, max_initial, timestamps;
+  int32_t begin;              /* step: run beam_full_begin first (the state arrays are then outputs only) */
+  const float* logits;        /* [live rows][ldl] */
+  const int64_t* ids;         /* [live rows][stride] the live hypotheses' ids, */
+  const float* lp;            /* [live rows][stride] log-probabilities (index = the id's position) */
+  const uint8_t* anc;         /* [live rows][cap] and ancestor tables */
+  int32_t* ts_state;          /* [128][3]: tick, last_is_ts, prev_is_ts per row */
+  int32_t* n_live;            /* [64] */
+  double* live_sum;           /* [64][8] */
+  int32_t* fin_tok;           /* [64][8][stride] */
+  float* fin_lp;              /* [64][8][stride] */
+  double* fin_sum;            /* [64][8] */
+  int32_t *fin_len, *n_fin, *done; /* [64][8], [64], [64] */
+  int32_t* parent;            /* step, out: [K * clips] */
+  int64_t* token;             /* [K * clips] */
+  float* tok_lp;              /* [K * clips] */
+  int64_t* ids_next;          /* [K * clips][stride], in / out (cells the kernel must not write come back as sent) */
+  float* lp_next;             /* [K * clips][stride] */
+  uint8_t* anc_next;          /* [K * clips][cap] */
+  double* lse;                /* [live rows]: logsumexp_A, NaN where A is empty; untouched for rows that are not live */
+  float* part_stats;          /* optional [live rows][chunks][4]: mt, st, ms, ss of beam_full_partial */
+  uint64_t* part_keys;        /* optional [live rows][chunks][2][K + 1]: its text keys, then its timestamp keys */
+  int64_t* out_ids;           /* finalize, out: [64][stride] */
+  float* out_lp;              /* [64][stride] */
+  int32_t *out_n, *out_len;   /* [64] */
+  double* out_sum;            /* [64] */
+} wt_dbg_beam_full_args;
+/* one step of decode_beam_full: (beam_full_begin,) beam_full_partial, beam_full_select, beam_full_advance */
+int wt_dbg_beam_full_step(wt_engine* h, const wt_dbg_beam_full_args* a);
+/* beam_full_finalize; ids / lp: the [K * clips] rows after the last step's advance, pos that step's */
+int wt_dbg_beam_full_finalize(wt_engine* h, const wt_dbg_beam_full_args* a);
 /* the tail of a greedy decoder step kernel by kernel (k_decoder.hip, select_token in k_misc.hip); bf16 != 0 selects
  * the BF = true instantiation.  fc2 as the engine runs it with fc2_ksplit = 2 (M <= 128 rows = M / B positions x B
  * clips, K % 256 == 0): Y = R + bias + X[:, :K/2] . W[:, :K/2]^T and part = X[:, K/2:] . W[:, K/2:]^T, out of place;

@@ -2,9 +2,12 @@
 """Beam-search costs on one MI355X, synthetic tiny weights:
   * single-clip transcribe latency (wt_transcribe_pcm) at beam_size 1 and K;
   * audio-sec/s of wt_encdec_tokens_batch_dev at beam_size K with 25 and 64 clips (and greedy beside it).
+With --max-positions P the batch cases run the full-length chains instead: full-length beam
+search (full_beam = 1) beside full-length greedy decoding at the same P, ms per call and per decoder step; the
+synthetic weights never emit EOT, so every step runs.
 Every GPU step runs in a child process of its own under a time limit; the parent only collects the JSON lines.
 
-  python tools/beam_bench.py [--beam 5] [--iters 10] [--only CASE]
+  python tools/beam_bench.py [--beam 5] [--iters 10] [--only CASE] [--max-positions P]
 """
 from __future__ import annotations
 
@@ -21,13 +24,16 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def child(case: str, beam: int, iters: int, tmp: str) -> dict:
+def child(case: str, beam: int, iters: int, tmp: str, max_positions: int = 0) -> dict:
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
     pkg = ge.load_package()
     prefix, vocab = ge._assets(tmp, "tiny", 0)
     eng = pkg.Engine(prefix, vocab, True)
     eng.set_option("beam_size", beam)
+    if max_positions:
+        eng.set_option("max_positions", max_positions)
+        eng.set_option("full_beam", 1)
     rng = np.random.default_rng(1234)
     if case == "latency":
         pcm = (0.1 * rng.standard_normal(eng.pcm_len)).astype(np.float32)
@@ -44,15 +50,19 @@ def child(case: str, beam: int, iters: int, tmp: str) -> dict:
         batch = int(case)
         mel = rng.uniform(-1.0, 1.5, size=(batch,) + eng.mel_shape).astype(np.float32)
         d = ctypes_dev(pkg, eng, mel)
+        run = (lambda: eng.encdec_tokens_full_dev(d, batch)) if max_positions else (lambda: eng.encdec_tokens_batch_dev(d, batch))
         for _ in range(3):
-            eng.encdec_tokens_batch_dev(d, batch)
+            run()
         t0 = time.perf_counter()
         for _ in range(iters):
-            eng.encdec_tokens_batch_dev(d, batch)
+            run()
         dt = (time.perf_counter() - t0) / iters
         tm = eng.timings()
-        out = {"case": "encdec_tokens_batch_dev", "beam_size": beam, "batch": batch, "ms_per_call": 1e3 * dt,
-               "audio_sec_per_s": batch * 30.0 / dt, "decoder_ms": tm.decoder_ms}
+        out = {"case": "encdec_tokens_full_batch_dev" if max_positions else "encdec_tokens_batch_dev", "beam_size": beam,
+               "batch": batch, "ms_per_call": 1e3 * dt, "audio_sec_per_s": batch * 30.0 / dt, "decoder_ms": tm.decoder_ms}
+        if max_positions:
+            steps = int(tm.decoder_steps)
+            out.update(max_positions=max_positions, decoder_steps=steps, decoder_ms_per_step=tm.decoder_ms / max(steps, 1))
     eng.close()
     return out
 
@@ -72,10 +82,11 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--timeout", type=int, default=300, help="seconds per child")
     ap.add_argument("--only", default=None, help="latency, 25 or 64")
+    ap.add_argument("--max-positions", type=int, default=0, help="full-length chains over this many positions (0: 31-position chains)")
     ap.add_argument("--child", nargs=3, metavar=("CASE", "BEAM", "TMP"), help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        print(json.dumps(child(a.child[0], int(a.child[1]), a.iters, a.child[2])))
+        print(json.dumps(child(a.child[0], int(a.child[1]), a.iters, a.child[2], a.max_positions)))
         return 0
     runs = [("latency", 1), ("latency", a.beam), ("25", 1), ("25", a.beam), ("64", 1), ("64", a.beam)]
     if a.only:
@@ -83,7 +94,8 @@ def main():
     results = []
     with tempfile.TemporaryDirectory() as tmp:
         for case, beam in runs:
-            cmd = [sys.executable, os.path.abspath(__file__), "--iters", str(a.iters), "--child", case, str(beam), tmp]
+            cmd = [sys.executable, os.path.abspath(__file__), "--iters", str(a.iters), "--max-positions", str(a.max_positions),
+                   "--child", case, str(beam), tmp]
             try:
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
             except subprocess.TimeoutExpired:

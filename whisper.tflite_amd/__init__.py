@@ -61,9 +61,10 @@ DEBUG_SYMBOLS = [
     "wt_dbg_gemm_planes", "wt_dbg_set_plane_gemm_mode", "wt_dbg_set_forced_ids", "wt_dbg_dec_gemm_bf16", "wt_dbg_dec_ln_gemm_bf16",
     "wt_dbg_self_attention_bf16", "wt_dbg_cross_attention_bf16", "wt_dbg_encoder_attention_planes", "wt_dbg_gemm_bf16", "wt_dbg_gemm_bf16_ln", "wt_dbg_encoder_attention_bf16",
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
+    "wt_dbg_beam_full_step", "wt_dbg_beam_full_finalize",
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_self_attention_long",
-    "wt_dbg_self_attention_prefill",
+    "wt_dbg_self_attention_prefill", "wt_dbg_self_attention_long_gather",
     "wt_dbg_self_attention_long_ragged", "wt_dbg_self_attention_prefill_ragged", "wt_dbg_dec_ln_gemm_ragged", "wt_dbg_ragged_cap",
     "wt_dbg_timestamp_select", "wt_dbg_token_scores", "wt_dbg_sample_select",
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
@@ -71,6 +72,28 @@ DEBUG_SYMBOLS = [
     "wt_dbg_gemm_addressed", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes", "wt_dbg_encoder_attention_at",
     "wt_dbg_align_scores", "wt_dbg_align_matrix", "wt_dbg_align_dtw", "wt_dbg_last_alignment", "wt_dbg_set_alignment",
 ]
+
+
+class BeamFullArgs(ctypes.Structure):
+    """wt_dbg_beam_full_args (include/wt_debug.h)."""
+    _SCALARS = ("K", "clips", "c0", "pos", "n_prompt", "V", "ldl", "stride", "cap", "eot", "beg", "max_initial", "timestamps",
+                "begin")
+    _ARRAYS = (("logits", np.float32), ("ids", np.int64), ("lp", np.float32), ("anc", np.uint8), ("ts_state", np.int32),
+               ("n_live", np.int32), ("live_sum", np.float64), ("fin_tok", np.int32), ("fin_lp", np.float32),
+               ("fin_sum", np.float64), ("fin_len", np.int32), ("n_fin", np.int32), ("done", np.int32), ("parent", np.int32),
+               ("token", np.int64), ("tok_lp", np.float32), ("ids_next", np.int64), ("lp_next", np.float32),
+               ("anc_next", np.uint8), ("lse", np.float64), ("part_stats", np.float32), ("part_keys", np.uint64),
+               ("out_ids", np.int64), ("out_lp", np.float32), ("out_n", np.int32), ("out_len", np.int32),
+               ("out_sum", np.float64))
+    _fields_ = [(n, c_int32) for n in _SCALARS] + [(n, c_void_p) for n, _ in _ARRAYS]
+
+
+def beam_full_state(stride):
+    """The per-clip state of a full-length beam chain as decode_beam_full keeps it, before beam_full_begin."""
+    return {"ts_state": np.zeros((128, 3), np.int32), "n_live": np.zeros(64, np.int32), "live_sum": np.zeros((64, 8), np.float64),
+            "fin_tok": np.zeros((64, 8, stride), np.int32), "fin_lp": np.zeros((64, 8, stride), np.float32),
+            "fin_sum": np.zeros((64, 8), np.float64), "fin_len": np.zeros((64, 8), np.int32), "n_fin": np.zeros(64, np.int32),
+            "done": np.zeros(64, np.int32)}
 
 
 class WtError(RuntimeError):
@@ -223,6 +246,9 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_self_attention_long.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp]
         L.wt_dbg_self_attention_prefill.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp]
         L.wt_dbg_self_attention_long_ragged.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp, ip32, c_int]
+        L.wt_dbg_beam_full_step.argtypes = [c_void_p, POINTER(BeamFullArgs)]
+        L.wt_dbg_beam_full_finalize.argtypes = [c_void_p, POINTER(BeamFullArgs)]
+        L.wt_dbg_self_attention_long_gather.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp, POINTER(ctypes.c_uint8)]
         L.wt_dbg_self_attention_prefill_ragged.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp, ip32, c_int]
         L.wt_dbg_dec_ln_gemm_ragged.argtypes = [c_void_p, c_int, c_int, c_int, ip64, c_int, ip32, fp, fp,
                                                 c_int, c_int, fp, fp, fp, fp, c_int, fp, fp]
@@ -1253,6 +1279,18 @@ class Engine:
                                                             _fp(out), _ip32(start), P))
         return out, kcache, vcache
 
+    def dbg_self_attention_long_gather(self, qkv, kcache, vcache, pos, anc):
+        """self_attention_long over a shared cache: row r reads key k < pos from cache row min(anc[r][k], rows - 1);
+        anc [rows][cap] uint8, rows <= 128."""
+        qkv, kcache, vcache = _f32(qkv), _f32(kcache).copy(), _f32(vcache).copy()
+        anc = np.ascontiguousarray(anc, np.uint8)
+        B, cap, d = kcache.shape
+        assert anc.shape == (B, cap)
+        out = np.full((B, d), np.nan, np.float32)
+        self._check(lib().wt_dbg_self_attention_long_gather(self._h, B, d // 64, cap, pos, _fp(qkv), _fp(kcache), _fp(vcache),
+                                                            _fp(out), anc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        return out, kcache, vcache
+
     def dbg_self_attention_prefill_ragged(self, qkv, kcache, vcache, pos, npos, start, P):
         """self_attention_prefill under a slot count: query p of clip b at position pos + p - start[b], void outside [0, P)."""
         qkv, kcache, vcache = _f32(qkv), _f32(kcache).copy(), _f32(vcache).copy()
@@ -1327,6 +1365,56 @@ class Engine:
         self._check(lib().wt_dbg_beam_step(self._h, K, clips, c0, n_live, pos, n_prompt, V, eot, _fp(logits), _ip64(ids),
                                            *self._beam_state_ptrs(state), _ip32(parent), _ip64(token), _ip64(ids_next)))
         return parent, token, ids_next
+
+    def _beam_full_args(self, scalars, arrays):
+        a = BeamFullArgs()
+        for name in BeamFullArgs._SCALARS:
+            setattr(a, name, int(scalars.get(name, 0)))
+        for name, dt in BeamFullArgs._ARRAYS:
+            arr = arrays.get(name)
+            if arr is not None:
+                assert arr.dtype == dt and arr.flags.c_contiguous, name
+                setattr(a, name, arr.ctypes.data)
+        return a
+
+    def dbg_beam_full_step(self, state, logits, ids, lp, anc, *, K, clips, pos, n_prompt, cap, eot, beg=0, timestamps=False,
+                           max_initial=-1, c0=0, begin=False, want_part=False):
+        """One step of decode_beam_full over the live rows' logits [rows][ldl >= V... here ldl = V], ids / lp [rows][cap + 1]
+        and anc [rows][cap]; `state` (beam_full_state) is updated in place.  Returns dict(parent, token, tok_lp, ids_next,
+        lp_next, anc_next [K * clips][..], lse [rows], and with want_part: part_stats, part_keys)."""
+        logits = _f32(logits)
+        rows, V = logits.shape
+        stride = cap + 1
+        R = K * clips
+        arrays = dict(state)
+        arrays.update(logits=logits, ids=np.ascontiguousarray(ids, np.int64), lp=_f32(lp), anc=np.ascontiguousarray(anc, np.uint8))
+        assert arrays["ids"].shape == (rows, stride) and arrays["lp"].shape == (rows, stride) and arrays["anc"].shape == (rows, cap)
+        out = {"parent": np.full(R, -1, np.int32), "token": np.full(R, -1, np.int64), "tok_lp": np.full(R, np.nan, np.float32),
+               "ids_next": np.full((R, stride), -7, np.int64), "lp_next": np.full((R, stride), -7.0, np.float32),
+               "anc_next": np.full((R, cap), 251, np.uint8), "lse": np.full(rows, -7.0, np.float64)}
+        if want_part:
+            chunks = (V + 4095) // 4096
+            out["part_stats"] = np.zeros((rows, chunks, 4), np.float32)
+            out["part_keys"] = np.zeros((rows, chunks, 2, K + 1), np.uint64)
+        arrays.update(out)
+        a = self._beam_full_args(dict(K=K, clips=clips, c0=c0, pos=pos, n_prompt=n_prompt, V=V, ldl=V, stride=stride, cap=cap, eot=eot,
+                                      beg=beg, max_initial=max_initial, timestamps=int(bool(timestamps)), begin=int(bool(begin))), arrays)
+        self._check(lib().wt_dbg_beam_full_step(self._h, ctypes.byref(a)))
+        return out
+
+    def dbg_beam_full_finalize(self, state, ids, lp, *, K, clips, pos, n_prompt, cap, c0=0):
+        """beam_full_finalize over the rows after the last advance, ids / lp [K * clips][cap + 1]; `state` updated in place.
+        Returns dict(out_ids [64][cap + 1], out_lp, out_n, out_len, out_sum [64])."""
+        stride = cap + 1
+        arrays = dict(state)
+        arrays.update(ids=np.ascontiguousarray(ids, np.int64), lp=_f32(lp))
+        assert arrays["ids"].shape == (K * clips, stride) and arrays["lp"].shape == (K * clips, stride)
+        out = {"out_ids": np.full((64, stride), -7, np.int64), "out_lp": np.full((64, stride), -7.0, np.float32),
+               "out_n": np.full(64, -7, np.int32), "out_len": np.full(64, -7, np.int32), "out_sum": np.full(64, -7.0, np.float64)}
+        arrays.update(out)
+        a = self._beam_full_args(dict(K=K, clips=clips, c0=c0, pos=pos, n_prompt=n_prompt, V=1, ldl=1, stride=stride, cap=cap), arrays)
+        self._check(lib().wt_dbg_beam_full_finalize(self._h, ctypes.byref(a)))
+        return out
 
     def dbg_beam_reorder(self, src_rows, dst_rows, cap, d, slabs, pos, V, kv_src, kv_dst, ids_src, ids_dst, parent, token):
         """kv_dst [slabs * dst_rows + 1][cap][d] and ids_dst [128][32]: returned updated (copies)."""

@@ -29,6 +29,7 @@ void usage(const char* argv0) {
             << "  --english       English-only vocabulary ids (multilingual = false; the reference hard-codes true)\n"
             << "  --long          transcribe every 30 s window of the file, not only the first\n"
             << "  --beam N        beam search with N hypotheses, 2..8 (default: greedy, as the reference)\n"
+            << "                  with --max-positions: full-length beam search, with or without --timestamps and --scores\n"
             << "  --max-positions N  full-length greedy decoding over N positions, 32 .. n_text_ctx (default: the\n"
             << "                  reference's 31 positions)\n"
             << "  --timestamps    with --max-positions: decode with timestamps and print one line per segment,\n"
@@ -174,6 +175,11 @@ int main(int argc, char* argv[]) {
     const long n = std::strtol(max_positions.c_str(), &end, 10);
     if (end == max_positions.c_str() || *end || wt_engine_set_option(encdec.handle(), "max_positions", n) != WT_OK) {
       std::cerr << "--max-positions: expected 0 or a position count in [32, n_text_ctx], got " << max_positions << "\n";
+      return 105;
+    }
+    // --beam N with --max-positions: full-length beam search (the option full_beam; the library's default refuses it)
+    if (!beam.empty() && n > 0 && wt_engine_set_option(encdec.handle(), "full_beam", 1) != WT_OK) {
+      std::cerr << "--beam with --max-positions: " << wt_last_error(encdec.handle()) << "\n";
       return 105;
     }
   }

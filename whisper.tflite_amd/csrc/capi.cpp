@@ -286,6 +286,9 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
   } else if (k == "beam_size") {
     if (value < 1 || value > wt::kBeamMax) return fail(h, WT_ERR_INVALID_ARG, "beam_size must be in [1, 8] (1 = greedy)");
     e.beam_size = value;
+  } else if (k == "full_beam") {
+    if (value < 0 || value > 1) return fail(h, WT_ERR_INVALID_ARG, "full_beam must be 0 or 1");
+    e.full_beam = value;
   } else if (k == "bf16") {
     // bf16 storage mode (BASELINE configs[3]); the first switch reads the weight file again for the bf16 copies
     try {
@@ -377,6 +380,7 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "cross_absorb_active") *value = e.absorb_active() ? 1 : 0;  // read-only
   else if (k == "bf16") *value = e.bf16;
   else if (k == "beam_size") *value = e.beam_size;
+  else if (k == "full_beam") *value = e.full_beam;
   else if (k == "kernel_timers") *value = e.kernel_timers;
   else if (k == "fc2_ksplit") *value = e.fc2_ksplit;
   else if (k == "attn_variant") *value = e.attn_variant;

@@ -754,6 +754,22 @@ int wt_dbg_self_attention_long_ragged(wt_engine* h, int batch, int heads, int ca
     dv.to_host(vcache, nc);
   });
 }
+int wt_dbg_self_attention_long_gather(wt_engine* h, int rows, int heads, int cap, int pos, const float* qkv, float* kcache,
+                                      float* vcache, float* out, const uint8_t* anc) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::check_self_attention_long_gather(cap, pos, rows, heads);  // the launcher's own refusals, before anything is allocated
+    if (!qkv || !kcache || !vcache || !out || !anc) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_self_attention_long_gather: NULL array");
+    const size_t d = size_t(heads) * 64, nc = size_t(rows) * cap * d;
+    DevArr<float> dq(size_t(rows) * 3 * d, qkv), dk(nc, kcache), dv(nc, vcache), dout(size_t(rows) * d);
+    const DevArr<unsigned char> da(size_t(rows) * cap, anc);
+    wt::launch_self_attention_long_gather(dq.p, dk.p, dv.p, cap, pos, da.p, dout.p, rows, heads, h->impl->stream());
+    h->impl->sync();
+    dout.to_host(out, size_t(rows) * d);
+    dk.to_host(kcache, nc);
+    dv.to_host(vcache, nc);
+  });
+}
 int wt_dbg_self_attention_prefill_ragged(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
                                          float* kcache, float* vcache, float* out, const int32_t* start, int P) {
   if (!h) return WT_ERR_INVALID_ARG;
@@ -854,6 +870,131 @@ int wt_dbg_beam_step(wt_engine* h, int K, int clips, int c0, int n_live, int pos
     dparent.to_host(parent);
     dtoken.to_host(reinterpret_cast<long long*>(token));
     dnext.to_host(reinterpret_cast<long long*>(ids_next));
+  });
+}
+
+namespace {
+// device mirror of a wt_dbg_beam_full_args
+struct DevBeamFull {
+  static constexpr size_t C = wt::kBeamClipsMax, S = wt::kBeamMax;
+  const wt_dbg_beam_full_args& a;
+  size_t live, rows, chunks, stride, cap;
+  DevArr<float> logits;
+  DevArr<wt::BeamFullPart> part;
+  DevArr<long long> ids, ids_next;
+  DevArr<float> lp, lp_next;
+  DevArr<unsigned char> anc, anc_next;
+  DevArr<wt::TsState> ts;
+  DevArr<int> n_live, fin_tok, fin_len, n_fin, done, parent, out_n, out_len;
+  DevArr<double> live_sum, fin_sum, lse, out_sum;
+  DevArr<float> fin_lp, tok_lp, out_lp;
+  DevArr<long long> token, out_ids;
+  static size_t live_rows(const wt_dbg_beam_full_args& a) { return size_t(a.pos + 1 == a.n_prompt ? a.clips : a.K * a.clips); }
+  explicit DevBeamFull(const wt_dbg_beam_full_args& a_)
+      : a(a_), live(live_rows(a_)), rows(size_t(a_.K) * a_.clips), chunks(size_t(wt::beam_chunks(a_.V))), stride(size_t(a_.stride)),
+        cap(size_t(a_.cap)),
+        logits(live * a_.ldl, a_.logits), part(live * chunks),
+        ids(live * stride, reinterpret_cast<const long long*>(a_.ids)), ids_next(rows * stride, reinterpret_cast<const long long*>(a_.ids_next)),
+        lp(live * stride, a_.lp), lp_next(rows * stride, a_.lp_next), anc(live * cap, a_.anc), anc_next(rows * cap, a_.anc_next),
+        ts(128, reinterpret_cast<const wt::TsState*>(a_.ts_state)), n_live(C, a_.n_live), fin_tok(C * S * stride, a_.fin_tok),
+        fin_len(C * S, a_.fin_len), n_fin(C, a_.n_fin), done(C, a_.done), parent(rows), out_n(C, a_.out_n), out_len(C, a_.out_len),
+        live_sum(C * S, a_.live_sum), fin_sum(C * S, a_.fin_sum), lse(live, a_.lse), out_sum(C, a_.out_sum),
+        fin_lp(C * S * stride, a_.fin_lp), tok_lp(rows), out_lp(C * stride, a_.out_lp), token(rows),
+        out_ids(C * stride, reinterpret_cast<const long long*>(a_.out_ids)) {}
+  wt::BeamFullArgs args() const {
+    wt::BeamFullArgs x;
+    x.clips = a.clips; x.K = a.K; x.c0 = a.c0; x.pos = a.pos; x.n_prompt = a.n_prompt; x.V = a.V; x.ldl = a.ldl;
+    x.stride = a.stride; x.cap = a.cap; x.eot = a.eot; x.beg = a.beg; x.max_initial = a.max_initial; x.timestamps = a.timestamps;
+    x.logits = logits.p; x.part = part.p; x.ids_src = ids.p; x.ids_dst = ids_next.p; x.lp_src = lp.p; x.lp_dst = lp_next.p;
+    x.anc_src = anc.p; x.anc_dst = anc_next.p; x.ts = ts.p; x.n_live = n_live.p; x.live_sum = live_sum.p;
+    x.fin_tok = fin_tok.p; x.fin_lp = fin_lp.p; x.fin_sum = fin_sum.p; x.fin_len = fin_len.p; x.n_fin = n_fin.p; x.done = done.p;
+    x.parent = parent.p; x.token = token.p; x.tok_lp = tok_lp.p; x.dbg_lse = a.lse ? lse.p : nullptr;
+    x.out_ids = out_ids.p; x.out_lp = out_lp.p; x.out_n = out_n.p; x.out_len = out_len.p; x.out_sum = out_sum.p;
+    return x;
+  }
+  void state_to_host() const {
+    ts.to_host(reinterpret_cast<wt::TsState*>(a.ts_state));
+    n_live.to_host(a.n_live);
+    live_sum.to_host(a.live_sum);
+    fin_tok.to_host(a.fin_tok);
+    fin_lp.to_host(a.fin_lp);
+    fin_sum.to_host(a.fin_sum);
+    fin_len.to_host(a.fin_len);
+    n_fin.to_host(a.n_fin);
+    done.to_host(a.done);
+  }
+};
+bool beam_full_args_ok(const wt_dbg_beam_full_args* a) {
+  return a && a->K >= 1 && a->clips >= 1 && size_t(a->K) * a->clips <= 128 && a->V >= 1 && a->ldl >= a->V && a->stride >= 1 &&
+         a->cap >= 1 && a->stride <= 4096 && a->cap <= 4096 && a->ids && a->lp && a->ts_state && a->n_live && a->live_sum &&
+         a->fin_tok && a->fin_lp && a->fin_sum && a->fin_len && a->n_fin && a->done;
+}
+}  // namespace
+
+int wt_dbg_beam_full_step(wt_engine* h, const wt_dbg_beam_full_args* a) {
+  if (!h || !beam_full_args_ok(a) || !a->logits || !a->anc || !a->parent || !a->token || !a->tok_lp || !a->ids_next ||
+      !a->lp_next || !a->anc_next) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    hipStream_t st = h->impl->stream();
+    DevBeamFull dv(*a);
+    wt::BeamFullArgs x = dv.args();
+    if (a->begin) {  // the chain's start writes the prompt's ancestor entries into the rows the first step reads
+      wt::BeamFullArgs b = x;
+      b.anc_dst = dv.anc.p;
+      wt::launch_beam_full_begin(b, st);
+    }
+    wt::launch_beam_full_partial(x, st);
+    wt::launch_beam_full_select(x, st);
+    wt::launch_beam_full_advance(x, st);
+    h->impl->sync();
+    dv.state_to_host();
+    dv.parent.to_host(a->parent);
+    dv.token.to_host(reinterpret_cast<long long*>(a->token));
+    dv.tok_lp.to_host(a->tok_lp);
+    dv.ids_next.to_host(reinterpret_cast<long long*>(a->ids_next));
+    dv.lp_next.to_host(a->lp_next);
+    dv.anc_next.to_host(a->anc_next);
+    dv.lse.to_host(a->lse);
+    if (a->part_stats || a->part_keys) {
+      std::vector<wt::BeamFullPart> hp(dv.part.n);
+      dv.part.to_host(hp.data());
+      const size_t kk = size_t(a->K) + 1;
+      for (size_t i = 0; i < hp.size(); ++i) {
+        if (a->part_stats) {
+          float* o = a->part_stats + i * 4;
+          o[0] = hp[i].mt, o[1] = hp[i].st, o[2] = hp[i].ms, o[3] = hp[i].ss;
+        }
+        for (size_t r = 0; a->part_keys && r < kk; ++r) {
+          a->part_keys[(i * 2 + 0) * kk + r] = hp[i].kt[r];
+          a->part_keys[(i * 2 + 1) * kk + r] = hp[i].ks[r];
+        }
+      }
+    }
+  });
+}
+
+int wt_dbg_beam_full_finalize(wt_engine* h, const wt_dbg_beam_full_args* a) {
+  if (!h || !beam_full_args_ok(a) || !a->out_ids || !a->out_lp || !a->out_n || !a->out_len || !a->out_sum) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    // (the rows handed in are the K * clips rows after the last advance, whatever the step)
+    wt_dbg_beam_full_args b = *a;
+    b.logits = nullptr, b.anc = nullptr, b.ids_next = nullptr, b.lp_next = nullptr, b.anc_next = nullptr, b.lse = nullptr;
+    const size_t rows = size_t(a->K) * a->clips, stride = size_t(a->stride);
+    DevBeamFull dv(b);
+    DevArr<long long> ids(rows * stride, reinterpret_cast<const long long*>(a->ids));
+    DevArr<float> lp(rows * stride, a->lp);
+    wt::BeamFullArgs x = dv.args();
+    x.ids_src = ids.p, x.lp_src = lp.p;
+    wt::launch_beam_full_finalize(x, h->impl->stream());
+    h->impl->sync();
+    dv.state_to_host();
+    dv.out_ids.to_host(reinterpret_cast<long long*>(a->out_ids));
+    dv.out_lp.to_host(a->out_lp);
+    dv.out_n.to_host(a->out_n);
+    dv.out_len.to_host(a->out_len);
+    dv.out_sum.to_host(a->out_sum);
   });
 }
 

@@ -1831,7 +1831,7 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
   const int B = p.B, M = p.np * B;
   const bool bf = p.bf, split = p.split;  // bf16 storage mode: bf16 weights and caches (element size 2 in the cache offsets)
   const size_t kv_slab = size_t(p.clips) * T * d;  // one (layer, k|v) slab of the cross cache
-  const size_t self_slab = size_t(B) * p.self_cap * d;
+  const size_t self_slab = size_t(p.self_rows > 0 ? p.self_rows : B) * p.self_cap * d;
   auto cache_at = [&](float* base, size_t elems) -> void* {
     return bf ? static_cast<void*>(reinterpret_cast<unsigned short*>(base) + elems) : static_cast<void*>(base + elems);
   };
@@ -1855,7 +1855,10 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
     void* const kc = cache_at(p.self_kv, (size_t(l) * 2 + 0) * self_slab);
     void* const vc = cache_at(p.self_kv, (size_t(l) * 2 + 1) * self_slab);
     timed(tm, 1, [&] {
-      if (p.pos_start && p.self_prefill) {  // the ragged chain: prompt slots, then one generated slot per pass
+      if (p.self_anc) {  // full-length beam search: the hypotheses share one cache through their ancestor tables
+        launch_self_attention_long_gather(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0,
+                                          p.self_anc, dw.attd, B, H, st);
+      } else if (p.pos_start && p.self_prefill) {  // the ragged chain: prompt slots, then one generated slot per pass
         launch_self_attention_prefill_ragged(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0, p.np,
                                              p.pos_start, p.pos_limit, dw.attd, B, H, st);
       } else if (p.pos_start) {
@@ -2536,10 +2539,18 @@ void Engine::check_full_args(int batch, int ids_stride) const {
 void Engine::check_full_call() const {
   if (max_positions <= 0) return;
   auto no = [](const char* why) { throw Error(kErrUnsupported, std::string("full-length decoding (max_positions): ") + why); };
-  if (beam_size > 1) no("greedy only, not with beam search (beam_size > 1)");
+  if (beam_size > 1 && !full_beam) no("greedy only, not with beam search (beam_size > 1) unless the option full_beam = 1 is set");
   if (bf16) no("not in the bf16 storage mode");
   if (language < 0) no("not with automatic language detection (language = -1)");
   if (!forced_ids.empty()) no("not with forced ids");
+  if (beam_size > 1) {  // full_beam = 1: beam search's own scope, and what the beam chain does not run
+    auto nb = [](const char* why) { throw Error(kErrUnsupported, std::string("full-length beam search (full_beam): ") + why); };
+    check_beam_call(false);
+    if (sampling() || temperature_fallback) nb("not with a temperature or the temperature fall-back");
+    if (!context_ids.empty() || !clip_contexts.empty()) nb("not with a context");
+    if (seek) nb("not with seek");
+    if (word_timestamps) nb("not with word_timestamps");
+  }
   if (timestamps && !has_timestamp_tokens()) no("timestamps: the model's vocabulary has no timestamp ids");
   if (scores && !has_no_speech_token()) no("scores: the model's vocabulary has no <|nospeech|> id");
   if (!context_ids.empty() && long(fed_prompt().size()) >= max_positions) {
@@ -2691,6 +2702,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   last_words_valid = false;
   last_alignment.clear();
   clear_last_scores();  // (the decode info with them)
+  if (beam_size > 1) return decode_beam_full(batch, ids, ids_stride, n_ids);  // (full_beam = 1: check_full_call)
   const bool ts = timestamps != 0, sc = scores != 0, smp = sampling();
   ensure_batch(batch);
   ensure_full_workspace(batch);  // (before any capture: nothing may be allocated inside one)
@@ -3022,6 +3034,249 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   }
   if (word_timestamps && !defer_word_alignment) {
     align_words(batch, last_segments, valid_samples ? *valid_samples : std::vector<long long>());
+  }
+}
+
+// ------------------------------------------- full-length beam search ---
+
+void Engine::ensure_beam_full_workspace() {
+  if (bf_.h_done) return;  // (allocated last)
+  const wtw::Dims& c = dims_;
+  const size_t R = kDecRowsMax, d = c.n_text_state, V = c.n_vocab, C = kBeamClipsMax, S = kBeamMax;
+  const size_t cap = size_t(full_cap()), stride = cap + 1, chunks = size_t(beam_chunks(int(V)));
+  auto alloc = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, std::max<size_t>(bytes, 4)));
+    allocations_.push_back(p);
+    HIPCHK(hipMemset(p, 0, std::max<size_t>(bytes, 4)));
+    return p;
+  };
+  auto pinned = [&](size_t bytes) -> void* {
+    void* q = nullptr;
+    HIPCHK(hipHostMalloc(&q, bytes, 0));
+    return q;
+  };
+  bf_.kv = static_cast<float*>(alloc(size_t(c.n_text_layer) * 2 * R * cap * d * sizeof(float)));
+  for (int i = 0; i < 2; ++i) {
+    bf_.ids[i] = static_cast<long long*>(alloc(R * stride * sizeof(long long)));
+    bf_.lp[i] = static_cast<float*>(alloc(R * stride * sizeof(float)));
+    bf_.anc[i] = static_cast<unsigned char*>(alloc(R * cap));
+  }
+  bf_.ldl = int((V + 3) & ~size_t(3));
+  bf_.logits = static_cast<float*>(alloc(R * size_t(bf_.ldl) * sizeof(float)));
+  bf_.best = static_cast<unsigned long long*>(alloc(R * ((V + 31) / 32) * sizeof(unsigned long long)));
+  bf_.part = static_cast<BeamFullPart*>(alloc(R * chunks * sizeof(BeamFullPart)));
+  bf_.ts = static_cast<TsState*>(alloc(R * sizeof(TsState)));
+  bf_.n_live = static_cast<int*>(alloc(C * sizeof(int)));
+  bf_.live_sum = static_cast<double*>(alloc(C * S * sizeof(double)));
+  bf_.fin_tok = static_cast<int*>(alloc(C * S * stride * sizeof(int)));
+  bf_.fin_lp = static_cast<float*>(alloc(C * S * stride * sizeof(float)));
+  bf_.fin_sum = static_cast<double*>(alloc(C * S * sizeof(double)));
+  bf_.fin_len = static_cast<int*>(alloc(C * S * sizeof(int)));
+  bf_.n_fin = static_cast<int*>(alloc(C * sizeof(int)));
+  bf_.done = static_cast<int*>(alloc(C * sizeof(int)));
+  bf_.parent = static_cast<int*>(alloc(R * sizeof(int)));
+  bf_.token = static_cast<long long*>(alloc(R * sizeof(long long)));
+  bf_.tok_lp = static_cast<float*>(alloc(R * sizeof(float)));
+  bf_.out_ids = static_cast<long long*>(alloc(C * stride * sizeof(long long)));
+  bf_.out_lp = static_cast<float*>(alloc(C * stride * sizeof(float)));
+  bf_.out_n = static_cast<int*>(alloc(C * sizeof(int)));
+  bf_.out_len = static_cast<int*>(alloc(C * sizeof(int)));
+  bf_.out_sum = static_cast<double*>(alloc(C * sizeof(double)));
+  bf_.sc_part = static_cast<ScorePart*>(alloc(C * size_t(ts_chunks(int(V))) * sizeof(ScorePart)));
+  bf_.nosp = static_cast<float*>(alloc(C * sizeof(float)));
+  bf_.h_prompt = static_cast<long long*>(pinned(C * stride * sizeof(long long)));
+  bf_.h_ids = static_cast<long long*>(pinned(C * stride * sizeof(long long)));
+  bf_.h_lp = static_cast<float*>(pinned(C * stride * sizeof(float)));
+  bf_.h_nosp = static_cast<float*>(pinned(C * sizeof(float)));
+  bf_.h_sum = static_cast<double*>(pinned(C * sizeof(double)));
+  bf_.h_n = static_cast<int*>(pinned(C * sizeof(int)));
+  bf_.h_len = static_cast<int*>(pinned(C * sizeof(int)));
+  bf_.h_done = static_cast<int*>(pinned(C * sizeof(int)));
+}
+
+// Full-length beam search: decode_beam's chains — nc <= 128 / K clips, the prompt over nc rows, then
+// one position per pass over K * nc rows, row = k * nc + c — continued to P = max_positions in decode_full's segments of
+// 32 positions.  The hypotheses share ONE self-attention cache of 128 rows: the prompt's K / V land in rows c (the
+// clips' slot 0), every later pass writes row r's new position in place and reads the earlier ones through the row's
+// ancestor table (the gathered form of self_attention_long), so a step moves id, log-probability and table rows only.
+// Between the logits GEMM and the next pass: beam_full_partial, beam_full_select, beam_full_advance (k_beam_full.hip).
+// After each segment the clips' done flags come back and a chain ends once every clip is done.
+void Engine::decode_beam_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids) {
+  const int K = int(beam_size), P = int(max_positions), slot_idx = last_enc_slot_;
+  Slot& slot = slots_[slot_idx];
+  if (!slot.absorbed) throw Error(kErrUnsupported, "full-length beam search: the encoder pass did not prepare the absorbed cross-attention");
+  ensure_batch(batch);
+  ensure_beam_full_workspace();  // (before any capture: nothing may be allocated inside one)
+  const wtw::Dims& c = dims_;
+  const int d = c.n_text_state, T = c.n_audio_ctx, V = c.n_vocab, cap = full_cap(), stride = cap + 1;
+  const bool ts = timestamps != 0, sc = scores != 0;
+  const std::vector<long long> prompt = this->prompt();
+  const int n_prompt = int(prompt.size());
+  check_prompt_ids(prompt, kErrInvalidArg);
+  if (n_prompt >= P) throw Error(kErrInvalidArg, "full-length beam search: the prompt leaves no position to generate");
+  const int per_chain = kDecRowsMax / K, sot_idx = 0;  // Whisper's sot_index: the no-speech logits are read there
+  slot.dec = slot_idx % n_dec_streams_;
+  slot.pair_leader = -1;
+  DecWorkspace& dw = dws_[slot.dec];
+  hipStream_t const st = dec_stream_at(slot.dec);
+  for (int b = 0; b < kBeamClipsMax; ++b) {
+    for (int i = 0; i < stride; ++i) bf_.h_prompt[size_t(b) * stride + i] = i < n_prompt ? prompt[size_t(i)] : 0;
+  }
+  HIPCHK(hipStreamWaitEvent(st, slot.enc_done, 0));
+  HIPCHK(hipEventRecord(slot.dec_begin, st));
+  int steps = 0;
+  for (int c0 = 0; c0 < batch; c0 += per_chain) {
+    const int nc = std::min(per_chain, batch - c0), rows = K * nc;
+    const int n_abs = abs_chunks_for(nc, 256);
+    BeamFullArgs fa;
+    fa.clips = nc; fa.K = K; fa.c0 = c0; fa.n_prompt = n_prompt; fa.pos = n_prompt - 1; fa.V = V; fa.ldl = bf_.ldl;
+    fa.stride = stride; fa.cap = cap; fa.eot = vocab_.token_eot; fa.beg = vocab_.token_beg;
+    fa.max_initial = int(max_initial_timestamp); fa.timestamps = ts ? 1 : 0;
+    fa.logits = bf_.logits; fa.part = bf_.part; fa.ts = bf_.ts; fa.n_live = bf_.n_live; fa.live_sum = bf_.live_sum;
+    fa.fin_tok = bf_.fin_tok; fa.fin_lp = bf_.fin_lp; fa.fin_sum = bf_.fin_sum; fa.fin_len = bf_.fin_len; fa.n_fin = bf_.n_fin;
+    fa.done = bf_.done; fa.parent = bf_.parent; fa.token = bf_.token; fa.tok_lp = bf_.tok_lp;
+    fa.out_ids = bf_.out_ids; fa.out_lp = bf_.out_lp; fa.out_n = bf_.out_n; fa.out_len = bf_.out_len; fa.out_sum = bf_.out_sum;
+    // step t = pos + 1 - n_prompt reads the half t & 1 of the double buffers and writes the other
+    auto halves = [&](int t) {
+      const int cur = t & 1;
+      fa.ids_src = bf_.ids[cur]; fa.ids_dst = bf_.ids[cur ^ 1]; fa.lp_src = bf_.lp[cur]; fa.lp_dst = bf_.lp[cur ^ 1];
+      fa.anc_src = bf_.anc[cur]; fa.anc_dst = bf_.anc[cur ^ 1];
+    };
+    DecPass p;
+    p.clips = nc; p.ids_stride = stride; p.self_kv = bf_.kv; p.self_cap = cap; p.self_rows = kDecRowsMax;
+    p.absorbed = true; p.n_abs = n_abs; p.e = slot.e_planes + size_t(c0) * T * d; p.split = fc2_split(); p.dw = &dw;
+    p.Y = bf_.logits; p.ldy = bf_.ldl;
+    ScoreArgs sa;
+    sa.logits = bf_.logits; sa.ldl = bf_.ldl; sa.V = V; sa.batch = nc; sa.part = bf_.sc_part;
+    const int np_max = std::max(1, std::min(4, kDecRowsMax / nc));
+    // the passes whose first position lies in [lo, hi), each with its step; returns the steps among them
+    auto enqueue_segment = [&](int lo, int hi) {
+      int seg_steps = 0;
+      for (int pos0 = 0, np = 1; pos0 < hi; pos0 += np) {
+        np = pos0 < n_prompt ? std::min(np_max, n_prompt - pos0) : 1;
+        if (sc && pos0 <= sot_idx) np = std::min(np, sot_idx - pos0 + 1);  // a pass ends at sot, with logits: the no-speech probability
+        if (pos0 < lo) continue;
+        const int last = pos0 + np - 1, t = last + 1 - n_prompt;
+        const bool logits = t >= 0, nosp = sc && last == sot_idx;
+        if (pos0 < n_prompt) {  // the prompt: nc rows, their K / V into rows c of the shared cache
+          p.B = nc; p.ids = bf_.ids[0]; p.self_anc = nullptr;
+        } else {  // the id the step before chose, over the K * nc rows that step wrote
+          p.B = rows; p.ids = bf_.ids[t & 1]; p.self_anc = bf_.anc[t & 1];
+        }
+        p.pos0 = pos0; p.np = np; p.best = logits || nosp ? bf_.best : nullptr;
+        decoder_pass(p, st);
+        if (nosp) launch_no_speech_prob(sa, vocab_.token_solm, bf_.nosp + c0, st);
+        if (logits) {
+          fa.pos = last;
+          halves(t);
+          launch_beam_full_partial(fa, st);
+          launch_beam_full_select(fa, st);
+          launch_beam_full_advance(fa, st);
+          ++seg_steps;
+        }
+      }
+      return seg_steps;
+    };
+    HIPCHK(hipMemcpyAsync(bf_.ids[0], bf_.h_prompt, size_t(nc) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
+    halves(1);  // (begin writes the prompt's table entries into the half step 0 reads)
+    launch_beam_full_begin(fa, st);
+    int end = P;  // the position behind the last pass that ran
+    for (int lo = 0; lo < P; lo += 32) {
+      const int hi = std::min(P, lo + 32);
+      // (greedy's keys start with the slot, a beam key with -beam_size, a full-length key with kFullKey)
+      const std::vector<long long> key{kBeamFullKey, slot_idx, c0, nc, lo, P, n_prompt, K, fc2_ksplit, n_abs, slot.dec, ts ? 1 : 0,
+                                       ts ? max_initial_timestamp : 0, sc ? 1 : 0};
+      auto it = use_graphs ? graphs_.find(key) : graphs_.end();
+      if (it != graphs_.end()) {
+        HIPCHK(hipGraphLaunch(it->second.exec, st));
+        steps += it->second.steps;
+      } else {
+        const int seg_steps = enqueue_segment(lo, hi);  // eager the first time, then captured for the next calls
+        steps += seg_steps;
+        if (use_graphs) {
+          try {
+            graphs_.emplace(key, GraphEntry{capture_graph(st, [&] { enqueue_segment(lo, hi); }), seg_steps});
+          } catch (const std::exception& e) {
+            (void)hipGetLastError();
+            use_graphs = 0;
+            std::fprintf(stderr, "[wt] full-length beam hipGraph capture failed (%s): continuing with eager launches\n", e.what());
+          }
+        }
+      }
+      if (hi == P) break;
+      // every clip done: the remaining segments would change nothing
+      HIPCHK(hipMemcpyAsync(bf_.h_done, bf_.done + c0, size_t(nc) * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      bool all = true;
+      for (int b = 0; b < nc; ++b) all = all && bf_.h_done[b] != 0;
+      if (all) {
+        end = hi;
+        break;
+      }
+    }
+    fa.pos = end - 1;  // the last step that ran; its advance wrote the half the NEXT step would read
+    halves(end - n_prompt + 1);
+    launch_beam_full_finalize(fa, st);
+  }
+  HIPCHK(hipMemcpyAsync(bf_.h_ids, bf_.out_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(bf_.h_lp, bf_.out_lp, size_t(batch) * stride * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(bf_.h_n, bf_.out_n, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(bf_.h_len, bf_.out_len, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(bf_.h_sum, bf_.out_sum, size_t(batch) * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (sc) HIPCHK(hipMemcpyAsync(bf_.h_nosp, bf_.nosp, size_t(batch) * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord(slot.dec_done, st));
+  slot.steps = steps;
+  finish_slot(slot_idx);  // waits; the encoder's non-finite flag, timings
+  beam_sum.assign(size_t(batch), 0.0f);
+  beam_len.assign(bf_.h_len, bf_.h_len + batch);
+  for (int b = 0; b < batch; ++b) beam_sum[size_t(b)] = float(bf_.h_sum[b]);
+  beam_scores_valid = true;
+  if (sc) {
+    last_scores.assign(size_t(batch), ClipScore{});
+    last_lp_stride = stride;
+    last_token_logprob.assign(size_t(batch) * stride, 0.0f);
+    for (int b = 0; b < batch; ++b) {
+      ClipScore& s = last_scores[size_t(b)];
+      if (bf_.h_len[b] < 1) throw Error(kErrDevice, "scores: a clip came back with no generated id counted");
+      s.n_generated = bf_.h_len[b];
+      s.sum_logprob = float(bf_.h_sum[b]);
+      s.avg_logprob = float(bf_.h_sum[b] / double(s.n_generated));
+      s.no_speech_prob = bf_.h_nosp[b];
+      s.skipped = skip_silence && double(s.no_speech_prob) > double(no_speech_threshold) / 1000.0 &&
+                  !(double(s.avg_logprob) > double(logprob_threshold) / 1000.0);
+      for (int i = n_prompt; i < std::min(bf_.h_n[b], stride); ++i) {
+        last_token_logprob[size_t(b) * stride + i] = bf_.h_lp[size_t(b) * stride + i];
+      }
+    }
+    last_segment_score.clear();
+    last_scores_valid = true;
+  }
+  for (int b = 0; b < batch; ++b) {
+    n_ids[b] = bf_.h_n[b];
+    for (int i = 0; i < ids_stride; ++i) {
+      ids[size_t(b) * ids_stride + i] = i < bf_.h_n[b] && i < stride ? bf_.h_ids[size_t(b) * stride + i] : 0;
+    }
+  }
+  if (ts) {
+    last_segments.clear();
+    last_segment_text.clear();
+    for (int b = 0; b < batch; ++b) {
+      if (sc && last_scores[size_t(b)].skipped) continue;  // a silent clip has no segments
+      const int64_t* const row = reinterpret_cast<const int64_t*>(bf_.h_ids + size_t(b) * stride);
+      const size_t first = last_segments.size();
+      parse_segments(vocab_, row, std::min(bf_.h_n[b], stride), n_prompt, b, &last_segments);
+      for (size_t i = first; i < last_segments.size(); ++i) {
+        bool missing = false;
+        last_segment_text.push_back(decode_tokens(vocab_, row + last_segments[i].id_begin, last_segments[i].id_count, false, &missing));
+        if (sc) {  // the mean log-probability of the segment's text ids
+          double sum = 0.0;
+          for (int k = 0; k < last_segments[i].id_count; ++k) sum += double(bf_.h_lp[size_t(b) * stride + last_segments[i].id_begin + k]);
+          last_segment_score.push_back(float(sum / double(std::max(last_segments[i].id_count, 1))));
+        }
+      }
+    }
+    last_segments_valid = true;
   }
 }
 

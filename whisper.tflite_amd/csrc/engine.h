@@ -21,6 +21,7 @@ struct TsPart;   // kernels.h
 struct TsState;
 
 struct BeamPart;  // kernels.h
+struct BeamFullPart;
 struct ScorePart;
 struct SamplePart;
 struct SampleParams;
@@ -205,6 +206,12 @@ class Engine {
   // valid_samples (word timestamps): the samples each clip holds before its zero padding; nullptr = full-length clips
   void decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids, const std::vector<long long>* valid_samples = nullptr);
   void encode_full(const float* d_mel, int batch);  // encode() into slot 0: the slot every full-length call uses
+  // Full-length beam search (decode_beam_full).  0: a full-length call with beam_size > 1 is refused.
+  // 1: beam_size 2..8 with max_positions runs the beam chain to P positions, with or without timestamps, scores and
+  // skip_silence; decode_full hands such a call over, so every full-length entry point honours the mode.  Scope:
+  // beam search's (check_beam_call) and full-length decoding's, and no temperature, context, seek, word timestamps or
+  // batched seeking (check_full_call).
+  long full_beam = 0;
   // Timestamp decoding.  1: the default prompt ends before <|notimestamps|> and decode_full applies
   // Whisper's timestamp rules on the device (k_timestamps.hip) in place of select_token.  Full-length greedy decoding
   // only: with the option set every decode call outside that scope is kErrUnsupported (check_timestamp_call; with
@@ -468,6 +475,31 @@ class Engine {
     int* h_len = nullptr;           // pinned [64]
   } bw_;
   void ensure_beam_workspace();
+  // the chain behind decode_full when beam_size > 1 and full_beam = 1: consecutive chains of <= 128 / beam_size clips
+  void decode_beam_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids);
+  struct BeamFullWorkspace {  // allocated on the first full-length beam call, sized for 128 rows and 64 clips
+    float* kv = nullptr;                         // ONE self-attention cache [layer][k|v][128][full_cap()][d]: K / V never move
+    long long* ids[2] = {nullptr, nullptr};      // id rows [128][full_cap() + 1], double-buffered
+    float* lp[2] = {nullptr, nullptr};           // their log-probabilities, likewise
+    unsigned char* anc[2] = {nullptr, nullptr};  // ancestor tables [128][full_cap()], likewise
+    float* logits = nullptr;                     // [128][ldl], rows 16-byte aligned
+    int ldl = 0;
+    unsigned long long* best = nullptr;          // the logits GEMM's argmax records (unused here, written anyway)
+    BeamFullPart* part = nullptr;                // [128][chunks]
+    TsState* ts = nullptr;                       // [128]
+    int *n_live = nullptr, *fin_tok = nullptr, *fin_len = nullptr, *n_fin = nullptr, *done = nullptr, *parent = nullptr;
+    double *live_sum = nullptr, *fin_sum = nullptr, *out_sum = nullptr;
+    float *fin_lp = nullptr, *tok_lp = nullptr, *out_lp = nullptr;
+    long long *token = nullptr, *out_ids = nullptr;
+    int *out_n = nullptr, *out_len = nullptr;
+    ScorePart* sc_part = nullptr;                // option scores: the no-speech probability's records [64][chunks]
+    float* nosp = nullptr;                       // [64]
+    long long *h_prompt = nullptr, *h_ids = nullptr;  // pinned: the prompt rows [64][stride], the results
+    float *h_lp = nullptr, *h_nosp = nullptr;
+    double* h_sum = nullptr;
+    int *h_n = nullptr, *h_len = nullptr, *h_done = nullptr;
+  } bf_;
+  void ensure_beam_full_workspace();
   struct FullWorkspace {  // allocated on the first full-length call
     float* kv = nullptr;            // self-attention caches [layer][k|v][clip][full_cap()][d] for kv_clips clips
     int kv_clips = 0;               // the largest batch of a full-length call so far
@@ -510,6 +542,7 @@ class Engine {
   } aw_;
   static constexpr size_t kAlignWeightBytes = size_t(256) << 20;  // bound of the weight workspace: clips go through in sub-groups
   static constexpr long long kFullKey = -1000;  // first entry of a full-length segment's graph key
+  static constexpr long long kBeamFullKey = -2000;  // ... and of a full-length beam segment's
 
   int enc_cus_masked_ = 0;  // CUs the pipelined encoder stream may use
  public:
@@ -639,6 +672,10 @@ class Engine {
     int ids_stride = 32, self_cap = 32;
     bool self_long = false;  // self_attention_long (np = 1, any position below self_cap) instead of self_attention
     bool self_prefill = false;  // self_attention_prefill (np >= 1: a prompt behind a context) instead of either
+    // full-length beam search: the cache holds self_rows >= B rows per slab (0: B), and with self_anc set every pass runs
+    // the gathered form of self_attention_long over the B rows (np = 1), row r reading key k from row self_anc[r][k]
+    int self_rows = 0;
+    const unsigned char* self_anc = nullptr;
     // ragged chain: pos0 counts slots, sequence b is at Whisper position slot - pos_start[b] (device [B]) and may feed
     // positions [0, pos_limit); the embedding and the ragged self-attention kernels take both (self_prefill or the long form)
     const int* pos_start = nullptr;

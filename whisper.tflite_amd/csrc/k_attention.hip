@@ -560,11 +560,17 @@ __global__ void self_attention_step(const float* __restrict__ qkv, void* __restr
 // RAGGED: `pos` counts slots and clip b is at Whisper position pos - start[b]; everything below
 // runs at that position, so a clip's sums are the unragged kernel's there.  A clip whose position lies outside
 // [0, min(P, cap)) is void: its blocks write zeros to `out` and touch no cache row.
-template <bool RAGGED>
+// GATHER: the `rows` <= kSelfGatherRows rows of a beam chain share one cache.  Key k < pos of row b
+// is read from cache row min(anc[b][k], rows - 1) — the row that held b's ancestor when position k was written —
+// and key pos goes to row b itself as above, so no K/V ever moves between rows.  anc[b][0 .. pos) is staged in LDS
+// before the first load round (one more round trip per launch, not per round); a key is still one 256-byte segment
+// and the order of every sum is the ungathered kernel's: with anc[b][k] = b the two are bit-identical.
+template <bool RAGGED, bool GATHER>
 __global__ __launch_bounds__(256) void self_attention_long(const float* __restrict__ qkv, float* __restrict__ kcache,
                                                            float* __restrict__ vcache, int cap, int pos,
                                                            float* __restrict__ out, int heads,
-                                                           const int* __restrict__ start, int P) {
+                                                           const int* __restrict__ start, int P,
+                                                           const unsigned char* __restrict__ anc, int rows) {
   constexpr int NG = 16, U = 4;  // key rows per load round, rounds in flight
   if (RAGGED) {
     const int bb = blockIdx.x / heads;
@@ -589,13 +595,25 @@ __global__ __launch_bounds__(256) void self_attention_long(const float* __restri
   const int last_old = pos > 0 ? pos - 1 : 0;  // where the loads of keys >= pos go instead (their values are dropped)
   const float* kb = kc + gl16 * 4;
   const float* vb = vc + gl16 * 4;
+  __shared__ unsigned char ancs[GATHER ? kSelfLongCap : 1];
+  long hop = 0;  // GATHER: floats from one cache row to the next
+  if (GATHER) {
+    for (int k = tid; k < pos; k += 256) ancs[k] = anc[(long)b * cap + k];
+    __syncthreads();
+    hop = (long)cap * d;
+    kb -= b * hop;  // row 0
+    vb -= b * hop;
+  }
+  // GATHER: floats from row 0 to the row that holds key kk (kk = pos only at pos = 0: the block's own row, value dropped)
+  auto src = [&](int kk) -> long { return (kk < pos ? min((int)ancs[kk], rows - 1) : b) * hop; };
   f32x4 kv[U], vv[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {  // the first 64 keys are requested before the new row is staged
     const int k = grp + NG * u;
     const int kk = k < pos ? k : last_old;
-    kv[u] = *reinterpret_cast<const f32x4*>(kb + (long)kk * d);
-    vv[u] = *reinterpret_cast<const f32x4*>(vb + (long)kk * d);
+    const long at = (long)kk * d + (GATHER ? src(kk) : 0);
+    kv[u] = *reinterpret_cast<const f32x4*>(kb + at);
+    vv[u] = *reinterpret_cast<const f32x4*>(vb + at);
   }
   constexpr float kScale = 0.125f * 1.44269504088896340736f;
   if (tid < 64) {
@@ -619,8 +637,9 @@ __global__ __launch_bounds__(256) void self_attention_long(const float* __restri
       for (int u = 0; u < U; ++u) {
         const int k = k0 + NG * u;
         const int kk = k < pos ? k : last_old;
-        kv[u] = *reinterpret_cast<const f32x4*>(kb + (long)kk * d);
-        vv[u] = *reinterpret_cast<const f32x4*>(vb + (long)kk * d);
+        const long at = (long)kk * d + (GATHER ? src(kk) : 0);
+        kv[u] = *reinterpret_cast<const f32x4*>(kb + at);
+        vv[u] = *reinterpret_cast<const f32x4*>(vb + at);
       }
     }
 #pragma unroll
@@ -1037,8 +1056,22 @@ void check_self_attention_long(int cap, int pos, int batch, int heads) {
 void launch_self_attention_long(const float* qkv, float* kcache, float* vcache, int cap, int pos, float* out, int batch,
                                 int heads, hipStream_t s) {
   check_self_attention_long(cap, pos, batch, heads);
-  hipLaunchKernelGGL(self_attention_long<false>, dim3(batch * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out, heads,
-                     static_cast<const int*>(nullptr), 0);
+  hipLaunchKernelGGL((self_attention_long<false, false>), dim3(batch * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out,
+                     heads, static_cast<const int*>(nullptr), 0, static_cast<const unsigned char*>(nullptr), 0);
+}
+
+// The gathered form: the ungathered refusals, plus the row limit (a table entry is one byte) and the table.
+void check_self_attention_long_gather(int cap, int pos, int rows, int heads) {
+  check_self_attention_long(cap, pos, rows, heads);
+  if (rows > kSelfGatherRows) throw Error(kErrInvalidArg, "decoder self-attention (long cache, gathered): rows outside [1, 128]");
+}
+
+void launch_self_attention_long_gather(const float* qkv, float* kcache, float* vcache, int cap, int pos,
+                                       const unsigned char* anc, float* out, int rows, int heads, hipStream_t s) {
+  check_self_attention_long_gather(cap, pos, rows, heads);
+  if (!anc) throw Error(kErrInvalidArg, "decoder self-attention (long cache, gathered): no ancestor table");
+  hipLaunchKernelGGL((self_attention_long<false, true>), dim3(rows * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out,
+                     heads, static_cast<const int*>(nullptr), 0, anc, rows);
 }
 
 void check_self_attention_prefill(int cap, int pos0, int np, int batch, int heads) {
@@ -1068,8 +1101,8 @@ void launch_self_attention_long_ragged(const float* qkv, float* kcache, float* v
                                        int P, float* out, int batch, int heads, hipStream_t s) {
   check_self_attention_long_ragged(cap, pos, P, batch, heads);
   if (!start) throw Error(kErrInvalidArg, "decoder self-attention (long cache, ragged): no start array");
-  hipLaunchKernelGGL(self_attention_long<true>, dim3(batch * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out, heads,
-                     start, P);
+  hipLaunchKernelGGL((self_attention_long<true, false>), dim3(batch * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out,
+                     heads, start, P, static_cast<const unsigned char*>(nullptr), 0);
 }
 
 void check_self_attention_prefill_ragged(int cap, int pos0, int np, int P, int batch, int heads) {

@@ -293,6 +293,15 @@ void launch_self_attention_long_ragged(const float* qkv, float* kcache, float* v
 void check_self_attention_prefill_ragged(int cap, int pos0, int np, int P, int batch, int heads);
 void launch_self_attention_prefill_ragged(const float* qkv, float* kcache, float* vcache, int cap, int pos0, int np,
                                           const int* start, int P, float* out, int batch, int heads, hipStream_t s);
+// The gathered form of self_attention_long: `rows` <= kSelfGatherRows rows share the cache
+// [rows][cap][d], and row r reads key k < pos from cache row min(anc[r][k], rows - 1) (anc: device [rows][cap] bytes;
+// entries at k >= pos are not read).  Key pos is appended to row r itself and out rows are r, as above; with
+// anc[r][k] = r output and cache are bit-identical to launch_self_attention_long's.  Refused: what
+// check_self_attention_long refuses, rows > kSelfGatherRows and a null table.
+constexpr int kSelfGatherRows = 128;  // rows of one decoder pass; a table entry is one byte
+void check_self_attention_long_gather(int cap, int pos, int rows, int heads);
+void launch_self_attention_long_gather(const float* qkv, float* kcache, float* vcache, int cap, int pos,
+                                       const unsigned char* anc, float* out, int rows, int heads, hipStream_t s);
 // Cross attention of nq (1..4) query rows per clip over T cached keys, the query projection included:
 // q = LayerNorm(x[row]) . Wq^T + bq with x the residual stream [nq * B][d], rows p * B + b.  wq_t = Wq in the
 // layout of cross_q_layout(); kc, vc [B][heads][T][64]; partial results per key chunk in ws
@@ -518,6 +527,60 @@ void launch_score_partial(const ScoreArgs& a, hipStream_t s);  // throws kErrInv
 void launch_score_finish(const ScoreArgs& a, hipStream_t s);   // reads the records launch_score_partial wrote
 // prob[b] = exp(z[b][nosp] - logsumexp(z[b][0 .. V - 1])): score_partial over the whole row + a finish kernel
 void launch_no_speech_prob(const ScoreArgs& a, int nosp, float* prob, hipStream_t s);
+
+// ------------------------------------------------- full-length beam search ---
+// k_beam_full.hip (option full_beam): beam search over up to full_cap() positions behind the timestamp
+// rules.  Rows are laid out row = k * clips + c as in k_beam.hip; a row's ids [stride] int64, its log-probabilities
+// [stride] float (index = position of the id) and its ancestor table [cap] bytes (launch_self_attention_long_gather) live
+// in two halves of a double buffer: a step reads the live hypotheses from `src` and writes the next ones to `dst`.  No
+// K / V moves.  Per step every live hypothesis applies its OWN allowed set A (the whole vocabulary, or rules 1 .. 5 of
+// section 14 on its TsState), lp = z - logsumexp_A(z) in float64 from fp32 chunk sums merged in chunk order, and offers
+// its top K+1 ids of A (a logit of -inf is never in A); beam_select's walk follows.  The number of live hypotheses of a
+// clip is state: a walk that finds fewer than K non-EOT candidates leaves fewer, and a clip with none is done.
+struct BeamFullPart {                // one (row, chunk of kBeamChunk entries); keys as BeamPart's
+  float mt, st, ms, ss;              // max and sum of exp(logit - max) of the allowed text ids / the allowed timestamps
+  unsigned long long kt[kBeamMax + 1], ks[kBeamMax + 1];  // their top K+1 keys, 0 = none
+};
+struct BeamFullArgs {
+  int clips = 0, K = 0, c0 = 0;      // clips of the chain, beam size, the chain's first clip in the per-clip state
+  int pos = 0, n_prompt = 0;         // the position the logits belong to; step t = pos + 1 - n_prompt has clips live rows
+  int V = 0, ldl = 0, stride = 0, cap = 0;  // at t = 0 and K * clips afterwards; pos < cap < stride
+  int eot = 0, beg = 0, max_initial = -1, timestamps = 0;
+  const float* logits = nullptr;     // [live rows][ldl]
+  BeamFullPart* part = nullptr;      // [live rows][beam_chunks(V)]
+  const long long* ids_src = nullptr;
+  long long* ids_dst = nullptr;
+  const float* lp_src = nullptr;
+  float* lp_dst = nullptr;
+  const unsigned char* anc_src = nullptr;
+  unsigned char* anc_dst = nullptr;
+  TsState* ts = nullptr;             // [K * clips] per row, read and advanced in place
+  // per-clip state, indexed by c0 + clip: [kBeamClipsMax] or [kBeamClipsMax][kBeamMax] (fin_tok / fin_lp: [..][stride],
+  // the generated ids of a finished hypothesis and their log-probabilities)
+  int* n_live = nullptr;
+  double* live_sum = nullptr;
+  int* fin_tok = nullptr;
+  float* fin_lp = nullptr;
+  double* fin_sum = nullptr;
+  int *fin_len = nullptr, *n_fin = nullptr, *done = nullptr;
+  int* parent = nullptr;             // [K * clips]: the row each new row continues, its id at pos + 1 and that id's lp
+  long long* token = nullptr;
+  float* tok_lp = nullptr;
+  double* dbg_lse = nullptr;         // optional [live rows]: logsumexp_A of the live rows (NaN where A is empty)
+  // launch_beam_full_finalize only: the chosen hypothesis per clip, indexed by c0 + clip
+  long long* out_ids = nullptr;      // [kBeamClipsMax][stride]: prompt + generated ids
+  float* out_lp = nullptr;           // [kBeamClipsMax][stride]
+  int *out_n = nullptr, *out_len = nullptr;
+  double* out_sum = nullptr;
+};
+// Every launcher throws kErrInvalidArg for a shape outside: K in [2, 8], K * clips <= 128, c0 + clips <= 64,
+// 1 <= n_prompt <= pos + 1, pos < cap <= kSelfLongCap, cap < stride, V <= ldl, beam_chunks(V) <= kBeamMaxChunks and,
+// with timestamps, 0 <= eot < beg < V.
+void launch_beam_full_begin(const BeamFullArgs& a, hipStream_t s);     // a chain's start: state of the clips, rows c of dst
+void launch_beam_full_partial(const BeamFullArgs& a, hipStream_t s);
+void launch_beam_full_select(const BeamFullArgs& a, hipStream_t s);
+void launch_beam_full_advance(const BeamFullArgs& a, hipStream_t s);
+void launch_beam_full_finalize(const BeamFullArgs& a, hipStream_t s);  // src = the rows after the last step's advance
 
 // ------------------------------------------------------------- alignment ---
 // k_align.hip (word-level timestamps): from the cross-attention weights W of a teacher-forced pass
