@@ -72,7 +72,25 @@ int wt_dbg_encoder_attention(wt_engine* h, int batch, int T, int heads, const fl
 int wt_dbg_cross_attention(wt_engine* h, int batch, int heads, int T, int chunks, int nq, const float* x,
                            const float* ln_g, const float* ln_b, const float* wq, const float* bq, const float* kc,
                            const float* vc, float* out);
-/* qkv [npos*B][3d] (row = p * B + b); caches [B][cap][d] updated in place at rows pos .. pos+npos-1; out [npos*B][d] */
+/* launch_cross_attention ALONE, positions row0 .. row0 + n_rows - 1 of a buffer of nq positions (nq * batch <= 128): the
+ * arguments of wt_dbg_cross_attention, x [nq * batch][d] whole; ws [nq * batch][heads][chunks][68] (o[64], m, l, pad per
+ * record) is in / out: uploaded as given, written by the one launch at the rows of its positions (addressed as the
+ * engine's position loop addresses them) and downloaded whole, so that every record the launch does not own comes back
+ * as given.  What the launcher refuses (batch, heads or T below 1, chunks outside [1, T], n_rows outside [1, 4]:
+ * WT_ERR_INVALID_ARG; a d = 64 heads other than 128, 384, 512: WT_ERR_FORMAT) is refused before anything is allocated
+ * or launched, and so are a NULL array and positions outside the buffer (WT_ERR_INVALID_ARG). */
+int wt_dbg_cross_attention_records(wt_engine* h, int batch, int heads, int T, int chunks, int nq, const float* x,
+                                   const float* ln_g, const float* ln_b, const float* wq, const float* bq, const float* kc,
+                                   const float* vc, int row0, int n_rows, float* ws);
+/* the kProCombine prologue of dec_gemm alone, on given records [M][heads][chunks][68]: Y = R + bias + combine(records) . W^T
+ * through launch_dec_gemm(kProCombine, kDecResid) with R aliasing Y, as in the engine; W [d][d], bias [d], R [M][d],
+ * d = 64 heads, M = positions x B rows (M <= 128, M % B == 0), chunks in {1, 2, 4, 8}.  Y [M + guard_rows][d] is in / out:
+ * rows < M are set to R before the launch, rows >= M are uploaded as given, and all come back. */
+int wt_dbg_cross_combine(wt_engine* h, int M, int B, int heads, int chunks, const float* records, const float* W,
+                         const float* bias, const float* R, int guard_rows, float* Y);
+/* decoder self attention (self_attention_step): qkv [npos*B][3d] (row = p * B + b); caches [B][cap][d], cap <= 448,
+ * updated in place at rows pos .. pos+npos-1; out [npos*B][d].  pos < 0, npos < 1, pos + npos > 32, pos + npos > cap, cap
+ * outside [1, 448] and a batch or head count below 1 are WT_ERR_INVALID_ARG, before anything is launched. */
 /* absorbed cross-attention (k_cross_absorbed.hip) + chunk combine with the heads' value projections: qp [nq * batch]
  * [heads * d] absorbed queries (log2 domain), E [batch][T][d] encoder output (split into planes on the host), wv [d][d],
  * bv [d]; out [nq * batch][d]: out[r][64 h + j] = Wv[64 h + j] . (sum_k softmax2_k(qp_h . e_k) e_k) + bv[64 h + j];
@@ -193,6 +211,11 @@ int wt_dbg_self_attention_bf16(wt_engine* h, int batch, int heads, int cap, int 
 int wt_dbg_cross_attention_bf16(wt_engine* h, int batch, int heads, int T, int chunks, int nq, const float* x,
                                 const float* ln_g, const float* ln_b, const float* wq, const float* bq, const float* kc,
                                 const float* vc, float* out);
+int wt_dbg_cross_attention_records_bf16(wt_engine* h, int batch, int heads, int T, int chunks, int nq, const float* x,
+                                        const float* ln_g, const float* ln_b, const float* wq, const float* bq, const float* kc,
+                                        const float* vc, int row0, int n_rows, float* ws);
+int wt_dbg_cross_combine_bf16(wt_engine* h, int M, int B, int heads, int chunks, const float* records, const float* W,
+                              const float* bias, const float* R, int guard_rows, float* Y);
 /* beam search (k_beam.hip).  Rows are laid out row = k * clips + c; the per-clip state is the
  * engine's: live_sum / fin_sum / fin_len [64][8], fin_tok [64][8][32], n_fin / done [64], indexed by c0 + clip, all
  * in / out.  A shape the launcher refuses is WT_ERR_INVALID_ARG. */

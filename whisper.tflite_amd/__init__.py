@@ -70,6 +70,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
     "wt_dbg_pcm_to_planes",
     "wt_dbg_gemm_addressed", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes", "wt_dbg_encoder_attention_at",
+    "wt_dbg_cross_attention_records", "wt_dbg_cross_attention_records_bf16", "wt_dbg_cross_combine", "wt_dbg_cross_combine_bf16",
     "wt_dbg_align_scores", "wt_dbg_align_matrix", "wt_dbg_align_dtw", "wt_dbg_last_alignment", "wt_dbg_set_alignment",
 ]
 
@@ -219,6 +220,11 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_self_attention.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp]
         L.wt_dbg_self_attention_bf16.argtypes = L.wt_dbg_self_attention.argtypes
         L.wt_dbg_cross_attention_bf16.argtypes = L.wt_dbg_cross_attention.argtypes
+        L.wt_dbg_cross_attention_records.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp, fp, fp, fp,
+                                                     c_int, c_int, fp]
+        L.wt_dbg_cross_attention_records_bf16.argtypes = L.wt_dbg_cross_attention_records.argtypes
+        L.wt_dbg_cross_combine.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp, c_int, fp]
+        L.wt_dbg_cross_combine_bf16.argtypes = L.wt_dbg_cross_combine.argtypes
         u64p = POINTER(c_uint64)
         L.wt_dbg_beam_topk.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, u64p]
         L.wt_dbg_beam_step.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, fp, ip64, fp, ip32,
@@ -1097,12 +1103,39 @@ class Engine:
         self._check(fn(self._h, B, H, T, chunks, nq, _fp(x), _fp(ln_g), _fp(ln_b), _fp(wq), _fp(bq), _fp(kc), _fp(vc), _fp(out)))
         return out
 
-    def dbg_self_attention(self, qkv, kcache, vcache, pos, npos=1, bf16=False):
+    def dbg_cross_attention_records(self, x, ln_g, ln_b, wq, bq, kc, vc, chunks=2, nq=1, bf16=False, row0=0, n_rows=None,
+                                    guard=None, batch=None, heads=None):
+        """launch_cross_attention alone: the per-chunk records ws [nq*B][H][chunks][68] (o[64], m, l, pad).  The buffer is
+        `guard` as given (default: all 1e30) and ONE launch writes the records of positions row0 .. row0 + n_rows - 1
+        (default: all nq).  batch / heads override the counts taken from kc's shape (refusal tests)."""
+        x, ln_g, ln_b, wq, bq, kc, vc = (_f32(a) for a in (x, ln_g, ln_b, wq, bq, kc, vc))
+        B, H, T, _ = kc.shape
+        ws = np.full((max(nq, 1) * B, H, max(chunks, 1), 68), 1e30, np.float32) if guard is None else _f32(guard).copy()
+        fn = lib().wt_dbg_cross_attention_records_bf16 if bf16 else lib().wt_dbg_cross_attention_records
+        self._check(fn(self._h, B if batch is None else batch, H if heads is None else heads, T, chunks, nq, _fp(x), _fp(ln_g),
+                       _fp(ln_b), _fp(wq), _fp(bq), _fp(kc), _fp(vc), row0, nq if n_rows is None else n_rows, _fp(ws)))
+        return ws
+
+    def dbg_cross_combine(self, records, W, bias, R, B, bf16=False, guard=None):
+        """dec_gemm's kProCombine prologue on given records [M][H][chunks][68]: Y = R + bias + combine(records) . W^T with
+        R in place; guard [n][d] = rows behind the M of Y the kernel must not write.  Returns Y [M + n][d]."""
+        records, W, bias, R = _f32(records), _f32(W), _f32(bias), _f32(R)
+        M, H, chunks, _ = records.shape
+        d = H * 64
+        guard = np.zeros((0, d), np.float32) if guard is None else _f32(guard)
+        Y = np.ascontiguousarray(np.concatenate([np.zeros((M, d), np.float32), guard]))
+        fn = lib().wt_dbg_cross_combine_bf16 if bf16 else lib().wt_dbg_cross_combine
+        self._check(fn(self._h, M, B, H, chunks, _fp(records), _fp(W), _fp(bias), _fp(R), guard.shape[0], _fp(Y)))
+        return Y
+
+    def dbg_self_attention(self, qkv, kcache, vcache, pos, npos=1, bf16=False, batch=None, heads=None):
+        """batch / heads override the counts taken from the cache's shape (refusal tests)."""
         qkv, kcache, vcache = _f32(qkv), _f32(kcache).copy(), _f32(vcache).copy()
         B, cap, d = kcache.shape
-        out = np.zeros((npos * B, d), np.float32)
+        out = np.zeros((npos * B if npos > 0 else 0, d), np.float32)
         fn = lib().wt_dbg_self_attention_bf16 if bf16 else lib().wt_dbg_self_attention
-        self._check(fn(self._h, B, d // 64, cap, pos, npos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
+        self._check(fn(self._h, B if batch is None else batch, d // 64 if heads is None else heads, cap, pos, npos, _fp(qkv),
+                       _fp(kcache), _fp(vcache), _fp(out)))
         return out, kcache, vcache
 
     def dbg_timestamp_select(self, logits, ids, n_ids, sample_begin, eot, beg, max_initial_timestamp=50):

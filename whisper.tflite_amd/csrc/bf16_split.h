@@ -99,10 +99,16 @@ __device__ __forceinline__ void split_f16x2(float a, float b, unsigned* hi, unsi
 }
 
 // bf16 storage mode: two fp32 values -> one packed dword of bf16 (a in bits 0-15), round to nearest even in hardware
+// (one v_cvt_pk_bf16_f32).  A conversion the compiler sees, NOT inline asm: an MFMA that reads the dword as an operand
+// needs two wait states behind the VALU write, and the hazard recognizer pads only instructions it knows.  With the asm
+// form dec_gemm<kProCombine, .., CH = 8, GT = 2, BF> issued the MFMA of its second row tile one state behind the pack
+// of elements 2 | 3 of its first k-step; whenever the loads in front had already landed (a last tile of one row, whose
+// clamped lanes all hit one cached record) the MFMA took the register's previous contents
+// (tests/test_gpu_decoder_attention.py, C1 at M = 33 and 97).
 __device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, bf16x2_t));
 }
 __device__ __forceinline__ float bf16_lo(unsigned packed) { return __uint_as_float(packed << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned packed) { return __uint_as_float(packed & 0xFFFF0000u); }

@@ -198,6 +198,13 @@ std::vector<float> scale_qkv(const float* qkv, size_t rows, size_t d, float sq, 
   return scaled;
 }
 
+// launch_cross_attention's own refusals for a shape, before a tap sizes or allocates anything from it
+void check_cross_shape(int batch, int heads, int T, int chunks, int nq) {
+  wt::CrossAttnArgs ca;
+  ca.batch = batch; ca.heads = heads; ca.T = T; ca.chunks = chunks; ca.nq = nq;
+  wt::check_cross_attention(ca);
+}
+
 // --- what the timestamp, sample and score taps share ---
 // logits [B][V] -> rows of ldl floats (V rounded up to a multiple of 4), zero padded
 std::vector<float> pad_logits(const float* logits, int B, int V, int ldl) {
@@ -606,6 +613,7 @@ static int dbg_cross_attention_impl(wt_engine* h, int batch, int heads, int T, i
       !x || !ln_g || !ln_b || !wq || !bq || !kc || !vc || !out)
     return WT_ERR_INVALID_ARG;
   return guarded(h, [&] {
+    check_cross_shape(batch, heads, T, chunks, nq);
     const size_t d = size_t(heads) * 64, rows = size_t(nq) * batch, nc = size_t(batch) * T * d;
     DevArr<float> dx(rows * d, x), dg(d, ln_g), db(d, ln_b), dbq(d, bq), dk(bf ? 0 : nc, kc), dv(bf ? 0 : nc, vc);
     const DevBf16 dkb(kc, bf ? nc : 0), dvb(vc, bf ? nc : 0);
@@ -645,6 +653,74 @@ int wt_dbg_cross_attention_bf16(wt_engine* h, int batch, int heads, int T, int c
   return dbg_cross_attention_impl(h, batch, heads, T, chunks, nq, x, ln_g, ln_b, wq, bq, kc, vc, out, true);
 }
 
+static int dbg_cross_records_impl(wt_engine* h, int batch, int heads, int T, int chunks, int nq, const float* x,
+                                  const float* ln_g, const float* ln_b, const float* wq, const float* bq, const float* kc,
+                                  const float* vc, int row0, int n_rows, float* ws, bool bf) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    check_cross_shape(batch, heads, T, chunks, n_rows);  // the launcher's own refusals, before anything is allocated
+    if (!x || !ln_g || !ln_b || !wq || !bq || !kc || !vc || !ws || row0 < 0 || nq < 1 || nq > 128 / batch || row0 > nq - n_rows)
+      throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_cross_attention_records: NULL array or positions outside the buffer");
+    const size_t d = size_t(heads) * 64, rows = size_t(nq) * batch, nc = size_t(batch) * T * d;
+    const size_t rec = size_t(heads) * chunks * 68;  // floats per row of ws
+    DevArr<float> dx(rows * d, x), dg(d, ln_g), db(d, ln_b), dbq(d, bq), dk(bf ? 0 : nc, kc), dv(bf ? 0 : nc, vc);
+    const DevBf16 dkb(kc, bf ? nc : 0), dvb(vc, bf ? nc : 0);
+    DevArr<float> dwq(wt::cross_q_layout(wq, int(d)));
+    DevArr<float> dws(rows * rec, ws);  // the caller's guard pattern
+    wt::CrossAttnArgs ca;
+    ca.ln_g = dg.p; ca.ln_b = db.p; ca.wq_t = dwq.p; ca.bq = dbq.p;
+    ca.kc = bf ? static_cast<const void*>(dkb.ptr()) : dk.p; ca.vc = bf ? static_cast<const void*>(dvb.ptr()) : dv.p; ca.bf16 = bf;
+    ca.batch = batch; ca.heads = heads; ca.T = T; ca.chunks = chunks;
+    // positions row0 .. row0 + n_rows - 1 of the buffer, addressed as Engine::decoder_pass's p0 loop addresses them
+    ca.x = dx.p + size_t(row0) * batch * d; ca.ws = dws.p + size_t(row0) * batch * rec; ca.nq = n_rows;
+    wt::launch_cross_attention(ca, h->impl->stream());
+    h->impl->sync();
+    dws.to_host(ws);
+  });
+}
+
+int wt_dbg_cross_attention_records(wt_engine* h, int batch, int heads, int T, int chunks, int nq, const float* x,
+                                   const float* ln_g, const float* ln_b, const float* wq, const float* bq, const float* kc,
+                                   const float* vc, int row0, int n_rows, float* ws) {
+  return dbg_cross_records_impl(h, batch, heads, T, chunks, nq, x, ln_g, ln_b, wq, bq, kc, vc, row0, n_rows, ws, false);
+}
+int wt_dbg_cross_attention_records_bf16(wt_engine* h, int batch, int heads, int T, int chunks, int nq, const float* x,
+                                        const float* ln_g, const float* ln_b, const float* wq, const float* bq, const float* kc,
+                                        const float* vc, int row0, int n_rows, float* ws) {
+  return dbg_cross_records_impl(h, batch, heads, T, chunks, nq, x, ln_g, ln_b, wq, bq, kc, vc, row0, n_rows, ws, true);
+}
+
+static int dbg_cross_combine_impl(wt_engine* h, int M, int B, int heads, int chunks, const float* records, const float* W,
+                                  const float* bias, const float* R, int guard_rows, float* Y, bool bf) {
+  if (!h || !records || !W || !bias || !R || !Y || M < 1 || M > 128 || B < 1 || heads < 1 || heads > 8 || chunks < 1 ||
+      chunks > 8 || guard_rows < 0 || guard_rows > 128)
+    return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    const size_t d = size_t(heads) * 64;
+    const DevTiled dW(W, int(d), int(d), bf);
+    DevArr<float> dws(size_t(M) * heads * chunks * 68, records), db(d, bias);
+    std::vector<float> y0(Y, Y + (size_t(M) + guard_rows) * d);  // rows >= M: the caller's guard pattern
+    std::copy(R, R + size_t(M) * d, y0.begin());
+    DevArr<float> dY(y0);
+    wt::DecGemmArgs g;
+    g.Wt = dW.w(); g.w_scale = dW.scale; g.N = int(d); g.K = int(d); g.B = B; g.M = M; g.bf16 = bf;
+    g.cross_ws = dws.p; g.heads = heads; g.chunks = chunks;
+    g.bias = db.p; g.R = dY.p; g.Y = dY.p; g.ldy = int(d);  // residual in place, as the engine does
+    wt::launch_dec_gemm(g, wt::kProCombine, wt::kDecResid, h->impl->stream());
+    h->impl->sync();
+    dY.to_host(Y);
+  });
+}
+
+int wt_dbg_cross_combine(wt_engine* h, int M, int B, int heads, int chunks, const float* records, const float* W,
+                         const float* bias, const float* R, int guard_rows, float* Y) {
+  return dbg_cross_combine_impl(h, M, B, heads, chunks, records, W, bias, R, guard_rows, Y, false);
+}
+int wt_dbg_cross_combine_bf16(wt_engine* h, int M, int B, int heads, int chunks, const float* records, const float* W,
+                              const float* bias, const float* R, int guard_rows, float* Y) {
+  return dbg_cross_combine_impl(h, M, B, heads, chunks, records, W, bias, R, guard_rows, Y, true);
+}
+
 static int dbg_cross_absorbed_impl(wt_engine* h, int batch, int heads, int T, int chunks, int nq, const float* qp, const float* E,
                                    const float* wv, const float* bv, float* out, int iters, float* avg_us, bool bf) {
   if (!h || !qp || !E || !wv || !bv || !out || batch < 1 || heads < 1 || T < 1 || nq < 1 || chunks < 1 || chunks > 16) return WT_ERR_INVALID_ARG;
@@ -682,8 +758,10 @@ int wt_dbg_cross_absorbed_bf16(wt_engine* h, int batch, int heads, int T, int ch
 
 static int dbg_self_attention_impl(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
                                    float* kcache, float* vcache, float* out, bool bf) {
-  if (!h || npos < 1 || pos < 0 || pos + npos > cap || cap > 64) return WT_ERR_INVALID_ARG;
+  if (!h || cap > wt::kSelfLongCap) return WT_ERR_INVALID_ARG;
   return guarded(h, [&] {
+    wt::check_self_attention(cap, pos, npos, batch, heads);  // the launcher's own refusals, before anything is allocated
+    if (!qkv || !kcache || !vcache || !out) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_self_attention: NULL array");
     const size_t d = size_t(heads) * 64, rows = size_t(npos) * batch, nc = size_t(batch) * cap * d;
     DevArr<float> dq(rows * 3 * d, qkv), dk(bf ? 0 : nc, kcache), dv(bf ? 0 : nc, vcache), dout(rows * d);
     const DevBf16 dkb(kcache, bf ? nc : 0), dvb(vcache, bf ? nc : 0);  // bf16 caches (storage mode)

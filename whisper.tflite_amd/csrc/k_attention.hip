@@ -1032,12 +1032,18 @@ void launch_encoder_attention(const float* qkv, float* out, int batch, int T, in
   }
 }
 
-void launch_self_attention(const float* qkv, void* kcache, void* vcache, int cap, int pos0, int npos, float* out,
-                           int batch, int heads, hipStream_t s, bool bf16) {
+void check_self_attention(int cap, int pos0, int npos, int batch, int heads) {
+  if (batch < 1 || heads < 1) throw Error(kErrInvalidArg, "decoder self-attention: no clips or no heads");
+  if (cap < 1) throw Error(kErrInvalidArg, "decoder self-attention: no cache rows");
   // the kernel stages at most 32 cached rows in LDS
-  if (pos0 < 0 || npos < 1 || pos0 + npos > 32 || pos0 + npos > cap) {
+  if (pos0 < 0 || npos < 1 || pos0 > 32 - npos || pos0 > cap - npos) {
     throw Error(kErrInvalidArg, "decoder self-attention: positions outside [0, 31]");
   }
+}
+
+void launch_self_attention(const float* qkv, void* kcache, void* vcache, int cap, int pos0, int npos, float* out,
+                           int batch, int heads, hipStream_t s, bool bf16) {
+  check_self_attention(cap, pos0, npos, batch, heads);
   if (bf16) {
     hipLaunchKernelGGL(self_attention_step<true>, dim3(batch * heads), dim3(64), 0, s, qkv, kcache, vcache, cap, pos0,
                        npos, batch, out, heads);
@@ -1141,8 +1147,14 @@ static void launch_cross_bf(const CrossAttnArgs& a, hipStream_t s) {
   }
 }
 
+void check_cross_attention(const CrossAttnArgs& a) {
+  if (a.batch < 1 || a.heads < 1 || a.T < 1 || a.chunks < 1 || a.chunks > a.T) throw Error(kErrInvalidArg, "cross attention: bad shape");
+  if (a.nq < 1 || a.nq > 4) throw Error(kErrInvalidArg, "cross attention: 1..4 query rows per clip");
+  if (a.heads != 2 && a.heads != 6 && a.heads != 8) throw Error(kErrFormat, "decoder kernels support d_model 128, 384 or 512");
+}
+
 void launch_cross_attention(const CrossAttnArgs& a, hipStream_t s) {
-  if (a.batch < 1 || a.T < 1 || a.chunks < 1 || a.chunks > a.T) throw Error(kErrInvalidArg, "cross attention: bad shape");
+  check_cross_attention(a);
   if (a.bf16) {
     launch_cross_bf<true>(a, s);
   } else {

@@ -263,6 +263,9 @@ void launch_mel_normalize(float* logmel, const unsigned* clip_max, int batch, in
 // Appends k, v of positions pos0 .. pos0 + npos - 1 (from qkv rows p * B + b, [.][3d]) to the self-attention
 // cache [2][B][cap][d] and attends each new position's q causally over positions 0 .. pos0 + p.  out rows likewise.
 // bf16: the cache holds bf16 elements (bf16 storage mode).
+// Throws kErrInvalidArg for pos0 < 0, npos < 1, pos0 + npos > 32 (the rows the kernel stages), pos0 + npos > cap, cap < 1,
+// batch < 1 or heads < 1 (check_self_attention), before anything is launched.
+void check_self_attention(int cap, int pos0, int npos, int batch, int heads);
 void launch_self_attention(const float* qkv, void* kcache, void* vcache, int cap, int pos0, int npos, float* out,
                            int batch, int heads, hipStream_t s, bool bf16 = false);
 // Full-length decoding (option max_positions): ONE new position `pos` (any in [0, cap); the engine uses it from 32 on)
@@ -314,6 +317,9 @@ struct CrossAttnArgs {
   int batch = 0, heads = 0, T = 0, chunks = 1, nq = 1;
   bool bf16 = false;
 };
+// Throws before anything is launched (check_cross_attention): kErrInvalidArg for batch, heads or T below 1, chunks
+// outside [1, T] and nq outside [1, 4]; kErrFormat for a d_model = 64 heads other than 128, 384 or 512.
+void check_cross_attention(const CrossAttnArgs& a);
 void launch_cross_attention(const CrossAttnArgs& a, hipStream_t s);
 // Cross attention with the K / V projections absorbed (k_cross_absorbed.hip): scores and context are taken against
 // the encoder output E itself (planes: hi at e, lo at e + e_plane, scaled by the power of two e_scale; [clip][T][d]),
