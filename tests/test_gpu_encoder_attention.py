@@ -18,7 +18,9 @@ tests/test_encoder_attention_reference.py holds to a plain float32 attention on 
      same bits;
   d  softmax edges: a dominating key at tile edges and in a nearly empty last tile, one key with all others underflowing,
      equal scores, falling scores;
-  e  refusals before anything is launched.
+  e  refusals before anything is launched;
+  f  the two plane kernels (MFMA operands written in registers just before the MFMA: DESIGN section 25) six times behind
+     polluted allocations: the same bits every call.
 
 Every launch of a, b and d has three guard rows of NaN behind the last clip and an output pre-filled with a NaN bit
 pattern: no sentinel may remain in a clip's rows, and the output's guard rows must come back bit for bit.
@@ -170,3 +172,32 @@ def test_refusals(eng, pkg, form, name):
     assert (out.view(SENTINEL[kind][0]) == SENTINEL[kind][1]).all(), name
     got, _ = run(eng, form, qkv, B, T, H)
     ac.check(form, got, qkv, B, T, H, f"e after {name}")
+
+
+# ------------------------------------------------------------------------------------ f: the same bits every call ---
+
+# one key; one key past a 32-key PV step, past the 64-key tile and past the 128-query block (all of them in ac.SWEEP)
+REPEAT_SHAPES = [(1, 1, 1), (3, 33, 3), (11, 65, 1), (1, 129, 7)]
+HUGE = np.float32([3e34, -7e33, 1e30, 5e36, -2e34, 1e25])
+
+
+@pytest.mark.parametrize("form", ["planes", "bf16"])
+@pytest.mark.parametrize("B,T,H", REPEAT_SHAPES)
+def test_same_bits_every_call(eng, form, B, T, H):
+    """Six calls, each behind a call of the same shape on the input times a huge number, so that the allocations the
+    launch reuses (and whatever registers and LDS the polluting launch left) held huge values, infinities or NaN: every
+    call inside the form's bar and bit-identical to the first.  A probability plane that an MFMA reads before its
+    conversion has landed (tools/isa_hazards.py holds the distance in the ISA; this is the run-time side) is a timing
+    defect and shows as a difference between calls, as pack_bf16x2's did in the decoder."""
+    kind, variant = ac.FORMS[form]
+    qkv, refs = ac.normal_case(B, T, H)
+    x, ref = refs[form == "bf16"]
+    scales = ac.plane_scales(qkv, B, T, H)
+    first = None
+    for rep in range(6):
+        eng.dbg_encoder_attention_at(kind, with_guard(qkv * HUGE[rep]), B, T, H, sentinel_out(kind, B * T + GUARD, 64 * H),
+                                     variant=variant, scales=scales)
+        got, bits = run(eng, form, qkv, B, T, H, scales=scales)
+        ac.check_against(form, got, ref, x, B, T, H, f"f ({B}, {T}, {H}) call {rep}")
+        first = bits if first is None else first
+        assert np.array_equal(bits, first), f"f ({B}, {T}, {H}): call {rep} differs from call 0 in {int((bits != first).sum())} cells"

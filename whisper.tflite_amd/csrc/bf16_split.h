@@ -89,6 +89,16 @@ __device__ __forceinline__ void split_f16(float a, _Float16* hi, _Float16* lo) {
 // is consistent by construction; the generic form above costs 5 instructions per element (cvt, cvt back, sub, cvt,
 // pack), which made the softmax's probability split the longest VALU stretch of the encoder attention.
 // Returns packed dwords: element a in bits 0-15, b in bits 16-31 (the order MFMA fragments want).
+// Two forms, the same three instructions per pair and the same bits:
+//  * split_f16x2, one pair, three asm statements hipcc is free to move: for planes that are STORED (the GEMM and
+//    attention epilogues, k_misc.hip) and never for a dword an MFMA reads.  An MFMA needs two wait states behind the
+//    VALU write of an operand, hipcc's hazard recognizer pads only instructions it knows, and behind an asm statement
+//    it leaves one state (DESIGN sections 24 and 25; tools/isa_hazards.py finds such a pair in the built library).
+//  * split_f16x8_mfma, a whole MFMA fragment (four pairs), for the probability planes of the encoder attention and of
+//    absorbed cross-attention: ONE asm statement that ends with the two wait states, so that whatever hipcc puts
+//    behind it may be an MFMA.  One pad per fragment, not per pair; the conversions the compiler sees (and pads
+//    itself) were measured 1.5 to 3.5 % slower in the encoder attention, this form within the run-to-run spread
+//    (DESIGN section 25).
 __device__ __forceinline__ void split_f16x2(float a, float b, unsigned* hi, unsigned* lo) {
   unsigned h, l;
   asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(a), "v"(b));
@@ -96,6 +106,29 @@ __device__ __forceinline__ void split_f16x2(float a, float b, unsigned* hi, unsi
   asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(h), "v"(b));
   *hi = h;
   *lo = l;
+}
+
+// x[2j], x[2j + 1] -> element j of hi and of lo.  Every output is early-clobber (written before the last input is
+// read); the hi dwords are written eight instructions before the end, the lo dwords get their upper halves last.
+__device__ __forceinline__ void split_f16x8_mfma(const float (&x)[8], u32x4_t& hi, u32x4_t& lo) {
+  unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+  asm("v_cvt_pk_f16_f32 %0, %8, %9\n\t"
+      "v_cvt_pk_f16_f32 %1, %10, %11\n\t"
+      "v_cvt_pk_f16_f32 %2, %12, %13\n\t"
+      "v_cvt_pk_f16_f32 %3, %14, %15\n\t"
+      "v_fma_mixlo_f16 %4, %0, -1.0, %8 op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixlo_f16 %5, %1, -1.0, %10 op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixlo_f16 %6, %2, -1.0, %12 op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixlo_f16 %7, %3, -1.0, %14 op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixhi_f16 %4, %0, -1.0, %9 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixhi_f16 %5, %1, -1.0, %11 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixhi_f16 %6, %2, -1.0, %13 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixhi_f16 %7, %3, -1.0, %15 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+      "s_nop 1"  // VALU write -> MFMA operand: two wait states
+      : "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3), "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3)
+      : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]), "v"(x[6]), "v"(x[7]));
+  hi = u32x4_t{h0, h1, h2, h3};
+  lo = u32x4_t{l0, l1, l2, l3};
 }
 
 // bf16 storage mode: two fp32 values -> one packed dword of bf16 (a in bits 0-15), round to nearest even in hardware

@@ -257,17 +257,17 @@ __global__ __launch_bounds__(256, BF ? 4 : 3) void encoder_attention_planes(cons
 #pragma unroll
       for (int qa = 0; qa < 2; ++qa) {
         u32x4 phu, plu;
+        if constexpr (BF) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const f32x4& sp = sacc[2 * kp + (e >> 1)][qa];
-          unsigned hh, ll = 0;
-          if constexpr (BF) {
-            hh = pack_bf16x2(sp[2 * (e & 1)], sp[2 * (e & 1) + 1]);
-          } else {
-            split_f16x2(sp[2 * (e & 1)], sp[2 * (e & 1) + 1], &hh, &ll);
+          for (int e = 0; e < 4; ++e) {
+            const f32x4& sp = sacc[2 * kp + (e >> 1)][qa];
+            phu[e] = pack_bf16x2(sp[2 * (e & 1)], sp[2 * (e & 1) + 1]);
+            plu[e] = 0;
           }
-          phu[e] = hh;
-          plu[e] = ll;
+        } else {
+          const f32x4 &s0 = sacc[2 * kp][qa], &s1 = sacc[2 * kp + 1][qa];
+          const float x8[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
+          split_f16x8_mfma(x8, phu, plu);  // the form whose outputs an MFMA may read at once (bf16_split.h)
         }
         ph[qa] = __builtin_bit_cast(half8, phu);
         pl[qa] = __builtin_bit_cast(half8, plu);

@@ -354,20 +354,15 @@ __global__ __launch_bounds__(320) void cross_absorbed_attention(CrossAbsDev a) {
     psum = xor32_sum(xor16_sum(psum));
     l_run += psum;
     // P^T B fragment: element j of this lane = key 4 lq + j (j < 4, sub-tile 0) / 16 + 4 lq + j - 4 (sub-tile 1)
-    unsigned ph[4], pl[4] = {0, 0, 0, 0};
+    u32x4 ph, pl = {0, 0, 0, 0};
     if constexpr (BF) {
-      ph[0] = pack_bf16x2(s0[0], s0[1]);
-      ph[1] = pack_bf16x2(s0[2], s0[3]);
-      ph[2] = pack_bf16x2(s1[0], s1[1]);
-      ph[3] = pack_bf16x2(s1[2], s1[3]);
+      ph = u32x4{pack_bf16x2(s0[0], s0[1]), pack_bf16x2(s0[2], s0[3]), pack_bf16x2(s1[0], s1[1]), pack_bf16x2(s1[2], s1[3])};
     } else {
-      split_f16x2(s0[0], s0[1], &ph[0], &pl[0]);
-      split_f16x2(s0[2], s0[3], &ph[1], &pl[1]);
-      split_f16x2(s1[0], s1[1], &ph[2], &pl[2]);
-      split_f16x2(s1[2], s1[3], &ph[3], &pl[3]);
+      const float p8[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
+      split_f16x8_mfma(p8, ph, pl);  // the form whose outputs an MFMA may read at once (bf16_split.h)
     }
-    const half8 pH = __builtin_bit_cast(half8, u32x4{ph[0], ph[1], ph[2], ph[3]});
-    const half8 pL = __builtin_bit_cast(half8, u32x4{pl[0], pl[1], pl[2], pl[3]});
+    const half8 pH = __builtin_bit_cast(half8, ph);
+    const half8 pL = __builtin_bit_cast(half8, pl);
     ABS_ACC(4);  // softmax + split
     // -- context: this wave's DT d tiles; E^T fragments by transposed reads, keys in the same order as P^T
     const unsigned sa = lds0 + (unsigned)((t % NST) * kStage);
