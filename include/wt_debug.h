@@ -353,6 +353,30 @@ int wt_dbg_gemm_addressed(wt_engine* h, int kind, int epi, int M, int N, int K, 
                           long a_bs, int lda, const float* W, const float* bias, const float* pos, int pos_period,
                           int out_format, void* out, long c_len, long c_off, int c_rpb, long c_bs, int ldc,
                           const float* out_scale, int seg, int kv_batch, int kv_heads, int kv_dmodel, int n_cu);
+/* What the encoder GEMM launchers WILL launch for a shape (plane_gemm_plan / bf16_gemm_plan in csrc/kernels.h, the
+ * functions the launchers themselves launch from); no GPU work, no engine.  ln != 0: the LayerNorm outputs are set.
+ * family 0 (launch_gemm_planes, under the current wt_dbg_set_plane_gemm_mode): plan = {tile (0 = 192 x 128, 1 = 192 x 384,
+ * 2 = 256 x 384), schedule (0 = gemm_planes_tile, in step; 1 = gemm_planes_pp; 2 = gemm_planes_pp16; 3 =
+ * gemm_planes_pp16_persist), LayerNorm fused (0 / 1), the mode}; c_rpb and ldc are not read.
+ * family 1 (launch_gemm_bf16_planes; planes_out = bf16 output): plan = {tile columns, tile rows, whole-row tile with the
+ * LayerNorm fused (0 / 1), 0}; K and n_cu are not read. */
+int wt_dbg_plane_gemm_plan(int family, int M, int N, int K, int epi, int planes_out, int ln, int n_cu, int c_rpb, int ldc,
+                           int32_t plan[4]);
+/* An encoder GEMM with the LayerNorm of its finished rows fused into the epilogue, as Engine's fuse_ln launches it, with
+ * guard rows behind every output.  family 0: launch_gemm_planes (K % 32 == 0), 1: launch_gemm_bf16_planes (K % 64 == 0);
+ * epi 5 (bias | residual, R = C in place) or 11 (bias | gelu | pos).  A [a_len], a_rpb, a_bs, lda, W, bias, pos as in
+ * wt_dbg_gemm_addressed.  Every output has M + guard_rows rows of N (guard_rows >= 256, one whole tile), in / out:
+ * uploaded as given, downloaded whole.  C: fp32, written under c_rpb, c_bs, ldc (the fusion needs c_rpb >= M and ldc == N);
+ * planes: the LayerNorm planes, fp16 bits [2][(M + guard_rows) * N] (hi, then lo, of y * ln_scale) or, family 1, bf16 bits
+ * [(M + guard_rows) * N]; ln_y32 (may be NULL: the kernel writes no fp32 copy); p_out (usually NULL): a plane OUTPUT of
+ * the GEMM itself, laid out like `planes`, which the fusion excludes.  ln_g, ln_b (may be NULL) and ln_scale go to the
+ * launcher as they are.  *flag: the non-finite word, cleared first; *fused: what the launcher returned.
+ * WT_ERR_INVALID_ARG before anything is launched: operands or outputs the buffers do not hold, and whatever the launcher
+ * refuses (family 0: the LayerNorm outputs without gain or shift, ln_scale <= 0, ldc != N, c_rpb < M, p_out). */
+int wt_dbg_gemm_ln_fused(wt_engine* h, int family, int epi, int M, int N, int K, const float* A, long a_len, int a_rpb, long a_bs,
+                         int lda, const float* W, const float* bias, const float* pos, int pos_period, const float* ln_g,
+                         const float* ln_b, float ln_scale, int n_cu, int guard_rows, int c_rpb, long c_bs, int ldc, float* C,
+                         uint16_t* planes, float* ln_y32, uint16_t* p_out, int32_t* flag, int32_t* fused);
 /* launch_layernorm_planes: x [M][d], g, b [d] -> planes in / out: fp16 bits [2][M * d + guard] (hi, then lo; y * scale)
  * or, bf16 != 0, bf16 bits [M * d + guard]; y32 [M * d + guard] in / out (may be NULL: the kernel writes no fp32 copy);
  * *nonfinite (may be NULL: no flag is passed) is cleared first and comes back 1 when a row's mean or variance was not

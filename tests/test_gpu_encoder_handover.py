@@ -18,7 +18,7 @@ to float64 on the bf16-rounded operands, as there.  LayerNorm's fp32 copy: 5e-6 
 distribution.  Operands are drawn as in those tests: A standard normal, W standard normal / sqrt(K), bias and pos
 standard normal.
 
-Tile choice of the plane GEMM (launch_planes in k_gemm_planes.hip: cost = rows x 128-column units x rounds of n_cu CUs).
+Tile choice of the plane GEMM (plane_gemm_plan in k_gemm_planes.hip: cost = rows x 128-column units x rounds of n_cu CUs).
 n_cu = 0, 8, 11 are the values test_plane_gemm_every_tile_shape_gives_the_same_result reaches the three tiles with at
 M = 2000; at the row counts used here they pick the 192 x 128 tile except for N = 1152, M = 200 at n_cu = 8 (192 x 384).
 n_cu = 1 and 2 are added because they do reach the 384-column tiles here: M = 240, N = 384: n_cu 1 -> 256 x 384 (one row

@@ -105,7 +105,7 @@ def test_plane_gemm_epilogues(eng, epi):
 
 @pytest.mark.parametrize("M,K,epi,n_cu", [(500, 384, 5, 0), (700, 1536, 5, 224), (3000, 96, 11, 0), (193, 384, 5, 0),
                                           (48000, 384, 5, 224), (48000, 384, 5, 256)])
-def test_plane_gemm_with_fused_layernorm(eng, M, K, epi, n_cu):
+def test_plane_gemm_with_fused_layernorm(pkg, eng, M, K, epi, n_cu):
     """The N = 384 residual GEMMs (out-projection, fc2) and conv2 write the NEXT LayerNorm's planes from their epilogue
     (the 384-column tile owns whole rows: two-pass statistics exchanged between the four wavefront columns through LDS).
     Checked against fp64: C as before, LayerNorm(C) * g + b to the LayerNorm kernel's own tolerance, the fp32 copy, and
@@ -120,7 +120,9 @@ def test_plane_gemm_with_fused_layernorm(eng, M, K, epi, n_cu):
     b = rng.standard_normal(384).astype(np.float32)
     if M > 10000:  # tile heights at the engine's size: force the 384-column tile the cost model would pick there
         A[:] = A[:1000].repeat(48, axis=0)[:M]
+    plan = pkg.plane_gemm_plan(M, 384, K, epi, False, True, n_cu)  # what the launcher says it will launch, before it does
     C, ln, y32, fused = eng.dbg_gemm_planes_ln(A, W, bias, g, b, R=R, pos=pos, epi=epi, n_cu=n_cu)
+    print(f"M={M} K={K} epi={epi} n_cu={n_cu}: {plan.kernel}")
     ref = A.astype(np.float64) @ W.astype(np.float64).T + bias
     if epi & 2:
         ref = gelu(ref)
@@ -131,8 +133,17 @@ def test_plane_gemm_with_fused_layernorm(eng, M, K, epi, n_cu):
     assert rel_err(C, ref) < 3e-6
     if M > 10000:
         assert fused  # at the engine's size a 384-column tile is always the choice
-    if not fused:  # small M: the cost model may prefer the narrow tile, and the engine then launches the LayerNorm
-        return     # kernel itself (covered by the path tests)
+    assert fused == plan.fused
+    if not fused:
+        # The cost model takes the 192 x 128 tile at this n_cu (M = 500, 700, 3000, 193: DESIGN section 26), which cannot
+        # fuse; the engine then launches the LayerNorm kernel itself.  The same operands go through the fused epilogue at
+        # the first n_cu whose plan fuses, so that no case ends without the checks below.
+        n_fuse = next(n for n in (1, 2, 4, 8) if pkg.plane_gemm_plan(M, 384, K, epi, False, True, n).fused)
+        plan = pkg.plane_gemm_plan(M, 384, K, epi, False, True, n_fuse)
+        C2, ln, y32, fused = eng.dbg_gemm_planes_ln(A, W, bias, g, b, R=R, pos=pos, epi=epi, n_cu=n_fuse)
+        print(f"M={M} K={K} epi={epi} n_cu={n_fuse}: {plan.kernel}")
+        assert fused and plan.fused
+        assert rel_err(C2, ref) < 3e-6
     lnref = (ref - ref.mean(1, keepdims=True)) / np.sqrt(ref.var(1, keepdims=True) + 1e-5) * g + b
     assert np.abs(ln - lnref).max() < 1e-5 and np.abs(y32 - lnref).max() < 1e-5
     assert np.abs(ln - y32).max() < 4e-6  # the planes carry 22 bits of the same values

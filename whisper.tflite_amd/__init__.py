@@ -19,6 +19,7 @@ from __future__ import annotations
 import ctypes
 import enum
 import os
+import types
 from ctypes import (POINTER, byref, c_char_p, c_float, c_int, c_int32, c_int64, c_long, c_size_t,
                     c_uint64, c_void_p)
 
@@ -69,7 +70,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_timestamp_select", "wt_dbg_token_scores", "wt_dbg_sample_select",
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
     "wt_dbg_pcm_to_planes",
-    "wt_dbg_gemm_addressed", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes", "wt_dbg_encoder_attention_at",
+    "wt_dbg_gemm_addressed", "wt_dbg_plane_gemm_plan", "wt_dbg_gemm_ln_fused", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes", "wt_dbg_encoder_attention_at",
     "wt_dbg_cross_attention_records", "wt_dbg_cross_attention_records_bf16", "wt_dbg_cross_combine", "wt_dbg_cross_combine_bf16",
     "wt_dbg_align_scores", "wt_dbg_align_matrix", "wt_dbg_align_dtw", "wt_dbg_last_alignment", "wt_dbg_set_alignment",
 ]
@@ -284,6 +285,10 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_gemm_addressed.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, c_long, c_int, c_long, c_int, fp, fp,
                                             fp, c_int, c_int, c_void_p, c_long, c_long, c_int, c_long, c_int, fp, c_int, c_int,
                                             c_int, c_int, c_int]
+        L.wt_dbg_plane_gemm_plan.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ip32]
+        L.wt_dbg_gemm_ln_fused.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, c_long, c_int, c_long, c_int, fp, fp, fp,
+                                           c_int, fp, fp, c_float, c_int, c_int, c_int, c_long, c_int, fp, u16p, fp, u16p, ip32,
+                                           ip32]
         L.wt_dbg_layernorm_planes.argtypes = [c_void_p, c_int, c_int, fp, fp, fp, c_float, c_int, c_int, u16p, fp, ip32]
         L.wt_dbg_f32_to_planes.argtypes = [c_void_p, c_int, c_int, fp, fp, c_int, c_int, u16p]
         L.wt_dbg_encoder_attention_at.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, fp, c_void_p]
@@ -301,6 +306,34 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_align_dtw.argtypes = [c_void_p, c_int, c_int, c_int, fp, ip32, ip32, ip32, POINTER(ctypes.c_uint8)]
         _lib = L
     return _lib
+
+
+PLANE_GEMM_TILES = ("192x128", "192x384", "256x384")
+PLANE_GEMM_SCHEDULES = ("in step", "pp", "pp16", "pp16_persist")
+
+
+def plane_gemm_plan(M, N, K, epi, planes_out=False, ln=False, n_cu=0):
+    """What launch_gemm_planes will launch for this shape under the current plane GEMM mode (wt_dbg_plane_gemm_plan, no
+    GPU work): SimpleNamespace(tile, schedule, fused, mode, kernel); tile indexes PLANE_GEMM_TILES, schedule
+    PLANE_GEMM_SCHEDULES, kernel names both."""
+    plan = np.zeros(4, np.int32)
+    rc = lib().wt_dbg_plane_gemm_plan(0, M, N, K, epi, int(planes_out), int(ln), int(n_cu), 0, 0, _ip32(plan))
+    if rc != WT_OK:
+        raise WtError(rc, "wt_dbg_plane_gemm_plan")
+    tile, schedule, fused, mode = (int(v) for v in plan)
+    return types.SimpleNamespace(tile=tile, schedule=schedule, fused=bool(fused), mode=mode,
+                                 kernel=f"{PLANE_GEMM_TILES[tile]} {PLANE_GEMM_SCHEDULES[schedule]}" + (" + LayerNorm" if fused else ""))
+
+
+def bf16_gemm_plan(M, N, epi, bf16_out=False, ln=False, c_rpb=1 << 30, ldc=None):
+    """What launch_gemm_bf16_planes will launch: SimpleNamespace(bn, bm, whole_row, kernel); whole_row = the tile that
+    holds whole rows, with the LayerNorm fused."""
+    plan = np.zeros(4, np.int32)
+    rc = lib().wt_dbg_plane_gemm_plan(1, M, N, 64, epi, int(bf16_out), int(ln), 0, c_rpb, N if ldc is None else ldc, _ip32(plan))
+    if rc != WT_OK:
+        raise WtError(rc, "wt_dbg_plane_gemm_plan")
+    bn, bm, whole = (int(v) for v in plan[:3])
+    return types.SimpleNamespace(bn=bn, bm=bm, whole_row=bool(whole), kernel=f"bf16 {bm}x{bn}" + (" + LayerNorm" if whole else ""))
 
 
 def _f32(a) -> np.ndarray:
@@ -1676,6 +1709,50 @@ class Engine:
             _fp(pos), pos_period, fmt, out.ctypes.data_as(c_void_p), c_len, c_off, c_rpb, c_bs, ldc, _fp(scales), seg,
             kv[0], kv[1], kv[2], int(n_cu)))
         return out
+
+    def dbg_gemm_ln_fused(self, family, epi, M, N, K, A, a_rpb, a_bs, lda, W, bias, C, planes, ln_g, ln_b, ln_scale=64.0, pos=None,
+                          pos_period=None, y32=None, n_cu=0, c_rpb=1 << 30, c_bs=0, ldc=None, p_out=None, copy=True):
+        """An encoder GEMM with the LayerNorm fused into its epilogue and guard rows behind every output
+        (wt_dbg_gemm_ln_fused).  family 0 = fp16 planes, 1 = bf16; A is one flat float32 buffer, W [N][K].  C float32
+        [M + guard][N] is in / out (epi 5: the residual, in place); planes float16 [2][M + guard][N] (family 0) or uint16
+        [M + guard][N] (family 1) and y32 float32 [M + guard][N] or None are in / out too; guard >= 256 rows.  Returns
+        SimpleNamespace(C, planes, y32, p_out, flag, fused) of copies after the launch (copy=False: the given arrays
+        themselves, written in place)."""
+        A, W = _f32(A).reshape(-1), _f32(W)
+        if W.shape != (N, K):
+            raise ValueError("W must be [N][K]")
+
+        def own(a, dtype):
+            if copy:
+                return np.array(a, dtype, order="C")
+            if a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError("copy=False needs contiguous arrays of the tap's types")
+            return a
+        C = own(C, np.float32)
+        rows = C.shape[0]
+        planes = own(planes, np.uint16 if family else np.float16)
+        shape = (rows, N) if family else (2, rows, N)
+        if C.shape != (rows, N) or planes.shape != shape:
+            raise ValueError("C must be [M + guard][N], planes [2][M + guard][N] float16 or, bf16, [M + guard][N] uint16")
+        if y32 is not None:
+            y32 = own(y32, np.float32)
+            if y32.shape != (rows, N):
+                raise ValueError("y32 must be [M + guard][N]")
+        if p_out is not None:
+            p_out = own(p_out, planes.dtype)
+            if p_out.shape != shape:
+                raise ValueError("p_out must be laid out like planes")
+        pos = _f32(pos) if pos is not None else None
+        if pos_period is None:
+            pos_period = pos.shape[0] if pos is not None else 0
+        u16p = POINTER(ctypes.c_uint16)
+        flag, fused = np.full(1, -1, np.int32), np.full(1, -1, np.int32)
+        self._check(lib().wt_dbg_gemm_ln_fused(
+            self._h, family, epi, M, N, K, _fp(A), A.shape[0], a_rpb, a_bs, lda, _fp(W), _fp(_f32(bias)), _fp(pos), pos_period,
+            _fp(_f32(ln_g)) if ln_g is not None else None, _fp(_f32(ln_b)) if ln_b is not None else None, ln_scale, int(n_cu),
+            rows - M, c_rpb, c_bs, N if ldc is None else ldc, _fp(C), planes.ctypes.data_as(u16p), _fp(y32),
+            p_out.ctypes.data_as(u16p) if p_out is not None else None, _ip32(flag), _ip32(fused)))
+        return types.SimpleNamespace(C=C, planes=planes, y32=y32, p_out=p_out, flag=int(flag[0]), fused=bool(fused[0]))
 
     def dbg_layernorm_planes(self, x, g, b, scale, planes, y32=None, bf16=False, want_flag=True):
         """launch_layernorm_planes over x [M][d].  planes: float16 [2][M * d + guard] (hi, lo) or, bf16, uint16

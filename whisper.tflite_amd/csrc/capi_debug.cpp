@@ -1702,6 +1702,73 @@ int wt_dbg_gemm_addressed(wt_engine* h, int kind, int epi, int M, int N, int K, 
   });
 }
 
+int wt_dbg_plane_gemm_plan(int family, int M, int N, int K, int epi, int planes_out, int ln, int n_cu, int c_rpb, int ldc,
+                           int32_t plan[4]) {
+  if (!plan || family < 0 || family > 1 || M < 1 || N < 1 || K < 1 || n_cu < 0) return WT_ERR_INVALID_ARG;
+  if (family == 0) {
+    const int mode = wt::plane_gemm_mode();
+    const wt::PlaneGemmPlan p = wt::plane_gemm_plan(M, N, K, epi, planes_out != 0, ln != 0, n_cu, mode);
+    plan[0] = p.tile; plan[1] = p.schedule; plan[2] = p.fused ? 1 : 0; plan[3] = mode;
+  } else {
+    const wt::Bf16GemmPlan p = wt::bf16_gemm_plan(M, N, epi, planes_out != 0, ln != 0, c_rpb, ldc);
+    plan[0] = p.bn; plan[1] = p.bm; plan[2] = p.whole_row ? 1 : 0; plan[3] = 0;
+  }
+  return WT_OK;
+}
+
+int wt_dbg_gemm_ln_fused(wt_engine* h, int family, int epi, int M, int N, int K, const float* A, long a_len, int a_rpb, long a_bs,
+                         int lda, const float* W, const float* bias, const float* pos, int pos_period, const float* ln_g,
+                         const float* ln_b, float ln_scale, int n_cu, int guard_rows, int c_rpb, long c_bs, int ldc, float* C,
+                         uint16_t* planes, float* ln_y32, uint16_t* p_out, int32_t* flag, int32_t* fused) {
+  const int kmul = family == 0 ? 32 : 64;
+  if (!h || !A || !W || !C || !planes || !flag || !fused || family < 0 || family > 1 || M < 1 || N < 128 || N % 128 != 0 || K < kmul ||
+      K % kmul != 0 || guard_rows < 256 || a_rpb < 1 || a_bs < 0 || lda < 0 || c_rpb < 1 || c_bs < 0 || ldc < 0 || n_cu < 0 ||
+      (epi != (wt::kEpiBias | wt::kEpiResidual) && epi != (wt::kEpiBias | wt::kEpiGelu | wt::kEpiPos)) || !bias ||
+      ((epi & wt::kEpiPos) && (!pos || pos_period < 1))) {
+    return WT_ERR_INVALID_ARG;
+  }
+  // nothing is launched over an operand or an output the buffers do not hold; every output has M + guard_rows rows, a
+  // whole tile more than the launch owns, so that a store to any row of the last tile still lands inside it
+  const size_t cells = size_t(M + guard_rows) * N;
+  if (a_len < rows_extent(M, a_rpb, a_bs, lda, K) || rows_extent(M, c_rpb, c_bs, ldc, N) > long(cells)) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    DevArr<float> dB(N, bias), dP(pos ? size_t(pos_period) * N : 0, pos), dG(ln_g ? N : 0, ln_g), dS(ln_b ? N : 0, ln_b),
+        dC(cells, C), dY(ln_y32 ? cells : 0, ln_y32);
+    DevArr<unsigned short> dL((family == 0 ? 2 : 1) * cells, planes), dO(p_out ? (family == 0 ? 2 : 1) * cells : 0, p_out);
+    DevArr<int> dF(1);
+    hipStream_t st = h->impl->stream();
+    dF.zero(st);  // as the engine clears its flag
+    wt::PlaneGemmArgs g;
+    g.a_rpb = a_rpb; g.a_bs = a_bs; g.lda = lda; g.bias = dB.p;
+    g.C = dC.p; g.R = dC.p; g.c_rpb = c_rpb; g.c_bs = c_bs; g.ldc = ldc;  // the residual in place, as the engine runs it
+    g.pos = dP.p; g.pos_period = pos_period > 0 ? pos_period : 1;
+    g.M = M; g.N = N; g.K = K; g.n_cu = n_cu;
+    g.ln_g = ln_g ? dG.p : nullptr; g.ln_b = ln_b ? dS.p : nullptr; g.ln_P = dL.p; g.ln_plane = long(cells); g.ln_scale = ln_scale;
+    g.ln_y32 = ln_y32 ? dY.p : nullptr; g.nonfinite = dF.p;
+    if (p_out) { g.P = dO.p; g.p_plane = long(cells); }
+    bool did = false;
+    if (family == 0) {
+      const float sa = wt::f16_scale_for(max_abs(A, size_t(a_len))), sw = wt::f16_scale_for(max_abs(W, size_t(N) * K));
+      const DevPlanes dA(A, size_t(a_len), sa);
+      const DevArr<unsigned short> dW(weight_planes(W, N, K, sw));
+      g.A = dA.ptr(); g.a_plane = dA.plane; g.W = dW.p; g.a_scale = sa; g.w_scale = sw;
+      did = wt::launch_gemm_planes(g, epi, st);
+      h->impl->sync();
+    } else {
+      const DevBf16 dA(A, size_t(a_len)), dW(W, size_t(N) * K);
+      g.A = dA.ptr(); g.W = dW.ptr();
+      did = wt::launch_gemm_bf16_planes(g, epi, st);
+      h->impl->sync();
+    }
+    dC.to_host(C);
+    dL.to_host(planes);
+    dY.to_host(ln_y32);
+    if (p_out) dO.to_host(p_out);
+    dF.to_host(flag);
+    *fused = did ? 1 : 0;
+  });
+}
+
 int wt_dbg_layernorm_planes(wt_engine* h, int M, int d, const float* x, const float* g, const float* b, float scale, int bf16,
                             int guard, uint16_t* planes, float* y32, int32_t* nonfinite) {
   if (!h || !x || !g || !b || !planes || M < 1 || d < 1 || guard < 0 || guard % 4 != 0 || !(scale > 0.0f)) return WT_ERR_INVALID_ARG;

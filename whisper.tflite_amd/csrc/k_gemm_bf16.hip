@@ -360,26 +360,21 @@ void launch_shape(const Bf16GemmDev& g, hipStream_t s) {
 
 // LayerNorm fusion: the tile whose columns are the whole row (d_model 512 / 384 / 128)
 template <int EPI>
-bool launch_bf16_ln(const Bf16GemmDev& g, hipStream_t s) {
-  switch (g.N) {
-    case 512: launch_shape<EPI, false, 4, 4, 2, true>(g, s); return true;
-    case 384: launch_shape<EPI, false, 4, 3, 3, true>(g, s); return true;
-    case 128: launch_shape<EPI, false, 2, 2, 3, true>(g, s); return true;
-    default: return false;
+void launch_bf16_ln(const Bf16GemmDev& g, hipStream_t s, const Bf16GemmPlan& plan) {
+  switch (plan.bn) {
+    case 512: launch_shape<EPI, false, 4, 4, 2, true>(g, s); return;
+    case 384: launch_shape<EPI, false, 4, 3, 3, true>(g, s); return;
+    case 128: launch_shape<EPI, false, 2, 2, 3, true>(g, s); return;
+    default: throw Error(kErrUnsupported, "bf16 GEMM: the plan names a whole-row tile there is none of");
   }
 }
 
+// the tile bf16_gemm_plan (below) names
 template <int EPI, bool BF_OUT>
-void launch_bf16_planes(const Bf16GemmDev& g, hipStream_t s) {
-  static const int forced = [] {
-    const char* v = getenv("WT_BF16_TILE");  // measurement knob: 128 / 256 / 384 = that tile where N allows it
-    return v ? atoi(v) : 0;
-  }();
-  int bn = g.N % 384 == 0 ? 384 : g.N % 256 == 0 ? 256 : 128;
-  if (forced && g.N % forced == 0) bn = forced;
-  if (bn == 384) {
+void launch_bf16_planes(const Bf16GemmDev& g, hipStream_t s, const Bf16GemmPlan& plan) {
+  if (plan.bn == 384) {
     launch_shape<EPI, BF_OUT, 4, 3>(g, s);
-  } else if (bn == 256) {
+  } else if (plan.bn == 256) {
     launch_shape<EPI, BF_OUT, 4, 2>(g, s);
   } else {
     launch_shape<EPI, BF_OUT, 2, 2>(g, s);
@@ -387,6 +382,31 @@ void launch_bf16_planes(const Bf16GemmDev& g, hipStream_t s) {
 }
 
 }  // namespace
+
+Bf16GemmPlan bf16_gemm_plan(int M, int N, int epi, bool bf16_out, bool ln, int c_rpb, int ldc) {
+  static const int forced = [] {
+    const char* v = getenv("WT_BF16_TILE");  // measurement knob: 128 / 256 / 384 = that tile where N allows it
+    return v ? atoi(v) : 0;
+  }();
+  // LayerNorm fusion: fp32 output in contiguous [M][N] rows, N one of the whole-row tiles; WT_BF16_LN_FUSE=0
+  // keeps the separate LayerNorm launch (A/B runs)
+  static const bool fuse = [] {
+    const char* v = getenv("WT_BF16_LN_FUSE");
+    return !v || atoi(v) != 0;
+  }();
+  Bf16GemmPlan p;
+  if (ln && fuse && !bf16_out && ldc == N && c_rpb >= M && (N == 512 || N == 384 || N == 128) &&
+      (epi == (kEpiBias | kEpiResidual) || epi == (kEpiBias | kEpiGelu | kEpiPos))) {
+    p.whole_row = true;
+    p.bn = N;
+    p.bm = N == 512 ? 128 : 192;
+    return p;
+  }
+  p.bn = N % 384 == 0 ? 384 : N % 256 == 0 ? 256 : 128;
+  if (forced && N % forced == 0) p.bn = forced;
+  if (p.bn != 384 && p.bn != 256) p.bn = 128;
+  return p;
+}
 
 bool launch_gemm_bf16_planes(const PlaneGemmArgs& a, int epi, hipStream_t s) {
   Bf16GemmDev g{};
@@ -410,26 +430,26 @@ bool launch_gemm_bf16_planes(const PlaneGemmArgs& a, int epi, hipStream_t s) {
       throw Error(kErrInvalidArg, "bf16 GEMM operand spans more than the 4 GiB its 32-bit offsets reach");
     }
   }
-  // LayerNorm fusion (ln_g set): fp32 output in contiguous [M][N] rows, N one of the whole-row tiles; WT_BF16_LN_FUSE=0
-  // keeps the separate LayerNorm launch (A/B runs).  Returns whether the LayerNorm was done here.
-  static const bool fuse = [] {
-    const char* v = getenv("WT_BF16_LN_FUSE");
-    return !v || atoi(v) != 0;
-  }();
-  if (a.ln_g != nullptr && fuse && !bf_out && a.ln_b != nullptr && a.ln_P != nullptr && a.ldc == a.N && a.c_rpb >= a.M &&
-      (a.N == 512 || a.N == 384 || a.N == 128)) {
+  // LayerNorm fusion (ln_g, ln_b, ln_P set; the conditions are bf16_gemm_plan's).  Returns whether the LayerNorm was done here.
+  const Bf16GemmPlan plan =
+      bf16_gemm_plan(a.M, a.N, epi, bf_out, a.ln_g != nullptr && a.ln_b != nullptr && a.ln_P != nullptr, a.c_rpb, a.ldc);
+  if (plan.whole_row) {
     g.ln_g = a.ln_g; g.ln_b = a.ln_b; g.ln_P = a.ln_P; g.ln_y32 = a.ln_y32; g.nonfinite = a.nonfinite;
-    if (epi == (kEpiBias | kEpiResidual)) return launch_bf16_ln<kEpiBias | kEpiResidual>(g, s);
-    if (epi == (kEpiBias | kEpiGelu | kEpiPos)) return launch_bf16_ln<kEpiBias | kEpiGelu | kEpiPos>(g, s);
+    if (epi == (kEpiBias | kEpiResidual)) {
+      launch_bf16_ln<kEpiBias | kEpiResidual>(g, s, plan);
+    } else {
+      launch_bf16_ln<kEpiBias | kEpiGelu | kEpiPos>(g, s, plan);
+    }
+    return true;
   }
   switch (epi | (bf_out ? 256 : 0)) {
-    case kEpiBias: launch_bf16_planes<kEpiBias, false>(g, s); break;
-    case kEpiBias | kEpiGelu: launch_bf16_planes<kEpiBias | kEpiGelu, false>(g, s); break;  // fp32 copy of a GELU output (kernel-level taps)
-    case kEpiBias | kEpiResidual: launch_bf16_planes<kEpiBias | kEpiResidual, false>(g, s); break;
-    case kEpiBias | kEpiGelu | kEpiPos: launch_bf16_planes<kEpiBias | kEpiGelu | kEpiPos, false>(g, s); break;
-    case kEpiBias | 256: launch_bf16_planes<kEpiBias, true>(g, s); break;
-    case kEpiBias | kEpiGelu | 256: launch_bf16_planes<kEpiBias | kEpiGelu, true>(g, s); break;
-    case kEpiBias | kEpiKvLayout | 256: launch_bf16_planes<kEpiBias | kEpiKvLayout, true>(g, s); break;
+    case kEpiBias: launch_bf16_planes<kEpiBias, false>(g, s, plan); break;
+    case kEpiBias | kEpiGelu: launch_bf16_planes<kEpiBias | kEpiGelu, false>(g, s, plan); break;  // fp32 copy of a GELU output (kernel-level taps)
+    case kEpiBias | kEpiResidual: launch_bf16_planes<kEpiBias | kEpiResidual, false>(g, s, plan); break;
+    case kEpiBias | kEpiGelu | kEpiPos: launch_bf16_planes<kEpiBias | kEpiGelu | kEpiPos, false>(g, s, plan); break;
+    case kEpiBias | 256: launch_bf16_planes<kEpiBias, true>(g, s, plan); break;
+    case kEpiBias | kEpiGelu | 256: launch_bf16_planes<kEpiBias | kEpiGelu, true>(g, s, plan); break;
+    case kEpiBias | kEpiKvLayout | 256: launch_bf16_planes<kEpiBias | kEpiKvLayout, true>(g, s, plan); break;
     default: throw Error(kErrInvalidArg, "unsupported bf16 GEMM epilogue combination");
   }
   return false;

@@ -969,8 +969,9 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_pp16_persist(PlaneGemmDev 
   }
 }
 
+// Launches what `plan` (plane_gemm_plan below) names for this tile: the schedule is decided there, not here.
 template <int EPI, bool PLANES_OUT, int WN, int NI, int MI = 3, bool LN = false>
-void launch_planes_shape(const PlaneGemmDev& g, hipStream_t s, int n_cu = 0) {
+void launch_planes_shape(const PlaneGemmDev& g, hipStream_t s, const PlaneGemmPlan& plan, int n_cu = 0) {
   constexpr int BN = WN * NI * 32, BM = 64 * MI;
   const int blocks = ((g.M + BM - 1) / BM) * (g.N / BN);
   constexpr size_t smem = 2 * (2 * BM * BK * 2 + 2 * BN * BK * 2);  // two stages; the epilogue stages fit inside
@@ -983,8 +984,8 @@ void launch_planes_shape(const PlaneGemmDev& g, hipStream_t s, int n_cu = 0) {
   if constexpr (WN == 4 && NI == 3 && MI == 3) {  // (the 256-row tile's fragments do not fit beside its accumulators)
     if constexpr (PLANES_OUT && !LN && (EPI & ~(kEpiBias | kEpiGelu)) == 0) {
       // several tiles per CU: one persistent block per CU that prefetches across tiles (WT_PLANE_GEMM_MODE=4 switches it off)
-      const int cu = n_cu > 0 ? n_cu : 256;
-      if (plane_gemm_mode() == 2 && cu % 8 == 0 && blocks >= 2 * cu && (g.K / BK) % 2 == 0 && g.K / BK >= 4) {
+      if (plan.schedule == 3) {
+        const int cu = n_cu > 0 ? n_cu : 256;
         static const bool raised_p = [] {
           (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_planes_pp16_persist<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     160 * 1024);
@@ -995,7 +996,7 @@ void launch_planes_shape(const PlaneGemmDev& g, hipStream_t s, int n_cu = 0) {
         return;
       }
     }
-    if (plane_gemm_mode() == 2 || plane_gemm_mode() == 4) {
+    if (plan.schedule == 2) {
       static const bool raised_pp16 = [] {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_planes_pp16<EPI, PLANES_OUT, LN>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1005,7 +1006,7 @@ void launch_planes_shape(const PlaneGemmDev& g, hipStream_t s, int n_cu = 0) {
       WT_LAUNCH_TIMED((gemm_planes_pp16<EPI, PLANES_OUT, LN>), dim3(blocks), dim3(512), smem, s, g);
       return;
     }
-    if (plane_gemm_mode() == 1) {
+    if (plan.schedule == 1) {
       static const bool raised_pp = [] {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_planes_pp<EPI, PLANES_OUT, MI, LN>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1016,49 +1017,36 @@ void launch_planes_shape(const PlaneGemmDev& g, hipStream_t s, int n_cu = 0) {
       return;
     }
   }
+  if (plan.schedule != 0) throw Error(kErrUnsupported, "plane GEMM: the plan names a schedule this tile does not have");
   WT_LAUNCH_TIMED((gemm_planes_tile<EPI, PLANES_OUT, WN, NI, MI, LN>), dim3(blocks), dim3(128 * WN), smem, s, g);
+}
+
+// the epilogues whose 384-column tiles can also write the LayerNorm of the rows they finish
+constexpr bool ln_fusable(int epi, bool planes_out) {
+  return !planes_out && (epi == (kEpiBias | kEpiResidual) || epi == (kEpiBias | kEpiGelu | kEpiPos));
 }
 
 // returns true when the launch also wrote the LayerNorm planes (g.ln_P set and a 384-column tile chosen)
 template <int EPI, bool PLANES_OUT>
 bool launch_planes(const PlaneGemmDev& g, int n_cu, hipStream_t s) {
-  static const int forced = [] {
-    const char* v = getenv("WT_PLANE_TILE");  // measurement knob (tools/gemm_planes_bench.py): 128 / 384 = that tile only
-    return v ? atoi(v) : 0;
-  }();
-  // Tile choice by how the blocks fill the CUs this stream may use (the pipelined encoder stream leaves some CUs
-  // to the decoders): 250 wide row tiles are one round on 256 CUs but two on 224, 188 tall ones one round on either.
-  // Cost of a candidate = rows x 128-column units x rounds of the CUs; the narrow kernel (two co-resident blocks per
-  // CU, which share the CU's throughput) costs ~10 % more per unit.
-  const int cu = n_cu > 0 ? n_cu : 256;
-  auto rounds = [&](long tiles) { return (tiles + cu - 1) / cu; };
-  const long rt192 = (g.M + 191) / 192, rt256 = (g.M + 255) / 256;
-  const bool can_wide = g.N % 384 == 0;
-  const double c_wide = can_wide ? 192.0 * 3 * rounds(rt192 * (g.N / 384)) : 1e30;
-  // (round 4: the 192-row tile runs the ping-pong 16 x 16 x 32 kernel, the 256-row one the older in-step kernel — 8 % more per
-  // unit of work instead of 5 % less: fc1 236 us on 4 rounds of 192-row tiles against 260 us on 3 rounds of 256-row tiles)
-  const double c_tall = can_wide ? 256.0 * 3 * 1.08 * rounds(rt256 * (g.N / 384)) : 1e30;
-  const double c_narrow = 192.0 * 1.1 * rounds(rt192 * (g.N / 128));
-  int pick = c_wide <= c_narrow ? (c_tall < c_wide ? 2 : 1) : (c_tall < c_narrow ? 2 : 0);
-  if (forced == 128) pick = 0;
-  if (forced == 384 && can_wide) pick = 1;
-  if (forced == 256 && can_wide) pick = 2;
-  if constexpr (!PLANES_OUT && (EPI == (kEpiBias | kEpiResidual) || EPI == (kEpiBias | kEpiGelu | kEpiPos))) {
-    if (g.ln_P != nullptr && g.N == 384 && pick != 0) {  // whole rows in one block: LayerNorm fused into the epilogue
-      if (pick == 2) {
-        launch_planes_shape<EPI, false, 4, 3, 4, true>(g, s);
+  const PlaneGemmPlan plan = plane_gemm_plan(g.M, g.N, g.K, EPI, PLANES_OUT, g.ln_P != nullptr, n_cu, plane_gemm_mode());
+  if constexpr (ln_fusable(EPI, PLANES_OUT)) {
+    if (plan.fused) {  // whole rows in one block: LayerNorm fused into the epilogue
+      if (plan.tile == 2) {
+        launch_planes_shape<EPI, false, 4, 3, 4, true>(g, s, plan);
       } else {
-        launch_planes_shape<EPI, false, 4, 3, 3, true>(g, s);
+        launch_planes_shape<EPI, false, 4, 3, 3, true>(g, s, plan);
       }
       return true;
     }
   }
-  if (pick == 2) {
-    launch_planes_shape<EPI, PLANES_OUT, 4, 3, 4>(g, s);
-  } else if (pick == 1) {
-    launch_planes_shape<EPI, PLANES_OUT, 4, 3, 3>(g, s, n_cu);
+  if (plan.fused) throw Error(kErrUnsupported, "plane GEMM: the plan fuses a LayerNorm this epilogue cannot");
+  if (plan.tile == 2) {
+    launch_planes_shape<EPI, PLANES_OUT, 4, 3, 4>(g, s, plan);
+  } else if (plan.tile == 1) {
+    launch_planes_shape<EPI, PLANES_OUT, 4, 3, 3>(g, s, plan, n_cu);
   } else {
-    launch_planes_shape<EPI, PLANES_OUT, 2, 2, 3>(g, s);
+    launch_planes_shape<EPI, PLANES_OUT, 2, 2, 3>(g, s, plan);
   }
   return false;
 }
@@ -1087,6 +1075,41 @@ std::vector<unsigned short> split_weight_planes(const float* W, int N, int K, in
     }
   }
   return out;
+}
+
+PlaneGemmPlan plane_gemm_plan(int M, int N, int K, int epi, bool planes_out, bool ln, int n_cu, int mode) {
+  static const int forced = [] {
+    const char* v = getenv("WT_PLANE_TILE");  // measurement knob (tools/gemm_planes_bench.py): 128 / 384 = that tile only
+    return v ? atoi(v) : 0;
+  }();
+  // Tile choice by how the blocks fill the CUs this stream may use (the pipelined encoder stream leaves some CUs
+  // to the decoders): 250 wide row tiles are one round on 256 CUs but two on 224, 188 tall ones one round on either.
+  // Cost of a candidate = rows x 128-column units x rounds of the CUs; the narrow kernel (two co-resident blocks per
+  // CU, which share the CU's throughput) costs ~10 % more per unit.
+  const int cu = n_cu > 0 ? n_cu : 256;
+  auto rounds = [&](long tiles) { return (tiles + cu - 1) / cu; };
+  const long rt192 = (M + 191) / 192, rt256 = (M + 255) / 256;
+  const bool can_wide = N % 384 == 0;
+  const double c_wide = can_wide ? 192.0 * 3 * rounds(rt192 * (N / 384)) : 1e30;
+  // (round 4: the 192-row tile runs the ping-pong 16 x 16 x 32 kernel, the 256-row one the older in-step kernel — 8 % more per
+  // unit of work instead of 5 % less: fc1 236 us on 4 rounds of 192-row tiles against 260 us on 3 rounds of 256-row tiles)
+  const double c_tall = can_wide ? 256.0 * 3 * 1.08 * rounds(rt256 * (N / 384)) : 1e30;
+  const double c_narrow = 192.0 * 1.1 * rounds(rt192 * (N / 128));
+  int pick = c_wide <= c_narrow ? (c_tall < c_wide ? 2 : 1) : (c_tall < c_narrow ? 2 : 0);
+  if (forced == 128) pick = 0;
+  if (forced == 384 && can_wide) pick = 1;
+  if (forced == 256 && can_wide) pick = 2;
+  PlaneGemmPlan p;
+  p.tile = pick;
+  p.fused = ln_fusable(epi, planes_out) && ln && N == 384 && pick != 0;
+  if (pick == 1) {  // the 192 x 384 tile has every schedule; the other two run in step only
+    const long blocks = rt192 * (N / 384);
+    // several tiles per CU: one persistent block per CU that prefetches across tiles (mode 4 switches it off)
+    const bool persist = planes_out && !p.fused && (epi & ~(kEpiBias | kEpiGelu)) == 0 && mode == 2 && cu % 8 == 0 &&
+                         blocks >= 2 * cu && (K / BK) % 2 == 0 && K / BK >= 4;
+    p.schedule = persist ? 3 : (mode == 2 || mode == 4) ? 2 : mode == 1 ? 1 : 0;
+  }
+  return p;
 }
 
 bool launch_gemm_planes(const PlaneGemmArgs& a, int epi, hipStream_t s) {

@@ -128,11 +128,28 @@ bool launch_gemm_planes(const PlaneGemmArgs& a, int epi, hipStream_t s);
 // schedule of the 384-column plane tiles (0 in step, 1 ping-pong groups; k_gemm_planes.hip) — measurement knob
 int plane_gemm_mode();
 void set_plane_gemm_mode(int m);
+// What launch_gemm_planes launches for a shape, and the only place that decides it (the launcher launches from this):
+// tile 0 = 192 x 128, 1 = 192 x 384, 2 = 256 x 384; schedule 0 = gemm_planes_tile (in step), 1 = gemm_planes_pp,
+// 2 = gemm_planes_pp16, 3 = gemm_planes_pp16_persist; fused = the LayerNorm is done in the epilogue.  `ln` = ln_P set,
+// `mode` = plane_gemm_mode().  No GPU work; the measurement knob WT_PLANE_TILE is read here (once per process).
+struct PlaneGemmPlan {
+  int tile = 0, schedule = 0;
+  bool fused = false;
+};
+PlaneGemmPlan plane_gemm_plan(int M, int N, int K, int epi, bool planes_out, bool ln, int n_cu, int mode);
 // bf16 storage mode (k_gemm_bf16.hip): A, W single bf16 matrices (the plane offsets and scales of the struct are
 // unused), K a multiple of 64; P set = bf16 output (row-major, or the cross-KV cache layout with kEpiKvLayout),
 // else fp32 output C
 // returns true when the LayerNorm fusion (a.ln_g ...: as in launch_gemm_planes, ONE bf16 plane at ln_P, ln_scale unused) was done
 bool launch_gemm_bf16_planes(const PlaneGemmArgs& a, int epi, hipStream_t s);
+// What launch_gemm_bf16_planes launches (it launches from this): block tile bm x bn; whole_row = the tile whose columns
+// are the whole row, with the LayerNorm fused into its epilogue.  `ln` = ln_g, ln_b and ln_P all set.  WT_BF16_TILE and
+// WT_BF16_LN_FUSE are read here (once per process).
+struct Bf16GemmPlan {
+  int bm = 192, bn = 128;
+  bool whole_row = false;
+};
+Bf16GemmPlan bf16_gemm_plan(int M, int N, int epi, bool bf16_out, bool ln, int c_rpb, int ldc);
 // W [N][K] fp32 -> bf16 [N][Kpad] (round to nearest even, zero filled)
 std::vector<unsigned short> round_weights_bf16(const float* W, int N, int K, int Kpad);
 // W [N][K] fp32 -> both fp16 planes, scaled by `scale`, as [N / 16][Kpad / 32][hi | lo][16 rows][32 k] with swizzled
