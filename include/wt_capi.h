@@ -179,6 +179,24 @@ int wt_engine_set_context(wt_engine* h, const int64_t* ids, int n);
  * "temperature_fallback". */
 int wt_engine_set_contexts(wt_engine* h, const int64_t* ids, const int32_t* offsets, int n_clips);
 
+/* Logit suppression: Whisper's SuppressTokens and SuppressBlank.  Every full-length decode
+ * ("max_positions") sets the logits of `ids` to -inf at every generated position and those of `first_ids` at the first
+ * one only (the position behind the whole fed prompt and context), on the device, behind the no-speech probability (read
+ * from the unfiltered logits) and in front of every other rule: the timestamp rules, the log-softmax of the scores, the
+ * sampler and every beam hypothesis's allowed set then see a vocabulary without them.  Both lists take 0..1024 ids,
+ * duplicates allowed; n = n_first = 0 clears both, after which every call is what it was before.  WT_ERR_INVALID_ARG: an id
+ * outside [0, n_vocab), EOT among `ids` (the allowed set must never be empty; EOT may be in `first_ids`), a count outside
+ * 0..1024.  WT_ERR_UNSUPPORTED: a Monolith engine.  The read-only options "suppress_ids" and "suppress_first_ids" give
+ * the counts in effect.  Option "suppress_default" = 1 installs the lists of wt_vocab_default_suppress over the engine's
+ * vocabulary (ids below the model's n_vocab), 0 clears them.  With a list set a decode call is WT_ERR_UNSUPPORTED without
+ * "max_positions" and wherever "max_positions" refuses one (the calls with rows of WT_MAX_IDS ids, the pipeline, the bf16
+ * storage mode, language = WT_LANGUAGE_AUTO, the forced-ids tap) and on a model whose vocabulary holds no EOT id
+ * (token_eot >= n_vocab: the selectors behind the filter take one); the engine stays usable after each.  It works with and
+ * without "timestamps", "scores", "skip_silence", "temperature", "temperature_fallback" (every attempt), either kind of
+ * context, "seek", wt_transcribe_long_pcm (every window), wt_transcribe_long_batch, "word_timestamps" (the alignment pass
+ * is teacher-forced and unaffected) and "full_beam" = 1 with beam_size 2..8.  Call it with nothing in flight. */
+int wt_engine_set_suppress(wt_engine* h, const int64_t* ids, int n, const int64_t* first_ids, int n_first);
+
 /* ---- single-clip entry points (the reference's two virtuals) ----------------------------
  * Replace Engine::transcribe(std::vector<float>&) (whisper.h:160, whisper.cpp:752-769; JNI
  * transcribeBuffer, bindings/java/whisper.tflite.cpp:45-58) and
@@ -445,6 +463,20 @@ int wt_vocab_segments(const wt_vocab* v, const int64_t* ids, int n, int sample_b
  * -WT_ERR_INVALID_ARG. */
 int wt_vocab_seek_step(const wt_vocab* v, const int64_t* g, int n, int win_ticks, int seg_ticks, wt_segment* out, int cap,
                        int32_t* advance_ticks);
+
+/* Whisper's default suppression lists from a vocabulary; no GPU.  first_ids: the id whose bytes are exactly " " (if the
+ * vocabulary has one) and EOT.  ids: those of sot, translate, transcribe, <|startoflm|> (the id in front of prev: 50360
+ * multilingual; wt_vocab_info does not name it), prev and solm (this table's name of the <|nospeech|> id; multilingual
+ * 50258 and 50358 .. 50362) that lie below n_vocab, then the non-speech symbols, typed out in csrc/host_util.cpp: for every symbol s of
+ * Whisper's non_speech_tokens list the id whose bytes are exactly s and the one whose bytes are exactly " " + s, the exact
+ * " -" and " '", and for the musical symbols ♩♪♫♬♭♮♯ a string without an exact match gives the longest token whose
+ * bytes are a proper prefix of it (behind the leading space of " " + s the prefix must reach into the symbol: the bare
+ * " " is never taken), the smallest id on equal length.  Text matches are ids below EOT.  This prefix rule is NOT
+ * byte-pair encoding: the list equals Whisper's wherever Whisper's encoder yields that prefix token first, which holds
+ * for its own vocabularies, and may differ on another vocabulary.  Both lists come back sorted and unique; *n and
+ * *n_first get the full counts, at most cap / first_cap ids are written, WT_ERR_BUFFER when either is too small. */
+int wt_vocab_default_suppress(const wt_vocab* v, int64_t* ids, int cap, int32_t* n, int64_t* first_ids, int first_cap,
+                              int32_t* n_first);
 
 /* ---- word-level timestamps -------------------------------------------
  * Option "word_timestamps" = 1 (default 0; needs "timestamps" = 1, "max_positions" and the absorbed cross-attention the

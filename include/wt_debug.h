@@ -432,6 +432,13 @@ int wt_dbg_align_matrix(wt_engine* h, int clips, int heads, int L_max, int ld, i
  * [0, N_max], an F[b] outside [1, ld], and what the launcher refuses (N_max > 447, ld > 1500). */
 int wt_dbg_align_dtw(wt_engine* h, int clips, int N_max, int ld, const float* C, const int32_t* N, const int32_t* F,
                      int32_t* jump, uint8_t* trace);
+/* launch_suppress_logits (k_suppress.hip, wt_engine_set_suppress): logits [rows][ldl] -> out
+ * [rows][ldl], the padding columns V .. ldl - 1 included, with -inf at every id of ids [n] and, when first != 0, of
+ * first_ids [n_first]; the two lists are uploaded as the engine keeps them, one buffer, the always-ids first.  The ids are
+ * data to the kernel: one outside [0, V) changes nothing.  WT_ERR_INVALID_ARG before anything is launched: a null
+ * pointer, and what the launcher refuses (rows outside 1..128, V < 1, ldl < V, a count outside 0..1024). */
+int wt_dbg_suppress_logits(wt_engine* h, int rows, int V, int ldl, const float* logits, float* out, const int64_t* ids, int n,
+                           const int64_t* first_ids, int n_first, int first);
 /* Measurement and test handles of the alignment pass (word_timestamps): keep = 1 keeps what the pass forms per clip for
  * wt_dbg_last_alignment (it then synchronises and copies per clip); mode = the form of align_scores, 0 or 1 (default 1);
  * sub = the most clips per sub-group of the pass, 0 = as many as the weight workspace's bound allows (default).  A

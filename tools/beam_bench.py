@@ -4,10 +4,11 @@
   * audio-sec/s of wt_encdec_tokens_batch_dev at beam_size K with 25 and 64 clips (and greedy beside it).
 With --max-positions P the batch cases run the full-length chains instead: full-length beam
 search (full_beam = 1) beside full-length greedy decoding at the same P, ms per call and per decoder step; the
-synthetic weights never emit EOT, so every step runs.
+synthetic weights never emit EOT, so every step runs.  With --suppress-ab every full-length case runs four times, the
+suppression lists cleared and option suppress_default = 1 alternating.
 Every GPU step runs in a child process of its own under a time limit; the parent only collects the JSON lines.
 
-  python tools/beam_bench.py [--beam 5] [--iters 10] [--only CASE] [--max-positions P]
+  python tools/beam_bench.py [--beam 5] [--iters 10] [--only CASE] [--max-positions P [--suppress-ab]]
 """
 from __future__ import annotations
 
@@ -24,7 +25,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def child(case: str, beam: int, iters: int, tmp: str, max_positions: int = 0) -> dict:
+def child(case: str, beam: int, iters: int, tmp: str, max_positions: int = 0, suppress: int = 0) -> dict:
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
     pkg = ge.load_package()
@@ -34,6 +35,7 @@ def child(case: str, beam: int, iters: int, tmp: str, max_positions: int = 0) ->
     if max_positions:
         eng.set_option("max_positions", max_positions)
         eng.set_option("full_beam", 1)
+        eng.set_option("suppress_default", suppress)
     rng = np.random.default_rng(1234)
     if case == "latency":
         pcm = (0.1 * rng.standard_normal(eng.pcm_len)).astype(np.float32)
@@ -62,7 +64,9 @@ def child(case: str, beam: int, iters: int, tmp: str, max_positions: int = 0) ->
                "batch": batch, "ms_per_call": 1e3 * dt, "audio_sec_per_s": batch * 30.0 / dt, "decoder_ms": tm.decoder_ms}
         if max_positions:
             steps = int(tm.decoder_steps)
-            out.update(max_positions=max_positions, decoder_steps=steps, decoder_ms_per_step=tm.decoder_ms / max(steps, 1))
+            out.update(max_positions=max_positions, decoder_steps=steps, decoder_ms_per_step=tm.decoder_ms / max(steps, 1),
+                       suppress_default=suppress, suppress_ids=eng.get_option("suppress_ids"),
+                       suppress_first_ids=eng.get_option("suppress_first_ids"))
     eng.close()
     return out
 
@@ -83,19 +87,24 @@ def main():
     ap.add_argument("--timeout", type=int, default=300, help="seconds per child")
     ap.add_argument("--only", default=None, help="latency, 25 or 64")
     ap.add_argument("--max-positions", type=int, default=0, help="full-length chains over this many positions (0: 31-position chains)")
+    ap.add_argument("--suppress-ab", action="store_true", help="with --max-positions: lists cleared / suppress_default, alternating")
+    ap.add_argument("--suppress", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--child", nargs=3, metavar=("CASE", "BEAM", "TMP"), help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        print(json.dumps(child(a.child[0], int(a.child[1]), a.iters, a.child[2], a.max_positions)))
+        print(json.dumps(child(a.child[0], int(a.child[1]), a.iters, a.child[2], a.max_positions, a.suppress)))
         return 0
     runs = [("latency", 1), ("latency", a.beam), ("25", 1), ("25", a.beam), ("64", 1), ("64", a.beam)]
     if a.only:
         runs = [r for r in runs if r[0] == a.only]
+    runs = [r + (0,) for r in runs]
+    if a.suppress_ab and a.max_positions:
+        runs = [(c, b, s) for c, b, _ in runs if c != "latency" for s in (0, 1, 0, 1)]
     results = []
     with tempfile.TemporaryDirectory() as tmp:
-        for case, beam in runs:
+        for case, beam, suppress in runs:
             cmd = [sys.executable, os.path.abspath(__file__), "--iters", str(a.iters), "--max-positions", str(a.max_positions),
-                   "--child", case, str(beam), tmp]
+                   "--suppress", str(suppress), "--child", case, str(beam), tmp]
             try:
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
             except subprocess.TimeoutExpired:

@@ -40,7 +40,7 @@ STATUS_NAMES = {0: "WT_OK", 1: "WT_ERR_INVALID_ARG", 2: "WT_ERR_IO", 3: "WT_ERR_
 CAPI_SYMBOLS = [
     "wt_device_alloc", "wt_device_free", "wt_device_upload", "wt_device_download", "wt_device_synchronize",
     "wt_engine_create", "wt_engine_destroy", "wt_last_error", "wt_engine_dims",
-    "wt_engine_set_option", "wt_engine_get_option", "wt_engine_set_prompt", "wt_engine_set_context", "wt_engine_set_contexts", "wt_transcribe_pcm", "wt_transcribe_long_pcm", "wt_transcribe_file",
+    "wt_engine_set_option", "wt_engine_get_option", "wt_engine_set_prompt", "wt_engine_set_context", "wt_engine_set_contexts", "wt_engine_set_suppress", "wt_vocab_default_suppress", "wt_transcribe_pcm", "wt_transcribe_long_pcm", "wt_transcribe_file",
     "wt_logmel_batch", "wt_logmel_batch_dev", "wt_encdec_tokens_batch",
     "wt_encdec_tokens_batch_dev", "wt_transcribe_tokens_batch_dev", "wt_pipeline_submit_dev", "wt_pipeline_submit_pcm_dev", "wt_pipeline_collect",
     "wt_encdec_debug_batch",
@@ -67,7 +67,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_self_attention_long",
     "wt_dbg_self_attention_prefill", "wt_dbg_self_attention_long_gather",
     "wt_dbg_self_attention_long_ragged", "wt_dbg_self_attention_prefill_ragged", "wt_dbg_dec_ln_gemm_ragged", "wt_dbg_ragged_cap",
-    "wt_dbg_timestamp_select", "wt_dbg_token_scores", "wt_dbg_sample_select",
+    "wt_dbg_timestamp_select", "wt_dbg_token_scores", "wt_dbg_sample_select", "wt_dbg_suppress_logits",
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
     "wt_dbg_pcm_to_planes",
     "wt_dbg_gemm_addressed", "wt_dbg_plane_gemm_plan", "wt_dbg_gemm_ln_fused", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes", "wt_dbg_encoder_attention_at",
@@ -150,6 +150,9 @@ def lib() -> ctypes.CDLL:
         L.wt_engine_set_prompt.argtypes = [c_void_p, ip64, c_int]
         L.wt_engine_set_context.argtypes = [c_void_p, ip64, c_int]
         L.wt_engine_set_contexts.argtypes = [c_void_p, ip64, ip32, c_int]
+        L.wt_engine_set_suppress.argtypes = [c_void_p, ip64, c_int, ip64, c_int]
+        L.wt_vocab_default_suppress.argtypes = [c_void_p, ip64, c_int, ip32, ip64, c_int, ip32]
+        L.wt_dbg_suppress_logits.argtypes = [c_void_p, c_int, c_int, c_int, fp, fp, ip64, c_int, ip64, c_int, c_int]
         L.wt_transcribe_long_batch.argtypes = [c_void_p, POINTER(fp), POINTER(c_size_t), c_int]
         L.wt_last_file_text.argtypes = [c_void_p, c_int, c_char_p, c_size_t, POINTER(c_size_t)]
         L.wt_last_window_files.argtypes = [c_void_p, ip32, c_int]
@@ -510,6 +513,16 @@ class Vocab:
                                                                    int(win_ticks), int(seg_ticks), out, cap, byref(adv)))
         return segs, adv.value
 
+    def default_suppress(self):
+        """Whisper's default suppression lists from this vocabulary (wt_vocab_default_suppress):
+        (ids masked at every generated position, ids masked at the first one), int64, each sorted and unique."""
+        ids, first = np.zeros(1024, np.int64), np.zeros(1024, np.int64)
+        n, nf = c_int32(0), c_int32(0)
+        rc = lib().wt_vocab_default_suppress(self._v, _ip64(ids), ids.size, byref(n), _ip64(first), first.size, byref(nf))
+        if rc != WT_OK:
+            raise WtError(rc, "default_suppress: more than 1024 ids")
+        return ids[: n.value].copy(), first[: nf.value].copy()
+
     def split_words(self, ids, unicode_only: bool = False) -> np.ndarray:
         """Whisper's split_to_word_tokens (wt_vocab_split_words, DESIGN.md section 21) on a row of ids, usually a clip's
         text ids and then EOT: the id counts of its words, int32; they add up to len(ids).  unicode_only: the split of the
@@ -629,6 +642,29 @@ class Engine:
         flat = np.ascontiguousarray(flat, dtype=np.int64)
         self._check(lib().wt_engine_set_contexts(self._h, flat.ctypes.data_as(POINTER(c_int64)),
                                                  offsets.ctypes.data_as(POINTER(c_int32)), len(rows)))
+
+    def set_suppress(self, ids=(), first_ids=()) -> None:
+        """Whisper's SuppressTokens / SuppressBlank (wt_engine_set_suppress): every full-length
+        decode masks `ids` at every generated position and `first_ids` at the first one, on the device, in front of every
+        other decoding rule.  Two empty lists clear (options suppress_ids, suppress_first_ids; suppress_default = 1
+        installs Whisper's defaults from the vocabulary)."""
+        a = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        f = np.ascontiguousarray(first_ids, dtype=np.int64).reshape(-1)
+        self._check(lib().wt_engine_set_suppress(self._h, _ip64(a) if a.size else None, a.size,
+                                                 _ip64(f) if f.size else None, f.size))
+
+    def dbg_suppress_logits(self, logits, ids=(), first_ids=(), first=False, V=None):
+        """suppress_logits (k_suppress.hip) on logits [rows][ldl] whose first V columns are the vocabulary (default: all
+        of them): the rows with -inf at the listed ids, and at first_ids when `first` is set; padding columns included."""
+        logits = _f32(logits)
+        rows, ldl = logits.shape
+        a = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        f = np.ascontiguousarray(first_ids, dtype=np.int64).reshape(-1)
+        out = np.zeros_like(logits)
+        self._check(lib().wt_dbg_suppress_logits(self._h, rows, ldl if V is None else int(V), ldl, _fp(logits), _fp(out),
+                                                 _ip64(a) if a.size else None, a.size, _ip64(f) if f.size else None, f.size,
+                                                 int(bool(first))))
+        return out
 
     # -- shapes ----------------------------------------------------------------------
     @property

@@ -48,6 +48,10 @@ void usage(const char* argv0) {
             << "  --inputs a.wav,b.wav  with --long --timestamps --seek: the recordings side by side, one window of every file\n"
             << "                  per decoder chain; prints every file's text under a \"== <path>\" line\n"
             << "  --context-ids 1,2,3  with --max-positions: token ids fed in front of the prompt (Whisper's initial_prompt)\n"
+            << "  --suppress-default  with --max-positions: Whisper's default logit suppression (the non-speech symbols and\n"
+            << "                  the special ids at every position, the bare space and EOT at the first)\n"
+            << "  --suppress-tokens 1,2,3  with --max-positions: token ids never generated; --suppress-blank adds the bare\n"
+            << "                  space and EOT at the first generated position\n"
             << "  --word-timestamps  with --timestamps: align every word to the audio and print, behind the segment lines,\n"
             << "                  one line per word: t0 t1 text (seconds)\n"
             << "  --alignment-heads 2:2,3:0,...  with --word-timestamps: the layer:head pairs to align on (default: every\n"
@@ -56,8 +60,9 @@ void usage(const char* argv0) {
 }  // namespace
 
 int main(int argc, char* argv[]) {
-  std::string model_prefix, vocab, input, inputs, lang, beam, max_positions, temperature, seed, cr_threshold, context_ids, alignment_heads;
-  bool word_timestamps = false;
+  std::string model_prefix, vocab, input, inputs, lang, beam, max_positions, temperature, seed, cr_threshold, context_ids, alignment_heads,
+      suppress_tokens;
+  bool word_timestamps = false, suppress_default = false, suppress_blank = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
        no_condition = false;
   for (int i = 1; i < argc; ++i) {
@@ -84,6 +89,14 @@ int main(int argc, char* argv[]) {
     }
     if (a == "--word-timestamps") {
       word_timestamps = true;
+      continue;
+    }
+    if (a == "--suppress-default") {
+      suppress_default = true;
+      continue;
+    }
+    if (a == "--suppress-blank") {
+      suppress_blank = true;
       continue;
     }
     if (a == "--skip-silence") {
@@ -124,6 +137,7 @@ int main(int argc, char* argv[]) {
     else if (a == "--compression-ratio-threshold") cr_threshold = v;
     else if (a == "--context-ids") context_ids = v;
     else if (a == "--alignment-heads") alignment_heads = v;
+    else if (a == "--suppress-tokens") suppress_tokens = v;
     else {
       std::cerr << "The following argument was not expected: " << a << "\n";
       usage(argv[0]);
@@ -276,6 +290,64 @@ int main(int argc, char* argv[]) {
     if (wt_engine_set_context(encdec.handle(), ids.data(), int(ids.size())) != WT_OK) {
       std::cerr << "--context-ids: " << wt_last_error(encdec.handle()) << "\n";
       return 105;
+    }
+  }
+  if (suppress_default || suppress_blank || !suppress_tokens.empty()) {
+    if (max_positions.empty()) {
+      std::cerr << "--suppress-default, --suppress-tokens and --suppress-blank require --max-positions\n";
+      return 105;
+    }
+    if (suppress_default && (suppress_blank || !suppress_tokens.empty())) {
+      std::cerr << "--suppress-default: not together with --suppress-tokens or --suppress-blank\n";
+      return 105;
+    }
+    if (suppress_blank && suppress_tokens.empty()) {
+      std::cerr << "--suppress-blank requires --suppress-tokens\n";
+      return 105;
+    }
+    if (suppress_default) {
+      if (wt_engine_set_option(encdec.handle(), "suppress_default", 1) != WT_OK) {
+        std::cerr << "--suppress-default: " << wt_last_error(encdec.handle()) << "\n";
+        return 105;
+      }
+    } else {
+      std::vector<int64_t> ids, first;
+      const char* p = suppress_tokens.c_str();
+      bool ok = true;
+      while (ok) {
+        char* end = nullptr;
+        const long long id = std::strtoll(p, &end, 10);
+        ok = end != p && id >= 0;
+        if (!ok) break;
+        ids.push_back(id);
+        if (!*end) break;
+        ok = *end == ',';
+        p = end + 1;
+      }
+      if (!ok || ids.size() > 1024) {
+        std::cerr << "--suppress-tokens: expected at most 1024 token ids separated by commas, got " << suppress_tokens << "\n";
+        return 105;
+      }
+      if (suppress_blank) {  // the default first-list of the vocabulary, below the model's n_vocab
+        wt_vocab* vv = nullptr;
+        wt_dims dims;
+        std::vector<int64_t> all(1024), f(1024);
+        int32_t n = 0, nf = 0;
+        if (wt_vocab_open(vocab.c_str(), multilingual ? 1 : 0, &vv) != WT_OK || wt_engine_dims(encdec.handle(), &dims) != WT_OK ||
+            wt_vocab_default_suppress(vv, all.data(), 1024, &n, f.data(), 1024, &nf) != WT_OK) {
+          std::cerr << "--suppress-blank: could not form the list from " << vocab << "\n";
+          wt_vocab_close(vv);
+          return 105;
+        }
+        wt_vocab_close(vv);
+        for (int i = 0; i < nf; ++i) {
+          if (f[size_t(i)] < dims.n_vocab) first.push_back(f[size_t(i)]);
+        }
+      }
+      if (wt_engine_set_suppress(encdec.handle(), ids.data(), int(ids.size()), first.data(), int(first.size())) != WT_OK) {
+        std::cerr << "--suppress-tokens: " << wt_last_error(encdec.handle()) << "\n";
+        return 105;
+      }
     }
   }
   if (seek || no_condition) {

@@ -289,6 +289,16 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
   } else if (k == "full_beam") {
     if (value < 0 || value > 1) return fail(h, WT_ERR_INVALID_ARG, "full_beam must be 0 or 1");
     e.full_beam = value;
+  } else if (k == "suppress_default") {
+    // logit suppression: 1 = Whisper's default lists from the engine's vocabulary, 0 = none
+    if (value < 0 || value > 1) return fail(h, WT_ERR_INVALID_ARG, "suppress_default must be 0 or 1");
+    try {
+      e.set_suppress_default(value == 1);
+    } catch (const wt::Error& err) {
+      return fail(h, err.code, err.what());
+    } catch (const std::exception& err) {
+      return fail(h, WT_ERR_DEVICE, err.what());
+    }
   } else if (k == "bf16") {
     // bf16 storage mode (BASELINE configs[3]); the first switch reads the weight file again for the bf16 copies
     try {
@@ -331,6 +341,18 @@ int wt_engine_set_contexts(wt_engine* h, const int64_t* ids, const int32_t* offs
   return WT_OK;
 }
 
+int wt_engine_set_suppress(wt_engine* h, const int64_t* ids, int n, const int64_t* first_ids, int n_first) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  try {
+    h->impl->set_suppress(ids, n, first_ids, n_first);
+  } catch (const wt::Error& err) {
+    return fail(h, err.code, err.what());
+  } catch (const std::exception& err) {
+    return fail(h, WT_ERR_DEVICE, err.what());
+  }
+  return WT_OK;
+}
+
 int wt_engine_set_alignment_heads(wt_engine* h, const int32_t* layer_head, int n) {
   if (!h) return WT_ERR_INVALID_ARG;
   try {
@@ -366,6 +388,8 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "alignment_heads") *value = long(e.alignment_heads_in_effect().size());  // read-only: the count in effect
   else if (k == "context_ids") *value = long(e.context_ids.size());  // read-only: ids kept by wt_engine_set_context
   else if (k == "context_clips") *value = long(e.clip_contexts.size());  // read-only: clips given to wt_engine_set_contexts
+  else if (k == "suppress_ids") *value = long(e.suppress_ids.size());  // read-only: the lists of wt_engine_set_suppress in effect
+  else if (k == "suppress_first_ids") *value = long(e.suppress_first_ids.size());
   else if (k == "graphs_cached") *value = e.graphs_cached();          // read-only: captured decoder graphs held
   else if (k == "stop_at_eot") *value = e.stop_at_eot;
   else if (k == "verbose") *value = e.verbose;
@@ -1123,6 +1147,19 @@ int wt_vocab_seek_step(const wt_vocab* v, const int64_t* g, int n, int win_ticks
   std::vector<wt::Segment> segs;
   *advance_ticks = wt::seek_step(v->vocab, g, n, win_ticks, seg_ticks, &segs);
   return copy_segments(segs, out, cap);
+}
+
+int wt_vocab_default_suppress(const wt_vocab* v, int64_t* ids, int cap, int32_t* n, int64_t* first_ids, int first_cap,
+                              int32_t* n_first) {
+  if (!v || !n || !n_first || cap < 0 || first_cap < 0 || (cap > 0 && !ids) || (first_cap > 0 && !first_ids)) {
+    return WT_ERR_INVALID_ARG;
+  }
+  std::vector<long long> a, f;
+  wt::default_suppress(v->vocab, v->vocab.n_vocab, &a, &f);
+  *n = int32_t(a.size()), *n_first = int32_t(f.size());
+  for (size_t i = 0; i < a.size() && i < size_t(cap); ++i) ids[i] = a[i];
+  for (size_t i = 0; i < f.size() && i < size_t(first_cap); ++i) first_ids[i] = f[i];
+  return a.size() <= size_t(cap) && f.size() <= size_t(first_cap) ? WT_OK : WT_ERR_BUFFER;
 }
 
 static int copy_counts(const std::vector<int>& counts, int32_t* out, int cap) {

@@ -1903,6 +1903,29 @@ int wt_dbg_align_dtw(wt_engine* h, int clips, int N_max, int ld, const float* C,
   });
 }
 
+int wt_dbg_suppress_logits(wt_engine* h, int rows, int V, int ldl, const float* logits, float* out, const int64_t* ids, int n,
+                           const int64_t* first_ids, int n_first, int first) {
+  if (!h || !logits || !out || (n > 0 && !ids) || (n_first > 0 && !first_ids)) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    h->impl->bind_device();
+    // a shape the launcher refuses allocates nothing of its size: the launcher itself is asked, and throws
+    const bool ok = rows >= 1 && rows <= wt::kSuppressRowsMax && V >= 1 && ldl >= V && n >= 0 && n <= wt::kSuppressIdsMax &&
+                    n_first >= 0 && n_first <= wt::kSuppressIdsMax;
+    std::vector<int> list;  // the engine's buffer layout: the always-ids, then the first-ids; an id no int holds: none
+    for (int i = 0; ok && i < n + n_first; ++i) {
+      const int64_t id = i < n ? ids[i] : first_ids[i - n];
+      list.push_back(id >= 0 && id <= std::numeric_limits<int>::max() ? int(id) : -1);
+    }
+    DevArr<float> dlog(ok ? size_t(rows) * size_t(ldl) : 0, ok ? logits : nullptr);
+    DevArr<int> dids(list);
+    wt::SuppressArgs u;
+    u.logits = dlog.p; u.ldl = ldl; u.V = V; u.rows = rows; u.ids = dids.p; u.n = n; u.n_first = n_first; u.first = first;
+    wt::launch_suppress_logits(u, h->impl->stream());
+    h->impl->sync();
+    dlog.to_host(out);
+  });
+}
+
 int wt_dbg_set_alignment(wt_engine* h, int keep, int mode, int sub) {
   if (!h || keep > 1 || mode > 1 || sub > wt::kAlignClipsMax) return WT_ERR_INVALID_ARG;
   wt::Engine& e = *h->impl;

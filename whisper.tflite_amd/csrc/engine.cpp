@@ -842,6 +842,7 @@ void Engine::release() noexcept {
                   static_cast<void*>(fw_.h_count), static_cast<void*>(fw_.h_prm)})
     if (p) (void)hipHostFree(p);
   fw_ = FullWorkspace();
+  d_suppress_ = nullptr;  // (in allocations_)
   for (void* p : {static_cast<void*>(rw_.h_ids), static_cast<void*>(rw_.h_lp), static_cast<void*>(rw_.h_start)})
     if (p) (void)hipHostFree(p);
   rw_ = RaggedWorkspace();
@@ -1742,6 +1743,49 @@ void Engine::set_contexts(const int64_t* ids, const int32_t* offsets, int n_clip
   context_ids.clear();
 }
 
+void Engine::set_suppress(const int64_t* ids, int n, const int64_t* first_ids, int n_first) {
+  if (n < 0 || n > kSuppressIdsMax || n_first < 0 || n_first > kSuppressIdsMax || (n > 0 && !ids) || (n_first > 0 && !first_ids)) {
+    throw Error(kErrInvalidArg, "suppress: 0 .. 1024 ids per list");
+  }
+  require_idle();  // (a chain in flight reads the buffer)
+  if (n == 0 && n_first == 0) {
+    suppress_ids.clear(), suppress_first_ids.clear();
+    return;
+  }
+  if (monolith_) throw Error(kErrUnsupported, "suppress: not on a Monolith engine (the reference's single graph takes no logit filter)");
+  std::vector<int> host;
+  for (int i = 0; i < n + n_first; ++i) {
+    const int64_t id = i < n ? ids[i] : first_ids[i - n];
+    if (id < 0 || id >= dims_.n_vocab) throw Error(kErrInvalidArg, "suppress: a token id outside the model's vocabulary");
+    if (i < n && id == vocab_.token_eot) {
+      throw Error(kErrInvalidArg, "suppress: EOT cannot be suppressed at every position (the allowed set must never be empty)");
+    }
+    host.push_back(int(id));
+  }
+  bind_device();
+  if (!d_suppress_) {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, 2 * size_t(kSuppressIdsMax) * sizeof(int)));
+    allocations_.push_back(p);
+    HIPCHK(hipMemset(p, 0, 2 * size_t(kSuppressIdsMax) * sizeof(int)));
+    d_suppress_ = static_cast<int*>(p);
+  }
+  sync();  // full-length calls are synchronous: nothing reads the buffer now
+  HIPCHK(hipMemcpy(d_suppress_, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));  // (blocking)
+  suppress_ids.assign(host.begin(), host.begin() + n);
+  suppress_first_ids.assign(host.begin() + n, host.end());
+}
+
+void Engine::set_suppress_default(bool on) {
+  if (!on) return set_suppress(nullptr, 0, nullptr, 0);
+  std::vector<long long> a, f;
+  default_suppress(vocab_, dims_.n_vocab, &a, &f);
+  if (a.empty() && f.empty()) throw Error(kErrUnsupported, "suppress_default: the vocabulary yields no id below the model's n_vocab");
+  if (a.size() > size_t(kSuppressIdsMax) || f.size() > size_t(kSuppressIdsMax)) throw Error(kErrUnsupported, "suppress_default: more than 1024 ids");
+  static_assert(sizeof(long long) == sizeof(int64_t), "id lists are int64");
+  set_suppress(reinterpret_cast<const int64_t*>(a.data()), int(a.size()), reinterpret_cast<const int64_t*>(f.data()), int(f.size()));
+}
+
 std::vector<long long> Engine::fed_prompt_of(int clip) const {
   std::vector<long long> out;
   const std::vector<long long>& c = clip_contexts[size_t(clip)];
@@ -2445,6 +2489,9 @@ void Engine::check_timestamp_call() const {
   if (!clip_contexts.empty() && max_positions <= 0) {
     throw Error(kErrUnsupported, "contexts: full-length decoding only, set the option max_positions (32 .. n_text_ctx) or clear the contexts");
   }
+  if (suppressing() && max_positions <= 0) {
+    throw Error(kErrUnsupported, "suppress: full-length decoding only, set the option max_positions (32 .. n_text_ctx) or clear the lists");
+  }
   if (!clip_contexts.empty() && word_timestamps) {
     throw Error(kErrUnsupported, "contexts: not with word_timestamps (the alignment pass takes one prompt length per call)");
   }
@@ -2551,6 +2598,8 @@ void Engine::check_full_call() const {
     if (seek) nb("not with seek");
     if (word_timestamps) nb("not with word_timestamps");
   }
+  // (a suppressed row is selected by ts_select or by the sampler's greedy step: both take an EOT inside the vocabulary)
+  if (suppressing() && (vocab_.token_eot < 0 || vocab_.token_eot >= dims_.n_vocab)) no("suppress: the model's vocabulary has no EOT id (token_eot >= n_vocab)");
   if (timestamps && !has_timestamp_tokens()) no("timestamps: the model's vocabulary has no timestamp ids");
   if (scores && !has_no_speech_token()) no("scores: the model's vocabulary has no <|nospeech|> id");
   if (!context_ids.empty() && long(fed_prompt().size()) >= max_positions) {
@@ -2615,7 +2664,7 @@ void Engine::ensure_full_workspace(int batch) {
     fw_.kv = static_cast<float*>(alloc(size_t(c.n_text_layer) * 2 * size_t(batch) * cap * d * sizeof(float)));
     fw_.kv_clips = batch;
   }
-  if ((timestamps || scores || sampling()) && !fw_.ts_logits) {  // the logits of a step: the timestamp rules and the scores read whole rows
+  if ((timestamps || scores || sampling() || suppressing()) && !fw_.ts_logits) {  // the logits of a step: the timestamp rules, the scores and the suppression work on whole rows
     const size_t ldl = (size_t(c.n_vocab) + 3) & ~size_t(3);
     fw_.ts_ldl = int(ldl);
     fw_.ts_logits = static_cast<float*>(alloc(C * ldl * sizeof(float)));
@@ -2639,6 +2688,10 @@ void Engine::ensure_full_workspace(int batch) {
     if (!fw_.h_nosp) fw_.h_nosp = static_cast<float*>(pinned(C * sizeof(float)));
     if (!fw_.h_sum) fw_.h_sum = static_cast<double*>(pinned(C * sizeof(double)));
     if (!fw_.h_count) fw_.h_count = static_cast<int*>(pinned(C * sizeof(int)));
+  }
+  if (suppressing() && !timestamps && !sampling()) {  // the greedy step on the sampler's kernels (alloc clears: T = 0)
+    if (!fw_.sm_part) fw_.sm_part = static_cast<SamplePart*>(alloc(C * size_t(ts_chunks(c.n_vocab)) * sizeof(SamplePart)));
+    if (!fw_.zero_prm) fw_.zero_prm = static_cast<SampleParams*>(alloc(sizeof(SampleParams)));
   }
   if (sampling()) {
     if (!fw_.sm_part) fw_.sm_part = static_cast<SamplePart*>(alloc(C * size_t(ts_chunks(c.n_vocab)) * sizeof(SamplePart)));
@@ -2703,7 +2756,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   last_alignment.clear();
   clear_last_scores();  // (the decode info with them)
   if (beam_size > 1) return decode_beam_full(batch, ids, ids_stride, n_ids);  // (full_beam = 1: check_full_call)
-  const bool ts = timestamps != 0, sc = scores != 0, smp = sampling();
+  const bool ts = timestamps != 0, sc = scores != 0, smp = sampling(), sup = suppressing();
+  const int n_sup = int(suppress_ids.size()), n_sup_first = int(suppress_first_ids.size());
   ensure_batch(batch);
   ensure_full_workspace(batch);  // (before any capture: nothing may be allocated inside one)
   // per-clip contexts (set_contexts): the chain runs in slots, the fed prompts right-aligned so that
@@ -2756,7 +2810,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   if (rag) p.pos_start = rw_.start, p.pos_limit = P;
   p.absorbed = absorbed; p.n_abs = n_abs; p.chunks = chunks; p.e = slot.e_planes; p.cross_kv = slot.cross_kv;
   p.split = fc2_split(); p.dw = &dw; p.ldy = V;
-  if (ts || sc || smp) p.Y = fw_.ts_logits, p.ldy = fw_.ts_ldl;  // the timestamp rules, the scores and the sampler read the whole row
+  // the timestamp rules, the scores and the sampler read the whole row, the suppression writes into it
+  if (ts || sc || smp || sup) p.Y = fw_.ts_logits, p.ldy = fw_.ts_ldl;
   ScoreArgs sa;
   if (sc) {
     sa.logits = fw_.ts_logits; sa.ldl = fw_.ts_ldl; sa.V = V; sa.batch = batch; sa.part = fw_.sc_part;
@@ -2784,15 +2839,25 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
         launch_no_speech_prob(sa, vocab_.token_solm, fw_.sc_nosp, st);
       }
       if (logits) {
+        if (sup) {  // Whisper's SuppressTokens / SuppressBlank, behind the no-speech probability and in front of every rule
+          SuppressArgs u;
+          u.logits = fw_.ts_logits; u.ldl = fw_.ts_ldl; u.V = V; u.rows = batch; u.ids = d_suppress_;
+          u.n = n_sup; u.n_first = n_sup_first; u.first = last + 1 - n_prompt == 0;
+          launch_suppress_logits(u, st);
+        }
         if (sc) {  // the partial sums of the allowed set, from the state BEFORE the selection advances it
           sa.state = ts ? fw_.ts_state : nullptr; sa.n_gen = last + 1 - n_prompt; sa.pos = last;
           launch_score_partial(sa, st);
         }
-        if (smp) {  // a sample at the temperature the parameter block holds (0: the greedy step), in both modes
+        // a sample at the temperature the parameter block holds (0: the greedy step), in both modes; a suppressed row
+        // without timestamps takes the same kernels under the block of zeros: the fused argmax records of the logits
+        // GEMM were formed before the filter, and T = 0 here is select_token's rule (larger logit, then larger id)
+        if (smp || (sup && !ts)) {
           SampleArgs t;
           t.logits = fw_.ts_logits; t.ldl = fw_.ts_ldl; t.V = V; t.batch = batch;
           t.eot = vocab_.token_eot; t.beg = vocab_.token_beg; t.max_initial = int(max_initial_timestamp);
-          t.n_gen = last + 1 - n_prompt; t.params = fw_.sm_prm; t.part = fw_.sm_part; t.state = ts ? fw_.ts_state : nullptr;
+          t.n_gen = last + 1 - n_prompt; t.params = smp ? fw_.sm_prm : fw_.zero_prm; t.part = fw_.sm_part;
+          t.state = ts ? fw_.ts_state : nullptr;
           t.ids = d_ids; t.ids_stride = stride; t.pos = last; t.stop_at_eot = int(stop_at_eot);
           t.n_ids = dw.n_ids; t.finished = dw.finished;
           launch_sample_select(t, st);
@@ -2855,9 +2920,10 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       const int hi = std::min(PS, lo + 32);
       // (greedy's keys start with the slot, a beam key with -beam_size; a full-length key starts with kFullKey)
       // (the sampling kernels are one entry; temperature, seed and attempt are data, never part of the key)
-      const std::vector<long long> key{kFullKey, slot_idx, batch, lo, P, n_prompt, chunks, long(stop_at_eot), fc2_ksplit,
+      std::vector<long long> key{kFullKey, slot_idx, batch, lo, P, n_prompt, chunks, long(stop_at_eot), fc2_ksplit,
                                        absorbed ? 1 : 0, n_abs, slot.dec, ts ? 1 : 0, ts ? max_initial_timestamp : 0, sc ? 1 : 0,
                                        smp ? 1 : 0};
+      if (sup) key.push_back(n_sup), key.push_back(n_sup_first);  // launch constants; the ids themselves are device data
       auto it = graphs() ? graphs_.find(key) : graphs_.end();
       if (it != graphs_.end()) {
         HIPCHK(hipGraphLaunch(it->second.exec, st));
@@ -3110,7 +3176,8 @@ void Engine::decode_beam_full(int batch, int64_t* ids, int ids_stride, int32_t* 
   ensure_beam_full_workspace();  // (before any capture: nothing may be allocated inside one)
   const wtw::Dims& c = dims_;
   const int d = c.n_text_state, T = c.n_audio_ctx, V = c.n_vocab, cap = full_cap(), stride = cap + 1;
-  const bool ts = timestamps != 0, sc = scores != 0;
+  const bool ts = timestamps != 0, sc = scores != 0, sup = suppressing();
+  const int n_sup = int(suppress_ids.size()), n_sup_first = int(suppress_first_ids.size());
   const std::vector<long long> prompt = this->prompt();
   const int n_prompt = int(prompt.size());
   check_prompt_ids(prompt, kErrInvalidArg);
@@ -3170,6 +3237,12 @@ void Engine::decode_beam_full(int batch, int64_t* ids, int ids_stride, int32_t* 
         if (logits) {
           fa.pos = last;
           halves(t);
+          if (sup) {  // behind the no-speech probability, in front of every hypothesis's allowed set
+            SuppressArgs u;
+            u.logits = bf_.logits; u.ldl = bf_.ldl; u.V = V; u.rows = p.B; u.ids = d_suppress_;
+            u.n = n_sup; u.n_first = n_sup_first; u.first = t == 0;
+            launch_suppress_logits(u, st);
+          }
           launch_beam_full_partial(fa, st);
           launch_beam_full_select(fa, st);
           launch_beam_full_advance(fa, st);
@@ -3185,8 +3258,9 @@ void Engine::decode_beam_full(int batch, int64_t* ids, int ids_stride, int32_t* 
     for (int lo = 0; lo < P; lo += 32) {
       const int hi = std::min(P, lo + 32);
       // (greedy's keys start with the slot, a beam key with -beam_size, a full-length key with kFullKey)
-      const std::vector<long long> key{kBeamFullKey, slot_idx, c0, nc, lo, P, n_prompt, K, fc2_ksplit, n_abs, slot.dec, ts ? 1 : 0,
-                                       ts ? max_initial_timestamp : 0, sc ? 1 : 0};
+      std::vector<long long> key{kBeamFullKey, slot_idx, c0, nc, lo, P, n_prompt, K, fc2_ksplit, n_abs, slot.dec, ts ? 1 : 0,
+                                 ts ? max_initial_timestamp : 0, sc ? 1 : 0};
+      if (sup) key.push_back(n_sup), key.push_back(n_sup_first);  // launch constants; the ids themselves are device data
       auto it = use_graphs ? graphs_.find(key) : graphs_.end();
       if (it != graphs_.end()) {
         HIPCHK(hipGraphLaunch(it->second.exec, st));

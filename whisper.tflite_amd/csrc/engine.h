@@ -313,6 +313,18 @@ class Engine {
   void set_contexts(const int64_t* ids, const int32_t* offsets, int n_clips);
   std::vector<long long> fed_prompt_of(int clip) const;  // [prev] + clip_contexts[clip] + prompt(), or prompt() alone
   int graphs_cached() const { return int(graphs_.size()); }
+  // Logit suppression: Whisper's SuppressTokens / SuppressBlank in front of every other decoding
+  // rule of a full-length chain.  suppress_ids are masked at every generated position, suppress_first_ids at the first
+  // one (n_gen == 0, behind the whole fed prompt).  set_suppress uploads both into ONE device buffer (always-ids, then
+  // first-ids) that suppress_logits reads at run time: the counts are launch constants and part of the graph keys, the
+  // contents are not.  0 .. kSuppressIdsMax ids per list, duplicates allowed; an id outside the model's vocabulary or EOT
+  // among suppress_ids (the allowed set must never be empty): kErrInvalidArg; a Monolith engine: kErrUnsupported.
+  // n = n_first = 0 clears, and every launch sequence, graph key and workspace is then what it is without the feature.
+  // Scope: wherever max_positions decoding is (check_timestamp_call, check_full_call).
+  std::vector<long long> suppress_ids, suppress_first_ids;
+  bool suppressing() const { return !suppress_ids.empty() || !suppress_first_ids.empty(); }
+  void set_suppress(const int64_t* ids, int n, const int64_t* first_ids, int n_first);
+  void set_suppress_default(bool on);  // option suppress_default: host_util's default_suppress over the model's ids
   // Seeking long-audio transcription (wt_transcribe_long_pcm with seek = 1, longform.cpp): needs timestamps and
   // max_positions; condition_on_previous_text is read only then
   long seek = 0, condition_on_previous_text = 1;
@@ -523,7 +535,11 @@ class Engine {
     // parameter block and its pinned mirror
     SamplePart* sm_part = nullptr;
     SampleParams *sm_prm = nullptr, *h_prm = nullptr;
+    // suppression without sampling or timestamps: the greedy step runs on the sampler's kernels at T = 0 under a
+    // parameter block of zeros that is never written again (it shares ts_logits and sm_part)
+    SampleParams* zero_prm = nullptr;
   } fw_;
+  int* d_suppress_ = nullptr;  // [2 * kSuppressIdsMax]: the always-ids, then the first-ids (set_suppress)
   void ensure_full_workspace(int batch);
   struct RaggedWorkspace {  // allocated by the first ragged call: the slot-space rows [64][ragged_stride()] and the starts [64]
     long long *ids = nullptr, *h_ids = nullptr;

@@ -324,6 +324,71 @@ std::string remove_extra_spaces(const std::string& in) {
   return out;
 }
 
+void default_suppress(const VocabData& vocab, int n_limit, std::vector<long long>* ids, std::vector<long long>* first) {
+  // Whisper's non_speech_tokens: the annotation symbols a transcript of speech does not contain
+  static const char* const kSymbols[] = {
+      "\"", "#", "(", ")", "*", "+", "/", ":", ";", "<", "=", ">", "@", "[", "\\", "]", "^", "_", "`", "{", "|", "}", "~",
+      "「", "」", "『", "』", "<<", ">>", "<<<", ">>>", "--", "---", "-(", "-[", "('", "(\"", "((", "))", "(((", ")))",
+      "[[", "]]", "{{", "}}", "♪♪", "♪♪♪"};
+  static const char* const kMusical[] = {"♩", "♪", "♫", "♬", "♭", "♮", "♯"};
+  const int text_end = std::min(n_limit, vocab.token_eot);  // text ids: [0, text_end)
+  // the smallest id whose bytes are exactly s, or -1
+  auto exact = [&](const std::string& s) {
+    for (const auto& kv : vocab.id_to_token) {  // (ascending ids)
+      if (kv.first >= text_end) break;
+      if (kv.first >= 0 && kv.second == s) return kv.first;
+    }
+    return -1;
+  };
+  // the longest token whose bytes are a proper prefix of s, the smallest id among equally long ones, or -1
+  // (longer than `above` bytes: behind a leading space the prefix must reach into the symbol, so the bare " " — an id
+  // SuppressBlank masks at the first position only — never lands on the always-list)
+  auto prefix = [&](const std::string& s, size_t above) {
+    int best = -1;
+    size_t len = above;
+    for (const auto& kv : vocab.id_to_token) {
+      if (kv.first >= text_end) break;
+      const std::string& t = kv.second;
+      if (kv.first < 0 || t.empty() || t.size() >= s.size() || s.compare(0, t.size(), t) != 0) continue;
+      if (t.size() > len) best = kv.first, len = t.size();
+    }
+    return best;
+  };
+  std::vector<long long> a, f;
+  // <|startoflm|> has no name in this table: it is the id in front of <|startofprev|> in Whisper's own vocabularies
+  // (50360 multilingual; 50359 English-only, which this table calls token_transcribe)
+  const int token_startoflm = vocab.token_prev - 1;
+  for (const int id : {vocab.token_sot, vocab.token_prev, token_startoflm, vocab.token_solm, vocab.token_translate,
+                       vocab.token_transcribe}) {
+    if (id >= 0 && id < n_limit && id != vocab.token_eot) a.push_back(id);
+  }
+  auto add = [&](int id) {
+    if (id >= 0) a.push_back(id);
+  };
+  add(exact(" -"));
+  add(exact(" '"));
+  for (const char* s : kSymbols) {
+    add(exact(s));
+    add(exact(std::string(" ") + s));
+  }
+  for (const char* s : kMusical) {
+    for (const int lead : {0, 1}) {
+      const std::string w = std::string(lead ? " " : "") + s;
+      const int id = exact(w);
+      add(id >= 0 ? id : prefix(w, size_t(lead)));
+    }
+  }
+  const int blank = exact(" ");
+  if (blank >= 0) f.push_back(blank);
+  if (vocab.token_eot >= 0 && vocab.token_eot < n_limit) f.push_back(vocab.token_eot);
+  for (std::vector<long long>* v : {&a, &f}) {
+    std::sort(v->begin(), v->end());
+    v->erase(std::unique(v->begin(), v->end()), v->end());
+  }
+  *ids = a;
+  *first = f;
+}
+
 void parse_segments(const VocabData& vocab, const int64_t* ids, int n, int sample_begin, int clip, std::vector<Segment>* out) {
   int t_open = 0, begin = -1, count = 0;
   for (int i = std::max(sample_begin, 0); i < n; ++i) {

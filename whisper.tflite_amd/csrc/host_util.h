@@ -75,6 +75,16 @@ struct Segment {
 constexpr int kWindowMs = 30000;
 void parse_segments(const VocabData& vocab, const int64_t* ids, int n, int sample_begin, int clip, std::vector<Segment>* out);
 
+// Whisper's default suppression lists from a vocabulary (wt_vocab_default_suppress), ids below
+// n_limit only, each list sorted and unique.  *first: the id whose bytes are exactly " " (the smallest such id) and EOT.
+// *ids: token_sot, token_prev, token_prev - 1 (Whisper's <|startoflm|>, which this table does not name), token_solm (this
+// table's name of the <|nospeech|> id), token_translate, token_transcribe, then the non-speech symbols: for every symbol
+// s of Whisper's list the ids whose bytes are exactly s and " " + s,
+// the exact " -" and " '", and for a musical symbol without an exact match the longest token whose bytes are a proper
+// prefix of the string (the smallest id among equally long ones).  Text matches are taken among the ids below EOT; EOT
+// itself never enters *ids.  The prefix rule is not BPE: see the header.
+void default_suppress(const VocabData& vocab, int n_limit, std::vector<long long>* ids, std::vector<long long>* first);
+
 int language_count();
 int language_id(const std::string& code);  // == language_count() when absent
 const std::string& lang_code(size_t id);

@@ -551,6 +551,21 @@ void launch_score_finish(const ScoreArgs& a, hipStream_t s);   // reads the reco
 // prob[b] = exp(z[b][nosp] - logsumexp(z[b][0 .. V - 1])): score_partial over the whole row + a finish kernel
 void launch_no_speech_prob(const ScoreArgs& a, int nosp, float* prob, hipStream_t s);
 
+// ----------------------------------------------------------- suppression ---
+// k_suppress.hip (wt_engine_set_suppress): Whisper's SuppressTokens / SuppressBlank.  Row r of
+// logits [rows][ldl] gets -inf at every id of ids[0 .. n) and, with first != 0 (the first generated position), of
+// ids[n .. n + n_first).  ids is device memory, read at run time: its contents are no launch constant.  Nothing is read
+// from the logits, an id outside [0, V) is skipped.
+constexpr int kSuppressIdsMax = 1024;  // ids per list
+constexpr int kSuppressRowsMax = 128;  // rows of one launch (kDecRowsMax)
+struct SuppressArgs {
+  float* logits = nullptr;
+  int ldl = 0, V = 0, rows = 0;
+  const int* ids = nullptr;  // [n + n_first]
+  int n = 0, n_first = 0, first = 0;
+};
+void launch_suppress_logits(const SuppressArgs& a, hipStream_t s);  // throws kErrInvalidArg, as launch_ts_select
+
 // ------------------------------------------------- full-length beam search ---
 // k_beam_full.hip (option full_beam): beam search over up to full_cap() positions behind the timestamp
 // rules.  Rows are laid out row = k * clips + c as in k_beam.hip; a row's ids [stride] int64, its log-probabilities
