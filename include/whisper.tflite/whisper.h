@@ -113,6 +113,14 @@ struct ClipDecode {
   float compression_ratio = 0.0f;
 };
 
+// An addition: the samples of one 30 s window of the last transcribe() under the option "best_of" = N > 1 (wt_capi.h,
+// wt_last_best_of): the kept sample and every sample's sum of token log-probabilities and count, EOT included.
+struct ClipBestOf {
+  int picked = 0;
+  std::vector<double> sum_logprob;  // [8], zeros from N on
+  std::vector<int> n_generated;     // [8]
+};
+
 // An addition: the confidence of one 30 s window of the last transcribe() with the options "scores" = 1 and
 // "max_positions" set (wt_capi.h, wt_last_scores).
 struct ClipScore {
@@ -137,6 +145,7 @@ struct Monolith : public Engine {
   std::pair<int, float> detect_language(std::vector<float>& samples);
   std::vector<ClipScore> scores() const;  // an addition: as EncDec::scores
   std::vector<ClipDecode> decode_info() const;  // an addition: as EncDec::decode_info
+  std::vector<ClipBestOf> best_of() const;      // an addition: as EncDec::best_of
   wt_engine* handle() const { return handle_; }
 
  private:
@@ -173,6 +182,8 @@ struct EncDec : public Engine {
   std::vector<ClipScore> scores() const;
   // one per window of the last transcribe(); empty when that call neither sampled nor ran the temperature fall-back
   std::vector<ClipDecode> decode_info() const;
+  // one per window of the last transcribe(); empty unless some window was kept from an attempt that ran "best_of" > 1 samples
+  std::vector<ClipBestOf> best_of() const;
   // for the batch entry points and options of wt_capi.h: wt_engine_set_option(handle(), "beam_size", 5) makes both
   // transcribe() overloads decode with beam search
   wt_engine* handle() const { return handle_; }

@@ -131,7 +131,8 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * without "timestamps", "scores" and "skip_silence" on every full-length entry point, wt_transcribe_pcm / _file and
  * wt_transcribe_long_pcm with fixed windows included; with "scores" the sums, counts and token log-probabilities are the
  * chosen hypothesis's, and wt_last_beam_scores is valid too.  WT_ERR_UNSUPPORTED with full_beam = 1 and beam_size > 1:
- * what beam_size and "max_positions" refuse, "temperature" > 0 and "temperature_fallback", either kind of context,
+ * what beam_size and "max_positions" refuse, "temperature" > 0 and "temperature_fallback" (unless "fallback_beam" = 1,
+ * see wt_last_best_of below), either kind of context,
  * "seek", "word_timestamps" and wt_transcribe_long_batch; the engine stays usable after each),
  * "last_batches" (N = the next N pipelined submits are the last of a job: they are decoded one chain per batch, the very
  * last on the encoder's stream, so the pipeline drains sooner; counts down to 0 by itself, may be set with batches in
@@ -360,6 +361,32 @@ typedef struct wt_clip_decode { int32_t temperature_milli, attempts, needs_fallb
  * whose clip index in the counter is its index in the file); returns the clip count, or -WT_ERR_INVALID_ARG when that
  * decode did neither (as wt_last_scores) */
 int wt_last_decode_info(const wt_engine* h, wt_clip_decode* out, int cap);
+
+/* Several samples per clip (option "best_of" = N, 1 = default .. 8).  In a full-length decode every
+ * attempt whose temperature is above 0 — a fixed "temperature" > 0, or the later attempts of "temperature_fallback" —
+ * decodes N samples of every clip in one chain and keeps the FIRST sample with the largest sum_logprob / n_generated in
+ * float64 (every generated id counted, EOT included: the avg_logprob of wt_last_scores; Whisper's ranker divides by the
+ * length without EOT).  A sample whose average is NaN never wins; where all are, sample 0 is kept.  Sample j draws from
+ * the Philox stream of wt_last_decode_info's counter with the attempt word attempt + (j << 16): sample 0 is the decode
+ * of "best_of" = 1 under the same seed, bit for bit.  An attempt at temperature 0 draws nothing and ignores the option,
+ * as Whisper does; "best_of" > 1 with "temperature" = 0 and no fall-back changes nothing.  Thresholds, scores, segments
+ * and wt_last_decode_info are those of the kept sample.  With sampling or fall-back set, "best_of" > 1 is
+ * WT_ERR_UNSUPPORTED (the engine stays usable) beside a context of either kind, "seek", "word_timestamps",
+ * "stop_at_eot" = 0, wt_transcribe_long_batch, a decoder without the absorbed cross-attention ("cross_absorb" = 0), and
+ * wherever "max_positions" refuses a call; with "beam_size" > 1 a temperature is refused as before, unless:
+ * option "fallback_beam" (0 = default, 1; it means something only with "full_beam" = 1 and beam_size 2..8).  At 1 such a
+ * call accepts "temperature" and "temperature_fallback": an attempt at temperature 0 — the schedule's first when
+ * "temperature" = 0 — is full-length beam search over all clips, its chosen hypothesis's ids, token log-probabilities,
+ * float64 sum, length (EOT counted) and no-speech probability judged by the thresholds like any attempt's; an attempt
+ * above 0 runs the sampler with "best_of" rows per clip and ignores the beam, as Whisper does; a fixed "temperature" > 0
+ * without fall-back is a sampling call.  wt_last_beam_scores is not valid after such a call: wt_last_scores and
+ * wt_last_decode_info tell what each clip was kept with.  Everything else "full_beam" refuses stays refused.  The options
+ * of Whisper's default command line: beam_size 5, full_beam 1, fallback_beam 1, best_of 5, temperature_fallback 1.
+ * wt_last_best_of: per clip of the last synchronous decode (after wt_transcribe_long_pcm with fixed windows: per window)
+ * the kept sample picked[i] and every sample's sum_logprob[i][8] / n_generated[i][8] (zeros from N on; a clip whose kept
+ * attempt ran at temperature 0: sample 0 alone, with "scores" its own sum and count).  Returns the clip count (at most cap
+ * clips written), or -WT_ERR_INVALID_ARG when no clip of that decode was kept from an attempt that ran N > 1 samples. */
+int wt_last_best_of(const wt_engine* h, int32_t* picked, double* sum_logprob, int32_t* n_generated, int cap);
 
 /* Seeking long-audio transcription (option "seek" = 1 together with "timestamps" = 1 and "max_positions", else a decode
  * call is WT_ERR_UNSUPPORTED).  wt_transcribe_long_pcm then decodes one window at a time as Whisper's

@@ -175,6 +175,31 @@ int wt_dbg_sample_select(wt_engine* h, int B, int V, const float* logits, const 
                          const int32_t* n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
                          const float* temperature, uint64_t seed, int attempt, int clip_base, int pos, int64_t* token,
                          double* L, float* M, float* key);
+/* The grouped sampler (SampleArgs::group, option "best_of"): ONE launch over B rows that are `group`
+ * samples of clips = ceil(B / group) clips, row r = sample r / clips of clip r % clips.  Arguments as
+ * wt_dbg_sample_select, except: every row holds the same number n_ids of ids; temperature [clips] is per clip; row0 is the
+ * first clip's entry of the parameter block.  Sample j draws under the attempt word attempt + (j << 16), clip c under the
+ * clip word clip_base + row0 + c.  group = 1 is the ungrouped launch.  Needs group <= 8 and, for group > 1, B <= 128 and
+ * row0 + clips <= 64 (group = 1: row0 + B <= 64), else WT_ERR_INVALID_ARG before anything is launched. */
+int wt_dbg_sample_select_group(wt_engine* h, int B, int group, int V, const float* logits, const int64_t* ids, int ids_stride,
+                               int n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
+                               const float* temperature, uint64_t seed, int attempt, int clip_base, int row0, int pos,
+                               int64_t* token, double* L, float* M, float* key);
+/* best_of_begin (k_best_of.hip): the start of a chain over N samples of `clips` clips, rows
+ * r = j * clips + c.  All arrays are in / out with N * clips rows: ids [..][stride] (rows c < clips hold the clips' prompts
+ * on entry), n_ids, finished, sum (float64), count, anc [..][cap] (bytes); frozen [clips] is optional.  Needs N <= 8,
+ * N * clips <= 128, clips <= 64 and 1 <= n_prompt <= cap < stride, cap <= 448. */
+int wt_dbg_best_of_begin(wt_engine* h, int clips, int N, int n_prompt, int stride, int cap, const int32_t* frozen,
+                         int64_t* ids, int32_t* n_ids, int32_t* finished, double* sum, int32_t* count, uint8_t* anc);
+/* best_of_pick (k_best_of.hip): per clip the first sample with the largest sum / count in float64 (a NaN or a count
+ * below 1 never wins; sample 0 where none is left).  Inputs over N * clips rows, r = j * clips + c: ids [..][stride],
+ * lp [..][stride], n_ids, sum, count.  Outputs, in / out over n_out rows of which c0 .. c0 + clips - 1 are written:
+ * out_ids / out_lp [n_out][stride] (the winner's first n_ids entries, zeros behind them), out_n, out_sum, out_count,
+ * picked, all_sum / all_count [n_out][8].  Needs N <= 8, N * clips <= 128, c0 + clips <= n_out <= 64, 2 <= stride <= 449. */
+int wt_dbg_best_of_pick(wt_engine* h, int clips, int N, int c0, int n_out, int stride, const int64_t* ids, const float* lp,
+                        const int32_t* n_ids, const double* sum, const int32_t* count, int64_t* out_ids, float* out_lp,
+                        int32_t* out_n, double* out_sum, int32_t* out_count, int32_t* picked, double* all_sum,
+                        int32_t* all_count);
 /* score_partial + score_finish (k_scores.hip, option "scores") alone: the log-probability of the id
  * each row chose at one step.  logits [B][V]; row b of ids [B][ids_stride] holds n_ids[b] ids, the LAST of them the id
  * the step chose (any id in [0, V)), the first sample_begin the prompt.  timestamps = 0: every id is allowed; 1: the set

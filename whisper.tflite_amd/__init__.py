@@ -49,7 +49,7 @@ CAPI_SYMBOLS = [
     "wt_transcribe_long_batch", "wt_last_file_text", "wt_last_window_files",
     "wt_vocab_split_words", "wt_vocab_merge_punctuation", "wt_dtw_path",
     "wt_engine_set_alignment_heads", "wt_last_words", "wt_last_word_text",
-    "wt_last_scores", "wt_last_token_logprobs", "wt_last_segment_scores", "wt_last_decode_info",
+    "wt_last_scores", "wt_last_token_logprobs", "wt_last_segment_scores", "wt_last_decode_info", "wt_last_best_of",
     "wt_language_count", "wt_detect_language_batch", "wt_detect_language_batch_dev", "wt_detect_language_pcm", "wt_last_languages",
     "wt_last_timings", "wt_last_beam_scores", "wt_last_kernel_stats", "wt_decode_text", "wt_language_id", "wt_lang_code", "wt_wav_read_legacy",
     "wt_vocab_info", "wt_filters", "wt_write_synthetic_weights", "wt_write_synthetic_vocab",
@@ -68,6 +68,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_self_attention_prefill", "wt_dbg_self_attention_long_gather",
     "wt_dbg_self_attention_long_ragged", "wt_dbg_self_attention_prefill_ragged", "wt_dbg_dec_ln_gemm_ragged", "wt_dbg_ragged_cap",
     "wt_dbg_timestamp_select", "wt_dbg_token_scores", "wt_dbg_sample_select", "wt_dbg_suppress_logits",
+    "wt_dbg_sample_select_group", "wt_dbg_best_of_begin", "wt_dbg_best_of_pick",
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
     "wt_dbg_pcm_to_planes",
     "wt_dbg_gemm_addressed", "wt_dbg_plane_gemm_plan", "wt_dbg_gemm_ln_fused", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes", "wt_dbg_encoder_attention_at",
@@ -272,8 +273,15 @@ def lib() -> ctypes.CDLL:
                                               ip64, POINTER(ctypes.c_double), fp]
         L.wt_dbg_sample_select.argtypes = [c_void_p, c_int, c_int, fp, ip64, c_int, ip32, c_int, c_int, c_int, c_int, c_int,
                                            fp, ctypes.c_uint64, c_int, c_int, c_int, ip64, POINTER(ctypes.c_double), fp, fp]
+        dp, u8p = POINTER(ctypes.c_double), POINTER(ctypes.c_uint8)
+        L.wt_dbg_sample_select_group.argtypes = [c_void_p, c_int, c_int, c_int, fp, ip64, c_int, c_int, c_int, c_int, c_int,
+                                                 c_int, c_int, fp, ctypes.c_uint64, c_int, c_int, c_int, c_int, ip64, dp, fp, fp]
+        L.wt_dbg_best_of_begin.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, ip32, ip64, ip32, ip32, dp, ip32, u8p]
+        L.wt_dbg_best_of_pick.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, ip64, fp, ip32, dp, ip32, ip64, fp,
+                                          ip32, dp, ip32, ip32, dp, ip32]
         L.wt_last_scores.argtypes = [c_void_p, c_void_p, c_int]
         L.wt_last_decode_info.argtypes = [c_void_p, c_void_p, c_int]
+        L.wt_last_best_of.argtypes = [c_void_p, ip32, POINTER(ctypes.c_double), ip32, c_int]
         L.wt_last_token_logprobs.argtypes = [c_void_p, fp, c_int, c_int]
         L.wt_last_segment_scores.argtypes = [c_void_p, fp, c_int]
         L.wt_dbg_token_scores.argtypes = [c_void_p, c_int, c_int, fp, ip64, c_int, ip32, c_int, c_int, c_int, c_int, c_int,
@@ -886,6 +894,17 @@ class Engine:
             lib().wt_last_decode_info(self._h, out.ctypes.data_as(c_void_p), n)
         return out
 
+    def last_best_of(self):
+        """(picked int32 [clips], sum_logprob float64 [clips][8], n_generated int32 [clips][8]) of the last synchronous
+        decode in which some clip was kept from an attempt that ran best_of > 1 samples."""
+        n = lib().wt_last_best_of(self._h, None, None, None, 0)
+        if n < 0:
+            raise WtError(-n, "no best-of record: no clip of the last synchronous decode was kept from an attempt with best_of > 1")
+        picked, s, c = np.zeros(n, np.int32), np.zeros((n, 8), np.float64), np.zeros((n, 8), np.int32)
+        if n:
+            lib().wt_last_best_of(self._h, _ip32(picked), s.ctypes.data_as(POINTER(ctypes.c_double)), _ip32(c), n)
+        return picked, s, c
+
     def last_token_logprobs(self, stride: int) -> np.ndarray:
         """float32 [clips][stride] aligned with the id rows of that decode: 0 for prompt ids and padding."""
         n = lib().wt_last_token_logprobs(self._h, None, 0, 0)
@@ -1329,6 +1348,68 @@ class Engine:
                                                int(clip_base), int(pos), _ip64(tok),
                                                L.ctypes.data_as(POINTER(ctypes.c_double)), _fp(M), _fp(key)))
         return tok, L, M, key
+
+    def dbg_sample_select_group(self, logits, ids, n_ids, sample_begin, temperature, group, seed=0, attempt=0, clip_base=0,
+                                row0=0, pos=-1, timestamps=False, eot=0, beg=1, max_initial_timestamp=50):
+        """The grouped sampler (k_sample.hip) in ONE launch: the B rows of logits / ids are `group`
+        samples of clips = ceil(B / group) clips, row r = sample r // clips of clip r % clips; every row holds n_ids (an
+        int) ids; temperature float32 [clips]; row0 = the first clip's entry of the parameter block.  Returns as
+        dbg_sample_select."""
+        logits = _f32(logits)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        B, V = logits.shape
+        clips = (B + int(group) - 1) // max(int(group), 1)
+        temperature = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, np.float32), (clips,)))
+        assert ids.shape[0] == B
+        tok, L, M, key = np.zeros(B, np.int64), np.zeros(B, np.float64), np.zeros(B, np.float32), np.zeros(B, np.float32)
+        self._check(lib().wt_dbg_sample_select_group(self._h, B, int(group), V, _fp(logits), _ip64(ids), ids.shape[1],
+                                                     int(n_ids), int(sample_begin), int(bool(timestamps)), int(eot),
+                                                     int(beg), int(max_initial_timestamp), _fp(temperature), int(seed),
+                                                     int(attempt), int(clip_base), int(row0), int(pos), _ip64(tok),
+                                                     L.ctypes.data_as(POINTER(ctypes.c_double)), _fp(M), _fp(key)))
+        return tok, L, M, key
+
+    def dbg_best_of_begin(self, ids, n_prompt, N, cap, frozen=None, fill=0x5a):
+        """best_of_begin (k_best_of.hip): ids int64 [N * clips][stride], rows c < clips holding the clips' prompts.  The
+        other arrays start filled with the byte `fill`.  Returns (ids, n_ids, finished, sum, count, anc [N * clips][cap])."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).copy()
+        R, stride = ids.shape
+        clips = R // int(N)
+        assert clips * int(N) == R
+        n_ids, fin, count = (np.full(R, fill * 0x01010101, np.int32) for _ in range(3))
+        s = np.frombuffer(bytes([fill]) * (8 * R), np.float64).copy()
+        anc = np.full((R, int(cap)), fill, np.uint8)
+        fr = None if frozen is None else np.ascontiguousarray(frozen, dtype=np.int32)
+        assert fr is None or fr.shape == (clips,)
+        self._check(lib().wt_dbg_best_of_begin(self._h, clips, int(N), int(n_prompt), stride, int(cap),
+                                               None if fr is None else _ip32(fr), _ip64(ids), _ip32(n_ids), _ip32(fin),
+                                               s.ctypes.data_as(POINTER(ctypes.c_double)), _ip32(count),
+                                               anc.ctypes.data_as(POINTER(ctypes.c_uint8))))
+        return ids, n_ids, fin, s, count, anc
+
+    def dbg_best_of_pick(self, ids, lp, n_ids, sums, counts, N, c0, out):
+        """best_of_pick (k_best_of.hip): ids int64 / lp float32 [N * clips][stride], n_ids / counts int32 and sums float64
+        [N * clips], rows r = j * clips + c.  out = dict of the in / out arrays over n_out rows: ids, lp [n_out][stride],
+        n, count, picked int32 [n_out], sum float64 [n_out], all_sum float64 / all_count int32 [n_out][8].  Returns the
+        dict after the launch (copies)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        lp = _f32(lp)
+        R, stride = ids.shape
+        clips = R // int(N)
+        assert clips * int(N) == R and lp.shape == ids.shape
+        n_ids, counts = np.ascontiguousarray(n_ids, np.int32), np.ascontiguousarray(counts, np.int32)
+        sums = np.ascontiguousarray(sums, np.float64)
+        kinds = {"ids": np.int64, "lp": np.float32, "n": np.int32, "count": np.int32, "picked": np.int32, "sum": np.float64,
+                 "all_sum": np.float64, "all_count": np.int32}
+        o = {k: np.ascontiguousarray(out[k], dtype=t).copy() for k, t in kinds.items()}
+        n_out = o["n"].shape[0]
+        assert o["ids"].shape == (n_out, stride) and o["lp"].shape == (n_out, stride) and o["all_sum"].shape == (n_out, 8)
+        dp = POINTER(ctypes.c_double)
+        self._check(lib().wt_dbg_best_of_pick(self._h, clips, int(N), int(c0), n_out, stride, _ip64(ids), _fp(lp), _ip32(n_ids),
+                                              sums.ctypes.data_as(dp), _ip32(counts), _ip64(o["ids"]), _fp(o["lp"]),
+                                              _ip32(o["n"]), o["sum"].ctypes.data_as(dp), _ip32(o["count"]),
+                                              _ip32(o["picked"]), o["all_sum"].ctypes.data_as(dp), _ip32(o["all_count"])))
+        return o
 
     def dbg_token_scores(self, logits, ids, n_ids, sample_begin, live=None, sums=None, counts=None, timestamps=False, eot=0,
                          beg=1, max_initial_timestamp=50):

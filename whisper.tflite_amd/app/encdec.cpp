@@ -38,6 +38,8 @@ void usage(const char* argv0) {
             << "                  --timestamps also each segment's mean log-probability on its line)\n"
             << "  --skip-silence  with --scores: windows Whisper's no-speech rule calls silent yield no text\n"
             << "  --temperature T with --max-positions: sample every id at temperature T in [0, 1] (default 0: greedy)\n"
+            << "  --best-of N     with --temperature or --fallback: N samples, 1..8, per window at every temperature above 0,\n"
+            << "                  the one with the best average log-probability kept (default 1)\n"
             << "  --seed N        the sampler's 64-bit seed (default 0): same audio, options and seed, same text\n"
             << "  --fallback      with --scores: Whisper's temperature fall-back, T, T + 0.2, ... 1.0 per window, and one\n"
             << "                  line per window with the temperature kept, the attempts and the compression ratio\n"
@@ -60,7 +62,7 @@ void usage(const char* argv0) {
 }  // namespace
 
 int main(int argc, char* argv[]) {
-  std::string model_prefix, vocab, input, inputs, lang, beam, max_positions, temperature, seed, cr_threshold, context_ids, alignment_heads,
+  std::string model_prefix, vocab, input, inputs, lang, beam, max_positions, temperature, seed, best_of, cr_threshold, context_ids, alignment_heads,
       suppress_tokens;
   bool word_timestamps = false, suppress_default = false, suppress_blank = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
@@ -134,6 +136,7 @@ int main(int argc, char* argv[]) {
     else if (a == "--max-positions") max_positions = v;
     else if (a == "--temperature") temperature = v;
     else if (a == "--seed") seed = v;
+    else if (a == "--best-of") best_of = v;
     else if (a == "--compression-ratio-threshold") cr_threshold = v;
     else if (a == "--context-ids") context_ids = v;
     else if (a == "--alignment-heads") alignment_heads = v;
@@ -227,9 +230,9 @@ int main(int argc, char* argv[]) {
       return 105;
     }
   }
-  if (!temperature.empty() || fallback || !seed.empty() || !cr_threshold.empty()) {
+  if (!temperature.empty() || fallback || !seed.empty() || !cr_threshold.empty() || !best_of.empty()) {
     if (max_positions.empty()) {
-      std::cerr << "--temperature, --seed, --fallback and --compression-ratio-threshold require --max-positions\n";
+      std::cerr << "--temperature, --seed, --best-of, --fallback and --compression-ratio-threshold require --max-positions\n";
       return 105;
     }
     if (fallback && !scores) {
@@ -256,8 +259,21 @@ int main(int argc, char* argv[]) {
         return 105;
       }
     }
+    if (!best_of.empty()) {
+      char* end = nullptr;
+      const long n = std::strtol(best_of.c_str(), &end, 10);
+      if (end == best_of.c_str() || *end || wt_engine_set_option(encdec.handle(), "best_of", n) != WT_OK) {
+        std::cerr << "--best-of: expected a number of samples in [1, 8], got " << best_of << "\n";
+        return 105;
+      }
+    }
     if (fallback && wt_engine_set_option(encdec.handle(), "temperature_fallback", 1) != WT_OK) {
       std::cerr << "--fallback: " << wt_last_error(encdec.handle()) << "\n";
+      return 105;
+    }
+    // --beam N with --max-positions and --fallback: beam search is the fall-back's attempt at temperature 0
+    if (fallback && !beam.empty() && wt_engine_set_option(encdec.handle(), "fallback_beam", 1) != WT_OK) {
+      std::cerr << "--beam with --fallback: " << wt_last_error(encdec.handle()) << "\n";
       return 105;
     }
   }

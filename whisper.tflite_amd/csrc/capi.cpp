@@ -220,6 +220,14 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
     e.compression_ratio_threshold = value;
   } else if (k == "seed") {
     e.seed = value;  // all 64 bits are the Philox key
+  } else if (k == "best_of") {
+    // samples per clip of an attempt above temperature 0 in a full-length decode, 1 = one
+    if (value < 1 || value > wt::kSampleGroupMax) return fail(h, WT_ERR_INVALID_ARG, "best_of must be in [1, 8]");
+    e.best_of = value;
+  } else if (k == "fallback_beam") {
+    // with full_beam = 1 and beam_size 2..8: the fall-back's attempt at temperature 0 is beam search
+    if (value < 0 || value > 1) return fail(h, WT_ERR_INVALID_ARG, "fallback_beam must be 0 or 1");
+    e.fallback_beam = value;
   } else if (k == "max_initial_timestamp") {
     if (value < -1 || value > 1500) return fail(h, WT_ERR_INVALID_ARG, "max_initial_timestamp must be in [-1, 1500] (ticks of 20 ms, -1 = no limit)");
     e.max_initial_timestamp = value;
@@ -381,6 +389,8 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "temperature_increment") *value = e.temperature_increment;
   else if (k == "compression_ratio_threshold") *value = e.compression_ratio_threshold;
   else if (k == "seed") *value = e.seed;
+  else if (k == "best_of") *value = e.best_of;
+  else if (k == "fallback_beam") *value = e.fallback_beam;
   else if (k == "prompt_group") *value = e.prompt_group;
   else if (k == "seek") *value = e.seek;
   else if (k == "condition_on_previous_text") *value = e.condition_on_previous_text;
@@ -721,6 +731,21 @@ int wt_last_decode_info(const wt_engine* h, wt_clip_decode* out, int cap) {
   return n;
 }
 
+int wt_last_best_of(const wt_engine* h, int32_t* picked, double* sum_logprob, int32_t* n_generated, int cap) {
+  if (!h || cap < 0 || (cap > 0 && (!picked || !sum_logprob || !n_generated))) return -WT_ERR_INVALID_ARG;
+  const wt::Engine& e = *h->impl;
+  if (!e.last_best_of_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last_picked.size()), G = wt::kSampleGroupMax;
+  for (int i = 0; i < n && i < cap; ++i) {
+    picked[i] = e.last_picked[size_t(i)];
+    for (int j = 0; j < G; ++j) {
+      sum_logprob[i * G + j] = e.last_best_of_sum[size_t(i) * G + j];
+      n_generated[i * G + j] = e.last_best_of_count[size_t(i) * G + j];
+    }
+  }
+  return n;
+}
+
 int wt_last_windows(const wt_engine* h, wt_window* out, int cap) {
   static_assert(sizeof(wt_window) == sizeof(wt::Engine::Window), "wt_window mirrors wt::Engine::Window");
   if (!h || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
@@ -891,6 +916,8 @@ int wt_transcribe_long_batch(wt_engine* h, const float* const* pcm, const size_t
     e.require_idle();
     e.check_timestamp_call();  // before anything is enqueued
     e.check_full_call();
+    if (e.best_of_sampling()) throw wt::Error(WT_ERR_UNSUPPORTED, "best_of: not with wt_transcribe_long_batch (contexts and seeking are outside the best-of chain)");
+    if (e.beam_fallback()) throw wt::Error(WT_ERR_UNSUPPORTED, "fallback_beam: not with wt_transcribe_long_batch (contexts and seeking are outside the beam chain)");
     wt::transcribe_seek_batch(e, pcm, n_samples, n_files);
   });
 }
@@ -923,6 +950,9 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
     std::vector<wt::ClipScore> scores;  // option scores: every window's
     std::vector<float> token_logprob, segment_score;
     std::vector<wt::Engine::ClipDecode> decode_info;  // sampling / fall-back: every window's
+    std::vector<int32_t> picked, best_of_count;       // best_of: every window's (zeros where a batch kept no sampled attempt)
+    std::vector<double> best_of_sum;
+    bool best_of_valid = false;
     std::vector<wt::Engine::Word> words;  // option word_timestamps: every window's, clip = window index, times in the file
     std::vector<std::string> word_text;
     struct ClipBase {  // a window's Philox clip index is its index in the file, however the windows are batched
@@ -959,6 +989,19 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
       }
       e.sync();  // clips[] is read by the H2D copy on the encoder stream
       if (e.last_decode_info_valid) decode_info.insert(decode_info.end(), e.last_decode_info.begin(), e.last_decode_info.end());
+      if (full && e.best_of_sampling()) {
+        const size_t G = wt::kSampleGroupMax;
+        if (e.last_best_of_valid) {
+          picked.insert(picked.end(), e.last_picked.begin(), e.last_picked.end());
+          best_of_sum.insert(best_of_sum.end(), e.last_best_of_sum.begin(), e.last_best_of_sum.end());
+          best_of_count.insert(best_of_count.end(), e.last_best_of_count.begin(), e.last_best_of_count.end());
+          best_of_valid = true;
+        } else {
+          picked.resize(picked.size() + size_t(B), 0);
+          best_of_sum.resize(best_of_sum.size() + size_t(B) * G, 0.0);
+          best_of_count.resize(best_of_count.size() + size_t(B) * G, 0);
+        }
+      }
       if (e.last_lang_valid) {
         langs.insert(langs.end(), e.last_lang.begin(), e.last_lang.end());
         lang_probs.insert(lang_probs.end(), e.last_lang_prob.begin(), e.last_lang_prob.end());
@@ -995,6 +1038,8 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
     }
     if (e.last_scores_valid) e.last_scores = scores, e.last_token_logprob = token_logprob, e.last_segment_score = segment_score;
     if (e.last_decode_info_valid) e.last_decode_info = decode_info;
+    e.last_best_of_valid = best_of_valid;
+    if (best_of_valid) e.last_picked = picked, e.last_best_of_sum = best_of_sum, e.last_best_of_count = best_of_count;
     if (e.last_lang_valid) e.last_lang = langs, e.last_lang_prob = lang_probs;
     if (e.last_segments_valid) e.last_segments = segments, e.last_segment_text = segment_text;
     if (e.last_words_valid) e.last_words = words, e.last_word_text = word_text;

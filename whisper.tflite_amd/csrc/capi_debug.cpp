@@ -1330,6 +1330,110 @@ int wt_dbg_sample_select(wt_engine* h, int B, int V, const float* logits, const 
   });
 }
 
+int wt_dbg_sample_select_group(wt_engine* h, int B, int group, int V, const float* logits, const int64_t* ids, int ids_stride,
+                               int n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
+                               const float* temperature, uint64_t seed, int attempt, int clip_base, int row0, int pos,
+                               int64_t* token, double* L, float* M, float* key) {
+  if (!h || !logits || !ids || !token || !temperature || B < 1 || group < 1 || V < 2 || ids_stride < 1 || sample_begin < 1 ||
+      attempt < 0 || clip_base < 0 || row0 < 0 || n_ids < sample_begin || n_ids > ids_stride) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const int clips = (B + group - 1) / group;
+    // (the launcher refuses what the parameter block cannot hold; the block is filled for the clips it can)
+    wt::SampleParams prm{};
+    prm.seed_lo = unsigned(seed & 0xffffffffull), prm.seed_hi = unsigned(seed >> 32);
+    prm.attempt = unsigned(attempt), prm.clip_base = unsigned(clip_base);
+    for (int c = 0; c < clips && row0 + c < wt::kSampleClipsMax; ++c) {
+      if (!(temperature[c] >= 0.0f) || std::isinf(temperature[c])) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_sample_select_group: a temperature is negative or not finite");
+      prm.inv_t[row0 + c] = temperature[c] > 0.0f ? 1.0f / temperature[c] : 0.0f;
+    }
+    if (B > 4 * wt::kSampleRowsMax) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_sample_select_group: too many rows");
+    const int ldl = (V + 3) & ~3, stride = ids_stride + 1;  // the kernel writes the token at ids[b][n_ids]
+    std::vector<int32_t> n(size_t(B), n_ids);
+    std::vector<long long> rows = widen_ids(ids, B, ids_stride, n.data(), 0);
+    DevArr<float> dlog(pad_logits(logits, B, V, ldl));
+    DevArr<long long> dids(rows);
+    DevArr<int> dn(B, n.data()), dfin(B);
+    DevArr<wt::SamplePart> dpart(size_t(B) * wt::ts_chunks(V));
+    DevArr<wt::TsState> dstate(B);
+    DevArr<wt::SampleParams> dprm(1, &prm);
+    DevArr<double> dL(B);
+    DevArr<float> dM(B), dK(B);
+    dfin.zero(h->impl->stream());
+    if (timestamps) wt::launch_ts_state_init(dids.p, stride, dn.p, 0, sample_begin, V, beg, dstate.p, B, h->impl->stream());
+    wt::SampleArgs t;
+    t.logits = dlog.p; t.ldl = ldl; t.V = V; t.batch = B; t.group = group;
+    t.eot = eot; t.beg = beg; t.max_initial = max_initial_timestamp;
+    t.n_gen = n_ids - sample_begin; t.part = dpart.p;
+    t.state = timestamps ? dstate.p : nullptr;
+    t.params = dprm.p; t.row0 = row0; t.rng_pos = pos;
+    t.ids = dids.p; t.ids_stride = stride; t.pos = n_ids - 1; t.stop_at_eot = 1;
+    t.n_ids = dn.p; t.finished = dfin.p;
+    t.dbg_L = dL.p; t.dbg_M = dM.p; t.dbg_key = dK.p;
+    wt::launch_sample_select(t, h->impl->stream());
+    h->impl->sync();
+    dids.to_host(rows.data());
+    for (int b = 0; b < B; ++b) token[b] = rows[size_t(b) * stride + n_ids];
+    if (L) dL.to_host(L);
+    if (M) dM.to_host(M);
+    if (key) dK.to_host(key);
+  });
+}
+
+int wt_dbg_best_of_begin(wt_engine* h, int clips, int N, int n_prompt, int stride, int cap, const int32_t* frozen,
+                         int64_t* ids, int32_t* n_ids, int32_t* finished, double* sum, int32_t* count, uint8_t* anc) {
+  if (!h || !ids || !n_ids || !finished || !sum || !count || !anc || clips < 1 || N < 1 || stride < 1 || cap < 1 ||
+      clips > 4 * wt::kSampleRowsMax || N > 4 * wt::kSampleRowsMax) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const size_t R = size_t(N) * clips;
+    static_assert(sizeof(long long) == sizeof(int64_t), "id rows");
+    DevArr<long long> dids(R * stride, reinterpret_cast<const long long*>(ids));
+    DevArr<int> dn(R, n_ids), dfin(R, finished), dcount(R, count), dfrozen(size_t(clips), frozen);
+    DevArr<double> dsum(R, sum);
+    DevArr<unsigned char> danc(R * cap, anc);
+    wt::BestOfArgs a;
+    a.clips = clips; a.N = N; a.n_prompt = n_prompt; a.stride = stride; a.cap = cap;
+    a.ids = dids.p; a.n_ids = dn.p; a.finished = dfin.p; a.sum = dsum.p; a.count = dcount.p;
+    a.frozen = frozen ? dfrozen.p : nullptr; a.anc = danc.p;
+    wt::launch_best_of_begin(a, h->impl->stream());
+    h->impl->sync();
+    dids.to_host(reinterpret_cast<long long*>(ids));
+    dn.to_host(n_ids), dfin.to_host(finished), dcount.to_host(count), dsum.to_host(sum), danc.to_host(anc);
+  });
+}
+
+int wt_dbg_best_of_pick(wt_engine* h, int clips, int N, int c0, int n_out, int stride, const int64_t* ids, const float* lp,
+                        const int32_t* n_ids, const double* sum, const int32_t* count, int64_t* out_ids, float* out_lp,
+                        int32_t* out_n, double* out_sum, int32_t* out_count, int32_t* picked, double* all_sum,
+                        int32_t* all_count) {
+  if (!h || !ids || !lp || !n_ids || !sum || !count || !out_ids || !out_lp || !out_n || !out_sum || !out_count || !picked ||
+      !all_sum || !all_count || clips < 1 || N < 1 || stride < 2 || c0 < 0 || n_out < 1 || n_out > wt::kSampleClipsMax ||
+      clips > 4 * wt::kSampleRowsMax || N > 4 * wt::kSampleRowsMax) {
+    return WT_ERR_INVALID_ARG;
+  }
+  if (c0 + clips > n_out) return WT_ERR_INVALID_ARG;  // (the output rows the kernel may write are the caller's arrays)
+  return guarded(h, [&] {
+    const size_t R = size_t(N) * clips, O = size_t(n_out), G = wt::kSampleGroupMax;
+    DevArr<long long> dids(R * stride, reinterpret_cast<const long long*>(ids)), doids(O * stride, reinterpret_cast<const long long*>(out_ids));
+    DevArr<float> dlp(R * stride, lp), dolp(O * stride, out_lp);
+    DevArr<int> dn(R, n_ids), dcount(R, count), don(O, out_n), docount(O, out_count), dpicked(O, picked), dacount(O * G, all_count);
+    DevArr<double> dsum(R, sum), dosum(O, out_sum), dasum(O * G, all_sum);
+    wt::BestOfArgs a;
+    a.clips = clips; a.N = N; a.c0 = c0; a.n_prompt = 1; a.stride = stride; a.cap = stride - 1;
+    a.ids = dids.p; a.lp = dlp.p; a.n_ids = dn.p; a.sum = dsum.p; a.count = dcount.p;
+    a.out_ids = doids.p; a.out_lp = dolp.p; a.out_n = don.p; a.out_count = docount.p; a.picked = dpicked.p;
+    a.out_sum = dosum.p; a.all_sum = dasum.p; a.all_count = dacount.p;
+    wt::launch_best_of_pick(a, h->impl->stream());
+    h->impl->sync();
+    doids.to_host(reinterpret_cast<long long*>(out_ids));
+    dolp.to_host(out_lp), don.to_host(out_n), docount.to_host(out_count), dpicked.to_host(picked);
+    dosum.to_host(out_sum), dasum.to_host(all_sum), dacount.to_host(all_count);
+  });
+}
+
 int wt_dbg_token_scores(wt_engine* h, int B, int V, const float* logits, const int64_t* ids, int ids_stride,
                         const int32_t* n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
                         const int32_t* live, float* lp, double* sum, int32_t* count, double* den) {

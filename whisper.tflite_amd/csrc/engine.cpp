@@ -837,6 +837,15 @@ void Engine::release() noexcept {
   for (void* p : {static_cast<void*>(bw_.h_prompt), static_cast<void*>(bw_.h_sum), static_cast<void*>(bw_.h_len)})
     if (p) (void)hipHostFree(p);
   bw_ = BeamWorkspace();  // (its device buffers are in allocations_)
+  for (void* p : {static_cast<void*>(bf_.h_prompt), static_cast<void*>(bf_.h_ids), static_cast<void*>(bf_.h_lp),
+                  static_cast<void*>(bf_.h_nosp), static_cast<void*>(bf_.h_sum), static_cast<void*>(bf_.h_n),
+                  static_cast<void*>(bf_.h_len), static_cast<void*>(bf_.h_done)})
+    if (p) (void)hipHostFree(p);
+  bf_ = BeamFullWorkspace();
+  for (void* p : {static_cast<void*>(bo_.h_frozen), static_cast<void*>(bo_.h_fin), static_cast<void*>(bo_.h_picked),
+                  static_cast<void*>(bo_.h_all_count), static_cast<void*>(bo_.h_all_sum)})
+    if (p) (void)hipHostFree(p);
+  bo_ = BestOfWorkspace();
   for (void* p : {static_cast<void*>(fw_.h_ids), static_cast<void*>(fw_.h_n), static_cast<void*>(fw_.h_fin),
                   static_cast<void*>(fw_.h_lp), static_cast<void*>(fw_.h_nosp), static_cast<void*>(fw_.h_sum),
                   static_cast<void*>(fw_.h_count), static_cast<void*>(fw_.h_prm)})
@@ -2463,6 +2472,7 @@ void Engine::clear_last_scores() {
   last_segment_score.clear();
   last_lp_stride = 0;
   last_decode_info_valid = false;  // (nor a sampled one)
+  last_best_of_valid = false;
   last_decode_info.clear();
 }
 
@@ -2593,10 +2603,21 @@ void Engine::check_full_call() const {
   if (beam_size > 1) {  // full_beam = 1: beam search's own scope, and what the beam chain does not run
     auto nb = [](const char* why) { throw Error(kErrUnsupported, std::string("full-length beam search (full_beam): ") + why); };
     check_beam_call(false);
-    if (sampling() || temperature_fallback) nb("not with a temperature or the temperature fall-back");
+    // (fallback_beam = 1: the beam chain is the fall-back's attempt at temperature 0; every other
+    // refusal here and in check_beam_call holds for it as it stands)
+    if (!fallback_beam && (sampling() || temperature_fallback)) nb("not with a temperature or the temperature fall-back");
     if (!context_ids.empty() || !clip_contexts.empty()) nb("not with a context");
     if (seek) nb("not with seek");
     if (word_timestamps) nb("not with word_timestamps");
+  }
+  if (best_of_sampling()) {  // the best-of chain's own scope
+    auto nb = [](const char* why) { throw Error(kErrUnsupported, std::string("best_of: ") + why); };
+    if (!context_ids.empty() || !clip_contexts.empty()) nb("not with a context");
+    if (seek) nb("not with seek");
+    if (word_timestamps) nb("not with word_timestamps");
+    if (!stop_at_eot) nb("not with stop_at_eot = 0");
+    if (!cross_absorb || !absorb_active()) nb("needs the absorbed cross-attention (cross_absorb = 1, weights and gemm_variant that allow it)");
+    if (vocab_.token_eot < 0 || vocab_.token_eot >= dims_.n_vocab) nb("the model's vocabulary has no EOT id (token_eot >= n_vocab)");
   }
   // (a suppressed row is selected by ts_select or by the sampler's greedy step: both take an EOT inside the vocabulary)
   if (suppressing() && (vocab_.token_eot < 0 || vocab_.token_eot >= dims_.n_vocab)) no("suppress: the model's vocabulary has no EOT id (token_eot >= n_vocab)");
@@ -2755,11 +2776,20 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   last_words_valid = false;
   last_alignment.clear();
   clear_last_scores();  // (the decode info with them)
-  if (beam_size > 1) return decode_beam_full(batch, ids, ids_stride, n_ids);  // (full_beam = 1: check_full_call)
+  // (full_beam = 1: check_full_call; fallback_beam = 1 with a temperature: the beam chain is the attempt at 0 below)
+  const bool bfb = beam_fallback();
+  if (beam_size > 1 && !bfb) return decode_beam_full(batch, ids, ids_stride, n_ids);
   const bool ts = timestamps != 0, sc = scores != 0, smp = sampling(), sup = suppressing();
   const int n_sup = int(suppress_ids.size()), n_sup_first = int(suppress_first_ids.size());
   ensure_batch(batch);
   ensure_full_workspace(batch);  // (before any capture: nothing may be allocated inside one)
+  const bool bo = best_of_sampling();  // attempts above temperature 0 decode best_of samples per clip
+  last_best_of_valid = false;
+  if (bo) {
+    if (!slots_[slot_idx].absorbed) throw Error(kErrUnsupported, "best_of: the encoder pass did not prepare the absorbed cross-attention");
+    ensure_best_of_workspace();
+  }
+  if (bfb) ensure_beam_full_workspace();
   // per-clip contexts (set_contexts): the chain runs in slots, the fed prompts right-aligned so that
   // every clip's prompt ends at slot n_prompt - 1; `stride`, `n_prompt`, `sot_idx` and the chain's length are in slots,
   // and the rows come back to the caller's layout when the chain has ended (run_chain)
@@ -2991,6 +3021,11 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     std::vector<int> m_n(size_t(batch), 0), m_count(size_t(batch), 0);
     std::vector<float> m_lp(sc ? size_t(batch) * stride : 0, 0.0f), m_nosp(size_t(batch), 0.0f);
     std::vector<double> m_sum(size_t(batch), 0.0);
+    // best_of: the kept sample and every sample's sum and count, from the attempt a clip was kept with
+    const size_t G = kSampleGroupMax;
+    std::vector<int32_t> m_picked(size_t(batch), 0), m_bo_count(bo ? size_t(batch) * G : 0, 0);
+    std::vector<double> m_bo_sum(bo ? size_t(batch) * G : 0, 0.0);
+    bool any_wide = false;
     last_decode_info.assign(size_t(batch), ClipDecode{0, 0, 0, 0.0f});
     for (size_t attempt = 0; attempt < temps.size(); ++attempt) {
       SampleParams& prm = *fw_.h_prm;
@@ -3004,10 +3039,33 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
         prm.pos_off[b] = rag && b < batch ? rw_.h_start[b] : 0;
         prm.clip_off[b] = rag && size_t(b) < clip_index_off.size() ? clip_index_off[size_t(b)] : 0;
       }
-      run_chain(attempt == 0 ? nullptr : &frozen, attempt == 0);
+      const bool wide = bo && temps[attempt] > 0;  // (an attempt at temperature 0 draws nothing: one row per clip)
+      if (wide) {
+        decode_best_of(batch, prompt, attempt == 0 ? nullptr : &frozen, attempt == 0, steps);
+      } else if (bfb && temps[attempt] == 0) {
+        // fallback_beam: beam search over all clips (temperature 0 is the schedule's first entry only), its results
+        // into the mirrors an attempt leaves; the length counts EOT as the scores' count does.  (The fall-back needs
+        // scores, so the log-probabilities and the no-speech probability are there.)
+        beam_full_chains(batch, true, steps);
+        std::copy(bf_.h_ids, bf_.h_ids + size_t(batch) * stride, h_ids);
+        std::copy(bf_.h_n, bf_.h_n + batch, fw_.h_n);
+        std::copy(bf_.h_lp, bf_.h_lp + size_t(batch) * stride, h_lp);
+        std::copy(bf_.h_sum, bf_.h_sum + batch, fw_.h_sum);
+        std::copy(bf_.h_len, bf_.h_len + batch, fw_.h_count);
+        std::copy(bf_.h_nosp, bf_.h_nosp + batch, fw_.h_nosp);
+      } else {
+        run_chain(attempt == 0 ? nullptr : &frozen, attempt == 0);
+      }
       bool again = false;
       for (int b = 0; b < batch; ++b) {
         if (frozen[size_t(b)]) continue;
+        if (bo) {
+          m_picked[size_t(b)] = wide ? bo_.h_picked[b] : 0;
+          for (size_t j = 0; j < G; ++j) {
+            m_bo_sum[size_t(b) * G + j] = wide ? bo_.h_all_sum[size_t(b) * G + j] : j == 0 && sc ? fw_.h_sum[b] : 0.0;
+            m_bo_count[size_t(b) * G + j] = wide ? bo_.h_all_count[size_t(b) * G + j] : j == 0 && sc ? fw_.h_count[b] : 0;
+          }
+        }
         std::copy(h_ids + size_t(b) * stride, h_ids + size_t(b + 1) * stride, m_ids.begin() + size_t(b) * stride);
         m_n[size_t(b)] = fw_.h_n[b];
         ClipDecode& info = last_decode_info[size_t(b)];
@@ -3036,7 +3094,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
           info.needs_fallback = need ? 1 : 0;
         }
         if (info.needs_fallback && attempt + 1 < temps.size()) again = true;
-        else frozen[size_t(b)] = 1;  // accepted, or the schedule is exhausted: the last result is kept
+        else frozen[size_t(b)] = 1, any_wide = any_wide || wide;  // accepted, or the schedule is exhausted: the last result is kept
       }
       if (!again) break;
     }
@@ -3049,6 +3107,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       std::copy(m_nosp.begin(), m_nosp.end(), fw_.h_nosp);
     }
     last_decode_info_valid = true;
+    if (any_wide) last_picked = m_picked, last_best_of_sum = m_bo_sum, last_best_of_count = m_bo_count, last_best_of_valid = true;
   }
   if (sc) {
     last_scores.assign(size_t(batch), ClipScore{});
@@ -3167,8 +3226,67 @@ void Engine::ensure_beam_full_workspace() {
 // clips' slot 0), every later pass writes row r's new position in place and reads the earlier ones through the row's
 // ancestor table (the gathered form of self_attention_long), so a step moves id, log-probability and table rows only.
 // Between the logits GEMM and the next pass: beam_full_partial, beam_full_select, beam_full_advance (k_beam_full.hip).
-// After each segment the clips' done flags come back and a chain ends once every clip is done.
+// After each segment the clips' done flags come back and a chain ends once every clip is done.  beam_full_chains leaves
+// the results in bf_'s pinned mirrors; decode_beam_full publishes them as a call's (ids, beam scores, scores, segments),
+// and decode_full's fall-back loop merges them as its attempt at temperature 0 (option fallback_beam).
 void Engine::decode_beam_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids) {
+  int steps = 0;
+  beam_full_chains(batch, true, steps);
+  const int stride = full_cap() + 1, n_prompt = int(prompt().size());
+  const bool ts = timestamps != 0, sc = scores != 0;
+  beam_sum.assign(size_t(batch), 0.0f);
+  beam_len.assign(bf_.h_len, bf_.h_len + batch);
+  for (int b = 0; b < batch; ++b) beam_sum[size_t(b)] = float(bf_.h_sum[b]);
+  beam_scores_valid = true;
+  if (sc) {
+    last_scores.assign(size_t(batch), ClipScore{});
+    last_lp_stride = stride;
+    last_token_logprob.assign(size_t(batch) * stride, 0.0f);
+    for (int b = 0; b < batch; ++b) {
+      ClipScore& s = last_scores[size_t(b)];
+      if (bf_.h_len[b] < 1) throw Error(kErrDevice, "scores: a clip came back with no generated id counted");
+      s.n_generated = bf_.h_len[b];
+      s.sum_logprob = float(bf_.h_sum[b]);
+      s.avg_logprob = float(bf_.h_sum[b] / double(s.n_generated));
+      s.no_speech_prob = bf_.h_nosp[b];
+      s.skipped = skip_silence && double(s.no_speech_prob) > double(no_speech_threshold) / 1000.0 &&
+                  !(double(s.avg_logprob) > double(logprob_threshold) / 1000.0);
+      for (int i = n_prompt; i < std::min(bf_.h_n[b], stride); ++i) {
+        last_token_logprob[size_t(b) * stride + i] = bf_.h_lp[size_t(b) * stride + i];
+      }
+    }
+    last_segment_score.clear();
+    last_scores_valid = true;
+  }
+  for (int b = 0; b < batch; ++b) {
+    n_ids[b] = bf_.h_n[b];
+    for (int i = 0; i < ids_stride; ++i) {
+      ids[size_t(b) * ids_stride + i] = i < bf_.h_n[b] && i < stride ? bf_.h_ids[size_t(b) * stride + i] : 0;
+    }
+  }
+  if (ts) {
+    last_segments.clear();
+    last_segment_text.clear();
+    for (int b = 0; b < batch; ++b) {
+      if (sc && last_scores[size_t(b)].skipped) continue;  // a silent clip has no segments
+      const int64_t* const row = reinterpret_cast<const int64_t*>(bf_.h_ids + size_t(b) * stride);
+      const size_t first = last_segments.size();
+      parse_segments(vocab_, row, std::min(bf_.h_n[b], stride), n_prompt, b, &last_segments);
+      for (size_t i = first; i < last_segments.size(); ++i) {
+        bool missing = false;
+        last_segment_text.push_back(decode_tokens(vocab_, row + last_segments[i].id_begin, last_segments[i].id_count, false, &missing));
+        if (sc) {  // the mean log-probability of the segment's text ids
+          double sum = 0.0;
+          for (int k = 0; k < last_segments[i].id_count; ++k) sum += double(bf_.h_lp[size_t(b) * stride + last_segments[i].id_begin + k]);
+          last_segment_score.push_back(float(sum / double(std::max(last_segments[i].id_count, 1))));
+        }
+      }
+    }
+    last_segments_valid = true;
+  }
+}
+
+void Engine::beam_full_chains(int batch, bool first, int& steps) {
   const int K = int(beam_size), P = int(max_positions), slot_idx = last_enc_slot_;
   Slot& slot = slots_[slot_idx];
   if (!slot.absorbed) throw Error(kErrUnsupported, "full-length beam search: the encoder pass did not prepare the absorbed cross-attention");
@@ -3191,8 +3309,7 @@ void Engine::decode_beam_full(int batch, int64_t* ids, int ids_stride, int32_t* 
     for (int i = 0; i < stride; ++i) bf_.h_prompt[size_t(b) * stride + i] = i < n_prompt ? prompt[size_t(i)] : 0;
   }
   HIPCHK(hipStreamWaitEvent(st, slot.enc_done, 0));
-  HIPCHK(hipEventRecord(slot.dec_begin, st));
-  int steps = 0;
+  if (first) HIPCHK(hipEventRecord(slot.dec_begin, st));
   for (int c0 = 0; c0 < batch; c0 += per_chain) {
     const int nc = std::min(per_chain, batch - c0), rows = K * nc;
     const int n_abs = abs_chunks_for(nc, 256);
@@ -3300,58 +3417,195 @@ void Engine::decode_beam_full(int batch, int64_t* ids, int ids_stride, int32_t* 
   HIPCHK(hipMemcpyAsync(bf_.h_sum, bf_.out_sum, size_t(batch) * sizeof(double), hipMemcpyDeviceToHost, st));
   if (sc) HIPCHK(hipMemcpyAsync(bf_.h_nosp, bf_.nosp, size_t(batch) * sizeof(float), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(slot.dec_done, st));
-  slot.steps = steps;
+  slot.steps = steps;  // (summed over the attempts of a fall-back)
   finish_slot(slot_idx);  // waits; the encoder's non-finite flag, timings
-  beam_sum.assign(size_t(batch), 0.0f);
-  beam_len.assign(bf_.h_len, bf_.h_len + batch);
-  for (int b = 0; b < batch; ++b) beam_sum[size_t(b)] = float(bf_.h_sum[b]);
-  beam_scores_valid = true;
-  if (sc) {
-    last_scores.assign(size_t(batch), ClipScore{});
-    last_lp_stride = stride;
-    last_token_logprob.assign(size_t(batch) * stride, 0.0f);
-    for (int b = 0; b < batch; ++b) {
-      ClipScore& s = last_scores[size_t(b)];
-      if (bf_.h_len[b] < 1) throw Error(kErrDevice, "scores: a clip came back with no generated id counted");
-      s.n_generated = bf_.h_len[b];
-      s.sum_logprob = float(bf_.h_sum[b]);
-      s.avg_logprob = float(bf_.h_sum[b] / double(s.n_generated));
-      s.no_speech_prob = bf_.h_nosp[b];
-      s.skipped = skip_silence && double(s.no_speech_prob) > double(no_speech_threshold) / 1000.0 &&
-                  !(double(s.avg_logprob) > double(logprob_threshold) / 1000.0);
-      for (int i = n_prompt; i < std::min(bf_.h_n[b], stride); ++i) {
-        last_token_logprob[size_t(b) * stride + i] = bf_.h_lp[size_t(b) * stride + i];
+}
+
+// ------------------------------------------------ several samples per clip ---
+
+void Engine::ensure_best_of_workspace() {
+  ensure_beam_full_workspace();  // the 128-row cache, id rows, log-probabilities, table, logits and output rows
+  if (bo_.h_all_sum) return;     // (allocated last)
+  const size_t R = kDecRowsMax, C = kSampleClipsMax, G = kSampleGroupMax, chunks = size_t(ts_chunks(dims_.n_vocab));
+  auto alloc = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    allocations_.push_back(p);
+    HIPCHK(hipMemset(p, 0, bytes));
+    return p;
+  };
+  auto pinned = [&](size_t bytes) -> void* {
+    void* q = nullptr;
+    HIPCHK(hipHostMalloc(&q, bytes, 0));
+    return q;
+  };
+  bo_.sc_part = static_cast<ScorePart*>(alloc(R * chunks * sizeof(ScorePart)));
+  bo_.sm_part = static_cast<SamplePart*>(alloc(R * chunks * sizeof(SamplePart)));
+  bo_.n_ids = static_cast<int*>(alloc(R * sizeof(int)));
+  bo_.finished = static_cast<int*>(alloc(R * sizeof(int)));
+  bo_.count = static_cast<int*>(alloc(R * sizeof(int)));
+  bo_.sum = static_cast<double*>(alloc(R * sizeof(double)));
+  bo_.frozen = static_cast<int*>(alloc(C * sizeof(int)));
+  bo_.out_count = static_cast<int*>(alloc(C * sizeof(int)));
+  bo_.picked = static_cast<int*>(alloc(C * sizeof(int)));
+  bo_.all_count = static_cast<int*>(alloc(C * G * sizeof(int)));
+  bo_.all_sum = static_cast<double*>(alloc(C * G * sizeof(double)));
+  bo_.h_frozen = static_cast<int*>(pinned(C * sizeof(int)));
+  bo_.h_fin = static_cast<int*>(pinned(R * sizeof(int)));
+  bo_.h_picked = static_cast<int*>(pinned(C * sizeof(int)));
+  bo_.h_all_count = static_cast<int*>(pinned(C * G * sizeof(int)));
+  bo_.h_all_sum = static_cast<double*>(pinned(C * G * sizeof(double)));
+}
+
+// Several samples per clip: decode_beam_full's chains with the sampler in the beam's place.  A chain
+// decodes nc <= 128 / N clips on rows j * nc + c of bf_'s ONE cache.  The prompt positions 0 .. n_prompt - 2 run over the
+// nc clips into cache rows c; from position n_prompt - 1 on every pass runs over the N * nc rows on the gathered
+// self_attention_long under the FIXED table best_of_begin wrote (the prompt's K / V from row c, the rest from the row
+// itself), so the first sampling step already has one logits row per sample and no K / V is copied.  Per step:
+// suppression, score_partial, the grouped sampler, score_finish (the ranking needs the sums whether or not scores are
+// published).  best_of_pick ends a chain.  The attempt's parameter block is decode_full's; a chain's clips are its
+// entries c0 .. c0 + nc - 1.
+void Engine::decode_best_of(int batch, const std::vector<long long>& prompt, const std::vector<int>* frozen, bool first, int& steps) {
+  const int N = int(best_of), P = int(max_positions), slot_idx = last_enc_slot_;
+  Slot& slot = slots_[slot_idx];
+  const wtw::Dims& c = dims_;
+  const int d = c.n_text_state, T = c.n_audio_ctx, V = c.n_vocab, cap = full_cap(), stride = cap + 1;
+  const bool ts = timestamps != 0, sc = scores != 0, sup = suppressing();
+  const int n_sup = int(suppress_ids.size()), n_sup_first = int(suppress_first_ids.size());
+  const int n_prompt = int(prompt.size());
+  const int per_chain = kDecRowsMax / N, sot_idx = 0;  // Whisper's sot_index: the no-speech logits are read there
+  DecWorkspace& dw = dws_[slot.dec];
+  hipStream_t const st = dec_stream_at(slot.dec);
+  for (int b = 0; b < kBeamClipsMax; ++b) {
+    for (int i = 0; i < stride; ++i) bf_.h_prompt[size_t(b) * stride + i] = i < n_prompt ? prompt[size_t(i)] : 0;
+  }
+  for (int b = 0; b < batch; ++b) bo_.h_frozen[b] = frozen ? (*frozen)[size_t(b)] : 0;
+  HIPCHK(hipStreamWaitEvent(st, slot.enc_done, 0));
+  if (first) HIPCHK(hipEventRecord(slot.dec_begin, st));
+  HIPCHK(hipMemcpyAsync(fw_.sm_prm, fw_.h_prm, sizeof(SampleParams), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(bo_.frozen, bo_.h_frozen, size_t(batch) * sizeof(int), hipMemcpyHostToDevice, st));
+  for (int c0 = 0; c0 < batch; c0 += per_chain) {
+    const int nc = std::min(per_chain, batch - c0), rows = N * nc;
+    bool any = false;
+    for (int b = c0; b < c0 + nc; ++b) any = any || !bo_.h_frozen[b];
+    if (!any) continue;  // every clip of the range was accepted by an earlier attempt
+    const int n_abs = abs_chunks_for(nc, 256);
+    BestOfArgs ba;
+    ba.clips = nc; ba.N = N; ba.c0 = c0; ba.n_prompt = n_prompt; ba.stride = stride; ba.cap = cap;
+    ba.ids = bf_.ids[0]; ba.lp = bf_.lp[0]; ba.n_ids = bo_.n_ids; ba.finished = bo_.finished; ba.sum = bo_.sum; ba.count = bo_.count;
+    ba.frozen = bo_.frozen + c0; ba.anc = bf_.anc[0];
+    ba.out_ids = bf_.out_ids; ba.out_lp = bf_.out_lp; ba.out_n = bf_.out_n; ba.out_count = bo_.out_count; ba.picked = bo_.picked;
+    ba.out_sum = bf_.out_sum; ba.all_sum = bo_.all_sum; ba.all_count = bo_.all_count;
+    DecPass p;
+    p.clips = nc; p.ids = bf_.ids[0]; p.ids_stride = stride; p.self_kv = bf_.kv; p.self_cap = cap; p.self_rows = kDecRowsMax;
+    p.absorbed = true; p.n_abs = n_abs; p.e = slot.e_planes + size_t(c0) * T * d; p.split = fc2_split(); p.dw = &dw;
+    p.Y = bf_.logits; p.ldy = bf_.ldl;
+    ScoreArgs sa;
+    sa.logits = bf_.logits; sa.ldl = bf_.ldl; sa.V = V; sa.part = bo_.sc_part;
+    sa.eot = vocab_.token_eot; sa.beg = vocab_.token_beg; sa.max_initial = int(max_initial_timestamp);
+    sa.ids = bf_.ids[0]; sa.ids_stride = stride; sa.n_ids = bo_.n_ids; sa.token_logprob = bf_.lp[0]; sa.lp_stride = stride;
+    sa.sum = bo_.sum; sa.count = bo_.count;
+    const int wide0 = n_prompt - 1;  // the first position that runs over all the rows
+    const int np_max = std::max(1, std::min(4, kDecRowsMax / nc));
+    // the chain's passes: the prompt below wide0 over the nc clips (a pass ends at sot, with logits: the no-speech
+    // probability), then one position per pass over all the rows.  Where the wide passes begin at sot (a prompt of one
+    // id) the narrow pass at sot still runs for the no-speech probability and the wide pass repeats that position.
+    struct Pass {
+      int pos0, np;
+      bool narrow, nosp;
+    };
+    std::vector<Pass> passes;
+    for (int pos0 = 0, np = 1; pos0 < wide0; pos0 += np) {
+      np = std::min(np_max, wide0 - pos0);
+      if (sc && pos0 <= sot_idx) np = std::min(np, sot_idx - pos0 + 1);
+      passes.push_back(Pass{pos0, np, true, sc && pos0 + np - 1 == sot_idx});
+    }
+    if (sc && wide0 <= sot_idx) passes.push_back(Pass{sot_idx, 1, true, true});
+    for (int pos0 = wide0; pos0 < P; ++pos0) passes.push_back(Pass{pos0, 1, false, false});
+    // the passes whose first position lies in [lo, hi), each wide one with its step; returns the steps among them
+    auto enqueue_segment = [&](int lo, int hi) {
+      int seg_steps = 0;
+      for (const Pass& q : passes) {
+        if (q.pos0 < lo || q.pos0 >= hi) continue;
+        const int last = q.pos0 + q.np - 1, t = last + 1 - n_prompt;
+        p.B = q.narrow ? nc : rows; p.self_anc = q.narrow ? nullptr : bf_.anc[0];
+        p.pos0 = q.pos0; p.np = q.np; p.best = !q.narrow || q.nosp ? bf_.best : nullptr;
+        decoder_pass(p, st);
+        if (q.nosp) {
+          sa.batch = nc; sa.state = nullptr;
+          launch_no_speech_prob(sa, vocab_.token_solm, bf_.nosp + c0, st);
+        }
+        if (q.narrow) continue;
+        if (sup) {  // behind the no-speech probability, in front of every sample's allowed set
+          SuppressArgs u;
+          u.logits = bf_.logits; u.ldl = bf_.ldl; u.V = V; u.rows = rows; u.ids = d_suppress_;
+          u.n = n_sup; u.n_first = n_sup_first; u.first = t == 0;
+          launch_suppress_logits(u, st);
+        }
+        // the partial sums of the allowed set, from the state BEFORE the selection advances it
+        sa.batch = rows; sa.state = ts ? bf_.ts : nullptr; sa.n_gen = t; sa.pos = last;
+        launch_score_partial(sa, st);
+        SampleArgs g;
+        g.logits = bf_.logits; g.ldl = bf_.ldl; g.V = V; g.batch = rows; g.group = N;
+        g.eot = vocab_.token_eot; g.beg = vocab_.token_beg; g.max_initial = int(max_initial_timestamp);
+        g.n_gen = t; g.params = fw_.sm_prm; g.row0 = c0; g.part = bo_.sm_part; g.state = ts ? bf_.ts : nullptr;
+        g.ids = bf_.ids[0]; g.ids_stride = stride; g.pos = last; g.stop_at_eot = 1;
+        g.n_ids = bo_.n_ids; g.finished = bo_.finished;
+        launch_sample_select(g, st);
+        launch_score_finish(sa, st);
+        ++seg_steps;
       }
-    }
-    last_segment_score.clear();
-    last_scores_valid = true;
-  }
-  for (int b = 0; b < batch; ++b) {
-    n_ids[b] = bf_.h_n[b];
-    for (int i = 0; i < ids_stride; ++i) {
-      ids[size_t(b) * ids_stride + i] = i < bf_.h_n[b] && i < stride ? bf_.h_ids[size_t(b) * stride + i] : 0;
-    }
-  }
-  if (ts) {
-    last_segments.clear();
-    last_segment_text.clear();
-    for (int b = 0; b < batch; ++b) {
-      if (sc && last_scores[size_t(b)].skipped) continue;  // a silent clip has no segments
-      const int64_t* const row = reinterpret_cast<const int64_t*>(bf_.h_ids + size_t(b) * stride);
-      const size_t first = last_segments.size();
-      parse_segments(vocab_, row, std::min(bf_.h_n[b], stride), n_prompt, b, &last_segments);
-      for (size_t i = first; i < last_segments.size(); ++i) {
-        bool missing = false;
-        last_segment_text.push_back(decode_tokens(vocab_, row + last_segments[i].id_begin, last_segments[i].id_count, false, &missing));
-        if (sc) {  // the mean log-probability of the segment's text ids
-          double sum = 0.0;
-          for (int k = 0; k < last_segments[i].id_count; ++k) sum += double(bf_.h_lp[size_t(b) * stride + last_segments[i].id_begin + k]);
-          last_segment_score.push_back(float(sum / double(std::max(last_segments[i].id_count, 1))));
+      return seg_steps;
+    };
+    HIPCHK(hipMemcpyAsync(bf_.ids[0], bf_.h_prompt, size_t(nc) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
+    launch_best_of_begin(ba, st);
+    if (ts) launch_ts_state_init(bf_.ids[0], stride, nullptr, n_prompt, n_prompt, V, vocab_.token_beg, bf_.ts, rows, st);
+    for (int lo = 0; lo < P; lo += 32) {
+      const int hi = std::min(P, lo + 32);
+      std::vector<long long> key{kBestOfKey, slot_idx, N, c0, nc, lo, P, n_prompt, fc2_ksplit, n_abs, slot.dec, ts ? 1 : 0,
+                                 ts ? max_initial_timestamp : 0, sc ? 1 : 0};
+      if (sup) key.push_back(n_sup), key.push_back(n_sup_first);  // launch constants; the ids themselves are device data
+      auto it = use_graphs ? graphs_.find(key) : graphs_.end();
+      if (it != graphs_.end()) {
+        HIPCHK(hipGraphLaunch(it->second.exec, st));
+        steps += it->second.steps;
+      } else {
+        const int seg_steps = enqueue_segment(lo, hi);  // eager the first time, then captured for the next calls
+        steps += seg_steps;
+        if (use_graphs) {
+          try {
+            graphs_.emplace(key, GraphEntry{capture_graph(st, [&] { enqueue_segment(lo, hi); }), seg_steps});
+          } catch (const std::exception& e) {
+            (void)hipGetLastError();
+            use_graphs = 0;
+            std::fprintf(stderr, "[wt] best-of hipGraph capture failed (%s): continuing with eager launches\n", e.what());
+          }
         }
       }
+      if (hi == P) break;
+      // every row finished: the remaining segments would change nothing
+      HIPCHK(hipMemcpyAsync(bo_.h_fin, bo_.finished, size_t(rows) * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      bool all = true;
+      for (int r = 0; r < rows; ++r) all = all && bo_.h_fin[r] != 0;
+      if (all) break;
     }
-    last_segments_valid = true;
+    launch_best_of_pick(ba, st);
   }
+  HIPCHK(hipMemcpyAsync(fw_.h_ids, bf_.out_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(fw_.h_n, bf_.out_n, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(bo_.h_picked, bo_.picked, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(bo_.h_all_sum, bo_.all_sum, size_t(batch) * kSampleGroupMax * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(bo_.h_all_count, bo_.all_count, size_t(batch) * kSampleGroupMax * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (sc) {
+    HIPCHK(hipMemcpyAsync(fw_.h_lp, bf_.out_lp, size_t(batch) * stride * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(fw_.h_sum, bf_.out_sum, size_t(batch) * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(fw_.h_count, bo_.out_count, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(fw_.h_nosp, bf_.nosp, size_t(batch) * sizeof(float), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipEventRecord(slot.dec_done, st));
+  slot.steps = steps;  // (summed over the attempts)
+  finish_slot(slot_idx);  // waits; the encoder's non-finite flag, timings
 }
 
 // Word-level timestamps: the alignment pass over the kept results of a timestamp decode.  Clips go

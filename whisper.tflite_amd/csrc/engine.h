@@ -163,7 +163,7 @@ class Engine {
   // synchronous calls only from 32 clips on — below that the cached form's 7 launches per decoder layer beat the absorbed
   // form's 9 (single clip 7.2 against 9.0 ms, 16 clips 11.1 against 12.1 ms, 32 clips 15.2 against 15.0 ms)
   // (beam search: always, whatever the batch size; its K query rows per clip ride the absorbed form's position loop)
-  bool absorb_for(int batch) const { return absorb_active() && (pipelined_call_ || batch >= 32 || beam_size > 1); }
+  bool absorb_for(int batch) const { return absorb_active() && (pipelined_call_ || batch >= 32 || beam_size > 1 || (max_positions > 0 && best_of_sampling())); }
   // 1 = greedy (the reference's argmax loop); 2..8 = beam search with that many hypotheses per clip on the synchronous
   // entry points (decode_beam).  Scope: stop_at_eot = 1, the absorbed cross-attention, fp32-accurate
   // storage; no pipeline, no forced ids, no logits tap (check_beam_call).
@@ -209,8 +209,8 @@ class Engine {
   // Full-length beam search (decode_beam_full).  0: a full-length call with beam_size > 1 is refused.
   // 1: beam_size 2..8 with max_positions runs the beam chain to P positions, with or without timestamps, scores and
   // skip_silence; decode_full hands such a call over, so every full-length entry point honours the mode.  Scope:
-  // beam search's (check_beam_call) and full-length decoding's, and no temperature, context, seek, word timestamps or
-  // batched seeking (check_full_call).
+  // beam search's (check_beam_call) and full-length decoding's, and no temperature (unless fallback_beam = 1), context,
+  // seek, word timestamps or batched seeking (check_full_call).
   long full_beam = 0;
   // Timestamp decoding.  1: the default prompt ends before <|notimestamps|> and decode_full applies
   // Whisper's timestamp rules on the device (k_timestamps.hip) in place of select_token.  Full-length greedy decoding
@@ -256,6 +256,26 @@ class Engine {
   long seed = 0;
   long clip_base = 0;  // index of the call's first clip in the Philox counter (wt_transcribe_long_pcm: the window index)
   bool sampling() const { return temperature > 0 || temperature_fallback != 0; }
+  // Several samples per clip.  best_of = N > 1: every attempt of a full-length decode whose
+  // temperature is above 0 decodes N samples per clip (decode_best_of) and keeps the first with the largest
+  // sum_logprob / n_generated in float64, EOT counted; an attempt at temperature 0 draws nothing and runs as ever.
+  // With sampling() it is refused (kErrUnsupported, check_full_call) beside a context, seek, word_timestamps,
+  // stop_at_eot = 0, the batched seeking entry point and a decoder without the absorbed cross-attention.
+  long best_of = 1;
+  bool best_of_sampling() const { return best_of > 1 && sampling(); }
+  // Beam search inside the fall-back.  It means something only with full_beam = 1 and beam_size
+  // 2..8.  0: such a call refuses a temperature and the fall-back (section 23).  1: an attempt at temperature 0 runs
+  // the beam chain (beam_full_chains) over all clips, an attempt above 0 runs the sampler with best_of rows per clip and
+  // ignores the beam; a fixed temperature > 0 without fall-back is then a sampling call.  The beam chain's own refusals
+  // (context, seek, word_timestamps, stop_at_eot = 0, no absorbed cross-attention) and the batched seeking entry
+  // point's stand.
+  long fallback_beam = 0;
+  bool beam_fallback() const { return fallback_beam != 0 && full_beam != 0 && beam_size > 1 && sampling(); }
+  // per clip of the last decode in which some clip's kept attempt ran N > 1 samples: the kept sample and every
+  // sample's sum and count [clips][8] (a clip kept from an attempt at temperature 0: sample 0, its own sum and count)
+  std::vector<int32_t> last_picked, last_best_of_count;
+  std::vector<double> last_best_of_sum;
+  bool last_best_of_valid = false;
   struct ClipDecode {  // (wt_clip_decode)
     int32_t temperature_milli, attempts, needs_fallback;
     float compression_ratio;
@@ -489,6 +509,9 @@ class Engine {
   void ensure_beam_workspace();
   // the chain behind decode_full when beam_size > 1 and full_beam = 1: consecutive chains of <= 128 / beam_size clips
   void decode_beam_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids);
+  // its chains alone: the results stay in bf_'s pinned mirrors (h_ids, h_lp, h_n, h_len, h_sum, h_nosp); adds the
+  // decoder steps to `steps`; first: the call's first chain records the slot's dec_begin
+  void beam_full_chains(int batch, bool first, int& steps);
   struct BeamFullWorkspace {  // allocated on the first full-length beam call, sized for 128 rows and 64 clips
     float* kv = nullptr;                         // ONE self-attention cache [layer][k|v][128][full_cap()][d]: K / V never move
     long long* ids[2] = {nullptr, nullptr};      // id rows [128][full_cap() + 1], double-buffered
@@ -512,6 +535,22 @@ class Engine {
     int *h_n = nullptr, *h_len = nullptr, *h_done = nullptr;
   } bf_;
   void ensure_beam_full_workspace();
+  // One attempt of decode_full's fall-back loop at a temperature above 0 with best_of = N > 1: consecutive chains of
+  // <= 128 / N clips on bf_'s cache, rows j * nc + c, each ended by best_of_pick; the kept rows land in the mirrors
+  // the loop merges from (fw_.h_ids, h_n, and with scores h_lp, h_sum, h_count, h_nosp).  frozen: clips that need no
+  // result.  Adds the attempt's decoder steps to `steps`.
+  void decode_best_of(int batch, const std::vector<long long>& prompt, const std::vector<int>* frozen, bool first, int& steps);
+  struct BestOfWorkspace {  // beside bf_, allocated on the first such call: per row [128], per clip [64]
+    ScorePart* sc_part = nullptr;    // [128][chunks]
+    SamplePart* sm_part = nullptr;   // [128][chunks]
+    int *n_ids = nullptr, *finished = nullptr, *count = nullptr;  // [128]
+    double* sum = nullptr;           // [128]
+    int *frozen = nullptr, *out_count = nullptr, *picked = nullptr, *all_count = nullptr;  // [64], all_count [64][8]
+    double* all_sum = nullptr;       // [64][8]
+    int *h_frozen = nullptr, *h_fin = nullptr, *h_picked = nullptr, *h_all_count = nullptr;  // pinned
+    double* h_all_sum = nullptr;
+  } bo_;
+  void ensure_best_of_workspace();
   struct FullWorkspace {  // allocated on the first full-length call
     float* kv = nullptr;            // self-attention caches [layer][k|v][clip][full_cap()][d] for kv_clips clips
     int kv_clips = 0;               // the largest batch of a full-length call so far
@@ -559,6 +598,7 @@ class Engine {
   static constexpr size_t kAlignWeightBytes = size_t(256) << 20;  // bound of the weight workspace: clips go through in sub-groups
   static constexpr long long kFullKey = -1000;  // first entry of a full-length segment's graph key
   static constexpr long long kBeamFullKey = -2000;  // ... and of a full-length beam segment's
+  static constexpr long long kBestOfKey = -3000;    // ... and of a best-of segment's
 
   int enc_cus_masked_ = 0;  // CUs the pipelined encoder stream may use
  public:

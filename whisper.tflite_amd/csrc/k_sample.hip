@@ -9,6 +9,11 @@
 // A is the whole vocabulary (state == nullptr) or what the timestamp rules leave (ts_rules.h).  Everything that varies
 // from attempt to attempt (1 / T per clip, seed, attempt, the first clip's index) is read from a SampleParams block in
 // device memory, so one captured launch sequence serves them all.
+// Several samples per clip (SampleArgs::group = N > 1): the launch's rows are N samples of
+// ceil(rows / N) clips, row r = sample j = r / clips of clip r % clips (the rows of a beam chain, which the absorbed
+// cross-attention groups per clip).  The parameter block is indexed by the clip; the counter's fourth word is
+// attempt + (j << 16), so sample 0 is the ungrouped draw.  sample_partial<true, int> is that form, sample_partial<false>
+// the launch of group = 1.  sample_select reads nothing of the block and serves both.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -70,10 +75,15 @@ __device__ __forceinline__ float gumbel_of(unsigned x) {
 
 // grid (chunks, clips): thread t holds the 4 consecutive entries chunk * 4096 + j * 1024 + 4 t .. + 3, j = 0 .. 3 (the
 // load shape of ts_partial, and its reductions for key_text, m and s: the same bits)
+// (kGroup = true takes one more argument, the clips of the launch; without it the argument list, and with it every
+// instruction, is the ungrouped kernel's)
+template <bool kGroup, typename... Clips>
 __global__ __launch_bounds__(kThreads) void sample_partial(const float* __restrict__ logits, int ldl, int V,
                                                            const TsState* __restrict__ state, int n_gen, int eot, int beg,
                                                            int mit, const SampleParams* __restrict__ prm, int row0,
-                                                           int rng_pos, SamplePart* __restrict__ part) {
+                                                           int rng_pos, SamplePart* __restrict__ part, Clips... n_clips) {
+  static_assert(sizeof...(Clips) == (kGroup ? 1 : 0), "the grouped kernel takes the number of clips");
+  const int clips = (n_clips + ... + 0);
   __shared__ float red[4];
   __shared__ unsigned long long kred[4][4];
   const int chunk = blockIdx.x, row = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -83,10 +93,12 @@ __global__ __launch_bounds__(kThreads) void sample_partial(const float* __restri
   } else {  // plain mode: every id is "text"
     a.t_lo = 0, a.t_hi = V - 1, a.s_lo = V, a.s_hi = V - 1;
   }
-  const float inv_t = prm->inv_t[row0 + row];  // 0: greedy
-  const unsigned k0 = prm->seed_lo, k1 = prm->seed_hi, attempt = prm->attempt;
-  const unsigned clip = prm->clip_base + (unsigned)(row0 + row) + (unsigned)prm->clip_off[row0 + row];
-  rng_pos -= prm->pos_off[row0 + row];
+  // the row's entry of the parameter block, and its sample index on top of the attempt
+  const int crow = kGroup ? row % clips : row;
+  const float inv_t = prm->inv_t[row0 + crow];  // 0: greedy
+  const unsigned k0 = prm->seed_lo, k1 = prm->seed_hi, attempt = prm->attempt + (kGroup ? (unsigned)(row / clips) << 16 : 0u);
+  const unsigned clip = prm->clip_base + (unsigned)(row0 + crow) + (unsigned)prm->clip_off[row0 + crow];
+  rng_pos -= prm->pos_off[row0 + crow];
   const float* z = logits + (long)row * ldl;  // ldl % 4 == 0 and a 16-byte base: every quad below is aligned
   float v[4 * kQuads];
   unsigned long long kt = 0ull, ks = 0ull, pt = 0ull, ps = 0ull;
@@ -203,11 +215,20 @@ void launch_sample_select(const SampleArgs& a, hipStream_t s) {
   if (a.batch < 1 || a.V < 2 || n_chunks > kTsMaxChunks || a.eot < 0 || a.eot >= a.V || (ts && (a.eot >= a.beg || a.beg >= a.V)) ||
       a.ldl < a.V || a.ldl % 4 != 0 || (reinterpret_cast<uintptr_t>(a.logits) & 15) != 0 || a.pos < 0 ||
       a.pos + 1 >= a.ids_stride || a.n_gen < 0 || a.max_initial < -1 || !a.params || a.row0 < 0 ||
-      a.row0 + a.batch > kSampleClipsMax) {
+      (a.group == 1 && a.row0 + a.batch > kSampleClipsMax)) {
     throw Error(kErrInvalidArg, "sample_select: needs 0 <= eot (< beg) < V <= 4096 * 64, 16-byte aligned logits rows, pos + 1 < ids_stride and at most 64 clips");
   }
-  hipLaunchKernelGGL(sample_partial, dim3(n_chunks, a.batch), dim3(kThreads), 0, s, a.logits, a.ldl, a.V, a.state, a.n_gen,
-                     a.eot, a.beg, a.max_initial, a.params, a.row0, a.rng_pos >= 0 ? a.rng_pos : a.pos, a.part);
+  const int clips = a.group > 0 ? (a.batch + a.group - 1) / a.group : 0;
+  if (a.group < 1 || a.group > kSampleGroupMax || (a.group > 1 && (a.batch > kSampleRowsMax || a.row0 + clips > kSampleClipsMax))) {
+    throw Error(kErrInvalidArg, "sample_select: a group is 1 .. 8 samples per clip, at most 128 rows and 64 clips");
+  }
+  if (a.group > 1) {
+    hipLaunchKernelGGL((sample_partial<true, int>), dim3(n_chunks, a.batch), dim3(kThreads), 0, s, a.logits, a.ldl, a.V, a.state,
+                       a.n_gen, a.eot, a.beg, a.max_initial, a.params, a.row0, a.rng_pos >= 0 ? a.rng_pos : a.pos, a.part, clips);
+  } else {
+    hipLaunchKernelGGL(sample_partial<false>, dim3(n_chunks, a.batch), dim3(kThreads), 0, s, a.logits, a.ldl, a.V, a.state, a.n_gen,
+                       a.eot, a.beg, a.max_initial, a.params, a.row0, a.rng_pos >= 0 ? a.rng_pos : a.pos, a.part);
+  }
   hipLaunchKernelGGL(sample_select, dim3(a.batch), dim3(64), 0, s, a.part, n_chunks, a.ids, a.ids_stride, a.pos, a.n_ids,
                      a.finished, a.state, ts ? a.beg : a.V, (long long)a.eot, a.stop_at_eot, a.dbg_L, a.dbg_M, a.dbg_key);
 }

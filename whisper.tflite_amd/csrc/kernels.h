@@ -489,6 +489,8 @@ void launch_ts_select(const TsSelectArgs& a, hipStream_t s);  // ts_partial + ts
 // z_i, the step of select_token / ts_select.  The allowed set is the whole vocabulary (state == nullptr) or what the
 // timestamp rules leave, rule 5 decided on the untempered logits exactly as ts_select decides it.
 constexpr int kSampleClipsMax = 64;  // clips of one synchronous call
+constexpr int kSampleGroupMax = 8;   // samples per clip of one launch (option best_of)
+constexpr int kSampleRowsMax = 128;  // rows of a grouped launch (kDecRowsMax)
 struct SampleParams {                // device memory, written ahead of a chain: nothing here is a kernel argument
   unsigned seed_lo, seed_hi, attempt, clip_base;
   float inv_t[kSampleClipsMax];      // 1 / T per clip, 0 = greedy
@@ -508,6 +510,10 @@ struct SampleArgs {
   int eot = 0, beg = 0, max_initial = -1, n_gen = 0;
   const SampleParams* params = nullptr;
   int row0 = 0;                   // clip b of this launch is clip row0 + b of the parameter block
+  // group = N > 1: the batch rows are N samples of clips = ceil(batch / N) clips, row r = sample r / clips of clip
+  // r % clips (k_beam_full.hip's row order); the block is indexed by row0 + clip and sample j draws under the attempt
+  // word attempt + (j << 16), so sample 0 is the draw of group = 1.  batch <= 128, row0 + clips <= kSampleClipsMax.
+  int group = 1;
   int rng_pos = -1;               // the counter's position word; -1 = pos
   SamplePart* part = nullptr;     // [batch][ts_chunks(V)]
   TsState* state = nullptr;       // [batch], read and advanced; nullptr = plain mode
@@ -619,6 +625,39 @@ void launch_beam_full_partial(const BeamFullArgs& a, hipStream_t s);
 void launch_beam_full_select(const BeamFullArgs& a, hipStream_t s);
 void launch_beam_full_advance(const BeamFullArgs& a, hipStream_t s);
 void launch_beam_full_finalize(const BeamFullArgs& a, hipStream_t s);  // src = the rows after the last step's advance
+
+// ---------------------------------------------------------------- best of ---
+// k_best_of.hip (option best_of): the two ends of a chain that decodes N samples of each of its
+// clips.  Rows are laid out row = j * clips + c (sample j of clip c) as k_beam_full.hip's, a row's ids [stride] int64
+// and log-probabilities [stride] float as there.  best_of_begin copies the clips' prompt rows (rows c, j = 0) into
+// their other samples' rows, sets n_ids, finished (1 where frozen[c]), the score sums and counts, and writes the
+// FIXED ancestor table of the gathered self_attention_long: anc[r][k] = r % clips for k < n_prompt - 1 (the prompt's
+// K / V, which the narrow passes wrote to rows c), else r.  best_of_pick keeps, per clip, the first sample with the
+// largest sum / count in float64 (a NaN, or a count below 1, never wins; sample 0 where none is left) and copies its
+// row to the clip's output row c0 + c.
+struct BestOfArgs {
+  int clips = 0, N = 0, c0 = 0;      // clips of the chain, samples per clip, the chain's first clip in the output rows
+  int n_prompt = 0, stride = 0, cap = 0;  // 1 <= n_prompt <= cap < stride
+  long long* ids = nullptr;          // [N * clips][stride]; begin reads rows c < clips and writes the others
+  float* lp = nullptr;               // [N * clips][stride]: pick reads it
+  int* n_ids = nullptr;              // [N * clips]
+  int* finished = nullptr;           // [N * clips]
+  double* sum = nullptr;             // [N * clips]: score_finish's carried sum and count
+  int* count = nullptr;
+  // launch_best_of_begin only
+  const int* frozen = nullptr;       // optional [clips]
+  unsigned char* anc = nullptr;      // [N * clips][cap]
+  // launch_best_of_pick only: indexed by c0 + clip
+  long long* out_ids = nullptr;      // [..][stride]: the row's first n_ids ids, zeros behind them
+  float* out_lp = nullptr;           // [..][stride]
+  int *out_n = nullptr, *out_count = nullptr, *picked = nullptr;
+  double* out_sum = nullptr;
+  double* all_sum = nullptr;         // [..][kSampleGroupMax]: every sample's sum and count, zeros from N on
+  int* all_count = nullptr;
+};
+// Both throw kErrInvalidArg outside N in [1, 8], N * clips <= 128, c0 + clips <= 64, 1 <= n_prompt <= cap < stride.
+void launch_best_of_begin(const BestOfArgs& a, hipStream_t s);
+void launch_best_of_pick(const BestOfArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------- alignment ---
 // k_align.hip (word-level timestamps): from the cross-attention weights W of a teacher-forced pass

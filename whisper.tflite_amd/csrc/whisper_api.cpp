@@ -119,6 +119,27 @@ std::vector<ClipDecode> clip_decodes(const wt_engine* h) {
 std::vector<ClipDecode> EncDec::decode_info() const { return clip_decodes(handle_); }
 std::vector<ClipDecode> Monolith::decode_info() const { return clip_decodes(handle_); }
 
+namespace {
+std::vector<ClipBestOf> clip_best_ofs(const wt_engine* h) {
+  std::vector<ClipBestOf> out;
+  const int n = wt_last_best_of(h, nullptr, nullptr, nullptr, 0);
+  if (n <= 0) return out;
+  std::vector<int32_t> picked(static_cast<size_t>(n)), count(static_cast<size_t>(n) * 8);
+  std::vector<double> sum(static_cast<size_t>(n) * 8);
+  wt_last_best_of(h, picked.data(), sum.data(), count.data(), n);
+  for (int i = 0; i < n; ++i) {
+    ClipBestOf b;
+    b.picked = picked[static_cast<size_t>(i)];
+    b.sum_logprob.assign(sum.begin() + i * 8, sum.begin() + (i + 1) * 8);
+    b.n_generated.assign(count.begin() + i * 8, count.begin() + (i + 1) * 8);
+    out.push_back(b);
+  }
+  return out;
+}
+}  // namespace
+std::vector<ClipBestOf> EncDec::best_of() const { return clip_best_ofs(handle_); }
+std::vector<ClipBestOf> Monolith::best_of() const { return clip_best_ofs(handle_); }
+
 std::vector<EncDec::Segment> EncDec::segments() const {
   std::vector<Segment> out;
   const int n = wt_last_segments(handle_, nullptr, 0);
