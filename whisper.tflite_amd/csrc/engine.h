@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -579,6 +580,33 @@ class Engine {
     SampleParams* zero_prm = nullptr;
   } fw_;
   int* d_suppress_ = nullptr;  // [2 * kSuppressIdsMax]: the always-ids, then the first-ids (set_suppress)
+  // suppress_logits over `rows` rows of a chain's logits; first: the step behind the fed prompt (n_gen == 0)
+  void enqueue_suppress(float* logits, int ldl, int rows, bool first, hipStream_t st);
+  // what SampleArgs, ScoreArgs and TsSelectArgs share in every chain: the logits rows and the model's constants
+  template <class Args>
+  void fill_rule_args(Args& a, const float* logits, int ldl) const {
+    a.logits = logits; a.ldl = ldl; a.V = dims_.n_vocab;
+    a.eot = vocab_.token_eot; a.beg = vocab_.token_beg; a.max_initial = int(max_initial_timestamp);
+  }
+  // What a full-length chain left on the host, for publish_full: id rows and token log-probabilities [clip][stride], id
+  // counts, and per clip the sum and count of the log-probabilities and the no-speech probability (read with scores)
+  struct FullResult {
+    const long long* ids = nullptr;
+    int stride = 0;
+    const int* n = nullptr;
+    const float* lp = nullptr;
+    const double* sum = nullptr;
+    const int* count = nullptr;
+    const float* nosp = nullptr;
+    std::function<int(int)> n_prompt;  // clip -> the ids of its fed prompt
+  };
+  // the caller's id rows and counts, and last_scores / last_token_logprob, last_segments / _text / _score as the
+  // options ask: scores first, the segment pass reads `skipped`
+  void publish_full(const FullResult& r, int batch, int64_t* ids, int ids_stride, int32_t* n_ids);
+  // Whisper's two silence tests on (no_speech_prob, avg_logprob).  They differ where avg_logprob equals the threshold:
+  // transcribe() skips a clip unless avg > threshold (below = false), decode_with_fallback exempts a clip from another
+  // attempt only when avg < threshold (below = true)
+  bool silent(float no_speech_prob, float avg_logprob, bool below) const;
   void ensure_full_workspace(int batch);
   struct RaggedWorkspace {  // allocated by the first ragged call: the slot-space rows [64][ragged_stride()] and the starts [64]
     long long *ids = nullptr, *h_ids = nullptr;
@@ -650,6 +678,23 @@ class Engine {
   };
   void need_cross_kv(Slot& slot);  // the cached decoder form's cross K/V cache of a slot, on first use
   std::map<std::vector<long long>, GraphEntry> graphs_;
+  // Replays the graph cached under `key` on `st`, or runs enqueue() eagerly (which also performs the kernels' one-time
+  // set-up) and, with `graphs`, captures it for the next calls; returns the steps enqueue() counted.  A failed capture
+  // is not fatal: use_graphs drops to 0 and the message names the chain by `label`.  Every chain but decode_enqueue's
+  // (all slots or none) goes through it.
+  int replay_or_capture(const std::vector<long long>& key, hipStream_t st, bool graphs, const char* label,
+                        const std::function<int()>& enqueue);
+  struct DonePoll {  // "all done?" after a segment: n device flags and their pinned mirror; flags = nullptr: never asked
+    const int* flags = nullptr;
+    int n = 0;
+    int* mirror = nullptr;
+  };
+  // A full-length chain's segments [lo, hi) of 32 positions up to `len`, each through replay_or_capture under
+  // key_of(lo) with graphs = use_graphs && capturable, read again for every segment; adds the steps to `steps`.  Stops
+  // behind the segment after which every flag of `poll` is set and returns that segment's hi (len: the chain ran out).
+  int run_segments(int len, hipStream_t st, bool capturable, const char* label,
+                   const std::function<std::vector<long long>(int)>& key_of,
+                   const std::function<int(int, int)>& enqueue_segment, const DonePoll& poll, int& steps);
   hipEvent_t trace_base_ = nullptr;  // WT_TRACE_PIPELINE=1: origin of the per-batch device timeline
   int enc_slot_ = 0;        // slot the next encode() fills
   int last_enc_slot_ = 0;   // slot the last encode() filled
@@ -660,7 +705,13 @@ class Engine {
   Timings timings_;
   bool have_logmel_ = false;
 
-  std::vector<void*> allocations_;
+  std::vector<void*> allocations_;  // device memory, freed by release()
+  std::vector<void*> pinned_;       // pinned host memory, likewise
+  void* dev_zeroed_bytes(size_t bytes);
+  void* pinned_bytes(size_t bytes);
+  // n zero-filled elements of device memory / n elements of pinned host memory, owned by the engine until release()
+  template <class T> T* dev_zeroed(size_t n) { return static_cast<T*>(dev_zeroed_bytes(n * sizeof(T))); }
+  template <class T> T* pinned(size_t n) { return static_cast<T*>(pinned_bytes(n * sizeof(T))); }
   std::map<std::string, const float*> tensors_;  // raw tensors by .wtw name
 
   // derived, re-laid-out weights
