@@ -12,7 +12,7 @@ CXXFLAGS := -std=c++17 -O3 -fPIC -Iinclude -I$(SRC) -Wall -Wno-unused-result
 HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH) -ffp-contract=fast $(HIPFLAGS_EXTRA)
 
 KERNELS := k_gemm k_gemm_planes k_gemm_bf16 k_misc k_attention k_attention_planes k_decoder k_cross_absorbed k_beam k_beam_full k_timestamps k_scores k_sample k_align k_suppress k_best_of
-HOSTSRC := engine engine_full capi capi_debug host_util longform words weights_gen whisper_api tflite_extract
+HOSTSRC := engine engine_full decode_results capi capi_debug host_util longform words weights_gen whisper_api tflite_extract
 OBJS := $(addprefix $(OBJ)/,$(addsuffix .o,$(KERNELS) $(HOSTSRC)))
 
 all: lib apps oracle

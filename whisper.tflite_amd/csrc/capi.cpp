@@ -485,10 +485,8 @@ int wt_logmel_batch(wt_engine* h, const float* pcm, int batch, float* mel) {
   return guarded(h, [&] {
     wt::Engine& e = *h->impl;
     e.require_idle();
-    float* d_pcm = e.staging_pcm(batch);
     float* d_mel = e.staging_mel(batch);
-    hipchk(hipMemcpyAsync(d_pcm, pcm, size_t(batch) * e.pcm_elems() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D pcm");
-    e.logmel(d_pcm, batch, d_mel);
+    e.logmel(e.upload_pcm(pcm, batch), batch, d_mel);
     hipchk(hipMemcpyAsync(mel, d_mel, size_t(batch) * e.mel_elems() * sizeof(float), hipMemcpyDeviceToHost, e.stream()), "D2H mel");
     e.sync();
   });
@@ -513,11 +511,11 @@ int wt_encdec_tokens_batch_dev(wt_engine* h, const float* d_mel, int batch, int6
         const int nb = std::min(64, batch - b0);
         e.encode(d_mel + size_t(b0) * e.mel_elems(), nb);
         e.decode(nb, ids + size_t(b0) * WT_MAX_IDS, n_ids + b0, nullptr, 0);
-        sums.insert(sums.end(), e.beam_sum.begin(), e.beam_sum.end());
-        lens.insert(lens.end(), e.beam_len.begin(), e.beam_len.end());
+        sums.insert(sums.end(), e.last.beam_sum.begin(), e.last.beam_sum.end());
+        lens.insert(lens.end(), e.last.beam_len.begin(), e.last.beam_len.end());
       }
-      e.beam_sum = sums;
-      e.beam_len = lens;
+      e.last.beam_sum = sums;
+      e.last.beam_len = lens;
       return;
     }
     // larger batches run as pipelined sub-batches of 32 clips: the encoder of a later
@@ -660,11 +658,11 @@ int wt_last_timings(const wt_engine* h, wt_timings* out) {
 int wt_last_beam_scores(const wt_engine* h, float* sum_logprob, int32_t* n_generated, int cap) {
   if (!h || cap < 0 || (cap > 0 && (!sum_logprob || !n_generated))) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.beam_scores_valid) return -WT_ERR_INVALID_ARG;
-  const int n = int(e.beam_sum.size());
+  if (!e.last.beam_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last.beam_sum.size());
   for (int i = 0; i < n && i < cap; ++i) {
-    sum_logprob[i] = e.beam_sum[i];
-    n_generated[i] = e.beam_len[i];
+    sum_logprob[i] = e.last.beam_sum[i];
+    n_generated[i] = e.last.beam_len[i];
   }
   return n;
 }
@@ -678,100 +676,101 @@ static int copy_segments(const std::vector<wt::Segment>& v, wt_segment* out, int
 int wt_last_segments(const wt_engine* h, wt_segment* out, int cap) {
   if (!h || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_segments_valid) return -WT_ERR_INVALID_ARG;
-  return copy_segments(e.last_segments, out, cap);
+  if (!e.last.segments_valid) return -WT_ERR_INVALID_ARG;
+  return copy_segments(e.last.segments, out, cap);
 }
 
 int wt_last_segment_text(const wt_engine* h, int index, char* out, size_t cap, size_t* len) {
   if (!h) return WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_segments_valid || index < 0 || size_t(index) >= e.last_segment_text.size()) {
+  if (!e.last.segments_valid || index < 0 || size_t(index) >= e.last.segment_text.size()) {
     if (len) *len = 0;
     return WT_ERR_INVALID_ARG;
   }
-  return copy_text(e.last_segment_text[size_t(index)], out, cap, len);
+  return copy_text(e.last.segment_text[size_t(index)], out, cap, len);
 }
 
 int wt_last_words(const wt_engine* h, wt_word* out, int cap) {
-  static_assert(sizeof(wt_word) == sizeof(wt::Engine::Word), "wt_word mirrors wt::Engine::Word");
+  static_assert(sizeof(wt_word) == sizeof(wt::Word), "wt_word mirrors wt::Word");
   if (!h || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_words_valid) return -WT_ERR_INVALID_ARG;
-  for (int i = 0; i < int(e.last_words.size()) && i < cap; ++i) std::memcpy(&out[i], &e.last_words[size_t(i)], sizeof(wt_word));
-  return int(e.last_words.size());
+  if (!e.last.words_valid) return -WT_ERR_INVALID_ARG;
+  for (int i = 0; i < int(e.last.words.size()) && i < cap; ++i) std::memcpy(&out[i], &e.last.words[size_t(i)], sizeof(wt_word));
+  return int(e.last.words.size());
 }
 
 int wt_last_word_text(const wt_engine* h, int index, char* out, size_t cap, size_t* len) {
   if (!h) return WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_words_valid || index < 0 || size_t(index) >= e.last_word_text.size()) {
+  if (!e.last.words_valid || index < 0 || size_t(index) >= e.last.word_text.size()) {
     if (len) *len = 0;
     return WT_ERR_INVALID_ARG;
   }
-  return copy_text(e.last_word_text[size_t(index)], out, cap, len);
+  return copy_text(e.last.word_text[size_t(index)], out, cap, len);
 }
 
 int wt_last_scores(const wt_engine* h, wt_clip_score* out, int cap) {
   static_assert(sizeof(wt_clip_score) == sizeof(wt::ClipScore), "wt_clip_score mirrors wt::ClipScore");
   if (!h || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_scores_valid) return -WT_ERR_INVALID_ARG;
-  const int n = int(e.last_scores.size());
-  for (int i = 0; i < n && i < cap; ++i) std::memcpy(&out[i], &e.last_scores[size_t(i)], sizeof(wt_clip_score));
+  if (!e.last.scores_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last.scores.size());
+  for (int i = 0; i < n && i < cap; ++i) std::memcpy(&out[i], &e.last.scores[size_t(i)], sizeof(wt_clip_score));
   return n;
 }
 
 int wt_last_decode_info(const wt_engine* h, wt_clip_decode* out, int cap) {
-  static_assert(sizeof(wt_clip_decode) == sizeof(wt::Engine::ClipDecode), "wt_clip_decode mirrors wt::Engine::ClipDecode");
+  static_assert(sizeof(wt_clip_decode) == sizeof(wt::ClipDecode), "wt_clip_decode mirrors wt::ClipDecode");
   if (!h || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_decode_info_valid) return -WT_ERR_INVALID_ARG;
-  const int n = int(e.last_decode_info.size());
-  for (int i = 0; i < n && i < cap; ++i) std::memcpy(&out[i], &e.last_decode_info[size_t(i)], sizeof(wt_clip_decode));
+  if (!e.last.decode_info_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last.decode_info.size());
+  for (int i = 0; i < n && i < cap; ++i) std::memcpy(&out[i], &e.last.decode_info[size_t(i)], sizeof(wt_clip_decode));
   return n;
 }
 
 int wt_last_best_of(const wt_engine* h, int32_t* picked, double* sum_logprob, int32_t* n_generated, int cap) {
   if (!h || cap < 0 || (cap > 0 && (!picked || !sum_logprob || !n_generated))) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_best_of_valid) return -WT_ERR_INVALID_ARG;
-  const int n = int(e.last_picked.size()), G = wt::kSampleGroupMax;
+  if (!e.last.best_of_valid) return -WT_ERR_INVALID_ARG;
+  static_assert(wt::kBestOfSlots == wt::kSampleGroupMax, "a best-of row holds one slot per sample of a launch");
+  const int n = int(e.last.picked.size()), G = wt::kBestOfSlots;
   for (int i = 0; i < n && i < cap; ++i) {
-    picked[i] = e.last_picked[size_t(i)];
+    picked[i] = e.last.picked[size_t(i)];
     for (int j = 0; j < G; ++j) {
-      sum_logprob[i * G + j] = e.last_best_of_sum[size_t(i) * G + j];
-      n_generated[i * G + j] = e.last_best_of_count[size_t(i) * G + j];
+      sum_logprob[i * G + j] = e.last.best_of_sum[size_t(i) * G + j];
+      n_generated[i * G + j] = e.last.best_of_count[size_t(i) * G + j];
     }
   }
   return n;
 }
 
 int wt_last_windows(const wt_engine* h, wt_window* out, int cap) {
-  static_assert(sizeof(wt_window) == sizeof(wt::Engine::Window), "wt_window mirrors wt::Engine::Window");
+  static_assert(sizeof(wt_window) == sizeof(wt::Window), "wt_window mirrors wt::Window");
   if (!h || cap < 0 || (cap > 0 && !out)) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_windows_valid) return -WT_ERR_INVALID_ARG;
-  const int n = int(e.last_windows.size());
-  for (int i = 0; i < n && i < cap; ++i) std::memcpy(&out[i], &e.last_windows[size_t(i)], sizeof(wt_window));
+  if (!e.last.windows_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last.windows.size());
+  for (int i = 0; i < n && i < cap; ++i) std::memcpy(&out[i], &e.last.windows[size_t(i)], sizeof(wt_window));
   return n;
 }
 
 int wt_last_window_files(const wt_engine* h, int32_t* file, int cap) {
   if (!h || cap < 0 || (cap > 0 && !file)) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_windows_valid || e.last_window_files.size() != e.last_windows.size()) return -WT_ERR_INVALID_ARG;
-  const int n = int(e.last_window_files.size());
-  for (int i = 0; i < n && i < cap; ++i) file[i] = e.last_window_files[size_t(i)];
+  if (!e.last.windows_valid || e.last.window_files.size() != e.last.windows.size()) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last.window_files.size());
+  for (int i = 0; i < n && i < cap; ++i) file[i] = e.last.window_files[size_t(i)];
   return n;
 }
 
 int wt_last_token_logprobs(const wt_engine* h, float* out, int stride, int cap_clips) {
   if (!h || cap_clips < 0 || stride < 0 || (cap_clips > 0 && stride > 0 && !out)) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_scores_valid) return -WT_ERR_INVALID_ARG;
-  const int n = int(e.last_scores.size()), own = e.last_lp_stride;
+  if (!e.last.scores_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last.scores.size()), own = e.last.lp_stride;
   for (int b = 0; b < n && b < cap_clips; ++b) {
-    for (int i = 0; i < stride; ++i) out[size_t(b) * stride + i] = i < own ? e.last_token_logprob[size_t(b) * own + i] : 0.0f;
+    for (int i = 0; i < stride; ++i) out[size_t(b) * stride + i] = i < own ? e.last.token_logprob[size_t(b) * own + i] : 0.0f;
   }
   return n;
 }
@@ -779,9 +778,9 @@ int wt_last_token_logprobs(const wt_engine* h, float* out, int stride, int cap_c
 int wt_last_segment_scores(const wt_engine* h, float* avg_logprob, int cap) {
   if (!h || cap < 0 || (cap > 0 && !avg_logprob)) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_scores_valid || !e.last_segments_valid) return -WT_ERR_INVALID_ARG;
-  const int n = int(e.last_segment_score.size());
-  for (int i = 0; i < n && i < cap; ++i) avg_logprob[i] = e.last_segment_score[size_t(i)];
+  if (!e.last.scores_valid || !e.last.segments_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last.segment_score.size());
+  for (int i = 0; i < n && i < cap; ++i) avg_logprob[i] = e.last.segment_score[size_t(i)];
   return n;
 }
 
@@ -830,10 +829,8 @@ int wt_detect_language_pcm(wt_engine* h, const float* pcm, size_t n_samples, int
     if (e.lang_tokens() < 1) throw wt::Error(WT_ERR_UNSUPPORTED, "language detection: this engine's vocabulary has no language tokens");
     std::vector<float> clip(e.pcm_elems(), 0.0f);  // one 30 s window, as wt_transcribe_pcm
     std::memcpy(clip.data(), pcm, std::min(n_samples, clip.size()) * sizeof(float));
-    float* d_pcm = e.staging_pcm(1);
     float* d_mel = e.staging_mel(1);
-    hipchk(hipMemcpyAsync(d_pcm, clip.data(), clip.size() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D pcm");
-    e.logmel(d_pcm, 1, d_mel);
+    e.logmel(e.upload_pcm(clip.data(), 1), 1, d_mel);
     e.encode(d_mel, 1);
     e.detect_language(1, lang, nullptr, prob);
     e.sync();
@@ -843,11 +840,11 @@ int wt_detect_language_pcm(wt_engine* h, const float* pcm, size_t n_samples, int
 int wt_last_languages(const wt_engine* h, int32_t* lang, float* prob, int cap) {
   if (!h || cap < 0 || (cap > 0 && (!lang || !prob))) return -WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_lang_valid) return -WT_ERR_INVALID_ARG;
-  const int n = int(e.last_lang.size());
+  if (!e.last.lang_valid) return -WT_ERR_INVALID_ARG;
+  const int n = int(e.last.lang.size());
   for (int i = 0; i < n && i < cap; ++i) {
-    lang[i] = e.last_lang[i];
-    prob[i] = e.last_lang_prob[i];
+    lang[i] = e.last.lang[i];
+    prob[i] = e.last.lang_prob[i];
   }
   return n;
 }
@@ -879,26 +876,15 @@ int wt_transcribe_pcm(wt_engine* h, const float* pcm, size_t n_samples, char* ou
     // pad with zeros or truncate to one 30 s window (whisper.cpp:753)
     std::vector<float> clip(e.pcm_elems(), 0.0f);
     std::memcpy(clip.data(), pcm, std::min(n_samples, clip.size()) * sizeof(float));
-    float* d_pcm = e.staging_pcm(1);
-    float* d_mel = e.staging_mel(1);
-    hipchk(hipMemcpyAsync(d_pcm, clip.data(), clip.size() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D pcm");
-    e.logmel(d_pcm, 1, d_mel);
-    const bool full = e.max_positions > 0;  // full-length decoding: rows of max_positions + 1 ids
-    std::vector<int64_t> ids(full ? size_t(e.max_positions) + 1 : size_t(WT_MAX_IDS));
-    int32_t n = 0;
-    if (full) {
-      e.encode_full(d_mel, 1);
-      const std::vector<long long> valid{(long long)std::min(n_samples, clip.size())};  // word timestamps: the window's own frames
-      e.decode_full(1, ids.data(), int(ids.size()), &n, &valid);
-    } else {
-      e.encode(d_mel, 1);
-      e.decode(1, ids.data(), &n, nullptr, 0);
-    }
+    const std::vector<long long> valid{(long long)std::min(n_samples, clip.size())};  // word timestamps: the window's own frames
+    std::vector<int64_t> ids;  // full-length decoding: a row of max_positions + 1 ids
+    std::vector<int32_t> n;
+    e.decode_windows(clip.data(), 1, &valid, &ids, &n);
     bool missing = false;
     // omit_special_tokens = false, as EncDec::transcribe passes (whisper.cpp:766-767)
-    text = wt::decode_tokens(e.vocab(), ids.data(), n, false, &missing);
+    text = wt::decode_tokens(e.vocab(), ids.data(), n[0], false, &missing);
     // option skip_silence: a silent window (only a call that itself ran with scores has them)
-    if (full && e.scores && e.last_scores_valid && !e.last_scores.empty() && e.last_scores[0].skipped) text.clear();
+    if (e.max_positions > 0 && e.scores && e.last.scores_valid && !e.last.scores.empty() && e.last.scores[0].skipped) text.clear();
     if (missing && e.verbose) std::fprintf(stderr, "[wt] token id without a vocab entry skipped\n");
   });
   if (rc != WT_OK) {
@@ -925,8 +911,8 @@ int wt_transcribe_long_batch(wt_engine* h, const float* const* pcm, const size_t
 int wt_last_file_text(const wt_engine* h, int file, char* out, size_t cap, size_t* len) {
   if (!h) return WT_ERR_INVALID_ARG;
   const wt::Engine& e = *h->impl;
-  if (!e.last_windows_valid || file < 0 || size_t(file) >= e.last_file_text.size()) return WT_ERR_INVALID_ARG;
-  return copy_text(e.last_file_text[size_t(file)], out, cap, len);
+  if (!e.last.windows_valid || file < 0 || size_t(file) >= e.last.file_text.size()) return WT_ERR_INVALID_ARG;
+  return copy_text(e.last.file_text[size_t(file)], out, cap, len);
 }
 
 int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, char* out, size_t cap,
@@ -937,112 +923,9 @@ int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, cha
     wt::Engine& e = *h->impl;
     e.require_idle();
     e.check_timestamp_call();  // before anything is enqueued
-    if (e.seek) {  // one window at a time, each starting at the last closed timestamp of the one before (longform.cpp)
-      wt::transcribe_seek(e, pcm, n_samples, &text);
-      return;
-    }
-    const size_t win = e.pcm_elems();
-    const size_t n_win = std::max<size_t>(1, (n_samples + win - 1) / win);
-    std::vector<int> langs;  // automatic language: every window's, joined over the batches
-    std::vector<float> lang_probs;
-    std::vector<wt::Segment> segments;  // option timestamps: every window's, clip = window index, times in the file
-    std::vector<std::string> segment_text;
-    std::vector<wt::ClipScore> scores;  // option scores: every window's
-    std::vector<float> token_logprob, segment_score;
-    std::vector<wt::Engine::ClipDecode> decode_info;  // sampling / fall-back: every window's
-    std::vector<int32_t> picked, best_of_count;       // best_of: every window's (zeros where a batch kept no sampled attempt)
-    std::vector<double> best_of_sum;
-    bool best_of_valid = false;
-    std::vector<wt::Engine::Word> words;  // option word_timestamps: every window's, clip = window index, times in the file
-    std::vector<std::string> word_text;
-    struct ClipBase {  // a window's Philox clip index is its index in the file, however the windows are batched
-      wt::Engine& e;
-      ~ClipBase() { e.clip_base = 0; }
-    } clip_base{e};
-    for (size_t w0 = 0; w0 < n_win; w0 += 32) {
-      const int B = int(std::min<size_t>(32, n_win - w0));
-      std::vector<float> clips(size_t(B) * win, 0.0f);
-      for (int b = 0; b < B; ++b) {
-        const size_t off = (w0 + b) * win;
-        if (off < n_samples) std::memcpy(&clips[size_t(b) * win], pcm + off, std::min(win, n_samples - off) * sizeof(float));
-      }
-      float* d_pcm = e.staging_pcm(B);
-      float* d_mel = e.staging_mel(B);
-      hipchk(hipMemcpyAsync(d_pcm, clips.data(), clips.size() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D pcm");
-      e.logmel(d_pcm, B, d_mel);
-      const bool full = e.max_positions > 0;
-      const size_t row = full ? size_t(e.max_positions) + 1 : size_t(WT_MAX_IDS);
-      std::vector<int64_t> ids(size_t(B) * row);
-      std::vector<int32_t> n(B);
-      if (full) {
-        e.encode_full(d_mel, B);
-        e.clip_base = long(w0);
-        std::vector<long long> valid;
-        for (int b = 0; b < B; ++b) {
-          const size_t off = (w0 + b) * win;
-          valid.push_back(off < n_samples ? (long long)std::min(win, n_samples - off) : 0);
-        }
-        e.decode_full(B, ids.data(), int(row), n.data(), &valid);
-      } else {
-        e.encode(d_mel, B);
-        e.decode(B, ids.data(), n.data(), nullptr, 0);
-      }
-      e.sync();  // clips[] is read by the H2D copy on the encoder stream
-      if (e.last_decode_info_valid) decode_info.insert(decode_info.end(), e.last_decode_info.begin(), e.last_decode_info.end());
-      if (full && e.best_of_sampling()) {
-        const size_t G = wt::kSampleGroupMax;
-        if (e.last_best_of_valid) {
-          picked.insert(picked.end(), e.last_picked.begin(), e.last_picked.end());
-          best_of_sum.insert(best_of_sum.end(), e.last_best_of_sum.begin(), e.last_best_of_sum.end());
-          best_of_count.insert(best_of_count.end(), e.last_best_of_count.begin(), e.last_best_of_count.end());
-          best_of_valid = true;
-        } else {
-          picked.resize(picked.size() + size_t(B), 0);
-          best_of_sum.resize(best_of_sum.size() + size_t(B) * G, 0.0);
-          best_of_count.resize(best_of_count.size() + size_t(B) * G, 0);
-        }
-      }
-      if (e.last_lang_valid) {
-        langs.insert(langs.end(), e.last_lang.begin(), e.last_lang.end());
-        lang_probs.insert(lang_probs.end(), e.last_lang_prob.begin(), e.last_lang_prob.end());
-      }
-      if (e.last_words_valid) {  // (before the segments are renumbered: a word's segment index counts in the whole file)
-        for (wt::Engine::Word wd : e.last_words) {
-          wd.clip += int(w0);
-          wd.segment += int(segments.size());
-          wd.t0_ms += wt::kWindowMs * wd.clip, wd.t1_ms += wt::kWindowMs * wd.clip;
-          words.push_back(wd);
-        }
-        word_text.insert(word_text.end(), e.last_word_text.begin(), e.last_word_text.end());
-      }
-      if (e.last_segments_valid) {
-        for (wt::Segment sg : e.last_segments) {
-          sg.clip += int(w0);
-          sg.t0_ms += wt::kWindowMs * sg.clip, sg.t1_ms += wt::kWindowMs * sg.clip;
-          segments.push_back(sg);
-        }
-        segment_text.insert(segment_text.end(), e.last_segment_text.begin(), e.last_segment_text.end());
-      }
-      const bool scored = full && e.scores && e.last_scores_valid && e.last_scores.size() == size_t(B);  // THIS batch ran with scores
-      if (scored) {
-        scores.insert(scores.end(), e.last_scores.begin(), e.last_scores.end());
-        token_logprob.insert(token_logprob.end(), e.last_token_logprob.begin(), e.last_token_logprob.end());
-        segment_score.insert(segment_score.end(), e.last_segment_score.begin(), e.last_segment_score.end());
-      }
-      for (int b = 0; b < B; ++b) {
-        if (w0 + b) text += '\n';
-        if (scored && e.last_scores[size_t(b)].skipped) continue;  // option skip_silence: an empty line
-        bool missing = false;
-        text += wt::decode_tokens(e.vocab(), &ids[size_t(b) * row], n[b], false, &missing);
-      }
-    }
-    if (e.last_scores_valid) e.last_scores = scores, e.last_token_logprob = token_logprob, e.last_segment_score = segment_score;
-    if (e.last_decode_info_valid) e.last_decode_info = decode_info;
-    e.last_best_of_valid = best_of_valid;
-    if (best_of_valid) e.last_picked = picked, e.last_best_of_sum = best_of_sum, e.last_best_of_count = best_of_count;
-    if (e.last_lang_valid) e.last_lang = langs, e.last_lang_prob = lang_probs;
-    if (e.last_segments_valid) e.last_segments = segments, e.last_segment_text = segment_text;
-    if (e.last_words_valid) e.last_words = words, e.last_word_text = word_text;
+    // seek: one window at a time, each starting at the last closed timestamp of the one before; else 32 at a time (longform.cpp)
+    if (e.seek) wt::transcribe_seek(e, pcm, n_samples, &text);
+    else wt::transcribe_windows(e, pcm, n_samples, &text);
   });
   if (rc != WT_OK) {
     if (len) *len = 0;
@@ -1309,12 +1192,10 @@ int wt_log_mel_spectrogram(const float* samples, int n_samples, const float* fil
     if (cap < size_t(n_mel) * frames) throw wt::Error(WT_ERR_BUFFER, "mel_out too small");
     std::vector<float> clip(e.pcm_elems(), 0.0f);
     std::memcpy(clip.data(), samples, size_t(n_samples) * sizeof(float));
-    float* d_pcm = e.staging_pcm(1);
     float* d_mel = e.staging_mel(1);
-    hipchk(hipMemcpyAsync(d_pcm, clip.data(), clip.size() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D pcm");
     // frames past n_len exist only in the 30 s window the kernels work on: they take no part in the
     // reference's maximum (whisper.cpp:198-203 runs over n_mel * n_len values)
-    e.logmel(d_pcm, 1, d_mel, frames);
+    e.logmel(e.upload_pcm(clip.data(), 1), 1, d_mel, frames);
     std::vector<float> full(e.mel_elems());
     hipchk(hipMemcpyAsync(full.data(), d_mel, full.size() * sizeof(float), hipMemcpyDeviceToHost, e.stream()), "D2H mel");
     e.sync();

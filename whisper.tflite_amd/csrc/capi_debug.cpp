@@ -1626,11 +1626,9 @@ int wt_dbg_frontend_stages(wt_engine* h, int batch, const float* pcm, int valid_
     wt::Engine& e = *h->impl;
     e.require_idle();
     const size_t nb = size_t(batch), T0 = size_t(e.mel_frames());
-    float* d_pcm = e.staging_pcm(batch);
     float* d_mel = e.staging_mel(batch);
     DevArr<float> d_raw(nb * e.mel_elems());
-    hipchk(hipMemcpyAsync(d_pcm, pcm, nb * e.pcm_elems() * sizeof(float), hipMemcpyHostToDevice, e.stream()), "H2D pcm");
-    e.logmel(d_pcm, batch, d_mel, valid_frames, d_raw.p);
+    e.logmel(e.upload_pcm(pcm, batch), batch, d_mel, valid_frames, d_raw.p);
     e.sync();
     const wt::Engine::FrontendView v = e.frontend_view();
     hipchk(hipMemcpy(mel, d_mel, nb * e.mel_elems() * sizeof(float), hipMemcpyDeviceToHost), "D2H mel");
@@ -2040,8 +2038,8 @@ int wt_dbg_set_alignment(wt_engine* h, int keep, int mode, int sub) {
 }
 
 int wt_dbg_last_alignment(const wt_engine* h, int clip, int32_t dims[6], int64_t* row, float* W, float* C, int32_t* jump) {
-  if (!h || clip < 0 || size_t(clip) >= h->impl->last_alignment.size()) return WT_ERR_INVALID_ARG;
-  const wt::Engine::ClipAlignment& a = h->impl->last_alignment[size_t(clip)];
+  if (!h || clip < 0 || size_t(clip) >= h->impl->last.alignment.size()) return WT_ERR_INVALID_ARG;
+  const wt::ClipAlignment& a = h->impl->last.alignment[size_t(clip)];
   if (dims) {
     const int32_t v[6] = {a.n_a, a.L, a.N, a.F, a.heads, a.T};
     std::memcpy(dims, v, sizeof(v));

@@ -1020,6 +1020,13 @@ float* Engine::staging_mel(int batch) {
   return ws_.mel_stage;
 }
 
+float* Engine::upload_pcm(const float* pcm, int batch) {
+  float* d_pcm = staging_pcm(batch);
+  const hipError_t rc = hipMemcpyAsync(d_pcm, pcm, size_t(batch) * pcm_elems() * sizeof(float), hipMemcpyHostToDevice, stream_);
+  if (rc != hipSuccess) throw Error(kErrDevice, std::string("H2D pcm: ") + hipGetErrorString(rc));
+  return d_pcm;
+}
+
 float* Engine::staging_pcm(int batch) {
   ensure_batch(batch);
   if (!ws_.pcm_stage) {
@@ -1486,23 +1493,35 @@ void Engine::decode(int batch, int64_t* ids, int32_t* n_ids, float* logits_host,
   check_timestamp_call();
   check_language_call();
   check_beam_call(logits_host != nullptr);
-  last_lang_valid = false;
-  last_segments_valid = false;
-  last_windows_valid = false;
-  last_window_files.clear(), last_file_text.clear();
-  clear_last_scores();
+  last.forget(kForgetSyncDecode);
   if (beam_size > 1) {
     decode_beam(batch, last_enc_slot_, ids, n_ids);
     return;
   }
-  beam_scores_valid = false;
   decode_enqueue(batch, last_enc_slot_, logits_host, logits_steps_cap);
   decode_collect(last_enc_slot_, ids, n_ids);
   if (language < 0) {  // the chain's language_head results came back with the ids (pinned copies, decode_enqueue)
-    last_lang.assign(h_lang_, h_lang_ + batch);
-    last_lang_prob.assign(h_lang_prob_, h_lang_prob_ + batch);
-    last_lang_valid = true;
+    last.lang.assign(h_lang_, h_lang_ + batch);
+    last.lang_prob.assign(h_lang_prob_, h_lang_prob_ + batch);
+    last.lang_valid = true;
   }
+}
+
+void Engine::decode_windows(const float* pcm, int batch, const std::vector<long long>* valid_samples, std::vector<int64_t>* ids,
+                            std::vector<int32_t>* n_ids) {
+  float* d_mel = staging_mel(batch);
+  logmel(upload_pcm(pcm, batch), batch, d_mel);
+  const size_t row = max_positions > 0 ? size_t(max_positions) + 1 : 32;
+  ids->assign(size_t(batch) * row, 0);
+  n_ids->assign(size_t(batch), 0);
+  if (max_positions > 0) {
+    encode_full(d_mel, batch);
+    decode_full(batch, ids->data(), int(row), n_ids->data(), valid_samples);
+  } else {
+    encode(d_mel, batch);
+    decode(batch, ids->data(), n_ids->data(), nullptr, 0);
+  }
+  sync();  // pcm is read by the H2D copy on the encoder stream
 }
 
 // -------------------------------------------------- language detection ---
@@ -1620,8 +1639,7 @@ void Engine::submit(const float* d_mel, int batch) {
   if (max_positions > 0) throw Error(kErrUnsupported, "full-length decoding (max_positions) runs on the synchronous entry points only, not in the pipeline");
   if (beam_size > 1) throw Error(kErrUnsupported, "beam search runs on the synchronous entry points only, not in the pipeline");
   check_language_call();
-  last_lang_valid = false;
-  clear_last_scores();  // (the getters report the last decode, and this one has no scores)
+  last.forget(kForgetSubmit);  // (the getters report the last decode, and this one has no scores)
   if (int(inflight_.size()) >= kSlots) throw Error(1, "pipeline is full (24 batches in flight): collect() first");
   if (batch > 64) throw Error(1, "decoder batches are limited to 64 clips per call");
   select_stream(true);
@@ -1635,8 +1653,7 @@ void Engine::submit_pcm(const float* d_pcm, int batch) {
   if (max_positions > 0) throw Error(kErrUnsupported, "full-length decoding (max_positions) runs on the synchronous entry points only, not in the pipeline");
   if (beam_size > 1) throw Error(kErrUnsupported, "beam search runs on the synchronous entry points only, not in the pipeline");
   check_language_call();
-  last_lang_valid = false;
-  clear_last_scores();  // (the getters report the last decode, and this one has no scores)
+  last.forget(kForgetSubmit);  // (the getters report the last decode, and this one has no scores)
   if (int(inflight_.size()) >= kSlots) throw Error(1, "pipeline is full (24 batches in flight): collect() first");
   if (batch > 64) throw Error(1, "decoder batches are limited to 64 clips per call");
   select_stream(true);
@@ -2338,7 +2355,6 @@ void Engine::ensure_beam_workspace() {
 // offset.  Like greedy's, a chain's launch sequence is fixed for its key and replayed from a hipGraph.
 void Engine::decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids) {
   const int K = int(beam_size);
-  beam_scores_valid = false;
   if (batch < 1 || batch > kBeamClipsMax) throw Error(kErrInvalidArg, "decoder batches are limited to 64 clips per call");
   Slot& slot = slots_[slot_idx];
   if (!slot.absorbed) throw Error(kErrUnsupported, "beam search: the encoder pass did not prepare the absorbed cross-attention");
@@ -2425,9 +2441,9 @@ void Engine::decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids) 
   HIPCHK(hipEventRecord(slot.dec_done, st));
   slot.steps = n_steps;
   decode_collect(slot_idx, ids, n_ids);  // waits; the encoder's non-finite flag, timings
-  beam_sum.assign(bw_.h_sum, bw_.h_sum + batch);
-  beam_len.assign(bw_.h_len, bw_.h_len + batch);
-  beam_scores_valid = true;
+  last.beam_sum.assign(bw_.h_sum, bw_.h_sum + batch);
+  last.beam_len.assign(bw_.h_len, bw_.h_len + batch);
+  last.beam_valid = true;
 }
 
 }  // namespace wt

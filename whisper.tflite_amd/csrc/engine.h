@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 
+#include "decode_results.h"
 #include "error.h"
 #include "host_util.h"
 #include "wtw_format.h"
@@ -26,12 +27,6 @@ struct BeamFullPart;
 struct ScorePart;
 struct SamplePart;
 struct SampleParams;
-
-// option scores: one clip of the last full-length decode (wt_clip_score mirrors it)
-struct ClipScore {
-  float sum_logprob, avg_logprob, no_speech_prob;
-  int32_t n_generated, skipped;
-};
 
 // WT_DEC_KERNEL_TIMERS diagnostics: the event pairs and launch classes of a slot's eager decoder launches
 struct DecTimers {
@@ -171,11 +166,9 @@ class Engine {
   long beam_size = 1;
   // throws kErrUnsupported when beam_size > 1 and the call or the options fall outside beam search's scope
   void check_beam_call(bool logits_tap) const;
-  // per clip of the last synchronous beam call: the chosen hypothesis's sum of log-probabilities and generated ids
-  // (EOT included); valid = the last synchronous decode was a beam search
-  std::vector<float> beam_sum;
-  std::vector<int> beam_len;
-  bool beam_scores_valid = false;
+  // What the last decode call left for the wt_last_* getters, in groups with one flag each (decode_results.h, DESIGN
+  // section 29).  Every entry point forgets its own mask of groups first and fills the groups its options ask for.
+  DecodeResults last;
   // Spoken-language detection.  The language tokens are ids [kLangLo, kLangLo + lang_tokens()): lang_tokens() =
   // min(language_count(), token_translate - kLangLo), or 0 when the engine has none (English-only, or a vocabulary
   // that ends before them).  language = -1 makes every greedy decode detect per clip (decode_enqueue); scope:
@@ -188,10 +181,6 @@ class Engine {
   // encoder output of the last encode() -> one decoder pass over position 0 of [sot] + language_head, nothing else
   // decoded: lang [batch], probs [batch][lang_tokens()] (or nullptr), prob [batch] (or nullptr).  batch <= 64.
   void detect_language(int batch, int32_t* lang, float* probs, float* prob);
-  // per clip of the last synchronous decode with language = -1: the language used and its probability
-  std::vector<int> last_lang;
-  std::vector<float> last_lang_prob;
-  bool last_lang_valid = false;
   // Full-length greedy decoding (decode_full).  0 = off: the max_tokens path above, 31 positions.
   // P in [32, full_cap()]: the oracle's max_positions — positions 0 .. P - 1 are fed, a row holds at most P + 1 ids —
   // on the synchronous full-length entry points and the text entry points.  Scope: greedy, fp32-accurate storage, a
@@ -222,11 +211,6 @@ class Engine {
   // the model's logits reach past <|0.00|>: ids token_beg .. n_vocab - 1 are the timestamps
   bool has_timestamp_tokens() const { return dims_.n_vocab > vocab_.token_beg + 1 && vocab_.token_eot >= 0 && vocab_.token_eot < vocab_.token_beg; }
   void check_timestamp_call() const;
-  // segments of every clip of the last synchronous timestamp decode (clip = index in the call; wt_transcribe_long_pcm
-  // renumbers them per window); valid = the last synchronous decode ran with timestamps
-  std::vector<Segment> last_segments;
-  std::vector<std::string> last_segment_text;  // the decoded text ids of each
-  bool last_segments_valid = false;
   // Decode confidence.  scores = 1: decode_full also forms, on the device inside the chain
   // (k_scores.hip), the log-probability of every generated id under the set it was chosen from, their sum and count per
   // clip, and the no-speech probability of the position-0 row.  Full-length greedy decoding only, with or without
@@ -237,14 +221,6 @@ class Engine {
   long no_speech_threshold = 600, logprob_threshold = -1000;  // thousandths
   // <|nospeech|> is the id the vocabulary calls token_solm (50361, multilingual 50362); the option needs it below n_vocab
   bool has_no_speech_token() const { return vocab_.token_solm >= 0 && vocab_.token_solm < dims_.n_vocab; }
-  // per clip of the last synchronous decode with scores (wt_transcribe_long_pcm: per window); token log-probabilities
-  // [clips][last_lp_stride] aligned with the id rows (0 for prompt ids and padding); the mean over each segment's text ids
-  std::vector<ClipScore> last_scores;
-  std::vector<float> last_token_logprob;
-  int last_lp_stride = 0;
-  std::vector<float> last_segment_score;
-  bool last_scores_valid = false;
-  void clear_last_scores();  // every decode that forms no scores calls it: the getters never report an earlier call
   // Temperature sampling and fall-back.  temperature (thousandths) > 0 or temperature_fallback = 1:
   // decode_full selects with sample_partial + sample_select (k_sample.hip) in place of select_token / ts_select; the
   // parameters of an attempt (1 / T per clip, seed, attempt, clip_base) reach the kernels through a block in device
@@ -272,18 +248,6 @@ class Engine {
   // point's stand.
   long fallback_beam = 0;
   bool beam_fallback() const { return fallback_beam != 0 && full_beam != 0 && beam_size > 1 && sampling(); }
-  // per clip of the last decode in which some clip's kept attempt ran N > 1 samples: the kept sample and every
-  // sample's sum and count [clips][8] (a clip kept from an attempt at temperature 0: sample 0, its own sum and count)
-  std::vector<int32_t> last_picked, last_best_of_count;
-  std::vector<double> last_best_of_sum;
-  bool last_best_of_valid = false;
-  struct ClipDecode {  // (wt_clip_decode)
-    int32_t temperature_milli, attempts, needs_fallback;
-    float compression_ratio;
-  };
-  // per clip of the last synchronous decode that sampled or ran fall-back; cleared by every decode that did neither
-  std::vector<ClipDecode> last_decode_info;
-  bool last_decode_info_valid = false;
   // bytes of text / bytes of zlib's compress() of it at the default level, 0 for empty text; zlib is loaded at first
   // use (libz.so.1): kErrUnsupported when it cannot be
   static bool zlib_available();
@@ -366,37 +330,11 @@ class Engine {
   void check_word_call() const;  // throws kErrUnsupported when word_timestamps is set outside its scope
   // The alignment pass over the id rows the last decode_full left on the host: segs = the segments whose ids below EOT
   // are the clips' text (clip = index in that call, id_begin an index into the clip's id row), valid_samples = the
-  // samples of every clip (empty: full length).  Fills last_words (segment = index into segs) and, with keep_alignment,
-  // appends to last_alignment.  decode_full calls it with its own segments unless defer_word_alignment is set: the
+  // samples of every clip (empty: full length).  Fills last.words (segment = index into segs) and, with keep_alignment,
+  // appends to last.alignment.  decode_full calls it with its own segments unless defer_word_alignment is set: the
   // seeking loop sets that and aligns each window over the segments seek_step kept.
   void align_words(int batch, const std::vector<Segment>& segs, const std::vector<long long>& valid_samples);
   bool defer_word_alignment = false;
-  struct Word {  // (wt_word)
-    int32_t clip, segment, t0_ms, t1_ms, id_begin, id_count;
-    float probability;
-  };
-  std::vector<Word> last_words;
-  std::vector<std::string> last_word_text;
-  bool last_words_valid = false;
-  struct ClipAlignment {  // keep_alignment: what the alignment pass formed for one clip
-    std::vector<long long> row;  // the L ids fed
-    int n_a = 0, L = 0, N = 0, F = 0, heads = 0, T = 0;
-    std::vector<float> W, C;     // [heads][L][T], [N][T]
-    std::vector<int> jump;       // [N]
-  };
-  std::vector<ClipAlignment> last_alignment;
-
-  struct Window {  // (wt_window)
-    int64_t seek_sample;
-    int32_t advance_samples, n_context, n_prompt, n_kept_ids, skipped, temperature_milli;
-  };
-  // one record per window of the last synchronous decode when that was a seeking one
-  std::vector<Window> last_windows;
-  bool last_windows_valid = false;
-  // wt_transcribe_long_batch: the file of every entry of last_windows, and every file's text (its windows' lines joined
-  // by '\n'); both empty after any other call
-  std::vector<int32_t> last_window_files;
-  std::vector<std::string> last_file_text;
 
   int mel_frames() const { return 2 * dims_.n_audio_ctx; }
   size_t mel_elems() const { return size_t(dims_.n_mels) * mel_frames(); }
@@ -456,6 +394,12 @@ class Engine {
   void ensure_batch(int batch);
   float* staging_mel(int batch);  // device buffer [B][mel_elems]
   float* staging_pcm(int batch);  // device buffer [B][pcm_elems]
+  float* upload_pcm(const float* pcm, int batch);  // host [B][pcm_elems] -> staging_pcm(batch), async on stream()
+  // `batch` host windows, already padded, through the front end, the encoder and the decoder: encode_full + decode_full
+  // (valid_samples as decode_full takes them) into rows of max_positions + 1 ids when max_positions is set, else
+  // encode + decode into rows of 32.  Synchronises every stream: pcm may be freed on return.
+  void decode_windows(const float* pcm, int batch, const std::vector<long long>* valid_samples, std::vector<int64_t>* ids,
+                      std::vector<int32_t>* n_ids);
 
   // test tap: `n_dec` decodes (slots 0..n_dec-1, whose cross-KV caches must hold a previous batch) next
   // to `n_enc` pipelined encoder passes; device time of each decode and of the encoder passes together
@@ -600,8 +544,8 @@ class Engine {
     const float* nosp = nullptr;
     std::function<int(int)> n_prompt;  // clip -> the ids of its fed prompt
   };
-  // the caller's id rows and counts, and last_scores / last_token_logprob, last_segments / _text / _score as the
-  // options ask: scores first, the segment pass reads `skipped`
+  // the caller's id rows and counts, and the scores and segments groups of `last` as the options ask: scores first, the
+  // segment pass reads `skipped`
   void publish_full(const FullResult& r, int batch, int64_t* ids, int ids_stride, int32_t* n_ids);
   // Whisper's two silence tests on (no_speech_prob, avg_logprob).  They differ where avg_logprob equals the threshold:
   // transcribe() skips a clip unless avg > threshold (below = false), decode_with_fallback exempts a clip from another

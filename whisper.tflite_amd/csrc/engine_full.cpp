@@ -16,17 +16,6 @@ namespace wt {
 
 // ------------------------------------------------ full-length decoding ---
 
-void Engine::clear_last_scores() {
-  last_scores_valid = false;
-  last_scores.clear();
-  last_token_logprob.clear();
-  last_segment_score.clear();
-  last_lp_stride = 0;
-  last_decode_info_valid = false;  // (nor a sampled one)
-  last_best_of_valid = false;
-  last_decode_info.clear();
-}
-
 // option timestamps outside full-length decoding: every decode call is refused (with max_positions set, the refusals
 // of check_full_call and of the other entry points apply as they are)
 // (options scores and skip_silence live in the same scope and are refused here with it)
@@ -302,11 +291,11 @@ void Engine::publish_full(const FullResult& r, int batch, int64_t* ids, int ids_
   const bool ts = timestamps != 0, sc = scores != 0;
   const int stride = r.stride, out_stride = full_cap() + 1;
   if (sc) {
-    last_scores.assign(size_t(batch), ClipScore{});
-    last_lp_stride = out_stride;
-    last_token_logprob.assign(size_t(batch) * out_stride, 0.0f);
+    last.scores.assign(size_t(batch), ClipScore{});
+    last.lp_stride = out_stride;
+    last.token_logprob.assign(size_t(batch) * out_stride, 0.0f);
     for (int b = 0; b < batch; ++b) {
-      ClipScore& s = last_scores[size_t(b)];
+      ClipScore& s = last.scores[size_t(b)];
       s.avg_logprob = avg_logprob(r.sum[b], r.count[b]);
       s.n_generated = r.count[b];
       s.sum_logprob = float(r.sum[b]);
@@ -314,11 +303,11 @@ void Engine::publish_full(const FullResult& r, int batch, int64_t* ids, int ids_
       // Whisper's rule: silence unless the text itself is confident
       s.skipped = skip_silence && silent(s.no_speech_prob, s.avg_logprob, false);
       for (int i = r.n_prompt(b); i < std::min(r.n[b], out_stride); ++i) {
-        last_token_logprob[size_t(b) * out_stride + i] = r.lp[size_t(b) * stride + i];
+        last.token_logprob[size_t(b) * out_stride + i] = r.lp[size_t(b) * stride + i];
       }
     }
-    last_segment_score.clear();
-    last_scores_valid = true;
+    last.segment_score.clear();
+    last.scores_valid = true;
   }
   for (int b = 0; b < batch; ++b) {
     n_ids[b] = r.n[b];
@@ -327,24 +316,24 @@ void Engine::publish_full(const FullResult& r, int batch, int64_t* ids, int ids_
     }
   }
   if (ts) {
-    last_segments.clear();
-    last_segment_text.clear();
+    last.segments.clear();
+    last.segment_text.clear();
     for (int b = 0; b < batch; ++b) {
-      if (sc && last_scores[size_t(b)].skipped) continue;  // a silent clip has no segments
+      if (sc && last.scores[size_t(b)].skipped) continue;  // a silent clip has no segments
       const int64_t* const row = reinterpret_cast<const int64_t*>(r.ids + size_t(b) * stride);
-      const size_t first = last_segments.size();
-      parse_segments(vocab_, row, std::min(r.n[b], stride), r.n_prompt(b), b, &last_segments);
-      for (size_t i = first; i < last_segments.size(); ++i) {
+      const size_t first = last.segments.size();
+      parse_segments(vocab_, row, std::min(r.n[b], stride), r.n_prompt(b), b, &last.segments);
+      for (size_t i = first; i < last.segments.size(); ++i) {
         bool missing = false;
-        last_segment_text.push_back(decode_tokens(vocab_, row + last_segments[i].id_begin, last_segments[i].id_count, false, &missing));
+        last.segment_text.push_back(decode_tokens(vocab_, row + last.segments[i].id_begin, last.segments[i].id_count, false, &missing));
         if (sc) {  // the mean log-probability of the segment's text ids
           double sum = 0.0;
-          for (int k = 0; k < last_segments[i].id_count; ++k) sum += double(r.lp[size_t(b) * stride + last_segments[i].id_begin + k]);
-          last_segment_score.push_back(float(sum / double(std::max(last_segments[i].id_count, 1))));
+          for (int k = 0; k < last.segments[i].id_count; ++k) sum += double(r.lp[size_t(b) * stride + last.segments[i].id_begin + k]);
+          last.segment_score.push_back(float(sum / double(std::max(last.segments[i].id_count, 1))));
         }
       }
     }
-    last_segments_valid = true;
+    last.segments_valid = true;
   }
 }
 
@@ -358,14 +347,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   require_idle();
   check_full_args(batch, ids_stride);
   const int P = int(max_positions), slot_idx = last_enc_slot_;
-  last_lang_valid = false;
-  beam_scores_valid = false;
-  last_segments_valid = false;
-  last_windows_valid = false;
-  last_window_files.clear(), last_file_text.clear();
-  last_words_valid = false;
-  last_alignment.clear();
-  clear_last_scores();  // (the decode info with them)
+  last.forget(kForgetFullDecode);
   // (full_beam = 1: check_full_call; fallback_beam = 1 with a temperature: the beam chain is the attempt at 0 below)
   const bool bfb = beam_fallback();
   if (beam_size > 1 && !bfb) return decode_beam_full(batch, ids, ids_stride, n_ids);
@@ -374,7 +356,6 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   ensure_batch(batch);
   ensure_full_workspace(batch);  // (before any capture: nothing may be allocated inside one)
   const bool bo = best_of_sampling();  // attempts above temperature 0 decode best_of samples per clip
-  last_best_of_valid = false;
   if (bo) {
     if (!slots_[slot_idx].absorbed) throw Error(kErrUnsupported, "best_of: the encoder pass did not prepare the absorbed cross-attention");
     ensure_best_of_workspace();
@@ -587,7 +568,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     std::vector<int32_t> m_picked(size_t(batch), 0), m_bo_count(bo ? size_t(batch) * G : 0, 0);
     std::vector<double> m_bo_sum(bo ? size_t(batch) * G : 0, 0.0);
     bool any_wide = false;
-    last_decode_info.assign(size_t(batch), ClipDecode{0, 0, 0, 0.0f});
+    last.decode_info.assign(size_t(batch), ClipDecode{0, 0, 0, 0.0f});
     for (size_t attempt = 0; attempt < temps.size(); ++attempt) {
       SampleParams& prm = *fw_.h_prm;
       const unsigned long long sd = static_cast<unsigned long long>(seed);
@@ -629,7 +610,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
         }
         std::copy(h_ids + size_t(b) * stride, h_ids + size_t(b + 1) * stride, m_ids.begin() + size_t(b) * stride);
         m_n[size_t(b)] = fw_.h_n[b];
-        ClipDecode& info = last_decode_info[size_t(b)];
+        ClipDecode& info = last.decode_info[size_t(b)];
         info.temperature_milli = int32_t(temps[attempt]);
         info.attempts = int32_t(attempt) + 1;
         info.needs_fallback = 0;
@@ -665,15 +646,15 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       std::copy(m_count.begin(), m_count.end(), fw_.h_count);
       std::copy(m_nosp.begin(), m_nosp.end(), fw_.h_nosp);
     }
-    last_decode_info_valid = true;
-    if (any_wide) last_picked = m_picked, last_best_of_sum = m_bo_sum, last_best_of_count = m_bo_count, last_best_of_valid = true;
+    last.decode_info_valid = true;
+    if (any_wide) last.picked = m_picked, last.best_of_sum = m_bo_sum, last.best_of_count = m_bo_count, last.best_of_valid = true;
   }
   FullResult r;
   r.ids = h_ids; r.stride = stride; r.n = fw_.h_n; r.lp = h_lp;
   r.sum = fw_.h_sum; r.count = fw_.h_count; r.nosp = fw_.h_nosp; r.n_prompt = np_of;
   publish_full(r, batch, ids, ids_stride, n_ids);
   if (word_timestamps && !defer_word_alignment) {
-    align_words(batch, last_segments, valid_samples ? *valid_samples : std::vector<long long>());
+    align_words(batch, last.segments, valid_samples ? *valid_samples : std::vector<long long>());
   }
 }
 
@@ -736,10 +717,10 @@ void Engine::decode_beam_full(int batch, int64_t* ids, int ids_stride, int32_t* 
   int steps = 0;
   beam_full_chains(batch, true, steps);
   const int stride = full_cap() + 1, n_prompt = int(prompt().size());
-  beam_sum.assign(size_t(batch), 0.0f);
-  beam_len.assign(bf_.h_len, bf_.h_len + batch);
-  for (int b = 0; b < batch; ++b) beam_sum[size_t(b)] = float(bf_.h_sum[b]);
-  beam_scores_valid = true;
+  last.beam_sum.assign(size_t(batch), 0.0f);
+  last.beam_len.assign(bf_.h_len, bf_.h_len + batch);
+  for (int b = 0; b < batch; ++b) last.beam_sum[size_t(b)] = float(bf_.h_sum[b]);
+  last.beam_valid = true;
   FullResult r;
   r.ids = bf_.h_ids; r.stride = stride; r.n = bf_.h_n; r.lp = bf_.h_lp;
   r.sum = bf_.h_sum; r.count = bf_.h_len; r.nosp = bf_.h_nosp; r.n_prompt = [n_prompt](int) { return n_prompt; };
@@ -1016,14 +997,14 @@ void Engine::align_words(int batch, const std::vector<Segment>& segs, const std:
   const int n_heads = int(heads.size());
   const int text_cap = cap - n_a - 2;
   if (text_cap < 1) throw Error(kErrInvalidArg, "word_timestamps: the prompt leaves no position for text");
-  const bool scored = scores != 0 && last_scores_valid;
+  const bool scored = scores != 0 && last.scores_valid;
   const std::string lang = language >= 0 && language < language_count() ? lang_code(size_t(language)) : std::string("en");
   const bool unicode_only = lang == "zh" || lang == "ja" || lang == "th" || lang == "lo" || lang == "my" || lang == "yue";
 
   // ---- the rows: per clip the text ids of its segments (below EOT, timestamps removed) and where they sit in its id row
   struct Clip {
     std::vector<long long> text;
-    std::vector<int> at, seg;  // index in the id row, index in last_segments
+    std::vector<int> at, seg;  // index in the id row, index in last.segments
     int L = 0, N = 0, F = 0;
   };
   std::vector<Clip> clips(static_cast<size_t>(batch));
@@ -1111,8 +1092,8 @@ void Engine::align_words(int batch, const std::vector<Segment>& segs, const std:
   sink.heads_total = n_heads; sink.L_max = L_max; sink.ldw = T; sink.W = aw_.W;
   sink.layer.resize(size_t(c.n_text_layer));
   for (int a = 0; a < n_heads; ++a) sink.layer[size_t(heads[size_t(a)].first)].emplace_back(heads[size_t(a)].second, a);
-  const size_t keep0 = last_alignment.size();  // (the seeking loop appends window after window)
-  if (keep_alignment) last_alignment.resize(keep0 + size_t(batch));
+  const size_t keep0 = last.alignment.size();  // (the seeking loop appends window after window)
+  if (keep_alignment) last.alignment.resize(keep0 + size_t(batch));
   for (int c0 = 0; c0 < batch; c0 += sub) {
     const int nb = std::min(sub, batch - c0);
     for (int b = 0; b < nb; ++b) sink.F[b] = clips[size_t(c0 + b)].F;
@@ -1132,7 +1113,7 @@ void Engine::align_words(int batch, const std::vector<Segment>& segs, const std:
     if (keep_alignment) {
       HIPCHK(hipStreamSynchronize(st));
       for (int b = 0; b < nb; ++b) {
-        ClipAlignment& ka = last_alignment[keep0 + size_t(c0 + b)];
+        ClipAlignment& ka = last.alignment[keep0 + size_t(c0 + b)];
         const Clip& cl = clips[size_t(c0 + b)];
         ka.n_a = n_a, ka.L = cl.L, ka.N = cl.N, ka.F = cl.F, ka.heads = n_heads, ka.T = T;
         ka.row.assign(fw_.h_ids + size_t(c0 + b) * stride, fw_.h_ids + size_t(c0 + b) * stride + cl.L);
@@ -1152,12 +1133,12 @@ void Engine::align_words(int batch, const std::vector<Segment>& segs, const std:
   HIPCHK(hipStreamSynchronize(st));
 
   // ---- words on the host
-  last_words.clear();
-  last_word_text.clear();
+  last.words.clear();
+  last.word_text.clear();
   for (int b = 0; b < batch; ++b) {
     const Clip& cl = clips[size_t(b)];
     const int* jump = aw_.h_jump + size_t(b) * N_max;
-    if (keep_alignment) last_alignment[keep0 + size_t(b)].jump.assign(jump, jump + cl.N);
+    if (keep_alignment) last.alignment[keep0 + size_t(b)].jump.assign(jump, jump + cl.N);
     const int n_text = int(cl.text.size());
     if (n_text == 0) continue;  // no segments (nothing decoded, or skip_silence blanked the clip): no words
     std::vector<int64_t> ids(cl.text.begin(), cl.text.end());
@@ -1180,15 +1161,15 @@ void Engine::align_words(int batch, const std::vector<Segment>& segs, const std:
       w.id_begin = cl.at[size_t(s0)]; w.id_count = cl.at[size_t(s0 + len - 1)] - cl.at[size_t(s0)] + 1;
       if (scored) {
         double sum = 0.0;
-        for (int k = 0; k < len; ++k) sum += std::exp(double(last_token_logprob[size_t(b) * last_lp_stride + cl.at[size_t(s0 + k)]]));
+        for (int k = 0; k < len; ++k) sum += std::exp(double(last.token_logprob[size_t(b) * last.lp_stride + cl.at[size_t(s0 + k)]]));
         w.probability = float(sum / double(len));
       }
-      last_words.push_back(w);
-      last_word_text.push_back(decode_tokens(vocab_, ids.data() + s0, len, true, nullptr));
+      last.words.push_back(w);
+      last.word_text.push_back(decode_tokens(vocab_, ids.data() + s0, len, true, nullptr));
       s0 += len;
     }
   }
-  last_words_valid = true;
+  last.words_valid = true;
 }
 
 }  // namespace wt
