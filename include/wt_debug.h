@@ -413,6 +413,28 @@ int wt_dbg_layernorm_planes(wt_engine* h, int M, int d, const float* x, const fl
  * segment, scales[0]); scales always holds three values.  guard % 4 == 0. */
 int wt_dbg_f32_to_planes(wt_engine* h, int M, int ld, const float* x, const float* scales, int seg, int guard,
                          uint16_t* planes);
+/* What Engine::upload_weights derived for the fp16-plane encoder, one record of 10 floats per contraction in the order
+ * of the force_fallback bits: conv1, conv2, then per layer qkv, attention, out, fc1, fc2, then cross-KV.  Read-only, no
+ * GPU work.  A GEMM record is {a_scale, w_scale, f16_ok, largest bound of the A operand, its typical magnitude, 0 ...};
+ * an attention record is {q, k, v scales, attn_f16_ok, then largest bound and typical magnitude of q (both times
+ * d_head^-1/2 log2 e, as the kernel splits it), of k and of v}.  The verdicts are the load-time ones, whatever
+ * force_fallback is set to.  *n = the number of records; the first min(*n, cap) are written to rec [cap][10]. */
+int wt_dbg_encoder_scales(wt_engine* h, float* rec, int cap, int* n);
+/* f16_scale_for (csrc/kernels.h) itself: no engine, no GPU work. */
+float wt_dbg_f16_scale_for(float bound);
+/* launch_gemm_planes on dense operands with every scale GIVEN, where the other plane GEMM taps take the tightest scale
+ * from the data: A [M][K], W [N][K], bias [N]; a_scale, w_scale, out_scale[3], seg, n_cu go to the launcher as they are.
+ * A is split on the host as the producers split it, hi = fp16(x * a_scale), lo = fp16(x * a_scale - hi), with no clamping:
+ * an element beyond fp16's range uploads as hi = inf, lo = -inf.  W goes through split_weight_planes at w_scale.
+ * epi 1 (bias), 3 (bias | gelu) or, fp32 output only, 5 (bias | residual: the residual is `out` itself, in place).
+ * out has M + guard_rows rows of N, in / out, uploaded as given and downloaded whole: float (planes_out = 0) or fp16 bits
+ * [2][(M + guard_rows) * N], hi then lo, of column n times out_scale[n / seg] (seg = 0: one segment).  The tap fills the
+ * launcher's arguments and calls it; it restates no addressing.  WT_ERR_INVALID_ARG before anything is launched: a null
+ * pointer, another epilogue, N % 128, K % 32, and whatever the launcher refuses (a scale that is not positive, seg % 8 or
+ * more than three segments). */
+int wt_dbg_gemm_planes_scaled(wt_engine* h, int M, int N, int K, const float* A, const float* W, const float* bias, int epi,
+                              float a_scale, float w_scale, const float out_scale[3], int seg, int n_cu, int planes_out,
+                              int guard_rows, void* out);
 /* The encoder attention launchers at a given shape, with given operand scales and with rows that belong to no clip
  * behind the last one.  The tap fills the launcher's arguments and calls the launcher; it restates no addressing.
  * kind 0: launch_encoder_attention with `variant` 0 (encoder_attention_f32) or 1 (encoder_attention_split<4, 3>), given

@@ -5,6 +5,7 @@ bar that an honest fp32 implementation of the same operation misses would say no
 The operation: out = softmax(q k^T / 8) v per (clip, head), d_head 64.  qkv is [B * T (+ guard rows)][3 * 64 * H],
 q | k | v thirds with the heads' 64 columns inside each third; out is [B * T][64 * H]."""
 import functools
+import math
 
 import numpy as np
 
@@ -29,14 +30,14 @@ ISOLATION_SHAPES = [(3, 65, 3), (2, 130, 2)]
 
 def f16_scale_for(bound):
     """csrc/kernels.h: the largest power of two s with bound * s <= 16384, clamped to 2^+-24; 1 for a bound that is not
-    positive.  (float32 arithmetic, as the engine's.)"""
-    bound = np.float32(bound)
+    positive.  (From the float32 bound's own exponent, as the engine's: no quotient that could overflow.)"""
+    bound = float(np.float32(bound))
     if not bound > 0:
         return 1.0
-    e = 24
-    while e > -24 and np.float32(16384.0) / bound < np.float32(2.0 ** e):  # (the engine compares the float32 quotient)
-        e -= 1
-    return 2.0 ** e
+    if math.isinf(bound):
+        return 2.0 ** -24
+    m, e = math.frexp(bound)  # bound = m 2^e, m in [0.5, 1): m 2^14 <= 2^14, and one more doubling fits only for m = 0.5
+    return 2.0 ** max(-24, min(24, 14 - e + (1 if m == 0.5 else 0)))
 
 
 def bf16_round(x):

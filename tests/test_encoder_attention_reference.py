@@ -9,12 +9,15 @@ import attn_cases as ac
 
 
 def test_f16_scale_for_is_the_largest_power_of_two_under_the_bound():
-    for bound in (1e-9, 2.0 ** -11, 0.3, 1.0, 4.4, 16384.0, 16385.0, 3e4, 1e12):
+    # (the last six: bounds whose quotient 16384 / bound overflows float32, subnormal ones, and the largest finite ones)
+    for bound in (1e-9, 2.0 ** -11, 0.3, 1.0, 4.4, 16384.0, 16385.0, 3e4, 1e12, 4.8e-35, 1e-38, 2.0 ** -140, 2.0 ** -149, 2.0 ** 127,
+                  3.4e38):
         s = ac.f16_scale_for(bound)
         assert np.log2(s) == round(np.log2(s)) and 2.0 ** -24 <= s <= 2.0 ** 24
         assert s == 2.0 ** -24 or bound * s <= 16384.0
         assert s == 2.0 ** 24 or bound * 2 * s > 16384.0
-    assert ac.f16_scale_for(0.0) == 1.0 and ac.f16_scale_for(float("nan")) == 1.0
+    assert ac.f16_scale_for(0.0) == 1.0 and ac.f16_scale_for(float("nan")) == 1.0 and ac.f16_scale_for(-1.0) == 1.0
+    assert ac.f16_scale_for(float("inf")) == 2.0 ** -24 and ac.f16_scale_for(1e-36) == 2.0 ** 24
 
 
 def test_sweep_reaches_every_grid_residue_and_tile_edge():

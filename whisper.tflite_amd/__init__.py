@@ -72,6 +72,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
     "wt_dbg_pcm_to_planes",
     "wt_dbg_gemm_addressed", "wt_dbg_plane_gemm_plan", "wt_dbg_gemm_ln_fused", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes", "wt_dbg_encoder_attention_at",
+    "wt_dbg_encoder_scales", "wt_dbg_f16_scale_for", "wt_dbg_gemm_planes_scaled",
     "wt_dbg_cross_attention_records", "wt_dbg_cross_attention_records_bf16", "wt_dbg_cross_combine", "wt_dbg_cross_combine_bf16",
     "wt_dbg_align_scores", "wt_dbg_align_matrix", "wt_dbg_align_dtw", "wt_dbg_last_alignment", "wt_dbg_set_alignment",
 ]
@@ -303,6 +304,11 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_layernorm_planes.argtypes = [c_void_p, c_int, c_int, fp, fp, fp, c_float, c_int, c_int, u16p, fp, ip32]
         L.wt_dbg_f32_to_planes.argtypes = [c_void_p, c_int, c_int, fp, fp, c_int, c_int, u16p]
         L.wt_dbg_encoder_attention_at.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, fp, c_void_p]
+        L.wt_dbg_encoder_scales.argtypes = [c_void_p, fp, c_int, POINTER(c_int)]
+        L.wt_dbg_f16_scale_for.argtypes = [c_float]
+        L.wt_dbg_f16_scale_for.restype = c_float
+        L.wt_dbg_gemm_planes_scaled.argtypes = [c_void_p, c_int, c_int, c_int, fp, fp, fp, c_int, c_float, c_float, fp, c_int, c_int,
+                                                c_int, c_int, c_void_p]
         L.wt_vocab_split_words.argtypes = [c_void_p, ip64, c_int, c_int, ip32, c_int]
         L.wt_vocab_merge_punctuation.argtypes = [c_void_p, ip64, c_int, ip32, c_int, ip32, c_int]
         L.wt_dtw_path.argtypes = [fp, c_int, c_int, ip32, ip32, c_int]
@@ -334,6 +340,11 @@ def plane_gemm_plan(M, N, K, epi, planes_out=False, ln=False, n_cu=0):
     tile, schedule, fused, mode = (int(v) for v in plan)
     return types.SimpleNamespace(tile=tile, schedule=schedule, fused=bool(fused), mode=mode,
                                  kernel=f"{PLANE_GEMM_TILES[tile]} {PLANE_GEMM_SCHEDULES[schedule]}" + (" + LayerNorm" if fused else ""))
+
+
+def f16_scale_for(bound) -> float:
+    """csrc/kernels.h f16_scale_for, the engine's own (wt_dbg_f16_scale_for; no GPU work)."""
+    return float(lib().wt_dbg_f16_scale_for(c_float(float(np.float32(bound)))))
 
 
 def bf16_gemm_plan(M, N, epi, bf16_out=False, ln=False, c_rpb=1 << 30, ldc=None):
@@ -1902,6 +1913,39 @@ class Engine:
         self._check(lib().wt_dbg_f32_to_planes(self._h, M, ld, _fp(x), _fp(scales), seg, planes.shape[1] - M * ld,
                                                planes.ctypes.data_as(POINTER(ctypes.c_uint16))))
         return planes
+
+    def dbg_encoder_scales(self) -> np.ndarray:
+        """What upload_weights derived per contraction (wt_dbg_encoder_scales): float32 [n][10], conv1, conv2, then per layer
+        qkv, attention, out, fc1, fc2, then cross-KV.  GEMM rows: a_scale, w_scale, f16_ok, bound, typical; attention rows:
+        q, k, v scales, attn_f16_ok, then (bound, typical) of q, k and v."""
+        n = c_int(0)
+        self._check(lib().wt_dbg_encoder_scales(self._h, None, 0, ctypes.byref(n)))
+        rec = np.zeros((n.value, 10), np.float32)
+        self._check(lib().wt_dbg_encoder_scales(self._h, _fp(rec), n.value, ctypes.byref(n)))
+        return rec
+
+    def dbg_gemm_planes_scaled(self, A, W, bias, out, a_scale, w_scale, epi=1, out_scale=None, seg=0, n_cu=0):
+        """launch_gemm_planes on dense A [M][K], W [N][K] with the caller's scales (wt_dbg_gemm_planes_scaled).  `out` is
+        the in / out buffer of M + guard rows and selects the form: float32 [M + guard][N] (epi 5: the residual, in place)
+        or float16 [2][M + guard][N], the hi and lo planes of column n times out_scale[n // seg].  Returns the buffer
+        after the launch, a copy."""
+        A, W, bias = _f32(A), _f32(W), _f32(bias)
+        (M, K), N = A.shape, W.shape[0]
+        out = np.array(out, order="C")
+        if out.dtype == np.float32 and out.ndim == 2 and out.shape[1] == N:
+            planes, rows = 0, out.shape[0]
+        elif out.dtype == np.float16 and out.ndim == 3 and out.shape[0] == 2 and out.shape[2] == N:
+            planes, rows = 1, out.shape[1]
+        else:
+            raise ValueError("out must be float32 [M + guard][N] or float16 [2][M + guard][N]")
+        if W.shape != (N, K) or bias.shape != (N,) or rows < M:
+            raise ValueError("W must be [N][K], bias [N], and out at least M rows")
+        scales = _f32(out_scale if out_scale is not None else [1.0, 1.0, 1.0])
+        if scales.shape != (3,):
+            raise ValueError("out_scale holds three values")
+        self._check(lib().wt_dbg_gemm_planes_scaled(self._h, M, N, K, _fp(A), _fp(W), _fp(bias), epi, a_scale, w_scale,
+                                                    _fp(scales), seg, int(n_cu), planes, rows - M, out.ctypes.data_as(c_void_p)))
+        return out
 
     def dbg_encoder_attention_at(self, kind, qkv, batch, T, heads, out, variant=0, scales=None, guard_rows=None, copy=True):
         """An encoder attention launcher (wt_dbg_encoder_attention_at): kind 0 = launch_encoder_attention with `variant`

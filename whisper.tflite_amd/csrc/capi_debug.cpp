@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1899,6 +1900,45 @@ int wt_dbg_f32_to_planes(wt_engine* h, int M, int ld, const float* x, const floa
     wt::launch_f32_to_planes(dx.p, dout.p, long(plane), M, ld, scales, seg, h->impl->stream());
     h->impl->sync();
     dout.to_host(planes);
+  });
+}
+
+int wt_dbg_encoder_scales(wt_engine* h, float* rec, int cap, int* n) {
+  if (!h || !n || cap < 0 || (cap && !rec)) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    const std::vector<std::array<float, 10>> r = h->impl->encoder_scales();
+    *n = int(r.size());
+    for (size_t i = 0; i < r.size() && i < size_t(cap); ++i) std::copy(r[i].begin(), r[i].end(), rec + 10 * i);
+  });
+}
+
+float wt_dbg_f16_scale_for(float bound) { return wt::f16_scale_for(bound); }
+
+int wt_dbg_gemm_planes_scaled(wt_engine* h, int M, int N, int K, const float* A, const float* W, const float* bias, int epi,
+                              float a_scale, float w_scale, const float out_scale[3], int seg, int n_cu, int planes_out,
+                              int guard_rows, void* out) {
+  const bool epi_ok = planes_out ? (epi == wt::kEpiBias || epi == (wt::kEpiBias | wt::kEpiGelu))
+                                 : (epi == wt::kEpiBias || epi == (wt::kEpiBias | wt::kEpiGelu) || epi == (wt::kEpiBias | wt::kEpiResidual));
+  if (!h || !A || !W || !bias || !out || !out_scale || !epi_ok || M < 1 || N < 128 || N % 128 || K < 32 || K % 32 || n_cu < 0 ||
+      guard_rows < 0 || seg < 0) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const size_t cells = size_t(M + guard_rows) * N;
+    const DevPlanes dA(A, size_t(M) * K, a_scale);  // no clamping: an element past fp16's range uploads as hi = inf, lo = -inf
+    const DevArr<unsigned short> dW(weight_planes(W, N, K, w_scale));
+    DevArr<float> dB(N, bias), dC(planes_out ? 0 : cells, static_cast<const float*>(out));
+    DevArr<unsigned short> dO(planes_out ? 2 * cells : 0, static_cast<const unsigned short*>(out));
+    wt::PlaneGemmArgs g;
+    dense_gemm_args(g, M, N, K, dB.p, planes_out ? nullptr : dC.p, nullptr, 0);
+    g.A = dA.ptr(); g.a_plane = dA.plane; g.W = dW.p; g.a_scale = a_scale; g.w_scale = w_scale; g.n_cu = n_cu;
+    if (planes_out) {
+      g.P = dO.p; g.p_plane = long(cells); g.seg = seg;
+      g.out_scale[0] = out_scale[0]; g.out_scale[1] = out_scale[1]; g.out_scale[2] = out_scale[2];
+    }
+    wt::launch_gemm_planes(g, epi, h->impl->stream());
+    h->impl->sync();
+    if (planes_out) dO.to_host(static_cast<unsigned short*>(out)); else dC.to_host(static_cast<float*>(out));
   });
 }
 

@@ -440,7 +440,9 @@ void Engine::upload_weights(const std::string& path) {
       o.typ = float(std::sqrt(acc / d));
       return o;
     };
-    // out[n] = sum_k |W[n][k]| in[k % in.size()] + |bias[n]|   (conv taps repeat the input bound)
+    // out[n] = sum_k |W[n][k]| in[k % in.size()] + |bias[n]|.  Column k of a Linear is input channel k.  Column k of a
+    // conv tensor [co][ci][3] is channel k / 3, so k % in.size() pairs it with the right channel only for a one-element
+    // input bound: that is conv1 (the mel bound), the only conv whose output bound is formed — conv2's never is.
     auto linear_op = [&](const float* w, const float* bias, int N, int K, const Op& in) {
       Op o{std::vector<float>(N), 0.0f};
       double sq = 0.0;
@@ -469,7 +471,16 @@ void Engine::upload_weights(const std::string& path) {
       if (b > 0.0f && o.typ > 0.0f) f16_min_slack_bits_ = std::min(f16_min_slack_bits_, std::log2(kF16Slack * o.typ / b));
       return !(b > kF16Slack * o.typ);
     };
+    // the operands' {largest bound, typical} beside each verdict (encoder_scales): up to three per contraction
+    load_ops_.clear();
+    auto note = [&](const Op& a, const Op* b = nullptr, const Op* c = nullptr, float a_factor = 1.0f) {
+      std::array<float, 6> r{vmax(a.bound) * a_factor, a.typ * a_factor, 0.0f, 0.0f, 0.0f, 0.0f};
+      if (b) r[2] = vmax(b->bound), r[3] = b->typ;
+      if (c) r[4] = vmax(c->bound), r[5] = c->typ;
+      load_ops_.push_back(r);
+    };
     auto scale_of = [&](const Op& in, const float* w, size_t n) {
+      note(in);
       GemmScale g{f16_scale_for(vmax(in.bound)), f16_scale_for(maxabs(w, n)), slack_ok(in)};
       if (!g.f16_ok) ++n_f16_fallbacks_;
       return g;
@@ -493,6 +504,7 @@ void Engine::upload_weights(const std::string& path) {
       const float wmax = std::max(maxabs(wq, dd2), std::max(maxabs(wk, dd2), maxabs(wv, dd2)));
       sl.qkv.sc = GemmScale{f16_scale_for(vmax(ln1.bound)), f16_scale_for(wmax), slack_ok(ln1)};
       if (!sl.qkv.sc.f16_ok) ++n_f16_fallbacks_;
+      note(ln1);
       const Op qo = linear_op(wq, H(blk + ".attn.query.bias", d), d, d, ln1);
       const Op ko = linear_op(wk, nullptr, d, d, ln1);
       const Op vo = linear_op(wv, H(blk + ".attn.value.bias", d), d, d, ln1);
@@ -501,6 +513,7 @@ void Engine::upload_weights(const std::string& path) {
       sl.v = f16_scale_for(vmax(vo.bound));
       sl.attn_f16_ok = slack_ok(qo) && slack_ok(ko) && slack_ok(vo);
       if (!sl.attn_f16_ok) ++n_f16_fallbacks_;
+      note(qo, &ko, &vo, 0.125f * 1.44269504f);  // q as the kernel splits it
       sl.out.sc = scale_of(vo, H(blk + ".attn.out.weight", dd2), dd2);  // a convex combination of V rows
       const Op ln2 = ln_op(blk + ".mlp_ln.weight", blk + ".mlp_ln.bias");
       const float* w1 = H(blk + ".mlp.0.weight", 4 * dd2);
@@ -512,6 +525,7 @@ void Engine::upload_weights(const std::string& path) {
     const std::vector<float> ckv_w = cross_kv_weight(file, c);
     cross_kv_.sc = GemmScale{f16_scale_for(vmax(lnp.bound)), f16_scale_for(maxabs(ckv_w.data(), ckv_w.size())), slack_ok(lnp)};
     if (!cross_kv_.sc.f16_ok) ++n_f16_fallbacks_;
+    note(lnp);
     load_ok_.clear();
     for (bool* f : ok_flags()) load_ok_.push_back(*f);
   }
@@ -536,6 +550,30 @@ std::vector<bool*> Engine::ok_flags() {
   }
   f.push_back(&cross_kv_.sc.f16_ok);
   return f;
+}
+
+// One record per contraction in the order of ok_flags(): the scales the launches take, the load-time verdict (load_ok_,
+// not what force_fallback made of it) and the operands' largest bound and typical magnitude.  GEMM: {a_scale, w_scale,
+// ok, bound, typical}; attention: {q, k, v scales, ok, then bound and typical of q (times d_head^-1/2 log2 e), k and v}.
+std::vector<std::array<float, 10>> Engine::encoder_scales() const {
+  std::vector<std::array<float, 10>> r;
+  auto gemm = [&](const EncLinear& L) {
+    const size_t i = r.size();
+    r.push_back({L.sc.a, L.sc.w, load_ok_[i] ? 1.0f : 0.0f, load_ops_[i][0], load_ops_[i][1], 0.0f, 0.0f, 0.0f, 0.0f, 0.0f});
+  };
+  gemm(conv1_);
+  gemm(conv2_);
+  for (const EncLayer& el : enc_layers_) {
+    gemm(el.qkv);
+    const size_t i = r.size();
+    const std::array<float, 6>& o = load_ops_[i];
+    r.push_back({el.q, el.k, el.v, load_ok_[i] ? 1.0f : 0.0f, o[0], o[1], o[2], o[3], o[4], o[5]});
+    gemm(el.out);
+    gemm(el.fc1);
+    gemm(el.fc2);
+  }
+  gemm(cross_kv_);
+  return r;
 }
 
 void Engine::set_force_fallback(long mask) {

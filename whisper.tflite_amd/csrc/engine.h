@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <functional>
 #include <map>
@@ -379,6 +380,8 @@ class Engine {
   int f16_fallbacks() const { return n_f16_fallbacks_; }
   float f16_min_slack_bits() const { return f16_min_slack_bits_; }
   int f16_contractions() const { return int(load_ok_.size()); }
+  // what upload_weights derived per contraction, in the order of force_fallback's bits (engine.cpp; wt_dbg_encoder_scales)
+  std::vector<std::array<float, 10>> encoder_scales() const;
   // Test hook (option "force_fallback"): bit i treats contraction i — launch order: conv1, conv2, then per layer
   // qkv, attention, out, fc1, fc2, and last the cross-KV projection — as flagged by the load-time slack check, on top
   // of the contractions that check flagged itself.  Exercises every plane <-> fall-back hand-over on any weights.
@@ -677,6 +680,7 @@ class Engine {
   float f16_min_slack_bits_ = 0.0f;  // smallest log2(kF16Slack * typical / bound) over the checked operands (load time)
   long force_fallback_ = 0;
   std::vector<bool> load_ok_;  // the slack check's own verdicts, in contraction order (set_force_fallback)
+  std::vector<std::array<float, 6>> load_ops_;  // beside load_ok_: {largest bound, typical} of up to three operands
   std::vector<bool*> ok_flags();  // the records' f16_ok / attn_f16_ok in that order: a walk in launch order
   // the fp32-storage GEMM a contraction falls back to: the forced variant, else three bf16 planes (13; 16 = the same
   // at two blocks per CU beside the decoders of the pipeline)

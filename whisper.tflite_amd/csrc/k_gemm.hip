@@ -409,9 +409,13 @@ int gemm_occupancy(int variant) {
 
 float f16_scale_for(float bound) {
   if (!(bound > 0.0f)) return 1.0f;
+  if (std::isinf(bound)) return std::ldexp(1.0f, -24);
+  // bound = m * 2^e, m in [0.5, 1): bound * 2^(14 - e) = m * 2^14 <= 2^14, and one more doubling fits only for m = 0.5.
+  // (Taken from the bound itself and not from 16384 / bound: that quotient overflows for bounds below 16384 / FLT_MAX,
+  // and frexp of inf or 0 leaves the exponent at 0.)
   int e = 0;
-  (void)std::frexp(16384.0f / bound, &e);  // 16384 / bound = m * 2^e, m in [0.5, 1)
-  e -= 1;
+  const float m = std::frexp(bound, &e);
+  e = 14 - e + (m == 0.5f ? 1 : 0);
   e = e > 24 ? 24 : (e < -24 ? -24 : e);
   return std::ldexp(1.0f, e);
 }
