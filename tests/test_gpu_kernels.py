@@ -623,6 +623,55 @@ def test_plane_gemm_every_tile_shape_gives_the_same_result(pkg, eng, n_cu, expec
     assert rel_err(eng.dbg_gemm_planes(A, W, bias, epi=3, planes_out=True, n_cu=n_cu), gelu(ref)) < 4e-6
 
 
+BOTH_EPILOGUES = ((1, False), (3, True))  # bias to fp32; bias + GELU to planes
+PLANE_PROLOGUE_CASES = [
+    # M, N, K, n_cu, tile, {mode: schedule}, (epi, planes_out)s, pairs of modes that must agree bit for bit
+    # the 192 x 384 tile, one whole tile and a ragged one, at 1, 2 and 3 k-tiles: every schedule's prologue and last turn
+    (300, 384, 32, 2, 1, {0: 0, 1: 1, 2: 2, 4: 2}, BOTH_EPILOGUES, ((0, 1), (2, 4))),
+    (300, 384, 64, 2, 1, {0: 0, 1: 1, 2: 2, 4: 2}, BOTH_EPILOGUES, ((0, 1), (2, 4))),
+    (300, 384, 96, 2, 1, {0: 0, 1: 1, 2: 2, 4: 2}, BOTH_EPILOGUES, ((0, 1), (2, 4))),
+    # the persistent kernel at its shortest loop (4 k-tiles) and at 6, three tiles per block, the last row tile ragged
+    (1530, 1152, 128, 8, 1, {2: 3, 4: 2}, ((3, True),), ((2, 4),)),
+    (1530, 1152, 192, 8, 1, {2: 3, 4: 2}, ((3, True),), ((2, 4),)),
+    # the other two tiles at one k-tile
+    (200, 384, 32, 11, 0, {2: 0}, BOTH_EPILOGUES, ()),
+    (250, 384, 32, 1, 2, {2: 0}, BOTH_EPILOGUES, ()),
+]
+
+
+@pytest.mark.parametrize("M,N,K,n_cu,tile,schedules,epilogues,same", PLANE_PROLOGUE_CASES,
+                         ids=[f"{c[0]}x{c[1]}x{c[2]}-cu{c[3]}" for c in PLANE_PROLOGUE_CASES])
+def test_plane_gemm_prologue_edges(pkg, eng, M, N, K, n_cu, tile, schedules, epilogues, same):
+    """The k-loops of the plane GEMM's tile kernels at their shortest: one, two and three k-tiles (the ping-pong kernels
+    issue their second k-tile only when there is one, and stop issuing two turns before the end), the persistent kernel at
+    the launcher's minimum of four, and ragged last row tiles.  The fused-LayerNorm instantiations have these K in
+    tests/test_gpu_gemm_ln_fused.py; these are the plain ones.  The plan is asserted first, so that a change of the plan
+    cannot quietly turn this into a test of other kernels.  Every schedule of one MFMA shape gives the same bits, and
+    each is inside the fp64 bar of test_plane_gemm_plain_and_plane_output."""
+    rng = np.random.default_rng(M * 7 + N + K)
+    A = rng.standard_normal((M, K)).astype(np.float32)
+    W = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
+    bias = rng.standard_normal(N).astype(np.float32)
+    ref = A.astype(np.float64) @ W.astype(np.float64).T + bias
+    L = pkg.lib()
+    try:
+        for epi, planes_out in epilogues:
+            want, bar = (gelu(ref), 4e-6) if epi & 2 else (ref, 2e-6)
+            outs = {}
+            for mode, schedule in schedules.items():
+                assert L.wt_dbg_set_plane_gemm_mode(mode) == 0
+                plan = pkg.plane_gemm_plan(M, N, K, epi, planes_out, False, n_cu)
+                assert (plan.tile, plan.schedule, plan.fused) == (tile, schedule, False), (mode, epi, plan.kernel)
+                outs[mode] = eng.dbg_gemm_planes(A, W, bias, epi=epi, planes_out=planes_out, n_cu=n_cu)
+                err = rel_err(outs[mode], want)
+                print(f"mode {mode} epi {epi} {plan.kernel}: rel_err {err:.3g}")
+                assert err < bar, (mode, epi, plan.kernel)
+            for a, b in same:
+                assert np.array_equal(outs[a], outs[b]), (a, b, epi)
+    finally:
+        assert L.wt_dbg_set_plane_gemm_mode(2) == 0
+
+
 @pytest.mark.parametrize("B,H,T,chunks,nq", [(1, 6, 1500, 8, 1), (3, 6, 333, 4, 2), (2, 2, 100, 2, 4), (2, 8, 200, 3, 2),
                                               (1, 6, 64, 2, 1), (2, 6, 1500, 16, 4), (5, 6, 97, 1, 1)])
 def test_cross_attention_absorbed(eng, B, H, T, chunks, nq):

@@ -263,4 +263,12 @@ __device__ __forceinline__ void lds_dma16_sgpr(unsigned voff, unsigned long long
 }
 #pragma clang diagnostic pop
 
+// XCD-aware bijective remap of a 1-D grid of nb blocks (speed only): the hardware deals blocks to the 8 XCDs round robin,
+// so blocks with equal bid % 8 share an XCD and its L2.  Block bid works on logical block xcd_logical_block(nb, bid):
+// XCD x gets the logical blocks of one contiguous range (q8 or q8 + 1 of them), whose neighbours share operands.
+__device__ __forceinline__ int xcd_logical_block(int nb, int bid) {
+  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+
 }  // namespace wt

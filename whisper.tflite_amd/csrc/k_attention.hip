@@ -44,9 +44,7 @@ __global__ __launch_bounds__(256) void encoder_attention_f32(const float* __rest
   const int q_blocks = (T + AQ - 1) / AQ;
   // consecutive blocks on one XCD (blockIdx % 8 equal) walk the q-blocks of one
   // (clip, head), so its K/V stay in that XCD's L2
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int logical = xcd_logical_block(gridDim.x, blockIdx.x);
   const int bh = logical / q_blocks, qb = logical % q_blocks;
   const int b = bh / heads, h = bh % heads;
 
@@ -244,9 +242,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void encoder_attention_sp
 
   const int d_model = heads * 64, ld = 3 * d_model;
   const int q_blocks = (T + AQS - 1) / AQS;
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int logical = xcd_logical_block(gridDim.x, blockIdx.x);
   const int bh = logical / q_blocks, qb = logical % q_blocks;
   const int b = bh / heads, h = bh % heads;
 

@@ -71,9 +71,7 @@ __global__ __launch_bounds__(256, BF ? 4 : 3) void encoder_attention_planes(cons
 
   const int d_model = heads * 64, ld = 3 * d_model;
   const int q_blocks = (T + 127) / 128;
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int logical = xcd_logical_block(gridDim.x, blockIdx.x);
   const int bh = logical / q_blocks, qb = logical % q_blocks;
   const int b = bh / heads, h = bh % heads;
 

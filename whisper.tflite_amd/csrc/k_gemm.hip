@@ -147,9 +147,7 @@ __global__ __launch_bounds__(256) void gemm_f32_tile(GemmDev g) {
   float* const Bs = smem + BM * LDS_LD;
 
   // XCD-aware bijective remap: blocks with equal blockIdx % 8 share an XCD (speed only).
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int logical = xcd_logical_block(gridDim.x, blockIdx.x);
   const int n_tiles = g.N / BN;
   const int m0 = (logical / n_tiles) * BM;
   const int n0 = (logical % n_tiles) * BN;
@@ -267,9 +265,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split16_tile(GemmDev g) {
   __shared__ __attribute__((aligned(16))) unsigned char smem_raw[kTileBytes > kStageBytes ? kTileBytes : kStageBytes];
   unsigned short* const lds = reinterpret_cast<unsigned short*>(smem_raw);
 
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int logical = xcd_logical_block(gridDim.x, blockIdx.x);
   const int n_tiles = g.N / BN;
   const int m0 = (logical / n_tiles) * BM;
   const int n0 = (logical % n_tiles) * BN;

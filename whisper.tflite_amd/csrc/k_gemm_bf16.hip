@@ -250,9 +250,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_bf16_planes(Bf16GemmDev g) {
   static_assert(QT % NW == 0, "whole instructions per wavefront");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int logical = xcd_logical_block(gridDim.x, blockIdx.x);
   const int n_tiles = g.N / BN;
   const int m0 = (logical / n_tiles) * BM;
   const int n0 = (logical % n_tiles) * BN;

@@ -19,7 +19,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <type_traits>
 
 #include "bf16_split.h"
 #include "kernels.h"
@@ -88,6 +87,30 @@ struct PlaneGemmDev {
 // 3's (r >> 2) & 3 served the first pattern only.
 __host__ __device__ __forceinline__ constexpr int chunk_swizzle(int row) { return (0 - (row >> 2)) & 3; }
 
+// ---- constants of a block tile BM x BN x BK: 2 x WN wavefronts, each owning MI x NI blocks of 32 x 32 outputs.  The tile
+// kernels, their epilogue and their launcher all take them from here.
+template <int WN_, int NI_, int MI_>
+struct PlaneTile {
+  static constexpr int WN = WN_, NI = NI_, MI = MI_;
+  static constexpr int BN = WN * NI * 32, NW = 2 * WN, BM = 64 * MI;
+  static constexpr int kAPlane = BM * BK * 2, kWPlane = BN * BK * 2;  // bytes of one plane of a stage
+  static constexpr int kStage = 2 * kAPlane + 2 * kWPlane;
+  static constexpr int QA = BM / 16, QW = BN / 16;                   // LDS-DMA instructions per A / W plane (16 rows each)
+  static constexpr int QT = 2 * QA + 2 * QW, QPW = QT / NW;          // per stage, per wavefront
+  static_assert(QT % NW == 0, "whole instructions per wavefront");
+};
+
+// a wavefront's place in its block: row wm (the ping-pong kernels' group) and column wn of the 2 x WN wavefronts
+struct WavePos {
+  int lane, wid, wm, wn;
+};
+template <class T>
+__device__ __forceinline__ WavePos wave_pos() {
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  return {lane, wid, wid / T::WN, wid % T::WN};
+}
+
 // ---- LDS-DMA source addresses of a stage, shared by the tile kernels.  Instruction q of a stage copies 16 rows x 64 B
 // (one plane of a 32-deep k-tile): q in [0, QA) A hi, [QA, 2 QA) A lo, [2 QA, 2 QA + QW) W hi, then W lo; its LDS
 // destination is the stage base + q * 1024 (lane-linear).  Wave w issues q = w, w + NW, ...  Lane i fills LDS slot
@@ -100,32 +123,66 @@ __host__ __device__ __forceinline__ constexpr int chunk_swizzle(int row) { retur
 //   KiBs (36 against 50 GB/s per CU), and the 9 issues of a wave 1070 against 480 cycles; W is two thirds of a stage.
 // Addresses are (uniform base) + (32-bit per-lane byte offset): the LDS-DMA takes its base from SGPRs that SALU
 // instructions advance per k-tile (by kstep[j] bytes), and its issue needs NO vector instruction.
-template <int QA, int QW, int NW, int QPW>
-__device__ __forceinline__ void setup_stage_dma(const PlaneGemmDev& g, int m0, int n0, int wid, int lane, unsigned (&voff)[QPW],
-                                                const unsigned char* (&ubase)[QPW], unsigned (&kstep)[QPW]) {
-  const int srow = lane >> 2;
-  const int nkt = g.K / BK;
+// StageDma is a wavefront's share of that: built for the tile of block bid of nb (in the persistent kernel: of a virtual
+// block of all tiles, and set_tile() moves it on to the next), issue() copies k-tile kt into stage buf.
+template <class T>
+struct StageDma {
+  unsigned voff[T::QPW], kstep[T::QPW];
+  const unsigned char* ubase[T::QPW];
+  unsigned lds_base;  // LDS address of stage 0
+  int wid;
+  int n_tiles;        // column tiles of the problem
+  int m0, n0;         // origin of the tile
+
+  // set up for the tile of block bid of nb
+  __device__ __forceinline__ StageDma(const PlaneGemmDev& g, const unsigned char* smem, int wid_, int nb, int bid, int lane)
+      : lds_base((unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)smem), wid(wid_) {
+    const int logical = xcd_logical_block(nb, bid);
+    n_tiles = g.N / T::BN;
+    place(g, logical, lane);
+  }
+  // move on to another tile (persistent kernel)
+  __device__ __forceinline__ void set_tile(const PlaneGemmDev& g, int nb, int bid, int lane) { place(g, xcd_logical_block(nb, bid), lane); }
+
+  __device__ __forceinline__ void place(const PlaneGemmDev& g, int logical, int lane) {
+    m0 = (logical / n_tiles) * T::BM;
+    n0 = (logical % n_tiles) * T::BN;
+    constexpr int QA = T::QA, QW = T::QW;
+    const int srow = lane >> 2;
+    const int nkt = g.K / BK;
 #pragma unroll
-  for (int j = 0; j < QPW; ++j) {
-    const int q = wid + NW * j;
-    if (q < 2 * QA) {
-      const bool lo = q >= QA;
-      const int row = 16 * (lo ? q - QA : q) + srow;
-      const int chunk = (lane & 3) ^ chunk_swizzle(row);
-      int m = m0 + row;
-      m = m < g.M ? m : g.M - 1;  // clamp: rows past M are computed and discarded
-      voff[j] = (unsigned)(2 * ((lo ? g.a_plane : 0) + (long)(m / g.a_rpb) * g.a_bs + (long)(m % g.a_rpb) * g.lda + chunk * 8));
-      ubase[j] = reinterpret_cast<const unsigned char*>(g.A);
-      kstep[j] = BK * 2;
-    } else {
-      const int wq = q - 2 * QA;
-      const int rg = wq % QW, plane = wq / QW;
-      voff[j] = (unsigned)(lane * 16);
-      ubase[j] = reinterpret_cast<const unsigned char*>(g.W) + ((size_t)(n0 / 16 + rg) * nkt * 2 + plane) * 1024;
-      kstep[j] = 2048;
+    for (int j = 0; j < T::QPW; ++j) {
+      const int q = wid + T::NW * j;
+      if (q < 2 * QA) {
+        const bool lo = q >= QA;
+        const int row = 16 * (lo ? q - QA : q) + srow;
+        const int chunk = (lane & 3) ^ chunk_swizzle(row);
+        int m = m0 + row;
+        m = m < g.M ? m : g.M - 1;  // clamp: rows past M are computed and discarded
+        voff[j] = (unsigned)(2 * ((lo ? g.a_plane : 0) + (long)(m / g.a_rpb) * g.a_bs + (long)(m % g.a_rpb) * g.lda + chunk * 8));
+        ubase[j] = reinterpret_cast<const unsigned char*>(g.A);
+        kstep[j] = BK * 2;
+      } else {
+        const int wq = q - 2 * QA;
+        const int rg = wq % QW, plane = wq / QW;
+        voff[j] = (unsigned)(lane * 16);
+        ubase[j] = reinterpret_cast<const unsigned char*>(g.W) + ((size_t)(n0 / 16 + rg) * nkt * 2 + plane) * 1024;
+        kstep[j] = 2048;
+      }
     }
   }
-}
+
+  __device__ __forceinline__ void issue(int kt, int buf) const {
+#pragma unroll
+    for (int j = 0; j < T::QPW; ++j) {
+      // global_load_lds_dwordx4 in its SGPR-base form, written out: the builtin only selects the 64-bit per-lane address
+      // form (a v_lshl_add_u64 in front of every issue, even with the base held in SGPRs)
+      const unsigned long long sb = reinterpret_cast<unsigned long long>(ubase[j]) + (size_t)kt * kstep[j];
+      const unsigned dst = lds_base + (unsigned)(buf * T::kStage + (wid + T::NW * j) * 1024);
+      lds_dma16_sgpr(voff[j], sb, dst);
+    }
+  }
+};
 
 // ---- accumulators of a wave tile as the epilogue sees them: MI x NI blocks of 32 x 32 outputs, 16 floats per lane and
 // block.  stage_write() puts a block into the wave's private LDS stage (32 rows x 32 floats, columns XORed by 20 — bits 2
@@ -195,8 +252,8 @@ struct ActiveEpilogueHook {
 template <int EPI, bool PLANES_OUT, int WN, bool LN, class Acc, class Hook = NoEpilogueHook>
 __device__ __forceinline__ void planes_epilogue(const PlaneGemmDev& g, Acc& acc, unsigned char* smem, int m0, int n0, int wid, int wm,
                                                 int wn, int lane, Hook hook = Hook{}) {
-  constexpr int MI = Acc::MI, NI = Acc::NI;
-  constexpr int BN = WN * NI * 32, NW = 2 * WN, BM = 64 * MI;
+  using T = PlaneTile<WN, Acc::NI, Acc::MI>;
+  constexpr int MI = T::MI, NI = T::NI, BN = T::BN, NW = T::NW, BM = T::BM;
   __syncthreads();  // the operand stages are dead: the epilogue reuses them
 
   // ---- epilogue: each wavefront transposes one 32 x 32 MFMA tile at a time through a private LDS stage and moves
@@ -384,7 +441,213 @@ __device__ __forceinline__ void planes_epilogue(const PlaneGemmDev& g, Acc& acc,
   }
 }
 
-// Block tile 192 x BN with BN = WN * NI * 32: 2 x WN wavefronts, each owning 3 x NI MFMA tiles.
+// ---- fragments of a wave tile, one type per MFMA shape: where the lane's 16-byte pieces of a stage are, the registers
+// they are read into, and the three plane products of them — smallest first (hi.lo, lo.hi, hi.hi), the one place the
+// product order is written per shape.  `stage` is the LDS address of the stage a k-tile lives in.  load_first /
+// load_second / compute<H> are what the ping-pong loop (pingpong_k_loop below) puts into its two L and two C phases.
+template <class T>
+struct Frag32 {  // v_mfma_f32_32x32x16_f16: one load and MI x NI x 3 MFMAs per 16-deep k-step, two k-steps per k-tile
+  static constexpr int MI = T::MI, NI = T::NI;
+  half8 ah[MI], al[MI], bh[NI], bl[NI];
+  int a_off, b_off, lh, swz;
+
+  // fragment addresses: row = tile base (a multiple of 32) + l31, so the swizzle term depends on the lane only
+  __device__ __forceinline__ Frag32(int wm, int wn, int lane) {
+    const int l31 = lane & 31;
+    lh = lane >> 5, swz = chunk_swizzle(l31);
+    a_off = (wm * (32 * MI) + l31) * 64, b_off = 2 * T::kAPlane + (wn * NI * 32 + l31) * 64;
+  }
+  __device__ __forceinline__ void load(const unsigned char* stage, int ks) {
+    const int slot = ((ks * 2 + lh) ^ swz) * 16;
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      ah[i] = *reinterpret_cast<const half8*>(stage + a_off + i * 32 * 64 + slot);
+      al[i] = *reinterpret_cast<const half8*>(stage + T::kAPlane + a_off + i * 32 * 64 + slot);
+    }
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      bh[j] = *reinterpret_cast<const half8*>(stage + b_off + j * 32 * 64 + slot);
+      bl[j] = *reinterpret_cast<const half8*>(stage + T::kWPlane + b_off + j * 32 * 64 + slot);
+    }
+  }
+  template <int H = 0>  // (both k-steps fill the whole accumulator)
+  __device__ __forceinline__ void compute(Acc32<MI, NI>& acc) const {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < NI; ++j) acc.t[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc.t[i][j], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < NI; ++j) acc.t[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc.t[i][j], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < NI; ++j) acc.t[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc.t[i][j], 0, 0, 0);
+  }
+  __device__ __forceinline__ void load_first(const unsigned char* stage) { load(stage, 0); }
+  __device__ __forceinline__ void load_second(const unsigned char* stage) { load(stage, 1); }
+};
+
+// v_mfma_f32_16x16x32_f16: a fragment is (row l & 15, chunk l >> 4) — one ds_read_b128 covers a whole 16-row x 64-byte
+// block, and chunk_swizzle() keeps its 16-lane service groups on distinct banks.  A k-tile is two half-tiles of rows:
+// the W fragments are read once and kept for both, the A fragments of a half's MI 16-row blocks replace the other half's.
+template <class T>
+struct Frag16 {
+  static constexpr int MI = T::MI, NI = T::NI;
+  half8 ah[MI], al[MI], bh[2 * NI], bl[2 * NI];
+  int a_off, b_off;
+
+  __device__ __forceinline__ Frag16(int wm, int wn, int lane) {
+    const int fc = lane & 15, fq = lane >> 4;
+    const int frag = fc * 64 + ((fq ^ chunk_swizzle(fc)) * 16);  // byte offset of the lane's 16 bytes inside a 16-row block
+    a_off = wm * (32 * MI) * 64 + frag, b_off = 2 * T::kAPlane + wn * (NI * 32) * 64 + frag;
+  }
+  __device__ __forceinline__ void load_b(const unsigned char* stage) {
+    const unsigned char* base = stage + b_off;
+#pragma unroll
+    for (int j = 0; j < 2 * NI; ++j) {
+      bh[j] = *reinterpret_cast<const half8*>(base + j * 1024);
+      bl[j] = *reinterpret_cast<const half8*>(base + T::kWPlane + j * 1024);
+    }
+  }
+  __device__ __forceinline__ void load_a(const unsigned char* stage, int half) {
+    const unsigned char* base = stage + a_off + half * MI * 1024;
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      ah[i] = *reinterpret_cast<const half8*>(base + i * 1024);
+      al[i] = *reinterpret_cast<const half8*>(base + T::kAPlane + i * 1024);
+    }
+  }
+  template <int H>  // the half-tile of rows the A fragments belong to
+  __device__ __forceinline__ void compute(Acc16<MI, NI>& acc) const {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < 2 * NI; ++j) acc.t[MI * H + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc.t[MI * H + i][j], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < 2 * NI; ++j) acc.t[MI * H + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc.t[MI * H + i][j], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < 2 * NI; ++j) acc.t[MI * H + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc.t[MI * H + i][j], 0, 0, 0);
+  }
+  __device__ __forceinline__ void load_first(const unsigned char* stage) {
+    load_b(stage);
+    load_a(stage, 0);
+  }
+  __device__ __forceinline__ void load_second(const unsigned char* stage) { load_a(stage, 1); }
+};
+
+// a phase boundary of the ping-pong kernels: nothing (the register-only MFMAs included) is scheduled across it
+__device__ __forceinline__ void phase_end() {
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void reads_done() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+__device__ __forceinline__ void dma_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+template <int N>  // all but the wave's N youngest vector-memory operations have landed
+__device__ __forceinline__ void dma_done_but() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// Diagnostic build (WT_PP_STAMPS, tools/gemm_phase_probe.hip): where a wavefront's cycles of the ping-pong kernels go.
+// Without the macro every member is empty and leaves no instruction behind.
+#ifdef WT_PP_STAMPS
+__device__ long long g_pp_stamps[1024 * 8 * 9];  // per wave: 4 phase sums, loop, prologue, epilogue, kernel, realtime ticks
+#endif
+struct PpStamps {
+#ifdef WT_PP_STAMPS
+  long long st[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  long long t_kernel, r_kernel, tl, t_begin, t_loop_end;
+  __device__ __forceinline__ PpStamps() : t_kernel(__builtin_readcyclecounter()), r_kernel((long long)__builtin_amdgcn_s_memrealtime()) {}
+  __device__ __forceinline__ void loop_begin() {
+    tl = __builtin_readcyclecounter();
+    t_begin = tl;
+    st[5] = tl - t_kernel;
+  }
+  __device__ __forceinline__ void phase(int i) {
+    const long long t = __builtin_readcyclecounter();
+    st[i] += t - tl;
+    tl = t;
+  }
+  __device__ __forceinline__ void loop_end() {
+    t_loop_end = __builtin_readcyclecounter();
+    st[4] = t_loop_end - t_begin;
+  }
+  __device__ __forceinline__ void store(int lane, int wid) {  // behind the epilogue
+    const long long t_end = __builtin_readcyclecounter();
+    st[6] = t_end - t_loop_end;
+    st[7] = t_end - t_kernel;
+    st[8] = (long long)__builtin_amdgcn_s_memrealtime() - r_kernel;
+    if (lane == 0 && blockIdx.x < 1024)
+      for (int i = 0; i < 9; ++i) g_pp_stamps[(blockIdx.x * 8 + wid) * 9 + i] = st[i];
+  }
+#else
+  __device__ __forceinline__ void loop_begin() {}
+  __device__ __forceinline__ void phase(int) {}
+  __device__ __forceinline__ void loop_end() {}
+  __device__ __forceinline__ void store(int, int) {}
+#endif
+};
+
+// ---- the k-loop of the ping-pong kernels.  Same tile, same staging image, same k order and product order as
+// gemm_planes_tile, another schedule: the block's eight wavefronts are two GROUPS of four — waves w and w + 4 share a
+// SIMD, wm is the group — that run the same program ONE PHASE apart.  A phase is either L, "read fragments (and issue the
+// wave's share of an LDS-DMA)", or C, "MFMAs only"; a raw s_barrier closes every phase, so while one wavefront of a SIMD
+// streams its MFMAs the other one does its LDS reads and DMA issues.  In gemm_planes_tile both wavefronts of a SIMD do
+// the same thing at the same time: the matrix pipe idles while both issue DMA (60-180 cycles per instruction, 9-10 per
+// wave and k-tile) and fragment reads, then both contend for it (profiles/r03_gemm_mainloop_ablation.txt: DMA + MFMA
+// cost nearly their sum).  A k-tile is four phases; L1(kt) is the fragment type's load_first, L2(kt) its load_second:
+//   phase p:     G0  L1(0) C0(0) L2(0) C1(0) L1(1) ...       Frag32: L1 / L2 = the two 16-deep k-steps (12 reads each),
+//                G1        L1(0) C0(0) L2(0) C1(0) ...                C0 / C1 = the 27 MFMAs of each
+//                                                            Frag16: L1 = 12 reads of W + 6 of A, L2 = 6 of A, C = 54 MFMAs
+// L1(kt), kt >= 1, also issues the LDS-DMA of k-tile kt + 1 (the caller's prologue issues k-tiles 0 and 1).  This function
+// runs C0(0) ... C1(nkt - 1) and the (empty) last L1 — the prologue has done L1(0), G1 one barrier behind G0 — and then
+// lets G0 sit out G1's last phase.  Every wave passes one barrier per phase whatever the branches inside a phase do:
+// 4 nkt here, plus the one extra that G1 takes in the prologue and G0 behind the loop.  Two groups that disagree on
+// the number of barriers hang the CU.
+// Stage lifetimes: k-tile kt lives in stage (kt + P) & 1 and is read in L1(kt) and L2(kt); its last reader is G1's L2(kt)
+// in phase 4 kt + 3, so k-tile kt + 2 is issued into it from phase 4 kt + 4 on: by every wave in its own L1(kt + 1).  It
+// is first read by G0's L1(kt + 2) in phase 4 kt + 8: G0 waves certify their DMA (vmcnt(0)) at the end of C1(kt + 1), G1
+// waves at the end of L2(kt + 1), both phase 4 kt + 7.
+template <int P>
+constexpr int stage_of(int kt) {
+  return (kt + P) & 1;
+}
+template <int P, class T, class Frag, class Acc>
+__device__ __forceinline__ void pingpong_k_loop(const unsigned char* smem, const StageDma<T>& dma, Frag& f, Acc& acc, int nkt, int wm,
+                                                PpStamps& st) {
+  st.loop_begin();
+  for (int kt = 0; kt < nkt; ++kt) {
+    f.template compute<0>(acc);  // C0(kt)
+    phase_end();
+    st.phase(0);
+    f.load_second(smem + stage_of<P>(kt) * T::kStage);  // L2(kt)
+    reads_done();
+    if (wm == 1) dma_done();
+    phase_end();
+    st.phase(1);
+    f.template compute<1>(acc);  // C1(kt)
+    if (wm == 0) dma_done();
+    phase_end();
+    st.phase(2);
+    if (kt + 1 < nkt) {  // L1(kt + 1)
+      if (kt + 2 < nkt) dma.issue(kt + 2, stage_of<P>(kt + 2));
+      f.load_first(smem + stage_of<P>(kt + 1) * T::kStage);
+      reads_done();
+    }
+    phase_end();
+    st.phase(3);
+  }
+  if (wm == 0) phase_end();
+  st.loop_end();
+}
+
+// Block tile (64 MI) x BN with BN = WN * NI * 32: 2 x WN wavefronts, each owning MI x NI MFMA tiles.
 //   WN 2, NI 2: 192 x 128, 4 wavefronts, 40 KB per stage, two blocks per CU (round 2's first shape);
 //   WN 4, NI 3: 192 x 384, 8 wavefronts, 72 KB per stage, one block per CU.  What bounds this kernel is the LDS-DMA
 //   round trip (one k-tile of prefetch distance, ~2 us under load) against the bytes a CU can hold in flight (LDS):
@@ -394,427 +657,105 @@ __device__ __forceinline__ void planes_epilogue(const PlaneGemmDev& g, Acc& acc,
 //   MI = 32-row MFMA tiles per wavefront (two wavefront rows): 3 -> 192 block rows; 4 -> 256 rows x 384 columns, the
 //   whole register file (255 VGPRs) and all 160 KB of LDS, 230 FLOP per staged byte — used where 188 row tiles fill the
 //   available CUs in fewer rounds than 250 (the CU-masked stream of the pipeline on the N = d_model shapes).
+// Both wavefronts of a SIMD in step: one barrier per k-tile, the LDS-DMA of k-tile kt + 1 in flight during the MFMAs of kt.
 template <int EPI, bool PLANES_OUT, int WN, int NI, int MI, bool LN = false>
 __global__ __launch_bounds__(128 * WN, WN == 2 ? 2 : 2) void gemm_planes_tile(PlaneGemmDev g) {
   static_assert(!LN || (!PLANES_OUT && WN == 4 && NI == 3), "LayerNorm fusion: fp32 output, 384-column tile");
-  constexpr int BN = WN * NI * 32, NW = 2 * WN, BM = 64 * MI;
-  constexpr int kAPlane = BM * BK * 2, kWPlane = BN * BK * 2;  // bytes of one plane of a stage
-  constexpr int kStage = 2 * kAPlane + 2 * kWPlane;
-  constexpr int QA = BM / 16, QW = BN / 16;                   // LDS-DMA instructions per A / W plane (16 rows each)
-  constexpr int QT = 2 * QA + 2 * QW, QPW = QT / NW;          // per stage, per wavefront
-  static_assert(QT % NW == 0, "whole instructions per wavefront");
+  using T = PlaneTile<WN, NI, MI>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
-  // XCD-aware bijective remap: blocks with equal blockIdx % 8 share an XCD (speed only).
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int n_tiles = g.N / BN;
-  const int m0 = (logical / n_tiles) * BM;
-  const int n0 = (logical % n_tiles) * BN;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid / WN, wn = wid % WN;
-  const int l31 = lane & 31, lh = lane >> 5;
-
-  unsigned voff[QPW], kstep[QPW];
-  const unsigned char* ubase[QPW];
-  const unsigned lds_base = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)smem;
-  setup_stage_dma<QA, QW, NW, QPW>(g, m0, n0, wid, lane, voff, ubase, kstep);
-  auto issue_stage = [&](int kt, int buf) {
-#pragma unroll
-    for (int j = 0; j < QPW; ++j) {
-      // global_load_lds_dwordx4 in its SGPR-base form, written out: the builtin only selects the 64-bit per-lane address
-      // form (a v_lshl_add_u64 in front of every issue, even with the base held in SGPRs)
-      const unsigned long long sb = reinterpret_cast<unsigned long long>(ubase[j]) + (size_t)kt * kstep[j];
-      const unsigned dst = lds_base + (unsigned)(buf * kStage + (wid + NW * j) * 1024);
-      lds_dma16_sgpr(voff[j], sb, dst);
-    }
-  };
-
-  Acc32<MI, NI> accs;
-  accs.zero();
-  auto& acc = accs.t;
-
-  // fragment addresses: row = tile base (a multiple of 32) + l31, so the swizzle term depends on the lane only
-  const int swz = chunk_swizzle(l31);
-  const int a_off = (wm * (32 * MI) + l31) * 64, b_off = 2 * kAPlane + (wn * NI * 32 + l31) * 64;
-  auto compute = [&](int buf) {
-    const unsigned char* base = smem + buf * kStage;
-#pragma unroll
-    for (int ks = 0; ks < BK / 16; ++ks) {
-      const int slot = ((ks * 2 + lh) ^ swz) * 16;
-      half8 ah[MI], al[MI], bh[NI], bl[NI];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        ah[i] = *reinterpret_cast<const half8*>(base + a_off + i * 32 * 64 + slot);
-        al[i] = *reinterpret_cast<const half8*>(base + kAPlane + a_off + i * 32 * 64 + slot);
-      }
-#pragma unroll
-      for (int j = 0; j < NI; ++j) {
-        bh[j] = *reinterpret_cast<const half8*>(base + b_off + j * 32 * 64 + slot);
-        bl[j] = *reinterpret_cast<const half8*>(base + kWPlane + b_off + j * 32 * 64 + slot);
-      }
-      // smallest products first
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-    }
-  };
+  const WavePos w = wave_pos<T>();
+  StageDma<T> dma(g, smem, w.wid, gridDim.x, blockIdx.x, w.lane);
+  Acc32<MI, NI> acc;
+  acc.zero();
+  Frag32<T> f(w.wm, w.wn, w.lane);
 
   const int nkt = g.K / BK;
-  issue_stage(0, 0);
+  dma.issue(0, 0);
   for (int kt = 0; kt < nkt; ++kt) {
     // k-tile kt has landed: every wave waits for its own LDS-DMA, the barrier for everybody else's; k-tile kt - 1 has
     // been read by everyone, so its stage may be refilled
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    dma_done();
     __builtin_amdgcn_s_barrier();
-    if (kt + 1 < nkt) issue_stage(kt + 1, (kt + 1) & 1);
-    compute(kt & 1);
+    if (kt + 1 < nkt) dma.issue(kt + 1, (kt + 1) & 1);
+    const unsigned char* stage = smem + (kt & 1) * T::kStage;
+#pragma unroll
+    for (int ks = 0; ks < BK / 16; ++ks) {
+      f.load(stage, ks);
+      f.compute(acc);
+    }
   }
-  planes_epilogue<EPI, PLANES_OUT, WN, LN>(g, accs, smem, m0, n0, wid, wm, wn, lane);
+  planes_epilogue<EPI, PLANES_OUT, WN, LN>(g, acc, smem, dma.m0, dma.n0, w.wid, w.wm, w.wn, w.lane);
 }
 
-// Ping-pong form of the 384-column tiles (round 4).  Same tile, same staging image, same k order and product order
-// (bit-identical results), another schedule: the block's eight wavefronts are two GROUPS of four — waves w and w + 4
-// share a SIMD — that run the same program ONE PHASE apart.  A phase is either "read the fragments of a 16-deep k-step
-// (12 ds_read_b128) and issue the wave's share of the next-but-one k-tile's LDS-DMA" or "27 MFMAs"; a raw s_barrier
-// closes every phase, so while one wavefront of a SIMD streams its MFMAs the other one does its LDS reads and DMA
-// issues.  In gemm_planes_tile both wavefronts of a SIMD did the same thing at the same time: the matrix pipe idled
-// while both issued DMA (60-180 cycles per instruction, 9-10 per wave and k-tile) and fragment reads, then both
-// contended for it (profiles/r03_gemm_mainloop_ablation.txt: DMA + MFMA cost nearly their sum).
-//   phase p:     G0  L(0) C(0) L(1) C(1) L(2) ...        L(s) = fragment reads of k-step s (+ DMA issue on even s)
-//                G1       L(0) C(0) L(1) C(1) ...        C(s) = the 27 MFMAs of k-step s
-// Stage kt & 1 is read in L(2 kt) and L(2 kt + 1); its last reader is G1's L(2 kt + 1) in phase 4 kt + 3, so k-tile
-// kt + 2 is issued into it from phase 4 kt + 4 on: by every wave in its own L(2 kt + 2).  It is first read by G0's
-// L(2 kt + 4) in phase 4 kt + 8: G0 waves certify their DMA (vmcnt(0)) at the end of C(2 kt + 3), G1 waves at the end of
-// L(2 kt + 3), both phase 4 kt + 7.
-#ifdef WT_PP_STAMPS  // diagnostic build (tools/gemm_phase_probe.hip): where a wavefront's cycles of the main loop go
-__device__ long long g_pp_stamps[1024 * 8 * 9];  // per wave: 4 phase sums, loop, prologue, epilogue, kernel, realtime ticks
-#define PP_STAMP(i)                                  \
-  do {                                               \
-    const long long t_ = __builtin_readcyclecounter(); \
-    st_[i] += t_ - tl_;                              \
-    tl_ = t_;                                        \
-  } while (0)
-#else
-#define PP_STAMP(i) \
-  do {              \
-  } while (0)
-#endif
-
+// Ping-pong form of the 384-column tiles (round 4) on the 32 x 32 x 16 MFMAs: pingpong_k_loop over Frag32, bit-identical
+// to gemm_planes_tile.
 template <int EPI, bool PLANES_OUT, int MI, bool LN = false>
 __global__ __launch_bounds__(512, 2) void gemm_planes_pp(PlaneGemmDev g) {
-  constexpr int WN = 4, NI = 3;
   static_assert(!LN || !PLANES_OUT, "LayerNorm fusion: fp32 output");
-  constexpr int BN = WN * NI * 32, NW = 2 * WN, BM = 64 * MI;
-  constexpr int kAPlane = BM * BK * 2, kWPlane = BN * BK * 2;
-  constexpr int kStage = 2 * kAPlane + 2 * kWPlane;
-  constexpr int QA = BM / 16, QW = BN / 16;
-  constexpr int QT = 2 * QA + 2 * QW, QPW = QT / NW;
-  static_assert(QT % NW == 0, "whole instructions per wavefront");
-#ifdef WT_PP_STAMPS
-  const long long t_kernel_ = __builtin_readcyclecounter();
-  const long long r_kernel_ = (long long)__builtin_amdgcn_s_memrealtime();
-#endif
+  using T = PlaneTile<4, 3, MI>;
+  PpStamps st;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int n_tiles = g.N / BN;
-  const int m0 = (logical / n_tiles) * BM;
-  const int n0 = (logical % n_tiles) * BN;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid / WN, wn = wid % WN;  // wm = the wave's group
-  const int l31 = lane & 31, lh = lane >> 5;
-
-  unsigned voff[QPW], kstep[QPW];
-  const unsigned char* ubase[QPW];
-  const unsigned lds_base = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)smem;
-  setup_stage_dma<QA, QW, NW, QPW>(g, m0, n0, wid, lane, voff, ubase, kstep);
-  auto issue_stage = [&](int kt, int buf) {
-#pragma unroll
-    for (int j = 0; j < QPW; ++j) {
-      const unsigned long long sb = reinterpret_cast<unsigned long long>(ubase[j]) + (size_t)kt * kstep[j];
-      const unsigned dst = lds_base + (unsigned)(buf * kStage + (wid + NW * j) * 1024);
-      lds_dma16_sgpr(voff[j], sb, dst);
-    }
-  };
-
-  Acc32<MI, NI> accs;
-  accs.zero();
-  auto& acc = accs.t;
-
-  const int swz = chunk_swizzle(l31);
-  const int a_off = (wm * (32 * MI) + l31) * 64, b_off = 2 * kAPlane + (wn * NI * 32 + l31) * 64;
-  half8 ah[MI], al[MI], bh[NI], bl[NI];
-  auto load_frags = [&](int buf, int ks) {
-    const unsigned char* base = smem + buf * kStage;
-    const int slot = ((ks * 2 + lh) ^ swz) * 16;
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      ah[i] = *reinterpret_cast<const half8*>(base + a_off + i * 32 * 64 + slot);
-      al[i] = *reinterpret_cast<const half8*>(base + kAPlane + a_off + i * 32 * 64 + slot);
-    }
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      bh[j] = *reinterpret_cast<const half8*>(base + b_off + j * 32 * 64 + slot);
-      bl[j] = *reinterpret_cast<const half8*>(base + kWPlane + b_off + j * 32 * 64 + slot);
-    }
-  };
-  auto compute = [&]() {  // smallest products first, as gemm_planes_tile
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-  };
-  // a phase boundary: nothing (the register-only MFMAs included) is scheduled across it
-  auto phase_end = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto reads_done = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
-  auto dma_done = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
+  const WavePos w = wave_pos<T>();
+  StageDma<T> dma(g, smem, w.wid, gridDim.x, blockIdx.x, w.lane);
+  Acc32<T::MI, T::NI> acc;
+  acc.zero();
+  Frag32<T> f(w.wm, w.wn, w.lane);
 
   const int nkt = g.K / BK;
-  issue_stage(0, 0);
+  dma.issue(0, 0);
   if (nkt > 1) {
-    issue_stage(1, 1);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(QPW) : "memory");  // k-tile 0 has landed, k-tile 1 stays in flight
+    dma.issue(1, 1);
+    dma_done_but<T::QPW>();  // k-tile 0 has landed, k-tile 1 stays in flight
   } else {
     dma_done();
   }
   phase_end();
-  if (wm == 1) phase_end();  // G1 runs one phase behind
-  load_frags(0, 0);
+  if (w.wm == 1) phase_end();  // G1 runs one phase behind
+  f.load_first(smem);
   reads_done();
   phase_end();
-#ifdef WT_PP_STAMPS
-  long long st_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  long long tl_ = __builtin_readcyclecounter();
-  const long long t_begin_ = tl_;
-  st_[5] = tl_ - t_kernel_;
-#endif
-  for (int kt = 0; kt < nkt; ++kt) {
-    compute();  // C(2 kt)
-    phase_end();
-    PP_STAMP(0);
-    load_frags(kt & 1, 1);  // L(2 kt + 1)
-    reads_done();
-    if (wm == 1) dma_done();
-    phase_end();
-    PP_STAMP(1);
-    compute();  // C(2 kt + 1)
-    if (wm == 0) dma_done();
-    phase_end();
-    PP_STAMP(2);
-    if (kt + 1 < nkt) {  // L(2 kt + 2)
-      if (kt + 2 < nkt) issue_stage(kt + 2, kt & 1);
-      load_frags((kt + 1) & 1, 0);
-      reads_done();
-    }
-    phase_end();
-    PP_STAMP(3);
-  }
-  if (wm == 0) phase_end();
-#ifdef WT_PP_STAMPS
-  const long long t_loop_end_ = __builtin_readcyclecounter();
-  st_[4] = t_loop_end_ - t_begin_;
-#endif
-  planes_epilogue<EPI, PLANES_OUT, WN, LN>(g, accs, smem, m0, n0, wid, wm, wn, lane);
-#ifdef WT_PP_STAMPS
-  {
-    const long long t_end_ = __builtin_readcyclecounter();
-    st_[6] = t_end_ - t_loop_end_;
-    st_[7] = t_end_ - t_kernel_;
-    st_[8] = (long long)__builtin_amdgcn_s_memrealtime() - r_kernel_;
-    if (lane == 0 && blockIdx.x < 1024)
-      for (int i = 0; i < 9; ++i) g_pp_stamps[(blockIdx.x * 8 + wid) * 9 + i] = st_[i];
-  }
-#endif
+  pingpong_k_loop<0>(smem, dma, f, acc, nkt, w.wm, st);
+  planes_epilogue<EPI, PLANES_OUT, T::WN, LN>(g, acc, smem, dma.m0, dma.n0, w.wid, w.wm, w.wn, w.lane);
+  st.store(w.lane, w.wid);
 }
 
-// The same ping-pong schedule on v_mfma_f32_16x16x32_f16 (round 4; tile 192 x 384, wave tile 96 x 96 = 6 x 6 MFMA tiles).
+// The same ping-pong schedule on v_mfma_f32_16x16x32_f16 (round 4; tile 192 x 384, wave tile 96 x 96 = 6 x 6 MFMA tiles):
+// pingpong_k_loop over Frag16.
 // Why another MFMA shape: this kernel is POWER-bound — the chip holds 1.25-1.4 GHz under it (s_memtime over s_memrealtime,
 // tools/gemm_phase_probe.hip) while the loop is within 15 % of its MFMA cycle count — and the 16 x 16 x 32 form does the
 // same arithmetic on less energy: a register-only loop of the three plane products on random planes sustains 1855 TF/s
 // at 1.79 GHz against 1590 TF/s at 1.53 GHz for 32 x 32 x 16 (tools/mfma_shape_probe.hip, profiles/r04_mfma_shape.txt).
 // A k-tile is two half-tiles of 54 MFMAs (864 cycles, as before): rows 0-47 of the wave tile, then rows 48-95.
-//   L_A(kt): 12 reads of the W fragments (kept for both halves) + 6 of the first three A tiles (+ the DMA issue of k-tile
-//   kt + 1's successor);  C_A: 54 MFMAs;  L_B: 6 reads of the other three A tiles;  C_B: 54 MFMAs.  Stage lifetimes and
-//   the vmcnt certification are those of gemm_planes_pp with L_A / L_B in the place of L(2 kt) / L(2 kt + 1).
-// A 16 x 16 x 32 fragment is (row l & 15, chunk l >> 4): one ds_read_b128 covers a whole 16-row x 64-byte block, and
-// chunk_swizzle() keeps its 16-lane service groups on distinct banks.  A 32-deep sum per MFMA instead of 16: results
-// differ from the 32 x 32 x 16 kernels in the last bits (both within the fp32 error budget of tests/test_gpu_kernels.py).
+// A 32-deep sum per MFMA instead of 16: results differ from the 32 x 32 x 16 kernels in the last bits (both within the
+// fp32 error budget of tests/test_gpu_kernels.py).
 template <int EPI, bool PLANES_OUT, bool LN = false>
 __global__ __launch_bounds__(512, 2) void gemm_planes_pp16(PlaneGemmDev g) {
-  constexpr int WN = 4, NI = 3, MI = 3;
   static_assert(!LN || !PLANES_OUT, "LayerNorm fusion: fp32 output");
-  constexpr int BN = WN * NI * 32, NW = 2 * WN, BM = 64 * MI;
-  constexpr int kAPlane = BM * BK * 2, kWPlane = BN * BK * 2;
-  constexpr int kStage = 2 * kAPlane + 2 * kWPlane;
-  constexpr int QA = BM / 16, QW = BN / 16;
-  constexpr int QT = 2 * QA + 2 * QW, QPW = QT / NW;
-  static_assert(QT % NW == 0, "whole instructions per wavefront");
-#ifdef WT_PP_STAMPS
-  const long long t_kernel_ = __builtin_readcyclecounter();
-  const long long r_kernel_ = (long long)__builtin_amdgcn_s_memrealtime();
-#endif
+  using T = PlaneTile<4, 3, 3>;
+  PpStamps st;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int n_tiles = g.N / BN;
-  const int m0 = (logical / n_tiles) * BM;
-  const int n0 = (logical % n_tiles) * BN;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid / WN, wn = wid % WN;  // wm = the wave's group
-
-  unsigned voff[QPW], kstep[QPW];
-  const unsigned char* ubase[QPW];
-  const unsigned lds_base = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)smem;
-  setup_stage_dma<QA, QW, NW, QPW>(g, m0, n0, wid, lane, voff, ubase, kstep);
-  auto issue_stage = [&](int kt, int buf) {
-#pragma unroll
-    for (int j = 0; j < QPW; ++j) {
-      const unsigned long long sb = reinterpret_cast<unsigned long long>(ubase[j]) + (size_t)kt * kstep[j];
-      const unsigned dst = lds_base + (unsigned)(buf * kStage + (wid + NW * j) * 1024);
-      lds_dma16_sgpr(voff[j], sb, dst);
-    }
-  };
-
-  Acc16<MI, NI> accs;
-  accs.zero();
-  auto& acc = accs.t;
-
-  const int fc = lane & 15, fq = lane >> 4;
-  const int frag = fc * 64 + ((fq ^ chunk_swizzle(fc)) * 16);  // byte offset of the lane's 16 bytes inside a 16-row block
-  const int a_off = wm * (32 * MI) * 64 + frag, b_off = 2 * kAPlane + wn * (NI * 32) * 64 + frag;
-  half8 ah[3], al[3], bh[6], bl[6];
-  auto load_b = [&](int buf) {
-    const unsigned char* base = smem + buf * kStage + b_off;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      bh[j] = *reinterpret_cast<const half8*>(base + j * 1024);
-      bl[j] = *reinterpret_cast<const half8*>(base + kWPlane + j * 1024);
-    }
-  };
-  auto load_a = [&](int buf, int half) {
-    const unsigned char* base = smem + buf * kStage + a_off + half * 3 * 1024;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      ah[i] = *reinterpret_cast<const half8*>(base + i * 1024);
-      al[i] = *reinterpret_cast<const half8*>(base + kAPlane + i * 1024);
-    }
-  };
-  auto compute = [&](auto half_c) {  // smallest products first
-    constexpr int H = decltype(half_c)::value;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) acc[3 * H + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[3 * H + i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) acc[3 * H + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[3 * H + i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) acc[3 * H + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[3 * H + i][j], 0, 0, 0);
-  };
-  using H0 = std::integral_constant<int, 0>;
-  using H1 = std::integral_constant<int, 1>;
-  auto phase_end = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto reads_done = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
-  auto dma_done = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
+  const WavePos w = wave_pos<T>();
+  StageDma<T> dma(g, smem, w.wid, gridDim.x, blockIdx.x, w.lane);
+  Acc16<T::MI, T::NI> acc;
+  acc.zero();
+  Frag16<T> f(w.wm, w.wn, w.lane);
 
   const int nkt = g.K / BK;
-  issue_stage(0, 0);
+  dma.issue(0, 0);
   if (nkt > 1) {
-    issue_stage(1, 1);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(QPW) : "memory");
+    dma.issue(1, 1);
+    dma_done_but<T::QPW>();  // k-tile 0 has landed, k-tile 1 stays in flight
   } else {
     dma_done();
   }
   phase_end();
-  if (wm == 1) phase_end();  // G1 runs one phase behind
-  load_b(0);
-  load_a(0, 0);
+  if (w.wm == 1) phase_end();  // G1 runs one phase behind
+  f.load_first(smem);
   reads_done();
   phase_end();
-#ifdef WT_PP_STAMPS
-  long long st_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  long long tl_ = __builtin_readcyclecounter();
-  const long long t_begin_ = tl_;
-  st_[5] = tl_ - t_kernel_;
-#endif
-  for (int kt = 0; kt < nkt; ++kt) {
-    compute(H0{});  // C_A(kt)
-    phase_end();
-    PP_STAMP(0);
-    load_a(kt & 1, 1);  // L_B(kt)
-    reads_done();
-    if (wm == 1) dma_done();
-    phase_end();
-    PP_STAMP(1);
-    compute(H1{});  // C_B(kt)
-    if (wm == 0) dma_done();
-    phase_end();
-    PP_STAMP(2);
-    if (kt + 1 < nkt) {  // L_A(kt + 1)
-      if (kt + 2 < nkt) issue_stage(kt + 2, kt & 1);
-      load_b((kt + 1) & 1);
-      load_a((kt + 1) & 1, 0);
-      reads_done();
-    }
-    phase_end();
-    PP_STAMP(3);
-  }
-  if (wm == 0) phase_end();
-#ifdef WT_PP_STAMPS
-  const long long t_loop_end_ = __builtin_readcyclecounter();
-  st_[4] = t_loop_end_ - t_begin_;
-#endif
-  planes_epilogue<EPI, PLANES_OUT, WN, LN>(g, accs, smem, m0, n0, wid, wm, wn, lane);
-#ifdef WT_PP_STAMPS
-  {
-    const long long t_end_ = __builtin_readcyclecounter();
-    st_[6] = t_end_ - t_loop_end_;
-    st_[7] = t_end_ - t_kernel_;
-    st_[8] = (long long)__builtin_amdgcn_s_memrealtime() - r_kernel_;
-    if (lane == 0 && blockIdx.x < 1024)
-      for (int i = 0; i < 9; ++i) g_pp_stamps[(blockIdx.x * 8 + wid) * 9 + i] = st_[i];
-  }
-#endif
+  pingpong_k_loop<0>(smem, dma, f, acc, nkt, w.wm, st);
+  planes_epilogue<EPI, PLANES_OUT, T::WN, LN>(g, acc, smem, dma.m0, dma.n0, w.wid, w.wm, w.wn, w.lane);
+  st.store(w.lane, w.wid);
 }
 
 // gemm_planes_pp16 as a PERSISTENT launch for the shapes a CU runs several tiles of (qkv, fc1: plane output, bias / GELU):
@@ -826,145 +767,54 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_pp16(PlaneGemmDev g) {
 // vmcnt: the epilogue's 36 plane stores per wave are younger (a tile with rows past M may skip stores: it waits for all).
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_planes_pp16_persist(PlaneGemmDev g, int total_tiles) {
-  constexpr int WN = 4, NI = 3, MI = 3;
+  using T = PlaneTile<4, 3, 3>;
   constexpr bool PLANES_OUT = true;
   static_assert((EPI & ~(kEpiBias | kEpiGelu)) == 0, "bias / GELU epilogues with plane output");
-  constexpr int BN = WN * NI * 32, NW = 2 * WN, BM = 64 * MI;
-  constexpr int kAPlane = BM * BK * 2, kWPlane = BN * BK * 2;
-  constexpr int kStage = 2 * kAPlane + 2 * kWPlane;
-  constexpr int QA = BM / 16, QW = BN / 16;
-  constexpr int QT = 2 * QA + 2 * QW, QPW = QT / NW;
-  constexpr int kEpiStores = MI * NI * 4;  // per wave: 9 blocks x 2 passes x (hi, lo)
+  constexpr int P = 1;                            // stage parity: a tile's first k-tile in stage 1
+  constexpr int kEpiStores = T::MI * T::NI * 4;  // per wave: 9 blocks x 2 passes x (hi, lo)
+  PpStamps st;                                    // (the probe reads the one-tile-per-block kernels' stamps only)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
-  const int grid = gridDim.x, bid = blockIdx.x;
-  const int q8 = total_tiles >> 3, r8 = total_tiles & 7;
-  const int n_tiles = g.N / BN;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid / WN, wn = wid % WN;
-
-  unsigned voff[QPW], kstep[QPW];
-  const unsigned char* ubase[QPW];
-  const unsigned lds_base = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)smem;
-  int m0 = 0, n0 = 0;
+  const int grid = gridDim.x;
+  const WavePos w = wave_pos<T>();
   // virtual block id -> tile: the XCD-aware bijective remap of the one-tile-per-block kernels over all tiles (grid is a
   // multiple of 8, so a block's tiles keep its XCD)
-  auto set_tile = [&](int vid) {
-    const int xcd = vid & 7;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (vid >> 3);
-    m0 = (logical / n_tiles) * BM;
-    n0 = (logical % n_tiles) * BN;
-    setup_stage_dma<QA, QW, NW, QPW>(g, m0, n0, wid, lane, voff, ubase, kstep);
-  };
-  auto issue_stage = [&](int kt) {
-    const int buf = (kt + 1) & 1;
-#pragma unroll
-    for (int j = 0; j < QPW; ++j) {
-      const unsigned long long sb = reinterpret_cast<unsigned long long>(ubase[j]) + (size_t)kt * kstep[j];
-      lds_dma16_sgpr(voff[j], sb, lds_base + (unsigned)(buf * kStage + (wid + NW * j) * 1024));
-    }
-  };
-
-  Acc16<MI, NI> accs;
-  auto& acc = accs.t;
-  const int fc = lane & 15, fq = lane >> 4;
-  const int frag = fc * 64 + ((fq ^ chunk_swizzle(fc)) * 16);
-  const int a_off = wm * (32 * MI) * 64 + frag, b_off = 2 * kAPlane + wn * (NI * 32) * 64 + frag;
-  half8 ah[3], al[3], bh[6], bl[6];
-  auto load_b = [&](int kt) {
-    const unsigned char* base = smem + ((kt + 1) & 1) * kStage + b_off;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      bh[j] = *reinterpret_cast<const half8*>(base + j * 1024);
-      bl[j] = *reinterpret_cast<const half8*>(base + kWPlane + j * 1024);
-    }
-  };
-  auto load_a = [&](int kt, int half) {
-    const unsigned char* base = smem + ((kt + 1) & 1) * kStage + a_off + half * 3 * 1024;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      ah[i] = *reinterpret_cast<const half8*>(base + i * 1024);
-      al[i] = *reinterpret_cast<const half8*>(base + kAPlane + i * 1024);
-    }
-  };
-  auto compute = [&](auto half_c) {
-    constexpr int H = decltype(half_c)::value;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) acc[3 * H + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[3 * H + i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) acc[3 * H + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[3 * H + i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) acc[3 * H + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[3 * H + i][j], 0, 0, 0);
-  };
-  using H0 = std::integral_constant<int, 0>;
-  using H1 = std::integral_constant<int, 1>;
-  auto phase_end = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto reads_done = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
-  auto dma_done = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
+  int vid = blockIdx.x;
+  StageDma<T> dma(g, smem, w.wid, total_tiles, vid, w.lane);
+  Acc16<T::MI, T::NI> acc;
+  Frag16<T> f(w.wm, w.wn, w.lane);
 
   const int nkt = g.K / BK;  // even and >= 4 (launcher)
-  int vid = bid;
-  set_tile(vid);
-  issue_stage(0);
-  issue_stage(1);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(QPW) : "memory");
+  dma.issue(0, stage_of<P>(0));
+  dma.issue(1, stage_of<P>(1));
+  dma_done_but<T::QPW>();
   phase_end();
   for (;;) {
-    if (wm == 1) phase_end();  // G1 runs one phase behind
-    accs.zero();
-    load_b(0);
-    load_a(0, 0);
+    if (w.wm == 1) phase_end();  // G1 runs one phase behind
+    acc.zero();
+    f.load_first(smem + stage_of<P>(0) * T::kStage);
     reads_done();
     phase_end();
-    for (int kt = 0; kt < nkt; ++kt) {
-      compute(H0{});
-      phase_end();
-      load_a(kt, 1);
-      reads_done();
-      if (wm == 1) dma_done();
-      phase_end();
-      compute(H1{});
-      if (wm == 0) dma_done();
-      phase_end();
-      if (kt + 1 < nkt) {
-        if (kt + 2 < nkt) issue_stage(kt + 2);
-        load_b(kt + 1);
-        load_a(kt + 1, 0);
-        reads_done();
-      }
-      phase_end();
-    }
-    if (wm == 0) phase_end();
-    const int m_cur = m0, n_cur = n0;
+    pingpong_k_loop<P>(smem, dma, f, acc, nkt, w.wm, st);
+    const int m_cur = dma.m0, n_cur = dma.n0;
     const int next = vid + grid;
     const bool has_next = next < total_tiles;
-    const bool whole = m_cur + BM <= g.M;
+    const bool whole = m_cur + T::BM <= g.M;
     auto prefetch = [&]() {
       if (has_next) {
-        set_tile(next);
-        issue_stage(0);
+        dma.set_tile(g, total_tiles, next, w.lane);
+        dma.issue(0, stage_of<P>(0));
       }
     };
-    planes_epilogue<EPI, PLANES_OUT, WN, false>(g, accs, smem, m_cur, n_cur, wid, wm, wn, lane, ActiveEpilogueHook<decltype(prefetch)>{prefetch});
+    planes_epilogue<EPI, PLANES_OUT, T::WN, false>(g, acc, smem, m_cur, n_cur, w.wid, w.wm, w.wn, w.lane,
+                                                   ActiveEpilogueHook<decltype(prefetch)>{prefetch});
     if (!has_next) break;
     if (whole) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kEpiStores) : "memory");
+      dma_done_but<kEpiStores>();
     } else {
       dma_done();
     }
     phase_end();  // every wave is done with the epilogue's LDS; the next tile's first k-tile is visible
-    issue_stage(1);
+    dma.issue(1, stage_of<P>(1));
     vid = next;
   }
 }
@@ -972,9 +822,9 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_pp16_persist(PlaneGemmDev 
 // Launches what `plan` (plane_gemm_plan below) names for this tile: the schedule is decided there, not here.
 template <int EPI, bool PLANES_OUT, int WN, int NI, int MI = 3, bool LN = false>
 void launch_planes_shape(const PlaneGemmDev& g, hipStream_t s, const PlaneGemmPlan& plan, int n_cu = 0) {
-  constexpr int BN = WN * NI * 32, BM = 64 * MI;
-  const int blocks = ((g.M + BM - 1) / BM) * (g.N / BN);
-  constexpr size_t smem = 2 * (2 * BM * BK * 2 + 2 * BN * BK * 2);  // two stages; the epilogue stages fit inside
+  using T = PlaneTile<WN, NI, MI>;
+  const int blocks = ((g.M + T::BM - 1) / T::BM) * (g.N / T::BN);
+  constexpr size_t smem = 2 * T::kStage;  // two stages; the epilogue stages fit inside
   static const bool raised = [] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_planes_tile<EPI, PLANES_OUT, WN, NI, MI, LN>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1054,7 +904,7 @@ bool launch_planes(const PlaneGemmDev& g, int n_cu, hipStream_t s) {
 }  // namespace
 
 // W [N][K] fp32 -> two fp16 planes (hi = fp16(w * scale), lo = fp16(w * scale - hi)) in the layout the plane GEMM's
-// LDS-DMA stages without rearranging (k_gemm_planes.hip, setup_stage_dma): [N / 16][Kpad / 32][hi | lo][16 rows][32 k],
+// LDS-DMA stages without rearranging (k_gemm_planes.hip, StageDma): [N / 16][Kpad / 32][hi | lo][16 rows][32 k],
 // 1 KiB per (row group, k-tile, plane) — exactly the LDS image of one global_load_lds_dwordx4, the four 16-byte chunks of
 // a row XOR-swizzled by (row >> 2) & 3 as the fragment reads expect.  N a multiple of 16, Kpad of 32, zero filled.
 std::vector<unsigned short> split_weight_planes(const float* W, int N, int K, int Kpad, float scale) {

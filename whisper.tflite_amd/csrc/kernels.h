@@ -125,7 +125,9 @@ struct PlaneGemmArgs {
   int* nonfinite = nullptr;
 };
 bool launch_gemm_planes(const PlaneGemmArgs& a, int epi, hipStream_t s);
-// schedule of the 384-column plane tiles (0 in step, 1 ping-pong groups; k_gemm_planes.hip) — measurement knob
+// schedule of the 384-column plane tiles (0 in step, 1 ping-pong groups, 2 ping-pong groups on 16 x 16 x 32 MFMAs and
+// persistent where a CU runs several plane-output tiles, 4 the same with one tile per block everywhere;
+// k_gemm_planes.hip) — measurement knob
 int plane_gemm_mode();
 void set_plane_gemm_mode(int m);
 // What launch_gemm_planes launches for a shape, and the only place that decides it (the launcher launches from this):
