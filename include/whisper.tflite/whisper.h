@@ -169,6 +169,12 @@ struct EncDec : public Engine {
   // {index into language_meta / lang_code, its probability among the language tokens}; encoder + one decoder position,
   // nothing is transcribed.  Throws std::runtime_error for an English-only engine or on a device error.
   std::pair<int, float> detect_language(std::vector<float>& samples);
+  // An addition: the languages every detection chooses among (wt_engine_set_language_candidates; an empty list clears),
+  // and {language, probability} per window of the last transcribe() that detected: "language" = -1, with
+  // "max_positions" also "full_language" = 1, where every window carries its file's language (wt_last_languages).
+  // set_language_candidates throws std::runtime_error where the C call fails.
+  void set_language_candidates(const std::vector<int>& langs);
+  std::vector<std::pair<int, float>> languages() const;
   // An addition: the time-stamped segments of the last transcribe() with the options "timestamps" = 1 and
   // "max_positions" set (wt_capi.h, wt_last_segments); empty when that call ran without timestamps.
   struct Segment {

@@ -292,6 +292,30 @@ int wt_detect_language_pcm(wt_engine* h, const float* pcm, size_t n_samples, int
  * entries written).  Returns the clip count, or -WT_ERR_INVALID_ARG when the last synchronous decode did not detect
  * (as wt_last_beam_scores).  Pipelined batches carry the language in their ids: ids[b][1] - 50259. */
 int wt_last_languages(const wt_engine* h, int32_t* lang, float* prob, int cap);
+/* Automatic language behind "max_positions" (DESIGN.md section 32): option "full_language" (0 = default: a full-length
+ * call with language = WT_LANGUAGE_AUTO is WT_ERR_UNSUPPORTED, as ever; 1 = every clip of such a call is decoded behind
+ * [sot, <its language>, task, ..]).  The language is a function of the audio alone: the argmax over the allowed language
+ * tokens of the logits at position 0 of [sot] — what wt_detect_language_batch returns for the clip — whatever the context,
+ * temperature, seed, attempt, suppression lists, batch or "use_graphs".  It works with and without "timestamps",
+ * "scores", "skip_silence", "temperature", "temperature_fallback" (every attempt), the suppression lists, either kind of
+ * context, "seek", "full_beam" = 1 with beam_size 2..8, "best_of" and "fallback_beam" (every hypothesis and sample of a clip
+ * carries the clip's language), "word_timestamps" (the alignment rows carry it too, and the word-splitting rule follows
+ * it per clip), wt_transcribe_long_pcm and wt_transcribe_long_batch; the long calls follow Whisper's transcribe():
+ * one language per file, detected on the file's first window and held for its later windows.  wt_last_languages then
+ * reports per clip of a full-length call, and per window of a long call each window's file's value (next to
+ * wt_last_window_files).  WT_ERR_UNSUPPORTED with full_language = 1 and language = WT_LANGUAGE_AUTO, the engine stays
+ * usable: a caller prompt, the forced-ids tap, the bf16 storage mode and the pipeline (a Monolith engine or one without
+ * language tokens already refuses language = WT_LANGUAGE_AUTO itself); beam_size > 1 without "max_positions" stays refused.
+ * Language candidates: langs [n] ids in [0, wt_language_count()), duplicates allowed, n = 0 clears the list, n > 128 or
+ * an id outside the range is WT_ERR_INVALID_ARG, a Monolith engine or one without language tokens WT_ERR_UNSUPPORTED.  With
+ * a list set every detecting path — wt_detect_language_*, the automatic decode of the calls with rows of WT_MAX_IDS ids,
+ * the pipeline included, and the full-length calls above — detects among the candidates only: probabilities are
+ * normalised over them and exactly 0 elsewhere, and a one-entry list gives that language with probability 1.  The
+ * read-only option "language_candidates" reports the number of distinct ids.  Call it with nothing in flight.
+ * Option "task" (0 = default: transcribe; 1 = translate): every prompt the engine builds itself carries <|translate|>
+ * where <|transcribe|> stands.  WT_ERR_UNSUPPORTED: an engine created with multilingual = 0, a Monolith engine, a
+ * vocabulary whose <|translate|> id lies outside the model's; a decode call with a caller prompt while task = 1. */
+int wt_engine_set_language_candidates(wt_engine* h, const int32_t* langs, int n);
 
 /* Beam search (option "beam_size" > 1): for every clip of the last synchronous beam call, the chosen hypothesis's sum of
  * natural-log probabilities and its number of generated ids, EOT included (at most cap entries written).  Returns the

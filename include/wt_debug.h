@@ -327,6 +327,16 @@ int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* record
 int wt_dbg_language_head(wt_engine* h, int rows, int d, int n_vocab, int lang_lo, int n_lang, int forced_lang, const float* x,
                          const float* xpart, const float* ln_g, const float* ln_b, const float* tok_emb, float* probs,
                          int32_t* lang, float* lang_prob, int64_t* ids, int ids_stride);
+/* language_head_rows (k_misc.hip) over host rows x [x_rows][d] (+ xpart or NULL): clip b reads row
+ * b * x_rows_per_clip.  allow: four words, bit r = language r (NULL: all); hold [clips] (NULL: detect every clip).
+ * probs [clips][n_lang], lang / lang_prob [clips].  ids0 / ids1 [ids_rows][ids_stride] in / out (ids1 or both may be
+ * NULL): column id_pos of rows b * fan .. b * fan + fan - 1 = lang_lo + lang[b].  Sizes that the host buffers cannot
+ * hold are refused here, everything else by the launcher (WT_ERR_INVALID_ARG both). */
+int wt_dbg_language_head_rows(wt_engine* h, int clips, int x_rows, int x_rows_per_clip, int d, int n_vocab, int lang_lo,
+                              int n_lang, const float* x, const float* xpart, const float* ln_g, const float* ln_b,
+                              const float* tok_emb, const uint32_t* allow, const int32_t* hold, float* probs, int32_t* lang,
+                              float* lang_prob, int64_t* ids0, int64_t* ids1, int ids_rows, int ids_stride, int id_pos,
+                              int fan);
 /* The log-mel front end, kernel by kernel (Engine::logmel, k_misc.hip; DESIGN "front end, kernel by kernel").
  * wt_dbg_frontend_dims: {frames T0, samples per clip, pcm_stride (samples + the zero tail), pw_ld, mel_n, mel_k, dft_n,
  * dft_k} of the engine's front end. */

@@ -51,6 +51,7 @@ CAPI_SYMBOLS = [
     "wt_engine_set_alignment_heads", "wt_last_words", "wt_last_word_text",
     "wt_last_scores", "wt_last_token_logprobs", "wt_last_segment_scores", "wt_last_decode_info", "wt_last_best_of",
     "wt_language_count", "wt_detect_language_batch", "wt_detect_language_batch_dev", "wt_detect_language_pcm", "wt_last_languages",
+    "wt_engine_set_language_candidates",
     "wt_last_timings", "wt_last_beam_scores", "wt_last_kernel_stats", "wt_decode_text", "wt_language_id", "wt_lang_code", "wt_wav_read_legacy",
     "wt_vocab_info", "wt_filters", "wt_write_synthetic_weights", "wt_write_synthetic_vocab",
     "wt_vocab_open", "wt_vocab_close", "wt_vocab_get_info", "wt_vocab_get_filters", "wt_vocab_size", "wt_vocab_token",
@@ -64,7 +65,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_beam_full_step", "wt_dbg_beam_full_finalize",
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
-    "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_self_attention_long",
+    "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_language_head_rows", "wt_dbg_self_attention_long",
     "wt_dbg_self_attention_prefill", "wt_dbg_self_attention_long_gather",
     "wt_dbg_self_attention_long_ragged", "wt_dbg_self_attention_prefill_ragged", "wt_dbg_dec_ln_gemm_ragged", "wt_dbg_ragged_cap",
     "wt_dbg_timestamp_select", "wt_dbg_token_scores", "wt_dbg_sample_select", "wt_dbg_suppress_logits",
@@ -153,6 +154,7 @@ def lib() -> ctypes.CDLL:
         L.wt_engine_set_context.argtypes = [c_void_p, ip64, c_int]
         L.wt_engine_set_contexts.argtypes = [c_void_p, ip64, ip32, c_int]
         L.wt_engine_set_suppress.argtypes = [c_void_p, ip64, c_int, ip64, c_int]
+        L.wt_engine_set_language_candidates.argtypes = [c_void_p, ip32, c_int]
         L.wt_vocab_default_suppress.argtypes = [c_void_p, ip64, c_int, ip32, ip64, c_int, ip32]
         L.wt_dbg_suppress_logits.argtypes = [c_void_p, c_int, c_int, c_int, fp, fp, ip64, c_int, ip64, c_int, c_int]
         L.wt_transcribe_long_batch.argtypes = [c_void_p, POINTER(fp), POINTER(c_size_t), c_int]
@@ -252,6 +254,8 @@ def lib() -> ctypes.CDLL:
         L.wt_last_languages.argtypes = [c_void_p, ip32, fp, c_int]
         L.wt_dbg_language_head.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp, fp, fp, ip32, fp,
                                            ip64, c_int]
+        L.wt_dbg_language_head_rows.argtypes = [c_void_p] + [c_int] * 7 + [fp] * 5 + [POINTER(ctypes.c_uint32), ip32, fp, ip32, fp,
+                                                                                   ip64, ip64, c_int, c_int, c_int, c_int]
         L.wt_encdec_tokens_full_batch.argtypes = [c_void_p, fp, c_int, ip64, c_int, ip32]
         L.wt_encdec_tokens_full_batch_dev.argtypes = [c_void_p, c_void_p, c_int, ip64, c_int, ip32]
         L.wt_transcribe_tokens_full_batch_dev.argtypes = [c_void_p, c_void_p, c_int, ip64, c_int, ip32]
@@ -671,6 +675,13 @@ class Engine:
         f = np.ascontiguousarray(first_ids, dtype=np.int64).reshape(-1)
         self._check(lib().wt_engine_set_suppress(self._h, _ip64(a) if a.size else None, a.size,
                                                  _ip64(f) if f.size else None, f.size))
+
+    def set_language_candidates(self, langs=()) -> None:
+        """The languages every detecting path chooses among (wt_engine_set_language_candidates):
+        probabilities are normalised over them and exactly 0 elsewhere.  An empty list clears (read-only option
+        language_candidates: the number of distinct ids)."""
+        a = np.ascontiguousarray(langs, dtype=np.int32).reshape(-1)
+        self._check(lib().wt_engine_set_language_candidates(self._h, _ip32(a) if a.size else None, a.size))
 
     def dbg_suppress_logits(self, logits, ids=(), first_ids=(), first=False, V=None):
         """suppress_logits (k_suppress.hip) on logits [rows][ldl] whose first V columns are the vocabulary (default: all
@@ -1705,6 +1716,31 @@ class Engine:
             _fp(tok_emb), _fp(probs), _ip32(lang), _fp(prob), _ip64(ids) if ids is not None else None,
             ids.shape[1] if ids is not None else 0))
         return probs, lang, prob, ids
+
+    def dbg_language_head_rows(self, x, ln_g, ln_b, tok_emb, lang_lo, n_lang, clips, x_rows_per_clip=1, xpart=None, allow=None,
+                               hold=None, ids=None, ids2=None, id_pos=1, fan=1):
+        """language_head_rows: clip b reads row b * x_rows_per_clip of x [x_rows][d] (+ xpart) and writes lang_lo + lang[b]
+        at column id_pos of rows b * fan .. b * fan + fan - 1 of ids (and ids2), both [ids_rows][stride] int64.  allow: four
+        uint32 words or None; hold: int32 [clips] or None (a held clip's probs are the detected ones).
+        Returns (probs [clips][n_lang], lang [clips], lang_prob [clips], ids copy or None, ids2 copy or None)."""
+        x, ln_g, ln_b, tok_emb = _f32(x), _f32(ln_g), _f32(ln_b), _f32(tok_emb)
+        xpart = _f32(xpart) if xpart is not None else None
+        x_rows, d = x.shape
+        probs = np.full((clips, max(n_lang, 1)), np.nan, np.float32)
+        lang = np.full(clips, -1, np.int32)
+        prob = np.full(clips, np.nan, np.float32)
+        allow = np.ascontiguousarray(allow, dtype=np.uint32) if allow is not None else None
+        hold = np.ascontiguousarray(hold, dtype=np.int32) if hold is not None else None
+        ids = np.array(ids, np.int64, order="C") if ids is not None else None
+        ids2 = np.array(ids2, np.int64, order="C") if ids2 is not None else None
+        shape = ids.shape if ids is not None else ids2.shape if ids2 is not None else (0, 0)
+        self._check(lib().wt_dbg_language_head_rows(
+            self._h, clips, x_rows, x_rows_per_clip, d, tok_emb.shape[0], lang_lo, n_lang, _fp(x), _fp(xpart), _fp(ln_g),
+            _fp(ln_b), _fp(tok_emb), allow.ctypes.data_as(POINTER(ctypes.c_uint32)) if allow is not None else None,
+            _ip32(hold) if hold is not None else None, _fp(probs), _ip32(lang), _fp(prob),
+            _ip64(ids) if ids is not None else None, _ip64(ids2) if ids2 is not None else None, shape[0], shape[1], id_pos,
+            fan if (ids is not None or ids2 is not None) else 0))
+        return probs, lang, prob, ids, ids2
 
     def dbg_select_token(self, records, ids, pos, n_ids, finished, eot, stop_at_eot=True, keep_ids=False):
         """select_token over records uint64 [B][n_tiles]; ids int64 [B][stride], n_ids / finished int32 [B] are copied

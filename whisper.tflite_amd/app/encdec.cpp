@@ -1,7 +1,7 @@
 // encdec — same command line as the reference's app/encdec.cpp:30-36:
 //   encdec --model-prefix P --vocab V --input WAV
 // prints the transcript followed by '\n' as the last line of stdout (with --lang auto, a line
-// "language: <code> (p=...)" per 30 s window before it).  The reference pulls
+// "language: <code> (p=...)" per 30 s window before it; with --max-positions per file).  The reference pulls
 // in the 11 kLoC CLI11 header for three required options; a minimal parser keeps the same
 // flags (and --flag=value spelling) and exit status on a usage error.
 #include <algorithm>
@@ -26,6 +26,9 @@ void usage(const char* argv0) {
             << "  --input         Path to the 16 kHz mono WAV        REQUIRED\n"
             << "  --lang          language code of the prompt (default de, as the reference hard-codes), or auto:\n"
             << "                  detected per 30 s window, printed as \"language: <code> (p=...)\" before the transcript\n"
+            << "                  with --max-positions: detected once per file, on its first window (option full_language)\n"
+            << "  --languages en,de,fr  the candidates --lang auto and every other detection choose among\n"
+            << "  --task translate|transcribe  the task token of the prompt (default transcribe)\n"
             << "  --english       English-only vocabulary ids (multilingual = false; the reference hard-codes true)\n"
             << "  --long          transcribe every 30 s window of the file, not only the first\n"
             << "  --beam N        beam search with N hypotheses, 2..8 (default: greedy, as the reference)\n"
@@ -62,7 +65,7 @@ void usage(const char* argv0) {
 }  // namespace
 
 int main(int argc, char* argv[]) {
-  std::string model_prefix, vocab, input, inputs, lang, beam, max_positions, temperature, seed, best_of, cr_threshold, context_ids, alignment_heads,
+  std::string model_prefix, vocab, input, inputs, lang, languages, task, beam, max_positions, temperature, seed, best_of, cr_threshold, context_ids, alignment_heads,
       suppress_tokens;
   bool word_timestamps = false, suppress_default = false, suppress_blank = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
@@ -132,6 +135,8 @@ int main(int argc, char* argv[]) {
     else if (a == "--input") input = v;
     else if (a == "--inputs") inputs = v;
     else if (a == "--lang") lang = v;
+    else if (a == "--languages") languages = v;
+    else if (a == "--task") task = v;
     else if (a == "--beam") beam = v;
     else if (a == "--max-positions") max_positions = v;
     else if (a == "--temperature") temperature = v;
@@ -179,6 +184,25 @@ int main(int argc, char* argv[]) {
       return 105;
     }
   }
+  if (!languages.empty()) {
+    std::vector<int32_t> ids;
+    for (size_t at = 0; at <= languages.size();) {
+      const size_t comma = std::min(languages.find(',', at), languages.size());
+      if (comma > at) ids.push_back(int32_t(language_id(languages.substr(at, comma - at))));
+      at = comma + 1;
+    }
+    if (ids.empty() || wt_engine_set_language_candidates(encdec.handle(), ids.data(), int(ids.size())) != WT_OK) {
+      std::cerr << "--languages: " << (ids.empty() ? "expected language codes, got " + languages : std::string(wt_last_error(encdec.handle()))) << "\n";
+      return 105;
+    }
+  }
+  if (!task.empty()) {
+    if ((task != "translate" && task != "transcribe") ||
+        wt_engine_set_option(encdec.handle(), "task", task == "translate" ? 1 : 0) != WT_OK) {
+      std::cerr << "--task: " << (task != "translate" && task != "transcribe" ? "expected translate or transcribe, got " + task : std::string(wt_last_error(encdec.handle()))) << "\n";
+      return 105;
+    }
+  }
   if (!beam.empty()) {
     char* end = nullptr;
     const long n = std::strtol(beam.c_str(), &end, 10);
@@ -192,6 +216,11 @@ int main(int argc, char* argv[]) {
     const long n = std::strtol(max_positions.c_str(), &end, 10);
     if (end == max_positions.c_str() || *end || wt_engine_set_option(encdec.handle(), "max_positions", n) != WT_OK) {
       std::cerr << "--max-positions: expected 0 or a position count in [32, n_text_ctx], got " << max_positions << "\n";
+      return 105;
+    }
+    // --lang auto with --max-positions: the automatic language of the full-length paths (the library's default refuses it)
+    if (lang == "auto" && n > 0 && wt_engine_set_option(encdec.handle(), "full_language", 1) != WT_OK) {
+      std::cerr << "--lang auto with --max-positions: " << wt_last_error(encdec.handle()) << "\n";
       return 105;
     }
     // --beam N with --max-positions: full-length beam search (the option full_beam; the library's default refuses it)
@@ -434,7 +463,17 @@ int main(int argc, char* argv[]) {
         return 1;
       }
       text.resize(len);
-      std::cout << "== " << paths[f] << "\n" << text << "\n";
+      std::cout << "== " << paths[f] << "\n";
+      if (lang == "auto") {  // the file's language: what its first window carries
+        const int n = wt_last_languages(encdec.handle(), nullptr, nullptr, 0);
+        std::vector<int32_t> l(size_t(std::max(n, 1))), wf(size_t(std::max(n, 1)));
+        std::vector<float> p(size_t(std::max(n, 1)));
+        if (n > 0 && wt_last_languages(encdec.handle(), l.data(), p.data(), n) == n && wt_last_window_files(encdec.handle(), wf.data(), n) == n) {
+          const auto w = std::find(wf.begin(), wf.begin() + n, int32_t(f)) - wf.begin();
+          if (w < n) std::cout << "language: " << lang_code(size_t(l[size_t(w)])) << " (p=" << p[size_t(w)] << ")\n";
+        }
+      }
+      std::cout << text << "\n";
     }
     return 0;
   }
@@ -462,7 +501,10 @@ int main(int argc, char* argv[]) {
     if (n > 0) {
       l.resize(size_t(n)), p.resize(size_t(n));
       wt_last_languages(encdec.handle(), l.data(), p.data(), n);
-      for (int i = 0; i < n; ++i) std::cout << "language: " << lang_code(size_t(l[i])) << " (p=" << p[i] << ")\n";
+      // (a full-length call, --max-positions above 0: every window carries its file's language, one line per file)
+      long positions = 0;
+      const bool full_length = wt_engine_get_option(encdec.handle(), "max_positions", &positions) == WT_OK && positions > 0;
+      for (int i = 0; i < (full_length ? 1 : n); ++i) std::cout << "language: " << lang_code(size_t(l[i])) << " (p=" << p[i] << ")\n";
     }
   }
   if (scores) {  // one line per window

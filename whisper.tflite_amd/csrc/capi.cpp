@@ -297,6 +297,18 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
   } else if (k == "full_beam") {
     if (value < 0 || value > 1) return fail(h, WT_ERR_INVALID_ARG, "full_beam must be 0 or 1");
     e.full_beam = value;
+  } else if (k == "full_language") {
+    // automatic language behind max_positions: 0 = such a call is refused, 1 = detected per clip
+    if (value < 0 || value > 1) return fail(h, WT_ERR_INVALID_ARG, "full_language must be 0 or 1");
+    e.full_language = value;
+  } else if (k == "task") {
+    try {  // 0 = transcribe, 1 = translate; unsupported on an English-only or Monolith engine or without <|translate|>
+      e.set_task(value);
+    } catch (const wt::Error& err) {
+      return fail(h, err.code, err.what());
+    }
+  } else if (k == "language_candidates") {
+    return fail(h, WT_ERR_INVALID_ARG, "language_candidates is read-only: wt_engine_set_language_candidates sets the list");
   } else if (k == "suppress_default") {
     // logit suppression: 1 = Whisper's default lists from the engine's vocabulary, 0 = none
     if (value < 0 || value > 1) return fail(h, WT_ERR_INVALID_ARG, "suppress_default must be 0 or 1");
@@ -415,6 +427,9 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "bf16") *value = e.bf16;
   else if (k == "beam_size") *value = e.beam_size;
   else if (k == "full_beam") *value = e.full_beam;
+  else if (k == "full_language") *value = e.full_language;
+  else if (k == "task") *value = e.task;
+  else if (k == "language_candidates") *value = long(e.language_candidates.size());
   else if (k == "kernel_timers") *value = e.kernel_timers;
   else if (k == "fc2_ksplit") *value = e.fc2_ksplit;
   else if (k == "attn_variant") *value = e.attn_variant;
@@ -790,6 +805,11 @@ int wt_language_count(const wt_engine* h) {
   if (!h) return -WT_ERR_INVALID_ARG;
   const int n = h->impl->lang_tokens();
   return n > 0 ? n : -WT_ERR_UNSUPPORTED;
+}
+
+int wt_engine_set_language_candidates(wt_engine* h, const int32_t* langs, int n) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] { h->impl->set_language_candidates(langs, n); });
 }
 
 int wt_detect_language_batch_dev(wt_engine* h, const float* d_mel, int batch, int32_t* lang, float* probs) {

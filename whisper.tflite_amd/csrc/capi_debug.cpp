@@ -1509,6 +1509,43 @@ int wt_dbg_language_head(wt_engine* h, int rows, int d, int n_vocab, int lang_lo
   });
 }
 
+int wt_dbg_language_head_rows(wt_engine* h, int clips, int x_rows, int x_rows_per_clip, int d, int n_vocab, int lang_lo,
+                              int n_lang, const float* x, const float* xpart, const float* ln_g, const float* ln_b,
+                              const float* tok_emb, const uint32_t* allow, const int32_t* hold, float* probs, int32_t* lang,
+                              float* lang_prob, int64_t* ids0, int64_t* ids1, int ids_rows, int ids_stride, int id_pos,
+                              int fan) {
+  // what the copies below need; shapes, ranges and the id rows are the launcher's to refuse
+  if (!h || !x || !ln_g || !ln_b || !tok_emb || !probs || !lang || !lang_prob || clips < 1 || clips > 128 || x_rows < 1 ||
+      x_rows > 1024 || d < 1 || d > 4096 || n_vocab < 1 || n_vocab > 4096 || n_lang < 1 || n_lang > 1024 ||
+      ((ids0 || ids1) && (ids_rows < 1 || ids_rows > 4096 || ids_stride < 1 || ids_stride > 4096))) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const size_t rd = size_t(x_rows) * d, ni = size_t(ids_rows) * ids_stride;
+    DevArr<float> dx(rd, x), dxp(xpart ? rd : 0, xpart), dg(d, ln_g), db(d, ln_b), demb(size_t(n_vocab) * d, tok_emb);
+    DevArr<float> dprobs(size_t(clips) * n_lang, probs), dprob(clips, lang_prob);
+    DevArr<int> dlang(clips, lang), dhold(hold ? clips : 0, hold);
+    DevArr<unsigned> dallow(allow ? 4 : 0, allow);
+    DevArr<long long> di0(ids0 ? ni : 0, reinterpret_cast<const long long*>(ids0));
+    DevArr<long long> di1(ids1 ? ni : 0, reinterpret_cast<const long long*>(ids1));
+    wt::LanguageRowsArgs a;
+    a.x = dx.p; a.xpart = xpart ? dxp.p : nullptr; a.ln_g = dg.p; a.ln_b = db.p; a.tok_emb = demb.p;
+    a.clips = clips; a.x_rows = x_rows; a.x_rows_per_clip = x_rows_per_clip; a.d = d; a.n_vocab = n_vocab;
+    a.lang_lo = lang_lo; a.n_lang = n_lang; a.allow = allow ? dallow.p : nullptr; a.hold = hold ? dhold.p : nullptr;
+    a.probs = dprobs.p; a.lang = dlang.p; a.lang_prob = dprob.p;
+    if (ids0) a.ids[0] = di0.p, a.ids_rows[0] = ids_rows, a.ids_stride[0] = ids_stride;
+    if (ids1) a.ids[1] = di1.p, a.ids_rows[1] = ids_rows, a.ids_stride[1] = ids_stride;
+    a.id_pos = id_pos; a.fan = fan;
+    wt::launch_language_head_rows(a, h->impl->stream());
+    h->impl->sync();
+    dprobs.to_host(probs);
+    dprob.to_host(lang_prob);
+    dlang.to_host(lang);
+    if (ids0) di0.to_host(reinterpret_cast<long long*>(ids0));
+    if (ids1) di1.to_host(reinterpret_cast<long long*>(ids1));
+  });
+}
+
 int wt_dbg_cross_absorbed_chain(wt_engine* h, int bf16, int batch, int heads, int T, int chunks, int nq, int split, int n_src,
                                 const float* const* E_src, const float* qp, const float* wv, const float* bv, int mode,
                                 int p0_only, int nq_only, float* out, float* ws) {

@@ -1723,9 +1723,84 @@ std::vector<long long> Engine::prompt() const {
     if (timestamps) return {vocab_.token_sot};
     return {vocab_.token_sot, vocab_.token_not};
   }
-  if (timestamps) return {vocab_.token_sot, kLangLo + std::max<long>(language, 0), vocab_.token_transcribe};
+  const long long task_id = task ? vocab_.token_translate : vocab_.token_transcribe;  // option task (set_task)
+  if (timestamps) return {vocab_.token_sot, kLangLo + std::max<long>(language, 0), task_id};
   // (language = -1: position 1 is a placeholder that language_head overwrites on the device, decode_enqueue)
-  return {vocab_.token_sot, kLangLo + std::max<long>(language, 0), vocab_.token_transcribe, vocab_.token_not};
+  return {vocab_.token_sot, kLangLo + std::max<long>(language, 0), task_id, vocab_.token_not};
+}
+
+void Engine::set_task(long value) {
+  if (value < 0 || value > 1) throw Error(kErrInvalidArg, "task must be 0 (transcribe) or 1 (translate)");
+  if (value == 1) {
+    auto no = [](const char* why) { throw Error(kErrUnsupported, std::string("task = translate: ") + why); };
+    if (!multilingual_) no("the engine was created with multilingual = 0");
+    if (monolith_) no("the Monolith engine's single graph takes no task");
+    if (vocab_.token_translate < 0 || vocab_.token_translate >= dims_.n_vocab) no("the model's vocabulary has no <|translate|> id");
+  }
+  task = value;
+}
+
+void Engine::check_task_call() const {
+  if (task && !prompt_override.empty()) {
+    throw Error(kErrUnsupported, "task = translate: not with a caller prompt (wt_engine_set_prompt), which names its own task");
+  }
+}
+
+void Engine::set_language_candidates(const int32_t* langs, int n) {
+  require_idle();
+  if (n < 0 || n > kLangMax || (n > 0 && !langs)) throw Error(kErrInvalidArg, "language candidates: 0 (clears the list) to 128 language ids");
+  if (monolith_) throw Error(kErrUnsupported, "language candidates: the Monolith engine forces <|en|>");
+  if (lang_tokens() < 1) throw Error(kErrUnsupported, "language candidates: this engine's vocabulary has no language tokens");
+  unsigned words[4] = {0, 0, 0, 0};
+  for (int i = 0; i < n; ++i) {
+    if (langs[i] < 0 || langs[i] >= lang_tokens()) throw Error(kErrInvalidArg, "language candidates: an id outside [0, wt_language_count())");
+    words[langs[i] >> 5] |= 1u << (langs[i] & 31);
+  }
+  std::vector<int> v;
+  for (int r = 0; r < lang_tokens(); ++r) {
+    if ((words[r >> 5] >> (r & 31)) & 1u) v.push_back(r);
+  }
+  if (n > 0) {  // (a list always holds an id below lang_tokens(): the kernel's contract)
+    if (!d_lang_allow_) d_lang_allow_ = dev_zeroed<unsigned>(4);
+    sync();
+    HIPCHK(hipMemcpy(d_lang_allow_, words, sizeof(words), hipMemcpyHostToDevice));
+  }
+  language_candidates = v;
+}
+
+void Engine::ensure_full_language_workspace() {
+  ensure_lang_workspace();
+  if (fl_.sot_ids) return;  // (allocated last)
+  fl_.hold = dev_zeroed<int>(kFullClipsMax);
+  fl_.h_hold = pinned<int>(kFullClipsMax);
+  long long* const ids = dev_zeroed<long long>(kFullClipsMax);
+  const std::vector<long long> sot(size_t(kFullClipsMax), vocab_.token_sot);
+  HIPCHK(hipMemcpy(ids, sot.data(), sot.size() * sizeof(long long), hipMemcpyHostToDevice));
+  fl_.sot_ids = ids;
+}
+
+void Engine::enqueue_full_language(const DecWorkspace& dw, int dec, bool split, int batch, long long* ids, int stride, int id_pos,
+                                   hipStream_t st) {
+  LangWorkspace& lw = lw_[dec];
+  LanguageRowsArgs a;
+  a.x = split ? dw.xb : dw.xd; a.xpart = split ? dw.xpart : nullptr; a.ln_g = dec_ln_g; a.ln_b = dec_ln_b; a.tok_emb = tok_emb;
+  a.clips = a.x_rows = batch; a.x_rows_per_clip = 1; a.d = dims_.n_text_state; a.n_vocab = dims_.n_vocab;
+  a.lang_lo = int(kLangLo); a.n_lang = lang_tokens();
+  a.allow = language_candidates.empty() ? nullptr : d_lang_allow_; a.hold = fl_.hold;
+  a.probs = lw.probs; a.lang = lw.lang; a.lang_prob = lw.prob;
+  a.ids[0] = ids; a.ids_rows[0] = kFullClipsMax;  // (the rows both tables are allocated with)
+  a.ids_stride[0] = stride; a.id_pos = id_pos; a.fan = 1;
+  launch_language_head_rows(a, st);
+  HIPCHK(hipMemcpyAsync(h_lang_, lw.lang, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h_lang_prob_, lw.prob, size_t(batch) * sizeof(float), hipMemcpyDeviceToHost, st));
+}
+
+void Engine::detect_windows(const float* pcm, int batch, int32_t* lang, float* prob) {
+  float* d_mel = staging_mel(batch);
+  logmel(upload_pcm(pcm, batch), batch, d_mel);
+  encode_full(d_mel, batch);
+  detect_language(batch, lang, nullptr, prob);
+  sync();  // pcm is read by the H2D copy on the encoder stream
 }
 
 std::vector<long long> Engine::fed_prompt() const {
@@ -2086,6 +2161,7 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
   // 2 = detection alone (detect_language): that first pass over [sot] and the head, nothing else
   const int lang_mode = detect_only_ ? 2 : (language < 0 ? 1 : 0);
   const int n_lang = lang_mode ? lang_tokens() : 0;
+  const bool cand = lang_mode && !language_candidates.empty();  // (the mask itself is device data)
   if (lang_mode) {
     if (n_lang < 1) throw Error(kErrUnsupported, "language detection: this engine's vocabulary has no language tokens");
     ensure_lang_workspace();  // (before any capture: nothing may be allocated inside one)
@@ -2153,12 +2229,21 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
       if (lang_mode && pos0 == 0) {
         // position 0's residual rows -> language probabilities and ids[b][1]; no logits GEMM at this position
         LangWorkspace& lw = lw_[dec_of(si)];
-        LanguageHeadArgs la;
-        la.x = p.split ? dw.xb : dw.xd; la.xpart = p.split ? dw.xpart : nullptr; la.ln_g = dec_ln_g; la.ln_b = dec_ln_b;
-        la.tok_emb = tok_emb; la.rows = batch; la.d = d; la.n_vocab = V; la.lang_lo = int(kLangLo); la.n_lang = n_lang;
-        la.probs = lw.probs; la.lang = lw.lang; la.lang_prob = lw.prob;
-        if (lang_mode == 1) la.ids = dw.ids, la.ids_stride = stride, la.id_pos = 1;
-        timed(tm, 10, [&] { launch_language_head(la, stream_); });
+        if (cand) {  // a candidate list: language_head_rows under its mask
+          LanguageRowsArgs la;
+          la.x = p.split ? dw.xb : dw.xd; la.xpart = p.split ? dw.xpart : nullptr; la.ln_g = dec_ln_g; la.ln_b = dec_ln_b;
+          la.tok_emb = tok_emb; la.clips = la.x_rows = batch; la.d = d; la.n_vocab = V; la.lang_lo = int(kLangLo); la.n_lang = n_lang;
+          la.allow = d_lang_allow_; la.probs = lw.probs; la.lang = lw.lang; la.lang_prob = lw.prob;
+          if (lang_mode == 1) la.ids[0] = dw.ids, la.ids_rows[0] = batch, la.ids_stride[0] = stride, la.id_pos = 1, la.fan = 1;
+          timed(tm, 10, [&] { launch_language_head_rows(la, stream_); });
+        } else {
+          LanguageHeadArgs la;
+          la.x = p.split ? dw.xb : dw.xd; la.xpart = p.split ? dw.xpart : nullptr; la.ln_g = dec_ln_g; la.ln_b = dec_ln_b;
+          la.tok_emb = tok_emb; la.rows = batch; la.d = d; la.n_vocab = V; la.lang_lo = int(kLangLo); la.n_lang = n_lang;
+          la.probs = lw.probs; la.lang = lw.lang; la.lang_prob = lw.prob;
+          if (lang_mode == 1) la.ids = dw.ids, la.ids_stride = stride, la.id_pos = 1;
+          timed(tm, 10, [&] { launch_language_head(la, stream_); });
+        }
         if (!pipelined) {  // a synchronous call reads them after decode_collect (pipelined callers read ids[b][1])
           HIPCHK(hipMemcpyAsync(h_lang_, lw.lang, size_t(batch) * sizeof(int), hipMemcpyDeviceToHost, stream_));
           HIPCHK(hipMemcpyAsync(h_lang_prob_, lw.prob, size_t(batch) * sizeof(float), hipMemcpyDeviceToHost, stream_));
@@ -2191,7 +2276,7 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
   // kernels' one-time attribute set-up) and then captures one hipGraph per slot; later calls
   // replay the slot's graph: one host call instead of ~1100. The logits tap stays eager.
   auto key_of = [&](int si) {
-    return std::vector<long long>{si, batch, max_pos, n_prompt, chunks, long(stop_at_eot), fc2_ksplit, bf16, absorbed ? 1 : 0, n_abs, group, stream_override, forced ? 1 : 0, pipelined ? 1 : 0, lang_mode};
+    return std::vector<long long>{si, batch, max_pos, n_prompt, chunks, long(stop_at_eot), fc2_ksplit, bf16, absorbed ? 1 : 0, n_abs, group, stream_override, forced ? 1 : 0, pipelined ? 1 : 0, lang_mode + (cand ? 2 : 0)};
   };
   // the cached form's graphs are captured for EVERY slot at once (below) and hold each slot's cache pointer: all of
   // them must exist before the capture (need_cross_kv allocates; nothing may be allocated inside a capture)

@@ -203,6 +203,35 @@ class Engine {
   // beam search's (check_beam_call) and full-length decoding's, and no temperature (unless fallback_beam = 1), context,
   // seek, word timestamps or batched seeking (check_full_call).
   long full_beam = 0;
+  // Automatic language behind max_positions.  0: a full-length call with language = -1 is refused.
+  // 1: every clip is decoded behind [sot, <its language>, task, ..]; the language is the argmax over the allowed
+  // language tokens of the logits at position 0 of [sot] alone — what detect_language returns for the clip, whatever
+  // the context, temperature, seed, attempt, suppression lists, batch or use_graphs.  A chain without a context
+  // reads it off its own position-0 pass (language_head_rows writes ids[b][1] before position 1 is embedded); behind
+  // a context one pass over [sot] runs in front of the chain.  The long loops detect once per file, on its first
+  // window, and hold that language for the file's later windows (clip_lang_hold).  Beam search and best_of build their
+  // id rows on the host: for them one detect_language pass runs in front of the chains.  Scope: full-length
+  // decoding's, and no caller prompt, forced ids or Monolith engine (check_full_call).
+  long full_language = 0;
+  bool auto_full() const { return full_language != 0 && language < 0 && max_positions > 0; }
+  // the long loops' per-clip prompt language of the next full-length calls, with the probability it was detected
+  // with: clip b is decoded behind language clip_lang_hold[b] (>= 0) and nothing is detected for it; empty: detect all
+  std::vector<int> clip_lang_hold;
+  std::vector<float> clip_lang_hold_prob;
+  // log-mel + encoder over `batch` host clips, then detect_language: what the long loops call on the first windows
+  void detect_windows(const float* pcm, int batch, int32_t* lang, float* prob);
+  // Language candidates (wt_engine_set_language_candidates): with a list set every detecting path — detect_language,
+  // the 31-position automatic decode, the full-length chains — runs language_head_rows under the list's mask, so
+  // probabilities are normalised over the candidates and exactly 0 elsewhere.  n = 0 clears; duplicates allowed; an id
+  // outside [0, lang_tokens()) or n > kLangMax: kErrInvalidArg; no language tokens or a Monolith engine: kErrUnsupported.
+  std::vector<int> language_candidates;  // distinct, ascending
+  void set_language_candidates(const int32_t* langs, int n);
+  // option "task": 0 = transcribe, 1 = translate (prompt() puts <|translate|> where <|transcribe|> stands); 1 is
+  // kErrUnsupported on an English-only or Monolith engine or with token_translate outside the vocabulary, and a call
+  // with a caller prompt is refused while it is set (check_task_call)
+  long task = 0;
+  void set_task(long value);
+  void check_task_call() const;
   // Timestamp decoding.  1: the default prompt ends before <|notimestamps|> and decode_full applies
   // Whisper's timestamp rules on the device (k_timestamps.hip) in place of select_token.  Full-length greedy decoding
   // only: with the option set every decode call outside that scope is kErrUnsupported (check_timestamp_call; with
@@ -211,6 +240,8 @@ class Engine {
   long max_initial_timestamp = 50;  // ticks of 20 ms allowed for the first timestamp (Whisper's 1.0 s); -1 = no limit
   // the model's logits reach past <|0.00|>: ids token_beg .. n_vocab - 1 are the timestamps
   bool has_timestamp_tokens() const { return dims_.n_vocab > vocab_.token_beg + 1 && vocab_.token_eot >= 0 && vocab_.token_eot < vocab_.token_beg; }
+  // every decode entry point (decode, check_full_args, submit, submit_pcm) calls this first; it therefore also carries
+  // the one refusal of option task (check_task_call)
   void check_timestamp_call() const;
   // Decode confidence.  scores = 1: decode_full also forms, on the device inside the chain
   // (k_scores.hip), the log-probability of every generated id under the set it was chosen from, their sum and count per
@@ -554,6 +585,7 @@ class Engine {
   // transcribe() skips a clip unless avg > threshold (below = false), decode_with_fallback exempts a clip from another
   // attempt only when avg < threshold (below = true)
   bool silent(float no_speech_prob, float avg_logprob, bool below) const;
+  static constexpr int kFullClipsMax = 64;  // rows of the full-length and the ragged id tables (a call's clips at most)
   void ensure_full_workspace(int batch);
   struct RaggedWorkspace {  // allocated by the first ragged call: the slot-space rows [64][ragged_stride()] and the starts [64]
     long long *ids = nullptr, *h_ids = nullptr;
@@ -763,6 +795,19 @@ class Engine {
   int* h_lang_ = nullptr;
   void ensure_lang_workspace();
   bool detect_only_ = false;  // set by detect_language() around its decode_enqueue
+  unsigned* d_lang_allow_ = nullptr;  // [4]: the candidate mask language_head_rows reads (set_language_candidates)
+  struct FullLangWorkspace {  // option full_language: allocated by the first detecting full-length call
+    int *hold = nullptr, *h_hold = nullptr;  // [64] device / pinned: the clips' held languages, -1 = detect
+    long long* sot_ids = nullptr;            // [64][1]: the id rows of the pass over [sot] in front of a context
+  } fl_;
+  void ensure_full_language_workspace();
+  // full_language: the language every clip of the running (or last) decode_full is decoded behind, for the chains and
+  // passes that build id rows on the host: beam_full_chains, decode_best_of, align_words.  Empty: the option language.
+  std::vector<int> call_lang_;
+  // language_head_rows over the `batch` position-0 rows a decoder pass has just left in dw: the language of every clip
+  // into column id_pos of ids [kFullClipsMax][stride] (fw_.ids or rw_.ids) and into lw_ / the pinned mirrors
+  void enqueue_full_language(const DecWorkspace& dw, int dec, bool split, int batch, long long* ids, int stride, int id_pos,
+                             hipStream_t st);
   struct Workspace {
     int batch = 0;
     float *melT = nullptr, *h1p = nullptr, *x = nullptr, *ln = nullptr, *qkv = nullptr,

@@ -20,6 +20,7 @@ namespace wt {
 // of check_full_call and of the other entry points apply as they are)
 // (options scores and skip_silence live in the same scope and are refused here with it)
 void Engine::check_timestamp_call() const {
+  check_task_call();  // (every decode entry point passes here: see the note in engine.h)
   if (timestamps && max_positions <= 0) {
     throw Error(kErrUnsupported, "timestamps: full-length greedy decoding only, set the option max_positions (32 .. n_text_ctx)");
   }
@@ -138,8 +139,14 @@ void Engine::check_full_call() const {
   auto no = [](const char* why) { throw Error(kErrUnsupported, std::string("full-length decoding (max_positions): ") + why); };
   if (beam_size > 1 && !full_beam) no("greedy only, not with beam search (beam_size > 1) unless the option full_beam = 1 is set");
   if (bf16) no("not in the bf16 storage mode");
-  if (language < 0) no("not with automatic language detection (language = -1)");
+  if (language < 0 && !full_language) no("not with automatic language detection (language = -1)");
   if (!forced_ids.empty()) no("not with forced ids");
+  if (language < 0) {  // full_language = 1: the scope of the automatic language behind max_positions
+    auto nl = [](const char* why) { throw Error(kErrUnsupported, std::string("full-length automatic language (full_language): ") + why); };
+    // (a Monolith engine or one without language tokens never gets here: set_language refuses -1 on them)
+    if (!prompt_override.empty()) nl("not with a caller prompt (wt_engine_set_prompt)");
+    if (!clip_lang_hold.empty() && clip_lang_hold.size() != clip_lang_hold_prob.size()) nl("the held languages and their probabilities differ in number");
+  }
   if (beam_size > 1) {  // full_beam = 1: beam search's own scope, and what the beam chain does not run
     auto nb = [](const char* why) { throw Error(kErrUnsupported, std::string("full-length beam search (full_beam): ") + why); };
     check_beam_call(false);
@@ -196,7 +203,7 @@ void Engine::encode_full(const float* d_mel, int batch) {
 // batch stride, are never read: the kernels read cache rows <= pos only, all written by the running chain.
 void Engine::ensure_full_workspace(int batch) {
   const wtw::Dims& c = dims_;
-  const size_t C = 64, cap = size_t(full_cap()), d = c.n_text_state;
+  const size_t C = kFullClipsMax, cap = size_t(full_cap()), d = c.n_text_state;
   if (batch > fw_.kv_clips) {
     if (fw_.kv) {
       HIPCHK(hipStreamSynchronize(stream_));
@@ -255,7 +262,7 @@ void Engine::ensure_full_workspace(int batch) {
 }
 
 void Engine::ensure_ragged_workspace() {
-  const size_t C = 64, S = size_t(ragged_stride());
+  const size_t C = kFullClipsMax, S = size_t(ragged_stride());
   if (!rw_.ids) rw_.ids = dev_zeroed<long long>(C * S);
   if (!rw_.h_ids) rw_.h_ids = pinned<long long>(C * S);
   if (!rw_.start) rw_.start = dev_zeroed<int>(C);
@@ -350,7 +357,45 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   last.forget(kForgetFullDecode);
   // (full_beam = 1: check_full_call; fallback_beam = 1 with a temperature: the beam chain is the attempt at 0 below)
   const bool bfb = beam_fallback();
-  if (beam_size > 1 && !bfb) return decode_beam_full(batch, ids, ids_stride, n_ids);
+  // option full_language: clip b's prompt language is hold[b] when the long loop holds one, else it is
+  // detected: off the chain's own position-0 pass, or behind a context off one pass over [sot] in front of the chain.
+  // The chains that carry several rows per clip — beam search and best_of — take their prompts from the host: for them
+  // one detect_language pass runs first, and every hypothesis, sample and attempt of a clip carries the clip's language.
+  const bool autol = auto_full();
+  std::vector<int> hold(size_t(batch), -1);
+  std::vector<float> hold_prob(size_t(batch), 0.0f);
+  if (autol && !clip_lang_hold.empty()) {
+    if (clip_lang_hold.size() != size_t(batch)) throw Error(kErrInvalidArg, "full_language: the held languages are for another number of clips");
+    for (int b = 0; b < batch; ++b) {
+      hold[size_t(b)] = std::min(clip_lang_hold[size_t(b)], lang_tokens() - 1);
+      hold_prob[size_t(b)] = clip_lang_hold_prob[size_t(b)];
+    }
+  }
+  auto undetected = [&] { return autol && std::any_of(hold.begin(), hold.end(), [](int h) { return h < 0; }); };
+  if (undetected() && (beam_size > 1 || best_of_sampling())) {
+    std::vector<int32_t> dl(static_cast<size_t>(batch), 0);
+    std::vector<float> dp(static_cast<size_t>(batch), 0.0f);
+    detect_language(batch, dl.data(), nullptr, dp.data());
+    for (int b = 0; b < batch; ++b) {
+      if (hold[size_t(b)] < 0) hold[size_t(b)] = dl[size_t(b)], hold_prob[size_t(b)] = dp[size_t(b)];
+    }
+  }
+  const bool det = undetected();
+  call_lang_ = autol ? hold : std::vector<int>();  // (a detecting chain fills the open entries once it has run)
+  auto publish_languages = [&] {  // per clip the language it was decoded behind: detected by the chain (the pinned mirrors), or held
+    if (!autol) return;
+    last.lang.assign(size_t(batch), 0);
+    last.lang_prob.assign(size_t(batch), 0.0f);
+    for (int b = 0; b < batch; ++b) {
+      last.lang[size_t(b)] = call_lang_[size_t(b)] = hold[size_t(b)] >= 0 ? hold[size_t(b)] : h_lang_[b];
+      last.lang_prob[size_t(b)] = hold[size_t(b)] >= 0 ? hold_prob[size_t(b)] : h_lang_prob_[b];
+    }
+    last.lang_valid = true;
+  };
+  if (beam_size > 1 && !bfb) {
+    decode_beam_full(batch, ids, ids_stride, n_ids);
+    return publish_languages();
+  }
   const bool ts = timestamps != 0, sc = scores != 0, smp = sampling(), sup = suppressing();
   const int n_sup = int(suppress_ids.size()), n_sup_first = int(suppress_first_ids.size());
   ensure_batch(batch);
@@ -366,6 +411,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   // and the rows come back to the caller's layout when the chain has ended (run_chain)
   const bool rag = !clip_contexts.empty();
   if (rag) ensure_ragged_workspace();
+  if (det) ensure_full_language_workspace();  // (before any capture)
   Slot& slot = slots_[slot_idx];
   const int V = dims_.n_vocab, cap = full_cap(), stride = rag ? ragged_stride() : cap + 1;
   // with a context (set_context): [prev] + context + prompt(), every count below starts behind all of it
@@ -425,6 +471,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     for (int pos0 = 0, np = 1; pos0 < hi; pos0 += np) {
       np = pos0 < prompt_end ? std::min(np_max, prompt_end - pos0) : 1;
       if (sc && pos0 <= sot_idx) np = std::min(np, sot_idx - pos0 + 1);  // a pass ends at sot, with logits: the no-speech probability
+      if (det && !ctx && pos0 == 0) np = 1;  // the language is read off position 0 before position 1 can be embedded
       if (pos0 < lo) continue;
       const int last = pos0 + np - 1;
       const bool logits = last >= n_prompt - 1;  // then the token of the last position's rows
@@ -438,6 +485,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
         sa.state = nullptr;
         launch_no_speech_prob(sa, vocab_.token_solm, fw_.sc_nosp, st);
       }
+      // position 0's residual rows -> ids[b][1], before any pass embeds position 1 (the logits GEMM leaves them as they are)
+      if (det && !ctx && pos0 == 0) enqueue_full_language(dw, slot.dec, p.split, batch, d_ids, stride, 1, st);
       if (logits) {
         // Whisper's SuppressTokens / SuppressBlank, behind the no-speech probability and in front of every rule
         if (sup) enqueue_suppress(fw_.ts_logits, fw_.ts_ldl, batch, last + 1 - n_prompt == 0, st);
@@ -490,6 +539,9 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
         }
       }
       fw_.h_n[b] = n_prompt;
+      // (behind sot, at the same slot for every clip: the held language, or a placeholder the device overwrites)
+      if (autol) h_ids[size_t(b) * stride + sot_idx + 1] = kLangLo + std::max(hold[size_t(b)], 0);
+      if (det) fl_.h_hold[b] = hold[size_t(b)];
     }
     HIPCHK(hipStreamWaitEvent(st, slot.enc_done, 0));
     if (first) HIPCHK(hipEventRecord(slot.dec_begin, st));
@@ -503,6 +555,17 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       HIPCHK(hipMemsetAsync(dw.finished, 0, size_t(batch) * sizeof(int), st));
     }
     if (smp) HIPCHK(hipMemcpyAsync(fw_.sm_prm, fw_.h_prm, sizeof(SampleParams), hipMemcpyHostToDevice, st));
+    if (det) HIPCHK(hipMemcpyAsync(fl_.hold, fl_.h_hold, size_t(batch) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (det && ctx) {
+      // one pass over [sot] at position 0 for all clips, as detect_language runs it, and the language into the slot
+      // behind sot.  It leaves row 0 of every clip's self-attention cache behind; the chain reads cache rows only
+      // after writing them itself (ensure_full_workspace), so nothing of this pass reaches it.
+      DecPass q = p;
+      q.ids = fl_.sot_ids; q.ids_stride = 1; q.pos0 = 0; q.np = 1; q.best = nullptr;
+      q.self_prefill = q.self_long = false; q.pos_start = nullptr; q.pos_limit = 0;
+      decoder_pass(q, st);
+      enqueue_full_language(dw, slot.dec, p.split, batch, d_ids, stride, sot_idx + 1, st);
+    }
     if (ts) {  // the carried state of the timestamp rules: nothing generated yet
       launch_ts_state_init(d_ids, stride, nullptr, n_prompt, n_prompt, V, vocab_.token_beg, fw_.ts_state, batch, st);
     }
@@ -517,6 +580,9 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
                                  absorbed ? 1 : 0, n_abs, slot.dec, ts ? 1 : 0, ts ? max_initial_timestamp : 0, sc ? 1 : 0,
                                  smp ? 1 : 0};
       if (sup) key.push_back(n_sup), key.push_back(n_sup_first);  // launch constants; the ids themselves are device data
+      // (one entry more, where suppression adds two: the detecting chain, under a candidate list or not; the mask, the
+      // held languages and the languages themselves are device data)
+      if (det) key.push_back(language_candidates.empty() ? 1 : 2);
       return key;
     };
     // every clip finished (ragged: or capped): the chain ends behind that segment
@@ -653,6 +719,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   r.ids = h_ids; r.stride = stride; r.n = fw_.h_n; r.lp = h_lp;
   r.sum = fw_.h_sum; r.count = fw_.h_count; r.nosp = fw_.h_nosp; r.n_prompt = np_of;
   publish_full(r, batch, ids, ids_stride, n_ids);
+  publish_languages();
   if (word_timestamps && !defer_word_alignment) {
     align_words(batch, last.segments, valid_samples ? *valid_samples : std::vector<long long>());
   }
@@ -748,6 +815,8 @@ void Engine::beam_full_chains(int batch, bool first, int& steps) {
   hipStream_t const st = dec_stream_at(slot.dec);
   for (int b = 0; b < kBeamClipsMax; ++b) {
     for (int i = 0; i < stride; ++i) bf_.h_prompt[size_t(b) * stride + i] = i < n_prompt ? prompt[size_t(i)] : 0;
+    // full_language: the clip's own language behind sot (decode_full detected or holds it)
+    if (size_t(b) < call_lang_.size()) bf_.h_prompt[size_t(b) * stride + 1] = kLangLo + std::max(call_lang_[size_t(b)], 0);
   }
   HIPCHK(hipStreamWaitEvent(st, slot.enc_done, 0));
   if (first) HIPCHK(hipEventRecord(slot.dec_begin, st));
@@ -805,7 +874,7 @@ void Engine::beam_full_chains(int batch, bool first, int& steps) {
       }
       return seg_steps;
     };
-    HIPCHK(hipMemcpyAsync(bf_.ids[0], bf_.h_prompt, size_t(nc) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(bf_.ids[0], bf_.h_prompt + size_t(c0) * stride, size_t(nc) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
     halves(1);  // (begin writes the prompt's table entries into the half step 0 reads)
     launch_beam_full_begin(fa, st);
     // (greedy's keys start with the slot, a beam key with -beam_size, a full-length key with kFullKey)
@@ -877,6 +946,8 @@ void Engine::decode_best_of(int batch, const std::vector<long long>& prompt, con
   hipStream_t const st = dec_stream_at(slot.dec);
   for (int b = 0; b < kBeamClipsMax; ++b) {
     for (int i = 0; i < stride; ++i) bf_.h_prompt[size_t(b) * stride + i] = i < n_prompt ? prompt[size_t(i)] : 0;
+    // full_language: the clip's own language behind sot (decode_full detected or holds it)
+    if (size_t(b) < call_lang_.size()) bf_.h_prompt[size_t(b) * stride + 1] = kLangLo + std::max(call_lang_[size_t(b)], 0);
   }
   for (int b = 0; b < batch; ++b) bo_.h_frozen[b] = frozen ? (*frozen)[size_t(b)] : 0;
   HIPCHK(hipStreamWaitEvent(st, slot.enc_done, 0));
@@ -952,7 +1023,7 @@ void Engine::decode_best_of(int batch, const std::vector<long long>& prompt, con
       }
       return seg_steps;
     };
-    HIPCHK(hipMemcpyAsync(bf_.ids[0], bf_.h_prompt, size_t(nc) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(bf_.ids[0], bf_.h_prompt + size_t(c0) * stride, size_t(nc) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
     launch_best_of_begin(ba, st);
     if (ts) launch_ts_state_init(bf_.ids[0], stride, nullptr, n_prompt, n_prompt, V, vocab_.token_beg, bf_.ts, rows, st);
     auto key_of = [&](int lo) {
@@ -998,8 +1069,13 @@ void Engine::align_words(int batch, const std::vector<Segment>& segs, const std:
   const int text_cap = cap - n_a - 2;
   if (text_cap < 1) throw Error(kErrInvalidArg, "word_timestamps: the prompt leaves no position for text");
   const bool scored = scores != 0 && last.scores_valid;
-  const std::string lang = language >= 0 && language < language_count() ? lang_code(size_t(language)) : std::string("en");
-  const bool unicode_only = lang == "zh" || lang == "ja" || lang == "th" || lang == "lo" || lang == "my" || lang == "yue";
+  // the language a clip was decoded behind: the option, or with full_language what decode_full left per clip
+  auto lang_of = [&](int b) { return language >= 0 ? language : size_t(b) < call_lang_.size() ? long(call_lang_[size_t(b)]) : -1l; };
+  auto unicode_only_of = [&](int b) {  // Whisper's word-splitting rule for the languages written without spaces
+    const long l = lang_of(b);
+    const std::string lang = l >= 0 && l < language_count() ? lang_code(size_t(l)) : std::string("en");
+    return lang == "zh" || lang == "ja" || lang == "th" || lang == "lo" || lang == "my" || lang == "yue";
+  };
 
   // ---- the rows: per clip the text ids of its segments (below EOT, timestamps removed) and where they sit in its id row
   struct Clip {
@@ -1035,6 +1111,7 @@ void Engine::align_words(int batch, const std::vector<Segment>& segs, const std:
     long long* row = fw_.h_ids + size_t(b) * stride;
     for (int i = 0; i < stride; ++i) row[i] = vocab_.token_eot;
     std::copy(A.begin(), A.end(), row);
+    if (language < 0 && lang_of(b) >= 0 && n_a > 1) row[1] = kLangLo + lang_of(b);  // full_language: the clip's own language token
     row[n_a] = vocab_.token_not;
     std::copy(cl.text.begin(), cl.text.end(), row + n_a + 1);
   }
@@ -1143,7 +1220,7 @@ void Engine::align_words(int batch, const std::vector<Segment>& segs, const std:
     if (n_text == 0) continue;  // no segments (nothing decoded, or skip_silence blanked the clip): no words
     std::vector<int64_t> ids(cl.text.begin(), cl.text.end());
     ids.push_back(vocab_.token_eot);
-    std::vector<int> words = split_words(vocab_, ids.data(), n_text + 1, unicode_only);
+    std::vector<int> words = split_words(vocab_, ids.data(), n_text + 1, unicode_only_of(b));
     // the final EOT served as the last end time; ids that share its word (none: a special id starts a word) stay
     int covered = 0;
     std::vector<int> kept;

@@ -430,7 +430,114 @@ __global__ __launch_bounds__(256) void language_head(const float* __restrict__ x
   if (ids) ids[(long)b * ids_stride + id_pos] = (long long)lang_lo + bi;
 }
 
+// language_head on 16-lane groups, one block per clip.  The LayerNorm is language_head's, in the
+// same order.  The 16 groups of 16 lanes then take one embedding row per round — group g rows g, g + 16, ... — in
+// float4 loads, four fmas per load and a four-step xor butterfly inside the group: ceil(n_lang / 16) dependent rounds.
+// allow (four words, bit r = language r; nullptr: all): a language outside it has logit -inf in the softmax and the
+// argmax and probability exactly 0.  hold[b] >= 0: lang / lang_prob / the ids report that language, clamped to the
+// range (probs are the detected ones); hold[b] < 0 or hold == nullptr: the argmax (larger logit, then larger id).
+// Clip b reads row b * x_rows_per_clip of x / xpart and writes lang_lo + lang[b] at column id_pos of rows b * fan .. b * fan +
+// fan - 1 of ids0 and, when given, ids1.  No reduction depends on the grid, the clip's index or fan.
+// Contract: finite row, d % 4 == 0, d <= kLangMaxD, 1 <= n_lang <= kLangMax, an allowed bit below n_lang (launcher,
+// Engine::set_language_candidates); the index stays inside [0, n_lang) whatever allow and hold hold.
+__global__ __launch_bounds__(256) void language_head_rows(const float* __restrict__ x, const float* __restrict__ xpart,
+                                                          int x_rows_per_clip, const float* __restrict__ g,
+                                                          const float* __restrict__ bta,
+                                                          const float* __restrict__ tok_emb, int d, int lang_lo,
+                                                          int n_lang, const unsigned* __restrict__ allow,
+                                                          const int* __restrict__ hold, float* __restrict__ probs,
+                                                          int* __restrict__ lang, float* __restrict__ lang_prob,
+                                                          long long* ids0, int stride0, long long* ids1, int stride1,
+                                                          int id_pos, int fan) {
+  __shared__ __align__(16) float ys[kLangMaxD];
+  __shared__ float zs[kLangMax];
+  __shared__ float red[4];
+  __shared__ unsigned ms[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* row = x + (long)b * x_rows_per_clip * d;
+  const float* prow = xpart ? xpart + (long)b * x_rows_per_clip * d : nullptr;
+  if (tid < 4) ms[tid] = allow ? allow[tid] : 0xffffffffu;
+  float s = 0.0f;
+  for (int i = tid; i < d; i += 256) {
+    const float v = prow ? row[i] + prow[i] : row[i];
+    ys[i] = v;
+    s += v;
+  }
+  const float mean = block_sum_256(s, red) / (float)d;
+  float q = 0.0f;
+  for (int i = tid; i < d; i += 256) {
+    const float t = ys[i] - mean;
+    q += t * t;
+  }
+  const float rstd = rsqrtf(block_sum_256(q, red) / (float)d + 1e-5f);
+  for (int i = tid; i < d; i += 256) ys[i] = (ys[i] - mean) * rstd * g[i] + bta[i];
+  __syncthreads();
+  const int grp = tid >> 4, gl = tid & 15, d4 = d >> 2;
+  const float4* y4 = reinterpret_cast<const float4*>(ys);
+  for (int r0 = 0; r0 < n_lang; r0 += 16) {  // uniform trips: the butterfly runs with every lane of the wavefront
+    const int r = r0 + grp, rr = r < n_lang ? r : n_lang - 1;
+    const float4* e = reinterpret_cast<const float4*>(tok_emb + (long)(lang_lo + rr) * d);
+    float acc = 0.0f;
+    for (int i = gl; i < d4; i += 16) {
+      const float4 w = e[i], y = y4[i];
+      acc = fmaf(y.x, w.x, acc);
+      acc = fmaf(y.y, w.y, acc);
+      acc = fmaf(y.z, w.z, acc);
+      acc = fmaf(y.w, w.w, acc);
+    }
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 16);
+    if (gl == 0 && r < n_lang) zs[r] = (ms[r >> 5] >> (r & 31)) & 1u ? acc : -INFINITY;
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  // softmax and argmax over the allowed entries by the first wavefront: lane l owns entries l and l + 64
+  float bz = -INFINITY;
+  int bi = -1;
+  for (int r = lane; r < n_lang; r += 64) {
+    if (zs[r] > -INFINITY && zs[r] >= bz) bz = zs[r], bi = r;  // ascending r: an equal logit at a larger id wins
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float oz = __shfl_xor(bz, off, 64);
+    const int oi = __shfl_xor(bi, off, 64);
+    if (oz > bz || (oz == bz && oi > bi)) bz = oz, bi = oi;
+  }
+  float sum = 0.0f;
+  for (int r = lane; r < n_lang; r += 64) sum += expf(zs[r] - bz);  // (-inf: exactly 0)
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
+  const float inv = 1.0f / sum;
+  for (int r = lane; r < n_lang; r += 64) probs[(long)b * n_lang + r] = zs[r] > -INFINITY ? expf(zs[r] - bz) * inv : 0.0f;
+  const int hv = hold ? hold[b] : -1;
+  if (hv >= 0) bi = hv;
+  bi = bi < 0 ? 0 : (bi < n_lang ? bi : n_lang - 1);  // (a broken contract keeps the index inside the range all the same)
+  for (int j = lane; j < fan; j += 64) {
+    ids0[((long)b * fan + j) * stride0 + id_pos] = (long long)lang_lo + bi;
+    if (ids1) ids1[((long)b * fan + j) * stride1 + id_pos] = (long long)lang_lo + bi;
+  }
+  if (lane != 0) return;
+  lang[b] = bi;
+  lang_prob[b] = zs[bi] > -INFINITY ? expf(zs[bi] - bz) * inv : 0.0f;
+}
+
 }  // namespace
+
+void launch_language_head_rows(const LanguageRowsArgs& a, hipStream_t s) {
+  const bool shape = a.clips >= 1 && a.x_rows_per_clip >= 1 && a.d >= 4 && a.d % 4 == 0 && a.d <= kLangMaxD && a.n_lang >= 1 &&
+                     a.n_lang <= kLangMax && a.lang_lo >= 0 && long(a.lang_lo) + a.n_lang <= long(a.n_vocab) &&
+                     long(a.clips - 1) * a.x_rows_per_clip + 1 <= long(a.x_rows);
+  const bool ptrs = a.x && a.ln_g && a.ln_b && a.tok_emb && a.probs && a.lang && a.lang_prob;
+  bool tables = a.fan >= 0 && (a.ids[0] || (!a.ids[1] && a.fan == 0));
+  for (int t = 0; t < 2; ++t) {
+    if (!a.ids[t]) continue;
+    tables = tables && a.fan >= 1 && a.id_pos >= 0 && a.id_pos < a.ids_stride[t] && long(a.clips) * a.fan <= long(a.ids_rows[t]);
+  }
+  if (!shape || !ptrs || !tables) throw Error(kErrInvalidArg, "language_head_rows: bad shape, language range or id rows");
+  hipLaunchKernelGGL(language_head_rows, dim3(a.clips), dim3(256), 0, s, a.x, a.xpart, a.x_rows_per_clip, a.ln_g, a.ln_b,
+                     a.tok_emb, a.d, a.lang_lo, a.n_lang, a.allow, a.hold, a.probs, a.lang, a.lang_prob, a.ids[0],
+                     a.ids_stride[0], a.ids[1], a.ids_stride[1], a.id_pos, a.ids[0] ? a.fan : 0);
+}
 
 void launch_language_head(const LanguageHeadArgs& a, hipStream_t s) {
   if (a.rows < 1 || a.d < 1 || a.d > kLangMaxD || a.n_lang < 1 || a.n_lang > kLangMax || a.lang_lo < 0 ||

@@ -394,6 +394,28 @@ struct LanguageHeadArgs {
 };
 void launch_language_head(const LanguageHeadArgs& a, hipStream_t s);
 
+// language_head on 16-lane groups with float4 loads (k_misc.hip): what the full-length chains
+// (option full_language) and every detecting path under a candidate list launch.  Over language_head it takes, all as
+// device data: allow (four words, bit r = language r, nullptr = all; outside it the logit is -inf and the probability
+// exactly 0), hold [clips] (>= 0: report that language, clamped, probs as detected; < 0 or nullptr: detect), and a
+// row mapping: clip b reads row b * x_rows_per_clip of x / xpart (x_rows rows in all) and writes lang_lo + lang[b] at
+// column id_pos of the id rows b * fan .. b * fan + fan - 1 of up to two tables (ids[t] [ids_rows[t]][ids_stride[t]]).
+// The launcher refuses d % 4 != 0, d > kLangMaxD, n_lang > kLangMax and rows or columns outside the buffers.
+struct LanguageRowsArgs {
+  const float *x = nullptr, *xpart = nullptr, *ln_g = nullptr, *ln_b = nullptr;
+  const float* tok_emb = nullptr;  // [n_vocab][d]
+  int clips = 0, x_rows = 0, x_rows_per_clip = 1, d = 0, n_vocab = 0, lang_lo = 0, n_lang = 0;
+  const unsigned* allow = nullptr;
+  const int* hold = nullptr;
+  float* probs = nullptr;  // [clips][n_lang]
+  int* lang = nullptr;
+  float* lang_prob = nullptr;
+  long long* ids[2] = {nullptr, nullptr};
+  int ids_rows[2] = {0, 0}, ids_stride[2] = {0, 0};
+  int id_pos = 1, fan = 0;  // fan = 0 without id tables
+};
+void launch_language_head_rows(const LanguageRowsArgs& a, hipStream_t s);
+
 // ----------------------------------------------------------- beam search ---
 // k_beam.hip (option beam_size 2..8).  Rows of a step are laid out row = k * clips + c (hypothesis slot k of clip c);
 // the id rows are [row][32] int64 and the self-attention caches [layer][k|v][row][cap][d] as in launch_self_attention.

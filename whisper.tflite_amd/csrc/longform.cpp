@@ -54,8 +54,25 @@ struct LoopScope {
   ~LoopScope() {
     e.context_ids = std::move(context), e.clip_contexts = std::move(clip_contexts);
     e.clip_base = 0, e.clip_index_off.clear(), e.defer_word_alignment = false;
+    e.clip_lang_hold.clear(), e.clip_lang_hold_prob.clear();
   }
 };
+
+// option full_language: Whisper's transcribe() detects one language per file, on the file's first
+// window, and decodes every window behind it.  The first windows of the n files go through one detection pass; the
+// loops then hold each file's language (Engine::clip_lang_hold) for every window they decode.
+void detect_files(Engine& e, const float* const* pcm, const size_t* n_samples, int n_files, std::vector<int32_t>* lang,
+                  std::vector<float>* prob) {
+  const size_t win = e.pcm_elems();
+  std::vector<float> clips(size_t(n_files) * win, 0.0f);
+  for (int f = 0; f < n_files; ++f) {
+    const size_t have = std::min(win, n_samples[f]);
+    if (have) std::memcpy(&clips[size_t(f) * win], pcm[f], have * sizeof(float));
+  }
+  lang->assign(size_t(n_files), 0);
+  prob->assign(size_t(n_files), 0.0f);
+  e.detect_windows(clips.data(), n_files, lang->data(), prob->data());
+}
 
 // What a seeking loop carries for one file, and what the file leaves for Engine::last
 struct SeekFile {
@@ -89,6 +106,11 @@ bool seek_window_step(Engine& e, SeekFile& fl, size_t n_samples, int b, const in
     rec.temperature_milli = e.last.decode_info[size_t(b)].temperature_milli;
     out.decode_info.push_back(e.last.decode_info[size_t(b)]);
     out.decode_info_valid = true;
+  }
+  if (e.last.lang_valid && size_t(b) < e.last.lang.size()) {  // full_language: the window carries its file's language
+    out.lang.push_back(e.last.lang[size_t(b)]);
+    out.lang_prob.push_back(e.last.lang_prob[size_t(b)]);
+    out.lang_valid = true;
   }
   const float* const lp = has_scores ? e.last.token_logprob.data() + size_t(b) * e.last.lp_stride : nullptr;
   if (has_scores) {
@@ -146,8 +168,12 @@ void transcribe_windows(Engine& e, const float* pcm, size_t n_samples, std::stri
   std::vector<long long> valid;  // word timestamps: every window's own samples
   std::vector<int64_t> ids;
   std::vector<int32_t> n;
+  std::vector<int32_t> file_lang;
+  std::vector<float> file_prob;
+  if (e.auto_full()) detect_files(e, &pcm, &n_samples, 1, &file_lang, &file_prob);
   for (size_t w0 = 0; w0 < n_win; w0 += 32) {
     const int B = int(std::min<size_t>(32, n_win - w0));
+    if (!file_lang.empty()) e.clip_lang_hold.assign(size_t(B), file_lang[0]), e.clip_lang_hold_prob.assign(size_t(B), file_prob[0]);
     clips.assign(size_t(B) * win, 0.0f);
     valid.assign(size_t(B), 0);
     for (int b = 0; b < B; ++b) {
@@ -188,6 +214,12 @@ void transcribe_seek(Engine& e, const float* pcm, size_t n_samples, std::string*
   std::vector<int64_t> ids;
   std::vector<int32_t> n;
   std::vector<float> clip(win);
+  if (e.auto_full()) {
+    std::vector<int32_t> file_lang;
+    std::vector<float> file_prob;
+    detect_files(e, &pcm, &n_samples, 1, &file_lang, &file_prob);
+    e.clip_lang_hold.assign(1, file_lang[0]), e.clip_lang_hold_prob.assign(1, file_prob[0]);
+  }
   do {
     const size_t have = fl.seek < n_samples ? std::min(win, n_samples - fl.seek) : 0;
     std::fill(clip.begin(), clip.end(), 0.0f);
@@ -241,6 +273,9 @@ void transcribe_seek_batch(Engine& e, const float* const* pcm, const size_t* n_s
   std::vector<bool> done(static_cast<size_t>(n_files), false);
   for (SeekFile& fl : files) fl.ctx.assign(e.context_ids.begin(), e.context_ids.end());  // the caller's context seeds every file
   e.clip_base = 0;
+  std::vector<int32_t> file_lang;
+  std::vector<float> file_prob;
+  if (e.auto_full()) detect_files(e, pcm, n_samples, n_files, &file_lang, &file_prob);
   std::vector<int> active;
   std::vector<float> clips;
   std::vector<int64_t> ids, flat;
@@ -264,6 +299,13 @@ void transcribe_seek_batch(Engine& e, const float* const* pcm, const size_t* n_s
       flat.insert(flat.end(), fl.ctx.begin(), fl.ctx.end());
       offsets.push_back(int32_t(flat.size()));
       e.clip_index_off[size_t(b)] = fl.w - b;  // window w of a file has clip index w in the sampler's counter
+    }
+    if (!file_lang.empty()) {
+      e.clip_lang_hold.assign(size_t(B), 0), e.clip_lang_hold_prob.assign(size_t(B), 0.0f);
+      for (int b = 0; b < B; ++b) {
+        e.clip_lang_hold[size_t(b)] = file_lang[size_t(active[size_t(b)])];
+        e.clip_lang_hold_prob[size_t(b)] = file_prob[size_t(active[size_t(b)])];
+      }
     }
     e.set_contexts(flat.data(), offsets.data(), B);
     e.decode_windows(clips.data(), B, nullptr, &ids, &n_ids);

@@ -81,6 +81,24 @@ std::pair<int, float> detect_samples(wt_engine* h, const std::vector<float>& sam
 }  // namespace
 std::pair<int, float> EncDec::detect_language(std::vector<float>& samples) { return detect_samples(handle_, samples); }
 
+void EncDec::set_language_candidates(const std::vector<int>& langs) {
+  const std::vector<int32_t> ids(langs.begin(), langs.end());
+  if (wt_engine_set_language_candidates(handle_, ids.data(), int(ids.size())) != WT_OK) {
+    throw std::runtime_error(std::string("set_language_candidates: ") + wt_last_error(handle_));
+  }
+}
+
+std::vector<std::pair<int, float>> EncDec::languages() const {
+  std::vector<std::pair<int, float>> out;
+  const int n = wt_last_languages(handle_, nullptr, nullptr, 0);
+  if (n <= 0) return out;
+  std::vector<int32_t> lang(static_cast<size_t>(n));
+  std::vector<float> prob(static_cast<size_t>(n));
+  wt_last_languages(handle_, lang.data(), prob.data(), n);
+  for (int i = 0; i < n; ++i) out.emplace_back(int(lang[size_t(i)]), prob[size_t(i)]);
+  return out;
+}
+
 namespace {
 std::vector<ClipScore> clip_scores(const wt_engine* h) {
   std::vector<ClipScore> out;
