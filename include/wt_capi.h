@@ -134,6 +134,17 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * what beam_size and "max_positions" refuse, "temperature" > 0 and "temperature_fallback" (unless "fallback_beam" = 1,
  * see wt_last_best_of below), either kind of context,
  * "seek", "word_timestamps" and wt_transcribe_long_batch; the engine stays usable after each),
+ * "full_bf16" (0 = default: a full-length call, "max_positions" set, on an engine with "bf16" = 1 is WT_ERR_UNSUPPORTED;
+ * 1 = such a call runs with bf16 weights, bf16 cross-attention operands and a bf16 self-attention cache, fp32
+ * accumulation and an fp32 residual stream, DESIGN.md section 33.  It works with and without "timestamps",
+ * "max_initial_timestamp", "scores", "skip_silence", "temperature", "seed", "temperature_fallback", the suppression
+ * lists, wt_engine_set_context, wt_transcribe_long_pcm with fixed windows and with "seek", "full_beam" = 1 with
+ * beam_size 2..8, "best_of", "fallback_beam", both cross-attention forms and "use_graphs" 0 and 1; a bf16 engine may
+ * choose other ids than the fp32 one wherever two logits lie within the mode's rounding of each other.
+ * WT_ERR_UNSUPPORTED with full_bf16 = 1, each with a text of its own that names the option, the engine stays usable:
+ * "word_timestamps", wt_engine_set_contexts and wt_transcribe_long_batch, language = WT_LANGUAGE_AUTO (also with
+ * "full_language" = 1); the pipeline, forced ids and the other refusals of "max_positions" stand, and so does
+ * beam_size > 1 without "max_positions"),
  * "last_batches" (N = the next N pipelined submits are the last of a job: they are decoded one chain per batch, the very
  * last on the encoder's stream, so the pipeline drains sooner; counts down to 0 by itself, may be set with batches in
  * flight), "force_fallback" (test hook: bit mask of contractions sent to the full-range kernels, nothing in flight).

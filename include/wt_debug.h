@@ -233,6 +233,17 @@ int wt_dbg_dec_ln_gemm_bf16(wt_engine* h, int B, int N, int K, const float* xin,
                             const float* ln_b, const float* W, const float* bias, int gelu, float* Y, float* xout);
 int wt_dbg_self_attention_bf16(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
                                float* kcache, float* vcache, float* out);
+/* The bf16 forms of self_attention_long, its gathered form and self_attention_prefill (option "full_bf16", DESIGN
+ * section 33): the arguments and the refusals of wt_dbg_self_attention_long, wt_dbg_self_attention_long_gather and
+ * wt_dbg_self_attention_prefill.  The caches go in and come back as float32 arrays holding bf16-representable values, as
+ * with wt_dbg_self_attention_bf16; the appended rows are the new k and v rounded to nearest even, and they are scored
+ * as rounded. */
+int wt_dbg_self_attention_long_bf16(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
+                                    float* vcache, float* out);
+int wt_dbg_self_attention_long_gather_bf16(wt_engine* h, int rows, int heads, int cap, int pos, const float* qkv,
+                                           float* kcache, float* vcache, float* out, const uint8_t* anc);
+int wt_dbg_self_attention_prefill_bf16(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
+                                       float* kcache, float* vcache, float* out);
 int wt_dbg_cross_attention_bf16(wt_engine* h, int batch, int heads, int T, int chunks, int nq, const float* x,
                                 const float* ln_g, const float* ln_b, const float* wq, const float* bq, const float* kc,
                                 const float* vc, float* out);

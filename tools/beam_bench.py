@@ -5,10 +5,11 @@
 With --max-positions P the batch cases run the full-length chains instead: full-length beam
 search (full_beam = 1) beside full-length greedy decoding at the same P, ms per call and per decoder step; the
 synthetic weights never emit EOT, so every step runs.  With --suppress-ab every full-length case runs four times, the
-suppression lists cleared and option suppress_default = 1 alternating.
+suppression lists cleared and option suppress_default = 1 alternating.  With --bf16 every case runs
+in the bf16 storage mode (with --max-positions: option full_bf16).
 Every GPU step runs in a child process of its own under a time limit; the parent only collects the JSON lines.
 
-  python tools/beam_bench.py [--beam 5] [--iters 10] [--only CASE] [--max-positions P [--suppress-ab]]
+  python tools/beam_bench.py [--beam 5] [--iters 10] [--only CASE] [--max-positions P [--suppress-ab]] [--bf16]
 """
 from __future__ import annotations
 
@@ -25,13 +26,17 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def child(case: str, beam: int, iters: int, tmp: str, max_positions: int = 0, suppress: int = 0) -> dict:
+def child(case: str, beam: int, iters: int, tmp: str, max_positions: int = 0, suppress: int = 0, bf16: bool = False) -> dict:
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
     pkg = ge.load_package()
     prefix, vocab = ge._assets(tmp, "tiny", 0)
     eng = pkg.Engine(prefix, vocab, True)
     eng.set_option("beam_size", beam)
+    if bf16:
+        eng.set_option("bf16", 1)
+        if max_positions:
+            eng.set_option("full_bf16", 1)
     if max_positions:
         eng.set_option("max_positions", max_positions)
         eng.set_option("full_beam", 1)
@@ -67,6 +72,7 @@ def child(case: str, beam: int, iters: int, tmp: str, max_positions: int = 0, su
             out.update(max_positions=max_positions, decoder_steps=steps, decoder_ms_per_step=tm.decoder_ms / max(steps, 1),
                        suppress_default=suppress, suppress_ids=eng.get_option("suppress_ids"),
                        suppress_first_ids=eng.get_option("suppress_first_ids"))
+    out["bf16"] = int(bf16)
     eng.close()
     return out
 
@@ -88,11 +94,12 @@ def main():
     ap.add_argument("--only", default=None, help="latency, 25 or 64")
     ap.add_argument("--max-positions", type=int, default=0, help="full-length chains over this many positions (0: 31-position chains)")
     ap.add_argument("--suppress-ab", action="store_true", help="with --max-positions: lists cleared / suppress_default, alternating")
+    ap.add_argument("--bf16", action="store_true", help="the bf16 storage mode (with --max-positions: option full_bf16)")
     ap.add_argument("--suppress", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--child", nargs=3, metavar=("CASE", "BEAM", "TMP"), help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        print(json.dumps(child(a.child[0], int(a.child[1]), a.iters, a.child[2], a.max_positions, a.suppress)))
+        print(json.dumps(child(a.child[0], int(a.child[1]), a.iters, a.child[2], a.max_positions, a.suppress, a.bf16)))
         return 0
     runs = [("latency", 1), ("latency", a.beam), ("25", 1), ("25", a.beam), ("64", 1), ("64", a.beam)]
     if a.only:
@@ -104,7 +111,7 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         for case, beam, suppress in runs:
             cmd = [sys.executable, os.path.abspath(__file__), "--iters", str(a.iters), "--max-positions", str(a.max_positions),
-                   "--suppress", str(suppress), "--child", case, str(beam), tmp]
+                   "--suppress", str(suppress)] + (["--bf16"] if a.bf16 else []) + ["--child", case, str(beam), tmp]
             try:
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
             except subprocess.TimeoutExpired:

@@ -67,6 +67,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_language_head_rows", "wt_dbg_self_attention_long",
     "wt_dbg_self_attention_prefill", "wt_dbg_self_attention_long_gather",
+    "wt_dbg_self_attention_long_bf16", "wt_dbg_self_attention_long_gather_bf16", "wt_dbg_self_attention_prefill_bf16",
     "wt_dbg_self_attention_long_ragged", "wt_dbg_self_attention_prefill_ragged", "wt_dbg_dec_ln_gemm_ragged", "wt_dbg_ragged_cap",
     "wt_dbg_timestamp_select", "wt_dbg_token_scores", "wt_dbg_sample_select", "wt_dbg_suppress_logits",
     "wt_dbg_sample_select_group", "wt_dbg_best_of_begin", "wt_dbg_best_of_pick",
@@ -261,10 +262,13 @@ def lib() -> ctypes.CDLL:
         L.wt_transcribe_tokens_full_batch_dev.argtypes = [c_void_p, c_void_p, c_int, ip64, c_int, ip32]
         L.wt_dbg_self_attention_long.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp]
         L.wt_dbg_self_attention_prefill.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp]
+        L.wt_dbg_self_attention_long_bf16.argtypes = L.wt_dbg_self_attention_long.argtypes
+        L.wt_dbg_self_attention_prefill_bf16.argtypes = L.wt_dbg_self_attention_prefill.argtypes
         L.wt_dbg_self_attention_long_ragged.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp, ip32, c_int]
         L.wt_dbg_beam_full_step.argtypes = [c_void_p, POINTER(BeamFullArgs)]
         L.wt_dbg_beam_full_finalize.argtypes = [c_void_p, POINTER(BeamFullArgs)]
         L.wt_dbg_self_attention_long_gather.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp, POINTER(ctypes.c_uint8)]
+        L.wt_dbg_self_attention_long_gather_bf16.argtypes = L.wt_dbg_self_attention_long_gather.argtypes
         L.wt_dbg_self_attention_prefill_ragged.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp, ip32, c_int]
         L.wt_dbg_dec_ln_gemm_ragged.argtypes = [c_void_p, c_int, c_int, c_int, ip64, c_int, ip32, fp, fp,
                                                 c_int, c_int, fp, fp, fp, fp, c_int, fp, fp]
@@ -1454,23 +1458,26 @@ class Engine:
                                               _ip32(counts), den.ctypes.data_as(dp)))
         return lp, sums, counts, den
 
-    def dbg_self_attention_long(self, qkv, kcache, vcache, pos):
+    def dbg_self_attention_long(self, qkv, kcache, vcache, pos, bf16=False):
         """self_attention_long: one new position against caches [B][cap][d] (cap <= 448); returns (out [B][d], kcache,
-        vcache) with row pos appended."""
+        vcache) with row pos appended.  bf16: the bf16 form (option full_bf16) — the caches hold bf16-representable
+        values and the appended row comes back rounded."""
         qkv, kcache, vcache = _f32(qkv), _f32(kcache).copy(), _f32(vcache).copy()
         B, cap, d = kcache.shape
         out = np.zeros((B, d), np.float32)
-        self._check(lib().wt_dbg_self_attention_long(self._h, B, d // 64, cap, pos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
+        fn = lib().wt_dbg_self_attention_long_bf16 if bf16 else lib().wt_dbg_self_attention_long
+        self._check(fn(self._h, B, d // 64, cap, pos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
         return out, kcache, vcache
 
-    def dbg_self_attention_prefill(self, qkv, kcache, vcache, pos, npos):
+    def dbg_self_attention_prefill(self, qkv, kcache, vcache, pos, npos, bf16=False):
         """self_attention_prefill: npos new positions pos .. pos + npos - 1 against caches [B][cap][d] (cap <= 448,
         npos * B <= 128), qkv [npos * B][3d] with rows p * B + b; returns (out [npos * B][d], kcache, vcache) with those
-        rows appended."""
+        rows appended.  bf16: the bf16 form (option full_bf16), caches of bf16-representable values."""
         qkv, kcache, vcache = _f32(qkv), _f32(kcache).copy(), _f32(vcache).copy()
         B, cap, d = kcache.shape
         out = np.zeros((npos * B, d), np.float32)
-        self._check(lib().wt_dbg_self_attention_prefill(self._h, B, d // 64, cap, pos, npos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
+        fn = lib().wt_dbg_self_attention_prefill_bf16 if bf16 else lib().wt_dbg_self_attention_prefill
+        self._check(fn(self._h, B, d // 64, cap, pos, npos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
         return out, kcache, vcache
 
     def dbg_self_attention_long_ragged(self, qkv, kcache, vcache, pos, start, P):
@@ -1484,16 +1491,17 @@ class Engine:
                                                             _fp(out), _ip32(start), P))
         return out, kcache, vcache
 
-    def dbg_self_attention_long_gather(self, qkv, kcache, vcache, pos, anc):
+    def dbg_self_attention_long_gather(self, qkv, kcache, vcache, pos, anc, bf16=False):
         """self_attention_long over a shared cache: row r reads key k < pos from cache row min(anc[r][k], rows - 1);
-        anc [rows][cap] uint8, rows <= 128."""
+        anc [rows][cap] uint8, rows <= 128.  bf16: the bf16 form (option full_bf16)."""
         qkv, kcache, vcache = _f32(qkv), _f32(kcache).copy(), _f32(vcache).copy()
         anc = np.ascontiguousarray(anc, np.uint8)
         B, cap, d = kcache.shape
         assert anc.shape == (B, cap)
         out = np.full((B, d), np.nan, np.float32)
-        self._check(lib().wt_dbg_self_attention_long_gather(self._h, B, d // 64, cap, pos, _fp(qkv), _fp(kcache), _fp(vcache),
-                                                            _fp(out), anc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        fn = lib().wt_dbg_self_attention_long_gather_bf16 if bf16 else lib().wt_dbg_self_attention_long_gather
+        self._check(fn(self._h, B, d // 64, cap, pos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out),
+                       anc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
         return out, kcache, vcache
 
     def dbg_self_attention_prefill_ragged(self, qkv, kcache, vcache, pos, npos, start, P):

@@ -33,6 +33,8 @@ void usage(const char* argv0) {
             << "  --long          transcribe every 30 s window of the file, not only the first\n"
             << "  --beam N        beam search with N hypotheses, 2..8 (default: greedy, as the reference)\n"
             << "                  with --max-positions: full-length beam search, with or without --timestamps and --scores\n"
+            << "  --bf16          the bf16 storage mode (option bf16): bf16 weights, activations and caches, fp32 accumulation\n"
+            << "                  with --max-positions: full-length decoding in that mode (option full_bf16)\n"
             << "  --max-positions N  full-length greedy decoding over N positions, 32 .. n_text_ctx (default: the\n"
             << "                  reference's 31 positions)\n"
             << "  --timestamps    with --max-positions: decode with timestamps and print one line per segment,\n"
@@ -69,7 +71,7 @@ int main(int argc, char* argv[]) {
       suppress_tokens;
   bool word_timestamps = false, suppress_default = false, suppress_blank = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
-       no_condition = false;
+       no_condition = false, bf16 = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], v;
     if (a == "-h" || a == "--help") {
@@ -82,6 +84,10 @@ int main(int argc, char* argv[]) {
     }
     if (a == "--english") {
       english = true;
+      continue;
+    }
+    if (a == "--bf16") {
+      bf16 = true;
       continue;
     }
     if (a == "--timestamps") {
@@ -203,6 +209,10 @@ int main(int argc, char* argv[]) {
       return 105;
     }
   }
+  if (bf16 && wt_engine_set_option(encdec.handle(), "bf16", 1) != WT_OK) {
+    std::cerr << "--bf16: " << wt_last_error(encdec.handle()) << "\n";
+    return 105;
+  }
   if (!beam.empty()) {
     char* end = nullptr;
     const long n = std::strtol(beam.c_str(), &end, 10);
@@ -221,6 +231,11 @@ int main(int argc, char* argv[]) {
     // --lang auto with --max-positions: the automatic language of the full-length paths (the library's default refuses it)
     if (lang == "auto" && n > 0 && wt_engine_set_option(encdec.handle(), "full_language", 1) != WT_OK) {
       std::cerr << "--lang auto with --max-positions: " << wt_last_error(encdec.handle()) << "\n";
+      return 105;
+    }
+    // --bf16 with --max-positions: full-length decoding in the bf16 storage mode (the library's default refuses it)
+    if (bf16 && n > 0 && wt_engine_set_option(encdec.handle(), "full_bf16", 1) != WT_OK) {
+      std::cerr << "--bf16 with --max-positions: " << wt_last_error(encdec.handle()) << "\n";
       return 105;
     }
     // --beam N with --max-positions: full-length beam search (the option full_beam; the library's default refuses it)

@@ -787,35 +787,75 @@ int wt_dbg_self_attention_bf16(wt_engine* h, int batch, int heads, int cap, int 
                                float* kcache, float* vcache, float* out) {
   return dbg_self_attention_impl(h, batch, heads, cap, pos, npos, qkv, kcache, vcache, out, true);
 }
-int wt_dbg_self_attention_long(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
-                               float* vcache, float* out) {
+// The fp32 or the bf16 pair of self-attention caches of a tap (bf16 storage mode: the host arrays are float32 holding
+// bf16-representable values, as wt_dbg_self_attention_bf16 takes them)
+struct DbgSelfCaches {
+  DevArr<float> dk, dv;
+  const DevBf16 dkb, dvb;
+  const bool bf;
+  DbgSelfCaches(float* kcache, float* vcache, size_t nc, bool bf_)
+      : dk(bf_ ? 0 : nc, kcache), dv(bf_ ? 0 : nc, vcache), dkb(kcache, bf_ ? nc : 0), dvb(vcache, bf_ ? nc : 0), bf(bf_) {}
+  void* k() const { return bf ? static_cast<void*>(dkb.ptr()) : dk.p; }
+  void* v() const { return bf ? static_cast<void*>(dvb.ptr()) : dv.p; }
+  void to_host(float* kcache, float* vcache, size_t nc) const {
+    if (bf) {
+      dkb.to_host(kcache, nc);
+      dvb.to_host(vcache, nc);
+    } else {
+      dk.to_host(kcache, nc);
+      dv.to_host(vcache, nc);
+    }
+  }
+};
+static int dbg_self_attention_long_impl(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
+                                        float* vcache, float* out, bool bf) {
   if (!h) return WT_ERR_INVALID_ARG;
   return guarded(h, [&] {
-    wt::check_self_attention_long(cap, pos, batch, heads);  // the launcher's own refusals, before anything is allocated
+    // the launcher's own refusals, before anything is allocated
+    if (bf) wt::check_self_attention_long_bf16(cap, pos, batch, heads);
+    else wt::check_self_attention_long(cap, pos, batch, heads);
     if (!qkv || !kcache || !vcache || !out) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_self_attention_long: NULL array");
     const size_t d = size_t(heads) * 64, nc = size_t(batch) * cap * d;
-    DevArr<float> dq(size_t(batch) * 3 * d, qkv), dk(nc, kcache), dv(nc, vcache), dout(size_t(batch) * d);
-    wt::launch_self_attention_long(dq.p, dk.p, dv.p, cap, pos, dout.p, batch, heads, h->impl->stream());
+    DevArr<float> dq(size_t(batch) * 3 * d, qkv), dout(size_t(batch) * d);
+    const DbgSelfCaches c(kcache, vcache, nc, bf);
+    wt::launch_self_attention_long(dq.p, c.k(), c.v(), cap, pos, dout.p, batch, heads, h->impl->stream(), bf);
     h->impl->sync();
     dout.to_host(out, size_t(batch) * d);
-    dk.to_host(kcache, nc);
-    dv.to_host(vcache, nc);
+    c.to_host(kcache, vcache, nc);
+  });
+}
+int wt_dbg_self_attention_long(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
+                               float* vcache, float* out) {
+  return dbg_self_attention_long_impl(h, batch, heads, cap, pos, qkv, kcache, vcache, out, false);
+}
+int wt_dbg_self_attention_long_bf16(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
+                                    float* vcache, float* out) {
+  return dbg_self_attention_long_impl(h, batch, heads, cap, pos, qkv, kcache, vcache, out, true);
+}
+static int dbg_self_attention_prefill_impl(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
+                                           float* kcache, float* vcache, float* out, bool bf) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    // the launcher's own refusals, before anything is allocated
+    if (bf) wt::check_self_attention_prefill_bf16(cap, pos, npos, batch, heads);
+    else wt::check_self_attention_prefill(cap, pos, npos, batch, heads);
+    if (!qkv || !kcache || !vcache || !out) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_self_attention_prefill: NULL array");
+    const size_t d = size_t(heads) * 64, rows = size_t(npos) * batch, nc = size_t(batch) * cap * d;
+    DevArr<float> dq(rows * 3 * d, qkv), dout(rows * d);
+    const DbgSelfCaches c(kcache, vcache, nc, bf);
+    wt::launch_self_attention_prefill(dq.p, c.k(), c.v(), cap, pos, npos, dout.p, batch, heads, h->impl->stream(), bf);
+    h->impl->sync();
+    dout.to_host(out, rows * d);
+    c.to_host(kcache, vcache, nc);
   });
 }
 int wt_dbg_self_attention_prefill(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
                                   float* kcache, float* vcache, float* out) {
-  if (!h) return WT_ERR_INVALID_ARG;
-  return guarded(h, [&] {
-    wt::check_self_attention_prefill(cap, pos, npos, batch, heads);  // the launcher's own refusals, before anything is allocated
-    if (!qkv || !kcache || !vcache || !out) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_self_attention_prefill: NULL array");
-    const size_t d = size_t(heads) * 64, rows = size_t(npos) * batch, nc = size_t(batch) * cap * d;
-    DevArr<float> dq(rows * 3 * d, qkv), dk(nc, kcache), dv(nc, vcache), dout(rows * d);
-    wt::launch_self_attention_prefill(dq.p, dk.p, dv.p, cap, pos, npos, dout.p, batch, heads, h->impl->stream());
-    h->impl->sync();
-    dout.to_host(out, rows * d);
-    dk.to_host(kcache, nc);
-    dv.to_host(vcache, nc);
-  });
+  return dbg_self_attention_prefill_impl(h, batch, heads, cap, pos, npos, qkv, kcache, vcache, out, false);
+}
+int wt_dbg_self_attention_prefill_bf16(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
+                                       float* kcache, float* vcache, float* out) {
+  return dbg_self_attention_prefill_impl(h, batch, heads, cap, pos, npos, qkv, kcache, vcache, out, true);
 }
 int wt_dbg_self_attention_long_ragged(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
                                       float* vcache, float* out, const int32_t* start, int P) {
@@ -833,21 +873,31 @@ int wt_dbg_self_attention_long_ragged(wt_engine* h, int batch, int heads, int ca
     dv.to_host(vcache, nc);
   });
 }
-int wt_dbg_self_attention_long_gather(wt_engine* h, int rows, int heads, int cap, int pos, const float* qkv, float* kcache,
-                                      float* vcache, float* out, const uint8_t* anc) {
+static int dbg_self_attention_long_gather_impl(wt_engine* h, int rows, int heads, int cap, int pos, const float* qkv,
+                                               float* kcache, float* vcache, float* out, const uint8_t* anc, bool bf) {
   if (!h) return WT_ERR_INVALID_ARG;
   return guarded(h, [&] {
-    wt::check_self_attention_long_gather(cap, pos, rows, heads);  // the launcher's own refusals, before anything is allocated
+    // the launcher's own refusals, before anything is allocated
+    if (bf) wt::check_self_attention_long_gather_bf16(cap, pos, rows, heads);
+    else wt::check_self_attention_long_gather(cap, pos, rows, heads);
     if (!qkv || !kcache || !vcache || !out || !anc) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_self_attention_long_gather: NULL array");
     const size_t d = size_t(heads) * 64, nc = size_t(rows) * cap * d;
-    DevArr<float> dq(size_t(rows) * 3 * d, qkv), dk(nc, kcache), dv(nc, vcache), dout(size_t(rows) * d);
+    DevArr<float> dq(size_t(rows) * 3 * d, qkv), dout(size_t(rows) * d);
+    const DbgSelfCaches c(kcache, vcache, nc, bf);
     const DevArr<unsigned char> da(size_t(rows) * cap, anc);
-    wt::launch_self_attention_long_gather(dq.p, dk.p, dv.p, cap, pos, da.p, dout.p, rows, heads, h->impl->stream());
+    wt::launch_self_attention_long_gather(dq.p, c.k(), c.v(), cap, pos, da.p, dout.p, rows, heads, h->impl->stream(), bf);
     h->impl->sync();
     dout.to_host(out, size_t(rows) * d);
-    dk.to_host(kcache, nc);
-    dv.to_host(vcache, nc);
+    c.to_host(kcache, vcache, nc);
   });
+}
+int wt_dbg_self_attention_long_gather(wt_engine* h, int rows, int heads, int cap, int pos, const float* qkv, float* kcache,
+                                      float* vcache, float* out, const uint8_t* anc) {
+  return dbg_self_attention_long_gather_impl(h, rows, heads, cap, pos, qkv, kcache, vcache, out, anc, false);
+}
+int wt_dbg_self_attention_long_gather_bf16(wt_engine* h, int rows, int heads, int cap, int pos, const float* qkv, float* kcache,
+                                           float* vcache, float* out, const uint8_t* anc) {
+  return dbg_self_attention_long_gather_impl(h, rows, heads, cap, pos, qkv, kcache, vcache, out, anc, true);
 }
 int wt_dbg_self_attention_prefill_ragged(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
                                          float* kcache, float* vcache, float* out, const int32_t* start, int P) {

@@ -1234,7 +1234,7 @@ void Engine::require_idle() const {
 
 void Engine::encode(const float* d_mel, int batch) {
   require_idle();
-  check_beam_call(false);
+  check_beam_call(false, max_positions > 0 && full_bf16 != 0);  // (a full-length call: check_full_call holds the rest)
   select_stream(false);
   encode_enqueue(d_mel, batch);
 }
@@ -2032,18 +2032,18 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
     void* const vc = cache_at(p.self_kv, (size_t(l) * 2 + 1) * self_slab);
     timed(tm, 1, [&] {
       if (p.self_anc) {  // full-length beam search: the hypotheses share one cache through their ancestor tables
-        launch_self_attention_long_gather(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0,
-                                          p.self_anc, dw.attd, B, H, st);
+        launch_self_attention_long_gather(dw.qkvd, kc, vc, p.self_cap, p.pos0, p.self_anc, dw.attd, B, H, st, bf);
       } else if (p.pos_start && p.self_prefill) {  // the ragged chain: prompt slots, then one generated slot per pass
+        // (fp32 caches only: check_full_call refuses per-clip contexts in the bf16 storage mode before anything is enqueued)
         launch_self_attention_prefill_ragged(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0, p.np,
                                              p.pos_start, p.pos_limit, dw.attd, B, H, st);
       } else if (p.pos_start) {
         launch_self_attention_long_ragged(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0,
                                           p.pos_start, p.pos_limit, dw.attd, B, H, st);
-      } else if (p.self_prefill) {  // np positions of a prompt behind a context, fp32 cache
-        launch_self_attention_prefill(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0, p.np, dw.attd, B, H, st);
-      } else if (p.self_long) {  // one position past 32, fp32 cache (full-length decoding)
-        launch_self_attention_long(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0, dw.attd, B, H, st);
+      } else if (p.self_prefill) {  // np positions of a prompt behind a context
+        launch_self_attention_prefill(dw.qkvd, kc, vc, p.self_cap, p.pos0, p.np, dw.attd, B, H, st, bf);
+      } else if (p.self_long) {  // one position past 32 (full-length decoding)
+        launch_self_attention_long(dw.qkvd, kc, vc, p.self_cap, p.pos0, dw.attd, B, H, st, bf);
       } else {
         launch_self_attention(dw.qkvd, kc, vc, p.self_cap, p.pos0, p.np, dw.attd, B, H, st, bf);
       }
@@ -2430,10 +2430,10 @@ void Engine::finish_slot(int slot_idx) {
 
 // -------------------------------------------------------- beam search ---
 
-void Engine::check_beam_call(bool logits_tap) const {
+void Engine::check_beam_call(bool logits_tap, bool allow_bf16) const {
   if (beam_size <= 1) return;
   auto no = [](const char* why) { throw Error(kErrUnsupported, std::string("beam search: ") + why); };
-  if (bf16) no("not in the bf16 storage mode");
+  if (bf16 && !allow_bf16) no("not in the bf16 storage mode");
   if (!cross_absorb) no("needs the absorbed cross-attention (cross_absorb = 1)");
   if (!absorb_active()) no("the absorbed cross-attention is not available with these weights or this gemm_variant");
   if (!stop_at_eot) no("needs stop_at_eot = 1");

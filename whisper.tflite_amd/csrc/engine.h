@@ -166,7 +166,7 @@ class Engine {
   // storage; no pipeline, no forced ids, no logits tap (check_beam_call).
   long beam_size = 1;
   // throws kErrUnsupported when beam_size > 1 and the call or the options fall outside beam search's scope
-  void check_beam_call(bool logits_tap) const;
+  void check_beam_call(bool logits_tap, bool allow_bf16 = false) const;  // allow_bf16: the full-length chain under full_bf16
   // What the last decode call left for the wt_last_* getters, in groups with one flag each (decode_results.h, DESIGN
   // section 29).  Every entry point forgets its own mask of groups first and fills the groups its options ask for.
   DecodeResults last;
@@ -213,6 +213,12 @@ class Engine {
   // id rows on the host: for them one detect_language pass runs in front of the chains.  Scope: full-length
   // decoding's, and no caller prompt, forced ids or Monolith engine (check_full_call).
   long full_language = 0;
+  // Full-length decoding in the bf16 storage mode.  0: a full-length call on a bf16 engine is
+  // refused.  1: the three full-length chains (decode_full, beam_full_chains, the best-of chain) run with bf16 weights,
+  // bf16 cross-attention operands and a bf16 self-attention cache (the first half of the fp32 allocation), on the bf16
+  // forms of self_attention_long, its gathered form and self_attention_prefill.  Scope: full-length decoding's, and no
+  // word_timestamps, per-clip contexts, batched seeking or automatic language (check_full_call).
+  long full_bf16 = 0;
   bool auto_full() const { return full_language != 0 && language < 0 && max_positions > 0; }
   // the long loops' per-clip prompt language of the next full-length calls, with the probability it was detected
   // with: clip b is decoded behind language clip_lang_hold[b] (>= 0) and nothing is detected for it; empty: detect all
@@ -606,6 +612,9 @@ class Engine {
   static constexpr long long kFullKey = -1000;  // first entry of a full-length segment's graph key
   static constexpr long long kBeamFullKey = -2000;  // ... and of a full-length beam segment's
   static constexpr long long kBestOfKey = -3000;    // ... and of a best-of segment's
+  // last entry of those three keys in the bf16 storage mode (option full_bf16), absent in fp32: the entries a key may end
+  // with otherwise (suppression's two counts, the detecting chain's 1 or 2, the flags) are never negative
+  static constexpr long long kBf16KeyMark = -16;
 
   int enc_cus_masked_ = 0;  // CUs the pipelined encoder stream may use
  public:

@@ -138,7 +138,13 @@ void Engine::check_full_call() const {
   if (max_positions <= 0) return;
   auto no = [](const char* why) { throw Error(kErrUnsupported, std::string("full-length decoding (max_positions): ") + why); };
   if (beam_size > 1 && !full_beam) no("greedy only, not with beam search (beam_size > 1) unless the option full_beam = 1 is set");
-  if (bf16) no("not in the bf16 storage mode");
+  if (bf16 && !full_bf16) no("not in the bf16 storage mode unless the option full_bf16 = 1 is set");
+  if (bf16) {  // full_bf16 = 1: what the bf16 chains do not run
+    auto nf = [](const char* why) { throw Error(kErrUnsupported, std::string("full-length decoding in the bf16 storage mode (full_bf16): ") + why); };
+    if (word_timestamps) nf("not with word_timestamps (the alignment pass reads the fp16 planes of the encoder output)");
+    if (!clip_contexts.empty()) nf("not with per-clip contexts (the ragged self-attention kernels have no bf16 form)");
+    if (language < 0) nf("not with automatic language detection (language = -1)");
+  }
   if (language < 0 && !full_language) no("not with automatic language detection (language = -1)");
   if (!forced_ids.empty()) no("not with forced ids");
   if (language < 0) {  // full_language = 1: the scope of the automatic language behind max_positions
@@ -149,7 +155,7 @@ void Engine::check_full_call() const {
   }
   if (beam_size > 1) {  // full_beam = 1: beam search's own scope, and what the beam chain does not run
     auto nb = [](const char* why) { throw Error(kErrUnsupported, std::string("full-length beam search (full_beam): ") + why); };
-    check_beam_call(false);
+    check_beam_call(false, full_bf16 != 0);
     // (fallback_beam = 1: the beam chain is the fall-back's attempt at temperature 0; every other
     // refusal here and in check_beam_call holds for it as it stands)
     if (!fallback_beam && (sampling() || temperature_fallback)) nb("not with a temperature or the temperature fall-back");
@@ -456,6 +462,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
   if (rag) p.pos_start = rw_.start, p.pos_limit = P;
   p.absorbed = absorbed; p.n_abs = n_abs; p.chunks = chunks; p.e = slot.e_planes; p.cross_kv = slot.cross_kv;
   p.split = fc2_split(); p.dw = &dw; p.ldy = V;
+  p.bf = bf16 != 0;  // option full_bf16: bf16 weights and operands, and fw_.kv holds bf16 rows (the first half of it)
   // the timestamp rules, the scores and the sampler read the whole row, the suppression writes into it
   if (ts || sc || smp || sup) p.Y = fw_.ts_logits, p.ldy = fw_.ts_ldl;
   ScoreArgs sa;
@@ -583,6 +590,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       // (one entry more, where suppression adds two: the detecting chain, under a candidate list or not; the mask, the
       // held languages and the languages themselves are device data)
       if (det) key.push_back(language_candidates.empty() ? 1 : 2);
+      // (last, and in the bf16 storage mode only: the fp32 keys stay what they were, and no entry above is negative)
+      if (p.bf) key.push_back(kBf16KeyMark);
       return key;
     };
     // every clip finished (ragged: or capped): the chain ends behind that segment
@@ -841,6 +850,7 @@ void Engine::beam_full_chains(int batch, bool first, int& steps) {
     p.clips = nc; p.ids_stride = stride; p.self_kv = bf_.kv; p.self_cap = cap; p.self_rows = kDecRowsMax;
     p.absorbed = true; p.n_abs = n_abs; p.e = slot.e_planes + size_t(c0) * T * d; p.split = fc2_split(); p.dw = &dw;
     p.Y = bf_.logits; p.ldy = bf_.ldl;
+    p.bf = bf16 != 0;  // option full_bf16: bf_.kv holds bf16 rows (the first half of it)
     ScoreArgs sa;
     sa.logits = bf_.logits; sa.ldl = bf_.ldl; sa.V = V; sa.batch = nc; sa.part = bf_.sc_part;
     const int np_max = std::max(1, std::min(4, kDecRowsMax / nc));
@@ -882,6 +892,7 @@ void Engine::beam_full_chains(int batch, bool first, int& steps) {
       std::vector<long long> key{kBeamFullKey, slot_idx, c0, nc, lo, P, n_prompt, K, fc2_ksplit, n_abs, slot.dec, ts ? 1 : 0,
                                  ts ? max_initial_timestamp : 0, sc ? 1 : 0};
       if (sup) key.push_back(n_sup), key.push_back(n_sup_first);  // launch constants; the ids themselves are device data
+      if (p.bf) key.push_back(kBf16KeyMark);  // (last, in the bf16 storage mode only)
       return key;
     };
     // the position behind the last pass that ran: every clip done ends the chain behind that segment
@@ -970,6 +981,7 @@ void Engine::decode_best_of(int batch, const std::vector<long long>& prompt, con
     p.clips = nc; p.ids = bf_.ids[0]; p.ids_stride = stride; p.self_kv = bf_.kv; p.self_cap = cap; p.self_rows = kDecRowsMax;
     p.absorbed = true; p.n_abs = n_abs; p.e = slot.e_planes + size_t(c0) * T * d; p.split = fc2_split(); p.dw = &dw;
     p.Y = bf_.logits; p.ldy = bf_.ldl;
+    p.bf = bf16 != 0;  // option full_bf16, as in beam_full_chains
     ScoreArgs sa;
     fill_rule_args(sa, bf_.logits, bf_.ldl);
     sa.part = bo_.sc_part;
@@ -1030,6 +1042,7 @@ void Engine::decode_best_of(int batch, const std::vector<long long>& prompt, con
       std::vector<long long> key{kBestOfKey, slot_idx, N, c0, nc, lo, P, n_prompt, fc2_ksplit, n_abs, slot.dec, ts ? 1 : 0,
                                  ts ? max_initial_timestamp : 0, sc ? 1 : 0};
       if (sup) key.push_back(n_sup), key.push_back(n_sup_first);  // launch constants; the ids themselves are device data
+      if (p.bf) key.push_back(kBf16KeyMark);  // (last, in the bf16 storage mode only)
       return key;
     };
     // every row finished: the chain ends behind that segment

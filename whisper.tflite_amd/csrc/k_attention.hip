@@ -561,13 +561,38 @@ __global__ void self_attention_step(const float* __restrict__ qkv, void* __restr
 // and key pos goes to row b itself as above, so no K/V ever moves between rows.  anc[b][0 .. pos) is staged in LDS
 // before the first load round (one more round trip per launch, not per round); a key is still one 256-byte segment
 // and the order of every sum is the ungathered kernel's: with anc[b][k] = b the two are bit-identical.
-template <bool RAGGED, bool GATHER>
-__global__ __launch_bounds__(256) void self_attention_long(const float* __restrict__ qkv, float* __restrict__ kcache,
-                                                           float* __restrict__ vcache, int cap, int pos,
+// BF (bf16 storage mode): the cache rows are bf16, a key of one head is one 128-byte segment and a
+// lane's share of it 8 bytes; eight rounds are in flight instead of four, so a round trip still covers as many bytes.
+// The groups, their keys and the order of every sum are the fp32 kernel's.  The new k and v are rounded (to nearest
+// even) before they are scored and before they are stored: a row contributes the same values whether it was just
+// computed or read back, here or in self_attention_step<true>, which writes rows 0 .. 31 of the same cache.
+template <bool BF>
+struct SelfCache {  // the element of a self-attention cache row, and a lane's four elements of a key as they are loaded
+  using elem = float;
+  using quad = f32x4;
+  static __device__ __forceinline__ f32x4 widen(const f32x4& v) { return v; }
+};
+template <>
+struct SelfCache<true> {
+  using elem = unsigned short;
+  using quad = __attribute__((ext_vector_type(2))) unsigned;
+  static __device__ __forceinline__ f32x4 widen(const quad& v) {
+    return f32x4{bf16_lo(v[0]), bf16_hi(v[0]), bf16_lo(v[1]), bf16_hi(v[1])};
+  }
+  // four fp32 values rounded to bf16, as the cache stores them
+  static __device__ __forceinline__ quad round(const f32x4& v) { return quad{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])}; }
+};
+
+template <bool RAGGED, bool GATHER, bool BF = false>
+__global__ __launch_bounds__(256) void self_attention_long(const float* __restrict__ qkv,
+                                                           typename SelfCache<BF>::elem* __restrict__ kcache,
+                                                           typename SelfCache<BF>::elem* __restrict__ vcache, int cap, int pos,
                                                            float* __restrict__ out, int heads,
                                                            const int* __restrict__ start, int P,
                                                            const unsigned char* __restrict__ anc, int rows) {
-  constexpr int NG = 16, U = 4;  // key rows per load round, rounds in flight
+  using CT = typename SelfCache<BF>::elem;
+  using QT = typename SelfCache<BF>::quad;
+  constexpr int NG = 16, U = BF ? 8 : 4;  // key rows per load round, rounds in flight
   if (RAGGED) {
     const int bb = blockIdx.x / heads;
     const int st = min(max(start[bb], -(1 << 20)), 1 << 20);  // (no overflow whatever the array holds)
@@ -585,14 +610,14 @@ __global__ __launch_bounds__(256) void self_attention_long(const float* __restri
   const int b = blockIdx.x / heads, h = blockIdx.x % heads;
   const int tid = threadIdx.x, grp = tid >> 4, gl16 = tid & 15;
   const int d = heads * 64;
-  float* kc = kcache + ((long)b * cap) * d + h * 64;
-  float* vc = vcache + ((long)b * cap) * d + h * 64;
+  CT* kc = kcache + ((long)b * cap) * d + h * 64;
+  CT* vc = vcache + ((long)b * cap) * d + h * 64;
   const int n = pos + 1;                      // causal: keys 0 .. pos
   const int last_old = pos > 0 ? pos - 1 : 0;  // where the loads of keys >= pos go instead (their values are dropped)
-  const float* kb = kc + gl16 * 4;
-  const float* vb = vc + gl16 * 4;
+  const CT* kb = kc + gl16 * 4;
+  const CT* vb = vc + gl16 * 4;
   __shared__ unsigned char ancs[GATHER ? kSelfLongCap : 1];
-  long hop = 0;  // GATHER: floats from one cache row to the next
+  long hop = 0;  // GATHER: elements from one cache row to the next
   if (GATHER) {
     for (int k = tid; k < pos; k += 256) ancs[k] = anc[(long)b * cap + k];
     __syncthreads();
@@ -600,26 +625,38 @@ __global__ __launch_bounds__(256) void self_attention_long(const float* __restri
     kb -= b * hop;  // row 0
     vb -= b * hop;
   }
-  // GATHER: floats from row 0 to the row that holds key kk (kk = pos only at pos = 0: the block's own row, value dropped)
+  // GATHER: elements from row 0 to the row that holds key kk (kk = pos only at pos = 0: the block's own row, value dropped)
   auto src = [&](int kk) -> long { return (kk < pos ? min((int)ancs[kk], rows - 1) : b) * hop; };
-  f32x4 kv[U], vv[U];
+  QT kv[U], vv[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {  // the first 64 keys are requested before the new row is staged
     const int k = grp + NG * u;
     const int kk = k < pos ? k : last_old;
     const long at = (long)kk * d + (GATHER ? src(kk) : 0);
-    kv[u] = *reinterpret_cast<const f32x4*>(kb + at);
-    vv[u] = *reinterpret_cast<const f32x4*>(vb + at);
+    kv[u] = *reinterpret_cast<const QT*>(kb + at);
+    vv[u] = *reinterpret_cast<const QT*>(vb + at);
   }
   constexpr float kScale = 0.125f * 1.44269504088896340736f;
   if (tid < 64) {
     const float* row = qkv + (long)b * 3 * d + h * 64 + tid;
-    const float knew = row[d], vnew = row[2 * d];
+    float knew = row[d], vnew = row[2 * d];
+    unsigned pk = 0;
+    (void)pk;
+    if constexpr (BF) {  // rounded before they are scored and before they are stored
+      pk = pack_bf16x2(knew, vnew);
+      knew = bf16_lo(pk);
+      vnew = bf16_hi(pk);
+    }
     qs[tid] = row[0] * kScale;
     kn[tid] = knew;
     vn[tid] = vnew;
-    kc[(long)pos * d + tid] = knew;
-    vc[(long)pos * d + tid] = vnew;
+    if constexpr (BF) {
+      kc[(long)pos * d + tid] = (CT)(pk & 0xFFFFu);
+      vc[(long)pos * d + tid] = (CT)(pk >> 16);
+    } else {
+      kc[(long)pos * d + tid] = knew;
+      vc[(long)pos * d + tid] = vnew;
+    }
   }
   __syncthreads();
   const f32x4 q4 = *reinterpret_cast<const f32x4*>(&qs[gl16 * 4]);
@@ -634,15 +671,15 @@ __global__ __launch_bounds__(256) void self_attention_long(const float* __restri
         const int k = k0 + NG * u;
         const int kk = k < pos ? k : last_old;
         const long at = (long)kk * d + (GATHER ? src(kk) : 0);
-        kv[u] = *reinterpret_cast<const f32x4*>(kb + at);
-        vv[u] = *reinterpret_cast<const f32x4*>(vb + at);
+        kv[u] = *reinterpret_cast<const QT*>(kb + at);
+        vv[u] = *reinterpret_cast<const QT*>(vb + at);
       }
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int k = k0 + NG * u;
-      const f32x4 kf = k == pos ? kn4 : kv[u];
-      const f32x4 vf = k == pos ? vn4 : vv[u];
+      const f32x4 kf = k == pos ? kn4 : SelfCache<BF>::widen(kv[u]);
+      const f32x4 vf = k == pos ? vn4 : SelfCache<BF>::widen(vv[u]);
       float s = (kf[0] * q4[0] + kf[1] * q4[1]) + (kf[2] * q4[2] + kf[3] * q4[3]);
       s += __shfl_xor(s, 8, 64);
       s += __shfl_xor(s, 4, 64);
@@ -693,11 +730,17 @@ constexpr int kPrefillQ = 16, kPrefillTile = 32;
 // query outside [0, min(P, cap)) is void: zeros in `out`, nothing appended; the others run as above at their own
 // positions, with keys from qkv for positions >= max(pos0 - start[b], 0) — qkv row = position - (pos0 - start[b]) —
 // and from the cache below that.  A block without a live query reads nothing.
-template <bool RAGGED>
-__global__ __launch_bounds__(256) void self_attention_prefill(const float* __restrict__ qkv, float* __restrict__ kcache,
-                                                              float* __restrict__ vcache, int cap, int pos0, int np,
+// BF (bf16 storage mode): the cache rows are bf16 (8 bytes per lane of a staged row), and every key
+// row taken from qkv is rounded to bf16 on its way into the tile, as the appended rows are: a key contributes the same
+// values whether it came from qkv or was read back, so one launch of np positions equals the same positions in two.
+template <bool RAGGED, bool BF = false>
+__global__ __launch_bounds__(256) void self_attention_prefill(const float* __restrict__ qkv,
+                                                              typename SelfCache<BF>::elem* __restrict__ kcache,
+                                                              typename SelfCache<BF>::elem* __restrict__ vcache, int cap, int pos0, int np,
                                                               int B, float* __restrict__ out, int heads,
                                                               const int* __restrict__ start, int P) {
+  using CT = typename SelfCache<BF>::elem;
+  using QT = typename SelfCache<BF>::quad;
   constexpr int TK = kPrefillTile;
   __shared__ __attribute__((aligned(16))) float Ks[TK][64];
   __shared__ __attribute__((aligned(16))) float Vs[TK][64];
@@ -706,8 +749,8 @@ __global__ __launch_bounds__(256) void self_attention_prefill(const float* __res
   const int b = bh / heads, h = bh % heads;
   const int tid = threadIdx.x, grp = tid >> 4, gl16 = tid & 15;
   const int d = heads * 64;
-  float* kc = kcache + ((long)b * cap) * d + h * 64;
-  float* vc = vcache + ((long)b * cap) * d + h * 64;
+  CT* kc = kcache + ((long)b * cap) * d + h * 64;
+  CT* vc = vcache + ((long)b * cap) * d + h * 64;
   const int p_first = qb * kPrefillQ;
   const int p_last = min(np, p_first + kPrefillQ) - 1;  // the block's last query
   int lim = 0;                                          // RAGGED: positions [0, lim) are live
@@ -730,13 +773,30 @@ __global__ __launch_bounds__(256) void self_attention_prefill(const float* __res
       const int k = k0 + grp + 16 * u;
       kr[u] = vr[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
       if (k < pos0) {
-        kr[u] = *reinterpret_cast<const f32x4*>(kc + (long)k * d + gl16 * 4);
-        vr[u] = *reinterpret_cast<const f32x4*>(vc + (long)k * d + gl16 * 4);
+        if constexpr (BF) {  // the two loaded dwords as they are: nothing waits for a load before the tile is staged
+          const QT k2 = *reinterpret_cast<const QT*>(kc + (long)k * d + gl16 * 4);
+          const QT v2 = *reinterpret_cast<const QT*>(vc + (long)k * d + gl16 * 4);
+          kr[u] = f32x4{__uint_as_float(k2[0]), __uint_as_float(k2[1]), 0.0f, 0.0f};
+          vr[u] = f32x4{__uint_as_float(v2[0]), __uint_as_float(v2[1]), 0.0f, 0.0f};
+        } else {
+          kr[u] = *reinterpret_cast<const f32x4*>(kc + (long)k * d + gl16 * 4);
+          vr[u] = *reinterpret_cast<const f32x4*>(vc + (long)k * d + gl16 * 4);
+        }
       } else if (k < kend) {
         const float* row = qkv + ((long)(k - pos0) * B + b) * 3 * d + h * 64 + gl16 * 4;
         kr[u] = *reinterpret_cast<const f32x4*>(row + d);
         vr[u] = *reinterpret_cast<const f32x4*>(row + 2 * d);
       }
+    }
+  };
+  // BF: what fetch(k0) left in a register as the tile holds it — a cache row's packed dwords widened, a qkv row rounded
+  // as the appended rows are (zeros past the block's last key stay zeros)
+  auto staged = [&](const f32x4& r, int k) -> f32x4 {
+    if constexpr (BF) {
+      if (k < pos0) return SelfCache<BF>::widen(QT{__float_as_uint(r[0]), __float_as_uint(r[1])});
+      return SelfCache<BF>::widen(SelfCache<BF>::round(r));
+    } else {
+      return r;
     }
   };
   fetch(0);
@@ -750,8 +810,13 @@ __global__ __launch_bounds__(256) void self_attention_prefill(const float* __res
     q4 = *reinterpret_cast<const f32x4*>(row);
 #pragma unroll
     for (int j = 0; j < 4; ++j) q4[j] *= kScale;
-    *reinterpret_cast<f32x4*>(kc + (long)(pos0 + p) * d + gl16 * 4) = *reinterpret_cast<const f32x4*>(row + d);
-    *reinterpret_cast<f32x4*>(vc + (long)(pos0 + p) * d + gl16 * 4) = *reinterpret_cast<const f32x4*>(row + 2 * d);
+    if constexpr (BF) {
+      *reinterpret_cast<QT*>(kc + (long)(pos0 + p) * d + gl16 * 4) = SelfCache<BF>::round(*reinterpret_cast<const f32x4*>(row + d));
+      *reinterpret_cast<QT*>(vc + (long)(pos0 + p) * d + gl16 * 4) = SelfCache<BF>::round(*reinterpret_cast<const f32x4*>(row + 2 * d));
+    } else {
+      *reinterpret_cast<f32x4*>(kc + (long)(pos0 + p) * d + gl16 * 4) = *reinterpret_cast<const f32x4*>(row + d);
+      *reinterpret_cast<f32x4*>(vc + (long)(pos0 + p) * d + gl16 * 4) = *reinterpret_cast<const f32x4*>(row + 2 * d);
+    }
   }
   float m = -1e30f, l = 0.0f;
   f32x4 o = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -759,8 +824,8 @@ __global__ __launch_bounds__(256) void self_attention_prefill(const float* __res
     __syncthreads();  // the previous tile has been scored by every group
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      *reinterpret_cast<f32x4*>(&Ks[grp + 16 * u][gl16 * 4]) = kr[u];
-      *reinterpret_cast<f32x4*>(&Vs[grp + 16 * u][gl16 * 4]) = vr[u];
+      *reinterpret_cast<f32x4*>(&Ks[grp + 16 * u][gl16 * 4]) = staged(kr[u], k0 + grp + 16 * u);
+      *reinterpret_cast<f32x4*>(&Vs[grp + 16 * u][gl16 * 4]) = staged(vr[u], k0 + grp + 16 * u);
     }
     __syncthreads();
     if (k0 + TK < kend) fetch(k0 + TK);
@@ -1055,8 +1120,19 @@ void check_self_attention_long(int cap, int pos, int batch, int heads) {
   if (pos < 0 || pos >= cap) throw Error(kErrInvalidArg, "decoder self-attention (long cache): position outside the cache");
 }
 
-void launch_self_attention_long(const float* qkv, float* kcache, float* vcache, int cap, int pos, float* out, int batch,
-                                int heads, hipStream_t s) {
+void check_self_attention_long_bf16(int cap, int pos, int batch, int heads) { check_self_attention_long(cap, pos, batch, heads); }
+
+void launch_self_attention_long(const float* qkv, void* kcache_v, void* vcache_v, int cap, int pos, float* out, int batch,
+                                int heads, hipStream_t s, bool bf16) {
+  if (bf16) {
+    check_self_attention_long_bf16(cap, pos, batch, heads);
+    hipLaunchKernelGGL((self_attention_long<false, false, true>), dim3(batch * heads), dim3(256), 0, s, qkv,
+                       static_cast<unsigned short*>(kcache_v), static_cast<unsigned short*>(vcache_v), cap, pos, out, heads,
+                       static_cast<const int*>(nullptr), 0, static_cast<const unsigned char*>(nullptr), 0);
+    return;
+  }
+  float* const kcache = static_cast<float*>(kcache_v);
+  float* const vcache = static_cast<float*>(vcache_v);
   check_self_attention_long(cap, pos, batch, heads);
   hipLaunchKernelGGL((self_attention_long<false, false>), dim3(batch * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out,
                      heads, static_cast<const int*>(nullptr), 0, static_cast<const unsigned char*>(nullptr), 0);
@@ -1068,10 +1144,23 @@ void check_self_attention_long_gather(int cap, int pos, int rows, int heads) {
   if (rows > kSelfGatherRows) throw Error(kErrInvalidArg, "decoder self-attention (long cache, gathered): rows outside [1, 128]");
 }
 
-void launch_self_attention_long_gather(const float* qkv, float* kcache, float* vcache, int cap, int pos,
-                                       const unsigned char* anc, float* out, int rows, int heads, hipStream_t s) {
+void check_self_attention_long_gather_bf16(int cap, int pos, int rows, int heads) {
   check_self_attention_long_gather(cap, pos, rows, heads);
+}
+
+void launch_self_attention_long_gather(const float* qkv, void* kcache_v, void* vcache_v, int cap, int pos,
+                                       const unsigned char* anc, float* out, int rows, int heads, hipStream_t s, bool bf16) {
+  if (bf16) check_self_attention_long_gather_bf16(cap, pos, rows, heads);
+  else check_self_attention_long_gather(cap, pos, rows, heads);
   if (!anc) throw Error(kErrInvalidArg, "decoder self-attention (long cache, gathered): no ancestor table");
+  if (bf16) {
+    hipLaunchKernelGGL((self_attention_long<false, true, true>), dim3(rows * heads), dim3(256), 0, s, qkv,
+                       static_cast<unsigned short*>(kcache_v), static_cast<unsigned short*>(vcache_v), cap, pos, out, heads,
+                       static_cast<const int*>(nullptr), 0, anc, rows);
+    return;
+  }
+  float* const kcache = static_cast<float*>(kcache_v);
+  float* const vcache = static_cast<float*>(vcache_v);
   hipLaunchKernelGGL((self_attention_long<false, true>), dim3(rows * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out,
                      heads, static_cast<const int*>(nullptr), 0, anc, rows);
 }
@@ -1083,11 +1172,24 @@ void check_self_attention_prefill(int cap, int pos0, int np, int batch, int head
   if (np > kSelfPrefillRows / batch) throw Error(kErrInvalidArg, "decoder self-attention (prefill): more than 128 rows");
 }
 
-void launch_self_attention_prefill(const float* qkv, float* kcache, float* vcache, int cap, int pos0, int np, float* out,
-                                   int batch, int heads, hipStream_t s) {
+void check_self_attention_prefill_bf16(int cap, int pos0, int np, int batch, int heads) {
   check_self_attention_prefill(cap, pos0, np, batch, heads);
+}
+
+void launch_self_attention_prefill(const float* qkv, void* kcache_v, void* vcache_v, int cap, int pos0, int np, float* out,
+                                   int batch, int heads, hipStream_t s, bool bf16) {
+  if (bf16) check_self_attention_prefill_bf16(cap, pos0, np, batch, heads);
+  else check_self_attention_prefill(cap, pos0, np, batch, heads);
   const int qblocks = (np + kPrefillQ - 1) / kPrefillQ;
-  hipLaunchKernelGGL(self_attention_prefill<false>, dim3(batch * heads * qblocks), dim3(256), 0, s, qkv, kcache, vcache, cap,
+  if (bf16) {
+    hipLaunchKernelGGL((self_attention_prefill<false, true>), dim3(batch * heads * qblocks), dim3(256), 0, s, qkv,
+                       static_cast<unsigned short*>(kcache_v), static_cast<unsigned short*>(vcache_v), cap, pos0, np, batch, out,
+                       heads, static_cast<const int*>(nullptr), 0);
+    return;
+  }
+  float* const kcache = static_cast<float*>(kcache_v);
+  float* const vcache = static_cast<float*>(vcache_v);
+  hipLaunchKernelGGL((self_attention_prefill<false, false>), dim3(batch * heads * qblocks), dim3(256), 0, s, qkv, kcache, vcache, cap,
                      pos0, np, batch, out, heads, static_cast<const int*>(nullptr), 0);
 }
 
@@ -1117,7 +1219,7 @@ void launch_self_attention_prefill_ragged(const float* qkv, float* kcache, float
   check_self_attention_prefill_ragged(cap, pos0, np, P, batch, heads);
   if (!start) throw Error(kErrInvalidArg, "decoder self-attention (prefill, ragged): no start array");
   const int qblocks = (np + kPrefillQ - 1) / kPrefillQ;
-  hipLaunchKernelGGL(self_attention_prefill<true>, dim3(batch * heads * qblocks), dim3(256), 0, s, qkv, kcache, vcache, cap,
+  hipLaunchKernelGGL((self_attention_prefill<true, false>), dim3(batch * heads * qblocks), dim3(256), 0, s, qkv, kcache, vcache, cap,
                      pos0, np, batch, out, heads, start, P);
 }
 

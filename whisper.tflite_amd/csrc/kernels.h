@@ -292,9 +292,13 @@ void launch_self_attention(const float* qkv, void* kcache, void* vcache, int cap
 // row pos and attends its q causally over rows 0 .. pos; out rows b.  Rows > pos are neither read nor written.
 // Throws kErrInvalidArg for pos < 0, pos >= cap, cap > kSelfLongCap, batch < 1 or heads < 1 (check_self_attention_long).
 constexpr int kSelfLongCap = 448;  // n_text_ctx of every Whisper
+// bf16 (bf16 storage mode): the cache holds bf16 elements, [B][cap][d]; the new k and v are rounded to
+// nearest even before they are scored and stored, so rows written by launch_self_attention(.., bf16) and by this launcher
+// read alike.  check_self_attention_long_bf16 refuses exactly what check_self_attention_long refuses.
 void check_self_attention_long(int cap, int pos, int batch, int heads);
-void launch_self_attention_long(const float* qkv, float* kcache, float* vcache, int cap, int pos, float* out, int batch,
-                                int heads, hipStream_t s);
+void check_self_attention_long_bf16(int cap, int pos, int batch, int heads);
+void launch_self_attention_long(const float* qkv, void* kcache, void* vcache, int cap, int pos, float* out, int batch,
+                                int heads, hipStream_t s, bool bf16 = false);
 // A prompt behind a context (wt_engine_set_context): np >= 1 new positions pos0 .. pos0 + np - 1 against a cache
 // [B][cap][d], cap <= kSelfLongCap, fp32.  Appends their k and v (qkv rows p * B + b, [.][3d]) at cache rows pos0 + p,
 // each row written once, and attends each q causally over rows 0 .. pos0 + p: rows < pos0 from the cache, the others from
@@ -302,9 +306,12 @@ void launch_self_attention_long(const float* qkv, float* kcache, float* vcache, 
 // Throws kErrInvalidArg for pos0 < 0, np < 1, pos0 + np > cap, cap > kSelfLongCap, np * batch > kSelfPrefillRows, batch < 1
 // or heads < 1 (check_self_attention_prefill).
 constexpr int kSelfPrefillRows = 128;  // rows of one decoder pass (Engine::kDecRowsMax)
+// bf16: the cache holds bf16 elements and every key row taken from qkv is rounded as the appended rows are, so one
+// launch of np positions equals the same positions in two launches, bit for bit.  Same refusals.
 void check_self_attention_prefill(int cap, int pos0, int np, int batch, int heads);
-void launch_self_attention_prefill(const float* qkv, float* kcache, float* vcache, int cap, int pos0, int np, float* out,
-                                   int batch, int heads, hipStream_t s);
+void check_self_attention_prefill_bf16(int cap, int pos0, int np, int batch, int heads);
+void launch_self_attention_prefill(const float* qkv, void* kcache, void* vcache, int cap, int pos0, int np, float* out,
+                                   int batch, int heads, hipStream_t s, bool bf16 = false);
 // The ragged forms of the two: pos / pos0 count SLOTS, clip b is at Whisper position slot - start[b]
 // (start: device [B]) and runs there exactly as above; a position outside [0, min(P, cap)) is void — zeros in `out`, no
 // cache row read or written.  The refusals are those above, except that self_attention_long's slot may lie past the
@@ -321,9 +328,12 @@ void launch_self_attention_prefill_ragged(const float* qkv, float* kcache, float
 // anc[r][k] = r output and cache are bit-identical to launch_self_attention_long's.  Refused: what
 // check_self_attention_long refuses, rows > kSelfGatherRows and a null table.
 constexpr int kSelfGatherRows = 128;  // rows of one decoder pass; a table entry is one byte
+// bf16: the cache holds bf16 elements; with anc[r][k] = r bit-identical to launch_self_attention_long(.., bf16).  Same refusals.
 void check_self_attention_long_gather(int cap, int pos, int rows, int heads);
-void launch_self_attention_long_gather(const float* qkv, float* kcache, float* vcache, int cap, int pos,
-                                       const unsigned char* anc, float* out, int rows, int heads, hipStream_t s);
+void check_self_attention_long_gather_bf16(int cap, int pos, int rows, int heads);
+void launch_self_attention_long_gather(const float* qkv, void* kcache, void* vcache, int cap, int pos,
+                                       const unsigned char* anc, float* out, int rows, int heads, hipStream_t s,
+                                       bool bf16 = false);
 // Cross attention of nq (1..4) query rows per clip over T cached keys, the query projection included:
 // q = LayerNorm(x[row]) . Wq^T + bq with x the residual stream [nq * B][d], rows p * B + b.  wq_t = Wq in the
 // layout of cross_q_layout(); kc, vc [B][heads][T][64]; partial results per key chunk in ws
