@@ -145,6 +145,12 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * "word_timestamps", wt_engine_set_contexts and wt_transcribe_long_batch, language = WT_LANGUAGE_AUTO (also with
  * "full_language" = 1); the pipeline, forced ids and the other refusals of "max_positions" stand, and so does
  * beam_size > 1 without "max_positions"),
+ * "full_bf16_all" (0 = default: those refusals stand; 1, beside "bf16" = 1, "full_bf16" = 1 and "max_positions": they are
+ * lifted — wt_engine_set_contexts and wt_transcribe_long_batch, language = WT_LANGUAGE_AUTO with "full_language" = 1 on every
+ * path of that option, and "word_timestamps" run in the bf16 storage mode; anything but 0 or 1 is
+ * WT_ERR_INVALID_ARG.  The cuts of other options keep their own texts: contexts with "word_timestamps"; contexts, "seek" or
+ * "word_timestamps" behind "full_beam" / "best_of"; "best_of" / "fallback_beam" with wt_transcribe_long_batch; the pipeline
+ * and forced ids),
  * "last_batches" (N = the next N pipelined submits are the last of a job: they are decoded one chain per batch, the very
  * last on the encoder's stream, so the pipeline drains sooner; counts down to 0 by itself, may be set with batches in
  * flight), "force_fallback" (test hook: bit mask of contractions sent to the full-range kernels, nothing in flight).

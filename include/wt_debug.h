@@ -139,6 +139,14 @@ int wt_dbg_self_attention_long_ragged(wt_engine* h, int batch, int heads, int ca
                                       float* vcache, float* out, const int32_t* start, int P);
 int wt_dbg_self_attention_prefill_ragged(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
                                          float* kcache, float* vcache, float* out, const int32_t* start, int P);
+/* The bf16 forms of the two ragged taps (option full_bf16_all): the caches are float32 arrays of
+ * bf16-representable values, as wt_dbg_self_attention_long_bf16 takes them.  A live clip's rows carry the bits of
+ * wt_dbg_self_attention_long_bf16 / wt_dbg_self_attention_prefill_bf16 at the shifted position; the refusals are those of
+ * the fp32 ragged taps. */
+int wt_dbg_self_attention_long_ragged_bf16(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
+                                           float* vcache, float* out, const int32_t* start, int P);
+int wt_dbg_self_attention_prefill_ragged_bf16(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
+                                              float* kcache, float* vcache, float* out, const int32_t* start, int P);
 /* The gathered form of self_attention_long (full-length beam search): the arguments of
  * wt_dbg_self_attention_long — `rows` in the place of the batch, at most 128 — plus anc [rows][cap] bytes.  Row r reads
  * key k < pos from cache row min(anc[r][k], rows - 1) and appends key pos to its own row; entries at k >= pos are not
@@ -485,6 +493,15 @@ int wt_dbg_encoder_attention_at(wt_engine* h, int kind, int variant, int batch, 
 int wt_dbg_align_scores(wt_engine* h, int batch, int H, int T, int np, int pos0, const float* qp, const float* E, int n_heads,
                         const int32_t* head, const int32_t* slot, int heads_total, const int32_t* F, int L_max, int ld, float* W,
                         int mode);
+/* The bf16 form (option full_bf16_all): E is rounded to ONE bf16 plane on the host (to nearest even) and
+ * q' to bf16 in the kernel, one bf16 MFMA per 32 columns and no operand scale.  Arguments and refusals are those above. */
+int wt_dbg_align_scores_bf16(wt_engine* h, int batch, int H, int T, int np, int pos0, const float* qp, const float* E, int n_heads,
+                             const int32_t* head, const int32_t* slot, int heads_total, const int32_t* F, int L_max, int ld,
+                             float* W, int mode);
+/* launch_f32_to_bf16 (k_misc.hip): x [n] -> ONE bf16 plane, rounded to nearest even.  out [n + guard] is in / out as
+ * float32 holding bf16-representable values: uploaded as given, the first n cells written, the guard cells untouched.
+ * n < 4 or n % 4 != 0 is WT_ERR_INVALID_ARG (the launcher's refusal), before anything is launched. */
+int wt_dbg_f32_to_bf16(wt_engine* h, int n, int guard, const float* x, float* out);
 /* launch_align_matrix (word-level timestamps): W [clips][heads][L_max][ld] attention weights ->
  * C [clips][N_max][ld] in / out and stats [clips][heads][2][ld] in / out (mean, then 1 / std; may be NULL), both
  * uploaded as given and downloaded whole, so that every cell the kernels do not write comes back as given.  L [clips] is

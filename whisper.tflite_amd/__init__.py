@@ -76,6 +76,8 @@ DEBUG_SYMBOLS = [
     "wt_dbg_gemm_addressed", "wt_dbg_plane_gemm_plan", "wt_dbg_gemm_ln_fused", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes", "wt_dbg_encoder_attention_at",
     "wt_dbg_encoder_scales", "wt_dbg_f16_scale_for", "wt_dbg_gemm_planes_scaled",
     "wt_dbg_cross_attention_records", "wt_dbg_cross_attention_records_bf16", "wt_dbg_cross_combine", "wt_dbg_cross_combine_bf16",
+    "wt_dbg_self_attention_long_ragged_bf16", "wt_dbg_self_attention_prefill_ragged_bf16", "wt_dbg_align_scores_bf16",
+    "wt_dbg_f32_to_bf16",
     "wt_dbg_align_scores", "wt_dbg_align_matrix", "wt_dbg_align_dtw", "wt_dbg_last_alignment", "wt_dbg_set_alignment",
 ]
 
@@ -265,11 +267,13 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_self_attention_long_bf16.argtypes = L.wt_dbg_self_attention_long.argtypes
         L.wt_dbg_self_attention_prefill_bf16.argtypes = L.wt_dbg_self_attention_prefill.argtypes
         L.wt_dbg_self_attention_long_ragged.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp, ip32, c_int]
+        L.wt_dbg_self_attention_long_ragged_bf16.argtypes = L.wt_dbg_self_attention_long_ragged.argtypes
         L.wt_dbg_beam_full_step.argtypes = [c_void_p, POINTER(BeamFullArgs)]
         L.wt_dbg_beam_full_finalize.argtypes = [c_void_p, POINTER(BeamFullArgs)]
         L.wt_dbg_self_attention_long_gather.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp, POINTER(ctypes.c_uint8)]
         L.wt_dbg_self_attention_long_gather_bf16.argtypes = L.wt_dbg_self_attention_long_gather.argtypes
         L.wt_dbg_self_attention_prefill_ragged.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp, ip32, c_int]
+        L.wt_dbg_self_attention_prefill_ragged_bf16.argtypes = L.wt_dbg_self_attention_prefill_ragged.argtypes
         L.wt_dbg_dec_ln_gemm_ragged.argtypes = [c_void_p, c_int, c_int, c_int, ip64, c_int, ip32, fp, fp,
                                                 c_int, c_int, fp, fp, fp, fp, c_int, fp, fp]
         L.wt_dbg_ragged_cap.argtypes = [c_void_p, c_int, c_int, c_int, ip32, ip32]
@@ -326,6 +330,8 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_last_alignment.argtypes = [c_void_p, c_int, ip32, ip64, fp, fp, ip32]
         L.wt_dbg_align_scores.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, c_int, ip32, ip32, c_int, ip32,
                                           c_int, c_int, fp, c_int]
+        L.wt_dbg_align_scores_bf16.argtypes = L.wt_dbg_align_scores.argtypes
+        L.wt_dbg_f32_to_bf16.argtypes = [c_void_p, c_int, c_int, fp, fp]
         L.wt_dbg_set_alignment.argtypes = [c_void_p, c_int, c_int, c_int]
         L.wt_dbg_align_matrix.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, ip32, ip32, fp, fp]
         L.wt_dbg_align_dtw.argtypes = [c_void_p, c_int, c_int, c_int, fp, ip32, ip32, ip32, POINTER(ctypes.c_uint8)]
@@ -1308,12 +1314,13 @@ class Engine:
         self._check(lib().wt_dbg_last_alignment(self._h, int(clip), _ip32(dims), _ip64(row), _fp(W), _fp(C), _ip32(jump)))
         return dict(n_a=n_a, L=L, N=N, F=F, heads=heads, T=T, row=row, W=W, C=C, jump=jump)
 
-    def dbg_align_scores(self, qp, E, head, slot, F, W, pos0=0, mode=1):
+    def dbg_align_scores(self, qp, E, head, slot, F, W, pos0=0, mode=1, bf16=False):
         """align_scores (k_align.hip): qp [np][batch][H * d] absorbed queries of one pass, E [batch]
         [T][d] encoder output, head / slot the layer's alignment heads and their places in W's head axis, F [batch]
         valid frames; W [batch][heads_total][L_max][ld] is the output buffer as given (in / out).  Returns the buffer
         with W[b][slot][pos0 + p][t < T] = softmax over t < F[b] of q'_head(p, b) . e_t written into it.  mode: 0 = the
-        fused kernel, 1 = frame chunks and the row softmax kernel."""
+        fused kernel, 1 = frame chunks and the row softmax kernel.  bf16: the bf16 form (option full_bf16_all), E a float32
+        array of bf16 values (anything else is rounded to nearest even on the host)."""
         qp, E, W = _f32(qp), _f32(E), _f32(W).copy()
         n_pos, batch, hd = qp.shape
         T, d = E.shape[1], E.shape[2]
@@ -1321,10 +1328,17 @@ class Engine:
         F = np.ascontiguousarray(F, dtype=np.int32)
         assert E.shape[0] == batch and hd == (d // 64) * d and W.shape[0] == batch and W.ndim == 4
         assert head.shape == slot.shape and F.shape == (batch,)
-        self._check(lib().wt_dbg_align_scores(self._h, batch, d // 64, T, n_pos, int(pos0), _fp(qp), _fp(E), head.size,
-                                              _ip32(head), _ip32(slot), W.shape[1], _ip32(F), W.shape[2], W.shape[3],
-                                              _fp(W), int(mode)))
+        fn = lib().wt_dbg_align_scores_bf16 if bf16 else lib().wt_dbg_align_scores
+        self._check(fn(self._h, batch, d // 64, T, n_pos, int(pos0), _fp(qp), _fp(E), head.size, _ip32(head), _ip32(slot),
+                       W.shape[1], _ip32(F), W.shape[2], W.shape[3], _fp(W), int(mode)))
         return W
+
+    def dbg_f32_to_bf16(self, x, out):
+        """launch_f32_to_bf16 (k_misc.hip): x [n] float32 -> a copy of out [n + guard] (float32 holding bf16 values) with
+        the first n cells = x rounded to bf16, to nearest even."""
+        x, out = _f32(x).ravel(), _f32(out).ravel().copy()
+        self._check(lib().wt_dbg_f32_to_bf16(self._h, x.size, out.size - x.size, _fp(x), _fp(out)))
+        return out
 
     def dbg_align_matrix(self, W, L, F, n_a, N_max=None, C=None, stats=None):
         """The two stage kernels of the alignment (k_align.hip): W [clips][heads][L_max][ld]
@@ -1480,15 +1494,16 @@ class Engine:
         self._check(fn(self._h, B, d // 64, cap, pos, npos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out)))
         return out, kcache, vcache
 
-    def dbg_self_attention_long_ragged(self, qkv, kcache, vcache, pos, start, P):
-        """self_attention_long under a slot count: clip b at position pos - start[b], void outside [0, P)."""
+    def dbg_self_attention_long_ragged(self, qkv, kcache, vcache, pos, start, P, bf16=False):
+        """self_attention_long under a slot count: clip b at position pos - start[b], void outside [0, P).  bf16: the bf16
+        form (option full_bf16_all), caches of bf16-representable values."""
         qkv, kcache, vcache = _f32(qkv), _f32(kcache).copy(), _f32(vcache).copy()
         start = np.ascontiguousarray(start, np.int32)
         B, cap, d = kcache.shape
         assert start.shape == (B,)
         out = np.full((B, d), np.nan, np.float32)
-        self._check(lib().wt_dbg_self_attention_long_ragged(self._h, B, d // 64, cap, pos, _fp(qkv), _fp(kcache), _fp(vcache),
-                                                            _fp(out), _ip32(start), P))
+        fn = lib().wt_dbg_self_attention_long_ragged_bf16 if bf16 else lib().wt_dbg_self_attention_long_ragged
+        self._check(fn(self._h, B, d // 64, cap, pos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out), _ip32(start), P))
         return out, kcache, vcache
 
     def dbg_self_attention_long_gather(self, qkv, kcache, vcache, pos, anc, bf16=False):
@@ -1504,15 +1519,16 @@ class Engine:
                        anc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
         return out, kcache, vcache
 
-    def dbg_self_attention_prefill_ragged(self, qkv, kcache, vcache, pos, npos, start, P):
-        """self_attention_prefill under a slot count: query p of clip b at position pos + p - start[b], void outside [0, P)."""
+    def dbg_self_attention_prefill_ragged(self, qkv, kcache, vcache, pos, npos, start, P, bf16=False):
+        """self_attention_prefill under a slot count: query p of clip b at position pos + p - start[b], void outside [0, P).
+        bf16: the bf16 form (option full_bf16_all), caches of bf16-representable values."""
         qkv, kcache, vcache = _f32(qkv), _f32(kcache).copy(), _f32(vcache).copy()
         start = np.ascontiguousarray(start, np.int32)
         B, cap, d = kcache.shape
         assert start.shape == (B,)
         out = np.full((npos * B, d), np.nan, np.float32)
-        self._check(lib().wt_dbg_self_attention_prefill_ragged(self._h, B, d // 64, cap, pos, npos, _fp(qkv), _fp(kcache),
-                                                               _fp(vcache), _fp(out), _ip32(start), P))
+        fn = lib().wt_dbg_self_attention_prefill_ragged_bf16 if bf16 else lib().wt_dbg_self_attention_prefill_ragged
+        self._check(fn(self._h, B, d // 64, cap, pos, npos, _fp(qkv), _fp(kcache), _fp(vcache), _fp(out), _ip32(start), P))
         return out, kcache, vcache
 
     def dbg_dec_ln_gemm_ragged(self, W, bias, ln_g, ln_b, ids, pos, pos_start, tok_emb, pos_emb, gelu=False):

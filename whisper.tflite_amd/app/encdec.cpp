@@ -35,6 +35,8 @@ void usage(const char* argv0) {
             << "                  with --max-positions: full-length beam search, with or without --timestamps and --scores\n"
             << "  --bf16          the bf16 storage mode (option bf16): bf16 weights, activations and caches, fp32 accumulation\n"
             << "                  with --max-positions: full-length decoding in that mode (option full_bf16)\n"
+            << "                  with --max-positions and --inputs a,b --long, --lang auto or --word-timestamps: these too\n"
+            << "                  (option full_bf16_all)\n"
             << "  --max-positions N  full-length greedy decoding over N positions, 32 .. n_text_ctx (default: the\n"
             << "                  reference's 31 positions)\n"
             << "  --timestamps    with --max-positions: decode with timestamps and print one line per segment,\n"
@@ -235,6 +237,12 @@ int main(int argc, char* argv[]) {
     }
     // --bf16 with --max-positions: full-length decoding in the bf16 storage mode (the library's default refuses it)
     if (bf16 && n > 0 && wt_engine_set_option(encdec.handle(), "full_bf16", 1) != WT_OK) {
+      std::cerr << "--bf16 with --max-positions: " << wt_last_error(encdec.handle()) << "\n";
+      return 105;
+    }
+    // ... and with --inputs, --lang auto or --word-timestamps: the rest of the full-length chains in that mode
+    if (bf16 && n > 0 && ((!inputs.empty() && long_audio) || lang == "auto" || word_timestamps) &&
+        wt_engine_set_option(encdec.handle(), "full_bf16_all", 1) != WT_OK) {
       std::cerr << "--bf16 with --max-positions: " << wt_last_error(encdec.handle()) << "\n";
       return 105;
     }

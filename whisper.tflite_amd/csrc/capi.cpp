@@ -301,6 +301,10 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
     // full-length decoding in the bf16 storage mode: 0 = such a call is refused, 1 = it runs
     if (value < 0 || value > 1) return fail(h, WT_ERR_INVALID_ARG, "full_bf16 must be 0 or 1");
     e.full_bf16 = value;
+  } else if (k == "full_bf16_all") {
+    // contexts, batched seeking, automatic language and word timestamps in that mode: 0 = refused
+    if (value < 0 || value > 1) return fail(h, WT_ERR_INVALID_ARG, "full_bf16_all must be 0 or 1");
+    e.full_bf16_all = value;
   } else if (k == "full_language") {
     // automatic language behind max_positions: 0 = such a call is refused, 1 = detected per clip
     if (value < 0 || value > 1) return fail(h, WT_ERR_INVALID_ARG, "full_language must be 0 or 1");
@@ -433,6 +437,7 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "full_beam") *value = e.full_beam;
   else if (k == "full_language") *value = e.full_language;
   else if (k == "full_bf16") *value = e.full_bf16;
+  else if (k == "full_bf16_all") *value = e.full_bf16_all;
   else if (k == "task") *value = e.task;
   else if (k == "language_candidates") *value = long(e.language_candidates.size());
   else if (k == "kernel_timers") *value = e.kernel_timers;
@@ -927,7 +932,7 @@ int wt_transcribe_long_batch(wt_engine* h, const float* const* pcm, const size_t
     e.require_idle();
     e.check_timestamp_call();  // before anything is enqueued
     e.check_full_call();
-    if (e.bf16 && e.max_positions > 0) throw wt::Error(WT_ERR_UNSUPPORTED, "full-length decoding in the bf16 storage mode (full_bf16): not with wt_transcribe_long_batch (the ragged self-attention kernels have no bf16 form)");
+    if (e.bf16 && e.max_positions > 0 && !e.full_bf16_all) throw wt::Error(WT_ERR_UNSUPPORTED, "full-length decoding in the bf16 storage mode (full_bf16): not with wt_transcribe_long_batch (the ragged self-attention kernels have no bf16 form)");
     if (e.best_of_sampling()) throw wt::Error(WT_ERR_UNSUPPORTED, "best_of: not with wt_transcribe_long_batch (contexts and seeking are outside the best-of chain)");
     if (e.beam_fallback()) throw wt::Error(WT_ERR_UNSUPPORTED, "fallback_beam: not with wt_transcribe_long_batch (contexts and seeking are outside the beam chain)");
     wt::transcribe_seek_batch(e, pcm, n_samples, n_files);

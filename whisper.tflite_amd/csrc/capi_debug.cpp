@@ -857,21 +857,31 @@ int wt_dbg_self_attention_prefill_bf16(wt_engine* h, int batch, int heads, int c
                                        float* kcache, float* vcache, float* out) {
   return dbg_self_attention_prefill_impl(h, batch, heads, cap, pos, npos, qkv, kcache, vcache, out, true);
 }
-int wt_dbg_self_attention_long_ragged(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
-                                      float* vcache, float* out, const int32_t* start, int P) {
+static int dbg_self_attention_long_ragged_impl(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv,
+                                               float* kcache, float* vcache, float* out, const int32_t* start, int P, bool bf) {
   if (!h) return WT_ERR_INVALID_ARG;
   return guarded(h, [&] {
-    wt::check_self_attention_long_ragged(cap, pos, P, batch, heads);  // the launcher's own refusals, before anything is allocated
+    // the launcher's own refusals, before anything is allocated
+    if (bf) wt::check_self_attention_long_ragged_bf16(cap, pos, P, batch, heads);
+    else wt::check_self_attention_long_ragged(cap, pos, P, batch, heads);
     if (!qkv || !kcache || !vcache || !out || !start) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_self_attention_long_ragged: NULL array");
     const size_t d = size_t(heads) * 64, nc = size_t(batch) * cap * d;
-    DevArr<float> dq(size_t(batch) * 3 * d, qkv), dk(nc, kcache), dv(nc, vcache), dout(size_t(batch) * d);
+    DevArr<float> dq(size_t(batch) * 3 * d, qkv), dout(size_t(batch) * d);
+    const DbgSelfCaches c(kcache, vcache, nc, bf);
     const DevArr<int> ds(size_t(batch), start);
-    wt::launch_self_attention_long_ragged(dq.p, dk.p, dv.p, cap, pos, ds.p, P, dout.p, batch, heads, h->impl->stream());
+    wt::launch_self_attention_long_ragged(dq.p, c.k(), c.v(), cap, pos, ds.p, P, dout.p, batch, heads, h->impl->stream(), bf);
     h->impl->sync();
     dout.to_host(out, size_t(batch) * d);
-    dk.to_host(kcache, nc);
-    dv.to_host(vcache, nc);
+    c.to_host(kcache, vcache, nc);
   });
+}
+int wt_dbg_self_attention_long_ragged(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
+                                      float* vcache, float* out, const int32_t* start, int P) {
+  return dbg_self_attention_long_ragged_impl(h, batch, heads, cap, pos, qkv, kcache, vcache, out, start, P, false);
+}
+int wt_dbg_self_attention_long_ragged_bf16(wt_engine* h, int batch, int heads, int cap, int pos, const float* qkv, float* kcache,
+                                           float* vcache, float* out, const int32_t* start, int P) {
+  return dbg_self_attention_long_ragged_impl(h, batch, heads, cap, pos, qkv, kcache, vcache, out, start, P, true);
 }
 static int dbg_self_attention_long_gather_impl(wt_engine* h, int rows, int heads, int cap, int pos, const float* qkv,
                                                float* kcache, float* vcache, float* out, const uint8_t* anc, bool bf) {
@@ -899,21 +909,32 @@ int wt_dbg_self_attention_long_gather_bf16(wt_engine* h, int rows, int heads, in
                                            float* vcache, float* out, const uint8_t* anc) {
   return dbg_self_attention_long_gather_impl(h, rows, heads, cap, pos, qkv, kcache, vcache, out, anc, true);
 }
-int wt_dbg_self_attention_prefill_ragged(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
-                                         float* kcache, float* vcache, float* out, const int32_t* start, int P) {
+static int dbg_self_attention_prefill_ragged_impl(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
+                                                  float* kcache, float* vcache, float* out, const int32_t* start, int P, bool bf) {
   if (!h) return WT_ERR_INVALID_ARG;
   return guarded(h, [&] {
-    wt::check_self_attention_prefill_ragged(cap, pos, npos, P, batch, heads);  // the launcher's own refusals, before anything is allocated
+    // the launcher's own refusals, before anything is allocated
+    if (bf) wt::check_self_attention_prefill_ragged_bf16(cap, pos, npos, P, batch, heads);
+    else wt::check_self_attention_prefill_ragged(cap, pos, npos, P, batch, heads);
     if (!qkv || !kcache || !vcache || !out || !start) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_self_attention_prefill_ragged: NULL array");
     const size_t d = size_t(heads) * 64, rows = size_t(npos) * batch, nc = size_t(batch) * cap * d;
-    DevArr<float> dq(rows * 3 * d, qkv), dk(nc, kcache), dv(nc, vcache), dout(rows * d);
+    DevArr<float> dq(rows * 3 * d, qkv), dout(rows * d);
+    const DbgSelfCaches c(kcache, vcache, nc, bf);
     const DevArr<int> ds(size_t(batch), start);
-    wt::launch_self_attention_prefill_ragged(dq.p, dk.p, dv.p, cap, pos, npos, ds.p, P, dout.p, batch, heads, h->impl->stream());
+    wt::launch_self_attention_prefill_ragged(dq.p, c.k(), c.v(), cap, pos, npos, ds.p, P, dout.p, batch, heads,
+                                             h->impl->stream(), bf);
     h->impl->sync();
     dout.to_host(out, rows * d);
-    dk.to_host(kcache, nc);
-    dv.to_host(vcache, nc);
+    c.to_host(kcache, vcache, nc);
   });
+}
+int wt_dbg_self_attention_prefill_ragged(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
+                                         float* kcache, float* vcache, float* out, const int32_t* start, int P) {
+  return dbg_self_attention_prefill_ragged_impl(h, batch, heads, cap, pos, npos, qkv, kcache, vcache, out, start, P, false);
+}
+int wt_dbg_self_attention_prefill_ragged_bf16(wt_engine* h, int batch, int heads, int cap, int pos, int npos, const float* qkv,
+                                              float* kcache, float* vcache, float* out, const int32_t* start, int P) {
+  return dbg_self_attention_prefill_ragged_impl(h, batch, heads, cap, pos, npos, qkv, kcache, vcache, out, start, P, true);
 }
 int wt_dbg_ragged_cap(wt_engine* h, int batch, int pos, int P, const int32_t* start, int32_t* finished) {
   if (!h || batch < 1 || batch > 64 || !start || !finished) return WT_ERR_INVALID_ARG;
@@ -2068,20 +2089,32 @@ int wt_dbg_encoder_attention_at(wt_engine* h, int kind, int variant, int batch, 
   });
 }
 
-int wt_dbg_align_scores(wt_engine* h, int batch, int H, int T, int np, int pos0, const float* qp, const float* E, int n_heads,
-                        const int32_t* head, const int32_t* slot, int heads_total, const int32_t* F, int L_max, int ld, float* W,
-                        int mode) {
+int wt_dbg_f32_to_bf16(wt_engine* h, int n, int guard, const float* x, float* out) {
+  if (!h || !x || !out || n < 1 || guard < 0) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    const DevArr<float> dx(size_t(n), x);
+    const DevBf16 dy(out, size_t(n) + size_t(guard), 0);  // as given: the guard cells must come back untouched
+    wt::launch_f32_to_bf16(dx.p, dy.ptr(), long(n), h->impl->stream());
+    h->impl->sync();
+    dy.to_host(out, size_t(n) + size_t(guard));
+  });
+}
+
+static int dbg_align_scores_impl(wt_engine* h, int batch, int H, int T, int np, int pos0, const float* qp, const float* E,
+                                 int n_heads, const int32_t* head, const int32_t* slot, int heads_total, const int32_t* F,
+                                 int L_max, int ld, float* W, int mode, bool bf) {
   if (!h || !qp || !E || !head || !slot || !F || !W || batch < 1 || batch > wt::kAlignClipsMax || H < 1 || T < 1 || np < 1 ||
       n_heads < 0 || n_heads > wt::kAlignLayerHeadsMax || heads_total < 1 || L_max < 1 || ld < 1) {
     return WT_ERR_INVALID_ARG;
   }
   return guarded(h, [&] {
     const size_t d = size_t(H) * 64, ne = size_t(batch) * T * d;
-    const float se = wt::f16_scale_for(max_abs(E, ne));
-    const DevArr<unsigned short> dE(to_f16_planes(E, ne, se, 64));
+    const float se = bf ? 1.0f : wt::f16_scale_for(max_abs(E, ne));
+    const DevArr<unsigned short> dE(bf ? to_bf16(E, ne, 64) : to_f16_planes(E, ne, se, 64));  // (bf16: ONE plane)
     DevArr<float> dq(size_t(np) * batch * H * d, qp), dW(size_t(batch) * heads_total * L_max * ld, W);
     wt::AlignScoresArgs a;
-    a.qp = dq.p; a.e = dE.p; a.e_plane = long(ne + 64); a.e_scale = se;
+    a.qp = dq.p; a.e = dE.p; a.bf16 = bf;
+    if (!bf) a.e_plane = long(ne + 64), a.e_scale = se;
     a.batch = batch; a.H = H; a.d_model = int(d); a.T = T; a.np = np; a.pos0 = pos0; a.n_heads = n_heads;
     for (int i = 0; i < n_heads; ++i) a.head[i] = head[i], a.slot[i] = slot[i];
     for (int b = 0; b < batch; ++b) a.F[b] = F[b];
@@ -2090,6 +2123,16 @@ int wt_dbg_align_scores(wt_engine* h, int batch, int H, int T, int np, int pos0,
     h->impl->sync();
     dW.to_host(W);
   });
+}
+int wt_dbg_align_scores(wt_engine* h, int batch, int H, int T, int np, int pos0, const float* qp, const float* E, int n_heads,
+                        const int32_t* head, const int32_t* slot, int heads_total, const int32_t* F, int L_max, int ld, float* W,
+                        int mode) {
+  return dbg_align_scores_impl(h, batch, H, T, np, pos0, qp, E, n_heads, head, slot, heads_total, F, L_max, ld, W, mode, false);
+}
+int wt_dbg_align_scores_bf16(wt_engine* h, int batch, int H, int T, int np, int pos0, const float* qp, const float* E, int n_heads,
+                             const int32_t* head, const int32_t* slot, int heads_total, const int32_t* F, int L_max, int ld,
+                             float* W, int mode) {
+  return dbg_align_scores_impl(h, batch, H, T, np, pos0, qp, E, n_heads, head, slot, heads_total, F, L_max, ld, W, mode, true);
 }
 
 int wt_dbg_align_matrix(wt_engine* h, int clips, int heads, int L_max, int ld, int n_a, int N_max, const float* W,

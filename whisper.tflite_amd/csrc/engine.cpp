@@ -2034,12 +2034,10 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
       if (p.self_anc) {  // full-length beam search: the hypotheses share one cache through their ancestor tables
         launch_self_attention_long_gather(dw.qkvd, kc, vc, p.self_cap, p.pos0, p.self_anc, dw.attd, B, H, st, bf);
       } else if (p.pos_start && p.self_prefill) {  // the ragged chain: prompt slots, then one generated slot per pass
-        // (fp32 caches only: check_full_call refuses per-clip contexts in the bf16 storage mode before anything is enqueued)
-        launch_self_attention_prefill_ragged(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0, p.np,
-                                             p.pos_start, p.pos_limit, dw.attd, B, H, st);
+        launch_self_attention_prefill_ragged(dw.qkvd, kc, vc, p.self_cap, p.pos0, p.np, p.pos_start, p.pos_limit, dw.attd, B, H,
+                                             st, bf);
       } else if (p.pos_start) {
-        launch_self_attention_long_ragged(dw.qkvd, static_cast<float*>(kc), static_cast<float*>(vc), p.self_cap, p.pos0,
-                                          p.pos_start, p.pos_limit, dw.attd, B, H, st);
+        launch_self_attention_long_ragged(dw.qkvd, kc, vc, p.self_cap, p.pos0, p.pos_start, p.pos_limit, dw.attd, B, H, st, bf);
       } else if (p.self_prefill) {  // np positions of a prompt behind a context
         launch_self_attention_prefill(dw.qkvd, kc, vc, p.self_cap, p.pos0, p.np, dw.attd, B, H, st, bf);
       } else if (p.self_long) {  // one position past 32 (full-length decoding)
@@ -2070,7 +2068,7 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
       if (p.align && !p.align->layer[size_t(l)].empty()) {  // word timestamps: keep this layer's alignment heads' weights
         const AlignSink& sk = *p.align;
         AlignScoresArgs as;
-        as.qp = dw.qp; as.e = p.e; as.e_plane = long(ws_.batch) * T * d; as.e_scale = cross_kv_.sc.a;
+        as.qp = dw.qp; as.e = p.e; as.e_plane = long(ws_.batch) * T * d; as.e_scale = cross_kv_.sc.a; as.bf16 = bf;
         as.batch = p.clips; as.H = H; as.d_model = d; as.T = T; as.np = p.np; as.pos0 = p.pos0;
         as.n_heads = int(sk.layer[size_t(l)].size());
         for (int i = 0; i < as.n_heads; ++i) as.head[i] = sk.layer[size_t(l)][size_t(i)].first, as.slot[i] = sk.layer[size_t(l)][size_t(i)].second;

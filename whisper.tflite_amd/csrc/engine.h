@@ -217,8 +217,14 @@ class Engine {
   // refused.  1: the three full-length chains (decode_full, beam_full_chains, the best-of chain) run with bf16 weights,
   // bf16 cross-attention operands and a bf16 self-attention cache (the first half of the fp32 allocation), on the bf16
   // forms of self_attention_long, its gathered form and self_attention_prefill.  Scope: full-length decoding's, and no
-  // word_timestamps, per-clip contexts, batched seeking or automatic language (check_full_call).
+  // word_timestamps, per-clip contexts, batched seeking or automatic language (check_full_call) unless full_bf16_all is set.
   long full_bf16 = 0;
+  // The rest of the full-length chains in the bf16 storage mode; means something only with bf16 = 1,
+  // full_bf16 = 1 and max_positions > 0.  0: per-clip contexts (and wt_transcribe_long_batch), language = -1 and
+  // word_timestamps are refused there, as under full_bf16 alone.  1: they run — the ragged bf16 forms of
+  // self_attention_long and self_attention_prefill, the detecting chain and the detect_language pre-pass on bf16 weights,
+  // and the alignment pass on the bf16 form of align_scores over the ONE bf16 plane of the encoder output.
+  long full_bf16_all = 0;
   bool auto_full() const { return full_language != 0 && language < 0 && max_positions > 0; }
   // the long loops' per-clip prompt language of the next full-length calls, with the probability it was detected
   // with: clip b is decoded behind language clip_lang_hold[b] (>= 0) and nothing is detected for it; empty: detect all

@@ -139,7 +139,7 @@ void Engine::check_full_call() const {
   auto no = [](const char* why) { throw Error(kErrUnsupported, std::string("full-length decoding (max_positions): ") + why); };
   if (beam_size > 1 && !full_beam) no("greedy only, not with beam search (beam_size > 1) unless the option full_beam = 1 is set");
   if (bf16 && !full_bf16) no("not in the bf16 storage mode unless the option full_bf16 = 1 is set");
-  if (bf16) {  // full_bf16 = 1: what the bf16 chains do not run
+  if (bf16 && !full_bf16_all) {  // full_bf16 = 1 alone: what stays refused until full_bf16_all = 1 (DESIGN sections 33, 34)
     auto nf = [](const char* why) { throw Error(kErrUnsupported, std::string("full-length decoding in the bf16 storage mode (full_bf16): ") + why); };
     if (word_timestamps) nf("not with word_timestamps (the alignment pass reads the fp16 planes of the encoder output)");
     if (!clip_contexts.empty()) nf("not with per-clip contexts (the ragged self-attention kernels have no bf16 form)");
@@ -1175,7 +1175,9 @@ void Engine::align_words(int batch, const std::vector<Segment>& segs, const std:
   for (int b = 0; b < batch; ++b) aw_.h_lfn[b] = clips[size_t(b)].L, aw_.h_lfn[64 + b] = clips[size_t(b)].F, aw_.h_lfn[128 + b] = clips[size_t(b)].N;
   HIPCHK(hipMemcpyAsync(aw_.lfn, aw_.h_lfn, size_t(3) * 64 * sizeof(int), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(fw_.ids, fw_.h_ids, size_t(batch) * stride * sizeof(long long), hipMemcpyHostToDevice, st));
-  if (!slot.absorbed) {  // the decode ran the cached form: the planes the absorbed form reads, from the fp32 encoder output
+  if (!slot.absorbed && bf16) {  // the decode ran the cached form: the ONE bf16 plane the bf16 absorbed form reads
+    launch_f32_to_bf16(ws_.enc_out, slot.e_planes, long(batch) * T * d, st);
+  } else if (!slot.absorbed) {  // the planes the absorbed form reads, from the fp32 encoder output
     launch_f32_to_planes(ws_.enc_out, slot.e_planes, long(ws_.batch) * T * d, long(batch) * T, d, &cross_kv_.sc.a, 0, st);
   }
   AlignSink sink;
@@ -1191,6 +1193,7 @@ void Engine::align_words(int batch, const std::vector<Segment>& segs, const std:
     p.B = p.clips = nb; p.ids = fw_.ids + size_t(c0) * stride; p.ids_stride = stride; p.self_kv = fw_.kv; p.self_cap = cap;
     p.absorbed = true; p.n_abs = abs_chunks_for(nb, 256); p.e = slot.e_planes + size_t(c0) * T * d;
     p.split = fc2_split(); p.dw = &dw; p.self_prefill = true; p.align = &sink; p.best = nullptr;
+    p.bf = bf16 != 0;  // option full_bf16_all: the decode's own bf16 weights and cache (the first half of fw_.kv)
     const int group = std::max(1, kDecRowsMax / nb);
     for (int pos0 = 0; pos0 < L_max; pos0 += group) {
       p.pos0 = pos0; p.np = std::min(group, L_max - pos0);

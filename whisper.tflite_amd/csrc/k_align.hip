@@ -18,6 +18,7 @@ namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using half8 = __attribute__((ext_vector_type(8))) _Float16;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 struct AlignScoresDev {
@@ -44,7 +45,11 @@ struct AlignScoresDev {
 // FUSED = false (AlignScoresArgs::mode 1): the frames are cut into chunks of tiles_per_chunk tiles, one block each
 // (blockIdx.z), so that a launch fills the chip whatever the number of columns; the kernel stores the scaled scores only
 // and align_softmax_rows, one wavefront per row, turns them into weights.
-template <int DM, bool FUSED>
+// BF (bf16 storage mode, option full_bf16_all): E is the ONE bf16 plane the bf16 encoder leaves for
+// the absorbed cross-attention (a.e points at it, e_plane and e_scale are not read), q' is rounded to bf16 in registers
+// and a 32-column step is one v_mfma_f32_16x16x32_bf16, the score product of cross_absorbed_attention<DM, 3, true>: no
+// operand scale, bf16 has the fp32 range.  Columns, tiles, chunks, maxima, sums and the zeros are as above.
+template <int DM, bool FUSED, bool BF = false>
 __global__ __launch_bounds__(256) void align_scores(AlignScoresDev a) {
   constexpr int KS = DM / 32;
   const int b = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -58,9 +63,20 @@ __global__ __launch_bounds__(256) void align_scores(AlignScoresDev a) {
   const int F = a.F[b];
 
   // ---- Q' planes of this lane's column: power-of-two scale from the column's largest element (k_cross_absorbed.hip)
-  u32x4 qh[KS], ql[KS];
+  u32x4 qh[KS], ql[BF ? 1 : KS];  // (BF: one plane of q', no lo plane)
+  (void)ql;
   float s_inv;
-  {
+  if constexpr (BF) {
+    const float* src = a.qp + ((long)p * a.B + b) * (long)(a.H * DM) + a.head[hi] * DM + 8 * lq;
+    const float keep = q_ok ? 1.0f : 0.0f;
+    s_inv = 1.0f;
+#pragma unroll
+    for (int c = 0; c < KS; ++c) {
+      const f32x4 v0 = *reinterpret_cast<const f32x4*>(src + 32 * c), v1 = *reinterpret_cast<const f32x4*>(src + 32 * c + 4);
+      qh[c] = u32x4{pack_bf16x2(v0[0] * keep, v0[1] * keep), pack_bf16x2(v0[2] * keep, v0[3] * keep),
+                    pack_bf16x2(v1[0] * keep, v1[1] * keep), pack_bf16x2(v1[2] * keep, v1[3] * keep)};
+    }
+  } else {
     const float* src = a.qp + ((long)p * a.B + b) * (long)(a.H * DM) + a.head[hi] * DM + 8 * lq;
     const float keep = q_ok ? 1.0f : 0.0f;
     float mx = 0.0f;
@@ -99,11 +115,16 @@ __global__ __launch_bounds__(256) void align_scores(AlignScoresDev a) {
     f32x4 sp = {0, 0, 0, 0};
 #pragma unroll
     for (int c = 0; c < KS; ++c) {
-      const half8 eh = *reinterpret_cast<const half8*>(er + 32 * c);
-      const half8 el = *reinterpret_cast<const half8*>(er + a.e_plane + 32 * c);
-      sp = __builtin_amdgcn_mfma_f32_16x16x32_f16(eh, __builtin_bit_cast(half8, ql[c]), sp, 0, 0, 0);
-      sp = __builtin_amdgcn_mfma_f32_16x16x32_f16(el, __builtin_bit_cast(half8, qh[c]), sp, 0, 0, 0);
-      sp = __builtin_amdgcn_mfma_f32_16x16x32_f16(eh, __builtin_bit_cast(half8, qh[c]), sp, 0, 0, 0);
+      if constexpr (BF) {  // eight bf16 of the one plane: 16 bytes, as a lane's share of an fp16 plane
+        const u32x4 eb = *reinterpret_cast<const u32x4*>(er + 32 * c);
+        sp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, eb), __builtin_bit_cast(bf16x8, qh[c]), sp, 0, 0, 0);
+      } else {
+        const half8 eh = *reinterpret_cast<const half8*>(er + 32 * c);
+        const half8 el = *reinterpret_cast<const half8*>(er + a.e_plane + 32 * c);
+        sp = __builtin_amdgcn_mfma_f32_16x16x32_f16(eh, __builtin_bit_cast(half8, ql[c]), sp, 0, 0, 0);
+        sp = __builtin_amdgcn_mfma_f32_16x16x32_f16(el, __builtin_bit_cast(half8, qh[c]), sp, 0, 0, 0);
+        sp = __builtin_amdgcn_mfma_f32_16x16x32_f16(eh, __builtin_bit_cast(half8, qh[c]), sp, 0, 0, 0);
+      }
     }
     // register r of this lane: frame 16 kt + 4 lq + r, column qc
     const int t0 = 16 * kt + 4 * lq;
@@ -176,14 +197,14 @@ __global__ __launch_bounds__(64) void align_softmax_rows(AlignScoresDev a) {
   }
 }
 
-template <int DM>
+template <int DM, bool BF = false>
 void launch_scores(const AlignScoresDev& g, bool fused, hipStream_t s) {
   const unsigned cols = unsigned((g.n_heads * g.np + 63) / 64);
   if (fused) {
-    hipLaunchKernelGGL((align_scores<DM, true>), dim3(cols, g.B), dim3(256), 0, s, g);
+    hipLaunchKernelGGL((align_scores<DM, true, BF>), dim3(cols, g.B), dim3(256), 0, s, g);
   } else {
     const int n_tiles = (g.T + 15) / 16;
-    hipLaunchKernelGGL((align_scores<DM, false>), dim3(cols, g.B, (n_tiles + g.tiles_per_chunk - 1) / g.tiles_per_chunk), dim3(256), 0, s, g);
+    hipLaunchKernelGGL((align_scores<DM, false, BF>), dim3(cols, g.B, (n_tiles + g.tiles_per_chunk - 1) / g.tiles_per_chunk), dim3(256), 0, s, g);
     hipLaunchKernelGGL(align_softmax_rows, dim3(g.np, g.n_heads, g.B), dim3(64), 0, s, g);
   }
 }
@@ -336,8 +357,9 @@ void launch_align_scores(const AlignScoresArgs& a, hipStream_t s) {
   bool ok = a.qp && a.e && a.W && a.batch >= 1 && a.batch <= kAlignClipsMax && a.H >= 1 && a.H * 64 == dm && a.T >= 4 &&
             a.T <= kAlignFramesMax && a.T % 4 == 0 && a.np >= 1 && (long)a.np * a.batch <= 128 && a.pos0 >= 0 && a.L_max >= 1 &&
             a.pos0 + a.np <= a.L_max && a.n_heads >= 1 && a.n_heads <= kAlignLayerHeadsMax && a.n_heads <= a.H &&
-            a.heads_total >= 1 && a.heads_total <= kAlignHeadsMax && a.ldw >= a.T && a.ldw % 4 == 0 && a.e_scale > 0.0f &&
-            a.e_plane >= (long)a.batch * a.T * dm && a.e_plane % 8 == 0;
+            a.heads_total >= 1 && a.heads_total <= kAlignHeadsMax && a.ldw >= a.T && a.ldw % 4 == 0;
+  // (bf16: one plane, no operand scale: e_plane and e_scale are not read)
+  ok = ok && (a.bf16 || (a.e_scale > 0.0f && a.e_plane >= (long)a.batch * a.T * dm && a.e_plane % 8 == 0));
   ok = ok && (a.mode == 0 || a.mode == 1);
   for (int i = 0; ok && i < a.n_heads; ++i) {
     ok = a.head[i] >= 0 && a.head[i] < a.H && a.slot[i] >= 0 && a.slot[i] < a.heads_total;
@@ -346,15 +368,16 @@ void launch_align_scores(const AlignScoresArgs& a, hipStream_t s) {
   for (int b = 0; ok && b < a.batch; ++b) ok = a.F[b] >= 1 && a.F[b] <= a.T;
   if (!ok) throw Error(kErrInvalidArg, "alignment scores: shape outside the kernel contract");
   AlignScoresDev g{};
-  g.qp = a.qp, g.e = reinterpret_cast<const _Float16*>(a.e), g.e_plane = a.e_plane, g.e_scale = a.e_scale, g.W = a.W;
+  g.qp = a.qp, g.e = reinterpret_cast<const _Float16*>(a.e), g.W = a.W;
+  g.e_plane = a.bf16 ? 0 : a.e_plane, g.e_scale = a.bf16 ? 1.0f : a.e_scale;
   g.B = a.batch, g.H = a.H, g.T = a.T, g.np = a.np, g.pos0 = a.pos0, g.n_heads = a.n_heads, g.heads_total = a.heads_total;
   g.L_max = a.L_max, g.ldw = a.ldw, g.tiles_per_chunk = kAlignChunkTiles;
   for (int i = 0; i < a.n_heads; ++i) g.head[i] = a.head[i], g.slot[i] = a.slot[i];
   for (int b = 0; b < a.batch; ++b) g.F[b] = a.F[b];
   switch (dm) {
-    case 128: launch_scores<128>(g, a.mode == 0, s); break;
-    case 384: launch_scores<384>(g, a.mode == 0, s); break;
-    case 512: launch_scores<512>(g, a.mode == 0, s); break;
+    case 128: a.bf16 ? launch_scores<128, true>(g, a.mode == 0, s) : launch_scores<128>(g, a.mode == 0, s); break;
+    case 384: a.bf16 ? launch_scores<384, true>(g, a.mode == 0, s) : launch_scores<384>(g, a.mode == 0, s); break;
+    case 512: a.bf16 ? launch_scores<512, true>(g, a.mode == 0, s) : launch_scores<512>(g, a.mode == 0, s); break;
     default: throw Error(kErrInvalidArg, "alignment scores: d_model 128, 384 or 512");
   }
 }

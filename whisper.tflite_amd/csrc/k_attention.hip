@@ -566,6 +566,8 @@ __global__ void self_attention_step(const float* __restrict__ qkv, void* __restr
 // The groups, their keys and the order of every sum are the fp32 kernel's.  The new k and v are rounded (to nearest
 // even) before they are scored and before they are stored: a row contributes the same values whether it was just
 // computed or read back, here or in self_attention_step<true>, which writes rows 0 .. 31 of the same cache.
+// RAGGED and BF together (option full_bf16_all): the head below only shifts `pos`, so a live clip
+// runs the bf16 form at its own position, bit for bit, and a void clip touches no cache row.
 template <bool BF>
 struct SelfCache {  // the element of a self-attention cache row, and a lane's four elements of a key as they are loaded
   using elem = float;
@@ -1201,10 +1203,23 @@ void check_self_attention_long_ragged(int cap, int pos, int P, int batch, int he
   if (P < 1 || P > cap) throw Error(kErrInvalidArg, "decoder self-attention (long cache, ragged): position limit outside [1, cap]");
 }
 
-void launch_self_attention_long_ragged(const float* qkv, float* kcache, float* vcache, int cap, int pos, const int* start,
-                                       int P, float* out, int batch, int heads, hipStream_t s) {
+void check_self_attention_long_ragged_bf16(int cap, int pos, int P, int batch, int heads) {
   check_self_attention_long_ragged(cap, pos, P, batch, heads);
+}
+
+void launch_self_attention_long_ragged(const float* qkv, void* kcache_v, void* vcache_v, int cap, int pos, const int* start,
+                                       int P, float* out, int batch, int heads, hipStream_t s, bool bf16) {
+  if (bf16) check_self_attention_long_ragged_bf16(cap, pos, P, batch, heads);
+  else check_self_attention_long_ragged(cap, pos, P, batch, heads);
   if (!start) throw Error(kErrInvalidArg, "decoder self-attention (long cache, ragged): no start array");
+  if (bf16) {
+    hipLaunchKernelGGL((self_attention_long<true, false, true>), dim3(batch * heads), dim3(256), 0, s, qkv,
+                       static_cast<unsigned short*>(kcache_v), static_cast<unsigned short*>(vcache_v), cap, pos, out, heads,
+                       start, P, static_cast<const unsigned char*>(nullptr), 0);
+    return;
+  }
+  float* const kcache = static_cast<float*>(kcache_v);
+  float* const vcache = static_cast<float*>(vcache_v);
   hipLaunchKernelGGL((self_attention_long<true, false>), dim3(batch * heads), dim3(256), 0, s, qkv, kcache, vcache, cap, pos, out,
                      heads, start, P, static_cast<const unsigned char*>(nullptr), 0);
 }
@@ -1214,11 +1229,24 @@ void check_self_attention_prefill_ragged(int cap, int pos0, int np, int P, int b
   if (P < 1 || P > cap) throw Error(kErrInvalidArg, "decoder self-attention (prefill, ragged): position limit outside [1, cap]");
 }
 
-void launch_self_attention_prefill_ragged(const float* qkv, float* kcache, float* vcache, int cap, int pos0, int np,
-                                          const int* start, int P, float* out, int batch, int heads, hipStream_t s) {
+void check_self_attention_prefill_ragged_bf16(int cap, int pos0, int np, int P, int batch, int heads) {
   check_self_attention_prefill_ragged(cap, pos0, np, P, batch, heads);
+}
+
+void launch_self_attention_prefill_ragged(const float* qkv, void* kcache_v, void* vcache_v, int cap, int pos0, int np,
+                                          const int* start, int P, float* out, int batch, int heads, hipStream_t s, bool bf16) {
+  if (bf16) check_self_attention_prefill_ragged_bf16(cap, pos0, np, P, batch, heads);
+  else check_self_attention_prefill_ragged(cap, pos0, np, P, batch, heads);
   if (!start) throw Error(kErrInvalidArg, "decoder self-attention (prefill, ragged): no start array");
   const int qblocks = (np + kPrefillQ - 1) / kPrefillQ;
+  if (bf16) {
+    hipLaunchKernelGGL((self_attention_prefill<true, true>), dim3(batch * heads * qblocks), dim3(256), 0, s, qkv,
+                       static_cast<unsigned short*>(kcache_v), static_cast<unsigned short*>(vcache_v), cap, pos0, np, batch, out,
+                       heads, start, P);
+    return;
+  }
+  float* const kcache = static_cast<float*>(kcache_v);
+  float* const vcache = static_cast<float*>(vcache_v);
   hipLaunchKernelGGL((self_attention_prefill<true, false>), dim3(batch * heads * qblocks), dim3(256), 0, s, qkv, kcache, vcache, cap,
                      pos0, np, batch, out, heads, start, P);
 }

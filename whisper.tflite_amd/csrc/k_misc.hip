@@ -146,6 +146,16 @@ __global__ __launch_bounds__(256) void f32_to_planes(const float* __restrict__ x
   }
 }
 
+// fp32 -> one bf16 plane (bf16 storage mode): round to nearest even, four elements = one 8-byte store per thread and step
+__global__ __launch_bounds__(256) void f32_to_bf16(const float* __restrict__ x, unsigned short* __restrict__ y, long n4) {
+  using f32x4 = __attribute__((ext_vector_type(4))) float;
+  using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * i);
+    *reinterpret_cast<u32x2*>(y + 4 * i) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+  }
+}
+
 // PCM -> planes for the STFT-as-GEMM (Engine::logmel): the clip's samples, clamped to the bound the scale was chosen for
 __global__ __launch_bounds__(256) void pcm_to_planes(const float* __restrict__ x, _Float16* __restrict__ yp, long plane, float scale,
                                                      float limit, long n4_per_clip, long out_stride, long total4) {
@@ -596,6 +606,13 @@ void launch_f32_to_planes(const float* x, unsigned short* yp, long plane, long M
   const long n4 = M * ld / 4;
   const unsigned blocks = (unsigned)std::min<long>((n4 + 255) / 256, 256 * 32);
   hipLaunchKernelGGL(f32_to_planes, dim3(blocks), dim3(256), 0, s, x, reinterpret_cast<_Float16*>(yp), plane, sc, seg, ld, n4);
+}
+
+void launch_f32_to_bf16(const float* x, unsigned short* y, long n, hipStream_t s) {
+  if (!x || !y || n < 4 || n % 4 != 0) throw Error(kErrInvalidArg, "f32_to_bf16: bad shape");
+  const long n4 = n / 4;
+  const unsigned blocks = (unsigned)std::min<long>((n4 + 255) / 256, 256 * 32);
+  hipLaunchKernelGGL(f32_to_bf16, dim3(blocks), dim3(256), 0, s, x, y, n4);
 }
 
 void launch_pcm_to_planes(const float* pcm, unsigned short* yp, long plane, float scale, float limit, int batch, long n,

@@ -231,6 +231,9 @@ void launch_layernorm_planes(const float* x, unsigned short* yp, long plane, flo
 // the operand hand-over between a contraction on the fp32-storage fall-back kernels and one on the plane kernels
 void launch_f32_to_planes(const float* x, unsigned short* yp, long plane, long M, int ld, const float* scales, int seg,
                           hipStream_t s);
+// fp32 [n] -> ONE bf16 plane [n], round to nearest even (n % 4 == 0; 8-byte packed stores): what the bf16 form of
+// align_scores reads when the decode ran the cached cross-attention form
+void launch_f32_to_bf16(const float* x, unsigned short* y, long n, hipStream_t s);
 // probe kernel of Engine::create_streams: one wavefront busy for `microseconds` (k_misc.hip)
 void launch_spin(int microseconds, hipStream_t s);
 // PCM [batch][n] fp32 -> fp16 planes of clamp(x, -limit, limit) * scale, [batch][out_stride] (columns >= n untouched:
@@ -316,12 +319,18 @@ void launch_self_attention_prefill(const float* qkv, void* kcache, void* vcache,
 // (start: device [B]) and runs there exactly as above; a position outside [0, min(P, cap)) is void — zeros in `out`, no
 // cache row read or written.  The refusals are those above, except that self_attention_long's slot may lie past the
 // cache (below 2 x kSelfLongCap); P outside [1, cap] and a null `start` are refused too.
+// bf16 (option full_bf16_all): the caches hold bf16 elements as in the unragged bf16 forms, and a live
+// clip's output and cache rows are those forms' at its own position, bit for bit.  The _bf16 checks refuse exactly what
+// the fp32 checks refuse.
 void check_self_attention_long_ragged(int cap, int pos, int P, int batch, int heads);
-void launch_self_attention_long_ragged(const float* qkv, float* kcache, float* vcache, int cap, int pos, const int* start,
-                                       int P, float* out, int batch, int heads, hipStream_t s);
+void check_self_attention_long_ragged_bf16(int cap, int pos, int P, int batch, int heads);
+void launch_self_attention_long_ragged(const float* qkv, void* kcache, void* vcache, int cap, int pos, const int* start,
+                                       int P, float* out, int batch, int heads, hipStream_t s, bool bf16 = false);
 void check_self_attention_prefill_ragged(int cap, int pos0, int np, int P, int batch, int heads);
-void launch_self_attention_prefill_ragged(const float* qkv, float* kcache, float* vcache, int cap, int pos0, int np,
-                                          const int* start, int P, float* out, int batch, int heads, hipStream_t s);
+void check_self_attention_prefill_ragged_bf16(int cap, int pos0, int np, int P, int batch, int heads);
+void launch_self_attention_prefill_ragged(const float* qkv, void* kcache, void* vcache, int cap, int pos0, int np,
+                                          const int* start, int P, float* out, int batch, int heads, hipStream_t s,
+                                          bool bf16 = false);
 // The gathered form of self_attention_long: `rows` <= kSelfGatherRows rows share the cache
 // [rows][cap][d], and row r reads key k < pos from cache row min(anc[r][k], rows - 1) (anc: device [rows][cap] bytes;
 // entries at k >= pos are not read).  Key pos is appended to row r itself and out rows are r, as above; with
@@ -708,6 +717,9 @@ struct AlignScoresArgs {
   const unsigned short* e = nullptr;  // E as fp16 planes [batch][T][d_model]: hi at e, lo at e + e_plane, times e_scale
   long e_plane = 0;
   float e_scale = 1.0f;
+  // bf16 storage mode (option full_bf16_all): e is ONE bf16 plane [batch][T][d_model], q' is rounded to
+  // bf16 in the kernel; e_plane and e_scale are not read
+  bool bf16 = false;
   int batch = 0, H = 0, d_model = 0, T = 0;  // T % 4 == 0
   int np = 0, pos0 = 0;            // the pass holds the fed positions pos0 .. pos0 + np - 1; np * batch <= 128
   int n_heads = 0;                 // alignment heads of this layer
