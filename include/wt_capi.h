@@ -494,6 +494,41 @@ const char* wt_lang_code(int id);
 /* wav_util.cpp:18-87 wav_read_legacy: *n gets the sample count (WT_ERR_IO when the reference
  * would return an empty vector); at most cap samples are written. */
 int wt_wav_read_legacy(const char* path, float* out, size_t cap, size_t* n);
+/* A plain RIFF / WAVE reader: walks the chunks to "fmt " and "data"; PCM16 and IEEE float32 (WAVE_FORMAT_EXTENSIBLE
+ * included), any channel count and rate.  `out` (may be NULL) gets at most cap_bytes bytes of the interleaved samples as
+ * the file holds them; *format WT_PCM_S16 or WT_PCM_F32, *n_frames the frames in the file.  WT_ERR_IO / WT_ERR_FORMAT. */
+int wt_wav_read(const char* path, void* out, size_t cap_bytes, int32_t* format, int32_t* channels, int32_t* rate,
+                size_t* n_frames);
+
+/* ---- input resampling: any rate to WT_SAMPLE_RATE on the device ------------------------------
+ * With R : 16000 = orig : new in lowest terms, lpw = 6, base = 0.99 min(orig, new), w = ceil(lpw orig / base) and
+ * K = 2 w + orig, the filter is h[p][k] = sinc(pi t) cos^2(pi t / (2 lpw)) base / orig at
+ * t = clamp(((k - w) / orig - p / new) base, -lpw, lpw), and y[i new + p] = sum_k h[p][k] x[i orig + k - w] with x zero
+ * outside its n frames and ceil(new n / orig) outputs: the Hann-windowed sinc resampler.  Samples are interleaved,
+ * 1..8 channels, float32 or int16 taken as v / 32768; the channels are averaged before the filter, and the values are
+ * clamped to +-32 as the front end clamps them.  A rate with orig or new above 1024 (or below 1) is WT_ERR_INVALID_ARG;
+ * R = 16000 averages and converts only.
+ * Options "input_sample_rate" (default 16000), "input_channels" (default 1) and "input_format" (default WT_PCM_F32): with
+ * any of them off its default, wt_transcribe_pcm, wt_transcribe_long_pcm, wt_transcribe_long_batch and
+ * wt_detect_language_pcm read their pcm argument as that description and n_samples as frames, resample every recording
+ * once, first, and then run as they do today on the 16 kHz result: window times, seeks and word timestamps are in
+ * output time.  Nothing else reads the options: wt_transcribe_file takes its samples from the legacy reader, 16 kHz. */
+#define WT_PCM_F32 0
+#define WT_PCM_S16 1
+/* out[0..6] = orig, new, w, K, and the kernel's geometry G, K', TM (rows of G input blocks, the row window padded to
+ * K' = a multiple of 32, TM rows per block); no GPU */
+int wt_resample_plan(int rate, int32_t out[7]);
+/* the float64 filter [new][K]; WT_ERR_BUFFER when cap (in doubles) is too small; no GPU */
+int wt_resample_filter(int rate, double* h, size_t cap);
+int wt_resample_len(int rate, size_t n_frames, size_t* n_out);
+/* host to host through the device: *n_out = wt_resample_len; WT_ERR_BUFFER when cap (in floats) is smaller */
+int wt_resample_pcm(wt_engine* h, const void* pcm, int format, int channels, int rate, size_t n_frames, float* out, size_t cap,
+                    size_t* n_out);
+/* device buffers: clip b's frames at d_in + b x in_stride_frames frames, its output at d_out + b x out_stride floats
+ * (wt_resample_len of them, nothing else is written); synchronous.  What feeds wt_pipeline_submit_pcm_dev and
+ * wt_transcribe_tokens_batch_dev from 30 s clips at another rate (out_stride = WT_CHUNK_SAMPLES). */
+int wt_resample_batch_dev(wt_engine* h, const void* d_in, int format, int channels, int rate, size_t n_frames, int batch,
+                          size_t in_stride_frames, float* d_out, size_t out_stride);
 /* token ids the engine uses: out[0..8] = n_vocab, eot, sot, translate, transcribe, prev,
  * solm, not, beg (whisper.h:69-91 after whisper.cpp:218-226). */
 int wt_vocab_info(const wt_engine* h, int32_t out[9]);

@@ -56,7 +56,9 @@ CAPI_SYMBOLS = [
     "wt_vocab_info", "wt_filters", "wt_write_synthetic_weights", "wt_write_synthetic_vocab",
     "wt_vocab_open", "wt_vocab_close", "wt_vocab_get_info", "wt_vocab_get_filters", "wt_vocab_size", "wt_vocab_token",
     "wt_vocab_decode", "wt_log_mel_spectrogram", "wt_convert_tflite", "wt_shutdown",
+    "wt_wav_read", "wt_resample_plan", "wt_resample_filter", "wt_resample_len", "wt_resample_pcm", "wt_resample_batch_dev",
 ]
+WT_PCM_F32, WT_PCM_S16 = 0, 1
 DEBUG_SYMBOLS = [
     "wt_dbg_cross_absorbed", "wt_dbg_cross_absorbed_bf16", "wt_dbg_gemm_planes_ln", "wt_dbg_gemm", "wt_dbg_gemm_bench", "wt_dbg_dec_gemm_bench", "wt_dbg_dec_gemm", "wt_dbg_dec_ln_gemm", "wt_dbg_layernorm", "wt_dbg_encoder_attention",
     "wt_dbg_cross_attention", "wt_dbg_self_attention", "wt_dbg_interference", "wt_dbg_concurrency",
@@ -183,6 +185,12 @@ def lib() -> ctypes.CDLL:
         L.wt_lang_code.argtypes = [c_int]
         L.wt_lang_code.restype = c_char_p
         L.wt_wav_read_legacy.argtypes = [c_char_p, fp, c_size_t, POINTER(c_size_t)]
+        L.wt_wav_read.argtypes = [c_char_p, c_void_p, c_size_t, ip32, ip32, ip32, POINTER(c_size_t)]
+        L.wt_resample_plan.argtypes = [c_int, ip32]
+        L.wt_resample_filter.argtypes = [c_int, POINTER(ctypes.c_double), c_size_t]
+        L.wt_resample_len.argtypes = [c_int, c_size_t, POINTER(c_size_t)]
+        L.wt_resample_pcm.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_size_t, fp, c_size_t, POINTER(c_size_t)]
+        L.wt_resample_batch_dev.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_size_t, c_int, c_size_t, c_void_p, c_size_t]
         L.wt_vocab_info.argtypes = [c_void_p, ip32]
         L.wt_filters.argtypes = [c_void_p, fp, c_size_t, ip32, ip32]
         L.wt_write_synthetic_weights.argtypes = [c_char_p, c_char_p, c_uint64]
@@ -436,6 +444,46 @@ def wav_read_legacy(path: str) -> np.ndarray:
     return out
 
 
+def _host_check(rc: int) -> None:
+    if rc != WT_OK:
+        raise WtError(rc, lib().wt_last_error(None).decode())
+
+
+def wav_read(path):
+    """wt_wav_read: (samples [frames][channels] int16 or float32 as the file holds them, rate)."""
+    fmt, ch, rate, n = c_int32(0), c_int32(0), c_int32(0), c_size_t(0)
+    _host_check(lib().wt_wav_read(os.fsencode(path), None, 0, byref(fmt), byref(ch), byref(rate), byref(n)))
+    out = np.zeros((n.value, ch.value), np.int16 if fmt.value == WT_PCM_S16 else np.float32)
+    _host_check(lib().wt_wav_read(os.fsencode(path), out.ctypes.data_as(c_void_p), out.nbytes, byref(fmt), byref(ch), byref(rate), byref(n)))
+    return out, rate.value
+
+
+def resample_plan(rate: int) -> dict:
+    """wt_resample_plan: orig, new, w, K of the rate's filter and the kernel's G, Kp, TM; no GPU."""
+    v = np.zeros(7, np.int32)
+    _host_check(lib().wt_resample_plan(int(rate), _ip32(v)))
+    return dict(zip(("orig", "new", "w", "K", "G", "Kp", "TM"), (int(x) for x in v)))
+
+
+def resample_filter(rate: int) -> np.ndarray:
+    """wt_resample_filter: the float64 filter [new][K]; no GPU."""
+    p = resample_plan(rate)
+    h = np.zeros((p["new"], p["K"]), np.float64)
+    _host_check(lib().wt_resample_filter(int(rate), h.ctypes.data_as(POINTER(ctypes.c_double)), h.size))
+    return h
+
+
+def resample_len(rate: int, n_frames: int) -> int:
+    n = c_size_t(0)
+    _host_check(lib().wt_resample_len(int(rate), int(n_frames), byref(n)))
+    return n.value
+
+
+def _frames(samples, fmt, channels):
+    """interleaved PCM as [frames][channels] of the format's dtype (a 1-D array: mono, or already interleaved)"""
+    return np.ascontiguousarray(samples, dtype=np.int16 if fmt == WT_PCM_S16 else np.float32).reshape(-1, channels)
+
+
 # one time-stamped segment (wt_segment, DESIGN.md section 14): the text ids row[id_begin : id_begin + id_count] of clip
 # `clip`, spoken from t0_ms to t1_ms; open = the text ran to the end of the row without a closing timestamp
 SEGMENT_DTYPE = np.dtype([(k, np.int32) for k in ("clip", "t0_ms", "t1_ms", "id_begin", "id_count", "open")])
@@ -654,6 +702,36 @@ class Engine:
         self._check(lib().wt_engine_get_option(self._h, key.encode(), byref(v)))
         return v.value
 
+    def _pcm_in(self, samples):
+        """(array kept alive, pointer, count) for the PCM entry points: float32 samples at the defaults; with the options
+        input_channels / input_format set, interleaved frames of that description and their number"""
+        fmt, ch = self.get_option("input_format"), self.get_option("input_channels")
+        if fmt == WT_PCM_F32 and ch == 1:
+            pcm = _f32(samples).reshape(-1)
+            return pcm, _fp(pcm), pcm.size
+        a = _frames(samples, fmt, ch)
+        return a, ctypes.cast(a.ctypes.data, POINTER(c_float)), a.shape[0]
+
+    def resample(self, samples, rate, channels=None) -> np.ndarray:
+        """wt_resample_pcm: samples [frames] or [frames][channels], int16 (taken as v / 32768) or float, at `rate` Hz ->
+        float32 at 16 kHz mono, on the device."""
+        a = np.asarray(samples)
+        fmt = WT_PCM_S16 if a.dtype == np.int16 else WT_PCM_F32
+        if channels is None:
+            channels = a.shape[1] if a.ndim == 2 else 1
+        a = _frames(a, fmt, channels)
+        out = np.zeros(resample_len(rate, a.shape[0]), np.float32)
+        n = c_size_t(0)
+        self._check(lib().wt_resample_pcm(self._h, a.ctypes.data_as(c_void_p), fmt, channels, int(rate), a.shape[0], _fp(out),
+                                          out.size, byref(n)))
+        return out
+
+    def resample_batch_dev(self, d_in_ptr, fmt, channels, rate, n_frames, batch, in_stride, d_out_ptr, out_stride) -> None:
+        """wt_resample_batch_dev on caller-owned device buffers (device_array): clip b at d_in + b x in_stride frames ->
+        resample_len(rate, n_frames) floats at d_out + b x out_stride."""
+        self._check(lib().wt_resample_batch_dev(self._h, c_void_p(d_in_ptr), int(fmt), int(channels), int(rate), int(n_frames),
+                                                int(batch), int(in_stride), c_void_p(d_out_ptr), int(out_stride)))
+
     def set_prompt(self, ids) -> None:
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
         self._check(lib().wt_engine_set_prompt(self._h, ids.ctypes.data_as(POINTER(c_int64)), ids.size))
@@ -723,27 +801,27 @@ class Engine:
             path = os.fsencode(samples_or_path)
             self._check(lib().wt_transcribe_file(self._h, path, buf, len(buf), byref(n)))
         else:
-            pcm = _f32(samples_or_path).reshape(-1)
-            self._check(lib().wt_transcribe_pcm(self._h, _fp(pcm), pcm.size, buf, len(buf), byref(n)))
+            keep, ptr, count = self._pcm_in(samples_or_path)
+            self._check(lib().wt_transcribe_pcm(self._h, ptr, count, buf, len(buf), byref(n)))
         return buf.raw[: n.value].decode("utf-8", errors="replace")
 
     def transcribe_long(self, samples) -> str:
         """Long audio: consecutive 30 s windows, batched; per-window texts joined with '\\n'.  Option seek = 1: one window
         at a time, each starting at the last closed timestamp of the one before."""
-        pcm = _f32(samples).reshape(-1)
+        keep, ptr, count = self._pcm_in(samples)
         buf = ctypes.create_string_buffer(1 << 20)
         n = c_size_t(0)
-        self._check(lib().wt_transcribe_long_pcm(self._h, _fp(pcm), pcm.size, buf, len(buf), byref(n)))
+        self._check(lib().wt_transcribe_long_pcm(self._h, ptr, count, buf, len(buf), byref(n)))
         return buf.raw[: n.value].decode("utf-8", errors="replace")
 
     def transcribe_long_batch(self, samples_list) -> list:
         """Seeking transcription of several recordings side by side: one window of every file per decoder chain (options
         as for transcribe_long with seek = 1).  Returns the per-file texts, each what transcribe_long
         gives for that file alone; last_windows() lists the windows file by file, last_window_files() is parallel to it."""
-        pcms = [_f32(s).reshape(-1) for s in samples_list]
+        pcms = [self._pcm_in(s) for s in samples_list]
         n = len(pcms)
-        ptrs = (POINTER(c_float) * max(n, 1))(*[_fp(p) if p.size else None for p in pcms])
-        sizes = (c_size_t * max(n, 1))(*[p.size for p in pcms])
+        ptrs = (POINTER(c_float) * max(n, 1))(*[p[1] if p[2] else None for p in pcms])
+        sizes = (c_size_t * max(n, 1))(*[p[2] for p in pcms])
         self._check(lib().wt_transcribe_long_batch(self._h, ptrs, sizes, n))
         texts = []
         for f in range(n):
@@ -974,9 +1052,9 @@ class Engine:
 
     def detect_language_pcm(self, samples):
         """One clip of PCM (padded or truncated to one window): (lang, probability)."""
-        pcm = _f32(samples).reshape(-1)
+        keep, ptr, count = self._pcm_in(samples)
         lang, prob = c_int32(0), c_float(0)
-        self._check(lib().wt_detect_language_pcm(self._h, _fp(pcm), pcm.size, byref(lang), byref(prob)))
+        self._check(lib().wt_detect_language_pcm(self._h, ptr, count, byref(lang), byref(prob)))
         return lang.value, prob.value
 
     def last_languages(self):

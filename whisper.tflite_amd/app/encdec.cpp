@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <memory>
 #include <string>
@@ -64,14 +65,32 @@ void usage(const char* argv0) {
             << "  --word-timestamps  with --timestamps: align every word to the audio and print, behind the segment lines,\n"
             << "                  one line per word: t0 t1 text (seconds)\n"
             << "  --alignment-heads 2:2,3:0,...  with --word-timestamps: the layer:head pairs to align on (default: every\n"
-            << "                  head of the upper half of the decoder layers)\n";
+            << "                  head of the upper half of the decoder layers)\n"
+            << "  --resample      read --input / --inputs as plain RIFF files of any rate, 1..8 channels, PCM16 or float32, and\n"
+            << "                  resample them to 16 kHz mono on the device, each by its own header\n";
+}
+
+// --resample: the file's samples as it holds them, read in one pass (the file's length bounds its data chunk)
+struct RawWav {
+  std::vector<unsigned char> bytes;
+  size_t frames = 0;
+  int32_t format = 0, channels = 0, rate = 0;
+};
+bool read_raw_wav(const std::string& path, RawWav* out) {
+  std::ifstream f(path, std::ios::binary | std::ios::ate);
+  out->bytes.resize(f.is_open() && f.tellg() > 0 ? size_t(f.tellg()) : 0);
+  if (wt_wav_read(path.c_str(), out->bytes.data(), out->bytes.size(), &out->format, &out->channels, &out->rate, &out->frames) != WT_OK) {
+    std::cerr << "--resample: " << wt_last_error(nullptr) << "\n";
+    return false;
+  }
+  return true;
 }
 }  // namespace
 
 int main(int argc, char* argv[]) {
   std::string model_prefix, vocab, input, inputs, lang, languages, task, beam, max_positions, temperature, seed, best_of, cr_threshold, context_ids, alignment_heads,
       suppress_tokens;
-  bool word_timestamps = false, suppress_default = false, suppress_blank = false;
+  bool word_timestamps = false, suppress_default = false, suppress_blank = false, resample = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
        no_condition = false, bf16 = false;
   for (int i = 1; i < argc; ++i) {
@@ -82,6 +101,10 @@ int main(int argc, char* argv[]) {
     }
     if (a == "--long") {
       long_audio = true;
+      continue;
+    }
+    if (a == "--resample") {
+      resample = true;
       continue;
     }
     if (a == "--english") {
@@ -471,7 +494,27 @@ int main(int argc, char* argv[]) {
     std::vector<std::vector<float>> pcms;
     std::vector<const float*> ptrs;
     std::vector<size_t> sizes;
-    for (const std::string& path : paths) pcms.push_back(wav_read_legacy(path.c_str()));
+    for (const std::string& path : paths) {
+      if (!resample) {
+        pcms.push_back(wav_read_legacy(path.c_str()));
+        continue;
+      }
+      // the engine's input options hold for a whole call, the files may differ: each is resampled by its own header
+      // here, and the call below runs at the defaults
+      RawWav raw;
+      size_t n16 = 0;
+      if (!read_raw_wav(path, &raw)) return 1;
+      if (wt_resample_len(raw.rate, raw.frames, &n16) != WT_OK) {
+        std::cerr << "--resample: " << path << ": " << wt_last_error(nullptr) << "\n";
+        return 1;
+      }
+      pcms.emplace_back(n16);
+      if (wt_resample_pcm(encdec.handle(), raw.bytes.data(), raw.format, raw.channels, raw.rate, raw.frames, pcms.back().data(), n16,
+                          &n16) != WT_OK) {
+        std::cerr << "--resample: " << path << ": " << wt_last_error(encdec.handle()) << "\n";
+        return 1;
+      }
+    }
     for (const std::vector<float>& x : pcms) ptrs.push_back(x.data()), sizes.push_back(x.size());
     if (wt_transcribe_long_batch(encdec.handle(), ptrs.data(), sizes.data(), int(paths.size())) != WT_OK) {
       std::cerr << "transcribe failed: " << wt_last_error(encdec.handle()) << "\n";
@@ -501,7 +544,25 @@ int main(int argc, char* argv[]) {
     return 0;
   }
   std::string text;
-  if (long_audio) {
+  if (resample) {
+    RawWav raw;
+    if (!read_raw_wav(input, &raw)) return 1;
+    if (wt_engine_set_option(encdec.handle(), "input_sample_rate", raw.rate) != WT_OK ||
+        wt_engine_set_option(encdec.handle(), "input_channels", raw.channels) != WT_OK ||
+        wt_engine_set_option(encdec.handle(), "input_format", raw.format) != WT_OK) {
+      std::cerr << "--resample: " << input << ": " << wt_last_error(encdec.handle()) << "\n";
+      return 1;
+    }
+    std::vector<char> buf(1 << 20);
+    size_t len = 0;
+    const float* pcm = reinterpret_cast<const float*>(raw.bytes.data());
+    if ((long_audio ? wt_transcribe_long_pcm(encdec.handle(), pcm, raw.frames, buf.data(), buf.size(), &len)
+                    : wt_transcribe_pcm(encdec.handle(), pcm, raw.frames, buf.data(), buf.size(), &len)) != WT_OK) {
+      std::cerr << "transcribe failed: " << wt_last_error(encdec.handle()) << "\n";
+      return 1;
+    }
+    text.assign(buf.data(), len);
+  } else if (long_audio) {
     std::vector<float> pcm = wav_read_legacy(input.c_str());
     std::vector<char> buf(1 << 20);
     size_t len = 0;

@@ -46,6 +46,16 @@ int copy_text(const std::string& s, char* out, size_t cap, size_t* len) {
 }
 
 // the token calls with rows of WT_MAX_IDS ids cannot return a full-length decode
+// Options input_sample_rate / input_channels / input_format off their defaults: `pcm` holds n_frames interleaved frames
+// of that description; *y gets the recording at 16 kHz mono, resampled on the device
+int resample_input(wt_engine* h, const void* pcm, size_t n_frames, std::vector<float>* y) {
+  return guarded(h, [&] {
+    wt::Engine& e = *h->impl;
+    e.require_idle();
+    *y = e.resample_host(pcm, int(e.input_format), int(e.input_channels), int(e.input_sample_rate), n_frames);
+  });
+}
+
 void refuse_fixed_rows(const wt::Engine& e) {
   e.check_timestamp_call();
   if (e.max_positions > 0) {
@@ -337,6 +347,20 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
     } catch (const std::exception& err) {
       return fail(h, WT_ERR_DEVICE, err.what());
     }
+  } else if (k == "input_sample_rate") {
+    // input resampling: what the pcm of the PCM entry points holds
+    try {
+      (void)wt::resample_len(int(std::min<long>(std::max<long>(value, 0), 1L << 30)), 0);
+    } catch (const wt::Error& err) {
+      return fail(h, err.code, err.what());
+    }
+    e.input_sample_rate = value;
+  } else if (k == "input_channels") {
+    if (value < 1 || value > wt::kResampleChannelsMax) return fail(h, WT_ERR_INVALID_ARG, "input_channels must be in [1, 8]");
+    e.input_channels = value;
+  } else if (k == "input_format") {
+    if (value != WT_PCM_F32 && value != WT_PCM_S16) return fail(h, WT_ERR_INVALID_ARG, "input_format must be WT_PCM_F32 or WT_PCM_S16");
+    e.input_format = value;
   } else {
     return fail(h, WT_ERR_INVALID_ARG, "unknown option: " + k);
   }
@@ -439,6 +463,9 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "full_bf16") *value = e.full_bf16;
   else if (k == "full_bf16_all") *value = e.full_bf16_all;
   else if (k == "task") *value = e.task;
+  else if (k == "input_sample_rate") *value = e.input_sample_rate;
+  else if (k == "input_channels") *value = e.input_channels;
+  else if (k == "input_format") *value = e.input_format;
   else if (k == "language_candidates") *value = long(e.language_candidates.size());
   else if (k == "kernel_timers") *value = e.kernel_timers;
   else if (k == "fc2_ksplit") *value = e.fc2_ksplit;
@@ -853,6 +880,18 @@ int wt_detect_language_batch(wt_engine* h, const float* mel, int batch, int32_t*
 
 int wt_detect_language_pcm(wt_engine* h, const float* pcm, size_t n_samples, int32_t* lang, float* prob) {
   if (!h || (!pcm && n_samples) || !lang) return WT_ERR_INVALID_ARG;
+  if (h->impl->input_is_default()) return detect_language_pcm16k(h, pcm, n_samples, lang, prob);
+  std::vector<float> rs;
+  const int rc = resample_input(h, pcm, n_samples, &rs);
+  return rc != WT_OK ? rc : detect_language_pcm16k(h, rs.data(), rs.size(), lang, prob);
+}
+
+}  // extern "C"
+
+// wt_detect_language_pcm on 16 kHz mono float samples, whatever the input options say: what the public entry point runs
+// after its resampling, and what the callers inside the library that hold such samples call (whisper_api.cpp)
+int detect_language_pcm16k(wt_engine* h, const float* pcm, size_t n_samples, int32_t* lang, float* prob) {
+  if (!h || (!pcm && n_samples) || !lang) return WT_ERR_INVALID_ARG;
   return guarded(h, [&] {
     wt::Engine& e = *h->impl;
     e.require_idle();
@@ -866,6 +905,8 @@ int wt_detect_language_pcm(wt_engine* h, const float* pcm, size_t n_samples, int
     e.sync();
   });
 }
+
+extern "C" {
 
 int wt_last_languages(const wt_engine* h, int32_t* lang, float* prob, int cap) {
   if (!h || cap < 0 || (cap > 0 && (!lang || !prob))) return -WT_ERR_INVALID_ARG;
@@ -898,6 +939,23 @@ int wt_last_kernel_stats(const wt_engine* h, wt_kernel_stat* out, int cap) {
 int wt_transcribe_pcm(wt_engine* h, const float* pcm, size_t n_samples, char* out, size_t cap,
                       size_t* len) {
   if (!h || (!pcm && n_samples)) return WT_ERR_INVALID_ARG;
+  if (h->impl->input_is_default()) return transcribe_pcm16k(h, pcm, n_samples, out, cap, len);
+  std::vector<float> rs;
+  const int rc = resample_input(h, pcm, n_samples, &rs);
+  if (rc != WT_OK) {
+    if (len) *len = 0;
+    if (out && cap) out[0] = 0;
+    return rc;
+  }
+  return transcribe_pcm16k(h, rs.data(), rs.size(), out, cap, len);
+}
+
+}  // extern "C"
+
+// wt_transcribe_pcm on 16 kHz mono float samples, whatever the input options say (as detect_language_pcm16k): also
+// wt_transcribe_file's decode, whose samples come from the legacy reader
+int transcribe_pcm16k(wt_engine* h, const float* pcm, size_t n_samples, char* out, size_t cap, size_t* len) {
+  if (!h || (!pcm && n_samples)) return WT_ERR_INVALID_ARG;
   std::string text;
   const int rc = guarded(h, [&] {
     wt::Engine& e = *h->impl;
@@ -925,8 +983,25 @@ int wt_transcribe_pcm(wt_engine* h, const float* pcm, size_t n_samples, char* ou
   return copy_text(text, out, cap, len);
 }
 
+extern "C" {
+
 int wt_transcribe_long_batch(wt_engine* h, const float* const* pcm, const size_t* n_samples, int n_files) {
   if (!h || !pcm || !n_samples) return WT_ERR_INVALID_ARG;
+  std::vector<std::vector<float>> rs;  // every recording once, before anything else
+  std::vector<const float*> rs_pcm;
+  std::vector<size_t> rs_n;
+  if (!h->impl->input_is_default() && n_files >= 1 && n_files <= 64) {
+    rs.resize(size_t(n_files));
+    for (int i = 0; i < n_files; ++i) {
+      if (!pcm[i] && n_samples[i]) return WT_ERR_INVALID_ARG;
+      const int rc = resample_input(h, pcm[i], n_samples[i], &rs[size_t(i)]);
+      if (rc != WT_OK) return rc;
+      rs_pcm.push_back(rs[size_t(i)].data());
+      rs_n.push_back(rs[size_t(i)].size());
+    }
+    pcm = rs_pcm.data();
+    n_samples = rs_n.data();
+  }
   return guarded(h, [&] {
     wt::Engine& e = *h->impl;
     e.require_idle();
@@ -949,6 +1024,17 @@ int wt_last_file_text(const wt_engine* h, int file, char* out, size_t cap, size_
 int wt_transcribe_long_pcm(wt_engine* h, const float* pcm, size_t n_samples, char* out, size_t cap,
                            size_t* len) {
   if (!h || (!pcm && n_samples)) return WT_ERR_INVALID_ARG;
+  std::vector<float> rs;
+  if (!h->impl->input_is_default()) {
+    const int rc = resample_input(h, pcm, n_samples, &rs);
+    if (rc != WT_OK) {
+      if (len) *len = 0;
+      if (out && cap) out[0] = 0;
+      return rc;
+    }
+    pcm = rs.data();
+    n_samples = rs.size();
+  }
   std::string text;
   const int rc = guarded(h, [&] {
     wt::Engine& e = *h->impl;
@@ -972,7 +1058,7 @@ int wt_transcribe_file(wt_engine* h, const char* wav_path, char* out, size_t cap
   // an unreadable WAV yields an empty vector in the reference and is then padded to 30 s
   // of silence (whisper.cpp:772-773); same here
   (void)wt::wav_read_legacy(wav_path, &pcm, h->impl->verbose != 0);
-  return wt_transcribe_pcm(h, pcm.data(), pcm.size(), out, cap, len);
+  return transcribe_pcm16k(h, pcm.data(), pcm.size(), out, cap, len);  // the reader's samples, not the caller's pcm
 }
 
 // -------------------------------------------------------------- helpers ---
@@ -1004,6 +1090,70 @@ int wt_wav_read_legacy(const char* path, float* out, size_t cap, size_t* n) {
   *n = s.size();
   if (out) std::memcpy(out, s.data(), std::min(cap, s.size()) * sizeof(float));
   return WT_OK;
+}
+
+int wt_wav_read(const char* path, void* out, size_t cap_bytes, int32_t* format, int32_t* channels, int32_t* rate,
+                size_t* n_frames) {
+  if (!path || !n_frames) return WT_ERR_INVALID_ARG;
+  *n_frames = 0;
+  return guarded(nullptr, [&] {
+    const wt::WavData wv = wt::wav_read(path);
+    if (format) *format = wv.format;
+    if (channels) *channels = wv.channels;
+    if (rate) *rate = wv.rate;
+    *n_frames = wv.n_frames;
+    if (out) std::memcpy(out, wv.bytes.data(), std::min(cap_bytes, wv.bytes.size()));
+  });
+}
+
+// ------------------------------------------------------------ resampler ---
+
+int wt_resample_plan(int rate, int32_t out[7]) {
+  if (!out) return WT_ERR_INVALID_ARG;
+  return guarded(nullptr, [&] {
+    const wt::ResamplePlan p = wt::make_resample_plan(rate, false);
+    const int32_t v[7] = {p.orig, p.nnew, p.w, p.K, p.G, p.Kp, p.TM};
+    std::memcpy(out, v, sizeof(v));
+  });
+}
+
+int wt_resample_filter(int rate, double* h, size_t cap) {
+  return guarded(nullptr, [&] {
+    const wt::ResamplePlan p = wt::make_resample_plan(rate, false);
+    if (!h || cap < p.h.size()) throw wt::Error(WT_ERR_BUFFER, "wt_resample_filter: the filter has new x K = " + std::to_string(p.h.size()) + " taps");
+    std::memcpy(h, p.h.data(), p.h.size() * sizeof(double));
+  });
+}
+
+int wt_resample_len(int rate, size_t n_frames, size_t* n_out) {
+  if (!n_out) return WT_ERR_INVALID_ARG;
+  return guarded(nullptr, [&] { *n_out = wt::resample_len(rate, n_frames); });
+}
+
+int wt_resample_pcm(wt_engine* h, const void* pcm, int format, int channels, int rate, size_t n_frames, float* out, size_t cap,
+                    size_t* n_out) {
+  if (!h || (!pcm && n_frames) || !n_out) return WT_ERR_INVALID_ARG;
+  *n_out = 0;
+  return guarded(h, [&] {
+    wt::Engine& e = *h->impl;
+    e.require_idle();
+    *n_out = wt::resample_len(rate, n_frames);
+    if (*n_out == 0) return;
+    if (!out || cap < *n_out) throw wt::Error(WT_ERR_BUFFER, "wt_resample_pcm: the output has " + std::to_string(*n_out) + " samples");
+    const std::vector<float> y = e.resample_host(pcm, format, channels, rate, n_frames);
+    if (!y.empty()) std::memcpy(out, y.data(), y.size() * sizeof(float));
+  });
+}
+
+int wt_resample_batch_dev(wt_engine* h, const void* d_in, int format, int channels, int rate, size_t n_frames, int batch,
+                          size_t in_stride_frames, float* d_out, size_t out_stride) {
+  if (!h || !d_in || !d_out) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    wt::Engine& e = *h->impl;
+    e.require_idle();
+    e.resample(d_in, format, channels, rate, n_frames, batch, in_stride_frames, d_out, out_stride);
+    e.sync();
+  });
 }
 
 static void vocab_info_of(const wt::VocabData& v, int32_t out[9]);

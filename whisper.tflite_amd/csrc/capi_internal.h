@@ -18,6 +18,13 @@ struct wt_engine {
 // records msg as h's last error (h == nullptr: the calling thread's creation error) and returns code; capi.cpp
 __attribute__((visibility("hidden"))) int fail(wt_engine* h, int code, const std::string& msg);
 
+// wt_transcribe_pcm / wt_detect_language_pcm on 16 kHz mono float samples whatever the options input_sample_rate,
+// input_channels and input_format say: for callers inside the library whose samples are not the caller's pcm; capi.cpp
+__attribute__((visibility("hidden"))) int transcribe_pcm16k(wt_engine* h, const float* pcm, size_t n_samples, char* out, size_t cap,
+                                                            size_t* len);
+__attribute__((visibility("hidden"))) int detect_language_pcm16k(wt_engine* h, const float* pcm, size_t n_samples, int32_t* lang,
+                                                                 float* prob);
+
 // Runs fn, translating every exception into a status code.
 template <class F>
 static int guarded(wt_engine* h, F&& fn) {

@@ -2567,4 +2567,86 @@ void Engine::decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids) 
   last.beam_valid = true;
 }
 
+// ------------------------------------------------------------ resampler ---
+// DESIGN section 35.  The plan of a rate (filter, geometry, band planes) is made and uploaded at the rate's first use
+// and kept; nothing is allocated for an engine that never resamples.
+void Engine::resample(const void* d_in, int format, int channels, int rate, size_t n_frames, int batch, size_t in_stride,
+                      float* d_out, size_t out_stride) {
+  if (!d_in || !d_out) throw Error(kErrInvalidArg, "resample: NULL buffer");
+  if (rate == kResampleRateOut) {
+    launch_pcm_downmix(d_in, format, channels, long(n_frames), batch, long(in_stride), d_out, long(out_stride), stream_);
+    return;
+  }
+  auto it = resample_plans_.find(rate);
+  if (it == resample_plans_.end()) {
+    ResampleDev rd;
+    rd.plan = make_resample_plan(rate);
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, rd.plan.band.size() * sizeof(unsigned short)));
+    allocations_.push_back(p);
+    HIPCHK(hipMemcpy(p, rd.plan.band.data(), rd.plan.band.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
+    rd.band = static_cast<unsigned short*>(p);
+    rd.plan.band = std::vector<unsigned short>();  // the device copy is the one in use
+    it = resample_plans_.emplace(rate, std::move(rd)).first;
+  }
+  const ResamplePlan& p = it->second.plan;
+  ResampleArgs a;
+  a.in = d_in;
+  a.format = format;
+  a.channels = channels;
+  a.batch = batch;
+  a.n_frames = long(n_frames);
+  a.in_stride = long(in_stride);
+  a.out = d_out;
+  a.n_out = long(resample_len(rate, n_frames));
+  a.out_stride = long(out_stride);
+  a.orig = p.orig;
+  a.nnew = p.nnew;
+  a.w = p.w;
+  a.K = p.K;
+  a.G = p.G;
+  a.Kp = p.Kp;
+  a.TM = p.TM;
+  a.RB = p.RB;
+  a.CB = p.CB;
+  a.band = it->second.band;
+  a.band_scale = p.band_scale;
+  a.pcm_scale = f16_scale_for(kPcmBound);
+  a.pcm_limit = kPcmBound;
+  if (a.n_out == 0) return;
+  constexpr long kTilesPerLaunch = 1 << 20;  // far inside the grid limit; an hour at 48 kHz has 14 k tiles
+  const long per_tile = long(p.TM) * p.cols;
+  const long tiles = (a.n_out + per_tile - 1) / per_tile;
+  for (long t0 = 0; t0 < tiles; t0 += kTilesPerLaunch) {
+    a.tile0 = t0;
+    a.tiles = int(std::min(kTilesPerLaunch, tiles - t0));
+    launch_resample(a, stream_);
+  }
+}
+
+std::vector<float> Engine::resample_host(const void* pcm, int format, int channels, int rate, size_t n_frames) {
+  if (format != 0 && format != 1) throw Error(kErrInvalidArg, "resample: format must be WT_PCM_F32 or WT_PCM_S16");
+  if (channels < 1 || channels > kResampleChannelsMax) throw Error(kErrInvalidArg, "resample: channels must be in [1, 8]");
+  std::vector<float> y(resample_len(rate, n_frames));  // refuses the rate before anything is allocated
+  if (y.empty()) return y;
+  const size_t in_bytes = n_frames * size_t(channels) * (format == 1 ? 2 : 4);
+  void *d_in = nullptr, *d_out = nullptr;
+  try {
+    HIPCHK(hipMalloc(&d_in, in_bytes));
+    HIPCHK(hipMalloc(&d_out, y.size() * sizeof(float)));
+    HIPCHK(hipMemcpyAsync(d_in, pcm, in_bytes, hipMemcpyHostToDevice, stream_));
+    resample(d_in, format, channels, rate, n_frames, 1, n_frames, static_cast<float*>(d_out), y.size());
+    HIPCHK(hipMemcpyAsync(y.data(), d_out, y.size() * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    throw;
+  }
+  (void)hipFree(d_in);
+  (void)hipFree(d_out);
+  return y;
+}
+
 }  // namespace wt

@@ -16,6 +16,7 @@
 #include "decode_results.h"
 #include "error.h"
 #include "host_util.h"
+#include "resample.h"
 #include "wtw_format.h"
 
 namespace wt {
@@ -379,6 +380,18 @@ class Engine {
   // seeking loop sets that and aligns each window over the segments seek_step kept.
   void align_words(int batch, const std::vector<Segment>& segs, const std::vector<long long>& valid_samples);
   bool defer_word_alignment = false;
+
+  // Input resampling.  The three options describe the `pcm` of wt_transcribe_pcm, _long_pcm,
+  // _long_batch and wt_detect_language_pcm; at their defaults those calls are what they were.
+  long input_sample_rate = 16000, input_channels = 1, input_format = 0;
+  bool input_is_default() const { return input_sample_rate == 16000 && input_channels == 1 && input_format == 0; }
+  // d_in [batch][in_stride frames][channels] (format 0 fp32, 1 int16) at `rate` Hz -> d_out [batch][out_stride] fp32 at
+  // 16 kHz, resample_len(rate, n_frames) samples per clip; device pointers, async on stream(), outside any graph, in as
+  // many launches as the grid limits need.  rate = 16000: channel mean and conversion only.
+  void resample(const void* d_in, int format, int channels, int rate, size_t n_frames, int batch, size_t in_stride,
+                float* d_out, size_t out_stride);
+  // host interleaved PCM -> host 16 kHz mono, through the device (buffers of this call alone); synchronises stream()
+  std::vector<float> resample_host(const void* pcm, int format, int channels, int rate, size_t n_frames);
 
   int mel_frames() const { return 2 * dims_.n_audio_ctx; }
   size_t mel_elems() const { return size_t(dims_.n_mels) * mel_frames(); }
@@ -839,6 +852,11 @@ class Engine {
     float *mel_stage = nullptr, *pcm_stage = nullptr;
     std::vector<void*> owned;
   } ws_;
+  struct ResampleDev {  // a plan and the device copy of its band planes, uploaded at the rate's first use
+    ResamplePlan plan;
+    unsigned short* band = nullptr;
+  };
+  std::map<int, ResampleDev> resample_plans_;
   // kernel-class timer (events live in the pipeline slot being encoded)
   bool kt_on_ = true;
   long enc_count_ = 0;

@@ -242,6 +242,31 @@ void launch_spin(int microseconds, hipStream_t s);
 void launch_pcm_to_planes(const float* pcm, unsigned short* yp, long plane, float scale, float limit, int batch, long n,
                           long out_stride, hipStream_t s);
 
+// ------------------------------------------------------------- resampler ---
+// k_resample.hip: interleaved PCM at any rate -> 16 kHz mono fp32 in one pass.  Per clip b the frames
+// in + b * in_stride (frames of `channels` samples; format 0 = fp32, 1 = int16 taken as v / 32768) are averaged over the
+// channels, clamped to +-pcm_limit, split into two fp16 planes times pcm_scale in LDS and contracted against the band
+// planes of a ResamplePlan (resample.h) by three v_mfma_f32_16x16x32_f16 per k-tile; out + b * out_stride gets
+// y[0 .. n_out), nothing else is written.  One launch covers the row tiles [tile0, tile0 + tiles) of TM rows each.
+struct ResampleArgs {
+  const void* in = nullptr;
+  int format = 0, channels = 1, batch = 1;
+  long n_frames = 0, in_stride = 0;
+  float* out = nullptr;
+  long n_out = 0, out_stride = 0;
+  int orig = 0, nnew = 0, w = 0, K = 0, G = 1, Kp = 0, TM = 16, RB = 1, CB = 1;  // the plan
+  const unsigned short* band = nullptr;  // device copy of ResamplePlan::band
+  float band_scale = 1.0f, pcm_scale = 1.0f, pcm_limit = 32.0f;
+  long tile0 = 0;
+  int tiles = 0;
+};
+// Throws kErrInvalidArg for a shape outside the kernel's contract (a plan that does not fit the LDS image, strides
+// shorter than the rows, channels outside 1..8, more than 65535 clips), before anything is launched.
+void launch_resample(const ResampleArgs& a, hipStream_t s);
+// The 16 kHz case: out[b][i] = the channel mean of frame i, converted as above, i < n_frames; no filter, no clamp.
+void launch_pcm_downmix(const void* in, int format, int channels, long n_frames, int batch, long in_stride, float* out,
+                        long out_stride, hipStream_t s);
+
 // ------------------------------------------------------ encoder attention ---
 // qkv [B*T][3*d] (q | k | v, heads of 64 inside each third) -> out [B*T][d].
 // Non-causal softmax(q k^T / 8) v per (clip, head), flash-style, on fp32 storage: the forms a layer falls back to

@@ -9,6 +9,7 @@
 #include <iostream>
 #include <stdexcept>
 
+#include "capi_internal.h"
 #include "host_util.h"
 #include "wt_capi.h"
 
@@ -22,15 +23,16 @@ wt_engine* open_engine(int type, const std::string& model_prefix, const std::str
   return h;
 }
 
-// Engine::transcribe(std::vector<float>&) of both engine types (whisper.cpp:752-769, :692-738)
+// Engine::transcribe(std::vector<float>&) of both engine types (whisper.cpp:752-769, :692-738): 16 kHz mono float by the
+// reference's contract, so the options input_* (a description of the C entry points' pcm) are not applied to it
 std::string transcribe_samples(wt_engine* h, std::vector<float>& samples) {
   samples.resize(size_t(kSampleRate) * kChunkSize, 0);  // whisper.cpp:753 mutates the caller's vector
   std::string text(8192, '\0');
   size_t len = 0;
-  int rc = wt_transcribe_pcm(h, samples.data(), samples.size(), &text[0], text.size(), &len);
+  int rc = transcribe_pcm16k(h, samples.data(), samples.size(), &text[0], text.size(), &len);
   if (rc == WT_ERR_BUFFER) {
     text.assign(len + 1, '\0');
-    rc = wt_transcribe_pcm(h, samples.data(), samples.size(), &text[0], text.size(), &len);
+    rc = transcribe_pcm16k(h, samples.data(), samples.size(), &text[0], text.size(), &len);
   }
   if (rc != WT_OK) {
     std::fprintf(stderr, "transcribe failed: %s\n", wt_last_error(h));
@@ -73,7 +75,7 @@ namespace {
 std::pair<int, float> detect_samples(wt_engine* h, const std::vector<float>& samples) {
   int32_t lang = 0;
   float prob = 0.0f;
-  if (wt_detect_language_pcm(h, samples.data(), samples.size(), &lang, &prob) != WT_OK) {
+  if (detect_language_pcm16k(h, samples.data(), samples.size(), &lang, &prob) != WT_OK) {
     throw std::runtime_error(std::string("detect_language: ") + wt_last_error(h));
   }
   return {int(lang), prob};
