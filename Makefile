@@ -11,7 +11,7 @@ OBJ   := $(PKG)/build
 CXXFLAGS := -std=c++17 -O3 -fPIC -Iinclude -I$(SRC) -Wall -Wno-unused-result
 HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH) -ffp-contract=fast $(HIPFLAGS_EXTRA)
 
-KERNELS := k_gemm k_gemm_planes k_gemm_bf16 k_misc k_attention k_attention_planes k_decoder k_cross_absorbed k_beam k_beam_full k_timestamps k_scores k_sample k_align k_suppress k_best_of k_resample
+KERNELS := k_gemm k_gemm_planes k_gemm_bf16 k_misc k_attention k_attention_planes k_decoder k_cross_absorbed k_beam k_beam_full k_timestamps k_scores k_sample k_align k_suppress k_best_of k_resample k_nucleus
 HOSTSRC := engine engine_full decode_results capi capi_debug host_util longform words weights_gen whisper_api tflite_extract resample
 OBJS := $(addprefix $(OBJ)/,$(addsuffix .o,$(KERNELS) $(HOSTSRC)))
 
@@ -25,6 +25,9 @@ oracle:
 # of its row sums) cost more than the scalar ones they replace (MI355X_MICROARCH.md, vector-instruction issue costs): 325.8
 # against 334.2 us per layer (tools/ab_attn.sh)
 $(OBJ)/k_attention_planes.o: HIPFLAGS += -fno-slp-vectorize
+
+# the fixed-point masses of nucleus_cut are products and sums of single floats: no packed fp32 instructions there
+$(OBJ)/k_nucleus.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(OBJ)/%.o: $(SRC)/%.hip $(SRC)/kernels.h $(SRC)/ts_rules.h
 	@mkdir -p $(OBJ)

@@ -429,6 +429,14 @@ int wt_last_decode_info(const wt_engine* h, wt_clip_decode* out, int cap);
  * clips written), or -WT_ERR_INVALID_ARG when no clip of that decode was kept from an attempt that ran N > 1 samples. */
 int wt_last_best_of(const wt_engine* h, int32_t* picked, double* sum_logprob, int32_t* n_generated, int cap);
 
+/* Truncated sampling (options "top_k": 0 = default, off, else 1 .. n_vocab; "top_p": thousandths, 1000 = default, off,
+ * else 1 .. 999; anything else WT_ERR_INVALID_ARG).  Every draw at a temperature above 0 (a fixed
+ * "temperature", the later attempts of "temperature_fallback", every sample of "best_of") is taken from the "top_k"
+ * largest logits the step allows, then from the shortest head of those that holds top_p / 1000 of their probability at
+ * that temperature (equal logits: the larger id first).  The random numbers stay those of the untruncated draw, so a
+ * step whose kept set is everything gives the same id.  Nothing changes at temperature 0 or in beam search; token
+ * log-probabilities, avg_logprob and the fall-back's tests are those of the whole allowed set. */
+
 /* Seeking long-audio transcription (option "seek" = 1 together with "timestamps" = 1 and "max_positions", else a decode
  * call is WT_ERR_UNSUPPORTED).  wt_transcribe_long_pcm then decodes one window at a time as Whisper's
  * transcribe() does: window w is pcm[seek : seek + 480000) zero-padded, decoded as one clip (all decode options apply; its

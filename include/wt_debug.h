@@ -193,6 +193,26 @@ int wt_dbg_sample_select_group(wt_engine* h, int B, int group, int V, const floa
                                int n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
                                const float* temperature, uint64_t seed, int attempt, int clip_base, int row0, int pos,
                                int64_t* token, double* L, float* M, float* key);
+/* nucleus_cut (k_nucleus.hip, options "top_k" / "top_p"): per row the cut of truncated sampling.
+ * logits [rows][V]; the allowed set is the whole vocabulary (timestamps = 0) or what rules 1 .. 4 leave behind the
+ * rows' ids (every row holds n_ids ids, as wt_dbg_sample_select_group takes them).  temperature [rows] > 0 (0: the row
+ * is not cut); top_k <= 0 and top_p outside (0, 1) are off.  cut [rows]: cut = ord(z) << 32 | id of the last id kept
+ * (0: everything), kept = the ids kept, kept_q / total_q = their mass and the allowed set's in units of 2^-40 of the
+ * largest probability.  Needs rows <= 64 and V <= 2^20, else WT_ERR_INVALID_ARG before anything is launched. */
+typedef struct wt_nucleus_cut {
+  uint64_t cut, kept_q, total_q;
+  int32_t kept, pad;
+} wt_nucleus_cut;
+int wt_dbg_nucleus_cut(wt_engine* h, int rows, int V, const float* logits, const int64_t* ids, int ids_stride, int n_ids,
+                       int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp, const float* temperature,
+                       int top_k, float top_p, wt_nucleus_cut* cut);
+/* wt_dbg_sample_select_group behind nucleus_cut: the draw is taken over the ids at or above the row's cut (rule 5 is
+ * decided on all allowed ids; where the class it leaves holds no kept id, the token is that class's largest logit).
+ * cut [B] (optional) receives the rows' cuts. */
+int wt_dbg_sample_select_cut(wt_engine* h, int B, int group, int V, const float* logits, const int64_t* ids, int ids_stride,
+                             int n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
+                             const float* temperature, uint64_t seed, int attempt, int clip_base, int row0, int pos, int top_k,
+                             float top_p, int64_t* token, double* L, float* M, float* key, wt_nucleus_cut* cut);
 /* best_of_begin (k_best_of.hip): the start of a chain over N samples of `clips` clips, rows
  * r = j * clips + c.  All arrays are in / out with N * clips rows: ids [..][stride] (rows c < clips hold the clips' prompts
  * on entry), n_ids, finished, sum (float64), count, anc [..][cap] (bytes); frozen [clips] is optional.  Needs N <= 8,

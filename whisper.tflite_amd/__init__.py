@@ -73,6 +73,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_self_attention_long_ragged", "wt_dbg_self_attention_prefill_ragged", "wt_dbg_dec_ln_gemm_ragged", "wt_dbg_ragged_cap",
     "wt_dbg_timestamp_select", "wt_dbg_token_scores", "wt_dbg_sample_select", "wt_dbg_suppress_logits",
     "wt_dbg_sample_select_group", "wt_dbg_best_of_begin", "wt_dbg_best_of_pick",
+    "wt_dbg_nucleus_cut", "wt_dbg_sample_select_cut",
     "wt_dbg_frontend_dims", "wt_dbg_frontend_stages", "wt_dbg_log_clipmax", "wt_dbg_mel_normalize", "wt_dbg_mel_transpose",
     "wt_dbg_pcm_to_planes",
     "wt_dbg_gemm_addressed", "wt_dbg_plane_gemm_plan", "wt_dbg_gemm_ln_fused", "wt_dbg_layernorm_planes", "wt_dbg_f32_to_planes", "wt_dbg_encoder_attention_at",
@@ -82,6 +83,11 @@ DEBUG_SYMBOLS = [
     "wt_dbg_f32_to_bf16",
     "wt_dbg_align_scores", "wt_dbg_align_matrix", "wt_dbg_align_dtw", "wt_dbg_last_alignment", "wt_dbg_set_alignment",
 ]
+
+
+# wt_nucleus_cut (include/wt_debug.h)
+NUCLEUS_CUT_DTYPE = np.dtype([("cut", np.uint64), ("kept_q", np.uint64), ("total_q", np.uint64), ("kept", np.int32),
+                              ("pad", np.int32)])
 
 
 class BeamFullArgs(ctypes.Structure):
@@ -297,6 +303,11 @@ def lib() -> ctypes.CDLL:
         dp, u8p = POINTER(ctypes.c_double), POINTER(ctypes.c_uint8)
         L.wt_dbg_sample_select_group.argtypes = [c_void_p, c_int, c_int, c_int, fp, ip64, c_int, c_int, c_int, c_int, c_int,
                                                  c_int, c_int, fp, ctypes.c_uint64, c_int, c_int, c_int, c_int, ip64, dp, fp, fp]
+        L.wt_dbg_sample_select_cut.argtypes = [c_void_p, c_int, c_int, c_int, fp, ip64, c_int, c_int, c_int, c_int, c_int,
+                                               c_int, c_int, fp, ctypes.c_uint64, c_int, c_int, c_int, c_int, c_int,
+                                               ctypes.c_float, ip64, dp, fp, fp, c_void_p]
+        L.wt_dbg_nucleus_cut.argtypes = [c_void_p, c_int, c_int, fp, ip64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                         fp, c_int, ctypes.c_float, c_void_p]
         L.wt_dbg_best_of_begin.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, ip32, ip64, ip32, ip32, dp, ip32, u8p]
         L.wt_dbg_best_of_pick.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, ip64, fp, ip32, dp, ip32, ip64, fp,
                                           ip32, dp, ip32, ip32, dp, ip32]
@@ -1486,6 +1497,44 @@ class Engine:
                                                      int(attempt), int(clip_base), int(row0), int(pos), _ip64(tok),
                                                      L.ctypes.data_as(POINTER(ctypes.c_double)), _fp(M), _fp(key)))
         return tok, L, M, key
+
+    def dbg_sample_select_cut(self, logits, ids, n_ids, sample_begin, temperature, group=1, top_k=0, top_p=1.0, seed=0,
+                              attempt=0, clip_base=0, row0=0, pos=-1, timestamps=False, eot=0, beg=1,
+                              max_initial_timestamp=50):
+        """dbg_sample_select_group behind nucleus_cut (k_nucleus.hip): the draw over the ids that
+        top_k / top_p (a float in (0, 1], 1 = off) keep.  Returns (tokens, L, M, keys, cuts); cuts as dbg_nucleus_cut."""
+        logits = _f32(logits)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        B, V = logits.shape
+        clips = (B + int(group) - 1) // max(int(group), 1)
+        temperature = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, np.float32), (clips,)))
+        assert ids.shape[0] == B
+        tok, L, M, key = np.zeros(B, np.int64), np.zeros(B, np.float64), np.zeros(B, np.float32), np.zeros(B, np.float32)
+        cut = np.zeros(B, NUCLEUS_CUT_DTYPE)
+        self._check(lib().wt_dbg_sample_select_cut(self._h, B, int(group), V, _fp(logits), _ip64(ids), ids.shape[1],
+                                                   int(n_ids), int(sample_begin), int(bool(timestamps)), int(eot),
+                                                   int(beg), int(max_initial_timestamp), _fp(temperature), int(seed),
+                                                   int(attempt), int(clip_base), int(row0), int(pos), int(top_k),
+                                                   float(top_p), _ip64(tok), L.ctypes.data_as(POINTER(ctypes.c_double)),
+                                                   _fp(M), _fp(key), cut.ctypes.data))
+        return tok, L, M, key, cut
+
+    def dbg_nucleus_cut(self, logits, ids, n_ids, sample_begin, temperature, top_k=0, top_p=1.0, timestamps=False, eot=0,
+                        beg=1, max_initial_timestamp=50):
+        """nucleus_cut (k_nucleus.hip) over the rows of logits float32 [rows][V]; ids / n_ids (an int)
+        / sample_begin give the state of the timestamp rules as in dbg_sample_select_group; temperature float32 [rows].
+        Returns a record array [rows] with the fields cut, kept_q, total_q (uint64) and kept (int32)."""
+        logits = _f32(logits)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        rows, V = logits.shape
+        temperature = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, np.float32), (rows,)))
+        assert ids.shape[0] == rows
+        cut = np.zeros(rows, NUCLEUS_CUT_DTYPE)
+        self._check(lib().wt_dbg_nucleus_cut(self._h, rows, V, _fp(logits), _ip64(ids), ids.shape[1], int(n_ids),
+                                             int(sample_begin), int(bool(timestamps)), int(eot), int(beg),
+                                             int(max_initial_timestamp), _fp(temperature), int(top_k), float(top_p),
+                                             cut.ctypes.data))
+        return cut
 
     def dbg_best_of_begin(self, ids, n_prompt, N, cap, frozen=None, fill=0x5a):
         """best_of_begin (k_best_of.hip): ids int64 [N * clips][stride], rows c < clips holding the clips' prompts.  The

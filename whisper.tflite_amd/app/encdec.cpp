@@ -48,6 +48,8 @@ void usage(const char* argv0) {
             << "  --temperature T with --max-positions: sample every id at temperature T in [0, 1] (default 0: greedy)\n"
             << "  --best-of N     with --temperature or --fallback: N samples, 1..8, per window at every temperature above 0,\n"
             << "                  the one with the best average log-probability kept (default 1)\n"
+            << "  --top-k N       with --temperature or --fallback: draw among the N most likely ids (default 0: all)\n"
+            << "  --top-p P       ... and within the smallest set of them that holds P in (0, 1] of the probability (default 1)\n"
             << "  --seed N        the sampler's 64-bit seed (default 0): same audio, options and seed, same text\n"
             << "  --fallback      with --scores: Whisper's temperature fall-back, T, T + 0.2, ... 1.0 per window, and one\n"
             << "                  line per window with the temperature kept, the attempts and the compression ratio\n"
@@ -88,7 +90,7 @@ bool read_raw_wav(const std::string& path, RawWav* out) {
 }  // namespace
 
 int main(int argc, char* argv[]) {
-  std::string model_prefix, vocab, input, inputs, lang, languages, task, beam, max_positions, temperature, seed, best_of, cr_threshold, context_ids, alignment_heads,
+  std::string model_prefix, vocab, input, inputs, lang, languages, task, beam, max_positions, temperature, seed, best_of, top_k, top_p, cr_threshold, context_ids, alignment_heads,
       suppress_tokens;
   bool word_timestamps = false, suppress_default = false, suppress_blank = false, resample = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
@@ -173,6 +175,8 @@ int main(int argc, char* argv[]) {
     else if (a == "--temperature") temperature = v;
     else if (a == "--seed") seed = v;
     else if (a == "--best-of") best_of = v;
+    else if (a == "--top-k") top_k = v;
+    else if (a == "--top-p") top_p = v;
     else if (a == "--compression-ratio-threshold") cr_threshold = v;
     else if (a == "--context-ids") context_ids = v;
     else if (a == "--alignment-heads") alignment_heads = v;
@@ -305,9 +309,9 @@ int main(int argc, char* argv[]) {
       return 105;
     }
   }
-  if (!temperature.empty() || fallback || !seed.empty() || !cr_threshold.empty() || !best_of.empty()) {
+  if (!temperature.empty() || fallback || !seed.empty() || !cr_threshold.empty() || !best_of.empty() || !top_k.empty() || !top_p.empty()) {
     if (max_positions.empty()) {
-      std::cerr << "--temperature, --seed, --best-of, --fallback and --compression-ratio-threshold require --max-positions\n";
+      std::cerr << "--temperature, --seed, --best-of, --top-k, --top-p, --fallback and --compression-ratio-threshold require --max-positions\n";
       return 105;
     }
     if (fallback && !scores) {
@@ -342,6 +346,15 @@ int main(int argc, char* argv[]) {
         return 105;
       }
     }
+    if (!top_k.empty()) {
+      char* end = nullptr;
+      const long n = std::strtol(top_k.c_str(), &end, 10);
+      if (end == top_k.c_str() || *end || wt_engine_set_option(encdec.handle(), "top_k", n) != WT_OK) {
+        std::cerr << "--top-k: expected 0 (off) or a number of ids up to the vocabulary's size, got " << top_k << "\n";
+        return 105;
+      }
+    }
+    if (!top_p.empty() && !thousandths(top_p, "--top-p", "top_p")) return 105;
     if (fallback && wt_engine_set_option(encdec.handle(), "temperature_fallback", 1) != WT_OK) {
       std::cerr << "--fallback: " << wt_last_error(encdec.handle()) << "\n";
       return 105;

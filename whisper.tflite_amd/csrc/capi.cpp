@@ -234,6 +234,14 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
     // samples per clip of an attempt above temperature 0 in a full-length decode, 1 = one
     if (value < 1 || value > wt::kSampleGroupMax) return fail(h, WT_ERR_INVALID_ARG, "best_of must be in [1, 8]");
     e.best_of = value;
+  } else if (k == "top_k") {
+    // truncated sampling: a draw above temperature 0 is among the top_k largest allowed logits, 0 = off
+    if (value < 0 || value > e.dims().n_vocab) return fail(h, WT_ERR_INVALID_ARG, "top_k must be 0 (off) or in [1, n_vocab]");
+    e.top_k = value;
+  } else if (k == "top_p") {
+    // ... and within the smallest set of those that holds top_p / 1000 of their probability, 1000 = off
+    if (value < 1 || value > 1000) return fail(h, WT_ERR_INVALID_ARG, "top_p must be in [1, 1000] (thousandths, 1000 = off)");
+    e.top_p = value;
   } else if (k == "fallback_beam") {
     // with full_beam = 1 and beam_size 2..8: the fall-back's attempt at temperature 0 is beam search
     if (value < 0 || value > 1) return fail(h, WT_ERR_INVALID_ARG, "fallback_beam must be 0 or 1");
@@ -434,6 +442,8 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "compression_ratio_threshold") *value = e.compression_ratio_threshold;
   else if (k == "seed") *value = e.seed;
   else if (k == "best_of") *value = e.best_of;
+  else if (k == "top_k") *value = e.top_k;
+  else if (k == "top_p") *value = e.top_p;
   else if (k == "fallback_beam") *value = e.fallback_beam;
   else if (k == "prompt_group") *value = e.prompt_group;
   else if (k == "seek") *value = e.seek;

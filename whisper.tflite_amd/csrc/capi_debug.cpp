@@ -1402,10 +1402,13 @@ int wt_dbg_sample_select(wt_engine* h, int B, int V, const float* logits, const 
   });
 }
 
-int wt_dbg_sample_select_group(wt_engine* h, int B, int group, int V, const float* logits, const int64_t* ids, int ids_stride,
-                               int n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
-                               const float* temperature, uint64_t seed, int attempt, int clip_base, int row0, int pos,
-                               int64_t* token, double* L, float* M, float* key) {
+namespace {
+// the grouped sampling step of wt_dbg_sample_select_group; cutting: nucleus_cut in front under (top_k, top_p), the
+// rows' cuts into cut_out (wt_dbg_sample_select_cut)
+int sample_group_step(wt_engine* h, int B, int group, int V, const float* logits, const int64_t* ids, int ids_stride, int n_ids,
+                      int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp, const float* temperature,
+                      uint64_t seed, int attempt, int clip_base, int row0, int pos, bool cutting, int top_k, float top_p,
+                      int64_t* token, double* L, float* M, float* key, wt_nucleus_cut* cut_out) {
   if (!h || !logits || !ids || !token || !temperature || B < 1 || group < 1 || V < 2 || ids_stride < 1 || sample_begin < 1 ||
       attempt < 0 || clip_base < 0 || row0 < 0 || n_ids < sample_begin || n_ids > ids_stride) {
     return WT_ERR_INVALID_ARG;
@@ -1416,6 +1419,7 @@ int wt_dbg_sample_select_group(wt_engine* h, int B, int group, int V, const floa
     wt::SampleParams prm{};
     prm.seed_lo = unsigned(seed & 0xffffffffull), prm.seed_hi = unsigned(seed >> 32);
     prm.attempt = unsigned(attempt), prm.clip_base = unsigned(clip_base);
+    prm.top_k = top_k, prm.top_p = top_p;
     for (int c = 0; c < clips && row0 + c < wt::kSampleClipsMax; ++c) {
       if (!(temperature[c] >= 0.0f) || std::isinf(temperature[c])) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_sample_select_group: a temperature is negative or not finite");
       prm.inv_t[row0 + c] = temperature[c] > 0.0f ? 1.0f / temperature[c] : 0.0f;
@@ -1443,6 +1447,8 @@ int wt_dbg_sample_select_group(wt_engine* h, int B, int group, int V, const floa
     t.ids = dids.p; t.ids_stride = stride; t.pos = n_ids - 1; t.stop_at_eot = 1;
     t.n_ids = dn.p; t.finished = dfin.p;
     t.dbg_L = dL.p; t.dbg_M = dM.p; t.dbg_key = dK.p;
+    DevArr<wt::NucleusCut> dcut(cutting ? size_t(B) : 0);
+    if (cutting) t.cut = dcut.p;
     wt::launch_sample_select(t, h->impl->stream());
     h->impl->sync();
     dids.to_host(rows.data());
@@ -1450,6 +1456,57 @@ int wt_dbg_sample_select_group(wt_engine* h, int B, int group, int V, const floa
     if (L) dL.to_host(L);
     if (M) dM.to_host(M);
     if (key) dK.to_host(key);
+    if (cutting) dcut.to_host(reinterpret_cast<wt::NucleusCut*>(cut_out));
+  });
+}
+}  // namespace
+
+int wt_dbg_sample_select_group(wt_engine* h, int B, int group, int V, const float* logits, const int64_t* ids, int ids_stride,
+                               int n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
+                               const float* temperature, uint64_t seed, int attempt, int clip_base, int row0, int pos,
+                               int64_t* token, double* L, float* M, float* key) {
+  return sample_group_step(h, B, group, V, logits, ids, ids_stride, n_ids, sample_begin, timestamps, eot, beg, max_initial_timestamp,
+                           temperature, seed, attempt, clip_base, row0, pos, false, 0, 1.0f, token, L, M, key, nullptr);
+}
+
+int wt_dbg_sample_select_cut(wt_engine* h, int B, int group, int V, const float* logits, const int64_t* ids, int ids_stride,
+                             int n_ids, int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp,
+                             const float* temperature, uint64_t seed, int attempt, int clip_base, int row0, int pos, int top_k,
+                             float top_p, int64_t* token, double* L, float* M, float* key, wt_nucleus_cut* cut) {
+  static_assert(sizeof(wt_nucleus_cut) == sizeof(wt::NucleusCut), "wt_nucleus_cut mirrors wt::NucleusCut");
+  return sample_group_step(h, B, group, V, logits, ids, ids_stride, n_ids, sample_begin, timestamps, eot, beg, max_initial_timestamp,
+                           temperature, seed, attempt, clip_base, row0, pos, true, top_k, top_p, token, L, M, key, cut);
+}
+
+int wt_dbg_nucleus_cut(wt_engine* h, int rows, int V, const float* logits, const int64_t* ids, int ids_stride, int n_ids,
+                       int sample_begin, int timestamps, int eot, int beg, int max_initial_timestamp, const float* temperature,
+                       int top_k, float top_p, wt_nucleus_cut* cut) {
+  if (!h || !logits || !ids || !temperature || !cut || rows < 1 || rows > wt::kSampleClipsMax || V < 2 || ids_stride < 1 ||
+      sample_begin < 1 || n_ids < sample_begin || n_ids > ids_stride) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    wt::SampleParams prm{};
+    prm.top_k = top_k, prm.top_p = top_p;
+    for (int b = 0; b < rows; ++b) {
+      if (!(temperature[b] >= 0.0f) || std::isinf(temperature[b])) throw wt::Error(WT_ERR_INVALID_ARG, "wt_dbg_nucleus_cut: a temperature is negative or not finite");
+      prm.inv_t[b] = temperature[b] > 0.0f ? 1.0f / temperature[b] : 0.0f;
+    }
+    const int ldl = (V + 3) & ~3, stride = ids_stride + 1;
+    std::vector<int32_t> n(size_t(rows), n_ids);
+    DevArr<float> dlog(pad_logits(logits, rows, V, ldl));
+    DevArr<long long> dids(widen_ids(ids, rows, ids_stride, n.data(), 0));
+    DevArr<int> dn(rows, n.data());
+    DevArr<wt::TsState> dstate(rows);
+    DevArr<wt::SampleParams> dprm(1, &prm);
+    DevArr<wt::NucleusCut> dcut(rows);
+    if (timestamps) wt::launch_ts_state_init(dids.p, stride, dn.p, 0, sample_begin, V, beg, dstate.p, rows, h->impl->stream());
+    wt::NucleusArgs a;
+    a.logits = dlog.p; a.ldl = ldl; a.V = V; a.rows = rows; a.eot = eot; a.beg = beg; a.max_initial = max_initial_timestamp;
+    a.n_gen = n_ids - sample_begin; a.state = timestamps ? dstate.p : nullptr; a.params = dprm.p; a.out = dcut.p;
+    wt::launch_nucleus_cut(a, h->impl->stream());
+    h->impl->sync();
+    dcut.to_host(reinterpret_cast<wt::NucleusCut*>(cut));
   });
 }
 

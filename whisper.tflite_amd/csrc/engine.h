@@ -29,6 +29,7 @@ struct BeamFullPart;
 struct ScorePart;
 struct SamplePart;
 struct SampleParams;
+struct NucleusCut;
 
 // WT_DEC_KERNEL_TIMERS diagnostics: the event pairs and launch classes of a slot's eager decoder launches
 struct DecTimers {
@@ -278,6 +279,13 @@ class Engine {
   long seed = 0;
   long clip_base = 0;  // index of the call's first clip in the Philox counter (wt_transcribe_long_pcm: the window index)
   bool sampling() const { return temperature > 0 || temperature_fallback != 0; }
+  // Truncated sampling.  top_k (0 = off, else 1 .. n_vocab) and top_p (thousandths, 1000 = off)
+  // narrow the set every draw at a temperature above 0 is taken from: the top_k largest allowed logits, then the
+  // shortest head of those that holds top_p of their mass at that temperature (nucleus_cut, k_nucleus.hip, in front
+  // of sample_partial).  They act in decode_full's chain and in decode_best_of, mean nothing at temperature 0 or to
+  // beam search, and leave the reported log-probabilities those of the whole allowed set.
+  long top_k = 0, top_p = 1000;
+  bool truncating() const { return sampling() && (top_k > 0 || top_p < 1000); }
   // Several samples per clip.  best_of = N > 1: every attempt of a full-length decode whose
   // temperature is above 0 decodes N samples per clip (decode_best_of) and keeps the first with the largest
   // sum_logprob / n_generated in float64, EOT counted; an attempt at temperature 0 draws nothing and runs as ever.
@@ -578,6 +586,7 @@ class Engine {
     // parameter block and its pinned mirror
     SamplePart* sm_part = nullptr;
     SampleParams *sm_prm = nullptr, *h_prm = nullptr;
+    NucleusCut* sm_cut = nullptr;  // options top_k / top_p: the rows' cuts [128], decode_best_of's rows too
     // suppression without sampling or timestamps: the greedy step runs on the sampler's kernels at T = 0 under a
     // parameter block of zeros that is never written again (it shares ts_logits and sm_part)
     SampleParams* zero_prm = nullptr;
@@ -634,6 +643,8 @@ class Engine {
   // last entry of those three keys in the bf16 storage mode (option full_bf16), absent in fp32: the entries a key may end
   // with otherwise (suppression's two counts, the detecting chain's 1 or 2, the flags) are never negative
   static constexpr long long kBf16KeyMark = -16;
+  // in front of that mark, in the full-length and best-of keys of a call with top_k / top_p on
+  static constexpr long long kCutKeyMark = -17;
 
   int enc_cus_masked_ = 0;  // CUs the pipelined encoder stream may use
  public:

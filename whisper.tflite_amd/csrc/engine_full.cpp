@@ -259,6 +259,7 @@ void Engine::ensure_full_workspace(int batch) {
     if (!fw_.sm_part) fw_.sm_part = dev_zeroed<SamplePart>(C * size_t(ts_chunks(c.n_vocab)));
     if (!fw_.sm_prm) fw_.sm_prm = dev_zeroed<SampleParams>(1);
     if (!fw_.h_prm) fw_.h_prm = pinned<SampleParams>(1);
+    if (truncating() && !fw_.sm_cut) fw_.sm_cut = dev_zeroed<NucleusCut>(kDecRowsMax);
   }
   if (fw_.h_fin) return;  // (allocated last)
   fw_.ids = dev_zeroed<long long>(C * (cap + 1));
@@ -402,7 +403,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     decode_beam_full(batch, ids, ids_stride, n_ids);
     return publish_languages();
   }
-  const bool ts = timestamps != 0, sc = scores != 0, smp = sampling(), sup = suppressing();
+  const bool ts = timestamps != 0, sc = scores != 0, smp = sampling(), sup = suppressing(), cutting = truncating();
   const int n_sup = int(suppress_ids.size()), n_sup_first = int(suppress_first_ids.size());
   ensure_batch(batch);
   ensure_full_workspace(batch);  // (before any capture: nothing may be allocated inside one)
@@ -511,6 +512,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
           t.state = ts ? fw_.ts_state : nullptr;
           t.ids = d_ids; t.ids_stride = stride; t.pos = last; t.stop_at_eot = int(stop_at_eot);
           t.n_ids = dw.n_ids; t.finished = dw.finished;
+          if (cutting) t.cut = fw_.sm_cut;  // top_k / top_p: nucleus_cut in front, under the block's values
           launch_sample_select(t, st);
         } else if (ts) {
           TsSelectArgs t;
@@ -590,6 +592,8 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       // (one entry more, where suppression adds two: the detecting chain, under a candidate list or not; the mask, the
       // held languages and the languages themselves are device data)
       if (det) key.push_back(language_candidates.empty() ? 1 : 2);
+      // (top_k / top_p on: another launch sequence; their values are device data.  A mark no other entry takes)
+      if (cutting) key.push_back(kCutKeyMark);
       // (last, and in the bf16 storage mode only: the fp32 keys stay what they were, and no entry above is negative)
       if (p.bf) key.push_back(kBf16KeyMark);
       return key;
@@ -649,6 +653,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
       const unsigned long long sd = static_cast<unsigned long long>(seed);
       prm.seed_lo = unsigned(sd & 0xffffffffull), prm.seed_hi = unsigned(sd >> 32);
       prm.attempt = unsigned(attempt), prm.clip_base = unsigned(clip_base);
+      prm.top_k = int(top_k), prm.top_p = float(top_p) / 1000.0f;  // (1000: 1.0f, off)
       const float T = float(temps[attempt]) / 1000.0f;
       for (int b = 0; b < kSampleClipsMax; ++b) {
         prm.inv_t[b] = temps[attempt] > 0 ? 1.0f / T : 0.0f;
@@ -1029,6 +1034,7 @@ void Engine::decode_best_of(int batch, const std::vector<long long>& prompt, con
         g.n_gen = t; g.params = fw_.sm_prm; g.row0 = c0; g.part = bo_.sm_part; g.state = ts ? bf_.ts : nullptr;
         g.ids = bf_.ids[0]; g.ids_stride = stride; g.pos = last; g.stop_at_eot = 1;
         g.n_ids = bo_.n_ids; g.finished = bo_.finished;
+        if (truncating()) g.cut = fw_.sm_cut;  // per row: the samples of a clip share logits at the first step only
         launch_sample_select(g, st);
         launch_score_finish(sa, st);
         ++seg_steps;
@@ -1042,6 +1048,7 @@ void Engine::decode_best_of(int batch, const std::vector<long long>& prompt, con
       std::vector<long long> key{kBestOfKey, slot_idx, N, c0, nc, lo, P, n_prompt, fc2_ksplit, n_abs, slot.dec, ts ? 1 : 0,
                                  ts ? max_initial_timestamp : 0, sc ? 1 : 0};
       if (sup) key.push_back(n_sup), key.push_back(n_sup_first);  // launch constants; the ids themselves are device data
+      if (truncating()) key.push_back(kCutKeyMark);  // top_k / top_p on: another launch sequence
       if (p.bf) key.push_back(kBf16KeyMark);  // (last, in the bf16 storage mode only)
       return key;
     };

@@ -14,6 +14,8 @@
 // cross-attention groups per clip).  The parameter block is indexed by the clip; the counter's fourth word is
 // attempt + (j << 16), so sample 0 is the ungrouped draw.  sample_partial<true, int> is that form, sample_partial<false>
 // the launch of group = 1.  sample_select reads nothing of the block and serves both.
+// Truncated sampling (SampleArgs::cut, options top_k / top_p): nucleus_cut (k_nucleus.hip) runs in
+// front and the kCut form of sample_partial draws over the kept ids only; rule 5 and the scores see the whole set.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -77,13 +79,21 @@ __device__ __forceinline__ float gumbel_of(unsigned x) {
 // load shape of ts_partial, and its reductions for key_text, m and s: the same bits)
 // (kGroup = true takes one more argument, the clips of the launch; without it the argument list, and with it every
 // instruction, is the ungrouped kernel's)
-template <bool kGroup, typename... Clips>
+// kCut = true (options top_k, top_p) takes the clips (0: ungrouped) and the rows' NucleusCut: the
+// perturbed maxima are formed over the ids with key >= cut; the unperturbed records stay those of the whole allowed set
+__device__ __forceinline__ int clips_of() { return 0; }
+__device__ __forceinline__ int clips_of(int c) { return c; }
+__device__ __forceinline__ int clips_of(int c, const NucleusCut*) { return c; }
+__device__ __forceinline__ const NucleusCut* cut_of(int, const NucleusCut* p) { return p; }
+template <bool kGroup, bool kCut, typename... Extra>
 __global__ __launch_bounds__(kThreads) void sample_partial(const float* __restrict__ logits, int ldl, int V,
                                                            const TsState* __restrict__ state, int n_gen, int eot, int beg,
                                                            int mit, const SampleParams* __restrict__ prm, int row0,
-                                                           int rng_pos, SamplePart* __restrict__ part, Clips... n_clips) {
-  static_assert(sizeof...(Clips) == (kGroup ? 1 : 0), "the grouped kernel takes the number of clips");
-  const int clips = (n_clips + ... + 0);
+                                                           int rng_pos, SamplePart* __restrict__ part, Extra... extra) {
+  static_assert(sizeof...(Extra) == (kCut ? 2 : kGroup ? 1 : 0), "the grouped kernel takes the number of clips, the cut kernel the cuts too");
+  const int clips = clips_of(extra...);
+  unsigned long long cut = 0ull;
+  if constexpr (kCut) cut = cut_of(extra...)[blockIdx.y].cut;
   __shared__ float red[4];
   __shared__ unsigned long long kred[4][4];
   const int chunk = blockIdx.x, row = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -120,8 +130,9 @@ __global__ __launch_bounds__(kThreads) void sample_partial(const float* __restri
       const bool is_t = i >= a.t_lo && i <= a.t_hi, is_s = i >= a.s_lo && i <= a.s_hi;  // (t_hi, s_hi < V)
       if (is_t && key > kt) kt = key;
       if (is_s && key > ks) ks = key;
-      if (is_t && pkey > pt) pt = pkey;
-      if (is_s && pkey > ps) ps = pkey;
+      const bool in_n = !kCut || key >= cut;
+      if (is_t && in_n && pkey > pt) pt = pkey;
+      if (is_s && in_n && pkey > ps) ps = pkey;
       v[4 * j + c] = is_s ? e[c] : -INFINITY;
       m = fmaxf(m, v[4 * j + c]);
     }
@@ -164,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void sample_partial(const float* __restri
 __global__ __launch_bounds__(64) void sample_select(const SamplePart* __restrict__ part, int n_chunks, long long* ids,
                                                     int ids_stride, int pos, int* n_ids, int* finished,
                                                     TsState* __restrict__ state, int beg, long long eot, int stop_at_eot,
-                                                    double* dbg_L, float* dbg_M, float* dbg_key) {
+                                                    double* dbg_L, float* dbg_M, float* dbg_key, int cut) {
   __shared__ SamplePart sp[kTsMaxChunks];
   const int b = blockIdx.x;
   for (int c = threadIdx.x; c < n_chunks; c += 64) sp[c] = part[(long)b * n_chunks + c];
@@ -188,9 +199,12 @@ __global__ __launch_bounds__(64) void sample_select(const SamplePart* __restrict
   const float M = kt != 0ull ? float_of((unsigned)(kt >> 32)) : -INFINITY;
   if (dbg_L) dbg_L[b] = ks != 0ull ? L : NAN;  // NaN: no such id is allowed
   if (dbg_M) dbg_M[b] = kt != 0ull ? M : NAN;
-  if (kt != 0ull && ks != 0ull && L > (double)M) pt = 0ull;
+  const bool mass = kt != 0ull && ks != 0ull && L > (double)M;
+  if (mass) pt = 0ull;
   // the allowed set is never empty, so one of the keys exists
-  const unsigned long long p = pt > ps ? pt : ps;
+  unsigned long long p = pt > ps ? pt : ps;
+  // behind a cut the class rule 5 left may hold no kept id: then its best unperturbed key, the choice at T = 0
+  if (cut && p == 0ull) p = mass ? ks : (kt > ks ? kt : ks);
   if (dbg_key) dbg_key[b] = float_of((unsigned)(p >> 32));
   const long long tok = (long long)(unsigned)(p & 0xffffffffull);
   ids[(long)b * ids_stride + pos + 1] = tok;
@@ -222,15 +236,30 @@ void launch_sample_select(const SampleArgs& a, hipStream_t s) {
   if (a.group < 1 || a.group > kSampleGroupMax || (a.group > 1 && (a.batch > kSampleRowsMax || a.row0 + clips > kSampleClipsMax))) {
     throw Error(kErrInvalidArg, "sample_select: a group is 1 .. 8 samples per clip, at most 128 rows and 64 clips");
   }
-  if (a.group > 1) {
-    hipLaunchKernelGGL((sample_partial<true, int>), dim3(n_chunks, a.batch), dim3(kThreads), 0, s, a.logits, a.ldl, a.V, a.state,
+  if (a.cut) {  // truncated sampling: the rows' cuts first, in the same sequence
+    NucleusArgs n;
+    n.logits = a.logits; n.ldl = a.ldl; n.V = a.V; n.rows = a.batch; n.eot = a.eot; n.beg = a.beg; n.max_initial = a.max_initial;
+    n.n_gen = a.n_gen; n.state = a.state; n.params = a.params; n.row0 = a.row0; n.clips = a.group > 1 ? clips : 0; n.out = a.cut;
+    launch_nucleus_cut(n, s);
+    const NucleusCut* const cut = a.cut;
+    if (a.group > 1) {
+      hipLaunchKernelGGL((sample_partial<true, true, int, const NucleusCut*>), dim3(n_chunks, a.batch), dim3(kThreads), 0, s, a.logits,
+                         a.ldl, a.V, a.state, a.n_gen, a.eot, a.beg, a.max_initial, a.params, a.row0, a.rng_pos >= 0 ? a.rng_pos : a.pos,
+                         a.part, clips, cut);
+    } else {
+      hipLaunchKernelGGL((sample_partial<false, true, int, const NucleusCut*>), dim3(n_chunks, a.batch), dim3(kThreads), 0, s, a.logits,
+                         a.ldl, a.V, a.state, a.n_gen, a.eot, a.beg, a.max_initial, a.params, a.row0, a.rng_pos >= 0 ? a.rng_pos : a.pos,
+                         a.part, 0, cut);
+    }
+  } else if (a.group > 1) {
+    hipLaunchKernelGGL((sample_partial<true, false, int>), dim3(n_chunks, a.batch), dim3(kThreads), 0, s, a.logits, a.ldl, a.V, a.state,
                        a.n_gen, a.eot, a.beg, a.max_initial, a.params, a.row0, a.rng_pos >= 0 ? a.rng_pos : a.pos, a.part, clips);
   } else {
-    hipLaunchKernelGGL(sample_partial<false>, dim3(n_chunks, a.batch), dim3(kThreads), 0, s, a.logits, a.ldl, a.V, a.state, a.n_gen,
+    hipLaunchKernelGGL((sample_partial<false, false>), dim3(n_chunks, a.batch), dim3(kThreads), 0, s, a.logits, a.ldl, a.V, a.state, a.n_gen,
                        a.eot, a.beg, a.max_initial, a.params, a.row0, a.rng_pos >= 0 ? a.rng_pos : a.pos, a.part);
   }
   hipLaunchKernelGGL(sample_select, dim3(a.batch), dim3(64), 0, s, a.part, n_chunks, a.ids, a.ids_stride, a.pos, a.n_ids,
-                     a.finished, a.state, ts ? a.beg : a.V, (long long)a.eot, a.stop_at_eot, a.dbg_L, a.dbg_M, a.dbg_key);
+                     a.finished, a.state, ts ? a.beg : a.V, (long long)a.eot, a.stop_at_eot, a.dbg_L, a.dbg_M, a.dbg_key, a.cut ? 1 : 0);
 }
 
 }  // namespace wt

@@ -566,7 +566,31 @@ struct SampleParams {                // device memory, written ahead of a chain:
   // position under a slot count) and its clip word clip_base + clip + clip_off[clip]; zeros give the words above
   int pos_off[kSampleClipsMax];
   int clip_off[kSampleClipsMax];
+  // truncated sampling (k_nucleus.hip), read by nucleus_cut alone: top_k <= 0 and a top_p outside
+  // (0, 1) are off, so a block of zeros is today's sampler
+  int top_k;
+  float top_p;
 };
+// k_nucleus.hip (options top_k, top_p): per row the record key (ord(z_i) << 32 | i) of the last id
+// that truncated sampling keeps.  With the allowed ids A in descending key order, K = the first min(top_k, |A|) of them
+// (all for top_k <= 0), N = the shortest prefix of K whose mass sum p_i, p_i = exp((z_i - m) * inv_t), reaches
+// top_p * (the mass of K); an id is kept where key >= cut.  cut = 0 (everything) for a row at inv_t = 0, with both
+// options off, or without a finite maximum.  Masses are sums of q_i = floor(p_i 2^40): integers, the same in any order.
+struct NucleusCut {
+  unsigned long long cut;              // key of the last id kept, 0: all of A
+  unsigned long long kept_q, total_q;  // sum of q over the kept ids, over A
+  int kept, pad;                       // ids kept
+};
+struct NucleusArgs {
+  const float* logits = nullptr;  // as SampleArgs: [rows][ldl], ldl % 4 == 0, 16-byte aligned
+  int ldl = 0, V = 0, rows = 0;   // V <= 2^20
+  int eot = 0, beg = 0, max_initial = -1, n_gen = 0;
+  const TsState* state = nullptr;        // [rows] or nullptr (A = the whole vocabulary)
+  const SampleParams* params = nullptr;  // inv_t of clip row0 + (clips ? row % clips : row), top_k, top_p
+  int row0 = 0, clips = 0;               // clips > 0: the rows of a grouped launch (SampleArgs::group > 1)
+  NucleusCut* out = nullptr;             // [rows]
+};
+void launch_nucleus_cut(const NucleusArgs& a, hipStream_t s);  // throws kErrInvalidArg
 struct SamplePart {                  // one (clip, chunk); keys as TsPart's
   unsigned long long pkey_text, pkey_ts;  // best perturbed key over the allowed ids below beg / the allowed timestamps
   unsigned long long key_text, key_ts;    // ts_partial's record: the same bits
@@ -591,6 +615,9 @@ struct SampleArgs {
   double* dbg_L = nullptr;        // optional [batch], as TsSelectArgs
   float* dbg_M = nullptr;
   float* dbg_key = nullptr;       // optional [batch]: the winning key k
+  // optional [batch]: nucleus_cut runs in front of sample_partial under params->top_k / top_p, and the perturbed
+  // maxima are taken over the ids whose record key is >= the row's cut (options top_k, top_p)
+  NucleusCut* cut = nullptr;
 };
 void launch_sample_select(const SampleArgs& a, hipStream_t s);  // sample_partial + sample_select; throws kErrInvalidArg
 
