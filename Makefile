@@ -11,7 +11,7 @@ OBJ   := $(PKG)/build
 CXXFLAGS := -std=c++17 -O3 -fPIC -Iinclude -I$(SRC) -Wall -Wno-unused-result
 HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH) -ffp-contract=fast $(HIPFLAGS_EXTRA)
 
-KERNELS := k_gemm k_gemm_planes k_gemm_bf16 k_misc k_attention k_attention_planes k_decoder k_cross_absorbed k_beam k_beam_full k_timestamps k_scores k_sample k_align k_suppress k_best_of k_resample k_nucleus
+KERNELS := k_gemm k_gemm_planes k_gemm_bf16 k_misc k_attention k_attention_planes k_decoder k_cross_absorbed k_beam k_beam_full k_timestamps k_scores k_sample k_align k_suppress k_best_of k_resample k_nucleus k_logits_i8
 HOSTSRC := engine engine_full decode_results capi capi_debug host_util longform words weights_gen whisper_api tflite_extract resample
 OBJS := $(addprefix $(OBJ)/,$(addsuffix .o,$(KERNELS) $(HOSTSRC)))
 
@@ -29,7 +29,10 @@ $(OBJ)/k_attention_planes.o: HIPFLAGS += -fno-slp-vectorize
 # the fixed-point masses of nucleus_cut are products and sums of single floats: no packed fp32 instructions there
 $(OBJ)/k_nucleus.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
-$(OBJ)/%.o: $(SRC)/%.hip $(SRC)/kernels.h $(SRC)/ts_rules.h
+# the int8 logits head scales back with two single fp32 products per element: no packed fp32 instructions there either
+$(OBJ)/k_logits_i8.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+
+$(OBJ)/%.o: $(SRC)/%.hip $(SRC)/kernels.h $(SRC)/ts_rules.h $(SRC)/dec_rows.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

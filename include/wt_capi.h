@@ -151,6 +151,11 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * WT_ERR_INVALID_ARG.  The cuts of other options keep their own texts: contexts with "word_timestamps"; contexts, "seek" or
  * "word_timestamps" behind "full_beam" / "best_of"; "best_of" / "fallback_beam" with wt_transcribe_long_batch; the pipeline
  * and forced ids),
+ * "logits_int8" (0 = default; 1 = the int8 dynamic-range logits head, DESIGN.md section 37: the logits of every decoding
+ * mode are int32 products of the final LayerNorm rows, quantised per row at every launch, with the tied embedding as int8
+ * rows + one fp32 scale per vocabulary row (wt_quantize_rows_i8 of the model's fp32 rows, made at the first switch: 1 byte
+ * per element streamed where the default head streams 4), y = ((float)acc * s_row) * s_column; both storage modes, every
+ * graph key; language detection keeps its fp32 rows; anything but 0 or 1 is WT_ERR_INVALID_ARG),
  * "last_batches" (N = the next N pipelined submits are the last of a job: they are decoded one chain per batch, the very
  * last on the encoder's stream, so the pipeline drains sooner; counts down to 0 by itself, may be set with batches in
  * flight), "force_fallback" (test hook: bit mask of contractions sent to the full-range kernels, nothing in flight).
@@ -644,6 +649,15 @@ int wt_vocab_merge_punctuation(const wt_vocab* v, const int64_t* ids, int n, con
  * (0, 0) to (N - 1, F - 1), at most path_cap pairs.  1 <= N <= 447, 1 <= F <= 1500.  Returns the number of path cells, or
  * -WT_ERR_INVALID_ARG. */
 int wt_dtw_path(const float* cost, int N, int F, int32_t* jump, int32_t* path_out, int path_cap);
+
+/* TFLite's SymmetricQuantizeFloats per row of a [rows][K], in fp32 on the host: mx = max |a_k|, scale = mx / 127 and
+ * inv = 127 / mx (both 0 when mx == 0), q_k = clamp(roundf(a_k * inv), -127, 127): ties round away from zero, -128 never
+ * appears.  q [rows][K], scale [rows].  What option "logits_int8" applies to the embedding rows. */
+int wt_quantize_rows_i8(const float* a, int rows, int K, int8_t* q, float* scale);
+/* q [rows][K] (K a multiple of 32) -> the int8 logits head's fragment order, tiled [ceil(rows / 32)][K / 32][64][16]: lane l of
+ * step s of tile t holds q[32 t + (l & 31)][32 s + 16 (l >> 5) .. + 15]; scale_tiled [ceil(rows / 32) * 32].  Rows past `rows`
+ * are zero with scale 0. */
+int wt_tile_rows_i8(const int8_t* q, const float* scale, int rows, int K, int8_t* tiled, float* scale_tiled);
 
 /* ---- the log-mel front end as a free function ---------------------------------------------
  * Replaces whisper::log_mel_spectrogram (whisper.h:123, whisper.cpp:109-216) for callers that hold a

@@ -356,6 +356,12 @@ int wt_dbg_dec_ln_gemm_rows(wt_engine* h, int bf16, int M, int B, int N, int K, 
  * records [M + 1][ceil(V / 32)] in / out, the last row of each a guard the kernel must not write */
 int wt_dbg_dec_logits(wt_engine* h, int bf16, int M, int V, int K, const float* xin, const float* xpart, const float* ln_g,
                       const float* ln_b, const float* E, int blocks, float* logits, uint64_t* records);
+/* The int8 logits head (dec_logits_i8, k_logits_i8.hip, option "logits_int8") over the same inputs: E [V][K]
+ * fp32 is quantised and tiled on the host (wt_quantize_rows_i8, wt_tile_rows_i8) as the engine does it.  logits and
+ * records as above, guard rows included; qx [M][K] and sx [M] (either may be NULL): the kernel's own quantised LayerNorm
+ * rows and their scales. */
+int wt_dbg_dec_logits_i8(wt_engine* h, int M, int V, int K, const float* xin, const float* xpart, const float* ln_g,
+                         const float* ln_b, const float* E, int blocks, float* logits, uint64_t* records, int8_t* qx, float* sx);
 /* select_token over records [B][n_tiles]; ids [B][stride], n_ids [B], finished [B] in / out */
 int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* records, int64_t* ids, int stride, int pos,
                         int32_t* n_ids, int32_t* finished, int64_t eot, int stop_at_eot, int keep_ids);

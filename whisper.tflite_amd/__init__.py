@@ -47,7 +47,7 @@ CAPI_SYMBOLS = [
     "wt_encdec_tokens_full_batch", "wt_encdec_tokens_full_batch_dev", "wt_transcribe_tokens_full_batch_dev",
     "wt_last_segments", "wt_last_segment_text", "wt_vocab_segments", "wt_vocab_seek_step", "wt_last_windows",
     "wt_transcribe_long_batch", "wt_last_file_text", "wt_last_window_files",
-    "wt_vocab_split_words", "wt_vocab_merge_punctuation", "wt_dtw_path",
+    "wt_vocab_split_words", "wt_vocab_merge_punctuation", "wt_dtw_path", "wt_quantize_rows_i8", "wt_tile_rows_i8",
     "wt_engine_set_alignment_heads", "wt_last_words", "wt_last_word_text",
     "wt_last_scores", "wt_last_token_logprobs", "wt_last_segment_scores", "wt_last_decode_info", "wt_last_best_of",
     "wt_language_count", "wt_detect_language_batch", "wt_detect_language_batch_dev", "wt_detect_language_pcm", "wt_last_languages",
@@ -66,7 +66,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_self_attention_bf16", "wt_dbg_cross_attention_bf16", "wt_dbg_encoder_attention_planes", "wt_dbg_gemm_bf16", "wt_dbg_gemm_bf16_ln", "wt_dbg_encoder_attention_bf16",
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_beam_full_step", "wt_dbg_beam_full_finalize",
-    "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_select_token",
+    "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_dec_logits_i8", "wt_dbg_select_token",
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_language_head_rows", "wt_dbg_self_attention_long",
     "wt_dbg_self_attention_prefill", "wt_dbg_self_attention_long_gather",
     "wt_dbg_self_attention_long_bf16", "wt_dbg_self_attention_long_gather_bf16", "wt_dbg_self_attention_prefill_bf16",
@@ -262,6 +262,7 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_dec_ln_gemm_rows.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, fp, ip64, c_int, c_int, fp, fp,
                                               c_int, c_int, fp, fp, fp, fp, c_int, fp, fp]
         L.wt_dbg_dec_logits.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp, fp, c_int, fp, u64p]
+        L.wt_dbg_dec_logits_i8.argtypes = [c_void_p, c_int, c_int, c_int, fp, fp, fp, fp, fp, c_int, fp, u64p, c_void_p, fp]
         L.wt_dbg_select_token.argtypes = [c_void_p, c_int, c_int, u64p, ip64, c_int, c_int, ip32, ip32, c_int64, c_int,
                                           c_int]
         L.wt_language_count.argtypes = [c_void_p]
@@ -343,6 +344,8 @@ def lib() -> ctypes.CDLL:
         L.wt_vocab_split_words.argtypes = [c_void_p, ip64, c_int, c_int, ip32, c_int]
         L.wt_vocab_merge_punctuation.argtypes = [c_void_p, ip64, c_int, ip32, c_int, ip32, c_int]
         L.wt_dtw_path.argtypes = [fp, c_int, c_int, ip32, ip32, c_int]
+        L.wt_quantize_rows_i8.argtypes = [fp, c_int, c_int, c_void_p, fp]
+        L.wt_tile_rows_i8.argtypes = [c_void_p, fp, c_int, c_int, c_void_p, fp]
         L.wt_engine_set_alignment_heads.argtypes = [c_void_p, ip32, c_int]
         L.wt_last_words.argtypes = [c_void_p, c_void_p, c_int]
         L.wt_last_word_text.argtypes = [c_void_p, c_int, c_char_p, c_size_t, POINTER(c_size_t)]
@@ -649,6 +652,31 @@ def dtw_path(cost):
     if n < 0:
         raise WtError(-n, "dtw_path: 1 <= N <= 447 and 1 <= F <= 1500")
     return jump, path[:n].copy()
+
+
+def quantize_rows_i8(a):
+    """TFLite's SymmetricQuantizeFloats per row on the host (wt_quantize_rows_i8): a [rows][K] fp32 ->
+    (q int8 [rows][K], scale float32 [rows])."""
+    a = _f32(a)
+    rows, K = a.shape
+    q, scale = np.zeros((rows, K), np.int8), np.zeros(rows, np.float32)
+    rc = lib().wt_quantize_rows_i8(_fp(a), rows, K, q.ctypes.data_as(c_void_p), _fp(scale))
+    if rc != WT_OK:
+        raise WtError(rc, "quantize_rows_i8")
+    return q, scale
+
+
+def tile_rows_i8(q, scale):
+    """q int8 [rows][K], scale [rows] -> the int8 logits head's table (wt_tile_rows_i8): (tiled int8 [ceil(rows / 32)][K / 32]
+    [64][16], scale_tiled float32 [ceil(rows / 32) * 32])."""
+    q, scale = np.ascontiguousarray(q, np.int8), _f32(scale)
+    rows, K = q.shape
+    n_tiles = (rows + 31) // 32
+    tiled, st = np.full((n_tiles, K // 32, 64, 16), 0x55, np.int8), np.full(n_tiles * 32, np.nan, np.float32)
+    rc = lib().wt_tile_rows_i8(q.ctypes.data_as(c_void_p), _fp(scale), rows, K, tiled.ctypes.data_as(c_void_p), _fp(st))
+    if rc != WT_OK:
+        raise WtError(rc, "tile_rows_i8: K must be a multiple of 32")
+    return tiled, st
 
 
 def log_mel_spectrogram(samples, filters, device_id: int = 0) -> np.ndarray:
@@ -1851,6 +1879,23 @@ class Engine:
         self._check(lib().wt_dbg_dec_logits(self._h, int(bf16), M, V, K, _fp(xin), _fp(xpart), _fp(ln_g), _fp(ln_b), _fp(E),
                                             blocks, _fp(logits), records.ctypes.data_as(POINTER(c_uint64))))
         return logits, records
+
+    def dbg_dec_logits_i8(self, xin, ln_g, ln_b, E, xpart=None, blocks=0, want_logits=True, logits_guard=1.0e30,
+                          records_guard=0xA5A5A5A5A5A5A5A5):
+        """The int8 logits head over dbg_dec_logits' inputs (option logits_int8).  Returns (logits
+        [M + 1][V] or None, records uint64 [M + 1][ceil(V / 32)], qx int8 [M][K], sx float32 [M]): the guard rows as there,
+        qx / sx the kernel's own quantised LayerNorm rows and scales."""
+        xin, ln_g, ln_b, E = _f32(xin), _f32(ln_g), _f32(ln_b), _f32(E)
+        xpart = _f32(xpart) if xpart is not None else None
+        M, K = xin.shape
+        V = E.shape[0]
+        logits = np.full((M + 1, V), logits_guard, np.float32) if want_logits else None
+        records = np.full((M + 1, (V + 31) // 32), records_guard, np.uint64)
+        qx, sx = np.zeros((M, K), np.int8), np.full(M, np.nan, np.float32)
+        self._check(lib().wt_dbg_dec_logits_i8(self._h, M, V, K, _fp(xin), _fp(xpart), _fp(ln_g), _fp(ln_b), _fp(E), blocks,
+                                               _fp(logits), records.ctypes.data_as(POINTER(c_uint64)),
+                                               qx.ctypes.data_as(c_void_p), _fp(sx)))
+        return logits, records, qx, sx
 
     def dbg_language_head(self, x, ln_g, ln_b, tok_emb, lang_lo, n_lang, xpart=None, ids=None, forced_lang=-1):
         """language_head over rows x [rows][d] (+ xpart) against tok_emb [n_vocab][d], language rows lang_lo .. lang_lo +

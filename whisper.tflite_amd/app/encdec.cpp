@@ -38,6 +38,8 @@ void usage(const char* argv0) {
             << "                  with --max-positions: full-length decoding in that mode (option full_bf16)\n"
             << "                  with --max-positions and --inputs a,b --long, --lang auto or --word-timestamps: these too\n"
             << "                  (option full_bf16_all)\n"
+            << "  --int8-logits   the int8 dynamic-range logits head (option logits_int8): int8 embedding rows with one scale\n"
+            << "                  each, activations quantised per row at run time, int32 accumulation\n"
             << "  --max-positions N  full-length greedy decoding over N positions, 32 .. n_text_ctx (default: the\n"
             << "                  reference's 31 positions)\n"
             << "  --timestamps    with --max-positions: decode with timestamps and print one line per segment,\n"
@@ -94,7 +96,7 @@ int main(int argc, char* argv[]) {
       suppress_tokens;
   bool word_timestamps = false, suppress_default = false, suppress_blank = false, resample = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
-       no_condition = false, bf16 = false;
+       no_condition = false, bf16 = false, int8_logits = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], v;
     if (a == "-h" || a == "--help") {
@@ -115,6 +117,10 @@ int main(int argc, char* argv[]) {
     }
     if (a == "--bf16") {
       bf16 = true;
+      continue;
+    }
+    if (a == "--int8-logits") {
+      int8_logits = true;
       continue;
     }
     if (a == "--timestamps") {
@@ -240,6 +246,10 @@ int main(int argc, char* argv[]) {
   }
   if (bf16 && wt_engine_set_option(encdec.handle(), "bf16", 1) != WT_OK) {
     std::cerr << "--bf16: " << wt_last_error(encdec.handle()) << "\n";
+    return 105;
+  }
+  if (int8_logits && wt_engine_set_option(encdec.handle(), "logits_int8", 1) != WT_OK) {
+    std::cerr << "--int8-logits: " << wt_last_error(encdec.handle()) << "\n";
     return 105;
   }
   if (!beam.empty()) {

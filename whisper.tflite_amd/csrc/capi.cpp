@@ -355,6 +355,17 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
     } catch (const std::exception& err) {
       return fail(h, WT_ERR_DEVICE, err.what());
     }
+  } else if (k == "logits_int8") {
+    // the int8 dynamic-range logits head; the first switch makes the int8 table
+    if (value != 0 && value != 1) return fail(h, WT_ERR_INVALID_ARG, "logits_int8 must be 0 or 1");
+    try {
+      e.bind_device();
+      e.set_logits_int8(value != 0);
+    } catch (const wt::Error& err) {
+      return fail(h, err.code, err.what());
+    } catch (const std::exception& err) {
+      return fail(h, WT_ERR_DEVICE, err.what());
+    }
   } else if (k == "input_sample_rate") {
     // input resampling: what the pcm of the PCM entry points holds
     try {
@@ -467,6 +478,7 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "last_batches") *value = e.last_batches;
   else if (k == "cross_absorb_active") *value = e.absorb_active() ? 1 : 0;  // read-only
   else if (k == "bf16") *value = e.bf16;
+  else if (k == "logits_int8") *value = e.logits_int8;
   else if (k == "beam_size") *value = e.beam_size;
   else if (k == "full_beam") *value = e.full_beam;
   else if (k == "full_language") *value = e.full_language;
@@ -1313,6 +1325,18 @@ int wt_dtw_path(const float* cost, int N, int F, int32_t* jump, int32_t* path_ou
   const int cells = wt::dtw_path(cost, N, F, F, jump, path_out ? &path : nullptr, nullptr);
   if (path_out) std::memcpy(path_out, path.data(), size_t(std::min(cells, path_cap)) * 2 * sizeof(int32_t));
   return cells;
+}
+
+int wt_quantize_rows_i8(const float* a, int rows, int K, int8_t* q, float* scale) {
+  if (!a || !q || !scale || rows < 1 || K < 1) return WT_ERR_INVALID_ARG;
+  wt::quantize_rows_i8(a, rows, K, q, scale);
+  return WT_OK;
+}
+
+int wt_tile_rows_i8(const int8_t* q, const float* scale, int rows, int K, int8_t* tiled, float* scale_tiled) {
+  if (!q || !scale || !tiled || !scale_tiled || rows < 1 || K < 32 || K % 32 != 0) return WT_ERR_INVALID_ARG;
+  wt::tile_rows_i8(q, scale, rows, K, tiled, scale_tiled);
+  return WT_OK;
 }
 
 // ------------------------------------------- log-mel as a free function ---

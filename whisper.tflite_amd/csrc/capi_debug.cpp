@@ -1295,6 +1295,39 @@ int wt_dbg_dec_logits(wt_engine* h, int bf16, int M, int V, int K, const float* 
   });
 }
 
+int wt_dbg_dec_logits_i8(wt_engine* h, int M, int V, int K, const float* xin, const float* xpart, const float* ln_g,
+                         const float* ln_b, const float* E, int blocks, float* logits, uint64_t* records, int8_t* qx, float* sx) {
+  if (!h || !xin || !ln_g || !ln_b || !E || !records || M < 1 || M > 128 || V < 1 || blocks < 0 ||
+      (K != 128 && K != 384 && K != 512)) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const int n_tiles = (V + 31) / 32;
+    std::vector<int8_t> q(size_t(V) * K), tiled(size_t(n_tiles) * 32 * K);
+    std::vector<float> sw(V), sw_tiled(size_t(n_tiles) * 32);
+    wt::quantize_rows_i8(E, V, K, q.data(), sw.data());
+    wt::tile_rows_i8(q.data(), sw.data(), V, K, tiled.data(), sw_tiled.data());
+    DevArr<int8_t> dW(tiled), dqx(qx ? size_t(M) * K : 0);
+    DevArr<float> dsw(sw_tiled), dsx(sx ? size_t(M) : 0);
+    const size_t mk = size_t(M) * K;
+    DevArr<float> dxin(mk, xin), dxp(xpart ? mk : 0, xpart), dg(K, ln_g), db(K, ln_b);
+    // [M + 1][V] and [M + 1][n_tiles]: the last row of each is a guard the kernel must not write
+    DevArr<float> dY(logits ? (size_t(M) + 1) * V : 0, logits);
+    DevArr<unsigned long long> dBest((size_t(M) + 1) * n_tiles, reinterpret_cast<const unsigned long long*>(records));
+    wt::DecLogitsI8Args g;
+    g.Wq = dW.p; g.sw = dsw.p; g.V = V; g.K = K; g.M = M; g.blocks = blocks;
+    g.xin = dxin.p; g.xpart = xpart ? dxp.p : nullptr; g.ln_g = dg.p; g.ln_b = db.p;
+    g.Y = logits ? dY.p : nullptr; g.ldy = V; g.best = dBest.p;
+    g.qx_out = qx ? dqx.p : nullptr; g.sx_out = sx ? dsx.p : nullptr;
+    wt::launch_dec_logits_i8(g, h->impl->stream());
+    h->impl->sync();
+    if (logits) dY.to_host(logits);
+    dBest.to_host(reinterpret_cast<unsigned long long*>(records));
+    if (qx) dqx.to_host(qx);
+    if (sx) dsx.to_host(sx);
+  });
+}
+
 int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* records, int64_t* ids, int stride, int pos,
                         int32_t* n_ids, int32_t* finished, int64_t eot, int stop_at_eot, int keep_ids) {
   if (!h || !records || !ids || !n_ids || !finished || B < 1 || n_tiles < 1 || pos < 0 || pos + 1 >= stride) {

@@ -79,6 +79,31 @@ std::vector<unsigned short> tile_weights_bf16(const float* W, int N, int K) {
   return out;
 }
 
+void quantize_rows_i8(const float* a, int rows, int K, int8_t* q, float* scale) {
+  for (int r = 0; r < rows; ++r) {
+    const float* x = a + size_t(r) * K;
+    float mx = 0.0f;
+    for (int k = 0; k < K; ++k) mx = std::max(mx, std::fabs(x[k]));
+    const float inv = mx > 0.0f ? 127.0f / mx : 0.0f;
+    scale[r] = mx > 0.0f ? mx / 127.0f : 0.0f;
+    // roundf: half away from zero in one rounding (trunc(v + 0.5) rounds twice)
+    for (int k = 0; k < K; ++k) q[size_t(r) * K + k] = int8_t(std::min(127.0f, std::max(-127.0f, roundf(x[k] * inv))));
+  }
+}
+
+void tile_rows_i8(const int8_t* q, const float* scale, int rows, int K, int8_t* tiled, float* scale_tiled) {
+  const int n_tiles = (rows + 31) / 32, steps = K / 32;
+  std::memset(tiled, 0, size_t(n_tiles) * 32 * K);
+  for (int t = 0; t < n_tiles; ++t)
+    for (int s = 0; s < steps; ++s)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int n = t * 32 + (lane & 31);
+        if (n >= rows) continue;
+        std::memcpy(tiled + ((size_t(t) * steps + s) * 64 + lane) * 16, q + size_t(n) * K + 32 * s + 16 * (lane >> 5), 16);
+      }
+  for (int n = 0; n < n_tiles * 32; ++n) scale_tiled[n] = n < rows ? scale[n] : 0.0f;
+}
+
 // bf16 storage mode: W [N][K] fp32 -> bf16 [N][Kpad], zero filled
 std::vector<unsigned short> round_weights_bf16(const float* W, int N, int K, int Kpad) {
   std::vector<unsigned short> out(size_t(N) * Kpad, 0);
@@ -1507,6 +1532,30 @@ void Engine::encode_enqueue(const float* d_mel, int batch) {
   enc_slot_ = (enc_slot_ + 1) % kSlots;
 }
 
+// Option "logits_int8": the table of the int8 logits head, made the first time the option is set — the fp32 embedding
+// rows (the decoder's look-up table, on the device in either storage mode) quantised row by row on the host and put
+// into the kernel's fragment order.  Made here, never inside a decode: nothing may be allocated under a capture.
+void Engine::set_logits_int8(bool on) {
+  require_idle();
+  if (on && !tok_emb_q8_) {
+    if (dims_.n_text_state == 0 || !tok_emb) throw Error(kErrUnsupported, "front-end-only engine: no model weights loaded");
+    const int V = dims_.n_vocab, d = dims_.n_text_state, rows = (V + 31) / 32 * 32;
+    if (d != 128 && d != 384 && d != 512) throw Error(kErrUnsupported, "logits_int8: d_model 128, 384 or 512");
+    std::vector<float> E(size_t(V) * d), sw(V), sw_tiled(rows);
+    HIPCHK(hipMemcpy(E.data(), tok_emb, E.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<int8_t> q(E.size()), tiled(size_t(rows) * d);
+    quantize_rows_i8(E.data(), V, d, q.data(), sw.data());
+    tile_rows_i8(q.data(), sw.data(), V, d, tiled.data(), sw_tiled.data());
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, tiled.size()));
+    allocations_.push_back(p);
+    HIPCHK(hipMemcpy(p, tiled.data(), tiled.size(), hipMemcpyHostToDevice));
+    tok_emb_q8_scale_ = upload(sw_tiled);
+    tok_emb_q8_ = static_cast<const int8_t*>(p);
+  }
+  logits_int8 = on ? 1 : 0;
+}
+
 void Engine::set_bf16(bool on) {
   require_idle();
   if (on) ensure_bf16_weights();
@@ -2120,6 +2169,14 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
   // logits against the tied embedding + argmax records (whisper.cpp:379-399); only the last position's rows exist
   // here, the reference computes and drops the others
   const size_t off = size_t(p.np - 1) * B * d;
+  if (logits_int8) {  // the int8 dynamic-range head: the same rows, Y and records, in either storage mode
+    DecLogitsI8Args li;
+    li.Wq = tok_emb_q8_; li.sw = tok_emb_q8_scale_; li.V = V; li.K = d; li.M = B;
+    li.xin = (split ? dw.xb : x) + off; li.xpart = split ? dw.xpart + off : nullptr; li.ln_g = dec_ln_g; li.ln_b = dec_ln_b;
+    li.Y = p.Y; li.ldy = p.ldy; li.best = p.best; li.blocks = p.logits_blocks;
+    timed(tm, 9, [&] { launch_dec_logits_i8(li, st); });
+    return;
+  }
   const TiledW& emb = bf ? tok_emb_tiled_bf_ : tok_emb_tiled;
   DecGemmArgs lg;  // final LayerNorm (of x, or of the two halves a K-split fc2 left) + logits + argmax records
   lg.bf16 = bf; lg.logits_blocks = p.logits_blocks;
@@ -2274,7 +2331,7 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
   // kernels' one-time attribute set-up) and then captures one hipGraph per slot; later calls
   // replay the slot's graph: one host call instead of ~1100. The logits tap stays eager.
   auto key_of = [&](int si) {
-    return std::vector<long long>{si, batch, max_pos, n_prompt, chunks, long(stop_at_eot), fc2_ksplit, bf16, absorbed ? 1 : 0, n_abs, group, stream_override, forced ? 1 : 0, pipelined ? 1 : 0, lang_mode + (cand ? 2 : 0)};
+    return std::vector<long long>{si, batch, max_pos, n_prompt, chunks, long(stop_at_eot), fc2_ksplit, logits_int8, bf16, absorbed ? 1 : 0, n_abs, group, stream_override, forced ? 1 : 0, pipelined ? 1 : 0, lang_mode + (cand ? 2 : 0)};
   };
   // the cached form's graphs are captured for EVERY slot at once (below) and hold each slot's cache pointer: all of
   // them must exist before the capture (need_cross_kv allocates; nothing may be allocated inside a capture)
@@ -2549,7 +2606,7 @@ void Engine::decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids) 
   for (int c0 = 0; c0 < batch; c0 += per_chain) {
     const int nc = std::min(per_chain, batch - c0);
     // (greedy's keys have 14 entries and start with the slot; a beam key starts with -beam_size)
-    const std::vector<long long> key{-K, slot_idx, c0, nc, max_pos, n_prompt, abs_chunks, fc2_ksplit, slot.dec};
+    const std::vector<long long> key{-K, slot_idx, c0, nc, max_pos, n_prompt, abs_chunks, fc2_ksplit, logits_int8, slot.dec};
     replay_or_capture(key, st, use_graphs != 0, "beam-search", [&] {
       enqueue_chain(c0, nc);
       return n_steps;

@@ -311,6 +311,12 @@ class Engine {
   // set_bf16(): the first switch uploads the bf16 weight copies.
   long bf16 = 0;
   void set_bf16(bool on);
+  // 1 = the int8 dynamic-range logits head (k_logits_i8.hip): the one logits launch of decoder_pass
+  // contracts int8 LayerNorm rows (quantised per row at every launch) with the embedding as int8 rows + one fp32 scale
+  // per vocabulary row, in int32.  Set through set_logits_int8(): the first switch makes the table (the fp32 embedding
+  // rows re-quantised on the host); an engine that never sets it allocates nothing.  An entry of every decoder graph key.
+  long logits_int8 = 0;
+  void set_logits_int8(bool on);
   // encoder kernel-class timers (wt_last_kernel_stats): 0 = off, N = event pairs around every launch of every N-th
   // encoder pass; passes without them report zero launches
   long kernel_timers = 1;
@@ -762,6 +768,8 @@ class Engine {
   const float *enc_ln_post_g = nullptr, *enc_ln_post_b = nullptr;
   const float *tok_emb = nullptr, *dec_pos = nullptr, *dec_ln_g = nullptr, *dec_ln_b = nullptr;
   TiledW tok_emb_tiled;  // logits GEMM against the tied embedding
+  const int8_t* tok_emb_q8_ = nullptr;  // option logits_int8: the embedding in tile_rows_i8's order, and its row scales
+  const float* tok_emb_q8_scale_ = nullptr;
   // front end
   const unsigned short* dft_basis_p_ = nullptr;  // [dft_n][dft_k] windowed basis, rows (2 k, 2 k + 1) = (re, im) of bin k, as fp16 planes
   const float* dft_zero_bias_ = nullptr;

@@ -218,6 +218,30 @@ void launch_dec_gemm(const DecGemmArgs& a, int pro, int epi, hipStream_t s);
 void launch_dec_finalize_ln(const float* xin, const float* g, const float* b, float* y, int B, int K,
                             hipStream_t s, const float* xpart = nullptr);
 
+// The int8 dynamic-range logits head (k_logits_i8.hip, option "logits_int8"): the final LayerNorm of
+// xin (+ xpart) as launch_dec_gemm(kProLn, kDecLogits) makes it, each row quantised to int8 with its own scale
+// (quantize_rows_i8's rule, on the device), int32 products against Wq / sw (tile_rows_i8 of quantize_rows_i8 of the
+// embedding), y = ((float)acc * sx[m]) * sw[n], and the same Y / best records.  K in {128, 384, 512}, 1 <= M <= 128,
+// V >= 1, ldy >= V, best_stride (0 = ceil(V / 32)) >= ceil(V / 32); anything else is kErrInvalidArg.
+struct DecLogitsI8Args {
+  const int8_t* Wq = nullptr;  // [ceil(V / 32)][K / 32][64 lanes][16]
+  const float* sw = nullptr;   // [ceil(V / 32) * 32], 0 behind V
+  int V = 0, K = 0, M = 0;
+  const float* xin = nullptr;
+  const float* xpart = nullptr;  // optional: rows = xin + xpart
+  const float* ln_g = nullptr;
+  const float* ln_b = nullptr;
+  float* Y = nullptr;  // optional [M][ldy]
+  int ldy = 0;
+  unsigned long long* best = nullptr;
+  int best_stride = 0;
+  int blocks = 0;  // resident blocks in all (0 = 512), as DecGemmArgs::logits_blocks
+  // debug outputs (optional, written by the blocks with blockIdx.x == 0): the quantised rows [M][K] and their scales [M]
+  int8_t* qx_out = nullptr;
+  float* sx_out = nullptr;
+};
+void launch_dec_logits_i8(const DecLogitsI8Args& a, hipStream_t s);
+
 // ------------------------------------------------------------- LayerNorm ---
 // y[m][:] = (x[m][:] - mean) * rstd * g + b, eps 1e-5, one wavefront per row.
 void launch_layernorm(const float* x, float* y, const float* g, const float* b, int M, int d,
@@ -819,6 +843,13 @@ std::vector<unsigned short> tile_weights_bf16(const float* W, int N, int K);
 // lane (l & 31, l >> 5) of tile t, step s holds W[32t + (l & 31)][16s + 8(l >> 5) .. +7] * scale as hi = fp16(v),
 // lo = fp16(v - hi).  *scale = f16_scale_for(max |W|).  K % 16 == 0.
 std::vector<unsigned short> tile_weights_f16(const float* W, int N, int K, float* scale);
+// TFLite's SymmetricQuantizeFloats per row of a [rows][K], in fp32: mx = max |a_k|, scale = mx / 127, inv = 127 / mx
+// (both 0 when mx == 0), q_k = clamp(roundf(a_k * inv), -127, 127) (half away from zero; -128 never appears)
+void quantize_rows_i8(const float* a, int rows, int K, int8_t* q, float* scale);
+// q [rows][K] int8 (K % 32 == 0) -> the int8 logits head's fragment order [ceil(rows/32)][K/32][64 lanes][16]: lane
+// (l & 31, l >> 5) of tile t, step s holds q[32t + (l & 31)][32s + 16(l >> 5) .. +15]; scale [rows] -> scale_tiled
+// [ceil(rows/32) * 32]; rows past `rows` are zero with scale 0
+void tile_rows_i8(const int8_t* q, const float* scale, int rows, int K, int8_t* tiled, float* scale_tiled);
 // Wq [d][d] -> [head][d / 4][64 outputs][4 k] for cross_attention_step's in-kernel query projection
 std::vector<float> cross_q_layout(const float* Wq, int d);
 // The absorbed cross-attention's fused query matrix (engine.cpp): A [heads * d][d], A_h = c0 Wk_h^T Wq_h, and
