@@ -156,6 +156,14 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * rows + one fp32 scale per vocabulary row (wt_quantize_rows_i8 of the model's fp32 rows, made at the first switch: 1 byte
  * per element streamed where the default head streams 4), y = ((float)acc * s_row) * s_column; both storage modes, every
  * graph key; language detection keeps its fp32 rows; anything but 0 or 1 is WT_ERR_INVALID_ARG),
+ * "decoder_int8" (0 = default; 1 = the int8 dynamic-range decoder blocks, DESIGN.md section 38: the five Linear matrices of
+ * every decoder layer of the model file (q|k|v, attention out, cross-attention out, fc1, fc2) are int8 rows + one fp32 scale
+ * per output (wt_quantize_rows_i8 of the model's fp32 rows, made at the first switch: 1 byte per element streamed where the
+ * default streams 4), their input rows are quantised per row over the whole K at every launch, the sums are int32 and
+ * y = ((float)acc * s_row) * s_column + bias; both storage modes, every decoding mode, every graph key; the absorbed
+ * cross-attention's derived query matrix, the cached cross-attention form's two projections and language detection keep
+ * their format, and "fc2_ksplit" has no effect while it is on; independent of "logits_int8" (both = the all-int8 decoder);
+ * anything but 0 or 1 is WT_ERR_INVALID_ARG),
  * "last_batches" (N = the next N pipelined submits are the last of a job: they are decoded one chain per batch, the very
  * last on the encoder's stream, so the pipeline drains sooner; counts down to 0 by itself, may be set with batches in
  * flight), "force_fallback" (test hook: bit mask of contractions sent to the full-range kernels, nothing in flight).

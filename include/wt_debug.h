@@ -362,6 +362,17 @@ int wt_dbg_dec_logits(wt_engine* h, int bf16, int M, int V, int K, const float* 
  * rows and their scales. */
 int wt_dbg_dec_logits_i8(wt_engine* h, int M, int V, int K, const float* xin, const float* xpart, const float* ln_g,
                          const float* ln_b, const float* E, int blocks, float* logits, uint64_t* records, int8_t* qx, float* sx);
+/* The int8 decoder-block GEMM (dec_gemm_i8, k_dec_gemm_i8.hip, option "decoder_int8"): W [N][K] fp32 is
+ * quantised and tiled on the host (wt_quantize_rows_i8, wt_tile_rows_i8) as the engine does it.  pro 0: rows X [M][ldx];
+ * pro 1: the LayerNorm (ln_g, ln_b) of xin [M][K] (+ xpart), or with ids [B][ids_stride] of the token + positional
+ * embedding of M = positions x B rows (pos_start [B] optional: the ragged rows; n_pos rows of pos_emb).  epi 0: Y = R +
+ * (t + bias), R [M][ldy] or R == Y (in place); 1: t + bias; 2: gelu(t + bias).  Y [M + 4][ldy] and xout [M + 1][K]
+ * (optional) are in / out, the rows behind M guards; qx [M][K] and sx [M] (optional): the kernel's own quantised rows
+ * and their scales.  The tap checks only what its copies need: the kernel contract is the launcher's to refuse. */
+int wt_dbg_dec_gemm_i8(wt_engine* h, int pro, int epi, int M, int B, int N, int K, const float* X, int ldx, const float* xin,
+                       const float* xpart, const int64_t* ids, int ids_stride, int pos, const float* tok_emb, const float* pos_emb,
+                       int n_vocab, int n_pos, const int32_t* pos_start, const float* ln_g, const float* ln_b, const float* W,
+                       const float* bias, const float* R, int ldy, int ksplit, float* Y, float* xout, int8_t* qx, float* sx);
 /* select_token over records [B][n_tiles]; ids [B][stride], n_ids [B], finished [B] in / out */
 int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* records, int64_t* ids, int stride, int pos,
                         int32_t* n_ids, int32_t* finished, int64_t eot, int stop_at_eot, int keep_ids);

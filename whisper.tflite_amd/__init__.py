@@ -66,7 +66,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_self_attention_bf16", "wt_dbg_cross_attention_bf16", "wt_dbg_encoder_attention_planes", "wt_dbg_gemm_bf16", "wt_dbg_gemm_bf16_ln", "wt_dbg_encoder_attention_bf16",
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_beam_full_step", "wt_dbg_beam_full_finalize",
-    "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_dec_logits_i8", "wt_dbg_select_token",
+    "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_dec_logits_i8", "wt_dbg_dec_gemm_i8", "wt_dbg_select_token",
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_language_head_rows", "wt_dbg_self_attention_long",
     "wt_dbg_self_attention_prefill", "wt_dbg_self_attention_long_gather",
     "wt_dbg_self_attention_long_bf16", "wt_dbg_self_attention_long_gather_bf16", "wt_dbg_self_attention_prefill_bf16",
@@ -263,6 +263,8 @@ def lib() -> ctypes.CDLL:
                                               c_int, c_int, fp, fp, fp, fp, c_int, fp, fp]
         L.wt_dbg_dec_logits.argtypes = [c_void_p, c_int, c_int, c_int, c_int, fp, fp, fp, fp, fp, c_int, fp, u64p]
         L.wt_dbg_dec_logits_i8.argtypes = [c_void_p, c_int, c_int, c_int, fp, fp, fp, fp, fp, c_int, fp, u64p, c_void_p, fp]
+        L.wt_dbg_dec_gemm_i8.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, c_int, fp, fp, ip64, c_int, c_int,
+                                         fp, fp, c_int, c_int, ip32, fp, fp, fp, fp, fp, c_int, c_int, fp, fp, c_void_p, fp]
         L.wt_dbg_select_token.argtypes = [c_void_p, c_int, c_int, u64p, ip64, c_int, c_int, ip32, ip32, c_int64, c_int,
                                           c_int]
         L.wt_language_count.argtypes = [c_void_p]
@@ -1896,6 +1898,43 @@ class Engine:
                                                _fp(logits), records.ctypes.data_as(POINTER(c_uint64)),
                                                qx.ctypes.data_as(c_void_p), _fp(sx)))
         return logits, records, qx, sx
+
+    def dbg_dec_gemm_i8(self, W, bias, X=None, xin=None, xpart=None, ids=None, pos=0, tok_emb=None, pos_emb=None,
+                        pos_start=None, ln_g=None, ln_b=None, R=None, in_place=False, pro=None, epi=1, M=None, B=None,
+                        ldy=None, ksplit=1, guard=1.0e30):
+        """The int8 decoder-block GEMM (option decoder_int8) over W [N][K] fp32, quantised and tiled
+        by the tap.  pro 0 (default with X): rows X [M][ldx]; pro 1: the LayerNorm of xin (+ xpart) or of the embedding
+        rows of ids [B][stride] (M = positions x B rows, pos_start [B] optional).  epi 0 residual (R [M][N], in_place: R
+        is the Y buffer itself), 1 bias, 2 bias + GELU.  Returns (Y [M + 4][ldy], the last four rows `guard`; xout
+        [M + 1][K] zeros-initialised; qx int8 [M][K]; sx float32 [M]): qx / sx the kernel's own quantised rows and scales."""
+        W = _f32(W)
+        N, K = W.shape
+        f = lambda a: _f32(a) if a is not None else None
+        bias, X, xin, xpart, tok_emb, pos_emb, ln_g, ln_b, R = (f(a) for a in (bias, X, xin, xpart, tok_emb, pos_emb, ln_g, ln_b, R))
+        ids_a = np.ascontiguousarray(ids, dtype=np.int64) if ids is not None else None
+        ps = np.ascontiguousarray(pos_start, dtype=np.int32) if pos_start is not None else None
+        if pro is None:
+            pro = 0 if X is not None else 1
+        stride = 0
+        if ids_a is not None:
+            B, stride = ids_a.shape
+            M = M or B
+        elif M is None:
+            M = (X if X is not None else xin).shape[0]
+        B = B or max(M, 1)
+        ldy = ldy or N
+        Y = np.full((M + 4, ldy), guard, np.float32)
+        if R is not None:
+            Y[:M, :R.shape[1]] = R if in_place else guard
+        xout = np.zeros((M + 1, K), np.float32)
+        qx, sx = np.zeros((M, K), np.int8), np.full(M, np.nan, np.float32)
+        self._check(lib().wt_dbg_dec_gemm_i8(
+            self._h, pro, epi, M, B, N, K, _fp(X), X.shape[1] if X is not None else 0, _fp(xin), _fp(xpart),
+            _ip64(ids_a) if ids_a is not None else None, stride, pos, _fp(tok_emb), _fp(pos_emb),
+            tok_emb.shape[0] if tok_emb is not None else 0, pos_emb.shape[0] if pos_emb is not None else 0,
+            _ip32(ps) if ps is not None else None, _fp(ln_g), _fp(ln_b), _fp(W), _fp(bias),
+            _fp(Y) if (in_place and R is not None) else _fp(R), ldy, ksplit, _fp(Y), _fp(xout), qx.ctypes.data_as(c_void_p), _fp(sx)))
+        return Y, xout, qx, sx
 
     def dbg_language_head(self, x, ln_g, ln_b, tok_emb, lang_lo, n_lang, xpart=None, ids=None, forced_lang=-1):
         """language_head over rows x [rows][d] (+ xpart) against tok_emb [n_vocab][d], language rows lang_lo .. lang_lo +

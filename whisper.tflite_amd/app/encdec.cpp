@@ -40,6 +40,8 @@ void usage(const char* argv0) {
             << "                  (option full_bf16_all)\n"
             << "  --int8-logits   the int8 dynamic-range logits head (option logits_int8): int8 embedding rows with one scale\n"
             << "                  each, activations quantised per row at run time, int32 accumulation\n"
+            << "  --int8-decoder  the int8 dynamic-range decoder blocks (option decoder_int8): the decoder layers' Linear\n"
+            << "                  matrices as int8 rows with one scale each, their inputs quantised per row at run time\n"
             << "  --max-positions N  full-length greedy decoding over N positions, 32 .. n_text_ctx (default: the\n"
             << "                  reference's 31 positions)\n"
             << "  --timestamps    with --max-positions: decode with timestamps and print one line per segment,\n"
@@ -96,7 +98,7 @@ int main(int argc, char* argv[]) {
       suppress_tokens;
   bool word_timestamps = false, suppress_default = false, suppress_blank = false, resample = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
-       no_condition = false, bf16 = false, int8_logits = false;
+       no_condition = false, bf16 = false, int8_logits = false, int8_decoder = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], v;
     if (a == "-h" || a == "--help") {
@@ -121,6 +123,10 @@ int main(int argc, char* argv[]) {
     }
     if (a == "--int8-logits") {
       int8_logits = true;
+      continue;
+    }
+    if (a == "--int8-decoder") {
+      int8_decoder = true;
       continue;
     }
     if (a == "--timestamps") {
@@ -250,6 +256,10 @@ int main(int argc, char* argv[]) {
   }
   if (int8_logits && wt_engine_set_option(encdec.handle(), "logits_int8", 1) != WT_OK) {
     std::cerr << "--int8-logits: " << wt_last_error(encdec.handle()) << "\n";
+    return 105;
+  }
+  if (int8_decoder && wt_engine_set_option(encdec.handle(), "decoder_int8", 1) != WT_OK) {
+    std::cerr << "--int8-decoder: " << wt_last_error(encdec.handle()) << "\n";
     return 105;
   }
   if (!beam.empty()) {

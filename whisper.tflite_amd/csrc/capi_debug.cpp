@@ -1328,6 +1328,56 @@ int wt_dbg_dec_logits_i8(wt_engine* h, int M, int V, int K, const float* xin, co
   });
 }
 
+int wt_dbg_dec_gemm_i8(wt_engine* h, int pro, int epi, int M, int B, int N, int K, const float* X, int ldx, const float* xin,
+                       const float* xpart, const int64_t* ids, int ids_stride, int pos, const float* tok_emb, const float* pos_emb,
+                       int n_vocab, int n_pos, const int32_t* pos_start, const float* ln_g, const float* ln_b, const float* W,
+                       const float* bias, const float* R, int ldy, int ksplit, float* Y, float* xout, int8_t* qx, float* sx) {
+  // only what the tap's own copies need; every rule of the kernel contract is the launcher's to refuse
+  if (!h || !W || !Y || M < 0 || M > 1024 || B < 1 || N < 1 || N > (1 << 16) || K < 32 || K > 8192 || K % 32 != 0 || ldx < 0 ||
+      ldy < 1 || ldy > (1 << 16)) {
+    return WT_ERR_INVALID_ARG;
+  }
+  const int np = (M + B - 1) / B;
+  if (ids && (!tok_emb || !pos_emb || n_vocab < 1 || pos < 0 || pos + np > ids_stride || (!pos_start && pos + np > n_pos) || n_pos < 1)) {
+    return WT_ERR_INVALID_ARG;
+  }
+  return guarded(h, [&] {
+    const int n_tiles = (N + 31) / 32;
+    std::vector<int8_t> q(size_t(N) * K), tiled(size_t(n_tiles) * 32 * K);
+    std::vector<float> sw(N), sw_tiled(size_t(n_tiles) * 32);
+    wt::quantize_rows_i8(W, N, K, q.data(), sw.data());
+    wt::tile_rows_i8(q.data(), sw.data(), N, K, tiled.data(), sw_tiled.data());
+    DevArr<int8_t> dW(tiled), dqx(qx ? size_t(M) * K : 0);
+    DevArr<float> dsw(sw_tiled), dsx(sx ? size_t(M) : 0);
+    const size_t mk = size_t(M) * K;
+    DevArr<float> dX(X ? size_t(M) * ldx : 0, X), dxin(xin ? mk : 0, xin), dxp(xpart ? mk : 0, xpart);
+    DevArr<long long> dids(ids ? size_t(B) * ids_stride : 0, reinterpret_cast<const long long*>(ids));
+    DevArr<float> dtok(ids ? size_t(n_vocab) * K : 0, tok_emb), dpos(ids ? size_t(n_pos) * K : 0, pos_emb);
+    DevArr<int> dps(pos_start ? size_t(B) : 0, pos_start);
+    DevArr<float> dg(ln_g ? K : 0, ln_g), db(ln_b ? K : 0, ln_b), dB(bias ? N : 0, bias);
+    const bool in_place = R == Y;  // the residual stream updated in place, as the engine does it
+    DevArr<float> dR(R && !in_place ? size_t(M) * ldy : 0, R);
+    // [M + 4][ldy] and [M + 1][K]: the rows behind M are guards the kernel must not write
+    DevArr<float> dY((size_t(M) + 4) * ldy, Y), dxo(xout ? mk + K : 0, xout);
+    wt::DecGemmI8Args g;
+    g.Wq = dW.p; g.sw = dsw.p; g.N = N; g.K = K; g.M = M; g.B = B; g.X = X ? dX.p : nullptr; g.ldx = ldx;
+    g.xin = xin ? dxin.p : nullptr; g.xpart = xpart ? dxp.p : nullptr; g.xout = xout ? dxo.p : nullptr;
+    g.ln_g = ln_g ? dg.p : nullptr; g.ln_b = ln_b ? db.p : nullptr;
+    if (ids) {
+      g.ids = dids.p; g.ids_stride = ids_stride; g.pos = pos; g.tok_emb = dtok.p; g.pos_emb = dpos.p; g.n_vocab = n_vocab;
+      g.pos_start = pos_start ? dps.p : nullptr; g.n_ctx = n_pos;
+    }
+    g.bias = bias ? dB.p : nullptr; g.R = in_place ? dY.p : (R ? dR.p : nullptr); g.Y = dY.p; g.ldy = ldy; g.ksplit = ksplit;
+    g.qx_out = qx ? dqx.p : nullptr; g.sx_out = sx ? dsx.p : nullptr;
+    wt::launch_dec_gemm_i8(g, pro, epi, h->impl->stream());
+    h->impl->sync();
+    dY.to_host(Y);
+    if (xout) dxo.to_host(xout);
+    if (qx) dqx.to_host(qx);
+    if (sx) dsx.to_host(sx);
+  });
+}
+
 int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* records, int64_t* ids, int stride, int pos,
                         int32_t* n_ids, int32_t* finished, int64_t eot, int stop_at_eot, int keep_ids) {
   if (!h || !records || !ids || !n_ids || !finished || B < 1 || n_tiles < 1 || pos < 0 || pos + 1 >= stride) {

@@ -1,5 +1,6 @@
-// Row helpers shared by the decoder kernels (k_decoder.hip, k_logits_i8.hip): the row sources of the residual stream,
-// the LayerNorm statistics of a row spread over 8 lanes, and the ordering rules of the argmax records.
+// Row helpers shared by the decoder kernels (k_decoder.hip, k_logits_i8.hip, k_dec_gemm_i8.hip): the row sources of the
+// residual stream, the LayerNorm statistics of a row spread over 8 lanes, the per-row int8 quantiser of the two int8
+// kernels, and the ordering rules of the argmax records.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -87,6 +88,48 @@ __device__ __forceinline__ void row_stats(const f32x4 (&v)[NF4], int K, float* m
   q += __shfl_xor(q, 4, 64);
   *mean = m;
   *rstd = rsqrtf(q / (float)K + 1e-5f);
+}
+
+// The LayerNorm of a row held by 8 lanes, in place, from the gain | shift parked in LDS (lnp [2][K]); returns this lane's
+// share of max |.| of the normalised row.
+template <int NF4>
+__device__ __forceinline__ float ln_apply_max(f32x4 (&v)[NF4], const float* lnp, int K, int sub, float mean, float rstd) {
+  float mx = 0.0f;
+#pragma unroll
+  for (int j = 0; j < NF4; ++j) {
+    const int c = (sub + 8 * j) * 4;
+    const f32x4 gg = *reinterpret_cast<const f32x4*>(&lnp[c]);
+    const f32x4 bb = *reinterpret_cast<const f32x4*>(&lnp[K + c]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[j][e] = (v[j][e] - mean) * rstd * gg[e] + bb[e];
+      mx = fmaxf(mx, fabsf(v[j][e]));
+    }
+  }
+  return mx;
+}
+
+// TFLite's SymmetricQuantizeFloats, the scales of a row whose 8 lanes each hold their share of max |a_k|: IEEE
+// divisions, both results 0 for an all-zero row
+__device__ __forceinline__ void row_scale_i8(float mx, float* sx, float* inv) {
+  mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 4, 64));
+  *sx = mx > 0.0f ? __fdiv_rn(mx, 127.0f) : 0.0f;
+  *inv = mx > 0.0f ? __fdiv_rn(127.0f, mx) : 0.0f;
+}
+// ... and one element: the product is rounded once (never contracted into roundf's own arithmetic), half away from
+// zero, then clamped to [-127, 127]
+__device__ __forceinline__ unsigned quant_i8(float a, float inv) {
+  const float r = fminf(fmaxf(roundf(__fmul_rn(a, inv)), -127.0f), 127.0f);
+  return (unsigned)(int)r & 0xFFu;
+}
+__device__ __forceinline__ unsigned quant4_i8(const f32x4& v, float inv) {
+  return quant_i8(v[0], inv) | (quant_i8(v[1], inv) << 8) | (quant_i8(v[2], inv) << 16) | (quant_i8(v[3], inv) << 24);
+}
+
+__device__ __forceinline__ float gelu_erf(float x) {
+  return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }
 
 }  // namespace

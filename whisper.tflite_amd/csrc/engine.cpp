@@ -1556,6 +1556,42 @@ void Engine::set_logits_int8(bool on) {
   logits_int8 = on ? 1 : 0;
 }
 
+// Option "decoder_int8": the int8 tables of the decoder layers' five Linear matrices, made the first time the option is
+// set from the model file's fp32 rows (as ensure_bf16_weights makes the bf16 copies): each output row quantised on the
+// host (quantize_rows_i8) and put into the kernel's fragment order (tile_rows_i8).  13 d^2 bytes per layer + scales.
+void Engine::set_decoder_int8(bool on) {
+  require_idle();
+  if (on && dec_blocks_q8_.empty()) {
+    if (dims_.n_text_state == 0) throw Error(kErrUnsupported, "front-end-only engine: no model weights loaded");
+    const WtwFile file(weights_path_);
+    const int d = dims_.n_text_state;
+    const size_t dd = size_t(d) * d;
+    auto table = [&](const float* W, int N, int K) {
+      std::vector<int8_t> q(size_t(N) * K), tiled(q.size());
+      std::vector<float> sw(N), sw_tiled(N);
+      quantize_rows_i8(W, N, K, q.data(), sw.data());
+      tile_rows_i8(q.data(), sw.data(), N, K, tiled.data(), sw_tiled.data());  // (N is a multiple of 32: no padding rows)
+      void* p = nullptr;
+      HIPCHK(hipMalloc(&p, tiled.size()));
+      allocations_.push_back(p);
+      HIPCHK(hipMemcpy(p, tiled.data(), tiled.size(), hipMemcpyHostToDevice));
+      return Int8W{static_cast<const int8_t*>(p), upload(sw_tiled)};
+    };
+    std::vector<DecBlockInt8> blocks(size_t(dims_.n_text_layer));
+    for (int l = 0; l < dims_.n_text_layer; ++l) {
+      const std::string blk = "decoder.blocks." + std::to_string(l);
+      DecBlockInt8& b = blocks[size_t(l)];
+      b.wqkv = table(fused_qkv_weight(file, blk + ".attn", d).data(), 3 * d, d);
+      b.wo = table(file.get(blk + ".attn.out.weight", dd), d, d);
+      b.cross_wo = table(file.get(blk + ".cross_attn.out.weight", dd), d, d);
+      b.w1 = table(file.get(blk + ".mlp.0.weight", 4 * dd), 4 * d, d);
+      b.w2 = table(file.get(blk + ".mlp.2.weight", 4 * dd), d, 4 * d);
+    }
+    dec_blocks_q8_ = std::move(blocks);
+  }
+  decoder_int8 = on ? 1 : 0;
+}
+
 void Engine::set_bf16(bool on) {
   require_idle();
   if (on) ensure_bf16_weights();
@@ -2061,8 +2097,21 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
     return bf ? static_cast<void*>(reinterpret_cast<unsigned short*>(base) + elems) : static_cast<void*>(base + elems);
   };
   float* const x = dw.xd;  // residual stream [rows][d], updated in place by the residual GEMMs
+  // A Linear of the model file: dec_gemm on the storage mode's planes, or with option decoder_int8 the same operands on
+  // the int8 dynamic-range kernel; the cached form's kProCombine out-projection stays on dec_gemm
+  auto linear = [&](const DecGemmArgs& a, const Int8W* q8, int pro, int epi) {
+    if (!q8 || pro == kProCombine) return launch_dec_gemm(a, pro, epi, st);
+    DecGemmI8Args g;
+    g.Wq = q8->w; g.sw = q8->scale; g.N = a.N; g.K = a.K; g.M = a.M; g.B = a.B; g.X = a.X; g.ldx = a.ldx;
+    g.xin = a.xin; g.xpart = a.xpart; g.xout = a.xout; g.ln_g = a.ln_g; g.ln_b = a.ln_b;
+    g.ids = a.ids; g.ids_stride = a.ids_stride; g.pos = a.pos; g.tok_emb = a.tok_emb; g.pos_emb = a.pos_emb;
+    g.n_vocab = a.n_vocab; g.pos_start = a.pos_start; g.n_ctx = a.n_ctx;
+    g.bias = a.bias; g.R = a.R; g.Y = a.Y; g.ldy = a.ldy; g.ksplit = a.ksplit;
+    launch_dec_gemm_i8(g, pro, epi, st);
+  };
   for (int l = 0; l < c.n_text_layer; ++l) {
     const DecBlockWeights& w = bf ? dec_blocks_bf_[l] : dec_blocks_[l];
+    const DecBlockInt8* const w8 = decoder_int8 ? &dec_blocks_q8_[size_t(l)] : nullptr;
     DecGemmArgs q;  // LN + fused q|k|v projection (+ token/positional embedding at layer 0)
     q.bf16 = bf;
     q.Wt = w.wqkv.w; q.w_scale = w.wqkv.scale; q.N = 3 * d; q.K = d; q.B = B; q.M = M;
@@ -2076,7 +2125,7 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
       q.pos_start = p.pos_start; q.n_ctx = c.n_text_ctx;
     }
     q.bias = w.bqkv; q.Y = dw.qkvd; q.ldy = 3 * d;
-    timed(tm, 0, [&] { launch_dec_gemm(q, kProLn, kDecBias, st); });
+    timed(tm, 0, [&] { linear(q, w8 ? &w8->wqkv : nullptr, kProLn, kDecBias); });
     void* const kc = cache_at(p.self_kv, (size_t(l) * 2 + 0) * self_slab);
     void* const vc = cache_at(p.self_kv, (size_t(l) * 2 + 1) * self_slab);
     timed(tm, 1, [&] {
@@ -2099,7 +2148,7 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
     o.bf16 = bf;
     o.Wt = w.wo.w; o.w_scale = w.wo.scale; o.N = d; o.K = d; o.B = B; o.M = M; o.X = dw.attd; o.ldx = d;
     o.bias = w.bo; o.R = x; o.Y = x; o.ldy = d;
-    timed(tm, 2, [&] { launch_dec_gemm(o, kProNone, kDecResid, st); });
+    timed(tm, 2, [&] { linear(o, w8 ? &w8->wo : nullptr, kProNone, kDecResid); });
 
     DecGemmArgs co;  // x += (cross-attention context) . Wco^T + bco
     co.bf16 = bf;
@@ -2148,14 +2197,14 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
       }
       co.cross_ws = dw.cross_ws; co.heads = H; co.chunks = p.chunks;  // the out-projection's prologue combines the chunks
     }
-    timed(tm, 5, [&] { launch_dec_gemm(co, p.absorbed ? kProNone : kProCombine, kDecResid, st); });
+    timed(tm, 5, [&] { linear(co, w8 ? &w8->cross_wo : nullptr, p.absorbed ? kProNone : kProCombine, kDecResid); });
 
     DecGemmArgs f1;  // LN + fc1 + GELU
     f1.bf16 = bf;
     f1.Wt = w.w1.w; f1.w_scale = w.w1.scale; f1.N = 4 * d; f1.K = d; f1.B = B; f1.M = M;
     f1.xin = x; f1.ln_g = w.mlp_ln_g; f1.ln_b = w.mlp_ln_b;
     f1.bias = w.b1; f1.Y = dw.hd; f1.ldy = 4 * d;
-    timed(tm, 6, [&] { launch_dec_gemm(f1, kProLn, kDecBiasGelu, st); });
+    timed(tm, 6, [&] { linear(f1, w8 ? &w8->w1 : nullptr, kProLn, kDecBiasGelu); });
     DecGemmArgs f2;  // x += h . W2^T + b2
     f2.bf16 = bf;
     f2.Wt = w.w2.w; f2.w_scale = w.w2.scale; f2.N = d; f2.K = 4 * d; f2.B = B; f2.M = M; f2.X = dw.hd; f2.ldx = 4 * d;
@@ -2163,7 +2212,7 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
     if (split) {  // x stays in two halves for the next kProLn consumer: the next layer's qkv, the logits GEMM, language_head
       f2.Y = dw.xb; f2.ksplit = 2; f2.part = dw.xpart;
     }
-    timed(tm, 7, [&] { launch_dec_gemm(f2, kProNone, kDecResid, st); });
+    timed(tm, 7, [&] { linear(f2, w8 ? &w8->w2 : nullptr, kProNone, kDecResid); });
   }
   if (!p.best) return;
   // logits against the tied embedding + argmax records (whisper.cpp:379-399); only the last position's rows exist
@@ -2331,7 +2380,7 @@ void Engine::decode_enqueue(int batch, int slot_idx, float* logits_host, int log
   // kernels' one-time attribute set-up) and then captures one hipGraph per slot; later calls
   // replay the slot's graph: one host call instead of ~1100. The logits tap stays eager.
   auto key_of = [&](int si) {
-    return std::vector<long long>{si, batch, max_pos, n_prompt, chunks, long(stop_at_eot), fc2_ksplit, logits_int8, bf16, absorbed ? 1 : 0, n_abs, group, stream_override, forced ? 1 : 0, pipelined ? 1 : 0, lang_mode + (cand ? 2 : 0)};
+    return std::vector<long long>{si, batch, max_pos, n_prompt, chunks, long(stop_at_eot), fc2_ksplit, int8_key(), bf16, absorbed ? 1 : 0, n_abs, group, stream_override, forced ? 1 : 0, pipelined ? 1 : 0, lang_mode + (cand ? 2 : 0)};
   };
   // the cached form's graphs are captured for EVERY slot at once (below) and hold each slot's cache pointer: all of
   // them must exist before the capture (need_cross_kv allocates; nothing may be allocated inside a capture)
@@ -2606,7 +2655,7 @@ void Engine::decode_beam(int batch, int slot_idx, int64_t* ids, int32_t* n_ids) 
   for (int c0 = 0; c0 < batch; c0 += per_chain) {
     const int nc = std::min(per_chain, batch - c0);
     // (greedy's keys have 14 entries and start with the slot; a beam key starts with -beam_size)
-    const std::vector<long long> key{-K, slot_idx, c0, nc, max_pos, n_prompt, abs_chunks, fc2_ksplit, logits_int8, slot.dec};
+    const std::vector<long long> key{-K, slot_idx, c0, nc, max_pos, n_prompt, abs_chunks, fc2_ksplit, int8_key(), slot.dec};
     replay_or_capture(key, st, use_graphs != 0, "beam-search", [&] {
       enqueue_chain(c0, nc);
       return n_steps;

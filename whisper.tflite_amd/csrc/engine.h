@@ -317,6 +317,17 @@ class Engine {
   // rows re-quantised on the host); an engine that never sets it allocates nothing.  An entry of every decoder graph key.
   long logits_int8 = 0;
   void set_logits_int8(bool on);
+  // 1 = the int8 dynamic-range decoder blocks (k_dec_gemm_i8.hip): decoder_pass runs the five Linear
+  // matrices of the model file's decoder layers — qkv, attention out, cross-attention out (absorbed form), fc1, fc2 — as
+  // int8 rows + one fp32 scale per output, against activation rows quantised per row at every launch, in int32; both
+  // storage modes (the launches read and write fp32 rows in either).  Staying on dec_gemm: wq_abs (derived from the
+  // absorbed form, not a matrix of the model file), the cached form's cross query and its kProCombine out-projection,
+  // and the language heads.  fc2 is never split over K while it is on (fc2_split).  Independent of logits_int8; both on
+  // is the all-int8 decoder.  Set through set_decoder_int8(): the first switch makes the tables; an engine that never
+  // sets it allocates nothing.  Shares logits_int8's entry of every decoder graph key (int8_key).
+  long decoder_int8 = 0;
+  void set_decoder_int8(bool on);
+  long long int8_key() const { return logits_int8 + 2 * decoder_int8; }
   // encoder kernel-class timers (wt_last_kernel_stats): 0 = off, N = event pairs around every launch of every N-th
   // encoder pass; passes without them report zero launches
   long kernel_timers = 1;
@@ -770,6 +781,14 @@ class Engine {
   TiledW tok_emb_tiled;  // logits GEMM against the tied embedding
   const int8_t* tok_emb_q8_ = nullptr;  // option logits_int8: the embedding in tile_rows_i8's order, and its row scales
   const float* tok_emb_q8_scale_ = nullptr;
+  struct Int8W {  // option decoder_int8: a Linear matrix in tile_rows_i8's order, and its per-output scales
+    const int8_t* w = nullptr;
+    const float* scale = nullptr;
+  };
+  struct DecBlockInt8 {
+    Int8W wqkv, wo, cross_wo, w1, w2;
+  };
+  std::vector<DecBlockInt8> dec_blocks_q8_;  // empty until the option is first set
   // front end
   const unsigned short* dft_basis_p_ = nullptr;  // [dft_n][dft_k] windowed basis, rows (2 k, 2 k + 1) = (re, im) of bin k, as fp16 planes
   const float* dft_zero_bias_ = nullptr;
@@ -830,7 +849,8 @@ class Engine {
   void decoder_pass(const DecPass& p, hipStream_t st);
   int cross_chunks_for(int batch) const;              // key chunks of the cached cross-attention (option cross_chunks)
   int abs_chunks_for(int clips, int blocks) const;    // key chunks of the absorbed one for ~`blocks` blocks (option abs_chunks)
-  bool fc2_split() const { return fc2_ksplit == 2 && (4 * dims_.n_text_state) % 256 == 0; }
+  // (never with decoder_int8: the int8 fc2 streams a quarter of the bytes and hands x on whole)
+  bool fc2_split() const { return fc2_ksplit == 2 && !decoder_int8 && (4 * dims_.n_text_state) % 256 == 0; }
   void check_prompt_ids(const std::vector<long long>& prompt, int code) const;  // throws Error(code, ..) outside the vocabulary
   // language_head outputs, one set per decoder workspace (128 rows whatever the batch), and the pinned copies a
   // synchronous call reads; allocated by the first detecting call

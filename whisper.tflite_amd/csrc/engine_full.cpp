@@ -585,7 +585,7 @@ void Engine::decode_full(int batch, int64_t* ids, int ids_stride, int32_t* n_ids
     // (greedy's keys start with the slot, a beam key with -beam_size; a full-length key starts with kFullKey)
     // (the sampling kernels are one entry; temperature, seed and attempt are data, never part of the key)
     auto key_of = [&](int lo) {
-      std::vector<long long> key{kFullKey, slot_idx, batch, lo, P, n_prompt, chunks, long(stop_at_eot), fc2_ksplit, logits_int8,
+      std::vector<long long> key{kFullKey, slot_idx, batch, lo, P, n_prompt, chunks, long(stop_at_eot), fc2_ksplit, int8_key(),
                                  absorbed ? 1 : 0, n_abs, slot.dec, ts ? 1 : 0, ts ? max_initial_timestamp : 0, sc ? 1 : 0,
                                  smp ? 1 : 0};
       if (sup) key.push_back(n_sup), key.push_back(n_sup_first);  // launch constants; the ids themselves are device data
@@ -894,7 +894,7 @@ void Engine::beam_full_chains(int batch, bool first, int& steps) {
     launch_beam_full_begin(fa, st);
     // (greedy's keys start with the slot, a beam key with -beam_size, a full-length key with kFullKey)
     auto key_of = [&](int lo) {
-      std::vector<long long> key{kBeamFullKey, slot_idx, c0, nc, lo, P, n_prompt, K, fc2_ksplit, logits_int8, n_abs, slot.dec, ts ? 1 : 0,
+      std::vector<long long> key{kBeamFullKey, slot_idx, c0, nc, lo, P, n_prompt, K, fc2_ksplit, int8_key(), n_abs, slot.dec, ts ? 1 : 0,
                                  ts ? max_initial_timestamp : 0, sc ? 1 : 0};
       if (sup) key.push_back(n_sup), key.push_back(n_sup_first);  // launch constants; the ids themselves are device data
       if (p.bf) key.push_back(kBf16KeyMark);  // (last, in the bf16 storage mode only)
@@ -1045,7 +1045,7 @@ void Engine::decode_best_of(int batch, const std::vector<long long>& prompt, con
     launch_best_of_begin(ba, st);
     if (ts) launch_ts_state_init(bf_.ids[0], stride, nullptr, n_prompt, n_prompt, V, vocab_.token_beg, bf_.ts, rows, st);
     auto key_of = [&](int lo) {
-      std::vector<long long> key{kBestOfKey, slot_idx, N, c0, nc, lo, P, n_prompt, fc2_ksplit, logits_int8, n_abs, slot.dec, ts ? 1 : 0,
+      std::vector<long long> key{kBestOfKey, slot_idx, N, c0, nc, lo, P, n_prompt, fc2_ksplit, int8_key(), n_abs, slot.dec, ts ? 1 : 0,
                                  ts ? max_initial_timestamp : 0, sc ? 1 : 0};
       if (sup) key.push_back(n_sup), key.push_back(n_sup_first);  // launch constants; the ids themselves are device data
       if (truncating()) key.push_back(kCutKeyMark);  // top_k / top_p on: another launch sequence

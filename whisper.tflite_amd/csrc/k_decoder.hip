@@ -34,10 +34,6 @@ namespace {
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using half8 = __attribute__((ext_vector_type(8))) _Float16;
 
-__device__ __forceinline__ float gelu_erf(float x) {
-  return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
-}
-
 struct DecGemmDev {
   const unsigned short* Wt;
   float w_descale;

@@ -49,13 +49,6 @@ struct LogitsI8Dev {
   float* sx_out;
 };
 
-// TFLite's SymmetricQuantizeFloats for one element: the product is rounded once (never contracted into roundf's own
-// arithmetic), half away from zero, then clamped to [-127, 127]
-__device__ __forceinline__ unsigned quant_i8(float a, float inv) {
-  const float r = fminf(fmaxf(roundf(__fmul_rn(a, inv)), -127.0f), 127.0f);
-  return (unsigned)(int)r & 0xFFu;
-}
-
 template <int KS>
 __device__ __forceinline__ void load_tile(i32x4 (&w)[KS], float* sw, const LogitsI8Dev& g, int tile, int lane) {
   const i32x4* p = g.Wq + (long)tile * (KS * 64) + lane;
@@ -132,29 +125,13 @@ __global__ __launch_bounds__(256, 2) void dec_logits_i8(LogitsI8Dev g) {
     __syncthreads();
     float mean, rstd;
     row_stats<KS>(v, K, &mean, &rstd);
-    float mx = 0.0f;
-#pragma unroll
-    for (int j = 0; j < KS; ++j) {
-      const int c = (sub + 8 * j) * 4;
-      const f32x4 gg = *reinterpret_cast<const f32x4*>(&lnp[c]);
-      const f32x4 bb = *reinterpret_cast<const f32x4*>(&lnp[K + c]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[j][e] = (v[j][e] - mean) * rstd * gg[e] + bb[e];
-        mx = fmaxf(mx, fabsf(v[j][e]));
-      }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 4, 64));
-    const float sx = mx > 0.0f ? __fdiv_rn(mx, 127.0f) : 0.0f;
-    const float inv = mx > 0.0f ? __fdiv_rn(127.0f, mx) : 0.0f;
+    float sx, inv;  // TFLite's SymmetricQuantizeFloats of the row (dec_rows.h)
+    row_scale_i8(ln_apply_max<KS>(v, lnp, K, sub, mean, rstd), &sx, &inv);
     const bool tap = blockIdx.x == 0 && row < M;
 #pragma unroll
     for (int j = 0; j < KS; ++j) {
       const int c = (sub + 8 * j) * 4;
-      const unsigned q4 = quant_i8(v[j][0], inv) | (quant_i8(v[j][1], inv) << 8) | (quant_i8(v[j][2], inv) << 16) |
-                          (quant_i8(v[j][3], inv) << 24);
+      const unsigned q4 = quant4_i8(v[j], inv);
       *reinterpret_cast<unsigned*>(&qs[lrow * QLD + c]) = q4;
       if (tap && g.qx_out) *reinterpret_cast<unsigned*>(g.qx_out + (long)row * K + c) = q4;
     }

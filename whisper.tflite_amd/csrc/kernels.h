@@ -242,6 +242,44 @@ struct DecLogitsI8Args {
 };
 void launch_dec_logits_i8(const DecLogitsI8Args& a, hipStream_t s);
 
+// The int8 dynamic-range decoder-block GEMM (k_dec_gemm_i8.hip, option "decoder_int8"):
+// out[M][N] = epi(q(pro(x))[M][K] . Wq[N][K]^T) with Wq / sw = tile_rows_i8 of quantize_rows_i8 of W [N][K], every A row
+// quantised over the whole K at every launch (quantize_rows_i8's rule, on the device), int32 accumulation, and
+// t = ((float)acc * sx[m]) * sw[n]; kDecBias: t + bias, kDecBiasGelu: gelu(t + bias), kDecResid: R + (t + bias).
+// pro = kProNone (X) or kProLn (the row sources of DecGemmArgs: xin, xin + xpart, or the embedding of ids; K <= 512; the
+// bias epilogues only).  kErrInvalidArg for: K outside {128, 384, 512, 1536, 2048}, M outside 1 .. 128, N no positive
+// multiple of 32, ldy < N, ldx < K (or no multiple of 4) with kProNone, kProCombine, kDecLogits, ksplit != 1, a null
+// required pointer.
+struct DecGemmI8Args {
+  const int8_t* Wq = nullptr;  // [N / 32][K / 32][64 lanes][16]
+  const float* sw = nullptr;   // [N]
+  int N = 0, K = 0, M = 0;
+  int B = 0;  // clips of the embedding rows (row = p * B + b); 0 = M
+  const float* X = nullptr;  // kProNone
+  int ldx = 0;
+  const float* xin = nullptr;  // kProLn, as in DecGemmArgs
+  const float* xpart = nullptr;
+  float* xout = nullptr;
+  const float* ln_g = nullptr;
+  const float* ln_b = nullptr;
+  const long long* ids = nullptr;
+  int ids_stride = 0, pos = 0;
+  const float* tok_emb = nullptr;
+  const float* pos_emb = nullptr;
+  int n_vocab = 0;
+  const int* pos_start = nullptr;
+  int n_ctx = 0;
+  const float* bias = nullptr;
+  const float* R = nullptr;  // kDecResid; may alias Y
+  float* Y = nullptr;
+  int ldy = 0;
+  int ksplit = 1;  // refused unless 1: this form never splits K over blocks
+  // debug outputs (optional, written by the block of column tile 0): the quantised rows [M][K] and their scales [M]
+  int8_t* qx_out = nullptr;
+  float* sx_out = nullptr;
+};
+void launch_dec_gemm_i8(const DecGemmI8Args& a, int pro, int epi, hipStream_t s);
+
 // ------------------------------------------------------------- LayerNorm ---
 // y[m][:] = (x[m][:] - mean) * rstd * g + b, eps 1e-5, one wavefront per row.
 void launch_layernorm(const float* x, float* y, const float* g, const float* b, int M, int d,
