@@ -164,6 +164,12 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * cross-attention's derived query matrix, the cached cross-attention form's two projections and language detection keep
  * their format, and "fc2_ksplit" has no effect while it is on; independent of "logits_int8" (both = the all-int8 decoder);
  * anything but 0 or 1 is WT_ERR_INVALID_ARG),
+ * "encoder_int8" (0 = default; 1 = the int8 dynamic-range encoder blocks, DESIGN.md section 39: the four Linear matrices of
+ * every encoder layer of the model file (q|k|v, attention out, fc1, fc2) are int8 rows + one fp32 scale per output, made at
+ * the first switch together with the scratch of the quantised rows; their input rows are quantised per row over the whole K
+ * by a launch of their own, the sums are int32 and y = ((float)acc * s_row) * s_column + bias; fp32 storage mode only: with
+ * "bf16" an encode is WT_ERR_UNSUPPORTED; both convolutions, attention, the cross-K/V projection and the front end keep their
+ * format; anything but 0 or 1 is WT_ERR_INVALID_ARG),
  * "last_batches" (N = the next N pipelined submits are the last of a job: they are decoded one chain per batch, the very
  * last on the encoder's stream, so the pipeline drains sooner; counts down to 0 by itself, may be set with batches in
  * flight), "force_fallback" (test hook: bit mask of contractions sent to the full-range kernels, nothing in flight).

@@ -373,6 +373,19 @@ int wt_dbg_dec_gemm_i8(wt_engine* h, int pro, int epi, int M, int B, int N, int 
                        const float* xpart, const int64_t* ids, int ids_stride, int pos, const float* tok_emb, const float* pos_emb,
                        int n_vocab, int n_pos, const int32_t* pos_start, const float* ln_g, const float* ln_b, const float* W,
                        const float* bias, const float* R, int ldy, int ksplit, float* Y, float* xout, int8_t* qx, float* sx);
+/* The int8 encoder-block kernels (k_enc_gemm_i8.hip, option "encoder_int8").
+ * wt_dbg_enc_quant_rows_i8: the row quantiser.  src 0: rows X [M][ld]; 1: X [M][K] as two fp16 planes made by the tap, hi =
+ * fp16(x * scale), lo = fp16(x * scale - hi), scale a power of two (the kernel quantises ((float)hi + (float)lo) / scale);
+ * 2: the LayerNorm (ln_g, ln_b) of X [M][K].  Out: qx [M][K], sx [M], the kernel's quantised rows and their scales; the tap
+ * fails with WT_ERR_DEVICE if the kernel wrote behind either.
+ * wt_dbg_enc_gemm_i8: the GEMM over qx [M][K], sx [M] and W [N][K] fp32, which the tap quantises and tiles on the host
+ * (wt_quantize_rows_i8, wt_tile_rows_i8) as the engine does it.  epi 0: Y = R + (t + bias), R [M][ldc] or R == Y (in
+ * place); 1: t + bias; 2: gelu(t + bias).  Y [M + 4][ldc] is in / out, the rows behind M guards.  The launcher's
+ * refusals come first and touch no memory; the tap itself takes M <= 65536, N and ldc <= 8192. */
+int wt_dbg_enc_quant_rows_i8(wt_engine* h, int src, int M, int K, const float* X, int ld, float scale, const float* ln_g,
+                             const float* ln_b, int8_t* qx, float* sx);
+int wt_dbg_enc_gemm_i8(wt_engine* h, int epi, int M, int N, int K, const int8_t* qx, const float* sx, const float* W,
+                       const float* bias, const float* R, int ldc, float* Y);
 /* select_token over records [B][n_tiles]; ids [B][stride], n_ids [B], finished [B] in / out */
 int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* records, int64_t* ids, int stride, int pos,
                         int32_t* n_ids, int32_t* finished, int64_t eot, int stop_at_eot, int keep_ids);

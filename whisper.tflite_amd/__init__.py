@@ -66,7 +66,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_self_attention_bf16", "wt_dbg_cross_attention_bf16", "wt_dbg_encoder_attention_planes", "wt_dbg_gemm_bf16", "wt_dbg_gemm_bf16_ln", "wt_dbg_encoder_attention_bf16",
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_beam_full_step", "wt_dbg_beam_full_finalize",
-    "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_dec_logits_i8", "wt_dbg_dec_gemm_i8", "wt_dbg_select_token",
+    "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_dec_logits_i8", "wt_dbg_dec_gemm_i8", "wt_dbg_enc_quant_rows_i8", "wt_dbg_enc_gemm_i8", "wt_dbg_select_token",
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_language_head_rows", "wt_dbg_self_attention_long",
     "wt_dbg_self_attention_prefill", "wt_dbg_self_attention_long_gather",
     "wt_dbg_self_attention_long_bf16", "wt_dbg_self_attention_long_gather_bf16", "wt_dbg_self_attention_prefill_bf16",
@@ -265,6 +265,8 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_dec_logits_i8.argtypes = [c_void_p, c_int, c_int, c_int, fp, fp, fp, fp, fp, c_int, fp, u64p, c_void_p, fp]
         L.wt_dbg_dec_gemm_i8.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, c_int, fp, fp, ip64, c_int, c_int,
                                          fp, fp, c_int, c_int, ip32, fp, fp, fp, fp, fp, c_int, c_int, fp, fp, c_void_p, fp]
+        L.wt_dbg_enc_quant_rows_i8.argtypes = [c_void_p, c_int, c_int, c_int, fp, c_int, c_float, fp, fp, c_void_p, fp]
+        L.wt_dbg_enc_gemm_i8.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, fp, fp, fp, fp, c_int, fp]
         L.wt_dbg_select_token.argtypes = [c_void_p, c_int, c_int, u64p, ip64, c_int, c_int, ip32, ip32, c_int64, c_int,
                                           c_int]
         L.wt_language_count.argtypes = [c_void_p]
@@ -1935,6 +1937,37 @@ class Engine:
             _ip32(ps) if ps is not None else None, _fp(ln_g), _fp(ln_b), _fp(W), _fp(bias),
             _fp(Y) if (in_place and R is not None) else _fp(R), ldy, ksplit, _fp(Y), _fp(xout), qx.ctypes.data_as(c_void_p), _fp(sx)))
         return Y, xout, qx, sx
+
+    def dbg_enc_quant_rows_i8(self, X, source="f32", scale=1.0, ln_g=None, ln_b=None, K=None):
+        """The row quantiser of the int8 encoder blocks (option encoder_int8) over X [M][ld] fp32.
+        source "f32": the rows themselves (K <= ld columns of each); "planes": the two fp16 planes of X * scale (made by
+        the tap, scale a power of two); "ln": LayerNorm(X) * ln_g + ln_b.  Returns (qx int8 [M][K], sx float32 [M])."""
+        X = _f32(X) if X is not None else None
+        M, ld = X.shape if X is not None else (1, K)
+        K = K or ld
+        g_, b_ = (_f32(a) if a is not None else None for a in (ln_g, ln_b))
+        qx, sx = np.zeros((M, K), np.int8), np.full(M, np.nan, np.float32)
+        self._check(lib().wt_dbg_enc_quant_rows_i8(self._h, {"f32": 0, "planes": 1, "ln": 2}[source], M, K, _fp(X), ld, scale,
+                                                   _fp(g_), _fp(b_), qx.ctypes.data_as(c_void_p), _fp(sx)))
+        return qx, sx
+
+    def dbg_enc_gemm_i8(self, qx, sx, W, bias, R=None, epi=1, in_place=False, ldc=None, guard=1.0e30):
+        """The int8 encoder-block GEMM (option encoder_int8) over quantised rows qx int8 [M][K] with
+        scales sx [M] and W [N][K] fp32, quantised and tiled by the tap.  epi 0 residual (R [M][N]; in_place: R is the Y
+        buffer itself), 1 bias, 2 bias + GELU.  Returns Y [M + 4][ldc], the last four rows `guard`."""
+        W = _f32(W)
+        N, K = W.shape
+        qx = np.ascontiguousarray(qx, dtype=np.int8)
+        M = qx.shape[0]
+        sx, bias, R = (_f32(a) if a is not None else None for a in (sx, bias, R))
+        ldc = ldc or N
+        Y = np.full((M + 4, max(ldc, 1)), guard, np.float32)
+        if R is not None and in_place:
+            Y[:M, :N] = R
+        Rp = _fp(Y) if (in_place and R is not None) else _fp(R)
+        self._check(lib().wt_dbg_enc_gemm_i8(self._h, epi, M, N, K, qx.ctypes.data_as(c_void_p), _fp(sx), _fp(W), _fp(bias), Rp,
+                                             ldc, _fp(Y)))
+        return Y
 
     def dbg_language_head(self, x, ln_g, ln_b, tok_emb, lang_lo, n_lang, xpart=None, ids=None, forced_lang=-1):
         """language_head over rows x [rows][d] (+ xpart) against tok_emb [n_vocab][d], language rows lang_lo .. lang_lo +

@@ -42,6 +42,8 @@ void usage(const char* argv0) {
             << "                  each, activations quantised per row at run time, int32 accumulation\n"
             << "  --int8-decoder  the int8 dynamic-range decoder blocks (option decoder_int8): the decoder layers' Linear\n"
             << "                  matrices as int8 rows with one scale each, their inputs quantised per row at run time\n"
+            << "  --int8-encoder  the int8 dynamic-range encoder blocks (option encoder_int8): the encoder layers' Linear\n"
+            << "                  matrices as int8 rows with one scale each, their inputs quantised per row at run time\n"
             << "  --max-positions N  full-length greedy decoding over N positions, 32 .. n_text_ctx (default: the\n"
             << "                  reference's 31 positions)\n"
             << "  --timestamps    with --max-positions: decode with timestamps and print one line per segment,\n"
@@ -98,7 +100,7 @@ int main(int argc, char* argv[]) {
       suppress_tokens;
   bool word_timestamps = false, suppress_default = false, suppress_blank = false, resample = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
-       no_condition = false, bf16 = false, int8_logits = false, int8_decoder = false;
+       no_condition = false, bf16 = false, int8_logits = false, int8_decoder = false, int8_encoder = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], v;
     if (a == "-h" || a == "--help") {
@@ -127,6 +129,10 @@ int main(int argc, char* argv[]) {
     }
     if (a == "--int8-decoder") {
       int8_decoder = true;
+      continue;
+    }
+    if (a == "--int8-encoder") {
+      int8_encoder = true;
       continue;
     }
     if (a == "--timestamps") {
@@ -260,6 +266,10 @@ int main(int argc, char* argv[]) {
   }
   if (int8_decoder && wt_engine_set_option(encdec.handle(), "decoder_int8", 1) != WT_OK) {
     std::cerr << "--int8-decoder: " << wt_last_error(encdec.handle()) << "\n";
+    return 105;
+  }
+  if (int8_encoder && wt_engine_set_option(encdec.handle(), "encoder_int8", 1) != WT_OK) {
+    std::cerr << "--int8-encoder: " << wt_last_error(encdec.handle()) << "\n";
     return 105;
   }
   if (!beam.empty()) {

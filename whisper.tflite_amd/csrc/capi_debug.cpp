@@ -1378,6 +1378,67 @@ int wt_dbg_dec_gemm_i8(wt_engine* h, int pro, int epi, int M, int B, int N, int 
   });
 }
 
+int wt_dbg_enc_quant_rows_i8(wt_engine* h, int src, int M, int K, const float* X, int ld, float scale, const float* ln_g,
+                             const float* ln_b, int8_t* qx, float* sx) {
+  // only what the tap's own copies need; every rule of the kernel contract is the launcher's to refuse
+  if (!h || !qx || !sx || M < 0 || M > (1 << 16) || K < 1 || K > 8192 || ld < 0 || ld > 8192) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    const int lda = src == wt::kEncSrcF32 ? ld : K;
+    const size_t mk = size_t(M) * K;
+    DevArr<float> dX(X && src != wt::kEncSrcPlanes ? size_t(M) * lda : 0, X), dg(ln_g ? K : 0, ln_g), db(ln_b ? K : 0, ln_b);
+    // the planes as the attention kernel leaves them: hi = fp16(x * scale), lo = fp16(x * scale - hi)
+    const bool planes = src == wt::kEncSrcPlanes && X;
+    DevPlanes dP(planes ? X : nullptr, planes ? mk : 0, scale);
+    DevArr<int8_t> dqx(mk + 64);  // 64 guard bytes behind the last row
+    DevArr<float> dsx(size_t(M) + 4);
+    std::vector<int8_t> gq(mk + 64, int8_t(0x55));
+    std::vector<float> gs(size_t(M) + 4, -1.0f);
+    hipchk(hipMemcpy(dqx.p, gq.data(), gq.size(), hipMemcpyHostToDevice), "H2D");
+    hipchk(hipMemcpy(dsx.p, gs.data(), gs.size() * sizeof(float), hipMemcpyHostToDevice), "H2D");
+    wt::EncQuantI8Args a;
+    a.X = X && !planes ? dX.p : nullptr; a.ld = lda; a.M = M; a.K = K; a.scale = scale;
+    if (planes) a.hi = dP.ptr(), a.lo = dP.ptr() + dP.plane;
+    a.ln_g = ln_g ? dg.p : nullptr; a.ln_b = ln_b ? db.p : nullptr; a.qx = dqx.p; a.sx = dsx.p;
+    wt::launch_enc_quant_rows_i8(a, src, h->impl->stream());
+    h->impl->sync();
+    dqx.to_host(gq.data());
+    dsx.to_host(gs.data());
+    for (size_t i = mk; i < gq.size(); ++i)
+      if (gq[i] != int8_t(0x55)) throw wt::Error(wt::kErrDevice, "enc_quant_rows_i8 wrote behind qx");
+    for (size_t i = size_t(M); i < gs.size(); ++i)
+      if (gs[i] != -1.0f) throw wt::Error(wt::kErrDevice, "enc_quant_rows_i8 wrote behind sx");
+    std::memcpy(qx, gq.data(), mk);
+    std::memcpy(sx, gs.data(), size_t(M) * sizeof(float));
+  });
+}
+
+int wt_dbg_enc_gemm_i8(wt_engine* h, int epi, int M, int N, int K, const int8_t* qx, const float* sx, const float* W,
+                       const float* bias, const float* R, int ldc, float* Y) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    // the launcher's own refusals first, on the caller's pointers (the check touches no memory), then what the tap's
+    // copies need
+    wt::EncGemmI8Args g;
+    g.qx = qx; g.sx = sx; g.Wq = reinterpret_cast<const int8_t*>(W); g.sw = W; g.bias = bias; g.R = R; g.Y = Y;
+    g.M = M; g.N = N; g.K = K; g.ldc = ldc;
+    wt::check_enc_gemm_i8(g, epi);
+    if (M > (1 << 16) || N > 8192 || ldc > 8192) throw wt::Error(wt::kErrInvalidArg, "wt_dbg_enc_gemm_i8: M <= 65536, N and ldc <= 8192");
+    std::vector<int8_t> q(size_t(N) * K), tiled(q.size());
+    std::vector<float> sw(N), sw_tiled(N);
+    wt::quantize_rows_i8(W, N, K, q.data(), sw.data());
+    wt::tile_rows_i8(q.data(), sw.data(), N, K, tiled.data(), sw_tiled.data());
+    DevArr<int8_t> dW(tiled), dqx(size_t(M) * K, qx);
+    DevArr<float> dsw(sw_tiled), dsx(size_t(M), sx), dB(size_t(N), bias);
+    const bool in_place = R == Y;  // the residual stream updated in place, as the engine does it
+    DevArr<float> dR(R && !in_place ? size_t(M) * ldc : 0, R);
+    DevArr<float> dY((size_t(M) + 4) * ldc, Y);  // [M + 4][ldc]: the rows behind M are guards the kernel must not write
+    g.qx = dqx.p; g.sx = dsx.p; g.Wq = dW.p; g.sw = dsw.p; g.bias = dB.p; g.R = in_place ? dY.p : (R ? dR.p : nullptr); g.Y = dY.p;
+    wt::launch_enc_gemm_i8(g, epi, h->impl->stream());
+    h->impl->sync();
+    dY.to_host(Y);
+  });
+}
+
 int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* records, int64_t* ids, int stride, int pos,
                         int32_t* n_ids, int32_t* finished, int64_t eot, int stop_at_eot, int keep_ids) {
   if (!h || !records || !ids || !n_ids || !finished || B < 1 || n_tiles < 1 || pos < 0 || pos + 1 >= stride) {

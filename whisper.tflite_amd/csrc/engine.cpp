@@ -1075,6 +1075,7 @@ void Engine::ensure_batch(int batch) {
   }
   ws_.mel_stage = alloc(B * mel_elems(), false);
   ws_.batch = batch;
+  if (!enc_blocks_q8_.empty()) alloc_enc_q8_scratch();  // option encoder_int8 has been set: its scratch follows the workspace
   HIPCHK(hipStreamSynchronize(stream_));
 }
 
@@ -1294,6 +1295,7 @@ struct PlaneOperand {  // where a plane consumer finds its A operand
 
 void Engine::encode_enqueue(const float* d_mel, int batch) {
   if (dims_.n_audio_state == 0) throw Error(kErrUnsupported, "front-end-only engine: no model weights loaded");
+  if (encoder_int8 && bf16) throw Error(kErrUnsupported, "encoder_int8 covers the fp32 storage mode: set bf16 or encoder_int8 to 0");
   ensure_batch(batch);
   TimerDisarm disarm_on_exit;
   // per-launch event pairs (bench.py's live roofline figures) on every kernel_timers-th encoder pass: an event pair
@@ -1337,6 +1339,7 @@ void Engine::encode_enqueue(const float* d_mel, int batch) {
   const long ln_plane = plane(Bw * T * d), qkv_plane = plane(Bw * T * 3 * d), hid_plane = plane(Bw * T * 4 * d);
   const long cvt_plane = plane(Bw * T * 4 * d), e_plane = plane(Bw * T * d);
   const bool absorb = absorb_for(batch);
+  const bool enc8 = encoder_int8 != 0;  // the layers' four Linear matrices on the int8 kernels
   const int alt = alt_gemm_variant();
   auto on_planes = [&](const EncLinear& w) { return bf || gemm_on_planes(w.sc); };
   auto a_scale = [&](const EncLinear& w) { return bf ? 1.0f : w.sc.a; };  // the scale of the A planes made for `w`
@@ -1355,7 +1358,7 @@ void Engine::encode_enqueue(const float* d_mel, int batch) {
   bool ln_done = false;
   static const bool no_ln_fuse = getenv("WT_NO_LN_FUSE") != nullptr;  // measurement knob: separate LayerNorm launches
   auto fuse_ln = [&](EncGemm& e, const float* gain, const float* shift, const EncLinear& consumer) {
-    if (no_ln_fuse || !on_planes(consumer)) return;
+    if (no_ln_fuse || enc8 || !on_planes(consumer)) return;  // (no LayerNorm is fused in front of an int8 GEMM)
     e.g.ln_g = gain; e.g.ln_b = shift; e.g.ln_P = lnp; e.g.ln_plane = ln_plane; e.g.ln_scale = a_scale(consumer);
   };
   // Runs a contraction on the kernel its record and the mode select and leaves the result in the consumer's format;
@@ -1443,6 +1446,54 @@ void Engine::encode_enqueue(const float* d_mel, int batch) {
     const int attn_alt = attn_variant == 4 ? 1 : int(attn_variant);  // fall-back form: three bf16 planes
     const float qkv_scales[3] = {kQScale * L.q, L.k, L.v}, s_out = a_scale(L.out), s_fc2 = a_scale(L.fc2);
 
+    if (enc8) {
+      // Option encoder_int8: every contraction is quantise its rows (whole K) -> int8 GEMM, fp32 out.  Attention keeps
+      // its kernel and its operand format: the fp32 q | k | v go through the hand-over, as behind a fall-back GEMM.
+      const EncBlockInt8& w8 = enc_blocks_q8_[size_t(l)];
+      auto quant = [&](int src, const EncQuantI8Args& from, int K) {
+        EncQuantI8Args a = from;
+        a.M = M; a.K = K; a.qx = ws_.qx; a.sx = ws_.sx;
+        kt_begin(kKcGemmI8, 0, 5.0 * M * K + 4.0 * M);
+        launch_enc_quant_rows_i8(a, src, stream_);
+        kt_end();
+      };
+      auto gemm8 = [&](const Int8W& w, const EncLinear& lin, int epi, float* Y) {
+        EncGemmI8Args a;
+        a.qx = ws_.qx; a.sx = ws_.sx; a.Wq = w.w; a.sw = w.scale; a.bias = lin.bias; a.R = epi == kDecResid ? Y : nullptr; a.Y = Y;
+        a.M = M; a.N = lin.N; a.K = lin.k; a.ldc = lin.N;
+        kt_begin(kKcGemmI8, 2.0 * M * lin.N * double(lin.k), 0);
+        launch_enc_gemm_i8(a, epi, stream_);
+        kt_end();
+      };
+      EncQuantI8Args ln1, att, ln2, hid;
+      ln1.X = ws_.x; ln1.ld = d; ln1.ln_g = L.attn_ln_g; ln1.ln_b = L.attn_ln_b;
+      quant(kEncSrcLn, ln1, d);
+      gemm8(w8.qkv, L.qkv, kDecBias, ws_.qkv);
+      const double attn_flops8 = 4.0 * batch * c.n_audio_head * double(T) * T * 64;
+      if (ap) {
+        const PlaneOperand qkv_src = hand_over(ws_.qkv, ws_.cvt, cvt_plane, M, 3 * d, qkv_scales, d);
+        kt_begin(kKcEncAttn, attn_flops8, 0);
+        launch_encoder_attention_planes(qkv_src.p, qkv_src.plane, attp, ln_plane, batch, T, c.n_audio_head, L.q, L.k, L.v,
+                                        L.out.sc.a, stream_);
+        kt_end();
+        att.hi = attp; att.lo = attp + ln_plane; att.scale = L.out.sc.a;
+        quant(kEncSrcPlanes, att, d);
+      } else {
+        kt_begin(kKcEncAttnAlt, attn_flops8, 0);
+        launch_encoder_attention(ws_.qkv, ws_.att, batch, T, c.n_audio_head, attn_alt, stream_);
+        kt_end();
+        att.X = ws_.att; att.ld = d;
+        quant(kEncSrcF32, att, d);
+      }
+      gemm8(w8.out, L.out, kDecResid, ws_.x);
+      ln2.X = ws_.x; ln2.ld = d; ln2.ln_g = L.mlp_ln_g; ln2.ln_b = L.mlp_ln_b;
+      quant(kEncSrcLn, ln2, d);
+      gemm8(w8.fc1, L.fc1, kDecBiasGelu, ws_.hid);
+      hid.X = ws_.hid; hid.ld = 4 * d;
+      quant(kEncSrcF32, hid, 4 * d);
+      gemm8(w8.fc2, L.fc2, kDecResid, ws_.x);
+      continue;
+    }
     layernorm_for(L.qkv, L.attn_ln_g, L.attn_ln_b);
     EncGemm q;  // q | k | v: the attention kernel's operand planes, or fp32 for the fall-back attention
     q.w = &L.qkv; q.epi = kEpiBias;
@@ -1590,6 +1641,54 @@ void Engine::set_decoder_int8(bool on) {
     dec_blocks_q8_ = std::move(blocks);
   }
   decoder_int8 = on ? 1 : 0;
+}
+
+// Option "encoder_int8": the int8 tables of the encoder layers' four Linear matrices, made the first time the option is
+// set from the model file's fp32 rows exactly as set_decoder_int8 makes the decoder's (12 d^2 bytes per layer + scales),
+// and the scratch the row quantiser writes.  Nothing is allocated during an encode.
+void Engine::alloc_enc_q8_scratch() {
+  if (ws_.batch == 0 || dims_.n_audio_state == 0) return;  // no workspace yet: ensure_batch calls again
+  const size_t rows = size_t(ws_.batch) * dims_.n_audio_ctx;
+  void* p = nullptr;
+  HIPCHK(hipMalloc(&p, rows * 4 * dims_.n_audio_state + rows * sizeof(float)));
+  ws_.owned.push_back(p);
+  ws_.qx = static_cast<int8_t*>(p);
+  ws_.sx = reinterpret_cast<float*>(ws_.qx + rows * 4 * dims_.n_audio_state);
+}
+
+void Engine::set_encoder_int8(bool on) {
+  require_idle();
+  if (on && enc_blocks_q8_.empty()) {
+    if (dims_.n_audio_state == 0) throw Error(kErrUnsupported, "front-end-only engine: no model weights loaded");
+    const int d = dims_.n_audio_state;
+    if (d != 128 && d != 384 && d != 512) throw Error(kErrUnsupported, "encoder_int8: d_model 128, 384 or 512");
+    const WtwFile file(weights_path_);
+    const size_t dd = size_t(d) * d;
+    auto table = [&](const float* W, int N, int K) {
+      std::vector<int8_t> q(size_t(N) * K), tiled(q.size());
+      std::vector<float> sw(N), sw_tiled(N);
+      quantize_rows_i8(W, N, K, q.data(), sw.data());
+      tile_rows_i8(q.data(), sw.data(), N, K, tiled.data(), sw_tiled.data());  // (N is a multiple of 32: no padding rows)
+      void* p = nullptr;
+      HIPCHK(hipMalloc(&p, tiled.size()));
+      allocations_.push_back(p);
+      HIPCHK(hipMemcpy(p, tiled.data(), tiled.size(), hipMemcpyHostToDevice));
+      return Int8W{static_cast<const int8_t*>(p), upload(sw_tiled)};
+    };
+    std::vector<EncBlockInt8> blocks(size_t(dims_.n_audio_layer));
+    for (int l = 0; l < dims_.n_audio_layer; ++l) {
+      const std::string blk = "encoder.blocks." + std::to_string(l);
+      EncBlockInt8& b = blocks[size_t(l)];
+      b.qkv = table(fused_qkv_weight(file, blk + ".attn", d).data(), 3 * d, d);
+      b.out = table(file.get(blk + ".attn.out.weight", dd), d, d);
+      b.fc1 = table(file.get(blk + ".mlp.0.weight", 4 * dd), 4 * d, d);
+      b.fc2 = table(file.get(blk + ".mlp.2.weight", 4 * dd), d, 4 * d);
+    }
+    HIPCHK(hipStreamSynchronize(stream_));
+    alloc_enc_q8_scratch();
+    enc_blocks_q8_ = std::move(blocks);
+  }
+  encoder_int8 = on ? 1 : 0;
 }
 
 void Engine::set_bf16(bool on) {

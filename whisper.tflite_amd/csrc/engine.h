@@ -55,8 +55,9 @@ struct KernelStat {
 };
 // kKcGemm / kKcEncAttn: the default plane kernels (or the bf16-storage ones); *Alt: contractions that ran on the
 // fp32-storage kernels instead (a load-time fall-back of that contraction, or a forced gemm_variant / attn_variant);
-// kKcConvert: the fp32 -> planes hand-over between the two kinds
-enum KernelClass { kKcGemm = 0, kKcEncAttn, kKcLayerNorm, kKcTranspose, kKcGemmAlt, kKcEncAttnAlt, kKcConvert, kKcCount };
+// kKcConvert: the fp32 -> planes hand-over between the two kinds; kKcGemmI8: option encoder_int8's two kernels, the row
+// quantiser (bytes) and the int8 GEMM (FLOPs)
+enum KernelClass { kKcGemm = 0, kKcEncAttn, kKcLayerNorm, kKcTranspose, kKcGemmAlt, kKcEncAttnAlt, kKcConvert, kKcGemmI8, kKcCount };
 
 // Operand scales of the two-plane fp16 encoder kernels (powers of two, f16_scale_for): derived at load
 // time from weight-only upper bounds of every contraction operand (LayerNorm output <= |g| sqrt(d-1) + |b|,
@@ -328,6 +329,15 @@ class Engine {
   long decoder_int8 = 0;
   void set_decoder_int8(bool on);
   long long int8_key() const { return logits_int8 + 2 * decoder_int8; }
+  // 1 = the int8 dynamic-range encoder blocks (k_enc_gemm_i8.hip): encode_enqueue runs the four Linear
+  // matrices of every encoder layer — q|k|v, attention out, fc1, fc2 — as int8 rows + one fp32 scale per output against
+  // activation rows quantised per row by a launch of their own (enc_quant_rows_i8), in int32, fp32 out; fp32 storage
+  // mode only (with bf16 an encode refuses, kErrUnsupported).  Staying as they are: both convolutions, attention, the
+  // cross-K/V projection, the final LayerNorm (unfused) and the front end.  Set through set_encoder_int8(): the first
+  // switch makes the tables and the qx / sx scratch of the workspace batch; an engine that never sets it allocates
+  // nothing.  No decoder graph key holds it: the decoder reads the encoder's output, never its launches.
+  long encoder_int8 = 0;
+  void set_encoder_int8(bool on);
   // encoder kernel-class timers (wt_last_kernel_stats): 0 = off, N = event pairs around every launch of every N-th
   // encoder pass; passes without them report zero launches
   long kernel_timers = 1;
@@ -789,6 +799,11 @@ class Engine {
     Int8W wqkv, wo, cross_wo, w1, w2;
   };
   std::vector<DecBlockInt8> dec_blocks_q8_;  // empty until the option is first set
+  struct EncBlockInt8 {  // option encoder_int8
+    Int8W qkv, out, fc1, fc2;
+  };
+  std::vector<EncBlockInt8> enc_blocks_q8_;  // empty until the option is first set
+  void alloc_enc_q8_scratch();  // qx [batch T][4 d] int8 + sx [batch T] for the workspace batch, into ws_
   // front end
   const unsigned short* dft_basis_p_ = nullptr;  // [dft_n][dft_k] windowed basis, rows (2 k, 2 k + 1) = (re, im) of bin k, as fp16 planes
   const float* dft_zero_bias_ = nullptr;
@@ -884,6 +899,9 @@ class Engine {
     unsigned short *melTp = nullptr, *h1pp = nullptr;
     // planes made by launch_f32_to_planes from the fp32 output of a fall-back contraction ([B T][4 d] elements)
     unsigned short* cvt = nullptr;
+    // option encoder_int8: the quantised rows of the contraction in flight and their scales (null until the option is set)
+    int8_t* qx = nullptr;
+    float* sx = nullptr;
     // front end
     unsigned short* pcm_planes = nullptr;
     float *pw = nullptr, *melacc = nullptr;
@@ -905,7 +923,7 @@ class Engine {
   KernelStat kstats_[kKcCount] = {{"gemm_planes_tile", 0, 0, 0, 0},     {"encoder_attention_planes", 0, 0, 0, 0},
                                   {"layernorm_rows", 0, 0, 0, 0},       {"mel_transpose", 0, 0, 0, 0},
                                   {"gemm_split16_tile", 0, 0, 0, 0},    {"encoder_attention_split", 0, 0, 0, 0},
-                                  {"f32_to_planes", 0, 0, 0, 0}};
+                                  {"f32_to_planes", 0, 0, 0, 0},        {"enc_gemm_i8", 0, 0, 0, 0}};
   int self_cap_ = 32;
   static constexpr int kDecRowsMax = 128;  // rows of one decoder pass (k_decoder.hip: up to four 32-row tiles)
 };

@@ -280,6 +280,43 @@ struct DecGemmI8Args {
 };
 void launch_dec_gemm_i8(const DecGemmI8Args& a, int pro, int epi, hipStream_t s);
 
+// The int8 dynamic-range encoder-block GEMM (k_enc_gemm_i8.hip, option "encoder_int8"), two launches
+// per contraction.  launch_enc_quant_rows_i8: rows -> qx int8 [M][K] + sx [M] by quantize_rows_i8's rule on the device.
+// src kEncSrcF32: X [M][ld]; kEncSrcPlanes: ((float)hi + (float)lo) * (1 / scale) of two fp16 planes [M][K], scale a
+// power of two; kEncSrcLn: LayerNorm(X [M][K]) * ln_g + ln_b (eps 1e-5), K in {128, 384, 512}.  kErrInvalidArg for: K no
+// multiple of 16 or above 2048, the LayerNorm source with K > 512, M < 1, ld < K, a null pointer the source needs.
+enum EncQuantSrc { kEncSrcF32 = 0, kEncSrcPlanes = 1, kEncSrcLn = 2 };
+struct EncQuantI8Args {
+  const float* X = nullptr;  // kEncSrcF32, kEncSrcLn
+  int ld = 0;                // kEncSrcF32
+  const unsigned short* hi = nullptr;  // kEncSrcPlanes
+  const unsigned short* lo = nullptr;
+  float scale = 1.0f;
+  const float* ln_g = nullptr;  // kEncSrcLn
+  const float* ln_b = nullptr;
+  int M = 0, K = 0;
+  int8_t* qx = nullptr;
+  float* sx = nullptr;
+};
+void launch_enc_quant_rows_i8(const EncQuantI8Args& a, int src, hipStream_t s);
+// launch_enc_gemm_i8: Y[M][N] = epi(qx . Wq^T) with Wq / sw = tile_rows_i8 of quantize_rows_i8 of W [N][K], int32 sums and
+// t = ((float)acc * sx[m]) * sw[n]; epi kDecBias: t + bias, kDecBiasGelu: gelu(t + bias), kDecResid: R + (t + bias), R
+// [M][ldc] may be Y.  kErrInvalidArg (check_enc_gemm_i8, which touches no memory) for: K outside {128, 384, 512, 1536,
+// 2048}, M < 1, N no positive multiple of 128, ldc < N, a null required pointer, kDecResid without R, another epilogue,
+// and an extent (M rounded up to 128 rows x ldc x 4, x K; N x K) whose byte offsets leave 32 bits.
+struct EncGemmI8Args {
+  const int8_t* qx = nullptr;  // [M][K]
+  const float* sx = nullptr;   // [M]
+  const int8_t* Wq = nullptr;  // [N / 32][K / 32][64 lanes][16]
+  const float* sw = nullptr;   // [N]
+  const float* bias = nullptr;
+  const float* R = nullptr;
+  float* Y = nullptr;
+  int M = 0, N = 0, K = 0, ldc = 0;
+};
+void check_enc_gemm_i8(const EncGemmI8Args& a, int epi);
+void launch_enc_gemm_i8(const EncGemmI8Args& a, int epi, hipStream_t s);
+
 // ------------------------------------------------------------- LayerNorm ---
 // y[m][:] = (x[m][:] - mean) * rstd * g + b, eps 1e-5, one wavefront per row.
 void launch_layernorm(const float* x, float* y, const float* g, const float* b, int M, int d,
