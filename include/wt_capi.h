@@ -169,7 +169,10 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * the first switch together with the scratch of the quantised rows; their input rows are quantised per row over the whole K
  * by a launch of their own, the sums are int32 and y = ((float)acc * s_row) * s_column + bias; fp32 storage mode only: with
  * "bf16" an encode is WT_ERR_UNSUPPORTED; both convolutions, attention, the cross-K/V projection and the front end keep their
- * format; anything but 0 or 1 is WT_ERR_INVALID_ARG),
+ * format; 2 = the same plus the conv stem, DESIGN.md section 40: conv1 and conv2 as int8 rows + one fp32 scale per output
+ * channel, their fp32 input quantised with one scale per clip (its largest |x| / 127) while the kernel stages it, so the
+ * encoder is int8 from the mel to ln_post; the two conv tables are made at the first switch to 2, n_mels other than 80 or
+ * 128 is WT_ERR_UNSUPPORTED; anything but 0, 1 or 2 is WT_ERR_INVALID_ARG),
  * "last_batches" (N = the next N pipelined submits are the last of a job: they are decoded one chain per batch, the very
  * last on the encoder's stream, so the pipeline drains sooner; counts down to 0 by itself, may be set with batches in
  * flight), "force_fallback" (test hook: bit mask of contractions sent to the full-range kernels, nothing in flight).

@@ -386,6 +386,15 @@ int wt_dbg_enc_quant_rows_i8(wt_engine* h, int src, int M, int K, const float* X
                              const float* ln_b, int8_t* qx, float* sx);
 int wt_dbg_enc_gemm_i8(wt_engine* h, int epi, int M, int N, int K, const int8_t* qx, const float* sx, const float* W,
                        const float* bias, const float* R, int ldc, float* Y);
+/* The int8 encoder conv stem (k_enc_conv_i8.hip, option "encoder_int8" = 2): the width-3, padding-1
+ * convolution at stride 1 or 2 over X [B][stride * T_out][C_in] fp32 (unpadded: the tap adds the zero rows) with W
+ * [N][C_in][3] fp32, which the tap reorders, quantises and tiles on the host as the engine does.  The tap runs
+ * clip_absmax_f32 over X, then the convolution with that scale per clip.  epi 0: t + bias; 1: gelu(t + bias); 2: gelu(t +
+ * bias) + pos [T_out][N].  Y [B][T_out + 4][N] is in / out, the four rows behind every clip guards; amax_in [B]: the
+ * clips' largest |x|; amax_out [B]: the kernel's own reduction of |Y|.  The launcher's refusals come first and touch no
+ * memory; the tap itself takes B <= 64, T_out and N <= 8192. */
+int wt_dbg_enc_conv_i8(wt_engine* h, int stride, int epi, int B, int T_out, int C_in, int N, const float* X, const float* W,
+                       const float* bias, const float* pos, float* Y, float* amax_in, float* amax_out);
 /* select_token over records [B][n_tiles]; ids [B][stride], n_ids [B], finished [B] in / out */
 int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* records, int64_t* ids, int stride, int pos,
                         int32_t* n_ids, int32_t* finished, int64_t eot, int stop_at_eot, int keep_ids);

@@ -66,7 +66,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_self_attention_bf16", "wt_dbg_cross_attention_bf16", "wt_dbg_encoder_attention_planes", "wt_dbg_gemm_bf16", "wt_dbg_gemm_bf16_ln", "wt_dbg_encoder_attention_bf16",
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_beam_full_step", "wt_dbg_beam_full_finalize",
-    "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_dec_logits_i8", "wt_dbg_dec_gemm_i8", "wt_dbg_enc_quant_rows_i8", "wt_dbg_enc_gemm_i8", "wt_dbg_select_token",
+    "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_dec_logits_i8", "wt_dbg_dec_gemm_i8", "wt_dbg_enc_quant_rows_i8", "wt_dbg_enc_gemm_i8", "wt_dbg_enc_conv_i8", "wt_dbg_select_token",
     "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_language_head_rows", "wt_dbg_self_attention_long",
     "wt_dbg_self_attention_prefill", "wt_dbg_self_attention_long_gather",
     "wt_dbg_self_attention_long_bf16", "wt_dbg_self_attention_long_gather_bf16", "wt_dbg_self_attention_prefill_bf16",
@@ -267,6 +267,7 @@ def lib() -> ctypes.CDLL:
                                          fp, fp, c_int, c_int, ip32, fp, fp, fp, fp, fp, c_int, c_int, fp, fp, c_void_p, fp]
         L.wt_dbg_enc_quant_rows_i8.argtypes = [c_void_p, c_int, c_int, c_int, fp, c_int, c_float, fp, fp, c_void_p, fp]
         L.wt_dbg_enc_gemm_i8.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, fp, fp, fp, fp, c_int, fp]
+        L.wt_dbg_enc_conv_i8.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, fp, fp, fp, fp]
         L.wt_dbg_select_token.argtypes = [c_void_p, c_int, c_int, u64p, ip64, c_int, c_int, ip32, ip32, c_int64, c_int,
                                           c_int]
         L.wt_language_count.argtypes = [c_void_p]
@@ -1968,6 +1969,21 @@ class Engine:
         self._check(lib().wt_dbg_enc_gemm_i8(self._h, epi, M, N, K, qx.ctypes.data_as(c_void_p), _fp(sx), _fp(W), _fp(bias), Rp,
                                              ldc, _fp(Y)))
         return Y
+
+    def dbg_enc_conv_i8(self, X, W, bias, stride=1, epi=0, pos=None, guard=1.0e30):
+        """The int8 encoder conv stem's kernels (option encoder_int8 = 2): the width-3, padding-1
+        convolution at `stride` over X [B][stride * T_out][C_in] fp32 with W [N][C_in][3], quantised with one scale per
+        clip.  epi 0 bias, 1 bias + GELU, 2 bias + GELU + pos [T_out][N].  Returns (Y [B][T_out + 4][N], the last four
+        rows of every clip `guard`; amax_in [B]; amax_out [B])."""
+        X, W = _f32(X), _f32(W)
+        B, T_in, C_in = X.shape
+        N, T_out = W.shape[0], T_in // max(stride, 1)
+        bias, pos = (_f32(a) if a is not None else None for a in (bias, pos))
+        Y = np.full((B, T_out + 4, N), guard, np.float32)
+        amax_in, amax_out = np.full(B, np.nan, np.float32), np.full(B, np.nan, np.float32)
+        self._check(lib().wt_dbg_enc_conv_i8(self._h, stride, epi, B, T_out, C_in, N, _fp(X), _fp(W), _fp(bias), _fp(pos), _fp(Y),
+                                             _fp(amax_in), _fp(amax_out)))
+        return Y, amax_in, amax_out
 
     def dbg_language_head(self, x, ln_g, ln_b, tok_emb, lang_lo, n_lang, xpart=None, ids=None, forced_lang=-1):
         """language_head over rows x [rows][d] (+ xpart) against tok_emb [n_vocab][d], language rows lang_lo .. lang_lo +

@@ -44,6 +44,8 @@ void usage(const char* argv0) {
             << "                  matrices as int8 rows with one scale each, their inputs quantised per row at run time\n"
             << "  --int8-encoder  the int8 dynamic-range encoder blocks (option encoder_int8): the encoder layers' Linear\n"
             << "                  matrices as int8 rows with one scale each, their inputs quantised per row at run time\n"
+            << "  --int8-encoder-conv  --int8-encoder plus the conv stem (option encoder_int8 = 2): both convolutions as int8\n"
+            << "                  rows with one scale per output channel, their input quantised with one scale per clip\n"
             << "  --max-positions N  full-length greedy decoding over N positions, 32 .. n_text_ctx (default: the\n"
             << "                  reference's 31 positions)\n"
             << "  --timestamps    with --max-positions: decode with timestamps and print one line per segment,\n"
@@ -100,7 +102,8 @@ int main(int argc, char* argv[]) {
       suppress_tokens;
   bool word_timestamps = false, suppress_default = false, suppress_blank = false, resample = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
-       no_condition = false, bf16 = false, int8_logits = false, int8_decoder = false, int8_encoder = false;
+       no_condition = false, bf16 = false, int8_logits = false, int8_decoder = false;
+  long int8_encoder = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], v;
     if (a == "-h" || a == "--help") {
@@ -131,8 +134,8 @@ int main(int argc, char* argv[]) {
       int8_decoder = true;
       continue;
     }
-    if (a == "--int8-encoder") {
-      int8_encoder = true;
+    if (a == "--int8-encoder" || a == "--int8-encoder-conv") {
+      int8_encoder = std::max(int8_encoder, a == "--int8-encoder" ? 1l : 2l);
       continue;
     }
     if (a == "--timestamps") {
@@ -268,8 +271,8 @@ int main(int argc, char* argv[]) {
     std::cerr << "--int8-decoder: " << wt_last_error(encdec.handle()) << "\n";
     return 105;
   }
-  if (int8_encoder && wt_engine_set_option(encdec.handle(), "encoder_int8", 1) != WT_OK) {
-    std::cerr << "--int8-encoder: " << wt_last_error(encdec.handle()) << "\n";
+  if (int8_encoder && wt_engine_set_option(encdec.handle(), "encoder_int8", int8_encoder) != WT_OK) {
+    std::cerr << "--int8-encoder" << (int8_encoder == 2 ? "-conv: " : ": ") << wt_last_error(encdec.handle()) << "\n";
     return 105;
   }
   if (!beam.empty()) {

@@ -378,11 +378,12 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
       return fail(h, WT_ERR_DEVICE, err.what());
     }
   } else if (k == "encoder_int8") {
-    // the int8 dynamic-range encoder blocks; the first switch makes the int8 tables and the scratch
-    if (value != 0 && value != 1) return fail(h, WT_ERR_INVALID_ARG, "encoder_int8 must be 0 or 1");
+    // the int8 dynamic-range encoder blocks and, at 2, the conv stem as well (section 40); the
+    // first switch to a level makes its int8 tables and its scratch
+    if (value < 0 || value > 2) return fail(h, WT_ERR_INVALID_ARG, "encoder_int8 must be 0, 1 or 2");
     try {
       e.bind_device();
-      e.set_encoder_int8(value != 0);
+      e.set_encoder_int8(value);
     } catch (const wt::Error& err) {
       return fail(h, err.code, err.what());
     } catch (const std::exception& err) {

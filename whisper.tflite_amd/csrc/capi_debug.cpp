@@ -1439,6 +1439,44 @@ int wt_dbg_enc_gemm_i8(wt_engine* h, int epi, int M, int N, int K, const int8_t*
   });
 }
 
+int wt_dbg_enc_conv_i8(wt_engine* h, int stride, int epi, int B, int T_out, int C_in, int N, const float* X, const float* W,
+                       const float* bias, const float* pos, float* Y, float* amax_in, float* amax_out) {
+  if (!h) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    // the launcher's own refusals first, on the caller's pointers (the check touches no memory), then what the tap's
+    // copies need
+    const int T_in = stride * T_out;
+    wt::EncConvI8Args g;
+    g.X = X; g.amax = X; g.Wq = reinterpret_cast<const int8_t*>(W); g.sw = W; g.bias = bias; g.pos = pos; g.Y = Y;
+    g.y_bs = (long long)(T_out + 4) * N;
+    g.B = B; g.T_in = T_in; g.T_out = T_out; g.C_in = C_in; g.N = N; g.stride = stride;
+    wt::check_enc_conv_i8(g, epi);
+    if (B > 64 || T_out > 8192 || N > 8192 || !amax_in || !amax_out) {
+      throw wt::Error(wt::kErrInvalidArg, "wt_dbg_enc_conv_i8: B <= 64, T_out and N <= 8192, amax_in and amax_out");
+    }
+    std::vector<int8_t> tiled;
+    std::vector<float> sw;
+    wt::conv_table_i8(W, N, C_in, &tiled, &sw);
+    const size_t clip = size_t(T_in) * C_in, clip_p = size_t(T_in + 2) * C_in;
+    std::vector<float> xp(size_t(B) * clip_p, 0.0f);  // one zero row in front of and behind every clip
+    for (int b = 0; b < B; ++b) std::memcpy(xp.data() + b * clip_p + C_in, X + b * clip, clip * sizeof(float));
+    DevArr<int8_t> dW(tiled);
+    DevArr<float> dsw(sw), dX(size_t(B) * clip, X), dXp(xp), dB(size_t(N), bias), dP(pos ? size_t(T_out) * N : 0, pos);
+    DevArr<float> dY(size_t(B) * (T_out + 4) * N, Y);  // the four rows behind every clip are guards
+    DevArr<float> dA(size_t(2) * B);
+    wt::launch_clip_absmax_f32(dX.p, B, long(clip), dA.p, 2 * B, h->impl->stream());
+    g.X = dXp.p; g.amax = dA.p; g.Wq = dW.p; g.sw = dsw.p; g.bias = dB.p; g.pos = pos ? dP.p : nullptr; g.Y = dY.p;
+    g.amax_out = dA.p + B;
+    wt::launch_enc_conv_i8(g, epi, h->impl->stream());
+    h->impl->sync();
+    dY.to_host(Y);
+    dA.to_host(amax_in, size_t(B));
+    std::vector<float> a2(size_t(2) * B);
+    dA.to_host(a2.data());
+    std::memcpy(amax_out, a2.data() + B, size_t(B) * sizeof(float));
+  });
+}
+
 int wt_dbg_select_token(wt_engine* h, int B, int n_tiles, const uint64_t* records, int64_t* ids, int stride, int pos,
                         int32_t* n_ids, int32_t* finished, int64_t eot, int stop_at_eot, int keep_ids) {
   if (!h || !records || !ids || !n_ids || !finished || B < 1 || n_tiles < 1 || pos < 0 || pos + 1 >= stride) {

@@ -289,6 +289,18 @@ void fill_enc_linears(const WtwFile& f, const wtw::Dims& c, EncLinear& conv1, En
 }
 }  // namespace
 
+void conv_table_i8(const float* W, int N, int C_in, std::vector<int8_t>* tiled, std::vector<float>* sw) {
+  const int K = 3 * C_in, KP = (K + 31) / 32 * 32;
+  const std::vector<float> g = conv_gemm_order(W, N, C_in);
+  std::vector<int8_t> q(size_t(N) * K), qp(size_t(N) * KP, int8_t(0));
+  std::vector<float> s(N);
+  quantize_rows_i8(g.data(), N, K, q.data(), s.data());
+  for (int n = 0; n < N; ++n) std::memcpy(qp.data() + size_t(n) * KP, q.data() + size_t(n) * K, size_t(K));
+  tiled->assign(qp.size(), int8_t(0));
+  sw->assign(size_t(N), 0.0f);
+  tile_rows_i8(qp.data(), s.data(), N, KP, tiled->data(), sw->data());
+}
+
 void check_wtw_file(const std::string& path) {
   const WtwFile file(path);  // throws kErrIo / kErrFormat
   if (file.hdr.file_bytes != 0 && file.hdr.file_bytes != file.bytes) {
@@ -1076,6 +1088,7 @@ void Engine::ensure_batch(int batch) {
   ws_.mel_stage = alloc(B * mel_elems(), false);
   ws_.batch = batch;
   if (!enc_blocks_q8_.empty()) alloc_enc_q8_scratch();  // option encoder_int8 has been set: its scratch follows the workspace
+  if (enc_conv1_q8_.w) alloc_enc_conv_scratch();  // ... and level 2's
   HIPCHK(hipStreamSynchronize(stream_));
 }
 
@@ -1408,34 +1421,59 @@ void Engine::encode_enqueue(const float* d_mel, int batch) {
     kt_end();
   };
 
-  kt_begin(kKcTranspose, 0, planes_io * batch * nm * T0 * 4);
-  if (on_planes(conv1_)) {
-    launch_mel_transpose_planes(d_mel, ws_.melTp, melT_plane, a_scale(conv1_), batch, nm, T0, nm, stream_, bf);
-  } else {
+  if (encoder_int8 == 2) {
+    // the stem on the int8 conv kernels.  fp32 mel rows -> conv1 + GELU -> fp32 h1 rows -> conv2 +
+    // GELU + positional embedding -> x; the clips' input scales come from clip_absmax_f32 (conv1) and from conv1's own
+    // epilogue (conv2).  Only rows 1 .. T0 of melT and h1p are ever written, by any mode: their pad rows stay zero.
+    kt_begin(kKcTranspose, 0, 2.0 * batch * nm * T0 * 4);
     launch_mel_transpose(d_mel, ws_.melT, batch, nm, T0, stream_);
-  }
-  kt_end();
-  const float s_conv2 = a_scale(conv2_);
-  {
-    EncGemm e;  // conv1 + GELU: rows (clip, t) read melT rows t..t+2 (input t-1..t+1); row t lands at padded row t + 1 of h1
-    e.w = &conv1_; e.epi = kEpiBias | kEpiGelu;
-    e.A32 = ws_.melT; e.g.A = ws_.melTp; e.g.a_plane = melT_plane;
-    e.g.M = batch * T0; e.g.a_rpb = T0; e.g.a_bs = long(T0 + 2) * nm; e.g.lda = nm;
-    e.g.c_rpb = T0; e.g.c_bs = long(T0 + 2) * d; e.g.ldc = d;
-    e.to_planes = on_planes(conv2_); e.C32 = ws_.h1p + d; e.P = ws_.h1pp + d; e.p_plane = h1p_plane; e.out_scale = &s_conv2;
-    // (the pad rows of h1p are zero and stay zero as planes)
-    e.cvt_src = ws_.h1p; e.cvt_dst = ws_.h1pp; e.cvt_plane = h1p_plane; e.cvt_rows = long(batch) * (T0 + 2);
-    enc_gemm(e);
-  }
-  {
-    EncGemm e;  // conv2 (stride 2) + GELU + positional embedding: output t reads padded rows 2t..2t+2
-    e.w = &conv2_; e.epi = kEpiBias | kEpiGelu | kEpiPos;
-    e.A32 = ws_.h1p; e.g.A = ws_.h1pp; e.g.a_plane = h1p_plane;
-    e.g.M = M; e.g.a_rpb = T; e.g.a_bs = long(T0 + 2) * d; e.g.lda = 2 * d; e.g.ldc = d;
-    e.g.pos = enc_pos; e.g.pos_period = T;
-    e.C32 = ws_.x;
-    fuse_ln(e, enc_layers_[0].attn_ln_g, enc_layers_[0].attn_ln_b, enc_layers_[0].qkv);
-    enc_gemm(e);
+    kt_end();
+    kt_begin(kKcGemmI8, 0, 4.0 * batch * nm * T0);
+    launch_clip_absmax_f32(d_mel, batch, long(nm) * T0, ws_.amax, 2 * batch, stream_);
+    kt_end();
+    EncConvI8Args c1, c2;
+    c1.X = ws_.melT; c1.amax = ws_.amax; c1.Wq = enc_conv1_q8_.w; c1.sw = enc_conv1_q8_.scale; c1.bias = conv1_.bias;
+    c1.Y = ws_.h1p + d; c1.y_bs = (long long)(T0 + 2) * d; c1.amax_out = ws_.amax + batch;
+    c1.B = batch; c1.T_in = T0; c1.T_out = T0; c1.C_in = nm; c1.N = d; c1.stride = 1;
+    kt_begin(kKcGemmI8, 2.0 * batch * T0 * d * 3.0 * nm, 0);
+    launch_enc_conv_i8(c1, kConvGelu, stream_);
+    kt_end();
+    c2.X = ws_.h1p; c2.amax = ws_.amax + batch; c2.Wq = enc_conv2_q8_.w; c2.sw = enc_conv2_q8_.scale; c2.bias = conv2_.bias;
+    c2.pos = enc_pos; c2.Y = ws_.x; c2.y_bs = (long long)T * d;
+    c2.B = batch; c2.T_in = T0; c2.T_out = T; c2.C_in = d; c2.N = d; c2.stride = 2;
+    kt_begin(kKcGemmI8, 2.0 * M * d * 3.0 * d, 0);
+    launch_enc_conv_i8(c2, kConvGeluPos, stream_);
+    kt_end();
+  } else {
+    kt_begin(kKcTranspose, 0, planes_io * batch * nm * T0 * 4);
+    if (on_planes(conv1_)) {
+      launch_mel_transpose_planes(d_mel, ws_.melTp, melT_plane, a_scale(conv1_), batch, nm, T0, nm, stream_, bf);
+    } else {
+      launch_mel_transpose(d_mel, ws_.melT, batch, nm, T0, stream_);
+    }
+    kt_end();
+    const float s_conv2 = a_scale(conv2_);
+    {
+      EncGemm e;  // conv1 + GELU: rows (clip, t) read melT rows t..t+2 (input t-1..t+1); row t lands at padded row t + 1 of h1
+      e.w = &conv1_; e.epi = kEpiBias | kEpiGelu;
+      e.A32 = ws_.melT; e.g.A = ws_.melTp; e.g.a_plane = melT_plane;
+      e.g.M = batch * T0; e.g.a_rpb = T0; e.g.a_bs = long(T0 + 2) * nm; e.g.lda = nm;
+      e.g.c_rpb = T0; e.g.c_bs = long(T0 + 2) * d; e.g.ldc = d;
+      e.to_planes = on_planes(conv2_); e.C32 = ws_.h1p + d; e.P = ws_.h1pp + d; e.p_plane = h1p_plane; e.out_scale = &s_conv2;
+      // (the pad rows of h1p are zero and stay zero as planes)
+      e.cvt_src = ws_.h1p; e.cvt_dst = ws_.h1pp; e.cvt_plane = h1p_plane; e.cvt_rows = long(batch) * (T0 + 2);
+      enc_gemm(e);
+    }
+    {
+      EncGemm e;  // conv2 (stride 2) + GELU + positional embedding: output t reads padded rows 2t..2t+2
+      e.w = &conv2_; e.epi = kEpiBias | kEpiGelu | kEpiPos;
+      e.A32 = ws_.h1p; e.g.A = ws_.h1pp; e.g.a_plane = h1p_plane;
+      e.g.M = M; e.g.a_rpb = T; e.g.a_bs = long(T0 + 2) * d; e.g.lda = 2 * d; e.g.ldc = d;
+      e.g.pos = enc_pos; e.g.pos_period = T;
+      e.C32 = ws_.x;
+      fuse_ln(e, enc_layers_[0].attn_ln_g, enc_layers_[0].attn_ln_b, enc_layers_[0].qkv);
+      enc_gemm(e);
+    }
   }
   constexpr float kQScale = 0.125f * 1.44269504088896340736f;  // d_head^-1/2 * log2(e): softmax as exp2
   for (int l = 0; l < c.n_audio_layer; ++l) {
@@ -1656,8 +1694,20 @@ void Engine::alloc_enc_q8_scratch() {
   ws_.sx = reinterpret_cast<float*>(ws_.qx + rows * 4 * dims_.n_audio_state);
 }
 
-void Engine::set_encoder_int8(bool on) {
+void Engine::alloc_enc_conv_scratch() {
+  if (ws_.batch == 0 || dims_.n_audio_state == 0) return;  // no workspace yet: ensure_batch calls again
+  void* p = nullptr;
+  HIPCHK(hipMalloc(&p, size_t(ws_.batch) * 2 * sizeof(float)));
+  ws_.owned.push_back(p);
+  ws_.amax = static_cast<float*>(p);
+}
+
+void Engine::set_encoder_int8(long level) {
   require_idle();
+  const bool on = level != 0;
+  if (level == 2 && dims_.n_audio_state != 0 && dims_.n_mels != 80 && dims_.n_mels != 128) {
+    throw Error(kErrUnsupported, "encoder_int8 = 2: n_mels 80 or 128");
+  }
   if (on && enc_blocks_q8_.empty()) {
     if (dims_.n_audio_state == 0) throw Error(kErrUnsupported, "front-end-only engine: no model weights loaded");
     const int d = dims_.n_audio_state;
@@ -1688,7 +1738,28 @@ void Engine::set_encoder_int8(bool on) {
     alloc_enc_q8_scratch();
     enc_blocks_q8_ = std::move(blocks);
   }
-  encoder_int8 = on ? 1 : 0;
+  if (level == 2 && !enc_conv1_q8_.w) {
+    // the two conv tables (conv_table_i8: [co][tap C_in + ci], K padded to 32) and the amax scratch
+    const int d = dims_.n_audio_state, nm = dims_.n_mels;
+    const WtwFile file(weights_path_);
+    auto table = [&](const float* W, int C_in) {
+      std::vector<int8_t> tiled;
+      std::vector<float> sw;
+      conv_table_i8(W, d, C_in, &tiled, &sw);
+      void* p = nullptr;
+      HIPCHK(hipMalloc(&p, tiled.size()));
+      allocations_.push_back(p);
+      HIPCHK(hipMemcpy(p, tiled.data(), tiled.size(), hipMemcpyHostToDevice));
+      return Int8W{static_cast<const int8_t*>(p), upload(sw)};
+    };
+    const Int8W c1 = table(file.get("encoder.conv1.weight", size_t(d) * nm * 3), nm);
+    const Int8W c2 = table(file.get("encoder.conv2.weight", size_t(d) * d * 3), d);
+    HIPCHK(hipStreamSynchronize(stream_));
+    alloc_enc_conv_scratch();
+    enc_conv1_q8_ = c1;
+    enc_conv2_q8_ = c2;
+  }
+  encoder_int8 = level;
 }
 
 void Engine::set_bf16(bool on) {

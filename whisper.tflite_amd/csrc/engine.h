@@ -336,8 +336,11 @@ class Engine {
   // cross-K/V projection, the final LayerNorm (unfused) and the front end.  Set through set_encoder_int8(): the first
   // switch makes the tables and the qx / sx scratch of the workspace batch; an engine that never sets it allocates
   // nothing.  No decoder graph key holds it: the decoder reads the encoder's output, never its launches.
+  // 2 = the blocks as at 1 plus the conv stem (k_enc_conv_i8.hip): conv1 and conv2 as int8 implicit
+  // GEMMs with one input scale per clip, fp32 mel in, fp32 residual stream out; no plane is written for the stem.  The
+  // first switch to 2 makes the two conv tables and the amax scratch; n_mels outside {80, 128} is kErrUnsupported.
   long encoder_int8 = 0;
-  void set_encoder_int8(bool on);
+  void set_encoder_int8(long level);
   // encoder kernel-class timers (wt_last_kernel_stats): 0 = off, N = event pairs around every launch of every N-th
   // encoder pass; passes without them report zero launches
   long kernel_timers = 1;
@@ -804,6 +807,8 @@ class Engine {
   };
   std::vector<EncBlockInt8> enc_blocks_q8_;  // empty until the option is first set
   void alloc_enc_q8_scratch();  // qx [batch T][4 d] int8 + sx [batch T] for the workspace batch, into ws_
+  Int8W enc_conv1_q8_, enc_conv2_q8_;  // encoder_int8 = 2: conv_table_i8 of the two convolutions, null until first set
+  void alloc_enc_conv_scratch();       // amax [2][batch] for the workspace batch, into ws_
   // front end
   const unsigned short* dft_basis_p_ = nullptr;  // [dft_n][dft_k] windowed basis, rows (2 k, 2 k + 1) = (re, im) of bin k, as fp16 planes
   const float* dft_zero_bias_ = nullptr;
@@ -902,6 +907,8 @@ class Engine {
     // option encoder_int8: the quantised rows of the contraction in flight and their scales (null until the option is set)
     int8_t* qx = nullptr;
     float* sx = nullptr;
+    // encoder_int8 = 2: the clips' largest |input| of conv1 [batch] and of conv2 [batch] (null until that level is set)
+    float* amax = nullptr;
     // front end
     unsigned short* pcm_planes = nullptr;
     float *pw = nullptr, *melacc = nullptr;

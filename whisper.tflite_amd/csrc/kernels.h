@@ -317,6 +317,39 @@ struct EncGemmI8Args {
 void check_enc_gemm_i8(const EncGemmI8Args& a, int epi);
 void launch_enc_gemm_i8(const EncGemmI8Args& a, int epi, hipStream_t s);
 
+// The int8 dynamic-range encoder conv stem (k_enc_conv_i8.hip, option "encoder_int8" = 2).
+// launch_clip_absmax_f32: amax[b] = max |x| over x [B][n] (fmaxf: a NaN is dropped), n a multiple of 4; the first
+// n_zero >= B floats of amax are zeroed on the stream in front (by a kernel: nothing a captured graph cannot hold).
+void launch_clip_absmax_f32(const float* x, int B, long n, float* amax, int n_zero, hipStream_t s);
+// launch_enc_conv_i8: the width-3, padding-1 convolution at stride 1 or 2 as an implicit int8 GEMM.  X fp32
+// [B][T_in + 2][C_in] with zero pad rows (output row t reads rows stride t .. stride t + 2), quantised while it is staged
+// with the clip's scale amax[b] / 127; Wq / sw = tile_rows_i8 of quantize_rows_i8 of conv_gemm_order(W) [N][3 C_in], K
+// padded with zero columns to a multiple of 32; t = ((float)acc * sx[b]) * sw[n]; kConvBias: t + bias, kConvGelu:
+// gelu(t + bias), kConvGeluPos: gelu(t + bias) + pos[t_out][n].  Clip b's output row t is Y + b y_bs + t N.  amax_out
+// (optional, zeroed by the caller): max |output| per clip, merged by atomicMax.  kErrInvalidArg (check_enc_conv_i8, which
+// touches no memory) for: C_in outside {80, 128} at stride 1 or {128, 384, 512} at stride 2, another stride, N no
+// positive multiple of 128, B < 1, T_out < 1, T_in != stride T_out, a null required pointer, kConvGeluPos without pos,
+// another epilogue, y_bs < T_out N, and an extent (rows rounded up to 128) whose byte offsets leave 32 bits.
+enum EncConvEpi { kConvBias = 0, kConvGelu = 1, kConvGeluPos = 2 };
+struct EncConvI8Args {
+  const float* X = nullptr;
+  const float* amax = nullptr;  // [B]
+  const int8_t* Wq = nullptr;   // [N / 32][KP / 32][64 lanes][16]
+  const float* sw = nullptr;    // [N]
+  const float* bias = nullptr;
+  const float* pos = nullptr;
+  float* Y = nullptr;
+  long long y_bs = 0;
+  float* amax_out = nullptr;
+  int B = 0, T_in = 0, T_out = 0, C_in = 0, N = 0, stride = 0;
+};
+void check_enc_conv_i8(const EncConvI8Args& a, int epi);
+void launch_enc_conv_i8(const EncConvI8Args& a, int epi, hipStream_t s);
+// A convolution weight W [N][C_in][3] as the model file holds it -> the conv kernels' table (host, engine.cpp): the
+// implicit GEMM's order [N][tap C_in + ci], quantize_rows_i8 over those 3 C_in columns, zero columns up to KP = 3 C_in
+// rounded up to 32, tile_rows_i8.  tiled: N x KP bytes, sw: N floats (N a multiple of 32).
+void conv_table_i8(const float* W, int N, int C_in, std::vector<int8_t>* tiled, std::vector<float>* sw);
+
 // ------------------------------------------------------------- LayerNorm ---
 // y[m][:] = (x[m][:] - mean) * rstd * g + b, eps 1e-5, one wavefront per row.
 void launch_layernorm(const float* x, float* y, const float* g, const float* b, int M, int d,
