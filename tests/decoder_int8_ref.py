@@ -45,11 +45,12 @@ def quantized_weights(dims, tensors):
             for l in range(dims["n_text_layer"]) for n in names}
 
 
-def decoder_rows(dims, tensors, row, enc, qweights=None, cross_out=True):
+def decoder_rows(dims, tensors, row, enc, qweights=None, cross_out=True, want_logits=True):
     """align_ref.decoder_forward's float64 decoder on one id row, returning (logits [L][V], final-LayerNorm rows [L][d]).
     With qweights (quantized_weights) the five matrices are int8 rows and each of their input rows goes through the same
     quantiser (of the float64 row rounded to float32); cross_out False keeps the cross-attention out-projection in
-    float64 (the cached cross-attention form)."""
+    float64 (the cached cross-attention form); want_logits False returns None for the logits (a step-by-step decode
+    takes the head of its last row alone)."""
     t = {k: np.asarray(v, np.float64) for k, v in tensors.items() if k.startswith("decoder.")}
     H, L = dims["n_text_head"], len(row)
     ln, enc = align_ref._ln, np.asarray(enc, np.float64)
@@ -87,4 +88,4 @@ def decoder_rows(dims, tensors, row, enc, qweights=None, cross_out=True):
         h = gelu64(lin(h, b + ".mlp.0.weight") + t[b + ".mlp.0.bias"])
         x = x + (lin(h, b + ".mlp.2.weight") + t[b + ".mlp.2.bias"])
     x = ln(x, t["decoder.ln.weight"], t["decoder.ln.bias"])
-    return x @ t["decoder.token_embedding.weight"].T, x
+    return (x @ t["decoder.token_embedding.weight"].T if want_logits else None), x

@@ -41,6 +41,7 @@ PROMPT_OTHER_LEN = [SOT, LANG_LO + 2, TRANSCRIBE]                # another lengt
 P_SHORT, P_LONG = 40, 96      # 40 ends inside the second 32-position segment, 96 makes three segments
 SLOTS = 24                    # the engine's pipeline slots: every encoder pass of a 31-position call takes the next one
 C2, C4, C6 = (1, 4), (0, 1, 4, 5), (0, 1, 2, 3, 4, 5)   # clips of scores_model.plain_mels()'s twelve
+G2 = (7, 10)                  # the clips of the int8 family's 31-position greedy pairs (NEIGHBOURS)
 SEED_A, SEED_B = 1, (7 << 32) | 5
 TEMP = 700
 MAX_INITIAL_OTHER = 0         # <|0.00|> alone may open the row (the default allows 50 ticks)
@@ -63,7 +64,7 @@ DEFAULTS = dict(
     temperature_fallback=0, temperature_increment=200, compression_ratio_threshold=2400, logprob_threshold=-1000,
     no_speech_threshold=600, seed=0, best_of=1, fallback_beam=0, beam_size=1, full_beam=0, seek=0,
     condition_on_previous_text=1, word_timestamps=0, stop_at_eot=1, cross_absorb=1, cross_chunks=0, abs_chunks=0,
-    fc2_ksplit=2, max_tokens=30, language=2, bf16=0, suppress_default=0)
+    fc2_ksplit=2, max_tokens=30, language=2, bf16=0, suppress_default=0, logits_int8=0, decoder_int8=0, encoder_int8=0)
 # settings that are no numeric option: name -> what reset() puts back
 SPECIAL_DEFAULTS = dict(prompt=(), context=(), contexts=(), suppress=((), ()))
 
@@ -163,8 +164,65 @@ def _wide():
 SEEK_WINDOWS = 3
 SEEK = Kind("seek/long", "seek", "long", (), dict(seek=1, condition_on_previous_text=0, timestamps=1, scores=1,
                                                   max_positions=P_SHORT))
-KINDS = {k.name: k for k in _short() + _full(P_SHORT) + _full(P_LONG) + _wide() + [SEEK]}
-FAMILIES = ("short", "full40", "full96", "wide", "seek")
+LOGITS, DECODER = dict(logits_int8=1), dict(decoder_int8=1)
+BOTH = dict(logits_int8=1, decoder_int8=1)
+ALL = dict(BOTH, encoder_int8=2)
+
+
+def _int8():
+    """The int8 options (DESIGN.md sections 37 .. 40) through every decode chain and all five graph keys: the chains of the
+    other families with logits_int8, decoder_int8 or both on, and the 31-position greedy call with encoder_int8."""
+    def k(name, entry="batch", clips=C2, P=0, **o):
+        return Kind("int8/" + name, "int8", entry, clips, dict(o, max_positions=P) if P else o)
+
+    def full(name, P=P_SHORT, **o):
+        return k("full_" + name, "full", P=P, **o)
+
+    def wide(name, **o):
+        return k("wide_" + name, "full", P=P_SHORT, **o)
+
+    best_of3 = dict(best_of=3, temperature=TEMP, seed=SEED_A)
+    return [
+        # the greedy key; the kinds of the greedy neighbour pairs at G2, where their ids part (see NEIGHBOURS)
+        k("plain", clips=G2),                         # short/default at G2
+        k("logits", clips=G2, **LOGITS),
+        k("decoder", clips=G2, **DECODER),
+        k("both", clips=G2, **BOTH),
+        k("both_ksplit1", fc2_ksplit=1, **BOTH),      # fc2 is never split under decoder_int8
+        k("both_no_absorb", cross_absorb=0, **BOTH),
+        k("both_bf16", bf16=1, **BOTH),
+        k("encoder1", clips=G2, encoder_int8=1),      # fp32 storage: encoder_int8 refuses under bf16
+        k("encoder2", clips=G2, encoder_int8=2),
+        k("all", **ALL),
+        k("detect_decoder", entry="detect", **DECODER),   # the language heads read x whole (fc2_split() is false)
+        k("language_auto_decoder", language=-1, **DECODER),
+        k("pipeline_all", entry="pipeline", clips=C4, **ALL),
+        # the 31-position beam key (captured slot by slot)
+        k("beam2_decoder", beam_size=2, **DECODER),
+        k("beam2_both", beam_size=2, **BOTH),
+        # the full key
+        full("plain_logits", **LOGITS),
+        full("plain_decoder", **DECODER),
+        full("plain_both", **BOTH),
+        full("scores_logits", scores=1, **LOGITS),
+        full("ts_scores_both", timestamps=1, scores=1, **BOTH),
+        full("temp_both", temperature=TEMP, seed=SEED_A, **BOTH),
+        full("fallback_both", **dict(FALLBACK, **BOTH)),
+        full("words_both", timestamps=1, word_timestamps=1, **BOTH),   # the alignment pass: int8 blocks, wq_abs on dec_gemm
+        full("context_both", context=CONTEXT, **BOTH),                 # the ragged prefill, eager
+        full("contexts_both", contexts=CONTEXTS, **BOTH),
+        full("long_both", P=P_LONG, **BOTH),                           # three segments, positions past 64
+        # the beam_full and best_of keys
+        wide("beam2_decoder", full_beam=1, beam_size=2, **DECODER),
+        wide("beam2_both", full_beam=1, beam_size=2, **BOTH),
+        wide("best_of3_logits", **dict(best_of3, **LOGITS)),
+        wide("best_of3_both", **dict(best_of3, **BOTH)),
+        Kind("int8/seek_both", "int8", "long", (), dict(SEEK.options, **BOTH)),
+    ]
+
+
+KINDS = {k.name: k for k in _short() + _full(P_SHORT) + _full(P_LONG) + _wide() + [SEEK] + _int8()}
+FAMILIES = ("short", "full40", "full96", "wide", "seek", "int8")
 
 
 def family(name):
@@ -194,6 +252,24 @@ NEIGHBOURS = [
     ("full40/temp_seed_a", "wide/best_of3", "best_of"),
     ("full40/plain", "full40/ts", "timestamps"),
     ("short/default", "short/max_tokens12", "max_tokens"),
+    # The int8 options: per graph key one pair in decoder_int8 alone and one in logits_int8 alone.  Four keys' kinds return
+    # float fields (beam scores, best-of sums, token log-probabilities); the plain greedy kinds return ids only, and a 1e-2
+    # change of the logits moves no id of clips C2 at 31 positions.  Decided on the CPU (float64 decoders with the options
+    # restated, test_int8_pairs_differ): at G2 clip 10 reaches EOT one position later under the int8 head, clip 7 four
+    # positions later under the int8 blocks behind it, and clip 1 of C2 at 40 positions never under the int8 blocks; the top-two
+    # margins at those positions are 0.03 .. 0.2, a hundred times the fp32 path's error.  So the greedy pairs are asserted.
+    ("int8/plain", "int8/logits", "logits_int8"),
+    ("int8/logits", "int8/both", "decoder_int8"),
+    ("short/beam2", "int8/beam2_decoder", "decoder_int8"),
+    ("int8/beam2_decoder", "int8/beam2_both", "logits_int8"),
+    ("full40/plain", "int8/full_plain_decoder", "decoder_int8"),
+    ("full40/scores", "int8/full_scores_logits", "logits_int8"),
+    ("wide/beam2", "int8/wide_beam2_decoder", "decoder_int8"),
+    ("int8/wide_beam2_decoder", "int8/wide_beam2_both", "logits_int8"),
+    ("wide/best_of3", "int8/wide_best_of3_logits", "logits_int8"),
+    ("int8/wide_best_of3_logits", "int8/wide_best_of3_both", "decoder_int8"),
+    # encoder_int8 0 against 1 moves the encoder output by 5e-2: clips 7 and 10 both reach EOT elsewhere
+    ("int8/plain", "int8/encoder1", "encoder_int8"),
 ]
 # Pairs that change the arrangement of the arithmetic alone: they may give identical bits; reported, never asserted.
 ARRANGEMENTS = [
@@ -203,6 +279,11 @@ ARRANGEMENTS = [
     ("short/default", "short/abs3", "abs_chunks"),
     ("short/default", "short/no_absorb", "cross_absorb"),
     ("full40/plain", "full40/no_absorb", "cross_absorb"),
+    # encoder_int8 1 against 2 (the conv stem as well) moves the encoder output by another 5e-2, and the float64 decode of
+    # none of the twelve clips parts at 31 positions (test_int8_pairs_differ reports it).  Acceptable: the option is in no
+    # decoder graph key (the encoder pass is not captured with the decoder), and level 2's encoder output is held to its
+    # float64 reference by tests/test_gpu_enc_conv_i8.py.
+    ("int8/encoder1", "int8/encoder2", "encoder_int8"),
 ]
 
 
@@ -236,6 +317,8 @@ def refusal(kind):
                      ("seek", s["seek"]), ("context", context), ("suppress", suppressing)):
         if on and P <= 0:
             return name + ": full-length decoding only"
+    if s["encoder_int8"] and s["bf16"]:  # encode_enqueue; logits_int8 and decoder_int8 run in both storage modes
+        return "encoder_int8 covers the fp32 storage mode"
     if s["skip_silence"] and not s["scores"]:
         return "skip_silence needs scores"
     if s["seek"] and not s["timestamps"]:

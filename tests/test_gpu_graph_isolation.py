@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 WARM = ms.with_clips(ms.KINDS["short/default"], ms.C6)   # sizes the workspace once, so that no schedule grows it
 STABLE = {"short": "short/default", "full40": "full40/ts_scores", "full96": "full96/fallback",
-          "wide": "wide/fallback_beam", "seek": "seek/long"}
+          "wide": "wide/fallback_beam", "seek": "seek/long", "int8": "int8/full_ts_scores_both"}
 
 
 class World:
@@ -181,8 +181,17 @@ def test_neighbour_pairs(world):
     try:
         for a, b, setting in ms.NEIGHBOURS + ms.ARRANGEMENTS:
             ka, kb = ms.KINDS[a], ms.KINDS[b]
+            start = v.slot
             for kind in (ka, ka, kb, kb, ka, kb):
                 v.visit(kind)
+            if ms.per_slot(ka):
+                # 31-position beam search captures slot by slot and every visit takes the next slot: so far no visit ran
+                # in a slot the other kind had captured in.  Go round the slots once; then B where A captured, A where A
+                # did, A where B did.
+                while v.slot != start:
+                    v.visit(ms.KINDS["short/default"])
+                for kind in (kb, ka, ka):
+                    v.visit(kind)
         assert v.eng.get_option("use_graphs") == 1
     finally:
         v.close()
@@ -217,9 +226,33 @@ def test_reallocations_destroy_exactly_their_graphs(world):
         v.close()
 
 
+def test_int8_reallocations(world):
+    """The int8 options across both reallocations: encoder_int8's scratch of quantised rows is part of the workspace and is
+    made again with it (alloc_enc_q8_scratch, alloc_enc_conv_scratch); the int8 tables of all three options are the
+    engine's own and outlive both.  Every visit against its fresh eager reference."""
+    every, plain = ms.KINDS["int8/all"], ms.KINDS["int8/full_plain_both"]
+    v = Visits(world, warm=False)
+    try:
+        assert v.visit(every) > 0
+        held = v.cached()
+        v.visit(ms.with_clips(every, ms.C6))     # the workspace and the encoder's int8 scratch grow: every graph goes
+        assert v.cached() == held                # ... and the 6-clip call has captured its own
+        assert v.visit(every) == held
+        first = v.visit(plain)
+        assert first > 0
+        v.visit(ms.with_clips(plain, ms.C6))     # the self-attention cache grows: the full-length greedy graphs go
+        assert v.visit(plain) == first
+        assert v.visit(plain, replay=True) == 0
+        v.visit(ms.KINDS["short/default"])       # every option off, the int8 tables still allocated: the default's bits
+        assert [v.eng.get_option(k) for k in ("logits_int8", "decoder_int8", "encoder_int8")] == [0, 0, 0]
+        assert v.eng.get_option("use_graphs") == 1
+    finally:
+        v.close()
+
+
 def test_cross_family_interleaving(world):
     names = ("short/default", "short/beam4", "full40/ts_scores", "full40/suppress_l1", "full96/temp_seed_a", "full96/words",
-             "wide/beam3", "wide/best_of3_ts", "seek/long")
+             "wide/beam3", "wide/best_of3_ts", "seek/long", "int8/both", "int8/wide_beam2_both", "int8/all")
     order = [ms.KINDS[n] for n in names] * 3
     random.Random(5).shuffle(order)
     v = Visits(world)

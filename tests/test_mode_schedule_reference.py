@@ -60,8 +60,20 @@ def test_every_pair_differs_in_exactly_its_named_setting():
         assert (ka.entry, ka.clips) == (kb.entry, kb.clips), (a, b)
     named = {s for _, _, s in ms.NEIGHBOURS}
     assert {"max_initial_timestamp", "stop_at_eot", "prompt", "seed", "suppress", "beam_size", "best_of",
-            "timestamps"} <= named
-    assert {s for _, _, s in ms.ARRANGEMENTS} == {"fc2_ksplit", "cross_chunks", "abs_chunks", "cross_absorb"}
+            "timestamps", "logits_int8", "decoder_int8", "encoder_int8"} <= named
+    assert {s for _, _, s in ms.ARRANGEMENTS} == {"fc2_ksplit", "cross_chunks", "abs_chunks", "cross_absorb", "encoder_int8"}
+    # the int8 entry of every one of the five graph keys: a pair in decoder_int8 alone and one in logits_int8 alone
+    for setting in ("decoder_int8", "logits_int8"):
+        keys = set()
+        for a, b, s in ms.NEIGHBOURS:
+            if s == setting:
+                assert ms.key_families(ms.KINDS[a]) == ms.key_families(ms.KINDS[b]) and len(ms.key_families(ms.KINDS[a])) == 1, (a, b)
+                keys |= set(ms.key_families(ms.KINDS[a]))
+        assert keys == {"greedy", "beam", "full", "beam_full", "best_of"}, setting
+    # encoder_int8: 0 against 1 and 1 against 2, both on the 31-position greedy entry
+    levels = {tuple(ms.settings_of(ms.KINDS[k])["encoder_int8"] for k in (a, b)): ms.KINDS[a].entry
+              for a, b, s in ms.NEIGHBOURS + ms.ARRANGEMENTS if s == "encoder_int8"}
+    assert levels == {(0, 1): "batch", (1, 2): "batch"}
     # the two prompt pairs: other ids at equal length, and another length
     assert len(ms.PROMPT_OTHER_IDS) == len(ms.PROMPT) != len(ms.PROMPT_OTHER_LEN)
     # the two list pairs: equal counts and other ids, and other counts
@@ -89,7 +101,10 @@ def test_every_kind_passes_the_engines_refusal_rules():
         ms.KINDS["short/beam2"]._replace(options=dict(beam_size=2, language=-1)),
         ms.KINDS["short/default"]._replace(options=dict(timestamps=1)),           # full-length decoding only
         ms.KINDS["short/language_auto"]._replace(options=dict(language=-1, prompt=tuple(ms.PROMPT))),
+        ms.KINDS["int8/encoder1"]._replace(options=dict(encoder_int8=1, bf16=1)),  # encoder_int8: fp32 storage only
+        ms.KINDS["int8/all"]._replace(options=dict(ms.ALL, bf16=1)),
     ]
+    assert ms.refusal(ms.KINDS["int8/both_bf16"]) is None   # logits_int8 and decoder_int8 run in both storage modes
     for kind in bad:
         assert ms.refusal(kind) is not None, kind.options
 
@@ -104,7 +119,25 @@ def test_key_families_of_the_kinds():
     assert ms.key_families(ms.KINDS["wide/best_of3"]) == ("best_of",)
     assert ms.key_families(ms.KINDS["wide/fallback_beam"]) == ("beam_full", "best_of")
     assert ms.key_families(ms.KINDS["full40/fallback"]) == ("full",)
-    assert [k.name for k in ms.KINDS.values() if ms.per_slot(k)] == ["short/beam2", "short/beam4"]
+    assert [k.name for k in ms.KINDS.values() if ms.per_slot(k)] == ["short/beam2", "short/beam4", "int8/beam2_decoder",
+                                                                     "int8/beam2_both"]
+    # the int8 family: an int8 option changes no chain, so every kind takes the keys of its kind without the option
+    want = {"greedy": ["plain", "logits", "decoder", "both", "both_ksplit1", "both_no_absorb", "both_bf16", "encoder1",
+                       "encoder2", "all", "detect_decoder", "language_auto_decoder", "pipeline_all"],
+            "beam": ["beam2_decoder", "beam2_both"],
+            "full": ["full_plain_logits", "full_plain_decoder", "full_plain_both", "full_scores_logits", "full_ts_scores_both",
+                     "full_temp_both", "full_fallback_both", "full_words_both", "full_long_both", "seek_both"],
+            "": ["full_context_both", "full_contexts_both"],
+            "beam_full": ["wide_beam2_decoder", "wide_beam2_both"],
+            "best_of": ["wide_best_of3_logits", "wide_best_of3_both"]}
+    got = {}
+    for kind in ms.family("int8"):
+        got.setdefault("+".join(ms.key_families(kind)), []).append(kind.name.split("/")[1])
+    assert got == want
+    for kind in ms.family("int8"):
+        plain = kind._replace(options={k: v for k, v in kind.options.items() if not k.endswith("_int8")})
+        assert ms.key_families(plain) == ms.key_families(kind) and ms.slot_advance(plain) == ms.slot_advance(kind)
+    assert ms.slot_advance(ms.KINDS["int8/pipeline_all"]) == 2 and ms.slot_advance(ms.KINDS["int8/seek_both"]) == 0
 
 
 # ---- the neighbour pairs on the CPU references ------------------------------------------------------------------------
@@ -203,3 +236,73 @@ def test_beam_size_pairs_differ(ref):
         short[b] = [beam_ref.beam_search(fn, ms.PROMPT, K, 30, ms.EOT)["ids"] for K in (2, 4)]
     assert any(full[b][0] != full[b][1] for b in ms.C2)      # wide/beam2 against wide/beam3
     assert any(short[b][0] != short[b][1] for b in ms.C2)    # short/beam2 against short/beam4
+
+
+# ---- the int8 pairs on float64 decoders that restate the options ------------------------------------------------------
+def test_int8_pairs_differ(orc, assets, tmp_path_factory):
+    """The greedy int8 pairs of NEIGHBOURS return ids alone: on the oracle's encoder output the float64 decoder
+    (decoder_int8_ref.decoder_rows) decodes their clips unquantised, with the int8 blocks, with the int8 head and with both,
+    at 30 positions (the 31-position kinds) and at P_SHORT (the full-length ones, cut from the same decode: every step
+    depends on its prefix alone), and the ids of some clip differ — decisively: where they part, both decodes' top-two
+    margins are above 1e-2, a hundred times what the fp32 path is off.  Calls of two clips take the cached cross-attention
+    form: its out-projection stays unquantised.  encoder_int8: the float64 fake-quantised encoders of
+    tests/encoder_int8_ref.py and tests/encoder_conv_int8_ref.py in front of the unquantised decoder."""
+    import numpy as np
+
+    import encoder_conv_int8_ref
+    import encoder_int8_ref
+    import int8_modes_ref
+    from wtw import read_wtw
+
+    prefix, _ = assets("micro")
+    path = str(tmp_path_factory.mktemp("mode-schedule-int8") / "micro-schedule.wtw")
+    ms.write_model(prefix + ".wtw", path)
+    dims, tensors = read_wtw(path)
+    net, data, model = int8_modes_ref.Net(dims, tensors), ms.Data(), orc.Model(path)
+    try:
+        enc = {b: np.asarray(model.encode(data.mel[b]), np.float64) for b in set(ms.C2 + ms.G2)}
+    finally:
+        model.close()
+    memo = {}
+
+    def decode(b, options, max_pos):
+        """(ids, margins) of clip b at max_pos positions under a kind's options, stop_at_eot = 1"""
+        s = dict(ms.DEFAULTS, **options)
+        key = (b, s["logits_int8"], s["decoder_int8"], s["encoder_int8"])
+        if key not in memo:
+            e = enc[b]
+            if s["encoder_int8"] == 1:
+                e = encoder_int8_ref.encoder_rows(dims, tensors, data.mel[b], encoder_int8_ref.quantized_weights(dims, tensors))
+            elif s["encoder_int8"] == 2:
+                e = encoder_conv_int8_ref.encoder_rows(dims, tensors, data.mel[b])
+            memo[key] = net.greedy(np.asarray(e, np.float64), ms.PROMPT, P, ms.EOT, bool(s["decoder_int8"]), bool(s["logits_int8"]))
+        ids, margins = memo[key]
+        ids = ids[: max_pos + 1]
+        return ids, margins[: len(ids) - len(ms.PROMPT)]
+
+    def parting(a, b):
+        """per clip: None, or (position, margin of a there, margin of b there)"""
+        ka, kb = ms.KINDS[a], ms.KINDS[b]
+        max_pos = ka.options.get("max_positions", 30)
+        out = []
+        for clip in ka.clips:
+            (x, mx), (y, my) = decode(clip, ka.options, max_pos), decode(clip, kb.options, max_pos)
+            i = next((i for i in range(min(len(x), len(y))) if x[i] != y[i]), None)
+            assert i is not None or len(x) == len(y)
+            out.append(None if i is None else (i, mx[i - len(ms.PROMPT)], my[i - len(ms.PROMPT)]))
+        return out
+
+    greedy = [(a, b, s) for a, b, s in ms.NEIGHBOURS if s.endswith("_int8") and ms.key_families(ms.KINDS[a]) in (("greedy",), ("full",))
+              and not ms.settings_of(ms.KINDS[a])["scores"]]
+    assert [p[:2] for p in greedy] == [("int8/plain", "int8/logits"), ("int8/logits", "int8/both"),
+                                       ("full40/plain", "int8/full_plain_decoder"), ("int8/plain", "int8/encoder1")]
+    for a, b, setting in greedy:
+        parts = parting(a, b)
+        print("%s / %s (%s): %s" % (a, b, setting, parts))
+        assert any(p is not None and min(p[1:]) > 1e-2 for p in parts), (a, b, parts)
+    # reported, not asserted: the arrangement pair, and what the same settings do at the clips C2
+    print("int8/encoder1 / int8/encoder2:", parting("int8/encoder1", "int8/encoder2"))
+    for a, b in (("int8/plain", "int8/logits"), ("int8/logits", "int8/both")):
+        ka, kb = ms.with_clips(ms.KINDS[a], ms.C2), ms.with_clips(ms.KINDS[b], ms.C2)
+        same = all(decode(c, ka.options, 30)[0] == decode(c, kb.options, 30)[0] for c in ms.C2)
+        print("%s / %s at C2: %s" % (a, b, "the same ids" if same else "other ids"))
