@@ -173,6 +173,15 @@ int wt_engine_dims(const wt_engine* h, wt_dims* out);
  * channel, their fp32 input quantised with one scale per clip (its largest |x| / 127) while the kernel stages it, so the
  * encoder is int8 from the mel to ln_post; the two conv tables are made at the first switch to 2, n_mels other than 80 or
  * 128 is WT_ERR_UNSUPPORTED; anything but 0, 1 or 2 is WT_ERR_INVALID_ARG),
+ * "cross_int8" (0 = default; 1 = the absorbed cross-attention on an int8 image of the encoder output, DESIGN.md section
+ * 41: every encode also stores its output as int8 rows + one fp32 scale per key row (the values the default kernel
+ * reconstructs from its planes, or the bf16 values, through wt_quantize_rows_i8's arithmetic on the device), every decoder
+ * pass in the absorbed form quantises its absorbed query columns the same way, takes the scores as int32 sums times the
+ * two scales and the contexts on the int8 values with weights p * scale: 1 byte per element streamed where the default
+ * streams 4 and the bf16 storage mode 2; both storage modes, every decoding mode, every graph key; the images are
+ * allocated at the first switch, and a switch with encoder output resident quantises it then; the cached cross-K/V form
+ * of small synchronous batches, word timestamps' alignment scores and the projections around the attention keep their
+ * format; anything but 0 or 1 is WT_ERR_INVALID_ARG),
  * "last_batches" (N = the next N pipelined submits are the last of a job: they are decoded one chain per batch, the very
  * last on the encoder's stream, so the pipeline drains sooner; counts down to 0 by itself, may be set with batches in
  * flight), "force_fallback" (test hook: bit mask of contractions sent to the full-range kernels, nothing in flight).

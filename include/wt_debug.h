@@ -113,6 +113,16 @@ int wt_dbg_cross_absorbed_bf16(wt_engine* h, int batch, int heads, int T, int ch
 int wt_dbg_cross_absorbed_chain(wt_engine* h, int bf16, int batch, int heads, int T, int chunks, int nq, int split, int n_src,
                                 const float* const* E_src, const float* qp, const float* wv, const float* bv, int mode,
                                 int p0_only, int nq_only, float* out, float* ws);
+/* the same chain on the int8 image of E (k_cross_absorbed_i8.hip, option "cross_int8"): every source is split into
+ * planes (bf16 != 0: rounded to ONE bf16 plane) exactly as above, quantised on the device by quantize_e_rows_i8 into an
+ * int8 image and a scale array of its own (room for `batch` clips; the absent clips hold 0x7F bytes and NaN scales) and
+ * attended to by launch_cross_absorbed_i8.  modes 0 and 1 as above.  omit = 1 / 2 hands the launcher no int8 image of
+ * the first source / no scales of the last one (it must refuse).  Also returns qe_out[i] [clips of group i * T][d],
+ * se_out[i] [clips of group i * T] and the planes' power of two e_scale_out. */
+int wt_dbg_cross_absorbed_i8_chain(wt_engine* h, int bf16, int batch, int heads, int T, int chunks, int nq, int split, int n_src,
+                                   const float* const* E_src, const float* qp, const float* wv, const float* bv, int mode,
+                                   int p0_only, int nq_only, int omit, float* out, float* ws, int8_t* const* qe_out,
+                                   float* const* se_out, float* e_scale_out);
 /* the host fold of the absorbed query projection (absorbed_query_matrix, engine.cpp): wq, wk [d][d] row-major, bq [d],
  * d = 64 * heads -> A [heads * d][d] (A_h = c0 Wk_h^T Wq_h), av [heads * d] (a_h = c0 Wk_h^T bq_h),
  * c0 = 1/8 log2 e.  Needs no engine and no GPU. */

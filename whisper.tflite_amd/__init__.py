@@ -67,7 +67,7 @@ DEBUG_SYMBOLS = [
     "wt_dbg_beam_topk", "wt_dbg_beam_step", "wt_dbg_beam_reorder", "wt_dbg_beam_finalize",
     "wt_dbg_beam_full_step", "wt_dbg_beam_full_finalize",
     "wt_dbg_dec_gemm_ksplit", "wt_dbg_dec_ln_gemm_rows", "wt_dbg_dec_logits", "wt_dbg_dec_logits_i8", "wt_dbg_dec_gemm_i8", "wt_dbg_enc_quant_rows_i8", "wt_dbg_enc_gemm_i8", "wt_dbg_enc_conv_i8", "wt_dbg_select_token",
-    "wt_dbg_cross_absorbed_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_language_head_rows", "wt_dbg_self_attention_long",
+    "wt_dbg_cross_absorbed_chain", "wt_dbg_cross_absorbed_i8_chain", "wt_dbg_absorbed_query_matrix", "wt_dbg_language_head", "wt_dbg_language_head_rows", "wt_dbg_self_attention_long",
     "wt_dbg_self_attention_prefill", "wt_dbg_self_attention_long_gather",
     "wt_dbg_self_attention_long_bf16", "wt_dbg_self_attention_long_gather_bf16", "wt_dbg_self_attention_prefill_bf16",
     "wt_dbg_self_attention_long_ragged", "wt_dbg_self_attention_prefill_ragged", "wt_dbg_dec_ln_gemm_ragged", "wt_dbg_ragged_cap",
@@ -219,6 +219,9 @@ def lib() -> ctypes.CDLL:
         L.wt_dbg_cross_absorbed_bf16.argtypes = L.wt_dbg_cross_absorbed.argtypes
         L.wt_dbg_cross_absorbed_chain.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(fp),
                                                   fp, fp, fp, c_int, c_int, c_int, fp, fp]
+        L.wt_dbg_cross_absorbed_i8_chain.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(fp),
+                                                     fp, fp, fp, c_int, c_int, c_int, c_int, fp, fp, POINTER(c_void_p),
+                                                     POINTER(fp), POINTER(c_float)]
         L.wt_dbg_absorbed_query_matrix.argtypes = [c_int, c_int, fp, fp, fp, fp, fp]
         L.wt_dbg_gemm_planes_ln.argtypes = [c_void_p, c_int, c_int, fp, fp, fp, fp, fp, c_int, c_int, fp, fp, c_int, fp, fp, fp,
                                             POINTER(c_int)]
@@ -1219,6 +1222,30 @@ class Engine:
             self._h, int(bf16), batch, heads, T, chunks, nq, batch if split is None else split, len(srcs), ptrs, _fp(qp),
             _fp(wv), _fp(bv), mode, p0, n1, _fp(out), _fp(ws)))
         return out, ws
+
+    def dbg_cross_absorbed_i8_chain(self, qp, E_src, wv, bv, batch, heads, T, chunks, nq, split=None, bf16=False, only=None,
+                                    omit=0, ws_fill=-7.0, out_fill=-9.0):
+        """dbg_cross_absorbed_chain on the int8 image of E (option cross_int8): every source is quantised on the device and
+        attended to by the int8 kernel.  omit = 1 / 2 withholds an int8 image / a scale array from the launcher.  Returns
+        (out, ws, qe, se, e_scale): out and ws with their guard rows, qe[i] int8 [clips of source i][T][d] and se[i]
+        float32 [clips of source i][T] as the device made them, e_scale the power of two of the fp16 planes."""
+        d, rows = heads * 64, nq * batch
+        qp, wv, bv = _f32(qp), _f32(wv), _f32(bv)
+        srcs = [_f32(e) for e in E_src]
+        ws = np.full((rows + 1, heads, chunks, d + 4), ws_fill, np.float32)
+        out = np.full((rows + 1, d), out_fill, np.float32)
+        qe = [np.zeros(e.shape, np.int8) for e in srcs]
+        se = [np.zeros(e.shape[:2], np.float32) for e in srcs]
+        n = max(1, len(srcs))
+        ptrs = (POINTER(c_float) * n)(*[_fp(e) for e in srcs])
+        qptrs = (c_void_p * n)(*[q.ctypes.data for q in qe])
+        sptrs = (POINTER(c_float) * n)(*[_fp(s) for s in se])
+        e_scale = c_float(0)
+        p0, n1 = only if only is not None else (0, 0)
+        self._check(lib().wt_dbg_cross_absorbed_i8_chain(
+            self._h, int(bf16), batch, heads, T, chunks, nq, batch if split is None else split, len(srcs), ptrs, _fp(qp),
+            _fp(wv), _fp(bv), 1 if only is not None else 0, p0, n1, omit, _fp(out), _fp(ws), qptrs, sptrs, byref(e_scale)))
+        return out, ws, qe, se, e_scale.value
 
     def dbg_encoder_attention_planes(self, qkv, batch, T, heads, iters=0):
         qkv = _f32(qkv)

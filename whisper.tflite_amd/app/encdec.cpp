@@ -42,6 +42,8 @@ void usage(const char* argv0) {
             << "                  each, activations quantised per row at run time, int32 accumulation\n"
             << "  --int8-decoder  the int8 dynamic-range decoder blocks (option decoder_int8): the decoder layers' Linear\n"
             << "                  matrices as int8 rows with one scale each, their inputs quantised per row at run time\n"
+            << "  --int8-cross    the absorbed cross-attention on an int8 image of the encoder output (option cross_int8):\n"
+            << "                  int8 rows with one scale per key row, made once per encoded batch\n"
             << "  --int8-encoder  the int8 dynamic-range encoder blocks (option encoder_int8): the encoder layers' Linear\n"
             << "                  matrices as int8 rows with one scale each, their inputs quantised per row at run time\n"
             << "  --int8-encoder-conv  --int8-encoder plus the conv stem (option encoder_int8 = 2): both convolutions as int8\n"
@@ -102,7 +104,7 @@ int main(int argc, char* argv[]) {
       suppress_tokens;
   bool word_timestamps = false, suppress_default = false, suppress_blank = false, resample = false;
   bool long_audio = false, english = false, timestamps = false, scores = false, skip_silence = false, fallback = false, seek = false,
-       no_condition = false, bf16 = false, int8_logits = false, int8_decoder = false;
+       no_condition = false, bf16 = false, int8_logits = false, int8_decoder = false, int8_cross = false;
   long int8_encoder = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], v;
@@ -132,6 +134,10 @@ int main(int argc, char* argv[]) {
     }
     if (a == "--int8-decoder") {
       int8_decoder = true;
+      continue;
+    }
+    if (a == "--int8-cross") {
+      int8_cross = true;
       continue;
     }
     if (a == "--int8-encoder" || a == "--int8-encoder-conv") {
@@ -269,6 +275,10 @@ int main(int argc, char* argv[]) {
   }
   if (int8_decoder && wt_engine_set_option(encdec.handle(), "decoder_int8", 1) != WT_OK) {
     std::cerr << "--int8-decoder: " << wt_last_error(encdec.handle()) << "\n";
+    return 105;
+  }
+  if (int8_cross && wt_engine_set_option(encdec.handle(), "cross_int8", 1) != WT_OK) {
+    std::cerr << "--int8-cross: " << wt_last_error(encdec.handle()) << "\n";
     return 105;
   }
   if (int8_encoder && wt_engine_set_option(encdec.handle(), "encoder_int8", int8_encoder) != WT_OK) {

@@ -377,6 +377,18 @@ int wt_engine_set_option(wt_engine* h, const char* key, long value) {
     } catch (const std::exception& err) {
       return fail(h, WT_ERR_DEVICE, err.what());
     }
+  } else if (k == "cross_int8") {
+    // the absorbed cross-attention on an int8 image of the encoder output; the first switch
+    // allocates the slots' images
+    if (value != 0 && value != 1) return fail(h, WT_ERR_INVALID_ARG, "cross_int8 must be 0 or 1");
+    try {
+      e.bind_device();
+      e.set_cross_int8(value != 0);
+    } catch (const wt::Error& err) {
+      return fail(h, err.code, err.what());
+    } catch (const std::exception& err) {
+      return fail(h, WT_ERR_DEVICE, err.what());
+    }
   } else if (k == "encoder_int8") {
     // the int8 dynamic-range encoder blocks and, at 2, the conv stem as well (section 40); the
     // first switch to a level makes its int8 tables and its scratch
@@ -503,6 +515,7 @@ int wt_engine_get_option(const wt_engine* h, const char* key, long* value) {
   else if (k == "bf16") *value = e.bf16;
   else if (k == "logits_int8") *value = e.logits_int8;
   else if (k == "decoder_int8") *value = e.decoder_int8;
+  else if (k == "cross_int8") *value = e.cross_int8;
   else if (k == "encoder_int8") *value = e.encoder_int8;
   else if (k == "beam_size") *value = e.beam_size;
   else if (k == "full_beam") *value = e.full_beam;

@@ -1919,6 +1919,76 @@ int wt_dbg_cross_absorbed_chain(wt_engine* h, int bf16, int batch, int heads, in
   });
 }
 
+int wt_dbg_cross_absorbed_i8_chain(wt_engine* h, int bf16, int batch, int heads, int T, int chunks, int nq, int split, int n_src,
+                                   const float* const* E_src, const float* qp, const float* wv, const float* bv, int mode,
+                                   int p0_only, int nq_only, int omit, float* out, float* ws, int8_t* const* qe_out,
+                                   float* const* se_out, float* e_scale_out) {
+  if (!h || !wv || !bv || !out || !ws || !qp || !E_src || !qe_out || !se_out || batch < 1 || heads < 1 || heads > 8 || T < 1 ||
+      nq < 1 || chunks < 1 || chunks > 16 || size_t(nq) * batch > 128 || mode < 0 || mode > 1 || omit < 0 || omit > 2 ||
+      n_src < 1 || n_src > 4 || split < 1 || split > batch || (n_src == 1 && split != batch)) {
+    return WT_ERR_INVALID_ARG;
+  }
+  for (int i = 0; i < n_src; ++i)
+    if (!E_src[i] || !qe_out[i] || !se_out[i]) return WT_ERR_INVALID_ARG;
+  if (mode == 1 && (p0_only < 0 || nq_only < 1 || p0_only + nq_only > nq)) return WT_ERR_INVALID_ARG;
+  return guarded(h, [&] {
+    const bool bf = bf16 != 0;
+    const size_t d = size_t(heads) * 64, rows = size_t(nq) * batch, clip = size_t(T) * d;
+    const std::vector<float> wvt = wt::cross_q_layout(wv, int(d));
+    DevArr<float> dwv(wvt), dbv(d, bv), dq(rows * heads * d, qp);
+    DevArr<float> dws((rows + 1) * heads * chunks * (d + 4), ws), dout((rows + 1) * d, out);  // guard rows, as the parent tap's
+    hipStream_t st = h->impl->stream();
+    // Every source has its own planes AND its own int8 image and scales, each with room for `batch` clips; the clips a
+    // group does not have hold NaN halfs, NaN scales and 0x7F bytes.
+    const size_t plane = size_t(batch) * clip + 64;
+    const auto clips_of = [&](int i) { return std::max(0, std::min(split, batch - i * split)); };
+    float mx = 0.0f;
+    for (int i = 0; i < n_src; ++i) mx = std::max(mx, max_abs(E_src[i], size_t(clips_of(i)) * clip));
+    const float se = wt::f16_scale_for(mx);  // one scale for all sources; bounds the weight planes in the bf16 form too
+    if (e_scale_out) *e_scale_out = se;
+    std::vector<std::unique_ptr<DevArr<unsigned short>>> src;
+    std::vector<std::unique_ptr<DevArr<int8_t>>> dqe;
+    std::vector<std::unique_ptr<DevArr<float>>> dse;
+    const std::vector<int8_t> q_poison(size_t(batch) * clip, int8_t(0x7F));
+    const std::vector<float> s_poison(size_t(batch) * T, std::numeric_limits<float>::quiet_NaN());
+    for (int i = 0; i < n_src; ++i) {
+      const size_t n = size_t(clips_of(i)) * clip;
+      src.push_back(std::make_unique<DevArr<unsigned short>>(bf ? to_bf16(E_src[i], n, plane - n, 0x7FC0)
+                                                                : to_f16_planes(E_src[i], n, se, plane - n, 0x7E00)));
+      dqe.push_back(std::make_unique<DevArr<int8_t>>(q_poison));
+      dse.push_back(std::make_unique<DevArr<float>>(s_poison));
+      if (n) wt::launch_quantize_e_rows_i8(src[size_t(i)]->p, long(plane), se, bf, long(n / d), int(d), dqe[size_t(i)]->p, dse[size_t(i)]->p, st);
+    }
+    const int nq_max = wt::cross_absorbed_max_nq(heads);
+    const auto launch = [&](int p0, int n) {
+      wt::CrossAbsorbedI8Args a;
+      a.qp = dq.p; a.qe = omit == 1 ? nullptr : dqe[0]->p; a.se = dse[0]->p; a.e_scale = se; a.ws = dws.p;
+      if (n_src > 1) {
+        a.split = split;
+        a.qe2 = dqe[1]->p, a.se2 = dse[1]->p;
+        if (n_src > 2) a.qe3 = dqe[2]->p, a.se3 = dse[2]->p;
+        if (n_src > 3) a.qe4 = dqe[3]->p, a.se4 = dse[3]->p;
+      }
+      if (omit == 2) (n_src > 3 ? a.se4 : n_src > 2 ? a.se3 : n_src > 1 ? a.se2 : a.se) = nullptr;
+      a.batch = batch; a.heads = heads; a.d_model = int(d); a.T = T; a.chunks = chunks; a.nq = n; a.p0 = p0;
+      wt::launch_cross_absorbed_i8(a, st);
+    };
+    if (mode == 1) {
+      launch(p0_only, nq_only);
+    } else {
+      for (int p0 = 0; p0 < nq; p0 += nq_max) launch(p0, std::min(nq_max, nq - p0));  // Engine::decoder_pass's loop
+    }
+    wt::launch_cross_absorbed_combine(dws.p, dwv.p, dbv.p, dout.p, int(rows), heads, chunks, int(d), st);
+    h->impl->sync();
+    dout.to_host(out);
+    dws.to_host(ws);
+    for (int i = 0; i < n_src; ++i) {
+      dqe[size_t(i)]->to_host(qe_out[i], size_t(clips_of(i)) * clip);
+      dse[size_t(i)]->to_host(se_out[i], size_t(clips_of(i)) * T);
+    }
+  });
+}
+
 int wt_dbg_absorbed_query_matrix(int heads, int d, const float* wq, const float* bq, const float* wk, float* A, float* av) {
   if (heads < 1 || d != heads * 64 || !wq || !bq || !wk || !A || !av) return WT_ERR_INVALID_ARG;
   return guarded(nullptr, [&] {

@@ -1089,6 +1089,7 @@ void Engine::ensure_batch(int batch) {
   ws_.batch = batch;
   if (!enc_blocks_q8_.empty()) alloc_enc_q8_scratch();  // option encoder_int8 has been set: its scratch follows the workspace
   if (enc_conv1_q8_.w) alloc_enc_conv_scratch();  // ... and level 2's
+  if (cross_q8_wanted_) alloc_cross_q8();  // option cross_int8 has been set: the slots' int8 images follow it too
   HIPCHK(hipStreamSynchronize(stream_));
 }
 
@@ -1600,6 +1601,8 @@ void Engine::encode_enqueue(const float* d_mel, int batch) {
   }
   HIPCHK(hipMemcpyAsync(slot.h_flag, slot.d_flag, sizeof(int), hipMemcpyDeviceToHost, stream_));
   if (bf) kt_end();
+  // option cross_int8: the int8 image of the planes just written, once per encoded batch
+  if (cross_int8 && absorb) quantize_slot_e(slot, batch, stream_);
   HIPCHK(hipEventRecord(slot.enc_mid, stream_));
   // cross-attention K/V of every decoder layer, projected once per clip into the persistent cache
   // [layer][k|v][clip][head][t][64] (the reference recomputes them inside every decoder Invoke(), whisper.cpp:375) —
@@ -1679,6 +1682,62 @@ void Engine::set_decoder_int8(bool on) {
     dec_blocks_q8_ = std::move(blocks);
   }
   decoder_int8 = on ? 1 : 0;
+}
+
+// Option "cross_int8": an int8 image (and a scale per key row) of the encoder output beside every slot's planes, for the
+// workspace batch; made at the first switch and again by ensure_batch, never inside a decode.
+void Engine::alloc_cross_q8() {
+  if (ws_.batch == 0 || dims_.n_audio_state == 0) return;  // no workspace yet: ensure_batch calls again
+  const size_t rows = size_t(ws_.batch) * dims_.n_audio_ctx, d = size_t(dims_.n_audio_state);
+  for (Slot& sl : slots_) {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, rows * d + rows * sizeof(float)));
+    ws_.owned.push_back(p);
+    sl.e_q8 = static_cast<int8_t*>(p);
+    sl.e_q8_scale = reinterpret_cast<float*>(sl.e_q8 + rows * d);
+  }
+}
+
+void Engine::quantize_slot_e(Slot& slot, int clips, hipStream_t st) {
+  const long T = dims_.n_audio_ctx;
+  const int d = dims_.n_audio_state;
+  launch_quantize_e_rows_i8(slot.e_planes, long(ws_.batch) * T * d, cross_kv_.sc.a, bf16 != 0, long(clips) * T, d, slot.e_q8,
+                            slot.e_q8_scale, st);
+}
+
+// the image behind a DecPass's plane pointer: the slot whose hi plane holds it, at the same clip offset
+void Engine::cross_q8_of(const unsigned short* e, const int8_t** qe, const float** se) const {
+  const size_t d = size_t(dims_.n_audio_state), span = size_t(ws_.batch) * dims_.n_audio_ctx * d;
+  for (const Slot& sl : slots_) {
+    if (!sl.e_planes || !sl.e_q8 || e < sl.e_planes || e >= sl.e_planes + span) continue;
+    const size_t off = size_t(e - sl.e_planes);
+    *qe = sl.e_q8 + off;
+    *se = sl.e_q8_scale + off / d;
+    return;
+  }
+  throw Error(kErrInvalidArg, "cross_int8: the pass's encoder output is no slot's");
+}
+
+void Engine::set_cross_int8(bool on) {
+  require_idle();
+  if (on && !cross_q8_wanted_) {
+    if (dims_.n_text_state == 0) throw Error(kErrUnsupported, "front-end-only engine: no model weights loaded");
+    const int d = dims_.n_audio_state;
+    if (d != 128 && d != 384 && d != 512) throw Error(kErrUnsupported, "cross_int8: d_model 128, 384 or 512");
+    HIPCHK(hipSetDevice(device_));
+    alloc_cross_q8();
+    cross_q8_wanted_ = true;
+  }
+  if (on && !cross_int8) {  // encoder output already resident in the absorbed form: its image is made here
+    bool any = false;
+    for (Slot& sl : slots_) {
+      if (!sl.used || !sl.absorbed || !sl.e_q8 || sl.batch < 1) continue;
+      quantize_slot_e(sl, sl.batch, stream_);
+      any = true;
+    }
+    if (any) HIPCHK(hipStreamSynchronize(stream_));
+  }
+  cross_int8 = on ? 1 : 0;
 }
 
 // Option "encoder_int8": the int8 tables of the encoder layers' four Linear matrices, made the first time the option is
@@ -2345,7 +2404,18 @@ void Engine::decoder_pass(const DecPass& p, hipStream_t st) {
         launch_align_scores(as, st);
       }
       const int nq_max = cross_absorbed_max_nq(H), nq_all = M / p.clips;
-      for (int p0 = 0; p0 < nq_all; p0 += nq_max) {
+      for (int p0 = 0; cross_int8 && p0 < nq_all; p0 += nq_max) {  // option cross_int8: the same sweep on the int8 image
+        CrossAbsorbedI8Args ca;
+        ca.qp = dw.qp; ca.e_scale = cross_kv_.sc.a; ca.split = p.e_split;
+        cross_q8_of(p.e, &ca.qe, &ca.se);
+        if (p.e2) cross_q8_of(p.e2, &ca.qe2, &ca.se2);
+        if (p.e3) cross_q8_of(p.e3, &ca.qe3, &ca.se3);
+        if (p.e4) cross_q8_of(p.e4, &ca.qe4, &ca.se4);
+        ca.ws = dw.abs_ws; ca.batch = p.clips; ca.heads = H; ca.d_model = d; ca.T = T; ca.chunks = p.n_abs;
+        ca.nq = std::min(nq_max, nq_all - p0); ca.p0 = p0;
+        timed(tm, 4, [&] { launch_cross_absorbed_i8(ca, st); });
+      }
+      for (int p0 = 0; !cross_int8 && p0 < nq_all; p0 += nq_max) {
         CrossAbsorbedArgs ca;
         ca.qp = dw.qp; ca.e = p.e; ca.e_plane = long(ws_.batch) * T * d; ca.e_scale = cross_kv_.sc.a;
         ca.bf16 = bf; ca.split = p.e_split; ca.e2 = p.e2; ca.e3 = p.e3; ca.e4 = p.e4;

@@ -328,7 +328,16 @@ class Engine {
   // sets it allocates nothing.  Shares logits_int8's entry of every decoder graph key (int8_key).
   long decoder_int8 = 0;
   void set_decoder_int8(bool on);
-  long long int8_key() const { return logits_int8 + 2 * decoder_int8; }
+  // 1 = the absorbed cross-attention on an int8 image of the encoder output (k_cross_absorbed_i8.hip):
+  // every encode also quantises its output rows (quantize_e_rows_i8, behind ln_post on the encoder's stream) into an int8
+  // image and a scale per key row beside the slot's planes, and every decoder_pass in the absorbed form reads those instead
+  // of the planes: 1 byte per element streamed instead of 4 (2 in the bf16 storage mode).  The cached cross-K/V form,
+  // align_scores, wq_abs, the chunk combine and the out-projection keep their formats.  Set through set_cross_int8(): the
+  // first switch allocates the images of the workspace batch and quantises what the slots already hold; an engine that
+  // never sets it allocates nothing.
+  long cross_int8 = 0;
+  void set_cross_int8(bool on);
+  long long int8_key() const { return logits_int8 + 2 * decoder_int8 + 4 * cross_int8; }
   // 1 = the int8 dynamic-range encoder blocks (k_enc_gemm_i8.hip): encode_enqueue runs the four Linear
   // matrices of every encoder layer — q|k|v, attention out, fc1, fc2 — as int8 rows + one fp32 scale per output against
   // activation rows quantised per row by a launch of their own (enc_quant_rows_i8), in int32, fp32 out; fp32 storage
@@ -706,6 +715,8 @@ class Engine {
     float* cross_kv = nullptr;  // [layer][k|v][clip][head][t][64]
     unsigned short* e_planes = nullptr;  // absorbed cross-attention: planes of the encoder output [clip][T][d]
     bool absorbed = false;               // which of the two this slot's encoder pass filled
+    int8_t* e_q8 = nullptr;              // option cross_int8: int8 rows of the encoder output [clip][T][d] ...
+    float* e_q8_scale = nullptr;         // ... and one scale per key row [clip][T]
     int pair_leader = -1;  // decoded by another slot's chain (which copies this batch's ids into THIS slot's buffers)
     hipEvent_t enc_begin = nullptr, enc_mid = nullptr, enc_done = nullptr;
     hipEvent_t dec_begin = nullptr, dec_done = nullptr;
@@ -725,6 +736,12 @@ class Engine {
     int steps;
   };
   void need_cross_kv(Slot& slot);  // the cached decoder form's cross K/V cache of a slot, on first use
+  // option cross_int8: the slots' int8 images (of the workspace batch; ensure_batch calls again), the quantiser launch
+  // over a slot's first `clips` clips, and the image behind a plane pointer a DecPass carries (slot planes + clip offset)
+  bool cross_q8_wanted_ = false;
+  void alloc_cross_q8();
+  void quantize_slot_e(Slot& slot, int clips, hipStream_t st);
+  void cross_q8_of(const unsigned short* e, const int8_t** qe, const float** se) const;
   std::map<std::vector<long long>, GraphEntry> graphs_;
   // Replays the graph cached under `key` on `st`, or runs enqueue() eagerly (which also performs the kernels' one-time
   // set-up) and, with `graphs`, captures it for the next calls; returns the steps enqueue() counted.  A failed capture

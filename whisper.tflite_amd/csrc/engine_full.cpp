@@ -1187,6 +1187,7 @@ void Engine::align_words(int batch, const std::vector<Segment>& segs, const std:
   } else if (!slot.absorbed) {  // the planes the absorbed form reads, from the fp32 encoder output
     launch_f32_to_planes(ws_.enc_out, slot.e_planes, long(ws_.batch) * T * d, long(batch) * T, d, &cross_kv_.sc.a, 0, st);
   }
+  if (cross_int8 && !slot.absorbed) quantize_slot_e(slot, batch, st);  // option cross_int8: the image of those planes
   AlignSink sink;
   sink.heads_total = n_heads; sink.L_max = L_max; sink.ldw = T; sink.W = aw_.W;
   sink.layer.resize(size_t(c.n_text_layer));

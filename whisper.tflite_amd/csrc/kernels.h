@@ -542,6 +542,28 @@ int cross_absorbed_max_nq(int heads);  // positions one launch can take
 // cross out-projection.  wv_t = cross_q_layout(Wv).
 void launch_cross_absorbed_combine(const float* ws, const float* wv_t, const float* bv, float* out, int rows, int heads,
                                    int chunks, int d_model, hipStream_t s);
+// The same attention on an int8 image of E (k_cross_absorbed_i8.hip, option "cross_int8"): qe int8
+// [clips * T][d], one fp32 scale per key row in se [clips * T], both made by launch_quantize_e_rows_i8 from the planes
+// (x = (hi + lo) / e_scale) or from the bf16 plane with section 37's row quantiser (an all-zero row: zeros, scale 0).
+// The absorbed query columns are quantised over their d elements in registers, the scores are exact int32 sums scaled
+// by sq * se[key], the context runs on the int8 values with weights p * se.  Same record format in ws, same contract
+// for chunks, nq * heads <= 16, p0 and split (qe2 .. qe4 / se2 .. se4: the chain's further encoder batches); e_scale is
+// the planes' power of two, which also bounds the weights' fp16 planes (the bf16 storage mode passes it all the same).
+struct CrossAbsorbedI8Args {
+  const float* qp = nullptr;
+  const int8_t *qe = nullptr, *qe2 = nullptr, *qe3 = nullptr, *qe4 = nullptr;
+  const float *se = nullptr, *se2 = nullptr, *se3 = nullptr, *se4 = nullptr;
+  int split = 0;
+  float e_scale = 1.0f;
+  float* ws = nullptr;
+  int batch = 0, heads = 0, d_model = 0, T = 0, chunks = 1, nq = 1, p0 = 0;
+};
+// Throws what launch_cross_absorbed throws, and kErrInvalidArg for a missing int8 image or scale array, before anything
+// is launched.
+void launch_cross_absorbed_i8(const CrossAbsorbedI8Args& a, hipStream_t s);
+// rows [rows][d_model] of E (planes hi at e, lo at e + e_plane, scaled by e_scale; bf16: ONE bf16 plane) -> qe, se
+void launch_quantize_e_rows_i8(const unsigned short* e, long e_plane, float e_scale, bool bf16, long rows, int d_model,
+                               int8_t* qe, float* se, hipStream_t s);
 // Greedy selection after the logits GEMM: reduces the per-tile (value, column) records
 // best[B][n_tiles], appends to ids and applies the EOT stop (reference whisper.cpp:397-399).
 // keep_ids: the id rows are given (test tap): the token is selected, counted and checked for EOT but not written.
